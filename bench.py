@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config standard_transformer]
                     [--batch 256] [--beam 5] [--streams 4] [--tune-concurrency C] [--no-cpu-baseline]
-                    [--precision f32] [--also-precision f16x3|none]
+                    [--precision f32] [--also-precision f16x3|none] [--dump-outputs DIR]
 
 One "step" is one pass of the hot path over one batch: ``[B=256, 50, 2048]`` fp32 region features
 already resident in HBM -> encoder -> 20 beam-search steps (beam 5, V=10201) -> token ids
@@ -36,12 +36,8 @@ import statistics
 import sys
 import time
 
-# HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): the four decode streams plus
-# torch's default stream need more, or two of them share a queue and serialise (tools/queue_probe.sh: 4 streams
-# give 0.93x of 3 streams on 4 queues and 1.025x on 8).  Read when the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-import torch                                                                       # noqa: E402
+import numpy as np
+import torch
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
@@ -61,10 +57,17 @@ GFLOP_PER_CAPTION = {"standard_transformer": 4.374, "standard_transformer_using_
 GEMM_CLASSES = ["feature_proj", "encoder", "decoder_proj_ffn", "vocab"]
 
 
-def parse():
+def positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("must be at least 1, got %d" % value)
+    return value
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=positive_int, default=30, help="timed steps (batches) of the headline region")
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--config", default="standard_transformer")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step")
@@ -88,7 +91,10 @@ def parse():
                          "the library (tools/libovc_hooks.so) is loaded.  The line then says \"valid_for_credit\": false.")
     ap.add_argument("--cpu-sample", type=int, default=256, help="images per CPU-oracle repeat (BASELINE.md: B=256; ~12 s each on 16 cores)")
     ap.add_argument("--cpu-repeats", type=int, default=3)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the token ids) to DIR/<name>.npy "
+                         "as float64, so that two builds can be compared output for output (inputs are seeded)")
+    return ap.parse_args(argv)
 
 
 PROFILE_VARIANT_TAGS = ("meshed_memory_transformer", "object_relation_transformer", "attention_on_attention")
@@ -193,6 +199,27 @@ def usable_cores():
         except (OSError, ValueError, IndexError):
             continue
     return max(1, min(cores, 32))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each ``name -> tensor`` as ``directory/<name>.npy`` in float64 (token ids are exact in it).  Should the arrays
+    exceed ``limit`` bytes in all, each keeps the same fixed, seeded sample of its leading-axis rows.  Returns the paths."""
+    arrays = {name: np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float64) for name, t in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        rows = min(a.shape[0] for a in arrays.values())
+        keep = max(1, int(rows * limit // total))
+        pick = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {name: a[pick] for name, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(directory, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
 
 
 def cpu_model_string():
@@ -329,12 +356,15 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        for path in dump_outputs(args.dump_outputs, {"ids": last}):
+            print("[bench] wrote %s" % path, file=sys.stderr, flush=True)
     if distributed:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -5,7 +5,6 @@ one image per beam search, fed by one thread or by DataLoader workers, with and 
     python tools/b1_loop_probe.py [images=1024]
 """
 import os, sys, tempfile, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch

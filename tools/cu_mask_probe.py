@@ -7,7 +7,6 @@ the 256 CUs, against the plain 4-stream mode of bench.py (every stream on every 
 Masks tried: 4 streams x 64 CUs (mask bits contiguous, and strided by 4), 2 x 128, and 8 streams x 32.
 """
 import ctypes, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from openviic_amd.builders import build_model

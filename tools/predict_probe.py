@@ -13,7 +13,6 @@
 Prints one JSON line.
 """
 import json, os, sys, tempfile, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch

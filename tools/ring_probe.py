@@ -3,7 +3,6 @@
 engine reads) against the copier thread (a collated batch comes back through the loader's shared memory and is copied into pinned
 buffers).    python tools/ring_probe.py [files=4096] [repeat=4]"""
 import os, sys, tempfile, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 

@@ -90,6 +90,18 @@ int ovc_attention(const float* q, const float* k, const float* v, int b, int nq,
                   const float* geometry, const float* mem_k, const float* mem_v, int m,
                   float mem_scale_k, float mem_scale_v, float* out, ovc_stream stream);
 
+/* The two element-wise tails of the cross-level (CaMo) encoder, encoders.py:238-247.
+ * ovc_linear_leaky: y[M,N] = residual + scale * leaky_relu(x W^T + bias, slope)  (residual [M,N] row stride ldr, or NULL = 0);
+ *   x [M,K] row stride ldx, y row stride ldy.  The product is ovc_linear's (same K order, same bits); the activation,
+ *   scale and residual are applied element by element after it (one fmaf per element).
+ * ovc_layer_norm_post: y[r,:] = alpha * (LayerNorm(x[r,:] + residual[r,:]) * gamma + beta) + residual[r,:] (alpha = 0.1,
+ *   the reference's only value, is the one instance built: OVC_EINVAL otherwise) -- the
+ *   MultiHeadAttention add-norm (attentions.py:309) followed by 0.1 * ... + out_l; residual required. */
+int ovc_linear_leaky(const float* x, int ldx, int K, const float* W, const float* bias, const float* residual, int ldr,
+                     float* y, int ldy, int M, int N, float slope, float scale, ovc_stream stream);
+int ovc_layer_norm_post(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
+                        float alpha, float* y, int rows, int d, ovc_stream stream);
+
 /* mask[r] = (sum_f x[r,f] == 0)  -- models/utils.py:48-61 on feature rows. */
 int ovc_zero_row_mask(const float* x, int rows, int d, uint8_t* mask, ovc_stream stream);
 
@@ -165,7 +177,7 @@ typedef struct {
     ovc_lin alpha[OVC_MAX_LEVELS];    /* fc_alphas (meshed decoder) or NULLs               */
 } ovc_dec_layer;
 
-enum { OVC_ENC_PLAIN = 0, OVC_ENC_MULTILEVEL = 1, OVC_ENC_GEOMETRIC = 2 };
+enum { OVC_ENC_PLAIN = 0, OVC_ENC_MULTILEVEL = 1, OVC_ENC_GEOMETRIC = 2, OVC_ENC_CROSS_LEVEL = 3 };
 enum { OVC_DEC_PLAIN = 0, OVC_DEC_MESHED = 1 };
 
 typedef struct {
@@ -200,7 +212,15 @@ typedef struct {
                                          fp16's range (checked by the host); the feature projection takes mode 3, so features
                                          need not; any other activation outside +-65504 SATURATES at that value while it is
                                          cut (never inf / NaN).  K-order classes 103 / 104.  1 and 2 (the one- and two-plane
-                                         bf16 modes of ABI 5) failed the parity bar and no longer exist: OVC_EINVAL.   */
+                                         bf16 modes of ABI 5) failed the parity bar and no longer exist: OVC_EINVAL.
+                                         OVC_ENC_CROSS_LEVEL takes mode 0 only (OVC_EINVAL otherwise).                */
+    /* ---- ABI 8: appended, every field above keeps its offset ---- */
+    int32_t enc_heads, enc_d_k, enc_d_v;  /* attention geometry of the ENCODER stack (its layers and cl_att); 0 = the same as
+                                         heads / d_k / d_v, which then describe the decoder only.  Same rules as those.    */
+    ovc_mha cl_att;                   /* OVC_ENC_CROSS_LEVEL: encoder.self_attn, the ONE attention both cross-level calls
+                                         share (no AoA gates, no memory slots)                                               */
+    ovc_lin cl_mlp1;                  /* encoder.mlp1 [d, 3d]                                                                */
+    ovc_lin cl_mlp2;                  /* encoder.mlp2 [d, d]                                                                 */
 } ovc_model;
 
 /* Sizes the engine accepts (anything else: ovc_workspace_bytes returns 0, the calls OVC_EINVAL) -- the
@@ -212,7 +232,10 @@ typedef struct {
  *   d_model <= 2048 (multiple of 4; of 32 for models with AoA gates or the meshed decoder, whose products over a
  *   concatenated input read the two halves from their own buffers);  d_k == d_v in {4, 8, 16, 32, 64}, heads <= 32,
  *   heads*d_k a multiple of 64 and <= 1024;  layers <= OVC_MAX_LAYERS (8);  meshed levels <= OVC_MAX_LEVELS (4) and equal to the
- *   number of encoder layers (the multilevel encoder emits one level per layer).
+ *   number of encoder layers (the multilevel encoder emits one level per layer);  the cross-level encoder
+ *   (OVC_ENC_CROSS_LEVEL, CaMo) exactly 3 encoder layers (its tail reads three level outputs, encoders.py:214-249 unpacks
+ *   three), the plain decoder, precision 0, and the encoder stack's own heads / d_k / d_v under the rules above (the
+ *   shipped camo_transformer.yaml: 1 x 64 in the encoder, 8 x 64 in the decoder).
  * tests/test_engine_gpu.py::test_unusual_dimensions_against_oracle runs each limit against the CPU oracle,
  * tests/test_fuzz_gpu.py a seeded random sweep of the space in between.
  *
@@ -221,7 +244,9 @@ typedef struct {
 size_t ovc_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs);
 
 /* vision_embedding + encoder: features [B,N,d_feat] (zero rows = padding), boxes [B,N,4] or
- * NULL -> enc_out [B,N,d] (multilevel: [B,levels,N,d]), mask_out [B,N].
+ * NULL -> enc_out [B,N,d] (multilevel: [B,levels,N,d]), mask_out [B,N].  Padding rows of enc_out are 0 for every
+ * encoder kind but OVC_ENC_CROSS_LEVEL, whose tail turns them into 0.1 LN(...) + ... as the reference does (the decoder
+ * masks them as keys either way).
  * Replaces *.encoder_forward (models/standard_stransformer.py:33-42 etc.). */
 int ovc_encode(const ovc_model* m, const float* features, const float* boxes, int B, int N,
                void* workspace, size_t workspace_bytes, float* enc_out, uint8_t* mask_out,

@@ -1,5 +1,5 @@
 """Model architectures (reference ``models/base_transformer.py:8-53``, ``standard_stransformer.py``,
-``meshed_memory_transformer.py``, ``object_relation_transformer.py``), registered under the
+``meshed_memory_transformer.py``, ``object_relation_transformer.py``, ``camo_transformer.py``), registered under the
 reference's names so its yaml files resolve unchanged.
 
 API kept: ``forward(input_features) -> log-probs (B,T,V)``; ``encoder_forward(input_features) ->
@@ -120,3 +120,10 @@ class MeshedMemoryTransformer(BaseTransformer):
 class ObjectRelationTransformer(BaseTransformer):
     feature_field = "region_features"
     uses_boxes = True
+
+
+@META_ARCHITECTURE.register()
+class CamoTransformer(BaseTransformer):
+    """Reference ``models/camo_transformer.py``: the cross-level encoder (``CrossAttentionMultiLevelEncoder``) in front of
+    the plain decoder."""
+    feature_field = "region_features"

@@ -86,22 +86,32 @@ _VARIANTS = {
     "attention_on_attention": ("StandardTransformerUsingRegion", "Encoder", "ScaledDotProductAttention", "Decoder", True),
     "meshed_memory_transformer": ("MeshedMemoryTransformer", "MultilevelEncoder", "AugmentedMemoryScaledDotProductAttention", "MeshedDecoder", False),
     "object_relation_transformer": ("ObjectRelationTransformer", "GeometricEncoder", "AugmentedGeometryScaledDotProductAttention", "Decoder", False),
+    "camo_transformer": ("CamoTransformer", "CrossAttentionMultiLevelEncoder", "ScaledDotProductAttention", "Decoder", False),
 }
+
+# encoder head count of a variant when ``model_config`` is not given one: the shipped camo_transformer.yaml runs its encoder
+# with ONE head of 64 (ENCODER.SELF_ATTENTION.HEAD: 1) and its decoder with eight; every other variant uses ``heads`` for both
+_ENCODER_HEADS = {"camo_transformer": 1}
 
 
 def model_config(variant: str, *, d_feature: int = 2048, d_model: int = 512, heads: int = 8,
                  d_kv: int = 64, d_ff: int = 2048, layers: int = 3, memory: int = 40,
-                 device: str = "cuda", trignometric_embedding: bool = False) -> ConfigNode:
+                 device: str = "cuda", trignometric_embedding: bool = False,
+                 enc_heads: Optional[int] = None) -> ConfigNode:
     """Build the ``MODEL`` node of one of the in-scope reference configurations.
 
     Key names follow ``configs/standard_transformer.yaml:39-97``,
-    ``configs/meshed_memory_transformer.yaml:38-97`` and
-    ``configs/object_relation_transformer.yaml:39-95`` of the reference.
+    ``configs/meshed_memory_transformer.yaml:38-97``,
+    ``configs/object_relation_transformer.yaml:39-95`` and ``configs/camo_transformer.yaml:39-97`` of the reference.
+    ``heads`` is the decoder's head count; ``enc_heads`` the encoder's (default: the variant's own -- 1 for
+    ``camo_transformer``, as its yaml -- else ``heads``).
     """
     if variant not in _VARIANTS:
         raise KeyError("unknown model variant '{}' (have: {})".format(variant, ", ".join(sorted(_VARIANTS))))
     arch, encoder, enc_attention, decoder, aoa = _VARIANTS[variant]
-    enc_self = _attention(enc_attention, d_model, heads, d_kv, d_ff, aoa, False,
+    if enc_heads is None:
+        enc_heads = _ENCODER_HEADS.get(variant, heads)
+    enc_self = _attention(enc_attention, d_model, enc_heads, d_kv, d_ff, aoa, False,
                           memory if "Memory" in enc_attention else None)
     encoder_node: Dict[str, Any] = {"ARCHITECTURE": encoder, "D_MODEL": d_model, "LAYERS": layers,
                                     "SELF_ATTENTION": enc_self}

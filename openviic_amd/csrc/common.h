@@ -256,5 +256,12 @@ int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream);
 int ovc_beam_gather_all_launch(const float* all_buf, const int* order, int B, int k, int T, int V, float* all_out,
                                hipStream_t stream);
 
+// Cross-level (CaMo) encoder tail (rowops.hip): y = residual + scale * leaky_relu(x, slope) (residual may be null: 0) on
+// rows x cols with row strides, and y = alpha * LayerNorm(x + residual) + residual (no device guard: engine-internal forms).
+int ovc_leaky_residual(const float* x, int ldx, const float* residual, int ldr, float slope, float scale, float* y, int ldy,
+                       int rows, int cols, hipStream_t stream);
+int ovc_layer_norm_post_launch(const float* x, const float* residual, const float* gamma, const float* beta, float eps, float alpha,
+                               float* y, int rows, int d, hipStream_t stream);
+
 // out = (sum_l sigmoid(alpha[l]) * enc[l]) / divisor over `levels` stacked [n] blocks (rowops.hip)
 int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream);

@@ -99,6 +99,8 @@ struct Workspace {
     uint8_t* enc_mask; float* pe; float* xe[2]; float* eq; float* ek; float* ev; float* eatt; float* ey;
     float* eff; float* einfo; float* egate; float* geometry; float* enc_levels;
     float* kx; float* vx;                         // [L][levels][B][N][h*dk|h*dv]
+    float* cl_out; float* cl_cat; float* cl_q;    // cross-level encoder: layer outputs [3][B*N][d], their concatenation
+                                                  // [B*N][3d], the two cross calls' queries [2][B*N][h_enc*dk_enc]
     // decoder
     float* x; float* x1; float* x2; float* y; float* q; float* att; float* ff; float* info; float* gate;
     float* enc_att; float* alpha; float* mixed; float* ymesh;
@@ -114,6 +116,21 @@ struct Workspace {
     int32_t* alive_count;                         // [T] beams still alive after each step (ovc_beam_search_early)
     size_t bytes;
 };
+
+// Attention geometry of the encoder stack (ABI 8): its own fields, or the decoder's when they are 0.
+int enc_heads(const ovc_model* m) { return m->enc_heads ? m->enc_heads : m->heads; }
+int enc_dk(const ovc_model* m) { return m->enc_d_k ? m->enc_d_k : m->d_k; }
+int enc_dv(const ovc_model* m) { return m->enc_d_v ? m->enc_d_v : m->d_v; }
+
+// the rules the encoder stack's attention geometry obeys (the decoder's: model_ok, the same rules)
+bool heads_ok(int h, int dk, int dv) {
+    // head size: the decode attention kernels need d_k == d_v in {4, 8, 16, 32, 64} (attention.hip: the self-attention
+    // reduces a head inside a power-of-two lane group), at most 32 heads and heads * d_k <= 1024
+    if (dk != dv || dk < 4 || dk > 64 || (dk & (dk - 1))) return false;
+    if (h <= 0 || h > 32 || h * dk > 1024) return false;
+    // fused q|k|v and cross k|v GEMMs need segment widths that are multiples of the 64-wide tile
+    return (h * dk) % 64 == 0;
+}
 
 bool model_ok(const ovc_model* m) {
     if (!m || m->abi != ovc_abi_version()) return false;
@@ -132,6 +149,14 @@ bool model_ok(const ovc_model* m) {
     if ((m->heads * m->d_k) % 64 || (m->heads * m->d_v) % 64 || (m->heads * m->d_k) != (m->heads * m->d_v)) return false;
     if (m->dec_kind == OVC_DEC_MESHED && m->enc_kind != OVC_ENC_MULTILEVEL) return false;
     if (m->dec_kind != OVC_DEC_MESHED && m->n_levels != 1) return false;
+    if (m->enc_heads < 0 || m->enc_d_k < 0 || m->enc_d_v < 0 || !heads_ok(enc_heads(m), enc_dk(m), enc_dv(m))) return false;
+    if (m->enc_kind < OVC_ENC_PLAIN || m->enc_kind > OVC_ENC_CROSS_LEVEL) return false;
+    // the cross-level (CaMo) encoder: its tail reads exactly three layer outputs (encoders.py:232 unpacks three), feeds the plain
+    // decoder, and runs in fp32 only (its tail products have no split-precision instances)
+    if (m->enc_kind == OVC_ENC_CROSS_LEVEL &&
+        (m->n_enc != 3 || m->dec_kind != OVC_DEC_PLAIN || m->precision != 0 || !m->cl_mlp1.w || !m->cl_mlp2.w ||
+         !m->cl_att.q.w || !m->cl_att.k.w || !m->cl_att.v.w || !m->cl_att.o.w || m->cl_att.aoa_i.w || m->cl_att.m_k))
+        return false;
     // the multilevel encoder writes one level per layer (engine.hip run_encoder_layers): the meshed decoder must
     // consume exactly that many
     if (m->enc_kind == OVC_ENC_MULTILEVEL && m->n_levels != m->n_enc) return false;
@@ -150,17 +175,22 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     Bump a{reinterpret_cast<char*>(base), 0};
     const size_t BN = (size_t)B * N, R = (size_t)B * k, d = m->d_model, T = m->max_len;
     const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels, L = m->n_dec;
+    const size_t ehk = (size_t)enc_heads(m) * enc_dk(m), ehv = (size_t)enc_heads(m) * enc_dv(m);
+    const bool cross_level = m->enc_kind == OVC_ENC_CROSS_LEVEL;
     w.enc_mask = a.take<uint8_t>(BN);
     w.pe = a.take<float>((size_t)N * d);
     w.xe[0] = a.take<float>(BN * d);
     w.xe[1] = a.take<float>(BN * d);
-    w.eq = a.take<float>(BN * hk); w.ek = a.take<float>(BN * hk); w.ev = a.take<float>(BN * hv);
-    w.eatt = a.take<float>(BN * hv);
+    w.eq = a.take<float>(BN * ehk); w.ek = a.take<float>(BN * ehk); w.ev = a.take<float>(BN * ehv);
+    w.eatt = a.take<float>(BN * ehv);
     w.ey = a.take<float>(BN * d);
     w.eff = a.take<float>(BN * m->d_ff);
     w.einfo = a.take<float>(BN * d); w.egate = a.take<float>(BN * d);
-    w.geometry = a.take<float>(m->enc_kind == OVC_ENC_GEOMETRIC ? (size_t)B * m->heads * N * N : 0);
+    w.geometry = a.take<float>(m->enc_kind == OVC_ENC_GEOMETRIC ? (size_t)B * enc_heads(m) * N * N : 0);
     w.enc_levels = a.take<float>(lv * BN * d);
+    w.cl_out = a.take<float>(cross_level ? 3 * BN * d : 0);
+    w.cl_cat = a.take<float>(cross_level ? 3 * BN * d : 0);
+    w.cl_q = a.take<float>(cross_level ? 2 * BN * ehk : 0);
     w.kx = a.take<float>(L * lv * BN * hk);
     w.vx = a.take<float>(L * lv * BN * hv);
     w.x = a.take<float>(R * d); w.x1 = a.take<float>(R * d); w.x2 = a.take<float>(R * d); w.y = a.take<float>(R * d);
@@ -236,6 +266,16 @@ __global__ void interleave_levels_kernel(const float* __restrict__ levels, float
         const size_t e = i % nd4, bl = i / nd4;
         const int l = (int)(bl % lv), b = (int)(bl / lv);
         reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(levels)[((size_t)l * B + b) * nd4 + e];
+    }
+}
+
+// out[r, lvl, :] = levels[lvl][r][:]  (rows r of `rows`, nd4 = d / 4 float4 per row)
+__global__ void concat_levels_kernel(const float* __restrict__ levels, float* __restrict__ out, int lv, size_t rows, size_t nd4) {
+    const size_t total = rows * lv * nd4;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t e = i % nd4, rl = i / nd4;
+        const size_t l = rl % lv, r = rl / lv;
+        reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(levels)[(l * rows + r) * nd4 + e];
     }
 }
 
@@ -388,13 +428,58 @@ int run_encoder_inputs(Engine& e, Workspace& w, const float* features, const flo
         TRY(e.gemm(a));
     }
     if (m->enc_kind == OVC_ENC_GEOMETRIC)
-        RUN(ovc_box_relation_weights(boxes, B, N, m->fc_g_w, m->fc_g_b, m->heads, m->d_g, m->trig, w.geometry, s));
+        RUN(ovc_box_relation_weights(boxes, B, N, m->fc_g_w, m->fc_g_b, enc_heads(m), m->d_g, m->trig, w.geometry, s));
+    return OVC_OK;
+}
+
+// The cross-level (CaMo) encoder's tail, encoders.py:234-247, on the three layer outputs o1..o3 in w.cl_out (their padding rows
+// are 0, as every encoder layer leaves them):
+//   o2' = 0.1 MHA(o2; o1, o1) + o2,   o3' = 0.1 MHA(o3; o2', o2') + o3      one shared MHA, MHA(q; k, v) = LN(q + fc_o(att))
+//   out = o3' + 0.2 leaky_relu(mlp2(leaky_relu(mlp1([o1 | o2 | o3]))))       the ORIGINAL o2, o3 in the concatenation
+// Nine launches on the caller's stream, in this order (nothing forks: the sequence is captured with the rest of the search).
+// Padding rows are NOT cleared afterwards -- the reference leaves them non-zero and the decoder masks them as keys.
+int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
+    const ovc_model* m = e.m;
+    const int BN = B * N, d = m->d_model, eh = enc_heads(m), edk = enc_dk(m), edv = enc_dv(m), hk = eh * edk, hv = eh * edv;
+    const size_t nd = (size_t)BN * d;
+    hipStream_t s = e.stream;
+    const ovc_mha& at = m->cl_att;
+    float* o1 = w.cl_out; float* o2 = w.cl_out + nd; float* o3 = w.cl_out + 2 * nd;
+    float* o2p = w.xe[0]; float* o3p = w.xe[1];
+    constexpr float kCrossScale = 0.1f, kMlpScale = 0.2f, kSlope = 0.01f;     // encoders.py:234-247, F.leaky_relu's default slope
+    e.gemm_class = 1;
+    e.kchains = 1;
+    // both calls' queries come from the original o2 / o3, which lie back to back: ONE product of 2 * B * N rows
+    TRY(e.linear(o2, d, at.q, nullptr, w.cl_q, 2 * BN, hk, 0));
+    const float* keys[2] = {o1, o2p};
+    const float* queries[2] = {o2, o3};
+    float* outs[2] = {o2p, o3p};
+    for (int c = 0; c < 2; ++c) {
+        GemmArgs a{};
+        a.A1 = keys[c]; a.lda1 = d; a.K1 = d; a.M = BN; a.seg_n = hk; a.nseg = 2; a.ldc = hk;
+        a.seg[0] = e.seg(at.k, w.ek);
+        a.seg[1] = e.seg(at.v, w.ev);
+        TRY(e.gemm(a));
+        RUN(ovc_attention(w.cl_q + (size_t)c * BN * hk, w.ek, w.ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0, nullptr, nullptr,
+                          nullptr, 0, 1.f, 1.f, w.eatt, s));
+        TRY(e.linear(w.eatt, hv, at.o, nullptr, w.ey, BN, d, 0));
+        RUN(ovc_layer_norm_post_launch(w.ey, queries[c], at.ln.g, at.ln.b, m->ln_eps, kCrossScale, outs[c], BN, d, s));
+    }
+    // [o1 | o2 | o3] row by row: mlp1 then reads ONE operand of K = 3d (the GEMM takes at most two input blocks)
+    if (!e.dry) {
+        hipLaunchKernelGGL(concat_levels_kernel, dim3(1024), dim3(256), 0, s, w.cl_out, w.cl_cat, 3, (size_t)BN, (size_t)d / 4);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
+    TRY(e.linear(w.cl_cat, 3 * d, m->cl_mlp1, nullptr, w.einfo, BN, d, 0));
+    RUN(ovc_leaky_residual(w.einfo, d, nullptr, 0, kSlope, 1.f, w.einfo, d, BN, d, s));
+    TRY(e.linear(w.einfo, d, m->cl_mlp2, nullptr, w.ey, BN, d, 0));
+    RUN(ovc_leaky_residual(w.ey, d, o3p, d, kSlope, kMlpScale, w.enc_levels, d, BN, d, s));
     return OVC_OK;
 }
 
 int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
     const ovc_model* m = e.m;
-    const int BN = B * N, d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v;
+    const int BN = B * N, d = m->d_model, eh = enc_heads(m), edk = enc_dk(m), edv = enc_dv(m), hk = eh * edk, hv = eh * edv;
     hipStream_t s = e.stream;
     e.gemm_class = 1;
     e.kchains = 1;
@@ -412,18 +497,20 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
         a.seg[2] = e.seg(at.v, w.ev);
         TRY(e.gemm(a));
         const int mem = at.m_k ? m->memory : 0;
-        RUN(ovc_attention(w.eq, w.ek, w.ev, B, N, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0,
+        RUN(ovc_attention(w.eq, w.ek, w.ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
                           m->enc_kind == OVC_ENC_GEOMETRIC ? w.geometry : nullptr, at.m_k, at.m_v, mem,
-                          sqrtf((float)m->d_k), sqrtf((float)(mem > 0 ? mem : 1)), w.eatt, s));
+                          sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), w.eatt, s));
         TRY(e.linear(w.eatt, hv, at.o, x, w.ey, BN, d, 0));
         RUN(ovc_layer_norm(w.ey, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, x1, BN, d, s));
         TRY(e.aoa(at, x, x1, w.einfo, w.egate, BN));
-        // layer output: straight into the level slot (multilevel) or the ping-pong buffer
+        // layer output: straight into the level slot (multilevel, cross-level) or the ping-pong buffer
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
-                                                       : (l == m->n_enc - 1 ? w.enc_levels : x);
+                   : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
+                                                        : (l == m->n_enc - 1 ? w.enc_levels : x);
         TRY(e.ffn(m->enc[l].ffn, x1, w.eff, w.ey, nullptr, out, w.enc_mask, BN));
         x = out;
     }
+    if (m->enc_kind == OVC_ENC_CROSS_LEVEL) TRY(run_cross_level_tail(e, w, B, N));
     return OVC_OK;
 }
 
@@ -628,7 +715,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
 
 }  // namespace
 
-extern "C" int ovc_abi_version(void) { return 7; }     // 7: ovc_beam_search_early, ovc_debug_vocab_select(kchains), OVC_MAX_REGIONS
+extern "C" int ovc_abi_version(void) { return 8; }     // 8: OVC_ENC_CROSS_LEVEL, encoder-stack heads / d_k / d_v (appended fields)
 
 extern "C" const char* ovc_build_info(void) {
 #ifdef OVC_MEASUREMENT_HOOKS

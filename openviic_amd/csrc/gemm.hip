@@ -1149,3 +1149,15 @@ extern "C" int ovc_linear(const float* x, int ldx, const float* x2, int ldx2, in
     a.seg[0] = GemmSegment{W, bias, y, nullptr};
     return ovc_gemm_launch(a, ovc_hip_stream(stream), GemmLaunchOpts{});
 }
+
+extern "C" int ovc_linear_leaky(const float* x, int ldx, int K, const float* W, const float* bias, const float* residual, int ldr,
+                                float* y, int ldy, int M, int N, float slope, float scale, ovc_stream stream) {
+    if (!x || !W || !y || M <= 0 || N <= 0 || K <= 0 || ldy < N || (residual && ldr < N)) return OVC_EINVAL;
+    GemmArgs a{};
+    a.A1 = x; a.lda1 = ldx; a.K1 = K; a.M = M; a.seg_n = N; a.nseg = 1; a.ldc = ldy;
+    a.kchains = 1;                                       // operator level: one chain, as ovc_linear
+    a.seg[0] = GemmSegment{W, bias, y, nullptr};
+    const hipStream_t s = ovc_hip_stream(stream);
+    if (const int rc = ovc_gemm_launch(a, s, GemmLaunchOpts{})) return rc;
+    return ovc_leaky_residual(y, ldy, residual, ldr, slope, scale, y, ldy, M, N, s);
+}

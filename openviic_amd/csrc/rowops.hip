@@ -1,5 +1,7 @@
 // Row-wise and element-wise kernels of the captioning path (all HBM-bound; one 64-lane wave per
 // row, 16-byte accesses, wave-shuffle reductions).  Reference call sites: include/ovc.h.
+#include <algorithm>
+
 #include "common.h"
 
 namespace {
@@ -15,10 +17,14 @@ namespace {
 // Everything a row needs (slices, bias, residual) is loaded before the first use: the operand set is a
 // template parameter, because hipcc turns every run-time "load or skip" into a branch with a full
 // s_waitcnt, which serialised the 3..6 loads of a row into as many memory round trips.
+//
+// kPostTenths > 0 (the cross-level encoder's tail, encoders.py:234-241): the row written is alpha * LN(...) + residual with
+// alpha = kPostTenths / 10 -- the residual that went INTO the norm is added again after the scale.  A compile-time constant
+// rather than a kernel argument, so the other instances keep their arguments and their code.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxVec = 8;   // float4 per lane -> d <= 2048
 
-template <int kVecs, int kParts, bool kBias, bool kRes>
+template <int kVecs, int kParts, bool kBias, bool kRes, int kPostTenths = 0>
 __global__ __launch_bounds__(256) void layer_norm_rows(const float* __restrict__ x, long part_stride,
                                                        const float* __restrict__ bias, const float* __restrict__ residual,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -94,19 +100,20 @@ __global__ __launch_bounds__(256) void layer_norm_rows(const float* __restrict__
         if (c < nvec) {
             f32x4 o = (v[i] - mean) * rstd * gv[i] + bev[i];
             if (ar) o += ar[c];
+            if constexpr (kPostTenths > 0) o = ((float)kPostTenths / 10.f) * o + rv[i];
             if (cleared) o = f32x4{0.f, 0.f, 0.f, 0.f};
             reinterpret_cast<f32x4*>(yrow)[c] = o;
         }
     }
 }
 
-template <int kParts, bool kBias, bool kRes>
+template <int kParts, bool kBias, bool kRes, int kPostTenths = 0>
 int launch_layer_norm(const float* x, long part_stride, const float* bias, const float* residual, const float* gamma,
                       const float* beta, const float* add, int add_rows, const uint8_t* zero_rows, float eps, float* y,
                       int rows, int d, hipStream_t stream) {
     const int vecs = ((d >> 2) + 63) / 64;
     const dim3 grid((rows + 3) / 4), block(256);
-#define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows<V, kParts, kBias, kRes>), grid, block, 0, stream, x, part_stride, bias, \
+#define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows<V, kParts, kBias, kRes, kPostTenths>), grid, block, 0, stream, x, part_stride, bias, \
                                      residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d)
     if (vecs <= 1) OVC_LN(1); else if (vecs <= 2) OVC_LN(2); else if (vecs <= 4) OVC_LN(4); else OVC_LN(8);
 #undef OVC_LN
@@ -275,7 +282,45 @@ __global__ void box_relation_kernel(const float* __restrict__ boxes, int n, cons
     }
 }
 
+// y = residual + scale * leaky_relu(x, slope) (residual may be null: 0), over `cols`-wide rows with their own strides -- the
+// element-wise tail of the cross-level encoder's mlp1 / mlp2 products.  One fmaf per element.
+__global__ __launch_bounds__(256) void leaky_residual_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ residual,
+                                                             int ldr, float slope, float scale, float* __restrict__ y, int ldy,
+                                                             int rows, int cols) {
+    const long total = (long)rows * cols;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / cols), c = (int)(i - (long)r * cols);
+        const float v = x[(size_t)r * ldx + c];
+        const float a = v >= 0.f ? v : v * slope;
+        y[(size_t)r * ldy + c] = residual ? fmaf(scale, a, residual[(size_t)r * ldr + c]) : scale * a;
+    }
+}
+
 }  // namespace
+
+int ovc_leaky_residual(const float* x, int ldx, const float* residual, int ldr, float slope, float scale, float* y, int ldy,
+                       int rows, int cols, hipStream_t stream) {
+    if (!x || !y || rows <= 0 || cols <= 0 || ldx < cols || ldy < cols || (residual && ldr < cols)) return OVC_EINVAL;
+    const long total = (long)rows * cols;
+    const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(leaky_residual_kernel, dim3(blocks), dim3(256), 0, stream, x, ldx, residual, ldr, slope, scale, y, ldy, rows, cols);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_layer_norm_post_launch(const float* x, const float* residual, const float* gamma, const float* beta, float eps, float alpha,
+                               float* y, int rows, int d, hipStream_t stream) {
+    if (!x || !residual || !gamma || !beta || !y || rows <= 0 || d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
+    if (!ovc_aligned16(x) || !ovc_aligned16(y) || !ovc_aligned16(gamma) || !ovc_aligned16(beta) || !ovc_aligned16(residual)) return OVC_EINVAL;
+    if (alpha != 0.1f) return OVC_EINVAL;     // the one instance built: the reference's 0.1 (encoders.py:234-237)
+    return launch_layer_norm<1, false, true, 1>(x, 0L, nullptr, residual, gamma, beta, nullptr, 0, nullptr, eps, y, rows, d, stream);
+}
+
+extern "C" int ovc_layer_norm_post(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
+                                   float alpha, float* y, int rows, int d, ovc_stream stream) {
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    return ovc_layer_norm_post_launch(x, residual, gamma, beta, eps, alpha, y, rows, d, ovc_hip_stream(stream));
+}
 
 extern "C" int ovc_layer_norm(const float* x, const float* residual, const float* gamma, const float* beta,
                               const float* add, int add_rows, const uint8_t* zero_rows, float eps,

@@ -154,10 +154,30 @@ class CaptionEngine:
         d.abi = native.ABI_VERSION
         d.enc_kind = (native.ENC_MULTILEVEL if isinstance(enc, encoders.MultilevelEncoder)
                       else native.ENC_GEOMETRIC if isinstance(enc, encoders.GeometricEncoder)
+                      else native.ENC_CROSS_LEVEL if isinstance(enc, encoders.CrossAttentionMultiLevelEncoder)
                       else native.ENC_PLAIN)
         d.dec_kind = native.DEC_MESHED if isinstance(dec, decoders.MeshedDecoder) else native.DEC_PLAIN
         d.d_feat = model.vision_embedding.proj.in_features
-        d.d_model, d.heads, d.d_k, d.d_v = first.d_model, first.h, first.d_k, first.d_v
+        # attention geometry per stack (ABI 8): the encoder's from its layers, the decoder's from its own -- the shipped
+        # camo_transformer.yaml has 1 x 64 in the encoder and 8 x 64 in the decoder.  Inside a stack every attention must
+        # agree, and both stacks must share d_model and d_ff (the descriptor holds one of each): anything else is refused
+        # here rather than described wrongly.
+        def geometry(att):
+            return (att.h, att.d_k, att.d_v)
+        enc_atts = [layer.mhatt.attention for layer in enc.layers]
+        if d.enc_kind == native.ENC_CROSS_LEVEL:
+            enc_atts.append(enc.self_attn.attention)
+        dec_atts = [a.attention for layer in dec.layers for a in (layer.self_attn, layer.enc_attn)]
+        ffns = [layer.pwff for layer in list(enc.layers) + list(dec.layers)]
+        for stack, atts in (("encoder", enc_atts), ("decoder", dec_atts)):
+            if len({geometry(a) for a in atts}) != 1:
+                raise native.OvcError("the fused engine needs one attention geometry per stack; the {} has (heads, d_k, d_v) "
+                                      "{}".format(stack, sorted({geometry(a) for a in atts})))
+        if len({a.d_model for a in enc_atts + dec_atts}) != 1 or len({f.fc1.out_features for f in ffns}) != 1:
+            raise native.OvcError("the fused engine needs one d_model and one d_ff across encoder and decoder")
+        d.d_model = first.d_model
+        d.heads, d.d_k, d.d_v = geometry(dec_atts[0])
+        d.enc_heads, d.enc_d_k, d.enc_d_v = geometry(first)
         d.d_ff = enc.layers[0].pwff.fc1.out_features
         d.n_enc, d.n_dec = len(enc.layers), len(dec.layers)
         d.n_levels = dec.layers[0].nlayers if d.dec_kind == native.DEC_MESHED else 1
@@ -180,6 +200,17 @@ class CaptionEngine:
             self._fc_g = (w, b)
             self._keep += [w, b]
             d.fc_g_w, d.fc_g_b = _p(w), _p(b)
+        if d.enc_kind == native.ENC_CROSS_LEVEL:
+            if len(enc.layers) != 3:
+                raise native.OvcError("the cross-level encoder needs exactly 3 layers (has {})".format(len(enc.layers)))
+            if mode != 0:
+                # its tail products have no split-precision instances: refused up front, not run in another precision
+                raise native.OvcError("precision={!r}: the cross-level (CaMo) encoder runs in 'f32' only".format(self.precision))
+            if enc.self_attn.use_aoa or hasattr(enc.self_attn.attention, "m_k"):
+                raise native.OvcError("the cross-level encoder's self_attn must be plain scaled dot-product attention")
+            _mha(d.cl_att, enc.self_attn, self._keep)
+            _lin(d.cl_mlp1, enc.mlp1)
+            _lin(d.cl_mlp2, enc.mlp2)
         for i, layer in enumerate(enc.layers):
             _mha(d.enc[i].att, layer.mhatt, self._keep, pl, mode)
             _ffn(d.enc[i].ffn, layer.pwff, pl, mode)

@@ -2,7 +2,8 @@
 
 ``Encoder`` returns the last layer, ``MultilevelEncoder`` all layers stacked on dim 1 (Meshed-
 Memory), ``GeometricEncoder`` adds the box-relation bias (Object-Relation Transformer),
-``DualCollaborativeLevelEncoder`` runs region and grid streams with locally-constrained cross-attention (DLCT).
+``DualCollaborativeLevelEncoder`` runs region and grid streams with locally-constrained cross-attention (DLCT),
+``CrossAttentionMultiLevelEncoder`` mixes its three layer outputs through cross-level attention and an MLP (CaMo).
 """
 import copy
 
@@ -10,6 +11,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from .. import native
 from ..builders.encoder_builder import META_ENCODER
 from .attentions import MultiHeadAttention
 from .embeddings import SinusoidPositionalEmbedding
@@ -164,3 +166,43 @@ class DualCollaborativeLevelEncoder(nn.Module):
                          padding_mask=grid2all_mask, attention_mask=grid2all_mask,
                          query_padding_mask=grid_padding_mask)
         return torch.cat([region, grid], dim=1), torch.cat([region_padding_mask, grid_padding_mask], dim=-1)
+
+
+@META_ENCODER.register()
+class CrossAttentionMultiLevelEncoder(_EncoderBase):
+    """CaMo encoder (reference ``encoders.py:214-249``): three encoder layers, then
+
+    ``o2' = 0.1 MHA(o2; o1) + o2``, ``o3' = 0.1 MHA(o3; o2') + o3`` with ONE shared ``self_attn`` (``MHA(q; k) = LN(q +
+    fc_o(att))``, keys masked), and ``out = o3' + 0.2 leaky_relu(mlp2(leaky_relu(mlp1([o1 | o2 | o3]))))`` over the
+    ORIGINAL ``o2``, ``o3``.  The padding rows of the output are not zero (the reference's are not either; the decoder masks
+    them).  Exactly three layers: the reference unpacks three outputs and fails on any other count.
+    """
+
+    def __init__(self, config):
+        if config.LAYERS != 3:
+            raise ValueError("CrossAttentionMultiLevelEncoder needs exactly 3 layers (LAYERS = {}): its tail combines the "
+                             "outputs of three encoder layers (reference encoders.py:232)".format(config.LAYERS))
+        super().__init__(config)
+        self.self_attn = MultiHeadAttention(config.SELF_ATTENTION)
+        self.mlp1 = nn.Linear(3 * config.D_MODEL, config.D_MODEL)
+        self.mlp2 = nn.Linear(config.D_MODEL, config.D_MODEL)
+
+    def _cross(self, queries, keys, padding_mask):
+        """``0.1 * self_attn(queries, keys, keys) + queries``."""
+        att = self.self_attn.attention(queries, keys, keys, attention_mask=padding_mask)
+        ln = self.self_attn.layer_norm
+        return ops.layer_norm_post(att, queries, ln.weight, ln.bias, alpha=0.1, eps=ln.eps)
+
+    def forward(self, features: torch.Tensor, padding_mask: torch.Tensor):
+        if self.self_attn.use_aoa:
+            raise native.OvcError("CrossAttentionMultiLevelEncoder: the cross-level attention has no AoA form here")
+        out = self._prologue(features)
+        outs = []
+        for layer in self.layers:
+            out = layer(queries=out, keys=out, values=out, padding_mask=padding_mask, attention_mask=padding_mask)
+            outs.append(out)
+        o1, o2, o3 = outs
+        o2_new = self._cross(o2, o1, padding_mask)
+        o3_new = self._cross(o3, o2_new, padding_mask)
+        h = ops.linear_leaky(torch.cat(outs, dim=-1), self.mlp1.weight, self.mlp1.bias)
+        return ops.linear_leaky(h, self.mlp2.weight, self.mlp2.bias, residual=o3_new, scale=0.2)

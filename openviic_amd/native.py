@@ -13,7 +13,7 @@ OVC_MAX_LEVELS = 4
 OVC_MAX_BEAM = 8
 OVC_MAX_REGIONS = 1024
 OVC_PROFILE_CLASSES = 4
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _ERRORS = {-1: "OVC_EINVAL (bad argument / unsupported shape)", -2: "OVC_EWORKSPACE (workspace too small)",
            -3: "OVC_ELAUNCH (HIP launch failed)",
@@ -59,10 +59,13 @@ class Model(ctypes.Structure):
         ("proj", Lin), ("enc_ln", Norm), ("fc_g_w", c_void_p), ("fc_g_b", c_void_p),
         ("enc", EncLayer * OVC_MAX_LAYERS), ("dec", DecLayer * OVC_MAX_LAYERS),
         ("word_emb", c_void_p), ("pos_emb", c_void_p), ("fc", c_void_p), ("fc_planes", c_void_p), ("tune_objective", c_int32), ("precision", c_int32),
+        # ABI 8: the encoder stack's own attention geometry (0 = the decoder's) and the cross-level encoder's tail
+        ("enc_heads", c_int32), ("enc_d_k", c_int32), ("enc_d_v", c_int32),
+        ("cl_att", Mha), ("cl_mlp1", Lin), ("cl_mlp2", Lin),
     ]
 
 
-ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC = 0, 1, 2
+ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC, ENC_CROSS_LEVEL = 0, 1, 2, 3
 DEC_PLAIN, DEC_MESHED = 0, 1
 
 # OVC_LIBRARY: load another build of the same ABI (A/B timing of kernel changes on one box)
@@ -81,6 +84,9 @@ SIGNATURES = {
     "ovc_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                               c_void_p, c_void_p]),
+    "ovc_linear_leaky": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                 c_float, c_float, c_void_p]),
+    "ovc_layer_norm_post": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int, c_int, c_void_p]),
     "ovc_zero_row_mask": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ovc_region_position_encoding": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_void_p, c_void_p]),
     "ovc_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),

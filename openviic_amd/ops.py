@@ -73,6 +73,46 @@ def linear(x, weight, bias=None, *, relu=False, residual=None, x2=None):
     return y.view(*lead, n)
 
 
+def linear_leaky(x, weight, bias=None, *, residual=None, scale=1.0, slope=0.01):
+    """``residual + scale * leaky_relu(x @ weight.T + bias, slope)`` over the last dimension (``residual`` None = 0): the
+    cross-level encoder's ``mlp1`` / ``mlp2`` (``ovc_linear_leaky``; the product is :func:`linear`'s)."""
+    lib = native.load()
+    x = _dev(x, "x"); weight = _dev(weight.detach(), "weight")
+    lead, k = x.shape[:-1], x.shape[-1]
+    x2d = x.reshape(-1, k)
+    m, n = x2d.shape[0], weight.shape[0]
+    if weight.shape[1] != k:
+        raise native.OvcError("weight is {} but inputs have {} features".format(tuple(weight.shape), k))
+    bias = None if bias is None else _dev(bias.detach(), "bias")
+    if bias is not None:
+        _expect(bias, (n,), "bias")
+    res2d = None
+    if residual is not None:
+        res2d = _dev(residual, "residual").reshape(-1, n)
+        _expect(res2d, (m, n), "residual (flattened)")
+    y = torch.empty(m, n, dtype=torch.float32, device=x.device)
+    check(lib.ovc_linear_leaky(_ptr(x2d), k, k, _ptr(weight), _ptr(bias), _ptr(res2d), n, _ptr(y), n, m, n, float(slope),
+                               float(scale), native.stream_handle()), "ovc_linear_leaky")
+    return y.view(*lead, n)
+
+
+def layer_norm_post(x, residual, gamma, beta, *, alpha, eps=1e-5):
+    """``alpha * (LayerNorm(x + residual) * gamma + beta) + residual`` (``ovc_layer_norm_post``): a multi-head attention's
+    add-norm scaled and added to its queries again, as the cross-level encoder does (reference ``encoders.py:234-241``).
+    ``alpha`` = 0.1, the reference's value, is the one instance the library builds."""
+    lib = native.load()
+    x, residual = _dev(x, "x"), _dev(residual, "residual")
+    _expect(residual, x.shape, "residual")
+    d = x.shape[-1]
+    gamma, beta = _dev(gamma.detach(), "gamma"), _dev(beta.detach(), "beta")
+    _expect(gamma, (d,), "gamma")
+    _expect(beta, (d,), "beta")
+    y = torch.empty_like(x)
+    check(lib.ovc_layer_norm_post(_ptr(x), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps), float(alpha), _ptr(y),
+                                  x.numel() // d, d, native.stream_handle()), "ovc_layer_norm_post")
+    return y
+
+
 def layer_norm(x, gamma, beta, *, residual=None, add=None, zero_rows=None, eps=1e-5):
     """``LayerNorm(x + residual) * gamma + beta + add`` with optional row zeroing.
 

@@ -43,6 +43,7 @@ typedef void* ovc_stream;              /* a hipStream_t (NULL = the null stream)
 #define OVC_MAX_BEAM      8
 #define OVC_MAX_SEGMENTS  8
 #define OVC_MAX_REGIONS   1024         /* regions (or grid cells) per image the engine accepts */
+#define OVC_MAX_LEN       256          /* ovc_model::max_len: decode steps (caption positions) the engine accepts */
 
 /* library / build identification ------------------------------------------------------ */
 int         ovc_abi_version(void);             /* bumps when a struct layout changes     */
@@ -227,8 +228,10 @@ typedef struct {
  * reference itself has no such limits, these are the template instances built so far:
  *   regions N <= OVC_MAX_REGIONS (1024), memory slots on top of them without a limit of their own (N <= 128 with
  *   N + memory <= 192 runs on the register-resident attention instances -- the shipped meshed_memory_transformer.yaml,
- *   MEMORY: 40, for every N <= 128 -- anything larger on the key-tiled ones);  beam k <= OVC_MAX_BEAM (8);  max_len <= 64;  any vocabulary (above 16384 words the
- *   selection streams each row k + 2 times instead of holding it in registers);
+ *   MEMORY: 40, for every N <= 128 -- anything larger on the key-tiled ones);  beam k <= OVC_MAX_BEAM (8);  1 <= max_len <=
+ *   OVC_MAX_LEN (256; steps t >= 64 run the decode self-attention over chunks of 16 positions and merge them, earlier steps
+ *   keep the kernels of max_len <= 64);  any vocabulary (above 16384 words the selection streams each row k + 2 times
+ *   instead of holding it in registers);
  *   d_model <= 2048 (multiple of 4; of 32 for models with AoA gates or the meshed decoder, whose products over a
  *   concatenated input read the two halves from their own buffers);  d_k == d_v in {4, 8, 16, 32, 64}, heads <= 32,
  *   heads*d_k a multiple of 64 and <= 1024;  layers <= OVC_MAX_LAYERS (8);  meshed levels <= OVC_MAX_LEVELS (4) and equal to the
@@ -237,7 +240,7 @@ typedef struct {
  *   three), the plain decoder, precision 0, and the encoder stack's own heads / d_k / d_v under the rules above (the
  *   shipped camo_transformer.yaml: 1 x 64 in the encoder, 8 x 64 in the decoder).
  * tests/test_engine_gpu.py::test_unusual_dimensions_against_oracle runs each limit against the CPU oracle,
- * tests/test_fuzz_gpu.py a seeded random sweep of the space in between.
+ * tests/test_long_captions_gpu.py max_len up to OVC_MAX_LEN, tests/test_fuzz_gpu.py a seeded random sweep of the space in between.
  *
  * Bytes of scratch the engine needs for batch B, N regions, beam k (return_probs adds the
  * [B,k,T,V] buffer).  0 on invalid arguments. */
@@ -352,7 +355,8 @@ int ovc_gemm_tuned_set(int M, int seg_n, int nseg, int K, int kchains, int kspli
 int ovc_engine_gemm_shapes(const ovc_model* m, int B, int N, int k, int32_t* shapes, int capacity);
 
 /* hipGraph cache housekeeping: entries are evicted least-recently-used beyond OVC_GRAPH_CACHE_MAX (default 24);
- * a host that frees or replaces a workspace must drop that workspace's graphs first. */
+ * a host that frees or replaces a workspace must drop that workspace's graphs first.  An ovc_beam_search_early entry holds
+ * max_len + 1 graphs (up to 257 at max_len = OVC_MAX_LEN) but counts as ONE entry against OVC_GRAPH_CACHE_MAX. */
 int ovc_graph_cache_drop_workspace(const void* workspace);   /* returns the number of entries dropped */
 int ovc_graph_cache_size(void);
 

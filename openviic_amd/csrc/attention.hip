@@ -609,11 +609,14 @@ constexpr int kSelfMaxHeads = 32;
 
 // CH = float4-per-lane instructions per key row (h*dk / 256 rounded up): compile-time so that the loads of
 // several keys can be issued back to back with clamped (always valid) addresses and no branches.
-template <int CH>
+// KB = blocks of 64 positions held in LDS: 1 for t < 64, 4 for t < OVC_MAX_LEN (phase 2 then reduces each head over
+// its KB blocks per lane before the wave reduction; KB = 1 is the round-1 kernel unchanged).
+template <int CH, int KB = 1>
 __global__ __launch_bounds__(256) void decode_self_attention_kernel(DecodeSelfArgs p) {
-    __shared__ int slots[64];
-    __shared__ uint8_t pads[64];
-    __shared__ float sc[kSelfMaxHeads][64];
+    static_assert(KB * 64 <= 256, "phase 0 lists one position per thread");
+    __shared__ int slots[KB * 64];
+    __shared__ uint8_t pads[KB * 64];
+    __shared__ float sc[kSelfMaxHeads][KB * 64];
     __shared__ __attribute__((aligned(16))) float red[256 * 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = blockIdx.x, t = p.t;
@@ -665,11 +668,30 @@ __global__ __launch_bounds__(256) void decode_self_attention_kernel(DecodeSelfAr
     __syncthreads();
 
     for (int hd = wave; hd < p.h; hd += 4) {
-        const float s = lane <= t ? sc[hd][lane] : -INFINITY;
-        const float mx = wave_max(s);
-        const float e = lane <= t ? expf(s - mx) : 0.f;
-        const float sum = wave_sum(e);
-        if (lane <= t) sc[hd][lane] = e / sum;
+        if constexpr (KB == 1) {
+            const float s = lane <= t ? sc[hd][lane] : -INFINITY;
+            const float mx = wave_max(s);
+            const float e = lane <= t ? expf(s - mx) : 0.f;
+            const float sum = wave_sum(e);
+            if (lane <= t) sc[hd][lane] = e / sum;
+        } else {                                     // keys lane, lane + 64, ...: per-lane max / sum first, then the wave's
+            float s[KB], e[KB], mx = -INFINITY, part = 0.f;
+#pragma unroll
+            for (int u = 0; u < KB; ++u) {
+                s[u] = lane + 64 * u <= t ? sc[hd][lane + 64 * u] : -INFINITY;
+                mx = fmaxf(mx, s[u]);
+            }
+            mx = wave_max(mx);
+#pragma unroll
+            for (int u = 0; u < KB; ++u) {
+                e[u] = lane + 64 * u <= t ? expf(s[u] - mx) : 0.f;
+                part += e[u];
+            }
+            const float sum = wave_sum(part);
+#pragma unroll
+            for (int u = 0; u < KB; ++u)
+                if (lane + 64 * u <= t) sc[hd][lane + 64 * u] = e[u] / sum;
+        }
     }
     __syncthreads();
 
@@ -715,14 +737,21 @@ __global__ __launch_bounds__(256) void decode_self_attention_kernel(DecodeSelfAr
 //   softmax over the keys held in accumulator registers, O^T = V^T P^T with the probabilities as the B operand.
 // Key tiles past the end of the list are skipped with wave-uniform branches.  NT = key tiles the instance can hold
 // (worst case k (t + 1) keys, chosen by the host), SB = d_k / 16.
-template <int NT, int SB>
+//
+// CHUNKED (t >= 64): the workgroup takes the kSelfChunk positions of chunk blockIdx.z only (at most 16 W listed keys, so
+// NT = W tiles) and writes its softmax partials -- the beam's chunk maximum M, sum L = sum exp(s - M) and the unnormalised
+// O = sum exp(s - M) v -- to p.part_ml / p.part_o; decode_self_merge_kernel combines the chunks.  A beam that names no
+// unpadded key in the chunk writes M = -inf, L = 0, O = 0 (its exponentials are taken against 0, never -inf - -inf).
+template <int NT, int SB, bool CHUNKED = false>
 __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeSelfArgs p) {
+    constexpr int kPos = CHUNKED ? kSelfChunk : 64;      // positions the workgroup lists (one per lane of wave 0)
     __shared__ unsigned short keyinfo[NT * 16];          // (position << 3) | local slot
     __shared__ uint8_t keypad[NT * 16];
-    __shared__ uint8_t sl[OVC_MAX_BEAM][64];             // local slot of beam i at position j
+    __shared__ uint8_t sl[OVC_MAX_BEAM][kPos];           // local slot of beam i at position j0 + j
     __shared__ int nkeys_shared;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x, t = p.t, W = p.width;
+    const int j0 = CHUNKED ? (int)blockIdx.z * kSelfChunk : 0;
     const int hd = min((int)blockIdx.y * 4 + wave, p.h - 1);
     const bool live = (int)blockIdx.y * 4 + wave < p.h;          // surplus waves redo the last head, store nothing
     const int r = lane & 15, kq = lane >> 4;
@@ -734,12 +763,12 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
     for (int S = 0; S < SB; ++S) qf[S] = *reinterpret_cast<const f32x4*>(qg + 16 * S + 4 * kq);
 
     if (wave == 0) {
-        const int j = lane;
+        const int j = j0 + lane;
         const int wj = j == 0 ? 1 : W;                        // slots of position j's cache block that belong to this image
         int slot[OVC_MAX_BEAM];
         uint8_t pad[OVC_MAX_BEAM];
         unsigned mask = 0;
-        if (j <= t) {
+        if (j <= t && lane < kPos) {
 #pragma unroll
             for (int i = 0; i < OVC_MAX_BEAM; ++i)             // all loads first: ancestor slots and the block's <pad> flags
                 slot[i] = i < W ? (j == t ? i : p.anc[(size_t)(b * W + i) * p.anc_ld + j] - b * wj) : 0;
@@ -749,7 +778,7 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
             for (int i = 0; i < OVC_MAX_BEAM; ++i)
                 if (i < W) {
                     const int s = min(max(slot[i], 0), wj - 1);   // a corrupt table can never index outside the image's block
-                    sl[i][j] = (uint8_t)s;
+                    sl[i][j - j0] = (uint8_t)s;
                     mask |= 1u << s;
                 }
         }
@@ -829,7 +858,7 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
             float s = -INFINITY;
             if (key < nkeys) {
                 const int info = keyinfo[key];
-                if (!keypad[key] && sl[beam][info >> 3] == (info & 7)) s = st[T][g] / scale_div;
+                if (!keypad[key] && sl[beam][(info >> 3) - j0] == (info & 7)) s = st[T][g] / scale_div;
             }
             st[T][g] = s;
             mx = fmaxf(mx, s);
@@ -837,21 +866,24 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mref = CHUNKED && mx == -INFINITY ? 0.f : mx;     // no key in this chunk: every exponential is exactly 0
     float sum = 0.f;
 #pragma unroll
     for (int T = 0; T < NT; ++T)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const float e = expf(st[T][g] - mx);
+            const float e = expf(st[T][g] - mref);
             st[T][g] = e;
             sum += e;
         }
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
+    if constexpr (!CHUNKED) {
 #pragma unroll
-    for (int T = 0; T < NT; ++T)
+        for (int T = 0; T < NT; ++T)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) st[T][g] = st[T][g] / sum;
+            for (int g = 0; g < 4; ++g) st[T][g] = st[T][g] / sum;
+    }
 
     // ---- O^T = V^T P^T -----------------------------------------------------------------------------------------------
     f32x4 acc[4];
@@ -867,7 +899,14 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
         }
     }
     if (live && r < W) {
-        float* orow = p.out + (size_t)(b * W + r) * p.ldo + hd * p.dv;
+        float* orow;
+        if constexpr (CHUNKED) {
+            const size_t prow = (size_t)blockIdx.z * gridDim.x * W + b * W + r;     // [chunk][row]
+            orow = p.part_o + prow * p.h * p.dv + hd * p.dv;
+            if (kq == 0) reinterpret_cast<float2*>(p.part_ml)[prow * p.h + hd] = make_float2(mx, sum);
+        } else {
+            orow = p.out + (size_t)(b * W + r) * p.ldo + hd * p.dv;
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int dvb = 16 * kq + 4 * g;
@@ -876,14 +915,71 @@ __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeS
     }
 }
 
+// The chunks of one (row, head) in ascending order: M = max_c M_c, then L = sum_c L_c exp(M_c - M) and O likewise, one
+// division at the end (the order and the partition are functions of t alone: the bits do not depend on B or on the launch).
+// A chunk with L_c = 0 named no key for the beam and is passed over.  Thread = one float4 of an output row.
+__global__ __launch_bounds__(256) void decode_self_merge_kernel(DecodeSelfArgs p, int rows, int chunks) {
+    const int hv4 = (p.h * p.dv) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * hv4) return;
+    const int row = idx / hv4, c4 = idx - row * hv4, hd = (c4 * 4) / p.dv;
+    const float2* ml = reinterpret_cast<const float2*>(p.part_ml);
+    const size_t hv = (size_t)p.h * p.dv;
+    float M = -INFINITY;
+    for (int c = 0; c < chunks; ++c) M = fmaxf(M, ml[((size_t)c * rows + row) * p.h + hd].x);
+    float L = 0.f;
+    f32x4 O = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < chunks; ++c) {
+        const float2 v = ml[((size_t)c * rows + row) * p.h + hd];
+        if (v.y > 0.f) {
+            const float w = expf(v.x - M);
+            L += v.y * w;
+            O += *reinterpret_cast<const f32x4*>(p.part_o + ((size_t)c * rows + row) * hv + c4 * 4) * w;
+        }
+    }
+    *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.ldo + c4 * 4) = O / L;
+}
+
+// Steps t >= 64 (max_len up to OVC_MAX_LEN).  d_k >= 16: one workgroup per (image, 4 heads, chunk of kSelfChunk positions),
+// de-duplicated as above, then the merge.  d_k in {4, 8} (and the per-row A/B switch): the per-row kernel over 4 blocks of
+// 64 positions.  t < 64 never comes here, so the bits of those steps are the round-3 kernels'.
+static int decode_self_attention_long(const DecodeSelfArgs& p, int rows, bool per_row, hipStream_t stream) {
+    const int W = p.width, hk = p.h * p.dk;
+    if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16) {
+        if (!p.part_o || !p.part_ml) return OVC_EINVAL;
+        const int chunks = (p.t + kSelfChunk) / kSelfChunk;
+        const dim3 grid(rows / W, (p.h + 3) / 4, chunks), block(256);
+#define OVC_SELF(NT, SB) hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB, true>), grid, block, 0, stream, p)
+#define OVC_SELF_NT(SB)                                                                                             \
+    do {                                                                                                            \
+        if (W <= 1) OVC_SELF(1, SB); else if (W <= 2) OVC_SELF(2, SB); else if (W <= 4) OVC_SELF(4, SB);           \
+        else if (W <= 5) OVC_SELF(5, SB); else OVC_SELF(8, SB);                                                     \
+    } while (0)
+        if (p.dk == 64) OVC_SELF_NT(4); else if (p.dk == 32) OVC_SELF_NT(2); else OVC_SELF_NT(1);
+#undef OVC_SELF_NT
+#undef OVC_SELF
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        const int threads = rows * ((p.h * p.dv) >> 2);
+        hipLaunchKernelGGL(decode_self_merge_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        return OVC_OK;
+    }
+    if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel<1, 4>), dim3(rows), dim3(256), 0, stream, p);
+    else if (hk <= 512) hipLaunchKernelGGL((decode_self_attention_kernel<2, 4>), dim3(rows), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((decode_self_attention_kernel<4, 4>), dim3(rows), dim3(256), 0, stream, p);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream) {
     const int hk = p.h * p.dk;
-    if (p.t < 0 || p.t >= 64 || p.h <= 0 || p.h > kSelfMaxHeads) return OVC_EINVAL;
+    if (p.t < 0 || p.t >= OVC_MAX_LEN || p.h <= 0 || p.h > kSelfMaxHeads) return OVC_EINVAL;
     if (p.dk != p.dv || (p.dk & (p.dk - 1)) || p.dk < 4 || p.dk > 64) return OVC_EINVAL;   // dk in {4,8,16,32,64}
     if (hk > 1024) return OVC_EINVAL;
-    // per-image kernel with ancestor de-duplication: the image's rows in one workgroup, at most 112 listed keys
     static const bool per_row = OVC_HOOK_ENV("OVC_SELF_ATTENTION_ROWS") != nullptr;     // A/B switch: the round-1 per-row kernel
     const int W = p.width;
+    if (p.t >= 64) return decode_self_attention_long(p, rows, per_row, stream);
+    // per-image kernel with ancestor de-duplication: the image's rows in one workgroup, at most 112 listed keys
     if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16 && (p.t == 0 ? 1 : W * (p.t + 1)) <= 112) {
         const int worst = p.t == 0 ? 1 : W * (p.t + 1), tiles = (worst + 15) / 16;
         const dim3 grid(rows / W, (p.h + 3) / 4), block(256);

@@ -177,7 +177,11 @@ struct DecodeSelfArgs {
     int h, dk, dv;
     float* out;            // [rows, ldo]
     int ldo;
+    // t >= 64 on the position-chunk path: per (chunk, row, head) softmax partials, merged into out by a second launch
+    float* part_o;         // [chunks][rows][h*dv]  unnormalised sum_j exp(s_j - M) v_j
+    float* part_ml;        // [chunks][rows][h]     float2 (running max M, sum L); M = -inf, L = 0 when the chunk names no key
 };
+constexpr int kSelfChunk = 16;        // positions per chunk of the t >= 64 decode self-attention (a function of t only)
 int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream);
 
 struct DecodeCrossArgs {

@@ -107,6 +107,7 @@ struct Workspace {
     float* part;                                  // [kMaxKSplit][R][d] partial outputs of K-split projections
     float* kc; float* vc;                         // [L][T][R][h*dk|h*dv]
     uint8_t* padflag;                             // [T][R]
+    float* sa_part_o; float* sa_part_ml;          // [ceil(T/16)][R][h*dv] / [ceil(T/16)][R][h][2] when T > 64, else empty
     float* logits;                                // [R][V]
     float* stats;                                 // [R][blocks of 32 words, padded to even] float2: block maxima / sums of exponentials
     float* running[2]; float* alive[2]; int32_t* hist[2]; float* lp[2]; int32_t* anc[2];
@@ -142,7 +143,7 @@ bool model_ok(const ovc_model* m) {
     if (m->d_k != m->d_v || m->d_k < 4 || m->d_k > 64 || (m->d_k & (m->d_k - 1))) return false;
     if ((m->d_feat & 3) || (m->d_ff & 3) || m->heads <= 0 || m->heads > 32 || m->heads * m->d_k > 1024 || m->vocab <= 1) return false;
     if (m->d_feat <= 0 || m->d_ff <= 0 || m->memory < 0) return false;
-    if (m->max_len < 1 || m->max_len > 64) return false;
+    if (m->max_len < 1 || m->max_len > OVC_MAX_LEN) return false;
     if ((m->precision != 0 && m->precision != 3 && m->precision != 4) || m->tune_objective < 0 || m->tune_objective > 8) return false;
     if (m->bos_idx < 0 || m->bos_idx >= m->vocab || m->pad_idx < 0 || m->pad_idx >= m->vocab || m->eos_idx < 0 || m->eos_idx >= m->vocab) return false;
     // fused q|k|v and cross k|v GEMMs need segment widths that are multiples of the 64-wide tile
@@ -204,6 +205,10 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     w.kc = a.take<float>(L * T * R * hk);
     w.vc = a.take<float>(L * T * R * hv);
     w.padflag = a.take<uint8_t>(T * R);
+    // decode self-attention partials of the steps t >= 64 (attention.hip: position chunks, merged per step; reused by every layer)
+    const size_t chunks = T > 64 ? (T + kSelfChunk - 1) / kSelfChunk : 0;
+    w.sa_part_o = a.take<float>(chunks * R * hv);
+    w.sa_part_ml = a.take<float>(chunks * R * m->heads * 2);
     w.logits = a.take<float>(((R + 3) & ~(size_t)3) * (((size_t)m->vocab + 3) & ~(size_t)3));   // [R][V] or [V][R], rows padded to 16 bytes
     w.stats = a.take<float>(2 * ((((size_t)m->vocab + 31) / 32 + 1) & ~(size_t)1) * R);
     for (int i = 0; i < 2; ++i) {
@@ -580,6 +585,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
         sa.q = w.q; sa.ldq = hk; sa.kcache = kc; sa.vcache = vc; sa.pos_stride = (size_t)R * hk; sa.ldkv = hk;
         sa.anc = w.anc[cur]; sa.anc_ld = T; sa.padflag = w.padflag; sa.pad_ld = R; sa.t = t; sa.width = width;
         sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = w.att; sa.ldo = hv;
+        sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
         if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s));
         TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, w.part, w.x1, rows));
         TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));

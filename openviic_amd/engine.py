@@ -183,6 +183,9 @@ class CaptionEngine:
         d.n_levels = dec.layers[0].nlayers if d.dec_kind == native.DEC_MESHED else 1
         d.memory = getattr(first, "m", 0)
         d.vocab, d.max_len = dec.fc.out_features, dec.max_len
+        if not 1 <= dec.max_len <= native.OVC_MAX_LEN:
+            raise native.OvcError("max_len={} is outside the engine's 1..{} (OVC_MAX_LEN): the caption length the decoder "
+                                  "was built for".format(dec.max_len, native.OVC_MAX_LEN))
         d.pad_idx, d.bos_idx, d.eos_idx = dec.padding_idx, model.vocab.bos_idx, model.eos_idx
         d.ln_eps = enc.layer_norm.eps
         if len(enc.layers) > native.OVC_MAX_LAYERS or len(dec.layers) > native.OVC_MAX_LAYERS:

@@ -12,6 +12,7 @@ OVC_MAX_LAYERS = 8
 OVC_MAX_LEVELS = 4
 OVC_MAX_BEAM = 8
 OVC_MAX_REGIONS = 1024
+OVC_MAX_LEN = 256            # decode steps (caption positions, the decoder's max_len) the engine accepts
 OVC_PROFILE_CLASSES = 4
 ABI_VERSION = 8
 

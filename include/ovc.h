@@ -293,6 +293,26 @@ int ovc_beam_search_early(const ovc_model* m, const float* features, const float
                           int k, int out_size, void* workspace, size_t workspace_bytes,
                           int64_t* ids_out, float* logp_out, int* steps_run_out, ovc_stream stream);
 
+/* Teacher-forced forward and caption scoring: the reference's BaseTransformer.forward (models/base_transformer.py:26-30,
+ * decoders.py:95-123) and what its dev-loss loop does with it (trainers/vi_trainer.py:56-76: NLLLoss(ignore_index = pad) against
+ * the shifted-right captions).  tokens / targets [B, T] int64 device ids in [0, vocab) (refuse others on the host: the device reads
+ * the nearest valid row), 1 <= T <= max_len.  Positions are 1..T, 0 where the token is <pad>; self-attention is masked by key
+ * padding OR the causal rule; FFN outputs are zeroed on <pad> query rows; cross-attention uses the encoder mask.  Outputs (either
+ * may be NULL, not both):
+ *   logp_out        [B, T, V] log-probabilities;
+ *   token_logp_out  [B, T] logp[b, t, targets[b, t]], 0 where targets[b, t] == pad_idx (targets required).
+ * Both outputs come from the same per-row log-softmax pieces, so token_logp_out is the gather of logp_out bit for bit; scoring
+ * alone stores no [B*T, V] logits (its workspace is smaller by about B*T*V*4 bytes).  Vocabularies above 16384 words take a row
+ * log-softmax and a gather instead.  fp32 models only (precision != 0: OVC_EINVAL), the search's B / N limits.
+ * use_graph != 0: everything between the kernels that read the caller's inputs and those that write its outputs is captured as a
+ * hipGraph on the second call for a given (model contents, workspace, B, N, T, logp_out != NULL) and replayed afterwards, in the
+ * cache ovc_beam_search_graph uses (same bound, same rules; identical results either way).
+ * ovc_forward_workspace_bytes: bytes of workspace (0 on invalid arguments; want_logp = whether logp_out will be passed). */
+size_t ovc_forward_workspace_bytes(const ovc_model* m, int B, int N, int T, int want_logp);
+int ovc_forward(const ovc_model* m, const float* features, const float* boxes, int B, int N, const int64_t* tokens,
+                const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* logp_out, float* token_logp_out,
+                int use_graph, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

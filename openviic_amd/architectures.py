@@ -2,7 +2,8 @@
 ``meshed_memory_transformer.py``, ``object_relation_transformer.py``, ``camo_transformer.py``), registered under the
 reference's names so its yaml files resolve unchanged.
 
-API kept: ``forward(input_features) -> log-probs (B,T,V)``; ``encoder_forward(input_features) ->
+API kept: ``forward(input_features, fused=False) -> log-probs (B,T,V)`` (``fused=True``: on the engine); ``score(input_features)
+-> (B,T)`` target log-probs (engine); ``encoder_forward(input_features) ->
 (encoder_features, padding_mask (B,1,1,N) bool)``; ``step(t, prev_output)``;
 ``beam_search(input_features, batch_size, beam_size, out_size=1, return_probs=False)``.
 
@@ -64,7 +65,12 @@ class BaseTransformer(Module):
             out = self.encoder(features=features, padding_mask=padding_mask)
         return out, padding_mask
 
-    def forward(self, input_features):
+    def forward(self, input_features, fused=False):
+        """Teacher-forced log-probabilities (B, T, V).  ``fused=False`` (default): operator by operator, as the reference
+        runs it; ``fused=True``: one call into the HIP engine (``CaptionEngine.forward``, ``ovc_forward``)."""
+        if fused:
+            boxes = input_features["region_boxes"] if self.uses_boxes else None
+            return self._fused_engine().forward(input_features[self.feature_field], boxes, input_features["caption_tokens"])
         encoder_features, encoder_padding_mask = self.encoder_forward(input_features)
         return self.decoder(caption_tokens=input_features["caption_tokens"],
                             encoder_features=encoder_features,
@@ -80,6 +86,20 @@ class BaseTransformer(Module):
                             encoder_attention_mask=self.encoder_padding_mask)
 
     # -- accelerated path -------------------------------------------------------------------
+    def _fused_engine(self):
+        if self._engine is None:
+            self._engine = engine.CaptionEngine(self)
+        return self._engine
+
+    def score(self, input_features):
+        """(B, T) log-probability of each word of ``shifted_right_caption_tokens`` given ``caption_tokens`` up to it, 0 where
+        the target is ``<pad>`` -- on the HIP engine, without a (B, T, V) tensor.  The reference's dev loss
+        (``vi_trainer.py:56-76``: NLLLoss(ignore_index=pad) over ``model(items)``) is
+        ``-score.sum() / (targets != pad).sum()``."""
+        boxes = input_features["region_boxes"] if self.uses_boxes else None
+        return self._fused_engine().score(input_features[self.feature_field], boxes, input_features["caption_tokens"],
+                                          input_features["shifted_right_caption_tokens"])
+
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
                     fused=True, **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
@@ -89,10 +109,8 @@ class BaseTransformer(Module):
         still native -- and exists for parity checks of ``step`` / ``statefulness``.
         """
         if fused:
-            if self._engine is None:
-                self._engine = engine.CaptionEngine(self)
             boxes = input_features["region_boxes"] if self.uses_boxes else None
-            return self._engine.beam_search(input_features[self.feature_field], boxes, batch_size, beam_size,
+            return self._fused_engine().beam_search(input_features[self.feature_field], boxes, batch_size, beam_size,
                                             out_size=out_size, return_probs=return_probs, early_exit=kwargs.get("early_exit"))
         searcher = BeamSearch(model=self, max_len=self.max_len, eos_idx=self.eos_idx, beam_size=beam_size,
                               b_s=batch_size, device=self.device)

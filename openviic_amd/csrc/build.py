@@ -13,7 +13,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "beam.hip", "engine.hip"]
-HEADERS = ["common.h", "gemm_split.h", "gemm_rows16.h", os.path.join("..", "..", "include", "ovc.h")]
+HEADERS = ["common.h", "gemm_split.h", "gemm_rows16.h", "gemm_f32_body.inc", os.path.join("..", "..", "include", "ovc.h")]
 LIBRARY = os.path.join(HERE, "libovc.so")
 ARCH = "gfx950"
 

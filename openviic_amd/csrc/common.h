@@ -145,6 +145,11 @@ struct GemmLaunchOpts {
     int forced_tiling = -1;                 // >= 0: use exactly this tiling (must fit the problem and its class)
     int copies = 1;                         // tuner: gridDim.z identical copies co-running in one launch
     hipEvent_t start = nullptr, stop = nullptr;   // kernel-scoped events (dispatch begin / end timestamps) for profiling
+    // scoring epilogue (a transposed product with stats_t, one-chain class): tgt_logit[n] = C[tgt[n], n] for every column n, and C
+    // itself is NOT stored (seg[0].C may be nullptr) -- the teacher-forced scoring path, which needs no [V, rows] logits.  Carried
+    // here rather than in GemmArgs so that the kernel argument layout of every other instance stays as it is.
+    const int32_t* tgt = nullptr;
+    float* tgt_logit = nullptr;
 };
 
 // Launches C = act([A1|A2] W^T + bias) + R on `stream`; returns an OVC_* code.

@@ -115,6 +115,9 @@ struct Workspace {
     float* all_buf;
     int64_t* out_ids; float* out_logp;            // graph replay writes here, then copied to the caller
     int32_t* alive_count;                         // [T] beams still alive after each step (ovc_beam_search_early)
+    // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
+    // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
+    uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
     size_t bytes;
 };
 
@@ -171,10 +174,9 @@ bool model_ok(const ovc_model* m) {
     return true;
 }
 
-Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_probs) {
-    Workspace w{};
-    Bump a{reinterpret_cast<char*>(base), 0};
-    const size_t BN = (size_t)B * N, R = (size_t)B * k, d = m->d_model, T = m->max_len;
+// The encoder's buffers and the projected cross-attention keys / values: the same layout for the search and the forward.
+void carve_encoder(Workspace& w, Bump& a, const ovc_model* m, int B, int N) {
+    const size_t BN = (size_t)B * N, d = m->d_model;
     const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels, L = m->n_dec;
     const size_t ehk = (size_t)enc_heads(m) * enc_dk(m), ehv = (size_t)enc_heads(m) * enc_dv(m);
     const bool cross_level = m->enc_kind == OVC_ENC_CROSS_LEVEL;
@@ -194,6 +196,14 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     w.cl_q = a.take<float>(cross_level ? 2 * BN * ehk : 0);
     w.kx = a.take<float>(L * lv * BN * hk);
     w.vx = a.take<float>(L * lv * BN * hv);
+}
+
+Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_probs) {
+    Workspace w{};
+    Bump a{reinterpret_cast<char*>(base), 0};
+    const size_t R = (size_t)B * k, d = m->d_model, T = m->max_len;
+    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels, L = m->n_dec;
+    carve_encoder(w, a, m, B, N);
     w.x = a.take<float>(R * d); w.x1 = a.take<float>(R * d); w.x2 = a.take<float>(R * d); w.y = a.take<float>(R * d);
     w.q = a.take<float>(R * hk);
     w.att = a.take<float>(lv * R * hv);
@@ -220,6 +230,43 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     w.all_buf = a.take<float>(return_probs ? T * R * (size_t)m->vocab : 0);
     w.out_ids = a.take<int64_t>(R * T); w.out_logp = a.take<float>(R * T);
     w.alive_count = a.take<int32_t>(T);
+    w.bytes = (a.off + 255) & ~(size_t)255;
+    return w;
+}
+
+// Vocabularies up to this many 32-word blocks take the fused vocabulary tail (the block pieces of the GEMM epilogue), larger
+// ones a row log-softmax -- the search's edge as well (run_decode_step).
+constexpr int kFusedVocabBlocks = 512;
+
+// ovc_forward: rows = B*T decoder rows.  With want_logp the transposed logits [V][rows padded to 4] are kept; scoring alone keeps
+// only the block pieces and one logit per row.  Above kFusedVocabBlocks the row-major logits [rows][V] and, for scoring, the
+// log-probabilities they turn into.
+Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int want_logp) {
+    Workspace w{};
+    Bump a{reinterpret_cast<char*>(base), 0};
+    const size_t rows = (size_t)B * T, d = m->d_model, V = m->vocab;
+    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels;
+    carve_encoder(w, a, m, B, N);
+    w.x = a.take<float>(rows * d); w.x1 = a.take<float>(rows * d); w.x2 = a.take<float>(rows * d); w.y = a.take<float>(rows * d);
+    w.q = a.take<float>(rows * hk); w.kc = a.take<float>(rows * hk); w.vc = a.take<float>(rows * hv);
+    w.att = a.take<float>(lv * rows * hv);
+    w.ff = a.take<float>(rows * m->d_ff);
+    w.info = a.take<float>(rows * d); w.gate = a.take<float>(rows * d);
+    w.enc_att = a.take<float>(lv * rows * d); w.alpha = a.take<float>(lv * rows * d); w.mixed = a.take<float>(rows * d);
+    w.ymesh = a.take<float>(lv > 1 ? lv * rows * d : 0);
+    w.padflag = a.take<uint8_t>(rows);
+    w.self_mask = a.take<uint8_t>(rows * T);
+    w.tgt = a.take<int32_t>(rows);
+    const size_t nblk = (V + 31) / 32;
+    if (nblk <= (size_t)kFusedVocabBlocks) {
+        w.logits = a.take<float>(want_logp ? V * ((rows + 3) & ~(size_t)3) : 0);
+        w.stats = a.take<float>(2 * ((nblk + 1) & ~(size_t)1) * rows);
+        w.tgt_logit = a.take<float>(rows);
+        w.lse = a.take<float>(2 * rows);
+    } else {
+        w.logits = a.take<float>(rows * V);
+        w.all_buf = a.take<float>(want_logp ? 0 : rows * V);
+    }
     w.bytes = (a.off + 255) & ~(size_t)255;
     return w;
 }
@@ -284,6 +331,93 @@ __global__ void concat_levels_kernel(const float* __restrict__ levels, float* __
     }
 }
 
+// ---- teacher-forced forward (ovc_forward) ----------------------------------------------------
+// decoders.py:95-112 in batch mode, one wave per row r = b*T + t: x[r,:] = word_emb[tok] + pos_emb[pos] with pos = t + 1, or 0 where
+// tok is <pad>; padflag[r] = (tok == pad); the self-attention mask row mask[b,t,j] = (tok[b,j] == pad) || j > t (padding OR the causal
+// rule); tgt[r] = the target word.  Ids outside [0, V) read the nearest valid row (the host refuses them before this runs).
+__global__ __launch_bounds__(256) void tf_inputs_kernel(const int64_t* __restrict__ tokens, const int64_t* __restrict__ targets,
+                                                        int V, int pad, int T, const float* __restrict__ table,
+                                                        const float* __restrict__ pos_table, float* __restrict__ x,
+                                                        uint8_t* __restrict__ padflag, uint8_t* __restrict__ mask,
+                                                        int32_t* __restrict__ tgt, int rows, int d) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / T, t = row - b * T;
+    const int token = (int)min(max(tokens[row], (int64_t)0), (int64_t)V - 1);
+    const bool is_pad = token == pad;
+    if (lane == 0) {
+        padflag[row] = is_pad ? 1 : 0;
+        tgt[row] = targets ? (int)min(max(targets[row], (int64_t)0), (int64_t)V - 1) : 0;
+    }
+    const int64_t* brow = tokens + (size_t)b * T;
+    for (int j = lane; j < T; j += 64) mask[(size_t)row * T + j] = (brow[j] == pad || j > t) ? 1 : 0;
+    const f32x4* e = reinterpret_cast<const f32x4*>(table + (size_t)token * d);
+    const f32x4* p = reinterpret_cast<const f32x4*>(pos_table + (size_t)(is_pad ? 0 : t + 1) * d);
+    f32x4* o = reinterpret_cast<f32x4*>(x + (size_t)row * d);
+    for (int c = lane; c < (d >> 2); c += 64) o[c] = e[c] + p[c];
+}
+
+// One wave per row: the row's log-softmax pieces from the vocabulary GEMM's block pieces (stats [rows][ld] float2, nblk valid),
+// combined in a fixed order -- maximum M over the blocks, then sum_b s_b exp(m_b - M) with lane partials over ascending blocks and
+// one xor butterfly -- into lse[row] = (M, log S).  With token_logp: token_logp[row] = 0 where the target is <pad>, else
+// (logit - M) - log S for the target's logit, read from tgt_logit (scoring) or from the transposed logits (ldt > 0).  The
+// log-probabilities kernel below applies the same (M, log S) with the same formula, so token_logp is their gather bit for bit.
+__global__ __launch_bounds__(256) void tf_lse_kernel(const float* __restrict__ stats, int nblk, int ld, int rows,
+                                                     const int32_t* __restrict__ tgt, int pad, const float* __restrict__ tgt_logit,
+                                                     const float* __restrict__ logits_t, long ldt, float* __restrict__ lse,
+                                                     float* __restrict__ token_logp) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const f32x2* st = reinterpret_cast<const f32x2*>(stats) + (size_t)row * ld;
+    float mx = -INFINITY;
+    for (int i = lane; i < nblk; i += 64) mx = fmaxf(mx, st[i][0]);
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int i = lane; i < nblk; i += 64) sum += st[i][1] * expf(st[i][0] - mx);
+    sum = wave_sum(sum);
+    const float ls = logf(sum);
+    if (lane == 0) {
+        lse[2 * row] = mx; lse[2 * row + 1] = ls;
+        if (token_logp) {
+            const int w = tgt[row];
+            const float logit = logits_t ? logits_t[(size_t)w * ldt + row] : tgt_logit[row];
+            token_logp[row] = w == pad ? 0.f : (logit - mx) - ls;
+        }
+    }
+}
+
+// logp[row, w] = (logits_t[w, row] - M) - log S: the transposed logits back to row-major [rows][V] through LDS, 64 rows x 64 words
+// per workgroup (reads along rows, writes along words).
+__global__ __launch_bounds__(256) void tf_logp_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                                      int rows, int V, float* __restrict__ logp) {
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, w0 = blockIdx.y * 64;
+    const int r = r0 + lane;
+#pragma unroll 4
+    for (int i = wv; i < 64; i += 4) {
+        const int w = w0 + i;
+        tile[i][lane] = (w < V && r < rows) ? logits_t[(size_t)w * ldt + r] : 0.f;
+    }
+    __syncthreads();
+    const int w = w0 + lane;
+    if (w >= V) return;
+#pragma unroll 4
+    for (int i = wv; i < 64; i += 4) {
+        const int row = r0 + i;
+        if (row < rows) logp[(size_t)row * V + w] = (tile[lane][i] - lse[2 * row]) - lse[2 * row + 1];
+    }
+}
+
+// Vocabularies above kFusedVocabBlocks blocks: token_logp[row] = logp[row, target] (0 where the target is <pad>).
+__global__ void tf_gather_kernel(const float* __restrict__ logp, const int32_t* __restrict__ tgt, int pad, int rows, int V,
+                                 float* __restrict__ token_logp) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row < rows) token_logp[row] = tgt[row] == pad ? 0.f : logp[(size_t)row * V + tgt[row]];
+}
+
 // ---------------------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------------------
@@ -315,7 +449,7 @@ struct Engine {
         return GemmSegment{l.w, l.b, C, A2, m->precision > 0 ? l.planes : nullptr};
     }
 
-    int gemm(GemmArgs& a) {
+    int gemm(GemmArgs& a, const GemmLaunchOpts& launch = GemmLaunchOpts{}) {
         a.kchains = m->precision > 0 ? 100 + m->precision : kchains;   // opt-in split precision: its own K-order classes
         // fp16 planes cannot hold what lies outside fp16's range.  Weights are checked when the mode is selected, activations
         // behind a LayerNorm / softmax / ReLU of bounded operands are bounded -- the caller's features are not: their
@@ -327,7 +461,7 @@ struct Engine {
             if (std::find(dry->begin(), dry->end(), sh) == dry->end()) dry->push_back(sh);
             return OVC_OK;
         }
-        if (!g_profile_on.load()) return ovc_gemm_launch(a, stream);
+        if (!g_profile_on.load()) return ovc_gemm_launch(a, stream, launch);
         std::lock_guard<std::mutex> lock(g_profile_mutex);
         if (g_profile.empty() && g_profile_empty.empty()) {
             // calibrate the bracket: event pairs with nothing in between
@@ -345,7 +479,7 @@ struct Engine {
         rec.cls = gemm_class;
         rec.tiling = ovc_gemm_pick_tiling(a);
         // kernel-scoped events: the dispatch's own begin / end timestamps (no marker latency in between)
-        GemmLaunchOpts opts{};
+        GemmLaunchOpts opts = launch;
         opts.start = rec.start; opts.stop = rec.stop;
         const int rc = ovc_gemm_launch(a, stream, opts);
         g_profile.push_back(rec);
@@ -719,6 +853,145 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
     return OVC_OK;
 }
 
+// The teacher-forced decoder (decoders.py:95-123 without the log-softmax) over rows = B*T rows whose inputs tf_inputs_kernel wrote:
+// per layer the masked self-attention over the caption (ovc_attention, nq = nk = T, the [B,T,T] mask), cross-attention over the
+// projected encoder keys / values of every level (nq = T, the encoder mask), the meshed level gates or the AddNorm, AoA gates where
+// the model has them, the FFN with <pad> query rows cleared -- then the vocabulary product.  Every product is of the one-chain
+// class (M = B*T rows, like the encoder's), so the decoder outputs are those of the operator path (ovc_linear) bit for bit.
+// Vocabulary: up to kFusedVocabBlocks blocks the transposed product of the search with its block pieces (want_logp: the logits are
+// stored; scoring: gemm_f32_mfma_score keeps only each row's target logit); beyond, the row-major logits.
+int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_logp) {
+    const ovc_model* m = e.m;
+    hipStream_t s = e.stream;
+    const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels;
+    const int rows = B * T, BN = B * N;
+    const float scale = sqrtf((float)m->d_k);
+    e.gemm_class = 2;
+    e.kchains = 1;
+    float* x = w.x;
+    for (int l = 0; l < m->n_dec; ++l) {
+        const ovc_dec_layer& dl = m->dec[l];
+        // ---- masked self-attention over the caption ------------------------------------------------
+        GemmArgs a{};
+        a.A1 = x; a.lda1 = d; a.K1 = d; a.M = rows; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
+        a.seg[0] = e.seg(dl.self_att.q, w.q);
+        a.seg[1] = e.seg(dl.self_att.k, w.kc);
+        a.seg[2] = e.seg(dl.self_att.v, w.vc);
+        TRY(e.gemm(a));
+        const int smem = dl.self_att.m_k ? m->memory : 0;
+        RUN(ovc_attention(w.q, w.kc, w.vc, B, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
+                          dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), w.att, s));
+        TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, nullptr, w.x1, rows));
+        TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));
+
+        // ---- cross-attention over every encoder level -----------------------------------------------
+        TRY(e.linear(w.x1, d, dl.cross_att.q, nullptr, w.q, rows, hk, 0));
+        const int cmem = dl.cross_att.m_k ? m->memory : 0;
+        for (int lvl = 0; lvl < lv; ++lvl) {
+            const size_t off = ((size_t)l * lv + lvl) * BN * hk;
+            RUN(ovc_attention(w.q, w.kx + off, w.vx + off, B, T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
+                              dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
+                              w.att + (size_t)lvl * rows * hv, s));
+        }
+        float* ffn_in;
+        if (m->dec_kind == OVC_DEC_MESHED) {
+            // the search's meshed block (run_decode_step) on rows = B*T
+            const size_t nrd = (size_t)rows * d;
+            if (!dl.cross_att.aoa_i.w) {
+                GemmArgs o{};
+                o.A1 = w.att; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
+                o.R = w.x1; o.ldr = d; o.res_mod = rows;
+                o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
+                TRY(e.gemm(o));
+                RUN(ovc_layer_norm(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                   w.enc_att, lv * rows, d, s));
+            } else {
+                for (int lvl = 0; lvl < lv; ++lvl) {
+                    TRY(e.linear(w.att + (size_t)lvl * rows * hv, hv, dl.cross_att.o, w.x1, w.y, rows, d, 0));
+                    RUN(ovc_layer_norm(w.y, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                       w.enc_att + lvl * nrd, rows, d, s));
+                    TRY(e.aoa(dl.cross_att, w.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
+                }
+            }
+            {
+                GemmArgs g{};
+                g.A1 = w.x1; g.lda1 = d; g.K1 = d; g.lda2 = d; g.K2 = d;
+                g.M = rows; g.seg_n = d; g.ldc = d;
+                const bool fused = d % 64 == 0 && lv <= OVC_MAX_SEGMENTS;
+                for (int lvl = 0; lvl < lv; ++lvl) {
+                    const GemmSegment seg = e.seg(dl.alpha[lvl], w.alpha + lvl * nrd, w.enc_att + lvl * nrd);
+                    if (fused) { g.seg[lvl] = seg; continue; }
+                    g.seg[0] = seg; g.nseg = 1;
+                    TRY(e.gemm(g));
+                }
+                if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
+            }
+            RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s));
+            ffn_in = w.mixed;
+        } else {
+            TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, nullptr, w.x2, rows));
+            TRY(e.aoa(dl.cross_att, w.x1, w.x2, w.info, w.gate, rows));
+            ffn_in = w.x2;
+        }
+        TRY(e.ffn(dl.ffn, ffn_in, w.ff, w.y, nullptr, w.x, w.padflag, rows));
+        x = w.x;
+    }
+
+    // ---- vocabulary product ----------------------------------------------------------------------
+    e.gemm_class = 3;
+    const int nblk = (m->vocab + 31) / 32;
+    GemmArgs g{};
+    if (nblk <= kFusedVocabBlocks) {
+        // logits^T [V][rows] = fc . x^T with the block pieces in its epilogue, as the search runs it (run_decode_step)
+        g.A1 = m->fc; g.lda1 = d; g.K1 = d; g.M = m->vocab; g.seg_n = rows; g.nseg = 1; g.ldc = (rows + 3) & ~3;
+        g.seg[0] = GemmSegment{x, nullptr, want_logp ? w.logits : nullptr, nullptr, nullptr};
+        g.stats_t = w.stats; g.stats_ld = (nblk + 1) & ~1;
+        GemmLaunchOpts scoring{};
+        if (!want_logp) { scoring.tgt = w.tgt; scoring.tgt_logit = w.tgt_logit; }
+        return e.gemm(g, scoring);
+    }
+    g.A1 = x; g.lda1 = d; g.K1 = d; g.M = rows; g.seg_n = m->vocab; g.nseg = 1; g.ldc = m->vocab;
+    g.seg[0] = GemmSegment{m->fc, nullptr, w.logits, nullptr, nullptr};
+    return e.gemm(g);
+}
+
+// After the decoder: the kernels that write the caller's outputs (kept out of the captured graph, like the input kernels).
+int finish_forward(Engine& e, Workspace& w, int B, int T, float* logp_out, float* token_logp_out) {
+    const ovc_model* m = e.m;
+    hipStream_t s = e.stream;
+    const int rows = B * T, V = m->vocab, nblk = (V + 31) / 32;
+    if (nblk <= kFusedVocabBlocks) {
+        const long ldt = (rows + 3) & ~3;
+        hipLaunchKernelGGL(tf_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.stats, nblk, (nblk + 1) & ~1, rows, w.tgt,
+                           m->pad_idx, w.tgt_logit, logp_out ? w.logits : nullptr, ldt, w.lse, token_logp_out);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        if (logp_out) {
+            hipLaunchKernelGGL(tf_logp_kernel, dim3((rows + 63) / 64, (V + 63) / 64), dim3(256), 0, s, w.logits, ldt, w.lse, rows, V,
+                               logp_out);
+            OVC_RETURN_IF_LAUNCH_FAILED();
+        }
+        return OVC_OK;
+    }
+    float* logp = logp_out ? logp_out : w.all_buf;
+    TRY(ovc_log_softmax(w.logits, logp, rows, V, s));
+    if (token_logp_out) {
+        hipLaunchKernelGGL(tf_gather_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, logp, w.tgt, m->pad_idx, rows, V, token_logp_out);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
+    return OVC_OK;
+}
+
+int issue_forward_body(Engine& e, Workspace& w, int B, int N, int T, int want_logp) {
+    TRY(run_encoder_layers(e, w, B, N));
+    TRY(project_cross_kv(e, w, B, N));
+    return run_forward_decoder(e, w, B, N, T, want_logp);
+}
+
+bool forward_ok(const ovc_model* m, int B, int N, int T) {
+    return model_ok(m) && m->precision == 0 && B > 0 && N > 0 && N <= OVC_MAX_REGIONS && T >= 1 && T <= m->max_len &&
+           (long)B * T <= (1L << 24);
+}
+
 }  // namespace
 
 extern "C" int ovc_abi_version(void) { return 8; }     // 8: OVC_ENC_CROSS_LEVEL, encoder-stack heads / d_k / d_v (appended fields)
@@ -812,8 +1085,9 @@ extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const 
 namespace {
 struct GraphKey {
     uint64_t model_hash; const void* ws; int B, N, k, out_size;
+    int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp)
     bool operator<(const GraphKey& o) const {
-        return std::tie(model_hash, ws, B, N, k, out_size) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size);
+        return std::tie(model_hash, ws, B, N, k, out_size, kind) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size, o.kind);
     }
 };
 struct GraphEntry { int calls; bool unsupported; hipGraph_t graph; hipGraphExec_t exec; hipStream_t last_stream; uint64_t last_use; };
@@ -1091,6 +1365,61 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
     TRY(ovc_beam_finalize_launch(bf, B, e.stream));
     if (steps_run_out) *steps_run_out = steps_run;
     return OVC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Teacher-forced forward / caption scoring (decoders.py:95-123; the dev-loss loop of vi_trainer.py:56-76).  Launch order: the
+// input kernels (feature projection, box relations, tf_inputs_kernel: they read the caller's features / boxes / tokens / targets),
+// then the body -- encoder layers, cross keys / values, the decoder over B*T rows, the vocabulary product -- captured as a hipGraph
+// on the second call of a (model, workspace, B, N, T, want_logp) when use_graph is set, then the output kernels (tf_lse_kernel,
+// tf_logp_kernel or the row log-softmax + gather), which write the caller's buffers.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ovc_forward_workspace_bytes(const ovc_model* m, int B, int N, int T, int want_logp) {
+    if (!forward_ok(m, B, N, T)) return 0;
+    return carve_forward(m, nullptr, B, N, T, want_logp ? 1 : 0).bytes;
+}
+
+extern "C" int ovc_forward(const ovc_model* m, const float* features, const float* boxes, int B, int N, const int64_t* tokens,
+                           const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* logp_out,
+                           float* token_logp_out, int use_graph, ovc_stream stream) {
+    if (!forward_ok(m, B, N, T) || !features || !tokens || !workspace || (!logp_out && !token_logp_out) ||
+        (token_logp_out && !targets)) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    const int want_logp = logp_out != nullptr;
+    Workspace w = carve_forward(m, workspace, B, N, T, want_logp);
+    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    const int rows = B * T;
+
+    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
+                       m->word_emb, m->pos_emb, w.x, w.padflag, w.self_mask, w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    if (!use_graph) {
+        TRY(issue_forward_body(e, w, B, N, T, want_logp));
+        return finish_forward(e, w, B, T, logp_out, token_logp_out);
+    }
+    {
+        GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, T, want_logp};
+        key.kind = 1;
+        std::lock_guard<std::mutex> lock(g_graph_mutex);
+        GraphEntry& entry = g_graphs[key];
+        entry.calls += 1;
+        entry.last_use = ++g_graph_tick;
+        entry.last_stream = e.stream;
+        evict_lru(&key, nullptr);
+        // captured on the private stream, as the search (ovc_beam_search_graph) explains
+        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec &&
+            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_forward_body(ce, w, B, N, T, want_logp); }))
+            entry.unsupported = true;
+        if (entry.exec && !g_profile_on) {
+            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        } else {
+            TRY(issue_forward_body(e, w, B, N, T, want_logp));
+        }
+    }
+    return finish_forward(e, w, B, T, logp_out, token_logp_out);
 }
 
 // Test hook: ONE selection step of the fused path on caller-supplied decoder outputs -- the vocabulary product with its

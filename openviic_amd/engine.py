@@ -73,6 +73,24 @@ class _WeightPlanes:
                 torch.cuda.current_stream().synchronize()
 
 
+def check_caption_ids(ids, name, batch, max_len, vocab):
+    """Host-side check of teacher-forced ids (``ovc_forward`` reads the nearest valid row for an id outside the vocabulary, it
+    never raises): an int64 tensor (B, T) with 1 <= T <= max_len and every id in [0, vocab).  Returns T."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
+        raise native.OvcError("{} must be an int64 tensor (got {})".format(
+            name, ids.dtype if isinstance(ids, torch.Tensor) else type(ids).__name__))
+    if ids.dim() != 2 or ids.shape[0] != batch:
+        raise native.OvcError("{} must be (B={}, T); got {}".format(name, batch, tuple(ids.shape)))
+    T = ids.shape[1]
+    if not 1 <= T <= max_len:
+        raise native.OvcError("{}: T={} is outside 1..{} (max_len, the caption length the decoder was built for)".format(
+            name, T, max_len))
+    lo, hi = (int(v) for v in torch.aminmax(ids))
+    if lo < 0 or hi >= vocab:
+        raise native.OvcError("{} holds ids in [{}, {}], outside the vocabulary [0, {})".format(name, lo, hi, vocab))
+    return T
+
+
 def _norm(dst, ln):
     dst.g, dst.b = _p(ln.weight.detach()), _p(ln.bias.detach())
 
@@ -139,6 +157,9 @@ class CaptionEngine:
         self._planes = _WeightPlanes(self.lib) if self.precision != "f32" and self.precut_weights else None
         self.desc = self._describe(model)
         self._workspaces = {}    # one scratch buffer per HIP stream: concurrent batches never share state
+        # the teacher-forced forward's and the scoring's own, per (stream, logp wanted): a dev-loss pass between two searches
+        # leaves the search's buffer -- whose address keys its captured graphs -- where it is
+        self._fw_workspaces = {}
         self._tuned = set()
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
@@ -325,25 +346,28 @@ class CaptionEngine:
         if need == 0:
             raise native.OvcError("unsupported engine configuration (B={}, N={}, beam={}; see ovc_workspace_bytes)"
                                   .format(B, N, k))
-        key = torch.cuda.current_stream().cuda_stream
-        ws = self._workspaces.get(key)
+        return self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need), need
+
+    def _cached_workspace(self, table, key, need):
+        ws = table.get(key)
         if ws is None or ws.numel() < need:
-            old = self._workspaces.pop(key, None)
+            old = table.pop(key, None)
             if old is not None:
                 # captured graphs reference the old buffer's addresses: drop them before it is freed
                 self.lib.ovc_graph_cache_drop_workspace(old.data_ptr())
             # grow geometrically so that a slowly increasing region count does not re-allocate (and re-capture) every time
             size = need if old is None else max(need, int(old.numel() * 1.25))
-            ws = self._workspaces[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
-        return ws, need
+            ws = table[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
+        return ws
 
     def release(self):
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
-        for ws in getattr(self, "_workspaces", {}).values():
+        for ws in list(getattr(self, "_workspaces", {}).values()) + list(getattr(self, "_fw_workspaces", {}).values()):
             if lib is not None:
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._workspaces = {}
+        self._fw_workspaces = {}
 
     def __del__(self):
         try:
@@ -453,3 +477,46 @@ class CaptionEngine:
         if out_size == 1:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
+
+    # -- teacher-forced forward / caption scoring ------------------------------------------------------------------
+    def forward(self, features, boxes, caption_tokens):
+        """Teacher-forced log-probabilities ``(B, T, V)`` of ``caption_tokens`` -- the reference's ``model(items)``
+        (``decoders.py:95-123``) in one call (``ovc_forward``)."""
+        return self._teacher_forced(features, boxes, caption_tokens, None)[0]
+
+    def score(self, features, boxes, caption_tokens, targets):
+        """``(B, T)`` log-probability of ``targets[b, t]`` after ``caption_tokens[b, :t + 1]``, 0 where the target is
+        ``<pad>``: the terms of the reference's dev loss (``NLLLoss(ignore_index=pad)`` against ``shifted_right_caption_tokens``,
+        ``vi_trainer.py:56-76``), which is then ``-score.sum() / (targets != pad).sum()``.  No ``(B, T, V)`` tensor is made."""
+        return self._teacher_forced(features, boxes, caption_tokens, targets)[1]
+
+    def _teacher_forced(self, features, boxes, caption_tokens, targets):
+        d = self.desc
+        if d.precision != 0:
+            raise native.OvcError("the teacher-forced forward runs in 'f32' only (precision={!r})".format(self.precision))
+        features, boxes = self._checked_inputs(features, boxes)
+        B, N = features.shape[:2]
+        T = check_caption_ids(caption_tokens, "caption_tokens", B, d.max_len, d.vocab)
+        if targets is not None:
+            check_caption_ids(targets, "targets", B, d.max_len, d.vocab)
+            if tuple(targets.shape) != tuple(caption_tokens.shape):
+                raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
+                    tuple(targets.shape), tuple(caption_tokens.shape)))
+            targets = targets.to(self.device).contiguous()
+        tokens = caption_tokens.to(self.device).contiguous()
+        want_logp = targets is None
+        need = self.lib.ovc_forward_workspace_bytes(ctypes.byref(d), B, N, T, 1 if want_logp else 0)
+        if need == 0:
+            raise native.OvcError("unsupported teacher-forced configuration (B={}, N={}, T={}; see ovc_forward_workspace_bytes)"
+                                  .format(B, N, T))
+        self._refresh_derived()
+        stream = torch.cuda.current_stream().cuda_stream
+        ws = self._cached_workspace(self._fw_workspaces, (stream, want_logp), need)
+        logp = torch.empty(B, T, d.vocab, dtype=torch.float32, device=self.device) if want_logp else None
+        token_logp = None if want_logp else torch.empty(B, T, dtype=torch.float32, device=self.device)
+        check(self.lib.ovc_forward(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
+                                   tokens.data_ptr(), None if targets is None else targets.data_ptr(), T, ws.data_ptr(), need,
+                                   None if logp is None else logp.data_ptr(),
+                                   None if token_logp is None else token_logp.data_ptr(), 1 if self.use_graph else 0,
+                                   native.stream_handle()), "ovc_forward")
+        return logp, token_logp

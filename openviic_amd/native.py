@@ -123,6 +123,9 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     "ovc_beam_search_early": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                       c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "ovc_forward_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_forward": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                            c_void_p, c_void_p, c_int, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),

@@ -293,6 +293,19 @@ int ovc_beam_search_early(const ovc_model* m, const float* features, const float
                           int k, int out_size, void* workspace, size_t workspace_bytes,
                           int64_t* ids_out, float* logp_out, int* steps_run_out, ovc_stream stream);
 
+/* The same early exit, decided ON THE DEVICE, without blocking.  The whole search is ONE graph as in ovc_beam_search_graph (plain
+ * launches on the first call of a (model contents, B, N, k, out_size, workspace), captured on the second, kept in the same LRU
+ * cache under its own key), and every launch of decode step t >= 1 is gated: it reads the number of beams still alive after step
+ * t - 1 (counted by that step's update kernel into a workspace array zeroed at the start of every search) and returns at entry
+ * when it is 0.  A dead step costs its empty launches, not its work.  The final ordering reads the number of steps that ran from
+ * the device; *steps_out (DEVICE memory, one int32, may be NULL) receives it, 1 .. max_len, in stream order.  No host
+ * synchronisation, no device-to-host copy: the call returns once the work is enqueued.  ids_out / logp_out equal
+ * ovc_beam_search_graph's under ovc_beam_search_early's assumptions (no total score below -999; an image without a valid region
+ * counts as ended).  fp32 only (precision != 0: OVC_EINVAL); no return_probs form; the workspace is ovc_workspace_bytes(..., 0). */
+int ovc_beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N,
+                          int k, int out_size, void* workspace, size_t workspace_bytes,
+                          int64_t* ids_out, float* logp_out, int32_t* steps_out, ovc_stream stream);
+
 /* Teacher-forced forward and caption scoring: the reference's BaseTransformer.forward (models/base_transformer.py:26-30,
  * decoders.py:95-123) and what its dev-loss loop does with it (trainers/vi_trainer.py:56-76: NLLLoss(ignore_index = pad) against
  * the shifted-right captions).  tokens / targets [B, T] int64 device ids in [0, vocab) (refuse others on the host: the device reads

@@ -613,113 +613,12 @@ constexpr int kSelfMaxHeads = 32;
 // its KB blocks per lane before the wave reduction; KB = 1 is the round-1 kernel unchanged).
 template <int CH, int KB = 1>
 __global__ __launch_bounds__(256) void decode_self_attention_kernel(DecodeSelfArgs p) {
-    static_assert(KB * 64 <= 256, "phase 0 lists one position per thread");
-    __shared__ int slots[KB * 64];
-    __shared__ uint8_t pads[KB * 64];
-    __shared__ float sc[kSelfMaxHeads][KB * 64];
-    __shared__ __attribute__((aligned(16))) float red[256 * 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = blockIdx.x, t = p.t;
-    const int hk = p.h * p.dk;                       // == h * dv (checked on the host)
-
-    if (tid <= t) {
-        const int slot = tid == t ? r : p.anc[(size_t)r * p.anc_ld + tid];
-        slots[tid] = slot;
-        pads[tid] = p.padflag[(size_t)tid * p.pad_ld + slot];
-    }
-    int ecol[CH];
-    bool evalid[CH];
-    f32x4 q4[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const int e = c * 256 + lane * 4;
-        evalid[c] = e < hk;
-        ecol[c] = min(e, hk - 4);
-        q4[c] = *reinterpret_cast<const f32x4*>(p.q + (size_t)r * p.ldq + ecol[c]);
-        if (!evalid[c]) q4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    __syncthreads();
-
-    const int group = p.dk >> 2;                     // lanes per head: a power of two <= 16
-    const float scale_div = sqrtf((float)p.dk);
-    const int niter = (t - wave + 4) >> 2;           // keys wave, wave+4, ... <= t
-    for (int i0 = 0; i0 < niter; i0 += 4) {
-        f32x4 k4[4][CH];
-        int jj[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {                // four keys in flight per wave
-            jj[u] = min(wave + 4 * (i0 + u), t);
-            const float* krow = p.kcache + (size_t)jj[u] * p.pos_stride + (size_t)slots[jj[u]] * p.ldkv;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) k4[u][c] = *reinterpret_cast<const f32x4*>(krow + ecol[c]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool live = i0 + u < niter;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                float part = (q4[c][0] * k4[u][c][0] + q4[c][1] * k4[u][c][1]) + (q4[c][2] * k4[u][c][2] + q4[c][3] * k4[u][c][3]);
-                for (int off = 1; off < group; off <<= 1) part += __shfl_xor(part, off, 64);
-                if (live && evalid[c] && (lane & (group - 1)) == 0)
-                    sc[(c * 256 + lane * 4) / p.dk][jj[u]] = pads[jj[u]] ? -INFINITY : part / scale_div;
-            }
-        }
-    }
-    __syncthreads();
-
-    for (int hd = wave; hd < p.h; hd += 4) {
-        if constexpr (KB == 1) {
-            const float s = lane <= t ? sc[hd][lane] : -INFINITY;
-            const float mx = wave_max(s);
-            const float e = lane <= t ? expf(s - mx) : 0.f;
-            const float sum = wave_sum(e);
-            if (lane <= t) sc[hd][lane] = e / sum;
-        } else {                                     // keys lane, lane + 64, ...: per-lane max / sum first, then the wave's
-            float s[KB], e[KB], mx = -INFINITY, part = 0.f;
-#pragma unroll
-            for (int u = 0; u < KB; ++u) {
-                s[u] = lane + 64 * u <= t ? sc[hd][lane + 64 * u] : -INFINITY;
-                mx = fmaxf(mx, s[u]);
-            }
-            mx = wave_max(mx);
-#pragma unroll
-            for (int u = 0; u < KB; ++u) {
-                e[u] = lane + 64 * u <= t ? expf(s[u] - mx) : 0.f;
-                part += e[u];
-            }
-            const float sum = wave_sum(part);
-#pragma unroll
-            for (int u = 0; u < KB; ++u)
-                if (lane + 64 * u <= t) sc[hd][lane + 64 * u] = e[u] / sum;
-        }
-    }
-    __syncthreads();
-
-    const int cols = hk >> 2;                        // float4 columns of the output row (<= 256)
-    const int groups = 256 / cols;                   // key groups working in parallel
-    const int col = tid % cols, g = tid / cols;
-    const int hd = (col * 4) / p.dv;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    // keys g, g+groups, ... <= t (0 when g > t); threads past the last whole key group (256 % cols != 0) idle
-    const int nkeys = g < groups ? (t - g + groups) / groups : 0;
-    for (int i0 = 0; i0 < nkeys; i0 += 4) {
-        f32x4 v4[4];
-        int jj[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            jj[u] = min(g + groups * (i0 + u), t);
-            v4[u] = *reinterpret_cast<const f32x4*>(p.vcache + (size_t)jj[u] * p.pos_stride + (size_t)slots[jj[u]] * p.ldkv + col * 4);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i0 + u < nkeys) acc += v4[u] * sc[hd][jj[u]];
-    }
-    if (g > 0) *reinterpret_cast<f32x4*>(red + (size_t)tid * 4) = acc;
-    __syncthreads();
-    if (g == 0) {
-        for (int gg = 1; gg < groups; ++gg) acc += *reinterpret_cast<const f32x4*>(red + (size_t)(gg * cols + col) * 4);
-        *reinterpret_cast<f32x4*>(p.out + (size_t)r * p.ldo + col * 4) = acc;
-    }
+#include "bodies/decode_self_attention_kernel.inc"
+}
+template <int CH, int KB = 1>
+__global__ __launch_bounds__(256) void decode_self_attention_kernel_gated(DecodeSelfArgs p, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_self_attention_kernel.inc"
 }
 
 // Per-image form with ancestor de-duplication (round 3).  The k beams of an image descend from one another: at step t
@@ -744,212 +643,39 @@ __global__ __launch_bounds__(256) void decode_self_attention_kernel(DecodeSelfAr
 // unpadded key in the chunk writes M = -inf, L = 0, O = 0 (its exponentials are taken against 0, never -inf - -inf).
 template <int NT, int SB, bool CHUNKED = false>
 __global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel(DecodeSelfArgs p) {
-    constexpr int kPos = CHUNKED ? kSelfChunk : 64;      // positions the workgroup lists (one per lane of wave 0)
-    __shared__ unsigned short keyinfo[NT * 16];          // (position << 3) | local slot
-    __shared__ uint8_t keypad[NT * 16];
-    __shared__ uint8_t sl[OVC_MAX_BEAM][kPos];           // local slot of beam i at position j0 + j
-    __shared__ int nkeys_shared;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x, t = p.t, W = p.width;
-    const int j0 = CHUNKED ? (int)blockIdx.z * kSelfChunk : 0;
-    const int hd = min((int)blockIdx.y * 4 + wave, p.h - 1);
-    const bool live = (int)blockIdx.y * 4 + wave < p.h;          // surplus waves redo the last head, store nothing
-    const int r = lane & 15, kq = lane >> 4;
-
-    // this wave's query fragments (independent of the key list: in flight while wave 0 builds it)
-    const float* qg = p.q + (size_t)(b * W + min(r, W - 1)) * p.ldq + hd * p.dk;
-    f32x4 qf[SB];
-#pragma unroll
-    for (int S = 0; S < SB; ++S) qf[S] = *reinterpret_cast<const f32x4*>(qg + 16 * S + 4 * kq);
-
-    if (wave == 0) {
-        const int j = j0 + lane;
-        const int wj = j == 0 ? 1 : W;                        // slots of position j's cache block that belong to this image
-        int slot[OVC_MAX_BEAM];
-        uint8_t pad[OVC_MAX_BEAM];
-        unsigned mask = 0;
-        if (j <= t && lane < kPos) {
-#pragma unroll
-            for (int i = 0; i < OVC_MAX_BEAM; ++i)             // all loads first: ancestor slots and the block's <pad> flags
-                slot[i] = i < W ? (j == t ? i : p.anc[(size_t)(b * W + i) * p.anc_ld + j] - b * wj) : 0;
-#pragma unroll
-            for (int l = 0; l < OVC_MAX_BEAM; ++l) pad[l] = l < wj ? p.padflag[(size_t)j * p.pad_ld + b * wj + l] : 0;
-#pragma unroll
-            for (int i = 0; i < OVC_MAX_BEAM; ++i)
-                if (i < W) {
-                    const int s = min(max(slot[i], 0), wj - 1);   // a corrupt table can never index outside the image's block
-                    sl[i][j - j0] = (uint8_t)s;
-                    mask |= 1u << s;
-                }
-        }
-        const int cnt = __popc(mask);
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        int n = incl - cnt;
-#pragma unroll
-        for (int l = 0; l < OVC_MAX_BEAM; ++l)
-            if (mask & (1u << l)) {
-                if (n < NT * 16) { keyinfo[n] = (unsigned short)((j << 3) | l); keypad[n] = pad[l]; }
-                ++n;
-            }
-        if (lane == 63) nkeys_shared = min(incl, NT * 16);
-    }
-    __syncthreads();
-    const int nkeys = nkeys_shared;
-
-    // ---- K fragments of the listed keys: tile T holds keys 16 T .. 16 T + 15, lane r loads key 16 T + r -------------
-    f32x4 kf[NT][SB];
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        if (16 * T < nkeys) {                                  // wave-uniform
-            const int info = keyinfo[min(16 * T + r, nkeys - 1)];
-            const int j = info >> 3, l = info & 7;
-            const float* krow = p.kcache + (size_t)j * p.pos_stride + (size_t)(b * (j == 0 ? 1 : W) + l) * p.ldkv + hd * p.dk + 4 * kq;
-#pragma unroll
-            for (int S = 0; S < SB; ++S) kf[T][S] = *reinterpret_cast<const f32x4*>(krow + 16 * S);
-        }
-    }
-    if (r >= W) {
-#pragma unroll
-        for (int S = 0; S < SB; ++S) qf[S] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    f32x4 st[NT];
-#pragma unroll
-    for (int T = 0; T < NT; ++T) st[T] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        if (16 * T < nkeys) {
-#pragma unroll
-            for (int S = 0; S < SB; ++S)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) st[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[T][S][e], qf[S][e], st[T], 0, 0, 0);
-        }
-    }
-
-    // ---- V fragments (in flight during the softmax): lane (r, kq), register g <-> key 16 T + 4 kq + g, columns 4 r .. ----
-    const int vc = 4 * min(r, (p.dv >> 2) - 1);
-    f32x4 vf[NT][4];
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        if (16 * T < nkeys) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int info = keyinfo[min(16 * T + 4 * kq + g, nkeys - 1)];
-                const int j = info >> 3, l = info & 7;
-                vf[T][g] = *reinterpret_cast<const f32x4*>(p.vcache + (size_t)j * p.pos_stride +
-                                                           (size_t)(b * (j == 0 ? 1 : W) + l) * p.ldkv + hd * p.dv + vc);
-            }
-        }
-    }
-
-    // ---- scale, validity, softmax over the keys of this lane's beam column -------------------------------------------
-    const float scale_div = sqrtf((float)p.dk);
-    const int beam = min(r, W - 1);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int key = 16 * T + 4 * kq + g;
-            float s = -INFINITY;
-            if (key < nkeys) {
-                const int info = keyinfo[key];
-                if (!keypad[key] && sl[beam][(info >> 3) - j0] == (info & 7)) s = st[T][g] / scale_div;
-            }
-            st[T][g] = s;
-            mx = fmaxf(mx, s);
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mref = CHUNKED && mx == -INFINITY ? 0.f : mx;     // no key in this chunk: every exponential is exactly 0
-    float sum = 0.f;
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float e = expf(st[T][g] - mref);
-            st[T][g] = e;
-            sum += e;
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    if constexpr (!CHUNKED) {
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) st[T][g] = st[T][g] / sum;
-    }
-
-    // ---- O^T = V^T P^T -----------------------------------------------------------------------------------------------
-    f32x4 acc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        if (16 * T < nkeys) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[T][g][e], st[T][g], acc[e], 0, 0, 0);
-        }
-    }
-    if (live && r < W) {
-        float* orow;
-        if constexpr (CHUNKED) {
-            const size_t prow = (size_t)blockIdx.z * gridDim.x * W + b * W + r;     // [chunk][row]
-            orow = p.part_o + prow * p.h * p.dv + hd * p.dv;
-            if (kq == 0) reinterpret_cast<float2*>(p.part_ml)[prow * p.h + hd] = make_float2(mx, sum);
-        } else {
-            orow = p.out + (size_t)(b * W + r) * p.ldo + hd * p.dv;
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int dvb = 16 * kq + 4 * g;
-            if (dvb < p.dv) *reinterpret_cast<f32x4*>(orow + dvb) = f32x4{acc[0][g], acc[1][g], acc[2][g], acc[3][g]};
-        }
-    }
+#include "bodies/decode_self_attention_mfma_kernel.inc"
+}
+template <int NT, int SB, bool CHUNKED = false>
+__global__ __launch_bounds__(256) void decode_self_attention_mfma_kernel_gated(DecodeSelfArgs p, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_self_attention_mfma_kernel.inc"
 }
 
 // The chunks of one (row, head) in ascending order: M = max_c M_c, then L = sum_c L_c exp(M_c - M) and O likewise, one
 // division at the end (the order and the partition are functions of t alone: the bits do not depend on B or on the launch).
 // A chunk with L_c = 0 named no key for the beam and is passed over.  Thread = one float4 of an output row.
 __global__ __launch_bounds__(256) void decode_self_merge_kernel(DecodeSelfArgs p, int rows, int chunks) {
-    const int hv4 = (p.h * p.dv) >> 2;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * hv4) return;
-    const int row = idx / hv4, c4 = idx - row * hv4, hd = (c4 * 4) / p.dv;
-    const float2* ml = reinterpret_cast<const float2*>(p.part_ml);
-    const size_t hv = (size_t)p.h * p.dv;
-    float M = -INFINITY;
-    for (int c = 0; c < chunks; ++c) M = fmaxf(M, ml[((size_t)c * rows + row) * p.h + hd].x);
-    float L = 0.f;
-    f32x4 O = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < chunks; ++c) {
-        const float2 v = ml[((size_t)c * rows + row) * p.h + hd];
-        if (v.y > 0.f) {
-            const float w = expf(v.x - M);
-            L += v.y * w;
-            O += *reinterpret_cast<const f32x4*>(p.part_o + ((size_t)c * rows + row) * hv + c4 * 4) * w;
-        }
-    }
-    *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.ldo + c4 * 4) = O / L;
+#include "bodies/decode_self_merge_kernel.inc"
+}
+__global__ __launch_bounds__(256) void decode_self_merge_kernel_gated(DecodeSelfArgs p, int rows, int chunks, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_self_merge_kernel.inc"
 }
 
 // Steps t >= 64 (max_len up to OVC_MAX_LEN).  d_k >= 16: one workgroup per (image, 4 heads, chunk of kSelfChunk positions),
 // de-duplicated as above, then the merge.  d_k in {4, 8} (and the per-row A/B switch): the per-row kernel over 4 blocks of
 // 64 positions.  t < 64 never comes here, so the bits of those steps are the round-3 kernels'.
-static int decode_self_attention_long(const DecodeSelfArgs& p, int rows, bool per_row, hipStream_t stream) {
+static int decode_self_attention_long(const DecodeSelfArgs& p, int rows, bool per_row, hipStream_t stream, const int32_t* gate) {
     const int W = p.width, hk = p.h * p.dk;
     if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16) {
         if (!p.part_o || !p.part_ml) return OVC_EINVAL;
         const int chunks = (p.t + kSelfChunk) / kSelfChunk;
         const dim3 grid(rows / W, (p.h + 3) / 4, chunks), block(256);
-#define OVC_SELF(NT, SB) hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB, true>), grid, block, 0, stream, p)
+#define OVC_SELF(NT, SB)                                                                                             \
+    do {                                                                                                             \
+        if (gate) hipLaunchKernelGGL((decode_self_attention_mfma_kernel_gated<NT, SB, true>), grid, block, 0, stream, p, gate); \
+        else hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB, true>), grid, block, 0, stream, p);      \
+    } while (0)
 #define OVC_SELF_NT(SB)                                                                                             \
     do {                                                                                                            \
         if (W <= 1) OVC_SELF(1, SB); else if (W <= 2) OVC_SELF(2, SB); else if (W <= 4) OVC_SELF(4, SB);           \
@@ -960,30 +686,39 @@ static int decode_self_attention_long(const DecodeSelfArgs& p, int rows, bool pe
 #undef OVC_SELF
         OVC_RETURN_IF_LAUNCH_FAILED();
         const int threads = rows * ((p.h * p.dv) >> 2);
-        hipLaunchKernelGGL(decode_self_merge_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks);
+        if (gate) hipLaunchKernelGGL(decode_self_merge_kernel_gated, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks, gate);
+        else hipLaunchKernelGGL(decode_self_merge_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks);
         OVC_RETURN_IF_LAUNCH_FAILED();
         return OVC_OK;
     }
-    if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel<1, 4>), dim3(rows), dim3(256), 0, stream, p);
+    if (gate) {
+        if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel_gated<1, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
+        else if (hk <= 512) hipLaunchKernelGGL((decode_self_attention_kernel_gated<2, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
+        else hipLaunchKernelGGL((decode_self_attention_kernel_gated<4, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
+    } else if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel<1, 4>), dim3(rows), dim3(256), 0, stream, p);
     else if (hk <= 512) hipLaunchKernelGGL((decode_self_attention_kernel<2, 4>), dim3(rows), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((decode_self_attention_kernel<4, 4>), dim3(rows), dim3(256), 0, stream, p);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
 
-int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream) {
+int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream, const int32_t* gate) {
     const int hk = p.h * p.dk;
     if (p.t < 0 || p.t >= OVC_MAX_LEN || p.h <= 0 || p.h > kSelfMaxHeads) return OVC_EINVAL;
     if (p.dk != p.dv || (p.dk & (p.dk - 1)) || p.dk < 4 || p.dk > 64) return OVC_EINVAL;   // dk in {4,8,16,32,64}
     if (hk > 1024) return OVC_EINVAL;
     static const bool per_row = OVC_HOOK_ENV("OVC_SELF_ATTENTION_ROWS") != nullptr;     // A/B switch: the round-1 per-row kernel
     const int W = p.width;
-    if (p.t >= 64) return decode_self_attention_long(p, rows, per_row, stream);
+    if (p.t >= 64) return decode_self_attention_long(p, rows, per_row, stream, gate);
     // per-image kernel with ancestor de-duplication: the image's rows in one workgroup, at most 112 listed keys
     if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16 && (p.t == 0 ? 1 : W * (p.t + 1)) <= 112) {
         const int worst = p.t == 0 ? 1 : W * (p.t + 1), tiles = (worst + 15) / 16;
         const dim3 grid(rows / W, (p.h + 3) / 4), block(256);
-#define OVC_SELF(NT, SB) hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p)
+#define OVC_SELF(NT, SB)                                                                                             \
+    do {                                                                                                             \
+        if (gate) hipLaunchKernelGGL((decode_self_attention_mfma_kernel_gated<NT, SB>), grid, block, 0, stream, p, gate); \
+        else hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p);            \
+    } while (0)
 #define OVC_SELF_NT(SB)                                                                                             \
     do {                                                                                                            \
         if (tiles <= 1) OVC_SELF(1, SB); else if (tiles <= 2) OVC_SELF(2, SB); else if (tiles <= 4) OVC_SELF(4, SB); \
@@ -995,7 +730,11 @@ int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t str
         OVC_RETURN_IF_LAUNCH_FAILED();
         return OVC_OK;
     }
-    if (hk <= 256) hipLaunchKernelGGL(decode_self_attention_kernel<1>, dim3(rows), dim3(256), 0, stream, p);
+    if (gate) {
+        if (hk <= 256) hipLaunchKernelGGL(decode_self_attention_kernel_gated<1>, dim3(rows), dim3(256), 0, stream, p, gate);
+        else if (hk <= 512) hipLaunchKernelGGL(decode_self_attention_kernel_gated<2>, dim3(rows), dim3(256), 0, stream, p, gate);
+        else hipLaunchKernelGGL(decode_self_attention_kernel_gated<4>, dim3(rows), dim3(256), 0, stream, p, gate);
+    } else if (hk <= 256) hipLaunchKernelGGL(decode_self_attention_kernel<1>, dim3(rows), dim3(256), 0, stream, p);
     else if (hk <= 512) hipLaunchKernelGGL(decode_self_attention_kernel<2>, dim3(rows), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(decode_self_attention_kernel<4>, dim3(rows), dim3(256), 0, stream, p);
     OVC_RETURN_IF_LAUNCH_FAILED();
@@ -1021,118 +760,12 @@ int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t str
 // (hipcc branches around a guarded load and waits vmcnt(0) after it, serialising the whole K/V stream).
 template <int NT, int SB>
 __global__ __launch_bounds__(256) void decode_cross_attention_mfma_kernel(DecodeCrossArgs p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x, hd = min((int)blockIdx.y * 4 + wave, p.heads - 1), lvl = blockIdx.z;
-    const bool live = (int)blockIdx.y * 4 + wave < p.heads;      // surplus waves redo the last head, store nothing
-    const int N = p.n, W = p.width;
-    const int r = lane & 15, kq = lane >> 4;
-    const float* kg = p.kx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv + hd * p.dk;
-    const float* vg = p.vx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv + hd * p.dv;
-    const float* qg = p.q + (size_t)(b * W + min(r, W - 1)) * p.ldq + hd * p.dk;
-
-    // ---- all loads of the score phase, back to back -------------------------------------------------
-    f32x4 qf[SB], kf[NT][SB];
-#pragma unroll
-    for (int S = 0; S < SB; ++S) qf[S] = *reinterpret_cast<const f32x4*>(qg + 16 * S + 4 * kq);
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        const float* krow = kg + (size_t)min(16 * T + r, N - 1) * p.ldkv + 4 * kq;
-#pragma unroll
-        for (int S = 0; S < SB; ++S) kf[T][S] = *reinterpret_cast<const f32x4*>(krow + 16 * S);
-    }
-    // key mask bytes of this lane's keys (16 T + 4 kq + g); a dummy all-zero row when there is no mask
-    uint8_t mk[NT][4];
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) mk[T][g] = 0;
-    if (p.encmask) {                                   // uniform: one branch around all the byte loads
-        const uint8_t* mrow = p.encmask + (size_t)b * N;
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) mk[T][g] = mrow[min(16 * T + 4 * kq + g, N - 1)];
-    }
-    if (r >= W) {
-#pragma unroll
-        for (int S = 0; S < SB; ++S) qf[S] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    // NT independent accumulation chains, issued round-robin: a 16x16x4 MFMA can issue every 32 cycles but its result is
-    // only available to a dependent one after 40, so one chain at a time would stall on every instruction.  The sum
-    // over d inside each key tile keeps its order (S, then e).
-    f32x4 st[NT];
-#pragma unroll
-    for (int T = 0; T < NT; ++T) st[T] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int S = 0; S < SB; ++S)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int T = 0; T < NT; ++T) st[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[T][S][e], qf[S][e], st[T], 0, 0, 0);
-
-    // ---- V loads are issued before the softmax arithmetic so that they are in flight meanwhile ------------------
-    const int vc = 4 * min(r, (p.dv >> 2) - 1);
-    f32x4 vf[NT][4];
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            vf[T][g] = *reinterpret_cast<const f32x4*>(vg + (size_t)min(16 * T + 4 * kq + g, N - 1) * p.ldkv + vc);
-
-    // scale, mask, softmax over the keys of this lane's beam column
-    const float scale_div = sqrtf((float)p.dk);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int key = 16 * T + 4 * kq + g;
-            float s = st[T][g] / scale_div;
-            if (key >= N || mk[T][g]) s = -INFINITY;
-            st[T][g] = s;
-            mx = fmaxf(mx, s);
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float e = expf(st[T][g] - mx);
-            st[T][g] = e;
-            sum += e;
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) st[T][g] = st[T][g] / sum;
-
-    // O^T = V^T P^T (columns of V beyond d_v contribute to output rows that are never stored)
-    f32x4 acc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[T][g][e], st[T][g], acc[e], 0, 0, 0);
-
-    // acc[e][g] is O[beam = column][dv = 4 (4 kq + g) + e] where row 4 kq + g of the MFMA is the V column
-    // group loaded by lane r' = 4 kq + g: four consecutive dv per (lane, g)
-    if (live && r < W) {
-        float* orow = p.out + (size_t)lvl * p.out_level_stride + (size_t)(b * W + r) * p.ldo + hd * p.dv;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int dvb = 16 * kq + 4 * g;
-            if (dvb < p.dv) *reinterpret_cast<f32x4*>(orow + dvb) = f32x4{acc[0][g], acc[1][g], acc[2][g], acc[3][g]};
-        }
-    }
+#include "bodies/decode_cross_attention_mfma_kernel.inc"
+}
+template <int NT, int SB>
+__global__ __launch_bounds__(256) void decode_cross_attention_mfma_kernel_gated(DecodeCrossArgs p, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_cross_attention_mfma_kernel.inc"
 }
 
 // The same kernel for more than 128 regions (round 4; the reference has no limit): the keys pass through the wave in chunks
@@ -1141,113 +774,12 @@ __global__ __launch_bounds__(256) void decode_cross_attention_mfma_kernel(Decode
 // registers all belong to ITS beam).  Fixed chunk order: results depend on the operands only.  N <= 128 never comes here.
 template <int SB>
 __global__ __launch_bounds__(256) void decode_cross_attention_tiled_kernel(DecodeCrossArgs p) {
-    constexpr int NT = 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x, hd = min((int)blockIdx.y * 4 + wave, p.heads - 1), lvl = blockIdx.z;
-    const bool live = (int)blockIdx.y * 4 + wave < p.heads;
-    const int N = p.n, W = p.width;
-    const int r = lane & 15, kq = lane >> 4;
-    const float* kg = p.kx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv + hd * p.dk;
-    const float* vg = p.vx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv + hd * p.dv;
-    const float* qg = p.q + (size_t)(b * W + min(r, W - 1)) * p.ldq + hd * p.dk;
-    const uint8_t* mrow = p.encmask ? p.encmask + (size_t)b * N : nullptr;
-
-    f32x4 qf[SB];
-#pragma unroll
-    for (int S = 0; S < SB; ++S) qf[S] = *reinterpret_cast<const f32x4*>(qg + 16 * S + 4 * kq);
-    if (r >= W) {
-#pragma unroll
-        for (int S = 0; S < SB; ++S) qf[S] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const float scale_div = sqrtf((float)p.dk);
-    const int vc = 4 * min(r, (p.dv >> 2) - 1);
-    float m_run = -INFINITY, l_run = 0.f;
-    f32x4 acc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int k0 = 0; k0 < N; k0 += 16 * NT) {
-        f32x4 kf[NT][SB];
-#pragma unroll
-        for (int T = 0; T < NT; ++T) {
-            const float* krow = kg + (size_t)min(k0 + 16 * T + r, N - 1) * p.ldkv + 4 * kq;
-#pragma unroll
-            for (int S = 0; S < SB; ++S) kf[T][S] = *reinterpret_cast<const f32x4*>(krow + 16 * S);
-        }
-        uint8_t mk[NT][4];
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) mk[T][g] = 0;
-        if (mrow) {
-#pragma unroll
-            for (int T = 0; T < NT; ++T)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) mk[T][g] = mrow[min(k0 + 16 * T + 4 * kq + g, N - 1)];
-        }
-        f32x4 st[NT];
-#pragma unroll
-        for (int T = 0; T < NT; ++T) st[T] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int S = 0; S < SB; ++S)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int T = 0; T < NT; ++T) st[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[T][S][e], qf[S][e], st[T], 0, 0, 0);
-        f32x4 vf[NT][4];
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                vf[T][g] = *reinterpret_cast<const f32x4*>(vg + (size_t)min(k0 + 16 * T + 4 * kq + g, N - 1) * p.ldkv + vc);
-
-        float mx = -INFINITY;
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int key = k0 + 16 * T + 4 * kq + g;
-                float s = st[T][g] / scale_div;
-                if (key >= N || mk[T][g]) s = -INFINITY;
-                st[T][g] = s;
-                mx = fmaxf(mx, s);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const bool none = m_new == -INFINITY;
-        const float alpha = none ? 1.f : expf(m_run - m_new);
-        float sum = 0.f;
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float e = none ? 0.f : expf(st[T][g] - m_new);
-                st[T][g] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        l_run = l_run * alpha + sum;
-        m_run = m_new;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = acc[e] * alpha;
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[T][g][e], st[T][g], acc[e], 0, 0, 0);
-    }
-    if (live && r < W) {
-        float* orow = p.out + (size_t)lvl * p.out_level_stride + (size_t)(b * W + r) * p.ldo + hd * p.dv;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int dvb = 16 * kq + 4 * g;
-            if (dvb < p.dv)
-                *reinterpret_cast<f32x4*>(orow + dvb) = f32x4{acc[0][g] / l_run, acc[1][g] / l_run, acc[2][g] / l_run, acc[3][g] / l_run};
-        }
-    }
+#include "bodies/decode_cross_attention_tiled_kernel.inc"
+}
+template <int SB>
+__global__ __launch_bounds__(256) void decode_cross_attention_tiled_kernel_gated(DecodeCrossArgs p, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_cross_attention_tiled_kernel.inc"
 }
 
 // Head sizes 4 and 8 (not multiples of the 16-deep MFMA k block): VALU dots on LDS-staged rows.  The scores of all N keys
@@ -1255,108 +787,37 @@ __global__ __launch_bounds__(256) void decode_cross_attention_tiled_kernel(Decod
 // (round 4) and the sums keep the key order of the one-shot form.
 // Exercised by tests/test_engine_gpu.py::test_unusual_dimensions_against_oracle (d_k = 8 and d_k = 4 cases).
 constexpr int kCrossChunk = 128;
-__global__ __launch_bounds__(256) void decode_cross_attention_lds_kernel(DecodeCrossArgs p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x, hd = blockIdx.y, lvl = blockIdx.z;
-    const int N = p.n, W = p.width;
-    float* Xs = lds;                         // [128][68]: a chunk of K rows, later of V rows
-    float* qs = Xs + kCrossChunk * kLdQK;    // [W][64]
-    float* sc = qs + W * 64;                 // [W][N]
 
-    const float* kg = p.kx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv;
-    const float* vg = p.vx + (size_t)lvl * p.level_stride + (size_t)b * N * p.ldkv;
-    const int c4 = tid & 15, r0 = tid >> 4, col = c4 * 4;
-    for (int idx = tid; idx < W * 16; idx += 256) {
-        const int i = idx >> 4, cc = (idx & 15) * 4;
-        f32x4 qv = {0.f, 0.f, 0.f, 0.f};
-        if (cc < p.dk) qv = *reinterpret_cast<const f32x4*>(p.q + (size_t)(b * W + i) * p.ldq + hd * p.dk + cc);
-        *reinterpret_cast<f32x4*>(qs + i * 64 + cc) = qv;
-    }
-    const float scale_div = sqrtf((float)p.dk);
-    const int k4n = (p.dk + 3) >> 2;
-    for (int k0 = 0; k0 < N; k0 += kCrossChunk) {
-        const int nc = min(kCrossChunk, N - k0);
-        for (int r = r0; r < nc; r += 16) {
-            f32x4 kv = {0.f, 0.f, 0.f, 0.f};
-            if (col < p.dk) kv = *reinterpret_cast<const f32x4*>(kg + (size_t)(k0 + r) * p.ldkv + hd * p.dk + col);
-            *reinterpret_cast<f32x4*>(Xs + r * kLdQK + col) = kv;
-        }
-        __syncthreads();
-        for (int idx = tid; idx < W * nc; idx += 256) {
-            const int i = idx / nc, j = idx - i * nc;
-            const f32x4* kr = reinterpret_cast<const f32x4*>(Xs + j * kLdQK);
-            const f32x4* qr = reinterpret_cast<const f32x4*>(qs + i * 64);
-            float acc = 0.f;
-            for (int c = 0; c < k4n; ++c) {
-                const f32x4 a = qr[c], kk = kr[c];
-                acc += (a[0] * kk[0] + a[1] * kk[1]) + (a[2] * kk[2] + a[3] * kk[3]);
-            }
-            float s = acc / scale_div;
-            if (p.encmask && p.encmask[(size_t)b * N + k0 + j]) s = -INFINITY;
-            sc[i * N + k0 + j] = s;
-        }
-        __syncthreads();
-    }
-    for (int i = wave; i < W; i += 4) {
-        float mx = -INFINITY;
-        for (int j = lane; j < N; j += 64) mx = fmaxf(mx, sc[i * N + j]);
-        mx = wave_max(mx);
-        float sum = 0.f;
-        for (int j = lane; j < N; j += 64) {
-            const float e = expf(sc[i * N + j] - mx);
-            sc[i * N + j] = e;
-            sum += e;
-        }
-        sum = wave_sum(sum);
-        for (int j = lane; j < N; j += 64) sc[i * N + j] = sc[i * N + j] / sum;
-    }
-    // out[i][d] = sum_j P[i][j] V[j][d], j ascending; W * d_v <= 512 outputs: at most two per thread
-    const int nout = W * p.dv;
-    float acc[2] = {0.f, 0.f};
-    for (int k0 = 0; k0 < N; k0 += kCrossChunk) {
-        const int nc = min(kCrossChunk, N - k0);
-        __syncthreads();                                   // the probabilities are complete / the previous chunk is consumed
-        for (int r = r0; r < nc; r += 16) {
-            f32x4 vv = {0.f, 0.f, 0.f, 0.f};
-            if (col < p.dv) vv = *reinterpret_cast<const f32x4*>(vg + (size_t)(k0 + r) * p.ldkv + hd * p.dv + col);
-            *reinterpret_cast<f32x4*>(Xs + r * kLdQK + col) = vv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int idx = tid + 256 * u;
-            if (idx < nout) {
-                const int i = idx / p.dv, d = idx - i * p.dv;
-                for (int j = 0; j < nc; ++j) acc[u] += sc[i * N + k0 + j] * Xs[j * kLdQK + d];
-            }
-        }
-    }
-    float* og = p.out + (size_t)lvl * p.out_level_stride;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int idx = tid + 256 * u;
-        if (idx < nout) {
-            const int i = idx / p.dv, d = idx - i * p.dv;
-            og[(size_t)(b * W + i) * p.ldo + hd * p.dv + d] = acc[u];
-        }
-    }
+__global__ __launch_bounds__(256) void decode_cross_attention_lds_kernel(DecodeCrossArgs p) {
+#include "bodies/decode_cross_attention_lds_kernel.inc"
+}
+__global__ __launch_bounds__(256) void decode_cross_attention_lds_kernel_gated(DecodeCrossArgs p, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/decode_cross_attention_lds_kernel.inc"
 }
 
-int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int levels, hipStream_t stream) {
+int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int levels, hipStream_t stream, const int32_t* gate) {
     if (p.n <= 0 || p.n > OVC_MAX_REGIONS || p.width <= 0 || p.width > OVC_MAX_BEAM) return OVC_EINVAL;
     if (p.dk > 64 || p.dv > 64 || (p.dk & 3) || (p.dv & 3) || p.heads != h) return OVC_EINVAL;
     if (p.dk == 16 || p.dk == 32 || p.dk == 64) {
         const dim3 grid(B, (h + 3) / 4, levels), block(256);
         if (p.n > 128) {        // more regions than the register-resident instances hold: key chunks + online softmax
-            if (p.dk == 64) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<4>, grid, block, 0, stream, p);
+            if (gate) {
+                if (p.dk == 64) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<4>, grid, block, 0, stream, p, gate);
+                else if (p.dk == 32) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<2>, grid, block, 0, stream, p, gate);
+                else hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<1>, grid, block, 0, stream, p, gate);
+            } else if (p.dk == 64) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<4>, grid, block, 0, stream, p);
             else if (p.dk == 32) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<2>, grid, block, 0, stream, p);
             else hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<1>, grid, block, 0, stream, p);
             OVC_RETURN_IF_LAUNCH_FAILED();
             return OVC_OK;
         }
         const bool small = p.n <= 64;
-#define OVC_CROSS(NT, SB) hipLaunchKernelGGL((decode_cross_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p)
+#define OVC_CROSS(NT, SB)                                                                                            \
+    do {                                                                                                             \
+        if (gate) hipLaunchKernelGGL((decode_cross_attention_mfma_kernel_gated<NT, SB>), grid, block, 0, stream, p, gate); \
+        else hipLaunchKernelGGL((decode_cross_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p);           \
+    } while (0)
         if (p.dk == 64) { if (small) OVC_CROSS(4, 4); else OVC_CROSS(8, 4); }
         else if (p.dk == 32) { if (small) OVC_CROSS(4, 2); else OVC_CROSS(8, 2); }
         else { if (small) OVC_CROSS(4, 1); else OVC_CROSS(8, 1); }
@@ -1369,8 +830,11 @@ int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int level
     std::call_once(attr_once, [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel_gated),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    hipLaunchKernelGGL(decode_cross_attention_lds_kernel, dim3(B, h, levels), dim3(256), lds_bytes, stream, p);
+    if (gate) hipLaunchKernelGGL(decode_cross_attention_lds_kernel_gated, dim3(B, h, levels), dim3(256), lds_bytes, stream, p, gate);
+    else hipLaunchKernelGGL(decode_cross_attention_lds_kernel, dim3(B, h, levels), dim3(256), lds_bytes, stream, p);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

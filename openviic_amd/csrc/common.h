@@ -98,6 +98,14 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- device-side early exit (ovc_beam_search_gated) -------------------------------------------
+// A gated launch of decode step t >= 1 receives gate = &alive_count[t - 1], the number of beams still alive after step t - 1
+// (written by atomics in that step's update kernel: the kernel boundary orders it), and does nothing when it is 0.  The check
+// is the first statement of the gated instance: one scalar load, uniform over the workgroup, before any LDS access, barrier or
+// store.  Gated instances are separate kernels around the body of the ungated one, so every ungated instance keeps its
+// arguments and its code.
+__device__ __forceinline__ bool ovc_gate_closed(const int32_t* __restrict__ gate) { return *gate == 0; }
+
 // ---- internal GEMM interface (gemm.hip) ---------------------------------------------------
 struct GemmSegment {
     const float* W;      // [seg_n, K] row-major
@@ -150,6 +158,9 @@ struct GemmLaunchOpts {
     // here rather than in GemmArgs so that the kernel argument layout of every other instance stays as it is.
     const int32_t* tgt = nullptr;
     float* tgt_logit = nullptr;
+    // device-side early exit (ovc_beam_search_gated): the launch takes the GATED instance of its tiling, which reads *gate at
+    // entry and returns when it is 0 (fp32 classes only).  Carried here for the same reason as tgt.
+    const int32_t* gate = nullptr;
 };
 
 // Launches C = act([A1|A2] W^T + bias) + R on `stream`; returns an OVC_* code.
@@ -161,7 +172,11 @@ constexpr int kMaxKSplit = 4;
 // a K-split GEMM (rowops.hip).
 int ovc_layer_norm_parts(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
                          const float* gamma, const float* beta, const uint8_t* zero_rows, float eps, float* y,
-                         int rows, int d, hipStream_t stream);
+                         int rows, int d, hipStream_t stream, const int32_t* gate = nullptr);
+// ovc_layer_norm / ovc_sigmoid_gate (include/ovc.h) with a gate (nullptr: the ungated launch)
+int ovc_layer_norm_gated(const float* x, const float* residual, const float* gamma, const float* beta, const float* add, int add_rows,
+                         const uint8_t* zero_rows, float eps, float* y, int rows, int d, hipStream_t stream, const int32_t* gate);
+int ovc_sigmoid_gate_gated(const float* a, const float* g, float* y, long n, hipStream_t stream, const int32_t* gate);
 const char* ovc_gemm_tiling_name(int tiling);        // kernel name as rocprofv3 prints it
 
 // ---- decode-time attention (attention.hip) -------------------------------------------------
@@ -187,7 +202,7 @@ struct DecodeSelfArgs {
     float* part_ml;        // [chunks][rows][h]     float2 (running max M, sum L); M = -inf, L = 0 when the chunk names no key
 };
 constexpr int kSelfChunk = 16;        // positions per chunk of the t >= 64 decode self-attention (a function of t only)
-int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream);
+int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream, const int32_t* gate = nullptr);
 
 struct DecodeCrossArgs {
     const float* q;        // [B*width, ldq]
@@ -203,7 +218,7 @@ struct DecodeCrossArgs {
     size_t out_level_stride;
     int ldo;
 };
-int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int levels, hipStream_t stream);
+int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int levels, hipStream_t stream, const int32_t* gate = nullptr);
 
 // ---- beam search (beam.hip) ------------------------------------------------------------------
 struct BeamSelectArgs {
@@ -221,7 +236,7 @@ struct BeamSelectArgs {
     float* row_max_out;      // [B, width] or nullptr: log-softmax pieces for the update kernel
     float* row_lsum_out;
 };
-int ovc_beam_select_launch(const BeamSelectArgs& p, int B, hipStream_t stream);
+int ovc_beam_select_launch(const BeamSelectArgs& p, int B, hipStream_t stream, const int32_t* gate = nullptr);
 
 struct BeamUpdateArgs {
     const float* cand_v; const int* cand_i;         // [B*width, k] row candidates of ovc_beam_select_launch
@@ -242,13 +257,13 @@ struct BeamUpdateArgs {
     // zeroed by the caller before the first step.  0 = every later step only appends word 0 / log-prob 0 to every beam.
     int32_t* alive_count;
 };
-int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream);
+int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, const int32_t* gate = nullptr);
 // Selection + update in one launch from the vocabulary GEMM's block pieces (GemmArgs::stats, [rows][stats_ld] float2,
 // stats_ld even): no pass over the logits.  nblk = ceil(V / 32) <= 512; p.cand_* / p.row_max / p.row_lsum are not used.
 // Logit (row, word) lives at logits[row * ld_row + word * ld_word]: (ld, 1) for the row-major product, (1, ld) for the
 // transposed one.
 int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
-                                 long ld_row, long ld_word, int B, hipStream_t stream);
+                                 long ld_row, long ld_word, int B, hipStream_t stream, const int32_t* gate = nullptr);
 int ovc_debug_collect_winners_launch(const int32_t* anc, const int32_t* word, const float* running, int B, int width, int V, int k,
                                      int64_t* chosen, float* score, hipStream_t stream);
 int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const float* row_max, const float* row_lsum,
@@ -262,6 +277,12 @@ struct BeamFinalArgs {
                              // written and are emitted as word 0 / log-prob 0 -- what the remaining steps would have appended
 };
 int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream);
+// The final ordering of a gated search: the number of steps that ran, S, is read from the device -- S = 1 + the first i < T - 1
+// with alive_count[i] == 0, else T (step t >= 1 ran iff alive_count[t - 1] != 0) -- and the state is read from buf[S & 1] (dead
+// steps swap no buffers).  Positions S..T-1 are emitted as word 0 / log-prob 0, as BeamFinalArgs::steps_run does; block 0 writes
+// S to steps_out (nullptr: not wanted).  buf[i].steps_run is not read.
+int ovc_beam_finalize_gated_launch(const BeamFinalArgs (&buf)[2], const int32_t* alive_count, int32_t* steps_out, int B,
+                                   hipStream_t stream);
 int ovc_beam_gather_all_launch(const float* all_buf, const int* order, int B, int k, int T, int V, float* all_out,
                                hipStream_t stream);
 
@@ -273,4 +294,5 @@ int ovc_layer_norm_post_launch(const float* x, const float* residual, const floa
                                float* y, int rows, int d, hipStream_t stream);
 
 // out = (sum_l sigmoid(alpha[l]) * enc[l]) / divisor over `levels` stacked [n] blocks (rowops.hip)
-int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream);
+int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream,
+                   const int32_t* gate = nullptr);

@@ -443,6 +443,8 @@ struct Engine {
     int gemm_class;                                  // profiling bin (OVC_PROFILE_CLASSES)
     int kchains = 1;                                 // K-order class of the GEMMs issued next (set per call site group)
     std::vector<GemmShape>* dry = nullptr;           // shape enumeration: record every GEMM, launch nothing
+    const int32_t* gate = nullptr;                   // device-side early exit: the gate of every launch issued next (run_decode_step
+                                                     // sets it per step of a gated search; nullptr = ungated launches)
 
     // A weight segment; in the split-precision modes with the weight's pre-cut planes (ovc_lin::planes) when the host built them
     GemmSegment seg(const ovc_lin& l, float* C, const float* A2 = nullptr) const {
@@ -461,7 +463,9 @@ struct Engine {
             if (std::find(dry->begin(), dry->end(), sh) == dry->end()) dry->push_back(sh);
             return OVC_OK;
         }
-        if (!g_profile_on.load()) return ovc_gemm_launch(a, stream, launch);
+        GemmLaunchOpts gated = launch;
+        gated.gate = gate;
+        if (!g_profile_on.load()) return ovc_gemm_launch(a, stream, gated);
         std::lock_guard<std::mutex> lock(g_profile_mutex);
         if (g_profile.empty() && g_profile_empty.empty()) {
             // calibrate the bracket: event pairs with nothing in between
@@ -479,7 +483,7 @@ struct Engine {
         rec.cls = gemm_class;
         rec.tiling = ovc_gemm_pick_tiling(a);
         // kernel-scoped events: the dispatch's own begin / end timestamps (no marker latency in between)
-        GemmLaunchOpts opts = launch;
+        GemmLaunchOpts opts = gated;
         opts.start = rec.start; opts.stop = rec.stop;
         const int rc = ovc_gemm_launch(a, stream, opts);
         g_profile.push_back(rec);
@@ -505,7 +509,7 @@ struct Engine {
         if (split != 2 && split != 4) {
             TRY(linear(x, K, l, residual, y_tmp, M, d, 0));
             if (dry) return OVC_OK;
-            return ovc_layer_norm(y_tmp, nullptr, ln.g, ln.b, nullptr, 0, zero_rows, m->ln_eps, out, M, d, stream);
+            return ovc_layer_norm_gated(y_tmp, nullptr, ln.g, ln.b, nullptr, 0, zero_rows, m->ln_eps, out, M, d, stream, gate);
         }
         GemmArgs a{};
         a.A1 = x; a.lda1 = K; a.K1 = K; a.M = M; a.seg_n = d; a.nseg = 1; a.ldc = d;
@@ -514,7 +518,7 @@ struct Engine {
         TRY(gemm(a));
         if (dry) return OVC_OK;
         if (!(debug_skip() & 1))
-            TRY(ovc_layer_norm_parts(part, split, a.part_stride, l.b, residual, ln.g, ln.b, zero_rows, m->ln_eps, out, M, d, stream));
+            TRY(ovc_layer_norm_parts(part, split, a.part_stride, l.b, residual, ln.g, ln.b, zero_rows, m->ln_eps, out, M, d, stream, gate));
         for (int i = 0; i < extra_launches(); ++i) hipLaunchKernelGGL(noop_kernel, dim3(1), dim3(64), 0, stream);
         return OVC_OK;
     }
@@ -537,7 +541,7 @@ struct Engine {
             TRY(gemm(a));
         }
         if (dry) return OVC_OK;
-        return ovc_sigmoid_gate(info, gate, x, (long)M * d, stream);
+        return ovc_sigmoid_gate_gated(info, gate, x, (long)M * d, stream, this->gate);
     }
 
     int ffn(const ovc_ffn& w, const float* x, float* ff, float* y, float* part, float* out, const uint8_t* zero_rows, int M) {
@@ -683,8 +687,11 @@ int project_cross_kv(Engine& e, Workspace& w, int B, int N) {
     return OVC_OK;
 }
 
-int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int return_probs, bool count_alive = false) {
+// gated (ovc_beam_search_gated): every launch of step t >= 1 is gated on alive_count[t - 1] and the update counts live beams.
+int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int return_probs, bool count_alive = false, bool gated = false) {
     const ovc_model* m = e.m;
+    e.gate = gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
+    count_alive = count_alive || gated;
     hipStream_t s = e.stream;
     const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels, T = m->max_len;
     const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
@@ -720,7 +727,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
         sa.anc = w.anc[cur]; sa.anc_ld = T; sa.padflag = w.padflag; sa.pad_ld = R; sa.t = t; sa.width = width;
         sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = w.att; sa.ldo = hv;
         sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
-        if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s));
+        if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s, e.gate));
         TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, w.part, w.x1, rows));
         TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));
 
@@ -731,7 +738,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
         ca.kx = w.kx + (size_t)l * lv * B * N * hk; ca.vx = w.vx + (size_t)l * lv * B * N * hv;
         ca.level_stride = (size_t)B * N * hk; ca.ldkv = hk; ca.encmask = w.enc_mask; ca.n = N; ca.width = width;
         ca.heads = m->heads; ca.dk = m->d_k; ca.dv = m->d_v; ca.out = w.att; ca.out_level_stride = (size_t)rows * hv; ca.ldo = hv;
-        if (!(debug_skip() & 4)) RUN(ovc_decode_cross_attention(ca, B, m->heads, lv, s));
+        if (!(debug_skip() & 4)) RUN(ovc_decode_cross_attention(ca, B, m->heads, lv, s, e.gate));
         float* ffn_in;
         if (m->dec_kind == OVC_DEC_MESHED) {
             // decoders.py:51-73: one shared enc_attn per level, sigmoid-gated sum / sqrt(levels).  The levels'
@@ -744,13 +751,13 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
                 o.R = w.x1; o.ldr = d; o.res_mod = rows;
                 o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
                 TRY(e.gemm(o));
-                RUN(ovc_layer_norm(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                   w.enc_att, lv * rows, d, s));
+                RUN(ovc_layer_norm_gated(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                         w.enc_att, lv * rows, d, s, e.gate));
             } else {
                 for (int lvl = 0; lvl < lv; ++lvl) {      // AoA gates need the per-level pair (x1, enc_att_l)
                     TRY(e.linear(w.att + (size_t)lvl * rows * hv, hv, dl.cross_att.o, w.x1, w.y, rows, d, 0));
-                    RUN(ovc_layer_norm(w.y, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                       w.enc_att + lvl * nrd, rows, d, s));
+                    RUN(ovc_layer_norm_gated(w.y, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                             w.enc_att + lvl * nrd, rows, d, s, e.gate));
                     TRY(e.aoa(dl.cross_att, w.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
                 }
             }
@@ -769,7 +776,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
                 }
                 if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
             }
-            RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s));
+            RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s, e.gate));
             ffn_in = w.mixed;
         } else {
             TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, w.part, w.x2, rows));
@@ -836,7 +843,8 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
     if (fused_select) {
         // selection + bookkeeping in one launch, from the block pieces the vocabulary GEMM's epilogue left: no pass over the logits
         bu.row_max_out = return_probs ? w.row_max : nullptr; bu.row_lsum_out = return_probs ? w.row_lsum : nullptr;
-        if (!(debug_skip() & 8)) RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s));
+        if (!(debug_skip() & 8))
+            RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s, e.gate));
         if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
             RUN(ovc_masked_logp_launch(w.logits, ld_row, ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab,
                                        w.all_buf + (size_t)t * R * m->vocab, s));
@@ -848,8 +856,8 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
-    RUN(ovc_beam_select_launch(bs, B, s));
-    RUN(ovc_beam_update_launch(bu, B, s));
+    RUN(ovc_beam_select_launch(bs, B, s, e.gate));
+    RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
 }
 
@@ -1085,7 +1093,8 @@ extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const 
 namespace {
 struct GraphKey {
     uint64_t model_hash; const void* ws; int B, N, k, out_size;
-    int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp)
+    int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp),
+                                   // 2 = the gated search (ovc_beam_search_gated)
     bool operator<(const GraphKey& o) const {
         return std::tie(model_hash, ws, B, N, k, out_size, kind) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size, o.kind);
     }
@@ -1365,6 +1374,75 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
     TRY(ovc_beam_finalize_launch(bf, B, e.stream));
     if (steps_run_out) *steps_run_out = steps_run;
     return OVC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-side early exit (ovc_beam_search_gated).  ROCm's HIP has no conditional graph nodes, so the whole-search graph keeps
+// every node and the decision moves into the kernels: every launch of step t >= 1 is gated on alive_count[t - 1], the number
+// of beams still alive after step t - 1, which that step's update kernel counts (common.h, ovc_gate_closed).  Once it is 0 the
+// step's ~35 launches return at entry, and so do all later ones: a step that does not run leaves its count at the 0 the search
+// began with.  Step s* + 1 (s* = the first step after which no beam is alive) is NOT run, unlike the blocking path, which reads
+// the count one step late: every beam is then frozen, so the step would append word 0 / log-prob 0 and re-order the beams by
+// (score descending, beam ascending) -- the order the final ordering establishes anyway, ties included.
+// The final ordering takes the number of steps that ran from the device.  Nothing blocks the host; results equal
+// ovc_beam_search_graph's under ovc_beam_search_early's assumptions.
+// ---------------------------------------------------------------------------------------------
+namespace {
+int issue_gated_body(Engine& e, Workspace& w, int B, int N, int k) {
+    const int R = B * k, T = e.m->max_len;
+    TRY(run_encoder_layers(e, w, B, N));
+    TRY(project_cross_kv(e, w, B, N));
+    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    // this search's counts, in the graph: a count left by the previous replay must never open a gate
+    if (hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * T, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0, true, true));
+    e.gate = nullptr;
+    return OVC_OK;
+}
+}  // namespace
+
+extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, int32_t* steps_out, ovc_stream stream) {
+    if (!model_ok(m) || m->precision != 0 || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
+    if ((long)m->vocab < k) return OVC_EINVAL;
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    Workspace w = carve(m, workspace, B, N, k, 0);
+    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    const int T = m->max_len;
+
+    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
+    {
+        GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, k, out_size};
+        key.kind = 2;
+        std::lock_guard<std::mutex> lock(g_graph_mutex);
+        GraphEntry& entry = g_graphs[key];
+        entry.calls += 1;
+        entry.last_use = ++g_graph_tick;
+        entry.last_stream = e.stream;
+        evict_lru(&key, nullptr);
+        // first call of a shape: plain gated launches; from the second on ONE graph, captured on the private stream as
+        // ovc_beam_search_graph explains
+        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec &&
+            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }))
+            entry.unsupported = true;
+        if (entry.exec && !g_profile_on) {
+            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        } else {
+            TRY(issue_gated_body(e, w, B, N, k));
+        }
+    }
+    // the final ordering reads the step count from the device and writes the caller's buffers directly
+    BeamFinalArgs bf[2] = {};
+    for (int i = 0; i < 2; ++i) {
+        bf[i].running = w.running[i]; bf[i].hist = w.hist[i]; bf[i].lp = w.lp[i];
+        bf[i].k = k; bf[i].T = T; bf[i].out_size = out_size; bf[i].ids_out = ids_out; bf[i].logp_out = logp_out; bf[i].order_out = w.order;
+    }
+    return ovc_beam_finalize_gated_launch(bf, w.alive_count, steps_out, B, e.stream);
 }
 
 // ---------------------------------------------------------------------------------------------

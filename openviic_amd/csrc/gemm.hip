@@ -330,6 +330,17 @@ __global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void g
 #undef OVC_GEMM_F32_EPILOGUE
 }
 
+// The gated instance (GemmLaunchOpts::gate, ovc_beam_search_gated): gemm_f32_mfma behind the gate check.
+template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
+__global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void gemm_f32_mfma_gated(TileMap tmap, GemmArgs p,
+                                                                                                 const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#define OVC_GEMM_F32_EPILOGUE \
+    store_wave_tiles<Cfg::TM, Cfg::TN>(p, seg_bias, seg_C, acc[0], m0 + wm * Cfg::kWaveM, n0 + wn * Cfg::kWaveN, lane)
+#include "gemm_f32_body.inc"
+#undef OVC_GEMM_F32_EPILOGUE
+}
+
 // The scoring epilogue (GemmLaunchOpts::tgt_logit) of the transposed vocabulary product: one-chain instances only, the class that
 // product runs in.  Stores the block pieces and the target logits (store_wave_tiles_score), no C tile.
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
@@ -429,11 +440,6 @@ int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& o
         return launch_score_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, dim3(grid, 1, opts.copies > 1 ? opts.copies : 1),
                                                                lds_bytes);
     }
-    static std::once_flag attr_once;   // raise the dynamic-LDS cap once per process
-    std::call_once(attr_once, [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma<BM, BN, WM, WN, WK, BK, NC>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    });
     int group_m, xcd_pm;
     tile_order(a, tiles_m, tiles_n, &group_m, &xcd_pm);
     const int slices = a.ksplit > 1 ? a.ksplit : 1;         // K slices run one after the other (gridDim.y is the slow index)
@@ -441,6 +447,25 @@ int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& o
     // opts.copies (tuner only): gridDim.z identical copies of the product in one launch (the kernel ignores
     // blockIdx.z), a proxy for "this many batches in flight" that needs no extra streams.
     const dim3 grid3(grid, slices, opts.copies > 1 ? opts.copies : 1);
+    if (opts.gate) {
+        static std::once_flag gated_attr_once;
+        std::call_once(gated_attr_once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_gated<BM, BN, WM, WN, WK, BK, NC>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        });
+        if (opts.start && opts.stop)
+            hipExtLaunchKernelGGL((gemm_f32_mfma_gated<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), (uint32_t)lds_bytes, stream,
+                                  opts.start, opts.stop, 0, map, a, opts.gate);
+        else
+            hipLaunchKernelGGL((gemm_f32_mfma_gated<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), lds_bytes, stream, map, a, opts.gate);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        return OVC_OK;
+    }
+    static std::once_flag attr_once;   // raise the dynamic-LDS cap once per process
+    std::call_once(attr_once, [&] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma<BM, BN, WM, WN, WK, BK, NC>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    });
     if (opts.start && opts.stop)     // kernel-scoped events: the dispatch packet's own begin / end timestamps
         hipExtLaunchKernelGGL((gemm_f32_mfma<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), (uint32_t)lds_bytes, stream,
                               opts.start, opts.stop, 0, map, a);
@@ -490,6 +515,20 @@ int launch_rows16_config(const GemmArgs& a, hipStream_t stream, const GemmLaunch
     });
     const int kslice = a.K1 / (a.ksplit > 1 ? a.ksplit : 1);
     const dim3 grid3(tiles_n * a.nseg, tiles_m * (opts.copies > 1 ? opts.copies : 1), a.ksplit > 1 ? a.ksplit : 1);
+    if (opts.gate) {
+        static std::once_flag gated_attr_once;
+        std::call_once(gated_attr_once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows16_f32_gated<NB>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds_bytes);
+        });
+        if (opts.start && opts.stop)
+            hipExtLaunchKernelGGL((gemm_rows16_f32_gated<NB>), grid3, dim3(256), (uint32_t)lds_bytes, stream, opts.start, opts.stop, 0, a,
+                                  tiles_m, tiles_n, kslice, opts.gate);
+        else
+            hipLaunchKernelGGL((gemm_rows16_f32_gated<NB>), grid3, dim3(256), lds_bytes, stream, a, tiles_m, tiles_n, kslice, opts.gate);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        return OVC_OK;
+    }
     if (opts.start && opts.stop)
         hipExtLaunchKernelGGL((gemm_rows16_f32<NB>), grid3, dim3(256), (uint32_t)lds_bytes, stream, opts.start, opts.stop, 0, a, tiles_m, tiles_n, kslice);
     else
@@ -697,6 +736,8 @@ int ovc_gemm_launch(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts&
     if (a.stats_t && (a.stats || a.seg[0].bias || a.nseg != 1 || a.ksplit > 1 || !ovc_aligned16(a.stats_t) || a.stats_ld < (a.M + 31) / 32)) return OVC_EINVAL;
     // scoring epilogue (gemm_f32_mfma_score): a transposed product with its block pieces, one-chain class, no K split
     if (opts.tgt_logit && (!opts.tgt || !a.stats_t || args_chains(a) != 1)) return OVC_EINVAL;
+    // gated instances (device-side early exit): the fp32 classes, never with the scoring epilogue
+    if (opts.gate && (opts.tgt_logit || a.kchains > kSplitClass)) return OVC_EINVAL;
     if (a.K2 > 0 && (a.K1 % 32)) return OVC_EINVAL;      // the A1|A2 seam must fall on a K-tile boundary
     if (a.ksplit > 1) {                                  // raw partial products: see GemmArgs::ksplit
         if (a.ksplit > kMaxKSplit || a.nseg != 1 || a.K2 || a.R || a.act || a.seg[0].bias) return OVC_EINVAL;

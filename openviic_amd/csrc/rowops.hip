@@ -24,95 +24,42 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxVec = 8;   // float4 per lane -> d <= 2048
 
+#define OVC_LN_PARAMS                                                                                                          \
+    const float* __restrict__ x, long part_stride, const float* __restrict__ bias, const float* __restrict__ residual,           \
+        const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ add, int add_rows,            \
+        const uint8_t* __restrict__ zero_rows, float eps, float* __restrict__ y, int rows, int d
+#define OVC_LN_ARGS x, part_stride, bias, residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d
 template <int kVecs, int kParts, bool kBias, bool kRes, int kPostTenths = 0>
-__global__ __launch_bounds__(256) void layer_norm_rows(const float* __restrict__ x, long part_stride,
-                                                       const float* __restrict__ bias, const float* __restrict__ residual,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       const float* __restrict__ add, int add_rows,
-                                                       const uint8_t* __restrict__ zero_rows, float eps,
-                                                       float* __restrict__ y, int rows, int d) {
-    // every argument in ONE scalar round trip (hipcc otherwise fetches `rows` for the guard below first and the pointers in a
-    // second, dependent round: the kernel is nothing but a chain of round trips -- gemm.hip, round 4)
-    asm volatile("" ::"s"(x), "s"(part_stride), "s"(bias), "s"(residual), "s"(gamma), "s"(beta), "s"(add), "s"(add_rows), "s"(zero_rows),
-                 "s"(eps), "s"(y), "s"(rows), "s"(d));
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = d >> 2;
-    float* yrow = y + (size_t)row * d;
-    // The row's "write zeros instead" flag travels WITH the row's loads and is applied as a select on the way out.  (Until round 4
-    // this was an early `if (cleared) { store zeros; return; }` behind the loads in the source -- hipcc moved the test in front of
-    // them and waited for the byte: one whole extra round trip in every launch that takes the flags.)
-    // (an unconditional load from an always-valid address: a load inside `if (zero_rows)` gets a full s_waitcnt at the join)
-    const uint8_t cleared_byte = *(zero_rows ? zero_rows + row : reinterpret_cast<const uint8_t*>(gamma));
-    const bool cleared = zero_rows != nullptr && cleared_byte != 0;
-    // column group of (lane, i), clamped in-range: out-of-range lanes load a valid address and are masked later
-    int col[kVecs];
-#pragma unroll
-    for (int i = 0; i < kVecs; ++i) col[i] = min(lane + i * 64, nvec - 1);
-    f32x4 part[kParts][kVecs], bv[kVecs], rv[kVecs];
-#pragma unroll
-    for (int s = 0; s < kParts; ++s)
-#pragma unroll
-        for (int i = 0; i < kVecs; ++i)
-            part[s][i] = reinterpret_cast<const f32x4*>(x + s * part_stride + (size_t)row * d)[col[i]];
-    if (kBias) {
-#pragma unroll
-        for (int i = 0; i < kVecs; ++i) bv[i] = reinterpret_cast<const f32x4*>(bias)[col[i]];
-    }
-    if (kRes) {
-#pragma unroll
-        for (int i = 0; i < kVecs; ++i) rv[i] = reinterpret_cast<const f32x4*>(residual + (size_t)row * d)[col[i]];
-    }
-    // gamma / beta do not depend on the row's moments: fetched now, not after them (one memory round trip less
-    // on a kernel that is nothing but a chain of them)
-    f32x4 gv[kVecs], bev[kVecs];
-#pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-        gv[i] = reinterpret_cast<const f32x4*>(gamma)[col[i]];
-        bev[i] = reinterpret_cast<const f32x4*>(beta)[col[i]];
-    }
-    f32x4 v[kVecs];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-        v[i] = part[0][i];
-#pragma unroll
-        for (int s = 1; s < kParts; ++s) v[i] += part[s][i];
-        if (kBias) v[i] += bv[i];
-        if (kRes) v[i] += rv[i];
-        if (lane + i * 64 < nvec) sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-    const float mean = wave_sum(sum) / (float)d;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-        if (lane + i * 64 < nvec) {
-            const f32x4 t = v[i] - mean;
-            sq += (t[0] * t[0] + t[1] * t[1]) + (t[2] * t[2] + t[3] * t[3]);
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)d + eps);
-    const f32x4* ar = add ? reinterpret_cast<const f32x4*>(add + (size_t)(row % add_rows) * d) : nullptr;
-#pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-        const int c = lane + i * 64;
-        if (c < nvec) {
-            f32x4 o = (v[i] - mean) * rstd * gv[i] + bev[i];
-            if (ar) o += ar[c];
-            if constexpr (kPostTenths > 0) o = ((float)kPostTenths / 10.f) * o + rv[i];
-            if (cleared) o = f32x4{0.f, 0.f, 0.f, 0.f};
-            reinterpret_cast<f32x4*>(yrow)[c] = o;
-        }
-    }
+__global__ __launch_bounds__(256) void layer_norm_rows(OVC_LN_PARAMS) {
+#include "bodies/layer_norm_rows.inc"
 }
+
+// The gated instance (ovc_beam_search_gated: common.h, ovc_gate_closed).
+template <int kVecs, int kParts, bool kBias, bool kRes>
+__global__ __launch_bounds__(256) void layer_norm_rows_gated(OVC_LN_PARAMS, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+    constexpr int kPostTenths = 0;
+#include "bodies/layer_norm_rows.inc"
+}
+#undef OVC_LN_PARAMS
+#undef OVC_LN_ARGS
 
 template <int kParts, bool kBias, bool kRes, int kPostTenths = 0>
 int launch_layer_norm(const float* x, long part_stride, const float* bias, const float* residual, const float* gamma,
                       const float* beta, const float* add, int add_rows, const uint8_t* zero_rows, float eps, float* y,
-                      int rows, int d, hipStream_t stream) {
+                      int rows, int d, hipStream_t stream, const int32_t* gate = nullptr) {
     const int vecs = ((d >> 2) + 63) / 64;
     const dim3 grid((rows + 3) / 4), block(256);
+    if constexpr (kPostTenths == 0) {
+        if (gate) {
+#define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows_gated<V, kParts, kBias, kRes>), grid, block, 0, stream, x, part_stride, bias, \
+                                     residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, gate)
+            if (vecs <= 1) OVC_LN(1); else if (vecs <= 2) OVC_LN(2); else if (vecs <= 4) OVC_LN(4); else OVC_LN(8);
+#undef OVC_LN
+            OVC_RETURN_IF_LAUNCH_FAILED();
+            return OVC_OK;
+        }
+    }
 #define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows<V, kParts, kBias, kRes, kPostTenths>), grid, block, 0, stream, x, part_stride, bias, \
                                      residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d)
     if (vecs <= 1) OVC_LN(1); else if (vecs <= 2) OVC_LN(2); else if (vecs <= 4) OVC_LN(4); else OVC_LN(8);
@@ -184,14 +131,14 @@ __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ 
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+
 __global__ void sigmoid_gate_kernel(const float* __restrict__ a, const float* __restrict__ g, float* __restrict__ y, long n4) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const f32x4 av = reinterpret_cast<const f32x4*>(a)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = av[j] * sigmoidf_(gv[j]);
-        reinterpret_cast<f32x4*>(y)[i] = o;
-    }
+#include "bodies/sigmoid_gate.inc"
+}
+__global__ void sigmoid_gate_kernel_gated(const float* __restrict__ a, const float* __restrict__ g, float* __restrict__ y, long n4,
+                                          const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/sigmoid_gate.inc"
 }
 
 __global__ void gated_accumulate_kernel(const float* __restrict__ acc_in, const float* __restrict__ alpha,
@@ -209,18 +156,12 @@ __global__ void gated_accumulate_kernel(const float* __restrict__ acc_in, const 
 // reference's order; alpha and enc are [levels][n] stacked.
 __global__ void meshed_mix_kernel(const float* __restrict__ alpha, const float* __restrict__ enc, int levels, long n4,
                                   float divisor, float* __restrict__ out) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int l = 0; l < levels; ++l) {
-            const f32x4 al = reinterpret_cast<const f32x4*>(alpha)[(size_t)l * n4 + i];
-            const f32x4 xv = reinterpret_cast<const f32x4*>(enc)[(size_t)l * n4 + i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = acc[j] + sigmoidf_(al[j]) * xv[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = acc[j] / divisor;
-        reinterpret_cast<f32x4*>(out)[i] = acc;
-    }
+#include "bodies/meshed_mix.inc"
+}
+__global__ void meshed_mix_kernel_gated(const float* __restrict__ alpha, const float* __restrict__ enc, int levels, long n4,
+                                        float divisor, float* __restrict__ out, const int32_t* __restrict__ gate) {
+    if (ovc_gate_closed(gate)) return;
+#include "bodies/meshed_mix.inc"
 }
 
 // y = x - logsumexp(x) per row; one 256-thread block per row (rows of ~10k vocabulary entries).
@@ -322,26 +263,30 @@ extern "C" int ovc_layer_norm_post(const float* x, const float* residual, const 
     return ovc_layer_norm_post_launch(x, residual, gamma, beta, eps, alpha, y, rows, d, ovc_hip_stream(stream));
 }
 
-extern "C" int ovc_layer_norm(const float* x, const float* residual, const float* gamma, const float* beta,
-                              const float* add, int add_rows, const uint8_t* zero_rows, float eps,
-                              float* y, int rows, int d, ovc_stream stream) {
+int ovc_layer_norm_gated(const float* x, const float* residual, const float* gamma, const float* beta, const float* add, int add_rows,
+                         const uint8_t* zero_rows, float eps, float* y, int rows, int d, hipStream_t s, const int32_t* gate) {
     if (!x || !gamma || !beta || !y || rows <= 0 || d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
     if (add && add_rows <= 0) return OVC_EINVAL;
     if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
     if (!ovc_aligned16(x) || !ovc_aligned16(y) || !ovc_aligned16(gamma) || !ovc_aligned16(beta) ||
         (residual && !ovc_aligned16(residual)) || (add && !ovc_aligned16(add))) return OVC_EINVAL;
-    hipStream_t s = ovc_hip_stream(stream);
-    return residual ? launch_layer_norm<1, false, true>(x, 0L, nullptr, residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, s)
-                    : launch_layer_norm<1, false, false>(x, 0L, nullptr, nullptr, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, s);
+    return residual ? launch_layer_norm<1, false, true>(x, 0L, nullptr, residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, s, gate)
+                    : launch_layer_norm<1, false, false>(x, 0L, nullptr, nullptr, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, s, gate);
+}
+
+extern "C" int ovc_layer_norm(const float* x, const float* residual, const float* gamma, const float* beta,
+                              const float* add, int add_rows, const uint8_t* zero_rows, float eps,
+                              float* y, int rows, int d, ovc_stream stream) {
+    return ovc_layer_norm_gated(x, residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, ovc_hip_stream(stream), nullptr);
 }
 
 int ovc_layer_norm_parts(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
                          const float* gamma, const float* beta, const uint8_t* zero_rows, float eps, float* y,
-                         int rows, int d, hipStream_t stream) {
+                         int rows, int d, hipStream_t stream, const int32_t* gate) {
     if (!parts || !bias || !residual || !gamma || !beta || !y || rows <= 0 || d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
     if ((part_stride & 3) || !ovc_aligned16(parts) || !ovc_aligned16(y) || !ovc_aligned16(bias) || !ovc_aligned16(residual)) return OVC_EINVAL;
-    if (nparts == 2) return launch_layer_norm<2, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream);
-    if (nparts == 4) return launch_layer_norm<4, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream);
+    if (nparts == 2) return launch_layer_norm<2, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
+    if (nparts == 4) return launch_layer_norm<4, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
     return OVC_EINVAL;
 }
 
@@ -381,12 +326,17 @@ static inline int elementwise_grid(long n4) {
     return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
 }
 
-extern "C" int ovc_sigmoid_gate(const float* a, const float* g, float* y, long n, ovc_stream stream) {
+int ovc_sigmoid_gate_gated(const float* a, const float* g, float* y, long n, hipStream_t s, const int32_t* gate) {
     if (!a || !g || !y || n <= 0 || (n & 3) || !ovc_aligned16(a) || !ovc_aligned16(g) || !ovc_aligned16(y)) return OVC_EINVAL;
     if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
-    hipLaunchKernelGGL(sigmoid_gate_kernel, dim3(elementwise_grid(n / 4)), dim3(256), 0, ovc_hip_stream(stream), a, g, y, n / 4);
+    if (gate) hipLaunchKernelGGL(sigmoid_gate_kernel_gated, dim3(elementwise_grid(n / 4)), dim3(256), 0, s, a, g, y, n / 4, gate);
+    else hipLaunchKernelGGL(sigmoid_gate_kernel, dim3(elementwise_grid(n / 4)), dim3(256), 0, s, a, g, y, n / 4);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+extern "C" int ovc_sigmoid_gate(const float* a, const float* g, float* y, long n, ovc_stream stream) {
+    return ovc_sigmoid_gate_gated(a, g, y, n, ovc_hip_stream(stream), nullptr);
 }
 
 extern "C" int ovc_gated_accumulate(const float* acc_in, const float* alpha, const float* x, float divisor,
@@ -400,9 +350,12 @@ extern "C" int ovc_gated_accumulate(const float* acc_in, const float* alpha, con
     return OVC_OK;
 }
 
-int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream) {
+int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream,
+                   const int32_t* gate) {
     if (!alpha || !enc || !out || levels <= 0 || n <= 0 || (n & 3)) return OVC_EINVAL;
-    hipLaunchKernelGGL(meshed_mix_kernel, dim3(elementwise_grid(n / 4)), dim3(256), 0, stream, alpha, enc, levels, n / 4, divisor, out);
+    if (gate) hipLaunchKernelGGL(meshed_mix_kernel_gated, dim3(elementwise_grid(n / 4)), dim3(256), 0, stream, alpha, enc, levels, n / 4, divisor,
+                                 out, gate);
+    else hipLaunchKernelGGL(meshed_mix_kernel, dim3(elementwise_grid(n / 4)), dim3(256), 0, stream, alpha, enc, levels, n / 4, divisor, out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

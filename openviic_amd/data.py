@@ -219,7 +219,7 @@ def feature_file_loader(paths: Sequence[str], batch_size: int, workers: int, key
 
 def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, beam_size: int = 5, slots: Optional[int] = None,
                           keys: Optional[Iterable[str]] = None, trusted: bool = False, workers: int = 0,
-                          loader_context="forkserver", early_exit: bool = False, direct: bool = True):
+                          loader_context="forkserver", early_exit=False, direct: bool = True):
     """The reference's prediction loop (``trainers/vi_trainer.py:241-252``: per batch ``items.to(device)`` ->
     ``model.beam_search(items, batch_size, beam_size, out_size=1)`` -> ``decode_caption`` -> duplicate collapse) as a
     software pipeline on ONE host thread:
@@ -260,7 +260,9 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
     ``early_exit=True``: decode with ``ovc_beam_search_early`` -- no step is issued once every beam of the batch has ended (real
     captions end well before ``max_len``); same strings.  That call blocks the launching thread until its batch is one step
     from done, so each slot's search runs on its own host thread (the call is one C function: the GIL is released for all of it)
-    and the slots keep overlapping.
+    and the slots keep overlapping.  ``early_exit="device"``: decode with ``ovc_beam_search_gated`` -- the steps after the last
+    live beam are skipped on the device, inside the batch's one graph; same strings.  That call does not block, so every slot is
+    issued from the launching thread, as without early exit (no thread pool).
 
     ``slots``: batches in flight, each on its own decode stream.  Default 4: a small batch is a chain of ~730 dependent launches
     of a few workgroups each -- four of them overlap almost freely (B = 1, files -> strings, 8 workers: 430 captions/s with two
@@ -299,8 +301,10 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
             done.record(decode_streams[slot])
         return names, ids_host, done
 
+    from .engine import early_exit_mode
+    early_exit = early_exit_mode(early_exit)
     searchers = None
-    if early_exit and slots > 1:
+    if early_exit is True and slots > 1:             # only the blocking mode needs a host thread per slot
         from concurrent.futures import ThreadPoolExecutor
         searchers = ThreadPoolExecutor(max_workers=slots, thread_name_prefix="ovc-search")
 

@@ -91,6 +91,26 @@ def check_caption_ids(ids, name, batch, max_len, vocab):
     return T
 
 
+EARLY_EXIT_MODES = (False, True, "device")
+
+
+def early_exit_mode(value):
+    """The early-exit mode a ``beam_search(early_exit=...)`` value / ``OVC_EARLY_EXIT`` names: ``None`` / ``False`` -> ``False``
+    (the whole-search graph, every step), ``True`` -> ``True`` (``ovc_beam_search_early``: the host stops issuing steps, the call
+    blocks), ``"device"`` -> ``"device"`` (``ovc_beam_search_gated``: one graph whose launches skip the dead steps on the device,
+    non-blocking).  Anything else raises ``OvcError``."""
+    if value is None or value is False:
+        return False
+    if value is True or (isinstance(value, str) and value == "device"):
+        return value
+    raise native.OvcError("early_exit must be one of None, False, True or 'device' (got {!r})".format(value))
+
+
+def _early_exit_from_env(value):
+    """OVC_EARLY_EXIT: "0" (default) off, "device" the device-side mode, any other value the host-driven one."""
+    return "device" if value == "device" else value != "0"
+
+
 def _norm(dst, ln):
     dst.g, dst.b = _p(ln.weight.detach()), _p(ln.bias.detach())
 
@@ -139,8 +159,10 @@ class CaptionEngine:
     # stop issuing decode steps once every beam of every image has ended (ovc_beam_search_early: identical results, but the call
     # blocks the host thread until the search is one step from its end -- use one host thread per stream to overlap batches).
     # Pays for real captions (they end well before max_len); random-weight benchmarks never emit <eos>.  Per call:
-    # beam_search(..., early_exit=True).
-    early_exit = os.environ.get("OVC_EARLY_EXIT", "0") != "0"
+    # beam_search(..., early_exit=True).  "device" (OVC_EARLY_EXIT=device): ovc_beam_search_gated -- the same results from ONE
+    # graph whose launches return at entry once every beam has ended; nothing blocks, so one host thread drives every stream.
+    # self.last_steps_device then holds the steps that ran (a one-element int32 device tensor per workspace).
+    early_exit = _early_exit_from_env(os.environ.get("OVC_EARLY_EXIT", "0"))
 
     def __init__(self, model, tune_concurrency=None, precision=None):
         self.lib = native.load()
@@ -160,6 +182,8 @@ class CaptionEngine:
         # the teacher-forced forward's and the scoring's own, per (stream, logp wanted): a dev-loss pass between two searches
         # leaves the search's buffer -- whose address keys its captured graphs -- where it is
         self._fw_workspaces = {}
+        self._steps_device = {}  # early_exit="device": the step count of each search workspace (keyed like _workspaces)
+        self.last_steps_device = None
         self._tuned = set()
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
@@ -368,6 +392,7 @@ class CaptionEngine:
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._workspaces = {}
         self._fw_workspaces = {}
+        self._steps_device = {}
 
     def __del__(self):
         try:
@@ -439,8 +464,14 @@ class CaptionEngine:
         return features, boxes
 
     def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None):
-        """``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above; ``self.last_steps_run`` then holds the
-        number of decode steps that were issued for the call."""
+        """``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above and ``early_exit_mode``.  ``True``:
+        ``self.last_steps_run`` then holds the number of decode steps that were issued for the call.  ``"device"``:
+        ``self.last_steps_device`` is a one-element int32 device tensor (one per workspace, i.e. per stream) that receives, in
+        stream order, the number of decode steps that did work; ``last_steps_run`` stays ``max_len``.  With ``return_probs``
+        every mode runs the full search."""
+        early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
+        if early == "device" and self.precision != "f32":
+            raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
         features, boxes = self._checked_inputs(features, boxes)
         features, boxes = self._bucketed(features, boxes)
         B, N = features.shape[:2]
@@ -455,9 +486,20 @@ class CaptionEngine:
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         everything = torch.empty(B, beam_size, T, V, dtype=torch.float32, device=self.device) if return_probs else None
-        early = self.early_exit if early_exit is None else bool(early_exit)
         self.last_steps_run = T
-        if early and not return_probs:
+        if early == "device" and not return_probs:
+            key = torch.cuda.current_stream().cuda_stream
+            steps = self._steps_device.get(key)
+            if steps is None:
+                steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if not self.use_graph:       # OVC_GRAPH=0: every call is the first of its shape (plain gated launches)
+                self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+            check(self.lib.ovc_beam_search_gated(ctypes.byref(d), features.data_ptr(),
+                                                 None if boxes is None else boxes.data_ptr(), B, N, beam_size, out_size,
+                                                 ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(), steps.data_ptr(),
+                                                 native.stream_handle()), "ovc_beam_search_gated")
+            self.last_steps_device = steps
+        elif early and not return_probs:
             steps = ctypes.c_int(0)
             check(self.lib.ovc_beam_search_early(ctypes.byref(d), features.data_ptr(),
                                                  None if boxes is None else boxes.data_ptr(), B, N, beam_size, out_size,

@@ -123,6 +123,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     "ovc_beam_search_early": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                       c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "ovc_beam_search_gated": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "ovc_forward_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_forward": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                             c_void_p, c_void_p, c_int, c_void_p]),

@@ -326,6 +326,30 @@ int ovc_forward(const ovc_model* m, const float* features, const float* boxes, i
                 const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* logp_out, float* token_logp_out,
                 int use_graph, ovc_stream stream);
 
+/* Training step of the reference's cross-entropy loss (vi_trainer.py:100-119): the forward of ovc_forward, then the gradient of
+ *   loss = -sum_{r: targets[r] != pad} logp[r, targets[r]] / #{r: targets[r] != pad}      (NLLLoss(ignore_index=pad), mean)
+ * with respect to every trainable parameter, dropout being the identity (eval mode).  tokens / targets [B, T] int64 as in
+ * ovc_forward (ids in [0, V), checked by the caller).  loss_out: ONE device float.
+ * grads: a second ovc_model-shaped table whose pointer fields name the gradient buffers, each shaped like the parameter of the same
+ * field in m; only those fields are read.  Every buffer is WRITTEN, not accumulated: proj, enc_ln, every layer's q / k / v / o
+ * Linears, their norms and FFNs (weight and, where m has one, bias), word_emb (its pad_idx row gets 0) and fc.  pos_emb (frozen)
+ * gets nothing, the remaining fields are ignored.
+ * Supported: the plain encoder and decoder (OVC_ENC_PLAIN, OVC_DEC_PLAIN) with plain attention (no AoA gates, no memory slots),
+ * precision 0, and vocabularies of at most 16384 words (512 blocks of 32: the fused vocabulary tail of ovc_forward) -- tighter
+ * than ovc_forward, which also takes larger vocabularies -- with (B*T + 256) * V and (V + 256) * B*T below 2^29.  Other sizes
+ * as ovc_forward.  Anything else: ovc_train_workspace_bytes returns 0 and ovc_forward_backward OVC_EINVAL, nothing launched.
+ * Deterministic: no float atomics; every sum over rows, queries, keys or layers has a fixed order, so the loss and the gradients
+ * are the same bits on every call, stream, GEMM tiling and with or without use_graph.
+ * use_graph != 0: as in ovc_forward (the body -- forward and backward -- is captured on the second call for a given (model
+ * contents, gradient table, workspace, B, N, T) and replayed afterwards).
+ * ovc_train_workspace_bytes: bytes of workspace, 0 when unsupported. */
+size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, int T);
+int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                         const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                         float* loss_out, int use_graph, ovc_stream stream);
+/* y[i] = x[i] * scale[0] for i < n, scale a device float (the autograd backward's grad_output).  x and y may be the same. */
+int ovc_scale(const float* x, const float* scale, float* y, long n, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

@@ -22,6 +22,28 @@ from .modules.beam_search import BeamSearch
 from .modules.containers import Module
 
 
+class _XeLoss(torch.autograd.Function):
+    """The reference's training loss on the engine.  ``forward`` runs ``ovc_forward_backward`` -- the forward AND the whole
+    backward -- and keeps the gradients; ``backward`` hands them out scaled by ``grad_output`` (``ovc_scale``).  A loss whose
+    ``backward`` is never called has still paid for the backward and holds one gradient buffer (the size of the parameters)
+    until it is freed; no ``.grad`` is touched."""
+
+    @staticmethod
+    def forward(ctx, engine_, features, boxes, tokens, targets, *params):
+        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets)
+        ctx.engine, ctx.arena = engine_, arena
+        ctx.layout = [(g.storage_offset(), g.shape) for g in grads]
+        ctx.wanted = [p.requires_grad for p in params]
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        scaled = ctx.engine.scale_gradients(ctx.arena, grad_output)
+        out = [scaled[off:off + shape.numel()].view(shape) if want else None
+               for (off, shape), want in zip(ctx.layout, ctx.wanted)]
+        return (None, None, None, None, None) + tuple(out)
+
+
 class BaseTransformer(Module):
     feature_field = "region_features"
     uses_boxes = False
@@ -99,6 +121,24 @@ class BaseTransformer(Module):
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         return self._fused_engine().score(input_features[self.feature_field], boxes, input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
+
+    def xe_loss(self, input_features):
+        """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
+        ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
+        every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer in
+        'f32' only; dropout counts as the identity, so a model in ``train()`` mode with any dropout probability above 0 is
+        refused (set ``DROPOUT: 0`` or call ``model.eval()``)."""
+        if self.training:
+            live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+            if live:
+                raise engine.native.OvcError(
+                    "xe_loss: the model is in train() mode with dropout > 0 ({}); the engine's backward takes dropout as the "
+                    "identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
+        eng = self._fused_engine()
+        boxes = input_features["region_boxes"] if self.uses_boxes else None
+        params = eng.gradient_parameters()
+        return _XeLoss.apply(eng, input_features[self.feature_field], boxes, input_features["caption_tokens"],
+                             input_features["shifted_right_caption_tokens"], *params)
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
                     fused=True, **kwargs):

@@ -1,0 +1,45 @@
+#pragma once
+// Kernels of the training backward (backward.hip), launched by engine.hip's ovc_forward_backward.  Every cross-row sum has a
+// fixed order that depends on the problem shape only -- no float atomics -- so the gradients are the same bits on every call,
+// stream, graph replay and GEMM tiling.
+#include "common.h"
+
+// dst[c * ldd + r] = src[r * lds + c] for r < rows, c < cols; 0 for rows <= r < rows_pad (the padded K of a weight-gradient GEMM)
+int ovc_bw_transpose(const float* src, long lds, int rows, int cols, float* dst, long ldd, int rows_pad, hipStream_t s);
+// dst[i] = sum_{j < n} src[i * ld + j]: per row, 64 lane partials over ascending j then one xor butterfly
+int ovc_bw_rowsum(const float* src, long ld, int rows, int n, float* dst, hipStream_t s);
+// dst[c] = sum_r src[r * ld + c]: partial sums over 64-row chunks in ascending rows, then the chunks in ascending order
+// (part: ceil(rows / 64) * cols floats)
+int ovc_bw_colsum(const float* src, long ld, int rows, int cols, float* part, float* dst, hipStream_t s);
+// LayerNorm backward from the pre-norm input x (statistics recomputed): dx = d(x), prod = dy * xhat, dyc = dy; rows flagged in
+// zero_rows (masked_fill after the norm) pass no gradient
+int ovc_bw_layer_norm(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows, int d,
+                      float* dx, float* prod, float* dyc, hipStream_t s);
+// g[i] = act[i] > 0 ? g[i] : 0  (ReLU backward on the stored ReLU output)
+int ovc_bw_relu(float* g, const float* act, long n, hipStream_t s);
+
+// Attention backward with P recomputed from q, k and the forward's mask (scores q.k / scale, masked keys excluded).  Rows pass:
+// one wave per (image, head, query) -> P, dS = P (dP - rowsum(P dP)) into [B][h][nq][nk] and dq = dS k / scale.  Keys pass: one
+// wave per (image, head, key) -> dk = dS^T q / scale, dv = P^T dout, each summed over the queries in ascending order.
+struct AttnBwdArgs {
+    const float* q; long ldq;          // [B*nq][ldq], head hh at columns hh*dk
+    const float* k; const float* v; long ldkv;    // [B*nk][ldkv]
+    const float* dout; long ldo;       // gradient of the attention output [B*nq][ldo]
+    const uint8_t* mask; long mask_b, mask_r;     // mask[b * mask_b + i * mask_r + j] != 0: key j masked for query i
+    int B, nq, nk, h, dk;
+    float scale;                       // sqrt(d_k)
+    float* P; float* dS;               // scratch [B][h][nq][nk]
+    float* dq; long lddq;
+    float* dk_out; float* dv_out; long lddkv;
+};
+int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s);
+
+// Vocabulary: loss = -sum_r w_r logp[r, tgt_r] with w_r = [tgt_r != pad] / count (fixed-order block sum), then
+// dlogit = (softmax - onehot(tgt)) w_r from the stored transposed logits and the forward's (max, log sum) pieces, written
+// transposed [V][ldt] and row-major [rows][ldv] (padding 0).
+int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, float* w_row,
+                float* loss, float* dl_t, float* dl, long ldv, hipStream_t s);
+// Word-embedding backward: out[w, :] = sum over rows r with tok[r] == w (ascending r) of dx[r, :]; the pad row 0.
+int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s);
+// tok32[r] = clamp(tokens[r], 0, V-1)
+int ovc_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, hipStream_t s);

@@ -1,0 +1,325 @@
+// Device kernels of the training backward (ovc_forward_backward, engine.hip).  Declarations and contracts: backward.h.
+// Everything here is deterministic by construction: each output element is written by one lane, and every sum over rows,
+// queries, keys or columns runs in an order fixed by the shape alone.
+#include "backward.h"
+
+namespace {
+
+constexpr int kChunk = 64;             // rows per partial of the column sums
+
+__global__ __launch_bounds__(256) void bw_transpose_kernel(const float* __restrict__ src, long lds, int rows, int cols,
+                                                           float* __restrict__ dst, long ldd, int rows_pad) {
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    for (int i = wv; i < 64; i += 4) {
+        const int r = r0 + i, c = c0 + lane;
+        tile[i][lane] = (r < rows && c < cols) ? src[(size_t)r * lds + c] : 0.f;
+    }
+    __syncthreads();
+    for (int i = wv; i < 64; i += 4) {
+        const int c = c0 + i, r = r0 + lane;
+        if (c < cols && r < rows_pad) dst[(size_t)c * ldd + r] = tile[lane][i];
+    }
+}
+
+__global__ __launch_bounds__(256) void bw_rowsum_kernel(const float* __restrict__ src, long ld, int rows, int n,
+                                                        float* __restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* p = src + (size_t)row * ld;
+    float s = 0.f;
+    for (int j = lane; j < n; j += 64) s += p[j];
+    s = wave_sum(s);
+    if (lane == 0) dst[row] = s;
+}
+
+__global__ __launch_bounds__(256) void bw_colsum_part_kernel(const float* __restrict__ src, long ld, int rows, int cols,
+                                                             float* __restrict__ part) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int r0 = blockIdx.y * kChunk, r1 = min(rows, r0 + kChunk);
+    float s = 0.f;
+    for (int r = r0; r < r1; ++r) s += src[(size_t)r * ld + c];
+    part[(size_t)blockIdx.y * cols + c] = s;
+}
+
+__global__ __launch_bounds__(256) void bw_colsum_final_kernel(const float* __restrict__ part, int nchunks, int cols,
+                                                              float* __restrict__ dst) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float s = 0.f;
+    for (int i = 0; i < nchunks; ++i) s += part[(size_t)i * cols + c];
+    dst[c] = s;
+}
+
+// one wave per row; d <= 2048 (32 columns per lane)
+__global__ __launch_bounds__(256) void bw_layer_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ dy, const uint8_t* __restrict__ zero_rows,
+                                                            float eps, int rows, int d, float* __restrict__ dx,
+                                                            float* __restrict__ prod, float* __restrict__ dyc) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const size_t o = (size_t)row * d;
+    if (zero_rows && zero_rows[row]) {
+        for (int c = lane; c < d; c += 64) { dx[o + c] = 0.f; prod[o + c] = 0.f; dyc[o + c] = 0.f; }
+        return;
+    }
+    float s = 0.f;
+    for (int c = lane; c < d; c += 64) s += x[o + c];
+    const float mean = wave_sum(s) / d;
+    float v = 0.f;
+    for (int c = lane; c < d; c += 64) { const float t = x[o + c] - mean; v += t * t; }
+    const float rstd = 1.f / sqrtf(wave_sum(v) / d + eps);
+    float a = 0.f, b = 0.f;
+    for (int c = lane; c < d; c += 64) {
+        const float xh = (x[o + c] - mean) * rstd, g = gamma[c] * dy[o + c];
+        a += g; b += g * xh;
+    }
+    a = wave_sum(a) / d; b = wave_sum(b) / d;
+    for (int c = lane; c < d; c += 64) {
+        const float xh = (x[o + c] - mean) * rstd, g = dy[o + c];
+        dx[o + c] = rstd * (gamma[c] * g - a - xh * b);
+        prod[o + c] = g * xh;
+        dyc[o + c] = g;
+    }
+}
+
+__global__ void bw_relu_kernel(float* __restrict__ g, const float* __restrict__ act, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        if (!(act[i] > 0.f)) g[i] = 0.f;
+}
+
+// one wave per (b, head, query row); LDS: q and dout of the row (dk <= 64), scores / dP of the nk keys
+__global__ __launch_bounds__(64) void bw_attention_rows_kernel(AttnBwdArgs a) {
+    extern __shared__ float sm[];
+    float* qs = sm; float* os = sm + 64; float* s = sm + 128; float* dp = s + a.nk;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x % a.nq, bh = blockIdx.x / a.nq, hh = bh % a.h, b = bh / a.h;
+    const size_t qrow = (size_t)b * a.nq + i;
+    const int dk = a.dk;
+    if (lane < dk) { qs[lane] = a.q[qrow * a.ldq + hh * dk + lane]; os[lane] = a.dout[qrow * a.ldo + hh * dk + lane]; }
+    __syncthreads();
+    const uint8_t* mrow = a.mask ? a.mask + (size_t)b * a.mask_b + (size_t)i * a.mask_r : nullptr;
+    float mx = -INFINITY;
+    for (int j = lane; j < a.nk; j += 64) {
+        const float* kr = a.k + ((size_t)b * a.nk + j) * a.ldkv + hh * dk;
+        const float* vr = a.v + ((size_t)b * a.nk + j) * a.ldkv + hh * dk;
+        float sc = 0.f, g = 0.f;
+        for (int t = 0; t < dk; ++t) { sc = fmaf(qs[t], kr[t], sc); g = fmaf(os[t], vr[t], g); }
+        sc = (mrow && mrow[j]) ? -INFINITY : sc / a.scale;
+        s[j] = sc; dp[j] = g;
+        mx = fmaxf(mx, sc);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < a.nk; j += 64) sum += s[j] == -INFINITY ? 0.f : expf(s[j] - mx);
+    sum = wave_sum(sum);
+    float delta = 0.f;
+    for (int j = lane; j < a.nk; j += 64) {
+        const float p = (s[j] == -INFINITY || !(sum > 0.f)) ? 0.f : expf(s[j] - mx) / sum;
+        s[j] = p;
+        delta = fmaf(p, dp[j], delta);
+    }
+    delta = wave_sum(delta);
+    const size_t po = (((size_t)b * a.h + hh) * a.nq + i) * a.nk;
+    for (int j = lane; j < a.nk; j += 64) {
+        const float p = s[j], g = p * (dp[j] - delta);
+        dp[j] = g;
+        a.P[po + j] = p; a.dS[po + j] = g;
+    }
+    __syncthreads();
+    if (lane < dk) {
+        float acc = 0.f;
+        for (int j = 0; j < a.nk; ++j) acc = fmaf(dp[j], a.k[((size_t)b * a.nk + j) * a.ldkv + hh * dk + lane], acc);
+        a.dq[qrow * a.lddq + hh * dk + lane] = acc / a.scale;
+    }
+}
+
+// one wave per (b, head, key): lanes over the head's columns, queries in ascending order
+__global__ __launch_bounds__(64) void bw_attention_keys_kernel(AttnBwdArgs a) {
+    const int lane = threadIdx.x;
+    const int j = blockIdx.x % a.nk, bh = blockIdx.x / a.nk, hh = bh % a.h, b = bh / a.h;
+    const int dk = a.dk;
+    if (lane >= dk) return;
+    const size_t po = ((size_t)b * a.h + hh) * a.nq * a.nk + j;
+    float gk = 0.f, gv = 0.f;
+    for (int i = 0; i < a.nq; ++i) {
+        const size_t qrow = (size_t)b * a.nq + i;
+        const float ds = a.dS[po + (size_t)i * a.nk], p = a.P[po + (size_t)i * a.nk];
+        gk = fmaf(ds, a.q[qrow * a.ldq + hh * dk + lane], gk);
+        gv = fmaf(p, a.dout[qrow * a.ldo + hh * dk + lane], gv);
+    }
+    const size_t krow = (size_t)b * a.nk + j;
+    a.dk_out[krow * a.lddkv + hh * dk + lane] = gk / a.scale;
+    a.dv_out[krow * a.lddkv + hh * dk + lane] = gv;
+}
+
+// one workgroup: count of non-pad targets and the summed negative log-likelihood, thread partials over rows t, t + 256, ...
+// then a fixed LDS tree; afterwards every row's weight
+__global__ __launch_bounds__(256) void bw_loss_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                                      const int32_t* __restrict__ tgt, int pad, int rows, float* __restrict__ w_row,
+                                                      float* __restrict__ loss) {
+    __shared__ float nll[256], cnt[256];
+    const int t = threadIdx.x;
+    float a = 0.f, c = 0.f;
+    for (int r = t; r < rows; r += 256) {
+        const int w = tgt[r];
+        if (w == pad) continue;
+        a -= (logits_t[(size_t)w * ldt + r] - lse[2 * r]) - lse[2 * r + 1];
+        c += 1.f;
+    }
+    nll[t] = a; cnt[t] = c;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) { nll[t] += nll[t + off]; cnt[t] += cnt[t + off]; }
+        __syncthreads();
+    }
+    const float count = cnt[0];
+    if (t == 0) *loss = nll[0] / count;
+    const float inv = 1.f / count;
+    for (int r = t; r < rows; r += 256) w_row[r] = tgt[r] == pad ? 0.f : inv;
+}
+
+// 64 words x 64 rows per workgroup: dlogit written transposed (along rows) and, through LDS, row-major (along words)
+__global__ __launch_bounds__(256) void bw_dlogit_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                                        const int32_t* __restrict__ tgt, const float* __restrict__ w_row, int rows,
+                                                        int V, float* __restrict__ dl_t, float* __restrict__ dl, long ldv) {
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, w0 = blockIdx.y * 64;
+    for (int i = wv; i < 64; i += 4) {
+        const int w = w0 + i, r = r0 + lane;
+        float g = 0.f;
+        if (w < V && r < rows) {
+            const float p = expf((logits_t[(size_t)w * ldt + r] - lse[2 * r]) - lse[2 * r + 1]);
+            g = (p - (tgt[r] == w ? 1.f : 0.f)) * w_row[r];
+        }
+        if (w < V && r < ldt) dl_t[(size_t)w * ldt + r] = g;
+        tile[i][lane] = g;
+    }
+    __syncthreads();
+    for (int i = wv; i < 64; i += 4) {
+        const int r = r0 + i, w = w0 + lane;
+        if (r < rows && w < ldv) dl[(size_t)r * ldv + w] = tile[lane][i];
+    }
+}
+
+// one workgroup per word; each thread keeps up to 8 columns (d <= 2048)
+__global__ __launch_bounds__(256) void bw_embedding_kernel(const int32_t* __restrict__ tok, int rows, int pad,
+                                                           const float* __restrict__ dx, int d, float* __restrict__ out) {
+    const int w = blockIdx.x, t = threadIdx.x;
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+    if (w != pad) {
+        for (int r = 0; r < rows; ++r) {
+            if (tok[r] != w) continue;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int c = t + 256 * k;
+                if (c < d) acc[k] += dx[(size_t)r * d + c];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = t + 256 * k;
+        if (c < d) out[(size_t)w * d + c] = acc[k];
+    }
+}
+
+__global__ void bw_tokens_kernel(const int64_t* __restrict__ tokens, int rows, int V, int32_t* __restrict__ tok32) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) tok32[r] = (int)min(max(tokens[r], (int64_t)0), (int64_t)V - 1);
+}
+
+__global__ void scale_kernel(const float* __restrict__ x, const float* __restrict__ s, float* __restrict__ y, long n) {
+    const float f = *s;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = x[i] * f;
+}
+
+unsigned blocks_for(long n, int per = 256) { return (unsigned)std::min<long>((n + per - 1) / per, 4096); }
+
+}  // namespace
+
+int ovc_bw_transpose(const float* src, long lds, int rows, int cols, float* dst, long ldd, int rows_pad, hipStream_t s) {
+    if (rows_pad < rows || ldd < rows_pad || cols <= 0 || rows_pad <= 0) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_transpose_kernel, dim3((rows_pad + 63) / 64, (cols + 63) / 64), dim3(256), 0, s, src, lds, rows, cols, dst,
+                       ldd, rows_pad);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_rowsum(const float* src, long ld, int rows, int n, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(bw_rowsum_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, src, ld, rows, n, dst);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_colsum(const float* src, long ld, int rows, int cols, float* part, float* dst, hipStream_t s) {
+    const int chunks = (rows + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(bw_colsum_part_kernel, dim3((cols + 255) / 256, chunks), dim3(256), 0, s, src, ld, rows, cols, part);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_colsum_final_kernel, dim3((cols + 255) / 256), dim3(256), 0, s, part, chunks, cols, dst);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_layer_norm(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows, int d,
+                      float* dx, float* prod, float* dyc, hipStream_t s) {
+    if (d > 2048) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_layer_norm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, dy, zero_rows, eps, rows, d, dx, prod, dyc);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_relu(float* g, const float* act, long n, hipStream_t s) {
+    hipLaunchKernelGGL(bw_relu_kernel, dim3(blocks_for(n)), dim3(256), 0, s, g, act, n);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s) {
+    if (a.dk > 64 || a.dk <= 0 || a.nk <= 0 || a.nq <= 0) return OVC_EINVAL;
+    const size_t lds = (128 + 2 * (size_t)a.nk) * sizeof(float);
+    hipLaunchKernelGGL(bw_attention_rows_kernel, dim3(a.B * a.h * a.nq), dim3(64), lds, s, a);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_attention_keys_kernel, dim3(a.B * a.h * a.nk), dim3(64), 0, s, a);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, float* w_row,
+                float* loss, float* dl_t, float* dl, long ldv, hipStream_t s) {
+    hipLaunchKernelGGL(bw_loss_kernel, dim3(1), dim3(256), 0, s, logits_t, ldt, lse, tgt, pad, rows, w_row, loss);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, tgt, w_row,
+                       rows, V, dl_t, dl, ldv);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s) {
+    if (d > 2048) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_embedding_kernel, dim3(V), dim3(256), 0, s, tok, rows, pad, dx, d, out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, hipStream_t s) {
+    hipLaunchKernelGGL(bw_tokens_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, tokens, rows, V, tok32);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+extern "C" int ovc_scale(const float* x, const float* scale, float* y, long n, ovc_stream stream) {
+    if (!x || !scale || !y || n < 0) return OVC_EINVAL;
+    if (n == 0) return OVC_OK;
+    if (const int rc = ovc_device_guard()) return rc;
+    hipLaunchKernelGGL(scale_kernel, dim3(blocks_for(n)), dim3(256), 0, ovc_hip_stream(stream), x, scale, y, n);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "backward.h"
 
 namespace {
 
@@ -94,7 +95,15 @@ struct Bump {
     }
 };
 
+// Training (ovc_forward_backward): per layer, what the backward reads from the forward -- the projected q / k / v, the attention
+// outputs, the pre-norm sums (the LayerNorm statistics are recomputed from them), the norm outputs, the ReLU outputs and the
+// layer outputs.  The inference forward reuses one set of buffers across layers instead (Workspace::tape == nullptr).
+struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out; };
+struct DecTape { float *q, *k, *v, *att, *ys, *x1, *qc, *attc, *yc, *x2, *ff, *yf, *out; };
+struct Tape { EncTape enc[OVC_MAX_LAYERS]; DecTape dec[OVC_MAX_LAYERS]; };
+
 struct Workspace {
+    const Tape* tape;                             // training only: the forward keeps every layer's intermediates here
     // encoder
     uint8_t* enc_mask; float* pe; float* xe[2]; float* eq; float* ek; float* ev; float* eatt; float* ey;
     float* eff; float* einfo; float* egate; float* geometry; float* enc_levels;
@@ -630,27 +639,33 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
     RUN(ovc_layer_norm(w.ey, nullptr, m->enc_ln.g, m->enc_ln.b, w.pe, N, nullptr, m->ln_eps, w.xe[0], BN, d, s));
 
     float* x = w.xe[0];
-    float* x1 = w.xe[1];
     for (int l = 0; l < m->n_enc; ++l) {
         const ovc_mha& at = m->enc[l].att;
+        // training (ovc_forward_backward): every intermediate the backward reads goes to the layer's own tape slot; the same
+        // launches on other buffers, so the bits are those of the inference forward
+        const EncTape* tp = w.tape ? &w.tape->enc[l] : nullptr;
+        float* eq = tp ? tp->q : w.eq; float* ek = tp ? tp->k : w.ek; float* ev = tp ? tp->v : w.ev;
+        float* eatt = tp ? tp->att : w.eatt; float* ya = tp ? tp->ya : w.ey; float* x1 = tp ? tp->x1 : w.xe[1];
+        float* eff = tp ? tp->ff : w.eff; float* yf = tp ? tp->yf : w.ey;
         GemmArgs a{};
         a.A1 = x; a.lda1 = d; a.K1 = d; a.M = BN; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
-        a.seg[0] = e.seg(at.q, w.eq);
-        a.seg[1] = e.seg(at.k, w.ek);
-        a.seg[2] = e.seg(at.v, w.ev);
+        a.seg[0] = e.seg(at.q, eq);
+        a.seg[1] = e.seg(at.k, ek);
+        a.seg[2] = e.seg(at.v, ev);
         TRY(e.gemm(a));
         const int mem = at.m_k ? m->memory : 0;
-        RUN(ovc_attention(w.eq, w.ek, w.ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
+        RUN(ovc_attention(eq, ek, ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
                           m->enc_kind == OVC_ENC_GEOMETRIC ? w.geometry : nullptr, at.m_k, at.m_v, mem,
-                          sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), w.eatt, s));
-        TRY(e.linear(w.eatt, hv, at.o, x, w.ey, BN, d, 0));
-        RUN(ovc_layer_norm(w.ey, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, x1, BN, d, s));
+                          sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), eatt, s));
+        TRY(e.linear(eatt, hv, at.o, x, ya, BN, d, 0));
+        RUN(ovc_layer_norm(ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, x1, BN, d, s));
         TRY(e.aoa(at, x, x1, w.einfo, w.egate, BN));
         // layer output: straight into the level slot (multilevel, cross-level) or the ping-pong buffer
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
                                                         : (l == m->n_enc - 1 ? w.enc_levels : x);
-        TRY(e.ffn(m->enc[l].ffn, x1, w.eff, w.ey, nullptr, out, w.enc_mask, BN));
+        if (tp && l < m->n_enc - 1) out = tp->out;
+        TRY(e.ffn(m->enc[l].ffn, x1, eff, yf, nullptr, out, w.enc_mask, BN));
         x = out;
     }
     if (m->enc_kind == OVC_ENC_CROSS_LEVEL) TRY(run_cross_level_tail(e, w, B, N));
@@ -879,27 +894,34 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
     float* x = w.x;
     for (int l = 0; l < m->n_dec; ++l) {
         const ovc_dec_layer& dl = m->dec[l];
+        // training: the layer's own tape slots (see run_encoder_layers); the meshed branch never runs with a tape
+        const DecTape* tp = w.tape ? &w.tape->dec[l] : nullptr;
+        float* sq = tp ? tp->q : w.q; float* sk = tp ? tp->k : w.kc; float* sv = tp ? tp->v : w.vc;
+        float* satt = tp ? tp->att : w.att; float* ys = tp ? tp->ys : w.y; float* x1 = tp ? tp->x1 : w.x1;
+        float* cq = tp ? tp->qc : w.q; float* catt = tp ? tp->attc : w.att; float* yc = tp ? tp->yc : w.y;
+        float* x2 = tp ? tp->x2 : w.x2; float* ff = tp ? tp->ff : w.ff; float* yf = tp ? tp->yf : w.y;
+        float* out = tp ? tp->out : w.x;
         // ---- masked self-attention over the caption ------------------------------------------------
         GemmArgs a{};
         a.A1 = x; a.lda1 = d; a.K1 = d; a.M = rows; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
-        a.seg[0] = e.seg(dl.self_att.q, w.q);
-        a.seg[1] = e.seg(dl.self_att.k, w.kc);
-        a.seg[2] = e.seg(dl.self_att.v, w.vc);
+        a.seg[0] = e.seg(dl.self_att.q, sq);
+        a.seg[1] = e.seg(dl.self_att.k, sk);
+        a.seg[2] = e.seg(dl.self_att.v, sv);
         TRY(e.gemm(a));
         const int smem = dl.self_att.m_k ? m->memory : 0;
-        RUN(ovc_attention(w.q, w.kc, w.vc, B, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
-                          dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), w.att, s));
-        TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, nullptr, w.x1, rows));
-        TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));
+        RUN(ovc_attention(sq, sk, sv, B, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
+                          dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), satt, s));
+        TRY(e.linear_ln(satt, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, ys, nullptr, x1, rows));
+        TRY(e.aoa(dl.self_att, x, x1, w.info, w.gate, rows));
 
         // ---- cross-attention over every encoder level -----------------------------------------------
-        TRY(e.linear(w.x1, d, dl.cross_att.q, nullptr, w.q, rows, hk, 0));
+        TRY(e.linear(x1, d, dl.cross_att.q, nullptr, cq, rows, hk, 0));
         const int cmem = dl.cross_att.m_k ? m->memory : 0;
         for (int lvl = 0; lvl < lv; ++lvl) {
             const size_t off = ((size_t)l * lv + lvl) * BN * hk;
-            RUN(ovc_attention(w.q, w.kx + off, w.vx + off, B, T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
+            RUN(ovc_attention(cq, w.kx + off, w.vx + off, B, T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
                               dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
-                              w.att + (size_t)lvl * rows * hv, s));
+                              catt + (size_t)lvl * rows * hv, s));
         }
         float* ffn_in;
         if (m->dec_kind == OVC_DEC_MESHED) {
@@ -937,12 +959,12 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
             RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s));
             ffn_in = w.mixed;
         } else {
-            TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, nullptr, w.x2, rows));
-            TRY(e.aoa(dl.cross_att, w.x1, w.x2, w.info, w.gate, rows));
-            ffn_in = w.x2;
+            TRY(e.linear_ln(catt, hv, dl.cross_att.o, x1, dl.cross_att.ln, nullptr, yc, nullptr, x2, rows));
+            TRY(e.aoa(dl.cross_att, x1, x2, w.info, w.gate, rows));
+            ffn_in = x2;
         }
-        TRY(e.ffn(dl.ffn, ffn_in, w.ff, w.y, nullptr, w.x, w.padflag, rows));
-        x = w.x;
+        TRY(e.ffn(dl.ffn, ffn_in, ff, yf, nullptr, out, w.padflag, rows));
+        x = out;
     }
 
     // ---- vocabulary product ----------------------------------------------------------------------
@@ -1600,3 +1622,330 @@ extern "C" double ovc_profile_overhead_ms(void) {
 }
 
 extern "C" const char* ovc_profile_kernel_name(int tiling) { return ovc_gemm_tiling_name(tiling); }
+
+// ---------------------------------------------------------------------------------------------
+// training: ovc_forward_backward
+// ---------------------------------------------------------------------------------------------
+// The forward of ovc_forward (want_logp: the transposed logits are kept) with every layer's intermediates on the tape, then one
+// reverse sweep -- vocabulary, decoder layers L-1 .. 0, encoder layers, the two embeddings.  Weight gradients dW = dY^T X are
+// the engine's NT GEMM on transposed operands (dY^T and X^T staged with K = rows padded to 4, zeros in the padding), input
+// gradients dX = dY W the NT GEMM on the transposed weight; both in the one-chain K-order class, so one fmaf chain over the
+// rows (resp. the output features) in ascending order, whatever the tiling.  Bias and LayerNorm gradients are fixed-order
+// row / column sums, the encoder output's gradient sums the decoder layers' cross-attention terms from layer L-1 down to 0 through
+// the GEMM's residual input, the word embedding sums its rows in ascending row order.  No float atomics anywhere.
+namespace {
+
+struct TrainWs {
+    Workspace w;                  // the forward's buffers (carve_forward, want_logp), tape pointer set by the caller
+    Tape tape;
+    float* feat_t;                // [d_feat][BN padded to 4] the caller's features, transposed (staged outside the captured body)
+    int32_t* tok;                 // [rows] caption tokens, clamped
+    float* w_row; float* loss;    // [rows] loss weight of every row, the loss
+    float* dl_t; float* dl;       // dlogit [V][ldt] and [rows][ldv]
+    float* fc_t;                  // fc^T [d][ldv]
+    float* wt;                    // a transposed weight (or stacked q|k|v, k|v), [max(d_ff, 3 h d_k)][d]
+    float* g[2];                  // gradient of a layer's output / input, [Rmax][d]
+    float* dy; float* prod; float* dyc; float* dx1;   // LayerNorm backward, [Rmax][d]
+    float* dff;                   // [Rmax][d_ff]
+    float* dqkv;                  // [Rmax][3 h d_k]
+    float* datt;                  // [Rmax][h d_v]
+    float* denc[2];               // gradient of the encoder output, [B*N][d]
+    float* dkv;                   // [B*N][2 h d_k]
+    float* ta; float* tb;         // transposed GEMM operands [max(d, d_ff, 3 h d_k)][Rmax padded to 4]
+    float* P; float* dS;          // attention backward [B][h][nq][nk]
+    float* part;                  // column-sum partials [ceil(Rmax / 64)][d]
+    size_t bytes;
+};
+
+inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T) {
+    TrainWs t{};
+    t.w = carve_forward(m, base, B, N, T, 1);
+    Bump a{reinterpret_cast<char*>(base), t.w.bytes};
+    const size_t rows = (size_t)B * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
+    const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
+    const size_t R = std::max(rows, BN), Rp = pad4(R);
+    for (int l = 0; l < m->n_enc; ++l) {
+        EncTape& p = t.tape.enc[l];
+        p.q = a.take<float>(BN * ehk); p.k = a.take<float>(BN * ehk); p.v = a.take<float>(BN * ehk); p.att = a.take<float>(BN * ehk);
+        p.ya = a.take<float>(BN * d); p.x1 = a.take<float>(BN * d); p.ff = a.take<float>(BN * dff); p.yf = a.take<float>(BN * d);
+        p.out = a.take<float>(l < m->n_enc - 1 ? BN * d : 0);
+    }
+    for (int l = 0; l < m->n_dec; ++l) {
+        DecTape& p = t.tape.dec[l];
+        p.q = a.take<float>(rows * hk); p.k = a.take<float>(rows * hk); p.v = a.take<float>(rows * hk); p.att = a.take<float>(rows * hk);
+        p.ys = a.take<float>(rows * d); p.x1 = a.take<float>(rows * d); p.qc = a.take<float>(rows * hk);
+        p.attc = a.take<float>(rows * hk); p.yc = a.take<float>(rows * d); p.x2 = a.take<float>(rows * d);
+        p.ff = a.take<float>(rows * dff); p.yf = a.take<float>(rows * d); p.out = a.take<float>(rows * d);
+    }
+    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk});
+    t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
+    t.tok = a.take<int32_t>(rows);
+    t.w_row = a.take<float>(rows); t.loss = a.take<float>(4);
+    t.dl_t = a.take<float>(V * pad4(rows)); t.dl = a.take<float>(rows * pad4(V));
+    t.fc_t = a.take<float>(d * pad4(V));
+    t.wt = a.take<float>(wide * d);
+    for (int i = 0; i < 2; ++i) t.g[i] = a.take<float>(R * d);
+    t.dy = a.take<float>(R * d); t.prod = a.take<float>(R * d); t.dyc = a.take<float>(R * d); t.dx1 = a.take<float>(R * d);
+    t.dff = a.take<float>(R * dff);
+    t.dqkv = a.take<float>(R * 3 * std::max(hk, ehk));
+    t.datt = a.take<float>(R * std::max(hk, ehk));
+    for (int i = 0; i < 2; ++i) t.denc[i] = a.take<float>(BN * d);
+    t.dkv = a.take<float>(BN * 2 * hk);
+    t.ta = a.take<float>(wide * Rp); t.tb = a.take<float>(wide * Rp);
+    const size_t pdec = (size_t)B * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * N;
+    t.P = a.take<float>(std::max(pdec, penc)); t.dS = a.take<float>(std::max(pdec, penc));
+    t.part = a.take<float>(((R + 63) / 64) * std::max(d, dff));
+    t.bytes = (a.off + 255) & ~(size_t)255;
+    return t;
+}
+
+bool lin_grad_ok(const ovc_lin& l, const ovc_lin& g) { return g.w && (!l.b || g.b); }
+bool norm_grad_ok(const ovc_norm& g) { return g.g && g.b; }
+bool mha_plain(const ovc_mha& a) { return !a.aoa_i.w && !a.aoa_g.w && !a.m_k && !a.m_v; }
+bool mha_grad_ok(const ovc_mha& a, const ovc_mha& g) {
+    return lin_grad_ok(a.q, g.q) && lin_grad_ok(a.k, g.k) && lin_grad_ok(a.v, g.v) && lin_grad_ok(a.o, g.o) && norm_grad_ok(g.ln);
+}
+bool ffn_grad_ok(const ovc_ffn& f, const ovc_ffn& g) { return lin_grad_ok(f.fc1, g.fc1) && lin_grad_ok(f.fc2, g.fc2) && norm_grad_ok(g.ln); }
+
+// What the backward covers: the plain encoder and decoder, plain scaled dot-product attention, fp32, and vocabularies that take
+// the fused vocabulary tail (its transposed logits and block pieces are what the cross-entropy backward reads).
+bool train_ok(const ovc_model* m, int B, int N, int T) {
+    if (!forward_ok(m, B, N, T)) return false;
+    if (m->enc_kind != OVC_ENC_PLAIN || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    for (int l = 0; l < m->n_enc; ++l) if (!mha_plain(m->enc[l].att)) return false;
+    for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
+    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
+    // the dlogit products address their operands with 32-bit buffer descriptors (ovc_gemm_launch)
+    const long kMax = 0x7fffffffL - (1L << 20), rows = (long)B * T;
+    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
+}
+
+bool grads_ok(const ovc_model* m, const ovc_model* g) {
+    if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
+    for (int l = 0; l < m->n_enc; ++l)
+        if (!mha_grad_ok(m->enc[l].att, g->enc[l].att) || !ffn_grad_ok(m->enc[l].ffn, g->enc[l].ffn)) return false;
+    for (int l = 0; l < m->n_dec; ++l)
+        if (!mha_grad_ok(m->dec[l].self_att, g->dec[l].self_att) || !mha_grad_ok(m->dec[l].cross_att, g->dec[l].cross_att) ||
+            !ffn_grad_ok(m->dec[l].ffn, g->dec[l].ffn)) return false;
+    return true;
+}
+
+inline float* out_ptr(const float* p) { return const_cast<float*>(p); }
+
+// C [M][N] = A [M][K] . Wt [N][K]^T (+ R), one-chain class
+int bw_mm(Engine& e, const float* A, int lda, int M, int K, const float* Wt, int N, float* C, const float* R = nullptr) {
+    GemmArgs a{};
+    a.A1 = A; a.lda1 = lda; a.K1 = K; a.M = M; a.seg_n = N; a.nseg = 1; a.ldc = N;
+    a.R = R; a.ldr = N;
+    a.seg[0] = GemmSegment{Wt, nullptr, C, nullptr, nullptr};
+    return e.gemm(a);
+}
+
+// dW [n][k] = dY^T X over `rows` rows (dY [rows][ldy] from column 0, n wide; X [rows][ldx], k wide), db [n] = column sums of dY
+int bw_weight(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const float* X, int ldx, int k, int rows, const ovc_lin& l,
+              const ovc_lin& g) {
+    hipStream_t s = e.stream;
+    const int rp = (int)pad4(rows);
+    RUN(ovc_bw_transpose(dY, ldy, rows, n, t.ta, rp, rp, s));
+    RUN(ovc_bw_transpose(X, ldx, rows, k, t.tb, rp, rp, s));
+    TRY(bw_mm(e, t.ta, rp, n, rp, t.tb, k, out_ptr(g.w)));
+    if (l.b) RUN(ovc_bw_rowsum(t.ta, rp, n, rows, out_ptr(g.b), s));
+    return OVC_OK;
+}
+
+// LayerNorm of the pre-norm sum y: t.dy = d(y) from dout; gamma / beta gradients
+int bw_norm(Engine& e, TrainWs& t, const float* y, const ovc_norm& n, const ovc_norm& gn, const float* dout, const uint8_t* zero_rows,
+            int rows) {
+    hipStream_t s = e.stream;
+    const int d = e.m->d_model;
+    RUN(ovc_bw_layer_norm(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, s));
+    RUN(ovc_bw_colsum(t.prod, d, rows, d, t.part, out_ptr(gn.g), s));
+    RUN(ovc_bw_colsum(t.dyc, d, rows, d, t.part, out_ptr(gn.b), s));
+    return OVC_OK;
+}
+
+// dX [rows][k] = dY [rows][n] . W (+ R), W [n][k] the weight of a Linear(k -> n)
+int bw_input(Engine& e, TrainWs& t, const float* dY, int n, const ovc_lin& l, int k, float* dX, const float* R, int rows) {
+    RUN(ovc_bw_transpose(l.w, k, n, k, t.wt, n, n, e.stream));
+    return bw_mm(e, dY, n, rows, n, t.wt, k, dX, R);
+}
+
+// The FFN + its AddNorm: from dout (gradient of the norm output; rows in zero_rows pass nothing) to t.dx1 = gradient of its input x
+int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const float* x, const float* ff, const float* yf,
+           const float* dout, const uint8_t* zero_rows, int rows) {
+    const int d = e.m->d_model, dff = e.m->d_ff;
+    TRY(bw_norm(e, t, yf, f.ln, gf.ln, dout, zero_rows, rows));
+    TRY(bw_weight(e, t, t.dy, d, d, ff, dff, dff, rows, f.fc2, gf.fc2));
+    TRY(bw_input(e, t, t.dy, d, f.fc2, dff, t.dff, nullptr, rows));
+    RUN(ovc_bw_relu(t.dff, ff, (long)rows * dff, e.stream));
+    TRY(bw_weight(e, t, t.dff, dff, dff, x, d, d, rows, f.fc1, gf.fc1));
+    return bw_input(e, t, t.dff, dff, f.fc1, d, t.dx1, t.dy, rows);
+}
+
+// Self-attention + AddNorm of one layer (rows = B*n): from dnorm (gradient of the norm output, read before anything is written)
+// to dx (gradient of the layer input x, which fed q, k, v and the residual)
+int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const float* x, const float* q, const float* k,
+                      const float* v, const float* att, const float* y, const float* dnorm, const uint8_t* mask, long mask_b,
+                      long mask_r, int B, int n, int h, int dk, float* dx) {
+    const int d = e.m->d_model, hk = h * dk, rows = B * n;
+    TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows));
+    TRY(bw_weight(e, t, t.dy, d, d, att, hk, hk, rows, at.o, ga.o));
+    TRY(bw_input(e, t, t.dy, d, at.o, hk, t.datt, nullptr, rows));
+    AttnBwdArgs p{};
+    p.q = q; p.ldq = hk; p.k = k; p.v = v; p.ldkv = hk; p.dout = t.datt; p.ldo = hk;
+    p.mask = mask; p.mask_b = mask_b; p.mask_r = mask_r;
+    p.B = B; p.nq = n; p.nk = n; p.h = h; p.dk = dk; p.scale = sqrtf((float)dk);
+    p.P = t.P; p.dS = t.dS; p.dq = t.dqkv; p.lddq = 3 * hk; p.dk_out = t.dqkv + hk; p.dv_out = t.dqkv + 2 * hk; p.lddkv = 3 * hk;
+    RUN(ovc_bw_attention(p, e.stream));
+    const ovc_lin* lins[3] = {&at.q, &at.k, &at.v};
+    const ovc_lin* glins[3] = {&ga.q, &ga.k, &ga.v};
+    for (int i = 0; i < 3; ++i) {
+        TRY(bw_weight(e, t, t.dqkv + i * hk, 3 * hk, hk, x, d, d, rows, *lins[i], *glins[i]));
+        RUN(ovc_bw_transpose(lins[i]->w, d, hk, d, t.wt + i * hk, 3 * hk, hk, e.stream));
+    }
+    return bw_mm(e, t.dqkv, 3 * hk, rows, 3 * hk, t.wt, d, dx, t.dy);
+}
+
+int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, int N, int T, const float* xin, const float* dout,
+                     float* dxin, float* denc_prev, float* denc_next) {
+    const ovc_model* m = e.m;
+    const Workspace& w = t.w;
+    const DecTape& p = t.tape.dec[l];
+    const ovc_dec_layer& dl = m->dec[l];
+    const ovc_dec_layer& gl = gr->dec[l];
+    const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * T, BN = B * N;
+    // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(x2)
+    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.x2, p.ff, p.yf, dout, w.padflag, rows));
+    // cross-attention AddNorm -> t.dy = d(yc), the residual's share of d(x1)
+    TRY(bw_norm(e, t, p.yc, dl.cross_att.ln, gl.cross_att.ln, t.dx1, nullptr, rows));
+    TRY(bw_weight(e, t, t.dy, d, d, p.attc, hk, hk, rows, dl.cross_att.o, gl.cross_att.o));
+    TRY(bw_input(e, t, t.dy, d, dl.cross_att.o, hk, t.datt, nullptr, rows));
+    const size_t kvoff = (size_t)l * BN * hk;
+    AttnBwdArgs a{};
+    a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
+    a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
+    a.B = B; a.nq = T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+    a.P = t.P; a.dS = t.dS; a.dq = t.dqkv; a.lddq = hk; a.dk_out = t.dkv; a.dv_out = t.dkv + hk; a.lddkv = 2 * hk;
+    RUN(ovc_bw_attention(a, e.stream));
+    TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
+    TRY(bw_input(e, t, t.dqkv, hk, dl.cross_att.q, d, t.dx1, t.dy, rows));      // t.dx1 = d(x1)
+    // the encoder output's share: this layer's cross keys / values, added to what layers above contributed
+    TRY(bw_weight(e, t, t.dkv, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.k, gl.cross_att.k));
+    TRY(bw_weight(e, t, t.dkv + hk, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.v, gl.cross_att.v));
+    RUN(ovc_bw_transpose(dl.cross_att.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
+    RUN(ovc_bw_transpose(dl.cross_att.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
+    TRY(bw_mm(e, t.dkv, 2 * hk, BN, 2 * hk, t.wt, d, denc_next, denc_prev));
+    // masked self-attention over the caption
+    return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
+                             B, T, h, dk, dxin);
+}
+
+int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T) {
+    const ovc_model* m = e.m;
+    Workspace& w = t.w;
+    hipStream_t s = e.stream;
+    const int d = m->d_model, V = m->vocab, rows = B * T, BN = B * N, L = m->n_dec;
+    const int nblk = (V + 31) / 32, ldt = (int)pad4(rows), ldv = (int)pad4(V);
+    TRY(issue_forward_body(e, w, B, N, T, 1));
+    if (!e.dry) {
+        hipLaunchKernelGGL(tf_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.stats, nblk, (nblk + 1) & ~1, rows, w.tgt,
+                           m->pad_idx, nullptr, nullptr, 0L, w.lse, nullptr);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
+    e.gemm_class = 3;
+    RUN(ovc_bw_xent(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
+    // decoder output: d(out) = dlogit . fc, d(fc) = dlogit^T . out
+    const float* dec_out = t.tape.dec[L - 1].out;
+    RUN(ovc_bw_transpose(m->fc, d, V, d, t.fc_t, ldv, ldv, s));
+    TRY(bw_mm(e, t.dl, ldv, rows, ldv, t.fc_t, d, t.g[0]));
+    RUN(ovc_bw_transpose(dec_out, d, rows, d, t.tb, ldt, ldt, s));
+    TRY(bw_mm(e, t.dl_t, ldt, V, ldt, t.tb, d, out_ptr(gr->fc)));
+    // decoder layers, top down; the encoder output's gradient accumulates in layer order L-1 .. 0
+    e.gemm_class = 2;
+    int cur = 0, enc_cur = 0;
+    for (int l = L - 1; l >= 0; --l) {
+        const float* xin = l == 0 ? w.x : t.tape.dec[l - 1].out;
+        TRY(bw_decoder_layer(e, t, gr, l, B, N, T, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
+                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1]));
+        if (l != L - 1) enc_cur ^= 1;
+        cur ^= 1;
+    }
+    RUN(ovc_bw_embedding(t.tok, rows, m->pad_idx, t.g[cur], d, V, out_ptr(gr->word_emb), s));
+    // encoder layers, top down: the output rows of padding regions were cleared after each layer's norm
+    e.gemm_class = 1;
+    const int eh = enc_heads(m), edk = enc_dk(m);
+    const float* dout = t.denc[enc_cur];
+    for (int l = m->n_enc - 1; l >= 0; --l) {
+        const EncTape& p = t.tape.enc[l];
+        const ovc_enc_layer& el = m->enc[l];
+        const ovc_enc_layer& gl = gr->enc[l];
+        const float* xin = l == 0 ? w.xe[0] : t.tape.enc[l - 1].out;
+        TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN));
+        TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur]));
+        dout = t.g[cur];
+        cur ^= 1;
+    }
+    // feature embedding: encoder.layer_norm over the projection (the sinusoid added after it has no parameters)
+    e.gemm_class = 0;
+    TRY(bw_norm(e, t, w.ey, m->enc_ln, gr->enc_ln, dout, nullptr, BN));
+    const int bnp = (int)pad4(BN);
+    RUN(ovc_bw_transpose(t.dy, d, BN, d, t.ta, bnp, bnp, s));
+    TRY(bw_mm(e, t.ta, bnp, d, bnp, t.feat_t, m->d_feat, out_ptr(gr->proj.w)));
+    if (m->proj.b) RUN(ovc_bw_rowsum(t.ta, bnp, d, BN, out_ptr(gr->proj.b), s));
+    return OVC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, int T) {
+    if (!train_ok(m, B, N, T)) return 0;
+    return carve_train(m, nullptr, B, N, T).bytes;
+}
+
+extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                    const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                    float* loss_out, int use_graph, ovc_stream stream) {
+    (void)boxes;       // the plain encoder reads no boxes
+    if (!train_ok(m, B, N, T) || !grads || !grads_ok(m, grads) || !features || !tokens || !targets || !workspace || !loss_out)
+        return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    TrainWs t = carve_train(m, workspace, B, N, T);
+    t.w.tape = &t.tape;
+    if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    const int rows = B * T, BN = B * N;
+
+    // the kernels that read the caller's inputs, outside the captured body
+    TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
+                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    TRY(ovc_bw_tokens(tokens, rows, m->vocab, t.tok, e.stream));
+    TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
+    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T); };
+    if (!use_graph) {
+        TRY(body(e));
+    } else {
+        // the body writes the gradient buffers: their table is part of the key
+        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull), workspace, B, N, T, 0};
+        key.kind = 3;
+        std::lock_guard<std::mutex> lock(g_graph_mutex);
+        GraphEntry& entry = g_graphs[key];
+        entry.calls += 1;
+        entry.last_use = ++g_graph_tick;
+        entry.last_stream = e.stream;
+        evict_lru(&key, nullptr);
+        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec && !capture_into(&entry.graph, &entry.exec, m, body))
+            entry.unsupported = true;
+        if (entry.exec && !g_profile_on) {
+            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        } else {
+            TRY(body(e));
+        }
+    }
+    if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    return OVC_OK;
+}

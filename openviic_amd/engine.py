@@ -131,6 +131,52 @@ def _ffn(dst, pwff, planes=None, mode=0):
     _lin(dst.fc1, pwff.fc1, planes, mode); _lin(dst.fc2, pwff.fc2, planes, mode); _norm(dst.ln, pwff.layer_norm)
 
 
+def _grad_slots(model):
+    """(parameter, field path in the ``ovc_model`` table) of every parameter ``ovc_forward_backward`` writes a gradient for:
+    the plain encoder / decoder's projections, norms and FFNs, the word embedding and the vocabulary projection."""
+    enc, dec = model.encoder, model.decoder
+    slots = []
+
+    def lin(path, fc):
+        slots.append((fc.weight, path + ("w",)))
+        if fc.bias is not None:
+            slots.append((fc.bias, path + ("b",)))
+
+    def norm(path, ln):
+        slots.extend(((ln.weight, path + ("g",)), (ln.bias, path + ("b",))))
+
+    def mha(path, m):
+        att = m.attention
+        for name, fc in (("q", att.fc_q), ("k", att.fc_k), ("v", att.fc_v), ("o", att.fc_o)):
+            lin(path + (name,), fc)
+        norm(path + ("ln",), m.layer_norm)
+
+    def ffn(path, pwff):
+        lin(path + ("fc1",), pwff.fc1)
+        lin(path + ("fc2",), pwff.fc2)
+        norm(path + ("ln",), pwff.layer_norm)
+
+    lin(("proj",), model.vision_embedding.proj)
+    norm(("enc_ln",), enc.layer_norm)
+    for i, layer in enumerate(enc.layers):
+        mha(("enc", i, "att"), layer.mhatt)
+        ffn(("enc", i, "ffn"), layer.pwff)
+    for i, layer in enumerate(dec.layers):
+        mha(("dec", i, "self_att"), layer.self_attn)
+        mha(("dec", i, "cross_att"), layer.enc_attn)
+        ffn(("dec", i, "ffn"), layer.pwff)
+    slots.append((dec.word_emb.components.weight, ("word_emb",)))
+    slots.append((dec.fc.weight, ("fc",)))
+    return slots
+
+
+def _set_field(desc, path, ptr):
+    obj = desc
+    for key in path[:-1]:
+        obj = obj[key] if isinstance(key, int) else getattr(obj, key)
+    setattr(obj, path[-1], ptr)
+
+
 class CaptionEngine:
     # measure GEMM tilings per shape on first use (one-off ~0.2 s, synchronises); OVC_AUTOTUNE=0 disables
     autotune = os.environ.get("OVC_AUTOTUNE", "1") != "0"
@@ -178,10 +224,12 @@ class CaptionEngine:
         # split-precision modes: the GEMM weights pre-cut into 16-bit planes (read straight from memory by the kernels)
         self._planes = _WeightPlanes(self.lib) if self.precision != "f32" and self.precut_weights else None
         self.desc = self._describe(model)
+        self._param_ptrs = tuple(p.data_ptr() for p in model.parameters())
         self._workspaces = {}    # one scratch buffer per HIP stream: concurrent batches never share state
         # the teacher-forced forward's and the scoring's own, per (stream, logp wanted): a dev-loss pass between two searches
         # leaves the search's buffer -- whose address keys its captured graphs -- where it is
         self._fw_workspaces = {}
+        self._train_workspaces = {}   # ovc_forward_backward's own, per stream
         self._steps_device = {}  # early_exit="device": the step count of each search workspace (keyed like _workspaces)
         self.last_steps_device = None
         self._tuned = set()
@@ -387,11 +435,13 @@ class CaptionEngine:
     def release(self):
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
-        for ws in list(getattr(self, "_workspaces", {}).values()) + list(getattr(self, "_fw_workspaces", {}).values()):
+        for ws in (list(getattr(self, "_workspaces", {}).values()) + list(getattr(self, "_fw_workspaces", {}).values()) +
+                   list(getattr(self, "_train_workspaces", {}).values())):
             if lib is not None:
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._workspaces = {}
         self._fw_workspaces = {}
+        self._train_workspaces = {}
         self._steps_device = {}
 
     def __del__(self):
@@ -519,6 +569,95 @@ class CaptionEngine:
         if out_size == 1:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
+
+    # -- training ---------------------------------------------------------------------------------------------------
+    def _check_trainable(self):
+        """The backward covers the plain standard transformer in fp32: anything else is refused before a launch."""
+        d = self.desc
+        if self.precision != "f32":
+            raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
+        if d.enc_kind != native.ENC_PLAIN or d.dec_kind != native.DEC_PLAIN:
+            raise native.OvcError("the training backward covers the plain Encoder / Decoder only (the meshed decoder and the "
+                                  "multilevel, geometric and cross-level encoders are not supported)")
+        model = self.model
+        mhas = [layer.mhatt for layer in model.encoder.layers]
+        mhas += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
+        if any(m.use_aoa for m in mhas):
+            raise native.OvcError("the training backward does not cover attention-on-attention gates")
+        if any(hasattr(m.attention, "m_k") for m in mhas) or d.memory:
+            raise native.OvcError("the training backward does not cover attention memory slots")
+        if not hasattr(model.decoder.word_emb, "components"):
+            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
+        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
+        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
+        if extra:
+            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
+
+    def _check_pointers(self):
+        """Re-read the pointer table when a parameter's storage moved (``p.data = ...``): in-place updates (an optimizer step)
+        keep the storage and are seen by every call as they are."""
+        ptrs = tuple(p.data_ptr() for p in self.model.parameters())
+        if ptrs != self._param_ptrs:
+            self.desc = self._describe(self.model)
+            self._param_ptrs = ptrs
+
+    def gradient_parameters(self):
+        """The parameters ``forward_backward`` returns gradients for, in the order of its list."""
+        return [p for p, _ in _grad_slots(self.model)]
+
+    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None):
+        """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
+        log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
+        ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
+        gradient, and the per-parameter views into it (fresh tensors on every call: nothing is accumulated).  Dropout is taken
+        as the identity; the caller (``BaseTransformer.xe_loss``) checks it.  Deterministic: the same bits on every call,
+        stream, graph replay and GEMM tiling."""
+        self._check_trainable()
+        d = self.desc
+        features, boxes = self._checked_inputs(features, boxes)
+        B, N = features.shape[:2]
+        T = check_caption_ids(caption_tokens, "caption_tokens", B, d.max_len, d.vocab)
+        check_caption_ids(targets, "targets", B, d.max_len, d.vocab)
+        if tuple(targets.shape) != tuple(caption_tokens.shape):
+            raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
+                tuple(targets.shape), tuple(caption_tokens.shape)))
+        need = self.lib.ovc_train_workspace_bytes(ctypes.byref(d), B, N, T)
+        if need == 0:
+            raise native.OvcError("unsupported training configuration (B={}, N={}, T={}, V={}; see ovc_train_workspace_bytes)"
+                                  .format(B, N, T, d.vocab))
+        tokens = caption_tokens.to(self.device).contiguous()
+        targets = targets.to(self.device).contiguous()
+        self._check_pointers()
+        self._refresh_derived()
+        d = self.desc
+        slots = _grad_slots(self.model)
+        sizes = [(p.numel() + 3) & ~3 for p, _ in slots]        # every gradient starts on 16 bytes
+        arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
+        table = native.Model()
+        grads, off = [], 0
+        for (p, path), size in zip(slots, sizes):
+            view = arena[off:off + p.numel()].view(p.shape)
+            _set_field(table, path, view.data_ptr())
+            grads.append(view)
+            off += size
+        stream = torch.cuda.current_stream().cuda_stream
+        ws = self._cached_workspace(self._train_workspaces, stream, need)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        graph = self.use_graph if use_graph is None else bool(use_graph)
+        check(self.lib.ovc_forward_backward(ctypes.byref(d), ctypes.byref(table), features.data_ptr(),
+                                            None if boxes is None else boxes.data_ptr(), B, N, tokens.data_ptr(),
+                                            targets.data_ptr(), T, ws.data_ptr(), need, loss.data_ptr(), 1 if graph else 0,
+                                            native.stream_handle()), "ovc_forward_backward")
+        return loss, arena, grads
+
+    def scale_gradients(self, arena, scale):
+        """``arena * scale`` into a new buffer (``ovc_scale``; ``scale`` a one-element fp32 device tensor): the autograd
+        backward's ``grad_output`` applied to the gradients of ``forward_backward``."""
+        scale = scale.reshape(1).to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(arena)
+        check(self.lib.ovc_scale(arena.data_ptr(), scale.data_ptr(), out.data_ptr(), arena.numel(), native.stream_handle()),
+              "ovc_scale")
+        return out
 
     # -- teacher-forced forward / caption scoring ------------------------------------------------------------------
     def forward(self, features, boxes, caption_tokens):

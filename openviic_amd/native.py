@@ -128,6 +128,10 @@ SIGNATURES = {
     "ovc_forward_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_forward": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                             c_void_p, c_void_p, c_int, c_void_p]),
+    "ovc_train_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
+    "ovc_forward_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),

@@ -1,0 +1,88 @@
+"""ms per training step -- ``model.xe_loss(items)`` + ``loss.backward()`` (``ovc_forward_backward``) -- at the full standard
+configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, V = 10 201), T = 20, N = 50 ragged regions.
+
+    python tools/train_step_probe.py [--batches 60 256] [--steps 20] [--warmup 5] [--out results/train_step_probe.json]
+
+Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
+end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
+times 3 -- the backward has two products per forward product -- over the step time, against the nominal 157.3 TF fp32 matrix
+rate: a whole-step rate, not a kernel's share of peak.  Needs a HIP device; there is no CPU fallback."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from openviic_amd.builders import build_model                                        # noqa: E402
+from openviic_amd.config import model_config                                         # noqa: E402
+from openviic_amd.instance import InstanceList                                       # noqa: E402
+from openviic_amd.utils.synthetic import SyntheticVocab, synthetic_features, synthetic_state_dict   # noqa: E402
+
+PEAK_F32_MATRIX = 157.3e12
+
+
+def step_flops(cfg_dims, B, N, T):
+    d, h, dk, dff, dfeat, V, Le, Ld = (cfg_dims[k] for k in ("d", "h", "dk", "dff", "dfeat", "V", "Le", "Ld"))
+    BN, R, hk = B * N, B * T, h * dk
+    f = 2 * BN * dfeat * d
+    f += Le * (2 * BN * d * 3 * hk + 4 * B * h * N * N * dk + 2 * BN * hk * d + 4 * BN * d * dff)
+    f += Ld * 2 * BN * d * 2 * hk
+    f += Ld * (2 * R * d * 3 * hk + 4 * B * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * B * h * T * N * dk
+               + 2 * R * hk * d + 4 * R * d * dff)
+    f += 2 * R * d * V
+    return 3 * f
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    V, T, N, D = 10201, 20, 50, 2048
+    vocab = SyntheticVocab(V, T)
+    cfg = model_config("standard_transformer", d_feature=D, device="cuda:0")
+    model = build_model(cfg, vocab).eval()
+    model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
+    dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
+    results = []
+    for B in args.batches:
+        g = torch.Generator().manual_seed(B)
+        tokens = torch.randint(4, V, (B, T), generator=g)
+        tokens[:, 0] = 1
+        items = InstanceList()
+        items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        items.caption_tokens = tokens.cuda()
+        items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
+        for _ in range(args.warmup):
+            model.zero_grad(set_to_none=True)
+            model.xe_loss(items).backward()
+        torch.cuda.synchronize()
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(args.steps):
+            model.zero_grad(set_to_none=True)
+            model.xe_loss(items).backward()
+        stop.record()
+        torch.cuda.synchronize()
+        ms = start.elapsed_time(stop) / args.steps
+        flops = step_flops(dims, B, N, T)
+        ws = model._fused_engine().lib.ovc_train_workspace_bytes(model._fused_engine().desc, B, N, T)
+        row = dict(B=B, T=T, N=N, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
+                   tflops=round(flops / ms / 1e9, 2), fp32_matrix_fraction=round(flops / (ms * 1e-3) / PEAK_F32_MATRIX, 4),
+                   workspace_mb=round(ws / 2 ** 20, 1))
+        results.append(row)
+        print(json.dumps(row))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

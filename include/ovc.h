@@ -328,8 +328,8 @@ int ovc_forward(const ovc_model* m, const float* features, const float* boxes, i
 
 /* Training step of the reference's cross-entropy loss (vi_trainer.py:100-119): the forward of ovc_forward, then the gradient of
  *   loss = -sum_{r: targets[r] != pad} logp[r, targets[r]] / #{r: targets[r] != pad}      (NLLLoss(ignore_index=pad), mean)
- * with respect to every trainable parameter, dropout being the identity (eval mode).  tokens / targets [B, T] int64 as in
- * ovc_forward (ids in [0, V), checked by the caller).  loss_out: ONE device float.
+ * with respect to every trainable parameter, dropout being the identity (eval mode; ovc_forward_backward_dropout below applies
+ * it).  tokens / targets [B, T] int64 as in ovc_forward (ids in [0, V), checked by the caller).  loss_out: ONE device float.
  * grads: a second ovc_model-shaped table whose pointer fields name the gradient buffers, each shaped like the parameter of the same
  * field in m; only those fields are read.  Every buffer is WRITTEN, not accumulated: proj, enc_ln, every layer's q / k / v / o
  * Linears, their norms and FFNs (weight and, where m has one, bias), word_emb (its pad_idx row gets 0) and fc.  pos_emb (frozen)
@@ -349,6 +349,41 @@ int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float
                          float* loss_out, int use_graph, ovc_stream stream);
 /* y[i] = x[i] * scale[0] for i < n, scale a device float (the autograd backward's grad_output).  x and y may be the same. */
 int ovc_scale(const float* x, const float* scale, float* y, long n, ovc_stream stream);
+
+/* Training with dropout (the reference's train() mode).  The standard transformer has one nn.Dropout per site below, each with
+ * its own p; none sits on the attention probabilities.  Site ids (fixed, independent of the layer counts):
+ *   0                          vision_embedding.dropout     on proj(features) incl. bias, before encoder.layer_norm      cols d
+ *   1 + 3 l + 0                encoder.layers.l.mhatt.dropout      on fc_o(att) incl. bias, before LN(x + .)         cols d
+ *   1 + 3 l + 1                encoder.layers.l.pwff.dropout_2     on relu(fc1(x)), the input of fc2                 cols d_ff
+ *   1 + 3 l + 2                encoder.layers.l.pwff.dropout       on fc2(.) incl. bias, before LN(x + .)            cols d
+ *   1 + 3 OVC_MAX_LAYERS + 4 l + {0, 1, 2, 3}   decoder.layers.l.{self_attn.dropout, enc_attn.dropout, pwff.dropout_2, pwff.dropout}
+ * Rows are the product's rows: b * N + n on the encoder side, b * T + t on the decoder side.
+ * Mask (counter-based, Philox4x32-10 -- the generator torch uses): idx = row * cols + col (64-bit),
+ *   r = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), site, 0), key = (lo32(seed), hi32(seed)))[idx & 3],
+ *   keep = r >= thr with thr = uint32(floor(p * 2^32 + 0.5)) (clamped to 2^32 - 1), out = keep ? x * s : 0, s = fp32(1 / (1 - p)).
+ * A pure function of (seed, site, row, col): the same masks, and so the same gradient bits, whatever the tiling, stream or graph
+ * replay.  The backward regenerates the masks instead of storing them. */
+#define OVC_DROPOUT_SITES (1 + 3 * OVC_MAX_LAYERS + 4 * OVC_MAX_LAYERS)
+typedef struct {
+    const int64_t* seed;                 /* device: the 64-bit seed of this step (read on the stream; never baked into a graph) */
+    float emb;                           /* p of every site, each in [0, 1); 0 = the identity */
+    float enc[OVC_MAX_LAYERS][3];        /* mhatt, pwff.dropout_2, pwff.dropout */
+    float dec[OVC_MAX_LAYERS][4];        /* self_attn, enc_attn, pwff.dropout_2, pwff.dropout */
+} ovc_dropout;
+
+/* ovc_forward_backward with dropout applied at every site whose p > 0 (the forward's masks in the GEMM epilogues; the backward
+ * masks the projections' gradients from the same counters).  Same models, sizes, determinism and use_graph as
+ * ovc_forward_backward; the seed is copied into the workspace outside the captured body, so a replayed graph reads each call's
+ * seed, and the p values are part of the graph's key.  Any p outside [0, 1) or a null dropout / seed: OVC_EINVAL, nothing
+ * launched.  With every p == 0 this is ovc_forward_backward (same launches, same bits, ovc_train_workspace_bytes suffices).
+ * ovc_train_dropout_workspace_bytes: bytes of workspace for calls with a site active (0 when unsupported). */
+size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T);
+int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                 const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                 float* loss_out, int use_graph, ovc_stream stream, const ovc_dropout* dropout);
+/* keep[r * cols + c] = 1 if element (r, c) of site `site` is kept under *seed and p, else 0 -- the mask the kernels apply
+ * (tests compare it with openviic_amd/dropout.py).  p in [0, 1), 0 <= site < OVC_DROPOUT_SITES. */
+int ovc_dropout_mask(const int64_t* seed, int site, long rows, long cols, float p, uint8_t* keep, ovc_stream stream);
 
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /

@@ -13,6 +13,7 @@ device without host round trips.  It needs the HIP library and a GPU; there is n
 """
 import torch
 
+from . import dropout as _dropout
 from . import engine
 from .builders.decoder_builder import build_decoder
 from .builders.encoder_builder import build_encoder
@@ -29,8 +30,8 @@ class _XeLoss(torch.autograd.Function):
     until it is freed; no ``.grad`` is touched."""
 
     @staticmethod
-    def forward(ctx, engine_, features, boxes, tokens, targets, *params):
-        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets)
+    def forward(ctx, engine_, dropout, features, boxes, tokens, targets, *params):
+        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout)
         ctx.engine, ctx.arena = engine_, arena
         ctx.layout = [(g.storage_offset(), g.shape) for g in grads]
         ctx.wanted = [p.requires_grad for p in params]
@@ -41,7 +42,7 @@ class _XeLoss(torch.autograd.Function):
         scaled = ctx.engine.scale_gradients(ctx.arena, grad_output)
         out = [scaled[off:off + shape.numel()].view(shape) if want else None
                for (off, shape), want in zip(ctx.layout, ctx.wanted)]
-        return (None, None, None, None, None) + tuple(out)
+        return (None, None, None, None, None, None) + tuple(out)
 
 
 class BaseTransformer(Module):
@@ -122,13 +123,29 @@ class BaseTransformer(Module):
         return self._fused_engine().score(input_features[self.feature_field], boxes, input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
 
-    def xe_loss(self, input_features):
+    def xe_loss(self, input_features, dropout=False, generator=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
         every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer in
-        'f32' only; dropout counts as the identity, so a model in ``train()`` mode with any dropout probability above 0 is
-        refused (set ``DROPOUT: 0`` or call ``model.eval()``)."""
-        if self.training:
+        'f32' only.
+
+        ``dropout=False``: dropout counts as the identity, so a model in ``train()`` mode with any dropout probability above 0
+        is refused (set ``DROPOUT: 0`` or call ``model.eval()``).  ``dropout=True``: in ``train()`` mode every ``nn.Dropout``
+        applies its own ``p`` as the reference's training does (``openviic_amd.dropout``; a ``p >= 1`` or a live dropout the
+        engine does not place is refused).  The step's seed is drawn on the stream from ``generator`` (default: the device's
+        CUDA generator), so ``torch.manual_seed`` reproduces a step.  In ``eval()`` mode, or with every ``p == 0``, this is the
+        ``dropout=False`` call: same bits, no random draw."""
+        if dropout:
+            probs = _dropout.model_probs(self) if self.training else {}
+            if probs:
+                eng = self._fused_engine()
+                feats = input_features[self.feature_field]
+                seed = _dropout.draw_seed(eng.device, generator)
+                boxes = input_features["region_boxes"] if self.uses_boxes else None
+                params = eng.gradient_parameters()
+                return _XeLoss.apply(eng, (probs, seed), feats, boxes, input_features["caption_tokens"],
+                                     input_features["shifted_right_caption_tokens"], *params)
+        elif self.training:
             live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
             if live:
                 raise engine.native.OvcError(
@@ -137,7 +154,7 @@ class BaseTransformer(Module):
         eng = self._fused_engine()
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         params = eng.gradient_parameters()
-        return _XeLoss.apply(eng, input_features[self.feature_field], boxes, input_features["caption_tokens"],
+        return _XeLoss.apply(eng, None, input_features[self.feature_field], boxes, input_features["caption_tokens"],
                              input_features["shifted_right_caption_tokens"], *params)
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,

@@ -3,6 +3,7 @@
 // fixed order that depends on the problem shape only -- no float atomics -- so the gradients are the same bits on every call,
 // stream, graph replay and GEMM tiling.
 #include "common.h"
+#include "dropout.h"
 
 // dst[c * ldd + r] = src[r * lds + c] for r < rows, c < cols; 0 for rows <= r < rows_pad (the padded K of a weight-gradient GEMM)
 int ovc_bw_transpose(const float* src, long lds, int rows, int cols, float* dst, long ldd, int rows_pad, hipStream_t s);
@@ -17,6 +18,15 @@ int ovc_bw_layer_norm(const float* x, const float* gamma, const float* dy, const
                       float* dx, float* prod, float* dyc, hipStream_t s);
 // g[i] = act[i] > 0 ? g[i] : 0  (ReLU backward on the stored ReLU output)
 int ovc_bw_relu(float* g, const float* act, long n, hipStream_t s);
+
+// Dropout (ovc_forward_backward_dropout).  ovc_bw_layer_norm of a norm whose input x = residual + drop(proj) has a dropout site on
+// the projection: the same dx / prod / dyc, and dproj = keep * s * dx, the projection's gradient (mask regenerated from the
+// counter, columns = d).
+int ovc_bw_layer_norm_dropout(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows, int d,
+                              float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop, hipStream_t s);
+// The FFN's inner site: act is the stored DROPPED ReLU output, nonzero iff kept and positive, so g[i] = act[i] > 0 ? g[i] * s : 0
+// needs no mask.
+int ovc_bw_relu_dropout(float* g, const float* act, float scale, long n, hipStream_t s);
 
 // Attention backward with P recomputed from q, k and the forward's mask (scores q.k / scale, masked keys excluded).  Rows pass:
 // one wave per (image, head, query) -> P, dS = P (dP - rowsum(P dP)) into [B][h][nq][nk] and dq = dS k / scale.  Keys pass: one

@@ -161,6 +161,13 @@ struct GemmLaunchOpts {
     // device-side early exit (ovc_beam_search_gated): the launch takes the GATED instance of its tiling, which reads *gate at
     // entry and returns when it is 0 (fp32 classes only).  Carried here for the same reason as tgt.
     const int32_t* gate = nullptr;
+    // training dropout (ovc_forward_backward_dropout): the launch takes the DROPOUT instance of its tiling (one-chain class, one
+    // segment, no K split, no gate / scoring / log-softmax epilogue), whose epilogue masks act(acc + bias) before the residual is
+    // added (csrc/dropout.h).  drop_seed points at the device seed; the other fields are per-model constants.
+    const int64_t* drop_seed = nullptr;
+    uint32_t drop_site = 0, drop_thr = 0;
+    float drop_scale = 1.f;
+    int drop_cols = 0;
 };
 
 // Launches C = act([A1|A2] W^T + bias) + R on `stream`; returns an OVC_* code.

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "backward.h"
+#include "dropout.h"
 
 namespace {
 
@@ -446,6 +447,18 @@ int decode_ksplit(int K) {
 
 using GemmShape = std::array<int, 7>;               // M, seg_n, nseg, K, kchains, ksplit, epilogue (0 plain, 1 stats, 2 stats_t)
 
+// Training dropout (ovc_forward_backward_dropout): per site (include/ovc.h numbering) whether it is active and its constants;
+// the seed is the training workspace's slot.  Engine::drop == nullptr everywhere else: every launch is the plain one.
+struct DropPlan {
+    const int64_t* seed;
+    bool on[OVC_DROPOUT_SITES];
+    uint32_t thr[OVC_DROPOUT_SITES];
+    float scale[OVC_DROPOUT_SITES];
+};
+constexpr int kSiteEmb = 0;
+inline int enc_site(int l, int j) { return 1 + 3 * l + j; }                        // j: 0 mhatt, 1 pwff.dropout_2, 2 pwff.dropout
+inline int dec_site(int l, int j) { return 1 + 3 * OVC_MAX_LAYERS + 4 * l + j; }   // j: 0 self_attn, 1 enc_attn, 2 / 3 pwff
+
 struct Engine {
     const ovc_model* m;
     hipStream_t stream;
@@ -454,6 +467,20 @@ struct Engine {
     std::vector<GemmShape>* dry = nullptr;           // shape enumeration: record every GEMM, launch nothing
     const int32_t* gate = nullptr;                   // device-side early exit: the gate of every launch issued next (run_decode_step
                                                      // sets it per step of a gated search; nullptr = ungated launches)
+    const DropPlan* drop = nullptr;                  // training dropout: the sites' masks (nullptr: no site is active)
+
+    bool site_on(int site) const { return drop && site >= 0 && drop->on[site]; }
+    DropoutSite drop_site(int site, int cols) const {
+        return DropoutSite{drop->seed, (uint32_t)site, drop->thr[site], drop->scale[site], cols};
+    }
+    // the launch options of a product of `cols` columns at dropout site `site` (-1: none)
+    GemmLaunchOpts drop_opts(int site, int cols) const {
+        GemmLaunchOpts o{};
+        if (!site_on(site)) return o;
+        o.drop_seed = drop->seed; o.drop_site = (uint32_t)site; o.drop_thr = drop->thr[site]; o.drop_scale = drop->scale[site];
+        o.drop_cols = cols;
+        return o;
+    }
 
     // A weight segment; in the split-precision modes with the weight's pre-cut planes (ovc_lin::planes) when the host built them
     GemmSegment seg(const ovc_lin& l, float* C, const float* A2 = nullptr) const {
@@ -499,24 +526,24 @@ struct Engine {
         return rc;
     }
 
-    // y = act(x W^T + b) + residual
-    int linear(const float* x, int K, const ovc_lin& l, const float* residual, float* y, int M, int N, int act) {
+    // y = drop(act(x W^T + b)) + residual, drop the mask of dropout site `site` (the identity when it is not active)
+    int linear(const float* x, int K, const ovc_lin& l, const float* residual, float* y, int M, int N, int act, int site = -1) {
         GemmArgs a{};
         a.A1 = x; a.lda1 = K; a.K1 = K; a.M = M; a.seg_n = N; a.nseg = 1; a.ldc = N;
         a.R = residual; a.ldr = N; a.act = act;
         a.seg[0] = seg(l, y);
-        return gemm(a);
+        return gemm(a, drop_opts(site, N));
     }
 
     // out = LayerNorm(x W^T + b + residual), rows flagged in zero_rows cleared.  With a partial-product buffer (the
     // M = B*k decode-step projections back to d_model) the GEMM runs as decode_ksplit(K) slices writing raw partial
     // products; the LayerNorm kernel sums them in slice order and applies bias and residual.
     int linear_ln(const float* x, int K, const ovc_lin& l, const float* residual, const ovc_norm& ln,
-                  const uint8_t* zero_rows, float* y_tmp, float* part, float* out, int M) {
+                  const uint8_t* zero_rows, float* y_tmp, float* part, float* out, int M, int site = -1) {
         const int d = m->d_model;
-        const int split = part && l.b && residual ? decode_ksplit(K) : 1;
+        const int split = part && l.b && residual && !site_on(site) ? decode_ksplit(K) : 1;
         if (split != 2 && split != 4) {
-            TRY(linear(x, K, l, residual, y_tmp, M, d, 0));
+            TRY(linear(x, K, l, residual, y_tmp, M, d, 0, site));
             if (dry) return OVC_OK;
             return ovc_layer_norm_gated(y_tmp, nullptr, ln.g, ln.b, nullptr, 0, zero_rows, m->ln_eps, out, M, d, stream, gate);
         }
@@ -553,9 +580,11 @@ struct Engine {
         return ovc_sigmoid_gate_gated(info, gate, x, (long)M * d, stream, this->gate);
     }
 
-    int ffn(const ovc_ffn& w, const float* x, float* ff, float* y, float* part, float* out, const uint8_t* zero_rows, int M) {
-        TRY(linear(x, m->d_model, w.fc1, nullptr, ff, M, m->d_ff, 1));
-        return linear_ln(ff, m->d_ff, w.fc2, x, w.ln, zero_rows, y, part, out, M);
+    // site_inner / site_out: the dropout sites on relu(fc1) and on fc2 (-1: none)
+    int ffn(const ovc_ffn& w, const float* x, float* ff, float* y, float* part, float* out, const uint8_t* zero_rows, int M,
+            int site_inner = -1, int site_out = -1) {
+        TRY(linear(x, m->d_model, w.fc1, nullptr, ff, M, m->d_ff, 1, site_inner));
+        return linear_ln(ff, m->d_ff, w.fc2, x, w.ln, zero_rows, y, part, out, M, site_out);
     }
 };
 
@@ -577,7 +606,7 @@ int run_encoder_inputs(Engine& e, Workspace& w, const float* features, const flo
         static const bool separate = OVC_HOOK_ENV("OVC_K1_SEPARATE") != nullptr;        // A/B switch: the round-1 mask kernel
         if (m->precision == 0 && !separate) a.zero_rows_out = w.enc_mask;
         else RUN(ovc_zero_row_mask(features, BN, m->d_feat, w.enc_mask, s));
-        TRY(e.gemm(a));
+        TRY(e.gemm(a, e.drop_opts(kSiteEmb, d)));
     }
     if (m->enc_kind == OVC_ENC_GEOMETRIC)
         RUN(ovc_box_relation_weights(boxes, B, N, m->fc_g_w, m->fc_g_b, enc_heads(m), m->d_g, m->trig, w.geometry, s));
@@ -657,7 +686,7 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
         RUN(ovc_attention(eq, ek, ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
                           m->enc_kind == OVC_ENC_GEOMETRIC ? w.geometry : nullptr, at.m_k, at.m_v, mem,
                           sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), eatt, s));
-        TRY(e.linear(eatt, hv, at.o, x, ya, BN, d, 0));
+        TRY(e.linear(eatt, hv, at.o, x, ya, BN, d, 0, enc_site(l, 0)));
         RUN(ovc_layer_norm(ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, x1, BN, d, s));
         TRY(e.aoa(at, x, x1, w.einfo, w.egate, BN));
         // layer output: straight into the level slot (multilevel, cross-level) or the ping-pong buffer
@@ -665,7 +694,7 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
                                                         : (l == m->n_enc - 1 ? w.enc_levels : x);
         if (tp && l < m->n_enc - 1) out = tp->out;
-        TRY(e.ffn(m->enc[l].ffn, x1, eff, yf, nullptr, out, w.enc_mask, BN));
+        TRY(e.ffn(m->enc[l].ffn, x1, eff, yf, nullptr, out, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         x = out;
     }
     if (m->enc_kind == OVC_ENC_CROSS_LEVEL) TRY(run_cross_level_tail(e, w, B, N));
@@ -911,7 +940,7 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
         const int smem = dl.self_att.m_k ? m->memory : 0;
         RUN(ovc_attention(sq, sk, sv, B, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
                           dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), satt, s));
-        TRY(e.linear_ln(satt, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, ys, nullptr, x1, rows));
+        TRY(e.linear_ln(satt, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, ys, nullptr, x1, rows, dec_site(l, 0)));
         TRY(e.aoa(dl.self_att, x, x1, w.info, w.gate, rows));
 
         // ---- cross-attention over every encoder level -----------------------------------------------
@@ -959,11 +988,11 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
             RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s));
             ffn_in = w.mixed;
         } else {
-            TRY(e.linear_ln(catt, hv, dl.cross_att.o, x1, dl.cross_att.ln, nullptr, yc, nullptr, x2, rows));
+            TRY(e.linear_ln(catt, hv, dl.cross_att.o, x1, dl.cross_att.ln, nullptr, yc, nullptr, x2, rows, dec_site(l, 1)));
             TRY(e.aoa(dl.cross_att, x1, x2, w.info, w.gate, rows));
             ffn_in = x2;
         }
-        TRY(e.ffn(dl.ffn, ffn_in, ff, yf, nullptr, out, w.padflag, rows));
+        TRY(e.ffn(dl.ffn, ffn_in, ff, yf, nullptr, out, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
         x = out;
     }
 
@@ -1116,7 +1145,7 @@ namespace {
 struct GraphKey {
     uint64_t model_hash; const void* ws; int B, N, k, out_size;
     int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp),
-                                   // 2 = the gated search (ovc_beam_search_gated)
+                                   // 2 = the gated search (ovc_beam_search_gated), 3 = ovc_forward_backward, 4 = the same with dropout
     bool operator<(const GraphKey& o) const {
         return std::tie(model_hash, ws, B, N, k, out_size, kind) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size, o.kind);
     }
@@ -1654,12 +1683,15 @@ struct TrainWs {
     float* ta; float* tb;         // transposed GEMM operands [max(d, d_ff, 3 h d_k)][Rmax padded to 4]
     float* P; float* dS;          // attention backward [B][h][nq][nk]
     float* part;                  // column-sum partials [ceil(Rmax / 64)][d]
+    // dropout (carve_train(..., dropout = true) only; ovc_train_dropout_workspace_bytes)
+    float* dproj;                 // [Rmax][d] gradient of a masked projection: keep * s * dy
+    int64_t* seed;                // the step's seed, copied in outside the captured body
     size_t bytes;
 };
 
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 
-TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T) {
+TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false) {
     TrainWs t{};
     t.w = carve_forward(m, base, B, N, T, 1);
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
@@ -1697,6 +1729,10 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T) {
     const size_t pdec = (size_t)B * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * N;
     t.P = a.take<float>(std::max(pdec, penc)); t.dS = a.take<float>(std::max(pdec, penc));
     t.part = a.take<float>(((R + 63) / 64) * std::max(d, dff));
+    if (dropout) {
+        t.dproj = a.take<float>(R * d);
+        t.seed = a.take<int64_t>(2);
+    }
     t.bytes = (a.off + 255) & ~(size_t)255;
     return t;
 }
@@ -1755,16 +1791,23 @@ int bw_weight(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const floa
     return OVC_OK;
 }
 
-// LayerNorm of the pre-norm sum y: t.dy = d(y) from dout; gamma / beta gradients
+// LayerNorm of the pre-norm sum y: t.dy = d(y) from dout; gamma / beta gradients.  With the dropout site `site` active on the
+// projection inside y, also t.dproj = keep * s * t.dy, that projection's gradient (proj_grad)
 int bw_norm(Engine& e, TrainWs& t, const float* y, const ovc_norm& n, const ovc_norm& gn, const float* dout, const uint8_t* zero_rows,
-            int rows) {
+            int rows, int site = -1) {
     hipStream_t s = e.stream;
     const int d = e.m->d_model;
-    RUN(ovc_bw_layer_norm(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, s));
+    if (e.site_on(site))
+        RUN(ovc_bw_layer_norm_dropout(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d), s));
+    else
+        RUN(ovc_bw_layer_norm(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, s));
     RUN(ovc_bw_colsum(t.prod, d, rows, d, t.part, out_ptr(gn.g), s));
     RUN(ovc_bw_colsum(t.dyc, d, rows, d, t.part, out_ptr(gn.b), s));
     return OVC_OK;
 }
+
+// the gradient of the projection at dropout site `site` after bw_norm: t.dy itself when the site is not active
+const float* proj_grad(const Engine& e, const TrainWs& t, int site) { return e.site_on(site) ? t.dproj : t.dy; }
 
 // dX [rows][k] = dY [rows][n] . W (+ R), W [n][k] the weight of a Linear(k -> n)
 int bw_input(Engine& e, TrainWs& t, const float* dY, int n, const ovc_lin& l, int k, float* dX, const float* R, int rows) {
@@ -1773,13 +1816,18 @@ int bw_input(Engine& e, TrainWs& t, const float* dY, int n, const ovc_lin& l, in
 }
 
 // The FFN + its AddNorm: from dout (gradient of the norm output; rows in zero_rows pass nothing) to t.dx1 = gradient of its input x
+// (dropout: ff is the stored dropped ReLU output; site_inner / site_out as in Engine::ffn)
 int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const float* x, const float* ff, const float* yf,
-           const float* dout, const uint8_t* zero_rows, int rows) {
+           const float* dout, const uint8_t* zero_rows, int rows, int site_inner = -1, int site_out = -1) {
     const int d = e.m->d_model, dff = e.m->d_ff;
-    TRY(bw_norm(e, t, yf, f.ln, gf.ln, dout, zero_rows, rows));
-    TRY(bw_weight(e, t, t.dy, d, d, ff, dff, dff, rows, f.fc2, gf.fc2));
-    TRY(bw_input(e, t, t.dy, d, f.fc2, dff, t.dff, nullptr, rows));
-    RUN(ovc_bw_relu(t.dff, ff, (long)rows * dff, e.stream));
+    TRY(bw_norm(e, t, yf, f.ln, gf.ln, dout, zero_rows, rows, site_out));
+    const float* dp = proj_grad(e, t, site_out);
+    TRY(bw_weight(e, t, dp, d, d, ff, dff, dff, rows, f.fc2, gf.fc2));
+    TRY(bw_input(e, t, dp, d, f.fc2, dff, t.dff, nullptr, rows));
+    if (e.site_on(site_inner))
+        RUN(ovc_bw_relu_dropout(t.dff, ff, e.drop->scale[site_inner], (long)rows * dff, e.stream));
+    else
+        RUN(ovc_bw_relu(t.dff, ff, (long)rows * dff, e.stream));
     TRY(bw_weight(e, t, t.dff, dff, dff, x, d, d, rows, f.fc1, gf.fc1));
     return bw_input(e, t, t.dff, dff, f.fc1, d, t.dx1, t.dy, rows);
 }
@@ -1788,11 +1836,12 @@ int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const flo
 // to dx (gradient of the layer input x, which fed q, k, v and the residual)
 int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const float* x, const float* q, const float* k,
                       const float* v, const float* att, const float* y, const float* dnorm, const uint8_t* mask, long mask_b,
-                      long mask_r, int B, int n, int h, int dk, float* dx) {
+                      long mask_r, int B, int n, int h, int dk, float* dx, int site = -1) {
     const int d = e.m->d_model, hk = h * dk, rows = B * n;
-    TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows));
-    TRY(bw_weight(e, t, t.dy, d, d, att, hk, hk, rows, at.o, ga.o));
-    TRY(bw_input(e, t, t.dy, d, at.o, hk, t.datt, nullptr, rows));
+    TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows, site));
+    const float* dp = proj_grad(e, t, site);
+    TRY(bw_weight(e, t, dp, d, d, att, hk, hk, rows, at.o, ga.o));
+    TRY(bw_input(e, t, dp, d, at.o, hk, t.datt, nullptr, rows));
     AttnBwdArgs p{};
     p.q = q; p.ldq = hk; p.k = k; p.v = v; p.ldkv = hk; p.dout = t.datt; p.ldo = hk;
     p.mask = mask; p.mask_b = mask_b; p.mask_r = mask_r;
@@ -1817,11 +1866,12 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, i
     const ovc_dec_layer& gl = gr->dec[l];
     const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * T, BN = B * N;
     // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(x2)
-    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.x2, p.ff, p.yf, dout, w.padflag, rows));
+    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.x2, p.ff, p.yf, dout, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
     // cross-attention AddNorm -> t.dy = d(yc), the residual's share of d(x1)
-    TRY(bw_norm(e, t, p.yc, dl.cross_att.ln, gl.cross_att.ln, t.dx1, nullptr, rows));
-    TRY(bw_weight(e, t, t.dy, d, d, p.attc, hk, hk, rows, dl.cross_att.o, gl.cross_att.o));
-    TRY(bw_input(e, t, t.dy, d, dl.cross_att.o, hk, t.datt, nullptr, rows));
+    TRY(bw_norm(e, t, p.yc, dl.cross_att.ln, gl.cross_att.ln, t.dx1, nullptr, rows, dec_site(l, 1)));
+    const float* dp = proj_grad(e, t, dec_site(l, 1));
+    TRY(bw_weight(e, t, dp, d, d, p.attc, hk, hk, rows, dl.cross_att.o, gl.cross_att.o));
+    TRY(bw_input(e, t, dp, d, dl.cross_att.o, hk, t.datt, nullptr, rows));
     const size_t kvoff = (size_t)l * BN * hk;
     AttnBwdArgs a{};
     a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
@@ -1839,7 +1889,7 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, i
     TRY(bw_mm(e, t.dkv, 2 * hk, BN, 2 * hk, t.wt, d, denc_next, denc_prev));
     // masked self-attention over the caption
     return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
-                             B, T, h, dk, dxin);
+                             B, T, h, dk, dxin, dec_site(l, 0));
 }
 
 int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T) {
@@ -1882,16 +1932,17 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
         const ovc_enc_layer& el = m->enc[l];
         const ovc_enc_layer& gl = gr->enc[l];
         const float* xin = l == 0 ? w.xe[0] : t.tape.enc[l - 1].out;
-        TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN));
-        TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur]));
+        TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
+        TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
+                              enc_site(l, 0)));
         dout = t.g[cur];
         cur ^= 1;
     }
     // feature embedding: encoder.layer_norm over the projection (the sinusoid added after it has no parameters)
     e.gemm_class = 0;
-    TRY(bw_norm(e, t, w.ey, m->enc_ln, gr->enc_ln, dout, nullptr, BN));
+    TRY(bw_norm(e, t, w.ey, m->enc_ln, gr->enc_ln, dout, nullptr, BN, kSiteEmb));
     const int bnp = (int)pad4(BN);
-    RUN(ovc_bw_transpose(t.dy, d, BN, d, t.ta, bnp, bnp, s));
+    RUN(ovc_bw_transpose(proj_grad(e, t, kSiteEmb), d, BN, d, t.ta, bnp, bnp, s));
     TRY(bw_mm(e, t.ta, bnp, d, bnp, t.feat_t, m->d_feat, out_ptr(gr->proj.w)));
     if (m->proj.b) RUN(ovc_bw_rowsum(t.ta, bnp, d, BN, out_ptr(gr->proj.b), s));
     return OVC_OK;
@@ -1904,19 +1955,27 @@ extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, in
     return carve_train(m, nullptr, B, N, T).bytes;
 }
 
-extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
-                                    const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
-                                    float* loss_out, int use_graph, ovc_stream stream) {
-    (void)boxes;       // the plain encoder reads no boxes
+namespace {
+
+// ovc_forward_backward (drop == nullptr) and ovc_forward_backward_dropout (drop: at least one site active; seed = the caller's)
+int forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, const int64_t* tokens,
+                     const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* loss_out, int use_graph,
+                     ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash) {
     if (!train_ok(m, B, N, T) || !grads || !grads_ok(m, grads) || !features || !tokens || !targets || !workspace || !loss_out)
         return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    TrainWs t = carve_train(m, workspace, B, N, T);
+    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr);
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const int rows = B * T, BN = B * N;
+    if (drop) {
+        // the seed slot is refreshed here, outside the captured body: a replayed graph reads this call's seed
+        if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        drop->seed = t.seed;
+        e.drop = drop;
+    }
 
     // the kernels that read the caller's inputs, outside the captured body
     TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
@@ -1925,13 +1984,18 @@ extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, 
     OVC_RETURN_IF_LAUNCH_FAILED();
     TRY(ovc_bw_tokens(tokens, rows, m->vocab, t.tok, e.stream));
     TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
-    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T); };
+    auto body = [&](Engine& ce) {
+        ce.drop = drop;
+        return issue_train_body(ce, t, grads, B, N, T);
+    };
     if (!use_graph) {
         TRY(body(e));
     } else {
-        // the body writes the gradient buffers: their table is part of the key
-        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull), workspace, B, N, T, 0};
-        key.kind = 3;
+        // the body writes the gradient buffers: their table is part of the key; so are the dropout constants (baked into the
+        // launches), never the seed (read from the workspace slot)
+        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ drop_hash, workspace, B,
+                     N, T, 0};
+        key.kind = drop ? 4 : 3;
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         GraphEntry& entry = g_graphs[key];
         entry.calls += 1;
@@ -1948,4 +2012,47 @@ extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, 
     }
     if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     return OVC_OK;
+}
+
+}  // namespace
+
+extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                    const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                    float* loss_out, int use_graph, ovc_stream stream) {
+    (void)boxes;       // the plain encoder reads no boxes
+    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
+                            nullptr, nullptr, 0);
+}
+
+extern "C" size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T) {
+    if (!train_ok(m, B, N, T)) return 0;
+    return carve_train(m, nullptr, B, N, T, true).bytes;
+}
+
+extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                            int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                            size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                            const ovc_dropout* dropout) {
+    (void)boxes;
+    if (!dropout || !dropout->seed || !m) return OVC_EINVAL;
+    float p[OVC_DROPOUT_SITES] = {};
+    p[kSiteEmb] = dropout->emb;
+    for (int l = 0; l < OVC_MAX_LAYERS; ++l) {
+        for (int j = 0; j < 3; ++j) p[enc_site(l, j)] = dropout->enc[l][j];
+        for (int j = 0; j < 4; ++j) p[dec_site(l, j)] = dropout->dec[l][j];
+    }
+    DropPlan plan{};
+    bool any = false;
+    for (int i = 0; i < OVC_DROPOUT_SITES; ++i) {
+        if (!(p[i] >= 0.f && p[i] < 1.f)) return OVC_EINVAL;         // NaN included
+        plan.on[i] = p[i] > 0.f;
+        plan.thr[i] = ovc_dropout_threshold(p[i]);
+        plan.scale[i] = ovc_dropout_scale(p[i]);
+        any = any || plan.on[i];
+    }
+    if (!any)
+        return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
+                                nullptr, nullptr, 0);
+    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
+                            &plan, dropout->seed, hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full);
 }

@@ -45,6 +45,7 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "dropout.h"
 
 namespace {
 
@@ -172,10 +173,14 @@ __device__ __forceinline__ void tile_coords_fast(const TileMap& t, int bid, int&
 // descriptors: one per-lane byte offset (first row of the lane's 16, its column) and a scalar row offset per accumulator
 // register; rows past M fall outside the descriptor and are dropped by the hardware, columns past seg_n get an
 // out-of-range offset.  (m0, n0) = first row / column of the wave's tiles.
-template <int TM, int TN>
+// kDrop (gemm_f32_mfma_dropout): act(acc + bias) is masked and scaled (csrc/dropout.h) before the residual is added.
+template <int TM, int TN, bool kDrop = false>
 __device__ __forceinline__ void store_wave_tiles(const GemmArgs& p, const float* __restrict__ bias, float* __restrict__ Cseg,
-                                                 const f32x16 (&acc)[TM][TN], int m0, int n0, int lane) {
+                                                 const f32x16 (&acc)[TM][TN], int m0, int n0, int lane,
+                                                 const DropoutSite& drop = DropoutSite{}) {
     float* __restrict__ C = Cseg + (size_t)blockIdx.y * p.part_stride;
+    uint64_t drop_seed = 0;
+    if constexpr (kDrop) drop_seed = (uint64_t)*drop.seed;
     const int half = lane >> 5;
     const bool has_res = p.R != nullptr;                          // uniform
     const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(C, 0, p.M * p.ldc * 4, 0x00020000);
@@ -195,6 +200,18 @@ __device__ __forceinline__ void store_wave_tiles(const GemmArgs& p, const float*
             for (int r = 0; r < 16; ++r) {
                 const float v = acc[i][j][r] + bv;
                 out[r] = p.act == 1 ? fmaxf(v, 0.f) : v;
+            }
+            if constexpr (kDrop) {
+                // the 16 keep decisions into a bit mask first (a rolled loop: sixteen unrolled Philox blocks are too much code),
+                // then the registers with compile-time indices
+                uint32_t keep = 0;
+#pragma unroll 1
+                for (int r = 0; r < 16; ++r) {
+                    const uint64_t row = (uint64_t)(mbase + (r & 3) + 8 * (r >> 2));
+                    keep |= (ovc_dropout_keep(drop_seed, drop.site, row * (uint64_t)drop.cols + (uint64_t)n, drop.thr) ? 1u : 0u) << r;
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) out[r] = (keep >> r) & 1u ? out[r] * drop.scale : 0.f;
             }
             if (has_res) {
                 float res[16];
@@ -341,6 +358,16 @@ __global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void g
 #undef OVC_GEMM_F32_EPILOGUE
 }
 
+// The dropout instance (GemmLaunchOpts::drop_seed, training): gemm_f32_mfma with the masked epilogue; one-chain tilings only.
+template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
+__global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void gemm_f32_mfma_dropout(TileMap tmap, GemmArgs p,
+                                                                                                   DropoutSite drop) {
+#define OVC_GEMM_F32_EPILOGUE \
+    store_wave_tiles<Cfg::TM, Cfg::TN, true>(p, seg_bias, seg_C, acc[0], m0 + wm * Cfg::kWaveM, n0 + wn * Cfg::kWaveN, lane, drop)
+#include "gemm_f32_body.inc"
+#undef OVC_GEMM_F32_EPILOGUE
+}
+
 // The scoring epilogue (GemmLaunchOpts::tgt_logit) of the transposed vocabulary product: one-chain instances only, the class that
 // product runs in.  Stores the block pieces and the target logits (store_wave_tiles_score), no C tile.
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
@@ -426,6 +453,29 @@ int launch_score_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchO
     }
 }
 
+// The dropout instance of a one-chain tiling (GemmLaunchOpts::drop_seed).
+template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
+int launch_dropout_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts, const TileMap& map, dim3 grid3,
+                          size_t lds_bytes) {
+    if constexpr (WK * NC == 1) {
+        static std::once_flag attr_once;
+        std::call_once(attr_once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_dropout<BM, BN, WM, WN, WK, BK, NC>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        });
+        const DropoutSite drop{opts.drop_seed, opts.drop_site, opts.drop_thr, opts.drop_scale, opts.drop_cols};
+        if (opts.start && opts.stop)
+            hipExtLaunchKernelGGL((gemm_f32_mfma_dropout<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), (uint32_t)lds_bytes, stream,
+                                  opts.start, opts.stop, 0, map, a, drop);
+        else
+            hipLaunchKernelGGL((gemm_f32_mfma_dropout<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), lds_bytes, stream, map, a, drop);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        return OVC_OK;
+    } else {
+        return OVC_EINVAL;           // ovc_gemm_launch refuses the dropout epilogue outside the one-chain class
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
 int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
     using Cfg = TileConfig<BM, BN, WM, WN, WK, BK, NC>;
@@ -447,6 +497,7 @@ int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& o
     // opts.copies (tuner only): gridDim.z identical copies of the product in one launch (the kernel ignores
     // blockIdx.z), a proxy for "this many batches in flight" that needs no extra streams.
     const dim3 grid3(grid, slices, opts.copies > 1 ? opts.copies : 1);
+    if (opts.drop_seed) return launch_dropout_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, grid3, lds_bytes);
     if (opts.gate) {
         static std::once_flag gated_attr_once;
         std::call_once(gated_attr_once, [&] {
@@ -738,6 +789,9 @@ int ovc_gemm_launch(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts&
     if (opts.tgt_logit && (!opts.tgt || !a.stats_t || args_chains(a) != 1)) return OVC_EINVAL;
     // gated instances (device-side early exit): the fp32 classes, never with the scoring epilogue
     if (opts.gate && (opts.tgt_logit || a.kchains > kSplitClass)) return OVC_EINVAL;
+    // dropout instances (training): one chain, one segment, no K split, no other epilogue, the whole column range masked
+    if (opts.drop_seed && (args_chains(a) != 1 || opts.gate || opts.tgt_logit || a.nseg != 1 || a.ksplit > 1 || a.stats || a.stats_t ||
+                           opts.drop_cols != a.seg_n)) return OVC_EINVAL;
     if (a.K2 > 0 && (a.K1 % 32)) return OVC_EINVAL;      // the A1|A2 seam must fall on a K-tile boundary
     if (a.ksplit > 1) {                                  // raw partial products: see GemmArgs::ksplit
         if (a.ksplit > kMaxKSplit || a.nseg != 1 || a.K2 || a.R || a.act || a.seg[0].bias) return OVC_EINVAL;

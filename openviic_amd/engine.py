@@ -18,6 +18,7 @@ import threading
 
 import torch
 
+from . import dropout as _dropout
 from . import native
 from .native import check
 
@@ -605,13 +606,17 @@ class CaptionEngine:
         """The parameters ``forward_backward`` returns gradients for, in the order of its list."""
         return [p for p, _ in _grad_slots(self.model)]
 
-    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None):
+    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
         gradient, and the per-parameter views into it (fresh tensors on every call: nothing is accumulated).  Dropout is taken
         as the identity; the caller (``BaseTransformer.xe_loss``) checks it.  Deterministic: the same bits on every call,
-        stream, graph replay and GEMM tiling."""
+        stream, graph replay and GEMM tiling.
+
+        ``dropout=(probs, seed)`` applies dropout (``ovc_forward_backward_dropout``): ``probs`` maps site ids
+        (``openviic_amd.dropout``) to ``p``, ``seed`` is a one-element int64 device tensor.  The masks are a function of
+        ``(seed, site, row, col)`` only, so the result is as deterministic as without; with no ``p > 0`` this is the plain call."""
         self._check_trainable()
         d = self.desc
         features, boxes = self._checked_inputs(features, boxes)
@@ -621,7 +626,18 @@ class CaptionEngine:
         if tuple(targets.shape) != tuple(caption_tokens.shape):
             raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
                 tuple(targets.shape), tuple(caption_tokens.shape)))
-        need = self.lib.ovc_train_workspace_bytes(ctypes.byref(d), B, N, T)
+        table_drop = None
+        if dropout is not None:
+            probs, seed = dropout
+            for site, p in probs.items():
+                if not 0 <= site < _dropout.NUM_SITES or not 0 <= p < 1:
+                    raise native.OvcError("dropout: site {} p = {} (sites 0..{}, 0 <= p < 1)".format(site, p, _dropout.NUM_SITES - 1))
+            if any(p > 0 for p in probs.values()):
+                if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+                    raise native.OvcError("dropout: the seed must be a one-element int64 device tensor")
+                table_drop = _dropout.native_table(probs, seed)
+        sizer = self.lib.ovc_train_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_workspace_bytes
+        need = sizer(ctypes.byref(d), B, N, T)
         if need == 0:
             raise native.OvcError("unsupported training configuration (B={}, N={}, T={}, V={}; see ovc_train_workspace_bytes)"
                                   .format(B, N, T, d.vocab))
@@ -644,10 +660,13 @@ class CaptionEngine:
         ws = self._cached_workspace(self._train_workspaces, stream, need)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         graph = self.use_graph if use_graph is None else bool(use_graph)
-        check(self.lib.ovc_forward_backward(ctypes.byref(d), ctypes.byref(table), features.data_ptr(),
-                                            None if boxes is None else boxes.data_ptr(), B, N, tokens.data_ptr(),
-                                            targets.data_ptr(), T, ws.data_ptr(), need, loss.data_ptr(), 1 if graph else 0,
-                                            native.stream_handle()), "ovc_forward_backward")
+        args = (ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
+                tokens.data_ptr(), targets.data_ptr(), T, ws.data_ptr(), need, loss.data_ptr(), 1 if graph else 0,
+                native.stream_handle())
+        if table_drop is None:
+            check(self.lib.ovc_forward_backward(*args), "ovc_forward_backward")
+        else:
+            check(self.lib.ovc_forward_backward_dropout(*args, ctypes.byref(table_drop)), "ovc_forward_backward_dropout")
         return loss, arena, grads
 
     def scale_gradients(self, arena, scale):

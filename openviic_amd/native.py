@@ -50,6 +50,12 @@ class DecLayer(ctypes.Structure):
     _fields_ = [("self_att", Mha), ("cross_att", Mha), ("ffn", Ffn), ("alpha", Lin * OVC_MAX_LEVELS)]
 
 
+class Dropout(ctypes.Structure):
+    """``ovc_dropout``: the seed's device pointer and ``p`` per site (``openviic_amd.dropout`` numbers the sites)."""
+    _fields_ = [("seed", c_void_p), ("emb", c_float), ("enc", (c_float * 3) * OVC_MAX_LAYERS),
+                ("dec", (c_float * 4) * OVC_MAX_LAYERS)]
+
+
 class Model(ctypes.Structure):
     _fields_ = [
         ("abi", c_int32), ("enc_kind", c_int32), ("dec_kind", c_int32),
@@ -132,6 +138,10 @@ SIGNATURES = {
     "ovc_forward_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "ovc_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "ovc_train_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
+    "ovc_forward_backward_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                             c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Dropout)]),
+    "ovc_dropout_mask": (c_int, [c_void_p, c_int, c_long, c_long, c_float, c_void_p, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),

@@ -1,7 +1,10 @@
 """ms per training step -- ``model.xe_loss(items)`` + ``loss.backward()`` (``ovc_forward_backward``) -- at the full standard
 configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, V = 10 201), T = 20, N = 50 ragged regions.
 
-    python tools/train_step_probe.py [--batches 60 256] [--steps 20] [--warmup 5] [--out results/train_step_probe.json]
+    python tools/train_step_probe.py [--batches 60 256] [--steps 20] [--warmup 5] [--dropout] [--out results/train_step_probe.json]
+
+--dropout: the model in train() mode with the reference's DROPOUT 0.1 at every site, ``model.xe_loss(items, dropout=True)``
+(ovc_forward_backward_dropout; a fresh seed per step).
 
 Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
 end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dropout", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -49,6 +53,8 @@ def main():
     cfg = model_config("standard_transformer", d_feature=D, device="cuda:0")
     model = build_model(cfg, vocab).eval()
     model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
+    if args.dropout:
+        model.train()
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     results = []
     for B in args.batches:
@@ -61,19 +67,21 @@ def main():
         items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)
-            model.xe_loss(items).backward()
+            model.xe_loss(items, dropout=args.dropout).backward()
         torch.cuda.synchronize()
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         for _ in range(args.steps):
             model.zero_grad(set_to_none=True)
-            model.xe_loss(items).backward()
+            model.xe_loss(items, dropout=args.dropout).backward()
         stop.record()
         torch.cuda.synchronize()
         ms = start.elapsed_time(stop) / args.steps
         flops = step_flops(dims, B, N, T)
-        ws = model._fused_engine().lib.ovc_train_workspace_bytes(model._fused_engine().desc, B, N, T)
-        row = dict(B=B, T=T, N=N, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
+        lib = model._fused_engine().lib
+        sizer = lib.ovc_train_dropout_workspace_bytes if args.dropout else lib.ovc_train_workspace_bytes
+        ws = sizer(model._fused_engine().desc, B, N, T)
+        row = dict(B=B, T=T, N=N, dropout=args.dropout, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
                    tflops=round(flops / ms / 1e9, 2), fp32_matrix_fraction=round(flops / (ms * 1e-3) / PEAK_F32_MATRIX, 4),
                    workspace_mb=round(ws / 2 ** 20, 1))
         results.append(row)

@@ -385,6 +385,24 @@ int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, con
  * (tests compare it with openviic_amd/dropout.py).  p in [0, 1), 0 <= site < OVC_DROPOUT_SITES. */
 int ovc_dropout_mask(const int64_t* seed, int site, long rows, long cols, float p, uint8_t* keep, ovc_stream stream);
 
+/* Self-critical sequence training: the gradient of a beam search's log-probabilities (the reference's train_scst,
+ * vi_trainer.py:121-158).  ids [B][S][T] are S generated sequences per image (the search's outputs), grad_logp [B][S][T] the
+ * gradient g of the loss with respect to the search's log_probs.  With e(b,s) = the first t with ids[b,s,t] == eos_idx (T-1 if
+ * none), the search's log_probs[b,s,t] for t <= e(b,s) is the teacher-forced log-probability of ids[b,s,t] after <bos>,
+ * ids[b,s,0..t-1] on image b, and 0 after it (beam_search.py:47-52, 85-92).  Writes (not accumulates) into the gradient table
+ * `grads` the gradient of  sum_{b,s,t <= e(b,s)} g[b,s,t] * logp[b,s,t]  for every parameter ovc_forward_backward covers; g after
+ * e(b,s) is ignored whatever it holds.  logp_out [B][S][T] (optional) receives the recomputed logp, 0 for t > e(b,s).
+ * The encoder and the cross-attention keys / values run once per image; image b's cross-attention is one attention over its S*T
+ * decoder rows (rows laid out (b, s, t)).  Models, precision, vocabulary and determinism as ovc_forward_backward, with B*S*T rows
+ * in its size bounds; S >= 1.  Ids outside [0, V) read the nearest valid row (callers check them).  Dropout is the identity.
+ * ids and grad_logp are read outside the captured body: with use_graph a replayed graph sees each call's values.
+ * ovc_train_beams_workspace_bytes: bytes of workspace, 0 when unsupported (ovc_sequence_backward then returns OVC_EINVAL,
+ * nothing launched). */
+size_t ovc_train_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N, int S,
+                          const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out,
+                          int use_graph, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

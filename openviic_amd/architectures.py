@@ -45,6 +45,33 @@ class _XeLoss(torch.autograd.Function):
         return (None, None, None, None, None, None) + tuple(out)
 
 
+class _BeamLogProbs(torch.autograd.Function):
+    """The search's log-probabilities with a gradient (self-critical sequence training, ``vi_trainer.py:121-158``).  ``forward``
+    returns a copy of the fused search's ``log_probs``; ``backward`` runs ``ovc_sequence_backward`` on the search's ids with
+    ``grad_output``: a teacher-forced recompute of the generated sequences and its backward, equal to differentiating the
+    reference's search (``beam_search.py:85-92``).  The parameters are saved for backward, so an in-place update between the
+    search and ``backward()`` (an optimizer step) raises torch's in-place error instead of differentiating other weights."""
+
+    @staticmethod
+    def forward(ctx, engine_, refusal, features, boxes, ids, log_probs, *params):
+        ctx.engine, ctx.refusal = engine_, refusal
+        ctx.features, ctx.boxes, ctx.ids = features, boxes, ids
+        ctx.save_for_backward(*params)
+        return log_probs.clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        params = ctx.saved_tensors           # raises if a parameter was modified in place since the search
+        if ctx.refusal is not None:
+            raise engine.native.OvcError(ctx.refusal)
+        ids = ctx.ids if ctx.ids.dim() == 3 else ctx.ids[:, None]
+        g = grad_output.reshape(ids.shape)
+        _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g)
+        by_param = {id(p): gr for p, gr in zip(ctx.engine.gradient_parameters(), grads)}
+        out = tuple(by_param.get(id(p)) if p.requires_grad else None for p in params)
+        return (None, None, None, None, None, None) + out
+
+
 class BaseTransformer(Module):
     feature_field = "region_features"
     uses_boxes = False
@@ -164,16 +191,36 @@ class BaseTransformer(Module):
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
         reference's host loop (``modules/beam_search.py``) over the step-wise API -- every operator
         still native -- and exists for parity checks of ``step`` / ``statefulness``.
+
+        Fused, in ``train()`` mode with gradients enabled: the returned ``log_probs`` carry a gradient (``_BeamLogProbs``), so
+        the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard transformer in 'f32'
+        with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
         """
         if fused:
             boxes = input_features["region_boxes"] if self.uses_boxes else None
-            return self._fused_engine().beam_search(input_features[self.feature_field], boxes, batch_size, beam_size,
-                                            out_size=out_size, return_probs=return_probs, early_exit=kwargs.get("early_exit"))
+            feats = input_features[self.feature_field]
+            out = self._fused_engine().beam_search(feats, boxes, batch_size, beam_size, out_size=out_size,
+                                                   return_probs=return_probs, early_exit=kwargs.get("early_exit"))
+            params = [p for p in self.parameters() if p.requires_grad]
+            if self.training and torch.is_grad_enabled() and params:
+                out = (out[0], self._scst_log_probs(feats, boxes, out[0], out[1], params)) + tuple(out[2:])
+            return out
         searcher = BeamSearch(model=self, max_len=self.max_len, eos_idx=self.eos_idx, beam_size=beam_size,
                               b_s=batch_size, device=self.device)
         with self.statefulness(batch_size):
             self.encoder_features, self.encoder_padding_mask = self.encoder_forward(input_features)
             return searcher.apply(out_size, return_probs, **kwargs)
+
+    def _scst_log_probs(self, features, boxes, ids, log_probs, params):
+        """The search's ``log_probs`` as a function of ``params`` (``_BeamLogProbs``): what the reference's ``train_scst`` backpropagates
+        through.  Anything the backward does not cover raises from ``backward()``, not here: the search itself runs for every model."""
+        refusal = None
+        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+        if live:
+            refusal = ("beam_search: the model is in train() mode with dropout > 0 ({}); the engine's search and its backward take "
+                       "dropout as the identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
+        return _BeamLogProbs.apply(self._fused_engine(), refusal, features.detach(), None if boxes is None else boxes.detach(),
+                                   ids, log_probs, *params)
 
 
 @META_ARCHITECTURE.register()

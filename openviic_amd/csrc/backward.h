@@ -49,6 +49,10 @@ int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s);
 // transposed [V][ldt] and row-major [rows][ldv] (padding 0).
 int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, float* w_row,
                 float* loss, float* dl_t, float* dl, long ldv, hipStream_t s);
+// The dlogit of ovc_bw_xent with caller-supplied row weights (no loss): dlogit = (softmax - onehot(tgt)) w_row
+// (ovc_sequence_backward: w_row = -grad_logp up to each sequence's first <eos>, 0 after it).
+int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, const float* w_row, int rows, int V,
+                  float* dl_t, float* dl, long ldv, hipStream_t s);
 // Word-embedding backward: out[w, :] = sum over rows r with tok[r] == w (ascending r) of dx[r, :]; the pad row 0.
 int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s);
 // tok32[r] = clamp(tokens[r], 0, V-1)

@@ -368,6 +368,14 @@ int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t
     return OVC_OK;
 }
 
+int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, const float* w_row, int rows, int V,
+                  float* dl_t, float* dl, long ldv, hipStream_t s) {
+    hipLaunchKernelGGL(bw_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, tgt, w_row,
+                       rows, V, dl_t, dl, ldv);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s) {
     if (d > 2048) return OVC_EINVAL;
     hipLaunchKernelGGL(bw_embedding_kernel, dim3(V), dim3(256), 0, s, tok, rows, pad, dx, d, out);

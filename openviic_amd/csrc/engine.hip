@@ -250,11 +250,11 @@ constexpr int kFusedVocabBlocks = 512;
 
 // ovc_forward: rows = B*T decoder rows.  With want_logp the transposed logits [V][rows padded to 4] are kept; scoring alone keeps
 // only the block pieces and one logit per row.  Above kFusedVocabBlocks the row-major logits [rows][V] and, for scoring, the
-// log-probabilities they turn into.
-Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int want_logp) {
+// log-probabilities they turn into.  S > 1 (ovc_sequence_backward): S sequences per image, rows = B*S*T laid out (b, s, t).
+Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int want_logp, int S = 1) {
     Workspace w{};
     Bump a{reinterpret_cast<char*>(base), 0};
-    const size_t rows = (size_t)B * T, d = m->d_model, V = m->vocab;
+    const size_t rows = (size_t)B * S * T, d = m->d_model, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels;
     carve_encoder(w, a, m, B, N);
     w.x = a.take<float>(rows * d); w.x1 = a.take<float>(rows * d); w.x2 = a.take<float>(rows * d); w.y = a.take<float>(rows * d);
@@ -419,6 +419,38 @@ __global__ __launch_bounds__(256) void tf_logp_kernel(const float* __restrict__ 
         const int row = r0 + i;
         if (row < rows) logp[(size_t)row * V + w] = (tile[lane][i] - lse[2 * row]) - lse[2 * row + 1];
     }
+}
+
+// ---- sequence backward (ovc_sequence_backward) ---------------------------------------------------
+// One wave per sequence q (rows q*T .. q*T + T-1): e = the first t with ids[q, t] == eos (T-1 if none); the teacher-forced
+// inputs tok = <bos>, ids[q, 0..T-2] and targets tgt = ids[q, :] for tf_inputs_kernel; keep[r] = t <= e, and the dlogit's row weight
+// w_row[r] = -grad[r] where kept, exactly 0 elsewhere whatever grad holds there (beam_search.py:47-52 masks those log-probabilities).
+// Row r of the recompute is the step-t decode of the search's beam q: the mapping a search-side mask key would follow.
+__global__ __launch_bounds__(256) void seq_inputs_kernel(const int64_t* __restrict__ ids, const float* __restrict__ grad, int nseq,
+                                                         int T, int bos, int eos, int64_t* __restrict__ tok, int64_t* __restrict__ tgt,
+                                                         uint8_t* __restrict__ keep, float* __restrict__ w_row) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nseq) return;
+    const size_t o = (size_t)q * T;
+    int first = T;
+    for (int t = lane; t < T; t += 64)
+        if (ids[o + t] == eos) { first = t; break; }
+    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off));
+    const int e = first < T ? first : T - 1;
+    for (int t = lane; t < T; t += 64) {
+        tok[o + t] = t == 0 ? (int64_t)bos : ids[o + t - 1];
+        tgt[o + t] = ids[o + t];
+        keep[o + t] = t <= e ? 1 : 0;
+        w_row[o + t] = t <= e ? -grad[o + t] : 0.f;
+    }
+}
+
+// logp[r] = the recomputed log-probability of the target where kept, 0 after the first <eos> (bw_loss_kernel's formula)
+__global__ void seq_logp_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                const int32_t* __restrict__ tgt, const uint8_t* __restrict__ keep, int rows, float* __restrict__ logp) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) logp[r] = keep[r] ? (logits_t[(size_t)tgt[r] * ldt + r] - lse[2 * r]) - lse[2 * r + 1] : 0.f;
 }
 
 // Vocabularies above kFusedVocabBlocks blocks: token_logp[row] = logp[row, target] (0 where the target is <pad>).
@@ -912,11 +944,14 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
 // class (M = B*T rows, like the encoder's), so the decoder outputs are those of the operator path (ovc_linear) bit for bit.
 // Vocabulary: up to kFusedVocabBlocks blocks the transposed product of the search with its block pieces (want_logp: the logits are
 // stored; scoring: gemm_f32_mfma_score keeps only each row's target logit); beyond, the row-major logits.
-int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_logp) {
+// S > 1 (ovc_sequence_backward): S sequences per image, rows (b, s, t).  The self-attention runs over the B*S sequences, the
+// cross-attention of image b over its S*T rows at once (nq = S*T against the image's N keys, the per-image mask): the encoder and
+// the cross keys / values are computed once per image.  S = 1 is the call above, launch for launch.
+int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_logp, int S = 1) {
     const ovc_model* m = e.m;
     hipStream_t s = e.stream;
     const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels;
-    const int rows = B * T, BN = B * N;
+    const int rows = B * S * T, BN = B * N;
     const float scale = sqrtf((float)m->d_k);
     e.gemm_class = 2;
     e.kchains = 1;
@@ -938,7 +973,7 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
         a.seg[2] = e.seg(dl.self_att.v, sv);
         TRY(e.gemm(a));
         const int smem = dl.self_att.m_k ? m->memory : 0;
-        RUN(ovc_attention(sq, sk, sv, B, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
+        RUN(ovc_attention(sq, sk, sv, B * S, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
                           dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), satt, s));
         TRY(e.linear_ln(satt, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, ys, nullptr, x1, rows, dec_site(l, 0)));
         TRY(e.aoa(dl.self_att, x, x1, w.info, w.gate, rows));
@@ -948,7 +983,7 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
         const int cmem = dl.cross_att.m_k ? m->memory : 0;
         for (int lvl = 0; lvl < lv; ++lvl) {
             const size_t off = ((size_t)l * lv + lvl) * BN * hk;
-            RUN(ovc_attention(cq, w.kx + off, w.vx + off, B, T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
+            RUN(ovc_attention(cq, w.kx + off, w.vx + off, B, S * T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
                               dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
                               catt + (size_t)lvl * rows * hv, s));
         }
@@ -1040,10 +1075,10 @@ int finish_forward(Engine& e, Workspace& w, int B, int T, float* logp_out, float
     return OVC_OK;
 }
 
-int issue_forward_body(Engine& e, Workspace& w, int B, int N, int T, int want_logp) {
+int issue_forward_body(Engine& e, Workspace& w, int B, int N, int T, int want_logp, int S = 1) {
     TRY(run_encoder_layers(e, w, B, N));
     TRY(project_cross_kv(e, w, B, N));
-    return run_forward_decoder(e, w, B, N, T, want_logp);
+    return run_forward_decoder(e, w, B, N, T, want_logp, S);
 }
 
 bool forward_ok(const ovc_model* m, int B, int N, int T) {
@@ -1145,7 +1180,8 @@ namespace {
 struct GraphKey {
     uint64_t model_hash; const void* ws; int B, N, k, out_size;
     int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp),
-                                   // 2 = the gated search (ovc_beam_search_gated), 3 = ovc_forward_backward, 4 = the same with dropout
+                                   // 2 = the gated search (ovc_beam_search_gated), 3 = ovc_forward_backward, 4 = the same with dropout,
+                                   // 5 = ovc_sequence_backward (k = T, out_size = S)
     bool operator<(const GraphKey& o) const {
         return std::tie(model_hash, ws, B, N, k, out_size, kind) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size, o.kind);
     }
@@ -1686,16 +1722,20 @@ struct TrainWs {
     // dropout (carve_train(..., dropout = true) only; ovc_train_dropout_workspace_bytes)
     float* dproj;                 // [Rmax][d] gradient of a masked projection: keep * s * dy
     int64_t* seed;                // the step's seed, copied in outside the captured body
+    // sequences (carve_train(..., seq = true) only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
+    // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
+    int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
     size_t bytes;
 };
 
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 
-TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false) {
+// S > 1 (with seq): S sequences per image, rows = B*S*T (run_forward_decoder)
+TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false, int S = 1, bool seq = false) {
     TrainWs t{};
-    t.w = carve_forward(m, base, B, N, T, 1);
+    t.w = carve_forward(m, base, B, N, T, 1, S);
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
-    const size_t rows = (size_t)B * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
+    const size_t rows = (size_t)B * S * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
     const size_t R = std::max(rows, BN), Rp = pad4(R);
     for (int l = 0; l < m->n_enc; ++l) {
@@ -1726,12 +1766,15 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
     for (int i = 0; i < 2; ++i) t.denc[i] = a.take<float>(BN * d);
     t.dkv = a.take<float>(BN * 2 * hk);
     t.ta = a.take<float>(wide * Rp); t.tb = a.take<float>(wide * Rp);
-    const size_t pdec = (size_t)B * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * N;
+    const size_t pdec = (size_t)B * S * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * N;
     t.P = a.take<float>(std::max(pdec, penc)); t.dS = a.take<float>(std::max(pdec, penc));
     t.part = a.take<float>(((R + 63) / 64) * std::max(d, dff));
     if (dropout) {
         t.dproj = a.take<float>(R * d);
         t.seed = a.take<int64_t>(2);
+    }
+    if (seq) {
+        t.seq_tok = a.take<int64_t>(rows); t.seq_tgt = a.take<int64_t>(rows); t.seq_keep = a.take<uint8_t>(rows);
     }
     t.bytes = (a.off + 255) & ~(size_t)255;
     return t;
@@ -1857,14 +1900,15 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
     return bw_mm(e, t.dqkv, 3 * hk, rows, 3 * hk, t.wt, d, dx, t.dy);
 }
 
+// S sequences per image (run_forward_decoder): the cross-attention of image b over its S*T query rows, the self-attention per sequence
 int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, int N, int T, const float* xin, const float* dout,
-                     float* dxin, float* denc_prev, float* denc_next) {
+                     float* dxin, float* denc_prev, float* denc_next, int S = 1) {
     const ovc_model* m = e.m;
     const Workspace& w = t.w;
     const DecTape& p = t.tape.dec[l];
     const ovc_dec_layer& dl = m->dec[l];
     const ovc_dec_layer& gl = gr->dec[l];
-    const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * T, BN = B * N;
+    const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * S * T, BN = B * N;
     // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(x2)
     TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.x2, p.ff, p.yf, dout, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
     // cross-attention AddNorm -> t.dy = d(yc), the residual's share of d(x1)
@@ -1876,7 +1920,7 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, i
     AttnBwdArgs a{};
     a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
     a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
-    a.B = B; a.nq = T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+    a.B = B; a.nq = S * T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
     a.P = t.P; a.dS = t.dS; a.dq = t.dqkv; a.lddq = hk; a.dk_out = t.dkv; a.dv_out = t.dkv + hk; a.lddkv = 2 * hk;
     RUN(ovc_bw_attention(a, e.stream));
     TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
@@ -1889,23 +1933,28 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, i
     TRY(bw_mm(e, t.dkv, 2 * hk, BN, 2 * hk, t.wt, d, denc_next, denc_prev));
     // masked self-attention over the caption
     return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
-                             B, T, h, dk, dxin, dec_site(l, 0));
+                             B * S, T, h, dk, dxin, dec_site(l, 0));
 }
 
-int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T) {
+// seq (ovc_sequence_backward): S sequences per image, and the row weights t.w_row come from the caller's grad_logp (written before the
+// body) instead of the cross-entropy's: the dlogit alone, no loss.
+int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T, int S = 1, bool seq = false) {
     const ovc_model* m = e.m;
     Workspace& w = t.w;
     hipStream_t s = e.stream;
-    const int d = m->d_model, V = m->vocab, rows = B * T, BN = B * N, L = m->n_dec;
+    const int d = m->d_model, V = m->vocab, rows = B * S * T, BN = B * N, L = m->n_dec;
     const int nblk = (V + 31) / 32, ldt = (int)pad4(rows), ldv = (int)pad4(V);
-    TRY(issue_forward_body(e, w, B, N, T, 1));
+    TRY(issue_forward_body(e, w, B, N, T, 1, S));
     if (!e.dry) {
         hipLaunchKernelGGL(tf_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.stats, nblk, (nblk + 1) & ~1, rows, w.tgt,
                            m->pad_idx, nullptr, nullptr, 0L, w.lse, nullptr);
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
     e.gemm_class = 3;
-    RUN(ovc_bw_xent(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
+    if (seq)
+        RUN(ovc_bw_dlogit(w.logits, ldt, w.lse, w.tgt, t.w_row, rows, V, t.dl_t, t.dl, ldv, s));
+    else
+        RUN(ovc_bw_xent(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
     // decoder output: d(out) = dlogit . fc, d(fc) = dlogit^T . out
     const float* dec_out = t.tape.dec[L - 1].out;
     RUN(ovc_bw_transpose(m->fc, d, V, d, t.fc_t, ldv, ldv, s));
@@ -1918,7 +1967,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
     for (int l = L - 1; l >= 0; --l) {
         const float* xin = l == 0 ? w.x : t.tape.dec[l - 1].out;
         TRY(bw_decoder_layer(e, t, gr, l, B, N, T, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
-                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1]));
+                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1], S));
         if (l != L - 1) enc_cur ^= 1;
         cur ^= 1;
     }
@@ -2055,4 +2104,79 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                 nullptr, nullptr, 0);
     return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
                             &plan, dropout->seed, hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training: ovc_sequence_backward (self-critical sequence training)
+// ---------------------------------------------------------------------------------------------
+// The gradient of sum_{b,s,t <= e(b,s)} g[b,s,t] logp[b,s,t], logp the teacher-forced log-probability of the generated sequence
+// ids[b,s,:] -- equal to the search's log_probs, whose decoder builds the same masks (decoders.py:95-110).  The body is
+// issue_train_body over rows (b, s, t) with the encoder and the cross keys / values once per image; the cross-attention backward's
+// dk / dv sum over the image's S*T queries in ascending order, so the encoder output's gradient sums every beam of the image.  The
+// dlogit is bw_dlogit_kernel with w_row = -g on kept rows; no loss.  Launch order: the input kernels (feature projection,
+// seq_inputs_kernel, tf_inputs_kernel, token and feature staging: they read the caller's features / ids / grad_logp), the body
+// (captured on the second call of a (model contents, gradient table, workspace, B, N, S, T) when use_graph is set), then
+// seq_logp_kernel into the caller's logp_out.
+namespace {
+
+bool seq_ok(const ovc_model* m, int B, int N, int S, int T) {
+    return S >= 1 && B >= 1 && (long)B * S <= (1L << 24) && train_ok(m, B * S, N, T);
+}
+
+}  // namespace
+
+extern "C" size_t ovc_train_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    if (!seq_ok(m, B, N, S, T)) return 0;
+    return carve_train(m, nullptr, B, N, T, false, S, true).bytes;
+}
+
+extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                     int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                                     float* logp_out, int use_graph, ovc_stream stream) {
+    (void)boxes;       // the plain encoder reads no boxes
+    if (!seq_ok(m, B, N, S, T) || !grads || !grads_ok(m, grads) || !features || !ids || !grad_logp || !workspace) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    TrainWs t = carve_train(m, workspace, B, N, T, false, S, true);
+    t.w.tape = &t.tape;
+    if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    const int nseq = B * S, rows = nseq * T, BN = B * N;
+
+    // the kernels that read the caller's inputs, outside the captured body
+    TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
+    hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, ids, grad_logp, nseq, T, m->bos_idx, m->eos_idx,
+                       t.seq_tok, t.seq_tgt, t.seq_keep, t.w_row);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, t.seq_tok, t.seq_tgt, m->vocab, m->pad_idx, T,
+                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    TRY(ovc_bw_tokens(t.seq_tok, rows, m->vocab, t.tok, e.stream));
+    TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
+    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T, S, true); };
+    if (!use_graph) {
+        TRY(body(e));
+    } else {
+        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull), workspace, B, N, T, S};
+        key.kind = 5;
+        std::lock_guard<std::mutex> lock(g_graph_mutex);
+        GraphEntry& entry = g_graphs[key];
+        entry.calls += 1;
+        entry.last_use = ++g_graph_tick;
+        entry.last_stream = e.stream;
+        evict_lru(&key, nullptr);
+        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec && !capture_into(&entry.graph, &entry.exec, m, body))
+            entry.unsupported = true;
+        if (entry.exec && !g_profile_on) {
+            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        } else {
+            TRY(body(e));
+        }
+    }
+    if (logp_out) {
+        hipLaunchKernelGGL(seq_logp_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, t.w.logits, (long)pad4(rows), t.w.lse,
+                           t.w.tgt, t.seq_keep, rows, logp_out);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
+    return OVC_OK;
 }

@@ -231,6 +231,7 @@ class CaptionEngine:
         # leaves the search's buffer -- whose address keys its captured graphs -- where it is
         self._fw_workspaces = {}
         self._train_workspaces = {}   # ovc_forward_backward's own, per stream
+        self._seq_workspaces = {}     # ovc_sequence_backward's own, per (stream, sequences per image)
         self._steps_device = {}  # early_exit="device": the step count of each search workspace (keyed like _workspaces)
         self.last_steps_device = None
         self._tuned = set()
@@ -437,12 +438,13 @@ class CaptionEngine:
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
         for ws in (list(getattr(self, "_workspaces", {}).values()) + list(getattr(self, "_fw_workspaces", {}).values()) +
-                   list(getattr(self, "_train_workspaces", {}).values())):
+                   list(getattr(self, "_train_workspaces", {}).values()) + list(getattr(self, "_seq_workspaces", {}).values())):
             if lib is not None:
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._workspaces = {}
         self._fw_workspaces = {}
         self._train_workspaces = {}
+        self._seq_workspaces = {}
         self._steps_device = {}
 
     def __del__(self):
@@ -646,16 +648,7 @@ class CaptionEngine:
         self._check_pointers()
         self._refresh_derived()
         d = self.desc
-        slots = _grad_slots(self.model)
-        sizes = [(p.numel() + 3) & ~3 for p, _ in slots]        # every gradient starts on 16 bytes
-        arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
-        table = native.Model()
-        grads, off = [], 0
-        for (p, path), size in zip(slots, sizes):
-            view = arena[off:off + p.numel()].view(p.shape)
-            _set_field(table, path, view.data_ptr())
-            grads.append(view)
-            off += size
+        arena, table, grads = self._gradient_arena()
         stream = torch.cuda.current_stream().cuda_stream
         ws = self._cached_workspace(self._train_workspaces, stream, need)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
@@ -668,6 +661,64 @@ class CaptionEngine:
         else:
             check(self.lib.ovc_forward_backward_dropout(*args, ctypes.byref(table_drop)), "ovc_forward_backward_dropout")
         return loss, arena, grads
+
+    def _gradient_arena(self):
+        """A fresh flat fp32 buffer for every gradient of ``gradient_parameters()``, the ``ovc_model`` table pointing into it and
+        the per-parameter views."""
+        slots = _grad_slots(self.model)
+        sizes = [(p.numel() + 3) & ~3 for p, _ in slots]        # every gradient starts on 16 bytes
+        arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
+        table = native.Model()
+        grads, off = [], 0
+        for (p, path), size in zip(slots, sizes):
+            view = arena[off:off + p.numel()].view(p.shape)
+            _set_field(table, path, view.data_ptr())
+            grads.append(view)
+            off += size
+        return arena, table, grads
+
+    def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False):
+        """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
+        (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
+        ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
+        teacher-forced log-probabilities of those sequences (``<bos>`` then ``ids[..., :t]``).  ``g`` after the first ``<eos>`` is
+        ignored.  The encoder runs once per image.  Returns ``(arena, grads)`` as ``forward_backward`` does -- fresh tensors,
+        nothing accumulated -- and with ``want_logp`` also the recomputed ``(B, S, T)`` log-probabilities (0 after ``<eos>``).
+        Deterministic: the same bits on every call, stream, graph replay and GEMM tiling.  Dropout is taken as the identity; the
+        caller (``BaseTransformer.beam_search``) checks it."""
+        self._check_trainable()
+        d = self.desc
+        features, boxes = self._checked_inputs(features, boxes)
+        B, N = features.shape[:2]
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 3 or ids.shape[0] != B:
+            raise native.OvcError("ids must be (B={}, S, T); got {}".format(
+                B, tuple(ids.shape) if isinstance(ids, torch.Tensor) else type(ids).__name__))
+        S = ids.shape[1]
+        if S < 1:
+            raise native.OvcError("ids must hold at least one sequence per image (got shape {})".format(tuple(ids.shape)))
+        T = check_caption_ids(ids.reshape(B * S, -1), "ids", B * S, d.max_len, d.vocab)
+        if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
+            raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
+        need = self.lib.ovc_train_beams_workspace_bytes(ctypes.byref(d), B, N, S, T)
+        if need == 0:
+            raise native.OvcError("unsupported training configuration (B={}, N={}, S={}, T={}, V={}; see "
+                                  "ovc_train_beams_workspace_bytes)".format(B, N, S, T, d.vocab))
+        ids = ids.to(self.device).contiguous()
+        grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
+        self._check_pointers()
+        self._refresh_derived()
+        d = self.desc
+        arena, table, grads = self._gradient_arena()
+        stream = torch.cuda.current_stream().cuda_stream
+        ws = self._cached_workspace(self._seq_workspaces, (stream, S), need)
+        logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device) if want_logp else None
+        graph = self.use_graph if use_graph is None else bool(use_graph)
+        check(self.lib.ovc_sequence_backward(ctypes.byref(d), ctypes.byref(table), features.data_ptr(),
+                                             None if boxes is None else boxes.data_ptr(), B, N, S, ids.data_ptr(),
+                                             grad_logp.data_ptr(), T, ws.data_ptr(), need,
+                                             None if logp is None else logp.data_ptr(), 1 if graph else 0,
+                                             native.stream_handle()), "ovc_sequence_backward")
+        return (arena, grads, logp) if want_logp else (arena, grads)
 
     def scale_gradients(self, arena, scale):
         """``arena * scale`` into a new buffer (``ovc_scale``; ``scale`` a one-element fp32 device tensor): the autograd

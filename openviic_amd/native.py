@@ -142,6 +142,9 @@ SIGNATURES = {
     "ovc_forward_backward_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                              c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Dropout)]),
     "ovc_dropout_mask": (c_int, [c_void_p, c_int, c_long, c_long, c_float, c_void_p, c_void_p]),
+    "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),

@@ -1,0 +1,124 @@
+"""ms per self-critical training step (the reference's ``train_scst``, vi_trainer.py:121-158) on the fused engine: the train-mode
+beam search ``beam_search(items, B, k, out_size=k)`` and ``loss.backward()`` (``ovc_sequence_backward``), timed separately, at the
+full standard configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, V = 10 201), T = 20, N = 50 ragged
+regions, dropout 0.  The weights are EOS-biased (``eos_biased_state_dict``) so captions end at realistic lengths.
+
+    python tools/scst_step_probe.py [--batches 60 256] [--beam 5] [--steps 10] [--warmup 3] [--out results/scst_step_probe.json]
+
+Time: device events around each phase after ``--warmup`` steps (the second call captures the graphs), one synchronise per step.
+Shared against expanded: ``sequence_backward`` with the encoder once per image (S = k) against the same entry at S = 1 on the
+features repeated k times, alternating in one process, median of ``--steps`` each.  FLOPs: the matrix products of the recompute
+from the shapes (projections, attention, FFN, vocabulary) times 3, for both layouts.  Needs a HIP device."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from openviic_amd.builders import build_model                                        # noqa: E402
+from openviic_amd.config import model_config                                         # noqa: E402
+from openviic_amd.instance import InstanceList                                       # noqa: E402
+from openviic_amd.utils.synthetic import (SyntheticVocab, eos_biased_state_dict, synthetic_features,   # noqa: E402
+                                          synthetic_state_dict)
+
+
+def recompute_flops(dims, images, S, N, T):
+    """Matrix FLOPs of forward + backward (3x the forward) of the teacher-forced recompute: ``images`` encoder passes, each
+    image's S sequences of T rows through the decoder."""
+    d, h, dk, dff, dfeat, V, Le, Ld = (dims[k] for k in ("d", "h", "dk", "dff", "dfeat", "V", "Le", "Ld"))
+    BN, R, hk = images * N, images * S * T, h * dk
+    f = 2 * BN * dfeat * d
+    f += Le * (2 * BN * d * 3 * hk + 4 * images * h * N * N * dk + 2 * BN * hk * d + 4 * BN * d * dff)
+    f += Ld * 2 * BN * d * 2 * hk
+    f += Ld * (2 * R * d * 3 * hk + 4 * images * S * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * R * N * h * dk
+               + 2 * R * hk * d + 4 * R * d * dff)
+    f += 2 * R * d * V
+    return 3 * f
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
+    ap.add_argument("--beam", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    V, T, N, D, k = 10201, 20, 50, 2048, args.beam
+    vocab = SyntheticVocab(V, T)
+    cfg = model_config("standard_transformer", d_feature=D, device="cuda:0")
+    model = build_model(cfg, vocab)
+    template = model.state_dict()
+    sd = eos_biased_state_dict({**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}, template)
+    model.load_state_dict(sd, strict=False)
+    model.train()
+    for m in model.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.p = 0.0
+    eng = model._fused_engine()
+    dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
+    results = []
+    for B in args.batches:
+        feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        items = InstanceList()
+        items.region_features = feats
+        reward = torch.rand(B, k, generator=torch.Generator().manual_seed(1)).cuda()
+        search_ms, backward_ms, lengths = [], [], []
+        try:
+            for i in range(args.warmup + args.steps):
+                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k))
+                loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
+                model.zero_grad(set_to_none=True)
+                ms_b, _ = timed(loss.backward)
+                if i >= args.warmup:
+                    search_ms.append(ms_s)
+                    backward_ms.append(ms_b)
+            ended = (ids == 2).any(-1)
+            first = torch.where(ended, (ids == 2).int().argmax(-1), torch.full_like(ended, T - 1, dtype=torch.long))
+            lengths = (first + 1).float().mean().item()
+            # shared encoder (S = k) against expanded features (S = 1), alternating
+            g = torch.randn(ids.shape, device="cuda")
+            fe, ie, ge = feats.repeat_interleave(k, 0), ids.reshape(B * k, 1, T), g.reshape(B * k, 1, T)
+            shared, expanded = [], []
+            for i in range(args.warmup + args.steps):
+                ms_a, _ = timed(lambda: eng.sequence_backward(feats, None, ids, g))
+                ms_e, _ = timed(lambda: eng.sequence_backward(fe, None, ie, ge))
+                if i >= args.warmup:
+                    shared.append(ms_a)
+                    expanded.append(ms_e)
+        except (RuntimeError, torch.cuda.OutOfMemoryError) as exc:        # B = 256: the expanded layout may not fit
+            results.append({"B": B, "k": k, "error": str(exc).splitlines()[0]})
+            print(json.dumps(results[-1]))
+            torch.cuda.empty_cache()
+            continue
+        f_shared, f_exp = recompute_flops(dims, B, k, N, T), recompute_flops(dims, B * k, 1, N, T)
+        med = statistics.median
+        r = {"B": B, "k": k, "T": T, "N": N, "mean_caption_length": lengths,
+             "search_ms": med(search_ms), "backward_ms": med(backward_ms), "step_ms": med(search_ms) + med(backward_ms),
+             "shared_ms": med(shared), "expanded_ms": med(expanded), "expanded_over_shared_time": med(expanded) / med(shared),
+             "shared_gflop": f_shared / 1e9, "expanded_gflop": f_exp / 1e9, "expanded_over_shared_flops": f_exp / f_shared,
+             "shared_tflops": f_shared / med(shared) / 1e9}
+        results.append(r)
+        print(json.dumps(r))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

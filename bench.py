@@ -2,8 +2,8 @@
 """Headline benchmark: captions/s of beam-5 decoding on synthetic region features.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config standard_transformer]
-                    [--batch 256] [--beam 5] [--streams 4] [--tune-concurrency C] [--no-cpu-baseline]
-                    [--precision f32] [--also-precision f16x3|none] [--dump-outputs DIR]
+                    [--batch 256] [--beam 5] [--streams 4] [--tune-concurrency C] [--precision f32]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--also-precision f16x3|none]]
 
 One "step" is one pass of the hot path over one batch: ``[B=256, 50, 2048]`` fp32 region features
 already resident in HBM -> encoder -> 20 beam-search steps (beam 5, V=10201) -> token ids
@@ -15,9 +15,12 @@ The images go through ``openviic_amd.distributed.decode_sharded`` -- the code th
 cover -- at every N: each rank decodes rows ``shard_bounds(B*N, rank, N)`` of the global batch.
 
 Timed region (``value``, ``ms_per_step``): consecutive batches alternate over ``--streams`` HIP streams, decode launch
-sequences replayed as hipGraphs.  ``roofline`` covers the dominant kernel, the fp32 MFMA GEMM (every projection / FFN /
-vocabulary product): algorithmic FLOPs 2*M*N*K per launch over the launch's own duration (kernel-scoped HIP events:
-dispatch begin / end on the launch stream).  Durations of kernels that overlap on different streams do not add up to
+sequences replayed as hipGraphs.  A plain run is set-up, warm-up, the timed region, ``--dump-outputs`` and the line, nothing
+else.  ``--full`` adds the legs below, which run after the timed region and never change ``value``.
+
+``roofline`` covers the dominant kernel, the fp32 MFMA GEMM (every projection / FFN / vocabulary product): algorithmic
+FLOPs 2*M*N*K per launch over the launch's own duration (kernel-scoped HIP events: dispatch begin / end on the launch
+stream).  Durations of kernels that overlap on different streams do not add up to
 wall time, so that leg runs on ONE stream, right after a timed single-stream region whose ``ms_per_step`` is reported
 next to it (``roofline.single_stream``); ``roofline.timed_mode`` relates the same GEMM FLOPs to the headline wall time.
 ``cpu_baseline`` times the CPU oracle (which reproduces the reference's operation sequence): B = 256, one warm-up and
@@ -82,10 +85,14 @@ def parse(argv=None):
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16x6", "f16x3"],
                     help="GEMM arithmetic.  f32 (default) = fp32 MFMA, the parity mode and the only headline.  The others are the "
                          "opt-in split-precision modes (bf16 planes, fp32 accumulate), reported separately: NOT bit-identical to f32.")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that take runs of their own: the single-stream region and "
+                         "the kernel-scoped GEMM roofline, the opt-in precision leg and the CPU-oracle baseline.  Without it the "
+                         "run ends after the timed steps (and --dump-outputs) with the headline line.")
     ap.add_argument("--also-precision", default="f16x3", choices=["none", "bf16x6", "f16x3"],
-                    help="with --precision f32 on one GPU: an extra, separately reported leg in this opt-in mode "
+                    help="with --full and --precision f32 on one GPU: an extra, separately reported leg in this opt-in mode "
                          "(same streams, same steps; never part of `value`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU-oracle baseline")
     ap.add_argument("--allow-measurement-hooks", action="store_true",
                     help="tools/ only: run although OVC_DEBUG_* / OVC_KSPLIT_* / a kernel A/B switch is set or the measurement build of "
                          "the library (tools/libovc_hooks.so) is loaded.  The line then says \"valid_for_credit\": false.")
@@ -222,6 +229,29 @@ def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
     return paths
 
 
+SPLIT_PRODUCTS = {"f32": 0, "bf16x6": 6, "f16x3": 3}     # 16-bit plane products per fp32 product of each --precision
+
+
+def headline(args, world, elapsed, streams, objective, build_info):
+    """The keys of every line, plain or --full: the timed region's figure (``elapsed`` seconds for ``args.steps`` steps,
+    max over ranks) and what it ran with."""
+    split_products = SPLIT_PRODUCTS[args.precision]
+    variant, B, k = args.config, args.batch, args.beam
+    return {
+        "metric": "captions/sec (whole node) at beam=%d, %d regions x d%d" % (k, N_REGIONS, D_FEAT),
+        "value": round(B * world * args.steps / elapsed, 2), "unit": "captions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if not split_products else "f32 in/out, GEMMs as %d 16-bit plane products (%s): opt-in mode, not the parity mode" % (split_products, args.precision),
+        "data": "synthetic",
+        "config": {"workload": "%s beam=%d, B=%d per GPU, %dx%d synthetic regions, V=%d, max_len=%d, "
+                               "random-init weights" % (variant, k, B, N_REGIONS, D_FEAT, V, T),
+                   "global_batch": B * world, "parallelism": "dp%d" % world, "streams": streams,
+                   "gemm_tuning_objective": {"timed_region": objective},
+                   "library": build_info, "environment": recorded_environment(os.environ)},
+    }
+
+
 def cpu_model_string():
     try:
         for line in open("/proc/cpuinfo"):
@@ -329,7 +359,6 @@ def main():
     # (round 3, one box, two alternating rounds: objective 1 / 2 / 3 / 4 = 22.8-23.0k / 23.2-23.3k / 23.3-23.4k / 23.44-23.46k)
     objective = args.tune_concurrency or (min(len(streams), 4) if len(streams) >= 3 else 1)
     engine_timed = CaptionEngine(model, tune_concurrency=objective, precision=args.precision)
-    engine_single = engine_timed if objective == 1 else CaptionEngine(model, tune_concurrency=1, precision=args.precision)
     model._engine = engine_timed
 
     def step(slot=None):
@@ -369,8 +398,31 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    captions_per_s = B * world * args.steps / elapsed
 
-    # ---- single-stream leg: a timed region on ONE stream, then the instrumented pass on the same stream -------------
+    def finish(result):
+        """Rank 0 prints its line (``result``; None on the other ranks); then the process group goes down."""
+        if result is not None:
+            if hooks:
+                result["measurement_hooks"] = hooks
+                result["valid_for_credit"] = False
+            sys.stdout.flush()
+            os.dup2(stdout_fd, 1)
+            print(json.dumps(result), flush=True)
+            os.dup2(2, 1)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print("[bench] gpu: %.1f captions/s, %.2f ms/step" % (captions_per_s, 1e3 * elapsed / args.steps),
+                  file=sys.stderr, flush=True)
+        finish(headline(args, world, elapsed, len(streams), objective, build_info) if rank == 0 else None)
+        return
+
+    # ---- --full only from here.  Single-stream leg: a timed region on ONE stream, then the instrumented pass on the same stream
+    engine_single = engine_timed if objective == 1 else CaptionEngine(model, tune_concurrency=1, precision=args.precision)
     single_steps = max(3, args.steps // 3)
     with torch.no_grad():
         if engine_single is not engine_timed:
@@ -417,7 +469,6 @@ def main():
             if n:
                 per_kernel[lib.ovc_profile_kernel_name(t).decode()] = entry(n, ms, fl)
             t += 1
-        captions_per_s = B * world * args.steps / elapsed
         # The dominant kernel is the fp32 MFMA GEMM template (every projection / FFN / vocabulary product):
         # >= 97 % of the algorithmic FLOPs and ~3/4 of the device time.  Its tilings are specialisations of one
         # kernel, so the roofline is taken over all of its launches in one batch; per-instance rows (names as
@@ -429,7 +480,7 @@ def main():
         gflop = GFLOP_PER_CAPTION.get(variant)
         traffic, traffic_source, counter_bytes = (profiled_gemm_traffic(variant, args.precision) if B == 256 and k == 5
                                                   else (None, None, None))
-        split_products = {"f32": 0, "bf16x6": 6, "f16x3": 3}[args.precision]
+        split_products = SPLIT_PRODUCTS[args.precision]
         if split_products:      # opt-in mode: the peak is the bf16 dense MFMA rate shared by the plane products of one fp32 product
             PEAK = round(PEAK_F32_MFMA_TFLOPS * 16 / split_products, 1)
             kernel_label = ("gemm_split_mfma<BM,BN,WM,WN,BK,MODE> (v_mfma_f32_32x32x16_bf16 / _f16, %d plane products per product; "
@@ -523,23 +574,9 @@ def main():
                 model._engine = engine_timed
                 also = {"mode": args.also_precision, "error": "%s: %s" % (type(exc).__name__, exc)}
                 print("[bench] opt-in %s leg failed: %s" % (args.also_precision, also["error"]), file=sys.stderr, flush=True)
-        result = {
-            "metric": "captions/sec (whole node) at beam=%d, %d regions x d%d" % (k, N_REGIONS, D_FEAT),
-            "value": round(captions_per_s, 2), "unit": "captions/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if not split_products else "f32 in/out, GEMMs as %d 16-bit plane products (%s): opt-in mode, not the parity mode" % (split_products, args.precision),
-            "data": "synthetic",
-            "config": {"workload": "%s beam=%d, B=%d per GPU, %dx%d synthetic regions, V=%d, max_len=%d, "
-                                   "random-init weights" % (variant, k, B, N_REGIONS, D_FEAT, V, T),
-                       "global_batch": B * world, "parallelism": "dp%d" % world, "streams": len(streams),
-                       "gemm_tuning_objective": {"timed_region": objective, "single_stream_leg": 1},
-                       "library": build_info, "environment": recorded_environment(os.environ)},
-            "roofline": roofline,
-        }
-        if hooks:
-            result["measurement_hooks"] = hooks
-            result["valid_for_credit"] = False
+        result = headline(args, world, elapsed, len(streams), objective, build_info)
+        result["config"]["gemm_tuning_objective"]["single_stream_leg"] = 1
+        result["roofline"] = roofline
         if also:
             result["opt_in_precision"] = also
         if world == 1 and not args.no_cpu_baseline:
@@ -548,13 +585,7 @@ def main():
             # the bench contract times the CPU path on rank 0 at N = 1 only; the N > 1 lines point there instead of dropping the key
             result["cpu_baseline"] = {"value": None, "unit": "captions/s", "kind": "port",
                                       "sample": "not timed at N > 1: see the N = 1 line of the same run (bench contract: rank 0, N = 1 only)"}
-        sys.stdout.flush()
-        os.dup2(stdout_fd, 1)
-        print(json.dumps(result), flush=True)
-        os.dup2(2, 1)
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(result)
 
 
 if __name__ == "__main__":

@@ -210,6 +210,21 @@ def test_bench_refuses_measurement_hooks_and_records_its_environment(monkeypatch
         assert refused.returncode != 0 and "measurement hooks are active (OVC_DEBUG_EXTRA_LAUNCHES)" in refused.stderr and not refused.stdout.strip()
 
 
+def test_bench_plain_line_is_the_headline_and_full_is_opt_in():
+    """A plain run prints the timed region's figure and what it ran with; the legs of their own (roofline, opt-in precision,
+    CPU baseline) need --full."""
+    bench = _bench_module()
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+    line = bench.headline(bench.parse(["--steps", "4", "--warmup", "2"]), 1, 0.04, 4, 4, "libovc test")
+    assert line["value"] == 25600.0 and line["ms_per_step"] == 10.0 and line["unit"] == "captions/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and (line["steps"], line["warmup"]) == (4, 2)
+    assert line["metric"] == "captions/sec (whole node) at beam=5, 50 regions x d2048"
+    assert line["config"]["gemm_tuning_objective"] == {"timed_region": 4} and line["config"]["library"] == "libovc test"
+    assert not {"roofline", "opt_in_precision", "cpu_baseline"} & set(line)
+    split = bench.headline(bench.parse(["--precision", "f16x3"]), 2, 1.0, 4, 4, "")
+    assert split["dtype"].startswith("f32 in/out, GEMMs as 3 16-bit plane products (f16x3)") and split["value"] == 512 * 30
+
+
 def test_bench_dumps_the_timed_outputs_exactly_and_within_its_limit(tmp_path):
     """--dump-outputs: token ids as float64 (exact), at most the byte limit in all (then the same seeded rows every time);
     --steps is the number of timed steps and must be at least 1."""

@@ -5,7 +5,7 @@ SUB=$1; CNT=${2:-"SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmck; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --also-precision none --streams 1 $PMC_ARGS > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
+rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --also-precision none --streams 1 $PMC_ARGS > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
 python3 - "$OUT" "$SUB" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*/*_counter_collection.csv")[0]

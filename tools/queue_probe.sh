@@ -10,7 +10,7 @@ for i in $(seq 1 ${3:-1}); do
   for Q in ${1:-1 2}; do
     for S in ${2:-3 4 5}; do
       echo -n "queues=$Q streams=$S: "
-      GPU_MAX_HW_QUEUES=$Q python3 $ROOT/bench.py --no-cpu-baseline --streams $S --steps 40 2>&1 >/dev/null | tail -1 | cut -c1-60
+      GPU_MAX_HW_QUEUES=$Q python3 $ROOT/bench.py --streams $S --steps 40 2>&1 >/dev/null | grep "\[bench\] gpu:" | cut -c1-60
     done
   done
 done

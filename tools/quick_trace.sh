@@ -9,7 +9,7 @@ i=0
 for L in $LIBS; do
   OUT=$ROOT/gpurun_out/${TAG}_$i
   rm -rf $OUT; mkdir -p $OUT
-  OVC_LIBRARY=$ROOT/$L rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --streams 1 ${QT_ARGS} > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
+  OVC_LIBRARY=$ROOT/$L rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --streams 1 ${QT_ARGS} > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
   python3 - "$OUT" "$L" <<'PY' | tee $ROOT/gpurun_out/${TAG}_$i.txt
 import csv, glob, sys, collections
 out, lib = sys.argv[1], sys.argv[2]

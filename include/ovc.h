@@ -332,9 +332,11 @@ int ovc_forward(const ovc_model* m, const float* features, const float* boxes, i
  * it).  tokens / targets [B, T] int64 as in ovc_forward (ids in [0, V), checked by the caller).  loss_out: ONE device float.
  * grads: a second ovc_model-shaped table whose pointer fields name the gradient buffers, each shaped like the parameter of the same
  * field in m; only those fields are read.  Every buffer is WRITTEN, not accumulated: proj, enc_ln, every layer's q / k / v / o
- * Linears, their norms and FFNs (weight and, where m has one, bias), word_emb (its pad_idx row gets 0) and fc.  pos_emb (frozen)
- * gets nothing, the remaining fields are ignored.
- * Supported: the plain encoder and decoder (OVC_ENC_PLAIN, OVC_DEC_PLAIN) with plain attention (no AoA gates, no memory slots),
+ * Linears, their norms and FFNs (weight and, where m has one, bias), word_emb (its pad_idx row gets 0) and fc; with
+ * OVC_ENC_CROSS_LEVEL also cl_att (q / k / v / o, ln), cl_mlp1 and cl_mlp2.  pos_emb (frozen) gets nothing, the remaining fields
+ * are ignored.
+ * Supported: the plain or cross-level (CaMo) encoder with the plain decoder (OVC_ENC_PLAIN / OVC_ENC_CROSS_LEVEL, OVC_DEC_PLAIN)
+ * with plain attention (no AoA gates, no memory slots),
  * precision 0, and vocabularies of at most 16384 words (512 blocks of 32: the fused vocabulary tail of ovc_forward) -- tighter
  * than ovc_forward, which also takes larger vocabularies -- with (B*T + 256) * V and (V + 256) * B*T below 2^29.  Other sizes
  * as ovc_forward.  Anything else: ovc_train_workspace_bytes returns 0 and ovc_forward_backward OVC_EINVAL, nothing launched.
@@ -376,7 +378,8 @@ typedef struct {
  * ovc_forward_backward; the seed is copied into the workspace outside the captured body, so a replayed graph reads each call's
  * seed, and the p values are part of the graph's key.  Any p outside [0, 1) or a null dropout / seed: OVC_EINVAL, nothing
  * launched.  With every p == 0 this is ovc_forward_backward (same launches, same bits, ovc_train_workspace_bytes suffices).
- * ovc_train_dropout_workspace_bytes: bytes of workspace for calls with a site active (0 when unsupported). */
+ * ovc_train_dropout_workspace_bytes: bytes of workspace for calls with a site active (0 when unsupported, and for the
+ * cross-level encoder, whose tail applies one nn.Dropout twice and has no site). */
 size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T);
 int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                  const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,

@@ -21,6 +21,7 @@ from .builders.model_builder import META_ARCHITECTURE
 from .builders.vision_embedding_builder import build_vision_embedding
 from .modules.beam_search import BeamSearch
 from .modules.containers import Module
+from .modules.encoders import CrossAttentionMultiLevelEncoder
 
 
 class _XeLoss(torch.autograd.Function):
@@ -153,16 +154,24 @@ class BaseTransformer(Module):
     def xe_loss(self, input_features, dropout=False, generator=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
-        every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer in
-        'f32' only.
+        every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer and the
+        CaMo transformer, in 'f32' only.
 
         ``dropout=False``: dropout counts as the identity, so a model in ``train()`` mode with any dropout probability above 0
         is refused (set ``DROPOUT: 0`` or call ``model.eval()``).  ``dropout=True``: in ``train()`` mode every ``nn.Dropout``
         applies its own ``p`` as the reference's training does (``openviic_amd.dropout``; a ``p >= 1`` or a live dropout the
-        engine does not place is refused).  The step's seed is drawn on the stream from ``generator`` (default: the device's
+        engine does not place is refused; the standard transformer only: a CaMo model with a live dropout is refused before
+        any draw).  The step's seed is drawn on the stream from ``generator`` (default: the device's
         CUDA generator), so ``torch.manual_seed`` reproduces a step.  In ``eval()`` mode, or with every ``p == 0``, this is the
         ``dropout=False`` call: same bits, no random draw."""
         if dropout:
+            if self.training and isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
+                live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+                if live:
+                    raise engine.native.OvcError(
+                        "xe_loss(dropout=True): dropout training covers the standard transformer; the cross-level encoder applies "
+                        "encoder.self_attn.dropout twice in its tail and the engine has no site for it -- set DROPOUT: 0 and "
+                        "call xe_loss(items), or call model.eval() (live: {})".format(live[0]))
             probs = _dropout.model_probs(self) if self.training else {}
             if probs:
                 eng = self._fused_engine()
@@ -193,8 +202,8 @@ class BaseTransformer(Module):
         still native -- and exists for parity checks of ``step`` / ``statefulness``.
 
         Fused, in ``train()`` mode with gradients enabled: the returned ``log_probs`` carry a gradient (``_BeamLogProbs``), so
-        the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard transformer in 'f32'
-        with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
+        the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard transformer or the CaMo
+        transformer in 'f32' with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
         """
         if fused:
             boxes = input_features["region_boxes"] if self.uses_boxes else None

@@ -57,3 +57,15 @@ int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32
 int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s);
 // tok32[r] = clamp(tokens[r], 0, V-1)
 int ovc_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, hipStream_t s);
+
+// The cross-level (CaMo) encoder's tail (engine.hip bw_cross_level_tail).
+// LayerNorm-post backward of y = alpha LN(x + r) + r (rowops.hip, kPostTenths): from dy, dx = the gradient of the pre-norm sum
+// x + r through the norm alone (the identity into r is not added), prod = alpha dy * xhat, dyc = alpha dy (gamma / beta partials)
+int ovc_bw_layer_norm_post(const float* x, const float* r, const float* gamma, const float* dy, float alpha, float eps, int rows, int d,
+                           float* dx, float* prod, float* dyc, hipStream_t s);
+// out[i] = (g[i] * scale) * (act[i] > 0 ? 1 : slope): leaky-ReLU backward on the stored pre-activation or activation (a leaky
+// ReLU keeps the sign, so both give the same answer, torch's at 0 included); out may be g
+int ovc_bw_leaky(const float* g, const float* act, float scale, float slope, float* out, long n, hipStream_t s);
+// y[r, k] = (a[r, k] + b[r, k]) + c[r, k] (c may be nullptr), each operand with its own row stride; y may alias a, b or c
+int ovc_bw_sum(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols, float* y, long ldy,
+               hipStream_t s);

@@ -409,3 +409,79 @@ extern "C" int ovc_dropout_mask(const int64_t* seed, int site, long rows, long c
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
+
+// ---- the cross-level (CaMo) encoder's tail (engine.hip, bw_cross_level_tail) ----------------------------------------------------
+namespace {
+
+// bw_layer_norm_kernel for y = alpha * LN(x + r) + r (the tail's AddNorm, rowops.hip kPostTenths): the pre-norm sum is formed here as
+// the forward formed it (x + r, one fp32 add), dx = the gradient of that sum through the norm only (the identity into r is the
+// caller's), prod / dyc take the alpha factor (gamma's and beta's gradients)
+__global__ __launch_bounds__(256) void bw_layer_norm_post_kernel(const float* __restrict__ x, const float* __restrict__ r,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ dy,
+                                                                 float alpha, float eps, int rows, int d, float* __restrict__ dx,
+                                                                 float* __restrict__ prod, float* __restrict__ dyc) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const size_t o = (size_t)row * d;
+    float s = 0.f;
+    for (int c = lane; c < d; c += 64) s += x[o + c] + r[o + c];
+    const float mean = wave_sum(s) / d;
+    float v = 0.f;
+    for (int c = lane; c < d; c += 64) { const float t = (x[o + c] + r[o + c]) - mean; v += t * t; }
+    const float rstd = 1.f / sqrtf(wave_sum(v) / d + eps);
+    float a = 0.f, b = 0.f;
+    for (int c = lane; c < d; c += 64) {
+        const float xh = ((x[o + c] + r[o + c]) - mean) * rstd, g = gamma[c] * (alpha * dy[o + c]);
+        a += g; b += g * xh;
+    }
+    a = wave_sum(a) / d; b = wave_sum(b) / d;
+    for (int c = lane; c < d; c += 64) {
+        const float xh = ((x[o + c] + r[o + c]) - mean) * rstd, g = alpha * dy[o + c];
+        dx[o + c] = rstd * (gamma[c] * g - a - xh * b);
+        prod[o + c] = g * xh;
+        dyc[o + c] = g;
+    }
+}
+
+// no __restrict__ here or in bw_sum_kernel: the output may be an input
+__global__ void bw_leaky_kernel(const float* g, const float* act, float scale, float slope, float* out, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        out[i] = (g[i] * scale) * (act[i] > 0.f ? 1.f : slope);
+}
+
+__global__ void bw_sum_kernel(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols, float* y,
+                              long ldy) {
+    const long n = (long)rows * cols;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cols, k = i - r * cols;
+        float s = a[r * lda + k] + b[r * ldb + k];
+        if (c) s += c[r * ldc + k];
+        y[r * ldy + k] = s;
+    }
+}
+
+}  // namespace
+
+int ovc_bw_layer_norm_post(const float* x, const float* r, const float* gamma, const float* dy, float alpha, float eps, int rows, int d,
+                           float* dx, float* prod, float* dyc, hipStream_t s) {
+    if (d > 2048 || rows <= 0) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_layer_norm_post_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, r, gamma, dy, alpha, eps, rows, d, dx, prod,
+                       dyc);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_leaky(const float* g, const float* act, float scale, float slope, float* out, long n, hipStream_t s) {
+    hipLaunchKernelGGL(bw_leaky_kernel, dim3(blocks_for(n)), dim3(256), 0, s, g, act, scale, slope, out, n);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_sum(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols, float* y, long ldy,
+               hipStream_t s) {
+    if (!a || !b || !y || rows <= 0 || cols <= 0) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_sum_kernel, dim3(blocks_for((long)rows * cols)), dim3(256), 0, s, a, lda, b, ldb, c, ldc, rows, cols, y, ldy);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}

@@ -101,7 +101,12 @@ struct Bump {
 // layer outputs.  The inference forward reuses one set of buffers across layers instead (Workspace::tape == nullptr).
 struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out; };
 struct DecTape { float *q, *k, *v, *att, *ys, *x1, *qc, *attc, *yc, *x2, *ff, *yf, *out; };
-struct Tape { EncTape enc[OVC_MAX_LAYERS]; DecTape dec[OVC_MAX_LAYERS]; };
+// The cross-level (CaMo) tail (run_cross_level_tail): per cross call c (0: q = o2, k = v = o1; 1: q = o3, k = v = o2') its k, v, the
+// attention output att [2][B*N][h_enc*dv_enc] and fc_o's output ya [2][B*N][d] (the pre-norm sum is ya + q, formed again by the
+// backward as the norm formed it); o2'; mlp1's leaky-ReLU output a1 and mlp2's output h2 (its activation's sign).  The layer
+// outputs o1..o3 and the queries of both calls stay in Workspace::cl_out / cl_q, which nothing else writes.
+struct ClTape { float *k[2], *v[2], *att, *ya, *o2p, *a1, *h2; };
+struct Tape { EncTape enc[OVC_MAX_LAYERS]; DecTape dec[OVC_MAX_LAYERS]; ClTape cl; };
 
 struct Workspace {
     const Tape* tape;                             // training only: the forward keeps every layer's intermediates here
@@ -651,6 +656,8 @@ int run_encoder_inputs(Engine& e, Workspace& w, const float* features, const flo
 //   out = o3' + 0.2 leaky_relu(mlp2(leaky_relu(mlp1([o1 | o2 | o3]))))       the ORIGINAL o2, o3 in the concatenation
 // Nine launches on the caller's stream, in this order (nothing forks: the sequence is captured with the rest of the search).
 // Padding rows are NOT cleared afterwards -- the reference leaves them non-zero and the decoder masks them as keys.
+constexpr float kCrossScale = 0.1f, kMlpScale = 0.2f, kSlope = 0.01f;     // encoders.py:234-247, F.leaky_relu's default slope
+
 int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
     const ovc_model* m = e.m;
     const int BN = B * N, d = m->d_model, eh = enc_heads(m), edk = enc_dk(m), edv = enc_dv(m), hk = eh * edk, hv = eh * edv;
@@ -658,8 +665,9 @@ int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
     hipStream_t s = e.stream;
     const ovc_mha& at = m->cl_att;
     float* o1 = w.cl_out; float* o2 = w.cl_out + nd; float* o3 = w.cl_out + 2 * nd;
-    float* o2p = w.xe[0]; float* o3p = w.xe[1];
-    constexpr float kCrossScale = 0.1f, kMlpScale = 0.2f, kSlope = 0.01f;     // encoders.py:234-247, F.leaky_relu's default slope
+    // training: what the backward reads goes to the tape (ClTape); the same launches on other buffers, the same bits
+    const ClTape* tp = w.tape ? &w.tape->cl : nullptr;
+    float* o2p = tp ? tp->o2p : w.xe[0]; float* o3p = w.xe[1];
     e.gemm_class = 1;
     e.kchains = 1;
     // both calls' queries come from the original o2 / o3, which lie back to back: ONE product of 2 * B * N rows
@@ -668,25 +676,28 @@ int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
     const float* queries[2] = {o2, o3};
     float* outs[2] = {o2p, o3p};
     for (int c = 0; c < 2; ++c) {
+        float* ek = tp ? tp->k[c] : w.ek; float* ev = tp ? tp->v[c] : w.ev;
+        float* eatt = tp ? tp->att + (size_t)c * BN * hv : w.eatt; float* ya = tp ? tp->ya + (size_t)c * nd : w.ey;
         GemmArgs a{};
         a.A1 = keys[c]; a.lda1 = d; a.K1 = d; a.M = BN; a.seg_n = hk; a.nseg = 2; a.ldc = hk;
-        a.seg[0] = e.seg(at.k, w.ek);
-        a.seg[1] = e.seg(at.v, w.ev);
+        a.seg[0] = e.seg(at.k, ek);
+        a.seg[1] = e.seg(at.v, ev);
         TRY(e.gemm(a));
-        RUN(ovc_attention(w.cl_q + (size_t)c * BN * hk, w.ek, w.ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0, nullptr, nullptr,
-                          nullptr, 0, 1.f, 1.f, w.eatt, s));
-        TRY(e.linear(w.eatt, hv, at.o, nullptr, w.ey, BN, d, 0));
-        RUN(ovc_layer_norm_post_launch(w.ey, queries[c], at.ln.g, at.ln.b, m->ln_eps, kCrossScale, outs[c], BN, d, s));
+        RUN(ovc_attention(w.cl_q + (size_t)c * BN * hk, ek, ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0, nullptr, nullptr,
+                          nullptr, 0, 1.f, 1.f, eatt, s));
+        TRY(e.linear(eatt, hv, at.o, nullptr, ya, BN, d, 0));
+        RUN(ovc_layer_norm_post_launch(ya, queries[c], at.ln.g, at.ln.b, m->ln_eps, kCrossScale, outs[c], BN, d, s));
     }
     // [o1 | o2 | o3] row by row: mlp1 then reads ONE operand of K = 3d (the GEMM takes at most two input blocks)
     if (!e.dry) {
         hipLaunchKernelGGL(concat_levels_kernel, dim3(1024), dim3(256), 0, s, w.cl_out, w.cl_cat, 3, (size_t)BN, (size_t)d / 4);
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
-    TRY(e.linear(w.cl_cat, 3 * d, m->cl_mlp1, nullptr, w.einfo, BN, d, 0));
-    RUN(ovc_leaky_residual(w.einfo, d, nullptr, 0, kSlope, 1.f, w.einfo, d, BN, d, s));
-    TRY(e.linear(w.einfo, d, m->cl_mlp2, nullptr, w.ey, BN, d, 0));
-    RUN(ovc_leaky_residual(w.ey, d, o3p, d, kSlope, kMlpScale, w.enc_levels, d, BN, d, s));
+    float* a1 = tp ? tp->a1 : w.einfo; float* h2 = tp ? tp->h2 : w.ey;
+    TRY(e.linear(w.cl_cat, 3 * d, m->cl_mlp1, nullptr, a1, BN, d, 0));
+    RUN(ovc_leaky_residual(a1, d, nullptr, 0, kSlope, 1.f, a1, d, BN, d, s));
+    TRY(e.linear(a1, d, m->cl_mlp2, nullptr, h2, BN, d, 0));
+    RUN(ovc_leaky_residual(h2, d, o3p, d, kSlope, kMlpScale, w.enc_levels, d, BN, d, s));
     return OVC_OK;
 }
 
@@ -725,7 +736,7 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
                                                         : (l == m->n_enc - 1 ? w.enc_levels : x);
-        if (tp && l < m->n_enc - 1) out = tp->out;
+        if (tp && l < m->n_enc - 1 && m->enc_kind != OVC_ENC_CROSS_LEVEL) out = tp->out;     // cl_out keeps every level
         TRY(e.ffn(m->enc[l].ffn, x1, eff, yf, nullptr, out, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         x = out;
     }
@@ -1725,6 +1736,12 @@ struct TrainWs {
     // sequences (carve_train(..., seq = true) only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
     // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
     int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
+    // the cross-level tail (bw_cross_level_tail; cross-level models only), rows B*N: the leaky-ReLU gradients dh [B*N][d] (mlp2's,
+    // then mlp1's in da), mlp1's input gradient dcat [B*N][3d], per cross call c the pre-norm sum's gradient dss [2][B*N][d], dq
+    // [2][B*N][h_enc dk_enc], dk|dv [2][B*N][2 h_enc dk_enc], then d(o2') and the q path plus dss, dq23 [2][B*N][d]; the levels'
+    // gradients dlev [3][B*N][d]
+    float* cl_dh; float* cl_da; float* cl_dcat; float* cl_dss; float* cl_dq; float* cl_dkv; float* cl_do2p; float* cl_dq23;
+    float* cl_dlev;
     size_t bytes;
 };
 
@@ -1737,12 +1754,23 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
     const size_t rows = (size_t)B * S * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
-    const size_t R = std::max(rows, BN), Rp = pad4(R);
+    const bool cl = m->enc_kind == OVC_ENC_CROSS_LEVEL;
+    // the tail's weight gradients run over both cross calls' rows at once (2 B*N), mlp1's over K = 3d
+    const size_t R = std::max(rows, cl ? 2 * BN : BN), Rp = pad4(R);
     for (int l = 0; l < m->n_enc; ++l) {
         EncTape& p = t.tape.enc[l];
         p.q = a.take<float>(BN * ehk); p.k = a.take<float>(BN * ehk); p.v = a.take<float>(BN * ehk); p.att = a.take<float>(BN * ehk);
         p.ya = a.take<float>(BN * d); p.x1 = a.take<float>(BN * d); p.ff = a.take<float>(BN * dff); p.yf = a.take<float>(BN * d);
-        p.out = a.take<float>(l < m->n_enc - 1 ? BN * d : 0);
+        p.out = a.take<float>(l < m->n_enc - 1 && !cl ? BN * d : 0);
+    }
+    if (cl) {
+        ClTape& p = t.tape.cl;
+        for (int c = 0; c < 2; ++c) { p.k[c] = a.take<float>(BN * ehk); p.v[c] = a.take<float>(BN * ehk); }
+        p.att = a.take<float>(2 * BN * ehk); p.ya = a.take<float>(2 * BN * d);
+        p.o2p = a.take<float>(BN * d); p.a1 = a.take<float>(BN * d); p.h2 = a.take<float>(BN * d);
+        t.cl_dh = a.take<float>(BN * d); t.cl_da = a.take<float>(BN * d); t.cl_dcat = a.take<float>(BN * 3 * d);
+        t.cl_dss = a.take<float>(2 * BN * d); t.cl_dq = a.take<float>(2 * BN * ehk); t.cl_dkv = a.take<float>(2 * BN * 2 * ehk);
+        t.cl_do2p = a.take<float>(BN * d); t.cl_dq23 = a.take<float>(2 * BN * d); t.cl_dlev = a.take<float>(3 * BN * d);
     }
     for (int l = 0; l < m->n_dec; ++l) {
         DecTape& p = t.tape.dec[l];
@@ -1751,7 +1779,7 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
         p.attc = a.take<float>(rows * hk); p.yc = a.take<float>(rows * d); p.x2 = a.take<float>(rows * d);
         p.ff = a.take<float>(rows * dff); p.yf = a.take<float>(rows * d); p.out = a.take<float>(rows * d);
     }
-    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk});
+    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d});
     t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
     t.tok = a.take<int32_t>(rows);
     t.w_row = a.take<float>(rows); t.loss = a.take<float>(4);
@@ -1788,11 +1816,14 @@ bool mha_grad_ok(const ovc_mha& a, const ovc_mha& g) {
 }
 bool ffn_grad_ok(const ovc_ffn& f, const ovc_ffn& g) { return lin_grad_ok(f.fc1, g.fc1) && lin_grad_ok(f.fc2, g.fc2) && norm_grad_ok(g.ln); }
 
-// What the backward covers: the plain encoder and decoder, plain scaled dot-product attention, fp32, and vocabularies that take
-// the fused vocabulary tail (its transposed logits and block pieces are what the cross-entropy backward reads).
+// What the backward covers: the plain or cross-level (CaMo) encoder with the plain decoder, plain scaled dot-product attention,
+// fp32, and vocabularies that take the fused vocabulary tail (its transposed logits and block pieces are what the cross-entropy
+// backward reads).
 bool train_ok(const ovc_model* m, int B, int N, int T) {
     if (!forward_ok(m, B, N, T)) return false;
-    if (m->enc_kind != OVC_ENC_PLAIN || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    if (m->enc_kind != OVC_ENC_PLAIN && m->enc_kind != OVC_ENC_CROSS_LEVEL) return false;
+    if (m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    if (m->enc_kind == OVC_ENC_CROSS_LEVEL && (m->precision != 0 || !mha_plain(m->cl_att))) return false;
     for (int l = 0; l < m->n_enc; ++l) if (!mha_plain(m->enc[l].att)) return false;
     for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
     if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
@@ -1808,8 +1839,15 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
     for (int l = 0; l < m->n_dec; ++l)
         if (!mha_grad_ok(m->dec[l].self_att, g->dec[l].self_att) || !mha_grad_ok(m->dec[l].cross_att, g->dec[l].cross_att) ||
             !ffn_grad_ok(m->dec[l].ffn, g->dec[l].ffn)) return false;
+    if (m->enc_kind == OVC_ENC_CROSS_LEVEL &&
+        (!mha_grad_ok(m->cl_att, g->cl_att) || !lin_grad_ok(m->cl_mlp1, g->cl_mlp1) || !lin_grad_ok(m->cl_mlp2, g->cl_mlp2)))
+        return false;
     return true;
 }
+
+// Dropout training (ovc_forward_backward_dropout) covers the plain encoder only: the cross-level tail applies its one nn.Dropout
+// twice and has no site of its own.
+bool dropout_train_ok(const ovc_model* m, int B, int N, int T) { return train_ok(m, B, N, T) && m->enc_kind == OVC_ENC_PLAIN; }
 
 inline float* out_ptr(const float* p) { return const_cast<float*>(p); }
 
@@ -1936,6 +1974,96 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, i
                              B * S, T, h, dk, dxin, dec_site(l, 0));
 }
 
+// bw_weight over 2 * rows rows whose inputs lie in two blocks: X0 for the first `rows`, X1 for the next (dY [2 rows][ldy] in one
+// block).  Both are staged into one transposed operand, so the sum still runs over the 2 * rows rows in ascending order.
+int bw_weight_pair(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const float* X0, const float* X1, int ldx, int k, int rows,
+                   const ovc_lin& l, const ovc_lin& g) {
+    hipStream_t s = e.stream;
+    const int rp = (int)pad4(2 * rows);
+    RUN(ovc_bw_transpose(dY, ldy, 2 * rows, n, t.ta, rp, rp, s));
+    RUN(ovc_bw_transpose(X0, ldx, rows, k, t.tb, rp, rows, s));
+    RUN(ovc_bw_transpose(X1, ldx, rows, k, t.tb + rows, rp, rp - rows, s));
+    TRY(bw_mm(e, t.ta, rp, n, rp, t.tb, k, out_ptr(g.w)));
+    if (l.b) RUN(ovc_bw_rowsum(t.ta, rp, n, 2 * rows, out_ptr(g.b), s));
+    return OVC_OK;
+}
+
+// t.wt = [W_k ; W_v]^T [d][2 hk] of one attention (the k|v input gradient dX = [dk | dv] . [W_k ; W_v])
+int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk) {
+    const int d = e.m->d_model;
+    RUN(ovc_bw_transpose(at.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
+    RUN(ovc_bw_transpose(at.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
+    return OVC_OK;
+}
+
+// The cross-level (CaMo) tail's backward (forward: run_cross_level_tail), from G = d(out) (the decoder's gradient of the encoder
+// output) to the gradients of the three layer outputs, t.cl_dlev[0..2] = d(o1), d(o2), d(o3) WITHOUT the layers above them (the
+// caller adds layer 2's input gradient to d(o1) and layer 3's to d(o2)), and every tail weight's gradient:
+//   mlp2:  dh2 = (0.2 G) * leaky'(h2);  mlp1: dh1 = (dh2 . W2) * leaky'(a1);  dcat = dh1 . W1 = [dcat1 | dcat2 | dcat3]
+//   call 2 (o3' = 0.1 LN(ya2 + o3) + o3, d(o3') = G): dss2 = the norm's backward of 0.1 G; datt = dss2 . W_o; attention backward
+//          -> dq2, dk2 | dv2;  d(o2') = [dk2 | dv2] . [W_k ; W_v]
+//   call 1 (o2' = 0.1 LN(ya1 + o2) + o2): the same from d(o2') -> dss1, dq1, dk1 | dv1
+//   self_attn's weights: one product over both calls' 2 B*N rows (call 1's rows, then call 2's) for W_q, W_k, W_v, W_o and their
+//   biases, and both calls' norm partials summed over the same 2 B*N rows for gamma / beta
+//   levels, each a fixed left-to-right sum of its terms:
+//     d(o1) = [dk1 | dv1] . [W_k ; W_v]  + dcat1                      (+ layer 2's input gradient, by the caller)
+//     d(o2) = (dq1 . W_q + dss1) + d(o2') + dcat2                     (+ layer 3's input gradient, by the caller)
+//     d(o3) = (dq2 . W_q + dss2) + G + dcat3
+// Padding rows: G is exactly 0 there (the decoder masks them as keys), so they pass exactly 0 through the tail; the tail's own
+// attention masks them as keys as well.
+int bw_cross_level_tail(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, const float* G) {
+    const ovc_model* m = e.m;
+    const Workspace& w = t.w;
+    const ClTape& p = t.tape.cl;
+    hipStream_t s = e.stream;
+    const ovc_mha& at = m->cl_att;
+    const ovc_mha& ga = gr->cl_att;
+    const int BN = B * N, d = m->d_model, eh = enc_heads(m), edk = enc_dk(m), hk = eh * edk;
+    const size_t nd = (size_t)BN * d;
+    const float* o1 = w.cl_out; const float* o2 = w.cl_out + nd; const float* o3 = w.cl_out + 2 * nd;
+    // mlp2, mlp1
+    RUN(ovc_bw_leaky(G, p.h2, kMlpScale, kSlope, t.cl_dh, (long)nd, s));
+    TRY(bw_weight(e, t, t.cl_dh, d, d, p.a1, d, d, BN, m->cl_mlp2, gr->cl_mlp2));
+    TRY(bw_input(e, t, t.cl_dh, d, m->cl_mlp2, d, t.cl_da, nullptr, BN));
+    RUN(ovc_bw_leaky(t.cl_da, p.a1, 1.f, kSlope, t.cl_da, (long)nd, s));
+    TRY(bw_weight(e, t, t.cl_da, d, d, w.cl_cat, 3 * d, 3 * d, BN, m->cl_mlp1, gr->cl_mlp1));
+    TRY(bw_input(e, t, t.cl_da, d, m->cl_mlp1, 3 * d, t.cl_dcat, nullptr, BN));
+    // the two cross calls, last first
+    const float* queries[2] = {o2, o3};
+    const float* dout[2] = {t.cl_do2p, G};
+    for (int c = 1; c >= 0; --c) {
+        float* dss = t.cl_dss + (size_t)c * nd;
+        RUN(ovc_bw_layer_norm_post(p.ya + (size_t)c * nd, queries[c], at.ln.g, dout[c], kCrossScale, m->ln_eps, BN, d, dss,
+                                   t.prod + (size_t)c * nd, t.dyc + (size_t)c * nd, s));
+        TRY(bw_input(e, t, dss, d, at.o, hk, t.datt, nullptr, BN));
+        AttnBwdArgs a{};
+        a.q = w.cl_q + (size_t)c * BN * hk; a.ldq = hk; a.k = p.k[c]; a.v = p.v[c]; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
+        a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
+        a.B = B; a.nq = N; a.nk = N; a.h = eh; a.dk = edk; a.scale = sqrtf((float)edk);
+        a.P = t.P; a.dS = t.dS;
+        a.dq = t.cl_dq + (size_t)c * BN * hk; a.lddq = hk;
+        a.dk_out = t.cl_dkv + (size_t)c * BN * 2 * hk; a.dv_out = a.dk_out + hk; a.lddkv = 2 * hk;
+        RUN(ovc_bw_attention(a, s));
+        TRY(stage_kv_weights(e, t, at, hk));
+        // call 2's keys / values are o2' (its whole gradient); call 1's are o1 (its tail share before dcat1)
+        TRY(bw_mm(e, a.dk_out, 2 * hk, BN, 2 * hk, t.wt, d, c == 1 ? t.cl_do2p : t.cl_dlev));
+    }
+    // self_attn's weights over both calls' rows
+    TRY(bw_weight(e, t, t.cl_dss, d, d, p.att, hk, hk, 2 * BN, at.o, ga.o));
+    RUN(ovc_bw_colsum(t.prod, d, 2 * BN, d, t.part, out_ptr(ga.ln.g), s));
+    RUN(ovc_bw_colsum(t.dyc, d, 2 * BN, d, t.part, out_ptr(ga.ln.b), s));
+    TRY(bw_weight(e, t, t.cl_dq, hk, hk, o2, d, d, 2 * BN, at.q, ga.q));              // queries: o2 | o3, back to back in cl_out
+    TRY(bw_weight_pair(e, t, t.cl_dkv, 2 * hk, hk, o1, p.o2p, d, d, BN, at.k, ga.k));
+    TRY(bw_weight_pair(e, t, t.cl_dkv + hk, 2 * hk, hk, o1, p.o2p, d, d, BN, at.v, ga.v));
+    // the levels
+    TRY(bw_input(e, t, t.cl_dq, hk, at.q, d, t.cl_dq23, t.cl_dss, 2 * BN));            // dq . W_q + dss, both calls
+    float* dlev = t.cl_dlev;
+    RUN(ovc_bw_sum(dlev, d, t.cl_dcat, 3 * d, nullptr, 0, BN, d, dlev, d, s));
+    RUN(ovc_bw_sum(t.cl_dq23, d, t.cl_do2p, d, t.cl_dcat + d, 3 * d, BN, d, dlev + nd, d, s));
+    RUN(ovc_bw_sum(t.cl_dq23 + nd, d, G, d, t.cl_dcat + 2 * d, 3 * d, BN, d, dlev + 2 * nd, d, s));
+    return OVC_OK;
+}
+
 // seq (ovc_sequence_backward): S sequences per image, and the row weights t.w_row come from the caller's grad_logp (written before the
 // body) instead of the cross-entropy's: the dlogit alone, no loss.
 int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T, int S = 1, bool seq = false) {
@@ -1975,16 +2103,28 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
     // encoder layers, top down: the output rows of padding regions were cleared after each layer's norm
     e.gemm_class = 1;
     const int eh = enc_heads(m), edk = enc_dk(m);
+    const bool cl = m->enc_kind == OVC_ENC_CROSS_LEVEL;
+    const size_t nd = (size_t)BN * d;
     const float* dout = t.denc[enc_cur];
+    if (cl) {
+        // the cross-level tail; then layer l's output gradient is the tail's share of it plus layer l+1's input gradient
+        TRY(bw_cross_level_tail(e, t, gr, B, N, dout));
+        dout = t.cl_dlev + 2 * nd;
+    }
     for (int l = m->n_enc - 1; l >= 0; --l) {
         const EncTape& p = t.tape.enc[l];
         const ovc_enc_layer& el = m->enc[l];
         const ovc_enc_layer& gl = gr->enc[l];
-        const float* xin = l == 0 ? w.xe[0] : t.tape.enc[l - 1].out;
+        const float* xin = l == 0 ? w.xe[0] : cl ? w.cl_out + (size_t)(l - 1) * nd : t.tape.enc[l - 1].out;
         TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
                               enc_site(l, 0)));
         dout = t.g[cur];
+        if (cl && l > 0) {
+            float* lev = t.cl_dlev + (size_t)(l - 1) * nd;
+            RUN(ovc_bw_sum(lev, d, t.g[cur], d, nullptr, 0, BN, d, lev, d, s));
+            dout = lev;
+        }
         cur ^= 1;
     }
     // feature embedding: encoder.layer_norm over the projection (the sinusoid added after it has no parameters)
@@ -2074,7 +2214,7 @@ extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, 
 }
 
 extern "C" size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T) {
-    if (!train_ok(m, B, N, T)) return 0;
+    if (!dropout_train_ok(m, B, N, T)) return 0;
     return carve_train(m, nullptr, B, N, T, true).bytes;
 }
 
@@ -2083,7 +2223,7 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                             size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                             const ovc_dropout* dropout) {
     (void)boxes;
-    if (!dropout || !dropout->seed || !m) return OVC_EINVAL;
+    if (!dropout || !dropout->seed || !m || !dropout_train_ok(m, B, N, T)) return OVC_EINVAL;
     float p[OVC_DROPOUT_SITES] = {};
     p[kSiteEmb] = dropout->emb;
     for (int l = 0; l < OVC_MAX_LAYERS; ++l) {

@@ -134,7 +134,9 @@ def _ffn(dst, pwff, planes=None, mode=0):
 
 def _grad_slots(model):
     """(parameter, field path in the ``ovc_model`` table) of every parameter ``ovc_forward_backward`` writes a gradient for:
-    the plain encoder / decoder's projections, norms and FFNs, the word embedding and the vocabulary projection."""
+    the plain encoder / decoder's projections, norms and FFNs, the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``,
+    ``mlp2``), the word embedding and the vocabulary projection."""
+    from .modules import encoders
     enc, dec = model.encoder, model.decoder
     slots = []
 
@@ -162,6 +164,10 @@ def _grad_slots(model):
     for i, layer in enumerate(enc.layers):
         mha(("enc", i, "att"), layer.mhatt)
         ffn(("enc", i, "ffn"), layer.pwff)
+    if isinstance(enc, encoders.CrossAttentionMultiLevelEncoder):
+        mha(("cl_att",), enc.self_attn)
+        lin(("cl_mlp1",), enc.mlp1)
+        lin(("cl_mlp2",), enc.mlp2)
     for i, layer in enumerate(dec.layers):
         mha(("dec", i, "self_att"), layer.self_attn)
         mha(("dec", i, "cross_att"), layer.enc_attn)
@@ -575,15 +581,18 @@ class CaptionEngine:
 
     # -- training ---------------------------------------------------------------------------------------------------
     def _check_trainable(self):
-        """The backward covers the plain standard transformer in fp32: anything else is refused before a launch."""
+        """The backward covers the plain standard transformer and the CaMo transformer (cross-level encoder, plain decoder) in
+        fp32: anything else is refused before a launch."""
         d = self.desc
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
-        if d.enc_kind != native.ENC_PLAIN or d.dec_kind != native.DEC_PLAIN:
-            raise native.OvcError("the training backward covers the plain Encoder / Decoder only (the meshed decoder and the "
-                                  "multilevel, geometric and cross-level encoders are not supported)")
+        if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
+            raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
+                                  "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
         model = self.model
         mhas = [layer.mhatt for layer in model.encoder.layers]
+        if d.enc_kind == native.ENC_CROSS_LEVEL:
+            mhas.append(model.encoder.self_attn)
         mhas += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
         if any(m.use_aoa for m in mhas):
             raise native.OvcError("the training backward does not cover attention-on-attention gates")

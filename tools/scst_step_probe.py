@@ -31,8 +31,12 @@ def recompute_flops(dims, images, S, N, T):
     image's S sequences of T rows through the decoder."""
     d, h, dk, dff, dfeat, V, Le, Ld = (dims[k] for k in ("d", "h", "dk", "dff", "dfeat", "V", "Le", "Ld"))
     BN, R, hk = images * N, images * S * T, h * dk
+    he = dims.get("he", h)
     f = 2 * BN * dfeat * d
-    f += Le * (2 * BN * d * 3 * hk + 4 * images * h * N * N * dk + 2 * BN * hk * d + 4 * BN * d * dff)
+    f += Le * (2 * BN * d * 3 * he * dk + 4 * images * he * N * N * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
+    if dims.get("tail"):            # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
+        f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * images * he * N * N * dk + 2 * BN * he * dk * d)
+        f += 2 * BN * 3 * d * d + 2 * BN * d * d
     f += Ld * 2 * BN * d * 2 * hk
     f += Ld * (2 * R * d * 3 * hk + 4 * images * S * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * R * N * h * dk
                + 2 * R * hk * d + 4 * R * d * dff)
@@ -55,12 +59,14 @@ def main():
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
+                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D, k = 10201, 20, 50, 2048, args.beam
     vocab = SyntheticVocab(V, T)
-    cfg = model_config("standard_transformer", d_feature=D, device="cuda:0")
+    cfg = model_config(args.variant, d_feature=D, device="cuda:0")
     model = build_model(cfg, vocab)
     template = model.state_dict()
     sd = eos_biased_state_dict({**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}, template)
@@ -71,6 +77,8 @@ def main():
             m.p = 0.0
     eng = model._fused_engine()
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
+    if args.variant == "camo_transformer":
+        dims.update(he=1, tail=True)
     results = []
     for B in args.batches:
         feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
@@ -101,13 +109,13 @@ def main():
                     shared.append(ms_a)
                     expanded.append(ms_e)
         except (RuntimeError, torch.cuda.OutOfMemoryError) as exc:        # B = 256: the expanded layout may not fit
-            results.append({"B": B, "k": k, "error": str(exc).splitlines()[0]})
+            results.append({"variant": args.variant, "B": B, "k": k, "error": str(exc).splitlines()[0]})
             print(json.dumps(results[-1]))
             torch.cuda.empty_cache()
             continue
         f_shared, f_exp = recompute_flops(dims, B, k, N, T), recompute_flops(dims, B * k, 1, N, T)
         med = statistics.median
-        r = {"B": B, "k": k, "T": T, "N": N, "mean_caption_length": lengths,
+        r = {"variant": args.variant, "B": B, "k": k, "T": T, "N": N, "mean_caption_length": lengths,
              "search_ms": med(search_ms), "backward_ms": med(backward_ms), "step_ms": med(search_ms) + med(backward_ms),
              "shared_ms": med(shared), "expanded_ms": med(expanded), "expanded_over_shared_time": med(expanded) / med(shared),
              "shared_gflop": f_shared / 1e9, "expanded_gflop": f_exp / 1e9, "expanded_over_shared_flops": f_exp / f_shared,

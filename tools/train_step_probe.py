@@ -30,8 +30,12 @@ PEAK_F32_MATRIX = 157.3e12
 def step_flops(cfg_dims, B, N, T):
     d, h, dk, dff, dfeat, V, Le, Ld = (cfg_dims[k] for k in ("d", "h", "dk", "dff", "dfeat", "V", "Le", "Ld"))
     BN, R, hk = B * N, B * T, h * dk
+    he = cfg_dims.get("he", h)
     f = 2 * BN * dfeat * d
-    f += Le * (2 * BN * d * 3 * hk + 4 * B * h * N * N * dk + 2 * BN * hk * d + 4 * BN * d * dff)
+    f += Le * (2 * BN * d * 3 * he * dk + 4 * B * he * N * N * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
+    if cfg_dims.get("tail"):        # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
+        f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * B * he * N * N * dk + 2 * BN * he * dk * d)
+        f += 2 * BN * 3 * d * d + 2 * BN * d * d
     f += Ld * 2 * BN * d * 2 * hk
     f += Ld * (2 * R * d * 3 * hk + 4 * B * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * B * h * T * N * dk
                + 2 * R * hk * d + 4 * R * d * dff)
@@ -45,17 +49,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
+    ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
+                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
-    cfg = model_config("standard_transformer", d_feature=D, device="cuda:0")
+    cfg = model_config(args.variant, d_feature=D, device="cuda:0")
     model = build_model(cfg, vocab).eval()
     model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
     if args.dropout:
         model.train()
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
+    if args.variant == "camo_transformer":
+        dims.update(he=1, tail=True)
     results = []
     for B in args.batches:
         g = torch.Generator().manual_seed(B)
@@ -81,7 +89,7 @@ def main():
         lib = model._fused_engine().lib
         sizer = lib.ovc_train_dropout_workspace_bytes if args.dropout else lib.ovc_train_workspace_bytes
         ws = sizer(model._fused_engine().desc, B, N, T)
-        row = dict(B=B, T=T, N=N, dropout=args.dropout, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
+        row = dict(variant=args.variant, B=B, T=T, N=N, dropout=args.dropout, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
                    tflops=round(flops / ms / 1e9, 2), fp32_matrix_fraction=round(flops / (ms * 1e-3) / PEAK_F32_MATRIX, 4),
                    workspace_mb=round(ws / 2 ** 20, 1))
         results.append(row)

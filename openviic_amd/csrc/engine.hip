@@ -225,7 +225,9 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     w.ff = a.take<float>(R * m->d_ff);
     w.info = a.take<float>(R * d); w.gate = a.take<float>(R * d);
     w.enc_att = a.take<float>(lv * R * d); w.alpha = a.take<float>(lv * R * d); w.mixed = a.take<float>(R * d);
-    w.ymesh = a.take<float>(lv > 1 ? lv * R * d : 0);
+    // the meshed block's stacked cross-attention outputs: written for every level count, one level included (a zero-byte
+    // take would alias the next buffer)
+    w.ymesh = a.take<float>(m->dec_kind == OVC_DEC_MESHED ? lv * R * d : 0);
     w.part = a.take<float>(kMaxKSplit * R * d);
     w.kc = a.take<float>(L * T * R * hk);
     w.vc = a.take<float>(L * T * R * hv);
@@ -268,7 +270,7 @@ Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int
     w.ff = a.take<float>(rows * m->d_ff);
     w.info = a.take<float>(rows * d); w.gate = a.take<float>(rows * d);
     w.enc_att = a.take<float>(lv * rows * d); w.alpha = a.take<float>(lv * rows * d); w.mixed = a.take<float>(rows * d);
-    w.ymesh = a.take<float>(lv > 1 ? lv * rows * d : 0);
+    w.ymesh = a.take<float>(m->dec_kind == OVC_DEC_MESHED ? lv * rows * d : 0);       // as in carve: one level too
     w.padflag = a.take<uint8_t>(rows);
     w.self_mask = a.take<uint8_t>(rows * T);
     w.tgt = a.take<int32_t>(rows);

@@ -1,5 +1,6 @@
 """Shared construction of parity cases: the same configuration, weights and inputs that
 ``tests/golden/make_goldens.py`` fed to the reference."""
+import math
 import os
 
 import numpy as np
@@ -124,3 +125,49 @@ def assert_ids_match_where_decided(ids, ref_ids, gaps, inner_gaps, tol, what="")
     bad = [b for b in np.nonzero(decided)[0] if not np.array_equal(ids[b], ref_ids[b])]
     assert not bad, "{}: ids differ for decided images {}".format(what, bad)
     return decided
+
+
+def rel_gap(a, b):
+    """||a - b|| / ||b|| (relative L2 distance; an exact 0 in ``b`` makes any nonzero ``a`` fail every bar)."""
+    return float((a - b).norm() / max(float(b.norm()), 1e-30))
+
+
+def check_gradients_per_tensor(got, g64, g32, floor=1e-5, factor=10.0, pad=0, what="", kink=None):
+    """Each parameter gradient on its own bar: ``rel(got_k, g64_k) <= eps_k = max(floor, factor * rel(g32_k, g64_k))``.
+
+    ``got`` / ``g64`` / ``g32``: ``{state_dict key: fp64 CPU gradient}`` of the engine, the float64 oracle and the float32
+    oracle on the same fp32 weights and inputs.  A tensor's bar follows that tensor's own conditioning, so a badly conditioned
+    tensor does not loosen the bar of the others.  Also: the same set of tensors, no gradient for ``decoder.pos_emb.weight``,
+    an exact 0 in the ``pad`` row of ``decoder.word_emb``, every ``fc_k.bias`` 0 (softmax is shift-invariant over keys) to 1e-6
+    of its weight's largest gradient or to ``factor`` times the fp32 oracle's own largest value, a tensor whose fp64 gradient is
+    exactly 0 exactly 0 as well, and no NaN / Inf anywhere.  ``kink``: ``{key: rel(g_on_k - g_off_k, g64_k)}``, the float64
+    gradients with every (leaky) ReLU pre-activation near its kink taken as positive / as negative -- which side an fp32
+    forward lands on there is rounding, so the bar is also at least twice that spread.
+    Returns ``{key: gap_k / eps_k}`` (for ``fc_k.bias``: largest |g| over its bar)."""
+    assert set(got) == set(g64), "{}: {}".format(what, sorted(set(got) ^ set(g64)))
+    assert "decoder.pos_emb.weight" not in got, what
+    assert torch.all(got["decoder.word_emb.components.weight"][pad] == 0), what
+    ratio, bad = {}, {}
+    for k, want in g64.items():
+        assert bool(torch.isfinite(got[k]).all()), "{}: {} is not finite".format(what, k)
+        if k.endswith("fc_k.bias"):
+            # exactly 0: what is left is rounding, which in deep stacks can exceed 1e-6 of the weight's gradient -- then the
+            # bar is the fp32 oracle's own rounding of the same 0, times ``factor``
+            ref = float(got[k[:-len("bias")] + "weight"].abs().max())
+            bar = max(1e-6 * ref, factor * float(g32[k].abs().max()))
+            ratio[k] = float(got[k].abs().max()) / max(bar, 1e-300)
+            assert ratio[k] <= 1, (what, k, float(got[k].abs().max()), ref, float(g32[k].abs().max()))
+            continue
+        if not bool((want != 0).any()):                             # an exact 0 (no target left): exactly 0 here too
+            ratio[k] = 0.0 if not bool((got[k] != 0).any()) else math.inf
+            if ratio[k]:
+                bad[k] = (float(got[k].abs().max()), 0.0)
+            continue
+        eps = max(floor, factor * rel_gap(g32[k], want), 2.0 * kink[k] if kink else 0.0)
+        gap = rel_gap(got[k], want)
+        ratio[k] = gap / eps
+        if not gap <= eps:
+            bad[k] = (gap, eps)
+    assert not bad, "{}: per-tensor gap above its bar (gap, eps): {}".format(
+        what, sorted(bad.items(), key=lambda kv: -ratio[kv[0]])[:8])
+    return ratio

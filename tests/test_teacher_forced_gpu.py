@@ -167,6 +167,11 @@ SWEEP = [   # variant, dims, (B, N, V, T)
     ("standard_transformer", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=2), (3, 9, 53, 1)),
     ("attention_on_attention", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=2), (3, 20, 97, 7)),
     ("meshed_memory_transformer", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=2, memory=5), (2, 33, 61, 64)),
+    # one encoder layer = one level: the meshed block's stacked output once had no room of its own in the workspace and its GEMM
+    # wrote over the padding flags and the buffers after them (every row came out uniform; scoring with a small vocabulary ran
+    # past the workspace's end).  The second row is the shape of tests/test_fuzz_train_gpu.py's default seed, case 32.
+    ("meshed_memory_transformer", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=1, memory=5), (3, 9, 53, 7)),
+    ("meshed_memory_transformer", dict(d_feature=36, d_model=192, heads=12, d_kv=16, d_ff=244, layers=1, memory=40), (6, 129, 32, 36)),
     ("object_relation_transformer", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=2), (2, 40, 53, 65)),
     ("standard_transformer", dict(d_feature=32, d_model=128, heads=4, d_kv=32, d_ff=256, layers=2), (2, 257, 61, 256)),
     ("standard_transformer", dict(d_feature=32, d_model=64, heads=4, d_kv=16, d_ff=128, layers=1), (2, 12, 16411, 9)),

@@ -406,6 +406,45 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
                           const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out,
                           int use_graph, ovc_stream stream);
 
+/* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
+ * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host
+ * (openviic_amd/cider.py) in float64.  An n-gram (n = 1..4) of word ids below 65535 is ONE 64-bit key: word j of the n-gram sits as
+ * id + 1 in bits 16 j .. 16 j + 15, the unused upper fields are 0, so n-grams of different orders never collide and 0 is no key.
+ *   hash_key / hash_idf [hash_size]   open addressing, linear probing, hash_size a power of two (or 0: no table), key 0 = empty:
+ *                                     n-gram -> idf = ref_len - log(max(1, df)) for every n-gram with df >= 1.  The slot of a key
+ *                                     is (mix(key) & (hash_size - 1)), mix(x) = y ^ (y >> 29) with y = (x ^ (x >> 32)) * 0x9E3779B97F4A7C15
+ *                                     (mod 2^64).  An absent key has df = 0: its idf is ref_len.
+ *   image_ref [n_images + 1]          image -> its references (CSR);  ref_entry [n_refs + 1]  reference -> its entries (CSR)
+ *   entry_key / entry_w               a reference's distinct n-grams, ascending by key, with their tf-idf weights
+ *   ref_norm [n_refs][4]              the reference's tf-idf norm per n-gram order;  ref_length [n_refs]  its "length": the
+ *                                     reference sums term frequencies where the 0-based order is 1, i.e. its number of BIGRAMS
+ * N-grams that hold a word no hypothesis can contain (out-of-vocabulary words, the special tokens) count in the norms and lengths
+ * but have no entry: they can never match. */
+typedef struct {
+    const uint64_t* hash_key;
+    const double*   hash_idf;
+    const int32_t*  image_ref;
+    const int32_t*  ref_entry;
+    const uint64_t* entry_key;
+    const double*   entry_w;
+    const double*   ref_norm;
+    const double*   ref_length;
+    int32_t hash_size, n_images, n_refs, vocab;
+    int32_t pad_idx, bos_idx, eos_idx, unk_idx;
+    double  sigma;                     /* the length penalty's standard deviation (6) */
+    double  ref_len;                   /* log(number of documents of the df corpus)   */
+} ovc_cider;
+
+/* reward_out[b][s] (fp32) = 10 * CIDEr-D of hypothesis ids[b][s][0..T-1] (int64) against the references of image rows[b] (int32;
+ * clamped into the corpus on the device).  The hypothesis is decoded as vocab.decode_caption does: ids are clamped into
+ * [0, vocab), tokens after the first eos_idx are dropped, and so are the four special ids.  One wave per hypothesis; n-grams are
+ * sorted in LDS, every sum is in float64 in a fixed order (lane partials over ascending index, one butterfly) and rounded to fp32
+ * once: the same bits on every call, stream and graph replay.  An empty hypothesis and an image without references score 0.
+ * One launch, no allocation, no synchronisation.  OVC_EINVAL (nothing launched): a null pointer, B < 1, S < 1, T outside
+ * 1..OVC_MAX_LEN, vocab outside 1..65535, a hash_size that is no power of two. */
+int ovc_cider_reward(const ovc_cider* c, const int64_t* ids, const int32_t* rows, int B, int S, int T,
+                     float* reward_out, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

@@ -72,6 +72,15 @@ class Model(ctypes.Structure):
     ]
 
 
+class Cider(ctypes.Structure):
+    """``ovc_cider``: the device tables of ``openviic_amd.cider.CiderCorpus``."""
+    _fields_ = [("hash_key", c_void_p), ("hash_idf", c_void_p), ("image_ref", c_void_p), ("ref_entry", c_void_p),
+                ("entry_key", c_void_p), ("entry_w", c_void_p), ("ref_norm", c_void_p), ("ref_length", c_void_p),
+                ("hash_size", c_int32), ("n_images", c_int32), ("n_refs", c_int32), ("vocab", c_int32),
+                ("pad_idx", c_int32), ("bos_idx", c_int32), ("eos_idx", c_int32), ("unk_idx", c_int32),
+                ("sigma", c_double), ("ref_len", c_double)]
+
+
 ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC, ENC_CROSS_LEVEL = 0, 1, 2, 3
 DEC_PLAIN, DEC_MESHED = 0, 1
 
@@ -145,6 +154,7 @@ SIGNATURES = {
     "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_cider_reward": (c_int, [POINTER(Cider), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),

@@ -4,20 +4,31 @@ full standard configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers,
 regions, dropout 0.  The weights are EOS-biased (``eos_biased_state_dict``) so captions end at realistic lengths.
 
     python tools/scst_step_probe.py [--batches 60 256] [--beam 5] [--steps 10] [--warmup 3] [--out results/scst_step_probe.json]
+    python tools/scst_step_probe.py --reward device|host [--corpus-images 5000] ...      # the step WITH its CIDEr reward
 
 Time: device events around each phase after ``--warmup`` steps (the second call captures the graphs), one synchronise per step.
 Shared against expanded: ``sequence_backward`` with the encoder once per image (S = k) against the same entry at S = 1 on the
-features repeated k times, alternating in one process, median of ``--steps`` each.  FLOPs: the matrix products of the recompute
+features repeated k times, alternating in one process, median of ``--steps`` each.
+``--reward device`` / ``host`` (default ``none``: the above, with a fixed random reward) time the whole step with the reward computed
+from the search's ids against a seeded synthetic corpus (``--corpus-images`` images x 5 references of 8..18 words): ``device`` is
+``CiderCorpus.reward`` (one kernel; its ms from device events), ``host`` is what the reference's loop does -- copy the ids to the
+host, ``decode_caption``, score the strings (``tests/cider_oracle.py``), copy the rewards back -- timed by the wall clock including the
+copies and the synchronisation.  Steps with the reward and steps with the fixed reward alternate in one process; a whole step is
+wall clock from before the search to a synchronise after the backward (one synchronise per step), and the spread of the repeated
+steps is reported with the medians.  FLOPs: the matrix products of the recompute
 from the shapes (projections, attention, FFN, vocabulary) times 3, for both layouts.  Needs a HIP device."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 
 from openviic_amd.builders import build_model                                        # noqa: E402
 from openviic_amd.config import model_config                                         # noqa: E402
@@ -53,6 +64,88 @@ def timed(fn):
     return a.elapsed_time(b), out
 
 
+def synthetic_corpus(images, V, seed=0):
+    """``images`` x 5 reference captions of 8..18 words over a vocabulary of V ids, frequent words first (seeded)."""
+    rng = np.random.default_rng(seed)
+    return [[" ".join("w%d" % min(int(rng.exponential(150.0)), V - 5) for _ in range(int(rng.integers(8, 19)))) for _ in range(5)]
+            for _ in range(images)]
+
+
+def spread(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
+
+
+def reward_probe(args, model, V, T, N, D, k):
+    """Whole SCST steps with the CIDEr reward (``args.reward``) against steps with a fixed reward, alternating."""
+    from cider_oracle import CiderOracle
+    from openviic_amd.cider import CiderCorpus
+    from openviic_amd.vocab import WordVocab
+    words = WordVocab(["<pad>", "<bos>", "<eos>", "<unk>"] + ["w%d" % i for i in range(V - 4)], T)
+    captions = synthetic_corpus(max(args.corpus_images, max(args.batches)), V)
+    t0 = time.perf_counter()
+    corpus = CiderCorpus(words, captions, captions).to("cuda")
+    build_s = time.perf_counter() - t0
+    oracle = CiderOracle(captions) if args.reward == "host" else None
+    results = []
+    for B in args.batches:
+        feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        items = InstanceList()
+        items.region_features = feats
+        batch_captions = captions[:B]                        # what the dictionary dataset yields as items.captions
+        fixed = torch.rand(B, k, generator=torch.Generator().manual_seed(1)).cuda()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+
+        def step(mode):
+            torch.cuda.synchronize()
+            t_start = time.perf_counter()
+            rows = corpus.rows(batch_captions) if mode == "device" else None
+            ev[0].record()
+            outs, log_probs = model.beam_search(items, batch_size=B, beam_size=k, out_size=k)
+            ev[1].record()
+            host_ms = 0.0
+            if mode == "none":
+                reward = fixed
+            elif mode == "device":
+                reward = corpus.reward(outs, rows)
+            else:
+                torch.cuda.synchronize()                     # the copy below would wait for the search anyway
+                t_host = time.perf_counter()
+                caps_gen = words.decode_caption(outs.contiguous().view(-1, T), join_words=True)
+                caps_gt = [refs for refs in batch_captions for _ in range(k)]
+                reward = np.array(oracle.rewards(caps_gen, caps_gt)).astype(np.float32)
+                reward = torch.from_numpy(reward).to(outs.device).view(B, k)
+                torch.cuda.synchronize()
+                host_ms = 1e3 * (time.perf_counter() - t_host)
+            ev[2].record()
+            loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
+            model.zero_grad(set_to_none=True)
+            loss.backward()
+            ev[3].record()
+            torch.cuda.synchronize()
+            whole = 1e3 * (time.perf_counter() - t_start)
+            return {"step": whole, "search": ev[0].elapsed_time(ev[1]), "reward": host_ms if mode == "host" else ev[1].elapsed_time(ev[2]),
+                    "backward": ev[2].elapsed_time(ev[3])}, reward
+
+        runs = {"none": [], args.reward: []}
+        for i in range(args.warmup + args.steps):
+            for mode in ("none", args.reward):
+                t, reward = step(mode)
+                if i >= args.warmup:
+                    runs[mode].append(t)
+        r = {"variant": args.variant, "reward": args.reward, "B": B, "k": k, "T": T, "N": N, "corpus_images": len(captions),
+             "corpus_build_s": build_s, "mean_reward": float(reward.mean()),
+             "reward_ms": spread([t["reward"] for t in runs[args.reward]]),
+             "reward_clock": "device events" if args.reward == "device" else "wall clock with the copies and the synchronisation",
+             "step_ms": spread([t["step"] for t in runs[args.reward]]),
+             "step_ms_fixed_reward": spread([t["step"] for t in runs["none"]]),
+             "search_ms": spread([t["search"] for t in runs[args.reward]]),
+             "backward_ms": spread([t["backward"] for t in runs[args.reward]])}
+        r["step_minus_fixed_ms"] = r["step_ms"]["median"] - r["step_ms_fixed_reward"]["median"]
+        results.append(r)
+        print(json.dumps(r))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
@@ -61,6 +154,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
+    ap.add_argument("--reward", default="none", choices=["none", "host", "device"],
+                    help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
+    ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -79,8 +175,8 @@ def main():
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     if args.variant == "camo_transformer":
         dims.update(he=1, tail=True)
-    results = []
-    for B in args.batches:
+    results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" else []
+    for B in args.batches if args.reward == "none" else []:
         feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
         items = InstanceList()
         items.region_features = feats

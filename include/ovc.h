@@ -406,6 +406,45 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
                           const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out,
                           int use_graph, ovc_stream stream);
 
+/* SCST under dropout (the reference's train_scst searches in train() mode, vi_trainer.py:121-158): the beam search with the
+ * dropout sites above applied, and the backward of its log-probabilities under the SAME masks.  The plain standard transformer,
+ * precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.
+ * Mask rows.  Encoder-side sites key on row b * N + n as above (the encoder runs once per image in both calls).  Decoder-side
+ * sites of the search key on the MASK ROW of the row that is being decoded,
+ *     mrow(b, slot, t) = (b * k + slot) * T + t,      T = max_len, slot = the beam slot that holds the row at decode step t
+ * (step 0 has one row per image, slot 0; k = 1 gives ovc_forward_backward_dropout's b * T + t).  A pure function of (seed, site, b,
+ * slot, t, col): never of the tiling, the 16- or 32-row GEMM family, the K split, the stream, graph replay or the search form.
+ * Each decoder site masks the finished value v = act(product + bias) -- the bits the search without dropout forms, same K order
+ * -- as keep ? v * s : 0 before the residual add: the AddNorm behind fc_o / fc2 masks the summed K slices plus bias, one row
+ * kernel masks relu(fc1).  The vocabulary product, the selection and the self-attention have no site.
+ * ovc_beam_search_dropout: ovc_beam_search_graph (mode 0), ovc_beam_search_early (mode 1; steps_run_out, HOST memory, as there) or
+ * ovc_beam_search_gated (mode 2; steps_out, DEVICE memory, as there) with dropout -- either may be NULL and is ignored by the other
+ * modes; identical ids / logp / slots in all three.  slots_out [B][out_size][T] int32 (required), in
+ * the order of ids_out: slots[b][o][t] = the slot the returned beam's ancestor held at step t (its own at its last step); entries
+ * after the beam's first <eos> are written as 0 (callers may pass anything there: those rows carry no gradient).  The seed is copied into the workspace outside the captured body and the p values
+ * are part of the graph key, as in ovc_forward_backward_dropout.  With every p == 0 the decode launches are the plain search's.
+ * Workspace: ovc_beam_search_dropout_workspace_bytes (the plain layout plus the seed slot; 0 when unsupported).
+ * ovc_sequence_backward_dropout: ovc_sequence_backward whose recompute masks decoder row (b, s, t) as mrow(b, slots[b][s][t], t)
+ * (a table written on the device from `slots` outside the captured body) and the encoder rows as above: with the search's
+ * seed, p values, k and slot table the recomputed logp are the search's log_probs and the gradient is that of the stochastic
+ * forward the search ran.  T must equal max_len (the T of the mask rows).  Same determinism as ovc_sequence_backward.
+ * ovc_train_beams_dropout_workspace_bytes: its workspace, 0 for anything ovc_train_dropout_workspace_bytes refuses.
+ * OVC_EINVAL, nothing launched: a null dropout table, seed or slot table, any p outside [0, 1), k outside 1..OVC_MAX_BEAM, S > k,
+ * an unsupported model.
+ * ovc_dropout_mask_rows: ovc_dropout_mask over an arbitrary list of mask rows (int32, device): keep[i * cols + c] = the keep
+ * decision of (site, mask_rows[i], c) -- openviic_amd/dropout.py keep_rows. */
+size_t ovc_beam_search_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k);
+int ovc_beam_search_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                            void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
+                            const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out, int* steps_run_out);
+size_t ovc_train_beams_dropout_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                  int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                                  float* logp_out, int use_graph, ovc_stream stream, int k, const int32_t* slots,
+                                  const ovc_dropout* dropout);
+int ovc_dropout_mask_rows(const int64_t* seed, int site, const int32_t* mask_rows, long rows, long cols, float p, uint8_t* keep,
+                          ovc_stream stream);
+
 /* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
  * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host
  * (openviic_amd/cider.py) in float64.  An n-gram (n = 1..4) of word ids below 65535 is ONE 64-bit key: word j of the n-gram sits as

@@ -54,8 +54,10 @@ class _BeamLogProbs(torch.autograd.Function):
     search and ``backward()`` (an optimizer step) raises torch's in-place error instead of differentiating other weights."""
 
     @staticmethod
-    def forward(ctx, engine_, refusal, features, boxes, ids, log_probs, *params):
-        ctx.engine, ctx.refusal = engine_, refusal
+    def forward(ctx, engine_, refusal, drop, features, boxes, ids, log_probs, *params):
+        # refusal: None or the text backward() raises.  drop: None or the search's dropout (probs, seed, slots, beam size) -- the
+        # recompute then runs under the masks the search used
+        ctx.engine, ctx.refusal, ctx.drop = engine_, refusal, drop
         ctx.features, ctx.boxes, ctx.ids = features, boxes, ids
         ctx.save_for_backward(*params)
         return log_probs.clone()
@@ -67,10 +69,14 @@ class _BeamLogProbs(torch.autograd.Function):
             raise engine.native.OvcError(ctx.refusal)
         ids = ctx.ids if ctx.ids.dim() == 3 else ctx.ids[:, None]
         g = grad_output.reshape(ids.shape)
-        _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g)
+        if ctx.drop is not None:
+            probs, seed, slots, beam = ctx.drop
+            _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g, dropout=(probs, seed), slots=slots, beam_size=beam)
+        else:
+            _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g)
         by_param = {id(p): gr for p, gr in zip(ctx.engine.gradient_parameters(), grads)}
         out = tuple(by_param.get(id(p)) if p.requires_grad else None for p in params)
-        return (None, None, None, None, None, None) + out
+        return (None, None, None, None, None, None, None) + out
 
 
 class BaseTransformer(Module):
@@ -193,8 +199,32 @@ class BaseTransformer(Module):
         return _XeLoss.apply(eng, None, input_features[self.feature_field], boxes, input_features["caption_tokens"],
                              input_features["shifted_right_caption_tokens"], *params)
 
+    def _search_dropout_probs(self):
+        """``{site: p}`` for ``beam_search(dropout=True)``, or the refusals of its scope: before any launch and any draw."""
+        if not self.training:
+            return {}
+        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+        if not live:
+            return {}
+        if isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
+            raise engine.native.OvcError(
+                "beam_search(dropout=True): dropout covers the standard transformer; the cross-level encoder applies "
+                "encoder.self_attn.dropout twice in its tail and the engine has no site for it -- set DROPOUT: 0 or call "
+                "model.eval() (live: {})".format(live[0]))
+        if type(self) not in (StandardTransformerUsingRegion, StandardTransformerUsingGrid):
+            raise engine.native.OvcError(
+                "beam_search(dropout=True): dropout covers the plain standard transformer only, not {} (live: {}) -- set "
+                "DROPOUT: 0 or call model.eval()".format(type(self).__name__, live[0]))
+        probs = _dropout.model_probs(self)          # names a p >= 1 and a live dropout without a site
+        eng = self._fused_engine()
+        if eng.precision != "f32":
+            raise engine.native.OvcError("beam_search(dropout=True) runs in 'f32' only (precision={!r}; live: {})".format(
+                eng.precision, live[0]))
+        eng._check_trainable()
+        return probs
+
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
-                    fused=True, **kwargs):
+                    fused=True, dropout=False, generator=None, **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
 
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
@@ -204,7 +234,33 @@ class BaseTransformer(Module):
         Fused, in ``train()`` mode with gradients enabled: the returned ``log_probs`` carry a gradient (``_BeamLogProbs``), so
         the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard transformer or the CaMo
         transformer in 'f32' with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
+
+        ``dropout=True`` (fused only; the plain standard transformer in 'f32'): in ``train()`` mode every ``nn.Dropout`` applies
+        its own ``p`` DURING the search, as the reference's ``train_scst`` does (``vi_trainer.py:121-158`` searches after
+        ``model.train()``), with or without grad; the backward of ``log_probs`` recomputes the sequences under the same masks.
+        One seed per call, drawn on the stream from ``generator`` as ``xe_loss`` draws it.  In ``eval()`` mode or with every
+        ``p == 0`` this is the plain call: same bits, no random draw.  Anything outside the scope is refused here, before any
+        launch or draw, naming the module; so is ``return_probs`` together with a live dropout (the masked search has no
+        ``return_probs`` form).  ``early_exit=`` selects the search form as without dropout.
         """
+        if dropout and not fused:
+            raise engine.native.OvcError("beam_search(dropout=True) needs fused=True: the host loop has no dropout site table")
+        if fused and dropout:
+            probs = self._search_dropout_probs()
+            if probs:
+                if return_probs:
+                    raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
+                eng = self._fused_engine()
+                feats = input_features[self.feature_field]
+                seed = _dropout.draw_seed(eng.device, generator)
+                ids, logp, slots = eng.beam_search(feats, None, batch_size, beam_size, out_size=out_size,
+                                                   early_exit=kwargs.get("early_exit"), dropout=(probs, seed))
+                params = [p for p in self.parameters() if p.requires_grad]
+                if torch.is_grad_enabled() and params:
+                    logp = _BeamLogProbs.apply(eng, None, (probs, seed, slots, beam_size), feats.detach(), None, ids, logp, *params)
+                if out_size == 1:
+                    ids, logp = ids.squeeze(1), logp.squeeze(1)
+                return ids, logp
         if fused:
             boxes = input_features["region_boxes"] if self.uses_boxes else None
             feats = input_features[self.feature_field]
@@ -228,7 +284,7 @@ class BaseTransformer(Module):
         if live:
             refusal = ("beam_search: the model is in train() mode with dropout > 0 ({}); the engine's search and its backward take "
                        "dropout as the identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
-        return _BeamLogProbs.apply(self._fused_engine(), refusal, features.detach(), None if boxes is None else boxes.detach(),
+        return _BeamLogProbs.apply(self._fused_engine(), refusal, None, features.detach(), None if boxes is None else boxes.detach(),
                                    ids, log_probs, *params)
 
 

@@ -24,6 +24,10 @@ int ovc_bw_relu(float* g, const float* act, long n, hipStream_t s);
 // counter, columns = d).
 int ovc_bw_layer_norm_dropout(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows, int d,
                               float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop, hipStream_t s);
+// the same with the mask row of row r read from rowmap[r] (ovc_sequence_backward_dropout, decoder sites)
+int ovc_bw_layer_norm_dropout_mapped(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows,
+                                     int d, float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop,
+                                     const int32_t* rowmap, hipStream_t s);
 // The FFN's inner site: act is the stored DROPPED ReLU output, nonzero iff kept and positive, so g[i] = act[i] > 0 ? g[i] * s : 0
 // needs no mask.
 int ovc_bw_relu_dropout(float* g, const float* act, float scale, long n, hipStream_t s);

@@ -93,35 +93,22 @@ __global__ __launch_bounds__(256) void bw_layer_norm_dropout_kernel(const float*
                                                                     float eps, int rows, int d, float* __restrict__ dx,
                                                                     float* __restrict__ prod, float* __restrict__ dyc,
                                                                     float* __restrict__ dproj, DropoutSite drop) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const size_t o = (size_t)row * d;
-    if (zero_rows && zero_rows[row]) {
-        for (int c = lane; c < d; c += 64) { dx[o + c] = 0.f; prod[o + c] = 0.f; dyc[o + c] = 0.f; dproj[o + c] = 0.f; }
-        return;
-    }
-    const uint64_t seed = (uint64_t)*drop.seed;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += x[o + c];
-    const float mean = wave_sum(s) / d;
-    float v = 0.f;
-    for (int c = lane; c < d; c += 64) { const float t = x[o + c] - mean; v += t * t; }
-    const float rstd = 1.f / sqrtf(wave_sum(v) / d + eps);
-    float a = 0.f, b = 0.f;
-    for (int c = lane; c < d; c += 64) {
-        const float xh = (x[o + c] - mean) * rstd, g = gamma[c] * dy[o + c];
-        a += g; b += g * xh;
-    }
-    a = wave_sum(a) / d; b = wave_sum(b) / d;
-    for (int c = lane; c < d; c += 64) {
-        const float xh = (x[o + c] - mean) * rstd, g = dy[o + c];
-        const float gx = rstd * (gamma[c] * g - a - xh * b);
-        dx[o + c] = gx;
-        prod[o + c] = g * xh;
-        dyc[o + c] = g;
-        dproj[o + c] = ovc_dropout_keep(seed, drop.site, (uint64_t)row * (uint64_t)drop.cols + (uint64_t)c, drop.thr) ? gx * drop.scale : 0.f;
-    }
+#define OVC_BW_MASK_ROW row
+#include "bodies/bw_layer_norm_dropout.inc"
+#undef OVC_BW_MASK_ROW
+}
+
+// bw_layer_norm_dropout_kernel with the mask row of row r taken from rowmap[r] (ovc_sequence_backward_dropout: the rows of a
+// generated sequence are masked as the search masked them, csrc/dropout.h)
+__global__ __launch_bounds__(256) void bw_layer_norm_dropout_mapped_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ dy, const uint8_t* __restrict__ zero_rows,
+                                                                    float eps, int rows, int d, float* __restrict__ dx,
+                                                                    float* __restrict__ prod, float* __restrict__ dyc,
+                                                                    float* __restrict__ dproj, DropoutSite drop,
+                                                                           const int32_t* __restrict__ rowmap) {
+#define OVC_BW_MASK_ROW (uint32_t)rowmap[row]
+#include "bodies/bw_layer_norm_dropout.inc"
+#undef OVC_BW_MASK_ROW
 }
 
 __global__ void bw_relu_dropout_kernel(float* __restrict__ g, const float* __restrict__ act, float scale, long n) {
@@ -136,6 +123,17 @@ __global__ void dropout_mask_kernel(const int64_t* __restrict__ seed_ptr, uint32
     const uint64_t n = (uint64_t)rows * (uint64_t)cols;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
         keep[i] = ovc_dropout_keep(seed, site, i, thr) ? 1 : 0;
+}
+
+// keep[i * cols + c] = the keep decision of (site, rowmap[i], c): dropout_mask_kernel over an arbitrary list of mask rows
+__global__ void dropout_mask_rows_kernel(const int64_t* __restrict__ seed_ptr, uint32_t site, uint32_t thr, const int32_t* __restrict__ rowmap,
+                                         long rows, long cols, uint8_t* __restrict__ keep) {
+    const uint64_t seed = (uint64_t)*seed_ptr;
+    const uint64_t n = (uint64_t)rows * (uint64_t)cols;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / (uint64_t)cols, c = i - r * (uint64_t)cols;
+        keep[i] = ovc_dropout_keep(seed, site, (uint64_t)(uint32_t)rowmap[r] * (uint64_t)cols + c, thr) ? 1 : 0;
+    }
 }
 
 __global__ void bw_relu_kernel(float* __restrict__ g, const float* __restrict__ act, long n) {
@@ -342,6 +340,16 @@ int ovc_bw_layer_norm_dropout(const float* x, const float* gamma, const float* d
     return OVC_OK;
 }
 
+int ovc_bw_layer_norm_dropout_mapped(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows,
+                                     int d, float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop,
+                                     const int32_t* rowmap, hipStream_t s) {
+    if (d > 2048 || !drop.seed || drop.cols != d || !rowmap) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_layer_norm_dropout_mapped_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, dy, zero_rows, eps, rows, d,
+                       dx, prod, dyc, dproj, drop, rowmap);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 int ovc_bw_relu_dropout(float* g, const float* act, float scale, long n, hipStream_t s) {
     hipLaunchKernelGGL(bw_relu_dropout_kernel, dim3(blocks_for(n)), dim3(256), 0, s, g, act, scale, n);
     OVC_RETURN_IF_LAUNCH_FAILED();
@@ -406,6 +414,20 @@ extern "C" int ovc_dropout_mask(const int64_t* seed, int site, long rows, long c
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks), dim3(256), 0, ovc_hip_stream(stream), seed, (uint32_t)site,
                        ovc_dropout_threshold(p), rows, cols, keep);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+extern "C" int ovc_dropout_mask_rows(const int64_t* seed, int site, const int32_t* mask_rows, long rows, long cols, float p, uint8_t* keep,
+                                     ovc_stream stream) {
+    if (!seed || !keep || !mask_rows || site < 0 || site >= OVC_DROPOUT_SITES || rows < 0 || cols < 0 || !(p >= 0.f && p < 1.f))
+        return OVC_EINVAL;
+    if (rows == 0 || cols == 0) return OVC_OK;
+    if (const int rc = ovc_device_guard()) return rc;
+    const uint64_t n = (uint64_t)rows * (uint64_t)cols;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(dropout_mask_rows_kernel, dim3(blocks), dim3(256), 0, ovc_hip_stream(stream), seed, (uint32_t)site,
+                       ovc_dropout_threshold(p), mask_rows, rows, cols, keep);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

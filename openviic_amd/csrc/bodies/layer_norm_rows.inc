@@ -49,6 +49,9 @@
 #pragma unroll
         for (int s = 1; s < kParts; ++s) v[i] += part[s][i];
         if (kBias) v[i] += bv[i];
+#ifdef OVC_LN_MASK
+        OVC_LN_MASK(v[i], col[i]);      // the dropout instances (layer_norm_rows_dropout): the finished projection, before the residual
+#endif
         if (kRes) v[i] += rv[i];
         if (lane + i * 64 < nvec) sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }

@@ -23,8 +23,8 @@ __host__ __device__ __forceinline__ uint32_t ovc_mulhi32(uint32_t a, uint32_t b)
     return (uint32_t)(((uint64_t)a * b) >> 32);
 }
 
-// Philox4x32-10 (Salmon et al., SC'11), word `w` of the output block
-__device__ __forceinline__ uint32_t ovc_philox_word(uint64_t key, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, int w) {
+// Philox4x32-10 (Salmon et al., SC'11): the output block of counter (c0..c3) under `key`, left in c0..c3
+__device__ __forceinline__ void ovc_philox_block(uint64_t key, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3) {
     uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
@@ -33,6 +33,11 @@ __device__ __forceinline__ uint32_t ovc_philox_word(uint64_t key, uint32_t c0, u
         c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
+}
+
+// word `w` of the output block
+__device__ __forceinline__ uint32_t ovc_philox_word(uint64_t key, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, int w) {
+    ovc_philox_block(key, c0, c1, c2, c3);
     return w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
 }
 
@@ -41,9 +46,40 @@ __device__ __forceinline__ bool ovc_dropout_keep(uint64_t seed, uint32_t site, u
     return ovc_philox_word(seed, (uint32_t)g, (uint32_t)(g >> 32), site, 0u, (int)(idx & 3)) >= thr;
 }
 
+// The four keep decisions of element group g (elements 4 g .. 4 g + 3 of the site's index space) as bits 0..3: one Philox block.
+// Bit j is ovc_dropout_keep(seed, site, 4 g + j, thr).
+__device__ __forceinline__ uint32_t ovc_dropout_keep4(uint64_t key, uint32_t site, uint64_t g, uint32_t thr) {
+    uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = site, c3 = 0u;
+    ovc_philox_block(key, c0, c1, c2, c3);
+    return (c0 >= thr ? 1u : 0u) | (c1 >= thr ? 2u : 0u) | (c2 >= thr ? 4u : 0u) | (c3 >= thr ? 8u : 0u);
+}
+
+// Dropout inside the beam search (ovc_beam_search_dropout): row r of decode step t is beam slot r % width of image r / width
+// (width = 1 at step 0, the beam size k later), and its decoder-side masks are keyed by the MASK ROW
+//   mrow(b, slot, t) = (b * k + slot) * T + t                                        (T = max_len; k = 1: xe_loss's b * T + t)
+// The teacher-forced recompute of a final beam (ovc_sequence_backward_dropout) reaches the same rows through a table built from
+// the beam's ancestor slots.
+struct DecodeRowKey { int width, k, T, t; };
+__device__ __forceinline__ uint64_t ovc_decode_mask_row(const DecodeRowKey& key, int row) {
+    const int b = row / key.width, slot = row - b * key.width;
+    return ((uint64_t)b * (uint64_t)key.k + (uint64_t)slot) * (uint64_t)key.T + (uint64_t)key.t;
+}
+
 // Host: the per-site constants from p (the caller has checked 0 <= p < 1)
 static inline uint32_t ovc_dropout_threshold(float p) {
     const double t = (double)p * 4294967296.0 + 0.5;
     return t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
 }
 static inline float ovc_dropout_scale(float p) { return (float)(1.0 / (1.0 - (double)p)); }
+
+// ---- row-keyed launches (rowops.hip, backward.hip) ----------------------------------------------
+// LayerNorm(keep ? v * s : 0 + residual) with v = sum_s parts[s] + bias, the AddNorm of a decode-step projection at a dropout site:
+// nparts in {1, 2, 4} (1: `parts` is the finished product, bias already applied, bias == nullptr), residual required.  v has the
+// bits the plain AddNorm forms.  Row r is masked as mask row ovc_decode_mask_row(key, r).  gate: nullptr = ungated.
+int ovc_layer_norm_parts_dropout(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
+                                 const float* gamma, const float* beta, const uint8_t* zero_rows, float eps, float* y, int rows, int d,
+                                 const DropoutSite& drop, const DecodeRowKey& key, hipStream_t stream, const int32_t* gate);
+// x[r, :] = (keep ? x[r, :] * s : 0) + residual[r, :] in place (residual may be nullptr), cols a multiple of 4.  The mask row of
+// row r is rowmap[r] when rowmap != nullptr (the teacher-forced recompute), else ovc_decode_mask_row(key, r) (the search).
+int ovc_dropout_rows(float* x, const float* residual, int rows, int cols, const DropoutSite& drop, const DecodeRowKey& key,
+                     const int32_t* rowmap, hipStream_t stream, const int32_t* gate);

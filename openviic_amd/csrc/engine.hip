@@ -130,6 +130,8 @@ struct Workspace {
     float* all_buf;
     int64_t* out_ids; float* out_logp;            // graph replay writes here, then copied to the caller
     int32_t* alive_count;                         // [T] beams still alive after each step (ovc_beam_search_early)
+    int64_t* drop_seed; int32_t* steps_dev;       // ovc_beam_search_dropout: the call's seed (refreshed outside the captured body)
+                                                  // and the gated search's step count for the slot table
     // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
     // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -213,7 +215,7 @@ void carve_encoder(Workspace& w, Bump& a, const ovc_model* m, int B, int N) {
     w.vx = a.take<float>(L * lv * BN * hv);
 }
 
-Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_probs) {
+Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_probs, bool dropout = false) {
     Workspace w{};
     Bump a{reinterpret_cast<char*>(base), 0};
     const size_t R = (size_t)B * k, d = m->d_model, T = m->max_len;
@@ -247,6 +249,10 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     w.all_buf = a.take<float>(return_probs ? T * R * (size_t)m->vocab : 0);
     w.out_ids = a.take<int64_t>(R * T); w.out_logp = a.take<float>(R * T);
     w.alive_count = a.take<int32_t>(T);
+    if (dropout) {                                // ovc_beam_search_dropout: behind everything else, so the plain layout is a prefix
+        w.drop_seed = a.take<int64_t>(2);
+        w.steps_dev = a.take<int32_t>(4);
+    }
     w.bytes = (a.off + 255) & ~(size_t)255;
     return w;
 }
@@ -453,6 +459,44 @@ __global__ __launch_bounds__(256) void seq_inputs_kernel(const int64_t* __restri
     }
 }
 
+// ovc_beam_search_dropout: slots[b, o, t] = the beam slot that held final beam o of image b (the o-th of the sorted output) at step
+// t, from the ancestor table of the state the final ordering read (anc[steps & 1]; an entry is the global row b * width_t + slot of
+// the ancestor at step t, the beam's own row at its last step).  steps = *steps_dev when given (the gated search), else
+// steps_host.  Positions behind the beam's first <eos> and positions that never ran get 0, so every search form writes the same
+// table.  One thread per returned beam.  An entry outside 0..width-1 cannot occur; the clamp keeps the table in range regardless
+// (it feeds index arithmetic).
+__global__ void beam_slots_kernel(const int32_t* __restrict__ anc0, const int32_t* __restrict__ anc1, const int32_t* __restrict__ hist0,
+                                  const int32_t* __restrict__ hist1, const int32_t* __restrict__ order,
+                                  const int32_t* __restrict__ steps_dev, int steps_host, int eos, int B, int k, int T, int out_size,
+                                  int32_t* __restrict__ slots) {
+    const int bo = blockIdx.x * blockDim.x + threadIdx.x;
+    if (bo >= B * out_size) return;
+    const int S = steps_dev ? *steps_dev : steps_host;
+    const int32_t* anc = S & 1 ? anc1 : anc0;
+    const int32_t* hist = S & 1 ? hist1 : hist0;
+    const int o = bo % out_size, b = bo / out_size;
+    const int beam = min(max(order[b * k + o], 0), k - 1);
+    const size_t src = ((size_t)b * k + beam) * T;
+    bool ended = false;
+    for (int t = 0; t < T; ++t) {
+        const int width = t == 0 ? 1 : k;
+        const bool live = t < S && !ended;
+        const int slot = live ? anc[src + t] - b * width : 0;
+        slots[(size_t)bo * T + t] = min(max(slot, 0), width - 1);
+        ended = ended || (live && hist[src + t] == eos);
+    }
+}
+
+// ovc_sequence_backward_dropout: maskrow[(b S + s) T + t] = (b k + slots[b, s, t]) T + t, the mask row the search used for that
+// row (slots clamped into 0..k-1: entries behind a beam's first <eos> are unspecified and their rows carry no gradient)
+__global__ void seq_maskrow_kernel(const int32_t* __restrict__ slots, int B, int S, int T, int k, int32_t* __restrict__ maskrow) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * S * T) return;
+    const int t = i % T, b = i / (S * T);
+    const int slot = min(max(slots[i], 0), k - 1);
+    maskrow[i] = (b * k + slot) * T + t;
+}
+
 // logp[r] = the recomputed log-probability of the target where kept, 0 after the first <eos> (bw_loss_kernel's formula)
 __global__ void seq_logp_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
                                 const int32_t* __restrict__ tgt, const uint8_t* __restrict__ keep, int rows, float* __restrict__ logp) {
@@ -507,6 +551,13 @@ struct Engine {
     const int32_t* gate = nullptr;                   // device-side early exit: the gate of every launch issued next (run_decode_step
                                                      // sets it per step of a gated search; nullptr = ungated launches)
     const DropPlan* drop = nullptr;                  // training dropout: the sites' masks (nullptr: no site is active)
+    // Dropout keyed by the search's rows.  decode_key.width > 0: a decode step of ovc_beam_search_dropout --
+    // the decoder sites mask row r as ovc_decode_mask_row(decode_key, r), in the AddNorm / a row kernel behind the four-chain
+    // products.  maskrow != nullptr: the recompute of ovc_sequence_backward_dropout -- the decoder sites read row r's mask row from
+    // the table.  Encoder sites key on b * N + n in both and take the masked GEMM epilogue.
+    DecodeRowKey decode_key{0, 0, 0, 0};
+    const int32_t* maskrow = nullptr;
+    bool row_keyed(int site) const { return site_on(site) && site >= dec_site(0, 0) && (decode_key.width > 0 || maskrow); }
 
     bool site_on(int site) const { return drop && site >= 0 && drop->on[site]; }
     DropoutSite drop_site(int site, int cols) const {
@@ -580,6 +631,30 @@ struct Engine {
     int linear_ln(const float* x, int K, const ovc_lin& l, const float* residual, const ovc_norm& ln,
                   const uint8_t* zero_rows, float* y_tmp, float* part, float* out, int M, int site = -1) {
         const int d = m->d_model;
+        if (row_keyed(site)) {
+            if (!residual) return OVC_EINVAL;
+            if (maskrow) {
+                // the recompute: the one-chain product with its bias, then the mask through the row table and the residual
+                TRY(linear(x, K, l, nullptr, y_tmp, M, d, 0));
+                TRY(ovc_dropout_rows(y_tmp, residual, M, d, drop_site(site, d), decode_key, maskrow, stream, nullptr));
+                return ovc_layer_norm_gated(y_tmp, nullptr, ln.g, ln.b, nullptr, 0, zero_rows, m->ln_eps, out, M, d, stream, gate);
+            }
+            // the search: the product exactly as without dropout (same class, same K slices); the AddNorm instance masks the
+            // finished projection -- the slices' sum plus bias -- before it adds the residual
+            const int dsplit = part && l.b ? decode_ksplit(K) : 1;
+            if (dsplit != 2 && dsplit != 4) {
+                TRY(linear(x, K, l, nullptr, y_tmp, M, d, 0));
+                return ovc_layer_norm_parts_dropout(y_tmp, 1, 0L, nullptr, residual, ln.g, ln.b, zero_rows, m->ln_eps, out, M, d,
+                                                    drop_site(site, d), decode_key, stream, gate);
+            }
+            GemmArgs a{};
+            a.A1 = x; a.lda1 = K; a.K1 = K; a.M = M; a.seg_n = d; a.nseg = 1; a.ldc = d;
+            a.ksplit = dsplit; a.part_stride = (long)M * d;
+            a.seg[0] = seg(l, part); a.seg[0].bias = nullptr;
+            TRY(gemm(a));
+            return ovc_layer_norm_parts_dropout(part, dsplit, a.part_stride, l.b, residual, ln.g, ln.b, zero_rows, m->ln_eps, out, M, d,
+                                                drop_site(site, d), decode_key, stream, gate);
+        }
         const int split = part && l.b && residual && !site_on(site) ? decode_ksplit(K) : 1;
         if (split != 2 && split != 4) {
             TRY(linear(x, K, l, residual, y_tmp, M, d, 0, site));
@@ -622,7 +697,12 @@ struct Engine {
     // site_inner / site_out: the dropout sites on relu(fc1) and on fc2 (-1: none)
     int ffn(const ovc_ffn& w, const float* x, float* ff, float* y, float* part, float* out, const uint8_t* zero_rows, int M,
             int site_inner = -1, int site_out = -1) {
-        TRY(linear(x, m->d_model, w.fc1, nullptr, ff, M, m->d_ff, 1, site_inner));
+        if (row_keyed(site_inner)) {
+            TRY(linear(x, m->d_model, w.fc1, nullptr, ff, M, m->d_ff, 1));
+            TRY(ovc_dropout_rows(ff, nullptr, M, m->d_ff, drop_site(site_inner, m->d_ff), decode_key, maskrow, stream, gate));
+        } else {
+            TRY(linear(x, m->d_model, w.fc1, nullptr, ff, M, m->d_ff, 1, site_inner));
+        }
         return linear_ln(ff, m->d_ff, w.fc2, x, w.ln, zero_rows, y, part, out, M, site_out);
     }
 };
@@ -786,6 +866,11 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
     const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
     const int cur = t & 1, nxt = cur ^ 1;
     uint8_t* padflag_t = w.padflag + (size_t)t * R;
+    // ovc_beam_search_dropout: this step's rows key the decoder sites' masks; without a plan no site is on and the launches are
+    // the plain ones
+    const bool keyed = e.drop != nullptr && !e.dry;
+    e.decode_key = keyed ? DecodeRowKey{width, k, T, t} : DecodeRowKey{0, 0, 0, 0};
+    auto site = [&](int l, int j) { return keyed ? dec_site(l, j) : -1; };
 
     if (t == 0 && !e.dry) {       // later steps: the previous step's update kernel has written the input rows and pad flags
         hipLaunchKernelGGL(decode_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.tok, m->bos_idx, m->pad_idx, t,
@@ -817,7 +902,7 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
         sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = w.att; sa.ldo = hv;
         sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
         if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s, e.gate));
-        TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, w.part, w.x1, rows));
+        TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, w.part, w.x1, rows, site(l, 0)));
         TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));
 
         // ---- cross-attention: the image's beams share its projected encoder keys/values -----------
@@ -868,11 +953,11 @@ int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int ret
             RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s, e.gate));
             ffn_in = w.mixed;
         } else {
-            TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, w.part, w.x2, rows));
+            TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, w.part, w.x2, rows, site(l, 1)));
             TRY(e.aoa(dl.cross_att, w.x1, w.x2, w.info, w.gate, rows));
             ffn_in = w.x2;
         }
-        TRY(e.ffn(dl.ffn, ffn_in, w.ff, w.y, w.part, w.x, padflag_t, rows));
+        TRY(e.ffn(dl.ffn, ffn_in, w.ff, w.y, w.part, w.x, padflag_t, rows, site(l, 2), site(l, 3)));
         x = w.x;
     }
 
@@ -1286,6 +1371,31 @@ hipStream_t private_capture_stream() {
     return capture_stream;
 }
 
+// ovc_beam_search_dropout: the plan of a search with dropout (nullptr everywhere else: the plain search, launch for launch).
+struct SearchDrop {
+    DropPlan* plan; const int64_t* seed; uint64_t hash;     // hash: the p values, part of every graph key
+    int32_t* slots_out;                                      // [B][out_size][T], the caller's
+};
+
+// Binds a search's Engine to its dropout plan: the seed slot is refreshed here, outside any captured body.
+int bind_search_drop(Engine& e, Workspace& w, SearchDrop* sd) {
+    if (!sd) return OVC_OK;
+    if (hipMemcpyAsync(w.drop_seed, sd->seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    sd->plan->seed = w.drop_seed;
+    e.drop = sd->plan;
+    return OVC_OK;
+}
+
+// The slot table of a finished search (beam_slots_kernel), after the final ordering has written w.order.
+int write_search_slots(Engine& e, Workspace& w, SearchDrop* sd, const int32_t* steps_dev, int steps_host, int B, int k, int out_size) {
+    if (!sd || !sd->slots_out) return OVC_OK;
+    const int T = e.m->max_len, n = B * out_size;
+    hipLaunchKernelGGL(beam_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, e.stream, w.anc[0], w.anc[1], w.hist[0], w.hist[1], w.order,
+                       steps_dev, steps_host, e.m->eos_idx, B, k, T, out_size, sd->slots_out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 int issue_decode_graph_body(Engine& e, Workspace& w, int B, int N, int k, int out_size) {
     const ovc_model* m = e.m;
     const int R = B * k, T = m->max_len;
@@ -1302,20 +1412,20 @@ int issue_decode_graph_body(Engine& e, Workspace& w, int B, int N, int k, int ou
 }
 }  // namespace
 
-extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                                     float* logp_out, ovc_stream stream) {
+namespace {
+int beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
+                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream, SearchDrop* sd) {
     if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
     if ((long)m->vocab < k) return OVC_EINVAL;
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0);
+    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
     if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const size_t out_n = (size_t)B * out_size * m->max_len;
 
-    const GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, k, out_size};
+    const GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
     std::lock_guard<std::mutex> lock(g_graph_mutex);
     GraphEntry& entry = g_graphs[key];
     entry.calls += 1;
@@ -1323,6 +1433,7 @@ extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, 
     entry.last_stream = e.stream;
     evict_lru(&key, nullptr);
 
+    TRY(bind_search_drop(e, w, sd));
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
     // The launch sequence is captured on a PRIVATE stream, never on the caller's: while a stream is capturing, HIP
     // refuses queries of events that were recorded on it earlier (hipErrorCapturedEvent), and other components poll
@@ -1338,6 +1449,7 @@ extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, 
             entry.unsupported = true;
         } else {
             Engine ce{m, capture_stream, 0};
+            ce.drop = e.drop;
             const int rc = issue_decode_graph_body(ce, w, B, N, k, out_size);
             const hipError_t end = hipStreamEndCapture(capture_stream, &entry.graph);
             if (rc != OVC_OK || end != hipSuccess || !entry.graph ||
@@ -1356,7 +1468,14 @@ extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, 
     }
     if (hipMemcpyAsync(ids_out, w.out_ids, sizeof(int64_t) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     if (hipMemcpyAsync(logp_out, w.out_logp, sizeof(float) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    return OVC_OK;
+    return write_search_slots(e, w, sd, nullptr, m->max_len, B, k, out_size);
+}
+}  // namespace
+
+extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, ovc_stream stream) {
+    return beam_search_graph(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1383,10 +1502,11 @@ int issue_early_prologue(Engine& e, Workspace& w, int B, int N, int k) {
 
 // Capture `issue` on the private stream into (graph, exec); false = capture not available (the caller launches plainly).
 template <typename Issue>
-bool capture_into(hipGraph_t* graph, hipGraphExec_t* exec, const ovc_model* m, Issue issue) {
+bool capture_into(hipGraph_t* graph, hipGraphExec_t* exec, const ovc_model* m, Issue issue, const DropPlan* drop = nullptr) {
     hipStream_t cs = private_capture_stream();
     if (!cs || hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return false; }
     Engine ce{m, cs, 0};
+    ce.drop = drop;
     const int rc = issue(ce);
     const hipError_t end = hipStreamEndCapture(cs, graph);
     if (rc != OVC_OK || end != hipSuccess || !*graph || hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) {
@@ -1399,22 +1519,22 @@ bool capture_into(hipGraph_t* graph, hipGraphExec_t* exec, const ovc_model* m, I
 }
 }  // namespace
 
-extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                                     float* logp_out, int* steps_run_out, ovc_stream stream) {
+namespace {
+int beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
+                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, int* steps_run_out, ovc_stream stream, SearchDrop* sd) {
     if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
     if ((long)m->vocab < k) return OVC_EINVAL;
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0);
+    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
     if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const int T = m->max_len;
 
     std::shared_ptr<EarlyEntry> entry;
     {
-        const GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, k, out_size};
+        const GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         std::shared_ptr<EarlyEntry>& slot = g_early[key];
         if (!slot) slot = std::make_shared<EarlyEntry>();
@@ -1437,10 +1557,11 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
     }
     const bool graphs = !entry->unsupported && !g_profile_on && entry->calls > 1;   // first call of a shape: plain (warms every kernel)
 
+    TRY(bind_search_drop(e, w, sd));
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
     if (graphs && !entry->prologue_exec) {
         std::lock_guard<std::mutex> lock(g_graph_mutex);           // the capture stream is shared process-wide
-        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_early_prologue(ce, w, B, N, k); }))
+        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_early_prologue(ce, w, B, N, k); }, e.drop))
             entry->unsupported = true;
     }
     if (graphs && entry->prologue_exec) { if (hipGraphLaunch(entry->prologue_exec, e.stream) != hipSuccess) return OVC_ELAUNCH; }
@@ -1451,7 +1572,7 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
         if (graphs && !entry->unsupported && !entry->step_exec[t]) {
             std::lock_guard<std::mutex> lock(g_graph_mutex);
             if (!capture_into(&entry->step_graph[t], &entry->step_exec[t], m,
-                              [&](Engine& ce) { return run_decode_step(ce, w, B, N, k, t, 0, true); }))
+                              [&](Engine& ce) { return run_decode_step(ce, w, B, N, k, t, 0, true); }, e.drop))
                 entry->unsupported = true;
         }
         if (graphs && entry->step_exec[t]) { if (hipGraphLaunch(entry->step_exec[t], e.stream) != hipSuccess) return OVC_ELAUNCH; }
@@ -1473,7 +1594,15 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
     bf.steps_run = steps_run < T ? steps_run : 0;
     TRY(ovc_beam_finalize_launch(bf, B, e.stream));
     if (steps_run_out) *steps_run_out = steps_run;
-    return OVC_OK;
+    return write_search_slots(e, w, sd, nullptr, steps_run, B, k, out_size);
+}
+}  // namespace
+
+extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, int* steps_run_out, ovc_stream stream) {
+    return beam_search_early(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_run_out, stream,
+                             nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1502,22 +1631,23 @@ int issue_gated_body(Engine& e, Workspace& w, int B, int N, int k) {
 }
 }  // namespace
 
-extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                                     float* logp_out, int32_t* steps_out, ovc_stream stream) {
+namespace {
+int beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
+                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, int32_t* steps_out, ovc_stream stream, SearchDrop* sd) {
     if (!model_ok(m) || m->precision != 0 || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
     if ((long)m->vocab < k) return OVC_EINVAL;
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0);
+    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
     if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const int T = m->max_len;
 
+    TRY(bind_search_drop(e, w, sd));
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
     {
-        GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, k, out_size};
+        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
         key.kind = 2;
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         GraphEntry& entry = g_graphs[key];
@@ -1528,7 +1658,7 @@ extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, 
         // first call of a shape: plain gated launches; from the second on ONE graph, captured on the private stream as
         // ovc_beam_search_graph explains
         if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec &&
-            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }))
+            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }, e.drop))
             entry.unsupported = true;
         if (entry.exec && !g_profile_on) {
             if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
@@ -1542,7 +1672,18 @@ extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, 
         bf[i].running = w.running[i]; bf[i].hist = w.hist[i]; bf[i].lp = w.lp[i];
         bf[i].k = k; bf[i].T = T; bf[i].out_size = out_size; bf[i].ids_out = ids_out; bf[i].logp_out = logp_out; bf[i].order_out = w.order;
     }
-    return ovc_beam_finalize_gated_launch(bf, w.alive_count, steps_out, B, e.stream);
+    if (!sd) return ovc_beam_finalize_gated_launch(bf, w.alive_count, steps_out, B, e.stream);
+    // the slot table reads the step count the final ordering found: through a workspace word, copied to the caller's afterwards
+    TRY(ovc_beam_finalize_gated_launch(bf, w.alive_count, w.steps_dev, B, e.stream));
+    if (steps_out && hipMemcpyAsync(steps_out, w.steps_dev, sizeof(int32_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    return write_search_slots(e, w, sd, w.steps_dev, 0, B, k, out_size);
+}
+}  // namespace
+
+extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, int32_t* steps_out, ovc_stream stream) {
+    return beam_search_gated(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_out, stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1738,6 +1879,7 @@ struct TrainWs {
     // sequences (carve_train(..., seq = true) only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
     // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
     int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
+    int32_t* maskrow;             // [rows] sequences with dropout: the mask row of every decoder row (seq_maskrow_kernel)
     // the cross-level tail (bw_cross_level_tail; cross-level models only), rows B*N: the leaky-ReLU gradients dh [B*N][d] (mlp2's,
     // then mlp1's in da), mlp1's input gradient dcat [B*N][3d], per cross call c the pre-norm sum's gradient dss [2][B*N][d], dq
     // [2][B*N][h_enc dk_enc], dk|dv [2][B*N][2 h_enc dk_enc], then d(o2') and the q path plus dss, dq23 [2][B*N][d]; the levels'
@@ -1805,6 +1947,7 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
     }
     if (seq) {
         t.seq_tok = a.take<int64_t>(rows); t.seq_tgt = a.take<int64_t>(rows); t.seq_keep = a.take<uint8_t>(rows);
+        if (dropout) t.maskrow = a.take<int32_t>(rows);
     }
     t.bytes = (a.off + 255) & ~(size_t)255;
     return t;
@@ -1880,7 +2023,10 @@ int bw_norm(Engine& e, TrainWs& t, const float* y, const ovc_norm& n, const ovc_
             int rows, int site = -1) {
     hipStream_t s = e.stream;
     const int d = e.m->d_model;
-    if (e.site_on(site))
+    if (e.row_keyed(site))
+        RUN(ovc_bw_layer_norm_dropout_mapped(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d),
+                                             e.maskrow, s));
+    else if (e.site_on(site))
         RUN(ovc_bw_layer_norm_dropout(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d), s));
     else
         RUN(ovc_bw_layer_norm(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, s));
@@ -2272,18 +2418,29 @@ extern "C" size_t ovc_train_beams_workspace_bytes(const ovc_model* m, int B, int
     return carve_train(m, nullptr, B, N, T, false, S, true).bytes;
 }
 
-extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
-                                     int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
-                                     float* logp_out, int use_graph, ovc_stream stream) {
-    (void)boxes;       // the plain encoder reads no boxes
+namespace {
+// ovc_sequence_backward (drop == nullptr) and ovc_sequence_backward_dropout (drop: at least one site active; the decoder sites'
+// mask rows come from the search's slot table)
+int sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, int S, const int64_t* ids,
+                      const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out, int use_graph,
+                      ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash, int k, const int32_t* slots) {
     if (!seq_ok(m, B, N, S, T) || !grads || !grads_ok(m, grads) || !features || !ids || !grad_logp || !workspace) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    TrainWs t = carve_train(m, workspace, B, N, T, false, S, true);
+    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr, S, true);
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const int nseq = B * S, rows = nseq * T, BN = B * N;
+    if (drop) {
+        // the seed slot and the row table are refreshed here, outside the captured body
+        if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        hipLaunchKernelGGL(seq_maskrow_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, slots, B, S, T, k, t.maskrow);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        drop->seed = t.seed;
+        e.drop = drop;
+        e.maskrow = t.maskrow;
+    }
 
     // the kernels that read the caller's inputs, outside the captured body
     TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
@@ -2295,11 +2452,15 @@ extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads,
     OVC_RETURN_IF_LAUNCH_FAILED();
     TRY(ovc_bw_tokens(t.seq_tok, rows, m->vocab, t.tok, e.stream));
     TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
-    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T, S, true); };
+    auto body = [&](Engine& ce) {
+        ce.drop = drop;
+        ce.maskrow = drop ? t.maskrow : nullptr;
+        return issue_train_body(ce, t, grads, B, N, T, S, true);
+    };
     if (!use_graph) {
         TRY(body(e));
     } else {
-        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull), workspace, B, N, T, S};
+        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ drop_hash, workspace, B, N, T, S};
         key.kind = 5;
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         GraphEntry& entry = g_graphs[key];
@@ -2321,4 +2482,86 @@ extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads,
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
     return OVC_OK;
+}
+
+// The per-site constants of a caller's table; OVC_EINVAL for a p outside [0, 1) (NaN included).  *any: a site is active.
+int make_drop_plan(const ovc_dropout* dropout, DropPlan* plan, uint64_t* hash, bool* any) {
+    float p[OVC_DROPOUT_SITES] = {};
+    p[kSiteEmb] = dropout->emb;
+    for (int l = 0; l < OVC_MAX_LAYERS; ++l) {
+        for (int j = 0; j < 3; ++j) p[enc_site(l, j)] = dropout->enc[l][j];
+        for (int j = 0; j < 4; ++j) p[dec_site(l, j)] = dropout->dec[l][j];
+    }
+    *any = false;
+    for (int i = 0; i < OVC_DROPOUT_SITES; ++i) {
+        if (!(p[i] >= 0.f && p[i] < 1.f)) return OVC_EINVAL;
+        plan->on[i] = p[i] > 0.f;
+        plan->thr[i] = ovc_dropout_threshold(p[i]);
+        plan->scale[i] = ovc_dropout_scale(p[i]);
+        *any = *any || plan->on[i];
+    }
+    *hash = hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full;
+    return OVC_OK;
+}
+}  // namespace
+
+extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                     int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                                     float* logp_out, int use_graph, ovc_stream stream) {
+    (void)boxes;       // the plain encoder reads no boxes
+    return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
+                             nullptr, nullptr, 0, 0, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// SCST under dropout: ovc_beam_search_dropout / ovc_sequence_backward_dropout
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ovc_train_beams_dropout_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    if (!seq_ok(m, B, N, S, T) || !dropout_train_ok(m, B * S, N, T)) return 0;
+    return carve_train(m, nullptr, B, N, T, true, S, true).bytes;
+}
+
+extern "C" int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                             int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                             size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream, int k,
+                                             const int32_t* slots, const ovc_dropout* dropout) {
+    (void)boxes;
+    if (!dropout || !dropout->seed || !slots || !m || k < 1 || k > OVC_MAX_BEAM || S > k || !seq_ok(m, B, N, S, T) ||
+        !dropout_train_ok(m, B * S, N, T) || T != m->max_len || (long)B * k * T > (1L << 30)) return OVC_EINVAL;
+    DropPlan plan{};
+    uint64_t hash = 0;
+    bool any = false;
+    TRY(make_drop_plan(dropout, &plan, &hash, &any));
+    if (!any)
+        return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
+                                 nullptr, nullptr, 0, 0, nullptr);
+    return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
+                             &plan, dropout->seed, hash ^ ((uint64_t)k << 56), k, slots);
+}
+
+extern "C" size_t ovc_beam_search_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k) {
+    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM) return 0;
+    if (!dropout_train_ok(m, B, N, m->max_len)) return 0;
+    return carve(m, nullptr, B, N, k, 0, true).bytes;
+}
+
+extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                       void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
+                                       const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out,
+                                       int* steps_run_out) {
+    if (!dropout || !dropout->seed || !slots_out || !m || mode < 0 || mode > 2) return OVC_EINVAL;
+    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || !dropout_train_ok(m, B, N, m->max_len) ||
+        (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
+    DropPlan plan{};
+    uint64_t hash = 0;
+    bool any = false;
+    TRY(make_drop_plan(dropout, &plan, &hash, &any));
+    // with every p == 0 the plan stays bound (the slot table is still written) but no site is on: today's launches, today's bits
+    SearchDrop sd{&plan, dropout->seed, any ? hash : 0x5D0Full, slots_out};
+    if (mode == 0)
+        return beam_search_graph(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, stream, &sd);
+    if (mode == 1)
+        return beam_search_early(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_run_out, stream,
+                                 &sd);
+    return beam_search_gated(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_out, stream, &sd);
 }

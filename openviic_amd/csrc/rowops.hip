@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dropout.h"
 
 namespace {
 
@@ -40,6 +41,49 @@ __global__ __launch_bounds__(256) void layer_norm_rows_gated(OVC_LN_PARAMS, cons
     if (ovc_gate_closed(gate)) return;
     constexpr int kPostTenths = 0;
 #include "bodies/layer_norm_rows.inc"
+}
+
+// The dropout instances (ovc_beam_search_dropout): the AddNorm of a decode-step projection whose output has a dropout site.  The
+// row's projection v = sum of the K slices + bias is masked and scaled (csrc/dropout.h, one Philox block per float4) before the
+// residual is added; everything else is the body above.  Separate kernels, so every other instance keeps its arguments and code.
+template <int kVecs, int kParts, bool kBias>
+__global__ __launch_bounds__(256) void layer_norm_rows_dropout(OVC_LN_PARAMS, DropoutSite drop, DecodeRowKey key,
+                                                               const int32_t* __restrict__ gate) {
+    if (gate && ovc_gate_closed(gate)) return;
+    constexpr bool kRes = true;
+    constexpr int kPostTenths = 0;
+    const uint64_t drop_seed = (uint64_t)*drop.seed;
+#define OVC_LN_MASK(vec, c)                                                                                                     \
+    do {                                                                                                                        \
+        const uint64_t g_ = ((ovc_decode_mask_row(key, row) * (uint64_t)drop.cols) >> 2) + (uint64_t)(c);                       \
+        const uint32_t keep_ = ovc_dropout_keep4(drop_seed, drop.site, g_, drop.thr);                                           \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) vec[j_] = (keep_ >> j_) & 1u ? vec[j_] * drop.scale : 0.f;                               \
+    } while (0)
+#include "bodies/layer_norm_rows.inc"
+#undef OVC_LN_MASK
+}
+
+// x[r, :] = (keep ? x[r, :] * s : 0) + residual[r, :], one wave per row, one Philox block per float4 (ovc_dropout_rows)
+__global__ __launch_bounds__(256) void dropout_rows_kernel(float* __restrict__ x, const float* __restrict__ residual, int rows, int cols,
+                                                           DropoutSite drop, DecodeRowKey key, const int32_t* __restrict__ rowmap,
+                                                           const int32_t* __restrict__ gate) {
+    if (gate && ovc_gate_closed(gate)) return;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const uint64_t seed = (uint64_t)*drop.seed;
+    const uint64_t mrow = rowmap ? (uint64_t)(uint32_t)rowmap[row] : ovc_decode_mask_row(key, row);
+    const uint64_t g0 = (mrow * (uint64_t)drop.cols) >> 2;
+    f32x4* xr = reinterpret_cast<f32x4*>(x + (size_t)row * cols);
+    const f32x4* rr = residual ? reinterpret_cast<const f32x4*>(residual + (size_t)row * cols) : nullptr;
+    for (int c = lane; c < (cols >> 2); c += 64) {
+        f32x4 v = xr[c];
+        const uint32_t keep = ovc_dropout_keep4(seed, drop.site, g0 + (uint64_t)c, drop.thr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (keep >> j) & 1u ? v[j] * drop.scale : 0.f;
+        if (rr) v += rr[c];
+        xr[c] = v;
+    }
 }
 #undef OVC_LN_PARAMS
 #undef OVC_LN_ARGS
@@ -288,6 +332,39 @@ int ovc_layer_norm_parts(const float* parts, int nparts, long part_stride, const
     if (nparts == 2) return launch_layer_norm<2, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
     if (nparts == 4) return launch_layer_norm<4, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
     return OVC_EINVAL;
+}
+
+int ovc_layer_norm_parts_dropout(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
+                                 const float* gamma, const float* beta, const uint8_t* zero_rows, float eps, float* y, int rows, int d,
+                                 const DropoutSite& drop, const DecodeRowKey& key, hipStream_t stream, const int32_t* gate) {
+    if (!parts || !residual || !gamma || !beta || !y || rows <= 0 || d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
+    if (!drop.seed || drop.cols != d || key.width < 1 || key.k < key.width || key.T < 1 || key.t < 0 || key.t >= key.T) return OVC_EINVAL;
+    if ((nparts == 1) != (bias == nullptr)) return OVC_EINVAL;
+    if ((part_stride & 3) || !ovc_aligned16(parts) || !ovc_aligned16(y) || (bias && !ovc_aligned16(bias)) || !ovc_aligned16(residual) ||
+        !ovc_aligned16(gamma) || !ovc_aligned16(beta)) return OVC_EINVAL;
+    const int vecs = ((d >> 2) + 63) / 64;
+    const dim3 grid((rows + 3) / 4), block(256);
+#define OVC_LN(V, P, Bs) hipLaunchKernelGGL((layer_norm_rows_dropout<V, P, Bs>), grid, block, 0, stream, parts, part_stride, bias, residual, \
+                                            gamma, beta, (const float*)nullptr, 0, zero_rows, eps, y, rows, d, drop, key, gate)
+#define OVC_LN_V(P, Bs) do { if (vecs <= 1) OVC_LN(1, P, Bs); else if (vecs <= 2) OVC_LN(2, P, Bs); else if (vecs <= 4) OVC_LN(4, P, Bs); else OVC_LN(8, P, Bs); } while (0)
+    if (nparts == 1) OVC_LN_V(1, false);
+    else if (nparts == 2) OVC_LN_V(2, true);
+    else if (nparts == 4) OVC_LN_V(4, true);
+    else return OVC_EINVAL;
+#undef OVC_LN_V
+#undef OVC_LN
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_dropout_rows(float* x, const float* residual, int rows, int cols, const DropoutSite& drop, const DecodeRowKey& key,
+                     const int32_t* rowmap, hipStream_t stream, const int32_t* gate) {
+    if (!x || rows <= 0 || cols <= 0 || (cols & 3) || !drop.seed || drop.cols != cols || !ovc_aligned16(x) ||
+        (residual && !ovc_aligned16(residual))) return OVC_EINVAL;
+    if (!rowmap && (key.width < 1 || key.k < key.width || key.T < 1 || key.t < 0 || key.t >= key.T)) return OVC_EINVAL;
+    hipLaunchKernelGGL(dropout_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, residual, rows, cols, drop, key, rowmap, gate);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
 }
 
 extern "C" int ovc_zero_row_mask(const float* x, int rows, int d, uint8_t* mask, ovc_stream stream) {

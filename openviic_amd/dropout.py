@@ -110,6 +110,34 @@ def keep_mask(seed, site, rows, cols, p, chunk=1 << 22):
     return out.reshape(int(rows), int(cols))
 
 
+def mask_row(b, slot, t, k, T):
+    """The mask row of a search row: image ``b``, beam slot ``slot`` at decode step ``t``, beam size ``k``, ``T = max_len``
+    (``include/ovc.h``, ``ovc_beam_search_dropout``).  ``k = 1`` gives ``xe_loss``'s ``b * T + t``.  Arrays broadcast."""
+    return (np.asarray(b, dtype=np.int64) * int(k) + np.asarray(slot, dtype=np.int64)) * int(T) + np.asarray(t, dtype=np.int64)
+
+
+def mask_rows_of_slots(slots, k):
+    """``maskrow[b, s, t] = mask_row(b, slots[b, s, t], t, k, T)`` of a search's slot table ``(B, S, T)`` (slots clamped into
+    ``0..k-1`` as the device does: entries behind a beam's first ``<eos>`` are unspecified): the rows the teacher-forced
+    recompute of the final beams is masked with."""
+    slots = np.clip(np.asarray(slots, dtype=np.int64), 0, int(k) - 1)
+    B, S, T = slots.shape
+    return mask_row(np.arange(B)[:, None, None], slots, np.arange(T)[None, None, :], k, T)
+
+
+def keep_rows(seed, site, mask_rows, cols, p):
+    """The keep bits of an arbitrary list of mask rows (``keep_mask`` does rows ``0..rows-1``): a bool array
+    ``(len(mask_rows), cols)``, ``ovc_dropout_mask_rows`` bit for bit."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    thr = np.uint32(threshold(p))
+    rows = np.asarray(mask_rows, dtype=np.uint64).reshape(-1)
+    idx = (rows[:, None] * np.uint64(cols) + np.arange(int(cols), dtype=np.uint64)[None, :]).reshape(-1)
+    g = idx >> np.uint64(2)
+    words = philox4x32_10(g & _LO, g >> np.uint64(32), np.full_like(g, site), np.zeros_like(g), seed, seed >> 32)
+    r = np.choose((idx & np.uint64(3)).astype(np.int64), words)
+    return (r >= thr).reshape(len(rows), int(cols))
+
+
 def draw_seed(device, generator=None):
     """A fresh 63-bit seed as a one-element int64 tensor on ``device``, drawn on the stream from ``generator`` (default: the
     device's default generator) -- no host synchronisation, so ``torch.manual_seed`` / ``torch.cuda.set_rng_state`` replay it."""

@@ -522,13 +522,81 @@ class CaptionEngine:
             raise native.OvcError("the geometric encoder needs region boxes")
         return features, boxes
 
-    def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None):
-        """``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above and ``early_exit_mode``.  ``True``:
+    def _dropout_table(self, dropout):
+        """``(probs, seed)`` -> the ``ovc_dropout`` table, or None when no site has ``p > 0`` (the plain call)."""
+        probs, seed = dropout
+        for site, p in probs.items():
+            if not 0 <= site < _dropout.NUM_SITES or not 0 <= p < 1:
+                raise native.OvcError("dropout: site {} p = {} (sites 0..{}, 0 <= p < 1)".format(site, p, _dropout.NUM_SITES - 1))
+        if not any(p > 0 for p in probs.values()):
+            return None
+        if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+            raise native.OvcError("dropout: the seed must be a one-element int64 device tensor")
+        return _dropout.native_table(probs, seed)
+
+    def _beam_search_dropout(self, features, boxes, batch_size, beam_size, out_size, early, table_drop):
+        """``ovc_beam_search_dropout``: the search with every site of ``table_drop`` applied, in the form ``early`` selects.
+        Returns ``(ids, logp, slots)`` with ``slots`` ``(B, out_size, T)`` int32: the beam slot each returned beam's ancestor held
+        at every step, the key of its masks (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
+        self._check_trainable()
+        if self.desc.enc_kind != native.ENC_PLAIN:
+            raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer only")
+        features, boxes = self._checked_inputs(features, boxes)
+        features, boxes = self._bucketed(features, boxes)
+        B, N = features.shape[:2]
+        if B != batch_size:
+            raise native.OvcError("batch_size={} but features hold {} images".format(batch_size, B))
+        self._refresh_derived()
+        d = self.desc
+        T = d.max_len
+        if self.autotune:
+            self.tune(B, N, beam_size)
+        need = self.lib.ovc_beam_search_dropout_workspace_bytes(ctypes.byref(d), B, N, beam_size)
+        if need == 0:
+            raise native.OvcError("unsupported configuration for a search with dropout (B={}, N={}, beam={}; see "
+                                  "ovc_beam_search_dropout_workspace_bytes)".format(B, N, beam_size))
+        ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
+        ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
+        logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
+        slots = torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
+        mode = 2 if early == "device" else (1 if early else 0)
+        steps = None
+        if mode == 2:
+            key = torch.cuda.current_stream().cuda_stream
+            steps = self._steps_device.get(key)
+            if steps is None:
+                steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.last_steps_device = steps
+        if not self.use_graph:           # OVC_GRAPH=0: every call is the first of its shape (plain launches)
+            self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+        self.last_steps_run = T
+        issued = ctypes.c_int(T)
+        check(self.lib.ovc_beam_search_dropout(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(),
+                                               B, N, beam_size, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
+                                               native.stream_handle(), ctypes.byref(table_drop), slots.data_ptr(), mode,
+                                               None if steps is None else steps.data_ptr(), ctypes.byref(issued)),
+              "ovc_beam_search_dropout")
+        if mode == 1:
+            self.last_steps_run = issued.value
+        return ids, logp, slots
+
+    def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None):
+        """``dropout=(probs, seed)`` (as ``forward_backward``): the search runs with every site's mask applied and returns
+        ``(ids, logp, slots)``, unsqueezed ``(B, out_size, T)``; with no ``p > 0`` it is the plain call and ``slots`` is None.
+        ``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above and ``early_exit_mode``.  ``True``:
         ``self.last_steps_run`` then holds the number of decode steps that were issued for the call.  ``"device"``:
         ``self.last_steps_device`` is a one-element int32 device tensor (one per workspace, i.e. per stream) that receives, in
         stream order, the number of decode steps that did work; ``last_steps_run`` stays ``max_len``.  With ``return_probs``
         every mode runs the full search."""
         early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
+        if dropout is not None:
+            if return_probs:
+                raise native.OvcError("beam_search(dropout=...) has no return_probs form")
+            table_drop = self._dropout_table(dropout)
+            if table_drop is not None:
+                return self._beam_search_dropout(features, boxes, batch_size, beam_size, out_size, early, table_drop)
+            ids, logp = self.beam_search(features, boxes, batch_size, beam_size, out_size=out_size, early_exit=early_exit)
+            return ids.reshape(batch_size, out_size, -1), logp.reshape(batch_size, out_size, -1), None
         if early == "device" and self.precision != "f32":
             raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
         features, boxes = self._checked_inputs(features, boxes)
@@ -686,7 +754,8 @@ class CaptionEngine:
             off += size
         return arena, table, grads
 
-    def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False):
+    def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
+                          beam_size=None):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -694,8 +763,19 @@ class CaptionEngine:
         ignored.  The encoder runs once per image.  Returns ``(arena, grads)`` as ``forward_backward`` does -- fresh tensors,
         nothing accumulated -- and with ``want_logp`` also the recomputed ``(B, S, T)`` log-probabilities (0 after ``<eos>``).
         Deterministic: the same bits on every call, stream, graph replay and GEMM tiling.  Dropout is taken as the identity; the
-        caller (``BaseTransformer.beam_search``) checks it."""
+        caller (``BaseTransformer.beam_search``) checks it.
+
+        ``dropout=(probs, seed)`` with ``slots`` (the search's table) and ``beam_size`` (its k): the recompute runs under the
+        masks ``beam_search(dropout=...)`` used (``ovc_sequence_backward_dropout``)."""
         self._check_trainable()
+        table_drop = self._dropout_table(dropout) if dropout is not None else None
+        if table_drop is not None:
+            if (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or
+                    tuple(slots.shape) != tuple(ids.shape)):
+                raise native.OvcError("sequence_backward(dropout=...): slots must be the search's int32 device table, shaped like ids")
+            if beam_size is None or not 1 <= int(beam_size) <= native.OVC_MAX_BEAM or ids.shape[1] > int(beam_size):
+                raise native.OvcError("sequence_backward(dropout=...): beam_size (the search's k, >= S) is required")
+            slots = slots.contiguous()
         d = self.desc
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
@@ -708,7 +788,8 @@ class CaptionEngine:
         T = check_caption_ids(ids.reshape(B * S, -1), "ids", B * S, d.max_len, d.vocab)
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
-        need = self.lib.ovc_train_beams_workspace_bytes(ctypes.byref(d), B, N, S, T)
+        sizer = self.lib.ovc_train_beams_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_beams_workspace_bytes
+        need = sizer(ctypes.byref(d), B, N, S, T)
         if need == 0:
             raise native.OvcError("unsupported training configuration (B={}, N={}, S={}, T={}, V={}; see "
                                   "ovc_train_beams_workspace_bytes)".format(B, N, S, T, d.vocab))
@@ -722,11 +803,14 @@ class CaptionEngine:
         ws = self._cached_workspace(self._seq_workspaces, (stream, S), need)
         logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device) if want_logp else None
         graph = self.use_graph if use_graph is None else bool(use_graph)
-        check(self.lib.ovc_sequence_backward(ctypes.byref(d), ctypes.byref(table), features.data_ptr(),
-                                             None if boxes is None else boxes.data_ptr(), B, N, S, ids.data_ptr(),
-                                             grad_logp.data_ptr(), T, ws.data_ptr(), need,
-                                             None if logp is None else logp.data_ptr(), 1 if graph else 0,
-                                             native.stream_handle()), "ovc_sequence_backward")
+        args = (ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N, S,
+                ids.data_ptr(), grad_logp.data_ptr(), T, ws.data_ptr(), need, None if logp is None else logp.data_ptr(),
+                1 if graph else 0, native.stream_handle())
+        if table_drop is None:
+            check(self.lib.ovc_sequence_backward(*args), "ovc_sequence_backward")
+        else:
+            check(self.lib.ovc_sequence_backward_dropout(*args, int(beam_size), slots.data_ptr(), ctypes.byref(table_drop)),
+                  "ovc_sequence_backward_dropout")
         return (arena, grads, logp) if want_logp else (arena, grads)
 
     def scale_gradients(self, arena, scale):

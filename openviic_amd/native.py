@@ -154,6 +154,14 @@ SIGNATURES = {
     "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_dropout_mask_rows": (c_int, [c_void_p, c_int, c_void_p, c_long, c_long, c_float, c_void_p, c_void_p]),
+    "ovc_beam_search_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
+    "ovc_beam_search_dropout": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_void_p, POINTER(Dropout), c_void_p, c_int, c_void_p, POINTER(c_int)]),
+    "ovc_train_beams_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                              c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                              POINTER(Dropout)]),
     "ovc_cider_reward": (c_int, [POINTER(Cider), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
@@ -161,6 +169,10 @@ SIGNATURES = {
     "ovc_profile_overhead_ms": (c_double, []),
     "ovc_profile_kernel_name": (c_char_p, [c_int]),
 }
+
+# appended to ABI 8 without a bump (include/ovc.h): a library built before them still loads under OVC_LIBRARY
+APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_bytes", "ovc_beam_search_dropout",
+                 "ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout")
 
 _lib = None
 
@@ -175,7 +187,13 @@ def load():
                        "(there is no CPU fallback)".format(LIBRARY_PATH))
     lib = ctypes.CDLL(LIBRARY_PATH)
     for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)            # AttributeError if the symbol is not exported
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # an older build of the same ABI loaded for an A/B (OVC_LIBRARY) lacks the entry points appended last; calling one then
+            # raises AttributeError.  Any other missing symbol is an error at load time, as always.
+            if os.environ.get("OVC_LIBRARY") and name in APPENDED_ABI8:
+                continue
+            raise AttributeError("{} does not export {}".format(LIBRARY_PATH, name))
         fn.restype, fn.argtypes = restype, argtypes
     if lib.ovc_abi_version() != ABI_VERSION:
         raise OvcError("libovc.so ABI {} != binding ABI {}; rebuild".format(lib.ovc_abi_version(), ABI_VERSION))

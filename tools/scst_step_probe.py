@@ -5,6 +5,11 @@ regions, dropout 0.  The weights are EOS-biased (``eos_biased_state_dict``) so c
 
     python tools/scst_step_probe.py [--batches 60 256] [--beam 5] [--steps 10] [--warmup 3] [--out results/scst_step_probe.json]
     python tools/scst_step_probe.py --reward device|host [--corpus-images 5000] ...      # the step WITH its CIDEr reward
+    python tools/scst_step_probe.py --dropout ...      # beam_search(dropout=True) at the reference's p = 0.1 against p = 0
+
+``--dropout``: steps with every ``nn.Dropout`` at 0.1 (a new seed per step, ``ovc_beam_search_dropout`` /
+``ovc_sequence_backward_dropout``) and steps of the same build with every p = 0 alternate in one process; search and backward
+from device events, medians and spread of ``--steps`` each, and the ratios.
 
 Time: device events around each phase after ``--warmup`` steps (the second call captures the graphs), one synchronise per step.
 Shared against expanded: ``sequence_backward`` with the encoder once per image (S = k) against the same entry at S = 1 on the
@@ -146,6 +151,37 @@ def reward_probe(args, model, V, T, N, D, k):
     return results
 
 
+def dropout_probe(args, model, N, D, k):
+    """SCST steps under dropout (p = 0.1 at every site) against the same build at p = 0, alternating."""
+    drops = [m for m in model.modules() if isinstance(m, torch.nn.Dropout)]
+    results = []
+    for B in args.batches:
+        items = InstanceList()
+        items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        reward = torch.rand(B, k, generator=torch.Generator().manual_seed(1)).cuda()
+        runs = {0.0: [], 0.1: []}
+        for i in range(args.warmup + args.steps):
+            for p in (0.0, 0.1):
+                for m in drops:
+                    m.p = p
+                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k, dropout=True))
+                loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
+                model.zero_grad(set_to_none=True)
+                ms_b, _ = timed(loss.backward)
+                if i >= args.warmup:
+                    runs[p].append((ms_s, ms_b))
+        r = {"variant": args.variant, "B": B, "k": k, "N": N, "p": 0.1}
+        for p, name in ((0.0, "p0"), (0.1, "dropout")):
+            r["search_ms_" + name] = spread([a for a, _ in runs[p]])
+            r["backward_ms_" + name] = spread([b for _, b in runs[p]])
+            r["step_ms_" + name] = spread([a + b for a, b in runs[p]])
+        for part in ("search", "backward", "step"):
+            r[part + "_dropout_over_p0"] = r[part + "_ms_dropout"]["median"] / r[part + "_ms_p0"]["median"]
+        results.append(r)
+        print(json.dumps(r))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
@@ -157,6 +193,7 @@ def main():
     ap.add_argument("--reward", default="none", choices=["none", "host", "device"],
                     help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
     ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
+    ap.add_argument("--dropout", action="store_true", help="steps under dropout (p = 0.1 everywhere) against p = 0, alternating")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -176,7 +213,9 @@ def main():
     if args.variant == "camo_transformer":
         dims.update(he=1, tail=True)
     results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" else []
-    for B in args.batches if args.reward == "none" else []:
+    if args.dropout:
+        results = dropout_probe(args, model, N, D, k)
+    for B in args.batches if args.reward == "none" and not args.dropout else []:
         feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
         items = InstanceList()
         items.region_features = feats

@@ -484,6 +484,42 @@ typedef struct {
 int ovc_cider_reward(const ovc_cider* c, const int64_t* ids, const int32_t* rows, int B, int S, int T,
                      float* reward_out, ovc_stream stream);
 
+/* The optimizer step: one multi-tensor Adam update (torch/optim/adam.py's single-tensor form without weight decay, AMSGrad or
+ * maximize -- the optimizer of the reference's trainers, base_trainer.py:89-90, vi_trainer.py:204).  Appended to ABI 8.
+ *   table  [n_tensors]  device memory: the four fp32 arrays of every tensor and its element count (<= OVC_ADAM_MAX_COUNT).  Any
+ *                       count and any 4-byte aligned pointers work (views into larger buffers); arrays whose four pointers share
+ *                       their offset within 16 bytes are updated with 16-byte loads and stores.
+ *   chunks [n_chunks]   device memory: the work list, (tensor, first element) of every 4096-element piece of every tensor.
+ *                       ovc_adam_chunk_count / ovc_adam_chunk_fill build it on the HOST from the element counts alone (it
+ *                       survives a change of pointers); both return the number of chunks, or -1 for a null or negative argument,
+ *                       a count above OVC_ADAM_MAX_COUNT, or a capacity below the chunk count.
+ * The scalars of step t (>= 1) are prepared on the host in double and rounded to fp32 once each: w1 = 1 - beta1, beta2,
+ * w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), eps.  Per element, every operation rounded once
+ * in this order (no contraction; sqrt and the divisions correctly rounded):
+ *   g = grad * s           s = *grad_scale, or exactly 1 when grad_scale is null (a device pointer to one float)
+ *   m = m + (g - m) * w1
+ *   v = beta2 * v + (w2 * g) * g
+ *   p = p - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ * ONE launch whatever n_tensors; every element is read and written by exactly one lane with plain vector stores, so the result
+ * is the same bits on every call, stream and grid.  No allocation, no synchronisation, nothing read back.  OVC_EINVAL (nothing
+ * launched): step < 1, lr < 0, eps < 0, a beta outside [0, 1), a null table with work to do. */
+#define OVC_ADAM_MAX_COUNT 0x7fffffffL
+typedef struct {
+    float*       param;
+    const float* grad;
+    float*       exp_avg;
+    float*       exp_avg_sq;
+    int64_t      count;
+} ovc_adam_tensor;
+typedef struct {
+    int32_t tensor;                    /* index into the tensor table        */
+    int32_t first;                     /* first element of the piece         */
+} ovc_adam_chunk;
+long ovc_adam_chunk_count(const int64_t* counts, int n_tensors);
+long ovc_adam_chunk_fill(const int64_t* counts, int n_tensors, ovc_adam_chunk* chunks, long capacity);
+int ovc_adam_step(const ovc_adam_tensor* table, int n_tensors, const ovc_adam_chunk* chunks, long n_chunks, double lr, double beta1,
+                  double beta2, double eps, long step, const float* grad_scale, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

@@ -170,34 +170,66 @@ class BaseTransformer(Module):
         any draw).  The step's seed is drawn on the stream from ``generator`` (default: the device's
         CUDA generator), so ``torch.manual_seed`` reproduces a step.  In ``eval()`` mode, or with every ``p == 0``, this is the
         ``dropout=False`` call: same bits, no random draw."""
-        if dropout:
-            if self.training and isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
-                live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
-                if live:
-                    raise engine.native.OvcError(
-                        "xe_loss(dropout=True): dropout training covers the standard transformer; the cross-level encoder applies "
-                        "encoder.self_attn.dropout twice in its tail and the engine has no site for it -- set DROPOUT: 0 and "
-                        "call xe_loss(items), or call model.eval() (live: {})".format(live[0]))
-            probs = _dropout.model_probs(self) if self.training else {}
-            if probs:
-                eng = self._fused_engine()
-                feats = input_features[self.feature_field]
-                seed = _dropout.draw_seed(eng.device, generator)
-                boxes = input_features["region_boxes"] if self.uses_boxes else None
-                params = eng.gradient_parameters()
-                return _XeLoss.apply(eng, (probs, seed), feats, boxes, input_features["caption_tokens"],
-                                     input_features["shifted_right_caption_tokens"], *params)
-        elif self.training:
-            live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
-            if live:
-                raise engine.native.OvcError(
-                    "xe_loss: the model is in train() mode with dropout > 0 ({}); the engine's backward takes dropout as the "
-                    "identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
+        probs = self._xe_dropout_probs(dropout, "xe_loss")
         eng = self._fused_engine()
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         params = eng.gradient_parameters()
-        return _XeLoss.apply(eng, None, input_features[self.feature_field], boxes, input_features["caption_tokens"],
+        drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
+        return _XeLoss.apply(eng, drop, input_features[self.feature_field], boxes, input_features["caption_tokens"],
                              input_features["shifted_right_caption_tokens"], *params)
+
+    def _xe_dropout_probs(self, dropout, what):
+        """``{site: p}`` of the live dropouts for ``xe_loss`` / ``xe_step`` (empty: the plain call), or the refusals of their
+        dropout rules: before any launch and any draw."""
+        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0] if self.training else []
+        if dropout:
+            if live and isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
+                raise engine.native.OvcError(
+                    "{0}(dropout=True): dropout training covers the standard transformer; the cross-level encoder applies "
+                    "encoder.self_attn.dropout twice in its tail and the engine has no site for it -- set DROPOUT: 0 and "
+                    "call {0}(items), or call model.eval() (live: {1})".format(what, live[0]))
+            return _dropout.model_probs(self) if self.training else {}
+        if live:
+            raise engine.native.OvcError(
+                "{}: the model is in train() mode with dropout > 0 ({}); the engine's backward takes dropout as the "
+                "identity -- set DROPOUT: 0 in the config or call model.eval()".format(what, live[0]))
+        return {}
+
+    def xe_step(self, input_features, optimizer, dropout=False, generator=None):
+        """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
+        ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
+        stands for ::
+
+            optimizer.zero_grad(); loss = model.xe_loss(items, dropout=...); loss.backward(); optimizer.step()
+
+        and leaves the same parameter and optimizer-state bits as those four lines (there ``grad_output`` is exactly 1).
+        ``optimizer`` is an ``openviic_amd.optim.Adam`` that holds exactly the engine's ``gradient_parameters()`` that require a
+        gradient (frozen parameters may be in it; they are not updated); anything else is refused before any launch and any
+        random draw.  ``xe_loss``'s scope and refusals apply: the plain standard and CaMo transformers, 'f32', the dropout rules.
+
+        ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
+        ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
+        all-reduce.  A data-parallel run keeps the four lines above."""
+        from . import optim as _optim
+        if not isinstance(optimizer, _optim.Adam):
+            raise engine.native.OvcError("xe_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
+                type(optimizer).__name__))
+        probs = self._xe_dropout_probs(dropout, "xe_step")
+        eng = self._fused_engine()
+        eng._check_trainable()
+        wanted = [p for p in eng.gradient_parameters() if p.requires_grad]
+        held = {id(p) for group in optimizer.param_groups for p in group["params"] if p.requires_grad}
+        if held != {id(p) for p in wanted}:
+            raise engine.native.OvcError(
+                "xe_step: optimizer must hold exactly the model's trainable parameters ({} of them); it holds {} trainable "
+                "parameters, {} of them the model's".format(len(wanted), len(held), len(held & {id(p) for p in wanted})))
+        boxes = input_features["region_boxes"] if self.uses_boxes else None
+        drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
+        slots = eng.step_arena()
+        loss, _, grads = eng.forward_backward(input_features[self.feature_field], boxes, input_features["caption_tokens"],
+                                              input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots)
+        optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad})
+        return loss
 
     def _search_dropout_probs(self):
         """``{site: p}`` for ``beam_search(dropout=True)``, or the refusals of its scope: before any launch and any draw."""

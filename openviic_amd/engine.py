@@ -238,6 +238,7 @@ class CaptionEngine:
         self._fw_workspaces = {}
         self._train_workspaces = {}   # ovc_forward_backward's own, per stream
         self._seq_workspaces = {}     # ovc_sequence_backward's own, per (stream, sequences per image)
+        self._step_arenas = {}        # xe_step's gradient arena, per stream
         self._steps_device = {}  # early_exit="device": the step count of each search workspace (keyed like _workspaces)
         self.last_steps_device = None
         self._tuned = set()
@@ -451,6 +452,7 @@ class CaptionEngine:
         self._fw_workspaces = {}
         self._train_workspaces = {}
         self._seq_workspaces = {}
+        self._step_arenas = {}
         self._steps_device = {}
 
     def __del__(self):
@@ -685,7 +687,7 @@ class CaptionEngine:
         """The parameters ``forward_backward`` returns gradients for, in the order of its list."""
         return [p for p, _ in _grad_slots(self.model)]
 
-    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None):
+    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -695,7 +697,10 @@ class CaptionEngine:
 
         ``dropout=(probs, seed)`` applies dropout (``ovc_forward_backward_dropout``): ``probs`` maps site ids
         (``openviic_amd.dropout``) to ``p``, ``seed`` is a one-element int64 device tensor.  The masks are a function of
-        ``(seed, site, row, col)`` only, so the result is as deterministic as without; with no ``p > 0`` this is the plain call."""
+        ``(seed, site, row, col)`` only, so the result is as deterministic as without; with no ``p > 0`` this is the plain call.
+
+        ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer (``BaseTransformer.xe_step``: nothing
+        is handed out, and the captured graph, whose key holds the gradient table, is replayed whatever the allocator does)."""
         self._check_trainable()
         d = self.desc
         features, boxes = self._checked_inputs(features, boxes)
@@ -725,7 +730,7 @@ class CaptionEngine:
         self._check_pointers()
         self._refresh_derived()
         d = self.desc
-        arena, table, grads = self._gradient_arena()
+        arena, table, grads = self._gradient_arena() if arena is None else arena
         stream = torch.cuda.current_stream().cuda_stream
         ws = self._cached_workspace(self._train_workspaces, stream, need)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
@@ -753,6 +758,15 @@ class CaptionEngine:
             grads.append(view)
             off += size
         return arena, table, grads
+
+    def step_arena(self):
+        """The gradient arena ``xe_step`` reuses from call to call, one per stream: ``(arena, table, views)`` as
+        ``_gradient_arena`` makes them.  Its contents are one step's gradients, consumed by the optimizer launch that follows
+        on the same stream."""
+        key = torch.cuda.current_stream().cuda_stream
+        if key not in self._step_arenas:
+            self._step_arenas[key] = self._gradient_arena()
+        return self._step_arenas[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
                           beam_size=None):

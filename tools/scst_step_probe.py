@@ -7,6 +7,13 @@ regions, dropout 0.  The weights are EOS-biased (``eos_biased_state_dict``) so c
     python tools/scst_step_probe.py --reward device|host [--corpus-images 5000] ...      # the step WITH its CIDEr reward
     python tools/scst_step_probe.py --dropout ...      # beam_search(dropout=True) at the reference's p = 0.1 against p = 0
 
+    python tools/scst_step_probe.py --optimizer torch engine ...      # the whole step with its optimizer step
+
+``--optimizer`` (default ``none``): SCST steps that end in ``optimizer.step()`` -- ``torch``: ``torch.optim.Adam``, ``engine``:
+``openviic_amd.optim.Adam`` (``ovc_adam_step``), lr = 5e-6 as the reference's RL phase -- each form on its own copy of the model,
+alternating in one process; the whole step and the optimizer step from device events, medians and spread of ``--steps`` each, and
+the 28 bytes per element the optimizer step must move over its time against the 6.29 TB/s of a float4 copy on this chip.
+
 ``--dropout``: steps with every ``nn.Dropout`` at 0.1 (a new seed per step, ``ovc_beam_search_dropout`` /
 ``ovc_sequence_backward_dropout``) and steps of the same build with every p = 0 alternate in one process; search and backward
 from device events, medians and spread of ``--steps`` each, and the ratios.
@@ -182,6 +189,45 @@ def dropout_probe(args, model, N, D, k):
     return results
 
 
+def optimizer_probe(args, build, N, D, k):
+    """Whole SCST steps (search, loss, backward, optimizer step) with each form of ``args.optimizer``, alternating."""
+    from openviic_amd.optim import Adam
+    forms = {}
+    for kind in args.optimizer:
+        model = build()
+        params = [p for p in model.parameters() if p.requires_grad]
+        forms[kind] = (model, params, (torch.optim.Adam if kind == "torch" else Adam)(params, lr=5e-6))
+    results = []
+    for B in args.batches:
+        items = InstanceList()
+        items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        reward = torch.rand(B, k, generator=torch.Generator().manual_seed(1)).cuda()
+        runs = {kind: [] for kind in forms}
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        for i in range(args.warmup + args.steps):
+            for kind, (model, params, opt) in forms.items():
+                ev[0].record()
+                _, log_probs = model.beam_search(items, batch_size=B, beam_size=k, out_size=k)
+                loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
+                opt.zero_grad()
+                loss.backward()
+                ev[1].record()
+                opt.step()
+                ev[2].record()
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    runs[kind].append((ev[0].elapsed_time(ev[2]), ev[1].elapsed_time(ev[2])))
+        for kind, (model, params, opt) in forms.items():
+            elements = sum(p.numel() for p in params)
+            alone = spread([b for _, b in runs[kind]])
+            rate = 28.0 * elements / (alone["median"] * 1e-3)
+            results.append({"variant": args.variant, "B": B, "k": k, "N": N, "optimizer": kind, "step_ms": spread([a for a, _ in runs[kind]]),
+                            "optimizer_step_ms": alone, "elements": elements, "step_bytes": 28 * elements,
+                            "step_tb_per_s": rate / 1e12, "share_of_copy_rate": rate / 6.29e12})
+            print(json.dumps(results[-1]))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
@@ -194,20 +240,28 @@ def main():
                     help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
     ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
     ap.add_argument("--dropout", action="store_true", help="steps under dropout (p = 0.1 everywhere) against p = 0, alternating")
+    ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine"],
+                    help="none: search and backward only; torch / engine: the whole step with optimizer.step() (they alternate)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if "none" in args.optimizer and len(args.optimizer) > 1:
+        ap.error("--optimizer none stands alone")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D, k = 10201, 20, 50, 2048, args.beam
     vocab = SyntheticVocab(V, T)
     cfg = model_config(args.variant, d_feature=D, device="cuda:0")
-    model = build_model(cfg, vocab)
-    template = model.state_dict()
-    sd = eos_biased_state_dict({**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}, template)
-    model.load_state_dict(sd, strict=False)
-    model.train()
-    for m in model.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
+
+    def build():
+        model = build_model(cfg, vocab)
+        template = model.state_dict()
+        sd = eos_biased_state_dict({**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}, template)
+        model.load_state_dict(sd, strict=False)
+        model.train()
+        for m in model.modules():
+            if isinstance(m, torch.nn.Dropout):
+                m.p = 0.0
+        return model
+    model = build()
     eng = model._fused_engine()
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     if args.variant == "camo_transformer":
@@ -215,7 +269,9 @@ def main():
     results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" else []
     if args.dropout:
         results = dropout_probe(args, model, N, D, k)
-    for B in args.batches if args.reward == "none" and not args.dropout else []:
+    if args.optimizer != ["none"]:
+        results = optimizer_probe(args, build, N, D, k)
+    for B in args.batches if args.reward == "none" and not args.dropout and args.optimizer == ["none"] else []:
         feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
         items = InstanceList()
         items.region_features = feats

@@ -2,9 +2,18 @@
 configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, V = 10 201), T = 20, N = 50 ragged regions.
 
     python tools/train_step_probe.py [--batches 60 256] [--steps 20] [--warmup 5] [--dropout] [--out results/train_step_probe.json]
+    python tools/train_step_probe.py --optimizer torch engine xe_step [--rounds 2] ...     # the whole iteration, optimizer included
 
 --dropout: the model in train() mode with the reference's DROPOUT 0.1 at every site, ``model.xe_loss(items, dropout=True)``
 (ovc_forward_backward_dropout; a fresh seed per step).
+
+--optimizer (default ``none``: the lines above, today's numbers): the whole training iteration with its optimizer step.
+``torch``: ``zero_grad(); xe_loss(); backward(); step()`` with ``torch.optim.Adam`` and its defaults; ``engine``: the same four lines
+with ``openviic_amd.optim.Adam`` (``ovc_adam_step``); ``xe_step``: ``model.xe_step(items, optimizer)``.  Several values alternate in
+one process, ``--rounds`` rounds of ``--steps`` iterations each after ``--warmup`` iterations of every form, each form on its own
+copy of the model.  Per form: ms per iteration (device events) per round, and the optimizer step on its own -- ``--steps``
+back-to-back ``step()`` calls on the gradients of the last iteration -- with the bytes it must move (28 per element: p, g, m, v
+read, p, m, v written) over its time as achieved bytes/s, against the 6.29 TB/s of a float4 copy on this chip.
 
 Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
 end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
@@ -25,6 +34,7 @@ from openviic_amd.instance import InstanceList                                  
 from openviic_amd.utils.synthetic import SyntheticVocab, synthetic_features, synthetic_state_dict   # noqa: E402
 
 PEAK_F32_MATRIX = 157.3e12
+COPY_RATE = 6.29e12           # bytes/s of a float4 copy on one MI355X (measured; HBM3E nominal 8.0e12)
 
 
 def step_flops(cfg_dims, B, N, T):
@@ -43,6 +53,56 @@ def step_flops(cfg_dims, B, N, T):
     return 3 * f
 
 
+def events_ms(fn, repeats):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(repeats):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / repeats
+
+
+def optimizer_probe(args, build, items, B):
+    """The iteration with its optimizer step, every form of ``args.optimizer`` on its own model, alternating."""
+    from openviic_amd.optim import Adam
+    forms = {}
+    for kind in args.optimizer:
+        model = build()
+        params = [p for p in model.parameters() if p.requires_grad]
+        opt = (torch.optim.Adam if kind == "torch" else Adam)(params, lr=1e-4, betas=(0.9, 0.98))
+        if kind == "xe_step":
+            iteration = lambda model=model, opt=opt: model.xe_step(items, opt, dropout=args.dropout)
+        else:
+            def iteration(model=model, opt=opt):
+                opt.zero_grad()
+                loss = model.xe_loss(items, dropout=args.dropout)
+                loss.backward()
+                opt.step()
+                return loss
+        forms[kind] = (model, params, opt, iteration)
+        for _ in range(args.warmup):
+            iteration()
+    torch.cuda.synchronize()
+    rows = []
+    for rnd in range(args.rounds):
+        for kind, (model, params, opt, iteration) in forms.items():
+            ms = events_ms(iteration, args.steps)
+            if kind == "xe_step":               # the same launch as "engine", fed from the arena of the last iteration
+                grads = dict(zip(model._fused_engine().gradient_parameters(), model._fused_engine().step_arena()[2]))
+                grads = {p: g for p, g in grads.items() if p.requires_grad}
+                alone = events_ms(lambda: opt.apply_gradients(grads), args.steps)
+            else:
+                alone = events_ms(opt.step, args.steps)
+            elements = sum(p.numel() for p in params)
+            rate = 28.0 * elements / (alone * 1e-3)
+            rows.append(dict(variant=args.variant, B=B, dropout=args.dropout, optimizer=kind, round=rnd, ms_per_iteration=round(ms, 3),
+                             optimizer_step_ms=round(alone, 4), tensors=len(params), elements=elements, step_bytes=28 * elements,
+                             step_tb_per_s=round(rate / 1e12, 3), share_of_copy_rate=round(rate / COPY_RATE, 3)))
+            print(json.dumps(rows[-1]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
@@ -51,16 +111,22 @@ def main():
     ap.add_argument("--dropout", action="store_true")
     ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
+    ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
+                    help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
+    ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if "none" in args.optimizer and len(args.optimizer) > 1:
+        ap.error("--optimizer none stands alone")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
     cfg = model_config(args.variant, d_feature=D, device="cuda:0")
-    model = build_model(cfg, vocab).eval()
-    model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
-    if args.dropout:
-        model.train()
+    def build():
+        model = build_model(cfg, vocab).eval()
+        model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
+        return model.train() if args.dropout else model
+    model = build() if args.optimizer == ["none"] else None
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     if args.variant == "camo_transformer":
         dims.update(he=1, tail=True)
@@ -73,6 +139,9 @@ def main():
         items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
         items.caption_tokens = tokens.cuda()
         items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
+        if args.optimizer != ["none"]:
+            results += optimizer_probe(args, build, items, B)
+            continue
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)
             model.xe_loss(items, dropout=args.dropout).backward()

@@ -333,10 +333,12 @@ int ovc_forward(const ovc_model* m, const float* features, const float* boxes, i
  * grads: a second ovc_model-shaped table whose pointer fields name the gradient buffers, each shaped like the parameter of the same
  * field in m; only those fields are read.  Every buffer is WRITTEN, not accumulated: proj, enc_ln, every layer's q / k / v / o
  * Linears, their norms and FFNs (weight and, where m has one, bias), word_emb (its pad_idx row gets 0) and fc; with
- * OVC_ENC_CROSS_LEVEL also cl_att (q / k / v / o, ln), cl_mlp1 and cl_mlp2.  pos_emb (frozen) gets nothing, the remaining fields
- * are ignored.
+ * OVC_ENC_CROSS_LEVEL also cl_att (q / k / v / o, ln), cl_mlp1 and cl_mlp2; with encoder memory slots also enc[l].att.m_k / m_v
+ * ([memory][enc_heads * enc_d_k], summed over the whole batch: per image over its queries in ascending order, then the images in
+ * 64-image chunks, ascending).  pos_emb (frozen) gets nothing, the remaining fields are ignored.
  * Supported: the plain or cross-level (CaMo) encoder with the plain decoder (OVC_ENC_PLAIN / OVC_ENC_CROSS_LEVEL, OVC_DEC_PLAIN)
- * with plain attention (no AoA gates, no memory slots),
+ * with plain attention (no AoA gates; memory slots only in the layers of the PLAIN encoder -- memory > 0 with m_k and m_v set in
+ * every encoder layer, the reference's augmented_memory_transformer.yaml -- never in a decoder attention or in cl_att),
  * precision 0, and vocabularies of at most 16384 words (512 blocks of 32: the fused vocabulary tail of ovc_forward) -- tighter
  * than ovc_forward, which also takes larger vocabularies -- with (B*T + 256) * V and (V + 256) * B*T below 2^29.  Other sizes
  * as ovc_forward.  Anything else: ovc_train_workspace_bytes returns 0 and ovc_forward_backward OVC_EINVAL, nothing launched.
@@ -379,7 +381,8 @@ typedef struct {
  * seed, and the p values are part of the graph's key.  Any p outside [0, 1) or a null dropout / seed: OVC_EINVAL, nothing
  * launched.  With every p == 0 this is ovc_forward_backward (same launches, same bits, ovc_train_workspace_bytes suffices).
  * ovc_train_dropout_workspace_bytes: bytes of workspace for calls with a site active (0 when unsupported, and for the
- * cross-level encoder, whose tail applies one nn.Dropout twice and has no site). */
+ * cross-level encoder, whose tail applies one nn.Dropout twice and has no site).  The plain encoder with memory slots is
+ * covered: its dropout modules are the standard transformer's. */
 size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T);
 int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                  const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
@@ -408,7 +411,7 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
 
 /* SCST under dropout (the reference's train_scst searches in train() mode, vi_trainer.py:121-158): the beam search with the
  * dropout sites above applied, and the backward of its log-probabilities under the SAME masks.  The plain standard transformer,
- * precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.
+ * with or without encoder memory slots, precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.
  * Mask rows.  Encoder-side sites key on row b * N + n as above (the encoder runs once per image in both calls).  Decoder-side
  * sites of the search key on the MASK ROW of the row that is being decoded,
  *     mrow(b, slot, t) = (b * k + slot) * T + t,      T = max_len, slot = the beam slot that holds the row at decode step t
@@ -596,6 +599,14 @@ int ovc_debug_force_gemm_tiling(int tiling);
 int ovc_debug_clear_tuning(void);                 /* forget every remembered tiling (tests) */
 int ovc_debug_linear_tiling(const float* x, int K, const float* W, const float* bias, float* y, int M, int N,
                             int tiling, int ksplit, int iters, ovc_stream stream);
+/* Test hook: the attention backward with m memory slots (the encoder self-attention of ovc_forward_backward, nq = nk = n) on
+ * caller buffers.  q / k / v / dout [B*n][h*dk], mask [B][n] (may be NULL), m_k / m_v [m][h*dk]; scales as the forward's
+ * (sqrt(dk), sqrt(dk), sqrt(m)).  Out: P / dS [B][h][n][n + m], dq / dk_out / dv_out [B*n][h*dk], part_k / part_v [B][m][h*dk]
+ * (each image's share), colpart [ceil(B / 64)][m*h*dk] (scratch), d_mk / d_mv [m][h*dk]. */
+int ovc_debug_attention_mem_backward(const float* q, const float* k, const float* v, const float* dout, const uint8_t* mask,
+                                     const float* m_k, const float* m_v, int B, int n, int h, int dk, int m, float* P, float* dS,
+                                     float* dq, float* dk_out, float* dv_out, float* part_k, float* part_v, float* colpart,
+                                     float* d_mk, float* d_mv, ovc_stream stream);
 
 /* Test hook: ONE selection step of the engine's fused path on caller-supplied decoder outputs x [B*width, d] -- the
  * vocabulary product fc [V, d] with its log-softmax epilogue (transposed != 0: logits^T = fc . x^T as the fp32 engine runs

@@ -21,7 +21,8 @@ from .builders.model_builder import META_ARCHITECTURE
 from .builders.vision_embedding_builder import build_vision_embedding
 from .modules.beam_search import BeamSearch
 from .modules.containers import Module
-from .modules.encoders import CrossAttentionMultiLevelEncoder
+from .modules.decoders import Decoder
+from .modules.encoders import CrossAttentionMultiLevelEncoder, Encoder
 
 
 class _XeLoss(torch.autograd.Function):
@@ -160,18 +161,20 @@ class BaseTransformer(Module):
     def xe_loss(self, input_features, dropout=False, generator=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
-        every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer and the
-        CaMo transformer, in 'f32' only.
+        every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer, the
+        augmented-memory transformer (plain encoder with memory slots, plain decoder) and the CaMo transformer, in 'f32' only.
 
         ``dropout=False``: dropout counts as the identity, so a model in ``train()`` mode with any dropout probability above 0
         is refused (set ``DROPOUT: 0`` or call ``model.eval()``).  ``dropout=True``: in ``train()`` mode every ``nn.Dropout``
         applies its own ``p`` as the reference's training does (``openviic_amd.dropout``; a ``p >= 1`` or a live dropout the
-        engine does not place is refused; the standard transformer only: a CaMo model with a live dropout is refused before
-        any draw).  The step's seed is drawn on the stream from ``generator`` (default: the device's
+        engine does not place is refused; the standard and augmented-memory transformers only: a CaMo model with a live
+        dropout is refused before any draw).  The step's seed is drawn on the stream from ``generator`` (default: the device's
         CUDA generator), so ``torch.manual_seed`` reproduces a step.  In ``eval()`` mode, or with every ``p == 0``, this is the
         ``dropout=False`` call: same bits, no random draw."""
         probs = self._xe_dropout_probs(dropout, "xe_loss")
         eng = self._fused_engine()
+        if probs:
+            eng._check_trainable()                  # a model outside the scope is refused before the seed is drawn
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         params = eng.gradient_parameters()
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
@@ -205,7 +208,8 @@ class BaseTransformer(Module):
         and leaves the same parameter and optimizer-state bits as those four lines (there ``grad_output`` is exactly 1).
         ``optimizer`` is an ``openviic_amd.optim.Adam`` that holds exactly the engine's ``gradient_parameters()`` that require a
         gradient (frozen parameters may be in it; they are not updated); anything else is refused before any launch and any
-        random draw.  ``xe_loss``'s scope and refusals apply: the plain standard and CaMo transformers, 'f32', the dropout rules.
+        random draw.  ``xe_loss``'s scope and refusals apply: the plain standard, augmented-memory and CaMo transformers, 'f32', the dropout
+        rules.
 
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
@@ -243,7 +247,9 @@ class BaseTransformer(Module):
                 "beam_search(dropout=True): dropout covers the standard transformer; the cross-level encoder applies "
                 "encoder.self_attn.dropout twice in its tail and the engine has no site for it -- set DROPOUT: 0 or call "
                 "model.eval() (live: {})".format(live[0]))
-        if type(self) not in (StandardTransformerUsingRegion, StandardTransformerUsingGrid):
+        # by structure, not by class: the plain Encoder and Decoder (MeshedMemoryTransformer is also the class of the
+        # augmented-memory transformer, whose encoder and decoder are plain); _check_trainable below refuses the rest
+        if type(self.encoder) is not Encoder or type(self.decoder) is not Decoder:
             raise engine.native.OvcError(
                 "beam_search(dropout=True): dropout covers the plain standard transformer only, not {} (live: {}) -- set "
                 "DROPOUT: 0 or call model.eval()".format(type(self).__name__, live[0]))
@@ -264,10 +270,10 @@ class BaseTransformer(Module):
         still native -- and exists for parity checks of ``step`` / ``statefulness``.
 
         Fused, in ``train()`` mode with gradients enabled: the returned ``log_probs`` carry a gradient (``_BeamLogProbs``), so
-        the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard transformer or the CaMo
-        transformer in 'f32' with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
+        the reference's ``train_scst`` loss backpropagates (``ovc_sequence_backward``; the plain standard, the augmented-memory or
+        the CaMo transformer in 'f32' with dropout 0, anything else raises from ``backward()``).  In ``eval()`` mode or under ``no_grad``: plain tensors.
 
-        ``dropout=True`` (fused only; the plain standard transformer in 'f32'): in ``train()`` mode every ``nn.Dropout`` applies
+        ``dropout=True`` (fused only; the plain standard transformer, with or without encoder memory slots, in 'f32'): in ``train()`` mode every ``nn.Dropout`` applies
         its own ``p`` DURING the search, as the reference's ``train_scst`` does (``vi_trainer.py:121-158`` searches after
         ``model.train()``), with or without grad; the backward of ``log_probs`` recomputes the sequences under the same masks.
         One seed per call, drawn on the stream from ``generator`` as ``xe_loss`` draws it.  In ``eval()`` mode or with every

@@ -85,6 +85,8 @@ _VARIANTS = {
     "standard_transformer_using_grid": ("StandardTransformerUsingGrid", "Encoder", "ScaledDotProductAttention", "Decoder", False),
     "attention_on_attention": ("StandardTransformerUsingRegion", "Encoder", "ScaledDotProductAttention", "Decoder", True),
     "meshed_memory_transformer": ("MeshedMemoryTransformer", "MultilevelEncoder", "AugmentedMemoryScaledDotProductAttention", "MeshedDecoder", False),
+    # configs/augmented_memory_transformer.yaml: memory slots in a plain Encoder, plain Decoder
+    "augmented_memory_transformer": ("MeshedMemoryTransformer", "Encoder", "AugmentedMemoryScaledDotProductAttention", "Decoder", False),
     "object_relation_transformer": ("ObjectRelationTransformer", "GeometricEncoder", "AugmentedGeometryScaledDotProductAttention", "Decoder", False),
     "camo_transformer": ("CamoTransformer", "CrossAttentionMultiLevelEncoder", "ScaledDotProductAttention", "Decoder", False),
 }
@@ -101,7 +103,7 @@ def model_config(variant: str, *, d_feature: int = 2048, d_model: int = 512, hea
     """Build the ``MODEL`` node of one of the in-scope reference configurations.
 
     Key names follow ``configs/standard_transformer.yaml:39-97``,
-    ``configs/meshed_memory_transformer.yaml:38-97``,
+    ``configs/meshed_memory_transformer.yaml:38-97``, ``configs/augmented_memory_transformer.yaml``,
     ``configs/object_relation_transformer.yaml:39-95`` and ``configs/camo_transformer.yaml:39-97`` of the reference.
     ``heads`` is the decoder's head count; ``enc_heads`` the encoder's (default: the variant's own -- 1 for
     ``camo_transformer``, as its yaml -- else ``heads``).

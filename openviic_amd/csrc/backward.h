@@ -48,6 +48,25 @@ struct AttnBwdArgs {
 };
 int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s);
 
+// ovc_bw_attention for an attention with m memory slots (the encoder's AugmentedMemoryScaledDotProductAttention): the forward's m
+// extra keys mem_scale_k * m_k[slot] and values mem_scale_v * m_v[slot] (each one fp32 product, as attention.hip forms them) follow
+// the nk real keys and are never masked.  P / dS are [B][h][nq][nk + m]; dq sums the real keys in ascending order, then the slots.
+// The keys pass is ovc_bw_attention's over the wider scratch rows.  Memory pass: one wave per (image, head, slot) sums the image's
+// queries in ascending order into part_k / part_v [B][m][h dk],
+//   part_k = ((sum_i dS[b, head, i, nk + slot] q[b, i, head, :]) / scale) * mem_scale_k,   part_v = (sum_i P dout) * mem_scale_v,
+// and the images are then summed by ovc_bw_colsum (64-image chunks in ascending order, then the chunks in ascending order) into
+// d_mk / d_mv [m][h dk].  colpart: ceil(B / 64) * m * h * dk floats.
+struct AttnBwdMemArgs {
+    AttnBwdArgs a;                     // P / dS sized for nk + m keys
+    const float* m_k; const float* m_v;          // [m][h dk]
+    int m;
+    float mem_scale_k, mem_scale_v;
+    float* part_k; float* part_v;      // [B][m][h dk]
+    float* colpart;
+    float* d_mk; float* d_mv;          // [m][h dk]
+};
+int ovc_bw_attention_mem(const AttnBwdMemArgs& p, hipStream_t s);
+
 // Vocabulary: loss = -sum_r w_r logp[r, tgt_r] with w_r = [tgt_r != pad] / count (fixed-order block sum), then
 // dlogit = (softmax - onehot(tgt)) w_r from the stored transposed logits and the forward's (max, log sum) pieces, written
 // transposed [V][ldt] and row-major [rows][ldv] (padding 0).

@@ -206,6 +206,110 @@ __global__ __launch_bounds__(64) void bw_attention_keys_kernel(AttnBwdArgs a) {
     a.dv_out[krow * a.lddkv + hh * dk + lane] = gv;
 }
 
+// bw_attention_rows_kernel with p.m memory slots behind the nk real keys (ovc_bw_attention_mem): slot keys / values are the
+// forward's fp32 products mem_scale * m, never masked; LDS: 128 + 2 (nk + m) floats
+__global__ __launch_bounds__(64) void bw_attention_rows_mem_kernel(AttnBwdMemArgs p) {
+    extern __shared__ float sm[];
+    const AttnBwdArgs& a = p.a;
+    const int nkt = a.nk + p.m;
+    float* qs = sm; float* os = sm + 64; float* s = sm + 128; float* dp = s + nkt;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x % a.nq, bh = blockIdx.x / a.nq, hh = bh % a.h, b = bh / a.h;
+    const size_t qrow = (size_t)b * a.nq + i;
+    const int dk = a.dk, hk = a.h * a.dk;
+    if (lane < dk) { qs[lane] = a.q[qrow * a.ldq + hh * dk + lane]; os[lane] = a.dout[qrow * a.ldo + hh * dk + lane]; }
+    __syncthreads();
+    const uint8_t* mrow = a.mask ? a.mask + (size_t)b * a.mask_b + (size_t)i * a.mask_r : nullptr;
+    float mx = -INFINITY;
+    for (int j = lane; j < nkt; j += 64) {
+        float sc = 0.f, g = 0.f;
+        if (j < a.nk) {
+            const float* kr = a.k + ((size_t)b * a.nk + j) * a.ldkv + hh * dk;
+            const float* vr = a.v + ((size_t)b * a.nk + j) * a.ldkv + hh * dk;
+            for (int t = 0; t < dk; ++t) { sc = fmaf(qs[t], kr[t], sc); g = fmaf(os[t], vr[t], g); }
+            sc = (mrow && mrow[j]) ? -INFINITY : sc / a.scale;
+        } else {
+            const float* kr = p.m_k + (size_t)(j - a.nk) * hk + hh * dk;
+            const float* vr = p.m_v + (size_t)(j - a.nk) * hk + hh * dk;
+            for (int t = 0; t < dk; ++t) {
+                const float kx = kr[t] * p.mem_scale_k, vx = vr[t] * p.mem_scale_v;
+                sc = fmaf(qs[t], kx, sc); g = fmaf(os[t], vx, g);
+            }
+            sc = sc / a.scale;
+        }
+        s[j] = sc; dp[j] = g;
+        mx = fmaxf(mx, sc);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < nkt; j += 64) sum += s[j] == -INFINITY ? 0.f : expf(s[j] - mx);
+    sum = wave_sum(sum);
+    float delta = 0.f;
+    for (int j = lane; j < nkt; j += 64) {
+        const float pj = (s[j] == -INFINITY || !(sum > 0.f)) ? 0.f : expf(s[j] - mx) / sum;
+        s[j] = pj;
+        delta = fmaf(pj, dp[j], delta);
+    }
+    delta = wave_sum(delta);
+    const size_t po = (((size_t)b * a.h + hh) * a.nq + i) * nkt;
+    for (int j = lane; j < nkt; j += 64) {
+        const float pj = s[j], g = pj * (dp[j] - delta);
+        dp[j] = g;
+        a.P[po + j] = pj; a.dS[po + j] = g;
+    }
+    __syncthreads();
+    if (lane < dk) {
+        float acc = 0.f;
+        for (int j = 0; j < a.nk; ++j) acc = fmaf(dp[j], a.k[((size_t)b * a.nk + j) * a.ldkv + hh * dk + lane], acc);
+        for (int sl = 0; sl < p.m; ++sl) acc = fmaf(dp[a.nk + sl], p.m_k[(size_t)sl * hk + hh * dk + lane] * p.mem_scale_k, acc);
+        a.dq[qrow * a.lddq + hh * dk + lane] = acc / a.scale;
+    }
+}
+
+// The column sums of one key column `col` of the [nq][nk + m] scratch rows of (image b, head hh), for the lane's column of the head:
+// gk = sum_i dS[i][col] q[i], gv = sum_i P[i][col] dout[i], ONE fmaf chain each over the queries in ascending order.  Shared by the
+// two kernels below only: bw_attention_keys_kernel keeps its own loop (and with it its instructions).
+__device__ __forceinline__ void bw_mem_column_sums(const AttnBwdArgs& a, int m, int b, int hh, int col, int lane, float& gk, float& gv) {
+    const int dk = a.dk;
+    const size_t ld = (size_t)a.nk + m;
+    const size_t po = ((size_t)b * a.h + hh) * a.nq * ld + col;
+    gk = 0.f; gv = 0.f;
+    for (int i = 0; i < a.nq; ++i) {
+        const size_t qrow = (size_t)b * a.nq + i;
+        const float ds = a.dS[po + (size_t)i * ld], pj = a.P[po + (size_t)i * ld];
+        gk = fmaf(ds, a.q[qrow * a.ldq + hh * dk + lane], gk);
+        gv = fmaf(pj, a.dout[qrow * a.ldo + hh * dk + lane], gv);
+    }
+}
+
+// the keys pass over scratch rows of nk + m entries: one wave per (image, head, real key), the real keys' gradients
+__global__ __launch_bounds__(64) void bw_attention_keys_mem_kernel(AttnBwdMemArgs p) {
+    const AttnBwdArgs& a = p.a;
+    const int lane = threadIdx.x;
+    const int j = blockIdx.x % a.nk, bh = blockIdx.x / a.nk, hh = bh % a.h, b = bh / a.h;
+    const int dk = a.dk;
+    if (lane >= dk) return;
+    float gk, gv;
+    bw_mem_column_sums(a, p.m, b, hh, j, lane, gk, gv);
+    const size_t krow = (size_t)b * a.nk + j;
+    a.dk_out[krow * a.lddkv + hh * dk + lane] = gk / a.scale;
+    a.dv_out[krow * a.lddkv + hh * dk + lane] = gv;
+}
+
+// one wave per (image, head, slot): the image's share of d(m_k) / d(m_v), queries in ascending order, both scales applied here
+__global__ __launch_bounds__(64) void bw_attention_slots_kernel(AttnBwdMemArgs p) {
+    const AttnBwdArgs& a = p.a;
+    const int lane = threadIdx.x;
+    const int sl = blockIdx.x % p.m, bh = blockIdx.x / p.m, hh = bh % a.h, b = bh / a.h;
+    const int dk = a.dk, hk = a.h * a.dk;
+    if (lane >= dk) return;
+    float gk, gv;
+    bw_mem_column_sums(a, p.m, b, hh, a.nk + sl, lane, gk, gv);
+    const size_t o = ((size_t)b * p.m + sl) * hk + hh * dk + lane;
+    p.part_k[o] = (gk / a.scale) * p.mem_scale_k;
+    p.part_v[o] = gv * p.mem_scale_v;
+}
+
 // one workgroup: count of non-pad targets and the summed negative log-likelihood, thread partials over rows t, t + 256, ...
 // then a fixed LDS tree; afterwards every row's weight
 __global__ __launch_bounds__(256) void bw_loss_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
@@ -366,6 +470,23 @@ int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s) {
     return OVC_OK;
 }
 
+int ovc_bw_attention_mem(const AttnBwdMemArgs& p, hipStream_t s) {
+    const AttnBwdArgs& a = p.a;
+    if (a.dk > 64 || a.dk <= 0 || a.nk <= 0 || a.nq <= 0 || a.B <= 0 || p.m <= 0) return OVC_EINVAL;
+    if (!p.m_k || !p.m_v || !p.part_k || !p.part_v || !p.colpart || !p.d_mk || !p.d_mv) return OVC_EINVAL;
+    const size_t lds = (128 + 2 * ((size_t)a.nk + p.m)) * sizeof(float);
+    if (lds > 64 * 1024) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_attention_rows_mem_kernel, dim3(a.B * a.h * a.nq), dim3(64), lds, s, p);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_attention_keys_mem_kernel, dim3(a.B * a.h * a.nk), dim3(64), 0, s, p);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_attention_slots_kernel, dim3(a.B * a.h * p.m), dim3(64), 0, s, p);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    const int cols = p.m * a.h * a.dk;
+    if (const int rc = ovc_bw_colsum(p.part_k, cols, a.B, cols, p.colpart, p.d_mk, s)) return rc;
+    return ovc_bw_colsum(p.part_v, cols, a.B, cols, p.colpart, p.d_mv, s);
+}
+
 int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, float* w_row,
                 float* loss, float* dl_t, float* dl, long ldv, hipStream_t s) {
     hipLaunchKernelGGL(bw_loss_kernel, dim3(1), dim3(256), 0, s, logits_t, ldt, lse, tgt, pad, rows, w_row, loss);
@@ -395,6 +516,24 @@ int ovc_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, hipStr
     hipLaunchKernelGGL(bw_tokens_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, tokens, rows, V, tok32);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+// Test hook (include/ovc.h): ovc_bw_attention_mem on caller-supplied buffers.
+extern "C" int ovc_debug_attention_mem_backward(const float* q, const float* k, const float* v, const float* dout, const uint8_t* mask,
+                                                const float* m_k, const float* m_v, int B, int n, int h, int dk, int m, float* P,
+                                                float* dS, float* dq, float* dk_out, float* dv_out, float* part_k, float* part_v,
+                                                float* colpart, float* d_mk, float* d_mv, ovc_stream stream) {
+    if (!q || !k || !v || !dout || !P || !dS || !dq || !dk_out || !dv_out || B <= 0 || n <= 0 || h <= 0 || m <= 0) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    const int hk = h * dk;
+    AttnBwdMemArgs p{};
+    p.a.q = q; p.a.ldq = hk; p.a.k = k; p.a.v = v; p.a.ldkv = hk; p.a.dout = dout; p.a.ldo = hk;
+    p.a.mask = mask; p.a.mask_b = n; p.a.mask_r = 0;
+    p.a.B = B; p.a.nq = n; p.a.nk = n; p.a.h = h; p.a.dk = dk; p.a.scale = sqrtf((float)dk);
+    p.a.P = P; p.a.dS = dS; p.a.dq = dq; p.a.lddq = hk; p.a.dk_out = dk_out; p.a.dv_out = dv_out; p.a.lddkv = hk;
+    p.m_k = m_k; p.m_v = m_v; p.m = m; p.mem_scale_k = sqrtf((float)dk); p.mem_scale_v = sqrtf((float)m);
+    p.part_k = part_k; p.part_v = part_v; p.colpart = colpart; p.d_mk = d_mk; p.d_mv = d_mv;
+    return ovc_bw_attention_mem(p, ovc_hip_stream(stream));
 }
 
 extern "C" int ovc_scale(const float* x, const float* scale, float* y, long n, ovc_stream stream) {

@@ -1871,8 +1871,11 @@ struct TrainWs {
     float* denc[2];               // gradient of the encoder output, [B*N][d]
     float* dkv;                   // [B*N][2 h d_k]
     float* ta; float* tb;         // transposed GEMM operands [max(d, d_ff, 3 h d_k)][Rmax padded to 4]
-    float* P; float* dS;          // attention backward [B][h][nq][nk]
+    float* P; float* dS;          // attention backward [B][h][nq][nk]; the encoder's with memory slots [B][h][N][N + memory]
     float* part;                  // column-sum partials [ceil(Rmax / 64)][d]
+    // encoder memory slots (train_memory(m) > 0 only; ovc_bw_attention_mem): each image's share of d(m_k) / d(m_v),
+    // [B][memory][h_enc dk_enc] each, and the partials of their sum over the images [ceil(B / 64)][memory h_enc dk_enc]
+    float* mem_part_k; float* mem_part_v; float* mem_colpart;
     // dropout (carve_train(..., dropout = true) only; ovc_train_dropout_workspace_bytes)
     float* dproj;                 // [Rmax][d] gradient of a masked projection: keep * s * dy
     int64_t* seed;                // the step's seed, copied in outside the captured body
@@ -1890,6 +1893,9 @@ struct TrainWs {
 };
 
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// the memory slots of the encoder layers' self-attention in a training call (train_ok: every layer has them, or none)
+inline int train_memory(const ovc_model* m) { return m->enc[0].att.m_k ? m->memory : 0; }
 
 // S > 1 (with seq): S sequences per image, rows = B*S*T (run_forward_decoder)
 TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false, int S = 1, bool seq = false) {
@@ -1938,9 +1944,14 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
     for (int i = 0; i < 2; ++i) t.denc[i] = a.take<float>(BN * d);
     t.dkv = a.take<float>(BN * 2 * hk);
     t.ta = a.take<float>(wide * Rp); t.tb = a.take<float>(wide * Rp);
-    const size_t pdec = (size_t)B * S * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * N;
+    const size_t mem = train_memory(m);
+    const size_t pdec = (size_t)B * S * m->heads * T * std::max(T, N), penc = (size_t)B * enc_heads(m) * N * (N + mem);
     t.P = a.take<float>(std::max(pdec, penc)); t.dS = a.take<float>(std::max(pdec, penc));
     t.part = a.take<float>(((R + 63) / 64) * std::max(d, dff));
+    if (mem) {
+        t.mem_part_k = a.take<float>((size_t)B * mem * ehk); t.mem_part_v = a.take<float>((size_t)B * mem * ehk);
+        t.mem_colpart = a.take<float>((((size_t)B + 63) / 64) * mem * ehk);
+    }
     if (dropout) {
         t.dproj = a.take<float>(R * d);
         t.seed = a.take<int64_t>(2);
@@ -1956,20 +1967,24 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
 bool lin_grad_ok(const ovc_lin& l, const ovc_lin& g) { return g.w && (!l.b || g.b); }
 bool norm_grad_ok(const ovc_norm& g) { return g.g && g.b; }
 bool mha_plain(const ovc_mha& a) { return !a.aoa_i.w && !a.aoa_g.w && !a.m_k && !a.m_v; }
+// an encoder layer's self-attention with memory slots (AugmentedMemoryScaledDotProductAttention): both tables, no AoA gates
+bool mha_memory(const ovc_mha& a) { return !a.aoa_i.w && !a.aoa_g.w && a.m_k && a.m_v; }
 bool mha_grad_ok(const ovc_mha& a, const ovc_mha& g) {
     return lin_grad_ok(a.q, g.q) && lin_grad_ok(a.k, g.k) && lin_grad_ok(a.v, g.v) && lin_grad_ok(a.o, g.o) && norm_grad_ok(g.ln);
 }
 bool ffn_grad_ok(const ovc_ffn& f, const ovc_ffn& g) { return lin_grad_ok(f.fc1, g.fc1) && lin_grad_ok(f.fc2, g.fc2) && norm_grad_ok(g.ln); }
 
-// What the backward covers: the plain or cross-level (CaMo) encoder with the plain decoder, plain scaled dot-product attention,
-// fp32, and vocabularies that take the fused vocabulary tail (its transposed logits and block pieces are what the cross-entropy
-// backward reads).
+// What the backward covers: the plain or cross-level (CaMo) encoder with the plain decoder, plain scaled dot-product attention
+// -- in the PLAIN encoder's layers also with memory slots (memory > 0 and m_k / m_v in every layer: the augmented-memory
+// transformer) -- fp32, and vocabularies that take the fused vocabulary tail (its transposed logits and block pieces are what the
+// cross-entropy backward reads).
 bool train_ok(const ovc_model* m, int B, int N, int T) {
     if (!forward_ok(m, B, N, T)) return false;
     if (m->enc_kind != OVC_ENC_PLAIN && m->enc_kind != OVC_ENC_CROSS_LEVEL) return false;
-    if (m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    if (m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1) return false;
+    if (m->memory != 0 && m->enc_kind != OVC_ENC_PLAIN) return false;
     if (m->enc_kind == OVC_ENC_CROSS_LEVEL && (m->precision != 0 || !mha_plain(m->cl_att))) return false;
-    for (int l = 0; l < m->n_enc; ++l) if (!mha_plain(m->enc[l].att)) return false;
+    for (int l = 0; l < m->n_enc; ++l) if (!(m->memory != 0 ? mha_memory(m->enc[l].att) : mha_plain(m->enc[l].att))) return false;
     for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
     if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
     // the dlogit products address their operands with 32-bit buffer descriptors (ovc_gemm_launch)
@@ -1980,7 +1995,8 @@ bool train_ok(const ovc_model* m, int B, int N, int T) {
 bool grads_ok(const ovc_model* m, const ovc_model* g) {
     if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
     for (int l = 0; l < m->n_enc; ++l)
-        if (!mha_grad_ok(m->enc[l].att, g->enc[l].att) || !ffn_grad_ok(m->enc[l].ffn, g->enc[l].ffn)) return false;
+        if (!mha_grad_ok(m->enc[l].att, g->enc[l].att) || !ffn_grad_ok(m->enc[l].ffn, g->enc[l].ffn) ||
+            (m->enc[l].att.m_k && (!g->enc[l].att.m_k || !g->enc[l].att.m_v))) return false;
     for (int l = 0; l < m->n_dec; ++l)
         if (!mha_grad_ok(m->dec[l].self_att, g->dec[l].self_att) || !mha_grad_ok(m->dec[l].cross_att, g->dec[l].cross_att) ||
             !ffn_grad_ok(m->dec[l].ffn, g->dec[l].ffn)) return false;
@@ -2065,7 +2081,7 @@ int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const flo
 // to dx (gradient of the layer input x, which fed q, k, v and the residual)
 int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const float* x, const float* q, const float* k,
                       const float* v, const float* att, const float* y, const float* dnorm, const uint8_t* mask, long mask_b,
-                      long mask_r, int B, int n, int h, int dk, float* dx, int site = -1) {
+                      long mask_r, int B, int n, int h, int dk, float* dx, int site = -1, int mem = 0) {
     const int d = e.m->d_model, hk = h * dk, rows = B * n;
     TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows, site));
     const float* dp = proj_grad(e, t, site);
@@ -2076,7 +2092,17 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
     p.mask = mask; p.mask_b = mask_b; p.mask_r = mask_r;
     p.B = B; p.nq = n; p.nk = n; p.h = h; p.dk = dk; p.scale = sqrtf((float)dk);
     p.P = t.P; p.dS = t.dS; p.dq = t.dqkv; p.lddq = 3 * hk; p.dk_out = t.dqkv + hk; p.dv_out = t.dqkv + 2 * hk; p.lddkv = 3 * hk;
-    RUN(ovc_bw_attention(p, e.stream));
+    if (mem > 0) {
+        // the encoder's memory slots: the forward's scales (run_encoder_layers), d(m_k) / d(m_v) summed over the whole batch
+        AttnBwdMemArgs pm{};
+        pm.a = p; pm.m_k = at.m_k; pm.m_v = at.m_v; pm.m = mem;
+        pm.mem_scale_k = sqrtf((float)dk); pm.mem_scale_v = sqrtf((float)mem);
+        pm.part_k = t.mem_part_k; pm.part_v = t.mem_part_v; pm.colpart = t.mem_colpart;
+        pm.d_mk = out_ptr(ga.m_k); pm.d_mv = out_ptr(ga.m_v);
+        RUN(ovc_bw_attention_mem(pm, e.stream));
+    } else {
+        RUN(ovc_bw_attention(p, e.stream));
+    }
     const ovc_lin* lins[3] = {&at.q, &at.k, &at.v};
     const ovc_lin* glins[3] = {&ga.q, &ga.k, &ga.v};
     for (int i = 0; i < 3; ++i) {
@@ -2266,7 +2292,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
         const float* xin = l == 0 ? w.xe[0] : cl ? w.cl_out + (size_t)(l - 1) * nd : t.tape.enc[l - 1].out;
         TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
-                              enc_site(l, 0)));
+                              enc_site(l, 0), train_memory(m)));
         dout = t.g[cur];
         if (cl && l > 0) {
             float* lev = t.cl_dlev + (size_t)(l - 1) * nd;

@@ -134,8 +134,9 @@ def _ffn(dst, pwff, planes=None, mode=0):
 
 def _grad_slots(model):
     """(parameter, field path in the ``ovc_model`` table) of every parameter ``ovc_forward_backward`` writes a gradient for:
-    the plain encoder / decoder's projections, norms and FFNs, the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``,
-    ``mlp2``), the word embedding and the vocabulary projection."""
+    the plain encoder / decoder's projections, norms and FFNs, the encoder layers' memory slots (``attention.m_k`` / ``m_v``,
+    the augmented-memory transformer), the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``, ``mlp2``), the word
+    embedding and the vocabulary projection."""
     from .modules import encoders
     enc, dec = model.encoder, model.decoder
     slots = []
@@ -163,6 +164,9 @@ def _grad_slots(model):
     norm(("enc_ln",), enc.layer_norm)
     for i, layer in enumerate(enc.layers):
         mha(("enc", i, "att"), layer.mhatt)
+        if hasattr(layer.mhatt.attention, "m_k"):
+            slots.append((layer.mhatt.attention.m_k, ("enc", i, "att", "m_k")))
+            slots.append((layer.mhatt.attention.m_v, ("enc", i, "att", "m_v")))
         ffn(("enc", i, "ffn"), layer.pwff)
     if isinstance(enc, encoders.CrossAttentionMultiLevelEncoder):
         mha(("cl_att",), enc.self_attn)
@@ -542,7 +546,8 @@ class CaptionEngine:
         at every step, the key of its masks (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
         self._check_trainable()
         if self.desc.enc_kind != native.ENC_PLAIN:
-            raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer only")
+            raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer (with or without "
+                                  "encoder memory slots) only")
         features, boxes = self._checked_inputs(features, boxes)
         features, boxes = self._bucketed(features, boxes)
         B, N = features.shape[:2]
@@ -651,8 +656,9 @@ class CaptionEngine:
 
     # -- training ---------------------------------------------------------------------------------------------------
     def _check_trainable(self):
-        """The backward covers the plain standard transformer and the CaMo transformer (cross-level encoder, plain decoder) in
-        fp32: anything else is refused before a launch."""
+        """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'
+        self-attention has memory slots, plain decoder) and the CaMo transformer (cross-level encoder, plain decoder) in fp32:
+        anything else is refused before a launch."""
         d = self.desc
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
@@ -660,13 +666,15 @@ class CaptionEngine:
             raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
                                   "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
         model = self.model
-        mhas = [layer.mhatt for layer in model.encoder.layers]
-        if d.enc_kind == native.ENC_CROSS_LEVEL:
-            mhas.append(model.encoder.self_attn)
-        mhas += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
-        if any(m.use_aoa for m in mhas):
+        layers = [layer.mhatt for layer in model.encoder.layers]
+        others = [model.encoder.self_attn] if d.enc_kind == native.ENC_CROSS_LEVEL else []
+        others += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
+        if any(m.use_aoa for m in layers + others):
             raise native.OvcError("the training backward does not cover attention-on-attention gates")
-        if any(hasattr(m.attention, "m_k") for m in mhas) or d.memory:
+        # memory slots: in every layer of the plain encoder (the augmented-memory transformer) or nowhere
+        with_memory = [hasattr(m.attention, "m_k") for m in layers]
+        memory_ok = all(with_memory) and d.enc_kind == native.ENC_PLAIN and d.memory > 0
+        if any(hasattr(m.attention, "m_k") for m in others) or (any(with_memory) or d.memory) and not memory_ok:
             raise native.OvcError("the training backward does not cover attention memory slots")
         if not hasattr(model.decoder.word_emb, "components"):
             raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")

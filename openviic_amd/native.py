@@ -125,6 +125,7 @@ SIGNATURES = {
     "ovc_graph_cache_size": (c_int, []),
     "ovc_debug_force_gemm_tiling": (c_int, [c_int]),
     "ovc_debug_clear_tuning": (c_int, []),
+    "ovc_debug_attention_mem_backward": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p] * 11),
     "ovc_debug_linear_tiling": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ovc_debug_vocab_select_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ovc_debug_vocab_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
@@ -176,7 +177,7 @@ SIGNATURES = {
 # appended to ABI 8 without a bump (include/ovc.h): a library built before them still loads under OVC_LIBRARY
 APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_bytes", "ovc_beam_search_dropout",
                  "ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout",
-                 "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step")
+                 "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step", "ovc_debug_attention_mem_backward")
 
 _lib = None
 

@@ -56,7 +56,7 @@ def recompute_flops(dims, images, S, N, T):
     BN, R, hk = images * N, images * S * T, h * dk
     he = dims.get("he", h)
     f = 2 * BN * dfeat * d
-    f += Le * (2 * BN * d * 3 * he * dk + 4 * images * he * N * N * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
+    f += Le * (2 * BN * d * 3 * he * dk + 4 * images * he * N * (N + dims.get("memory", 0)) * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
     if dims.get("tail"):            # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
         f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * images * he * N * N * dk + 2 * BN * he * dk * d)
         f += 2 * BN * 3 * d * d + 2 * BN * d * d
@@ -234,8 +234,10 @@ def main():
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
-                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
+    ap.add_argument("--variant", default="standard_transformer",
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer"],
+                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
+                         "augmented_memory_transformer: the plain encoder with 40 memory slots per layer")
     ap.add_argument("--reward", default="none", choices=["none", "host", "device"],
                     help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
     ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
@@ -266,6 +268,8 @@ def main():
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     if args.variant == "camo_transformer":
         dims.update(he=1, tail=True)
+    if args.variant == "augmented_memory_transformer":
+        dims.update(memory=40)
     results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" else []
     if args.dropout:
         results = dropout_probe(args, model, N, D, k)

@@ -4,6 +4,10 @@ configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, 
     python tools/train_step_probe.py [--batches 60 256] [--steps 20] [--warmup 5] [--dropout] [--out results/train_step_probe.json]
     python tools/train_step_probe.py --optimizer torch engine xe_step [--rounds 2] ...     # the whole iteration, optimizer included
 
+--variant augmented_memory_transformer: the plain encoder with 40 memory slots per layer (the memory-slot attention backward).
+Several --variant values alternate in ONE process -- per batch size, ``--rounds`` rounds of ``--steps`` steps of each variant in
+turn, each on its own model -- so a variant's step time stands next to the standard transformer's from the same run.
+
 --dropout: the model in train() mode with the reference's DROPOUT 0.1 at every site, ``model.xe_loss(items, dropout=True)``
 (ovc_forward_backward_dropout; a fresh seed per step).
 
@@ -42,7 +46,7 @@ def step_flops(cfg_dims, B, N, T):
     BN, R, hk = B * N, B * T, h * dk
     he = cfg_dims.get("he", h)
     f = 2 * BN * dfeat * d
-    f += Le * (2 * BN * d * 3 * he * dk + 4 * B * he * N * N * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
+    f += Le * (2 * BN * d * 3 * he * dk + 4 * B * he * N * (N + cfg_dims.get("memory", 0)) * dk + 2 * BN * he * dk * d + 4 * BN * d * dff)
     if cfg_dims.get("tail"):        # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
         f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * B * he * N * N * dk + 2 * BN * he * dk * d)
         f += 2 * BN * 3 * d * d + 2 * BN * d * d
@@ -103,14 +107,62 @@ def optimizer_probe(args, build, items, B):
     return rows
 
 
+def variant_dims(variant):
+    return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40)}.get(variant, {})
+
+
+def alternate_variants(args, vocab, V, T, N, D):
+    """Every --variant in turn, --rounds times per batch size, in this one process: one model per variant."""
+    models = {}
+    for variant in args.variant:
+        model = build_model(model_config(variant, d_feature=D, device="cuda:0"), vocab).eval()
+        model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
+        models[variant] = model.train() if args.dropout else model
+    results = []
+    for B in args.batches:
+        g = torch.Generator().manual_seed(B)
+        tokens = torch.randint(4, V, (B, T), generator=g)
+        tokens[:, 0] = 1
+        items = InstanceList()
+        items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        items.caption_tokens = tokens.cuda()
+        items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
+
+        def step(model):
+            model.zero_grad(set_to_none=True)
+            model.xe_loss(items, dropout=args.dropout).backward()
+        for model in models.values():
+            for _ in range(args.warmup):
+                step(model)
+        torch.cuda.synchronize()
+        for rnd in range(args.rounds):
+            for variant, model in models.items():
+                ms = events_ms(lambda: step(model), args.steps)
+                dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3, **variant_dims(variant))
+                flops = step_flops(dims, B, N, T)
+                lib = model._fused_engine().lib
+                sizer = lib.ovc_train_dropout_workspace_bytes if args.dropout else lib.ovc_train_workspace_bytes
+                ws = sizer(model._fused_engine().desc, B, N, T)
+                row = dict(variant=variant, B=B, T=T, N=N, dropout=args.dropout, round=rnd, ms_per_step=round(ms, 3),
+                           gflop_per_step=round(flops / 1e9, 1), tflops=round(flops / ms / 1e9, 2), workspace_mb=round(ws / 2 ** 20, 1))
+                results.append(row)
+                print(json.dumps(row), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
-    ap.add_argument("--variant", default="standard_transformer", choices=["standard_transformer", "camo_transformer"],
-                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail")
+    ap.add_argument("--variant", nargs="+", default=["standard_transformer"],
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer"],
+                    help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
+                         "augmented_memory_transformer: 40 memory slots in the encoder; several values alternate in one process")
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
                     help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
@@ -121,6 +173,11 @@ def main():
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
+    if len(args.variant) > 1:
+        if args.optimizer != ["none"]:
+            ap.error("several --variant values go with --optimizer none")
+        return alternate_variants(args, vocab, V, T, N, D)
+    args.variant = args.variant[0]
     cfg = model_config(args.variant, d_feature=D, device="cuda:0")
     def build():
         model = build_model(cfg, vocab).eval()
@@ -128,8 +185,7 @@ def main():
         return model.train() if args.dropout else model
     model = build() if args.optimizer == ["none"] else None
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
-    if args.variant == "camo_transformer":
-        dims.update(he=1, tail=True)
+    dims.update(variant_dims(args.variant))
     results = []
     for B in args.batches:
         g = torch.Generator().manual_seed(B)

@@ -143,7 +143,7 @@ int enc_heads(const ovc_model* m) { return m->enc_heads ? m->enc_heads : m->head
 int enc_dk(const ovc_model* m) { return m->enc_d_k ? m->enc_d_k : m->d_k; }
 int enc_dv(const ovc_model* m) { return m->enc_d_v ? m->enc_d_v : m->d_v; }
 
-// the rules the encoder stack's attention geometry obeys (the decoder's: model_ok, the same rules)
+// the rules an attention geometry obeys: the decoder's and the encoder stack's own (model_ok)
 bool heads_ok(int h, int dk, int dv) {
     // head size: the decode attention kernels need d_k == d_v in {4, 8, 16, 32, 64} (attention.hip: the self-attention
     // reduces a head inside a power-of-two lane group), at most 32 heads and heads * d_k <= 1024
@@ -158,16 +158,12 @@ bool model_ok(const ovc_model* m) {
     if (m->n_enc < 1 || m->n_enc > OVC_MAX_LAYERS || m->n_dec < 1 || m->n_dec > OVC_MAX_LAYERS) return false;
     if (m->n_levels < 1 || m->n_levels > OVC_MAX_LEVELS) return false;
     if (m->d_model <= 0 || (m->d_model & 3) || m->d_model > 2048) return false;
-    // head size: the decode attention kernels need d_k == d_v in {4, 8, 16, 32, 64} (attention.hip: the self-attention
-    // reduces a head inside a power-of-two lane group), at most 32 heads and heads * d_k <= 1024
-    if (m->d_k != m->d_v || m->d_k < 4 || m->d_k > 64 || (m->d_k & (m->d_k - 1))) return false;
-    if ((m->d_feat & 3) || (m->d_ff & 3) || m->heads <= 0 || m->heads > 32 || m->heads * m->d_k > 1024 || m->vocab <= 1) return false;
+    if (!heads_ok(m->heads, m->d_k, m->d_v)) return false;
+    if ((m->d_feat & 3) || (m->d_ff & 3) || m->vocab <= 1) return false;
     if (m->d_feat <= 0 || m->d_ff <= 0 || m->memory < 0) return false;
     if (m->max_len < 1 || m->max_len > OVC_MAX_LEN) return false;
     if ((m->precision != 0 && m->precision != 3 && m->precision != 4) || m->tune_objective < 0 || m->tune_objective > 8) return false;
     if (m->bos_idx < 0 || m->bos_idx >= m->vocab || m->pad_idx < 0 || m->pad_idx >= m->vocab || m->eos_idx < 0 || m->eos_idx >= m->vocab) return false;
-    // fused q|k|v and cross k|v GEMMs need segment widths that are multiples of the 64-wide tile
-    if ((m->heads * m->d_k) % 64 || (m->heads * m->d_v) % 64 || (m->heads * m->d_k) != (m->heads * m->d_v)) return false;
     if (m->dec_kind == OVC_DEC_MESHED && m->enc_kind != OVC_ENC_MULTILEVEL) return false;
     if (m->dec_kind != OVC_DEC_MESHED && m->n_levels != 1) return false;
     if (m->enc_heads < 0 || m->enc_d_k < 0 || m->enc_d_v < 0 || !heads_ok(enc_heads(m), enc_dk(m), enc_dv(m))) return false;
@@ -1184,6 +1180,42 @@ bool forward_ok(const ovc_model* m, int B, int N, int T) {
            (long)B * T <= (1L << 24);
 }
 
+// The front end the four searches share: the argument checks, the workspace carved (dropout: with the seed / step-count slots
+// behind the plain layout) and the Engine on the caller's stream.
+int open_search(const ovc_model* m, const float* features, int B, int N, int k, int out_size, void* workspace, size_t workspace_bytes,
+                const int64_t* ids_out, const float* logp_out, int return_probs, bool dropout, ovc_stream stream, Workspace& w,
+                Engine& e) {
+    if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
+    if ((long)m->vocab < k) return OVC_EINVAL;
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    w = carve(m, workspace, B, N, k, return_probs, dropout);
+    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    e = Engine{m, ovc_hip_stream(stream), 0};
+    return OVC_OK;
+}
+
+// What every search issues behind its input kernels and before step 0.  clear_alive_count (the early-exit searches): this search's
+// counts -- in the gated search's graph, where a count left by the previous replay must never open a gate.
+int issue_search_prologue(Engine& e, Workspace& w, int B, int N, int k, bool clear_alive_count) {
+    const int R = B * k;
+    TRY(run_encoder_layers(e, w, B, N));
+    TRY(project_cross_kv(e, w, B, N));
+    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    if (clear_alive_count && hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * e.m->max_len, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    return OVC_OK;
+}
+
+// The final ordering's arguments: the beam state of buffer `parity`, written to ids / logp.
+BeamFinalArgs final_args(const Workspace& w, int parity, int k, int T, int out_size, int64_t* ids, float* logp) {
+    BeamFinalArgs bf{};
+    bf.running = w.running[parity]; bf.hist = w.hist[parity]; bf.lp = w.lp[parity];
+    bf.k = k; bf.T = T; bf.out_size = out_size; bf.ids_out = ids; bf.logp_out = logp; bf.order_out = w.order;
+    return bf;
+}
+
 }  // namespace
 
 extern "C" int ovc_abi_version(void) { return 8; }     // 8: OVC_ENC_CROSS_LEVEL, encoder-stack heads / d_k / d_v (appended fields)
@@ -1243,28 +1275,16 @@ extern "C" int ovc_encode(const ovc_model* m, const float* features, const float
 extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
                                int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
                                float* logp_out, float* all_logp_out, ovc_stream stream) {
-    if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
-    if ((long)m->vocab < k) return OVC_EINVAL;
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
     const int return_probs = all_logp_out != nullptr;
-    Workspace w = carve(m, workspace, B, N, k, return_probs);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
-    const int R = B * k, T = m->max_len;
+    Workspace w;
+    Engine e{};
+    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, return_probs, false, stream, w, e));
+    const int T = m->max_len;
 
-    TRY(run_encoder(e, w, features, boxes, B, N));
-    TRY(project_cross_kv(e, w, B, N));
-    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
-    OVC_RETURN_IF_LAUNCH_FAILED();
+    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
+    TRY(issue_search_prologue(e, w, B, N, k, false));
     for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, return_probs));
-
-    const int fin = T & 1;
-    BeamFinalArgs bf{};
-    bf.running = w.running[fin]; bf.hist = w.hist[fin]; bf.lp = w.lp[fin];
-    bf.k = k; bf.T = T; bf.out_size = out_size; bf.ids_out = ids_out; bf.logp_out = logp_out; bf.order_out = w.order;
-    TRY(ovc_beam_finalize_launch(bf, B, e.stream));
+    TRY(ovc_beam_finalize_launch(final_args(w, T & 1, k, T, out_size, ids_out, logp_out), B, e.stream));
     if (return_probs) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, B, k, T, m->vocab, all_logp_out, e.stream));
     return OVC_OK;
 }
@@ -1275,11 +1295,18 @@ extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const 
 // for a given (model, B, N, k, workspace), so it is captured once and replayed.
 // ---------------------------------------------------------------------------------------------
 namespace {
+// What a cached launch sequence is, and with it what its key's k / out_size hold.  The first member of GraphKey and without a
+// default: a key cannot be built without naming its kind, so two call sites never share entries by accident.
+enum class GraphKind {
+    Search,             // ovc_beam_search_graph and the per-step graphs of ovc_beam_search_early (k = beam, out_size)
+    Forward,            // ovc_forward (k = T, out_size = want_logp)
+    GatedSearch,        // ovc_beam_search_gated (k = beam, out_size)
+    Train,              // ovc_forward_backward (k = T)
+    TrainDropout,       // ovc_forward_backward_dropout (k = T)
+    SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
+};
 struct GraphKey {
-    uint64_t model_hash; const void* ws; int B, N, k, out_size;
-    int kind = 0;                  // 0 = the search (k = beam, out_size), 1 = ovc_forward (k = T, out_size = want_logp),
-                                   // 2 = the gated search (ovc_beam_search_gated), 3 = ovc_forward_backward, 4 = the same with dropout,
-                                   // 5 = ovc_sequence_backward (k = T, out_size = S)
+    GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
     bool operator<(const GraphKey& o) const {
         return std::tie(model_hash, ws, B, N, k, out_size, kind) < std::tie(o.model_hash, o.ws, o.B, o.N, o.k, o.out_size, o.kind);
     }
@@ -1360,8 +1387,12 @@ uint64_t hash_bytes(const void* p, size_t n) {
     return h;
 }
 
-// The stream launch sequences are captured on (never the caller's: see ovc_beam_search_graph).  One device per process
-// (ovc_device_guard): the stream belongs to the bound device.  Caller holds g_graph_mutex; nullptr = no capture support.
+// The stream launch sequences are captured on: a PRIVATE stream, never the caller's.  While a stream is capturing, HIP refuses
+// queries of events that were recorded on it earlier (hipErrorCapturedEvent), and other components poll such events from their
+// own threads -- torch's NCCL watchdog does, for the all-gather that follows each batch.  Kernel nodes carry no stream, so the
+// instantiated graph is launched on the caller's stream as usual.  (The legacy null stream can launch a graph but offers nothing
+// else here; it takes the same path.)  One device per process (ovc_device_guard): the stream belongs to the bound device.
+// Caller holds g_graph_mutex; nullptr = no capture support.
 hipStream_t private_capture_stream() {
     static hipStream_t capture_stream = nullptr;
     if (!capture_stream && hipStreamCreateWithFlags(&capture_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1369,6 +1400,45 @@ hipStream_t private_capture_stream() {
         capture_stream = nullptr;
     }
     return capture_stream;
+}
+
+// Capture `issue` on the private stream into (graph, exec); false = capture not available (the caller launches plainly).
+template <typename Issue>
+bool capture_into(hipGraph_t* graph, hipGraphExec_t* exec, const ovc_model* m, Issue issue, const DropPlan* drop = nullptr) {
+    hipStream_t cs = private_capture_stream();
+    if (!cs || hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return false; }
+    Engine ce{m, cs, 0};
+    ce.drop = drop;
+    const int rc = issue(ce);
+    const hipError_t end = hipStreamEndCapture(cs, graph);
+    if (rc != OVC_OK || end != hipSuccess || !*graph || hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (*graph) (void)hipGraphDestroy(*graph);
+        *graph = nullptr; *exec = nullptr;
+        return false;
+    }
+    return true;
+}
+
+// The one replay path of every whole-sequence graph: look `key` up (least-recently-used bookkeeping, the bound shared with the
+// early-exit cache, the entry in use never evicted), capture `body` on the second call of the key, then replay the graph on
+// `stream` -- or issue `body` there plainly: the first call of a key (it warms every kernel's one-off attribute set-up), while
+// profiling (nothing is captured or replayed), or without capture support (sticky per entry).  Everything under g_graph_mutex.
+// `body` takes the Engine to issue on, bound to `drop`; the caller has already issued whatever reads its own inputs.
+template <typename Body>
+int replay_or_issue(const GraphKey& key, hipStream_t stream, const ovc_model* m, Body body, const DropPlan* drop = nullptr) {
+    std::lock_guard<std::mutex> lock(g_graph_mutex);
+    GraphEntry& entry = g_graphs[key];
+    entry.calls += 1;
+    entry.last_use = ++g_graph_tick;
+    entry.last_stream = stream;                 // destroy_entry waits for a replay that may still be running there
+    evict_lru(&key, nullptr);
+    if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec && !capture_into(&entry.graph, &entry.exec, m, body, drop))
+        entry.unsupported = true;
+    if (entry.exec && !g_profile_on) return hipGraphLaunch(entry.exec, stream) == hipSuccess ? OVC_OK : OVC_ELAUNCH;
+    Engine e{m, stream, 0};
+    e.drop = drop;
+    return body(e);
 }
 
 // ovc_beam_search_dropout: the plan of a search with dropout (nullptr everywhere else: the plain search, launch for launch).
@@ -1397,75 +1467,23 @@ int write_search_slots(Engine& e, Workspace& w, SearchDrop* sd, const int32_t* s
 }
 
 int issue_decode_graph_body(Engine& e, Workspace& w, int B, int N, int k, int out_size) {
-    const ovc_model* m = e.m;
-    const int R = B * k, T = m->max_len;
-    TRY(run_encoder_layers(e, w, B, N));
-    TRY(project_cross_kv(e, w, B, N));
-    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
-    OVC_RETURN_IF_LAUNCH_FAILED();
+    const int T = e.m->max_len;
+    TRY(issue_search_prologue(e, w, B, N, k, false));
     for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0));
-    const int fin = T & 1;
-    BeamFinalArgs bf{};
-    bf.running = w.running[fin]; bf.hist = w.hist[fin]; bf.lp = w.lp[fin];
-    bf.k = k; bf.T = T; bf.out_size = out_size; bf.ids_out = w.out_ids; bf.logp_out = w.out_logp; bf.order_out = w.order;
-    return ovc_beam_finalize_launch(bf, B, e.stream);
+    return ovc_beam_finalize_launch(final_args(w, T & 1, k, T, out_size, w.out_ids, w.out_logp), B, e.stream);
 }
-}  // namespace
 
-namespace {
 int beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
                       size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream, SearchDrop* sd) {
-    if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
-    if ((long)m->vocab < k) return OVC_EINVAL;
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
+    Workspace w;
+    Engine e{};
+    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
     const size_t out_n = (size_t)B * out_size * m->max_len;
-
-    const GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
-    std::lock_guard<std::mutex> lock(g_graph_mutex);
-    GraphEntry& entry = g_graphs[key];
-    entry.calls += 1;
-    entry.last_use = ++g_graph_tick;
-    entry.last_stream = e.stream;
-    evict_lru(&key, nullptr);
 
     TRY(bind_search_drop(e, w, sd));
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    // The launch sequence is captured on a PRIVATE stream, never on the caller's: while a stream is capturing, HIP
-    // refuses queries of events that were recorded on it earlier (hipErrorCapturedEvent), and other components poll
-    // such events from their own threads -- torch's NCCL watchdog does, for the all-gather that follows each batch.
-    // Kernel nodes carry no stream, so the instantiated graph is launched on the caller's stream as usual.
-    // (The legacy null stream can launch a graph but offers nothing else here; it takes the same path.)
-    if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec) {
-        hipStream_t capture_stream = private_capture_stream();
-        if (!capture_stream) {
-            entry.unsupported = true;
-        } else if (hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            entry.unsupported = true;
-        } else {
-            Engine ce{m, capture_stream, 0};
-            ce.drop = e.drop;
-            const int rc = issue_decode_graph_body(ce, w, B, N, k, out_size);
-            const hipError_t end = hipStreamEndCapture(capture_stream, &entry.graph);
-            if (rc != OVC_OK || end != hipSuccess || !entry.graph ||
-                hipGraphInstantiate(&entry.exec, entry.graph, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                if (entry.graph) (void)hipGraphDestroy(entry.graph);
-                entry.graph = nullptr; entry.exec = nullptr; entry.unsupported = true;
-            }
-        }
-    }
-    if (entry.exec && !g_profile_on) {
-        if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    } else {
-        // first call of a shape (warms every kernel's one-off attribute set-up), profiling, or no capture support
-        TRY(issue_decode_graph_body(e, w, B, N, k, out_size));
-    }
+    const GraphKey key{GraphKind::Search, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
+    TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_decode_graph_body(ce, w, B, N, k, out_size); }, e.drop));
     if (hipMemcpyAsync(ids_out, w.out_ids, sizeof(int64_t) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     if (hipMemcpyAsync(logp_out, w.out_logp, sizeof(float) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     return write_search_slots(e, w, sd, nullptr, m->max_len, B, k, out_size);
@@ -1489,52 +1507,16 @@ extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, 
 // below -999 (a frozen beam's other candidates, beam_search.py:54).
 // ---------------------------------------------------------------------------------------------
 namespace {
-
-int issue_early_prologue(Engine& e, Workspace& w, int B, int N, int k) {
-    const int R = B * k;
-    TRY(run_encoder_layers(e, w, B, N));
-    TRY(project_cross_kv(e, w, B, N));
-    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    if (hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * e.m->max_len, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    return OVC_OK;
-}
-
-// Capture `issue` on the private stream into (graph, exec); false = capture not available (the caller launches plainly).
-template <typename Issue>
-bool capture_into(hipGraph_t* graph, hipGraphExec_t* exec, const ovc_model* m, Issue issue, const DropPlan* drop = nullptr) {
-    hipStream_t cs = private_capture_stream();
-    if (!cs || hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return false; }
-    Engine ce{m, cs, 0};
-    ce.drop = drop;
-    const int rc = issue(ce);
-    const hipError_t end = hipStreamEndCapture(cs, graph);
-    if (rc != OVC_OK || end != hipSuccess || !*graph || hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        if (*graph) (void)hipGraphDestroy(*graph);
-        *graph = nullptr; *exec = nullptr;
-        return false;
-    }
-    return true;
-}
-}  // namespace
-
-namespace {
 int beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
                       size_t workspace_bytes, int64_t* ids_out, float* logp_out, int* steps_run_out, ovc_stream stream, SearchDrop* sd) {
-    if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
-    if ((long)m->vocab < k) return OVC_EINVAL;
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
+    Workspace w;
+    Engine e{};
+    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
     const int T = m->max_len;
 
     std::shared_ptr<EarlyEntry> entry;
     {
-        const GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
+        const GraphKey key{GraphKind::Search, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         std::shared_ptr<EarlyEntry>& slot = g_early[key];
         if (!slot) slot = std::make_shared<EarlyEntry>();
@@ -1561,11 +1543,11 @@ int beam_search_early(const ovc_model* m, const float* features, const float* bo
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
     if (graphs && !entry->prologue_exec) {
         std::lock_guard<std::mutex> lock(g_graph_mutex);           // the capture stream is shared process-wide
-        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_early_prologue(ce, w, B, N, k); }, e.drop))
+        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_search_prologue(ce, w, B, N, k, true); }, e.drop))
             entry->unsupported = true;
     }
     if (graphs && entry->prologue_exec) { if (hipGraphLaunch(entry->prologue_exec, e.stream) != hipSuccess) return OVC_ELAUNCH; }
-    else TRY(issue_early_prologue(e, w, B, N, k));
+    else TRY(issue_search_prologue(e, w, B, N, k, true));
 
     int steps_run = T;
     for (int t = 0; t < T; ++t) {
@@ -1587,10 +1569,7 @@ int beam_search_early(const ovc_model* m, const float* features, const float* bo
         }
     }
 
-    const int fin = steps_run & 1;
-    BeamFinalArgs bf{};
-    bf.running = w.running[fin]; bf.hist = w.hist[fin]; bf.lp = w.lp[fin];
-    bf.k = k; bf.T = T; bf.out_size = out_size; bf.ids_out = ids_out; bf.logp_out = logp_out; bf.order_out = w.order;
+    BeamFinalArgs bf = final_args(w, steps_run & 1, k, T, out_size, ids_out, logp_out);
     bf.steps_run = steps_run < T ? steps_run : 0;
     TRY(ovc_beam_finalize_launch(bf, B, e.stream));
     if (steps_run_out) *steps_run_out = steps_run;
@@ -1618,60 +1597,27 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
 // ---------------------------------------------------------------------------------------------
 namespace {
 int issue_gated_body(Engine& e, Workspace& w, int B, int N, int k) {
-    const int R = B * k, T = e.m->max_len;
-    TRY(run_encoder_layers(e, w, B, N));
-    TRY(project_cross_kv(e, w, B, N));
-    hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    // this search's counts, in the graph: a count left by the previous replay must never open a gate
-    if (hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * T, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0, true, true));
+    TRY(issue_search_prologue(e, w, B, N, k, true));
+    for (int t = 0; t < e.m->max_len; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0, true, true));
     e.gate = nullptr;
     return OVC_OK;
 }
-}  // namespace
 
-namespace {
 int beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
                       size_t workspace_bytes, int64_t* ids_out, float* logp_out, int32_t* steps_out, ovc_stream stream, SearchDrop* sd) {
-    if (!model_ok(m) || m->precision != 0 || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
-    if ((long)m->vocab < k) return OVC_EINVAL;
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve(m, workspace, B, N, k, 0, sd != nullptr);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
+    if (!model_ok(m) || m->precision != 0) return OVC_EINVAL;
+    Workspace w;
+    Engine e{};
+    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
     const int T = m->max_len;
 
     TRY(bind_search_drop(e, w, sd));
     TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    {
-        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
-        key.kind = 2;
-        std::lock_guard<std::mutex> lock(g_graph_mutex);
-        GraphEntry& entry = g_graphs[key];
-        entry.calls += 1;
-        entry.last_use = ++g_graph_tick;
-        entry.last_stream = e.stream;
-        evict_lru(&key, nullptr);
-        // first call of a shape: plain gated launches; from the second on ONE graph, captured on the private stream as
-        // ovc_beam_search_graph explains
-        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec &&
-            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }, e.drop))
-            entry.unsupported = true;
-        if (entry.exec && !g_profile_on) {
-            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        } else {
-            TRY(issue_gated_body(e, w, B, N, k));
-        }
-    }
+    // first call of a shape: plain gated launches; from the second on ONE graph
+    const GraphKey key{GraphKind::GatedSearch, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
+    TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }, e.drop));
     // the final ordering reads the step count from the device and writes the caller's buffers directly
-    BeamFinalArgs bf[2] = {};
-    for (int i = 0; i < 2; ++i) {
-        bf[i].running = w.running[i]; bf[i].hist = w.hist[i]; bf[i].lp = w.lp[i];
-        bf[i].k = k; bf[i].T = T; bf[i].out_size = out_size; bf[i].ids_out = ids_out; bf[i].logp_out = logp_out; bf[i].order_out = w.order;
-    }
+    const BeamFinalArgs bf[2] = {final_args(w, 0, k, T, out_size, ids_out, logp_out), final_args(w, 1, k, T, out_size, ids_out, logp_out)};
     if (!sd) return ovc_beam_finalize_gated_launch(bf, w.alive_count, steps_out, B, e.stream);
     // the slot table reads the step count the final ordering found: through a workspace word, copied to the caller's afterwards
     TRY(ovc_beam_finalize_gated_launch(bf, w.alive_count, w.steps_dev, B, e.stream));
@@ -1717,26 +1663,9 @@ extern "C" int ovc_forward(const ovc_model* m, const float* features, const floa
     OVC_RETURN_IF_LAUNCH_FAILED();
     if (!use_graph) {
         TRY(issue_forward_body(e, w, B, N, T, want_logp));
-        return finish_forward(e, w, B, T, logp_out, token_logp_out);
-    }
-    {
-        GraphKey key{hash_bytes(m, sizeof(*m)), workspace, B, N, T, want_logp};
-        key.kind = 1;
-        std::lock_guard<std::mutex> lock(g_graph_mutex);
-        GraphEntry& entry = g_graphs[key];
-        entry.calls += 1;
-        entry.last_use = ++g_graph_tick;
-        entry.last_stream = e.stream;
-        evict_lru(&key, nullptr);
-        // captured on the private stream, as the search (ovc_beam_search_graph) explains
-        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec &&
-            !capture_into(&entry.graph, &entry.exec, m, [&](Engine& ce) { return issue_forward_body(ce, w, B, N, T, want_logp); }))
-            entry.unsupported = true;
-        if (entry.exec && !g_profile_on) {
-            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        } else {
-            TRY(issue_forward_body(e, w, B, N, T, want_logp));
-        }
+    } else {
+        const GraphKey key{GraphKind::Forward, hash_bytes(m, sizeof(*m)), workspace, B, N, T, want_logp};
+        TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_forward_body(ce, w, B, N, T, want_logp); }));
     }
     return finish_forward(e, w, B, T, logp_out, token_logp_out);
 }
@@ -2320,6 +2249,53 @@ extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, in
 
 namespace {
 
+// The per-site constants of a caller's table; OVC_EINVAL for a p outside [0, 1) (NaN included).  *any: a site is active.
+int make_drop_plan(const ovc_dropout* dropout, DropPlan* plan, uint64_t* hash, bool* any) {
+    float p[OVC_DROPOUT_SITES] = {};
+    p[kSiteEmb] = dropout->emb;
+    for (int l = 0; l < OVC_MAX_LAYERS; ++l) {
+        for (int j = 0; j < 3; ++j) p[enc_site(l, j)] = dropout->enc[l][j];
+        for (int j = 0; j < 4; ++j) p[dec_site(l, j)] = dropout->dec[l][j];
+    }
+    *any = false;
+    for (int i = 0; i < OVC_DROPOUT_SITES; ++i) {
+        if (!(p[i] >= 0.f && p[i] < 1.f)) return OVC_EINVAL;
+        plan->on[i] = p[i] > 0.f;
+        plan->thr[i] = ovc_dropout_threshold(p[i]);
+        plan->scale[i] = ovc_dropout_scale(p[i]);
+        *any = *any || plan->on[i];
+    }
+    *hash = hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full;
+    return OVC_OK;
+}
+
+// Binds a training call's Engine to its dropout plan: the seed slot is refreshed here, outside the captured body -- a replayed
+// graph reads this call's seed.
+int bind_train_drop(Engine& e, TrainWs& t, DropPlan* drop, const int64_t* seed) {
+    if (!drop) return OVC_OK;
+    if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    drop->seed = t.seed;
+    e.drop = drop;
+    return OVC_OK;
+}
+
+// The staging that reads the caller's (or seq_inputs_kernel's) tokens / targets and features, outside the captured body: the
+// decoder's inputs, the token rows and the transposed features of the embedding gradients.
+int stage_train_inputs(Engine& e, TrainWs& t, const float* features, const int64_t* tokens, const int64_t* targets, int rows, int T,
+                       int BN) {
+    const ovc_model* m = e.m;
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
+                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    TRY(ovc_bw_tokens(tokens, rows, m->vocab, t.tok, e.stream));
+    return ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream);
+}
+
+// The body writes the gradient buffers: their table is part of the key, next to the model's contents.
+uint64_t train_hash(const ovc_model* m, const ovc_model* grads) {
+    return hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull);
+}
+
 // ovc_forward_backward (drop == nullptr) and ovc_forward_backward_dropout (drop: at least one site active; seed = the caller's)
 int forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, const int64_t* tokens,
                      const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* loss_out, int use_graph,
@@ -2332,46 +2308,18 @@ int forward_backward(const ovc_model* m, const ovc_model* grads, const float* fe
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
-    const int rows = B * T, BN = B * N;
-    if (drop) {
-        // the seed slot is refreshed here, outside the captured body: a replayed graph reads this call's seed
-        if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        drop->seed = t.seed;
-        e.drop = drop;
-    }
+    TRY(bind_train_drop(e, t, drop, seed));
 
     // the kernels that read the caller's inputs, outside the captured body
     TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
-    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
-                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    TRY(ovc_bw_tokens(tokens, rows, m->vocab, t.tok, e.stream));
-    TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
-    auto body = [&](Engine& ce) {
-        ce.drop = drop;
-        return issue_train_body(ce, t, grads, B, N, T);
-    };
+    TRY(stage_train_inputs(e, t, features, tokens, targets, B * T, T, B * N));
+    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T); };
     if (!use_graph) {
         TRY(body(e));
     } else {
-        // the body writes the gradient buffers: their table is part of the key; so are the dropout constants (baked into the
-        // launches), never the seed (read from the workspace slot)
-        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ drop_hash, workspace, B,
-                     N, T, 0};
-        key.kind = drop ? 4 : 3;
-        std::lock_guard<std::mutex> lock(g_graph_mutex);
-        GraphEntry& entry = g_graphs[key];
-        entry.calls += 1;
-        entry.last_use = ++g_graph_tick;
-        entry.last_stream = e.stream;
-        evict_lru(&key, nullptr);
-        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec && !capture_into(&entry.graph, &entry.exec, m, body))
-            entry.unsupported = true;
-        if (entry.exec && !g_profile_on) {
-            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        } else {
-            TRY(body(e));
-        }
+        // the dropout constants are baked into the launches, so they are part of the key; never the seed (read from the workspace slot)
+        const GraphKey key{drop ? GraphKind::TrainDropout : GraphKind::Train, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, 0};
+        TRY(replay_or_issue(key, e.stream, m, body, drop));
     }
     if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     return OVC_OK;
@@ -2398,26 +2346,15 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                             const ovc_dropout* dropout) {
     (void)boxes;
     if (!dropout || !dropout->seed || !m || !dropout_train_ok(m, B, N, T)) return OVC_EINVAL;
-    float p[OVC_DROPOUT_SITES] = {};
-    p[kSiteEmb] = dropout->emb;
-    for (int l = 0; l < OVC_MAX_LAYERS; ++l) {
-        for (int j = 0; j < 3; ++j) p[enc_site(l, j)] = dropout->enc[l][j];
-        for (int j = 0; j < 4; ++j) p[dec_site(l, j)] = dropout->dec[l][j];
-    }
     DropPlan plan{};
+    uint64_t hash = 0;
     bool any = false;
-    for (int i = 0; i < OVC_DROPOUT_SITES; ++i) {
-        if (!(p[i] >= 0.f && p[i] < 1.f)) return OVC_EINVAL;         // NaN included
-        plan.on[i] = p[i] > 0.f;
-        plan.thr[i] = ovc_dropout_threshold(p[i]);
-        plan.scale[i] = ovc_dropout_scale(p[i]);
-        any = any || plan.on[i];
-    }
+    TRY(make_drop_plan(dropout, &plan, &hash, &any));
     if (!any)
         return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
                                 nullptr, nullptr, 0);
     return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
-                            &plan, dropout->seed, hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full);
+                            &plan, dropout->seed, hash);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2457,14 +2394,12 @@ int sequence_backward(const ovc_model* m, const ovc_model* grads, const float* f
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
-    const int nseq = B * S, rows = nseq * T, BN = B * N;
+    const int nseq = B * S, rows = nseq * T;
+    TRY(bind_train_drop(e, t, drop, seed));
     if (drop) {
-        // the seed slot and the row table are refreshed here, outside the captured body
-        if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        // the row table is refreshed here as well, outside the captured body
         hipLaunchKernelGGL(seq_maskrow_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, slots, B, S, T, k, t.maskrow);
         OVC_RETURN_IF_LAUNCH_FAILED();
-        drop->seed = t.seed;
-        e.drop = drop;
         e.maskrow = t.maskrow;
     }
 
@@ -2473,60 +2408,22 @@ int sequence_backward(const ovc_model* m, const ovc_model* grads, const float* f
     hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, ids, grad_logp, nseq, T, m->bos_idx, m->eos_idx,
                        t.seq_tok, t.seq_tgt, t.seq_keep, t.w_row);
     OVC_RETURN_IF_LAUNCH_FAILED();
-    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, t.seq_tok, t.seq_tgt, m->vocab, m->pad_idx, T,
-                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    TRY(ovc_bw_tokens(t.seq_tok, rows, m->vocab, t.tok, e.stream));
-    TRY(ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream));
+    TRY(stage_train_inputs(e, t, features, t.seq_tok, t.seq_tgt, rows, T, B * N));
     auto body = [&](Engine& ce) {
-        ce.drop = drop;
         ce.maskrow = drop ? t.maskrow : nullptr;
         return issue_train_body(ce, t, grads, B, N, T, S, true);
     };
     if (!use_graph) {
         TRY(body(e));
     } else {
-        GraphKey key{hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ drop_hash, workspace, B, N, T, S};
-        key.kind = 5;
-        std::lock_guard<std::mutex> lock(g_graph_mutex);
-        GraphEntry& entry = g_graphs[key];
-        entry.calls += 1;
-        entry.last_use = ++g_graph_tick;
-        entry.last_stream = e.stream;
-        evict_lru(&key, nullptr);
-        if (!entry.unsupported && !g_profile_on && entry.calls > 1 && !entry.exec && !capture_into(&entry.graph, &entry.exec, m, body))
-            entry.unsupported = true;
-        if (entry.exec && !g_profile_on) {
-            if (hipGraphLaunch(entry.exec, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        } else {
-            TRY(body(e));
-        }
+        const GraphKey key{GraphKind::SequenceBackward, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, S};
+        TRY(replay_or_issue(key, e.stream, m, body, drop));
     }
     if (logp_out) {
         hipLaunchKernelGGL(seq_logp_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, t.w.logits, (long)pad4(rows), t.w.lse,
                            t.w.tgt, t.seq_keep, rows, logp_out);
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
-    return OVC_OK;
-}
-
-// The per-site constants of a caller's table; OVC_EINVAL for a p outside [0, 1) (NaN included).  *any: a site is active.
-int make_drop_plan(const ovc_dropout* dropout, DropPlan* plan, uint64_t* hash, bool* any) {
-    float p[OVC_DROPOUT_SITES] = {};
-    p[kSiteEmb] = dropout->emb;
-    for (int l = 0; l < OVC_MAX_LAYERS; ++l) {
-        for (int j = 0; j < 3; ++j) p[enc_site(l, j)] = dropout->enc[l][j];
-        for (int j = 0; j < 4; ++j) p[dec_site(l, j)] = dropout->dec[l][j];
-    }
-    *any = false;
-    for (int i = 0; i < OVC_DROPOUT_SITES; ++i) {
-        if (!(p[i] >= 0.f && p[i] < 1.f)) return OVC_EINVAL;
-        plan->on[i] = p[i] > 0.f;
-        plan->thr[i] = ovc_dropout_threshold(p[i]);
-        plan->scale[i] = ovc_dropout_scale(p[i]);
-        *any = *any || plan->on[i];
-    }
-    *hash = hash_bytes(p, sizeof(p)) * 0xC2B2AE3D27D4EB4Full;
     return OVC_OK;
 }
 }  // namespace

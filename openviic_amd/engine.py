@@ -540,6 +540,27 @@ class CaptionEngine:
             raise native.OvcError("dropout: the seed must be a one-element int64 device tensor")
         return _dropout.native_table(probs, seed)
 
+    def _search_inputs(self, features, boxes, batch_size, beam_size):
+        """The preamble of every search: the inputs checked and bucketed, the batch size verified, the derived weights refreshed
+        and the GEMM tilings chosen.  Returns ``(features, boxes, B, N)``."""
+        features, boxes = self._checked_inputs(features, boxes)
+        features, boxes = self._bucketed(features, boxes)
+        B, N = features.shape[:2]
+        if B != batch_size:
+            raise native.OvcError("batch_size={} but features hold {} images".format(batch_size, B))
+        self._refresh_derived()
+        if self.autotune:
+            self.tune(B, N, beam_size)
+        return features, boxes, B, N
+
+    def _steps_tensor(self):
+        """The one-element int32 device tensor a gated search writes its step count to: one per stream, as the workspaces."""
+        key = torch.cuda.current_stream().cuda_stream
+        steps = self._steps_device.get(key)
+        if steps is None:
+            steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return steps
+
     def _beam_search_dropout(self, features, boxes, batch_size, beam_size, out_size, early, table_drop):
         """``ovc_beam_search_dropout``: the search with every site of ``table_drop`` applied, in the form ``early`` selects.
         Returns ``(ids, logp, slots)`` with ``slots`` ``(B, out_size, T)`` int32: the beam slot each returned beam's ancestor held
@@ -548,16 +569,9 @@ class CaptionEngine:
         if self.desc.enc_kind != native.ENC_PLAIN:
             raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer (with or without "
                                   "encoder memory slots) only")
-        features, boxes = self._checked_inputs(features, boxes)
-        features, boxes = self._bucketed(features, boxes)
-        B, N = features.shape[:2]
-        if B != batch_size:
-            raise native.OvcError("batch_size={} but features hold {} images".format(batch_size, B))
-        self._refresh_derived()
+        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, beam_size)
         d = self.desc
         T = d.max_len
-        if self.autotune:
-            self.tune(B, N, beam_size)
         need = self.lib.ovc_beam_search_dropout_workspace_bytes(ctypes.byref(d), B, N, beam_size)
         if need == 0:
             raise native.OvcError("unsupported configuration for a search with dropout (B={}, N={}, beam={}; see "
@@ -569,11 +583,7 @@ class CaptionEngine:
         mode = 2 if early == "device" else (1 if early else 0)
         steps = None
         if mode == 2:
-            key = torch.cuda.current_stream().cuda_stream
-            steps = self._steps_device.get(key)
-            if steps is None:
-                steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.last_steps_device = steps
+            steps = self.last_steps_device = self._steps_tensor()
         if not self.use_graph:           # OVC_GRAPH=0: every call is the first of its shape (plain launches)
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self.last_steps_run = T
@@ -606,26 +616,16 @@ class CaptionEngine:
             return ids.reshape(batch_size, out_size, -1), logp.reshape(batch_size, out_size, -1), None
         if early == "device" and self.precision != "f32":
             raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
-        features, boxes = self._checked_inputs(features, boxes)
-        features, boxes = self._bucketed(features, boxes)
-        B, N = features.shape[:2]
-        if B != batch_size:
-            raise native.OvcError("batch_size={} but features hold {} images".format(batch_size, B))
-        self._refresh_derived()
+        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, beam_size)
         d = self.desc
         T, V = d.max_len, d.vocab
-        if self.autotune:
-            self.tune(B, N, beam_size)
         ws, need = self._get_workspace(B, N, beam_size, return_probs)
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         everything = torch.empty(B, beam_size, T, V, dtype=torch.float32, device=self.device) if return_probs else None
         self.last_steps_run = T
         if early == "device" and not return_probs:
-            key = torch.cuda.current_stream().cuda_stream
-            steps = self._steps_device.get(key)
-            if steps is None:
-                steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            steps = self._steps_tensor()
             if not self.use_graph:       # OVC_GRAPH=0: every call is the first of its shape (plain gated launches)
                 self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
             check(self.lib.ovc_beam_search_gated(ctypes.byref(d), features.data_ptr(),
@@ -718,16 +718,7 @@ class CaptionEngine:
         if tuple(targets.shape) != tuple(caption_tokens.shape):
             raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
                 tuple(targets.shape), tuple(caption_tokens.shape)))
-        table_drop = None
-        if dropout is not None:
-            probs, seed = dropout
-            for site, p in probs.items():
-                if not 0 <= site < _dropout.NUM_SITES or not 0 <= p < 1:
-                    raise native.OvcError("dropout: site {} p = {} (sites 0..{}, 0 <= p < 1)".format(site, p, _dropout.NUM_SITES - 1))
-            if any(p > 0 for p in probs.values()):
-                if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
-                    raise native.OvcError("dropout: the seed must be a one-element int64 device tensor")
-                table_drop = _dropout.native_table(probs, seed)
+        table_drop = self._dropout_table(dropout) if dropout is not None else None
         sizer = self.lib.ovc_train_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_workspace_bytes
         need = sizer(ctypes.byref(d), B, N, T)
         if need == 0:

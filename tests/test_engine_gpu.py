@@ -559,6 +559,46 @@ def test_hipgraph_replay_matches_plain_launches():
     assert torch.equal(got[0][0], got[3][0])
 
 
+def test_graph_kinds_do_not_collide():
+    """The whole-search graph and the gated search's graph of ONE (model, workspace, B, N, k, out_size) differ in their key's kind
+    only.  Called alternately on the same workspace and stream -- plain, capture, replay, three calls each -- both must keep
+    returning ovc_beam_search's bits (a shared entry would replay the other search's graph: other output buffers, other final
+    ordering), and the cache must hold exactly the two entries.  B = 2, N = 5 with a padded trailing region, k = 2, out_size = 2:
+    the smallest case whose captured body has several steps, two beams and a masked key."""
+    import ctypes
+    from openviic_amd import native
+    from openviic_amd.utils.synthetic import synthetic_features
+    lib = native.load()
+    cfg, vocab, sd, _, _ = tiny_case("standard_transformer")
+    model = device_model(cfg, vocab, sd)
+    eng = model._fused_engine()
+    B, N, k, out_size, T = 2, 5, 2, 2, TINY_SHAPE["T"]
+    feats = synthetic_features(B, N, TINY["d_feature"], seed=47)
+    feats[1, N - 1] = 0                                                   # ragged: image 1's last region is padding
+    feats = feats.cuda().contiguous()
+    desc = ctypes.byref(eng.desc)
+    need = lib.ovc_workspace_bytes(desc, B, N, k, 0)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    steps = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def run(call, *extra):
+        ids = torch.empty(B, out_size, T, dtype=torch.int64, device="cuda")
+        logp = torch.empty(B, out_size, T, dtype=torch.float32, device="cuda")
+        rc = call(desc, feats.data_ptr(), None, B, N, k, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(), *extra,
+                  native.stream_handle())
+        assert rc == 0, rc
+        return ids, logp
+
+    assert lib.ovc_graph_cache_clear() == 0
+    want_ids, want_logp = run(lib.ovc_beam_search, None)
+    for call in range(3):
+        for name, got in (("graph", run(lib.ovc_beam_search_graph)), ("gated", run(lib.ovc_beam_search_gated, steps.data_ptr()))):
+            assert torch.equal(got[0], want_ids) and torch.equal(got[1], want_logp), (name, call)
+    assert lib.ovc_graph_cache_size() == 2
+    lib.ovc_graph_cache_drop_workspace(ws.data_ptr())                     # the graphs reference ws: dropped before it is freed
+
+
 # ---- edges of the domain -----------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("B,N,k,out_size", [(1, 1, 1, 1), (1, 7, 8, 8), (2, 3, 2, 2), (5, 7, 4, 1), (3, 7, 5, 3)])

@@ -523,6 +523,25 @@ long ovc_adam_chunk_fill(const int64_t* counts, int n_tensors, ovc_adam_chunk* c
 int ovc_adam_step(const ovc_adam_tensor* table, int n_tensors, const ovc_adam_chunk* chunks, long n_chunks, double lr, double beta1,
                   double beta2, double eps, long step, const float* grad_scale, ovc_stream stream);
 
+/* The self-critical baseline, advantage and loss gradient: what the reference's train_scst (vi_trainer.py:121-158) computes
+ * between the search and loss.backward().  Appended to ABI 8.  reward [B][S] and logp [B][S][T] are fp32 device arrays (the
+ * search's out_size = S beams per image), 1 <= S <= OVC_MAX_BEAM, 1 <= T <= OVC_MAX_LEN, B >= 1, B*S*T < 2^31.
+ *   rsum[b] = ((r[b,0] + r[b,1]) + ...) + r[b,S-1]   and   a64[b,s] = r[b,s] - rsum[b] / S        in float64 from the fp32 rewards
+ *   a[b,s]  = float(a64[b,s])                                  the advantage, rounded to fp32 once: exactly 0 for equal rewards
+ *   grad_logp[b,s,t] = (-a[b,s] / float(B*S)) / float(T)       in fp32, for every t: the outer mean's scaling, then the inner mean's
+ * (no contraction, the divisions correctly rounded): the gradient of loss = mean_{b,s}(-mean_t(logp[b,s,:]) * a[b,s]) with respect
+ * to logp.  stats[0] = that loss, stats[1] = mean_{b,s} r, stats[2] = mean_b rsum[b] / S, stats[3] = 0: float64 sums in a fixed
+ * order, rounded to fp32 once.  A pair's loss term is -(sum_t logp[b,s,t] / T) * a64[b,s], its T log-probabilities summed ascending;
+ * terms, rewards and baselines are summed ascending inside an image, then the images ascending in chunks of 64, then the chunks
+ * ascending.
+ * scratch: ovc_scst_advantage_bytes(B, S, T) bytes of device memory, 8-byte aligned (0: the shape is refused); contents need no
+ * initialisation.  One launch for B <= 64, two otherwise; no atomics, plain vector stores (16 bytes wide where T % 4 == 0 and the
+ * arrays are 16-byte aligned), no allocation, no synchronisation, capturable: the same bits on every call, stream and replay.
+ * OVC_EINVAL (nothing launched): a null pointer, a shape outside the limits, a misaligned scratch; OVC_EWORKSPACE: scratch too small. */
+size_t ovc_scst_advantage_bytes(int B, int S, int T);
+int ovc_scst_advantage(const float* reward, const float* logp, int B, int S, int T, float* grad_logp, float* stats, void* scratch,
+                       size_t scratch_bytes, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

@@ -11,6 +11,8 @@ API kept: ``forward(input_features, fused=False) -> log-probs (B,T,V)`` (``fused
 (``csrc/engine.hip``) which runs encoder, every decode step and the beam bookkeeping on the
 device without host round trips.  It needs the HIP library and a GPU; there is no CPU fallback.
 """
+import collections
+
 import torch
 
 from . import dropout as _dropout
@@ -23,6 +25,12 @@ from .modules.beam_search import BeamSearch
 from .modules.containers import Module
 from .modules.decoders import Decoder
 from .modules.encoders import CrossAttentionMultiLevelEncoder, Encoder
+
+
+ScstStep = collections.namedtuple("ScstStep", ["loss", "reward_mean", "baseline_mean", "outs", "reward"])
+ScstStep.__doc__ = """What ``BaseTransformer.scst_step`` returns: detached device tensors.  ``loss``, ``reward_mean`` and
+``baseline_mean`` are 0-dim views of one ``stats`` tensor (``openviic_amd.scst.advantage``), ``outs`` ``[B, k, T]`` int64 the
+search's sequences, ``reward`` ``[B, k]`` float32 their rewards."""
 
 
 class _XeLoss(torch.autograd.Function):
@@ -234,6 +242,95 @@ class BaseTransformer(Module):
                                               input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots)
         optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad})
         return loss
+
+    def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None):
+        """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
+        autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
+        advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
+        that arena in place.  Returns a ``ScstStep`` ``(loss, reward_mean, baseline_mean, outs, reward)`` of detached device
+        tensors.  It stands for ::
+
+            outs, log_probs = model.beam_search(items, B, k, out_size=k, dropout=dropout, generator=generator)
+            optimizer.zero_grad(); r = reward(outs); g, _ = scst.advantage(r, log_probs.detach()); log_probs.backward(g)
+            optimizer.step()
+
+        and leaves the same parameter and optimizer-state bits as those lines.  ``reward`` is a ``CiderCorpus`` on the model's
+        device -- the reward is then ``reward.reward(outs, rows)`` with ``rows`` an int32 device tensor ``[B]``, by default
+        ``reward.rows(input_features["captions"])`` -- or a callable ``outs [B, k, T] int64 -> [B, k] float32`` device tensor.
+        ``optimizer`` is an ``openviic_amd.optim.Adam`` that holds exactly the engine's trainable ``gradient_parameters()``, as
+        for ``xe_step``.  ``dropout`` / ``generator``: as ``beam_search(dropout=...)``: the search runs under the masks of one
+        seed and the backward recomputes under the same masks.  ``early_exit`` selects the search form; every form gives the
+        same bits.
+
+        Refused before any launch and any random draw: what ``xe_step`` and the SCST search refuse -- the optimizer's type and
+        parameter set, a model the backward does not cover, a ``train()``-mode model with live dropout and ``dropout=False``,
+        the scope of ``beam_search(dropout=True)``, a precision other than 'f32' -- and a corpus on another device, or ``rows``
+        of the wrong shape, dtype or device.  What a callable returns is checked as soon as it exists, after the search and
+        before anything else is launched: parameters and optimizer state are untouched (under live dropout the seed has been
+        drawn by then).
+
+        ``p.grad`` is neither read nor written, and autograd is not involved (the call works under ``torch.no_grad()``): gradient
+        hooks do NOT fire -- ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them
+        DistributedDataParallel's gradient all-reduce.  A data-parallel run keeps the lines above."""
+        from . import optim as _optim
+        from . import scst as _scst
+        from .cider import CiderCorpus
+        if not isinstance(optimizer, _optim.Adam):
+            raise engine.native.OvcError("scst_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
+                type(optimizer).__name__))
+        corpus = reward if isinstance(reward, CiderCorpus) else None
+        if corpus is None and not callable(reward):
+            raise engine.native.OvcError("scst_step: reward must be a CiderCorpus or a callable outs -> [B, k] float32 (got {})"
+                                         .format(type(reward).__name__))
+        k = int(beam_size)
+        if not 1 <= k <= engine.native.OVC_MAX_BEAM:
+            raise engine.native.OvcError("scst_step: 1 <= beam_size <= {} expected, got {}".format(engine.native.OVC_MAX_BEAM, k))
+        probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
+        eng = self._fused_engine()
+        eng._check_trainable()
+        wanted = [p for p in eng.gradient_parameters() if p.requires_grad]
+        held = {id(p) for group in optimizer.param_groups for p in group["params"] if p.requires_grad}
+        if held != {id(p) for p in wanted}:
+            raise engine.native.OvcError(
+                "scst_step: optimizer must hold exactly the model's trainable parameters ({} of them); it holds {} trainable "
+                "parameters, {} of them the model's".format(len(wanted), len(held), len(held & {id(p) for p in wanted})))
+        boxes = input_features["region_boxes"] if self.uses_boxes else None
+        feats, boxes = eng._checked_inputs(input_features[self.feature_field], boxes)
+        B = feats.shape[0]
+        if corpus is not None:
+            if corpus.device != eng.device or corpus._struct is None:
+                raise engine.native.OvcError("scst_step: the reward corpus is on {}, the model on {} -- move the corpus with "
+                                             ".to(device) once".format(corpus.device, eng.device))
+            if rows is None:
+                rows = corpus.rows(input_features["captions"])
+            if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or tuple(rows.shape) != (B,) or
+                    rows.device != eng.device or not rows.is_contiguous()):
+                raise engine.native.OvcError("scst_step: rows must be a contiguous int32 [{}] tensor on {}, got {}".format(
+                    B, eng.device, "{} {} on {}".format(rows.dtype, tuple(rows.shape), rows.device)
+                    if isinstance(rows, torch.Tensor) else type(rows).__name__))
+        drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
+        if drop is not None:
+            outs, log_probs, slots = eng.beam_search(feats, None, B, k, out_size=k, early_exit=early_exit, dropout=drop)
+        else:
+            outs, log_probs = eng.beam_search(feats, boxes, B, k, out_size=k, early_exit=early_exit)
+            outs, log_probs, slots = outs.reshape(B, k, -1), log_probs.reshape(B, k, -1), None
+        if corpus is not None:
+            r = corpus.reward(outs, rows)
+        else:
+            r = reward(outs)
+            if (not isinstance(r, torch.Tensor) or r.dtype != torch.float32 or tuple(r.shape) != (B, k) or
+                    r.device != eng.device):
+                raise engine.native.OvcError("scst_step: the reward callable must return a float32 [{}, {}] tensor on {}, got {}"
+                                             .format(B, k, eng.device, "{} {} on {}".format(r.dtype, tuple(r.shape), r.device)
+                                                     if isinstance(r, torch.Tensor) else type(r).__name__))
+            r = r.detach().contiguous()
+        g, stats = _scst.advantage(r, log_probs)
+        if drop is not None:
+            _, grads = eng.sequence_backward(feats, None, outs, g, dropout=drop, slots=slots, beam_size=k, arena=eng.step_arena())
+        else:
+            _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena())
+        optimizer.apply_gradients({p: gr for p, gr in zip(eng.gradient_parameters(), grads) if p.requires_grad})
+        return ScstStep(stats[0], stats[1], stats[2], outs, r)
 
     def _search_dropout_probs(self):
         """``{site: p}`` for ``beam_search(dropout=True)``, or the refusals of its scope: before any launch and any draw."""

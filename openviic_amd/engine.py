@@ -768,7 +768,7 @@ class CaptionEngine:
         return self._step_arenas[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
-                          beam_size=None):
+                          beam_size=None, arena=None):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -779,7 +779,10 @@ class CaptionEngine:
         caller (``BaseTransformer.beam_search``) checks it.
 
         ``dropout=(probs, seed)`` with ``slots`` (the search's table) and ``beam_size`` (its k): the recompute runs under the
-        masks ``beam_search(dropout=...)`` used (``ovc_sequence_backward_dropout``)."""
+        masks ``beam_search(dropout=...)`` used (``ovc_sequence_backward_dropout``).
+
+        ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer, as ``forward_backward`` takes it
+        (``BaseTransformer.scst_step``); the returned ``arena`` and ``grads`` are then that arena's."""
         self._check_trainable()
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         if table_drop is not None:
@@ -811,7 +814,7 @@ class CaptionEngine:
         self._check_pointers()
         self._refresh_derived()
         d = self.desc
-        arena, table, grads = self._gradient_arena()
+        arena, table, grads = self._gradient_arena() if arena is None else arena
         stream = torch.cuda.current_stream().cuda_stream
         ws = self._cached_workspace(self._seq_workspaces, (stream, S), need)
         logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device) if want_logp else None

@@ -14,6 +14,12 @@ regions, dropout 0.  The weights are EOS-biased (``eos_biased_state_dict``) so c
 alternating in one process; the whole step and the optimizer step from device events, medians and spread of ``--steps`` each, and
 the 28 bytes per element the optimizer step must move over its time against the 6.29 TB/s of a float4 copy on this chip.
 
+``--fused`` (with ``--reward device --optimizer engine``): ``model.scst_step`` -- search, ``CiderCorpus.reward``, ``ovc_scst_advantage``,
+``ovc_sequence_backward`` into the step arena, ``ovc_adam_step`` -- against the lines it stands for (the search with autograd, the
+reward, ``scst.advantage``, ``log_probs.backward(g)``, ``zero_grad`` / ``step()``), each form on its own copy of the model,
+alternating in one process for ``--rounds`` rounds; a whole step is wall clock from before the call to a synchronise after it,
+``rows`` precomputed; medians and spread of ``--steps`` per round, and ``scst.advantage`` alone from device events.
+
 ``--dropout``: steps with every ``nn.Dropout`` at 0.1 (a new seed per step, ``ovc_beam_search_dropout`` /
 ``ovc_sequence_backward_dropout``) and steps of the same build with every p = 0 alternate in one process; search and backward
 from device events, medians and spread of ``--steps`` each, and the ratios.
@@ -228,6 +234,65 @@ def optimizer_probe(args, build, N, D, k):
     return results
 
 
+def fused_probe(args, build, V, T, N, D, k):
+    """``scst_step`` against the lines it stands for, alternating (module docstring)."""
+    from openviic_amd import scst
+    from openviic_amd.cider import CiderCorpus
+    from openviic_amd.optim import Adam
+    from openviic_amd.vocab import WordVocab
+    words = WordVocab(["<pad>", "<bos>", "<eos>", "<unk>"] + ["w%d" % i for i in range(V - 4)], T)
+    captions = synthetic_corpus(max(args.corpus_images, max(args.batches)), V)
+    corpus = CiderCorpus(words, captions, captions).to("cuda")
+    forms = {}
+    for kind in ("lines", "fused"):
+        model = build()
+        params = [p for p in model.parameters() if p.requires_grad]
+        forms[kind] = (model, Adam(params, lr=5e-6))
+    results = []
+    for B in args.batches:
+        items = InstanceList()
+        items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        rows = corpus.rows(captions[:B])
+
+        def step(kind):
+            model, opt = forms[kind]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == "fused":
+                model.scst_step(items, opt, corpus, k, rows=rows)
+            else:
+                outs, log_probs = model.beam_search(items, batch_size=B, beam_size=k, out_size=k)
+                opt.zero_grad()
+                reward = corpus.reward(outs, rows)
+                g, _ = scst.advantage(reward, log_probs.detach())
+                log_probs.backward(g)
+                opt.step()
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0)
+
+        rounds = []
+        for _ in range(args.rounds):
+            runs = {"lines": [], "fused": []}
+            for i in range(args.warmup + args.steps):
+                for kind in ("lines", "fused"):
+                    ms = step(kind)
+                    if i >= args.warmup:
+                        runs[kind].append(ms)
+            rounds.append({kind: spread(v) for kind, v in runs.items()})
+        same = all(torch.equal(a, b) for a, b in zip(forms["lines"][0].parameters(), forms["fused"][0].parameters()))
+        reward = torch.rand(B, k, device="cuda")
+        logp = -torch.rand(B, k, T, device="cuda")
+        alone = [timed(lambda: scst.advantage(reward, logp))[0] for _ in range(args.warmup + args.steps)][args.warmup:]
+        r = {"variant": args.variant, "B": B, "k": k, "T": T, "N": N, "rounds": rounds, "parameters_equal_bit_for_bit": same,
+             "lines_ms": statistics.median(x["lines"]["median"] for x in rounds),
+             "fused_ms": statistics.median(x["fused"]["median"] for x in rounds),
+             "advantage_ms_device_events": spread(alone)}
+        r["fused_over_lines"] = r["fused_ms"] / r["lines_ms"]
+        results.append(r)
+        print(json.dumps(r))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[60, 256])
@@ -244,8 +309,13 @@ def main():
     ap.add_argument("--dropout", action="store_true", help="steps under dropout (p = 0.1 everywhere) against p = 0, alternating")
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine"],
                     help="none: search and backward only; torch / engine: the whole step with optimizer.step() (they alternate)")
+    ap.add_argument("--fused", action="store_true",
+                    help="model.scst_step against the lines it stands for, alternating (needs --reward device --optimizer engine)")
+    ap.add_argument("--rounds", type=int, default=2, help="--fused: alternating rounds of --warmup + --steps steps per form")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.fused and (args.reward != "device" or args.optimizer != ["engine"]):
+        ap.error("--fused needs --reward device --optimizer engine")
     if "none" in args.optimizer and len(args.optimizer) > 1:
         ap.error("--optimizer none stands alone")
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -270,10 +340,12 @@ def main():
         dims.update(he=1, tail=True)
     if args.variant == "augmented_memory_transformer":
         dims.update(memory=40)
-    results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" else []
+    results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" and not args.fused else []
+    if args.fused:
+        results = fused_probe(args, build, V, T, N, D, k)
     if args.dropout:
         results = dropout_probe(args, model, N, D, k)
-    if args.optimizer != ["none"]:
+    if args.optimizer != ["none"] and not args.fused:
         results = optimizer_probe(args, build, N, D, k)
     for B in args.batches if args.reward == "none" and not args.dropout and args.optimizer == ["none"] else []:
         feats = synthetic_features(B, N, D, seed=0, ragged=True).cuda()

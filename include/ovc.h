@@ -542,6 +542,56 @@ size_t ovc_scst_advantage_bytes(int B, int S, int T);
 int ovc_scst_advantage(const float* reward, const float* logp, int B, int S, int T, float* grad_logp, float* stats, void* scratch,
                        size_t scratch_bytes, ovc_stream stream);
 
+/* The evaluation metrics' integer statistics: BLEU-1..4 counts and ROUGE-L LCS lengths of generated captions against a fixed
+ * reference corpus, from token ids (the reference's evaluate_metrics decodes to strings on the host and runs
+ * evaluation/bleu/bleu_scorer.py and evaluation/rouge/rouge.py there: vi_trainer.py:78-98).  Appended to ABI 8.  The tables are
+ * built once on the host (openviic_amd/metrics.py); n-gram keys are packed as for ovc_cider.
+ *   image_ref  [n_images + 1]   image -> its references (CSR), the same array as ovc_cider's
+ *   image_gram [n_images + 1]   image -> its BLEU entries (CSR);  gram_key / gram_max: the union of the references' 1..4-grams,
+ *                               ascending by key, with the maximum count over the references (n-grams holding a word no hypothesis
+ *                               can contain have no entry)
+ *   ref_words  [n_refs]         len(ref.split()), BLEU's reference lengths
+ *   ref_token  [n_refs + 1]     reference -> its ROUGE-L tokens (CSR), ref.split(" ");  token_code: id + 1 of a word a hypothesis
+ *                               can contain, 0 for any other word (it counts in the length and never matches), pad_idx + 1 for the
+ *                               EMPTY token that split(" ") makes of a double space -- it matches only the one token of an empty
+ *                               hypothesis ("".split(" ") == [""])
+ *   max_refs                    the largest number of references of one image (>= 0, <= OVC_METRIC_MAX_REFS) */
+#define OVC_METRIC_STATS    12
+#define OVC_METRIC_MAX_REFS 4096
+typedef struct {
+    const int32_t*  image_ref;
+    const int32_t*  image_gram;
+    const uint64_t* gram_key;
+    const int32_t*  gram_max;
+    const int32_t*  ref_words;
+    const int32_t*  ref_token;
+    const uint16_t* token_code;
+    int32_t n_images, n_refs, vocab, max_refs;
+    int32_t pad_idx, bos_idx, eos_idx, unk_idx;
+} ovc_eval_corpus;
+
+/* Per caption ids[b][0..T-1] (int64) of image rows[b] (int32; clamped into the corpus on the device):
+ *   clean_out[b][0..T-1] (int64)  the caption as evaluate_metrics scores it: ids clamped into [0, vocab), cut at the first
+ *                                 eos_idx, the four specials dropped, THEN consecutive equal words collapsed (itertools.groupby
+ *                                 sees the words after decode_caption removed the specials: a <unk> a becomes a); L words, then
+ *                                 one eos_idx if L < T, then pad_idx.  ovc_cider_reward on it gives the evaluation CIDEr.
+ *   stats_out[b][0..3]   correct[n]  sum over the caption's distinct n-grams of min(count, the image's maximum count)
+ *   stats_out[b][4..7]   guess[n]    max(0, L - n), n 0-based
+ *   stats_out[b][8], [9] testlen = L and reflen, the ref_words closest to L (a tie goes to the shorter; 0 without references)
+ *   stats_out[b][10]     the caption's ROUGE-L length max(L, 1): the empty caption is the one EMPTY token
+ *   stats_out[b][11]     the clamped row
+ *   stats_out[b][12 + i] the LCS length against the image's i-th reference, -1 for i at or past its number of references
+ * with a row of stats_out being OVC_METRIC_STATS + max_refs int32.  ovc_caption_metrics_bytes gives the bytes of stats_out for B
+ * captions, 0 when the shape is refused.  One wave per caption: the n-grams are sorted in LDS and looked up by binary search, the
+ * LCS is the bit-parallel row update V = (V + (V & M)) | (V & ~M) over ceil(L / 64) 64-bit words with M one ballot per word.
+ * Integers only, each written by one lane with plain vector stores, no atomics: the same values on every call, stream and
+ * replay.  One launch, no allocation, no synchronisation.  OVC_EINVAL (nothing launched): a null pointer, B < 1, T outside
+ * 1..OVC_MAX_LEN, vocab outside 1..65535, max_refs outside 0..OVC_METRIC_MAX_REFS, missing tables; OVC_EWORKSPACE: stats_bytes
+ * below ovc_caption_metrics_bytes(B, T, max_refs). */
+size_t ovc_caption_metrics_bytes(int B, int T, int max_refs);
+int ovc_caption_metrics(const ovc_eval_corpus* c, const int64_t* ids, const int32_t* rows, int B, int T, int64_t* clean_out,
+                        int32_t* stats_out, size_t stats_bytes, ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

@@ -81,6 +81,17 @@ class Cider(ctypes.Structure):
                 ("sigma", c_double), ("ref_len", c_double)]
 
 
+class EvalCorpus(ctypes.Structure):
+    """``ovc_eval_corpus``: the device tables of ``openviic_amd.metrics.EvalCorpus`` (BLEU and ROUGE-L)."""
+    _fields_ = [("image_ref", c_void_p), ("image_gram", c_void_p), ("gram_key", c_void_p), ("gram_max", c_void_p),
+                ("ref_words", c_void_p), ("ref_token", c_void_p), ("token_code", c_void_p),
+                ("n_images", c_int32), ("n_refs", c_int32), ("vocab", c_int32), ("max_refs", c_int32),
+                ("pad_idx", c_int32), ("bos_idx", c_int32), ("eos_idx", c_int32), ("unk_idx", c_int32)]
+
+
+OVC_METRIC_STATS = 12        # int32 per caption in front of the per-reference LCS lengths (include/ovc.h)
+OVC_METRIC_MAX_REFS = 4096
+
 ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC, ENC_CROSS_LEVEL = 0, 1, 2, 3
 DEC_PLAIN, DEC_MESHED = 0, 1
 
@@ -169,6 +180,8 @@ SIGNATURES = {
     "ovc_adam_step": (c_int, [c_void_p, c_int, c_void_p, c_long, c_double, c_double, c_double, c_double, c_long, c_void_p, c_void_p]),
     "ovc_scst_advantage_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ovc_scst_advantage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ovc_caption_metrics_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ovc_caption_metrics": (c_int, [POINTER(EvalCorpus), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -180,7 +193,7 @@ SIGNATURES = {
 APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_bytes", "ovc_beam_search_dropout",
                  "ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout",
                  "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step", "ovc_debug_attention_mem_backward",
-                 "ovc_scst_advantage_bytes", "ovc_scst_advantage")
+                 "ovc_scst_advantage_bytes", "ovc_scst_advantage", "ovc_caption_metrics_bytes", "ovc_caption_metrics")
 
 _lib = None
 

@@ -523,6 +523,25 @@ long ovc_adam_chunk_fill(const int64_t* counts, int n_tensors, ovc_adam_chunk* c
 int ovc_adam_step(const ovc_adam_tensor* table, int n_tensors, const ovc_adam_chunk* chunks, long n_chunks, double lr, double beta1,
                   double beta2, double eps, long step, const float* grad_scale, ovc_stream stream);
 
+/* The global L2 norm of the gradients and torch.nn.utils.clip_grad_norm_'s coefficient, on the device.  Appended to ABI 8.
+ * table / chunks are ovc_adam_step's (only grad and count are read; the other pointers may be null), so exactly the elements the
+ * Adam launch reads are summed and nothing between them is.  partials: n_chunks floats of device memory, contents need no
+ * initialisation; out: 2 floats.
+ *   pass 1  one partial per chunk.  Element e of a chunk (of 4096) belongs to lane (e / 4) % 256 whatever the pointer's
+ *           alignment; a lane runs acc = fmaf(g, g, acc) from 0 over its elements in ascending address order (at most 16);
+ *           the 64 lanes of a wave are added by the xor butterfly 32, 16, 8, 4, 2, 1 (v += v[lane ^ off]), the four waves
+ *           as (w0 + w1) + (w2 + w3); all fp32.
+ *   pass 2  lane l of 256 adds partials l, l + 256, ... ascending IN FLOAT64, then the same butterfly and tree in float64;
+ *           the sum is rounded to fp32 once.  out[0] = total_norm = sqrtf(sum), correctly rounded.
+ *           out[1] = clip_coef = min(1, float(max_norm) / (total_norm + 1e-6f)) in fp32 as torch forms it (a NaN stays a
+ *           NaN, an infinite norm gives 0); exactly 1.0f when only measuring: max_norm <= 0, +inf or above FLT_MAX.
+ * A non-finite gradient gives a non-finite total_norm; nothing is raised.  Two launches (one when n_chunks == 0: the norm
+ * is 0), no atomics, each value stored by one lane with a vector store, no allocation, no synchronisation, nothing read back,
+ * capturable: the same bits on every call, stream, grid and replay.  OVC_EINVAL (nothing launched): a NaN max_norm, a null out,
+ * a negative count, a null table, chunk table or partials with chunks to do. */
+int ovc_grad_norm(const ovc_adam_tensor* table, int n_tensors, const ovc_adam_chunk* chunks, long n_chunks, double max_norm,
+                  float* partials, float* out, ovc_stream stream);
+
 /* The self-critical baseline, advantage and loss gradient: what the reference's train_scst (vi_trainer.py:121-158) computes
  * between the search and loss.backward().  Appended to ABI 8.  reward [B][S] and logp [B][S][T] are fp32 device arrays (the
  * search's out_size = S beams per image), 1 <= S <= OVC_MAX_BEAM, 1 <= T <= OVC_MAX_LEN, B >= 1, B*S*T < 2^31.

@@ -206,7 +206,7 @@ class BaseTransformer(Module):
                 "identity -- set DROPOUT: 0 in the config or call model.eval()".format(what, live[0]))
         return {}
 
-    def xe_step(self, input_features, optimizer, dropout=False, generator=None):
+    def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None):
         """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
         ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
         stands for ::
@@ -219,6 +219,13 @@ class BaseTransformer(Module):
         random draw.  ``xe_loss``'s scope and refusals apply: the plain standard, augmented-memory and CaMo transformers, 'f32', the dropout
         rules.
 
+        ``max_norm``: clip the global L2 norm of the step's gradients to it, as ``torch.nn.utils.clip_grad_norm_`` between
+        ``backward()`` and ``step()`` does: ``ovc_grad_norm`` runs between the backward and the Adam launch on the same stream,
+        over the arena's per-parameter views (never its padding), and the call leaves the bits of the four lines with
+        ``optimizer.step(max_norm=max_norm)``.  ``(total_norm, clip_coef)`` stay on the device in ``optimizer.last_grad_norm``;
+        ``max_norm=float("inf")`` measures the norm and clips nothing.  ``max_norm <= 0`` or NaN is refused before any launch and
+        any draw.  With ``max_norm=None`` nothing of this is launched.
+
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
         all-reduce.  A data-parallel run keeps the four lines above."""
@@ -226,6 +233,7 @@ class BaseTransformer(Module):
         if not isinstance(optimizer, _optim.Adam):
             raise engine.native.OvcError("xe_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
                 type(optimizer).__name__))
+        max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
         probs = self._xe_dropout_probs(dropout, "xe_step")
         eng = self._fused_engine()
         eng._check_trainable()
@@ -240,10 +248,11 @@ class BaseTransformer(Module):
         slots = eng.step_arena()
         loss, _, grads = eng.forward_backward(input_features[self.feature_field], boxes, input_features["caption_tokens"],
                                               input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots)
-        optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad})
+        optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
         return loss
 
-    def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None):
+    def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
+                  max_norm=None):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -260,7 +269,9 @@ class BaseTransformer(Module):
         ``optimizer`` is an ``openviic_amd.optim.Adam`` that holds exactly the engine's trainable ``gradient_parameters()``, as
         for ``xe_step``.  ``dropout`` / ``generator``: as ``beam_search(dropout=...)``: the search runs under the masks of one
         seed and the backward recomputes under the same masks.  ``early_exit`` selects the search form; every form gives the
-        same bits.
+        same bits.  ``max_norm``: as ``xe_step`` takes it -- the global gradient norm is clipped between the backward and the
+        Adam launch, the bits are those of the lines with ``optimizer.step(max_norm=max_norm)``, and the norm is left in
+        ``optimizer.last_grad_norm``.
 
         Refused before any launch and any random draw: what ``xe_step`` and the SCST search refuse -- the optimizer's type and
         parameter set, a model the backward does not cover, a ``train()``-mode model with live dropout and ``dropout=False``,
@@ -278,6 +289,7 @@ class BaseTransformer(Module):
         if not isinstance(optimizer, _optim.Adam):
             raise engine.native.OvcError("scst_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
                 type(optimizer).__name__))
+        max_norm = _optim.checked_max_norm(max_norm, None, "scst_step")
         corpus = reward if isinstance(reward, CiderCorpus) else None
         if corpus is None and not callable(reward):
             raise engine.native.OvcError("scst_step: reward must be a CiderCorpus or a callable outs -> [B, k] float32 (got {})"
@@ -329,7 +341,7 @@ class BaseTransformer(Module):
             _, grads = eng.sequence_backward(feats, None, outs, g, dropout=drop, slots=slots, beam_size=k, arena=eng.step_arena())
         else:
             _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena())
-        optimizer.apply_gradients({p: gr for p, gr in zip(eng.gradient_parameters(), grads) if p.requires_grad})
+        optimizer.apply_gradients({p: gr for p, gr in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
 
     def _search_dropout_probs(self):

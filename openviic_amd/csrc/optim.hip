@@ -96,6 +96,91 @@ __global__ __launch_bounds__(kThreads) void adam_step_kernel(const ovc_adam_tens
     }
 }
 
+// ---- the global L2 norm of the gradients and the clip coefficient (ovc_grad_norm, include/ovc.h) ---------------------------------
+// Pass 1, one workgroup per chunk (workgroups stride over the chunk table as above): element e of the chunk belongs to lane
+// (e / 4) % 256 whatever the pointer's alignment, so a lane's elements are the float4 groups lane, lane + 256, lane + 512,
+// lane + 768 of the chunk, taken in ascending address order through one fmaf chain.  A group past the end contributes
+// fmaf(0, 0, acc), which is acc bit for bit (acc is never -0), so all four loads are issued before the first use.  Then the xor
+// butterfly of wave_sum (32, 16, 8, 4, 2, 1), and (w0 + w1) + (w2 + w3) over the four waves in LDS.  Lane 0 stores the partial.
+constexpr int kWaves = kThreads / OVC_WAVE;
+constexpr int kGroupsPerLane = kChunk / (4 * kThreads);
+
+__global__ __launch_bounds__(kThreads) void grad_norm_partial_kernel(const ovc_adam_tensor* __restrict__ table, int n_tensors,
+                                                                     const ovc_adam_chunk* __restrict__ chunks, int n_chunks,
+                                                                     float* __restrict__ partials) {
+    __shared__ float wave_sums[kWaves];
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const ovc_adam_chunk ch = chunks[c];
+        const gfloat* g = nullptr;
+        int len = 0;                                              // a chunk that is not this table's: a partial of 0
+        if (ch.tensor >= 0 && ch.tensor < n_tensors && ch.first >= 0) {
+            const long left = table[ch.tensor].count - ch.first;
+            len = left <= 0 ? 0 : left < kChunk ? (int)left : kChunk;
+            g = (const gfloat*)table[ch.tensor].grad + ch.first;
+        }
+        f32x4 v[kGroupsPerLane];
+        if ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) {        // uniform per chunk
+            const gf32x4* g4 = (const gf32x4*)g;
+#pragma unroll
+            for (int k = 0; k < kGroupsPerLane; ++k) {
+                const int e = 4 * ((int)threadIdx.x + k * kThreads);
+                if (e + 4 <= len) {
+                    v[k] = g4[e >> 2];
+                } else {                                          // the tensor's last, partial group (or nothing)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[k][j] = e + j < len ? g[e + j] : 0.f;
+                }
+            }
+        } else {                                                  // a view 4, 8 or 12 bytes into a line: the same elements, scalar loads
+#pragma unroll
+            for (int k = 0; k < kGroupsPerLane; ++k) {
+                const int e = 4 * ((int)threadIdx.x + k * kThreads);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[k][j] = e + j < len ? g[e + j] : 0.f;
+            }
+        }
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < kGroupsPerLane; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = fmaf(v[k][j], v[k][j], acc);
+        acc = wave_sum(acc);
+        if ((threadIdx.x & (OVC_WAVE - 1)) == 0) wave_sums[threadIdx.x / OVC_WAVE] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) partials[c] = (wave_sums[0] + wave_sums[1]) + (wave_sums[2] + wave_sums[3]);
+        __syncthreads();                                          // wave_sums is written again for the next chunk
+    }
+}
+
+// Pass 2, one workgroup: lane l adds partials l, l + 256, ... ascending in float64, the same butterfly and tree in float64, the
+// sum rounded to fp32 once, sqrtf (correctly rounded), and torch's clip_grad_norm_ arithmetic in fp32.  Lane 0 stores both values.
+__global__ __launch_bounds__(kThreads) void grad_norm_final_kernel(const float* __restrict__ partials, int n_chunks, float max_norm,
+                                                                   int clip, float* __restrict__ out) {
+    __shared__ double wave_sums[kWaves];
+    double acc = 0.0;
+    for (long base = threadIdx.x; base < n_chunks; base += 8 * kThreads) {    // eight loads in flight; + 0.0 keeps acc's bits
+        float p[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p[k] = base + k * kThreads < n_chunks ? partials[base + k * kThreads] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += (double)p[k];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((threadIdx.x & (OVC_WAVE - 1)) == 0) wave_sums[threadIdx.x / OVC_WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float total = sqrtf((float)((wave_sums[0] + wave_sums[1]) + (wave_sums[2] + wave_sums[3])));
+        float coef = 1.f;
+        if (clip) {
+            coef = max_norm / (total + 1e-6f);
+            coef = coef > 1.f ? 1.f : coef;                       // torch.clamp(max=1): a NaN stays a NaN
+        }
+        out[0] = total;
+        out[1] = coef;
+    }
+}
+
 }  // namespace
 
 extern "C" long ovc_adam_chunk_count(const int64_t* counts, int n_tensors) {
@@ -137,6 +222,24 @@ extern "C" int ovc_adam_step(const ovc_adam_tensor* table, int n_tensors, const 
     const unsigned blocks = n_chunks < (long)kMaxBlocks ? (unsigned)n_chunks : kMaxBlocks;
     hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(kThreads), 0, ovc_hip_stream(stream), table, n_tensors, chunks, (int)n_chunks,
                        grad_scale, s);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+extern "C" int ovc_grad_norm(const ovc_adam_tensor* table, int n_tensors, const ovc_adam_chunk* chunks, long n_chunks, double max_norm,
+                             float* partials, float* out, ovc_stream stream) {
+    if (n_tensors < 0 || n_chunks < 0 || n_chunks > 0x7fffffffL || max_norm != max_norm || !out) return OVC_EINVAL;
+    if (n_chunks > 0 && (!table || !chunks || !partials)) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    const int clip = max_norm > 0.0 && max_norm <= 3.4028234663852886e38;      // <= 0, +inf, beyond fp32: measure only
+    if (n_chunks > 0) {
+        const unsigned blocks = n_chunks < (long)kMaxBlocks ? (unsigned)n_chunks : kMaxBlocks;
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(blocks), dim3(kThreads), 0, ovc_hip_stream(stream), table, n_tensors, chunks,
+                           (int)n_chunks, partials);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(kThreads), 0, ovc_hip_stream(stream), partials, (int)n_chunks,
+                       clip ? (float)max_norm : 0.f, clip, out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -178,6 +178,7 @@ SIGNATURES = {
     "ovc_adam_chunk_count": (c_long, [c_void_p, c_int]),
     "ovc_adam_chunk_fill": (c_long, [c_void_p, c_int, c_void_p, c_long]),
     "ovc_adam_step": (c_int, [c_void_p, c_int, c_void_p, c_long, c_double, c_double, c_double, c_double, c_long, c_void_p, c_void_p]),
+    "ovc_grad_norm": (c_int, [c_void_p, c_int, c_void_p, c_long, c_double, c_void_p, c_void_p, c_void_p]),
     "ovc_scst_advantage_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ovc_scst_advantage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ovc_caption_metrics_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -193,7 +194,8 @@ SIGNATURES = {
 APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_bytes", "ovc_beam_search_dropout",
                  "ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout",
                  "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step", "ovc_debug_attention_mem_backward",
-                 "ovc_scst_advantage_bytes", "ovc_scst_advantage", "ovc_caption_metrics_bytes", "ovc_caption_metrics")
+                 "ovc_scst_advantage_bytes", "ovc_scst_advantage", "ovc_caption_metrics_bytes", "ovc_caption_metrics",
+                 "ovc_grad_norm")
 
 _lib = None
 

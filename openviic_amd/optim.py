@@ -20,6 +20,13 @@ and every element goes through, each operation rounded to fp32 once, nothing con
     p = p - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
 
 ``mirror_step`` does the same in numpy: the kernel's bits on the host.
+
+Clipping (``torch.nn.utils.clip_grad_norm_``, L2, one global norm over every group).  ``step(max_norm=c)`` /
+``apply_gradients(..., max_norm=c)`` launch ``ovc_grad_norm`` once in front of the Adam launches; it leaves
+``(total_norm, clip_coef)`` in a 2-element device tensor, ``optimizer.last_grad_norm``, and the Adam launches read
+``clip_coef = min(1, c / (total_norm + 1e-6))`` from there as their ``grad_scale``.  Nothing comes to the host.
+``grad_norm()`` is the measurement alone.  ``mirror_grad_norm`` restates the two passes' summation order in numpy
+(``include/ovc.h``), so ``mirror_step(..., grad_scale=clip_coef)`` gives the clipped step's bits.
 """
 import ctypes
 import math
@@ -51,6 +58,93 @@ def mirror_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, step, grad_sca
     v = beta2 * v + (w2 * g) * g
     p = p - (step_size * m) / (np.sqrt(v) / bc2_sqrt + eps)
     return p, m, v
+
+
+CHUNK_ELEMS = 4096          # the chunk of ovc_adam_chunk_fill, which is ovc_grad_norm's
+_LANES, _WAVE = 256, 64
+
+
+def _fma_square(g, acc):
+    """``float32(g * g + acc)`` rounded ONCE, as ``fmaf`` does, on fp32 arrays.  numpy has no fma: the product is exact in
+    float64 (24 x 24 bits), the float64 sum is turned into its round-to-odd value with the error term of TwoSum, and the
+    rounding of that to fp32 is the rounding of the exact sum (53 >= 24 + 2 bits)."""
+    with np.errstate(all="ignore"):
+        p = g.astype(np.float64)
+        p = p * p
+        a = acc.astype(np.float64)
+        s = p + a
+        t = s - p
+        err = (p - (s - t)) + (a - t)
+        odd = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(odd, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def _lane_tree(v):
+    """``[..., 256]`` lane values to ``[...]``: the xor butterfly 32, 16, 8, 4, 2, 1 inside each wave of 64, then
+    ``(w0 + w1) + (w2 + w3)``, in ``v``'s dtype."""
+    with np.errstate(all="ignore"):
+        v = v.reshape(v.shape[:-1] + (_LANES // _WAVE, _WAVE))
+        lane = np.arange(_WAVE)
+        for off in (32, 16, 8, 4, 2, 1):
+            v = v + v[..., lane ^ off]
+        w = v[..., 0]
+        return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def mirror_grad_norm(grads, chunk_elems=CHUNK_ELEMS, max_norm=None):
+    """``ovc_grad_norm`` in numpy: ``(total_norm, clip_coef)`` as ``np.float32``, the kernel's bits.  ``grads``: the gradient
+    arrays in table order (for ``Adam``: group by group, each group's parameters in order); ``max_norm`` ``None``, ``<= 0`` or
+    ``inf`` measures only (``clip_coef`` exactly 1).  Pass 1: one fp32 partial per chunk of ``chunk_elems`` of every tensor --
+    element ``e`` of a chunk belongs to lane ``(e // 4) % 256``, a lane chains ``acc = fma(g, g, acc)`` over its elements
+    ascending, then the lane tree.  Pass 2: lane ``l`` adds partials ``l, l + 256, ...`` ascending in float64, the lane tree in
+    float64, one rounding to fp32, ``sqrt``, and torch's ``min(1, max_norm / (total_norm + 1e-6))`` in fp32."""
+    if chunk_elems < 4 * _LANES or chunk_elems % (4 * _LANES):
+        raise ValueError("mirror_grad_norm: chunk_elems must be a positive multiple of {}".format(4 * _LANES))
+    rounds = chunk_elems // (4 * _LANES)
+    partials = []
+    for g in grads:
+        g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+        n_chunks = -(-g.size // chunk_elems)
+        if n_chunks == 0:
+            continue
+        padded = np.zeros(n_chunks * chunk_elems, dtype=np.float32)      # fma(0, 0, acc) is acc: the kernel's own argument
+        padded[:g.size] = g
+        padded = padded.reshape(n_chunks, rounds, _LANES, 4)
+        acc = np.zeros((n_chunks, _LANES), dtype=np.float32)
+        for k in range(rounds):
+            for j in range(4):
+                acc = _fma_square(padded[:, k, :, j], acc)
+        partials.append(_lane_tree(acc))
+    partials = np.concatenate(partials) if partials else np.zeros(0, dtype=np.float32)
+    padded = np.zeros(-(-max(partials.size, 1) // _LANES) * _LANES, dtype=np.float64)
+    padded[:partials.size] = partials
+    acc = np.zeros(_LANES, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for row in padded.reshape(-1, _LANES):
+            acc = acc + row
+        total = np.sqrt(np.float32(_lane_tree(acc)))
+        coef = np.float32(1.0)
+        if max_norm is not None and 0.0 < max_norm <= float(np.finfo(np.float32).max):
+            coef = np.float32(max_norm) / (total + np.float32(1e-6))
+            coef = np.float32(1.0) if coef > np.float32(1.0) else coef
+    return np.float32(total), np.float32(coef)
+
+
+def checked_max_norm(max_norm, grad_scale=None, what="Adam.step"):
+    """``max_norm`` as a float (``None`` stays ``None``), or the refusals of the clipping keyword: with a caller's
+    ``grad_scale``, not a number, ``<= 0`` or NaN.  ``inf`` is allowed: it measures the norm and clips nothing."""
+    if max_norm is None:
+        return None
+    if grad_scale is not None:
+        raise OvcError("{}: max_norm and grad_scale cannot be combined (with max_norm the clip coefficient takes "
+                       "grad_scale's place)".format(what))
+    if isinstance(max_norm, (torch.Tensor, bool)) or not isinstance(max_norm, (int, float, np.integer, np.floating)):
+        raise OvcError("{}: max_norm must be a python number (got {}); it is passed to the kernel by value".format(
+            what, type(max_norm).__name__))
+    if not float(max_norm) > 0.0:
+        raise OvcError("{}: max_norm must be > 0 (got {!r})".format(what, max_norm))
+    return float(max_norm)
 
 
 def _check_group(group):
@@ -99,11 +193,13 @@ class Adam(torch.optim.Optimizer):
                         decoupled_weight_decay=decoupled_weight_decay)
         self._tables = {}        # (group, part) -> (key, device tensor table): re-uploaded only when a pointer in it moved
         self._chunks = {}        # (device, element counts) -> (device chunk table, chunks): pointers do not enter
+        self.last_grad_norm = None      # (total_norm, clip_coef) of the last clipped step: a device tensor, never synchronised
         super().__init__(params, defaults)
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self._tables, self._chunks = {}, {}
+        self.last_grad_norm = None
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -126,10 +222,13 @@ class Adam(torch.optim.Optimizer):
 
     # -- the step -----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=None):
+    def step(self, closure=None, grad_scale=None, max_norm=None):
         """Update every parameter that has a ``.grad``.  ``grad_scale``: an optional one-element fp32 device tensor; the
-        gradients are read as ``grad * grad_scale`` (it is never brought to the host).  No host synchronisation, no
-        device-to-host copy.  Every refusal is raised before the first launch."""
+        gradients are read as ``grad * grad_scale`` (it is never brought to the host).  ``max_norm``: clip the global L2 norm
+        of all these gradients to it first, as ``torch.nn.utils.clip_grad_norm_(params, max_norm)`` in front of the step does
+        -- the gradients themselves are left as they are, the update reads them scaled -- and leave ``(total_norm,
+        clip_coef)`` in ``self.last_grad_norm``.  No host synchronisation, no device-to-host copy.  Every refusal is raised
+        before the first launch: ``max_norm`` with ``grad_scale``, ``max_norm <= 0`` or NaN among them."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -138,29 +237,78 @@ class Adam(torch.optim.Optimizer):
         for group in self.param_groups:
             params = [p for p in group["params"] if p.grad is not None]
             work.append((params, [p.grad for p in params]))
-        self._update(work, grad_scale)
+        self._update(work, grad_scale, max_norm, "Adam.step")
         return loss
 
     @torch.no_grad()
-    def apply_gradients(self, gradients, grad_scale=None):
+    def apply_gradients(self, gradients, grad_scale=None, max_norm=None):
         """The step with the gradients given instead of read from ``.grad``: ``gradients`` maps parameters of this optimizer
         to gradient tensors (fp32, contiguous, on the parameter's device; views into a larger buffer are fine).  Exactly
         those parameters are updated; ``p.grad`` is neither read nor written.  ``model.xe_step`` hands the engine's gradient
-        arena over this way."""
+        arena over this way.  ``max_norm``: as ``step`` takes it, the norm over exactly the given gradients."""
+        work = self._given(gradients, "apply_gradients")
+        self._update(work, grad_scale, max_norm, "Adam.apply_gradients")
+        self._opt_called = True      # what torch's schedulers look at to warn about a scheduler stepped before its optimizer
+
+    @torch.no_grad()
+    def grad_norm(self, gradients=None, max_norm=None):
+        """``(total_norm, clip_coef)`` as a 2-element fp32 device tensor (``ovc_grad_norm``): the L2 norm over the ``.grad`` of
+        every parameter of this optimizer that has one, all groups together, or over a ``{parameter: gradient}`` mapping as
+        ``apply_gradients`` takes it; ``clip_coef`` is ``min(1, max_norm / (total_norm + 1e-6))``, exactly 1 without
+        ``max_norm``.  Nothing is updated, nothing comes to the host.  Capturable once a first call on the capturing stream
+        has uploaded the tables."""
+        max_norm = checked_max_norm(max_norm, None, "Adam.grad_norm")
+        if gradients is None:
+            work = []
+            for group in self.param_groups:
+                params = [p for p in group["params"] if p.grad is not None]
+                work.append((params, [p.grad for p in params]))
+        else:
+            work = self._given(gradients, "grad_norm")
+        pairs = [(p, g) for params, grads in work for p, g in zip(params, grads)]
+        for p, g in pairs:
+            self._check_pair(p, g)
+        if not pairs:
+            raise OvcError("Adam.grad_norm: no parameter of this optimizer has a gradient")
+        device = pairs[0][0].device
+        with torch.cuda.device(device):
+            return self._norm(native.load(), torch.cuda.current_stream(device).cuda_stream, device, pairs, max_norm)
+
+    def _given(self, gradients, what):
         by_id = {id(p): (p, g) for p, g in gradients.items()}
         work = []
         for group in self.param_groups:
             chosen = [by_id.pop(id(p)) for p in group["params"] if id(p) in by_id]
             work.append(([p for p, _ in chosen], [g for _, g in chosen]))
         if by_id:
-            raise ValueError("openviic_amd.optim.Adam.apply_gradients: {} of the given parameters are not in this optimizer"
-                             .format(len(by_id)))
-        self._update(work, grad_scale)
-        self._opt_called = True      # what torch's schedulers look at to warn about a scheduler stepped before its optimizer
+            raise ValueError("openviic_amd.optim.Adam.{}: {} of the given parameters are not in this optimizer"
+                             .format(what, len(by_id)))
+        return work
 
-    def _update(self, work, grad_scale):
+    def _norm(self, lib, stream, device, pairs, max_norm, tables=None):
+        """Launch ``ovc_grad_norm`` over ``pairs`` (``(parameter, gradient)`` in table order) and return its fresh output tensor.
+        ``tables``: ``(tensor table, tensors, chunk table, chunks)`` of an Adam launch over exactly these pairs, read instead
+        of a table of the gradients alone."""
+        if tables is None:
+            counts = tuple(p.numel() for p, _ in pairs)
+            key = (stream, device, counts) + tuple(g.data_ptr() for _, g in pairs)
+            cached = self._tables.get("norm")
+            if cached is None or cached[0] != key:
+                table = np.zeros((len(pairs), 5), dtype=np.int64)          # ovc_adam_tensor: only grad and count are read
+                table[:, 1], table[:, 4] = key[3:], counts
+                cached = self._tables["norm"] = (key, _upload(table, device))
+            tables = (cached[1], len(pairs)) + self._chunk_table(lib, stream, device, counts)
+        table, n_tensors, chunks, n_chunks = tables
+        partials = torch.empty(max(n_chunks, 1), dtype=torch.float32, device=device)
+        out = torch.empty(2, dtype=torch.float32, device=device)
+        check(lib.ovc_grad_norm(table.data_ptr(), n_tensors, chunks.data_ptr(), n_chunks, 0.0 if max_norm is None else max_norm,
+                                partials.data_ptr(), out.data_ptr(), ctypes.c_void_p(stream)), "ovc_grad_norm")
+        return out
+
+    def _update(self, work, grad_scale, max_norm=None, what="Adam.step"):
         # 1. every refusal, before any launch and any change of state
         scale_ptr = None
+        max_norm = checked_max_norm(max_norm, grad_scale, what)
         for group, (params, grads) in zip(self.param_groups, work):
             _check_group(group)
             for p, g in zip(params, grads):
@@ -194,6 +342,7 @@ class Adam(torch.optim.Optimizer):
         # 3. tables (cached) and launches
         stream = torch.cuda.current_stream(device).cuda_stream
         with torch.cuda.device(device):
+            ready = []
             for gi, pi, group, step, entries in launches:
                 counts = tuple(p.numel() for p, _, _ in entries)
                 key = (stream, device, counts) + tuple(
@@ -203,10 +352,18 @@ class Adam(torch.optim.Optimizer):
                     rows = np.array(key[3:], dtype=np.int64).reshape(len(entries), 4)
                     table = np.concatenate([rows, np.array(counts, dtype=np.int64)[:, None]], axis=1)
                     cached = self._tables[(gi, pi)] = (key, _upload(table, device))
-                chunks, n_chunks = self._chunk_table(lib, stream, device, counts)
+                ready.append((group, step, entries, cached[1]) + self._chunk_table(lib, stream, device, counts))
+            if max_norm is not None:
+                # one global norm in front of every launch, over the pairs in group order.  A single launch (xe_step, scst_step:
+                # one group at one step count) covers exactly those pairs in that order, and the norm reads its tables.
+                pairs = [(p, g) for params, grads in work for p, g in zip(params, grads)]
+                shared = (ready[0][3], len(ready[0][2])) + ready[0][4:] if len(ready) == 1 else None
+                self.last_grad_norm = self._norm(lib, stream, device, pairs, max_norm, shared)
+                scale_ptr = self.last_grad_norm.data_ptr() + 4
+            for group, step, entries, table, chunks, n_chunks in ready:
                 for _, _, state in entries:
                     state["step"] += 1
-                check(lib.ovc_adam_step(cached[1].data_ptr(), len(entries), chunks.data_ptr(), n_chunks, float(group["lr"]),
+                check(lib.ovc_adam_step(table.data_ptr(), len(entries), chunks.data_ptr(), n_chunks, float(group["lr"]),
                                         float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), step, scale_ptr,
                                         ctypes.c_void_p(stream)), "ovc_adam_step")
         # 4. the kernel wrote through raw pointers: move the version counters as an in-place torch update would (the engine

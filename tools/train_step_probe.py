@@ -19,6 +19,11 @@ copy of the model.  Per form: ms per iteration (device events) per round, and th
 back-to-back ``step()`` calls on the gradients of the last iteration -- with the bytes it must move (28 per element: p, g, m, v
 read, p, m, v written) over its time as achieved bytes/s, against the 6.29 TB/s of a float4 copy on this chip.
 
+--max-norm C (with ``--optimizer ... xe_step``): a further form, ``xe_step_clip`` = ``model.xe_step(items, optimizer, max_norm=C)``
+(``ovc_grad_norm`` between the backward and the Adam launch), alternating with the others; its rows also carry ``grad_norm_ms``,
+``optimizer.grad_norm(gradients)`` alone, back to back, with the 4 bytes per element it reads as achieved bytes/s.  ``xe_step``
+without ``max_norm`` launches what it launched before the keyword existed, so it is the baseline of the same run.
+
 Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
 end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
 times 3 -- the backward has two products per forward product -- over the step time, against the nominal 157.3 TF fp32 matrix
@@ -71,12 +76,14 @@ def optimizer_probe(args, build, items, B):
     """The iteration with its optimizer step, every form of ``args.optimizer`` on its own model, alternating."""
     from openviic_amd.optim import Adam
     forms = {}
-    for kind in args.optimizer:
+    for kind in list(args.optimizer) + (["xe_step_clip"] if args.max_norm is not None else []):
         model = build()
         params = [p for p in model.parameters() if p.requires_grad]
         opt = (torch.optim.Adam if kind == "torch" else Adam)(params, lr=1e-4, betas=(0.9, 0.98))
         if kind == "xe_step":
             iteration = lambda model=model, opt=opt: model.xe_step(items, opt, dropout=args.dropout)
+        elif kind == "xe_step_clip":
+            iteration = lambda model=model, opt=opt: model.xe_step(items, opt, dropout=args.dropout, max_norm=args.max_norm)
         else:
             def iteration(model=model, opt=opt):
                 opt.zero_grad()
@@ -92,17 +99,24 @@ def optimizer_probe(args, build, items, B):
     for rnd in range(args.rounds):
         for kind, (model, params, opt, iteration) in forms.items():
             ms = events_ms(iteration, args.steps)
-            if kind == "xe_step":               # the same launch as "engine", fed from the arena of the last iteration
+            extra = {}
+            if kind in ("xe_step", "xe_step_clip"):     # the same launch as "engine", fed from the arena of the last iteration
                 grads = dict(zip(model._fused_engine().gradient_parameters(), model._fused_engine().step_arena()[2]))
                 grads = {p: g for p, g in grads.items() if p.requires_grad}
-                alone = events_ms(lambda: opt.apply_gradients(grads), args.steps)
+                clip = args.max_norm if kind == "xe_step_clip" else None
+                alone = events_ms(lambda: opt.apply_gradients(grads, max_norm=clip), args.steps)
+                if clip is not None:
+                    norm_ms = events_ms(lambda: opt.grad_norm(grads, max_norm=clip), args.steps)
+                    total, coef = opt.last_grad_norm.tolist()
+                    extra = dict(max_norm=clip, grad_norm_ms=round(norm_ms, 4), total_norm=total, clip_coef=coef,
+                                 grad_norm_tb_per_s=round(4.0 * sum(p.numel() for p in params) / (norm_ms * 1e-3) / 1e12, 3))
             else:
                 alone = events_ms(opt.step, args.steps)
             elements = sum(p.numel() for p in params)
             rate = 28.0 * elements / (alone * 1e-3)
             rows.append(dict(variant=args.variant, B=B, dropout=args.dropout, optimizer=kind, round=rnd, ms_per_iteration=round(ms, 3),
                              optimizer_step_ms=round(alone, 4), tensors=len(params), elements=elements, step_bytes=28 * elements,
-                             step_tb_per_s=round(rate / 1e12, 3), share_of_copy_rate=round(rate / COPY_RATE, 3)))
+                             step_tb_per_s=round(rate / 1e12, 3), share_of_copy_rate=round(rate / COPY_RATE, 3), **extra))
             print(json.dumps(rows[-1]))
     return rows
 
@@ -166,10 +180,14 @@ def main():
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
                     help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
+    ap.add_argument("--max-norm", type=float, default=None,
+                    help="with --optimizer ... xe_step: also time model.xe_step(items, optimizer, max_norm=C)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if "none" in args.optimizer and len(args.optimizer) > 1:
         ap.error("--optimizer none stands alone")
+    if args.max_norm is not None and "xe_step" not in args.optimizer:
+        ap.error("--max-norm goes with --optimizer ... xe_step")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)

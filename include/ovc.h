@@ -391,6 +391,34 @@ int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, con
  * (tests compare it with openviic_amd/dropout.py).  p in [0, 1), 0 <= site < OVC_DROPOUT_SITES. */
 int ovc_dropout_mask(const int64_t* seed, int site, long rows, long cols, float p, uint8_t* keep, ovc_stream stream);
 
+/* Label-smoothed cross-entropy (the reference's loss_utils/label_smoothing.py, LabelSmoothing(size = V, padding_idx = pad,
+ * smoothing = s) on the log-probabilities [R, V], R = B*T, and the targets).  Appended to ABI 8.  With conf = 1 - s, u = s / (V - 2),
+ * t[r, v] = conf at v = targets[r], 0 at v = pad, u elsewhere, and keep_r = targets[r] != pad:
+ *   row_r = C - conf logp[r, tgt_r] - u (sum_v logp[r, v] - logp[r, tgt_r] - logp[r, pad]),   C = conf log conf + (V - 2) u log u
+ *   loss  = w sum_r keep_r row_r,       dlogit[r, v] = keep_r w (softmax[r, v] - t[r, v])
+ * (terms of C with a zero factor are 0).  reduction OVC_LOSS_MEAN: w = 1 / (R V), KLDivLoss(reduction="mean"), pad rows counted in
+ * R -- the reference's value; a batch without a kept row then has loss 0 and every gradient 0.  OVC_LOSS_TOKENS: w = 1 / #kept
+ * rows, the scale of ovc_forward_backward's loss, which smoothing = 0 with OVC_LOSS_TOKENS equals.  sum_v logp[r, v] is summed as
+ * differences (logit - max) - log S in a fixed order: ascending v within slices of 64 words, then the slices ascending. */
+#define OVC_LOSS_MEAN    0
+#define OVC_LOSS_TOKENS  1
+typedef struct {
+    float smoothing;                     /* s in [0, 1); s > 0 needs V > 2 */
+    int32_t reduction;                   /* OVC_LOSS_MEAN or OVC_LOSS_TOKENS */
+} ovc_loss;
+
+/* ovc_forward_backward (dropout == NULL) or ovc_forward_backward_dropout (dropout != NULL) with the loss above in place of the
+ * NLL: same models, sizes, gradient table, determinism and use_graph; the loss parameters are part of the graph's key.  A null
+ * loss, smoothing outside [0, 1) (NaN included), an unknown reduction, smoothing > 0 with V <= 2, or anything
+ * ovc_forward_backward (with dropout: ovc_forward_backward_dropout) refuses: OVC_EINVAL, nothing launched.
+ * ovc_train_smoothed_workspace_bytes: bytes of workspace (dropout != 0: for calls that pass a dropout table) -- the carve of
+ * ovc_train_workspace_bytes / ovc_train_dropout_workspace_bytes plus the rows' log-probability sums and their slice partials; 0
+ * wherever that sizer answers 0. */
+size_t ovc_train_smoothed_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout);
+int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                  const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                  float* loss_out, int use_graph, ovc_stream stream, const ovc_loss* loss, const ovc_dropout* dropout);
+
 /* Self-critical sequence training: the gradient of a beam search's log-probabilities (the reference's train_scst,
  * vi_trainer.py:121-158).  ids [B][S][T] are S generated sequences per image (the search's outputs), grad_logp [B][S][T] the
  * gradient g of the loss with respect to the search's log_probs.  With e(b,s) = the first t with ids[b,s,t] == eos_idx (T-1 if

@@ -40,8 +40,9 @@ class _XeLoss(torch.autograd.Function):
     until it is freed; no ``.grad`` is touched."""
 
     @staticmethod
-    def forward(ctx, engine_, dropout, features, boxes, tokens, targets, *params):
-        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout)
+    def forward(ctx, engine_, dropout, smoothed, features, boxes, tokens, targets, *params):
+        # smoothed: None (the NLL) or (label_smoothing, reduction)
+        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout, loss=smoothed)
         ctx.engine, ctx.arena = engine_, arena
         ctx.layout = [(g.storage_offset(), g.shape) for g in grads]
         ctx.wanted = [p.requires_grad for p in params]
@@ -52,7 +53,7 @@ class _XeLoss(torch.autograd.Function):
         scaled = ctx.engine.scale_gradients(ctx.arena, grad_output)
         out = [scaled[off:off + shape.numel()].view(shape) if want else None
                for (off, shape), want in zip(ctx.layout, ctx.wanted)]
-        return (None, None, None, None, None, None) + tuple(out)
+        return (None, None, None, None, None, None, None) + tuple(out)
 
 
 class _BeamLogProbs(torch.autograd.Function):
@@ -166,7 +167,7 @@ class BaseTransformer(Module):
         return self._fused_engine().score(input_features[self.feature_field], boxes, input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
 
-    def xe_loss(self, input_features, dropout=False, generator=None):
+    def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
         every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer, the
@@ -178,7 +179,18 @@ class BaseTransformer(Module):
         engine does not place is refused; the standard and augmented-memory transformers only: a CaMo model with a live
         dropout is refused before any draw).  The step's seed is drawn on the stream from ``generator`` (default: the device's
         CUDA generator), so ``torch.manual_seed`` reproduces a step.  In ``eval()`` mode, or with every ``p == 0``, this is the
-        ``dropout=False`` call: same bits, no random draw."""
+        ``dropout=False`` call: same bits, no random draw.
+
+        ``label_smoothing=s``: the reference's ``LabelSmoothing(V, pad, s)`` (``loss_utils/label_smoothing.py``) in place of the
+        NLL (``ovc_forward_backward_smoothed``): the KL divergence from the target distribution -- ``1 - s`` on the target,
+        ``s / (V - 2)`` on every other word but ``<pad>``, nothing on rows whose target is ``<pad>`` -- to the model's, for every
+        model and dropout setting above.  ``reduction="mean"`` (the default) is the reference's ``KLDivLoss(reduction="mean")``:
+        the sum over all elements divided by ``B * T * V``, pad rows counted, so the loss is of the order of ``1 / V`` of the
+        NLL; ``reduction="tokens"`` divides by the number of kept rows instead, the scale of the plain loss, which
+        ``label_smoothing=0.0, reduction="tokens"`` is bit for bit.  Refused before any launch and any draw: an ``s`` that is
+        not a Python number in ``0 <= s < 1``, ``s > 0`` with a vocabulary of 2 words or fewer, an unknown ``reduction``, and a
+        ``reduction`` without ``label_smoothing``.  ``label_smoothing=None`` is the plain call, launch for launch."""
+        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, "xe_loss", len(self.vocab))
         probs = self._xe_dropout_probs(dropout, "xe_loss")
         eng = self._fused_engine()
         if probs:
@@ -186,7 +198,7 @@ class BaseTransformer(Module):
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         params = eng.gradient_parameters()
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        return _XeLoss.apply(eng, drop, input_features[self.feature_field], boxes, input_features["caption_tokens"],
+        return _XeLoss.apply(eng, drop, smoothed, input_features[self.feature_field], boxes, input_features["caption_tokens"],
                              input_features["shifted_right_caption_tokens"], *params)
 
     def _xe_dropout_probs(self, dropout, what):
@@ -206,7 +218,8 @@ class BaseTransformer(Module):
                 "identity -- set DROPOUT: 0 in the config or call model.eval()".format(what, live[0]))
         return {}
 
-    def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None):
+    def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None, label_smoothing=None,
+                reduction=None):
         """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
         ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
         stands for ::
@@ -226,6 +239,9 @@ class BaseTransformer(Module):
         ``max_norm=float("inf")`` measures the norm and clips nothing.  ``max_norm <= 0`` or NaN is refused before any launch and
         any draw.  With ``max_norm=None`` nothing of this is launched.
 
+        ``label_smoothing`` / ``reduction``: as ``xe_loss`` takes them -- the label-smoothed loss in the four lines and here, with
+        the same refusals before any launch and any draw.
+
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
         all-reduce.  A data-parallel run keeps the four lines above."""
@@ -234,6 +250,7 @@ class BaseTransformer(Module):
             raise engine.native.OvcError("xe_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
                 type(optimizer).__name__))
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
+        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, "xe_step", len(self.vocab))
         probs = self._xe_dropout_probs(dropout, "xe_step")
         eng = self._fused_engine()
         eng._check_trainable()
@@ -247,7 +264,8 @@ class BaseTransformer(Module):
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
         slots = eng.step_arena()
         loss, _, grads = eng.forward_backward(input_features[self.feature_field], boxes, input_features["caption_tokens"],
-                                              input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots)
+                                              input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots,
+                                              loss=smoothed)
         optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
         return loss
 

@@ -76,6 +76,19 @@ int ovc_bw_xent(const float* logits_t, long ldt, const float* lse, const int32_t
 // (ovc_sequence_backward: w_row = -grad_logp up to each sequence's first <eos>, 0 after it).
 int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, const float* w_row, int rows, int V,
                   float* dl_t, float* dl, long ldv, hipStream_t s);
+// Label-smoothed cross-entropy (include/ovc.h, ovc_loss): ovc_bw_xent with the target distribution t = conf at the target, 0 at
+// pad, u elsewhere.  Four launches: the rows' sums of log-probabilities (differences (logit - M) - log S, ascending words within
+// slices of 64 words into lp_part [ceil(V / 64)][ldt], then the slices in ascending order into lp_sum [rows]; read by the loss
+// only), the loss and the row weights (one workgroup, ovc_bw_xent's order; reduction 0: w = w_mean on kept rows, 1: 1 / count),
+// and dlogit = (softmax - t) w_row in ovc_bw_xent's two layouts.  C, conf, u and w_mean are the host's float64 values rounded once.
+struct SmoothedLoss {
+    float conf, u, C, w_mean;
+    int reduction;
+};
+size_t ovc_bw_smoothed_part_floats(int rows, int V);
+int ovc_bw_xent_smoothed(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V,
+                         const SmoothedLoss& l, float* lp_part, float* lp_sum, float* w_row, float* loss, float* dl_t, float* dl,
+                         long ldv, hipStream_t s);
 // Word-embedding backward: out[w, :] = sum over rows r with tok[r] == w (ascending r) of dx[r, :]; the pad row 0.
 int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s);
 // tok32[r] = clamp(tokens[r], 0, V-1)

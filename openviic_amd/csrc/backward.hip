@@ -360,6 +360,95 @@ __global__ __launch_bounds__(256) void bw_dlogit_kernel(const float* __restrict_
     }
 }
 
+// Label smoothing.  Row sums of the log-probabilities: lanes along rows (every load coalesced), one wave per (64 rows, slice of
+// kLpSlice words), the slice's words in ascending order: part[slice][r] = sum_v ((logit - M) - log S)
+constexpr int kLpSlice = 64;
+
+__global__ __launch_bounds__(256) void bw_logp_rowsum_part_kernel(const float* __restrict__ logits_t, long ldt,
+                                                                  const float* __restrict__ lse, int rows, int V,
+                                                                  float* __restrict__ part) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = blockIdx.x * 64 + lane, slice = blockIdx.y * 4 + wv;
+    const int w0 = slice * kLpSlice;
+    if (r >= rows || w0 >= V) return;
+    const float mx = lse[2 * r], ls = lse[2 * r + 1];
+    const int w1 = min(w0 + kLpSlice, V);
+    float acc = 0.f;
+#pragma unroll 8
+    for (int w = w0; w < w1; ++w) acc += (logits_t[(size_t)w * ldt + r] - mx) - ls;
+    part[(size_t)slice * ldt + r] = acc;
+}
+
+// the slices in ascending order
+__global__ __launch_bounds__(256) void bw_logp_rowsum_final_kernel(const float* __restrict__ part, long ldt, int rows, int slices,
+                                                                   float* __restrict__ lp_sum) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float acc = 0.f;
+    for (int i = 0; i < slices; ++i) acc += part[(size_t)i * ldt + r];
+    lp_sum[r] = acc;
+}
+
+// bw_loss_kernel for the smoothed loss: one workgroup, thread partials over rows t, t + 256, ... of
+// C - conf logp[tgt] - u ((sum_v logp - logp[tgt]) - logp[pad]) and of the kept-row count, the same fixed LDS tree, then every
+// row's weight: w_mean (reduction 0) or 1 / count on kept rows, 0 on pad rows
+__global__ __launch_bounds__(256) void bw_smoothed_loss_kernel(const float* __restrict__ logits_t, long ldt,
+                                                               const float* __restrict__ lse, const float* __restrict__ lp_sum,
+                                                               const int32_t* __restrict__ tgt, int pad, int rows, float conf, float u,
+                                                               float C, int reduction, float w_mean, float* __restrict__ w_row,
+                                                               float* __restrict__ loss) {
+    __shared__ float tot[256], cnt[256];
+    const int t = threadIdx.x;
+    float a = 0.f, c = 0.f;
+    for (int r = t; r < rows; r += 256) {
+        const int w = tgt[r];
+        if (w == pad) continue;
+        const float lt = (logits_t[(size_t)w * ldt + r] - lse[2 * r]) - lse[2 * r + 1];
+        const float lpad = (logits_t[(size_t)pad * ldt + r] - lse[2 * r]) - lse[2 * r + 1];
+        a += (C - conf * lt) - u * ((lp_sum[r] - lt) - lpad);
+        c += 1.f;
+    }
+    tot[t] = a; cnt[t] = c;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) { tot[t] += tot[t + off]; cnt[t] += cnt[t + off]; }
+        __syncthreads();
+    }
+    const float inv = reduction == 0 ? w_mean : 1.f / cnt[0];
+    if (t == 0) *loss = reduction == 0 ? tot[0] * w_mean : tot[0] / cnt[0];
+    for (int r = t; r < rows; r += 256) w_row[r] = tgt[r] == pad ? 0.f : inv;
+}
+
+// bw_dlogit_kernel's tile with the smoothed target distribution: g = (p - t[r, w]) w_row[r], t = conf at the target, 0 at pad, u
+// elsewhere; a row of weight 0 gets +0
+__global__ __launch_bounds__(256) void bw_smoothed_dlogit_kernel(const float* __restrict__ logits_t, long ldt,
+                                                                 const float* __restrict__ lse, const int32_t* __restrict__ tgt,
+                                                                 const float* __restrict__ w_row, int pad, float conf, float u,
+                                                                 int rows, int V, float* __restrict__ dl_t, float* __restrict__ dl,
+                                                                 long ldv) {
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, w0 = blockIdx.y * 64;
+    for (int i = wv; i < 64; i += 4) {
+        const int w = w0 + i, r = r0 + lane;
+        float g = 0.f;
+        if (w < V && r < rows) {
+            const float wr = w_row[r];
+            if (wr != 0.f) {
+                const float p = expf((logits_t[(size_t)w * ldt + r] - lse[2 * r]) - lse[2 * r + 1]);
+                g = (p - (tgt[r] == w ? conf : w == pad ? 0.f : u)) * wr;
+            }
+        }
+        if (w < V && r < ldt) dl_t[(size_t)w * ldt + r] = g;
+        tile[i][lane] = g;
+    }
+    __syncthreads();
+    for (int i = wv; i < 64; i += 4) {
+        const int r = r0 + i, w = w0 + lane;
+        if (r < rows && w < ldv) dl[(size_t)r * ldv + w] = tile[lane][i];
+    }
+}
+
 // one workgroup per word; each thread keeps up to 8 columns (d <= 2048)
 __global__ __launch_bounds__(256) void bw_embedding_kernel(const int32_t* __restrict__ tok, int rows, int pad,
                                                            const float* __restrict__ dx, int d, float* __restrict__ out) {
@@ -501,6 +590,30 @@ int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32
                   float* dl_t, float* dl, long ldv, hipStream_t s) {
     hipLaunchKernelGGL(bw_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, tgt, w_row,
                        rows, V, dl_t, dl, ldv);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+size_t ovc_bw_smoothed_part_floats(int rows, int V) {
+    return (size_t)((V + kLpSlice - 1) / kLpSlice) * (((size_t)rows + 3) & ~(size_t)3);
+}
+
+int ovc_bw_xent_smoothed(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V,
+                         const SmoothedLoss& l, float* lp_part, float* lp_sum, float* w_row, float* loss, float* dl_t, float* dl,
+                         long ldv, hipStream_t s) {
+    if (rows <= 0 || V <= 0 || pad < 0 || pad >= V || ldt < rows || !lp_part || !lp_sum || (l.reduction != 0 && l.reduction != 1))
+        return OVC_EINVAL;
+    const int slices = (V + kLpSlice - 1) / kLpSlice;
+    hipLaunchKernelGGL(bw_logp_rowsum_part_kernel, dim3((rows + 63) / 64, (slices + 3) / 4), dim3(256), 0, s, logits_t, ldt, lse, rows,
+                       V, lp_part);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_logp_rowsum_final_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, lp_part, ldt, rows, slices, lp_sum);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_smoothed_loss_kernel, dim3(1), dim3(256), 0, s, logits_t, ldt, lse, lp_sum, tgt, pad, rows, l.conf, l.u, l.C,
+                       l.reduction, l.w_mean, w_row, loss);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_smoothed_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, tgt,
+                       w_row, pad, l.conf, l.u, rows, V, dl_t, dl, ldv);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

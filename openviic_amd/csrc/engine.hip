@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -1304,6 +1305,7 @@ enum class GraphKind {
     Train,              // ovc_forward_backward (k = T)
     TrainDropout,       // ovc_forward_backward_dropout (k = T)
     SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
+    TrainSmoothed,      // ovc_forward_backward_smoothed (k = T, out_size = with dropout; the loss parameters in the hash)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1812,6 +1814,9 @@ struct TrainWs {
     // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
     int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
     int32_t* maskrow;             // [rows] sequences with dropout: the mask row of every decoder row (seq_maskrow_kernel)
+    // label smoothing (carve_train(..., smoothed = true) only; ovc_train_smoothed_workspace_bytes): the rows' sums of
+    // log-probabilities [rows] and their slice partials [ceil(V / 64)][rows padded to 4]
+    float* lp_sum; float* lp_part;
     // the cross-level tail (bw_cross_level_tail; cross-level models only), rows B*N: the leaky-ReLU gradients dh [B*N][d] (mlp2's,
     // then mlp1's in da), mlp1's input gradient dcat [B*N][3d], per cross call c the pre-norm sum's gradient dss [2][B*N][d], dq
     // [2][B*N][h_enc dk_enc], dk|dv [2][B*N][2 h_enc dk_enc], then d(o2') and the q path plus dss, dq23 [2][B*N][d]; the levels'
@@ -1827,7 +1832,8 @@ inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 inline int train_memory(const ovc_model* m) { return m->enc[0].att.m_k ? m->memory : 0; }
 
 // S > 1 (with seq): S sequences per image, rows = B*S*T (run_forward_decoder)
-TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false, int S = 1, bool seq = false) {
+TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false, int S = 1, bool seq = false,
+                    bool smoothed = false) {
     TrainWs t{};
     t.w = carve_forward(m, base, B, N, T, 1, S);
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
@@ -1888,6 +1894,10 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
     if (seq) {
         t.seq_tok = a.take<int64_t>(rows); t.seq_tgt = a.take<int64_t>(rows); t.seq_keep = a.take<uint8_t>(rows);
         if (dropout) t.maskrow = a.take<int32_t>(rows);
+    }
+    if (smoothed) {
+        t.lp_sum = a.take<float>(rows);
+        t.lp_part = a.take<float>(ovc_bw_smoothed_part_floats((int)rows, m->vocab));
     }
     t.bytes = (a.off + 255) & ~(size_t)255;
     return t;
@@ -2169,7 +2179,9 @@ int bw_cross_level_tail(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N
 
 // seq (ovc_sequence_backward): S sequences per image, and the row weights t.w_row come from the caller's grad_logp (written before the
 // body) instead of the cross-entropy's: the dlogit alone, no loss.
-int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T, int S = 1, bool seq = false) {
+// smoothed (ovc_forward_backward_smoothed): the label-smoothed loss head in place of the cross-entropy's; the sweep behind it is the same.
+int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T, int S = 1, bool seq = false,
+                     const SmoothedLoss* smoothed = nullptr) {
     const ovc_model* m = e.m;
     Workspace& w = t.w;
     hipStream_t s = e.stream;
@@ -2184,6 +2196,9 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
     e.gemm_class = 3;
     if (seq)
         RUN(ovc_bw_dlogit(w.logits, ldt, w.lse, w.tgt, t.w_row, rows, V, t.dl_t, t.dl, ldv, s));
+    else if (smoothed)
+        RUN(ovc_bw_xent_smoothed(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, *smoothed, t.lp_part, t.lp_sum, t.w_row, t.loss,
+                                 t.dl_t, t.dl, ldv, s));
     else
         RUN(ovc_bw_xent(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
     // decoder output: d(out) = dlogit . fc, d(fc) = dlogit^T . out
@@ -2296,15 +2311,17 @@ uint64_t train_hash(const ovc_model* m, const ovc_model* grads) {
     return hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull);
 }
 
-// ovc_forward_backward (drop == nullptr) and ovc_forward_backward_dropout (drop: at least one site active; seed = the caller's)
+// ovc_forward_backward (drop == nullptr) and ovc_forward_backward_dropout (drop: at least one site active; seed = the caller's);
+// smoothed: ovc_forward_backward_smoothed's loss (loss_hash: its parameters, part of the graph key), nullptr for the two above
 int forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, const int64_t* tokens,
                      const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* loss_out, int use_graph,
-                     ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash) {
+                     ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash, const SmoothedLoss* smoothed = nullptr,
+                     uint64_t loss_hash = 0) {
     if (!train_ok(m, B, N, T) || !grads || !grads_ok(m, grads) || !features || !tokens || !targets || !workspace || !loss_out)
         return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr);
+    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr, 1, false, smoothed != nullptr);
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
@@ -2313,12 +2330,15 @@ int forward_backward(const ovc_model* m, const ovc_model* grads, const float* fe
     // the kernels that read the caller's inputs, outside the captured body
     TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
     TRY(stage_train_inputs(e, t, features, tokens, targets, B * T, T, B * N));
-    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T); };
+    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T, 1, false, smoothed); };
     if (!use_graph) {
         TRY(body(e));
     } else {
-        // the dropout constants are baked into the launches, so they are part of the key; never the seed (read from the workspace slot)
-        const GraphKey key{drop ? GraphKind::TrainDropout : GraphKind::Train, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, 0};
+        // the dropout constants are baked into the launches, so they are part of the key; never the seed (read from the workspace slot).
+        // So are the smoothed loss's constants: a kind of its own, its parameters in the hash
+        const GraphKey key = smoothed
+            ? GraphKey{GraphKind::TrainSmoothed, train_hash(m, grads) ^ drop_hash ^ loss_hash, workspace, B, N, T, drop ? 1 : 0}
+            : GraphKey{drop ? GraphKind::TrainDropout : GraphKind::Train, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, 0};
         TRY(replay_or_issue(key, e.stream, m, body, drop));
     }
     if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
@@ -2355,6 +2375,54 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                 nullptr, nullptr, 0);
     return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
                             &plan, dropout->seed, hash);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training: ovc_forward_backward_smoothed (label-smoothed cross-entropy)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// x log x with 0 log 0 = 0 (torch.xlogy, which KLDivLoss applies to the target distribution)
+double xlogx(double x) { return x > 0 ? x * std::log(x) : 0.0; }
+
+// The loss's constants in float64, rounded once; OVC_EINVAL outside 0 <= s < 1 (NaN included), for an unknown reduction and for
+// s > 0 with V <= 2 (u = s / (V - 2))
+int make_smoothed_loss(const ovc_model* m, const ovc_loss* loss, long rows, SmoothedLoss* out, uint64_t* hash) {
+    const double s = loss->smoothing;
+    if (!(s >= 0.0 && s < 1.0)) return OVC_EINVAL;
+    if (loss->reduction != OVC_LOSS_MEAN && loss->reduction != OVC_LOSS_TOKENS) return OVC_EINVAL;
+    if (s > 0.0 && m->vocab <= 2) return OVC_EINVAL;
+    const double conf = 1.0 - s, u = s > 0.0 ? s / (m->vocab - 2) : 0.0;
+    out->conf = (float)conf; out->u = (float)u;
+    out->C = (float)(xlogx(conf) + (m->vocab - 2) * xlogx(u));
+    out->w_mean = (float)(1.0 / ((double)rows * m->vocab));
+    out->reduction = loss->reduction;
+    const struct { float s; int32_t reduction; } key{loss->smoothing, loss->reduction};
+    *hash = (hash_bytes(&key, sizeof(key)) | 1) * 0xD6E8FEB86659FD93ull;
+    return OVC_OK;
+}
+}  // namespace
+
+extern "C" size_t ovc_train_smoothed_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
+    if (!(dropout ? dropout_train_ok(m, B, N, T) : train_ok(m, B, N, T))) return 0;
+    return carve_train(m, nullptr, B, N, T, dropout != 0, 1, false, true).bytes;
+}
+
+extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                             int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                             size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                             const ovc_loss* loss, const ovc_dropout* dropout) {
+    (void)boxes;
+    if (!loss || !m || !(dropout ? dropout_train_ok(m, B, N, T) : train_ok(m, B, N, T))) return OVC_EINVAL;
+    if (dropout && !dropout->seed) return OVC_EINVAL;
+    SmoothedLoss sl{};
+    uint64_t loss_hash = 0;
+    TRY(make_smoothed_loss(m, loss, (long)B * T, &sl, &loss_hash));
+    DropPlan plan{};
+    uint64_t hash = 0;
+    bool any = false;
+    if (dropout) TRY(make_drop_plan(dropout, &plan, &hash, &any));
+    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
+                            any ? &plan : nullptr, any ? dropout->seed : nullptr, any ? hash : 0, &sl, loss_hash);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -92,6 +92,31 @@ def check_caption_ids(ids, name, batch, max_len, vocab):
     return T
 
 
+def checked_label_smoothing(label_smoothing, reduction, what, vocab):
+    """The arguments of the label-smoothed cross-entropy (``xe_loss`` / ``xe_step`` / ``forward_backward(loss=...)``), or the
+    refusal that names the offending one.  ``label_smoothing=None``: the plain loss -- ``None`` is returned, and a ``reduction``
+    given with it is refused.  Otherwise ``(s, reduction)``: ``s`` a Python number with ``0 <= s < 1`` (``s > 0`` needs more than
+    two words: ``u = s / (V - 2)``), ``reduction`` ``"mean"`` (the default, the reference's ``1 / (R V)``) or ``"tokens"``."""
+    if label_smoothing is None:
+        if reduction is not None:
+            raise native.OvcError("{}: reduction={!r} belongs to the label-smoothed loss; pass label_smoothing as well "
+                                  "(label_smoothing=0.0, reduction='tokens' is the plain loss)".format(what, reduction))
+        return None
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)):
+        raise native.OvcError("{}: label_smoothing must be a Python number (got {})".format(what, type(label_smoothing).__name__))
+    s = float(label_smoothing)
+    if not 0.0 <= s < 1.0:                      # NaN fails both comparisons
+        raise native.OvcError("{}: label_smoothing must satisfy 0 <= s < 1 (got {!r})".format(what, label_smoothing))
+    if reduction is None:
+        reduction = "mean"
+    if not isinstance(reduction, str) or reduction not in native.LOSS_REDUCTIONS:
+        raise native.OvcError("{}: reduction must be 'mean' or 'tokens' (got {!r})".format(what, reduction))
+    if s > 0.0 and vocab <= 2:
+        raise native.OvcError("{}: label_smoothing > 0 spreads s over V - 2 words and needs a vocabulary of more than 2 "
+                              "(V = {})".format(what, vocab))
+    return s, reduction
+
+
 EARLY_EXIT_MODES = (False, True, "device")
 
 
@@ -695,7 +720,7 @@ class CaptionEngine:
         """The parameters ``forward_backward`` returns gradients for, in the order of its list."""
         return [p for p, _ in _grad_slots(self.model)]
 
-    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None):
+    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -708,7 +733,18 @@ class CaptionEngine:
         ``(seed, site, row, col)`` only, so the result is as deterministic as without; with no ``p > 0`` this is the plain call.
 
         ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer (``BaseTransformer.xe_step``: nothing
-        is handed out, and the captured graph, whose key holds the gradient table, is replayed whatever the allocator does)."""
+        is handed out, and the captured graph, whose key holds the gradient table, is replayed whatever the allocator does).
+
+        ``loss=(smoothing, reduction)``: the label-smoothed cross-entropy in place of the NLL
+        (``ovc_forward_backward_smoothed``; ``checked_label_smoothing`` states the arguments, ``BaseTransformer.xe_loss`` the
+        loss).  The loss parameters are part of the graph key.  ``(0.0, "tokens")`` is the plain loss and takes the plain
+        path: the same launches, the same bits."""
+        if loss is not None:
+            if not isinstance(loss, (tuple, list)) or len(loss) != 2:
+                raise native.OvcError("forward_backward: loss must be a (label_smoothing, reduction) pair (got {!r})".format(loss))
+            loss = checked_label_smoothing(loss[0], loss[1], "forward_backward", self.desc.vocab)
+            if loss == (0.0, "tokens"):
+                loss = None
         self._check_trainable()
         d = self.desc
         features, boxes = self._checked_inputs(features, boxes)
@@ -719,8 +755,11 @@ class CaptionEngine:
             raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
                 tuple(targets.shape), tuple(caption_tokens.shape)))
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        sizer = self.lib.ovc_train_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_workspace_bytes
-        need = sizer(ctypes.byref(d), B, N, T)
+        if loss is not None:
+            need = self.lib.ovc_train_smoothed_workspace_bytes(ctypes.byref(d), B, N, T, 1 if table_drop is not None else 0)
+        else:
+            sizer = self.lib.ovc_train_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_workspace_bytes
+            need = sizer(ctypes.byref(d), B, N, T)
         if need == 0:
             raise native.OvcError("unsupported training configuration (B={}, N={}, T={}, V={}; see ovc_train_workspace_bytes)"
                                   .format(B, N, T, d.vocab))
@@ -732,16 +771,21 @@ class CaptionEngine:
         arena, table, grads = self._gradient_arena() if arena is None else arena
         stream = torch.cuda.current_stream().cuda_stream
         ws = self._cached_workspace(self._train_workspaces, stream, need)
-        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        out = torch.empty((), dtype=torch.float32, device=self.device)
         graph = self.use_graph if use_graph is None else bool(use_graph)
         args = (ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
-                tokens.data_ptr(), targets.data_ptr(), T, ws.data_ptr(), need, loss.data_ptr(), 1 if graph else 0,
+                tokens.data_ptr(), targets.data_ptr(), T, ws.data_ptr(), need, out.data_ptr(), 1 if graph else 0,
                 native.stream_handle())
-        if table_drop is None:
+        if loss is not None:
+            table_loss = native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])
+            check(self.lib.ovc_forward_backward_smoothed(*args, ctypes.byref(table_loss),
+                                                         None if table_drop is None else ctypes.byref(table_drop)),
+                  "ovc_forward_backward_smoothed")
+        elif table_drop is None:
             check(self.lib.ovc_forward_backward(*args), "ovc_forward_backward")
         else:
             check(self.lib.ovc_forward_backward_dropout(*args, ctypes.byref(table_drop)), "ovc_forward_backward_dropout")
-        return loss, arena, grads
+        return out, arena, grads
 
     def _gradient_arena(self):
         """A fresh flat fp32 buffer for every gradient of ``gradient_parameters()``, the ``ovc_model`` table pointing into it and

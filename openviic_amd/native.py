@@ -56,6 +56,15 @@ class Dropout(ctypes.Structure):
                 ("dec", (c_float * 4) * OVC_MAX_LAYERS)]
 
 
+class Loss(ctypes.Structure):
+    """``ovc_loss``: the label-smoothed cross-entropy's ``smoothing`` and ``reduction`` (``LOSS_MEAN`` / ``LOSS_TOKENS``)."""
+    _fields_ = [("smoothing", c_float), ("reduction", c_int32)]
+
+
+LOSS_MEAN, LOSS_TOKENS = 0, 1
+LOSS_REDUCTIONS = {"mean": LOSS_MEAN, "tokens": LOSS_TOKENS}
+
+
 class Model(ctypes.Structure):
     _fields_ = [
         ("abi", c_int32), ("enc_kind", c_int32), ("dec_kind", c_int32),
@@ -163,6 +172,9 @@ SIGNATURES = {
     "ovc_forward_backward_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                              c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Dropout)]),
     "ovc_dropout_mask": (c_int, [c_void_p, c_int, c_long, c_long, c_float, c_void_p, c_void_p]),
+    "ovc_train_smoothed_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_forward_backward_smoothed": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Loss), POINTER(Dropout)]),
     "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
@@ -195,7 +207,7 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout",
                  "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step", "ovc_debug_attention_mem_backward",
                  "ovc_scst_advantage_bytes", "ovc_scst_advantage", "ovc_caption_metrics_bytes", "ovc_caption_metrics",
-                 "ovc_grad_norm")
+                 "ovc_grad_norm", "ovc_train_smoothed_workspace_bytes", "ovc_forward_backward_smoothed")
 
 _lib = None
 

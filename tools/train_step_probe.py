@@ -24,6 +24,13 @@ read, p, m, v written) over its time as achieved bytes/s, against the 6.29 TB/s 
 ``optimizer.grad_norm(gradients)`` alone, back to back, with the 4 bytes per element it reads as achieved bytes/s.  ``xe_step``
 without ``max_norm`` launches what it launched before the keyword existed, so it is the baseline of the same run.
 
+--label-smoothing S [--reduction mean|tokens] (with --optimizer none and one --variant): the plain step and the step under
+``model.xe_loss(items, label_smoothing=S, reduction=...)`` (``ovc_forward_backward_smoothed``) alternate in ONE process on one
+model -- per batch size ``--warmup`` steps of each, then ``--rounds`` rounds of ``--steps`` steps of each in turn -- so the
+smoothed step's time stands next to the plain step's from the same build and run.  ``extra_mb`` is what the smoothed loss head
+reads and writes beyond the plain one from the shapes: one more pass over the stored logits (R * V * 4 bytes) and the slice
+partials.
+
 Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
 end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
 times 3 -- the backward has two products per forward product -- over the step time, against the nominal 157.3 TF fp32 matrix
@@ -121,6 +128,37 @@ def optimizer_probe(args, build, items, B):
     return rows
 
 
+def smoothing_probe(args, model, items, B, T, N, V):
+    """The plain step and the label-smoothed step in turn on one model: rows ``loss = "plain"`` / ``"smoothed"`` per round."""
+    def step(**kw):
+        model.zero_grad(set_to_none=True)
+        model.xe_loss(items, dropout=args.dropout, **kw).backward()
+    forms = {"plain": {}, "smoothed": dict(label_smoothing=args.label_smoothing, reduction=args.reduction)}
+    for kw in forms.values():
+        for _ in range(args.warmup):
+            step(**kw)
+    torch.cuda.synchronize()
+    eng = model._fused_engine()
+    rows = []
+    for rnd in range(args.rounds):
+        for name, kw in forms.items():
+            ms = events_ms(lambda: step(**kw), args.steps)
+            if name == "plain":
+                sizer = eng.lib.ovc_train_dropout_workspace_bytes if args.dropout else eng.lib.ovc_train_workspace_bytes
+                ws = sizer(eng.desc, B, N, T)
+            else:
+                ws = eng.lib.ovc_train_smoothed_workspace_bytes(eng.desc, B, N, T, 1 if args.dropout else 0)
+            row = dict(variant=args.variant, B=B, T=T, N=N, dropout=args.dropout, loss=name, round=rnd, ms_per_step=round(ms, 3),
+                       workspace_mb=round(ws / 2 ** 20, 1))
+            if name == "smoothed":
+                R = B * T
+                row.update(label_smoothing=args.label_smoothing, reduction=args.reduction or "mean",
+                           extra_mb=round(4.0 * (R * V + 2 * R * ((V + 63) // 64)) / 1e6, 1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def variant_dims(variant):
     return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40)}.get(variant, {})
 
@@ -182,12 +220,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
     ap.add_argument("--max-norm", type=float, default=None,
                     help="with --optimizer ... xe_step: also time model.xe_step(items, optimizer, max_norm=C)")
+    ap.add_argument("--label-smoothing", type=float, default=None,
+                    help="with --optimizer none and one --variant: alternate the plain step and the label-smoothed step")
+    ap.add_argument("--reduction", default=None, choices=["mean", "tokens"], help="the smoothed loss's reduction (default mean)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if "none" in args.optimizer and len(args.optimizer) > 1:
         ap.error("--optimizer none stands alone")
     if args.max_norm is not None and "xe_step" not in args.optimizer:
         ap.error("--max-norm goes with --optimizer ... xe_step")
+    if args.label_smoothing is not None and (args.optimizer != ["none"] or len(args.variant) > 1):
+        ap.error("--label-smoothing goes with --optimizer none and one --variant")
+    if args.reduction is not None and args.label_smoothing is None:
+        ap.error("--reduction goes with --label-smoothing")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
@@ -215,6 +260,9 @@ def main():
         items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
         if args.optimizer != ["none"]:
             results += optimizer_probe(args, build, items, B)
+            continue
+        if args.label_smoothing is not None:
+            results += smoothing_probe(args, model, items, B, T, N, V)
             continue
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)

@@ -33,6 +33,28 @@ ScstStep.__doc__ = """What ``BaseTransformer.scst_step`` returns: detached devic
 search's sequences, ``reward`` ``[B, k]`` float32 their rewards."""
 
 
+def _checked_step_optimizer(optimizer, what, eng=None):
+    """The optimizer rules of the one-call steps, each at its own place in the order of refusals: the type first of all (without
+    ``eng``), the parameter set once the engine has passed ``_check_trainable`` (with it)."""
+    from . import optim as _optim
+    if not isinstance(optimizer, _optim.Adam):
+        raise engine.native.OvcError("{}: optimizer must be an openviic_amd.optim.Adam (got {})".format(
+            what, type(optimizer).__name__))
+    if eng is None:
+        return
+    wanted = [p for p in eng.gradient_parameters() if p.requires_grad]
+    held = {id(p) for group in optimizer.param_groups for p in group["params"] if p.requires_grad}
+    if held != {id(p) for p in wanted}:
+        raise engine.native.OvcError(
+            "{}: optimizer must hold exactly the model's trainable parameters ({} of them); it holds {} trainable "
+            "parameters, {} of them the model's".format(what, len(wanted), len(held), len(held & {id(p) for p in wanted})))
+
+
+def _apply_step_gradients(eng, optimizer, grads, max_norm):
+    """The tail of the one-call steps: the Adam launch reading the step arena's views in place."""
+    optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
+
+
 class _XeLoss(torch.autograd.Function):
     """The reference's training loss on the engine.  ``forward`` runs ``ovc_forward_backward`` -- the forward AND the whole
     backward -- and keeps the gradients; ``backward`` hands them out scaled by ``grad_output`` (``ovc_scale``).  A loss whose
@@ -246,27 +268,20 @@ class BaseTransformer(Module):
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
         all-reduce.  A data-parallel run keeps the four lines above."""
         from . import optim as _optim
-        if not isinstance(optimizer, _optim.Adam):
-            raise engine.native.OvcError("xe_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
-                type(optimizer).__name__))
+        _checked_step_optimizer(optimizer, "xe_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
         smoothed = engine.checked_label_smoothing(label_smoothing, reduction, "xe_step", len(self.vocab))
         probs = self._xe_dropout_probs(dropout, "xe_step")
         eng = self._fused_engine()
         eng._check_trainable()
-        wanted = [p for p in eng.gradient_parameters() if p.requires_grad]
-        held = {id(p) for group in optimizer.param_groups for p in group["params"] if p.requires_grad}
-        if held != {id(p) for p in wanted}:
-            raise engine.native.OvcError(
-                "xe_step: optimizer must hold exactly the model's trainable parameters ({} of them); it holds {} trainable "
-                "parameters, {} of them the model's".format(len(wanted), len(held), len(held & {id(p) for p in wanted})))
+        _checked_step_optimizer(optimizer, "xe_step", eng)
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
         slots = eng.step_arena()
         loss, _, grads = eng.forward_backward(input_features[self.feature_field], boxes, input_features["caption_tokens"],
                                               input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots,
                                               loss=smoothed)
-        optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
+        _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
@@ -304,9 +319,7 @@ class BaseTransformer(Module):
         from . import optim as _optim
         from . import scst as _scst
         from .cider import CiderCorpus
-        if not isinstance(optimizer, _optim.Adam):
-            raise engine.native.OvcError("scst_step: optimizer must be an openviic_amd.optim.Adam (got {})".format(
-                type(optimizer).__name__))
+        _checked_step_optimizer(optimizer, "scst_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "scst_step")
         corpus = reward if isinstance(reward, CiderCorpus) else None
         if corpus is None and not callable(reward):
@@ -318,12 +331,7 @@ class BaseTransformer(Module):
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
         eng._check_trainable()
-        wanted = [p for p in eng.gradient_parameters() if p.requires_grad]
-        held = {id(p) for group in optimizer.param_groups for p in group["params"] if p.requires_grad}
-        if held != {id(p) for p in wanted}:
-            raise engine.native.OvcError(
-                "scst_step: optimizer must hold exactly the model's trainable parameters ({} of them); it holds {} trainable "
-                "parameters, {} of them the model's".format(len(wanted), len(held), len(held & {id(p) for p in wanted})))
+        _checked_step_optimizer(optimizer, "scst_step", eng)
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         feats, boxes = eng._checked_inputs(input_features[self.feature_field], boxes)
         B = feats.shape[0]
@@ -359,7 +367,7 @@ class BaseTransformer(Module):
             _, grads = eng.sequence_backward(feats, None, outs, g, dropout=drop, slots=slots, beam_size=k, arena=eng.step_arena())
         else:
             _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena())
-        optimizer.apply_gradients({p: gr for p, gr in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
+        _apply_step_gradients(eng, optimizer, grads, max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
 
     def _search_dropout_probs(self):

@@ -1298,14 +1298,17 @@ extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const 
 namespace {
 // What a cached launch sequence is, and with it what its key's k / out_size hold.  The first member of GraphKey and without a
 // default: a key cannot be built without naming its kind, so two call sites never share entries by accident.
+// The rule: a kind per launch sequence that differs in its kernels -- for training, one per loss head (train_graph_key) -- and
+// every constant baked into the launches either in the key's fields (shapes, workspace) or in its hash (model contents, gradient
+// table, dropout constants, loss parameters, the search's k).  Two calls share an entry only if all of these agree; a dropout
+// call with every p == 0 is the plain call and shares the plain entry.
 enum class GraphKind {
     Search,             // ovc_beam_search_graph and the per-step graphs of ovc_beam_search_early (k = beam, out_size)
     Forward,            // ovc_forward (k = T, out_size = want_logp)
     GatedSearch,        // ovc_beam_search_gated (k = beam, out_size)
-    Train,              // ovc_forward_backward (k = T)
-    TrainDropout,       // ovc_forward_backward_dropout (k = T)
+    Train,              // ovc_forward_backward, with or without dropout (k = T, out_size = 1)
     SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
-    TrainSmoothed,      // ovc_forward_backward_smoothed (k = T, out_size = with dropout; the loss parameters in the hash)
+    TrainSmoothed,      // ovc_forward_backward_smoothed, with or without dropout (k = T, out_size = 1)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1807,14 +1810,14 @@ struct TrainWs {
     // encoder memory slots (train_memory(m) > 0 only; ovc_bw_attention_mem): each image's share of d(m_k) / d(m_v),
     // [B][memory][h_enc dk_enc] each, and the partials of their sum over the images [ceil(B / 64)][memory h_enc dk_enc]
     float* mem_part_k; float* mem_part_v; float* mem_colpart;
-    // dropout (carve_train(..., dropout = true) only; ovc_train_dropout_workspace_bytes)
+    // dropout (TrainCall::plan only; ovc_train_dropout_workspace_bytes)
     float* dproj;                 // [Rmax][d] gradient of a masked projection: keep * s * dy
     int64_t* seed;                // the step's seed, copied in outside the captured body
-    // sequences (carve_train(..., seq = true) only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
+    // sequences (LossHead::RowWeights only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
     // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
     int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
     int32_t* maskrow;             // [rows] sequences with dropout: the mask row of every decoder row (seq_maskrow_kernel)
-    // label smoothing (carve_train(..., smoothed = true) only; ovc_train_smoothed_workspace_bytes): the rows' sums of
+    // label smoothing (LossHead::SmoothedXent only; ovc_train_smoothed_workspace_bytes): the rows' sums of
     // log-probabilities [rows] and their slice partials [ceil(V / 64)][rows padded to 4]
     float* lp_sum; float* lp_part;
     // the cross-level tail (bw_cross_level_tail; cross-level models only), rows B*N: the leaky-ReLU gradients dh [B*N][d] (mlp2's,
@@ -1831,9 +1834,31 @@ inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 // the memory slots of the encoder layers' self-attention in a training call (train_ok: every layer has them, or none)
 inline int train_memory(const ovc_model* m) { return m->enc[0].att.m_k ? m->memory : 0; }
 
-// S > 1 (with seq): S sequences per image, rows = B*S*T (run_forward_decoder)
-TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dropout = false, int S = 1, bool seq = false,
-                    bool smoothed = false) {
+// The loss head of a training call's body: issue_train_body switches on it, and nothing else does.
+enum class LossHead {
+    Xent,           // ovc_bw_xent: NLLLoss(ignore_index = pad) and its dlogit
+    SmoothedXent,   // ovc_bw_xent_smoothed: the label-smoothed loss, its constants in TrainCall::smoothed
+    RowWeights,     // ovc_bw_dlogit: the caller's row weights and no loss -- the sequence form, S sequences per image
+};
+
+// One training call, described once.  The ten exported functions fill one of these, and the scope (call_ok), the workspace
+// layout and size (carve_train), the captured body (issue_train_body), the graph key (train_graph_key) and the launches around
+// the body (run_train_call) are functions of it: a sizer and the entry point that carves its buffer cannot disagree.
+struct TrainCall {
+    // the members every call states, first: TrainCall{B, N, S, T, head}; the rest is zero unless a form fills it in
+    int B, N, S, T;                                 // S sequences per image, rows = B*S*T (run_forward_decoder); 1 but for RowWeights
+    LossHead head;
+    SmoothedLoss smoothed; uint64_t loss_hash;      // SmoothedXent: the loss's constants and their hash (make_smoothed_loss)
+    // Dropout: the plan, or nullptr when no site is active (the plain call, launch for launch), with the caller's seed and the
+    // hash of the plan's constants (bind_dropout).  A sizer binds an empty plan: its presence alone adds the dropout buffers
+    // and narrows the scope.
+    DropPlan* plan; const int64_t* seed; uint64_t drop_hash;
+    int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
+    bool seq() const { return head == LossHead::RowWeights; }
+};
+
+TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
+    const int B = c.B, N = c.N, S = c.S, T = c.T;
     TrainWs t{};
     t.w = carve_forward(m, base, B, N, T, 1, S);
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
@@ -1887,15 +1912,15 @@ TrainWs carve_train(const ovc_model* m, void* base, int B, int N, int T, bool dr
         t.mem_part_k = a.take<float>((size_t)B * mem * ehk); t.mem_part_v = a.take<float>((size_t)B * mem * ehk);
         t.mem_colpart = a.take<float>((((size_t)B + 63) / 64) * mem * ehk);
     }
-    if (dropout) {
+    if (c.plan) {
         t.dproj = a.take<float>(R * d);
         t.seed = a.take<int64_t>(2);
     }
-    if (seq) {
+    if (c.seq()) {
         t.seq_tok = a.take<int64_t>(rows); t.seq_tgt = a.take<int64_t>(rows); t.seq_keep = a.take<uint8_t>(rows);
-        if (dropout) t.maskrow = a.take<int32_t>(rows);
+        if (c.plan) t.maskrow = a.take<int32_t>(rows);
     }
-    if (smoothed) {
+    if (c.head == LossHead::SmoothedXent) {
         t.lp_sum = a.take<float>(rows);
         t.lp_part = a.take<float>(ovc_bw_smoothed_part_floats((int)rows, m->vocab));
     }
@@ -1948,6 +1973,19 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
 // Dropout training (ovc_forward_backward_dropout) covers the plain encoder only: the cross-level tail applies its one nn.Dropout
 // twice and has no site of its own.
 bool dropout_train_ok(const ovc_model* m, int B, int N, int T) { return train_ok(m, B, N, T) && m->enc_kind == OVC_ENC_PLAIN; }
+
+// The scope of a training call, for its sizer and its entry point alike: train_ok over the B*S sequences, under dropout the
+// dropout scope.
+bool call_ok(const ovc_model* m, const TrainCall& c) {
+    if (c.S < 1 || c.B < 1 || (long)c.B * c.S > (1L << 24)) return false;
+    return c.plan ? dropout_train_ok(m, c.B * c.S, c.N, c.T) : train_ok(m, c.B * c.S, c.N, c.T);
+}
+
+// A sequence call with dropout recomputes under the masks of the search that made its sequences: that search's limits
+// (ovc_beam_search_dropout), full-length sequences and its slot table.  After call_ok: m has been checked.
+bool search_ok(const ovc_model* m, const TrainCall& c) {
+    return c.slots && c.k >= 1 && c.k <= OVC_MAX_BEAM && c.S <= c.k && c.T == m->max_len && (long)c.B * c.k * c.T <= (1L << 30);
+}
 
 inline float* out_ptr(const float* p) { return const_cast<float*>(p); }
 
@@ -2052,9 +2090,10 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
 }
 
 // S sequences per image (run_forward_decoder): the cross-attention of image b over its S*T query rows, the self-attention per sequence
-int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, int B, int N, int T, const float* xin, const float* dout,
-                     float* dxin, float* denc_prev, float* denc_next, int S = 1) {
+int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const TrainCall& c, const float* xin, const float* dout,
+                     float* dxin, float* denc_prev, float* denc_next) {
     const ovc_model* m = e.m;
+    const int B = c.B, N = c.N, S = c.S, T = c.T;
     const Workspace& w = t.w;
     const DecTape& p = t.tape.dec[l];
     const ovc_dec_layer& dl = m->dec[l];
@@ -2177,12 +2216,12 @@ int bw_cross_level_tail(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N
     return OVC_OK;
 }
 
-// seq (ovc_sequence_backward): S sequences per image, and the row weights t.w_row come from the caller's grad_logp (written before the
-// body) instead of the cross-entropy's: the dlogit alone, no loss.
-// smoothed (ovc_forward_backward_smoothed): the label-smoothed loss head in place of the cross-entropy's; the sweep behind it is the same.
-int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, int T, int S = 1, bool seq = false,
-                     const SmoothedLoss* smoothed = nullptr) {
+// The captured body of a training call: the forward onto the tape, the call's loss head, one reverse sweep -- the same sweep
+// behind every head.  RowWeights (ovc_sequence_backward): the row weights t.w_row come from the caller's grad_logp, written before
+// the body, instead of the cross-entropy's: the dlogit alone, no loss.
+int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall& c) {
     const ovc_model* m = e.m;
+    const int B = c.B, N = c.N, S = c.S, T = c.T;
     Workspace& w = t.w;
     hipStream_t s = e.stream;
     const int d = m->d_model, V = m->vocab, rows = B * S * T, BN = B * N, L = m->n_dec;
@@ -2194,13 +2233,18 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
     e.gemm_class = 3;
-    if (seq)
-        RUN(ovc_bw_dlogit(w.logits, ldt, w.lse, w.tgt, t.w_row, rows, V, t.dl_t, t.dl, ldv, s));
-    else if (smoothed)
-        RUN(ovc_bw_xent_smoothed(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, *smoothed, t.lp_part, t.lp_sum, t.w_row, t.loss,
-                                 t.dl_t, t.dl, ldv, s));
-    else
+    switch (c.head) {
+    case LossHead::Xent:
         RUN(ovc_bw_xent(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
+        break;
+    case LossHead::SmoothedXent:
+        RUN(ovc_bw_xent_smoothed(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, c.smoothed, t.lp_part, t.lp_sum, t.w_row, t.loss,
+                                 t.dl_t, t.dl, ldv, s));
+        break;
+    case LossHead::RowWeights:
+        RUN(ovc_bw_dlogit(w.logits, ldt, w.lse, w.tgt, t.w_row, rows, V, t.dl_t, t.dl, ldv, s));
+        break;
+    }
     // decoder output: d(out) = dlogit . fc, d(fc) = dlogit^T . out
     const float* dec_out = t.tape.dec[L - 1].out;
     RUN(ovc_bw_transpose(m->fc, d, V, d, t.fc_t, ldv, ldv, s));
@@ -2212,8 +2256,8 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
     int cur = 0, enc_cur = 0;
     for (int l = L - 1; l >= 0; --l) {
         const float* xin = l == 0 ? w.x : t.tape.dec[l - 1].out;
-        TRY(bw_decoder_layer(e, t, gr, l, B, N, T, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
-                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1], S));
+        TRY(bw_decoder_layer(e, t, gr, l, c, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
+                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1]));
         if (l != L - 1) enc_cur ^= 1;
         cur ^= 1;
     }
@@ -2255,15 +2299,6 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N, i
     return OVC_OK;
 }
 
-}  // namespace
-
-extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, int T) {
-    if (!train_ok(m, B, N, T)) return 0;
-    return carve_train(m, nullptr, B, N, T).bytes;
-}
-
-namespace {
-
 // The per-site constants of a caller's table; OVC_EINVAL for a p outside [0, 1) (NaN included).  *any: a site is active.
 int make_drop_plan(const ovc_dropout* dropout, DropPlan* plan, uint64_t* hash, bool* any) {
     float p[OVC_DROPOUT_SITES] = {};
@@ -2284,13 +2319,28 @@ int make_drop_plan(const ovc_dropout* dropout, DropPlan* plan, uint64_t* hash, b
     return OVC_OK;
 }
 
+// A caller's ovc_dropout table on a training call: the call's (plan, seed, hash) -- or, with no site active, the plain call
+// (plan == nullptr: the plain layout, launches, graph entry and bits).  The dropout scope and the table are checked either way.
+int bind_dropout(const ovc_model* m, const ovc_dropout* dropout, DropPlan* plan, TrainCall& c) {
+    c.plan = plan;
+    if (!dropout || !dropout->seed || !call_ok(m, c) || (c.seq() && !search_ok(m, c))) return OVC_EINVAL;
+    bool any = false;
+    TRY(make_drop_plan(dropout, plan, &c.drop_hash, &any));
+    if (any) {
+        c.seed = dropout->seed;
+    } else {
+        c.plan = nullptr; c.drop_hash = 0; c.k = 0; c.slots = nullptr;
+    }
+    return OVC_OK;
+}
+
 // Binds a training call's Engine to its dropout plan: the seed slot is refreshed here, outside the captured body -- a replayed
 // graph reads this call's seed.
-int bind_train_drop(Engine& e, TrainWs& t, DropPlan* drop, const int64_t* seed) {
-    if (!drop) return OVC_OK;
-    if (hipMemcpyAsync(t.seed, seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    drop->seed = t.seed;
-    e.drop = drop;
+int bind_train_drop(Engine& e, TrainWs& t, const TrainCall& c) {
+    if (!c.plan) return OVC_OK;
+    if (hipMemcpyAsync(t.seed, c.seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    c.plan->seed = t.seed;
+    e.drop = c.plan;
     return OVC_OK;
 }
 
@@ -2306,58 +2356,89 @@ int stage_train_inputs(Engine& e, TrainWs& t, const float* features, const int64
     return ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream);
 }
 
-// The body writes the gradient buffers: their table is part of the key, next to the model's contents.
-uint64_t train_hash(const ovc_model* m, const ovc_model* grads) {
-    return hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull);
+// The graph key of a training call, built here and nowhere else (the rule: GraphKind).  The body writes the gradient buffers, so
+// their table is hashed next to the model's contents; so are the constants baked into the launches -- the dropout plan's (never
+// the seed: it is read from its workspace slot), the smoothed loss's, the search's k.  Each is 0 for a call without it.
+GraphKey train_graph_key(const ovc_model* m, const ovc_model* grads, const void* workspace, const TrainCall& c) {
+    const GraphKind kind = c.seq() ? GraphKind::SequenceBackward
+                           : c.head == LossHead::SmoothedXent ? GraphKind::TrainSmoothed : GraphKind::Train;
+    const uint64_t hash = hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ c.drop_hash ^
+                          c.loss_hash ^ ((uint64_t)c.k << 56);
+    return GraphKey{kind, hash, workspace, c.B, c.N, c.T, c.S};
 }
 
-// ovc_forward_backward (drop == nullptr) and ovc_forward_backward_dropout (drop: at least one site active; seed = the caller's);
-// smoothed: ovc_forward_backward_smoothed's loss (loss_hash: its parameters, part of the graph key), nullptr for the two above
-int forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, const int64_t* tokens,
-                     const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* loss_out, int use_graph,
-                     ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash, const SmoothedLoss* smoothed = nullptr,
-                     uint64_t loss_hash = 0) {
-    if (!train_ok(m, B, N, T) || !grads || !grads_ok(m, grads) || !features || !tokens || !targets || !workspace || !loss_out)
-        return OVC_EINVAL;
+// Every training entry point.  tokens / targets: the caller's caption and its targets, loss_out the loss; for RowWeights tokens are
+// the caller's ids [B][S][T], grad_logp their row weights, targets is unused and logp_out (optional) takes the recomputed
+// log-probabilities.  Launch order: the seed slot and, for sequences under dropout, the mask-row table; the kernels that read the
+// caller's inputs (feature projection, seq_inputs_kernel, tf_inputs_kernel, token and feature staging); the body -- captured on
+// the second call of its key when use_graph is set; the loss copy or seq_logp_kernel.  Only the body is ever captured.
+int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& c, const float* features, const int64_t* tokens,
+                   const int64_t* targets, const float* grad_logp, void* workspace, size_t workspace_bytes, float* loss_out,
+                   float* logp_out, int use_graph, ovc_stream stream) {
+    if (!call_ok(m, c) || !grads || !grads_ok(m, grads) || !features || !tokens || !workspace) return OVC_EINVAL;
+    if (c.seq() ? !grad_logp : (!targets || !loss_out)) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr, 1, false, smoothed != nullptr);
+    TrainWs t = carve_train(m, workspace, c);
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
-    TRY(bind_train_drop(e, t, drop, seed));
+    const int nseq = c.B * c.S, rows = nseq * c.T;
+    TRY(bind_train_drop(e, t, c));
+    if (c.seq() && c.plan) {
+        // the row table is refreshed here as well, outside the captured body
+        hipLaunchKernelGGL(seq_maskrow_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, c.slots, c.B, c.S, c.T, c.k, t.maskrow);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
 
     // the kernels that read the caller's inputs, outside the captured body
-    TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
-    TRY(stage_train_inputs(e, t, features, tokens, targets, B * T, T, B * N));
-    auto body = [&](Engine& ce) { return issue_train_body(ce, t, grads, B, N, T, 1, false, smoothed); };
-    if (!use_graph) {
-        TRY(body(e));
-    } else {
-        // the dropout constants are baked into the launches, so they are part of the key; never the seed (read from the workspace slot).
-        // So are the smoothed loss's constants: a kind of its own, its parameters in the hash
-        const GraphKey key = smoothed
-            ? GraphKey{GraphKind::TrainSmoothed, train_hash(m, grads) ^ drop_hash ^ loss_hash, workspace, B, N, T, drop ? 1 : 0}
-            : GraphKey{drop ? GraphKind::TrainDropout : GraphKind::Train, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, 0};
-        TRY(replay_or_issue(key, e.stream, m, body, drop));
+    TRY(run_encoder_inputs(e, t.w, features, nullptr, c.B, c.N));
+    if (c.seq()) {
+        hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, tokens, grad_logp, nseq, c.T, m->bos_idx,
+                           m->eos_idx, t.seq_tok, t.seq_tgt, t.seq_keep, t.w_row);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        tokens = t.seq_tok; targets = t.seq_tgt;
     }
-    if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    TRY(stage_train_inputs(e, t, features, tokens, targets, rows, c.T, c.B * c.N));
+    auto body = [&](Engine& ce) {
+        ce.maskrow = t.maskrow;         // nullptr but for sequences under dropout (carve_train)
+        return issue_train_body(ce, t, grads, c);
+    };
+    if (!use_graph) TRY(body(e));
+    else TRY(replay_or_issue(train_graph_key(m, grads, workspace, c), e.stream, m, body, c.plan));
+    if (!c.seq()) {
+        if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    } else if (logp_out) {
+        hipLaunchKernelGGL(seq_logp_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, t.w.logits, (long)pad4(rows), t.w.lse,
+                           t.w.tgt, t.seq_keep, rows, logp_out);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+    }
     return OVC_OK;
 }
 
+// A sizer builds the TrainCall its entry point will build; `sized`: an empty plan for the forms with dropout (TrainCall::plan).
+size_t train_workspace_bytes(const ovc_model* m, TrainCall c, bool dropout) {
+    DropPlan sized{};
+    if (dropout) c.plan = &sized;
+    return call_ok(m, c) ? carve_train(m, nullptr, c).bytes : 0;
+}
+
 }  // namespace
+
+extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, int T) {
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent}, false);
+}
 
 extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                     const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
                                     float* loss_out, int use_graph, ovc_stream stream) {
     (void)boxes;       // the plain encoder reads no boxes
-    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
-                            nullptr, nullptr, 0);
+    return run_train_call(m, grads, TrainCall{B, N, 1, T, LossHead::Xent}, features, tokens, targets, nullptr, workspace,
+                          workspace_bytes, loss_out, nullptr, use_graph, stream);
 }
 
 extern "C" size_t ovc_train_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T) {
-    if (!dropout_train_ok(m, B, N, T)) return 0;
-    return carve_train(m, nullptr, B, N, T, true).bytes;
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent}, true);
 }
 
 extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
@@ -2365,16 +2446,11 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                             size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                             const ovc_dropout* dropout) {
     (void)boxes;
-    if (!dropout || !dropout->seed || !m || !dropout_train_ok(m, B, N, T)) return OVC_EINVAL;
+    TrainCall c{B, N, 1, T, LossHead::Xent};
     DropPlan plan{};
-    uint64_t hash = 0;
-    bool any = false;
-    TRY(make_drop_plan(dropout, &plan, &hash, &any));
-    if (!any)
-        return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
-                                nullptr, nullptr, 0);
-    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
-                            &plan, dropout->seed, hash);
+    TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+                          stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2403,8 +2479,7 @@ int make_smoothed_loss(const ovc_model* m, const ovc_loss* loss, long rows, Smoo
 }  // namespace
 
 extern "C" size_t ovc_train_smoothed_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
-    if (!(dropout ? dropout_train_ok(m, B, N, T) : train_ok(m, B, N, T))) return 0;
-    return carve_train(m, nullptr, B, N, T, dropout != 0, 1, false, true).bytes;
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::SmoothedXent}, dropout != 0);
 }
 
 extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
@@ -2412,17 +2487,13 @@ extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model
                                              size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                              const ovc_loss* loss, const ovc_dropout* dropout) {
     (void)boxes;
-    if (!loss || !m || !(dropout ? dropout_train_ok(m, B, N, T) : train_ok(m, B, N, T))) return OVC_EINVAL;
-    if (dropout && !dropout->seed) return OVC_EINVAL;
-    SmoothedLoss sl{};
-    uint64_t loss_hash = 0;
-    TRY(make_smoothed_loss(m, loss, (long)B * T, &sl, &loss_hash));
+    TrainCall c{B, N, 1, T, LossHead::SmoothedXent};
     DropPlan plan{};
-    uint64_t hash = 0;
-    bool any = false;
-    if (dropout) TRY(make_drop_plan(dropout, &plan, &hash, &any));
-    return forward_backward(m, grads, features, B, N, tokens, targets, T, workspace, workspace_bytes, loss_out, use_graph, stream,
-                            any ? &plan : nullptr, any ? dropout->seed : nullptr, any ? hash : 0, &sl, loss_hash);
+    if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
+    if (!loss || !call_ok(m, c)) return OVC_EINVAL;
+    TRY(make_smoothed_loss(m, loss, (long)B * T, &c.smoothed, &c.loss_hash));
+    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+                          stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2432,84 +2503,25 @@ extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model
 // ids[b,s,:] -- equal to the search's log_probs, whose decoder builds the same masks (decoders.py:95-110).  The body is
 // issue_train_body over rows (b, s, t) with the encoder and the cross keys / values once per image; the cross-attention backward's
 // dk / dv sum over the image's S*T queries in ascending order, so the encoder output's gradient sums every beam of the image.  The
-// dlogit is bw_dlogit_kernel with w_row = -g on kept rows; no loss.  Launch order: the input kernels (feature projection,
-// seq_inputs_kernel, tf_inputs_kernel, token and feature staging: they read the caller's features / ids / grad_logp), the body
-// (captured on the second call of a (model contents, gradient table, workspace, B, N, S, T) when use_graph is set), then
-// seq_logp_kernel into the caller's logp_out.
-namespace {
-
-bool seq_ok(const ovc_model* m, int B, int N, int S, int T) {
-    return S >= 1 && B >= 1 && (long)B * S <= (1L << 24) && train_ok(m, B * S, N, T);
-}
-
-}  // namespace
-
+// dlogit is bw_dlogit_kernel with w_row = -g on kept rows; no loss.  The call is run_train_call's, its body captured on the second
+// call of a (model contents, gradient table, workspace, B, N, S, T) when use_graph is set.
 extern "C" size_t ovc_train_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    if (!seq_ok(m, B, N, S, T)) return 0;
-    return carve_train(m, nullptr, B, N, T, false, S, true).bytes;
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights}, false);
 }
-
-namespace {
-// ovc_sequence_backward (drop == nullptr) and ovc_sequence_backward_dropout (drop: at least one site active; the decoder sites'
-// mask rows come from the search's slot table)
-int sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, int B, int N, int S, const int64_t* ids,
-                      const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out, int use_graph,
-                      ovc_stream stream, DropPlan* drop, const int64_t* seed, uint64_t drop_hash, int k, const int32_t* slots) {
-    if (!seq_ok(m, B, N, S, T) || !grads || !grads_ok(m, grads) || !features || !ids || !grad_logp || !workspace) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    TrainWs t = carve_train(m, workspace, B, N, T, drop != nullptr, S, true);
-    t.w.tape = &t.tape;
-    if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
-    const int nseq = B * S, rows = nseq * T;
-    TRY(bind_train_drop(e, t, drop, seed));
-    if (drop) {
-        // the row table is refreshed here as well, outside the captured body
-        hipLaunchKernelGGL(seq_maskrow_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, slots, B, S, T, k, t.maskrow);
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        e.maskrow = t.maskrow;
-    }
-
-    // the kernels that read the caller's inputs, outside the captured body
-    TRY(run_encoder_inputs(e, t.w, features, nullptr, B, N));
-    hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, ids, grad_logp, nseq, T, m->bos_idx, m->eos_idx,
-                       t.seq_tok, t.seq_tgt, t.seq_keep, t.w_row);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    TRY(stage_train_inputs(e, t, features, t.seq_tok, t.seq_tgt, rows, T, B * N));
-    auto body = [&](Engine& ce) {
-        ce.maskrow = drop ? t.maskrow : nullptr;
-        return issue_train_body(ce, t, grads, B, N, T, S, true);
-    };
-    if (!use_graph) {
-        TRY(body(e));
-    } else {
-        const GraphKey key{GraphKind::SequenceBackward, train_hash(m, grads) ^ drop_hash, workspace, B, N, T, S};
-        TRY(replay_or_issue(key, e.stream, m, body, drop));
-    }
-    if (logp_out) {
-        hipLaunchKernelGGL(seq_logp_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, t.w.logits, (long)pad4(rows), t.w.lse,
-                           t.w.tgt, t.seq_keep, rows, logp_out);
-        OVC_RETURN_IF_LAUNCH_FAILED();
-    }
-    return OVC_OK;
-}
-}  // namespace
 
 extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                      int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
                                      float* logp_out, int use_graph, ovc_stream stream) {
     (void)boxes;       // the plain encoder reads no boxes
-    return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
-                             nullptr, nullptr, 0, 0, nullptr);
+    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights}, features, ids, nullptr, grad_logp, workspace,
+                          workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // SCST under dropout: ovc_beam_search_dropout / ovc_sequence_backward_dropout
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t ovc_train_beams_dropout_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    if (!seq_ok(m, B, N, S, T) || !dropout_train_ok(m, B * S, N, T)) return 0;
-    return carve_train(m, nullptr, B, N, T, true, S, true).bytes;
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights}, true);
 }
 
 extern "C" int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
@@ -2517,17 +2529,12 @@ extern "C" int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model
                                              size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream, int k,
                                              const int32_t* slots, const ovc_dropout* dropout) {
     (void)boxes;
-    if (!dropout || !dropout->seed || !slots || !m || k < 1 || k > OVC_MAX_BEAM || S > k || !seq_ok(m, B, N, S, T) ||
-        !dropout_train_ok(m, B * S, N, T) || T != m->max_len || (long)B * k * T > (1L << 30)) return OVC_EINVAL;
+    TrainCall c{B, N, S, T, LossHead::RowWeights};
+    c.k = k; c.slots = slots;
     DropPlan plan{};
-    uint64_t hash = 0;
-    bool any = false;
-    TRY(make_drop_plan(dropout, &plan, &hash, &any));
-    if (!any)
-        return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
-                                 nullptr, nullptr, 0, 0, nullptr);
-    return sequence_backward(m, grads, features, B, N, S, ids, grad_logp, T, workspace, workspace_bytes, logp_out, use_graph, stream,
-                             &plan, dropout->seed, hash ^ ((uint64_t)k << 56), k, slots);
+    TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, ids, nullptr, grad_logp, workspace, workspace_bytes, nullptr, logp_out, use_graph,
+                          stream);
 }
 
 extern "C" size_t ovc_beam_search_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k) {

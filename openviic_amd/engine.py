@@ -473,14 +473,11 @@ class CaptionEngine:
     def release(self):
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
-        for ws in (list(getattr(self, "_workspaces", {}).values()) + list(getattr(self, "_fw_workspaces", {}).values()) +
-                   list(getattr(self, "_train_workspaces", {}).values()) + list(getattr(self, "_seq_workspaces", {}).values())):
-            if lib is not None:
-                lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
-        self._workspaces = {}
-        self._fw_workspaces = {}
-        self._train_workspaces = {}
-        self._seq_workspaces = {}
+        for table in ("_workspaces", "_fw_workspaces", "_train_workspaces", "_seq_workspaces"):
+            for ws in getattr(self, table, {}).values():
+                if lib is not None:
+                    lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+            setattr(self, table, {})
         self._step_arenas = {}
         self._steps_device = {}
 
@@ -755,37 +752,61 @@ class CaptionEngine:
             raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
                 tuple(targets.shape), tuple(caption_tokens.shape)))
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        if loss is not None:
-            need = self.lib.ovc_train_smoothed_workspace_bytes(ctypes.byref(d), B, N, T, 1 if table_drop is not None else 0)
-        else:
-            sizer = self.lib.ovc_train_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_workspace_bytes
-            need = sizer(ctypes.byref(d), B, N, T)
-        if need == 0:
-            raise native.OvcError("unsupported training configuration (B={}, N={}, T={}, V={}; see ovc_train_workspace_bytes)"
-                                  .format(B, N, T, d.vocab))
+        form = self._train_form(False, loss, table_drop, (B, N, T))
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
+        arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
+        return out, arena, grads
+
+    # (sequence, smoothed loss, dropout) -> the sizer and the entry point of a training call: chosen here and nowhere else
+    _TRAIN_FORMS = {
+        (False, False, False): ("ovc_train_workspace_bytes", "ovc_forward_backward"),
+        (False, False, True): ("ovc_train_dropout_workspace_bytes", "ovc_forward_backward_dropout"),
+        (False, True, False): ("ovc_train_smoothed_workspace_bytes", "ovc_forward_backward_smoothed"),
+        (False, True, True): ("ovc_train_smoothed_workspace_bytes", "ovc_forward_backward_smoothed"),
+        (True, False, False): ("ovc_train_beams_workspace_bytes", "ovc_sequence_backward"),
+        (True, False, True): ("ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout"),
+    }
+
+    def _train_form(self, sequence, loss, table_drop, shape, search=()):
+        """One training call's form: ``(entry point, shape, workspace bytes, trailing arguments)`` for ``shape`` ``(B, N, T)``
+        or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes on.
+        A shape or model the sizer refuses raises here, before any launch."""
+        sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
+        drop = () if table_drop is None else (ctypes.byref(table_drop),)
+        size_tail, tail = (), (*search, *drop)
+        if loss is not None:
+            size_tail = (1 if drop else 0,)
+            tail = (ctypes.byref(native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])), drop[0] if drop else None)
+        need = getattr(self.lib, sizer)(ctypes.byref(self.desc), *shape, *size_tail)
+        if need == 0:
+            raise native.OvcError("unsupported training configuration ({}, V={}; see {})".format(
+                ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
+                "ovc_train_beams_workspace_bytes" if sequence else "ovc_train_workspace_bytes"))
+        return entry, shape, need, tail
+
+    def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
+        """The call of a ``_train_form``: the pointer table and derived weights refreshed, the gradient arena (a fresh one unless
+        ``arena`` is given), the stream's workspace -- per S for sequences -- and the entry point.  ``inputs``: the two device
+        tensors between the shape's leading sizes and T; ``out_shape``: the result the entry point writes (None: not asked for).
+        Returns ``(arena, grads, out)``."""
+        entry, shape, need, tail = form
         self._check_pointers()
         self._refresh_derived()
         d = self.desc
         arena, table, grads = self._gradient_arena() if arena is None else arena
         stream = torch.cuda.current_stream().cuda_stream
-        ws = self._cached_workspace(self._train_workspaces, stream, need)
-        out = torch.empty((), dtype=torch.float32, device=self.device)
-        graph = self.use_graph if use_graph is None else bool(use_graph)
-        args = (ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
-                tokens.data_ptr(), targets.data_ptr(), T, ws.data_ptr(), need, out.data_ptr(), 1 if graph else 0,
-                native.stream_handle())
-        if loss is not None:
-            table_loss = native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])
-            check(self.lib.ovc_forward_backward_smoothed(*args, ctypes.byref(table_loss),
-                                                         None if table_drop is None else ctypes.byref(table_drop)),
-                  "ovc_forward_backward_smoothed")
-        elif table_drop is None:
-            check(self.lib.ovc_forward_backward(*args), "ovc_forward_backward")
+        if len(shape) == 4:
+            ws = self._cached_workspace(self._seq_workspaces, (stream, shape[2]), need)
         else:
-            check(self.lib.ovc_forward_backward_dropout(*args, ctypes.byref(table_drop)), "ovc_forward_backward_dropout")
-        return out, arena, grads
+            ws = self._cached_workspace(self._train_workspaces, stream, need)
+        out = None if out_shape is None else torch.empty(out_shape, dtype=torch.float32, device=self.device)
+        graph = self.use_graph if use_graph is None else bool(use_graph)
+        check(getattr(self.lib, entry)(
+            ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), *shape[:-1],
+            inputs[0].data_ptr(), inputs[1].data_ptr(), shape[-1], ws.data_ptr(), need, None if out is None else out.data_ptr(),
+            1 if graph else 0, native.stream_handle(), *tail), entry)
+        return arena, grads, out
 
     def _gradient_arena(self):
         """A fresh flat fp32 buffer for every gradient of ``gradient_parameters()``, the ``ovc_model`` table pointing into it and
@@ -848,29 +869,12 @@ class CaptionEngine:
         T = check_caption_ids(ids.reshape(B * S, -1), "ids", B * S, d.max_len, d.vocab)
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
-        sizer = self.lib.ovc_train_beams_dropout_workspace_bytes if table_drop is not None else self.lib.ovc_train_beams_workspace_bytes
-        need = sizer(ctypes.byref(d), B, N, S, T)
-        if need == 0:
-            raise native.OvcError("unsupported training configuration (B={}, N={}, S={}, T={}, V={}; see "
-                                  "ovc_train_beams_workspace_bytes)".format(B, N, S, T, d.vocab))
+        form = self._train_form(True, None, table_drop, (B, N, S, T),
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()))
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
-        self._check_pointers()
-        self._refresh_derived()
-        d = self.desc
-        arena, table, grads = self._gradient_arena() if arena is None else arena
-        stream = torch.cuda.current_stream().cuda_stream
-        ws = self._cached_workspace(self._seq_workspaces, (stream, S), need)
-        logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device) if want_logp else None
-        graph = self.use_graph if use_graph is None else bool(use_graph)
-        args = (ctypes.byref(d), ctypes.byref(table), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N, S,
-                ids.data_ptr(), grad_logp.data_ptr(), T, ws.data_ptr(), need, None if logp is None else logp.data_ptr(),
-                1 if graph else 0, native.stream_handle())
-        if table_drop is None:
-            check(self.lib.ovc_sequence_backward(*args), "ovc_sequence_backward")
-        else:
-            check(self.lib.ovc_sequence_backward_dropout(*args, int(beam_size), slots.data_ptr(), ctypes.byref(table_drop)),
-                  "ovc_sequence_backward_dropout")
+        arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,
+                                                  arena, use_graph)
         return (arena, grads, logp) if want_logp else (arena, grads)
 
     def scale_gradients(self, arena, scale):

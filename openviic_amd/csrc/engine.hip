@@ -853,11 +853,57 @@ int project_cross_kv(Engine& e, Workspace& w, int B, int N) {
     return OVC_OK;
 }
 
-// gated (ovc_beam_search_gated): every launch of step t >= 1 is gated on alive_count[t - 1] and the update counts live beams.
-int run_decode_step(Engine& e, Workspace& w, int B, int N, int k, int t, int return_probs, bool count_alive = false, bool gated = false) {
+// The four forms a beam search runs in.  Each exported search names one (ovc_beam_search_dropout by its mode).
+enum class SearchForm {
+    Plain,       // ovc_beam_search: plain launches; with all_logp_out every step's masked log-probabilities as well
+    Graph,       // ovc_beam_search_graph: the whole search, final ordering included, one captured graph
+    HostEarly,   // ovc_beam_search_early: a graph per step; the host reads alive_count one step late and stops issuing
+    Gated,       // ovc_beam_search_gated: one graph whose launches of step t >= 1 are gated on alive_count[t - 1]
+};
+
+// One beam search, described once.  The five exported searches fill one of these, and the scope (search_ok), the workspace layout
+// and size (carve_search), what a step does (run_decode_step), the launches of the search (issue_search_body), the graph key
+// (search_graph_key) and everything around them (run_search) are functions of it.
+struct SearchCall {
+    // the members every call states, first: SearchCall{B, N, k, out_size, form, ids_out, logp_out}; the rest is zero unless a form
+    // fills it in
+    int B, N, k, out_size;
+    SearchForm form;
+    int64_t* ids_out; float* logp_out;              // [B][out_size][T], the caller's
+    float* all_logp_out;                            // Plain: [B][k][T][V], or nullptr
+    int32_t* steps_out;                             // Gated: the device word that takes the number of steps that did work
+    int* steps_run_out;                             // HostEarly: the host word that takes the number of steps issued
+    // Dropout (ovc_beam_search_dropout): the plan -- bound even when no site is active, the slot table is still written -- with
+    // the caller's seed, the hash of the plan's constants and the caller's slot table [B][out_size][T].  A sizer binds an empty
+    // plan (and any non-null all_logp_out): their presence alone adds the buffers.
+    DropPlan* plan; const int64_t* seed; uint64_t drop_hash; int32_t* slots_out;
+    bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
+};
+
+bool dropout_train_ok(const ovc_model* m, int B, int N, int T);     // the dropout scope, defined with the training calls
+
+// The models a form runs: the part of the scope that is checked before the device is touched.
+bool search_model_ok(const ovc_model* m, const SearchCall& c) {
+    return model_ok(m) && (c.form != SearchForm::Gated || m->precision == 0);
+}
+
+// The scope of a search, for the sizers (out_size = k) and the entry points alike.
+bool search_ok(const ovc_model* m, const SearchCall& c) {
+    if (!search_model_ok(m, c) || c.B <= 0 || c.N <= 0 || c.N > OVC_MAX_REGIONS || c.k <= 0 || c.k > OVC_MAX_BEAM) return false;
+    return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
+}
+
+// With a plan: the seed / step-count slots behind the plain layout.
+Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
+    return carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr);
+}
+
+// Step t of a search.  Gated: every launch of step t >= 1 is gated on alive_count[t - 1]; the early-exit forms count live beams.
+int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     const ovc_model* m = e.m;
-    e.gate = gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
-    count_alive = count_alive || gated;
+    const int B = c.B, N = c.N, k = c.k;
+    const bool return_probs = c.all_logp_out != nullptr, count_alive = c.counts_alive();
+    e.gate = c.form == SearchForm::Gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
     hipStream_t s = e.stream;
     const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels, T = m->max_len;
     const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
@@ -1181,40 +1227,45 @@ bool forward_ok(const ovc_model* m, int B, int N, int T) {
            (long)B * T <= (1L << 24);
 }
 
-// The front end the four searches share: the argument checks, the workspace carved (dropout: with the seed / step-count slots
-// behind the plain layout) and the Engine on the caller's stream.
-int open_search(const ovc_model* m, const float* features, int B, int N, int k, int out_size, void* workspace, size_t workspace_bytes,
-                const int64_t* ids_out, const float* logp_out, int return_probs, bool dropout, ovc_stream stream, Workspace& w,
-                Engine& e) {
-    if (!model_ok(m) || !features || !workspace || !ids_out || !logp_out) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || out_size <= 0 || out_size > k) return OVC_EINVAL;
-    if ((long)m->vocab < k) return OVC_EINVAL;
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    w = carve(m, workspace, B, N, k, return_probs, dropout);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    e = Engine{m, ovc_hip_stream(stream), 0};
-    return OVC_OK;
-}
-
-// What every search issues behind its input kernels and before step 0.  clear_alive_count (the early-exit searches): this search's
-// counts -- in the gated search's graph, where a count left by the previous replay must never open a gate.
-int issue_search_prologue(Engine& e, Workspace& w, int B, int N, int k, bool clear_alive_count) {
-    const int R = B * k;
-    TRY(run_encoder_layers(e, w, B, N));
-    TRY(project_cross_kv(e, w, B, N));
+// What every search issues behind its input kernels and before step 0.  The early-exit forms clear this search's live-beam counts
+// -- in the gated search's graph, where a count left by the previous replay must never open a gate.
+int issue_search_prologue(Engine& e, Workspace& w, const SearchCall& c) {
+    const int R = c.B * c.k;
+    TRY(run_encoder_layers(e, w, c.B, c.N));
+    TRY(project_cross_kv(e, w, c.B, c.N));
     hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
     OVC_RETURN_IF_LAUNCH_FAILED();
-    if (clear_alive_count && hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * e.m->max_len, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    if (c.counts_alive() && hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * e.m->max_len, e.stream) != hipSuccess) return OVC_ELAUNCH;
     return OVC_OK;
 }
 
 // The final ordering's arguments: the beam state of buffer `parity`, written to ids / logp.
-BeamFinalArgs final_args(const Workspace& w, int parity, int k, int T, int out_size, int64_t* ids, float* logp) {
+BeamFinalArgs final_args(const Workspace& w, int parity, const SearchCall& c, int T, int64_t* ids, float* logp) {
     BeamFinalArgs bf{};
     bf.running = w.running[parity]; bf.hist = w.hist[parity]; bf.lp = w.lp[parity];
-    bf.k = k; bf.T = T; bf.out_size = out_size; bf.ids_out = ids; bf.logp_out = logp; bf.order_out = w.order;
+    bf.k = c.k; bf.T = T; bf.out_size = c.out_size; bf.ids_out = ids; bf.logp_out = logp; bf.order_out = w.order;
     return bf;
+}
+
+// The launches of a search behind its input kernels: the prologue and max_len steps.  This is what the whole-search graphs
+// capture; the Graph form's holds the final ordering too, into the workspace (a graph cannot name the caller's buffers).
+// HostEarly issues the same prologue and steps one by one (run_host_early).
+int issue_search_body(Engine& e, Workspace& w, const SearchCall& c) {
+    const int T = e.m->max_len;
+    TRY(issue_search_prologue(e, w, c));
+    for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, c, t));
+    if (c.form != SearchForm::Graph) return OVC_OK;
+    return ovc_beam_finalize_launch(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), c.B, e.stream);
+}
+
+// A sizer builds the SearchCall its entry point will build (out_size plays no part in the layout).
+size_t search_workspace_bytes(const ovc_model* m, int B, int N, int k, bool return_probs, bool dropout) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    DropPlan sized{};
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (dropout) c.plan = &sized;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
 }
 
 }  // namespace
@@ -1231,21 +1282,21 @@ extern "C" const char* ovc_build_info(void) {
 }
 
 extern "C" size_t ovc_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs) {
-    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM) return 0;
-    return carve(m, nullptr, B, N, k, return_probs).bytes;
+    return search_workspace_bytes(m, B, N, k, return_probs != 0, false);
 }
 
 // Every distinct GEMM the engine issues for (B, N, k), found by running the launch sequence itself in dry mode (no
 // launch, no device access: the workspace is carved at a fake base address that is never dereferenced).
 extern "C" int ovc_engine_gemm_shapes(const ovc_model* m, int B, int N, int k, int32_t* shapes, int capacity) {
-    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM || capacity < 0 || (capacity > 0 && !shapes)) return OVC_EINVAL;
-    Workspace w = carve(m, reinterpret_cast<void*>(uintptr_t(1) << 20), B, N, k, 0);
+    const SearchCall c{B, N, k, k};
+    if (!search_ok(m, c) || capacity < 0 || (capacity > 0 && !shapes)) return OVC_EINVAL;
+    Workspace w = carve_search(m, reinterpret_cast<void*>(uintptr_t(1) << 20), c);
     std::vector<GemmShape> found;
     Engine e{m, nullptr, 0};
     e.dry = &found;
     TRY(run_encoder(e, w, nullptr, nullptr, B, N));
     TRY(project_cross_kv(e, w, B, N));
-    for (int t = 0; t < (m->max_len < 2 ? m->max_len : 2); ++t) TRY(run_decode_step(e, w, B, N, k, t, 0));   // step 0: B rows, later steps: B*k
+    for (int t = 0; t < (m->max_len < 2 ? m->max_len : 2); ++t) TRY(run_decode_step(e, w, c, t));   // step 0: B rows, later steps: B*k
     for (size_t i = 0; i < found.size() && (int)i < capacity; ++i)
         for (int j = 0; j < 7; ++j) shapes[i * 7 + j] = found[i][j];
     return (int)found.size();
@@ -1270,23 +1321,6 @@ extern "C" int ovc_encode(const ovc_model* m, const float* features, const float
         return OVC_ELAUNCH;
     }
     if (hipMemcpyAsync(mask_out, w.enc_mask, (size_t)B * N, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    return OVC_OK;
-}
-
-extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                               int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                               float* logp_out, float* all_logp_out, ovc_stream stream) {
-    const int return_probs = all_logp_out != nullptr;
-    Workspace w;
-    Engine e{};
-    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, return_probs, false, stream, w, e));
-    const int T = m->max_len;
-
-    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    TRY(issue_search_prologue(e, w, B, N, k, false));
-    for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, return_probs));
-    TRY(ovc_beam_finalize_launch(final_args(w, T & 1, k, T, out_size, ids_out, logp_out), B, e.stream));
-    if (return_probs) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, B, k, T, m->vocab, all_logp_out, e.stream));
     return OVC_OK;
 }
 
@@ -1446,60 +1480,26 @@ int replay_or_issue(const GraphKey& key, hipStream_t stream, const ovc_model* m,
     return body(e);
 }
 
-// ovc_beam_search_dropout: the plan of a search with dropout (nullptr everywhere else: the plain search, launch for launch).
-struct SearchDrop {
-    DropPlan* plan; const int64_t* seed; uint64_t hash;     // hash: the p values, part of every graph key
-    int32_t* slots_out;                                      // [B][out_size][T], the caller's
-};
-
-// Binds a search's Engine to its dropout plan: the seed slot is refreshed here, outside any captured body.
-int bind_search_drop(Engine& e, Workspace& w, SearchDrop* sd) {
-    if (!sd) return OVC_OK;
-    if (hipMemcpyAsync(w.drop_seed, sd->seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    sd->plan->seed = w.drop_seed;
-    e.drop = sd->plan;
-    return OVC_OK;
-}
-
-// The slot table of a finished search (beam_slots_kernel), after the final ordering has written w.order.
-int write_search_slots(Engine& e, Workspace& w, SearchDrop* sd, const int32_t* steps_dev, int steps_host, int B, int k, int out_size) {
-    if (!sd || !sd->slots_out) return OVC_OK;
-    const int T = e.m->max_len, n = B * out_size;
+// The slot table of a finished search (beam_slots_kernel), after the final ordering has written w.order and, for the gated
+// search, the number of steps that did work to w.steps_dev; every other form ran steps_host steps.
+int write_search_slots(Engine& e, Workspace& w, const SearchCall& c, int steps_host) {
+    if (!c.slots_out) return OVC_OK;
+    const int T = e.m->max_len, n = c.B * c.out_size;
+    const int32_t* steps_dev = c.form == SearchForm::Gated ? w.steps_dev : nullptr;
     hipLaunchKernelGGL(beam_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, e.stream, w.anc[0], w.anc[1], w.hist[0], w.hist[1], w.order,
-                       steps_dev, steps_host, e.m->eos_idx, B, k, T, out_size, sd->slots_out);
+                       steps_dev, steps_dev ? 0 : steps_host, e.m->eos_idx, c.B, c.k, T, c.out_size, c.slots_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
 
-int issue_decode_graph_body(Engine& e, Workspace& w, int B, int N, int k, int out_size) {
-    const int T = e.m->max_len;
-    TRY(issue_search_prologue(e, w, B, N, k, false));
-    for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0));
-    return ovc_beam_finalize_launch(final_args(w, T & 1, k, T, out_size, w.out_ids, w.out_logp), B, e.stream);
-}
-
-int beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
-                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream, SearchDrop* sd) {
-    Workspace w;
-    Engine e{};
-    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
-    const size_t out_n = (size_t)B * out_size * m->max_len;
-
-    TRY(bind_search_drop(e, w, sd));
-    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    const GraphKey key{GraphKind::Search, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
-    TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_decode_graph_body(ce, w, B, N, k, out_size); }, e.drop));
-    if (hipMemcpyAsync(ids_out, w.out_ids, sizeof(int64_t) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    if (hipMemcpyAsync(logp_out, w.out_logp, sizeof(float) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    return write_search_slots(e, w, sd, nullptr, m->max_len, B, k, out_size);
+// The graph key of a search, built here and nowhere else (the rule: GraphKind).  The gated launches are a kind of their own; the
+// whole-search graph and the per-step graphs share Search and live in different maps (g_graphs, g_early).  The dropout plan's
+// constants are hashed in -- 0 without a plan, so a search with dropout never shares an entry with the plain one.
+GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* workspace) {
+    const GraphKind kind = c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
+    return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
 }  // namespace
-
-extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                                     float* logp_out, ovc_stream stream) {
-    return beam_search_graph(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, stream, nullptr);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Early exit (round 4).  The reference always runs max_len steps (beam_search.py:94-95), although once every beam of every
@@ -1512,16 +1512,12 @@ extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, 
 // below -999 (a frozen beam's other candidates, beam_search.py:54).
 // ---------------------------------------------------------------------------------------------
 namespace {
-int beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
-                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, int* steps_run_out, ovc_stream stream, SearchDrop* sd) {
-    Workspace w;
-    Engine e{};
-    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
+// Issues the prologue and the steps of a HostEarly search on e (the input kernels are behind it); *steps_run: the steps issued.
+int run_host_early(Engine& e, Workspace& w, const SearchCall& c, const GraphKey& key, int* steps_run) {
+    const ovc_model* m = e.m;
     const int T = m->max_len;
-
     std::shared_ptr<EarlyEntry> entry;
     {
-        const GraphKey key{GraphKind::Search, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
         std::lock_guard<std::mutex> lock(g_graph_mutex);
         std::shared_ptr<EarlyEntry>& slot = g_early[key];
         if (!slot) slot = std::make_shared<EarlyEntry>();
@@ -1533,61 +1529,52 @@ int beam_search_early(const ovc_model* m, const float* features, const float* bo
     entry->calls += 1;
     entry->last_stream = e.stream;
     if (!entry->host_alive) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&entry->host_alive), sizeof(int32_t) * T, hipHostMallocDefault) != hipSuccess) {
+        // first use: the pinned buffer and the events, committed to the entry only when all of them exist
+        int32_t* host_alive = nullptr;
+        std::vector<hipEvent_t> step_done(T, nullptr);
+        bool ok = hipHostMalloc(reinterpret_cast<void**>(&host_alive), sizeof(int32_t) * T, hipHostMallocDefault) == hipSuccess;
+        for (int t = 0; ok && t < T; ++t) ok = hipEventCreateWithFlags(&step_done[t], hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
             (void)hipGetLastError();
-            entry->host_alive = nullptr;
+            for (hipEvent_t ev : step_done) if (ev) (void)hipEventDestroy(ev);
+            if (host_alive) (void)hipHostFree(host_alive);
             return OVC_ELAUNCH;
         }
-        entry->step_graph.assign(T, nullptr); entry->step_exec.assign(T, nullptr); entry->step_done.assign(T, nullptr);
-        for (int t = 0; t < T; ++t)
-            if (hipEventCreateWithFlags(&entry->step_done[t], hipEventDisableTiming) != hipSuccess) return OVC_ELAUNCH;
+        entry->step_graph.assign(T, nullptr); entry->step_exec.assign(T, nullptr);
+        entry->step_done = std::move(step_done);
+        entry->host_alive = host_alive;
     }
     const bool graphs = !entry->unsupported && !g_profile_on && entry->calls > 1;   // first call of a shape: plain (warms every kernel)
 
-    TRY(bind_search_drop(e, w, sd));
-    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
     if (graphs && !entry->prologue_exec) {
         std::lock_guard<std::mutex> lock(g_graph_mutex);           // the capture stream is shared process-wide
-        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_search_prologue(ce, w, B, N, k, true); }, e.drop))
+        if (!capture_into(&entry->prologue_graph, &entry->prologue_exec, m, [&](Engine& ce) { return issue_search_prologue(ce, w, c); }, e.drop))
             entry->unsupported = true;
     }
     if (graphs && entry->prologue_exec) { if (hipGraphLaunch(entry->prologue_exec, e.stream) != hipSuccess) return OVC_ELAUNCH; }
-    else TRY(issue_search_prologue(e, w, B, N, k, true));
+    else TRY(issue_search_prologue(e, w, c));
 
-    int steps_run = T;
+    *steps_run = T;
     for (int t = 0; t < T; ++t) {
         if (graphs && !entry->unsupported && !entry->step_exec[t]) {
             std::lock_guard<std::mutex> lock(g_graph_mutex);
-            if (!capture_into(&entry->step_graph[t], &entry->step_exec[t], m,
-                              [&](Engine& ce) { return run_decode_step(ce, w, B, N, k, t, 0, true); }, e.drop))
+            if (!capture_into(&entry->step_graph[t], &entry->step_exec[t], m, [&](Engine& ce) { return run_decode_step(ce, w, c, t); }, e.drop))
                 entry->unsupported = true;
         }
         if (graphs && entry->step_exec[t]) { if (hipGraphLaunch(entry->step_exec[t], e.stream) != hipSuccess) return OVC_ELAUNCH; }
-        else TRY(run_decode_step(e, w, B, N, k, t, 0, true));
+        else TRY(run_decode_step(e, w, c, t));
         if (t + 1 == T) break;                                      // nothing left to skip
         if (hipMemcpyAsync(entry->host_alive + t, w.alive_count + t, sizeof(int32_t), hipMemcpyDeviceToHost, e.stream) != hipSuccess ||
             hipEventRecord(entry->step_done[t], e.stream) != hipSuccess) return OVC_ELAUNCH;
         // one step late: step t is queued, step t - 1's count is (about to be) on the host
         if (t >= 1) {
             if (hipEventSynchronize(entry->step_done[t - 1]) != hipSuccess) return OVC_ELAUNCH;
-            if (entry->host_alive[t - 1] == 0) { steps_run = t + 1; break; }
+            if (entry->host_alive[t - 1] == 0) { *steps_run = t + 1; break; }
         }
     }
-
-    BeamFinalArgs bf = final_args(w, steps_run & 1, k, T, out_size, ids_out, logp_out);
-    bf.steps_run = steps_run < T ? steps_run : 0;
-    TRY(ovc_beam_finalize_launch(bf, B, e.stream));
-    if (steps_run_out) *steps_run_out = steps_run;
-    return write_search_slots(e, w, sd, nullptr, steps_run, B, k, out_size);
+    return OVC_OK;
 }
 }  // namespace
-
-extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
-                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
-                                     float* logp_out, int* steps_run_out, ovc_stream stream) {
-    return beam_search_early(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_run_out, stream,
-                             nullptr);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Device-side early exit (ovc_beam_search_gated).  ROCm's HIP has no conditional graph nodes, so the whole-search graph keeps
@@ -1601,40 +1588,93 @@ extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, 
 // ovc_beam_search_graph's under ovc_beam_search_early's assumptions.
 // ---------------------------------------------------------------------------------------------
 namespace {
-int issue_gated_body(Engine& e, Workspace& w, int B, int N, int k) {
-    TRY(issue_search_prologue(e, w, B, N, k, true));
-    for (int t = 0; t < e.m->max_len; ++t) TRY(run_decode_step(e, w, B, N, k, t, 0, true, true));
-    e.gate = nullptr;
-    return OVC_OK;
-}
-
-int beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, void* workspace,
-                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, int32_t* steps_out, ovc_stream stream, SearchDrop* sd) {
-    if (!model_ok(m) || m->precision != 0) return OVC_EINVAL;
-    Workspace w;
-    Engine e{};
-    TRY(open_search(m, features, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, 0, sd != nullptr, stream, w, e));
+// Every search.  Launch order: the seed slot (dropout); the kernels that read the caller's features and boxes; the search in its
+// form -- from the second call of a key one graph (Graph, Gated) or a graph per step (HostEarly); the final ordering where the
+// body does not hold it; the copies to the caller's buffers and the slot table.
+int run_search(const ovc_model* m, const SearchCall& c, const float* features, const float* boxes, void* workspace,
+               size_t workspace_bytes, ovc_stream stream) {
+    if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!search_ok(m, c) || (long)m->vocab < c.k) return OVC_EINVAL;
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    Workspace w = carve_search(m, workspace, c);
+    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
     const int T = m->max_len;
+    if (c.plan) {                                  // the seed slot is refreshed here, outside any captured body
+        if (hipMemcpyAsync(w.drop_seed, c.seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        c.plan->seed = w.drop_seed;
+        e.drop = c.plan;
+    }
+    TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
 
-    TRY(bind_search_drop(e, w, sd));
-    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    // first call of a shape: plain gated launches; from the second on ONE graph
-    const GraphKey key{GraphKind::GatedSearch, hash_bytes(m, sizeof(*m)) ^ (sd ? sd->hash : 0), workspace, B, N, k, out_size};
-    TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_gated_body(ce, w, B, N, k); }, e.drop));
-    // the final ordering reads the step count from the device and writes the caller's buffers directly
-    const BeamFinalArgs bf[2] = {final_args(w, 0, k, T, out_size, ids_out, logp_out), final_args(w, 1, k, T, out_size, ids_out, logp_out)};
-    if (!sd) return ovc_beam_finalize_gated_launch(bf, w.alive_count, steps_out, B, e.stream);
-    // the slot table reads the step count the final ordering found: through a workspace word, copied to the caller's afterwards
-    TRY(ovc_beam_finalize_gated_launch(bf, w.alive_count, w.steps_dev, B, e.stream));
-    if (steps_out && hipMemcpyAsync(steps_out, w.steps_dev, sizeof(int32_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
-    return write_search_slots(e, w, sd, w.steps_dev, 0, B, k, out_size);
+    auto body = [&](Engine& ce) { return issue_search_body(ce, w, c); };
+    int steps_run = T;                             // decode steps issued: fewer only from HostEarly
+    switch (c.form) {
+    case SearchForm::Plain:
+        TRY(body(e));
+        break;
+    case SearchForm::Graph:
+    case SearchForm::Gated:                        // first call of a key: plain (gated) launches; from the second on ONE graph
+        TRY(replay_or_issue(search_graph_key(m, c, workspace), e.stream, m, body, e.drop));
+        break;
+    case SearchForm::HostEarly:
+        TRY(run_host_early(e, w, c, search_graph_key(m, c, workspace), &steps_run));
+        break;
+    }
+
+    if (c.form == SearchForm::Graph) {             // ordered inside the body, into the workspace
+        const size_t out_n = (size_t)c.B * c.out_size * T;
+        if (hipMemcpyAsync(c.ids_out, w.out_ids, sizeof(int64_t) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        if (hipMemcpyAsync(c.logp_out, w.out_logp, sizeof(float) * out_n, hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
+    } else if (c.form == SearchForm::Gated) {
+        // the final ordering reads the step count from the device and writes the caller's buffers directly.  With a slot table to
+        // write, which reads the count the ordering found: through a workspace word, copied to the caller's afterwards
+        const BeamFinalArgs bf[2] = {final_args(w, 0, c, T, c.ids_out, c.logp_out), final_args(w, 1, c, T, c.ids_out, c.logp_out)};
+        int32_t* count = c.plan ? w.steps_dev : c.steps_out;
+        TRY(ovc_beam_finalize_gated_launch(bf, w.alive_count, count, c.B, e.stream));
+        if (c.plan && c.steps_out && hipMemcpyAsync(c.steps_out, count, sizeof(int32_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+            return OVC_ELAUNCH;
+    } else {                                       // the state the last issued step left: its parity, and the positions never written
+        BeamFinalArgs bf = final_args(w, steps_run & 1, c, T, c.ids_out, c.logp_out);
+        bf.steps_run = steps_run < T ? steps_run : 0;
+        TRY(ovc_beam_finalize_launch(bf, c.B, e.stream));
+    }
+    if (c.all_logp_out) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, c.B, c.k, T, m->vocab, c.all_logp_out, e.stream));
+    if (c.steps_run_out) *c.steps_run_out = steps_run;
+    return write_search_slots(e, w, c, steps_run);
 }
 }  // namespace
+
+extern "C" int ovc_beam_search(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                               int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                               float* logp_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, ovc_stream stream) {
+    return run_search(m, SearchCall{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out}, features, boxes, workspace, workspace_bytes,
+                      stream);
+}
+
+extern "C" int ovc_beam_search_early(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                     int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, int* steps_run_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::HostEarly, ids_out, logp_out};
+    c.steps_run_out = steps_run_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
 
 extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
                                      int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
                                      float* logp_out, int32_t* steps_out, ovc_stream stream) {
-    return beam_search_gated(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_out, stream, nullptr);
+    SearchCall c{B, N, k, out_size, SearchForm::Gated, ids_out, logp_out};
+    c.steps_out = steps_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2538,28 +2578,25 @@ extern "C" int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model
 }
 
 extern "C" size_t ovc_beam_search_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k) {
-    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || k <= 0 || k > OVC_MAX_BEAM) return 0;
-    if (!dropout_train_ok(m, B, N, m->max_len)) return 0;
-    return carve(m, nullptr, B, N, k, 0, true).bytes;
+    return search_workspace_bytes(m, B, N, k, false, true);
 }
 
 extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
                                        void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
                                        const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out,
                                        int* steps_run_out) {
+    constexpr SearchForm kModes[3] = {SearchForm::Graph, SearchForm::HostEarly, SearchForm::Gated};
     if (!dropout || !dropout->seed || !slots_out || !m || mode < 0 || mode > 2) return OVC_EINVAL;
-    if (!model_ok(m) || B <= 0 || N <= 0 || N > OVC_MAX_REGIONS || !dropout_train_ok(m, B, N, m->max_len) ||
-        (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
+    if (!model_ok(m) || !dropout_train_ok(m, B, N, m->max_len) || (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
     DropPlan plan{};
-    uint64_t hash = 0;
     bool any = false;
-    TRY(make_drop_plan(dropout, &plan, &hash, &any));
-    // with every p == 0 the plan stays bound (the slot table is still written) but no site is on: today's launches, today's bits
-    SearchDrop sd{&plan, dropout->seed, any ? hash : 0x5D0Full, slots_out};
-    if (mode == 0)
-        return beam_search_graph(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, stream, &sd);
-    if (mode == 1)
-        return beam_search_early(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_run_out, stream,
-                                 &sd);
-    return beam_search_gated(m, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out, steps_out, stream, &sd);
+    SearchCall c{B, N, k, out_size, kModes[mode], ids_out, logp_out};
+    TRY(make_drop_plan(dropout, &plan, &c.drop_hash, &any));
+    // with every p == 0 the plan stays bound (the slot table is still written) but no site is on: the plain launches, the plain
+    // bits, and a graph entry of its own
+    if (!any) c.drop_hash = 0x5D0Full;
+    c.plan = &plan; c.seed = dropout->seed; c.slots_out = slots_out;
+    if (c.form == SearchForm::Gated) c.steps_out = steps_out;
+    if (c.form == SearchForm::HostEarly) c.steps_run_out = steps_run_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }

@@ -583,41 +583,69 @@ class CaptionEngine:
             steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
         return steps
 
-    def _beam_search_dropout(self, features, boxes, batch_size, beam_size, out_size, early, table_drop):
-        """``ovc_beam_search_dropout``: the search with every site of ``table_drop`` applied, in the form ``early`` selects.
-        Returns ``(ids, logp, slots)`` with ``slots`` ``(B, out_size, T)`` int32: the beam slot each returned beam's ancestor held
-        at every step, the key of its masks (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
-        self._check_trainable()
-        if self.desc.enc_kind != native.ENC_PLAIN:
-            raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer (with or without "
-                                  "encoder memory slots) only")
+    # form -> the entry point of a search and the names of its arguments behind ``logp``: chosen here and nowhere else.  "graph",
+    # "early" and "device" are ``ovc_beam_search_dropout``'s modes 0, 1 and 2.
+    _SEARCH_FORMS = {
+        "plain": ("ovc_beam_search", ("everything", "stream")),
+        "graph": ("ovc_beam_search_graph", ("stream",)),
+        "early": ("ovc_beam_search_early", ("steps_run", "stream")),
+        "device": ("ovc_beam_search_gated", ("steps", "stream")),
+        "dropout": ("ovc_beam_search_dropout", ("stream", "table", "slots", "mode", "steps", "steps_run")),
+    }
+
+    def _run_search(self, features, boxes, batch_size, beam_size, out_size, return_probs, early, table_drop):
+        """Every search: the refusals, the form, its workspace and results, and the call.  ``table_drop``: the ``ovc_dropout``
+        table of a search with dropout (``ovc_beam_search_dropout`` in the form ``early`` selects), or None.  Returns
+        ``(ids, logp, everything, slots)``, ``ids`` / ``logp`` / ``slots`` ``(B, out_size, T)``; ``slots`` (int32, None without
+        dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
+        (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
+        if table_drop is not None:
+            self._check_trainable()
+            if self.desc.enc_kind != native.ENC_PLAIN:
+                raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer (with or without "
+                                      "encoder memory slots) only")
+        if early == "device" and self.precision != "f32":
+            raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
         features, boxes, B, N = self._search_inputs(features, boxes, batch_size, beam_size)
         d = self.desc
         T = d.max_len
-        need = self.lib.ovc_beam_search_dropout_workspace_bytes(ctypes.byref(d), B, N, beam_size)
-        if need == 0:
-            raise native.OvcError("unsupported configuration for a search with dropout (B={}, N={}, beam={}; see "
-                                  "ovc_beam_search_dropout_workspace_bytes)".format(B, N, beam_size))
-        ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
+        # with return_probs every early_exit value runs the full plain search; without use_graph (OVC_GRAPH=0) the whole-search
+        # graph's form is the plain search as well
+        form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
+        if table_drop is None:
+            if form == "graph" and not self.use_graph:
+                form = "plain"
+            ws, need = self._get_workspace(B, N, beam_size, return_probs)
+        else:
+            need = self.lib.ovc_beam_search_dropout_workspace_bytes(ctypes.byref(d), B, N, beam_size)
+            if need == 0:
+                raise native.OvcError("unsupported configuration for a search with dropout (B={}, N={}, beam={}; see "
+                                      "ovc_beam_search_dropout_workspace_bytes)".format(B, N, beam_size))
+            ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
-        slots = torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
-        mode = 2 if early == "device" else (1 if early else 0)
-        steps = None
-        if mode == 2:
-            steps = self.last_steps_device = self._steps_tensor()
-        if not self.use_graph:           # OVC_GRAPH=0: every call is the first of its shape (plain launches)
-            self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
-        self.last_steps_run = T
+        slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
+        everything = torch.empty(B, beam_size, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
+        steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
-        check(self.lib.ovc_beam_search_dropout(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(),
-                                               B, N, beam_size, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
-                                               native.stream_handle(), ctypes.byref(table_drop), slots.data_ptr(), mode,
-                                               None if steps is None else steps.data_ptr(), ctypes.byref(issued)),
-              "ovc_beam_search_dropout")
-        if mode == 1:
+        # OVC_GRAPH=0: every call is the first of its shape (plain launches; the host-early search without dropout keeps its graphs)
+        if not self.use_graph and (form == "device" or table_drop is not None):
+            self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+        args = {name: None if t is None else t.data_ptr() for name, t in (("everything", everything), ("slots", slots), ("steps", steps))}
+        args.update(stream=native.stream_handle(), steps_run=ctypes.byref(issued))
+        entry, tail = self._SEARCH_FORMS[form]
+        if table_drop is not None:
+            args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
+            entry, tail = self._SEARCH_FORMS["dropout"]
+        self.last_steps_run = T
+        check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
+                                       beam_size, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
+                                       *(args[name] for name in tail)), entry)
+        if form == "early":
             self.last_steps_run = issued.value
-        return ids, logp, slots
+        if form == "device":
+            self.last_steps_device = steps
+        return ids, logp, everything, slots
 
     def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None):
         """``dropout=(probs, seed)`` (as ``forward_backward``): the search runs with every site's mask applied and returns
@@ -628,50 +656,15 @@ class CaptionEngine:
         stream order, the number of decode steps that did work; ``last_steps_run`` stays ``max_len``.  With ``return_probs``
         every mode runs the full search."""
         early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
+        table_drop = None
         if dropout is not None:
             if return_probs:
                 raise native.OvcError("beam_search(dropout=...) has no return_probs form")
             table_drop = self._dropout_table(dropout)
-            if table_drop is not None:
-                return self._beam_search_dropout(features, boxes, batch_size, beam_size, out_size, early, table_drop)
-            ids, logp = self.beam_search(features, boxes, batch_size, beam_size, out_size=out_size, early_exit=early_exit)
-            return ids.reshape(batch_size, out_size, -1), logp.reshape(batch_size, out_size, -1), None
-        if early == "device" and self.precision != "f32":
-            raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
-        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, beam_size)
-        d = self.desc
-        T, V = d.max_len, d.vocab
-        ws, need = self._get_workspace(B, N, beam_size, return_probs)
-        ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
-        logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
-        everything = torch.empty(B, beam_size, T, V, dtype=torch.float32, device=self.device) if return_probs else None
-        self.last_steps_run = T
-        if early == "device" and not return_probs:
-            steps = self._steps_tensor()
-            if not self.use_graph:       # OVC_GRAPH=0: every call is the first of its shape (plain gated launches)
-                self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
-            check(self.lib.ovc_beam_search_gated(ctypes.byref(d), features.data_ptr(),
-                                                 None if boxes is None else boxes.data_ptr(), B, N, beam_size, out_size,
-                                                 ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(), steps.data_ptr(),
-                                                 native.stream_handle()), "ovc_beam_search_gated")
-            self.last_steps_device = steps
-        elif early and not return_probs:
-            steps = ctypes.c_int(0)
-            check(self.lib.ovc_beam_search_early(ctypes.byref(d), features.data_ptr(),
-                                                 None if boxes is None else boxes.data_ptr(), B, N, beam_size, out_size,
-                                                 ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(), ctypes.byref(steps),
-                                                 native.stream_handle()), "ovc_beam_search_early")
-            self.last_steps_run = steps.value
-        elif self.use_graph and not return_probs:
-            check(self.lib.ovc_beam_search_graph(ctypes.byref(d), features.data_ptr(),
-                                                 None if boxes is None else boxes.data_ptr(), B, N, beam_size, out_size,
-                                                 ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
-                                                 native.stream_handle()), "ovc_beam_search_graph")
-        else:
-            check(self.lib.ovc_beam_search(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(),
-                                           B, N, beam_size, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
-                                           None if everything is None else everything.data_ptr(),
-                                           native.stream_handle()), "ovc_beam_search")
+        ids, logp, everything, slots = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early,
+                                                        table_drop)
+        if dropout is not None:
+            return ids, logp, slots
         if out_size == 1:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)

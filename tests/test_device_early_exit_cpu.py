@@ -1,5 +1,6 @@
 """Device-side early exit (ovc_beam_search_gated) without a GPU: the C entry point is declared, bound and exported, and the
 host accepts exactly the early-exit values it documents."""
+import ctypes
 import os
 import re
 
@@ -28,6 +29,22 @@ def test_gated_search_refuses_bad_arguments_before_touching_a_device():
     lib = native.load()
     # a null model (and null buffers) is refused with OVC_EINVAL before any device call
     assert lib.ovc_beam_search_gated(None, None, None, 1, 1, 1, 1, None, 0, None, None, None, None) == -1      # OVC_EINVAL
+
+
+def test_every_search_refuses_null_arguments_before_touching_a_device():
+    """All five search entry points go through one front end: a null model and null buffers are OVC_EINVAL (-1) there, and
+    ovc_beam_search_dropout's own checks (a null table, a mode outside 0..2) come first."""
+    lib = native.load()
+    head = (None, None, None, 1, 1, 1, 1, None, 0, None, None)     # model, features, boxes, B, N, k, out_size, workspace, bytes, ids, logp
+    assert lib.ovc_beam_search(*head, None, None) == -1
+    assert lib.ovc_beam_search_graph(*head, None) == -1
+    assert lib.ovc_beam_search_early(*head, None, None) == -1
+    assert lib.ovc_beam_search_gated(*head, None, None) == -1
+    slots = (ctypes.c_int32 * 1)()
+    for mode in (0, 1, 2):
+        assert lib.ovc_beam_search_dropout(*head, None, None, None, mode, None, None) == -1
+        assert lib.ovc_beam_search_dropout(*head, None, None, slots, mode, None, None) == -1            # a null dropout table
+    assert lib.ovc_beam_search_dropout(*head, None, None, None, 3, None, None) == -1
 
 
 @pytest.mark.parametrize("value,mode", [(None, False), (False, False), (True, True), ("device", "device")])

@@ -212,21 +212,28 @@ void carve_encoder(Workspace& w, Bump& a, const ovc_model* m, int B, int N) {
     w.vx = a.take<float>(L * lv * BN * hv);
 }
 
+// The decoder's row buffers, one set shared by every layer: the same list for the search (rows = B*k) and the teacher-forced
+// forward (rows = B*S*T).
+void carve_decoder_rows(Workspace& w, Bump& a, const ovc_model* m, size_t rows) {
+    const size_t d = m->d_model, hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels;
+    w.x = a.take<float>(rows * d); w.x1 = a.take<float>(rows * d); w.x2 = a.take<float>(rows * d); w.y = a.take<float>(rows * d);
+    w.q = a.take<float>(rows * hk);
+    w.att = a.take<float>(lv * rows * hv);
+    w.ff = a.take<float>(rows * m->d_ff);
+    w.info = a.take<float>(rows * d); w.gate = a.take<float>(rows * d);
+    w.enc_att = a.take<float>(lv * rows * d); w.alpha = a.take<float>(lv * rows * d); w.mixed = a.take<float>(rows * d);
+    // the meshed block's stacked cross-attention outputs: written for every level count, one level included (a zero-byte
+    // take would alias the next buffer)
+    w.ymesh = a.take<float>(m->dec_kind == OVC_DEC_MESHED ? lv * rows * d : 0);
+}
+
 Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_probs, bool dropout = false) {
     Workspace w{};
     Bump a{reinterpret_cast<char*>(base), 0};
     const size_t R = (size_t)B * k, d = m->d_model, T = m->max_len;
-    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels, L = m->n_dec;
+    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, L = m->n_dec;
     carve_encoder(w, a, m, B, N);
-    w.x = a.take<float>(R * d); w.x1 = a.take<float>(R * d); w.x2 = a.take<float>(R * d); w.y = a.take<float>(R * d);
-    w.q = a.take<float>(R * hk);
-    w.att = a.take<float>(lv * R * hv);
-    w.ff = a.take<float>(R * m->d_ff);
-    w.info = a.take<float>(R * d); w.gate = a.take<float>(R * d);
-    w.enc_att = a.take<float>(lv * R * d); w.alpha = a.take<float>(lv * R * d); w.mixed = a.take<float>(R * d);
-    // the meshed block's stacked cross-attention outputs: written for every level count, one level included (a zero-byte
-    // take would alias the next buffer)
-    w.ymesh = a.take<float>(m->dec_kind == OVC_DEC_MESHED ? lv * R * d : 0);
+    carve_decoder_rows(w, a, m, R);
     w.part = a.take<float>(kMaxKSplit * R * d);
     w.kc = a.take<float>(L * T * R * hk);
     w.vc = a.take<float>(L * T * R * hv);
@@ -264,16 +271,11 @@ constexpr int kFusedVocabBlocks = 512;
 Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int want_logp, int S = 1) {
     Workspace w{};
     Bump a{reinterpret_cast<char*>(base), 0};
-    const size_t rows = (size_t)B * S * T, d = m->d_model, V = m->vocab;
-    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v, lv = m->n_levels;
+    const size_t rows = (size_t)B * S * T, V = m->vocab;
+    const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v;
     carve_encoder(w, a, m, B, N);
-    w.x = a.take<float>(rows * d); w.x1 = a.take<float>(rows * d); w.x2 = a.take<float>(rows * d); w.y = a.take<float>(rows * d);
-    w.q = a.take<float>(rows * hk); w.kc = a.take<float>(rows * hk); w.vc = a.take<float>(rows * hv);
-    w.att = a.take<float>(lv * rows * hv);
-    w.ff = a.take<float>(rows * m->d_ff);
-    w.info = a.take<float>(rows * d); w.gate = a.take<float>(rows * d);
-    w.enc_att = a.take<float>(lv * rows * d); w.alpha = a.take<float>(lv * rows * d); w.mixed = a.take<float>(rows * d);
-    w.ymesh = a.take<float>(m->dec_kind == OVC_DEC_MESHED ? lv * rows * d : 0);       // as in carve: one level too
+    carve_decoder_rows(w, a, m, rows);
+    w.kc = a.take<float>(rows * hk); w.vc = a.take<float>(rows * hv);        // one layer's keys / values, not a cache
     w.padflag = a.take<uint8_t>(rows);
     w.self_mask = a.take<uint8_t>(rows * T);
     w.tgt = a.take<int32_t>(rows);
@@ -289,6 +291,15 @@ Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int
     }
     w.bytes = (a.off + 255) & ~(size_t)255;
     return w;
+}
+
+// Without a tape (Workspace::tape == nullptr) every layer writes the ONE shared set of buffers: that set in the tape's shape, so
+// that a layer is issued against a tape slot either way.  The encoder's `out` is chosen per layer (run_encoder_layers); the
+// decoder's keys / values are the forward's w.kc / w.vc or the step's cache rows.
+EncTape scratch_enc(const Workspace& w) { return EncTape{w.eq, w.ek, w.ev, w.eatt, w.ey, w.xe[1], w.eff, w.ey, nullptr}; }
+ClTape scratch_cl(const Workspace& w) { return ClTape{{w.ek, w.ek}, {w.ev, w.ev}, w.eatt, w.ey, w.xe[0], w.einfo, w.ey}; }
+DecTape scratch_dec(const Workspace& w, float* k, float* v) {
+    return DecTape{w.q, k, v, w.att, w.y, w.x1, w.q, w.att, w.y, w.x2, w.ff, w.y, w.x};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -744,25 +755,27 @@ int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
     hipStream_t s = e.stream;
     const ovc_mha& at = m->cl_att;
     float* o1 = w.cl_out; float* o2 = w.cl_out + nd; float* o3 = w.cl_out + 2 * nd;
-    // training: what the backward reads goes to the tape (ClTape); the same launches on other buffers, the same bits
-    const ClTape* tp = w.tape ? &w.tape->cl : nullptr;
-    float* o2p = tp ? tp->o2p : w.xe[0]; float* o3p = w.xe[1];
+    // training: what the backward reads goes to the tape (ClTape); the same launches on other buffers, the same bits.  The tape
+    // keeps both cross calls' att / ya, the shared buffers the current call's
+    const ClTape scratch = scratch_cl(w);
+    const ClTape& b = w.tape ? w.tape->cl : scratch;
+    const size_t slot = w.tape ? 1 : 0;
+    float* o3p = w.xe[1];
     e.gemm_class = 1;
     e.kchains = 1;
     // both calls' queries come from the original o2 / o3, which lie back to back: ONE product of 2 * B * N rows
     TRY(e.linear(o2, d, at.q, nullptr, w.cl_q, 2 * BN, hk, 0));
-    const float* keys[2] = {o1, o2p};
+    const float* keys[2] = {o1, b.o2p};
     const float* queries[2] = {o2, o3};
-    float* outs[2] = {o2p, o3p};
+    float* outs[2] = {b.o2p, o3p};
     for (int c = 0; c < 2; ++c) {
-        float* ek = tp ? tp->k[c] : w.ek; float* ev = tp ? tp->v[c] : w.ev;
-        float* eatt = tp ? tp->att + (size_t)c * BN * hv : w.eatt; float* ya = tp ? tp->ya + (size_t)c * nd : w.ey;
+        float* eatt = b.att + slot * c * BN * hv; float* ya = b.ya + slot * c * nd;
         GemmArgs a{};
         a.A1 = keys[c]; a.lda1 = d; a.K1 = d; a.M = BN; a.seg_n = hk; a.nseg = 2; a.ldc = hk;
-        a.seg[0] = e.seg(at.k, ek);
-        a.seg[1] = e.seg(at.v, ev);
+        a.seg[0] = e.seg(at.k, b.k[c]);
+        a.seg[1] = e.seg(at.v, b.v[c]);
         TRY(e.gemm(a));
-        RUN(ovc_attention(w.cl_q + (size_t)c * BN * hk, ek, ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0, nullptr, nullptr,
+        RUN(ovc_attention(w.cl_q + (size_t)c * BN * hk, b.k[c], b.v[c], B, N, N, eh, edk, edv, w.enc_mask, N, 0, nullptr, nullptr,
                           nullptr, 0, 1.f, 1.f, eatt, s));
         TRY(e.linear(eatt, hv, at.o, nullptr, ya, BN, d, 0));
         RUN(ovc_layer_norm_post_launch(ya, queries[c], at.ln.g, at.ln.b, m->ln_eps, kCrossScale, outs[c], BN, d, s));
@@ -772,11 +785,10 @@ int run_cross_level_tail(Engine& e, Workspace& w, int B, int N) {
         hipLaunchKernelGGL(concat_levels_kernel, dim3(1024), dim3(256), 0, s, w.cl_out, w.cl_cat, 3, (size_t)BN, (size_t)d / 4);
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
-    float* a1 = tp ? tp->a1 : w.einfo; float* h2 = tp ? tp->h2 : w.ey;
-    TRY(e.linear(w.cl_cat, 3 * d, m->cl_mlp1, nullptr, a1, BN, d, 0));
-    RUN(ovc_leaky_residual(a1, d, nullptr, 0, kSlope, 1.f, a1, d, BN, d, s));
-    TRY(e.linear(a1, d, m->cl_mlp2, nullptr, h2, BN, d, 0));
-    RUN(ovc_leaky_residual(h2, d, o3p, d, kSlope, kMlpScale, w.enc_levels, d, BN, d, s));
+    TRY(e.linear(w.cl_cat, 3 * d, m->cl_mlp1, nullptr, b.a1, BN, d, 0));
+    RUN(ovc_leaky_residual(b.a1, d, nullptr, 0, kSlope, 1.f, b.a1, d, BN, d, s));
+    TRY(e.linear(b.a1, d, m->cl_mlp2, nullptr, b.h2, BN, d, 0));
+    RUN(ovc_leaky_residual(b.h2, d, o3p, d, kSlope, kMlpScale, w.enc_levels, d, BN, d, s));
     return OVC_OK;
 }
 
@@ -790,33 +802,31 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
     RUN(ovc_layer_norm(w.ey, nullptr, m->enc_ln.g, m->enc_ln.b, w.pe, N, nullptr, m->ln_eps, w.xe[0], BN, d, s));
 
     float* x = w.xe[0];
+    const EncTape scratch = scratch_enc(w);
     for (int l = 0; l < m->n_enc; ++l) {
         const ovc_mha& at = m->enc[l].att;
         // training (ovc_forward_backward): every intermediate the backward reads goes to the layer's own tape slot; the same
         // launches on other buffers, so the bits are those of the inference forward
-        const EncTape* tp = w.tape ? &w.tape->enc[l] : nullptr;
-        float* eq = tp ? tp->q : w.eq; float* ek = tp ? tp->k : w.ek; float* ev = tp ? tp->v : w.ev;
-        float* eatt = tp ? tp->att : w.eatt; float* ya = tp ? tp->ya : w.ey; float* x1 = tp ? tp->x1 : w.xe[1];
-        float* eff = tp ? tp->ff : w.eff; float* yf = tp ? tp->yf : w.ey;
+        const EncTape& b = w.tape ? w.tape->enc[l] : scratch;
         GemmArgs a{};
         a.A1 = x; a.lda1 = d; a.K1 = d; a.M = BN; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
-        a.seg[0] = e.seg(at.q, eq);
-        a.seg[1] = e.seg(at.k, ek);
-        a.seg[2] = e.seg(at.v, ev);
+        a.seg[0] = e.seg(at.q, b.q);
+        a.seg[1] = e.seg(at.k, b.k);
+        a.seg[2] = e.seg(at.v, b.v);
         TRY(e.gemm(a));
         const int mem = at.m_k ? m->memory : 0;
-        RUN(ovc_attention(eq, ek, ev, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
+        RUN(ovc_attention(b.q, b.k, b.v, B, N, N, eh, edk, edv, w.enc_mask, N, 0,
                           m->enc_kind == OVC_ENC_GEOMETRIC ? w.geometry : nullptr, at.m_k, at.m_v, mem,
-                          sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), eatt, s));
-        TRY(e.linear(eatt, hv, at.o, x, ya, BN, d, 0, enc_site(l, 0)));
-        RUN(ovc_layer_norm(ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, x1, BN, d, s));
-        TRY(e.aoa(at, x, x1, w.einfo, w.egate, BN));
+                          sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), b.att, s));
+        TRY(e.linear(b.att, hv, at.o, x, b.ya, BN, d, 0, enc_site(l, 0)));
+        RUN(ovc_layer_norm(b.ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, b.x1, BN, d, s));
+        TRY(e.aoa(at, x, b.x1, w.einfo, w.egate, BN));
         // layer output: straight into the level slot (multilevel, cross-level) or the ping-pong buffer
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
                                                         : (l == m->n_enc - 1 ? w.enc_levels : x);
-        if (tp && l < m->n_enc - 1 && m->enc_kind != OVC_ENC_CROSS_LEVEL) out = tp->out;     // cl_out keeps every level
-        TRY(e.ffn(m->enc[l].ffn, x1, eff, yf, nullptr, out, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
+        if (w.tape && l < m->n_enc - 1 && m->enc_kind != OVC_ENC_CROSS_LEVEL) out = b.out;   // cl_out keeps every level
+        TRY(e.ffn(m->enc[l].ffn, b.x1, b.ff, b.yf, nullptr, out, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         x = out;
     }
     if (m->enc_kind == OVC_ENC_CROSS_LEVEL) TRY(run_cross_level_tail(e, w, B, N));
@@ -898,6 +908,129 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
     return carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr);
 }
 
+// One pass over the decoder's layers, described once: a decode step of a search (run_decode_step) or the teacher-forced decoder
+// over whole sequences (run_forward_decoder).  It holds only what differs between the two; a layer's launches
+// (run_decoder_layer) are functions of it and of the buffers the layer writes (a DecTape: the training tape's slot, or
+// scratch_dec).  Engine::gemm_class, kchains, gate and decode_key stay with the caller.
+struct DecoderPass {
+    enum Kind { Step, Sequence } kind;              // which attention kernels run, over what
+    int rows;                                       // decoder rows: B*width, B*S*T
+    int B, N;
+    const uint8_t* zero_rows;                       // [rows] the <pad> rows, cleared behind the FFN
+    float* part;                                    // the AddNorms' K-split partial products (Workspace::part); nullptr: whole products
+    bool name_sites;                                // the dropout sites dec_site(l, j) are named (else -1: every launch the plain one)
+    int t, width, R; const int32_t* anc;            // Step: step t of B*width rows in caches of R slots per position, its ancestor table
+    int S, T;                                       // Sequence: S sequences of T positions per image
+    int site(int l, int j) const { return name_sites ? dec_site(l, j) : -1; }
+};
+
+// Decoder layer l of a pass: x -> b.out.  Both callers issue every stage from here; they differ in the attention kernels alone.
+int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, const DecTape& b, const float* x) {
+    const ovc_model* m = e.m;
+    const ovc_dec_layer& dl = m->dec[l];
+    hipStream_t s = e.stream;
+    const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels;
+    const int rows = p.rows, B = p.B, N = p.N;
+    const float scale = sqrtf((float)m->d_k);
+    // ---- masked self-attention: over the beam's own history, or over the caption ---------------
+    GemmArgs a{};
+    a.A1 = x; a.lda1 = d; a.K1 = d; a.M = rows; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
+    a.seg[0] = e.seg(dl.self_att.q, b.q);
+    a.seg[1] = e.seg(dl.self_att.k, b.k);
+    a.seg[2] = e.seg(dl.self_att.v, b.v);
+    TRY(e.gemm(a));
+    if (p.kind == DecoderPass::Step) {
+        DecodeSelfArgs sa{};
+        sa.q = b.q; sa.ldq = hk; sa.pos_stride = (size_t)p.R * hk; sa.ldkv = hk;
+        sa.kcache = b.k - p.t * sa.pos_stride; sa.vcache = b.v - p.t * sa.pos_stride;     // b.k, b.v: the cache rows of step t
+        sa.anc = p.anc; sa.anc_ld = m->max_len; sa.padflag = w.padflag; sa.pad_ld = p.R; sa.t = p.t; sa.width = p.width;
+        sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = b.att; sa.ldo = hv;
+        sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
+        if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s, e.gate));
+    } else {
+        const int smem = dl.self_att.m_k ? m->memory : 0;
+        RUN(ovc_attention(b.q, b.k, b.v, B * p.S, p.T, p.T, m->heads, m->d_k, m->d_v, w.self_mask, (long)p.T * p.T, p.T, nullptr,
+                          dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), b.att, s));
+    }
+    TRY(e.linear_ln(b.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, b.ys, p.part, b.x1, rows, p.site(l, 0)));
+    TRY(e.aoa(dl.self_att, x, b.x1, w.info, w.gate, rows));
+
+    // ---- cross-attention over every encoder level: the image's rows share its projected keys / values ----
+    TRY(e.linear(b.x1, d, dl.cross_att.q, nullptr, b.qc, rows, hk, 0));
+    if (p.kind == DecoderPass::Step) {
+        DecodeCrossArgs ca{};
+        ca.q = b.qc; ca.ldq = hk;
+        ca.kx = w.kx + (size_t)l * lv * B * N * hk; ca.vx = w.vx + (size_t)l * lv * B * N * hv;
+        ca.level_stride = (size_t)B * N * hk; ca.ldkv = hk; ca.encmask = w.enc_mask; ca.n = N; ca.width = p.width;
+        ca.heads = m->heads; ca.dk = m->d_k; ca.dv = m->d_v; ca.out = b.attc; ca.out_level_stride = (size_t)rows * hv; ca.ldo = hv;
+        if (!(debug_skip() & 4)) RUN(ovc_decode_cross_attention(ca, B, m->heads, lv, s, e.gate));
+    } else {
+        const int cmem = dl.cross_att.m_k ? m->memory : 0;
+        for (int lvl = 0; lvl < lv; ++lvl) {
+            const size_t off = ((size_t)l * lv + lvl) * B * N * hk;
+            RUN(ovc_attention(b.qc, w.kx + off, w.vx + off, B, p.S * p.T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
+                              dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
+                              b.attc + (size_t)lvl * rows * hv, s));
+        }
+    }
+    const float* ffn_in;
+    if (m->dec_kind == OVC_DEC_MESHED) {
+        // decoders.py:51-73: one shared enc_attn per level, sigmoid-gated sum / sqrt(levels).  The levels'
+        // attention outputs are stacked [levels][rows][h*dv], so the shared output projection and its
+        // LayerNorm run once over levels*rows rows (the residual x1 is broadcast with res_mod).
+        const size_t nrd = (size_t)rows * d;
+        if (!dl.cross_att.aoa_i.w) {
+            GemmArgs o{};
+            o.A1 = b.attc; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
+            o.R = b.x1; o.ldr = d; o.res_mod = rows;
+            o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
+            TRY(e.gemm(o));
+            RUN(ovc_layer_norm_gated(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                     w.enc_att, lv * rows, d, s, e.gate));
+        } else {
+            for (int lvl = 0; lvl < lv; ++lvl) {      // AoA gates need the per-level pair (x1, enc_att_l)
+                TRY(e.linear(b.attc + (size_t)lvl * rows * hv, hv, dl.cross_att.o, b.x1, b.yc, rows, d, 0));
+                RUN(ovc_layer_norm_gated(b.yc, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                         w.enc_att + lvl * nrd, rows, d, s, e.gate));
+                TRY(e.aoa(dl.cross_att, b.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
+            }
+        }
+        // level gates alpha_l = W_l [x1 ; enc_att_l] + b_l (decoders.py:59-66): one launch, a segment per level,
+        // each with its own second input block (separate launches when the width does not align with the tiles)
+        {
+            GemmArgs g{};
+            g.A1 = b.x1; g.lda1 = d; g.K1 = d; g.lda2 = d; g.K2 = d;
+            g.M = rows; g.seg_n = d; g.ldc = d;
+            const bool fused = d % 64 == 0 && lv <= OVC_MAX_SEGMENTS;
+            for (int lvl = 0; lvl < lv; ++lvl) {
+                const GemmSegment seg = e.seg(dl.alpha[lvl], w.alpha + lvl * nrd, w.enc_att + lvl * nrd);
+                if (fused) { g.seg[lvl] = seg; continue; }
+                g.seg[0] = seg; g.nseg = 1;
+                TRY(e.gemm(g));
+            }
+            if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
+        }
+        RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s, e.gate));
+        ffn_in = w.mixed;
+    } else {
+        TRY(e.linear_ln(b.attc, hv, dl.cross_att.o, b.x1, dl.cross_att.ln, nullptr, b.yc, p.part, b.x2, rows, p.site(l, 1)));
+        TRY(e.aoa(dl.cross_att, b.x1, b.x2, w.info, w.gate, rows));
+        ffn_in = b.x2;
+    }
+    return e.ffn(dl.ffn, ffn_in, b.ff, b.yf, p.part, b.out, p.zero_rows, rows, p.site(l, 2), p.site(l, 3));
+}
+
+// logits^T [V][ld] = fc [V, d] . x^T over `rows` decoder rows, ld = rows padded to 4, with the block pieces (per row and 32-word
+// block the maximum and the sum of exponentials) in the epilogue.  logits == nullptr: the pieces alone.
+GemmArgs transposed_vocab_product(const ovc_model* m, const float* x, int rows, float* logits, float* stats) {
+    const int d = m->d_model, nblk = (m->vocab + 31) / 32;
+    GemmArgs g{};
+    g.A1 = m->fc; g.lda1 = d; g.K1 = d; g.M = m->vocab; g.seg_n = rows; g.nseg = 1; g.ldc = (rows + 3) & ~3;
+    g.seg[0] = GemmSegment{x, nullptr, logits, nullptr, nullptr};
+    g.stats_t = stats; g.stats_ld = (nblk + 1) & ~1;
+    return g;
+}
+
 // Step t of a search.  Gated: every launch of step t >= 1 is gated on alive_count[t - 1]; the early-exit forms count live beams.
 int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     const ovc_model* m = e.m;
@@ -905,7 +1038,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     const bool return_probs = c.all_logp_out != nullptr, count_alive = c.counts_alive();
     e.gate = c.form == SearchForm::Gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
     hipStream_t s = e.stream;
-    const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels, T = m->max_len;
+    const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, T = m->max_len;
     const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
     const int cur = t & 1, nxt = cur ^ 1;
     uint8_t* padflag_t = w.padflag + (size_t)t * R;
@@ -913,7 +1046,6 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     // the plain ones
     const bool keyed = e.drop != nullptr && !e.dry;
     e.decode_key = keyed ? DecodeRowKey{width, k, T, t} : DecodeRowKey{0, 0, 0, 0};
-    auto site = [&](int l, int j) { return keyed ? dec_site(l, j) : -1; };
 
     if (t == 0 && !e.dry) {       // later steps: the previous step's update kernel has written the input rows and pad flags
         hipLaunchKernelGGL(decode_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.tok, m->bos_idx, m->pad_idx, t,
@@ -927,81 +1059,13 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
         static const int forced = [] { const char* v = OVC_HOOK_ENV("OVC_DEBUG_DECODE_KCHAINS"); return v ? atoi(v) : 0; }();
         if (forced == 1 || forced == 4) e.kchains = forced;
     }
-    float* x = w.x;
+    DecoderPass pass{DecoderPass::Step, rows, B, N, padflag_t, w.part, keyed};
+    pass.t = t; pass.width = width; pass.R = R; pass.anc = w.anc[cur];
+    const float* x = w.x;         // every layer reads and writes the one buffer
     for (int l = 0; l < m->n_dec; ++l) {
-        const ovc_dec_layer& dl = m->dec[l];
-        // ---- masked self-attention over the beam's own history ------------------------------------
-        float* kc = w.kc + (size_t)l * T * R * hk;
-        float* vc = w.vc + (size_t)l * T * R * hv;
-        GemmArgs a{};
-        a.A1 = x; a.lda1 = d; a.K1 = d; a.M = rows; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
-        a.seg[0] = e.seg(dl.self_att.q, w.q);
-        a.seg[1] = e.seg(dl.self_att.k, kc + (size_t)t * R * hk);
-        a.seg[2] = e.seg(dl.self_att.v, vc + (size_t)t * R * hv);
-        TRY(e.gemm(a));
-        DecodeSelfArgs sa{};
-        sa.q = w.q; sa.ldq = hk; sa.kcache = kc; sa.vcache = vc; sa.pos_stride = (size_t)R * hk; sa.ldkv = hk;
-        sa.anc = w.anc[cur]; sa.anc_ld = T; sa.padflag = w.padflag; sa.pad_ld = R; sa.t = t; sa.width = width;
-        sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = w.att; sa.ldo = hv;
-        sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
-        if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s, e.gate));
-        TRY(e.linear_ln(w.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, w.y, w.part, w.x1, rows, site(l, 0)));
-        TRY(e.aoa(dl.self_att, x, w.x1, w.info, w.gate, rows));
-
-        // ---- cross-attention: the image's beams share its projected encoder keys/values -----------
-        TRY(e.linear(w.x1, d, dl.cross_att.q, nullptr, w.q, rows, hk, 0));
-        DecodeCrossArgs ca{};
-        ca.q = w.q; ca.ldq = hk;
-        ca.kx = w.kx + (size_t)l * lv * B * N * hk; ca.vx = w.vx + (size_t)l * lv * B * N * hv;
-        ca.level_stride = (size_t)B * N * hk; ca.ldkv = hk; ca.encmask = w.enc_mask; ca.n = N; ca.width = width;
-        ca.heads = m->heads; ca.dk = m->d_k; ca.dv = m->d_v; ca.out = w.att; ca.out_level_stride = (size_t)rows * hv; ca.ldo = hv;
-        if (!(debug_skip() & 4)) RUN(ovc_decode_cross_attention(ca, B, m->heads, lv, s, e.gate));
-        float* ffn_in;
-        if (m->dec_kind == OVC_DEC_MESHED) {
-            // decoders.py:51-73: one shared enc_attn per level, sigmoid-gated sum / sqrt(levels).  The levels'
-            // attention outputs are stacked [levels][rows][h*dv], so the shared output projection and its
-            // LayerNorm run once over levels*rows rows (the residual x1 is broadcast with res_mod).
-            const size_t nrd = (size_t)rows * d;
-            if (!dl.cross_att.aoa_i.w) {
-                GemmArgs o{};
-                o.A1 = w.att; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
-                o.R = w.x1; o.ldr = d; o.res_mod = rows;
-                o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
-                TRY(e.gemm(o));
-                RUN(ovc_layer_norm_gated(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                         w.enc_att, lv * rows, d, s, e.gate));
-            } else {
-                for (int lvl = 0; lvl < lv; ++lvl) {      // AoA gates need the per-level pair (x1, enc_att_l)
-                    TRY(e.linear(w.att + (size_t)lvl * rows * hv, hv, dl.cross_att.o, w.x1, w.y, rows, d, 0));
-                    RUN(ovc_layer_norm_gated(w.y, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                             w.enc_att + lvl * nrd, rows, d, s, e.gate));
-                    TRY(e.aoa(dl.cross_att, w.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
-                }
-            }
-            // level gates alpha_l = W_l [x1 ; enc_att_l] + b_l (decoders.py:59-66): one launch, a segment per level,
-            // each with its own second input block (separate launches when the width does not align with the tiles)
-            {
-                GemmArgs g{};
-                g.A1 = w.x1; g.lda1 = d; g.K1 = d; g.lda2 = d; g.K2 = d;
-                g.M = rows; g.seg_n = d; g.ldc = d;
-                const bool fused = d % 64 == 0 && lv <= OVC_MAX_SEGMENTS;
-                for (int lvl = 0; lvl < lv; ++lvl) {
-                    const GemmSegment seg = e.seg(dl.alpha[lvl], w.alpha + lvl * nrd, w.enc_att + lvl * nrd);
-                    if (fused) { g.seg[lvl] = seg; continue; }
-                    g.seg[0] = seg; g.nseg = 1;
-                    TRY(e.gemm(g));
-                }
-                if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
-            }
-            RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s, e.gate));
-            ffn_in = w.mixed;
-        } else {
-            TRY(e.linear_ln(w.att, hv, dl.cross_att.o, w.x1, dl.cross_att.ln, nullptr, w.y, w.part, w.x2, rows, site(l, 1)));
-            TRY(e.aoa(dl.cross_att, w.x1, w.x2, w.info, w.gate, rows));
-            ffn_in = w.x2;
-        }
-        TRY(e.ffn(dl.ffn, ffn_in, w.ff, w.y, w.part, w.x, padflag_t, rows, site(l, 2), site(l, 3)));
-        x = w.x;
+        // the layer's keys / values go to its cache [L][T][R][h*dk|h*dv], the rows of step t
+        const size_t at = ((size_t)l * T + t) * R;
+        TRY(run_decoder_layer(e, w, l, pass, scratch_dec(w, w.kc + at * hk, w.vc + at * hv), x));
     }
 
     // ---- vocabulary projection, fused log-softmax + candidate scores + top-k, bookkeeping ---------
@@ -1012,7 +1076,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     // and OVC_SELECT_TWO_PASS (A/B switch) take the round-2 pair of kernels that read every logit back.
     const int nblk = (m->vocab + 31) / 32;
     static const bool two_pass = OVC_HOOK_ENV("OVC_SELECT_TWO_PASS") != nullptr;
-    const bool fused_select = !two_pass && nblk <= 512;
+    const bool fused_select = !two_pass && nblk <= kFusedVocabBlocks;
     // fp32 mode + fused selection: the product runs TRANSPOSED -- logits^T [V][rows] = fc [V, d] . x^T, the same kernel with the
     // operands' roles swapped (both are K-contiguous) and the same bits (every dot product sums the same k order; a * b
     // commutes).  A lane of the accumulator then holds 16 WORDS of one beam row, which makes the block maximum / sum exp an
@@ -1033,9 +1097,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
         if (transposed) e.kchains = vocab_chains == 4 ? 4 : 1;
         GemmArgs g{};
         if (transposed) {
-            g.A1 = m->fc; g.lda1 = d; g.K1 = d; g.M = m->vocab; g.seg_n = rows; g.nseg = 1; g.ldc = ldt;
-            g.seg[0] = GemmSegment{x, nullptr, w.logits, nullptr, nullptr};
-            g.stats_t = w.stats; g.stats_ld = (nblk + 1) & ~1;
+            g = transposed_vocab_product(m, x, rows, w.logits, w.stats);
         } else {
             g.A1 = x; g.lda1 = d; g.K1 = d; g.M = rows; g.seg_n = m->vocab; g.nseg = 1; g.ldc = ldv;
             g.seg[0] = GemmSegment{m->fc, nullptr, w.logits, nullptr, m->precision > 0 ? m->fc_planes : nullptr};
@@ -1090,101 +1152,29 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
 // the cross keys / values are computed once per image.  S = 1 is the call above, launch for launch.
 int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_logp, int S = 1) {
     const ovc_model* m = e.m;
-    hipStream_t s = e.stream;
-    const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, lv = m->n_levels;
-    const int rows = B * S * T, BN = B * N;
-    const float scale = sqrtf((float)m->d_k);
+    const int d = m->d_model, rows = B * S * T;
     e.gemm_class = 2;
     e.kchains = 1;
-    float* x = w.x;
+    DecoderPass pass{DecoderPass::Sequence, rows, B, N, w.padflag, nullptr, true};
+    pass.S = S; pass.T = T;
+    // training: the layer's own tape slots (see run_encoder_layers); the meshed branch never runs with a tape
+    const DecTape scratch = scratch_dec(w, w.kc, w.vc);
+    const float* x = w.x;
     for (int l = 0; l < m->n_dec; ++l) {
-        const ovc_dec_layer& dl = m->dec[l];
-        // training: the layer's own tape slots (see run_encoder_layers); the meshed branch never runs with a tape
-        const DecTape* tp = w.tape ? &w.tape->dec[l] : nullptr;
-        float* sq = tp ? tp->q : w.q; float* sk = tp ? tp->k : w.kc; float* sv = tp ? tp->v : w.vc;
-        float* satt = tp ? tp->att : w.att; float* ys = tp ? tp->ys : w.y; float* x1 = tp ? tp->x1 : w.x1;
-        float* cq = tp ? tp->qc : w.q; float* catt = tp ? tp->attc : w.att; float* yc = tp ? tp->yc : w.y;
-        float* x2 = tp ? tp->x2 : w.x2; float* ff = tp ? tp->ff : w.ff; float* yf = tp ? tp->yf : w.y;
-        float* out = tp ? tp->out : w.x;
-        // ---- masked self-attention over the caption ------------------------------------------------
-        GemmArgs a{};
-        a.A1 = x; a.lda1 = d; a.K1 = d; a.M = rows; a.seg_n = hk; a.nseg = 3; a.ldc = hk;
-        a.seg[0] = e.seg(dl.self_att.q, sq);
-        a.seg[1] = e.seg(dl.self_att.k, sk);
-        a.seg[2] = e.seg(dl.self_att.v, sv);
-        TRY(e.gemm(a));
-        const int smem = dl.self_att.m_k ? m->memory : 0;
-        RUN(ovc_attention(sq, sk, sv, B * S, T, T, m->heads, m->d_k, m->d_v, w.self_mask, (long)T * T, T, nullptr,
-                          dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), satt, s));
-        TRY(e.linear_ln(satt, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, ys, nullptr, x1, rows, dec_site(l, 0)));
-        TRY(e.aoa(dl.self_att, x, x1, w.info, w.gate, rows));
-
-        // ---- cross-attention over every encoder level -----------------------------------------------
-        TRY(e.linear(x1, d, dl.cross_att.q, nullptr, cq, rows, hk, 0));
-        const int cmem = dl.cross_att.m_k ? m->memory : 0;
-        for (int lvl = 0; lvl < lv; ++lvl) {
-            const size_t off = ((size_t)l * lv + lvl) * BN * hk;
-            RUN(ovc_attention(cq, w.kx + off, w.vx + off, B, S * T, N, m->heads, m->d_k, m->d_v, w.enc_mask, N, 0, nullptr,
-                              dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
-                              catt + (size_t)lvl * rows * hv, s));
-        }
-        float* ffn_in;
-        if (m->dec_kind == OVC_DEC_MESHED) {
-            // the search's meshed block (run_decode_step) on rows = B*T
-            const size_t nrd = (size_t)rows * d;
-            if (!dl.cross_att.aoa_i.w) {
-                GemmArgs o{};
-                o.A1 = w.att; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
-                o.R = w.x1; o.ldr = d; o.res_mod = rows;
-                o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
-                TRY(e.gemm(o));
-                RUN(ovc_layer_norm(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                   w.enc_att, lv * rows, d, s));
-            } else {
-                for (int lvl = 0; lvl < lv; ++lvl) {
-                    TRY(e.linear(w.att + (size_t)lvl * rows * hv, hv, dl.cross_att.o, w.x1, w.y, rows, d, 0));
-                    RUN(ovc_layer_norm(w.y, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                       w.enc_att + lvl * nrd, rows, d, s));
-                    TRY(e.aoa(dl.cross_att, w.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
-                }
-            }
-            {
-                GemmArgs g{};
-                g.A1 = w.x1; g.lda1 = d; g.K1 = d; g.lda2 = d; g.K2 = d;
-                g.M = rows; g.seg_n = d; g.ldc = d;
-                const bool fused = d % 64 == 0 && lv <= OVC_MAX_SEGMENTS;
-                for (int lvl = 0; lvl < lv; ++lvl) {
-                    const GemmSegment seg = e.seg(dl.alpha[lvl], w.alpha + lvl * nrd, w.enc_att + lvl * nrd);
-                    if (fused) { g.seg[lvl] = seg; continue; }
-                    g.seg[0] = seg; g.nseg = 1;
-                    TRY(e.gemm(g));
-                }
-                if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
-            }
-            RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s));
-            ffn_in = w.mixed;
-        } else {
-            TRY(e.linear_ln(catt, hv, dl.cross_att.o, x1, dl.cross_att.ln, nullptr, yc, nullptr, x2, rows, dec_site(l, 1)));
-            TRY(e.aoa(dl.cross_att, x1, x2, w.info, w.gate, rows));
-            ffn_in = x2;
-        }
-        TRY(e.ffn(dl.ffn, ffn_in, ff, yf, nullptr, out, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
-        x = out;
+        const DecTape& b = w.tape ? w.tape->dec[l] : scratch;
+        TRY(run_decoder_layer(e, w, l, pass, b, x));
+        x = b.out;
     }
 
     // ---- vocabulary product ----------------------------------------------------------------------
     e.gemm_class = 3;
-    const int nblk = (m->vocab + 31) / 32;
-    GemmArgs g{};
-    if (nblk <= kFusedVocabBlocks) {
-        // logits^T [V][rows] = fc . x^T with the block pieces in its epilogue, as the search runs it (run_decode_step)
-        g.A1 = m->fc; g.lda1 = d; g.K1 = d; g.M = m->vocab; g.seg_n = rows; g.nseg = 1; g.ldc = (rows + 3) & ~3;
-        g.seg[0] = GemmSegment{x, nullptr, want_logp ? w.logits : nullptr, nullptr, nullptr};
-        g.stats_t = w.stats; g.stats_ld = (nblk + 1) & ~1;
+    if ((m->vocab + 31) / 32 <= kFusedVocabBlocks) {
+        GemmArgs g = transposed_vocab_product(m, x, rows, want_logp ? w.logits : nullptr, w.stats);
         GemmLaunchOpts scoring{};
         if (!want_logp) { scoring.tgt = w.tgt; scoring.tgt_logit = w.tgt_logit; }
         return e.gemm(g, scoring);
     }
+    GemmArgs g{};
     g.A1 = x; g.lda1 = d; g.K1 = d; g.M = rows; g.seg_n = m->vocab; g.nseg = 1; g.ldc = m->vocab;
     g.seg[0] = GemmSegment{m->fc, nullptr, w.logits, nullptr, nullptr};
     return e.gemm(g);

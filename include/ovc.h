@@ -476,6 +476,42 @@ int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model* grads, co
 int ovc_dropout_mask_rows(const int64_t* seed, int site, const int32_t* mask_rows, long rows, long cols, float p, uint8_t* keep,
                           ovc_stream stream);
 
+/* Sampling: S captions per image drawn from the model's distribution, 1 <= S <= OVC_MAX_BEAM (appended to ABI 8; no struct
+ * changes).  The search machinery with a draw in place of the selection of the k best; every model the search runs, precision 0,
+ * vocabularies of at most 16 384 words (the block pieces of the fused vocabulary tail).  The rule, pinned to the bit:
+ * Rows.  Row (b, s) is row r = b * S + s at every step.  Step 0 runs one decoder row per image (as the beam search does) and all
+ * S samples of the image draw from that row's distribution, each with its own draw; from step 1 on sample s continues its own
+ * history: the ancestor of row (b, s) is row (b, s).
+ * Row pieces.  The beam search's: M = the maximum of the row's block maxima M_j, ls = log Z with Z = sum_j S_j exp(M_j - M) in the
+ * beam search's order, log-probability of word w = (x_w - M) - ls: the bits a beam's entry has for the same row and word.
+ * The draw.  r32 = Philox4x32-10(counter = (r, t, 0x53414D50, 0), key = (lo32(seed), hi32(seed)))[0] and
+ *     u = (float(r32 >> 8) + 0.5f) * 2^-24                                    (fp32 operations, round to nearest even)
+ * which is exact for r32 >> 8 < 2^23; above, the sum rounds to the even neighbour, and the single value r32 >> 8 = 2^24 - 1
+ * gives u = 1, where the last-word rule below applies.  Counter word 2 lies outside the dropout site range: no draw coincides
+ * with a mask word.  seed: one int64 in DEVICE memory, read on the device.
+ * The choice.  The inverse CDF in ascending word order, in two levels, target = u * Z.  Blocks: P(-1) = 0,
+ * P(j) = P(j - 1) + S_j exp(M_j - M); the block is the first j with P(j) > target.  Words: inside block j the prefix starts at
+ * P(j - 1) and adds exp(x_w - M) of the block's words below V, from the logits the vocabulary product stored; the word is the first
+ * whose prefix exceeds target.  If rounding leaves no such block or word the last block, or the block's last word below V, is
+ * taken; the word is in [0, V) whatever the logits hold.  The additions of the prefixes are wave scans in a fixed order (csrc/
+ * bodies/sample_fused_update.inc): the same bits on every call, stream, graph replay and GEMM tiling.
+ * Ended rows.  The beam search's bookkeeping: a row that has emitted <eos> is frozen -- word 0, log-probability exactly 0, its
+ * draw ignored, <pad> flags and next-input rows those of a frozen beam.
+ * Results in sample order, no final ordering: ids_out / logp_out [B][S][T].  ovc_sample: plain launches; all_logp_out
+ * [B][S][T][V] (or NULL) receives every step's log-probabilities (all 0 for a frozen row), as ovc_beam_search's does.
+ * ovc_sample_graph: the whole search as ONE captured graph from the second call of a (model, workspace, B, N, S); the seed is not
+ * baked in: it is copied to the workspace's seed slot before the replay.  Workspace: ovc_sample_workspace_bytes (0 when
+ * unsupported; return_probs as ovc_workspace_bytes).
+ * OVC_EINVAL, nothing launched: S outside 1..OVC_MAX_BEAM, a null seed, precision != 0, a vocabulary of more than 16 384 words.
+ * Not covered: temperature, top-k and nucleus sampling (the block pieces are those of the unscaled logits), sampling under
+ * dropout, the early-exit forms, more than OVC_MAX_BEAM samples per call (call again with another seed), results independent of
+ * an image's position in the batch (the counter holds b). */
+size_t ovc_sample_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs);
+int ovc_sample(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+               void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, float* all_logp_out, ovc_stream stream);
+int ovc_sample_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                     void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream);
+
 /* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
  * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host
  * (openviic_amd/cider.py) in float64.  An n-gram (n = 1..4) of word ids below 65535 is ONE 64-bit key: word j of the n-gram sits as

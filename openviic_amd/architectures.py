@@ -5,7 +5,8 @@ reference's names so its yaml files resolve unchanged.
 API kept: ``forward(input_features, fused=False) -> log-probs (B,T,V)`` (``fused=True``: on the engine); ``score(input_features)
 -> (B,T)`` target log-probs (engine); ``encoder_forward(input_features) ->
 (encoder_features, padding_mask (B,1,1,N) bool)``; ``step(t, prev_output)``;
-``beam_search(input_features, batch_size, beam_size, out_size=1, return_probs=False)``.
+``beam_search(input_features, batch_size, beam_size, out_size=1, return_probs=False)``;
+``sample(input_features, batch_size, n_samples, generator=None, return_probs=False)``.
 
 ``beam_search`` is the accelerated path: one call into the fused HIP engine
 (``csrc/engine.hip``) which runs encoder, every decode step and the beam bookkeeping on the
@@ -285,7 +286,7 @@ class BaseTransformer(Module):
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
-                  max_norm=None):
+                  max_norm=None, sample=False):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -313,12 +314,25 @@ class BaseTransformer(Module):
         before anything else is launched: parameters and optimizer state are untouched (under live dropout the seed has been
         drawn by then).
 
+        ``sample=True``: ``n_samples = beam_size`` sampled captions per image (``model.sample``: the original self-critical
+        recipe, sampled captions with their mean reward as baseline) in place of the beam search -- the first of the lines above
+        becomes ``outs, log_probs = model.sample(items, B, k, generator=generator)`` -- and everything behind it is unchanged.
+        One seed per call, drawn from ``generator``.  ``sample=True`` with ``dropout=True``, or with an ``early_exit`` other than
+        ``None`` / ``False``, is refused before any launch or draw (sampling has neither form; the ``OVC_EARLY_EXIT`` default does
+        not apply to it).
+
         ``p.grad`` is neither read nor written, and autograd is not involved (the call works under ``torch.no_grad()``): gradient
         hooks do NOT fire -- ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them
         DistributedDataParallel's gradient all-reduce.  A data-parallel run keeps the lines above."""
         from . import optim as _optim
         from . import scst as _scst
         from .cider import CiderCorpus
+        if sample and dropout:
+            raise engine.native.OvcError("scst_step(sample=True, dropout=True): sampling under dropout is not covered -- set "
+                                         "dropout=False (DROPOUT: 0 or model.eval())")
+        if sample and early_exit not in (None, False):
+            raise engine.native.OvcError("scst_step(sample=True, early_exit={!r}): sampling has no early-exit form -- leave "
+                                         "early_exit at None".format(early_exit))
         _checked_step_optimizer(optimizer, "scst_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "scst_step")
         corpus = reward if isinstance(reward, CiderCorpus) else None
@@ -331,6 +345,8 @@ class BaseTransformer(Module):
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
         eng._check_trainable()
+        if sample:
+            eng.check_sample(k)
         _checked_step_optimizer(optimizer, "scst_step", eng)
         boxes = input_features["region_boxes"] if self.uses_boxes else None
         feats, boxes = eng._checked_inputs(input_features[self.feature_field], boxes)
@@ -347,7 +363,10 @@ class BaseTransformer(Module):
                     B, eng.device, "{} {} on {}".format(rows.dtype, tuple(rows.shape), rows.device)
                     if isinstance(rows, torch.Tensor) else type(rows).__name__))
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        if drop is not None:
+        if sample:
+            outs, log_probs = eng.sample(feats, boxes, B, k, _dropout.draw_seed(eng.device, generator))
+            slots = None
+        elif drop is not None:
             outs, log_probs, slots = eng.beam_search(feats, None, B, k, out_size=k, early_exit=early_exit, dropout=drop)
         else:
             outs, log_probs = eng.beam_search(feats, boxes, B, k, out_size=k, early_exit=early_exit)
@@ -448,6 +467,30 @@ class BaseTransformer(Module):
         with self.statefulness(batch_size):
             self.encoder_features, self.encoder_padding_mask = self.encoder_forward(input_features)
             return searcher.apply(out_size, return_probs, **kwargs)
+
+    def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False):
+        """``n_samples`` captions per image drawn from the model's own distribution, on the HIP engine (``ovc_sample``; the rule
+        is stated in ``include/ovc.h`` and mirrored by ``openviic_amd.sampling``): ``(ids [B, S, T] int64, log_probs [B, S, T])``
+        in sample order, plus ``all_log_probs [B, S, T, V]`` with ``return_probs=True``.  After a caption's first ``<eos>`` every
+        id is 0 and every log-probability exactly 0, as a beam's.  ``1 <= n_samples <= 8`` per call, 'f32', vocabularies of at most
+        16 384 words, every model the search runs; anything else is refused before any launch and any draw.
+
+        One seed per call, drawn on the stream from ``generator`` (default: the device's CUDA generator) as ``xe_loss`` draws
+        its dropout seed, so ``torch.manual_seed`` reproduces a call bit for bit -- on every stream, GEMM tiling and graph replay.
+        Sample ``s`` of image ``b`` depends on ``b``'s position in the batch (the draw's counter holds it).
+
+        In ``train()`` mode with gradients enabled ``log_probs`` carries a gradient as ``beam_search``'s does (``_BeamLogProbs``,
+        ``ovc_sequence_backward``: the same scope, the refusals raised from ``backward()``).  Dropout counts as the identity: a
+        live dropout raises from ``backward()`` with the beam search's message.  No temperature, top-k or nucleus form."""
+        eng = self._fused_engine()
+        eng.check_sample(n_samples)
+        boxes = input_features["region_boxes"] if self.uses_boxes else None
+        feats = input_features[self.feature_field]
+        out = eng.sample(feats, boxes, batch_size, n_samples, _dropout.draw_seed(eng.device, generator), return_probs=return_probs)
+        params = [p for p in self.parameters() if p.requires_grad]
+        if self.training and torch.is_grad_enabled() and params:
+            out = (out[0], self._scst_log_probs(feats, boxes, out[0], out[1], params)) + tuple(out[2:])
+        return out
 
     def _scst_log_probs(self, features, boxes, ids, log_probs, params):
         """The search's ``log_probs`` as a function of ``params`` (``_BeamLogProbs``): what the reference's ``train_scst`` backpropagates

@@ -12,6 +12,7 @@
 // log-sum-exp, the candidate scores and a k-way partial selection are fused in one pass per beam row,
 // and the image's winners are the k best of its rows' k best.
 #include "common.h"
+#include "dropout.h"      // ovc_philox_block: the sampler's draw
 
 namespace {
 
@@ -233,6 +234,31 @@ __global__ __launch_bounds__(256) void masked_logp_kernel(const float* __restric
     for (int c = threadIdx.x; c < V; c += 256) y[c] = ((x[(size_t)c * ld_word] - m) - l) * a;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampling from the same block pieces (ovc_sample, include/ovc.h: the rule).  One workgroup per image, wave s = sample s of the
+// image: it reads the pieces of its parent row (row 0 of the image at step 0, row s later), forms M and ls as phase A above does,
+// draws u from Philox and walks the inverse CDF in ascending word order in two levels -- the block whose inclusive prefix of
+// masses S_j exp(M_j - M) first exceeds u * Z, then the word inside it from the block's 32 stored logits -- and ends with stage
+// D's writes and beam_follow_winners.  Every prefix is a wave scan in a fixed order: the same bits on every call, stream,
+// replay and GEMM tiling.  No workgroup-level reduction, no atomics.
+constexpr uint32_t kSampleCounterWord = 0x53414D50u;     // "SAMP": Philox counter word 2, outside the dropout site range
+
+// inclusive prefix sum over the 64 lanes of a wave (Hillis-Steele, six fixed steps)
+__device__ __forceinline__ float wave_prefix_sum(float v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float o = __shfl_up(v, off, 64);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kFusedThreads) void sample_fused_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                            int stats_ld, long ld_row, long ld_word,
+                                                                            const int64_t* __restrict__ seed) {
+#include "bodies/sample_fused_update.inc"
+}
+
 // Final ordering (beam_search.py:97-113): beams sorted by total score, descending, stable.
 __global__ __launch_bounds__(64) void beam_finalize_kernel(BeamFinalArgs p) {
 #include "bodies/beam_finalize.inc"
@@ -327,6 +353,17 @@ int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, in
                            ld_word, gate);
     else
         hipLaunchKernelGGL(beam_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, running_in, ld_row, ld_word);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+// p.width: 1 (step 0: every sample of an image draws from the image's one row) or p.k (sample s continues row s).
+int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
+                                   const int64_t* seed, int B, hipStream_t stream) {
+    if (B <= 0 || p.k <= 0 || p.k > kMaxK || (p.width != 1 && p.width != p.k) || p.V <= 0 || !stats || !seed) return OVC_EINVAL;
+    if (nblk != (p.V + 31) / 32 || nblk > 512 || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
+    if (ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
+    hipLaunchKernelGGL(sample_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, ld_row, ld_word, seed);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -1,0 +1,98 @@
+// The body of sample_fused_update_kernel (beam.hip).  Not a header: no include guard.
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
+    __shared__ int parent[kMaxK], word[kMaxK];
+
+    if (wave < k) {
+        // ---- A: the parent row's log-softmax pieces, as beam_fused_update forms them (same loads, same order of operations) ---
+        const int par = W == 1 ? 0 : wave;             // step 0: the image's one row; later: the sample's own
+        const int row = b * W + par;
+        const float* srow = stats + 2 * (size_t)row * stats_ld;
+        f32x4 st[kFusedPairs];
+#pragma unroll
+        for (int j = 0; j < kFusedPairs; ++j)      // unconditional loads from clamped addresses, masked below
+            st[j] = *reinterpret_cast<const f32x4*>(srow + 2 * min(2 * (lane + 64 * j), stats_ld - 2));
+        const float alive = p.alive_in[row];
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < kFusedPairs; ++j) {
+            const int blk0 = 2 * (lane + 64 * j);
+            if (blk0 >= nblk) { st[j][0] = -INFINITY; st[j][1] = 0.f; }
+            if (blk0 + 1 >= nblk) { st[j][2] = -INFINITY; st[j][3] = 0.f; }
+            m = fmaxf(m, fmaxf(st[j][0], st[j][2]));
+        }
+        const float M = wave_max_dpp(m);
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < kFusedPairs; ++j)      // a block past nblk holds (-inf, 0): 0 * exp(-inf) = 0
+            sum += st[j][1] * __expf(st[j][0] - M) + st[j][3] * __expf(st[j][2] - M);
+        const float Z = wave_sum_dpp(sum);
+        const float ls = logf(Z);
+
+        // ---- the draw: one Philox block per (row, step), word 0 (include/ovc.h, ovc_sample) --------------------------------------
+        uint32_t c0 = (uint32_t)(b * k + wave), c1 = (uint32_t)t, c2 = kSampleCounterWord, c3 = 0u;
+        ovc_philox_block((uint64_t)*seed, c0, c1, c2, c3);
+        const float u = ((float)(c0 >> 8) + 0.5f) * 0x1p-24f;
+        const float target = u * Z;
+
+        // ---- level 1: the first block whose inclusive prefix of masses exceeds target.  Ascending block order is (j, lane,
+        //      element); the prefix of a lane's pair starts from carry + the exclusive lane scan of the pair sums -------------
+        int blk = nblk - 1;                            // rounding left no block: the last one ...
+        float start = 0.f, last_start = 0.f;           // ... which starts at the prefix of the blocks before it
+        bool found = false;
+        float carry = 0.f;
+#pragma unroll
+        for (int j = 0; j < kFusedPairs; ++j) {
+            if (128 * j < nblk) {                      // uniform: the pairs of round j exist
+                const int blk0 = 2 * (lane + 64 * j);
+                const float m0 = st[j][1] * __expf(st[j][0] - M), m1 = st[j][3] * __expf(st[j][2] - M);
+                const float incl = wave_prefix_sum(m0 + m1, lane);
+                const float before = __shfl_up(incl, 1, 64);
+                const float e = carry + (lane == 0 ? 0.f : before);
+                const float p0 = e + m0, p1 = p0 + m1;
+                if (blk0 == nblk - 1) last_start = e;
+                if (blk0 + 1 == nblk - 1) last_start = p0;
+                const bool hit0 = blk0 < nblk && p0 > target, hit1 = blk0 + 1 < nblk && p1 > target;
+                const unsigned long long hits = __ballot(hit0 || hit1);
+                if (!found && hits != 0ull) {
+                    const int first = __ffsll((long long)hits) - 1;
+                    const int h0 = __shfl(hit0 ? 1 : 0, first, 64);
+                    const float fe = __shfl(e, first, 64), fp0 = __shfl(p0, first, 64);
+                    blk = 2 * (first + 64 * j) + (h0 ? 0 : 1);
+                    start = h0 ? fe : fp0;
+                    found = true;
+                }
+                carry = __shfl(p1, 63, 64);
+            }
+        }
+        if (!found) start = __shfl(last_start, ((nblk - 1) >> 1) & 63, 64);
+
+        // ---- level 2: inside the block, the first word whose prefix of exp(x - M), started from `start`, exceeds target ---------
+        const int col = min(blk * 32 + (lane & 31), V - 1);
+        const float x = p.logits[(size_t)row * ld_row + (size_t)col * ld_word];
+        const bool real = lane < 32 && blk * 32 + lane < V;
+        const float pw = start + wave_prefix_sum(real ? __expf(x - M) : 0.f, lane);
+        const unsigned long long whits = __ballot(real && pw > target);
+        const int last_word = min(blk * 32 + 31, V - 1) - blk * 32;       // rounding left no word: the block's last below V
+        const int pick = whits != 0ull ? __ffsll((long long)whits) - 1 : last_word;
+        // a row that has emitted <eos> is frozen: word 0, whatever was drawn (its log-probability is multiplied by alive = 0)
+        const bool live = alive != 0.0f;
+        const float x0 = p.logits[(size_t)row * ld_row];
+        const int wd = live ? blk * 32 + pick : 0;
+        const float xw = live ? __shfl(x, pick, 64) : x0;
+
+        // ---- D: the bookkeeping of beam_fused_update, winner = (parent row, drawn word) -----------------------------------------
+        if (lane == 0) {
+            if (wave < W && p.row_max_out) { p.row_max_out[row] = M; p.row_lsum_out[row] = ls; }
+            parent[wave] = par; word[wave] = wd;
+            const float lp = ((xw - M) - ls) * alive;
+            p.running_out[b * k + wave] = 0.f;         // no score: the final kernel then keeps the sample order
+            p.alive_out[b * k + wave] = alive * (wd != p.eos ? 1.0f : 0.0f);
+            p.hist_out[((size_t)b * k + wave) * T + t] = wd;
+            p.lp_out[((size_t)b * k + wave) * T + t] = lp;
+            p.next_tok[b * k + wave] = wd;
+            p.anc_out[((size_t)b * k + wave) * T + t] = b * W + par;
+        }
+    }
+    __syncthreads();
+    beam_follow_winners<kFusedThreads>(p, b, tid, parent, word);

@@ -271,6 +271,10 @@ int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, c
 // transposed one.
 int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
                                  long ld_row, long ld_word, int B, hipStream_t stream, const int32_t* gate = nullptr);
+// Sampling in place of the selection (ovc_sample): sample s of image b draws its word from the pieces of its parent row and the
+// bookkeeping is the fused update's.  seed: the device word the draw's Philox key is read from; p.alive_count must be nullptr.
+int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
+                                   const int64_t* seed, int B, hipStream_t stream);
 int ovc_debug_collect_winners_launch(const int32_t* anc, const int32_t* word, const float* running, int B, int width, int V, int k,
                                      int64_t* chosen, float* score, hipStream_t stream);
 int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const float* row_max, const float* row_lsum,

@@ -871,9 +871,9 @@ enum class SearchForm {
     Gated,       // ovc_beam_search_gated: one graph whose launches of step t >= 1 are gated on alive_count[t - 1]
 };
 
-// One beam search, described once.  The five exported searches fill one of these, and the scope (search_ok), the workspace layout
-// and size (carve_search), what a step does (run_decode_step), the launches of the search (issue_search_body), the graph key
-// (search_graph_key) and everything around them (run_search) are functions of it.
+// One beam search, described once.  The five exported searches and the two sampling calls fill one of these, and the scope
+// (search_ok), the workspace layout and size (carve_search), what a step does (run_decode_step), the launches of the search
+// (issue_search_body), the graph key (search_graph_key) and everything around them (run_search) are functions of it.
 struct SearchCall {
     // the members every call states, first: SearchCall{B, N, k, out_size, form, ids_out, logp_out}; the rest is zero unless a form
     // fills it in
@@ -887,6 +887,9 @@ struct SearchCall {
     // the caller's seed, the hash of the plan's constants and the caller's slot table [B][out_size][T].  A sizer binds an empty
     // plan (and any non-null all_logp_out): their presence alone adds the buffers.
     DropPlan* plan; const int64_t* seed; uint64_t drop_hash; int32_t* slots_out;
+    // Sampling (ovc_sample, ovc_sample_graph): the selection of every step is a draw from the row's distribution (k = out_size =
+    // the samples per image) and the caller's seed, copied to the workspace's seed slot outside any captured body.
+    bool sample; const int64_t* sample_seed;
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
 
@@ -900,12 +903,16 @@ bool search_model_ok(const ovc_model* m, const SearchCall& c) {
 // The scope of a search, for the sizers (out_size = k) and the entry points alike.
 bool search_ok(const ovc_model* m, const SearchCall& c) {
     if (!search_model_ok(m, c) || c.B <= 0 || c.N <= 0 || c.N > OVC_MAX_REGIONS || c.k <= 0 || c.k > OVC_MAX_BEAM) return false;
+    // sampling: fp32, the fused vocabulary tail's block pieces, no dropout plan, plain launches or the whole-search graph
+    if (c.sample && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.plan ||
+                     (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
+        return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
 }
 
-// With a plan: the seed / step-count slots behind the plain layout.
+// With a plan, or sampling: the seed / step-count slots behind the plain layout.
 Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
-    return carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr);
+    return carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr || c.sample);
 }
 
 // One pass over the decoder's layers, described once: a decode step of a search (run_decode_step) or the teacher-forced decoder
@@ -1076,7 +1083,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     // and OVC_SELECT_TWO_PASS (A/B switch) take the round-2 pair of kernels that read every logit back.
     const int nblk = (m->vocab + 31) / 32;
     static const bool two_pass = OVC_HOOK_ENV("OVC_SELECT_TWO_PASS") != nullptr;
-    const bool fused_select = !two_pass && nblk <= kFusedVocabBlocks;
+    const bool fused_select = c.sample || (!two_pass && nblk <= kFusedVocabBlocks);      // sampling: search_ok has checked nblk
     // fp32 mode + fused selection: the product runs TRANSPOSED -- logits^T [V][rows] = fc [V, d] . x^T, the same kernel with the
     // operands' roles swapped (both are K-contiguous) and the same bits (every dot product sums the same k order; a * b
     // commutes).  A lane of the accumulator then holds 16 WORDS of one beam row, which makes the block maximum / sum exp an
@@ -1122,7 +1129,9 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     if (fused_select) {
         // selection + bookkeeping in one launch, from the block pieces the vocabulary GEMM's epilogue left: no pass over the logits
         bu.row_max_out = return_probs ? w.row_max : nullptr; bu.row_lsum_out = return_probs ? w.row_lsum : nullptr;
-        if (!(debug_skip() & 8))
+        if (c.sample)         // the one branch of a sampling step: a draw from the row's distribution in place of the k best
+            RUN(ovc_sample_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.drop_seed, B, s));
+        else if (!(debug_skip() & 8))
             RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s, e.gate));
         if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
             RUN(ovc_masked_logp_launch(w.logits, ld_row, ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab,
@@ -1333,6 +1342,7 @@ enum class GraphKind {
     Train,              // ovc_forward_backward, with or without dropout (k = T, out_size = 1)
     SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
     TrainSmoothed,      // ovc_forward_backward_smoothed, with or without dropout (k = T, out_size = 1)
+    SampleSearch,       // ovc_sample_graph (k = out_size = S, the samples per image; the seed is read from its workspace slot)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1486,7 +1496,7 @@ int write_search_slots(Engine& e, Workspace& w, const SearchCall& c, int steps_h
 // whole-search graph and the per-step graphs share Search and live in different maps (g_graphs, g_early).  The dropout plan's
 // constants are hashed in -- 0 without a plan, so a search with dropout never shares an entry with the plain one.
 GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* workspace) {
-    const GraphKind kind = c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
+    const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
 }  // namespace
@@ -1583,9 +1593,9 @@ namespace {
 // body does not hold it; the copies to the caller's buffers and the slot table.
 int run_search(const ovc_model* m, const SearchCall& c, const float* features, const float* boxes, void* workspace,
                size_t workspace_bytes, ovc_stream stream) {
-    if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out) return OVC_EINVAL;
+    if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out || (c.sample && !c.sample_seed)) return OVC_EINVAL;
     TRY(ovc_device_guard());
-    if (!search_ok(m, c) || (long)m->vocab < c.k) return OVC_EINVAL;
+    if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
     Workspace w = carve_search(m, workspace, c);
     if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
@@ -1596,6 +1606,8 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
         c.plan->seed = w.drop_seed;
         e.drop = c.plan;
     }
+    if (c.sample && hipMemcpyAsync(w.drop_seed, c.sample_seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+        return OVC_ELAUNCH;                        // the same slot, refreshed the same way: a replayed graph reads this call's seed
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
 
     auto body = [&](Engine& ce) { return issue_search_body(ce, w, c); };
@@ -1664,6 +1676,34 @@ extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, 
                                      float* logp_out, int32_t* steps_out, ovc_stream stream) {
     SearchCall c{B, N, k, out_size, SearchForm::Gated, ids_out, logp_out};
     c.steps_out = steps_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sampling (include/ovc.h: the rule).  A search whose selection is a draw: S rows per image after step 0, row (b, s) its own
+// ancestor, every total score 0 -- so the final kernel, whose order is stable, returns the samples in sample order.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ovc_sample_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs) {
+    SearchCall c{B, N, S, S};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    c.sample = true;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+extern "C" int ovc_sample(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                          void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, float* all_logp_out,
+                          ovc_stream stream) {
+    SearchCall c{B, N, S, S, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    c.sample = true; c.sample_seed = seed;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_sample_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                                void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream) {
+    SearchCall c{B, N, S, S, SearchForm::Graph, ids_out, logp_out};
+    c.sample = true; c.sample_seed = seed;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 

@@ -669,6 +669,48 @@ class CaptionEngine:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
 
+    def check_sample(self, n_samples):
+        """The refusals of ``sample`` that need no input: callers that draw the seed themselves run them before the draw."""
+        S = int(n_samples)
+        if not 1 <= S <= native.OVC_MAX_BEAM:
+            raise native.OvcError("sample: 1 <= n_samples <= {} expected, got {} (call again with another seed for more)".format(
+                native.OVC_MAX_BEAM, n_samples))
+        if self.precision != "f32":
+            raise native.OvcError("sample runs in 'f32' only (precision={!r})".format(self.precision))
+        if self.desc.vocab > 16384:
+            raise native.OvcError("sample covers vocabularies of at most 16384 words (got {})".format(self.desc.vocab))
+        return S
+
+    def sample(self, features, boxes, batch_size, n_samples, seed, return_probs=False):
+        """``n_samples`` captions per image drawn from the model's distribution (``ovc_sample`` / ``ovc_sample_graph``;
+        ``include/ovc.h`` states the rule, ``openviic_amd.sampling`` mirrors it).  ``seed``: a one-element int64 device tensor,
+        read on the device.  Returns ``(ids, logp)`` ``(B, n_samples, T)`` in sample order, plus every step's log-probabilities
+        ``(B, n_samples, T, V)`` with ``return_probs``.  The workspace cache and the ``OVC_GRAPH`` switch are the beam
+        search's: one captured graph from the second call of a shape, plain launches with ``return_probs`` or ``OVC_GRAPH=0``.
+        Refused before any launch: ``n_samples`` outside ``1..OVC_MAX_BEAM``, a precision other than 'f32', a vocabulary of
+        more than 16 384 words, a seed that is not a one-element int64 device tensor."""
+        S = self.check_sample(n_samples)
+        if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != self.device:
+            raise native.OvcError("sample: the seed must be a one-element int64 tensor on {}".format(self.device))
+        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, S)
+        d = self.desc
+        T = d.max_len
+        need = self.lib.ovc_sample_workspace_bytes(ctypes.byref(d), B, N, S, 1 if return_probs else 0)
+        if need == 0:
+            raise native.OvcError("unsupported configuration for sampling (B={}, N={}, n_samples={}; see "
+                                  "ovc_sample_workspace_bytes)".format(B, N, S))
+        ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
+        ids = torch.empty(B, S, T, dtype=torch.int64, device=self.device)
+        logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device)
+        head = (ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N, S, seed.data_ptr(),
+                ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr())
+        if return_probs or not self.use_graph:
+            everything = torch.empty(B, S, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
+            check(self.lib.ovc_sample(*head, None if everything is None else everything.data_ptr(), native.stream_handle()), "ovc_sample")
+            return (ids, logp, everything) if return_probs else (ids, logp)
+        check(self.lib.ovc_sample_graph(*head, native.stream_handle()), "ovc_sample_graph")
+        return ids, logp
+
     # -- training ---------------------------------------------------------------------------------------------------
     def _check_trainable(self):
         """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'

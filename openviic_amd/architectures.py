@@ -87,10 +87,10 @@ class _BeamLogProbs(torch.autograd.Function):
     search and ``backward()`` (an optimizer step) raises torch's in-place error instead of differentiating other weights."""
 
     @staticmethod
-    def forward(ctx, engine_, refusal, drop, features, boxes, ids, log_probs, *params):
-        # refusal: None or the text backward() raises.  drop: None or the search's dropout (probs, seed, slots, beam size) -- the
-        # recompute then runs under the masks the search used
-        ctx.engine, ctx.refusal, ctx.drop = engine_, refusal, drop
+    def forward(ctx, engine_, refusal, recompute, features, boxes, ids, log_probs, *params):
+        # refusal: None or the text backward() raises.  recompute: the keyword arguments ``_generate`` returned with ids and
+        # log_probs (B, S, T) -- after a masked search the recompute runs under the masks the search used
+        ctx.engine, ctx.refusal, ctx.recompute = engine_, refusal, recompute
         ctx.features, ctx.boxes, ctx.ids = features, boxes, ids
         ctx.save_for_backward(*params)
         return log_probs.clone()
@@ -100,13 +100,7 @@ class _BeamLogProbs(torch.autograd.Function):
         params = ctx.saved_tensors           # raises if a parameter was modified in place since the search
         if ctx.refusal is not None:
             raise engine.native.OvcError(ctx.refusal)
-        ids = ctx.ids if ctx.ids.dim() == 3 else ctx.ids[:, None]
-        g = grad_output.reshape(ids.shape)
-        if ctx.drop is not None:
-            probs, seed, slots, beam = ctx.drop
-            _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g, dropout=(probs, seed), slots=slots, beam_size=beam)
-        else:
-            _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ids, g)
+        _, grads = ctx.engine.sequence_backward(ctx.features, ctx.boxes, ctx.ids, grad_output.reshape(ctx.ids.shape), **ctx.recompute)
         by_param = {id(p): gr for p, gr in zip(ctx.engine.gradient_parameters(), grads)}
         out = tuple(by_param.get(id(p)) if p.requires_grad else None for p in params)
         return (None, None, None, None, None, None, None) + out
@@ -159,8 +153,7 @@ class BaseTransformer(Module):
         """Teacher-forced log-probabilities (B, T, V).  ``fused=False`` (default): operator by operator, as the reference
         runs it; ``fused=True``: one call into the HIP engine (``CaptionEngine.forward``, ``ovc_forward``)."""
         if fused:
-            boxes = input_features["region_boxes"] if self.uses_boxes else None
-            return self._fused_engine().forward(input_features[self.feature_field], boxes, input_features["caption_tokens"])
+            return self._fused_engine().forward(*self._engine_inputs(input_features), input_features["caption_tokens"])
         encoder_features, encoder_padding_mask = self.encoder_forward(input_features)
         return self.decoder(caption_tokens=input_features["caption_tokens"],
                             encoder_features=encoder_features,
@@ -181,13 +174,21 @@ class BaseTransformer(Module):
             self._engine = engine.CaptionEngine(self)
         return self._engine
 
+    def _engine_inputs(self, items):
+        """``(features, boxes)`` of a batch as the engine's calls take them; ``boxes`` is None for a model that uses none."""
+        return items[self.feature_field], items["region_boxes"] if self.uses_boxes else None
+
+    def _live_dropouts(self):
+        """The names of the ``nn.Dropout`` modules a call in the model's present mode applies: those with ``p > 0`` in
+        ``train()`` mode, none in ``eval()`` mode."""
+        return [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0] if self.training else []
+
     def score(self, input_features):
         """(B, T) log-probability of each word of ``shifted_right_caption_tokens`` given ``caption_tokens`` up to it, 0 where
         the target is ``<pad>`` -- on the HIP engine, without a (B, T, V) tensor.  The reference's dev loss
         (``vi_trainer.py:56-76``: NLLLoss(ignore_index=pad) over ``model(items)``) is
         ``-score.sum() / (targets != pad).sum()``."""
-        boxes = input_features["region_boxes"] if self.uses_boxes else None
-        return self._fused_engine().score(input_features[self.feature_field], boxes, input_features["caption_tokens"],
+        return self._fused_engine().score(*self._engine_inputs(input_features), input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
 
     def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None):
@@ -213,21 +214,28 @@ class BaseTransformer(Module):
         ``label_smoothing=0.0, reduction="tokens"`` is bit for bit.  Refused before any launch and any draw: an ``s`` that is
         not a Python number in ``0 <= s < 1``, ``s > 0`` with a vocabulary of 2 words or fewer, an unknown ``reduction``, and a
         ``reduction`` without ``label_smoothing``.  ``label_smoothing=None`` is the plain call, launch for launch."""
-        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, "xe_loss", len(self.vocab))
-        probs = self._xe_dropout_probs(dropout, "xe_loss")
+        eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction)
+        return _XeLoss.apply(eng, drop, smoothed, *inputs, *eng.gradient_parameters())
+
+    def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None):
+        """The preamble of ``xe_loss`` / ``xe_step``: their refusals in their order -- the loss, the dropout rules, a model outside
+        the backward's scope, ``xe_step``'s optimizer set -- and only then the draw of the step's seed.  Returns ``(engine,
+        dropout (probs, seed) or None, smoothed loss or None, (features, boxes, caption tokens, targets))``."""
+        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
+        probs = self._xe_dropout_probs(dropout, what)
         eng = self._fused_engine()
-        if probs:
-            eng._check_trainable()                  # a model outside the scope is refused before the seed is drawn
-        boxes = input_features["region_boxes"] if self.uses_boxes else None
-        params = eng.gradient_parameters()
+        eng._check_trainable()
+        if optimizer is not None:
+            _checked_step_optimizer(optimizer, what, eng)
+        inputs = (*self._engine_inputs(input_features), input_features["caption_tokens"],
+                  input_features["shifted_right_caption_tokens"])
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        return _XeLoss.apply(eng, drop, smoothed, input_features[self.feature_field], boxes, input_features["caption_tokens"],
-                             input_features["shifted_right_caption_tokens"], *params)
+        return eng, drop, smoothed, inputs
 
     def _xe_dropout_probs(self, dropout, what):
         """``{site: p}`` of the live dropouts for ``xe_loss`` / ``xe_step`` (empty: the plain call), or the refusals of their
         dropout rules: before any launch and any draw."""
-        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0] if self.training else []
+        live = self._live_dropouts()
         if dropout:
             if live and isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
                 raise engine.native.OvcError(
@@ -271,17 +279,9 @@ class BaseTransformer(Module):
         from . import optim as _optim
         _checked_step_optimizer(optimizer, "xe_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
-        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, "xe_step", len(self.vocab))
-        probs = self._xe_dropout_probs(dropout, "xe_step")
-        eng = self._fused_engine()
-        eng._check_trainable()
-        _checked_step_optimizer(optimizer, "xe_step", eng)
-        boxes = input_features["region_boxes"] if self.uses_boxes else None
-        drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        slots = eng.step_arena()
-        loss, _, grads = eng.forward_backward(input_features[self.feature_field], boxes, input_features["caption_tokens"],
-                                              input_features["shifted_right_caption_tokens"], dropout=drop, arena=slots,
-                                              loss=smoothed)
+        eng, drop, smoothed, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
+                                                    optimizer)
+        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), loss=smoothed)
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
@@ -348,8 +348,7 @@ class BaseTransformer(Module):
         if sample:
             eng.check_sample(k)
         _checked_step_optimizer(optimizer, "scst_step", eng)
-        boxes = input_features["region_boxes"] if self.uses_boxes else None
-        feats, boxes = eng._checked_inputs(input_features[self.feature_field], boxes)
+        feats, boxes = eng._checked_inputs(*self._engine_inputs(input_features))
         B = feats.shape[0]
         if corpus is not None:
             if corpus.device != eng.device or corpus._struct is None:
@@ -362,15 +361,8 @@ class BaseTransformer(Module):
                 raise engine.native.OvcError("scst_step: rows must be a contiguous int32 [{}] tensor on {}, got {}".format(
                     B, eng.device, "{} {} on {}".format(rows.dtype, tuple(rows.shape), rows.device)
                     if isinstance(rows, torch.Tensor) else type(rows).__name__))
-        drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        if sample:
-            outs, log_probs = eng.sample(feats, boxes, B, k, _dropout.draw_seed(eng.device, generator))
-            slots = None
-        elif drop is not None:
-            outs, log_probs, slots = eng.beam_search(feats, None, B, k, out_size=k, early_exit=early_exit, dropout=drop)
-        else:
-            outs, log_probs = eng.beam_search(feats, boxes, B, k, out_size=k, early_exit=early_exit)
-            outs, log_probs, slots = outs.reshape(B, k, -1), log_probs.reshape(B, k, -1), None
+        outs, log_probs, _, recompute = self._generate(input_features, B, k, None if sample else k, probs, generator,
+                                                       early_exit=early_exit)
         if corpus is not None:
             r = corpus.reward(outs, rows)
         else:
@@ -382,18 +374,13 @@ class BaseTransformer(Module):
                                                      if isinstance(r, torch.Tensor) else type(r).__name__))
             r = r.detach().contiguous()
         g, stats = _scst.advantage(r, log_probs)
-        if drop is not None:
-            _, grads = eng.sequence_backward(feats, None, outs, g, dropout=drop, slots=slots, beam_size=k, arena=eng.step_arena())
-        else:
-            _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena())
+        _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena(), **recompute)
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
 
     def _search_dropout_probs(self):
         """``{site: p}`` for ``beam_search(dropout=True)``, or the refusals of its scope: before any launch and any draw."""
-        if not self.training:
-            return {}
-        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+        live = self._live_dropouts()
         if not live:
             return {}
         if isinstance(self.encoder, CrossAttentionMultiLevelEncoder):
@@ -437,31 +424,16 @@ class BaseTransformer(Module):
         """
         if dropout and not fused:
             raise engine.native.OvcError("beam_search(dropout=True) needs fused=True: the host loop has no dropout site table")
-        if fused and dropout:
-            probs = self._search_dropout_probs()
-            if probs:
-                if return_probs:
-                    raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
-                eng = self._fused_engine()
-                feats = input_features[self.feature_field]
-                seed = _dropout.draw_seed(eng.device, generator)
-                ids, logp, slots = eng.beam_search(feats, None, batch_size, beam_size, out_size=out_size,
-                                                   early_exit=kwargs.get("early_exit"), dropout=(probs, seed))
-                params = [p for p in self.parameters() if p.requires_grad]
-                if torch.is_grad_enabled() and params:
-                    logp = _BeamLogProbs.apply(eng, None, (probs, seed, slots, beam_size), feats.detach(), None, ids, logp, *params)
-                if out_size == 1:
-                    ids, logp = ids.squeeze(1), logp.squeeze(1)
-                return ids, logp
         if fused:
-            boxes = input_features["region_boxes"] if self.uses_boxes else None
-            feats = input_features[self.feature_field]
-            out = self._fused_engine().beam_search(feats, boxes, batch_size, beam_size, out_size=out_size,
-                                                   return_probs=return_probs, early_exit=kwargs.get("early_exit"))
-            params = [p for p in self.parameters() if p.requires_grad]
-            if self.training and torch.is_grad_enabled() and params:
-                out = (out[0], self._scst_log_probs(feats, boxes, out[0], out[1], params)) + tuple(out[2:])
-            return out
+            probs = self._search_dropout_probs() if dropout else None
+            if probs and return_probs:
+                raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
+            ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
+                                                              return_probs, kwargs.get("early_exit"))
+            logp = self._scst_log_probs(input_features, ids, logp, recompute)
+            if out_size == 1:
+                ids, logp = ids.squeeze(1), logp.squeeze(1)
+            return (ids, logp, everything) if return_probs else (ids, logp)
         searcher = BeamSearch(model=self, max_len=self.max_len, eos_idx=self.eos_idx, beam_size=beam_size,
                               b_s=batch_size, device=self.device)
         with self.statefulness(batch_size):
@@ -482,25 +454,47 @@ class BaseTransformer(Module):
         In ``train()`` mode with gradients enabled ``log_probs`` carries a gradient as ``beam_search``'s does (``_BeamLogProbs``,
         ``ovc_sequence_backward``: the same scope, the refusals raised from ``backward()``).  Dropout counts as the identity: a
         live dropout raises from ``backward()`` with the beam search's message.  No temperature, top-k or nucleus form."""
-        eng = self._fused_engine()
-        eng.check_sample(n_samples)
-        boxes = input_features["region_boxes"] if self.uses_boxes else None
-        feats = input_features[self.feature_field]
-        out = eng.sample(feats, boxes, batch_size, n_samples, _dropout.draw_seed(eng.device, generator), return_probs=return_probs)
-        params = [p for p in self.parameters() if p.requires_grad]
-        if self.training and torch.is_grad_enabled() and params:
-            out = (out[0], self._scst_log_probs(feats, boxes, out[0], out[1], params)) + tuple(out[2:])
-        return out
+        self._fused_engine().check_sample(n_samples)
+        ids, logp, everything, recompute = self._generate(input_features, batch_size, n_samples, generator=generator,
+                                                          return_probs=return_probs)
+        logp = self._scst_log_probs(input_features, ids, logp, recompute)
+        return (ids, logp, everything) if return_probs else (ids, logp)
 
-    def _scst_log_probs(self, features, boxes, ids, log_probs, params):
-        """The search's ``log_probs`` as a function of ``params`` (``_BeamLogProbs``): what the reference's ``train_scst`` backpropagates
-        through.  Anything the backward does not cover raises from ``backward()``, not here: the search itself runs for every model."""
-        refusal = None
-        live = [n for n, m in self.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
-        if live:
-            refusal = ("beam_search: the model is in train() mode with dropout > 0 ({}); the engine's search and its backward take "
-                       "dropout as the identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
-        return _BeamLogProbs.apply(self._fused_engine(), refusal, None, features.detach(), None if boxes is None else boxes.detach(),
+    def _generate(self, input_features, batch_size, width, out_size=None, probs=None, generator=None, return_probs=False,
+                  early_exit=None):
+        """One fused generation, for ``beam_search``, ``sample`` and ``scst_step``: ``width`` beams of which the best ``out_size``
+        are returned -- with ``probs`` (what ``_search_dropout_probs`` returned, not empty) under this call's dropout masks -- or,
+        with ``out_size=None``, ``width`` samples.  The masks' or the samples' seed is drawn here, one per call; plain beams draw
+        nothing.  Returns ``(ids, log_probs, all_log_probs, recompute)``: the first two unsqueezed ``(B, out_size, T)``, the third
+        None without ``return_probs``, the last the keyword arguments under which ``sequence_backward`` recomputes these
+        log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``)."""
+        eng = self._fused_engine()
+        feats, boxes = self._engine_inputs(input_features)
+        recompute = {}
+        if out_size is None:
+            out = eng.sample(feats, boxes, batch_size, width, _dropout.draw_seed(eng.device, generator), return_probs=return_probs)
+        elif probs:
+            drop = (probs, _dropout.draw_seed(eng.device, generator))
+            *out, slots = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, early_exit=early_exit, dropout=drop)
+            recompute = dict(dropout=drop, slots=slots, beam_size=width)
+        else:
+            out = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, return_probs=return_probs, early_exit=early_exit)
+        ids, logp = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in out[:2])       # out_size = 1: the engine squeezed them
+        return ids, logp, out[2] if return_probs else None, recompute
+
+    def _scst_log_probs(self, input_features, ids, log_probs, recompute):
+        """The generation's ``log_probs`` as a function of the parameters (``_BeamLogProbs``) in ``train()`` mode with gradients
+        enabled, as they are otherwise: what the reference's ``train_scst`` backpropagates through.  Anything the backward does not
+        cover raises from ``backward()``, not here: the search itself runs for every model."""
+        params = [p for p in self.parameters() if p.requires_grad]
+        if not (self.training and torch.is_grad_enabled() and params):
+            return log_probs
+        live = [] if recompute else self._live_dropouts()          # a live dropout counts where the search ran without its masks
+        refusal = None if not live else (
+            "beam_search: the model is in train() mode with dropout > 0 ({}); the engine's search and its backward take "
+            "dropout as the identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))
+        feats, boxes = self._engine_inputs(input_features)
+        return _BeamLogProbs.apply(self._fused_engine(), refusal, recompute, feats.detach(), None if boxes is None else boxes.detach(),
                                    ids, log_probs, *params)
 
 

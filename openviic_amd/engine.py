@@ -261,14 +261,12 @@ class CaptionEngine:
         self._planes = _WeightPlanes(self.lib) if self.precision != "f32" and self.precut_weights else None
         self.desc = self._describe(model)
         self._param_ptrs = tuple(p.data_ptr() for p in model.parameters())
-        self._workspaces = {}    # one scratch buffer per HIP stream: concurrent batches never share state
-        # the teacher-forced forward's and the scoring's own, per (stream, logp wanted): a dev-loss pass between two searches
-        # leaves the search's buffer -- whose address keys its captured graphs -- where it is
-        self._fw_workspaces = {}
-        self._train_workspaces = {}   # ovc_forward_backward's own, per stream
-        self._seq_workspaces = {}     # ovc_sequence_backward's own, per (stream, sequences per image)
-        self._step_arenas = {}        # xe_step's gradient arena, per stream
-        self._steps_device = {}  # early_exit="device": the step count of each search workspace (keyed like _workspaces)
+        # (kind, HIP stream, extra) -> what the engine keeps per stream: concurrent batches never share state.  The scratch
+        # buffers: "search" (every generation and the encoder; its address keys the captured graphs), "forward" (the
+        # teacher-forced forward's and the scoring's own, extra = logp wanted: a dev-loss pass between two searches leaves the
+        # search's buffer where it is), "train" (ovc_forward_backward's own) and "sequence" (ovc_sequence_backward's own, extra =
+        # sequences per image).  Besides them "arena" (xe_step's gradient arena) and "steps" (early_exit="device": the step count).
+        self._buffers = {}
         self.last_steps_device = None
         self._tuned = set()
         self.device = next(model.parameters()).device
@@ -451,35 +449,40 @@ class CaptionEngine:
                 json.dump(cache, f, indent=0, sort_keys=True)
 
     # -- workspace ----------------------------------------------------------------------------
-    def _get_workspace(self, B, N, k, return_probs):
-        need = self.lib.ovc_workspace_bytes(ctypes.byref(self.desc), B, N, k, 1 if return_probs else 0)
-        if need == 0:
-            raise native.OvcError("unsupported engine configuration (B={}, N={}, beam={}; see ovc_workspace_bytes)"
-                                  .format(B, N, k))
-        return self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need), need
+    def _stream_key(self, kind, extra=None):
+        """The key of the current stream's entry of ``_buffers``."""
+        return kind, torch.cuda.current_stream().cuda_stream, extra
 
-    def _cached_workspace(self, table, key, need):
-        ws = table.get(key)
+    def _workspace(self, kind, need, extra=None):
+        """The current stream's scratch buffer of a kind, of at least ``need`` bytes."""
+        key = self._stream_key(kind, extra)
+        ws = self._buffers.get(key)
         if ws is None or ws.numel() < need:
-            old = table.pop(key, None)
-            if old is not None:
+            size = need
+            if ws is not None:
                 # captured graphs reference the old buffer's addresses: drop them before it is freed
-                self.lib.ovc_graph_cache_drop_workspace(old.data_ptr())
-            # grow geometrically so that a slowly increasing region count does not re-allocate (and re-capture) every time
-            size = need if old is None else max(need, int(old.numel() * 1.25))
-            ws = table[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
+                self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+                # grow geometrically so that a slowly increasing region count does not re-allocate (and re-capture) every time
+                size = max(need, int(ws.numel() * 1.25))
+            ws = self._buffers[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
         return ws
+
+    def _search_workspace(self, kind, B, N, width, return_probs):
+        """The stream's search buffer and the bytes a generation of a ``_SEARCH_FORMS`` kind needs of it, or the kind's refusal."""
+        sizer, what, width_name, _ = self._SEARCH_FORMS[kind]
+        need = getattr(self.lib, sizer)(ctypes.byref(self.desc), B, N, width,
+                                        *(() if kind == "masked" else (1 if return_probs else 0,)))
+        if need == 0:
+            raise native.OvcError("unsupported {} (B={}, N={}, {}={}; see {})".format(what, B, N, width_name, width, sizer))
+        return self._workspace("search", need), need
 
     def release(self):
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
-        for table in ("_workspaces", "_fw_workspaces", "_train_workspaces", "_seq_workspaces"):
-            for ws in getattr(self, table, {}).values():
-                if lib is not None:
-                    lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
-            setattr(self, table, {})
-        self._step_arenas = {}
-        self._steps_device = {}
+        for (kind, _, _), ws in getattr(self, "_buffers", {}).items():
+            if lib is not None and kind not in ("arena", "steps"):
+                lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
+        self._buffers = {}
 
     def __del__(self):
         try:
@@ -527,7 +530,7 @@ class CaptionEngine:
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
         self._refresh_derived()
-        ws, need = self._get_workspace(B, N, 1, False)
+        ws, need = self._search_workspace("beam", B, N, 1, False)
         d = self.desc
         shape = (B, d.n_levels, N, d.d_model) if d.enc_kind == native.ENC_MULTILEVEL else (B, N, d.d_model)
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -549,6 +552,18 @@ class CaptionEngine:
         if self.desc.enc_kind == native.ENC_GEOMETRIC and boxes is None:
             raise native.OvcError("the geometric encoder needs region boxes")
         return features, boxes
+
+    def _check_caption_pair(self, B, caption_tokens, targets, optional=False):
+        """``check_caption_ids`` of a teacher-forced pair: ``caption_tokens`` and ``targets`` (``optional``: or None) of one
+        shape.  Returns T."""
+        d = self.desc
+        T = check_caption_ids(caption_tokens, "caption_tokens", B, d.max_len, d.vocab)
+        if targets is not None or not optional:
+            check_caption_ids(targets, "targets", B, d.max_len, d.vocab)
+            if tuple(targets.shape) != tuple(caption_tokens.shape):
+                raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
+                    tuple(targets.shape), tuple(caption_tokens.shape)))
+        return T
 
     def _dropout_table(self, dropout):
         """``(probs, seed)`` -> the ``ovc_dropout`` table, or None when no site has ``p > 0`` (the plain call)."""
@@ -577,28 +592,38 @@ class CaptionEngine:
 
     def _steps_tensor(self):
         """The one-element int32 device tensor a gated search writes its step count to: one per stream, as the workspaces."""
-        key = torch.cuda.current_stream().cuda_stream
-        steps = self._steps_device.get(key)
-        if steps is None:
-            steps = self._steps_device[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return steps
+        key = self._stream_key("steps")
+        if key not in self._buffers:
+            self._buffers[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._buffers[key]
 
-    # form -> the entry point of a search and the names of its arguments behind ``logp``: chosen here and nowhere else.  "graph",
-    # "early" and "device" are ``ovc_beam_search_dropout``'s modes 0, 1 and 2.
+    # kind of generation -> (its sizer, what its refusal calls the configuration and the width, form -> (the entry point, the
+    # names of its arguments behind the width)): chosen here and nowhere else.  The masked search's "graph", "early" and
+    # "device" are ``ovc_beam_search_dropout``'s modes 0, 1 and 2.
+    _RESULTS = ("ws", "need", "ids", "logp")
     _SEARCH_FORMS = {
-        "plain": ("ovc_beam_search", ("everything", "stream")),
-        "graph": ("ovc_beam_search_graph", ("stream",)),
-        "early": ("ovc_beam_search_early", ("steps_run", "stream")),
-        "device": ("ovc_beam_search_gated", ("steps", "stream")),
-        "dropout": ("ovc_beam_search_dropout", ("stream", "table", "slots", "mode", "steps", "steps_run")),
+        "beam": ("ovc_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search", ("out_size", *_RESULTS, "everything", "stream")),
+            "graph": ("ovc_beam_search_graph", ("out_size", *_RESULTS, "stream")),
+            "early": ("ovc_beam_search_early", ("out_size", *_RESULTS, "steps_run", "stream")),
+            "device": ("ovc_beam_search_gated", ("out_size", *_RESULTS, "steps", "stream"))}),
+        "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
+            ("graph", "early", "device"),
+            ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
+        "sample": ("ovc_sample_workspace_bytes", "configuration for sampling", "n_samples", {
+            "plain": ("ovc_sample", ("seed", *_RESULTS, "everything", "stream")),
+            "graph": ("ovc_sample_graph", ("seed", *_RESULTS, "stream"))}),
     }
 
-    def _run_search(self, features, boxes, batch_size, beam_size, out_size, return_probs, early, table_drop):
-        """Every search: the refusals, the form, its workspace and results, and the call.  ``table_drop``: the ``ovc_dropout``
-        table of a search with dropout (``ovc_beam_search_dropout`` in the form ``early`` selects), or None.  Returns
-        ``(ids, logp, everything, slots)``, ``ids`` / ``logp`` / ``slots`` ``(B, out_size, T)``; ``slots`` (int32, None without
+    def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None):
+        """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
+        beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
+        ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
+        the form ``early`` selects), or None.  Returns ``(ids, logp, everything, slots)``, ``ids`` / ``logp`` / ``slots``
+        ``(B, out_size, T)``; ``everything`` ``(B, width, T, V)`` with ``return_probs``, else None; ``slots`` (int32, None without
         dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
         (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
+        kind = "sample" if seed is not None else "beam" if table_drop is None else "masked"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -606,41 +631,33 @@ class CaptionEngine:
                                       "encoder memory slots) only")
         if early == "device" and self.precision != "f32":
             raise native.OvcError("early_exit='device' runs in 'f32' only (precision={!r})".format(self.precision))
-        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, beam_size)
+        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, width)
         d = self.desc
         T = d.max_len
-        # with return_probs every early_exit value runs the full plain search; without use_graph (OVC_GRAPH=0) the whole-search
-        # graph's form is the plain search as well
+        # with return_probs every early_exit value runs the full plain form; without use_graph (OVC_GRAPH=0) the whole-search
+        # graph's form is the plain one as well, for beams and samples (the masked search has no plain form)
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
-        if table_drop is None:
-            if form == "graph" and not self.use_graph:
-                form = "plain"
-            ws, need = self._get_workspace(B, N, beam_size, return_probs)
-        else:
-            need = self.lib.ovc_beam_search_dropout_workspace_bytes(ctypes.byref(d), B, N, beam_size)
-            if need == 0:
-                raise native.OvcError("unsupported configuration for a search with dropout (B={}, N={}, beam={}; see "
-                                      "ovc_beam_search_dropout_workspace_bytes)".format(B, N, beam_size))
-            ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
+        if form == "graph" and not self.use_graph and kind != "masked":
+            form = "plain"
+        ws, need = self._search_workspace(kind, B, N, width, return_probs)
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
-        everything = torch.empty(B, beam_size, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
+        everything = torch.empty(B, width, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
         steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
         # OVC_GRAPH=0: every call is the first of its shape (plain launches; the host-early search without dropout keeps its graphs)
         if not self.use_graph and (form == "device" or table_drop is not None):
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
-        args = {name: None if t is None else t.data_ptr() for name, t in (("everything", everything), ("slots", slots), ("steps", steps))}
-        args.update(stream=native.stream_handle(), steps_run=ctypes.byref(issued))
-        entry, tail = self._SEARCH_FORMS[form]
+        args = {name: None if t is None else t.data_ptr() for name, t in (
+            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", slots), ("steps", steps), ("seed", seed))}
+        args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
         if table_drop is not None:
             args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
-            entry, tail = self._SEARCH_FORMS["dropout"]
+        entry, names = self._SEARCH_FORMS[kind][3][form]
         self.last_steps_run = T
         check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
-                                       beam_size, out_size, ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(),
-                                       *(args[name] for name in tail)), entry)
+                                       width, *(args[name] for name in names)), entry)
         if form == "early":
             self.last_steps_run = issued.value
         if form == "device":
@@ -692,24 +709,8 @@ class CaptionEngine:
         S = self.check_sample(n_samples)
         if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != self.device:
             raise native.OvcError("sample: the seed must be a one-element int64 tensor on {}".format(self.device))
-        features, boxes, B, N = self._search_inputs(features, boxes, batch_size, S)
-        d = self.desc
-        T = d.max_len
-        need = self.lib.ovc_sample_workspace_bytes(ctypes.byref(d), B, N, S, 1 if return_probs else 0)
-        if need == 0:
-            raise native.OvcError("unsupported configuration for sampling (B={}, N={}, n_samples={}; see "
-                                  "ovc_sample_workspace_bytes)".format(B, N, S))
-        ws = self._cached_workspace(self._workspaces, torch.cuda.current_stream().cuda_stream, need)
-        ids = torch.empty(B, S, T, dtype=torch.int64, device=self.device)
-        logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device)
-        head = (ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N, S, seed.data_ptr(),
-                ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr())
-        if return_probs or not self.use_graph:
-            everything = torch.empty(B, S, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
-            check(self.lib.ovc_sample(*head, None if everything is None else everything.data_ptr(), native.stream_handle()), "ovc_sample")
-            return (ids, logp, everything) if return_probs else (ids, logp)
-        check(self.lib.ovc_sample_graph(*head, native.stream_handle()), "ovc_sample_graph")
-        return ids, logp
+        ids, logp, everything, _ = self._run_search(features, boxes, batch_size, S, S, return_probs, seed=seed)
+        return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------
     def _check_trainable(self):
@@ -778,14 +779,9 @@ class CaptionEngine:
             if loss == (0.0, "tokens"):
                 loss = None
         self._check_trainable()
-        d = self.desc
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
-        T = check_caption_ids(caption_tokens, "caption_tokens", B, d.max_len, d.vocab)
-        check_caption_ids(targets, "targets", B, d.max_len, d.vocab)
-        if tuple(targets.shape) != tuple(caption_tokens.shape):
-            raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
-                tuple(targets.shape), tuple(caption_tokens.shape)))
+        T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         form = self._train_form(False, loss, table_drop, (B, N, T))
         tokens = caption_tokens.to(self.device).contiguous()
@@ -817,7 +813,7 @@ class CaptionEngine:
         if need == 0:
             raise native.OvcError("unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                "ovc_train_beams_workspace_bytes" if sequence else "ovc_train_workspace_bytes"))
+                self._TRAIN_FORMS[sequence, False, False][0]))
         return entry, shape, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
@@ -830,11 +826,7 @@ class CaptionEngine:
         self._refresh_derived()
         d = self.desc
         arena, table, grads = self._gradient_arena() if arena is None else arena
-        stream = torch.cuda.current_stream().cuda_stream
-        if len(shape) == 4:
-            ws = self._cached_workspace(self._seq_workspaces, (stream, shape[2]), need)
-        else:
-            ws = self._cached_workspace(self._train_workspaces, stream, need)
+        ws = self._workspace("sequence", need, shape[2]) if len(shape) == 4 else self._workspace("train", need)
         out = None if out_shape is None else torch.empty(out_shape, dtype=torch.float32, device=self.device)
         graph = self.use_graph if use_graph is None else bool(use_graph)
         check(getattr(self.lib, entry)(
@@ -862,10 +854,10 @@ class CaptionEngine:
         """The gradient arena ``xe_step`` reuses from call to call, one per stream: ``(arena, table, views)`` as
         ``_gradient_arena`` makes them.  Its contents are one step's gradients, consumed by the optimizer launch that follows
         on the same stream."""
-        key = torch.cuda.current_stream().cuda_stream
-        if key not in self._step_arenas:
-            self._step_arenas[key] = self._gradient_arena()
-        return self._step_arenas[key]
+        key = self._stream_key("arena")
+        if key not in self._buffers:
+            self._buffers[key] = self._gradient_arena()
+        return self._buffers[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
                           beam_size=None, arena=None):
@@ -939,12 +931,8 @@ class CaptionEngine:
             raise native.OvcError("the teacher-forced forward runs in 'f32' only (precision={!r})".format(self.precision))
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
-        T = check_caption_ids(caption_tokens, "caption_tokens", B, d.max_len, d.vocab)
+        T = self._check_caption_pair(B, caption_tokens, targets, optional=True)
         if targets is not None:
-            check_caption_ids(targets, "targets", B, d.max_len, d.vocab)
-            if tuple(targets.shape) != tuple(caption_tokens.shape):
-                raise native.OvcError("targets {} must have the shape of caption_tokens {}".format(
-                    tuple(targets.shape), tuple(caption_tokens.shape)))
             targets = targets.to(self.device).contiguous()
         tokens = caption_tokens.to(self.device).contiguous()
         want_logp = targets is None
@@ -953,8 +941,7 @@ class CaptionEngine:
             raise native.OvcError("unsupported teacher-forced configuration (B={}, N={}, T={}; see ovc_forward_workspace_bytes)"
                                   .format(B, N, T))
         self._refresh_derived()
-        stream = torch.cuda.current_stream().cuda_stream
-        ws = self._cached_workspace(self._fw_workspaces, (stream, want_logp), need)
+        ws = self._workspace("forward", need, want_logp)
         logp = torch.empty(B, T, d.vocab, dtype=torch.float32, device=self.device) if want_logp else None
         token_logp = None if want_logp else torch.empty(B, T, dtype=torch.float32, device=self.device)
         check(self.lib.ovc_forward(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,

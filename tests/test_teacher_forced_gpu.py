@@ -219,6 +219,11 @@ def test_grid_feature_architecture():
     torch.testing.assert_close(got, ops, rtol=1e-4, atol=2e-5, equal_nan=True)
 
 
+def _search_buffers(model):
+    """The engine's search workspaces, one per stream."""
+    return {key: ws for key, ws in model._engine._buffers.items() if key[0] == "search"}
+
+
 def test_score_between_searches_leaves_the_search_alone():
     """beam_search / score / beam_search on one stream: the search keeps its workspace (its graphs are keyed on the address),
     the graph cache does not grow on the second search, and the search results are unchanged."""
@@ -228,7 +233,7 @@ def test_score_between_searches_leaves_the_search_alone():
     lib = native.load()
     with torch.no_grad():
         first = [model.beam_search(batch(feats), batch_size=4, beam_size=3) for _ in range(3)]   # captured by now
-        search_ws = dict(model._engine._workspaces)
+        search_ws = _search_buffers(model)
         size_before = lib.ovc_graph_cache_size()
         for _ in range(3):
             model.score(_items(feats, None, tokens))
@@ -236,7 +241,7 @@ def test_score_between_searches_leaves_the_search_alone():
         again = model.beam_search(batch(feats), batch_size=4, beam_size=3)
         size_after = lib.ovc_graph_cache_size()
     assert all(torch.equal(a, b) for a, b in zip(first[-1], again))
-    assert {k: v.data_ptr() for k, v in model._engine._workspaces.items()} == {k: v.data_ptr() for k, v in search_ws.items()}
+    assert {k: v.data_ptr() for k, v in _search_buffers(model).items()} == {k: v.data_ptr() for k, v in search_ws.items()}
     assert size_mid <= size_before + 1 and size_after == size_mid
 
 

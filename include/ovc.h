@@ -503,14 +503,62 @@ int ovc_dropout_mask_rows(const int64_t* seed, int site, const int32_t* mask_row
  * baked in: it is copied to the workspace's seed slot before the replay.  Workspace: ovc_sample_workspace_bytes (0 when
  * unsupported; return_probs as ovc_workspace_bytes).
  * OVC_EINVAL, nothing launched: S outside 1..OVC_MAX_BEAM, a null seed, precision != 0, a vocabulary of more than 16 384 words.
- * Not covered: temperature, top-k and nucleus sampling (the block pieces are those of the unscaled logits), sampling under
- * dropout, the early-exit forms, more than OVC_MAX_BEAM samples per call (call again with another seed), results independent of
- * an image's position in the batch (the counter holds b). */
+ * Temperature, top-k and nucleus sampling: ovc_sample_shaped below.  Not covered: sampling under dropout, the early-exit
+ * forms, more than OVC_MAX_BEAM samples per call (call again with another seed), results independent of an image's position in
+ * the batch (the counter holds b). */
 size_t ovc_sample_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs);
 int ovc_sample(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
                void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, float* all_logp_out, ovc_stream stream);
 int ovc_sample_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
                      void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream);
+
+/* Shaped sampling: ovc_sample with a temperature, a top-k and a nucleus (top-p) truncation (appended to ABI 8; no struct changes).
+ * The block pieces belong to the unshaped logits, so every step reads the row's V logits: a chooser (ovc_sample_choice: the same
+ * code) finds the kept set and draws from it, and the bookkeeping of ovc_sample takes its word.  The rule:
+ * Options.  temperature: finite, > 0 (1: off).  top_k: >= 0 (0: off; >= V: no truncation).  top_p: a normal fp32 number in
+ * (0, 1], i.e. >= FLT_MIN (1: off).  Applied in this order: temperature, top-k, top-p on the top-k survivors.
+ * For a live row with logits x_w, w < V:  M = max_w x_w (exact; the M of the block pieces).  Shaped mass m_w = exp((x_w - M) /
+ * temperature) in fp32; the maximum has mass exactly 1.
+ * Ranking.  Words ordered by x_w descending, ties by the lower word index: a total order on the stored fp32 values, -0.0 and
+ * +0.0 being one value (compared through their order-preserving 32-bit integer image, NaN last), no arithmetic.  The top-k set is the first min(top_k, V) words
+ * of the ranking, exactly.
+ * Nucleus.  Inside the top-k set, in ranking order, the shortest prefix whose mass reaches top_p * Z1, Z1 = the mass of the top-k
+ * set; at least one word.  Its length is the row's kept count n.  (fp32 sums in a fixed order; the words of one tie group have one
+ * mass and the group contributes as many as the goal still needs.)
+ * The draw.  The row's u is ovc_sample's: counter (r, t, 0x53414D50, 0), word 0, the same fp32 formula.
+ * The word.  The inverse CDF at u over the kept words in ascending word order: target = u * Z2, Z2 = the kept mass; the first kept
+ * word whose inclusive prefix exceeds target, the last kept word where rounding leaves none.  The word is in [0, V) and a kept
+ * word whatever the logits hold (a row of NaNs: every comparison fails, word 0).
+ * Ended rows, sample order, results: as ovc_sample.
+ * logp_out / all_logp_out stay the MODEL's log-probabilities (x_w - M) - ls with M and ls from the block pieces, as ovc_sample
+ * forms them: neither tempered nor renormalised.  logp_out is the gathered all_logp_out entry bit for bit and the teacher-forced
+ * log-probability of the sampled ids, so ovc_sequence_backward recomputes it unchanged; a policy gradient on shaped samples is
+ * the usual off-policy surrogate.
+ * Neutral options (temperature 1, top_k 0, top_p 1) are ovc_sample / ovc_sample_graph: the same launches, the same bits.
+ * Determinism.  Every floating-point sum of the chooser is per thread over its words in ascending order, then a fixed tree over
+ * the lanes, then the waves in ascending order: a function of V and the options alone, never of the grid, stream or replay; no
+ * floating-point atomics.  The same inputs and seed give the same bits.
+ * ovc_sample_shaped_graph: the options are part of the graph's key; a call never replays the graph of other options.
+ * ovc_sample_shaped_workspace_bytes: ovc_sample_workspace_bytes plus the chooser's scratch; 0 for everything that sizer refuses
+ * and for bad options.
+ * ovc_sample_choice: the chooser alone over `rows` rows of V <= 16 384 logits, word w of row i at logits[i * ld_row + w * ld_word]
+ * (the engine's layout: ld_row = 1, ld_word = rows padded to 4); row i draws with counter (i, t, ...); seed: one int64 in device
+ * memory.  word_out / kept_out [rows] (int32, device) receive the word and the kept count n.  Workspace:
+ * ovc_sample_choice_workspace_bytes(rows, V) (needed when ld_word != 1; 0: out of scope).
+ * OVC_EINVAL, nothing launched: temperature not finite or <= 0, top_k < 0, top_p outside [FLT_MIN, 1] or NaN, and everything ovc_sample
+ * refuses. */
+size_t ovc_sample_shaped_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs, float temperature, int top_k,
+                                         float top_p);
+int ovc_sample_shaped(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                      float temperature, int top_k, float top_p, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                      float* logp_out, float* all_logp_out, ovc_stream stream);
+int ovc_sample_shaped_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                            float temperature, int top_k, float top_p, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                            float* logp_out, ovc_stream stream);
+size_t ovc_sample_choice_workspace_bytes(long rows, int V);
+int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, int V, const int64_t* seed, int t, float temperature,
+                      int top_k, float top_p, void* workspace, size_t workspace_bytes, int32_t* word_out, int32_t* kept_out,
+                      ovc_stream stream);
 
 /* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
  * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host

@@ -6,7 +6,7 @@ API kept: ``forward(input_features, fused=False) -> log-probs (B,T,V)`` (``fused
 -> (B,T)`` target log-probs (engine); ``encoder_forward(input_features) ->
 (encoder_features, padding_mask (B,1,1,N) bool)``; ``step(t, prev_output)``;
 ``beam_search(input_features, batch_size, beam_size, out_size=1, return_probs=False)``;
-``sample(input_features, batch_size, n_samples, generator=None, return_probs=False)``.
+``sample(input_features, batch_size, n_samples, generator=None, return_probs=False, temperature=1.0, top_k=None, top_p=None)``.
 
 ``beam_search`` is the accelerated path: one call into the fused HIP engine
 (``csrc/engine.hip``) which runs encoder, every decode step and the beam bookkeeping on the
@@ -286,7 +286,7 @@ class BaseTransformer(Module):
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
-                  max_norm=None, sample=False):
+                  max_norm=None, sample=False, temperature=1.0, top_k=None, top_p=None):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -319,7 +319,9 @@ class BaseTransformer(Module):
         becomes ``outs, log_probs = model.sample(items, B, k, generator=generator)`` -- and everything behind it is unchanged.
         One seed per call, drawn from ``generator``.  ``sample=True`` with ``dropout=True``, or with an ``early_exit`` other than
         ``None`` / ``False``, is refused before any launch or draw (sampling has neither form; the ``OVC_EARLY_EXIT`` default does
-        not apply to it).
+        not apply to it).  ``temperature`` / ``top_k`` / ``top_p``: ``model.sample``'s, for ``sample=True`` only -- the captions are
+        drawn from the shaped distribution and the loss uses the model's own log-probabilities of them (the usual off-policy
+        surrogate); a bad option, or an option without ``sample=True``, is refused by name before any launch or draw.
 
         ``p.grad`` is neither read nor written, and autograd is not involved (the call works under ``torch.no_grad()``): gradient
         hooks do NOT fire -- ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them
@@ -327,6 +329,10 @@ class BaseTransformer(Module):
         from . import optim as _optim
         from . import scst as _scst
         from .cider import CiderCorpus
+        if not sample:
+            for name, given in (("temperature", temperature != 1.0), ("top_k", top_k is not None), ("top_p", top_p is not None)):
+                if given:
+                    raise engine.native.OvcError("scst_step({}=...) shapes sampled captions: it needs sample=True".format(name))
         if sample and dropout:
             raise engine.native.OvcError("scst_step(sample=True, dropout=True): sampling under dropout is not covered -- set "
                                          "dropout=False (DROPOUT: 0 or model.eval())")
@@ -345,8 +351,7 @@ class BaseTransformer(Module):
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
         eng._check_trainable()
-        if sample:
-            eng.check_sample(k)
+        checked = eng.check_sample(k, temperature, top_k, top_p) if sample else None
         _checked_step_optimizer(optimizer, "scst_step", eng)
         feats, boxes = eng._checked_inputs(*self._engine_inputs(input_features))
         B = feats.shape[0]
@@ -362,7 +367,7 @@ class BaseTransformer(Module):
                     B, eng.device, "{} {} on {}".format(rows.dtype, tuple(rows.shape), rows.device)
                     if isinstance(rows, torch.Tensor) else type(rows).__name__))
         outs, log_probs, _, recompute = self._generate(input_features, B, k, None if sample else k, probs, generator,
-                                                       early_exit=early_exit)
+                                                       early_exit=early_exit, checked=checked)
         if corpus is not None:
             r = corpus.reward(outs, rows)
         else:
@@ -440,7 +445,8 @@ class BaseTransformer(Module):
             self.encoder_features, self.encoder_padding_mask = self.encoder_forward(input_features)
             return searcher.apply(out_size, return_probs, **kwargs)
 
-    def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False):
+    def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False, temperature=1.0,
+               top_k=None, top_p=None):
         """``n_samples`` captions per image drawn from the model's own distribution, on the HIP engine (``ovc_sample``; the rule
         is stated in ``include/ovc.h`` and mirrored by ``openviic_amd.sampling``): ``(ids [B, S, T] int64, log_probs [B, S, T])``
         in sample order, plus ``all_log_probs [B, S, T, V]`` with ``return_probs=True``.  After a caption's first ``<eos>`` every
@@ -453,18 +459,26 @@ class BaseTransformer(Module):
 
         In ``train()`` mode with gradients enabled ``log_probs`` carries a gradient as ``beam_search``'s does (``_BeamLogProbs``,
         ``ovc_sequence_backward``: the same scope, the refusals raised from ``backward()``).  Dropout counts as the identity: a
-        live dropout raises from ``backward()`` with the beam search's message.  No temperature, top-k or nucleus form."""
-        self._fused_engine().check_sample(n_samples)
+        live dropout raises from ``backward()`` with the beam search's message.
+
+        ``temperature`` (finite, > 0), ``top_k`` (an integer >= 0; None or 0: off) and ``top_p`` (in (0, 1]; None or 1: off) shape
+        the distribution the words are drawn from, in this order (``ovc_sample_shaped``): masses
+        ``exp((x - max x) / temperature)``, the ``top_k`` best words (ties by the lower index), of those the shortest prefix that
+        reaches ``top_p`` of their mass.  ``log_probs`` and ``all_log_probs`` stay the MODEL's log-probabilities, neither tempered
+        nor renormalised, so the backward is unchanged and a loss on shaped samples is the usual off-policy surrogate.  ``top_k=1``
+        is the greedy decode; neutral options are the call without them, bit for bit.  A bad option is refused by name before any
+        launch and any draw."""
+        checked = self._fused_engine().check_sample(n_samples, temperature, top_k, top_p)
         ids, logp, everything, recompute = self._generate(input_features, batch_size, n_samples, generator=generator,
-                                                          return_probs=return_probs)
+                                                          return_probs=return_probs, checked=checked)
         logp = self._scst_log_probs(input_features, ids, logp, recompute)
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     def _generate(self, input_features, batch_size, width, out_size=None, probs=None, generator=None, return_probs=False,
-                  early_exit=None):
+                  early_exit=None, checked=None):
         """One fused generation, for ``beam_search``, ``sample`` and ``scst_step``: ``width`` beams of which the best ``out_size``
         are returned -- with ``probs`` (what ``_search_dropout_probs`` returned, not empty) under this call's dropout masks -- or,
-        with ``out_size=None``, ``width`` samples.  The masks' or the samples' seed is drawn here, one per call; plain beams draw
+        with ``out_size=None``, ``width`` samples under the sampler's options (``checked``: what ``check_sample`` returned).  The masks' or the samples' seed is drawn here, one per call; plain beams draw
         nothing.  Returns ``(ids, log_probs, all_log_probs, recompute)``: the first two unsqueezed ``(B, out_size, T)``, the third
         None without ``return_probs``, the last the keyword arguments under which ``sequence_backward`` recomputes these
         log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``)."""
@@ -472,7 +486,9 @@ class BaseTransformer(Module):
         feats, boxes = self._engine_inputs(input_features)
         recompute = {}
         if out_size is None:
-            out = eng.sample(feats, boxes, batch_size, width, _dropout.draw_seed(eng.device, generator), return_probs=return_probs)
+            checked = checked or eng.check_sample(width)
+            out = eng.sample(feats, boxes, batch_size, width, _dropout.draw_seed(eng.device, generator), return_probs=return_probs,
+                             checked=checked)
         elif probs:
             drop = (probs, _dropout.draw_seed(eng.device, generator))
             *out, slots = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, early_exit=early_exit, dropout=drop)

@@ -256,6 +256,44 @@ __device__ __forceinline__ float wave_prefix_sum(float v, int lane) {
 __global__ __launch_bounds__(kFusedThreads) void sample_fused_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
                                                                             int stats_ld, long ld_row, long ld_word,
                                                                             const int64_t* __restrict__ seed) {
+    constexpr bool kChosen = false;                     // the word is drawn here ...
+    constexpr const int32_t* chosen = nullptr;          // ... not taken from a chooser's output (the instance below)
+#include "bodies/sample_fused_update.inc"
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Shaped sampling (ovc_sample_shaped, include/ovc.h: the rule): temperature, top-k and nucleus.  The block pieces belong to the
+// unshaped logits, so the selection reads the row: sample_choice_kernel (one workgroup per draw, the row in registers, 16 words
+// per thread) finds the kept set and draws from it, and the bookkeeping instance of sample_fused_update takes the word from its
+// output.  The fused vocabulary tail stores logits^T, so a pass of its own (logits_to_rows_kernel: 64 x 64 tiles through LDS)
+// first lays the rows out row-major.
+constexpr int kChoicePer = 16;                           // words per thread: 256 threads up to V = 4096, 1024 up to 16 384
+
+__global__ __launch_bounds__(256) void logits_to_rows_kernel(const float* __restrict__ src, long ld_row, long ld_word, int rows, int V,
+                                                             float* __restrict__ dst) {
+    __shared__ float tile[64][65];
+    const int w0 = blockIdx.x * 64, r0 = blockIdx.y * 64, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int i = ty; i < 64; i += 4)                     // lanes along the rows: contiguous in logits^T
+        if (r0 + tx < rows && w0 + i < V) tile[i][tx] = src[(size_t)(r0 + tx) * ld_row + (size_t)(w0 + i) * ld_word];
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4)                     // lanes along the words: contiguous in the row-major copy
+        if (r0 + i < rows && w0 + tx < V) dst[(size_t)(r0 + i) * V + w0 + tx] = tile[tx][i];
+}
+
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void sample_choice_kernel(const float* __restrict__ x, long ldx, int V, int draws,
+                                                                 const int64_t* __restrict__ seed, int t, float temperature, int top_k,
+                                                                 float top_p, int32_t* __restrict__ word_out, int32_t* __restrict__ kept_out) {
+#include "bodies/sample_choice.inc"
+}
+
+// sample_fused_update with the word of sample (b, s) read from chosen[b * k + s]: stage A's pieces, stage D and
+// beam_follow_winners unchanged.
+__global__ __launch_bounds__(kFusedThreads) void sample_shaped_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                             int stats_ld, long ld_row, long ld_word,
+                                                                             const int32_t* __restrict__ chosen) {
+    constexpr bool kChosen = true;
+    constexpr const int64_t* seed = nullptr;
 #include "bodies/sample_fused_update.inc"
 }
 
@@ -366,6 +404,62 @@ int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, 
     hipLaunchKernelGGL(sample_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, ld_row, ld_word, seed);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+// The chooser (ovc_sample_choice; the engine's shaped step launches this same code): draw i of `rows * draws` draws is of row
+// i / draws with the Philox counter (i, t, ...).  scratch: rows * V floats, used when the words of a row are not contiguous.
+int ovc_sample_choice_launch(const float* logits, long ld_row, long ld_word, int rows, int V, int draws, const int64_t* seed, int t,
+                             float temperature, int top_k, float top_p, float* scratch, int32_t* word_out, int32_t* kept_out,
+                             hipStream_t stream) {
+    if (!logits || rows <= 0 || V <= 0 || V > 1024 * kChoicePer || draws <= 0 || draws > kMaxK || !seed || t < 0 || !word_out || !kept_out)
+        return OVC_EINVAL;
+    if (ld_row <= 0 || ld_word <= 0 || !ovc_sample_options_ok(temperature, top_k, top_p)) return OVC_EINVAL;
+    if ((long)rows * draws > 0x7fffffffL / 2) return OVC_EINVAL;
+    const float* x = logits;
+    long ldx = ld_row;
+    if (ld_word != 1) {
+        if (!scratch) return OVC_EWORKSPACE;
+        hipLaunchKernelGGL(logits_to_rows_kernel, dim3((V + 63) / 64, (rows + 63) / 64), dim3(256), 0, stream, logits, ld_row, ld_word, rows, V,
+                           scratch);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        x = scratch; ldx = V;
+    }
+    if (V <= 256 * kChoicePer)
+        hipLaunchKernelGGL(sample_choice_kernel<256>, dim3(rows * draws), dim3(256), 0, stream, x, ldx, V, draws, seed, t, temperature, top_k,
+                           top_p, word_out, kept_out);
+    else
+        hipLaunchKernelGGL(sample_choice_kernel<1024>, dim3(rows * draws), dim3(1024), 0, stream, x, ldx, V, draws, seed, t, temperature, top_k,
+                           top_p, word_out, kept_out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
+                                    const int32_t* chosen, int B, hipStream_t stream) {
+    if (B <= 0 || p.k <= 0 || p.k > kMaxK || (p.width != 1 && p.width != p.k) || p.V <= 0 || !stats || !chosen) return OVC_EINVAL;
+    if (nblk != (p.V + 31) / 32 || nblk > 512 || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
+    if (ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
+    hipLaunchKernelGGL(sample_shaped_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, ld_row, ld_word, chosen);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+extern "C" size_t ovc_sample_choice_workspace_bytes(long rows, int V) {
+    if (rows <= 0 || V <= 0 || V > 1024 * kChoicePer || rows > 0x7fffffffL / 2) return 0;
+    return ((size_t)rows * V * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, int V, const int64_t* seed, int t, float temperature,
+                                 int top_k, float top_p, void* workspace, size_t workspace_bytes, int32_t* word_out, int32_t* kept_out,
+                                 ovc_stream stream) {
+    if (!logits || rows <= 0 || V <= 0 || V > 1024 * kChoicePer || !seed || t < 0 || !word_out || !kept_out || ld_row <= 0 || ld_word <= 0 ||
+        !ovc_sample_options_ok(temperature, top_k, top_p))
+        return OVC_EINVAL;
+    if (ld_word != 1 && (!workspace || !ovc_aligned16(workspace) || workspace_bytes < ovc_sample_choice_workspace_bytes(rows, V)))
+        return OVC_EWORKSPACE;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_sample_choice_launch(logits, ld_row, ld_word, rows, V, 1, seed, t, temperature, top_k, top_p, reinterpret_cast<float*>(workspace),
+                                    word_out, kept_out, ovc_hip_stream(stream));
 }
 
 namespace {

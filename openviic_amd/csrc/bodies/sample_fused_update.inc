@@ -1,4 +1,5 @@
-// The body of sample_fused_update_kernel (beam.hip).  Not a header: no include guard.
+// The body of sample_fused_update_kernel and, with kChosen (the word is read from `chosen`, not drawn), of
+// sample_shaped_update_kernel (beam.hip).  Not a header: no include guard.
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
     __shared__ int parent[kMaxK], word[kMaxK];
@@ -29,6 +30,13 @@
         const float Z = wave_sum_dpp(sum);
         const float ls = logf(Z);
 
+        int wd; float xw;
+        if (kChosen) {
+            // ---- the word is the chooser's (sample_choice_kernel); a frozen row keeps word 0 -----------------------------------------
+            const bool live = alive != 0.0f;
+            wd = live ? min(max(chosen[b * k + wave], 0), V - 1) : 0;
+            xw = p.logits[(size_t)row * ld_row + (size_t)wd * ld_word];
+        } else {
         // ---- the draw: one Philox block per (row, step), word 0 (include/ovc.h, ovc_sample) --------------------------------------
         uint32_t c0 = (uint32_t)(b * k + wave), c1 = (uint32_t)t, c2 = kSampleCounterWord, c3 = 0u;
         ovc_philox_block((uint64_t)*seed, c0, c1, c2, c3);
@@ -78,8 +86,9 @@
         // a row that has emitted <eos> is frozen: word 0, whatever was drawn (its log-probability is multiplied by alive = 0)
         const bool live = alive != 0.0f;
         const float x0 = p.logits[(size_t)row * ld_row];
-        const int wd = live ? blk * 32 + pick : 0;
-        const float xw = live ? __shfl(x, pick, 64) : x0;
+        wd = live ? blk * 32 + pick : 0;
+        xw = live ? __shfl(x, pick, 64) : x0;
+        }
 
         // ---- D: the bookkeeping of beam_fused_update, winner = (parent row, drawn word) -----------------------------------------
         if (lane == 0) {

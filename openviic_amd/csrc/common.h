@@ -275,6 +275,16 @@ int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, in
 // bookkeeping is the fused update's.  seed: the device word the draw's Philox key is read from; p.alive_count must be nullptr.
 int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
                                    const int64_t* seed, int B, hipStream_t stream);
+// Shaped sampling (include/ovc.h, ovc_sample_shaped): the options' scope, the chooser and the bookkeeping that takes its word.
+static inline bool ovc_sample_options_ok(float temperature, int top_k, float top_p) {
+    // top_p: a normal number, so that top_p * Z1 (Z1 >= 1) never underflows to 0; NaN fails each comparison
+    return temperature > 0.0f && temperature <= 3.4028234664e38f && top_k >= 0 && top_p >= 1.17549435e-38f && top_p <= 1.0f;
+}
+int ovc_sample_choice_launch(const float* logits, long ld_row, long ld_word, int rows, int V, int draws, const int64_t* seed, int t,
+                             float temperature, int top_k, float top_p, float* scratch, int32_t* word_out, int32_t* kept_out,
+                             hipStream_t stream);
+int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
+                                    const int32_t* chosen, int B, hipStream_t stream);
 int ovc_debug_collect_winners_launch(const int32_t* anc, const int32_t* word, const float* running, int B, int width, int V, int k,
                                      int64_t* chosen, float* score, hipStream_t stream);
 int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const float* row_max, const float* row_lsum,

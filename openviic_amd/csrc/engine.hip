@@ -133,6 +133,8 @@ struct Workspace {
     int32_t* alive_count;                         // [T] beams still alive after each step (ovc_beam_search_early)
     int64_t* drop_seed; int32_t* steps_dev;       // ovc_beam_search_dropout: the call's seed (refreshed outside the captured body)
                                                   // and the gated search's step count for the slot table
+    float* choice_rows; int32_t* choice_word; int32_t* choice_kept;   // ovc_sample_shaped: the chooser's row-major logits [R][V],
+                                                  // the drawn words and the kept counts [R]
     // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
     // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -890,6 +892,10 @@ struct SearchCall {
     // Sampling (ovc_sample, ovc_sample_graph): the selection of every step is a draw from the row's distribution (k = out_size =
     // the samples per image) and the caller's seed, copied to the workspace's seed slot outside any captured body.
     bool sample; const int64_t* sample_seed;
+    // Shaped sampling (ovc_sample_shaped): has_options marks a call through the shaped entry points, whose workspace holds the
+    // chooser's buffers; with neutral options the launches are ovc_sample's.
+    bool has_options; float temperature; int top_k; float top_p;
+    bool shaped() const { return sample && has_options && !(temperature == 1.0f && top_k == 0 && top_p == 1.0f); }
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
 
@@ -907,12 +913,21 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
     if (c.sample && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.plan ||
                      (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
         return false;
+    if (c.has_options && (!c.sample || !ovc_sample_options_ok(c.temperature, c.top_k, c.top_p))) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
 }
 
 // With a plan, or sampling: the seed / step-count slots behind the plain layout.
 Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
-    return carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr || c.sample);
+    Workspace w = carve(m, base, c.B, c.N, c.k, c.all_logp_out != nullptr, c.plan != nullptr || c.sample);
+    if (c.has_options) {                          // behind everything else: ovc_sample's layout is a prefix
+        Bump a{reinterpret_cast<char*>(base), w.bytes};
+        const size_t R = (size_t)c.B * c.k;
+        w.choice_rows = a.take<float>(R * (size_t)m->vocab);
+        w.choice_word = a.take<int32_t>(R); w.choice_kept = a.take<int32_t>(R);
+        w.bytes = (a.off + 255) & ~(size_t)255;
+    }
+    return w;
 }
 
 // One pass over the decoder's layers, described once: a decode step of a search (run_decode_step) or the teacher-forced decoder
@@ -1129,7 +1144,11 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     if (fused_select) {
         // selection + bookkeeping in one launch, from the block pieces the vocabulary GEMM's epilogue left: no pass over the logits
         bu.row_max_out = return_probs ? w.row_max : nullptr; bu.row_lsum_out = return_probs ? w.row_lsum : nullptr;
-        if (c.sample)         // the one branch of a sampling step: a draw from the row's distribution in place of the k best
+        if (c.shaped()) {     // shaped sampling: the chooser reads the rows, the bookkeeping takes its words
+            RUN(ovc_sample_choice_launch(w.logits, ld_row, ld_word, rows, m->vocab, R / rows, w.drop_seed, t, c.temperature, c.top_k, c.top_p,
+                                         w.choice_rows, w.choice_word, w.choice_kept, s));
+            RUN(ovc_sample_shaped_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.choice_word, B, s));
+        } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.drop_seed, B, s));
         else if (!(debug_skip() & 8))
             RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s, e.gate));
@@ -1343,6 +1362,7 @@ enum class GraphKind {
     SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
     TrainSmoothed,      // ovc_forward_backward_smoothed, with or without dropout (k = T, out_size = 1)
     SampleSearch,       // ovc_sample_graph (k = out_size = S, the samples per image; the seed is read from its workspace slot)
+    ShapedSampleSearch, // ovc_sample_shaped_graph with options that are not neutral (as SampleSearch; the options in the hash)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1496,6 +1516,11 @@ int write_search_slots(Engine& e, Workspace& w, const SearchCall& c, int steps_h
 // whole-search graph and the per-step graphs share Search and live in different maps (g_graphs, g_early).  The dropout plan's
 // constants are hashed in -- 0 without a plan, so a search with dropout never shares an entry with the plain one.
 GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* workspace) {
+    if (c.shaped()) {
+        const struct { float temperature; int top_k; float top_p; } options{c.temperature, c.top_k, c.top_p};
+        return GraphKey{GraphKind::ShapedSampleSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N,
+                        c.k, c.out_size};
+    }
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1705,6 +1730,37 @@ extern "C" int ovc_sample_graph(const ovc_model* m, const float* features, const
     SearchCall c{B, N, S, S, SearchForm::Graph, ids_out, logp_out};
     c.sample = true; c.sample_seed = seed;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// Shaped sampling (include/ovc.h: the rule).  The three calls above with the options: a step's selection is then the chooser and the
+// bookkeeping that takes its word (run_decode_step); neutral options are the calls above, launch for launch.
+static SearchCall shaped_sample_call(SearchCall c, const int64_t* seed, float temperature, int top_k, float top_p) {
+    c.sample = true; c.sample_seed = seed;
+    c.has_options = true; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p;
+    return c;
+}
+
+extern "C" size_t ovc_sample_shaped_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs, float temperature,
+                                                    int top_k, float top_p) {
+    SearchCall c = shaped_sample_call(SearchCall{B, N, S, S}, nullptr, temperature, top_k, top_p);
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+extern "C" int ovc_sample_shaped(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
+                                 float temperature, int top_k, float top_p, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                 float* logp_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c = shaped_sample_call(SearchCall{B, N, S, S, SearchForm::Plain, ids_out, logp_out}, seed, temperature, top_k, top_p);
+    c.all_logp_out = all_logp_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_sample_shaped_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S,
+                                       const int64_t* seed, float temperature, int top_k, float top_p, void* workspace,
+                                       size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream) {
+    return run_search(m, shaped_sample_call(SearchCall{B, N, S, S, SearchForm::Graph, ids_out, logp_out}, seed, temperature, top_k, top_p),
+                      features, boxes, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@ Numerics never depend on a timing: the order in which every GEMM sums over K is 
 """
 import ctypes
 import json
+import math
+import operator
 import os
 import threading
 
@@ -467,11 +469,12 @@ class CaptionEngine:
             ws = self._buffers[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
         return ws
 
-    def _search_workspace(self, kind, B, N, width, return_probs):
-        """The stream's search buffer and the bytes a generation of a ``_SEARCH_FORMS`` kind needs of it, or the kind's refusal."""
+    def _search_workspace(self, kind, B, N, width, return_probs, options=()):
+        """The stream's search buffer and the bytes a generation of a ``_SEARCH_FORMS`` kind needs of it, or the kind's refusal.
+        ``options``: the shaped sampler's ``(temperature, top_k, top_p)``."""
         sizer, what, width_name, _ = self._SEARCH_FORMS[kind]
         need = getattr(self.lib, sizer)(ctypes.byref(self.desc), B, N, width,
-                                        *(() if kind == "masked" else (1 if return_probs else 0,)))
+                                        *(() if kind == "masked" else (1 if return_probs else 0,)), *options)
         if need == 0:
             raise native.OvcError("unsupported {} (B={}, N={}, {}={}; see {})".format(what, B, N, width_name, width, sizer))
         return self._workspace("search", need), need
@@ -613,17 +616,22 @@ class CaptionEngine:
         "sample": ("ovc_sample_workspace_bytes", "configuration for sampling", "n_samples", {
             "plain": ("ovc_sample", ("seed", *_RESULTS, "everything", "stream")),
             "graph": ("ovc_sample_graph", ("seed", *_RESULTS, "stream"))}),
+        "shaped": ("ovc_sample_shaped_workspace_bytes", "configuration for sampling", "n_samples", {
+            "plain": ("ovc_sample_shaped", ("seed", "temperature", "top_k", "top_p", *_RESULTS, "everything", "stream")),
+            "graph": ("ovc_sample_shaped_graph", ("seed", "temperature", "top_k", "top_p", *_RESULTS, "stream"))}),
     }
 
-    def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None):
+    def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
+                    options=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
         the form ``early`` selects), or None.  Returns ``(ids, logp, everything, slots)``, ``ids`` / ``logp`` / ``slots``
         ``(B, out_size, T)``; ``everything`` ``(B, width, T, V)`` with ``return_probs``, else None; ``slots`` (int32, None without
         dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
-        (``sequence_backward(dropout=..., slots=...)`` recomputes under them)."""
-        kind = "sample" if seed is not None else "beam" if table_drop is None else "masked"
+        (``sequence_backward(dropout=..., slots=...)`` recomputes under them).  ``options``: what ``sample_options`` returned --
+        the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw."""
+        kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -639,7 +647,7 @@ class CaptionEngine:
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
         if form == "graph" and not self.use_graph and kind != "masked":
             form = "plain"
-        ws, need = self._search_workspace(kind, B, N, width, return_probs)
+        ws, need = self._search_workspace(kind, B, N, width, return_probs, options or ())
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
@@ -654,6 +662,8 @@ class CaptionEngine:
         args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
         if table_drop is not None:
             args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
+        if options:
+            args.update(zip(("temperature", "top_k", "top_p"), options))
         entry, names = self._SEARCH_FORMS[kind][3][form]
         self.last_steps_run = T
         check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
@@ -686,8 +696,46 @@ class CaptionEngine:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
 
-    def check_sample(self, n_samples):
-        """The refusals of ``sample`` that need no input: callers that draw the seed themselves run them before the draw."""
+    @staticmethod
+    def sample_options(temperature=1.0, top_k=None, top_p=None):
+        """The shaped sampler's options checked and normalised: ``(temperature, top_k, top_p)`` with ``top_k`` 0 for off and
+        ``top_p`` 1 for off, or None when they are neutral (the plain draw).  A bad option is refused by name."""
+        try:
+            tau = float(temperature)
+        except (TypeError, ValueError):
+            tau = float("nan")
+        if not (math.isfinite(tau) and tau > 0):
+            raise native.OvcError("sample: temperature must be finite and > 0, got {!r}".format(temperature))
+        if top_k is None:
+            k = 0
+        else:
+            try:
+                k = -1 if isinstance(top_k, bool) else operator.index(top_k)
+            except TypeError:
+                k = -1
+            if not 0 <= k < 2 ** 31:
+                raise native.OvcError("sample: top_k must be an integer >= 0 (0 or None: off), got {!r}".format(top_k))
+        if top_p is None:
+            p = 1.0
+        else:
+            try:
+                p = float(top_p)
+            except (TypeError, ValueError):
+                p = float("nan")
+            if not 0 < p <= 1:
+                raise native.OvcError("sample: top_p must lie in (0, 1] (1 or None: off), got {!r}".format(top_p))
+        # the device takes fp32 options: what rounds out of the scope there is refused here, by name
+        tau32, p32 = ctypes.c_float(tau).value, ctypes.c_float(p).value
+        if not (math.isfinite(tau32) and tau32 > 0):
+            raise native.OvcError("sample: temperature must be finite and > 0 in float32, got {!r}".format(temperature))
+        if not 2.0 ** -126 <= p32 <= 1:                   # a normal fp32 number: top_p times the kept mass never underflows
+            raise native.OvcError("sample: top_p must be a normal float32 number in (0, 1], got {!r}".format(top_p))
+        return None if (tau32 == 1.0 and k == 0 and p32 == 1.0) else (tau32, k, p32)
+
+    def check_sample(self, n_samples, temperature=1.0, top_k=None, top_p=None):
+        """The refusals of ``sample`` that need no input: callers that draw the seed themselves run them before the draw.
+        Returns ``(S, options)``, ``options`` what ``sample_options`` returned: ``sample(..., checked=...)`` takes the pair."""
+        options = self.sample_options(temperature, top_k, top_p)
         S = int(n_samples)
         if not 1 <= S <= native.OVC_MAX_BEAM:
             raise native.OvcError("sample: 1 <= n_samples <= {} expected, got {} (call again with another seed for more)".format(
@@ -696,20 +744,24 @@ class CaptionEngine:
             raise native.OvcError("sample runs in 'f32' only (precision={!r})".format(self.precision))
         if self.desc.vocab > 16384:
             raise native.OvcError("sample covers vocabularies of at most 16384 words (got {})".format(self.desc.vocab))
-        return S
+        return S, options
 
-    def sample(self, features, boxes, batch_size, n_samples, seed, return_probs=False):
+    def sample(self, features, boxes, batch_size, n_samples, seed, return_probs=False, temperature=1.0, top_k=None, top_p=None,
+               checked=None):
         """``n_samples`` captions per image drawn from the model's distribution (``ovc_sample`` / ``ovc_sample_graph``;
         ``include/ovc.h`` states the rule, ``openviic_amd.sampling`` mirrors it).  ``seed``: a one-element int64 device tensor,
         read on the device.  Returns ``(ids, logp)`` ``(B, n_samples, T)`` in sample order, plus every step's log-probabilities
         ``(B, n_samples, T, V)`` with ``return_probs``.  The workspace cache and the ``OVC_GRAPH`` switch are the beam
         search's: one captured graph from the second call of a shape, plain launches with ``return_probs`` or ``OVC_GRAPH=0``.
         Refused before any launch: ``n_samples`` outside ``1..OVC_MAX_BEAM``, a precision other than 'f32', a vocabulary of
-        more than 16 384 words, a seed that is not a one-element int64 device tensor."""
-        S = self.check_sample(n_samples)
+        more than 16 384 words, a seed that is not a one-element int64 device tensor, a bad option.
+        ``temperature`` / ``top_k`` / ``top_p`` (``ovc_sample_shaped``): the draw is from the shaped and
+        truncated distribution, ``logp`` stays the model's own log-probability of the drawn word; neutral options are the plain
+        call, launch for launch.  ``checked``: what ``check_sample`` returned for these arguments, where the caller has run it."""
+        S, options = checked or self.check_sample(n_samples, temperature, top_k, top_p)
         if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != self.device:
             raise native.OvcError("sample: the seed must be a one-element int64 tensor on {}".format(self.device))
-        ids, logp, everything, _ = self._run_search(features, boxes, batch_size, S, S, return_probs, seed=seed)
+        ids, logp, everything, _ = self._run_search(features, boxes, batch_size, S, S, return_probs, seed=seed, options=options)
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------

@@ -191,6 +191,14 @@ SIGNATURES = {
                            c_void_p, c_void_p]),
     "ovc_sample_graph": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                  c_void_p, c_void_p]),
+    "ovc_sample_shaped_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int, c_float, c_int, c_float]),
+    "ovc_sample_shaped": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_int, c_float, c_void_p,
+                                  c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_sample_shaped_graph": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_int, c_float,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ovc_sample_choice_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "ovc_sample_choice": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_int, c_float, c_int, c_float, c_void_p, c_size_t,
+                                  c_void_p, c_void_p, c_void_p]),
     "ovc_cider_reward": (c_int, [POINTER(Cider), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_adam_chunk_count": (c_long, [c_void_p, c_int]),
     "ovc_adam_chunk_fill": (c_long, [c_void_p, c_int, c_void_p, c_long]),
@@ -213,7 +221,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_adam_chunk_count", "ovc_adam_chunk_fill", "ovc_adam_step", "ovc_debug_attention_mem_backward",
                  "ovc_scst_advantage_bytes", "ovc_scst_advantage", "ovc_caption_metrics_bytes", "ovc_caption_metrics",
                  "ovc_grad_norm", "ovc_train_smoothed_workspace_bytes", "ovc_forward_backward_smoothed",
-                 "ovc_sample_workspace_bytes", "ovc_sample", "ovc_sample_graph")
+                 "ovc_sample_workspace_bytes", "ovc_sample", "ovc_sample_graph",
+                 "ovc_sample_shaped_workspace_bytes", "ovc_sample_shaped", "ovc_sample_shaped_graph",
+                 "ovc_sample_choice_workspace_bytes", "ovc_sample_choice")
 
 _lib = None
 

@@ -832,6 +832,48 @@ int ovc_debug_linear_planes(const float* x, int K, const float* W, const void* p
 int ovc_debug_repeat_linear(const float* x, int K, const float* W, const float* bias, float* y,
                             int M, int N, int iters, ovc_stream stream);
 
+/* Test hooks: the decode-step attention launchers of the search on caller buffers (appended to ABI 8; no struct changes), so that
+ * every kernel instance can be compared with an fp64 restatement at the operator level (tests/test_decode_attention_gpu.py).
+ *
+ * ovc_debug_decode_self_attention: one query row per beam against its own history.  q [rows][ldq]; kcache / vcache
+ * [position][slot][ldkv] with pos_stride floats between positions, where position 0's block holds ONE slot per image (slot b) and
+ * every later position `width` slots per image (b * width ..); anc [rows][anc_ld]: the slot of position j < t that row r descends
+ * from (inside its image's block of that position); key t is the row's own slot r.  padflag [position][pad_ld]: 1 where the token
+ * fed at (position, slot) was <pad> -- such a key is masked (position 0 is <bos>, never flagged).  d_v = d_k.  out [rows][ldo].
+ * Steps t >= 64 need `partials`: ovc_debug_decode_self_partial_bytes(t, rows, h, d_k) bytes (part_o [chunks][rows][h * d_k], then
+ * part_ml [chunks][rows][h] float2, chunks = t / 16 + 1; 0 bytes below t = 64), 16-byte aligned.  gate: NULL = the ungated
+ * kernels, otherwise a device int32 the _gated twins read (0: nothing is written).  per_row != 0 forces the per-row kernel where
+ * the de-duplicated one is eligible.
+ *
+ * ovc_debug_decode_cross_attention: the `width` beams of image b against that image's N projected encoder keys, per level.
+ * q [B * width][ldq]; kx / vx [levels][B][N][ldkv] with level_stride floats between levels; encmask [B][N] (1 = masked) or NULL;
+ * out [levels][B * width][ldo] with out_level_stride floats between levels.  An image whose keys are all masked gives NaN rows.
+ *
+ * Both return OVC_EINVAL, nothing launched, for what the engine never sends: d_k outside {4, 8, 16, 32, 64}, h outside 1..32,
+ * h * d_k > 1024, width outside 1..8, rows % width != 0, t outside 0..255 (t = 0 with width != 1), N outside 1..1024, levels outside
+ * 1..OVC_MAX_LEVELS, a leading dimension or stride that is no multiple of 4 or smaller than h * d_k, q / K / V / out / partials
+ * not 16-byte aligned, t >= 64 without partials of the sizer's size.
+ *
+ * ovc_debug_decode_self_form / ovc_debug_decode_cross_form launch nothing: they return the instance the launch takes (the same
+ * selection function as the launchers), coded family * 100 + a * 10 + b, or OVC_EINVAL:
+ *   1 NT SB  decode_self_attention_mfma_kernel<NT, SB>           NT in {1,2,4,7} key tiles of 16, SB = d_k / 16 in {1,2,4}
+ *   2 NT SB  decode_self_attention_mfma_kernel<NT, SB, chunked>  NT in {1,2,4,5,8}, followed by decode_self_merge_kernel
+ *   3 CH KB  decode_self_attention_kernel<CH, KB>                CH in {1,2,4} float4 per lane and key row, KB in {1,4}
+ *   4 NT SB  decode_cross_attention_mfma_kernel<NT, SB>          NT in {4,8}
+ *   5 0 SB   decode_cross_attention_tiled_kernel<SB>
+ *   6 0 0    decode_cross_attention_lds_kernel
+ * e.g. 174 = the 7-tile de-duplicated self-attention at d_k = 64.  A non-NULL gate takes the _gated twin of the same form. */
+size_t ovc_debug_decode_self_partial_bytes(int t, int rows, int h, int d_k);
+int ovc_debug_decode_self_attention(const float* q, int ldq, const float* kcache, const float* vcache, size_t pos_stride, int ldkv,
+                                    const int32_t* anc, int anc_ld, const uint8_t* padflag, int pad_ld, int t, int width, int rows,
+                                    int h, int d_k, float* out, int ldo, void* partials, size_t partial_bytes, const int32_t* gate,
+                                    int per_row, ovc_stream stream);
+int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, const float* vx, size_t level_stride, int ldkv,
+                                     const uint8_t* encmask, int N, int width, int B, int heads, int d_k, int levels, float* out,
+                                     size_t out_level_stride, int ldo, const int32_t* gate, ovc_stream stream);
+int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
+int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -662,83 +662,90 @@ __global__ __launch_bounds__(256) void decode_self_merge_kernel_gated(DecodeSelf
 #include "bodies/decode_self_merge_kernel.inc"
 }
 
-// Steps t >= 64 (max_len up to OVC_MAX_LEN).  d_k >= 16: one workgroup per (image, 4 heads, chunk of kSelfChunk positions),
-// de-duplicated as above, then the merge.  d_k in {4, 8} (and the per-row A/B switch): the per-row kernel over 4 blocks of
-// 64 positions.  t < 64 never comes here, so the bits of those steps are the round-3 kernels'.
-static int decode_self_attention_long(const DecodeSelfArgs& p, int rows, bool per_row, hipStream_t stream, const int32_t* gate) {
-    const int W = p.width, hk = p.h * p.dk;
-    if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16) {
-        if (!p.part_o || !p.part_ml) return OVC_EINVAL;
-        const int chunks = (p.t + kSelfChunk) / kSelfChunk;
-        const dim3 grid(rows / W, (p.h + 3) / 4, chunks), block(256);
+// ---- which instance a decode self-attention launch takes ---------------------------------------------------------------
+// ONE selection function for the launcher below and for the form query of the test hook (ovc_debug_decode_self_form): the
+// choice is a function of (t, width, rows, h, d_k, per_row) alone and is coded as family * 100 + a * 10 + b (include/ovc.h):
+//   1 NT SB   decode_self_attention_mfma_kernel<NT, SB>         t < 64, d_k >= 16, at most 112 listed keys in the worst case
+//   2 NT SB   decode_self_attention_mfma_kernel<NT, SB, true>   t >= 64, d_k >= 16: one workgroup per chunk of kSelfChunk
+//             + decode_self_merge_kernel                        positions (at most 16 W listed keys: NT = W tiles), then the merge
+//   3 CH KB   decode_self_attention_kernel<CH, KB>              everything else (d_k in {4, 8}, more than 112 keys, per_row):
+//                                                               KB = 1 for t < 64, 4 blocks of 64 positions from there
+// t < 64 never takes a chunked instance, so the bits of those steps are the round-3 kernels'.  per_row forces family 3 where
+// the de-duplicated kernels are eligible (the A/B switch of the hooks build, and the test hook).
+constexpr int kFormSelfMfma = 100, kFormSelfChunked = 200, kFormSelfRows = 300;
+constexpr int kFormCrossMfma = 400, kFormCrossTiled = 500, kFormCrossLds = 600;
+
+static int decode_self_form(int t, int W, int rows, int h, int dk, bool per_row) {
+    if (t < 0 || t >= OVC_MAX_LEN || h <= 0 || h > kSelfMaxHeads) return OVC_EINVAL;
+    if ((dk & (dk - 1)) || dk < 4 || dk > 64) return OVC_EINVAL;                            // dk in {4,8,16,32,64}
+    const int hk = h * dk;
+    if (hk > 1024) return OVC_EINVAL;
+    const bool per_image = !per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && dk >= 16;
+    const int SB = dk >> 4, CH = hk <= 256 ? 1 : hk <= 512 ? 2 : 4;
+    if (t >= 64) {
+        if (per_image) return kFormSelfChunked + (W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : W <= 5 ? 5 : 8) * 10 + SB;
+        return kFormSelfRows + CH * 10 + 4;
+    }
+    // per-image kernel with ancestor de-duplication: the image's rows in one workgroup, at most 112 listed keys
+    const int worst = t == 0 ? 1 : W * (t + 1);
+    if (per_image && worst <= 112) {
+        const int tiles = (worst + 15) / 16;
+        return kFormSelfMfma + (tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 4 ? 4 : 7) * 10 + SB;
+    }
+    return kFormSelfRows + CH * 10 + 1;
+}
+
+static int decode_self_attention_as(const DecodeSelfArgs& p, int rows, bool per_row, hipStream_t stream, const int32_t* gate) {
+    if (p.dk != p.dv) return OVC_EINVAL;
+    const int form = decode_self_form(p.t, p.width, rows, p.h, p.dk, per_row);
+    if (form < 0) return form;
+    const int W = p.width;
+    const bool chunked = form >= kFormSelfChunked && form < kFormSelfRows;
+    if (chunked && (!p.part_o || !p.part_ml)) return OVC_EINVAL;
+    const int chunks = (p.t + kSelfChunk) / kSelfChunk;
+    switch (form) {
 #define OVC_SELF(NT, SB)                                                                                             \
-    do {                                                                                                             \
+    case kFormSelfMfma + NT * 10 + SB: {                                                                             \
+        const dim3 grid(rows / W, (p.h + 3) / 4), block(256);                                                        \
+        if (gate) hipLaunchKernelGGL((decode_self_attention_mfma_kernel_gated<NT, SB>), grid, block, 0, stream, p, gate); \
+        else hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p);            \
+    } break
+#define OVC_SELF_CHUNKED(NT, SB)                                                                                     \
+    case kFormSelfChunked + NT * 10 + SB: {                                                                          \
+        const dim3 grid(rows / W, (p.h + 3) / 4, chunks), block(256);                                                \
         if (gate) hipLaunchKernelGGL((decode_self_attention_mfma_kernel_gated<NT, SB, true>), grid, block, 0, stream, p, gate); \
         else hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB, true>), grid, block, 0, stream, p);      \
-    } while (0)
-#define OVC_SELF_NT(SB)                                                                                             \
-    do {                                                                                                            \
-        if (W <= 1) OVC_SELF(1, SB); else if (W <= 2) OVC_SELF(2, SB); else if (W <= 4) OVC_SELF(4, SB);           \
-        else if (W <= 5) OVC_SELF(5, SB); else OVC_SELF(8, SB);                                                     \
-    } while (0)
-        if (p.dk == 64) OVC_SELF_NT(4); else if (p.dk == 32) OVC_SELF_NT(2); else OVC_SELF_NT(1);
-#undef OVC_SELF_NT
+    } break
+#define OVC_SELF_ROWS(CH, KB)                                                                                        \
+    case kFormSelfRows + CH * 10 + KB:                                                                               \
+        if (gate) hipLaunchKernelGGL((decode_self_attention_kernel_gated<CH, KB>), dim3(rows), dim3(256), 0, stream, p, gate); \
+        else hipLaunchKernelGGL((decode_self_attention_kernel<CH, KB>), dim3(rows), dim3(256), 0, stream, p);       \
+        break
+#define OVC_SELF_SB(M, NT) M(NT, 1); M(NT, 2); M(NT, 4)
+        OVC_SELF_SB(OVC_SELF, 1); OVC_SELF_SB(OVC_SELF, 2); OVC_SELF_SB(OVC_SELF, 4); OVC_SELF_SB(OVC_SELF, 7);
+        OVC_SELF_SB(OVC_SELF_CHUNKED, 1); OVC_SELF_SB(OVC_SELF_CHUNKED, 2); OVC_SELF_SB(OVC_SELF_CHUNKED, 4);
+        OVC_SELF_SB(OVC_SELF_CHUNKED, 5); OVC_SELF_SB(OVC_SELF_CHUNKED, 8);
+        OVC_SELF_ROWS(1, 1); OVC_SELF_ROWS(2, 1); OVC_SELF_ROWS(4, 1);
+        OVC_SELF_ROWS(1, 4); OVC_SELF_ROWS(2, 4); OVC_SELF_ROWS(4, 4);
+#undef OVC_SELF_SB
+#undef OVC_SELF_ROWS
+#undef OVC_SELF_CHUNKED
 #undef OVC_SELF
-        OVC_RETURN_IF_LAUNCH_FAILED();
+        default: return OVC_EINVAL;
+    }
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    if (chunked) {                                         // the chunks' partials -> out
         const int threads = rows * ((p.h * p.dv) >> 2);
         if (gate) hipLaunchKernelGGL(decode_self_merge_kernel_gated, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks, gate);
         else hipLaunchKernelGGL(decode_self_merge_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, p, rows, chunks);
         OVC_RETURN_IF_LAUNCH_FAILED();
-        return OVC_OK;
     }
-    if (gate) {
-        if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel_gated<1, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
-        else if (hk <= 512) hipLaunchKernelGGL((decode_self_attention_kernel_gated<2, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
-        else hipLaunchKernelGGL((decode_self_attention_kernel_gated<4, 4>), dim3(rows), dim3(256), 0, stream, p, gate);
-    } else if (hk <= 256) hipLaunchKernelGGL((decode_self_attention_kernel<1, 4>), dim3(rows), dim3(256), 0, stream, p);
-    else if (hk <= 512) hipLaunchKernelGGL((decode_self_attention_kernel<2, 4>), dim3(rows), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((decode_self_attention_kernel<4, 4>), dim3(rows), dim3(256), 0, stream, p);
-    OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
 
 int ovc_decode_self_attention(const DecodeSelfArgs& p, int rows, hipStream_t stream, const int32_t* gate) {
-    const int hk = p.h * p.dk;
-    if (p.t < 0 || p.t >= OVC_MAX_LEN || p.h <= 0 || p.h > kSelfMaxHeads) return OVC_EINVAL;
-    if (p.dk != p.dv || (p.dk & (p.dk - 1)) || p.dk < 4 || p.dk > 64) return OVC_EINVAL;   // dk in {4,8,16,32,64}
-    if (hk > 1024) return OVC_EINVAL;
     static const bool per_row = OVC_HOOK_ENV("OVC_SELF_ATTENTION_ROWS") != nullptr;     // A/B switch: the round-1 per-row kernel
-    const int W = p.width;
-    if (p.t >= 64) return decode_self_attention_long(p, rows, per_row, stream, gate);
-    // per-image kernel with ancestor de-duplication: the image's rows in one workgroup, at most 112 listed keys
-    if (!per_row && W >= 1 && W <= OVC_MAX_BEAM && rows % W == 0 && p.dk >= 16 && (p.t == 0 ? 1 : W * (p.t + 1)) <= 112) {
-        const int worst = p.t == 0 ? 1 : W * (p.t + 1), tiles = (worst + 15) / 16;
-        const dim3 grid(rows / W, (p.h + 3) / 4), block(256);
-#define OVC_SELF(NT, SB)                                                                                             \
-    do {                                                                                                             \
-        if (gate) hipLaunchKernelGGL((decode_self_attention_mfma_kernel_gated<NT, SB>), grid, block, 0, stream, p, gate); \
-        else hipLaunchKernelGGL((decode_self_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p);            \
-    } while (0)
-#define OVC_SELF_NT(SB)                                                                                             \
-    do {                                                                                                            \
-        if (tiles <= 1) OVC_SELF(1, SB); else if (tiles <= 2) OVC_SELF(2, SB); else if (tiles <= 4) OVC_SELF(4, SB); \
-        else OVC_SELF(7, SB);                                                                                       \
-    } while (0)
-        if (p.dk == 64) OVC_SELF_NT(4); else if (p.dk == 32) OVC_SELF_NT(2); else OVC_SELF_NT(1);
-#undef OVC_SELF_NT
-#undef OVC_SELF
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        return OVC_OK;
-    }
-    if (gate) {
-        if (hk <= 256) hipLaunchKernelGGL(decode_self_attention_kernel_gated<1>, dim3(rows), dim3(256), 0, stream, p, gate);
-        else if (hk <= 512) hipLaunchKernelGGL(decode_self_attention_kernel_gated<2>, dim3(rows), dim3(256), 0, stream, p, gate);
-        else hipLaunchKernelGGL(decode_self_attention_kernel_gated<4>, dim3(rows), dim3(256), 0, stream, p, gate);
-    } else if (hk <= 256) hipLaunchKernelGGL(decode_self_attention_kernel<1>, dim3(rows), dim3(256), 0, stream, p);
-    else if (hk <= 512) hipLaunchKernelGGL(decode_self_attention_kernel<2>, dim3(rows), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(decode_self_attention_kernel<4>, dim3(rows), dim3(256), 0, stream, p);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    return OVC_OK;
+    return decode_self_attention_as(p, rows, per_row, stream, gate);
 }
 
 // Decode cross-attention: the k beams of an image share the image's projected encoder K/V.
@@ -785,7 +792,8 @@ __global__ __launch_bounds__(256) void decode_cross_attention_tiled_kernel_gated
 // Head sizes 4 and 8 (not multiples of the 16-deep MFMA k block): VALU dots on LDS-staged rows.  The scores of all N keys
 // stay in LDS; K and then V of the (image, head) pass through in chunks of 128 rows, ascending, so any region count fits
 // (round 4) and the sums keep the key order of the one-shot form.
-// Exercised by tests/test_engine_gpu.py::test_unusual_dimensions_against_oracle (d_k = 8 and d_k = 4 cases).
+// Exercised by tests/test_engine_gpu.py::test_unusual_dimensions_against_oracle (d_k = 8 and d_k = 4 cases) and, against fp64 at
+// the operator level with every other decode attention instance, by tests/test_decode_attention_gpu.py.
 constexpr int kCrossChunk = 128;
 
 __global__ __launch_bounds__(256) void decode_cross_attention_lds_kernel(DecodeCrossArgs p) {
@@ -796,45 +804,127 @@ __global__ __launch_bounds__(256) void decode_cross_attention_lds_kernel_gated(D
 #include "bodies/decode_cross_attention_lds_kernel.inc"
 }
 
+// Which instance a decode cross-attention launch takes (shared with ovc_debug_decode_cross_form; the coding continues the
+// self-attention's): 4 NT SB = decode_cross_attention_mfma_kernel<NT, SB> (N <= 64: NT = 4, N <= 128: NT = 8),
+// 5 0 SB = decode_cross_attention_tiled_kernel<SB> (N > 128), 6 0 0 = decode_cross_attention_lds_kernel (d_k not 16 / 32 / 64).
+static int decode_cross_form(int N, int W, int dk, int dv) {
+    if (N <= 0 || N > OVC_MAX_REGIONS || W <= 0 || W > OVC_MAX_BEAM) return OVC_EINVAL;
+    if (dk > 64 || dv > 64 || dk <= 0 || dv <= 0 || (dk & 3) || (dv & 3)) return OVC_EINVAL;
+    if (dk == 16 || dk == 32 || dk == 64) {
+        const int SB = dk >> 4;
+        if (N > 128) return kFormCrossTiled + SB;   // more regions than the register-resident instances hold: key chunks + online softmax
+        return kFormCrossMfma + (N <= 64 ? 4 : 8) * 10 + SB;
+    }
+    return kFormCrossLds;
+}
+
 int ovc_decode_cross_attention(const DecodeCrossArgs& p, int B, int h, int levels, hipStream_t stream, const int32_t* gate) {
-    if (p.n <= 0 || p.n > OVC_MAX_REGIONS || p.width <= 0 || p.width > OVC_MAX_BEAM) return OVC_EINVAL;
-    if (p.dk > 64 || p.dv > 64 || (p.dk & 3) || (p.dv & 3) || p.heads != h) return OVC_EINVAL;
-    if (p.dk == 16 || p.dk == 32 || p.dk == 64) {
-        const dim3 grid(B, (h + 3) / 4, levels), block(256);
-        if (p.n > 128) {        // more regions than the register-resident instances hold: key chunks + online softmax
-            if (gate) {
-                if (p.dk == 64) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<4>, grid, block, 0, stream, p, gate);
-                else if (p.dk == 32) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<2>, grid, block, 0, stream, p, gate);
-                else hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<1>, grid, block, 0, stream, p, gate);
-            } else if (p.dk == 64) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<4>, grid, block, 0, stream, p);
-            else if (p.dk == 32) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<2>, grid, block, 0, stream, p);
-            else hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<1>, grid, block, 0, stream, p);
-            OVC_RETURN_IF_LAUNCH_FAILED();
-            return OVC_OK;
-        }
-        const bool small = p.n <= 64;
+    if (p.heads != h) return OVC_EINVAL;
+    const int form = decode_cross_form(p.n, p.width, p.dk, p.dv);
+    if (form < 0) return form;
+    const dim3 grid(B, (h + 3) / 4, levels), block(256);
+    switch (form) {
 #define OVC_CROSS(NT, SB)                                                                                            \
-    do {                                                                                                             \
+    case kFormCrossMfma + NT * 10 + SB:                                                                              \
         if (gate) hipLaunchKernelGGL((decode_cross_attention_mfma_kernel_gated<NT, SB>), grid, block, 0, stream, p, gate); \
         else hipLaunchKernelGGL((decode_cross_attention_mfma_kernel<NT, SB>), grid, block, 0, stream, p);           \
-    } while (0)
-        if (p.dk == 64) { if (small) OVC_CROSS(4, 4); else OVC_CROSS(8, 4); }
-        else if (p.dk == 32) { if (small) OVC_CROSS(4, 2); else OVC_CROSS(8, 2); }
-        else { if (small) OVC_CROSS(4, 1); else OVC_CROSS(8, 1); }
+        break
+#define OVC_CROSS_TILED(SB)                                                                                          \
+    case kFormCrossTiled + SB:                                                                                       \
+        if (gate) hipLaunchKernelGGL(decode_cross_attention_tiled_kernel_gated<SB>, grid, block, 0, stream, p, gate); \
+        else hipLaunchKernelGGL(decode_cross_attention_tiled_kernel<SB>, grid, block, 0, stream, p);                \
+        break
+        OVC_CROSS(4, 1); OVC_CROSS(4, 2); OVC_CROSS(4, 4); OVC_CROSS(8, 1); OVC_CROSS(8, 2); OVC_CROSS(8, 4);
+        OVC_CROSS_TILED(1); OVC_CROSS_TILED(2); OVC_CROSS_TILED(4);
+#undef OVC_CROSS_TILED
 #undef OVC_CROSS
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        return OVC_OK;
+        case kFormCrossLds: {
+            const size_t lds_bytes = sizeof(float) * ((size_t)kCrossChunk * kLdQK + (size_t)p.width * 64 + (size_t)p.width * p.n);
+            static std::once_flag attr_once;
+            std::call_once(attr_once, [] {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel_gated),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            });
+            if (gate) hipLaunchKernelGGL(decode_cross_attention_lds_kernel_gated, dim3(B, h, levels), dim3(256), lds_bytes, stream, p, gate);
+            else hipLaunchKernelGGL(decode_cross_attention_lds_kernel, dim3(B, h, levels), dim3(256), lds_bytes, stream, p);
+        } break;
+        default: return OVC_EINVAL;
     }
-    const size_t lds_bytes = sizeof(float) * ((size_t)kCrossChunk * kLdQK + (size_t)p.width * 64 + (size_t)p.width * p.n);
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_cross_attention_lds_kernel_gated),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if (gate) hipLaunchKernelGGL(decode_cross_attention_lds_kernel_gated, dim3(B, h, levels), dim3(256), lds_bytes, stream, p, gate);
-    else hipLaunchKernelGGL(decode_cross_attention_lds_kernel, dim3(B, h, levels), dim3(256), lds_bytes, stream, p);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+// =================================================================================================
+// Test hooks: the two launchers above on caller buffers, and the instance each launch takes (include/ovc.h)
+// =================================================================================================
+// What the engine's model_ok / heads_ok never send is OVC_EINVAL here, with nothing launched.
+static bool debug_heads_ok(int h, int dk) {
+    return (dk == 4 || dk == 8 || dk == 16 || dk == 32 || dk == 64) && h >= 1 && h <= kSelfMaxHeads && h * dk <= 1024;
+}
+static bool debug_self_shape_ok(int t, int W, int rows, int h, int dk) {
+    return debug_heads_ok(h, dk) && t >= 0 && t < OVC_MAX_LEN && W >= 1 && W <= OVC_MAX_BEAM && rows >= 1 && rows % W == 0 &&
+           (t > 0 || W == 1);                                   // position 0 holds one slot per image: width_0 = 1
+}
+static bool debug_cross_shape_ok(int N, int W, int h, int dk) {
+    return debug_heads_ok(h, dk) && N >= 1 && N <= OVC_MAX_REGIONS && W >= 1 && W <= OVC_MAX_BEAM;
+}
+
+extern "C" int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row) {
+    if (!debug_self_shape_ok(t, width, rows, h, d_k)) return OVC_EINVAL;
+    return decode_self_form(t, width, rows, h, d_k, per_row != 0);
+}
+
+extern "C" int ovc_debug_decode_cross_form(int N, int width, int h, int d_k) {
+    if (!debug_cross_shape_ok(N, width, h, d_k)) return OVC_EINVAL;
+    return decode_cross_form(N, width, d_k, d_k);
+}
+
+extern "C" size_t ovc_debug_decode_self_partial_bytes(int t, int rows, int h, int d_k) {
+    if (t < 64 || t >= OVC_MAX_LEN || rows < 1 || !debug_heads_ok(h, d_k)) return 0;
+    const size_t chunks = (size_t)(t + kSelfChunk) / kSelfChunk;
+    return sizeof(float) * chunks * rows * ((size_t)h * d_k + 2 * (size_t)h);      // part_o, then part_ml
+}
+
+extern "C" int ovc_debug_decode_self_attention(const float* q, int ldq, const float* kcache, const float* vcache, size_t pos_stride,
+                                               int ldkv, const int32_t* anc, int anc_ld, const uint8_t* padflag, int pad_ld, int t,
+                                               int width, int rows, int h, int d_k, float* out, int ldo, void* partials,
+                                               size_t partial_bytes, const int32_t* gate, int per_row, ovc_stream stream) {
+    if (!q || !kcache || !vcache || !padflag || !out || (t > 0 && !anc)) return OVC_EINVAL;
+    if (!debug_self_shape_ok(t, width, rows, h, d_k)) return OVC_EINVAL;
+    const int hk = h * d_k;
+    if (ldq < hk || ldkv < hk || ldo < hk || (ldq & 3) || (ldkv & 3) || (ldo & 3) || (pos_stride & 3)) return OVC_EINVAL;
+    if (anc_ld < t || pad_ld < rows) return OVC_EINVAL;
+    if (!ovc_aligned16(q) || !ovc_aligned16(kcache) || !ovc_aligned16(vcache) || !ovc_aligned16(out)) return OVC_EINVAL;
+    const size_t need = ovc_debug_decode_self_partial_bytes(t, rows, h, d_k);
+    if (need && (!partials || !ovc_aligned16(partials) || partial_bytes < need)) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    DecodeSelfArgs p{};
+    p.q = q; p.ldq = ldq; p.kcache = kcache; p.vcache = vcache; p.pos_stride = pos_stride; p.ldkv = ldkv;
+    p.anc = anc; p.anc_ld = anc_ld; p.padflag = padflag; p.pad_ld = pad_ld;
+    p.t = t; p.width = width; p.h = h; p.dk = d_k; p.dv = d_k;
+    p.out = out; p.ldo = ldo;
+    if (need) {
+        const size_t chunks = (size_t)(t + kSelfChunk) / kSelfChunk;
+        p.part_o = static_cast<float*>(partials);
+        p.part_ml = p.part_o + chunks * rows * hk;
+    }
+    return decode_self_attention_as(p, rows, per_row != 0, ovc_hip_stream(stream), gate);
+}
+
+extern "C" int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, const float* vx, size_t level_stride, int ldkv,
+                                                const uint8_t* encmask, int N, int width, int B, int heads, int d_k, int levels,
+                                                float* out, size_t out_level_stride, int ldo, const int32_t* gate, ovc_stream stream) {
+    if (!q || !kx || !vx || !out || B < 1 || levels < 1 || levels > OVC_MAX_LEVELS) return OVC_EINVAL;
+    if (!debug_cross_shape_ok(N, width, heads, d_k)) return OVC_EINVAL;
+    const int hk = heads * d_k;
+    if (ldq < hk || ldkv < hk || ldo < hk || (ldq & 3) || (ldkv & 3) || (ldo & 3) || (level_stride & 3) || (out_level_stride & 3)) return OVC_EINVAL;
+    if (!ovc_aligned16(q) || !ovc_aligned16(kx) || !ovc_aligned16(vx) || !ovc_aligned16(out)) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    DecodeCrossArgs p{};
+    p.q = q; p.ldq = ldq; p.kx = kx; p.vx = vx; p.level_stride = level_stride; p.ldkv = ldkv;
+    p.encmask = encmask; p.n = N; p.width = width; p.heads = heads; p.dk = d_k; p.dv = d_k;
+    p.out = out; p.out_level_stride = out_level_stride; p.ldo = ldo;
+    return ovc_decode_cross_attention(p, B, heads, levels, ovc_hip_stream(stream), gate);
 }

@@ -208,6 +208,14 @@ SIGNATURES = {
     "ovc_scst_advantage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ovc_caption_metrics_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ovc_caption_metrics": (c_int, [POINTER(EvalCorpus), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ovc_debug_decode_self_partial_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ovc_debug_decode_self_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                                c_int, c_void_p]),
+    "ovc_debug_decode_cross_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_int,
+                                                 c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "ovc_debug_decode_self_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "ovc_debug_decode_cross_form": (c_int, [c_int, c_int, c_int, c_int]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -223,7 +231,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_grad_norm", "ovc_train_smoothed_workspace_bytes", "ovc_forward_backward_smoothed",
                  "ovc_sample_workspace_bytes", "ovc_sample", "ovc_sample_graph",
                  "ovc_sample_shaped_workspace_bytes", "ovc_sample_shaped", "ovc_sample_shaped_graph",
-                 "ovc_sample_choice_workspace_bytes", "ovc_sample_choice")
+                 "ovc_sample_choice_workspace_bytes", "ovc_sample_choice",
+                 "ovc_debug_decode_self_partial_bytes", "ovc_debug_decode_self_attention", "ovc_debug_decode_cross_attention",
+                 "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form")
 
 _lib = None
 

@@ -560,6 +560,47 @@ int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, 
                       int top_k, float top_p, void* workspace, size_t workspace_bytes, int32_t* word_out, int32_t* kept_out,
                       ovc_stream stream);
 
+/* Constrained beam search: the search of ovc_beam_search with words banned per beam row and step (appended to ABI 8; no struct
+ * changes).  The rule (openviic_amd/constraints.py mirrors it in numpy):
+ * Options.  no_repeat_ngram = n (0: off), min_length = L (0: off), banned: n_banned <= OVC_MAX_BANNED word ids in HOST memory
+ * (0: off), copied by value into every launch.
+ * At decode step t (0-based) a LIVE beam row has the history h[0..t-1]: its words of steps 0..t-1 (<bos> is not among them).  Word
+ * w is banned for that row iff
+ *   - w is one of the banned ids, or
+ *   - w == <eos> and t < L, or
+ *   - n >= 1, t >= n - 1 and some j in 0..t-n has h[j..j+n-2] == h[t-n+1..t-1] and h[j+n-1] == w (n = 1: every word of h).
+ * A banned word's candidate score is -inf: it is never selected.  Everything else is ovc_beam_search, bit for bit: candidates
+ * run + ((x - M) - ls) with M and ls of the UNMODIFIED row (the ban applies after the log-softmax), score descending with ties to
+ * the lower flat index row * V + w, a frozen beam's offers (word 0 at its running score, -999 for the others; never banned), NaN
+ * rows, the final ordering and out_size.  logp_out / all_logp_out stay the model's own log-probabilities, so
+ * ovc_sequence_backward recomputes them unchanged.
+ * Neutral options (0, 0, none) are ovc_beam_search / ovc_beam_search_graph: the same launches, graph entry and bits.
+ * ovc_beam_search_constrained: plain launches, all_logp_out as ovc_beam_search.  ovc_beam_search_constrained_graph: one captured
+ * graph from the second call; n, L and the sorted ids are part of its key.  Workspace: ovc_workspace_bytes.
+ * OVC_EINVAL, nothing launched: n < 0 or > OVC_MAX_LEN; L < 0 or > max_len - 1; more than OVC_MAX_BANNED ids, an id outside
+ * [0, V), a duplicate, <pad> or <eos> (min_length keeps <eos> out); V - n_banned - 1 - max_len < k (so that every live row keeps k
+ * finite candidates at every step); precision != 0; a vocabulary of more than 16 384 words; and everything ovc_beam_search
+ * refuses.  ovc_search_constraints_ok: 1 when (m, k, options) is in this scope, else 0; launches nothing.
+ * Not covered: length penalty or normalisation, repetition penalty, forced or prefix-constrained decoding, diverse beam search,
+ * more than OVC_MAX_BANNED ids, constraints under dropout, in the early-exit forms, in the split-precision modes or when sampling.
+ * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel on caller-given device inputs -- row-major
+ * logits [B*width][V], hist [B*width][T] (int32, steps 0..t-1 read), running / alive [B*width]; width = 1 iff t = 0, else k.  The
+ * entry forms the block pieces and the transposed logits itself.  parent_out / word_out [B][k] int32 (the beam inside the image,
+ * the word), running_out [B][k], row_max_out / row_lsum_out [B*width]: M and ls.  scratch: ovc_debug_beam_constrained_update_bytes. */
+#define OVC_MAX_BANNED 16
+int ovc_search_constraints_ok(const ovc_model* m, int k, int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned);
+int ovc_beam_search_constrained(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, void* workspace,
+                                size_t workspace_bytes, int64_t* ids_out, float* logp_out, float* all_logp_out, ovc_stream stream);
+int ovc_beam_search_constrained_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                      int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, void* workspace,
+                                      size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream);
+size_t ovc_debug_beam_constrained_update_bytes(int B, int width, int V, int k, int T);
+int ovc_debug_beam_constrained_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B, int width,
+                                      int V, int k, int T, int t, int eos, int no_repeat_ngram, int min_length, const int32_t* banned,
+                                      int n_banned, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
+                                      float* running_out, float* row_max_out, float* row_lsum_out, ovc_stream stream);
+
 /* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
  * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host
  * (openviic_amd/cider.py) in float64.  An n-gram (n = 1..4) of word ids below 65535 is ONE 64-bit key: word j of the n-gram sits as

@@ -16,6 +16,7 @@ import collections
 
 import torch
 
+from . import constraints as _constraints
 from . import dropout as _dropout
 from . import engine
 from .builders.decoder_builder import build_decoder
@@ -32,6 +33,13 @@ ScstStep = collections.namedtuple("ScstStep", ["loss", "reward_mean", "baseline_
 ScstStep.__doc__ = """What ``BaseTransformer.scst_step`` returns: detached device tensors.  ``loss``, ``reward_mean`` and
 ``baseline_mean`` are 0-dim views of one ``stats`` tensor (``openviic_amd.scst.advantage``), ``outs`` ``[B, k, T]`` int64 the
 search's sequences, ``reward`` ``[B, k]`` float32 their rewards."""
+
+
+def _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
+    """``(n, L, banned)`` as the caller gave them when any differs from its default (checked later, by the engine), else None."""
+    given = (no_repeat_ngram_size not in (0, None) or isinstance(no_repeat_ngram_size, bool) or
+             min_length not in (0, None) or isinstance(min_length, bool) or (banned_words is not None and len(banned_words) > 0))
+    return (no_repeat_ngram_size, min_length, banned_words) if given else None
 
 
 def _checked_step_optimizer(optimizer, what, eng=None):
@@ -286,7 +294,8 @@ class BaseTransformer(Module):
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
-                  max_norm=None, sample=False, temperature=1.0, top_k=None, top_p=None):
+                  max_norm=None, sample=False, temperature=1.0, top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0,
+                  banned_words=None):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -325,7 +334,13 @@ class BaseTransformer(Module):
 
         ``p.grad`` is neither read nor written, and autograd is not involved (the call works under ``torch.no_grad()``): gradient
         hooks do NOT fire -- ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them
-        DistributedDataParallel's gradient all-reduce.  A data-parallel run keeps the lines above."""
+        DistributedDataParallel's gradient all-reduce.  A data-parallel run keeps the lines above.
+
+        ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``beam_search``'s; anything but their defaults is refused by
+        name before any launch or draw (a constrained search inside ``scst_step`` is out of scope: run the lines above)."""
+        if _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
+            raise engine.native.OvcError("scst_step(no_repeat_ngram_size / min_length / banned_words): a constrained search inside "
+                                         "scst_step is out of scope -- call beam_search with them and backpropagate its log_probs")
         from . import optim as _optim
         from . import scst as _scst
         from .cider import CiderCorpus
@@ -408,7 +423,7 @@ class BaseTransformer(Module):
         return probs
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
-                    fused=True, dropout=False, generator=None, **kwargs):
+                    fused=True, dropout=False, generator=None, no_repeat_ngram_size=0, min_length=0, banned_words=None, **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
 
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
@@ -426,15 +441,34 @@ class BaseTransformer(Module):
         ``p == 0`` this is the plain call: same bits, no random draw.  Anything outside the scope is refused here, before any
         launch or draw, naming the module; so is ``return_probs`` together with a live dropout (the masked search has no
         ``return_probs`` form).  ``early_exit=`` selects the search form as without dropout.
+
+        ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words`` (fused only; ``ovc_beam_search_constrained``, DESIGN.md section
+        2s; the rule is stated in ``include/ovc.h`` and mirrored by ``openviic_amd.constraints``): no n-gram of a caption repeats,
+        ``<eos>`` is not emitted before step ``min_length``, and the at most 16 ``banned_words`` ids are never emitted.  The ban
+        applies after the log-softmax: ``log_probs`` / ``all_log_probs`` stay the model's own, so the gradient of ``log_probs``
+        is the plain search's.  The defaults are the plain call, bit for bit.  Refused by name before any launch or draw: a bad
+        option; active constraints with ``fused=False``, ``dropout=True``, an early-exit form, a precision other than 'f32' or a
+        vocabulary of more than 16 384 words; and length penalty, repetition penalty, forced or prefix-constrained decoding and
+        diverse beam search, which the engine does not have.
         """
+        _constraints.refuse_out_of_scope(kwargs, "beam_search")
+        constraints = _requested_constraints(no_repeat_ngram_size, min_length, banned_words)
+        if constraints and not fused:
+            raise engine.native.OvcError("beam_search(no_repeat_ngram_size / min_length / banned_words) needs fused=True: the host "
+                                         "loop has no ban set")
+        if constraints and dropout:
+            raise engine.native.OvcError("beam_search(no_repeat_ngram_size / min_length / banned_words): dropout=True is not covered "
+                                         "-- constraints under dropout are out of scope")
         if dropout and not fused:
             raise engine.native.OvcError("beam_search(dropout=True) needs fused=True: the host loop has no dropout site table")
         if fused:
+            if constraints:      # every refusal of the options, before any launch and any draw
+                constraints = self._fused_engine().check_constraints(beam_size, constraints, kwargs.get("early_exit"))
             probs = self._search_dropout_probs() if dropout else None
             if probs and return_probs:
                 raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
             ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
-                                                              return_probs, kwargs.get("early_exit"))
+                                                              return_probs, kwargs.get("early_exit"), constraints=constraints)
             logp = self._scst_log_probs(input_features, ids, logp, recompute)
             if out_size == 1:
                 ids, logp = ids.squeeze(1), logp.squeeze(1)
@@ -446,7 +480,7 @@ class BaseTransformer(Module):
             return searcher.apply(out_size, return_probs, **kwargs)
 
     def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False, temperature=1.0,
-               top_k=None, top_p=None):
+               top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0, banned_words=None):
         """``n_samples`` captions per image drawn from the model's own distribution, on the HIP engine (``ovc_sample``; the rule
         is stated in ``include/ovc.h`` and mirrored by ``openviic_amd.sampling``): ``(ids [B, S, T] int64, log_probs [B, S, T])``
         in sample order, plus ``all_log_probs [B, S, T, V]`` with ``return_probs=True``.  After a caption's first ``<eos>`` every
@@ -467,7 +501,11 @@ class BaseTransformer(Module):
         reaches ``top_p`` of their mass.  ``log_probs`` and ``all_log_probs`` stay the MODEL's log-probabilities, neither tempered
         nor renormalised, so the backward is unchanged and a loss on shaped samples is the usual off-policy surrogate.  ``top_k=1``
         is the greedy decode; neutral options are the call without them, bit for bit.  A bad option is refused by name before any
-        launch and any draw."""
+        launch and any draw.  ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words`` are the beam search's: anything but
+        their defaults is refused by name (constraints when sampling are out of scope)."""
+        if _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
+            raise engine.native.OvcError("sample(no_repeat_ngram_size / min_length / banned_words): constraints when sampling are "
+                                         "out of scope -- they shape beam_search only")
         checked = self._fused_engine().check_sample(n_samples, temperature, top_k, top_p)
         ids, logp, everything, recompute = self._generate(input_features, batch_size, n_samples, generator=generator,
                                                           return_probs=return_probs, checked=checked)
@@ -475,13 +513,14 @@ class BaseTransformer(Module):
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     def _generate(self, input_features, batch_size, width, out_size=None, probs=None, generator=None, return_probs=False,
-                  early_exit=None, checked=None):
+                  early_exit=None, checked=None, constraints=None):
         """One fused generation, for ``beam_search``, ``sample`` and ``scst_step``: ``width`` beams of which the best ``out_size``
         are returned -- with ``probs`` (what ``_search_dropout_probs`` returned, not empty) under this call's dropout masks -- or,
         with ``out_size=None``, ``width`` samples under the sampler's options (``checked``: what ``check_sample`` returned).  The masks' or the samples' seed is drawn here, one per call; plain beams draw
         nothing.  Returns ``(ids, log_probs, all_log_probs, recompute)``: the first two unsqueezed ``(B, out_size, T)``, the third
         None without ``return_probs``, the last the keyword arguments under which ``sequence_backward`` recomputes these
-        log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``)."""
+        log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``).  ``constraints``: the beam
+        search's ``(n, L, banned)`` as ``check_constraints`` returned them, or None."""
         eng = self._fused_engine()
         feats, boxes = self._engine_inputs(input_features)
         recompute = {}
@@ -494,7 +533,8 @@ class BaseTransformer(Module):
             *out, slots = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, early_exit=early_exit, dropout=drop)
             recompute = dict(dropout=drop, slots=slots, beam_size=width)
         else:
-            out = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, return_probs=return_probs, early_exit=early_exit)
+            out = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, return_probs=return_probs, early_exit=early_exit,
+                                  constraints=constraints)
         ids, logp = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in out[:2])       # out_size = 1: the engine squeezed them
         return ids, logp, out[2] if return_probs else None, recompute
 

@@ -222,6 +222,40 @@ __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel_gated(
 #include "bodies/beam_fused_update.inc"
 }
 
+// Constrained selection (ovc_beam_search_constrained, include/ovc.h: the rule): the fused selection and bookkeeping of one image
+// with a per-row ban set -- the call's banned ids, <eos> before the minimum length, the words that would complete a repeated
+// n-gram of the row's own history.  The set lives in LDS as one bit per (row, word), built by the row's wave before phase A; a
+// 32-bit word of the bitmap is one 32-word block of the vocabulary, so a block is "dirty" iff its word is non-zero.  The pieces
+// (M, ls) and every candidate's arithmetic are the plain kernel's; a dirty block keeps its upper bound but feeds no lower bound,
+// and a word whose bit is set is skipped by the hot-block pass and the exhaustive path.  LDS: the plain body's 14 KB + 16 KB
+// bitmap + 8 KB staged histories = 38 KB of the workgroup's 64 KB (static: the compiler refuses more).
+constexpr int kBanWords = 512;                           // 32 words each: V <= 16 384, the fused tail's 512 blocks
+static_assert(kBanWords == 512 && OVC_MAX_BANNED <= 64, "one bitmap word per block of the fused tail, one lane per banned id");
+
+__global__ __launch_bounds__(kFusedThreads) void beam_constrained_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                                int stats_ld, const float* __restrict__ running_in,
+                                                                                long ld_row, long ld_word, BeamConstraints cons) {
+#include "bodies/beam_constrained_update.inc"
+}
+
+// The block pieces of row-major logits [rows][V] as the vocabulary product's epilogue leaves them -- per (row, 32-word block) the
+// maximum and sum exp(x - maximum) -- and the logits laid out transposed, the engine's form (ovc_debug_beam_constrained_update).
+// One wave per (row, block pair group): lane l < 32 holds word l of the block.
+__global__ __launch_bounds__(64) void block_pieces_kernel(const float* __restrict__ x, int rows, int V, int nblk, int stats_ld, int ldt,
+                                                          float* __restrict__ stats, float* __restrict__ logits_t) {
+    const int row = blockIdx.y, blk = blockIdx.x * 2 + (threadIdx.x >> 5), l = threadIdx.x & 31, w = blk * 32 + l;
+    const bool in = blk < nblk && w < V;
+    const float v = in ? x[(size_t)row * V + w] : -INFINITY;
+    if (in) logits_t[(size_t)w * ldt + row] = v;
+    float m = v;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    float e = in ? __expf(v - m) : 0.f;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
+    if (l == 0 && blk < nblk) { stats[2 * ((size_t)row * stats_ld + blk)] = m; stats[2 * ((size_t)row * stats_ld + blk) + 1] = e; }
+}
+
 // masked_logp[row, c] = ((x - row_max) - row_lsum) * alive for every word (return_probs; beam_search.py:68-72) from the
 // row pieces beam_fused_update_kernel published -- the values its decisions were taken on.
 __global__ __launch_bounds__(256) void masked_logp_kernel(const float* __restrict__ logits, long ld_row, long ld_word,
@@ -395,6 +429,41 @@ int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, in
     return OVC_OK;
 }
 
+bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k, int eos, int pad) {
+    if (c.ngram < 0 || c.ngram > OVC_MAX_LEN || c.min_length < 0 || c.min_length > max_len - 1) return false;
+    if (c.n_banned < 0 || c.n_banned > OVC_MAX_BANNED) return false;
+    for (int i = 0; i < c.n_banned; ++i) {
+        if (c.banned[i] < 0 || c.banned[i] >= V || c.banned[i] == pad || c.banned[i] == eos) return false;
+        for (int j = 0; j < i; ++j) if (c.banned[j] == c.banned[i]) return false;
+    }
+    // every live row keeps k finite candidates at every step: the banned ids, <eos> and at most max_len history words are out
+    return (long)V - c.n_banned - 1 - max_len >= k;
+}
+
+// The constrained step: ovc_beam_fused_update_launch's arguments plus the constraints, by value (baked into a captured graph).
+// No gated instance: the early-exit forms are out of the constrained search's scope.
+int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
+                                       long ld_row, long ld_word, const BeamConstraints& cons, int B, hipStream_t stream) {
+    if (B <= 0 || p.width <= 0 || p.width > kMaxK || p.k <= 0 || p.k > kMaxK || p.V <= 0 || !stats || !running_in) return OVC_EINVAL;
+    if (nblk != (p.V + 31) / 32 || nblk > kBanWords || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
+    if ((long)p.width * p.V < p.k || ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
+    // the staged histories and the bitmap are sized for these: anything beyond would not fit the workgroup's LDS
+    if (p.T < 1 || p.T > OVC_MAX_LEN || p.t < 0 || p.t >= p.T || !p.hist_in) return OVC_EINVAL;
+    if (cons.ngram < 0 || cons.min_length < 0 || cons.n_banned < 0 || cons.n_banned > OVC_MAX_BANNED) return OVC_EINVAL;
+    for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
+    hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, running_in, ld_row,
+                       ld_word, cons);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_block_pieces_launch(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t, hipStream_t stream) {
+    const int nblk = (V + 31) / 32;
+    hipLaunchKernelGGL(block_pieces_kernel, dim3((nblk + 1) / 2, rows), dim3(64), 0, stream, x, rows, V, nblk, stats_ld, ldt, stats, logits_t);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 // p.width: 1 (step 0: every sample of an image draws from the image's one row) or p.k (sample s continues row s).
 int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
                                    const int64_t* seed, int B, hipStream_t stream) {
@@ -472,6 +541,24 @@ __global__ void collect_winners_kernel(const int32_t* anc, const int32_t* word, 
     score[i] = running[i];
 }
 }  // namespace
+
+namespace {
+__global__ void collect_parents_kernel(const int32_t* anc, const int32_t* hist, int n, int k, int width, int T, int t, int32_t* parent_out,
+                                       int32_t* word_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    parent_out[i] = anc[(size_t)i * T + t] - (i / k) * width;
+    word_out[i] = hist[(size_t)i * T + t];
+}
+}  // namespace
+
+int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, int B, int width, int k, int T, int t, int32_t* parent_out,
+                                     int32_t* word_out, hipStream_t stream) {
+    hipLaunchKernelGGL(collect_parents_kernel, dim3((B * k + 255) / 256), dim3(256), 0, stream, anc, hist, B * k, k, width, T, t, parent_out,
+                       word_out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
 
 int ovc_debug_collect_winners_launch(const int32_t* anc, const int32_t* word, const float* running, int B, int width, int V, int k,
                                      int64_t* chosen, float* score, hipStream_t stream) {

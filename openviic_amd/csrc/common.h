@@ -271,6 +271,22 @@ int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, c
 // transposed one.
 int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
                                  long ld_row, long ld_word, int B, hipStream_t stream, const int32_t* gate = nullptr);
+// The constrained search's options (include/ovc.h, ovc_beam_search_constrained): passed to the kernel by value.
+struct BeamConstraints {
+    int ngram, min_length, n_banned;                // 0, 0, 0: neutral
+    int banned[OVC_MAX_BANNED];                     // sorted ascending by the engine, so that equal sets hash equally
+    bool active() const { return ngram != 0 || min_length != 0 || n_banned != 0; }     // a bad option is active, and refused
+};
+// The options' scope for a model of V words, max_len steps, beam k: include/ovc.h lists the refusals.
+bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k, int eos, int pad);
+// ovc_beam_fused_update_launch with a per-row ban set (p.hist_in holds the rows' histories); p.alive_count must be nullptr.
+int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
+                                       long ld_row, long ld_word, const BeamConstraints& cons, int B, hipStream_t stream);
+// Test support: the block pieces [rows][stats_ld] float2 and the transposed logits [V][ldt] of row-major logits [rows][V].
+// parent_out / word_out [B][k]: the beam inside the image and the word of the winners a step t update left in anc / hist [B*k][T].
+int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, int B, int width, int k, int T, int t, int32_t* parent_out,
+                                     int32_t* word_out, hipStream_t stream);
+int ovc_block_pieces_launch(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t, hipStream_t stream);
 // Sampling in place of the selection (ovc_sample): sample s of image b draws its word from the pieces of its parent row and the
 // bookkeeping is the fused update's.  seed: the device word the draw's Philox key is read from; p.alive_count must be nullptr.
 int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,

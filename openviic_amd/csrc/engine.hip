@@ -895,6 +895,9 @@ struct SearchCall {
     // Shaped sampling (ovc_sample_shaped): has_options marks a call through the shaped entry points, whose workspace holds the
     // chooser's buffers; with neutral options the launches are ovc_sample's.
     bool has_options; float temperature; int top_k; float top_p;
+    // Constrained search (ovc_beam_search_constrained): the ban options, banned ids sorted; all zero: the plain search.
+    BeamConstraints cons;
+    bool constrained() const { return cons.active(); }
     bool shaped() const { return sample && has_options && !(temperature == 1.0f && top_k == 0 && top_p == 1.0f); }
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
@@ -914,6 +917,11 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                      (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
         return false;
     if (c.has_options && (!c.sample || !ovc_sample_options_ok(c.temperature, c.top_k, c.top_p))) return false;
+    // constraints: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, plain launches or the whole-search graph
+    if (c.constrained() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan ||
+                            (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
+                            !ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)))
+        return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
 }
 
@@ -1150,6 +1158,8 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_shaped_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.drop_seed, B, s));
+        else if (c.constrained())  // the one branch of a constrained step: the selection with a per-row ban set
+            RUN(ovc_beam_constrained_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, c.cons, B, s));
         else if (!(debug_skip() & 8))
             RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s, e.gate));
         if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
@@ -1363,6 +1373,7 @@ enum class GraphKind {
     TrainSmoothed,      // ovc_forward_backward_smoothed, with or without dropout (k = T, out_size = 1)
     SampleSearch,       // ovc_sample_graph (k = out_size = S, the samples per image; the seed is read from its workspace slot)
     ShapedSampleSearch, // ovc_sample_shaped_graph with options that are not neutral (as SampleSearch; the options in the hash)
+    ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1521,6 +1532,9 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
         return GraphKey{GraphKind::ShapedSampleSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N,
                         c.k, c.out_size};
     }
+    if (c.constrained())      // the options (banned ids sorted) are part of the key: no call replays another option set's graph
+        return GraphKey{GraphKind::ConstrainedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&c.cons, sizeof(c.cons)), workspace, c.B, c.N,
+                        c.k, c.out_size};
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1702,6 +1716,95 @@ extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, 
     SearchCall c{B, N, k, out_size, SearchForm::Gated, ids_out, logp_out};
     c.steps_out = steps_out;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Constrained search (include/ovc.h: the rule).  The plain search with a ban set in the selection of every step; neutral options
+// are the plain calls, launch for launch (the same SearchCall, hence the same graph key and workspace).
+// ---------------------------------------------------------------------------------------------
+// The options as the kernel takes them (ids sorted ascending); false: n_banned out of range or a null list.  The rest of the
+// scope is ovc_beam_constraints_ok's, inside search_ok.
+static bool constraints_from(int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, BeamConstraints* out) {
+    BeamConstraints c{};
+    if (n_banned < 0 || n_banned > OVC_MAX_BANNED || (n_banned > 0 && !banned)) return false;
+    c.ngram = no_repeat_ngram; c.min_length = min_length; c.n_banned = n_banned;
+    for (int i = 0; i < n_banned; ++i) c.banned[i] = banned[i];
+    std::sort(c.banned, c.banned + n_banned);
+    *out = c;
+    return true;
+}
+
+extern "C" int ovc_search_constraints_ok(const ovc_model* m, int k, int no_repeat_ngram, int min_length, const int32_t* banned,
+                                         int n_banned) {
+    SearchCall c{1, 1, k, k};
+    if (!model_ok(m) || !constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return 0;
+    return search_ok(m, c) ? 1 : 0;       // neutral options: the plain search's scope
+}
+
+extern "C" int ovc_beam_search_constrained(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                           int out_size, int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned,
+                                           void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                           float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return OVC_EINVAL;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_constrained_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                                 int out_size, int no_repeat_ngram, int min_length, const int32_t* banned,
+                                                 int n_banned, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                                 float* logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out};
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return OVC_EINVAL;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the constrained selection -- the production kernel instance -- on caller-given inputs (device memory):
+// row-major logits [B*width][V], histories hist [B*width][T] (words of steps 0..t-1), running / alive [B*width].  The block pieces
+// are computed here and the logits laid out transposed, as the engine's vocabulary product leaves them.  parent_out / word_out
+// [B][k] (int32), running_out [B][k], row_max_out / row_lsum_out [B*width].  scratch: ovc_debug_beam_constrained_update_bytes.
+extern "C" size_t ovc_debug_beam_constrained_update_bytes(int B, int width, int V, int k, int T) {
+    if (B <= 0 || width <= 0 || V <= 0 || k <= 0 || T <= 0) return 0;
+    const size_t R = (size_t)B * width, nblk = ((size_t)V + 31) / 32, ld = (nblk + 1) & ~(size_t)1, Rk = (size_t)B * k;
+    return 4 * ((size_t)V * ((R + 3) & ~(size_t)3) + 2 * R * ld + 4 * Rk + 6 * Rk * T + 64) + 4096;
+}
+
+extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B,
+                                                 int width, int V, int k, int T, int t, int eos, int no_repeat_ngram, int min_length,
+                                                 const int32_t* banned, int n_banned, void* scratch, size_t scratch_bytes,
+                                                 int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out,
+                                                 float* row_lsum_out, ovc_stream stream) {
+    BeamConstraints cons{};
+    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
+        return OVC_EINVAL;
+    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || (width != 1 && width != k) || V <= 0 ||
+        (V + 31) / 32 > kFusedVocabBlocks || T < 1 || T > OVC_MAX_LEN || t < 0 || t >= T || (width == 1) != (t == 0) || (long)B * k * T > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &cons) ||
+        !ovc_beam_constraints_ok(cons, V, T, k, eos, -1))
+        return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_beam_constrained_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const int rows = B * width, nblk = (V + 31) / 32, ld = (nblk + 1) & ~1, ldt = (rows + 3) & ~3;
+    const size_t Rk = (size_t)B * k;
+    Bump a{reinterpret_cast<char*>(scratch), 0};
+    float* logits_t = a.take<float>((size_t)V * ldt);
+    float* stats = a.take<float>(2 * (size_t)rows * ld);
+    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
+    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
+    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
+    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
+        return OVC_ELAUNCH;
+    TRY(ovc_block_pieces_launch(logits, rows, V, ld, ldt, stats, logits_t, s));
+    BeamUpdateArgs bu{};
+    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
+    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
+    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
+    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
+    TRY(ovc_beam_constrained_update_launch(bu, stats, nblk, ld, running, 1, ldt, cons, B, s));
+    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
 }
 
 // ---------------------------------------------------------------------------------------------

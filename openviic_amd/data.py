@@ -219,7 +219,8 @@ def feature_file_loader(paths: Sequence[str], batch_size: int, workers: int, key
 
 def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, beam_size: int = 5, slots: Optional[int] = None,
                           keys: Optional[Iterable[str]] = None, trusted: bool = False, workers: int = 0,
-                          loader_context="forkserver", early_exit=False, direct: bool = True):
+                          loader_context="forkserver", early_exit=False, direct: bool = True, no_repeat_ngram_size=0, min_length=0,
+                          banned_words=None):
     """The reference's prediction loop (``trainers/vi_trainer.py:241-252``: per batch ``items.to(device)`` ->
     ``model.beam_search(items, batch_size, beam_size, out_size=1)`` -> ``decode_caption`` -> duplicate collapse) as a
     software pipeline on ONE host thread:
@@ -268,6 +269,9 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
     of a few workgroups each -- four of them overlap almost freely (B = 1, files -> strings, 8 workers: 430 captions/s with two
     streams, 725 with four) --, a batch of 256 fills the chip better with four than with two (19.0k against 16.8k captions/s
     with the shared ring), and a fifth search serialises with the others whatever GPU_MAX_HW_QUEUES is (270-390 at B = 1).
+
+    ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``model.beam_search``'s constraints, passed through (default off:
+    the plain search).  They exclude the early-exit forms.
     """
     import sys
     import time
@@ -294,7 +298,8 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
     def search(slot, items, ready, names):
         with torch.no_grad(), torch.cuda.stream(decode_streams[slot]):
             decode_streams[slot].wait_event(ready)
-            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1, early_exit=early_exit)
+            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1, early_exit=early_exit,
+                                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
             ids_host = pinned_like(slot, "__ids__", outs.shape, outs.dtype)
             ids_host.copy_(outs, non_blocking=True)
             done = torch.cuda.Event()

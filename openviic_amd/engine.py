@@ -20,6 +20,7 @@ import threading
 
 import torch
 
+from . import constraints as _constraints
 from . import dropout as _dropout
 from . import native
 from .native import check
@@ -610,6 +611,11 @@ class CaptionEngine:
             "graph": ("ovc_beam_search_graph", ("out_size", *_RESULTS, "stream")),
             "early": ("ovc_beam_search_early", ("out_size", *_RESULTS, "steps_run", "stream")),
             "device": ("ovc_beam_search_gated", ("out_size", *_RESULTS, "steps", "stream"))}),
+        "constrained": ("ovc_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search_constrained", ("out_size", "ngram", "min_length", "banned", "n_banned", *_RESULTS, "everything",
+                                                      "stream")),
+            "graph": ("ovc_beam_search_constrained_graph", ("out_size", "ngram", "min_length", "banned", "n_banned", *_RESULTS,
+                                                            "stream"))}),
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
@@ -622,7 +628,7 @@ class CaptionEngine:
     }
 
     def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None):
+                    options=None, constraints=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
@@ -630,8 +636,11 @@ class CaptionEngine:
         ``(B, out_size, T)``; ``everything`` ``(B, width, T, V)`` with ``return_probs``, else None; ``slots`` (int32, None without
         dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
         (``sequence_backward(dropout=..., slots=...)`` recomputes under them).  ``options``: what ``sample_options`` returned --
-        the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw."""
+        the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw.  ``constraints``: what
+        ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search."""
         kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
+        if constraints:
+            kind = "constrained"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -664,6 +673,9 @@ class CaptionEngine:
             args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
         if options:
             args.update(zip(("temperature", "top_k", "top_p"), options))
+        if constraints:
+            n, L, banned = constraints
+            args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
         entry, names = self._SEARCH_FORMS[kind][3][form]
         self.last_steps_run = T
         check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
@@ -674,14 +686,47 @@ class CaptionEngine:
             self.last_steps_device = steps
         return ids, logp, everything, slots
 
-    def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None):
-        """``dropout=(probs, seed)`` (as ``forward_backward``): the search runs with every site's mask applied and returns
+    def check_constraints(self, beam_size, constraints=None, early_exit=None, dropout=None):
+        """The refusals of a constrained search that need no input, each naming its argument: callers run them before any
+        launch and any random draw.  ``constraints``: None or ``(no_repeat_ngram_size, min_length, banned_words)``.  Returns the
+        normalised options ``(n, L, banned)``, or None when they are neutral (the plain search)."""
+        if constraints is None:
+            return None
+        d = self.desc
+        n, L, banned = constraints
+        options = _constraints.check(n, L, banned, d.vocab, d.max_len, int(beam_size), d.eos_idx, d.pad_idx)
+        if options == _constraints.NEUTRAL:
+            return None
+        what = "beam_search(no_repeat_ngram_size / min_length / banned_words)"
+        if dropout is not None:
+            raise native.OvcError(what + ": dropout=... is not covered -- constraints under dropout are out of scope")
+        early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
+        if early:
+            raise native.OvcError(what + ": early_exit={!r} is not covered -- the constrained search has no early-exit form; pass "
+                                         "early_exit=False".format("device" if early == "device" else True))
+        if self.precision != "f32":
+            raise native.OvcError(what + ": precision={!r} is not covered -- constraints run in 'f32' only".format(self.precision))
+        if d.vocab > 16384:
+            raise native.OvcError(what + ": a vocabulary of {} words is not covered -- at most 16384".format(d.vocab))
+        banned_c = (ctypes.c_int32 * max(1, len(options[2])))(*options[2])
+        if not self.lib.ovc_search_constraints_ok(ctypes.byref(d), int(beam_size), options[0], options[1], banned_c, len(options[2])):
+            raise native.OvcError(what + ": the engine refuses these options for this model (ovc_search_constraints_ok)")
+        return options
+
+    def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None,
+                    constraints=None):
+        """``constraints=(no_repeat_ngram_size, min_length, banned_words)`` (``ovc_beam_search_constrained``; DESIGN.md section 2s,
+        ``openviic_amd.constraints`` mirrors the rule): words are banned per beam row and step, everything else is the plain
+        search; neutral values are the plain call.  Refused by name before any launch: a bad option, or constraints together with
+        ``dropout``, an early-exit form, a split precision or a vocabulary of more than 16 384 words.
+        ``dropout=(probs, seed)`` (as ``forward_backward``): the search runs with every site's mask applied and returns
         ``(ids, logp, slots)``, unsqueezed ``(B, out_size, T)``; with no ``p > 0`` it is the plain call and ``slots`` is None.
         ``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above and ``early_exit_mode``.  ``True``:
         ``self.last_steps_run`` then holds the number of decode steps that were issued for the call.  ``"device"``:
         ``self.last_steps_device`` is a one-element int32 device tensor (one per workspace, i.e. per stream) that receives, in
         stream order, the number of decode steps that did work; ``last_steps_run`` stays ``max_len``.  With ``return_probs``
         every mode runs the full search."""
+        constraints = self.check_constraints(beam_size, constraints, early_exit, dropout)
         early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
         table_drop = None
         if dropout is not None:
@@ -689,7 +734,7 @@ class CaptionEngine:
                 raise native.OvcError("beam_search(dropout=...) has no return_probs form")
             table_drop = self._dropout_table(dropout)
         ids, logp, everything, slots = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early,
-                                                        table_drop)
+                                                        table_drop, constraints=constraints)
         if dropout is not None:
             return ids, logp, slots
         if out_size == 1:

@@ -319,14 +319,16 @@ class EvalCorpus:
         return self.scores_from_stats(*self.statistics())
 
 
-def evaluate_metrics(model, dataloader, corpus, beam_size):
+def evaluate_metrics(model, dataloader, corpus, beam_size, no_repeat_ngram_size=0, min_length=0, banned_words=None):
     """The reference's ``evaluate_metrics`` (``vi_trainer.py:78-98``) with the scoring on the device: returns its ``scores``
-    (without METEOR).  Every batch needs ``items.captions``, per image the references the corpus was built from."""
+    (without METEOR).  Every batch needs ``items.captions``, per image the references the corpus was built from.
+    ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``model.beam_search``'s constraints (default off)."""
     model.eval()
     corpus.reset()
     for items in dataloader:
         items = items.to(corpus.device)
         with torch.no_grad():
-            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1)
+            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1,
+                                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
         corpus.update(outs, corpus.rows(items.captions))
     return corpus.compute()[0]

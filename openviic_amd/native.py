@@ -13,6 +13,7 @@ OVC_MAX_LEVELS = 4
 OVC_MAX_BEAM = 8
 OVC_MAX_REGIONS = 1024
 OVC_MAX_LEN = 256            # decode steps (caption positions, the decoder's max_len) the engine accepts
+OVC_MAX_BANNED = 16          # banned word ids a constrained search takes
 OVC_PROFILE_CLASSES = 4
 ABI_VERSION = 8
 
@@ -199,6 +200,15 @@ SIGNATURES = {
     "ovc_sample_choice_workspace_bytes": (c_size_t, [c_long, c_int]),
     "ovc_sample_choice": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_int, c_float, c_int, c_float, c_void_p, c_size_t,
                                   c_void_p, c_void_p, c_void_p]),
+    "ovc_search_constraints_ok": (c_int, [POINTER(Model), c_int, c_int, c_int, POINTER(c_int32), c_int]),
+    "ovc_beam_search_constrained": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_beam_search_constrained_graph": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_beam_constrained_update_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ovc_debug_beam_constrained_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  c_int, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ovc_cider_reward": (c_int, [POINTER(Cider), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_adam_chunk_count": (c_long, [c_void_p, c_int]),
     "ovc_adam_chunk_fill": (c_long, [c_void_p, c_int, c_void_p, c_long]),
@@ -233,7 +243,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_sample_shaped_workspace_bytes", "ovc_sample_shaped", "ovc_sample_shaped_graph",
                  "ovc_sample_choice_workspace_bytes", "ovc_sample_choice",
                  "ovc_debug_decode_self_partial_bytes", "ovc_debug_decode_self_attention", "ovc_debug_decode_cross_attention",
-                 "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form")
+                 "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form",
+                 "ovc_search_constraints_ok", "ovc_beam_search_constrained", "ovc_beam_search_constrained_graph",
+                 "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update")
 
 _lib = None
 

@@ -583,7 +583,8 @@ int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, 
  * refuses.  ovc_search_constraints_ok: 1 when (m, k, options) is in this scope, else 0; launches nothing.
  * Not covered: length penalty or normalisation, repetition penalty, forced or prefix-constrained decoding, diverse beam search,
  * more than OVC_MAX_BANNED ids, constraints under dropout, in the early-exit forms, in the split-precision modes or when sampling.
- * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel on caller-given device inputs -- row-major
+ * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel (the search's own routing: the constrained
+ * instance with active options, the plain selection with neutral ones) on caller-given device inputs -- row-major
  * logits [B*width][V], hist [B*width][T] (int32, steps 0..t-1 read), running / alive [B*width]; width = 1 iff t = 0, else k.  The
  * entry forms the block pieces and the transposed logits itself.  parent_out / word_out [B][k] int32 (the beam inside the image,
  * the word), running_out [B][k], row_max_out / row_lsum_out [B*width]: M and ls.  scratch: ovc_debug_beam_constrained_update_bytes. */

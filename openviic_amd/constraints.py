@@ -1,5 +1,5 @@
 """The constrained beam search's rule in plain Python / numpy (``include/ovc.h``, ``ovc_beam_search_constrained``: the rule's
-statement; ``csrc/bodies/beam_constrained_update.inc``: the kernel).  Three functions: ``check`` (the refusals), ``banned_at``
+statement; ``csrc/bodies/beam_fused_update.inc`` with ``kBan``: the kernel).  Three functions: ``check`` (the refusals), ``banned_at``
 (the ban set of one live row at one step) and ``mirror_search`` (a whole search replayed on the host from per-step
 log-probabilities).  Nothing here touches the device.
 """

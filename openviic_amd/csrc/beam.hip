@@ -160,29 +160,37 @@ __device__ __forceinline__ void beam_follow_winners(const BeamUpdateArgs& p, int
     }
 }
 
-// The per-beam scalars of winner `slot` (flat index f = beam * V + word, score v) of image b.
+// The per-beam scalars of winner `slot` of image b: word wd of beam par (inside the image), its score, its logit x, the log-softmax
+// pieces (M, ls) and the alive flag of its row; parent / word: the LDS slots beam_follow_winners reads.  The writer of the two-pass
+// update and of the samplers; the fused selection's phase D keeps these stores in its own order (bodies/beam_fused_update.inc).
+__device__ __forceinline__ void beam_write_winner(const BeamUpdateArgs& p, int b, int slot, int par, int wd, float score, float x,
+                                                  float M, float ls, float alive, int* parent, int* word) {
+    const int k = p.k, T = p.T, t = p.t;
+    parent[slot] = par; word[slot] = wd;
+    const float lp = ((x - M) - ls) * alive;
+    p.running_out[b * k + slot] = score;
+    p.alive_out[b * k + slot] = alive * (wd != p.eos ? 1.0f : 0.0f);
+    p.hist_out[((size_t)b * k + slot) * T + t] = wd;
+    p.lp_out[((size_t)b * k + slot) * T + t] = lp;
+    p.next_tok[b * k + slot] = wd;
+    p.anc_out[((size_t)b * k + slot) * T + t] = b * p.width + par;
+}
+
+// The two-pass path's winner `slot` (flat index f = beam * V + word, score v) of image b: its logit is read back through p.ld.
 // row_max / row_lsum: the log-softmax pieces of the image's rows, indexed by the beam inside the image.
 __device__ __forceinline__ void beam_record_winner(const BeamUpdateArgs& p, int b, int slot, int best_idx, float best_v,
                                                    const float* row_max, const float* row_lsum, int* parent, int* word) {
-    const int k = p.k, W = p.width, V = p.V, T = p.T, t = p.t;
+    const int W = p.width, V = p.V;
     // An image without a single valid region (all-zero features, e.g. the padding images of a ragged last shard)
     // has every key masked: its logits are NaN, no candidate compares greater than anything and no winner
     // exists.  The reference returns arbitrary in-range words for it; here slot j takes word j of beam 0, so
     // that every index derived from it stays in range.
     const int f = (unsigned)best_idx < (unsigned)(W * V) ? best_idx : slot;
     const int par = f / V, wd = f - par * V;
-    parent[slot] = par; word[slot] = wd;
     const float alive = p.alive_in[b * W + par];
     const float x = p.logits[((size_t)b * W + par) * p.ld + wd];
-    const float lp = ((x - row_max[par]) - row_lsum[par]) * alive;
-    p.running_out[b * k + slot] = best_v;
-    p.alive_out[b * k + slot] = alive * (wd != p.eos ? 1.0f : 0.0f);
-    p.hist_out[((size_t)b * k + slot) * T + t] = wd;
-    p.lp_out[((size_t)b * k + slot) * T + t] = lp;
-    p.next_tok[b * k + slot] = wd;
-    p.anc_out[((size_t)b * k + slot) * T + t] = b * W + par;
+    beam_write_winner(p, b, slot, par, wd, best_v, x, row_max[par], row_lsum[par], alive, parent, word);
 }
-
 
 __global__ __launch_bounds__(256) void beam_update_kernel(BeamUpdateArgs p) {
 #include "bodies/beam_update.inc"
@@ -207,18 +215,26 @@ __global__ __launch_bounds__(256) void beam_update_kernel_gated(BeamUpdateArgs p
 // 160 pairs per row instead of 10 201 logits; one launch instead of two.  Massive ties (a uniform row: every block hot)
 // overflow the lists and take k rounds of an exhaustive arg-max over the image's width * V candidates.
 constexpr int kHotCap = 512, kFusedSurvCap = 1024, kFusedThreads = 512, kFusedPairs = 4;   // 64 lanes x 4 loads x 2 blocks = 512 blocks
+constexpr int kBanWords = 512;                           // the constrained instance's bitmap, 32 words each: one per block
+static_assert(kBanWords == 512 && OVC_MAX_BANNED <= 64, "one bitmap word per block of the fused tail, one lane per banned id");
+static_assert(kFusedVocabBlocks == 2 * 64 * kFusedPairs && kFusedVocabBlocks == kBanWords, "fused_tail_ok admits what one wave loads");
 
 // 512 threads per image: wave w < width owns beam row w through phases A and B (no workgroup-level reduction), then all
-// eight waves gather the hot blocks and wave 0 ranks the survivors in registers.
+// eight waves gather the hot blocks and wave 0 ranks the survivors in registers.  One body for the three instances: the plain and
+// the gated kernel compile it without a ban set (kBan = false: no constraints among their arguments, nothing of them in their code).
 __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
                                                                           int stats_ld, const float* __restrict__ running_in,
                                                                           long ld_row, long ld_word) {
+    constexpr bool kBan = false;                        // no ban set ...
+    constexpr BeamConstraints cons{};                   // ... and no constraints among the arguments: the instance below has both
 #include "bodies/beam_fused_update.inc"
 }
 __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel_gated(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
                                                                                 int stats_ld, const float* __restrict__ running_in,
                                                                                 long ld_row, long ld_word, const int32_t* __restrict__ gate) {
     if (ovc_gate_closed(gate)) return;
+    constexpr bool kBan = false;
+    constexpr BeamConstraints cons{};
 #include "bodies/beam_fused_update.inc"
 }
 
@@ -227,15 +243,13 @@ __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel_gated(
 // n-gram of the row's own history.  The set lives in LDS as one bit per (row, word), built by the row's wave before phase A; a
 // 32-bit word of the bitmap is one 32-word block of the vocabulary, so a block is "dirty" iff its word is non-zero.  The pieces
 // (M, ls) and every candidate's arithmetic are the plain kernel's; a dirty block keeps its upper bound but feeds no lower bound,
-// and a word whose bit is set is skipped by the hot-block pass and the exhaustive path.  LDS: the plain body's 14 KB + 16 KB
+// and a word whose bit is set is skipped by the hot-block pass and the exhaustive path.  LDS: the plain instance's 14 KB + 16 KB
 // bitmap + 8 KB staged histories = 38 KB of the workgroup's 64 KB (static: the compiler refuses more).
-constexpr int kBanWords = 512;                           // 32 words each: V <= 16 384, the fused tail's 512 blocks
-static_assert(kBanWords == 512 && OVC_MAX_BANNED <= 64, "one bitmap word per block of the fused tail, one lane per banned id");
-
 __global__ __launch_bounds__(kFusedThreads) void beam_constrained_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
                                                                                 int stats_ld, const float* __restrict__ running_in,
                                                                                 long ld_row, long ld_word, BeamConstraints cons) {
-#include "bodies/beam_constrained_update.inc"
+    constexpr bool kBan = true;
+#include "bodies/beam_fused_update.inc"
 }
 
 // The block pieces of row-major logits [rows][V] as the vocabulary product's epilogue leaves them -- per (row, 32-word block) the
@@ -270,11 +284,11 @@ __global__ __launch_bounds__(256) void masked_logp_kernel(const float* __restric
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Sampling from the same block pieces (ovc_sample, include/ovc.h: the rule).  One workgroup per image, wave s = sample s of the
-// image: it reads the pieces of its parent row (row 0 of the image at step 0, row s later), forms M and ls as phase A above does,
+// image: it reads the pieces of its parent row (row 0 of the image at step 0, row s later) with phase A above (one text),
 // draws u from Philox and walks the inverse CDF in ascending word order in two levels -- the block whose inclusive prefix of
 // masses S_j exp(M_j - M) first exceeds u * Z, then the word inside it from the block's 32 stored logits -- and ends with stage
-// D's writes and beam_follow_winners.  Every prefix is a wave scan in a fixed order: the same bits on every call, stream,
-// replay and GEMM tiling.  No workgroup-level reduction, no atomics.
+// D's writes (beam_write_winner) and beam_follow_winners.  Every prefix is a wave scan in a fixed order: the same bits on every
+// call, stream, replay and GEMM tiling.  No workgroup-level reduction, no atomics.
 constexpr uint32_t kSampleCounterWord = 0x53414D50u;     // "SAMP": Philox counter word 2, outside the dropout site range
 
 // inclusive prefix sum over the 64 lanes of a wave (Hillis-Steele, six fixed steps)
@@ -414,17 +428,22 @@ int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, c
     return OVC_OK;
 }
 
-int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
-                                 long ld_row, long ld_word, int B, hipStream_t stream, const int32_t* gate) {
-    if (B <= 0 || p.width <= 0 || p.width > kMaxK || p.k <= 0 || p.k > kMaxK || p.V <= 0 || !stats || !running_in) return OVC_EINVAL;
-    if (nblk != (p.V + 31) / 32 || nblk > 512 || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
-    if ((long)p.width * p.V < p.k) return OVC_EINVAL;
-    if (ld_row <= 0 || ld_word <= 0) return OVC_EINVAL;
+// What every launcher of the fused tail requires: the shape, the block pieces as one wave loads them (phase A) and the strides.
+static bool fused_tail_ok(const BeamUpdateArgs& p, const FusedTail& f, int B) {
+    if (B <= 0 || p.width <= 0 || p.width > kMaxK || p.k <= 0 || p.k > kMaxK || p.V <= 0 || !f.stats) return false;
+    if (f.nblk != (p.V + 31) / 32 || f.nblk > kFusedVocabBlocks || f.stats_ld < f.nblk || (f.stats_ld & 1) || !ovc_aligned16(f.stats)) return false;
+    return f.ld_row > 0 && f.ld_word > 0;
+}
+
+int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, int B, hipStream_t stream,
+                                 const int32_t* gate) {
+    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k) return OVC_EINVAL;
     if (gate)
-        hipLaunchKernelGGL(beam_fused_update_kernel_gated, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, running_in, ld_row,
-                           ld_word, gate);
+        hipLaunchKernelGGL(beam_fused_update_kernel_gated, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
+                           f.ld_row, f.ld_word, gate);
     else
-        hipLaunchKernelGGL(beam_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, running_in, ld_row, ld_word);
+        hipLaunchKernelGGL(beam_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
+                           f.ld_row, f.ld_word);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -442,17 +461,15 @@ bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k
 
 // The constrained step: ovc_beam_fused_update_launch's arguments plus the constraints, by value (baked into a captured graph).
 // No gated instance: the early-exit forms are out of the constrained search's scope.
-int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
-                                       long ld_row, long ld_word, const BeamConstraints& cons, int B, hipStream_t stream) {
-    if (B <= 0 || p.width <= 0 || p.width > kMaxK || p.k <= 0 || p.k > kMaxK || p.V <= 0 || !stats || !running_in) return OVC_EINVAL;
-    if (nblk != (p.V + 31) / 32 || nblk > kBanWords || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
-    if ((long)p.width * p.V < p.k || ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
+int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const BeamConstraints& cons,
+                                       int B, hipStream_t stream) {
+    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || p.alive_count) return OVC_EINVAL;
     // the staged histories and the bitmap are sized for these: anything beyond would not fit the workgroup's LDS
     if (p.T < 1 || p.T > OVC_MAX_LEN || p.t < 0 || p.t >= p.T || !p.hist_in) return OVC_EINVAL;
     if (cons.ngram < 0 || cons.min_length < 0 || cons.n_banned < 0 || cons.n_banned > OVC_MAX_BANNED) return OVC_EINVAL;
     for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
-    hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, running_in, ld_row,
-                       ld_word, cons);
+    hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
+                       f.ld_row, f.ld_word, cons);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -465,12 +482,10 @@ int ovc_block_pieces_launch(const float* x, int rows, int V, int stats_ld, int l
 }
 
 // p.width: 1 (step 0: every sample of an image draws from the image's one row) or p.k (sample s continues row s).
-int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
-                                   const int64_t* seed, int B, hipStream_t stream) {
-    if (B <= 0 || p.k <= 0 || p.k > kMaxK || (p.width != 1 && p.width != p.k) || p.V <= 0 || !stats || !seed) return OVC_EINVAL;
-    if (nblk != (p.V + 31) / 32 || nblk > 512 || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
-    if (ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
-    hipLaunchKernelGGL(sample_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, ld_row, ld_word, seed);
+int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const int64_t* seed, int B, hipStream_t stream) {
+    if (!fused_tail_ok(p, f, B) || (p.width != 1 && p.width != p.k) || p.alive_count || !seed) return OVC_EINVAL;
+    hipLaunchKernelGGL(sample_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, f.ld_row, f.ld_word,
+                       seed);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -503,12 +518,10 @@ int ovc_sample_choice_launch(const float* logits, long ld_row, long ld_word, int
     return OVC_OK;
 }
 
-int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
-                                    const int32_t* chosen, int B, hipStream_t stream) {
-    if (B <= 0 || p.k <= 0 || p.k > kMaxK || (p.width != 1 && p.width != p.k) || p.V <= 0 || !stats || !chosen) return OVC_EINVAL;
-    if (nblk != (p.V + 31) / 32 || nblk > 512 || stats_ld < nblk || (stats_ld & 1) || !ovc_aligned16(stats)) return OVC_EINVAL;
-    if (ld_row <= 0 || ld_word <= 0 || p.alive_count) return OVC_EINVAL;
-    hipLaunchKernelGGL(sample_shaped_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, stats, nblk, stats_ld, ld_row, ld_word, chosen);
+int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const int32_t* chosen, int B, hipStream_t stream) {
+    if (!fused_tail_ok(p, f, B) || (p.width != 1 && p.width != p.k) || p.alive_count || !chosen) return OVC_EINVAL;
+    hipLaunchKernelGGL(sample_shaped_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, f.ld_row, f.ld_word,
+                       chosen);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -1,5 +1,9 @@
-// The body of beam_fused_update and its gated instance (beam.hip): included verbatim into both kernels, so that the
-// ungated one compiles exactly as before.  Not a header: no include guard.
+// The body of beam_fused_update_kernel, its gated instance and beam_constrained_update_kernel (beam.hip): included verbatim into
+// each, so that the ungated ones compile exactly as before.  The including kernel defines `constexpr bool kBan` and `cons`
+// (BeamConstraints: a kernel argument with kBan, a constexpr neutral value without).  With kBan every row carries a ban set
+// (include/ovc.h, ovc_beam_search_constrained: the rule); the four pieces that know of it are marked "ban:" and compile to nothing
+// without it -- the bitmap and the staged histories are then not even allocated.  The log-softmax pieces, the candidate
+// arithmetic, the order, the frozen beams' offers and phase D are the same text for all three.  Not a header: no include guard.
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
     __shared__ float rowM[kMaxK], rowLs[kMaxK], rowRun[kMaxK], thr[kMaxK];
@@ -12,48 +16,65 @@
     __shared__ float win_v[kMaxK], win_x[kMaxK];
     __shared__ int win_i[kMaxK];
     __shared__ int parent[kMaxK], word[kMaxK];
+    // ban: one bit per (row, word); 32-bit word j of a row IS the row's 32-word block j, so "block j holds a banned word"
+    // is one LDS read.  The row's history is staged once for the n-gram scan.
+    __shared__ unsigned ban[kMaxK][kBanWords];
+    __shared__ int hist_s[kMaxK][OVC_MAX_LEN];
+
+    // ---- ban: wave w builds row w's set.  Bits are set with integer LDS atomics: idempotent, so order plays no part ------------
+    if (kBan) {
+        for (int i = tid; i < kMaxK * kBanWords; i += kFusedThreads) (&ban[0][0])[i] = 0u;
+        if (wave < W)
+            for (int i = lane; i < t; i += 64) hist_s[wave][i] = p.hist_in[((size_t)b * W + wave) * T + i];
+        __syncthreads();
+        if (wave < W && p.alive_in[b * W + wave] != 0.0f) {        // a frozen beam is never subject to a ban
+            if (lane < cons.n_banned) atomicOr(&ban[wave][cons.banned[lane] >> 5], 1u << (cons.banned[lane] & 31));
+            if (lane == 0 && t < cons.min_length && (unsigned)p.eos < (unsigned)V) atomicOr(&ban[wave][p.eos >> 5], 1u << (p.eos & 31));
+            const int n = cons.ngram;
+            if (n >= 1 && t >= n - 1) {
+                // the n-gram that starts at j repeats the row's last n - 1 words: its last word would complete a repeat
+                const int* h = hist_s[wave];
+                const int* suffix = h + (t - n + 1);
+                for (int j = lane; j <= t - n; j += 64) {
+                    bool same = true;
+                    for (int i = 0; i < n - 1 && same; ++i) same = h[j + i] == suffix[i];
+                    const int wd = h[j + n - 1];
+                    if (same && (unsigned)wd < (unsigned)V) atomicOr(&ban[wave][wd >> 5], 1u << (wd & 31));
+                }
+            }
+        }
+        __syncthreads();
+    }
 
     if (tid == 0) { nhot = 0; nsurv = 0; }
     if (tid < kMaxK) { win_v[tid] = -INFINITY; win_i[tid] = 0x7fffffff; win_x[tid] = 0.f; }
-    // ---- A + B: wave w = beam row w.  Lane l holds the block pairs l + 64 j (four 16-byte loads per lane, 1 KB per wave and
-    //      load, all in flight together); log-softmax pieces, block bounds and the row's own k-th best bound by wave-level
-    //      reductions only ---------------------------------------------------------------------------------------------------
-    f32x4 st[kFusedPairs];
+    // ---- A + B: wave w = beam row w.  The log-softmax pieces (fused_row_pieces.inc: the samplers' phase A as well), block
+    //      bounds and the row's own k-th best bound by wave-level reductions only ------------------------------------------------
     float ub[kFusedPairs][2];
     float run = 0.f;
     bool live = false;
     if (wave < W) {
         const int row = b * W + wave;
-        const float* srow = stats + 2 * (size_t)row * stats_ld;
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j)      // unconditional loads from clamped addresses, masked below
-            st[j] = *reinterpret_cast<const f32x4*>(srow + 2 * min(2 * (lane + 64 * j), stats_ld - 2));
         run = running_in[row];
-        live = p.alive_in[row] != 0.0f;
-        float m = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j) {
-            const int blk0 = 2 * (lane + 64 * j);
-            if (blk0 >= nblk) { st[j][0] = -INFINITY; st[j][1] = 0.f; }
-            if (blk0 + 1 >= nblk) { st[j][2] = -INFINITY; st[j][3] = 0.f; }
-            m = fmaxf(m, fmaxf(st[j][0], st[j][2]));
-        }
-        const float M = wave_max_dpp(m);
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j)      // a block past nblk holds (-inf, 0): 0 * exp(-inf) = 0
-            sum += st[j][1] * __expf(st[j][0] - M) + st[j][3] * __expf(st[j][2] - M);
-        const float ls = logf(wave_sum_dpp(sum));
+#include "fused_row_pieces.inc"
+        live = alive != 0.0f;
+        const float ls = logf(Z);
         float lanemax = -INFINITY;
 #pragma unroll
         for (int j = 0; j < kFusedPairs; ++j) {
             const int blk0 = 2 * (lane + 64 * j);
-            // every block's maximum IS a candidate: its score, with the arithmetic of the per-word pass
+            // every block's maximum bounds the block's candidates from above, with the arithmetic of the per-word pass
             ub[j][0] = live && blk0 < nblk ? run + ((st[j][0] - M) - ls) : -INFINITY;
             ub[j][1] = live && blk0 + 1 < nblk ? run + ((st[j][2] - M) - ls) : -INFINITY;
-            lanemax = fmaxf(lanemax, fmaxf(ub[j][0], ub[j][1]));
+            // ban: only a block without a banned word is sure to HOLD a candidate of that score (a dirty block's maximum may be
+            // the banned word), so only clean blocks feed the lower bound.  Without a ban set the bound is ub itself, literally:
+            // a select that only repeats ub's own `blk0 < nblk` is not folded away
+            const float c0 = !kBan || (blk0 < nblk && ban[wave][blk0] == 0u) ? ub[j][0] : -INFINITY;
+            const float c1 = !kBan || (blk0 + 1 < nblk && ban[wave][blk0 + 1] == 0u) ? ub[j][1] : -INFINITY;
+            lanemax = fmaxf(lanemax, fmaxf(c0, c1));
         }
-        // k distinct candidates of this row reach the k-th largest lane maximum: a lower bound on the image's k-th best
+        // k distinct unbanned candidates of this row reach the k-th largest lane maximum: a lower bound on the image's k-th best
+        // (fewer than k lanes with a clean block: -inf, every block is hot and the lists overflow into the exhaustive path)
         const float kth = wave_kth_largest(lanemax, k);
         if (lane == 0) {
             rowM[wave] = M; rowLs[wave] = ls; rowRun[wave] = run; rowLive[wave] = live ? 1 : 0; thr[wave] = kth;
@@ -102,7 +123,8 @@
                 const int h = h0 + u * kPerPass + (tid >> 5);
                 if (h < H && hot_blk[h] * 32 + (tid & 31) < V) {
                     const float cand = rowRun[ri[u]] + ((x[u] - rowM[ri[u]]) - rowLs[ri[u]]);
-                    if (cand >= Tthr) {
+                    const bool banned = kBan && ((ban[ri[u]][hot_blk[h]] >> (tid & 31)) & 1u);      // ban: never a survivor
+                    if (!banned && cand >= Tthr) {
                         const int pos = atomicAdd(&nsurv, 1);
                         if (pos < kFusedSurvCap) { surv_v[pos] = cand; surv_i[pos] = ri[u] * V + col[u]; surv_x[pos] = x[u]; }
                     }
@@ -154,6 +176,7 @@
                     const float cand = alive_i ? ri + ((xc - mi) - li) : (col == 0 ? ri : -999.0f);
                     const int idx = i * V + col;
                     const bool after = cand < pv || (cand == pv && idx > pi);
+                    if (kBan && ((ban[i][col >> 5] >> (col & 31)) & 1u)) continue;        // ban: set for live rows only
                     if (after && better(cand, idx, c.v, c.idx)) { c.v = cand; c.idx = idx; cx = xc; }
                 }
             }
@@ -182,6 +205,8 @@
         // alive = 0 only needs a finite operand), the logit is read as the two-pass path reads it
         const float x = ((unsigned)win_i[tid] < (unsigned)(W * V) && rowLive[par]) ? win_x[tid]
                                                                                    : p.logits[(size_t)(b * W + par) * ld_row + (size_t)wd * ld_word];
+        // (beam_write_winner's stores, in this body's own order: through the writer, which stores parent / word after the loads
+        // above, the three instances come out with another instruction stream)
         const float lp = ((x - rowM[par]) - rowLs[par]) * alive;
         p.running_out[b * k + tid] = win_v[tid];
         p.alive_out[b * k + tid] = alive * (wd != p.eos ? 1.0f : 0.0f);

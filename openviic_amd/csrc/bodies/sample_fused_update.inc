@@ -1,33 +1,14 @@
 // The body of sample_fused_update_kernel and, with kChosen (the word is read from `chosen`, not drawn), of
 // sample_shaped_update_kernel (beam.hip).  Not a header: no include guard.
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
+    const int W = p.width, k = p.k, V = p.V, t = p.t;
     __shared__ int parent[kMaxK], word[kMaxK];
 
     if (wave < k) {
-        // ---- A: the parent row's log-softmax pieces, as beam_fused_update forms them (same loads, same order of operations) ---
+        // ---- A: the parent row's log-softmax pieces and alive flag: the selection's own phase A ---------------------------------------
         const int par = W == 1 ? 0 : wave;             // step 0: the image's one row; later: the sample's own
         const int row = b * W + par;
-        const float* srow = stats + 2 * (size_t)row * stats_ld;
-        f32x4 st[kFusedPairs];
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j)      // unconditional loads from clamped addresses, masked below
-            st[j] = *reinterpret_cast<const f32x4*>(srow + 2 * min(2 * (lane + 64 * j), stats_ld - 2));
-        const float alive = p.alive_in[row];
-        float m = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j) {
-            const int blk0 = 2 * (lane + 64 * j);
-            if (blk0 >= nblk) { st[j][0] = -INFINITY; st[j][1] = 0.f; }
-            if (blk0 + 1 >= nblk) { st[j][2] = -INFINITY; st[j][3] = 0.f; }
-            m = fmaxf(m, fmaxf(st[j][0], st[j][2]));
-        }
-        const float M = wave_max_dpp(m);
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j)      // a block past nblk holds (-inf, 0): 0 * exp(-inf) = 0
-            sum += st[j][1] * __expf(st[j][0] - M) + st[j][3] * __expf(st[j][2] - M);
-        const float Z = wave_sum_dpp(sum);
+#include "fused_row_pieces.inc"
         const float ls = logf(Z);
 
         int wd; float xw;
@@ -90,17 +71,10 @@
         xw = live ? __shfl(x, pick, 64) : x0;
         }
 
-        // ---- D: the bookkeeping of beam_fused_update, winner = (parent row, drawn word) -----------------------------------------
+        // ---- D: the bookkeeping of the selection, winner = (parent row, drawn word) ---------------------------------------------
         if (lane == 0) {
             if (wave < W && p.row_max_out) { p.row_max_out[row] = M; p.row_lsum_out[row] = ls; }
-            parent[wave] = par; word[wave] = wd;
-            const float lp = ((xw - M) - ls) * alive;
-            p.running_out[b * k + wave] = 0.f;         // no score: the final kernel then keeps the sample order
-            p.alive_out[b * k + wave] = alive * (wd != p.eos ? 1.0f : 0.0f);
-            p.hist_out[((size_t)b * k + wave) * T + t] = wd;
-            p.lp_out[((size_t)b * k + wave) * T + t] = lp;
-            p.next_tok[b * k + wave] = wd;
-            p.anc_out[((size_t)b * k + wave) * T + t] = b * W + par;
+            beam_write_winner(p, b, wave, par, wd, 0.f, xw, M, ls, alive, parent, word);      // no score: the final kernel then keeps the sample order
         }
     }
     __syncthreads();

@@ -265,12 +265,24 @@ struct BeamUpdateArgs {
     int32_t* alive_count;
 };
 int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, const int32_t* gate = nullptr);
-// Selection + update in one launch from the vocabulary GEMM's block pieces (GemmArgs::stats, [rows][stats_ld] float2,
-// stats_ld even): no pass over the logits.  nblk = ceil(V / 32) <= 512; p.cand_* / p.row_max / p.row_lsum are not used.
-// Logit (row, word) lives at logits[row * ld_row + word * ld_word]: (ld, 1) for the row-major product, (1, ld) for the
-// transposed one.
-int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
-                                 long ld_row, long ld_word, int B, hipStream_t stream, const int32_t* gate = nullptr);
+// What the fused vocabulary tail -- selection or draw + update in one launch, no pass over the logits -- reads of the vocabulary
+// product: the block pieces of its epilogue (GemmArgs::stats / stats_t) and where a logit lives.  One block of arguments for the
+// four launchers below, checked by one validator (beam.hip, fused_tail_ok).
+constexpr int kFusedVocabBlocks = 512;              // 32 words each: vocabularies up to 16 384 words take the fused tail
+struct FusedTail {
+    const float* stats;      // [rows][stats_ld] float2, 16-byte aligned: per 32-word block the maximum and sum exp(x - maximum)
+    int nblk, stats_ld;      // ceil(V / 32) <= kFusedVocabBlocks blocks of a row are valid; stats_ld >= nblk, even
+    long ld_row, ld_word;    // logit (row, word) lives at logits[row * ld_row + word * ld_word]: (ld, 1) for the row-major
+                             // product, (1, ld) for the transposed one
+};
+// The engine's layout of the pieces: rows padded to an even number of blocks (a lane's 16-byte load is one block pair).
+static inline FusedTail ovc_fused_tail(const float* stats, int V, long ld_row, long ld_word) {
+    const int nblk = (V + 31) / 32;
+    return FusedTail{stats, nblk, (nblk + 1) & ~1, ld_row, ld_word};
+}
+// Selection + update.  p.cand_* / p.row_max / p.row_lsum are not used.
+int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, int B, hipStream_t stream,
+                                 const int32_t* gate = nullptr);
 // The constrained search's options (include/ovc.h, ovc_beam_search_constrained): passed to the kernel by value.
 struct BeamConstraints {
     int ngram, min_length, n_banned;                // 0, 0, 0: neutral
@@ -280,8 +292,8 @@ struct BeamConstraints {
 // The options' scope for a model of V words, max_len steps, beam k: include/ovc.h lists the refusals.
 bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k, int eos, int pad);
 // ovc_beam_fused_update_launch with a per-row ban set (p.hist_in holds the rows' histories); p.alive_count must be nullptr.
-int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, const float* running_in,
-                                       long ld_row, long ld_word, const BeamConstraints& cons, int B, hipStream_t stream);
+int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamConstraints& cons,
+                                       int B, hipStream_t stream);
 // Test support: the block pieces [rows][stats_ld] float2 and the transposed logits [V][ldt] of row-major logits [rows][V].
 // parent_out / word_out [B][k]: the beam inside the image and the word of the winners a step t update left in anc / hist [B*k][T].
 int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, int B, int width, int k, int T, int t, int32_t* parent_out,
@@ -289,8 +301,7 @@ int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, in
 int ovc_block_pieces_launch(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t, hipStream_t stream);
 // Sampling in place of the selection (ovc_sample): sample s of image b draws its word from the pieces of its parent row and the
 // bookkeeping is the fused update's.  seed: the device word the draw's Philox key is read from; p.alive_count must be nullptr.
-int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
-                                   const int64_t* seed, int B, hipStream_t stream);
+int ovc_sample_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const int64_t* seed, int B, hipStream_t stream);
 // Shaped sampling (include/ovc.h, ovc_sample_shaped): the options' scope, the chooser and the bookkeeping that takes its word.
 static inline bool ovc_sample_options_ok(float temperature, int top_k, float top_p) {
     // top_p: a normal number, so that top_p * Z1 (Z1 >= 1) never underflows to 0; NaN fails each comparison
@@ -299,8 +310,7 @@ static inline bool ovc_sample_options_ok(float temperature, int top_k, float top
 int ovc_sample_choice_launch(const float* logits, long ld_row, long ld_word, int rows, int V, int draws, const int64_t* seed, int t,
                              float temperature, int top_k, float top_p, float* scratch, int32_t* word_out, int32_t* kept_out,
                              hipStream_t stream);
-int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const float* stats, int nblk, int stats_ld, long ld_row, long ld_word,
-                                    const int32_t* chosen, int B, hipStream_t stream);
+int ovc_sample_shaped_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const int32_t* chosen, int B, hipStream_t stream);
 int ovc_debug_collect_winners_launch(const int32_t* anc, const int32_t* word, const float* running, int B, int width, int V, int k,
                                      int64_t* chosen, float* score, hipStream_t stream);
 int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const float* row_max, const float* row_lsum,

@@ -263,9 +263,8 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
     return w;
 }
 
-// Vocabularies up to this many 32-word blocks take the fused vocabulary tail (the block pieces of the GEMM epilogue), larger
-// ones a row log-softmax -- the search's edge as well (run_decode_step).
-constexpr int kFusedVocabBlocks = 512;
+// Vocabularies up to kFusedVocabBlocks 32-word blocks (common.h) take the fused vocabulary tail (the block pieces of the GEMM
+// epilogue), larger ones a row log-softmax -- the search's edge as well (run_decode_step).
 
 // ovc_forward: rows = B*T decoder rows.  With want_logp the transposed logits [V][rows padded to 4] are kept; scoring alone keeps
 // only the block pieces and one logit per row.  Above kFusedVocabBlocks the row-major logits [rows][V] and, for scoring, the
@@ -1116,6 +1115,8 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     static const bool row_major = OVC_HOOK_ENV("OVC_VOCAB_ROW_MAJOR") != nullptr;        // A/B switch
     const bool transposed = fused_select && m->precision == 0 && !row_major;
     const int ldt = (rows + 3) & ~3;               // row stride of logits^T
+    // what the fused tail reads: the block pieces and logit (row, word), transposed or row-major
+    const FusedTail tail = ovc_fused_tail(w.stats, m->vocab, transposed ? 1 : ldv, transposed ? ldt : 1);
     {
         // K-order class of THIS call site: the transposed product has M = V rows -- thousands of output tiles whatever the batch
         // -- so it needs no chains spread over waves and takes the one-chain class of the other large-M products (a quarter of
@@ -1131,12 +1132,11 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
         } else {
             g.A1 = x; g.lda1 = d; g.K1 = d; g.M = rows; g.seg_n = m->vocab; g.nseg = 1; g.ldc = ldv;
             g.seg[0] = GemmSegment{m->fc, nullptr, w.logits, nullptr, m->precision > 0 ? m->fc_planes : nullptr};
-            g.stats = fused_select ? w.stats : nullptr; g.stats_ld = (nblk + 1) & ~1;
+            g.stats = fused_select ? w.stats : nullptr; g.stats_ld = tail.stats_ld;
         }
         TRY(e.gemm(g));
         e.kchains = saved_chains;
     }
-    const long ld_row = transposed ? 1 : ldv, ld_word = transposed ? ldt : 1;
     BeamUpdateArgs bu{};
     bu.cand_v = w.cand_v; bu.cand_i = w.cand_i; bu.logits = w.logits; bu.ld = ldv;
     bu.row_max = w.row_max; bu.row_lsum = w.row_lsum;
@@ -1153,17 +1153,17 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
         // selection + bookkeeping in one launch, from the block pieces the vocabulary GEMM's epilogue left: no pass over the logits
         bu.row_max_out = return_probs ? w.row_max : nullptr; bu.row_lsum_out = return_probs ? w.row_lsum : nullptr;
         if (c.shaped()) {     // shaped sampling: the chooser reads the rows, the bookkeeping takes its words
-            RUN(ovc_sample_choice_launch(w.logits, ld_row, ld_word, rows, m->vocab, R / rows, w.drop_seed, t, c.temperature, c.top_k, c.top_p,
-                                         w.choice_rows, w.choice_word, w.choice_kept, s));
-            RUN(ovc_sample_shaped_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.choice_word, B, s));
+            RUN(ovc_sample_choice_launch(w.logits, tail.ld_row, tail.ld_word, rows, m->vocab, R / rows, w.drop_seed, t, c.temperature, c.top_k,
+                                         c.top_p, w.choice_rows, w.choice_word, w.choice_kept, s));
+            RUN(ovc_sample_shaped_update_launch(bu, tail, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
-            RUN(ovc_sample_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, ld_row, ld_word, w.drop_seed, B, s));
+            RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
         else if (c.constrained())  // the one branch of a constrained step: the selection with a per-row ban set
-            RUN(ovc_beam_constrained_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, c.cons, B, s));
+            RUN(ovc_beam_constrained_update_launch(bu, tail, w.running[cur], c.cons, B, s));
         else if (!(debug_skip() & 8))
-            RUN(ovc_beam_fused_update_launch(bu, w.stats, nblk, (nblk + 1) & ~1, w.running[cur], ld_row, ld_word, B, s, e.gate));
+            RUN(ovc_beam_fused_update_launch(bu, tail, w.running[cur], B, s, e.gate));
         if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
-            RUN(ovc_masked_logp_launch(w.logits, ld_row, ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab,
+            RUN(ovc_masked_logp_launch(w.logits, tail.ld_row, tail.ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab,
                                        w.all_buf + (size_t)t * R * m->vocab, s));
         return OVC_OK;
     }
@@ -1760,7 +1760,8 @@ extern "C" int ovc_beam_search_constrained_graph(const ovc_model* m, const float
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
-// Test entry: ONE step of the constrained selection -- the production kernel instance -- on caller-given inputs (device memory):
+// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the constrained one
+// with active options, the plain one with neutral options -- on caller-given inputs (device memory):
 // row-major logits [B*width][V], histories hist [B*width][T] (words of steps 0..t-1), running / alive [B*width].  The block pieces
 // are computed here and the logits laid out transposed, as the engine's vocabulary product leaves them.  parent_out / word_out
 // [B][k] (int32), running_out [B][k], row_max_out / row_lsum_out [B*width].  scratch: ovc_debug_beam_constrained_update_bytes.
@@ -1782,28 +1783,31 @@ extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int3
         (V + 31) / 32 > kFusedVocabBlocks || T < 1 || T > OVC_MAX_LEN || t < 0 || t >= T || (width == 1) != (t == 0) || (long)B * k * T > 0x7fffffffL / 8)
         return OVC_EINVAL;
     if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &cons) ||
-        !ovc_beam_constraints_ok(cons, V, T, k, eos, -1))
+        (cons.active() && !ovc_beam_constraints_ok(cons, V, T, k, eos, -1)))      // neutral options: the plain step's scope
         return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_constrained_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
     TRY(ovc_device_guard());
     hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, nblk = (V + 31) / 32, ld = (nblk + 1) & ~1, ldt = (rows + 3) & ~3;
+    const int rows = B * width, ldt = (rows + 3) & ~3;
     const size_t Rk = (size_t)B * k;
     Bump a{reinterpret_cast<char*>(scratch), 0};
     float* logits_t = a.take<float>((size_t)V * ldt);
-    float* stats = a.take<float>(2 * (size_t)rows * ld);
+    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
+    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
+    tail.stats = stats;
     float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
     int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
     float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
     if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
         return OVC_ELAUNCH;
-    TRY(ovc_block_pieces_launch(logits, rows, V, ld, ldt, stats, logits_t, s));
+    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
     BeamUpdateArgs bu{};
     bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
     bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
     bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
     bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
-    TRY(ovc_beam_constrained_update_launch(bu, stats, nblk, ld, running, 1, ldt, cons, B, s));
+    if (cons.active()) TRY(ovc_beam_constrained_update_launch(bu, tail, running, cons, B, s));      // run_decode_step's routing
+    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
     return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
 }
 
@@ -1924,16 +1928,18 @@ extern "C" int ovc_debug_vocab_select(const float* x, const float* fc, const flo
     if (scratch_bytes < ovc_debug_vocab_select_bytes(B, width, V, k) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
     TRY(ovc_device_guard());
     hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, nblk = (V + 31) / 32, ld = (nblk + 1) & ~1, ldv = (V + 3) & ~3, ldt = (rows + 3) & ~3;
+    const int rows = B * width, ldv = (V + 3) & ~3, ldt = (rows + 3) & ~3;
     Bump a{reinterpret_cast<char*>(scratch), 0};
     float* logits = a.take<float>(((size_t)(rows + 3) & ~(size_t)3) * ldv);
-    float* stats = a.take<float>(2 * (size_t)rows * ld);
+    FusedTail tail = ovc_fused_tail(nullptr, V, transposed ? 1 : ldv, transposed ? ldt : 1);
+    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
+    tail.stats = stats;
     float* alive_out = a.take<float>((size_t)B * k); float* running_out = a.take<float>((size_t)B * k);
     float* lp_out = a.take<float>((size_t)B * k);
     int32_t* hist_out = a.take<int32_t>((size_t)B * k); int32_t* anc_out = a.take<int32_t>((size_t)B * k);
     int32_t* next_tok = a.take<int32_t>((size_t)B * k);
     GemmArgs g{};
-    g.kchains = kchains; g.K1 = d; g.lda1 = d; g.nseg = 1; g.stats_ld = ld;     // the fp32 engine: transposed, one chain
+    g.kchains = kchains; g.K1 = d; g.lda1 = d; g.nseg = 1; g.stats_ld = tail.stats_ld;     // the fp32 engine: transposed, one chain
     if (transposed) {
         g.A1 = fc; g.M = V; g.seg_n = rows; g.ldc = ldt; g.seg[0] = GemmSegment{x, nullptr, logits, nullptr, nullptr}; g.stats_t = stats;
     } else {
@@ -1945,7 +1951,7 @@ extern "C" int ovc_debug_vocab_select(const float* x, const float* fc, const flo
     bu.hist_out = hist_out; bu.lp_out = lp_out; bu.anc_out = anc_out; bu.next_tok = next_tok;
     bu.hist_in = hist_out; bu.lp_in = lp_out; bu.anc_in = anc_out;                 // t = 0: nothing is copied from them
     bu.width = width; bu.k = k; bu.V = V; bu.T = 1; bu.t = 0; bu.eos = -1;
-    TRY(ovc_beam_fused_update_launch(bu, stats, nblk, ld, running, transposed ? 1 : ldv, transposed ? ldt : 1, B, s));
+    TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
     return ovc_debug_collect_winners_launch(anc_out, hist_out, running_out, B, width, V, k, chosen, score, s);
 }
 

@@ -195,6 +195,53 @@ def test_kernel_all_logits_equal(Vv):
     assert (parents.numpy() == 0).all() and words.numpy().tolist() == [[0, 1, 7, 8, 9]] * 3     # 2 = <eos>, 3 5 banned, 4 6 history
 
 
+def _neutral_cases(Vv, k):
+    """The steps of the two tests below: t = 0 (width 1) and, for k > 1, t = 4 of T = 6 with the frozen rows ``_case`` makes."""
+    yield 0, _case(Vv, k, 0, 6, seed=17 * Vv + k)
+    if k > 1:
+        yield 4, _case(Vv, k, 4, 6, seed=19 * Vv + k)
+
+
+@pytest.mark.parametrize("Vv", [53, 4099])
+@pytest.mark.parametrize("k", [1, 5, 8])
+def test_plain_instance_equals_the_rule(Vv, k):
+    """Neutral options: the entry launches the plain instance (``run_decode_step``'s routing) -- histories, t > 0 and frozen rows
+    included.  V = 53: two blocks, the last one partial; V = 4099: 129 blocks, past one 128-block load round, the last one partial."""
+    for t, (logits, hist, running, alive, _) in _neutral_cases(Vv, k):
+        _check_step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL)
+
+
+def test_plain_instance_all_logits_equal():
+    """The massive tie of ``test_kernel_all_logits_equal`` at V = 4099 without a ban: the lists overflow into the exhaustive path,
+    and the winners are the lowest flat indices."""
+    k, t = 5, 3
+    logits, hist, running, alive, _ = _case(4099, k, t, 6, seed=2, frozen=False)
+    logits[:] = 1.25
+    running[:] = -1.0
+    parents, words = _check_step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL)
+    assert (parents.numpy() == 0).all() and words.numpy().tolist() == [[0, 1, 2, 3, 4]] * 3
+
+
+@pytest.mark.parametrize("Vv", [53, 4099])
+@pytest.mark.parametrize("k", [1, 5, 8])
+def test_both_instances_take_the_same_decisions(Vv, k):
+    """One step through the plain instance (neutral options) and through the ban instance with a ban that binds on nothing: a word
+    no row would pick.  All five outputs are equal."""
+    w = 41
+    assert w not in (PAD, EOS)
+    for t, (logits, hist, running, alive, _) in _neutral_cases(Vv, k):
+        logits[:, w] = -60.0
+        plain = _step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL)
+        ban = _step(logits, hist, running, alive, k, t, EOS, (0, 0, (w,)))
+        # a condition on the inputs: the rule gives the same winners with and without the ban
+        free = _mirror_step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL, plain[3], plain[4])
+        bound = _mirror_step(logits, hist, running, alive, k, t, EOS, (0, 0, (w,)), plain[3], plain[4])
+        assert all(np.array_equal(a, b) for a, b in zip(free, bound))
+        for name, a, b in zip(("parents", "words", "running_out", "M", "ls"), plain, ban):
+            assert torch.equal(a, b), (t, name)
+        assert np.array_equal(plain[0].numpy(), free[0]) and np.array_equal(plain[1].numpy(), free[1])
+
+
 def test_kernel_nan_row_and_frozen_rows():
     k, t = 5, 2
     logits, hist, running, alive, _ = _case(4099, k, t, 6, seed=6)
@@ -456,6 +503,34 @@ def test_refusals_name_the_argument_and_draw_nothing():
                                                      ws.data_ptr(), need, ids.data_ptr(), logp.data_ptr(), native.stream_handle()) == -1
     torch.cuda.synchronize()
     assert bool((ids == -5).all()) and bool((logp == 7.0).all())
+    # the step entries, one refusal per launcher of the fused tail (the samplers': tests/test_sample_gpu.py::test_refusals_come_
+    # before_any_draw and tests/test_sample_shaped_gpu.py::test_bad_options_are_refused_by_name_before_any_draw): OVC_EINVAL,
+    # nothing written.  The plain launcher: more than 512 blocks; the step entry of both selections: a width that is neither 1 nor k
+    big_v, dd = 512 * 32 + 1, 4
+    x, fc = torch.zeros(2, dd, device="cuda"), torch.zeros(big_v, dd, device="cuda")
+    run2, alive2 = torch.zeros(2, device="cuda"), torch.ones(2, device="cuda")
+    chosen = torch.full((2, 2), -5, dtype=torch.int64, device="cuda")
+    score = torch.full((2, 2), 7.0, device="cuda")
+    sel = torch.empty(lib.ovc_debug_vocab_select_bytes(2, 1, big_v, 2), dtype=torch.uint8, device="cuda")
+    for transposed, chains in ((1, 1), (0, 4)):
+        assert lib.ovc_debug_vocab_select(x.data_ptr(), fc.data_ptr(), run2.data_ptr(), alive2.data_ptr(), 2, 1, big_v, dd, 2, transposed,
+                                          chains, sel.data_ptr(), sel.numel(), chosen.data_ptr(), score.data_ptr(),
+                                          native.stream_handle()) == -1
+    torch.cuda.synchronize()
+    assert bool((chosen == -5).all()) and bool((score == 7.0).all())
+    kk, width, Tt = 4, 2, 6                                           # four beams, two rows per image
+    lg, hs = torch.zeros(2 * width, 53, device="cuda"), torch.zeros(2 * width, Tt, dtype=torch.int32, device="cuda")
+    run4, alive4 = torch.zeros(2 * width, device="cuda"), torch.ones(2 * width, device="cuda")
+    step = torch.empty(lib.ovc_debug_beam_constrained_update_bytes(2, width, 53, kk, Tt), dtype=torch.uint8, device="cuda")
+    par, wrd = (torch.full((2, kk), -5, dtype=torch.int32, device="cuda") for _ in range(2))
+    run_out, Mo, lso = torch.full((2, kk), 7.0, device="cuda"), torch.full((2 * width,), 7.0, device="cuda"), torch.full((2 * width,), 7.0, device="cuda")
+    for n, L, banned in ((0, 0, ()), (1, 0, (UNK,))):                 # the plain instance's routing and the ban instance's
+        assert lib.ovc_debug_beam_constrained_update(lg.data_ptr(), hs.data_ptr(), run4.data_ptr(), alive4.data_ptr(), 2, width, 53, kk, Tt, 3,
+                                                     EOS, n, L, arr(*banned), len(banned), step.data_ptr(), step.numel(), par.data_ptr(),
+                                                     wrd.data_ptr(), run_out.data_ptr(), Mo.data_ptr(), lso.data_ptr(),
+                                                     native.stream_handle()) == -1
+    torch.cuda.synchronize()
+    assert bool((par == -5).all()) and bool((wrd == -5).all()) and all(bool((o == 7.0).all()) for o in (run_out, Mo, lso))
     # in scope: the C entry gives the Python call's bits
     want_ids, want_logp = _search(model, items, no_repeat_ngram_size=2, banned_words=[UNK])
     assert lib.ovc_beam_search_constrained(ctypes.byref(d), f.data_ptr(), None, B, N, K, K, 2, 0, arr(UNK), 1, ws.data_ptr(), need,

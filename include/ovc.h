@@ -602,6 +602,46 @@ int ovc_debug_beam_constrained_update(const float* logits, const int32_t* hist, 
                                       int n_banned, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
                                       float* running_out, float* row_max_out, float* row_lsum_out, ovc_stream stream);
 
+/* Ensemble beam search: ONE search over the mean of the log-probabilities of M models (the meshed-memory authors'
+ * TransformerEnsemble).  Members m = 0..M-1, 1 <= M <= OVC_MAX_ENSEMBLE, read the same features (and the call's boxes, where a
+ * member's encoder takes boxes); at every step each member runs its own decoder step on the SAME beams -- the same words, the same
+ * ancestor table, the same pad flags -- and the selection ranks, for beam row r and word w,
+ *     lp_m = (x_m[r,w] - M_m[r]) - ls_m[r]        ovc_beam_search's arithmetic per member (M_m, ls_m: the pieces of member m's row)
+ *     sum  = M=1: lp_0   M=2: lp_0+lp_1   M=3: (lp_0+lp_1)+lp_2   M=4: (lp_0+lp_1)+(lp_2+lp_3)        fp32, in this order
+ *     mean = sum / (float)M                         a true fp32 division
+ *     cand = run[r] + mean
+ * Everything else is ovc_beam_search: score descending, ties to the lower flat index row * V + w; a frozen beam offers word 0 at its
+ * running score and -999 for words 1..k-1; logp_out is mean * alive and all_logp_out is mean * alive for every word; slot j takes
+ * word j of beam 0 when no candidate compares (NaN rows); the final ordering and out_size are unchanged.
+ * The mean of log-probabilities is NOT renormalised (exp(mean) does not sum to 1 over the words): the convention of the ensembles
+ * in the literature.  M = 1 is ovc_beam_search[_graph] itself: the same launches, the same graph entry, the same bits.  M identical
+ * members, M in {2, 4}, return the single model's bits (x + x, 2x + 2x and the divisions by 2 and 4 are exact).
+ * Scope (anything else: OVC_EINVAL / a size of 0, nothing launched): every member in the plain search's scope on its own, fp32
+ * (precision 0), at most 16 384 words; equal vocab, max_len, bos / eos / pad indices and d_feat; no dropout, sampling, constraints
+ * or early exit; 1 <= M <= OVC_MAX_ENSEMBLE.  Weighted means, means of probabilities, gradients and several devices are not covered.
+ * models: M pointers in HOST memory.  workspace: ovc_ensemble_workspace_bytes (M = 1: ovc_workspace_bytes), one buffer -- the
+ * members' workspaces one behind the other, the beam state in member 0's.  ovc_ensemble_ok: 1 in scope, else 0; launches nothing.
+ * ovc_ensemble_beam_search: plain launches, all_logp_out optional.  ovc_ensemble_beam_search_graph: one captured graph from the
+ * second call of its key (every member's contents, in member order, are part of the key).
+ * ovc_debug_ensemble_update: test entry, ONE step of the ensemble selection kernel on device inputs: row-major logits
+ * [M][B*width][V], running / alive [B*width], width = 1 at t = 0 and k at t > 0.  Outputs: parent_out / word_out (int32) / running_out / logp_out
+ * [B][k], row_max_out / row_lsum_out [M][B*width], hot_out [B] (int32): the blocks the image read to rank its candidates, or -1
+ * when it ranked all width * V candidates.  scratch: ovc_debug_ensemble_update_bytes. */
+#define OVC_MAX_ENSEMBLE 4
+int ovc_ensemble_ok(const ovc_model* const* models, int M, int B, int N, int k);
+size_t ovc_ensemble_workspace_bytes(const ovc_model* const* models, int M, int B, int N, int k, int return_probs);
+int ovc_ensemble_beam_search(const ovc_model* const* models, int M, const float* features, const float* boxes, int B, int N, int k,
+                             int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                             float* all_logp_out, ovc_stream stream);
+int ovc_ensemble_beam_search_graph(const ovc_model* const* models, int M, const float* features, const float* boxes, int B, int N,
+                                   int k, int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                   ovc_stream stream);
+size_t ovc_debug_ensemble_update_bytes(int M, int B, int width, int V, int k);
+int ovc_debug_ensemble_update(const float* logits, const float* running, const float* alive, int M, int B, int width, int V, int k,
+                              int t, int eos, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
+                              float* running_out, float* logp_out, float* row_max_out, float* row_lsum_out, int32_t* hot_out,
+                              ovc_stream stream);
+
 /* The SCST reward: CIDEr-D of generated captions against a fixed reference corpus, from token ids (the reference computes it on
  * the host from strings: vi_trainer.py:141-147 through evaluation/cider/cider_scorer.py).  The tables are built once on the host
  * (openviic_amd/cider.py) in float64.  An n-gram (n = 1..4) of word ids below 65535 is ONE 64-bit key: word j of the n-gram sits as

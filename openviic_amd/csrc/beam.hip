@@ -252,6 +252,54 @@ __global__ __launch_bounds__(kFusedThreads) void beam_constrained_update_kernel(
 #include "bodies/beam_fused_update.inc"
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Ensemble selection (ovc_ensemble_beam_search, include/ovc.h: the rule): one search over the mean of kM members' log-probabilities.
+// The mean of a word, in the rule's order: lp_0 | lp_0 + lp_1 | (lp_0 + lp_1) + lp_2 | (lp_0 + lp_1) + (lp_2 + lp_3), then a true
+// division by kM.  Pairwise, so that identical members give x + x and 2x + 2x (exact) and the divisions by 2 and 4 return the single
+// model's bits; never a running sum, never a product with 1 / kM.
+template <int kM>
+__device__ __forceinline__ float ens_mean(const float (&lp)[kM]) {
+    static_assert(kM >= 1 && kM <= OVC_MAX_ENSEMBLE && OVC_MAX_ENSEMBLE == 4, "the rule names the order for one to four members");
+    if constexpr (kM == 1) return lp[0] / 1.0f;
+    else if constexpr (kM == 2) return (lp[0] + lp[1]) / 2.0f;
+    else if constexpr (kM == 3) return ((lp[0] + lp[1]) + lp[2]) / 3.0f;
+    else return ((lp[0] + lp[1]) + (lp[2] + lp[3])) / 4.0f;
+}
+
+// One workgroup (512 threads) per image, the plain fused selection's layout.  With several members "every block maximum is itself
+// a candidate" no longer holds -- the members' maxima sit at different words -- so a block's U_b = run + mean_m(its maxima's lp) is
+// an upper bound only (sound in fp32 without an epsilon: the same operations in the same order on larger operands, and rounding
+// is monotone) and the lower bound comes from exact scores: each row reads its k blocks of largest U in full (32 words x kM logits
+// each).  Blocks with U_b >= the bound are hot and are scored exactly, kM reads per word; the ranking, the frozen beams' offers, the
+// exhaustive path and phase D are the plain kernel's, with the recorded log-prob mean * alive, and the next input rows are written
+// for every member from its own embedding table.  Members that disagree make many blocks hot: the hot list holds every block of
+// every row (it cannot overflow), and a survivor list that overflows tightens the bound from its own entries and gathers again, so
+// only massive ties reach the exhaustive path.  LDS (static: the compiler refuses more than the workgroup's 64 KB): the plain
+// instance's 14 KB + 10.5 KB for the longer hot list + 64 B of pieces per further member = 25 KB.  The ordinary step reads no logit
+// row.
+constexpr int kEnsHotCap = kMaxK * kFusedVocabBlocks;    // 4096 (row, block) pairs: 8 KB of block ids + 4 KB of rows
+template <int kM>
+__global__ __launch_bounds__(kFusedThreads) void beam_ensemble_update_kernel(EnsembleUpdateArgs a) {
+#include "bodies/beam_ensemble_update.inc"
+}
+
+// all_logp_out's rows of an ensemble step: mean_m((x_m - row_max_m) - row_lsum_m) * alive for every word, the selection's arithmetic.
+template <int kM>
+__global__ __launch_bounds__(256) void ensemble_masked_logp_kernel(EnsembleLogpArgs a) {
+    const int row = blockIdx.x;
+    const float al = a.alive ? a.alive[row] : 1.0f;
+    float m[kM], l[kM];
+#pragma unroll
+    for (int e = 0; e < kM; ++e) { m[e] = a.row_max[e][row]; l[e] = a.row_lsum[e][row]; }
+    float* y = a.out + (size_t)row * a.V;
+    for (int c = threadIdx.x; c < a.V; c += 256) {
+        float lp[kM];
+#pragma unroll
+        for (int e = 0; e < kM; ++e) lp[e] = (a.logits[e][(size_t)row * a.ld_row[e] + (size_t)c * a.ld_word[e]] - m[e]) - l[e];
+        y[c] = ens_mean<kM>(lp) * al;
+    }
+}
+
 // The block pieces of row-major logits [rows][V] as the vocabulary product's epilogue leaves them -- per (row, 32-word block) the
 // maximum and sum exp(x - maximum) -- and the logits laid out transposed, the engine's form (ovc_debug_beam_constrained_update).
 // One wave per (row, block pair group): lane l < 32 holds word l of the block.
@@ -470,6 +518,42 @@ int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail&
     for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
                        f.ld_row, f.ld_word, cons);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+// The ensemble step: every member's tail passes the fused tail's validator with the shared shape, and what the kernel indexes with
+// a member's own strides and widths is checked here.  No gated instance: the early-exit forms are out of the ensemble's scope.
+int ovc_beam_ensemble_update_launch(const EnsembleUpdateArgs& a, int B, hipStream_t stream) {
+    const BeamUpdateArgs& p = a.p;
+    if (a.M < 1 || a.M > OVC_MAX_ENSEMBLE || !a.running_in || (long)p.width * p.V < p.k || p.alive_count) return OVC_EINVAL;
+    if (p.T < 1 || p.t < 0 || p.t >= p.T) return OVC_EINVAL;
+    for (int e = 0; e < a.M; ++e) {
+        if (!fused_tail_ok(p, a.tail[e], B) || !a.logits[e] || (a.row_max_out[e] == nullptr) != (a.row_lsum_out[e] == nullptr)) return OVC_EINVAL;
+        if (p.next_x && (!a.word_emb[e] || !a.pos_emb[e] || !a.next_x[e] || a.d_model[e] <= 0 || (a.d_model[e] & 3))) return OVC_EINVAL;
+    }
+    if (p.next_x && (a.word_emb[0] != p.word_emb || a.pos_emb[0] != p.pos_emb || a.next_x[0] != p.next_x || a.d_model[0] != p.d_model))
+        return OVC_EINVAL;
+    switch (a.M) {
+    case 1: hipLaunchKernelGGL(beam_ensemble_update_kernel<1>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(beam_ensemble_update_kernel<2>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(beam_ensemble_update_kernel<3>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
+    default: hipLaunchKernelGGL(beam_ensemble_update_kernel<4>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
+    }
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_ensemble_masked_logp_launch(const EnsembleLogpArgs& a, int rows, hipStream_t stream) {
+    if (a.M < 1 || a.M > OVC_MAX_ENSEMBLE || rows <= 0 || a.V <= 0 || !a.out) return OVC_EINVAL;
+    for (int e = 0; e < a.M; ++e)
+        if (!a.logits[e] || !a.row_max[e] || !a.row_lsum[e] || a.ld_row[e] <= 0 || a.ld_word[e] <= 0) return OVC_EINVAL;
+    switch (a.M) {
+    case 1: hipLaunchKernelGGL(ensemble_masked_logp_kernel<1>, dim3(rows), dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(ensemble_masked_logp_kernel<2>, dim3(rows), dim3(256), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(ensemble_masked_logp_kernel<3>, dim3(rows), dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(ensemble_masked_logp_kernel<4>, dim3(rows), dim3(256), 0, stream, a); break;
+    }
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -294,6 +294,30 @@ bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k
 // ovc_beam_fused_update_launch with a per-row ban set (p.hist_in holds the rows' histories); p.alive_count must be nullptr.
 int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamConstraints& cons,
                                        int B, hipStream_t stream);
+// The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
+// log-probabilities and the bookkeeping, one launch.  One argument block, by value: p is member 0's -- the shared beam state, and
+// member 0's embedding tables / next_x / d_model for the next step's input rows -- and every member's tail, logits, embedding
+// tables and next input rows follow ([0] repeats p's).  p.logits / p.row_max_out / p.row_lsum_out / p.alive_count are not used.
+struct EnsembleUpdateArgs {
+    BeamUpdateArgs p;
+    int M;
+    FusedTail tail[OVC_MAX_ENSEMBLE];               // equal nblk; every member's own pieces and strides
+    const float* logits[OVC_MAX_ENSEMBLE];
+    const float* word_emb[OVC_MAX_ENSEMBLE]; const float* pos_emb[OVC_MAX_ENSEMBLE];
+    float* next_x[OVC_MAX_ENSEMBLE]; int d_model[OVC_MAX_ENSEMBLE];     // next_x[m]: [B*k][d_model[m]], with p.next_x set
+    float* row_max_out[OVC_MAX_ENSEMBLE]; float* row_lsum_out[OVC_MAX_ENSEMBLE];   // [B*width] per member, or nullptr
+    const float* running_in;
+    int32_t* hot_out;                               // [B] or nullptr: the hot blocks the image read, -1 = the exhaustive path
+};
+int ovc_beam_ensemble_update_launch(const EnsembleUpdateArgs& a, int B, hipStream_t stream);
+// out[row, c] = mean_m((x_m[row, c] - row_max_m[row]) - row_lsum_m[row]) * alive[row]: the ensemble's all_logp_out rows.
+struct EnsembleLogpArgs {
+    int M, V;
+    const float* logits[OVC_MAX_ENSEMBLE]; long ld_row[OVC_MAX_ENSEMBLE], ld_word[OVC_MAX_ENSEMBLE];
+    const float* row_max[OVC_MAX_ENSEMBLE]; const float* row_lsum[OVC_MAX_ENSEMBLE];
+    const float* alive; float* out;
+};
+int ovc_ensemble_masked_logp_launch(const EnsembleLogpArgs& a, int rows, hipStream_t stream);
 // Test support: the block pieces [rows][stats_ld] float2 and the transposed logits [V][ldt] of row-major logits [rows][V].
 // parent_out / word_out [B][k]: the beam inside the image and the word of the winners a step t update left in anc / hist [B*k][T].
 int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, int B, int width, int k, int T, int t, int32_t* parent_out,

@@ -138,6 +138,9 @@ struct Workspace {
     // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
     // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
+    // ensemble search: the M members' workspaces, [0] this one (nullptr otherwise).  The beam state -- running, alive, hist, lp, anc,
+    // tok, padflag, order, the out buffers -- lives once, here; the other members' structs alias those pointers and own the rest
+    Workspace* peers;
     size_t bytes;
 };
 
@@ -896,6 +899,10 @@ struct SearchCall {
     bool has_options; float temperature; int top_k; float top_p;
     // Constrained search (ovc_beam_search_constrained): the ban options, banned ids sorted; all zero: the plain search.
     BeamConstraints cons;
+    // Ensemble (ovc_ensemble_beam_search): ens_M > 1 members, ens[0] the call's model; every step runs each member's decoder rows
+    // on the shared beams and selects on the mean of their log-probabilities.  One member is the plain call: ens_M stays 0.
+    int ens_M; const ovc_model* ens[OVC_MAX_ENSEMBLE];
+    bool ensemble() const { return ens_M > 1; }
     bool constrained() const { return cons.active(); }
     bool shaped() const { return sample && has_options && !(temperature == 1.0f && top_k == 0 && top_p == 1.0f); }
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
@@ -906,6 +913,26 @@ bool dropout_train_ok(const ovc_model* m, int B, int N, int T);     // the dropo
 // The models a form runs: the part of the scope that is checked before the device is touched.
 bool search_model_ok(const ovc_model* m, const SearchCall& c) {
     return model_ok(m) && (c.form != SearchForm::Gated || m->precision == 0);
+}
+
+bool search_ok(const ovc_model* m, const SearchCall& c);
+
+// The scope of an ensemble: every member in the plain search's scope on its own, fp32 with the fused vocabulary tail, the members in
+// agreement on everything the shared beam state and the one selection depend on, plain launches or the whole-search graph, and
+// nothing else in the call.
+bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
+    if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
+    if (c.plan || c.sample || c.has_options || c.constrained() || (c.form != SearchForm::Plain && c.form != SearchForm::Graph)) return false;
+    SearchCall alone = c;
+    alone.ens_M = 0;
+    for (int i = 0; i < c.ens_M; ++i) {
+        const ovc_model* e = c.ens[i];
+        if (!search_ok(e, alone) || e->precision != 0 || (e->vocab + 31) / 32 > kFusedVocabBlocks) return false;
+        if (e->vocab != m->vocab || e->max_len != m->max_len || e->bos_idx != m->bos_idx || e->eos_idx != m->eos_idx ||
+            e->pad_idx != m->pad_idx || e->d_feat != m->d_feat)
+            return false;
+    }
+    return true;
 }
 
 // The scope of a search, for the sizers (out_size = k) and the entry points alike.
@@ -921,6 +948,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                             (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
                             !ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)))
         return false;
+    if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
 }
 
@@ -935,6 +963,25 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
         w.bytes = (a.off + 255) & ~(size_t)255;
     }
     return w;
+}
+
+// An ensemble's buffer: the members' search workspaces one behind the other, each with the plain layout (so the size is the sum of
+// the members' own), and the beam state once, in member 0's: the other members' structs alias it.  ws: OVC_MAX_ENSEMBLE slots.
+size_t carve_ensemble(const SearchCall& c, void* base, Workspace* ws) {
+    size_t off = 0;
+    for (int i = 0; i < c.ens_M; ++i) {
+        ws[i] = carve_search(c.ens[i], base ? reinterpret_cast<char*>(base) + off : nullptr, c);
+        off += ws[i].bytes;
+        ws[i].peers = ws;
+        if (i == 0) continue;
+        const Workspace& s = ws[0];
+        for (int j = 0; j < 2; ++j) {
+            ws[i].running[j] = s.running[j]; ws[i].alive[j] = s.alive[j]; ws[i].hist[j] = s.hist[j]; ws[i].lp[j] = s.lp[j]; ws[i].anc[j] = s.anc[j];
+        }
+        ws[i].tok = s.tok; ws[i].padflag = s.padflag; ws[i].order = s.order; ws[i].out_ids = s.out_ids; ws[i].out_logp = s.out_logp;
+        ws[i].all_buf = s.all_buf;
+    }
+    return off;
 }
 
 // One pass over the decoder's layers, described once: a decode step of a search (run_decode_step) or the teacher-forced decoder
@@ -1060,16 +1107,20 @@ GemmArgs transposed_vocab_product(const ovc_model* m, const float* x, int rows, 
     return g;
 }
 
-// Step t of a search.  Gated: every launch of step t >= 1 is gated on alive_count[t - 1]; the early-exit forms count live beams.
-int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
+// What a model's rows of step t leave for the selection: the form the vocabulary product ran in and what a fused tail reads of it.
+struct StepRows { bool fused_select, transposed; int ldv; FusedTail tail; };
+
+// A model's share of step t, up to its logits: the input rows (t = 0; later the previous step's update kernel has written them),
+// the decoder's layers on the rows of step t and the vocabulary product.  The search's model runs it, and so does every member of an
+// ensemble on its own workspace (Engine::m and w are the member's; the beams -- w.anc, w.padflag -- are the shared ones).
+// Engine::gate stays with the caller.
+int run_step_rows(Engine& e, Workspace& w, const SearchCall& c, int t, StepRows* out) {
     const ovc_model* m = e.m;
     const int B = c.B, N = c.N, k = c.k;
-    const bool return_probs = c.all_logp_out != nullptr, count_alive = c.counts_alive();
-    e.gate = c.form == SearchForm::Gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
     hipStream_t s = e.stream;
     const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, T = m->max_len;
     const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
-    const int cur = t & 1, nxt = cur ^ 1;
+    const int cur = t & 1;
     uint8_t* padflag_t = w.padflag + (size_t)t * R;
     // ovc_beam_search_dropout: this step's rows key the decoder sites' masks; without a plan no site is on and the launches are
     // the plain ones
@@ -1137,6 +1188,48 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
         TRY(e.gemm(g));
         e.kchains = saved_chains;
     }
+    *out = StepRows{fused_select, transposed, ldv, tail};
+    return OVC_OK;
+}
+
+// Step t of a search.  Gated: every launch of step t >= 1 is gated on alive_count[t - 1]; the early-exit forms count live beams.
+int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
+    const ovc_model* m = e.m;
+    const int B = c.B, k = c.k;
+    const bool return_probs = c.all_logp_out != nullptr, count_alive = c.counts_alive();
+    e.gate = c.form == SearchForm::Gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
+    hipStream_t s = e.stream;
+    const int d = m->d_model, T = m->max_len;
+    const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
+    const int cur = t & 1, nxt = cur ^ 1;
+    StepRows sr{};
+    TRY(run_step_rows(e, w, c, t, &sr));
+    const bool fused_select = sr.fused_select;
+    const int ldv = sr.ldv;
+    const FusedTail tail = sr.tail;
+    // Ensemble: the other members' rows behind member 0's, in member order on the one stream -- the same beams (w.tok, the ancestor
+    // table and the pad flags are shared), each member's own caches, logits and pieces -- and the one argument block of the selection
+    EnsembleUpdateArgs en{};
+    if (c.ensemble()) {
+        if (e.dry) return OVC_EINVAL;
+        en.M = c.ens_M;
+        for (int i = 0; i < c.ens_M; ++i) {
+            Workspace& wi = w.peers[i];
+            const ovc_model* mi = c.ens[i];
+            StepRows ri = sr;
+            if (i > 0) {
+                Engine me = e;
+                me.m = mi;
+                TRY(run_step_rows(me, wi, c, t, &ri));
+            }
+            if (!ri.fused_select || !ri.transposed) return OVC_EINVAL;      // search_ok: fp32 and the fused tail, for every member
+            en.tail[i] = ri.tail;
+            en.logits[i] = wi.logits;
+            en.row_max_out[i] = return_probs ? wi.row_max : nullptr; en.row_lsum_out[i] = return_probs ? wi.row_lsum : nullptr;
+            if (t + 1 < T) { en.word_emb[i] = mi->word_emb; en.pos_emb[i] = mi->pos_emb; en.next_x[i] = wi.x; en.d_model[i] = mi->d_model; }
+        }
+        en.running_in = w.running[cur];
+    }
     BeamUpdateArgs bu{};
     bu.cand_v = w.cand_v; bu.cand_i = w.cand_i; bu.logits = w.logits; bu.ld = ldv;
     bu.row_max = w.row_max; bu.row_lsum = w.row_lsum;
@@ -1152,6 +1245,20 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     if (fused_select) {
         // selection + bookkeeping in one launch, from the block pieces the vocabulary GEMM's epilogue left: no pass over the logits
         bu.row_max_out = return_probs ? w.row_max : nullptr; bu.row_lsum_out = return_probs ? w.row_lsum : nullptr;
+        if (c.ensemble()) {   // the one branch of an ensemble step: the selection over the mean of the members' log-probabilities
+            en.p = bu;
+            RUN(ovc_beam_ensemble_update_launch(en, B, s));
+            if (return_probs) {
+                EnsembleLogpArgs lg{};
+                lg.M = c.ens_M; lg.V = m->vocab; lg.alive = w.alive[cur]; lg.out = w.all_buf + (size_t)t * R * m->vocab;
+                for (int i = 0; i < c.ens_M; ++i) {
+                    lg.logits[i] = en.logits[i]; lg.ld_row[i] = en.tail[i].ld_row; lg.ld_word[i] = en.tail[i].ld_word;
+                    lg.row_max[i] = en.row_max_out[i]; lg.row_lsum[i] = en.row_lsum_out[i];
+                }
+                RUN(ovc_ensemble_masked_logp_launch(lg, rows, s));
+            }
+            return OVC_OK;
+        }
         if (c.shaped()) {     // shaped sampling: the chooser reads the rows, the bookkeeping takes its words
             RUN(ovc_sample_choice_launch(w.logits, tail.ld_row, tail.ld_word, rows, m->vocab, R / rows, w.drop_seed, t, c.temperature, c.top_k,
                                          c.top_p, w.choice_rows, w.choice_word, w.choice_kept, s));
@@ -1261,6 +1368,12 @@ int issue_search_prologue(Engine& e, Workspace& w, const SearchCall& c) {
     const int R = c.B * c.k;
     TRY(run_encoder_layers(e, w, c.B, c.N));
     TRY(project_cross_kv(e, w, c.B, c.N));
+    for (int i = 1; i < c.ens_M; ++i) {           // ensemble: the other members' encoders and cross keys / values, in member order
+        Engine me = e;
+        me.m = c.ens[i];
+        TRY(run_encoder_layers(me, w.peers[i], c.B, c.N));
+        TRY(project_cross_kv(me, w.peers[i], c.B, c.N));
+    }
     hipLaunchKernelGGL(init_beam_state_kernel, dim3((R + 255) / 256), dim3(256), 0, e.stream, w.running[0], w.alive[0], R);
     OVC_RETURN_IF_LAUNCH_FAILED();
     if (c.counts_alive() && hipMemsetAsync(w.alive_count, 0, sizeof(int32_t) * e.m->max_len, e.stream) != hipSuccess) return OVC_ELAUNCH;
@@ -1374,6 +1487,7 @@ enum class GraphKind {
     SampleSearch,       // ovc_sample_graph (k = out_size = S, the samples per image; the seed is read from its workspace slot)
     ShapedSampleSearch, // ovc_sample_shaped_graph with options that are not neutral (as SampleSearch; the options in the hash)
     ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
+    EnsembleSearch,     // ovc_ensemble_beam_search_graph with more than one member (as Search; every member's contents in the hash)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1527,6 +1641,11 @@ int write_search_slots(Engine& e, Workspace& w, const SearchCall& c, int steps_h
 // whole-search graph and the per-step graphs share Search and live in different maps (g_graphs, g_early).  The dropout plan's
 // constants are hashed in -- 0 without a plan, so a search with dropout never shares an entry with the plain one.
 GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* workspace) {
+    if (c.ensemble()) {       // every member's contents, chained in member order: another member, or another order, is another key
+        uint64_t h = 0;
+        for (int i = 0; i < c.ens_M; ++i) h = (h ^ hash_bytes(c.ens[i], sizeof(ovc_model))) * 1099511628211ull;
+        return GraphKey{GraphKind::EnsembleSearch, h, workspace, c.B, c.N, c.k, c.out_size};
+    }
     if (c.shaped()) {
         const struct { float temperature; int top_k; float top_p; } options{c.temperature, c.top_k, c.top_p};
         return GraphKey{GraphKind::ShapedSampleSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N,
@@ -1636,8 +1755,13 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     TRY(ovc_device_guard());
     if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    Workspace w = carve_search(m, workspace, c);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    for (int i = 1; i < c.ens_M; ++i)              // before any launch: a member that takes boxes needs the call's
+        if (c.ens[i]->enc_kind == OVC_ENC_GEOMETRIC && (!boxes || !c.ens[i]->fc_g_w || !c.ens[i]->fc_g_b)) return OVC_EINVAL;
+    Workspace members[OVC_MAX_ENSEMBLE];          // ensemble: every member's workspace; w is member 0's and holds the beam state
+    const size_t need = c.ensemble() ? carve_ensemble(c, workspace, members) : 0;
+    Workspace& w = members[0];
+    if (!c.ensemble()) w = carve_search(m, workspace, c);
+    if ((c.ensemble() ? need : w.bytes) > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
     const int T = m->max_len;
     if (c.plan) {                                  // the seed slot is refreshed here, outside any captured body
@@ -1648,6 +1772,11 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     if (c.sample && hipMemcpyAsync(w.drop_seed, c.sample_seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
         return OVC_ELAUNCH;                        // the same slot, refreshed the same way: a replayed graph reads this call's seed
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
+    for (int i = 1; i < c.ens_M; ++i) {            // every member reads the call's features, and its boxes where its encoder takes them
+        Engine me = e;
+        me.m = c.ens[i];
+        TRY(run_encoder_inputs(me, members[i], features, boxes, c.B, c.N));
+    }
 
     auto body = [&](Engine& ce) { return issue_search_body(ce, w, c); };
     int steps_run = T;                             // decode steps issued: fewer only from HostEarly
@@ -1809,6 +1938,108 @@ extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int3
     if (cons.active()) TRY(ovc_beam_constrained_update_launch(bu, tail, running, cons, B, s));      // run_decode_step's routing
     else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
     return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ensemble search (include/ovc.h: the rule).  M models, one search over the mean of their log-probabilities; one member is the
+// plain call, launch for launch (the same SearchCall, hence the same graph key and workspace).
+// ---------------------------------------------------------------------------------------------
+// The call's members; false: M outside 1..OVC_MAX_ENSEMBLE or a null pointer.  The rest of the scope is ensemble_ok's, inside search_ok.
+static bool members_from(const ovc_model* const* models, int M, SearchCall* c) {
+    if (!models || M < 1 || M > OVC_MAX_ENSEMBLE) return false;
+    for (int i = 0; i < M; ++i) if (!models[i]) return false;
+    if (M == 1) return true;
+    c->ens_M = M;
+    for (int i = 0; i < M; ++i) c->ens[i] = models[i];
+    return true;
+}
+
+extern "C" size_t ovc_ensemble_workspace_bytes(const ovc_model* const* models, int M, int B, int N, int k, int return_probs) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (!members_from(models, M, &c) || !search_ok(models[0], c)) return 0;
+    Workspace members[OVC_MAX_ENSEMBLE];
+    return c.ensemble() ? carve_ensemble(c, nullptr, members) : carve_search(models[0], nullptr, c).bytes;
+}
+
+extern "C" int ovc_ensemble_ok(const ovc_model* const* models, int M, int B, int N, int k) {
+    return ovc_ensemble_workspace_bytes(models, M, B, N, k, 0) != 0 ? 1 : 0;
+}
+
+extern "C" int ovc_ensemble_beam_search(const ovc_model* const* models, int M, const float* features, const float* boxes, int B, int N,
+                                        int k, int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                        float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    if (!members_from(models, M, &c)) return OVC_EINVAL;
+    return run_search(models[0], c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_ensemble_beam_search_graph(const ovc_model* const* models, int M, const float* features, const float* boxes, int B,
+                                              int N, int k, int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                              float* logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out};
+    if (!members_from(models, M, &c)) return OVC_EINVAL;
+    return run_search(models[0], c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the ensemble selection kernel (M = 1 included: the kernel's one-member instance, not the plain kernel the
+// search itself takes for one member) on caller-given device inputs: row-major logits [M][B*width][V], running / alive [B*width].
+// Every member's block pieces are computed here and its logits laid out transposed, as the engine's vocabulary product leaves
+// them.  The step is t of T = t + 1 positions with empty histories: no next input rows are written.
+extern "C" size_t ovc_debug_ensemble_update_bytes(int M, int B, int width, int V, int k) {
+    if (M < 1 || M > OVC_MAX_ENSEMBLE || B <= 0 || width <= 0 || V <= 0 || k <= 0 || k > OVC_MAX_BEAM) return 0;
+    const size_t R = (size_t)B * width, nblk = ((size_t)V + 31) / 32, ld = (nblk + 1) & ~(size_t)1, Rk = (size_t)B * k, T = OVC_MAX_LEN;
+    return 4 * ((size_t)M * ((size_t)V * ((R + 3) & ~(size_t)3) + 2 * R * ld + 128) + 4 * Rk + 6 * Rk * T + 64) + 4096;
+}
+
+extern "C" int ovc_debug_ensemble_update(const float* logits, const float* running, const float* alive, int M, int B, int width, int V,
+                                         int k, int t, int eos, void* scratch, size_t scratch_bytes, int32_t* parent_out,
+                                         int32_t* word_out, float* running_out, float* logp_out, float* row_max_out, float* row_lsum_out,
+                                         int32_t* hot_out, ovc_stream stream) {
+    if (!logits || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !logp_out || !row_max_out || !row_lsum_out ||
+        !hot_out)
+        return OVC_EINVAL;
+    if (M < 1 || M > OVC_MAX_ENSEMBLE || B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM ||
+        V <= 0 || (V + 31) / 32 > kFusedVocabBlocks || t < 0 || t >= OVC_MAX_LEN || width != (t == 0 ? 1 : k) || (long)width * V < k ||
+        (long)B * k * OVC_MAX_LEN > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_ensemble_update_bytes(M, B, width, V, k) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const int rows = B * width, ldt = (rows + 3) & ~3, T = t + 1;
+    const size_t Rk = (size_t)B * k;
+    Bump a{reinterpret_cast<char*>(scratch), 0};
+    EnsembleUpdateArgs en{};
+    en.M = M;
+    for (int i = 0; i < M; ++i) {
+        float* logits_t = a.take<float>((size_t)V * ldt);
+        en.tail[i] = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
+        float* stats = a.take<float>(2 * (size_t)rows * en.tail[i].stats_ld);
+        en.tail[i].stats = stats;
+        en.logits[i] = logits_t;
+        en.row_max_out[i] = row_max_out + (size_t)i * rows; en.row_lsum_out[i] = row_lsum_out + (size_t)i * rows;
+        TRY(ovc_block_pieces_launch(logits + (size_t)i * rows * V, rows, V, en.tail[i].stats_ld, ldt, stats, logits_t, s));
+    }
+    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
+    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
+    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T); int32_t* hist_in = a.take<int32_t>(Rk * T);
+    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess ||
+        hipMemsetAsync(hist_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
+        return OVC_ELAUNCH;
+    BeamUpdateArgs& bu = en.p;
+    bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
+    bu.hist_in = hist_in; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
+    bu.next_tok = next_tok;
+    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
+    en.running_in = running; en.hot_out = hot_out;
+    TRY(ovc_beam_ensemble_update_launch(en, B, s));
+    TRY(ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s));
+    // the step's recorded log-probs: column t of lp_out [B*k][T], as the caller's [B][k]
+    if (hipMemcpy2DAsync(logp_out, sizeof(float), lp_out + t, sizeof(float) * T, sizeof(float), Rk, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return OVC_ELAUNCH;
+    return OVC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ OVC_MAX_BEAM = 8
 OVC_MAX_REGIONS = 1024
 OVC_MAX_LEN = 256            # decode steps (caption positions, the decoder's max_len) the engine accepts
 OVC_MAX_BANNED = 16          # banned word ids a constrained search takes
+OVC_MAX_ENSEMBLE = 4         # members of an ensemble search
 OVC_PROFILE_CLASSES = 4
 ABI_VERSION = 8
 
@@ -209,6 +210,15 @@ SIGNATURES = {
     "ovc_debug_beam_constrained_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_int, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p,
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_ensemble_ok": (c_int, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int]),
+    "ovc_ensemble_workspace_bytes": (c_size_t, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int, c_int]),
+    "ovc_ensemble_beam_search": (c_int, [POINTER(POINTER(Model)), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_ensemble_beam_search_graph": (c_int, [POINTER(POINTER(Model)), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                               c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_ensemble_update_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ovc_debug_ensemble_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ovc_cider_reward": (c_int, [POINTER(Cider), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_adam_chunk_count": (c_long, [c_void_p, c_int]),
     "ovc_adam_chunk_fill": (c_long, [c_void_p, c_int, c_void_p, c_long]),
@@ -245,7 +255,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_debug_decode_self_partial_bytes", "ovc_debug_decode_self_attention", "ovc_debug_decode_cross_attention",
                  "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form",
                  "ovc_search_constraints_ok", "ovc_beam_search_constrained", "ovc_beam_search_constrained_graph",
-                 "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update")
+                 "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update",
+                 "ovc_ensemble_ok", "ovc_ensemble_workspace_bytes", "ovc_ensemble_beam_search", "ovc_ensemble_beam_search_graph",
+                 "ovc_debug_ensemble_update_bytes", "ovc_debug_ensemble_update")
 
 _lib = None
 

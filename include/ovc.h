@@ -956,6 +956,47 @@ int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, c
 int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
 int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
 
+/* Distillation: a soft-target loss (torch's KLDivLoss(log_target = True) beside the NLL; the reference has no distillation).
+ * Appended to ABI 8.  For row r = b T + t and word v, with
+ *   lq[r, v]  the student's teacher-forced log-probability, (logit - M_r) - log S_r,      q = exp(lq),
+ *   lt[r, v]  the caller's teacher log-probability, teacher_logp [B, T, V] fp32,          pt = exp(lt),
+ *   keep_r = targets[r] != pad,  count = the number of kept rows,  lambda = weight:
+ *   kl_r    = sum_v  pt[r,v] > 0 ? pt[r,v] * (lt[r,v] - lq[r,v]) : 0           (0 * (-inf - x) is 0, as xlogy)
+ *   mass_r  = sum_v  pt[r,v]
+ *   loss    = (1/count) * sum_r keep_r * ( (1-lambda) * (-lq[r, tgt_r]) + lambda * kl_r )
+ *   dlogit[r,v] = keep_r * (1/count) * ( (1-lambda) * (q[r,v] - [v == tgt_r]) + lambda * (mass_r * q[r,v] - pt[r,v]) )
+ * The teacher need not be normalised: mass_r is computed on the device, so the ensemble's un-renormalised mean (mass_r < 1) is a
+ * valid input; with mass_r = 1 the gradient is q - ((1-lambda) onehot + lambda pt).  Entries of -inf are allowed, at the target
+ * word too; NaN or +inf in the teacher is the caller's error and is not checked (checking would need a synchronisation).
+ * lambda = 0 is the NLL (openviic_amd routes it to ovc_forward_backward: the same launches, the same bits); lambda = 1 uses the
+ * targets for keep_r only.  The temperature is 1.  A row of weight 0 stores +0 in both dlogit layouts.  A batch whose targets are
+ * all <pad> divides by count = 0, as ovc_forward_backward does.  kl_r and mass_r are summed term by term in a fixed order:
+ * ascending v within slices of 64 words, then the slices ascending -- a function of V alone.
+ *
+ * ovc_forward_backward_distill: ovc_forward_backward (dropout == NULL) or ovc_forward_backward_dropout (dropout != NULL) with the
+ * loss above in place of the NLL: same models, sizes, gradient table, determinism and use_graph.  The teacher is copied into a
+ * workspace slot outside the captured body, so a replayed graph reads this call's teacher; the graph's key holds a kind of its own
+ * and the hash of lambda, never the teacher's contents.  A NULL distill or teacher_logp, a teacher that is not 16-byte aligned,
+ * weight outside [0, 1] (NaN included), or anything ovc_forward_backward (with dropout: ovc_forward_backward_dropout) refuses:
+ * OVC_EINVAL, nothing launched.  ovc_train_distill_workspace_bytes: the carve of ovc_train_workspace_bytes /
+ * ovc_train_dropout_workspace_bytes plus the teacher's slot (B T V floats), kl_r, mass_r and their slice partials; 0 wherever that
+ * sizer answers 0.
+ *
+ * ovc_ensemble_combine: out [rows][V] = the mean of M row-major [rows][V] fp32 log-probability tensors in the ensemble rule's order
+ * (pairwise sums, then a division by (float)M; 1 <= M <= OVC_MAX_ENSEMBLE), logps: M device pointers in HOST memory.  renormalise
+ * != 0: each row's log-sum-exp of that mean is subtracted, (mean - max) - log sum exp(mean - max), in a fixed order; a row that
+ * is -inf everywhere stays as it is.  renormalise == 0: openviic_amd.ensemble.combine bit for bit. */
+typedef struct {
+    const float* teacher_logp;           /* [B][T][V] fp32 log-probabilities on the device, 16-byte aligned */
+    float weight;                        /* lambda in [0, 1] */
+} ovc_distill;
+size_t ovc_train_distill_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout);
+int ovc_forward_backward_distill(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                 const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                 float* loss_out, int use_graph, ovc_stream stream, const ovc_distill* distill,
+                                 const ovc_dropout* dropout);
+int ovc_ensemble_combine(const float* const* logps, int M, long rows, int V, int renormalise, float* out, ovc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ import collections
 import torch
 
 from . import constraints as _constraints
+from . import distill as _distill
 from . import dropout as _dropout
 from . import engine
 from .builders.decoder_builder import build_decoder
@@ -64,6 +65,11 @@ def _apply_step_gradients(eng, optimizer, grads, max_norm):
     optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
 
 
+def _loss_head(head):
+    """``forward_backward``'s keyword for what ``_xe_call`` returned as the call's loss: the NLL, the smoothed loss or soft targets."""
+    return {"distill": tuple(head)} if isinstance(head, _distill.SoftTargets) else {"loss": head}
+
+
 class _XeLoss(torch.autograd.Function):
     """The reference's training loss on the engine.  ``forward`` runs ``ovc_forward_backward`` -- the forward AND the whole
     backward -- and keeps the gradients; ``backward`` hands them out scaled by ``grad_output`` (``ovc_scale``).  A loss whose
@@ -72,8 +78,9 @@ class _XeLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine_, dropout, smoothed, features, boxes, tokens, targets, *params):
-        # smoothed: None (the NLL) or (label_smoothing, reduction)
-        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout, loss=smoothed)
+        # smoothed: None (the NLL), (label_smoothing, reduction) or a distill.SoftTargets (teacher, weight) -- inside a tuple,
+        # so autograd never sees the teacher: no gradient flows into it
+        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout, **_loss_head(smoothed))
         ctx.engine, ctx.arena = engine_, arena
         ctx.layout = [(g.storage_offset(), g.shape) for g in grads]
         ctx.wanted = [p.requires_grad for p in params]
@@ -199,7 +206,8 @@ class BaseTransformer(Module):
         return self._fused_engine().score(*self._engine_inputs(input_features), input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
 
-    def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None):
+    def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None, teacher_log_probs=None,
+                distill_weight=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
         every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer, the
@@ -221,15 +229,37 @@ class BaseTransformer(Module):
         NLL; ``reduction="tokens"`` divides by the number of kept rows instead, the scale of the plain loss, which
         ``label_smoothing=0.0, reduction="tokens"`` is bit for bit.  Refused before any launch and any draw: an ``s`` that is
         not a Python number in ``0 <= s < 1``, ``s > 0`` with a vocabulary of 2 words or fewer, an unknown ``reduction``, and a
-        ``reduction`` without ``label_smoothing``.  ``label_smoothing=None`` is the plain call, launch for launch."""
-        eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction)
+        ``reduction`` without ``label_smoothing``.  ``label_smoothing=None`` is the plain call, launch for launch.
+
+        ``teacher_log_probs=P, distill_weight=w``: word-level distillation (``ovc_forward_backward_distill``;
+        ``openviic_amd.distill`` states the rule).  ``P`` is a teacher's teacher-forced ``(B, T, V)`` fp32 log-probabilities of
+        the same captions on the model's device -- ``teacher(items, fused=True)`` under ``torch.no_grad()``, or
+        ``Ensemble.teacher_log_probs(items)`` -- and the loss is ``(1 - w)`` times the NLL plus ``w`` times
+        ``KLDivLoss(log_target=True)`` from ``P`` to the model's distribution, summed over the rows whose target is not ``<pad>``
+        and divided by their number.  ``P`` need not be normalised and may hold ``-inf``; no gradient flows into it.  ``w = 0``
+        is the plain call, launch for launch; ``w = 1`` uses the targets to find the ``<pad>`` rows only.  For every model and
+        dropout setting above.  Refused before the engine is built, any launch and any draw: one of the two keywords without the
+        other, either with ``label_smoothing`` / ``reduction``, a ``w`` that is not a Python number in ``[0, 1]``, and a ``P``
+        that is not a contiguous fp32 ``(B, T, V)`` tensor on the model's device or that requires grad.  A temperature other
+        than 1, sparse teachers and 16-bit teachers are out of scope."""
+        eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
+                                                    teacher_log_probs=teacher_log_probs, distill_weight=distill_weight)
         return _XeLoss.apply(eng, drop, smoothed, *inputs, *eng.gradient_parameters())
 
-    def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None):
+    def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None, teacher_log_probs=None,
+                 distill_weight=None):
         """The preamble of ``xe_loss`` / ``xe_step``: their refusals in their order -- the loss, the dropout rules, a model outside
         the backward's scope, ``xe_step``'s optimizer set -- and only then the draw of the step's seed.  Returns ``(engine,
-        dropout (probs, seed) or None, smoothed loss or None, (features, boxes, caption tokens, targets))``."""
-        smoothed = engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
+        dropout (probs, seed) or None, smoothed loss / soft targets or None, (features, boxes, caption tokens, targets))``."""
+        soft = None
+        if teacher_log_probs is not None or distill_weight is not None:
+            try:            # a batch without caption tokens is refused where the inputs are checked, after the arguments
+                shape = (*input_features["caption_tokens"].shape, len(self.vocab))
+            except (KeyError, AttributeError, TypeError):
+                shape = None
+            soft = _distill.check(teacher_log_probs, distill_weight, what, shape=shape, device=self.device,
+                                  label_smoothing=label_smoothing, reduction=reduction)
+        smoothed = soft or engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
         probs = self._xe_dropout_probs(dropout, what)
         eng = self._fused_engine()
         eng._check_trainable()
@@ -258,7 +288,7 @@ class BaseTransformer(Module):
         return {}
 
     def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None, label_smoothing=None,
-                reduction=None):
+                reduction=None, teacher_log_probs=None, distill_weight=None):
         """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
         ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
         stands for ::
@@ -279,7 +309,8 @@ class BaseTransformer(Module):
         any draw.  With ``max_norm=None`` nothing of this is launched.
 
         ``label_smoothing`` / ``reduction``: as ``xe_loss`` takes them -- the label-smoothed loss in the four lines and here, with
-        the same refusals before any launch and any draw.
+        the same refusals before any launch and any draw.  ``teacher_log_probs`` / ``distill_weight``: as ``xe_loss`` takes them
+        -- the soft-target loss in the four lines and here.
 
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
@@ -288,8 +319,8 @@ class BaseTransformer(Module):
         _checked_step_optimizer(optimizer, "xe_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
         eng, drop, smoothed, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
-                                                    optimizer)
-        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), loss=smoothed)
+                                                    optimizer, teacher_log_probs=teacher_log_probs, distill_weight=distill_weight)
+        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed))
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 

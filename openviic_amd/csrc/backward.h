@@ -89,6 +89,19 @@ size_t ovc_bw_smoothed_part_floats(int rows, int V);
 int ovc_bw_xent_smoothed(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V,
                          const SmoothedLoss& l, float* lp_part, float* lp_sum, float* w_row, float* loss, float* dl_t, float* dl,
                          long ldv, hipStream_t s);
+// Soft-target cross-entropy (include/ovc.h, ovc_distill): ovc_bw_xent with a caller's teacher distribution beside the one-hot
+// target.  teacher: row-major log-probabilities [rows][V], entries of -inf allowed, not necessarily normalised.  Four launches: the
+// rows' kl_r = sum_v pt (lt - lq) and mass_r = sum_v pt (pt = exp(lt); terms with pt == 0 are 0; lq = (logit - M) - log S; ascending
+// words within slices of 64 words into part [2][ceil(V / 64)][ldt], the teacher's tile turned through LDS; then the slices in
+// ascending order into kl / mass [rows]), the loss (1 / count) sum_r keep_r (hard (-lq[tgt_r]) + soft kl_r) and the row weights
+// (one workgroup, ovc_bw_xent's order), and dlogit = w_row (hard (q - onehot) + soft (mass_r q - pt)) in ovc_bw_xent's two
+// layouts.  hard = 1 - lambda and soft = lambda are the host's float64 values rounded once.  part: 2 * ovc_bw_smoothed_part_floats.
+struct SoftLoss {
+    float hard, soft;
+};
+int ovc_bw_xent_soft(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, const SoftLoss& l,
+                     const float* teacher, float* part, float* kl, float* mass, float* w_row, float* loss, float* dl_t, float* dl,
+                     long ldv, hipStream_t s);
 // Word-embedding backward: out[w, :] = sum over rows r with tok[r] == w (ascending r) of dx[r, :]; the pad row 0.
 int ovc_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, hipStream_t s);
 // tok32[r] = clamp(tokens[r], 0, V-1)

@@ -449,6 +449,150 @@ __global__ __launch_bounds__(256) void bw_smoothed_dlogit_kernel(const float* __
     }
 }
 
+// Soft targets (distillation).  The stored logits are transposed (coalesced along rows), the teacher is row-major [rows][V]
+// (coalesced along words): each operand is read along its own contiguous axis and the teacher's 64 rows x 64 words tile is turned
+// through LDS.  Per (row, slice of kLpSlice words) the partials of
+//   kl = sum_v pt > 0 ? pt (lt - lq) : 0        and        mass = sum_v pt,        pt = exp(lt), lq = (logit - M) - log S
+// One workgroup per (64 rows, slice): the four waves form the terms (tt: the teacher tile, then pt in place; tk: the kl terms),
+// then wave 0 sums the slice's kl terms and wave 1 its pt in ascending words, one lane per row.  Words past V and rows past
+// `rows` contribute +0.
+__global__ __launch_bounds__(256) void bw_soft_rowsum_part_kernel(const float* __restrict__ logits_t, long ldt,
+                                                                  const float* __restrict__ lse, const float* __restrict__ teacher,
+                                                                  int rows, int V, float* __restrict__ part_kl,
+                                                                  float* __restrict__ part_mass) {
+    __shared__ float tt[64][65], tk[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, slice = blockIdx.y, w0 = slice * kLpSlice;
+    // every global load is unconditional at a clamped (always valid) address, so a thread's 16 loads of a phase are in flight
+    // together; what lies past the edges is replaced after the load
+    float v[16];
+    {
+        const int wc = min(w0 + lane, V - 1);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = teacher[(size_t)min(r0 + wv + 4 * j, rows - 1) * V + wc];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tt[wv + 4 * j][lane] = (r0 + wv + 4 * j < rows && w0 + lane < V) ? v[j] : -INFINITY;
+    }
+    __syncthreads();
+    const int r = r0 + lane, rc = min(r, rows - 1);
+    const float mx = lse[2 * rc], ls = lse[2 * rc + 1];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = logits_t[(size_t)min(w0 + wv + 4 * j, V - 1) * ldt + rc];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int i = wv + 4 * j;
+        float term = 0.f, pt = 0.f;
+        if (w0 + i < V && r < rows) {
+            const float lt = tt[lane][i];
+            pt = expf(lt);
+            if (pt > 0.f) term = pt * (lt - ((v[j] - mx) - ls));
+        }
+        tt[lane][i] = pt;              // read and written by this thread alone
+        tk[i][lane] = term;
+    }
+    __syncthreads();
+    if (wv > 1 || r >= rows) return;
+    float acc = 0.f;
+    if (wv == 0) {
+#pragma unroll 8
+        for (int i = 0; i < kLpSlice; ++i) acc += tk[i][lane];
+        part_kl[(size_t)slice * ldt + r] = acc;
+    } else {
+#pragma unroll 8
+        for (int i = 0; i < kLpSlice; ++i) acc += tt[lane][i];
+        part_mass[(size_t)slice * ldt + r] = acc;
+    }
+}
+
+// the slices in ascending order, both sums
+__global__ __launch_bounds__(256) void bw_soft_rowsum_final_kernel(const float* __restrict__ part_kl,
+                                                                   const float* __restrict__ part_mass, long ldt, int rows, int slices,
+                                                                   float* __restrict__ kl, float* __restrict__ mass) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float a = 0.f, b = 0.f;
+#pragma unroll 8
+    for (int i = 0; i < slices; ++i) { a += part_kl[(size_t)i * ldt + r]; b += part_mass[(size_t)i * ldt + r]; }
+    kl[r] = a; mass[r] = b;
+}
+
+// bw_loss_kernel for the soft-target loss: one workgroup, thread partials over rows t, t + 256, ... of
+// (1 - lambda) (-logp[tgt]) + lambda kl_r and of the kept-row count, the same fixed LDS tree, then every row's weight
+__global__ __launch_bounds__(256) void bw_soft_loss_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                                           const float* __restrict__ kl, const int32_t* __restrict__ tgt, int pad,
+                                                           int rows, float hard, float soft, float* __restrict__ w_row,
+                                                           float* __restrict__ loss) {
+    __shared__ float tot[256], cnt[256];
+    const int t = threadIdx.x;
+    float a = 0.f, c = 0.f;
+    for (int r = t; r < rows; r += 256) {
+        const int w = tgt[r];
+        if (w == pad) continue;
+        const float nll = -((logits_t[(size_t)w * ldt + r] - lse[2 * r]) - lse[2 * r + 1]);
+        a += hard * nll + soft * kl[r];
+        c += 1.f;
+    }
+    tot[t] = a; cnt[t] = c;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) { tot[t] += tot[t + off]; cnt[t] += cnt[t + off]; }
+        __syncthreads();
+    }
+    const float count = cnt[0];
+    if (t == 0) *loss = tot[0] / count;
+    const float inv = 1.f / count;
+    for (int r = t; r < rows; r += 256) w_row[r] = tgt[r] == pad ? 0.f : inv;
+}
+
+// bw_dlogit_kernel's tile with the soft-target rule: g = w_row ((1 - lambda) (q - [w == tgt]) + lambda (mass q - pt)); the
+// teacher's tile comes in along words and is read along rows through the same LDS array, before g takes it; a row of weight 0 gets +0
+__global__ __launch_bounds__(256) void bw_soft_dlogit_kernel(const float* __restrict__ logits_t, long ldt, const float* __restrict__ lse,
+                                                             const float* __restrict__ teacher, const float* __restrict__ mass,
+                                                             const int32_t* __restrict__ tgt, const float* __restrict__ w_row,
+                                                             float hard, float soft, int rows, int V, float* __restrict__ dl_t,
+                                                             float* __restrict__ dl, long ldv) {
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, w0 = blockIdx.y * 64;
+    // the one LDS array holds the teacher's tile first (in along words, out along rows into registers), then g (in along rows, out
+    // along words).  Every global load is unconditional at a clamped (always valid) address, so a thread's 16 loads of a phase
+    // are in flight together; what lies past the edges is never used.
+    float lt[16], x[16];
+    {
+        const int wc = min(w0 + lane, V - 1);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lt[j] = teacher[(size_t)min(r0 + wv + 4 * j, rows - 1) * V + wc];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tile[wv + 4 * j][lane] = lt[j];
+    }
+    __syncthreads();
+    const int r = r0 + lane, rc = min(r, rows - 1);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) lt[j] = tile[lane][wv + 4 * j];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) x[j] = logits_t[(size_t)min(w0 + wv + 4 * j, V - 1) * ldt + rc];
+    const float mx = lse[2 * rc], ls = lse[2 * rc + 1], wr = r < rows ? w_row[rc] : 0.f, ms = mass[rc];
+    const int tg = tgt[rc];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int i = wv + 4 * j, w = w0 + i;
+        float g = 0.f;
+        if (w < V && wr != 0.f) {
+            const float q = expf((x[j] - mx) - ls);
+            const float pt = expf(lt[j]);
+            g = (hard * (q - (tg == w ? 1.f : 0.f)) + soft * (ms * q - pt)) * wr;
+        }
+        if (w < V && r < ldt) dl_t[(size_t)w * ldt + r] = g;
+        tile[i][lane] = g;
+    }
+    __syncthreads();
+    for (int i = wv; i < 64; i += 4) {
+        const int r = r0 + i, w = w0 + lane;
+        if (r < rows && w < ldv) dl[(size_t)r * ldv + w] = tile[lane][i];
+    }
+}
+
 // one workgroup per word; each thread keeps up to 8 columns (d <= 2048)
 __global__ __launch_bounds__(256) void bw_embedding_kernel(const int32_t* __restrict__ tok, int rows, int pad,
                                                            const float* __restrict__ dx, int d, float* __restrict__ out) {
@@ -614,6 +758,28 @@ int ovc_bw_xent_smoothed(const float* logits_t, long ldt, const float* lse, cons
     OVC_RETURN_IF_LAUNCH_FAILED();
     hipLaunchKernelGGL(bw_smoothed_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, tgt,
                        w_row, pad, l.conf, l.u, rows, V, dl_t, dl, ldv);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_xent_soft(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V, const SoftLoss& l,
+                     const float* teacher, float* part, float* kl, float* mass, float* w_row, float* loss, float* dl_t, float* dl,
+                     long ldv, hipStream_t s) {
+    if (rows <= 0 || V <= 0 || pad < 0 || pad >= V || ldt < rows || ldt > (((long)rows + 3) & ~3L) || !teacher || !part || !kl || !mass)
+        return OVC_EINVAL;           // the partials' rows are ldt apart: ovc_bw_smoothed_part_floats sizes them for rows padded to 4
+    const int slices = (V + kLpSlice - 1) / kLpSlice;
+    float* part_mass = part + ovc_bw_smoothed_part_floats(rows, V);
+    hipLaunchKernelGGL(bw_soft_rowsum_part_kernel, dim3((rows + 63) / 64, slices), dim3(256), 0, s, logits_t, ldt, lse, teacher, rows,
+                       V, part, part_mass);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_soft_rowsum_final_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, part, part_mass, ldt, rows, slices, kl,
+                       mass);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_soft_loss_kernel, dim3(1), dim3(256), 0, s, logits_t, ldt, lse, kl, tgt, pad, rows, l.hard, l.soft, w_row,
+                       loss);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(bw_soft_dlogit_kernel, dim3((ldt + 63) / 64, (ldv + 63) / 64), dim3(256), 0, s, logits_t, ldt, lse, teacher,
+                       mass, tgt, w_row, l.hard, l.soft, rows, V, dl_t, dl, ldv);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -300,6 +300,34 @@ __global__ __launch_bounds__(256) void ensemble_masked_logp_kernel(EnsembleLogpA
     }
 }
 
+// The mean of kM members' row-major log-probabilities [rows][V] in ens_mean's order (ovc_ensemble_combine: teacher-forced rows, the
+// pieces already taken off), one wave per row.  renormalise: the row's log-sum-exp of that mean is subtracted -- the lane's words
+// in ascending order for the maximum and for sum exp(mean - maximum), one xor butterfly each, then (mean - maximum) - log(sum),
+// each lane reading back the words it wrote.  A row whose mean is -inf everywhere is left as it is.
+template <int kM>
+__global__ __launch_bounds__(256) void ensemble_combine_rows_kernel(EnsembleCombineArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.rows) return;
+    float* y = a.out + (size_t)row * a.V;
+    float mx = -INFINITY;
+    for (int c = lane; c < a.V; c += 64) {
+        float lp[kM];
+#pragma unroll
+        for (int e = 0; e < kM; ++e) lp[e] = a.logp[e][(size_t)row * a.V + c];
+        const float mean = ens_mean<kM>(lp);
+        y[c] = mean;
+        mx = fmaxf(mx, mean);
+    }
+    if (!a.renormalise) return;
+    mx = wave_max(mx);
+    if (mx == -INFINITY) return;
+    float sum = 0.f;
+    for (int c = lane; c < a.V; c += 64) sum += expf(y[c] - mx);
+    const float ls = logf(wave_sum(sum));
+    for (int c = lane; c < a.V; c += 64) y[c] = (y[c] - mx) - ls;
+}
+
 // The block pieces of row-major logits [rows][V] as the vocabulary product's epilogue leaves them -- per (row, 32-word block) the
 // maximum and sum exp(x - maximum) -- and the logits laid out transposed, the engine's form (ovc_debug_beam_constrained_update).
 // One wave per (row, block pair group): lane l < 32 holds word l of the block.
@@ -553,6 +581,21 @@ int ovc_ensemble_masked_logp_launch(const EnsembleLogpArgs& a, int rows, hipStre
     case 2: hipLaunchKernelGGL(ensemble_masked_logp_kernel<2>, dim3(rows), dim3(256), 0, stream, a); break;
     case 3: hipLaunchKernelGGL(ensemble_masked_logp_kernel<3>, dim3(rows), dim3(256), 0, stream, a); break;
     default: hipLaunchKernelGGL(ensemble_masked_logp_kernel<4>, dim3(rows), dim3(256), 0, stream, a); break;
+    }
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_ensemble_combine_launch(const EnsembleCombineArgs& a, hipStream_t stream) {
+    if (a.M < 1 || a.M > OVC_MAX_ENSEMBLE || a.rows <= 0 || a.rows > (1L << 31) - 4 || a.V <= 0 || !a.out) return OVC_EINVAL;
+    for (int e = 0; e < a.M; ++e)
+        if (!a.logp[e]) return OVC_EINVAL;
+    const dim3 grid((unsigned)((a.rows + 3) / 4));
+    switch (a.M) {
+    case 1: hipLaunchKernelGGL(ensemble_combine_rows_kernel<1>, grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(ensemble_combine_rows_kernel<2>, grid, dim3(256), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(ensemble_combine_rows_kernel<3>, grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(ensemble_combine_rows_kernel<4>, grid, dim3(256), 0, stream, a); break;
     }
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;

@@ -318,6 +318,14 @@ struct EnsembleLogpArgs {
     const float* alive; float* out;
 };
 int ovc_ensemble_masked_logp_launch(const EnsembleLogpArgs& a, int rows, hipStream_t stream);
+// ovc_ensemble_combine: out[r][v] = the rule's mean of logp[0..M-1][r][v] (row-major [rows][V] each), with renormalise minus the
+// row's log-sum-exp of that mean.  One wave per row.
+struct EnsembleCombineArgs {
+    int M, V, renormalise; long rows;
+    const float* logp[OVC_MAX_ENSEMBLE];
+    float* out;
+};
+int ovc_ensemble_combine_launch(const EnsembleCombineArgs& a, hipStream_t stream);
 // Test support: the block pieces [rows][stats_ld] float2 and the transposed logits [V][ldt] of row-major logits [rows][V].
 // parent_out / word_out [B][k]: the beam inside the image and the word of the winners a step t update left in anc / hist [B*k][T].
 int ovc_debug_collect_parents_launch(const int32_t* anc, const int32_t* hist, int B, int width, int k, int T, int t, int32_t* parent_out,

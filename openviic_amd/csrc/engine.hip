@@ -1488,6 +1488,7 @@ enum class GraphKind {
     ShapedSampleSearch, // ovc_sample_shaped_graph with options that are not neutral (as SampleSearch; the options in the hash)
     ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
     EnsembleSearch,     // ovc_ensemble_beam_search_graph with more than one member (as Search; every member's contents in the hash)
+    TrainDistill,       // ovc_forward_backward_distill, with or without dropout (k = T, out_size = 1; the weight in the hash)
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -2042,6 +2043,20 @@ extern "C" int ovc_debug_ensemble_update(const float* logits, const float* runni
     return OVC_OK;
 }
 
+// The mean of M row-major log-probability tensors in the rule's order, optionally renormalised (include/ovc.h): one launch.
+extern "C" int ovc_ensemble_combine(const float* const* logps, int M, long rows, int V, int renormalise, float* out, ovc_stream stream) {
+    if (!logps || !out || M < 1 || M > OVC_MAX_ENSEMBLE || rows < 0 || V <= 0) return OVC_EINVAL;
+    EnsembleCombineArgs a{};
+    a.M = M; a.V = V; a.renormalise = renormalise != 0; a.rows = rows; a.out = out;
+    for (int i = 0; i < M; ++i) {
+        if (!logps[i]) return OVC_EINVAL;
+        a.logp[i] = logps[i];
+    }
+    if (rows == 0) return OVC_OK;
+    TRY(ovc_device_guard());
+    return ovc_ensemble_combine_launch(a, ovc_hip_stream(stream));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Sampling (include/ovc.h: the rule).  A search whose selection is a draw: S rows per image after step 0, row (b, s) its own
 // ancestor, every total score 0 -- so the final kernel, whose order is stable, returns the samples in sample order.
@@ -2286,6 +2301,10 @@ struct TrainWs {
     // label smoothing (LossHead::SmoothedXent only; ovc_train_smoothed_workspace_bytes): the rows' sums of
     // log-probabilities [rows] and their slice partials [ceil(V / 64)][rows padded to 4]
     float* lp_sum; float* lp_part;
+    // soft targets (LossHead::SoftTargets only; ovc_train_distill_workspace_bytes): the teacher's log-probabilities [rows][V],
+    // copied in outside the captured body, the rows' kl_r and mass_r [rows] each and their slice partials
+    // [2][ceil(V / 64)][rows padded to 4]
+    float* teacher; float* kl_sum; float* mass; float* soft_part;
     // the cross-level tail (bw_cross_level_tail; cross-level models only), rows B*N: the leaky-ReLU gradients dh [B*N][d] (mlp2's,
     // then mlp1's in da), mlp1's input gradient dcat [B*N][3d], per cross call c the pre-norm sum's gradient dss [2][B*N][d], dq
     // [2][B*N][h_enc dk_enc], dk|dv [2][B*N][2 h_enc dk_enc], then d(o2') and the q path plus dss, dq23 [2][B*N][d]; the levels'
@@ -2305,9 +2324,10 @@ enum class LossHead {
     Xent,           // ovc_bw_xent: NLLLoss(ignore_index = pad) and its dlogit
     SmoothedXent,   // ovc_bw_xent_smoothed: the label-smoothed loss, its constants in TrainCall::smoothed
     RowWeights,     // ovc_bw_dlogit: the caller's row weights and no loss -- the sequence form, S sequences per image
+    SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The ten exported functions fill one of these, and the scope (call_ok), the workspace
+// One training call, described once.  The twelve exported functions fill one of these, and the scope (call_ok), the workspace
 // layout and size (carve_train), the captured body (issue_train_body), the graph key (train_graph_key) and the launches around
 // the body (run_train_call) are functions of it: a sizer and the entry point that carves its buffer cannot disagree.
 struct TrainCall {
@@ -2315,6 +2335,7 @@ struct TrainCall {
     int B, N, S, T;                                 // S sequences per image, rows = B*S*T (run_forward_decoder); 1 but for RowWeights
     LossHead head;
     SmoothedLoss smoothed; uint64_t loss_hash;      // SmoothedXent: the loss's constants and their hash (make_smoothed_loss)
+    SoftLoss soft; const float* teacher;            // SoftTargets: the two weights (their hash in loss_hash) and the caller's teacher
     // Dropout: the plan, or nullptr when no site is active (the plain call, launch for launch), with the caller's seed and the
     // hash of the plan's constants (bind_dropout).  A sizer binds an empty plan: its presence alone adds the dropout buffers
     // and narrows the scope.
@@ -2389,6 +2410,11 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     if (c.head == LossHead::SmoothedXent) {
         t.lp_sum = a.take<float>(rows);
         t.lp_part = a.take<float>(ovc_bw_smoothed_part_floats((int)rows, m->vocab));
+    }
+    if (c.head == LossHead::SoftTargets) {
+        t.teacher = a.take<float>(rows * V);
+        t.kl_sum = a.take<float>(rows); t.mass = a.take<float>(rows);
+        t.soft_part = a.take<float>(2 * ovc_bw_smoothed_part_floats((int)rows, m->vocab));
     }
     t.bytes = (a.off + 255) & ~(size_t)255;
     return t;
@@ -2710,6 +2736,10 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
     case LossHead::RowWeights:
         RUN(ovc_bw_dlogit(w.logits, ldt, w.lse, w.tgt, t.w_row, rows, V, t.dl_t, t.dl, ldv, s));
         break;
+    case LossHead::SoftTargets:
+        RUN(ovc_bw_xent_soft(w.logits, ldt, w.lse, w.tgt, m->pad_idx, rows, V, c.soft, t.teacher, t.soft_part, t.kl_sum, t.mass,
+                             t.w_row, t.loss, t.dl_t, t.dl, ldv, s));
+        break;
     }
     // decoder output: d(out) = dlogit . fc, d(fc) = dlogit^T . out
     const float* dec_out = t.tape.dec[L - 1].out;
@@ -2827,7 +2857,8 @@ int stage_train_inputs(Engine& e, TrainWs& t, const float* features, const int64
 // the seed: it is read from its workspace slot), the smoothed loss's, the search's k.  Each is 0 for a call without it.
 GraphKey train_graph_key(const ovc_model* m, const ovc_model* grads, const void* workspace, const TrainCall& c) {
     const GraphKind kind = c.seq() ? GraphKind::SequenceBackward
-                           : c.head == LossHead::SmoothedXent ? GraphKind::TrainSmoothed : GraphKind::Train;
+                           : c.head == LossHead::SmoothedXent ? GraphKind::TrainSmoothed
+                           : c.head == LossHead::SoftTargets ? GraphKind::TrainDistill : GraphKind::Train;
     const uint64_t hash = hash_bytes(m, sizeof(*m)) ^ (hash_bytes(grads, sizeof(*grads)) * 0x9E3779B97F4A7C15ull) ^ c.drop_hash ^
                           c.loss_hash ^ ((uint64_t)c.k << 56);
     return GraphKey{kind, hash, workspace, c.B, c.N, c.T, c.S};
@@ -2851,6 +2882,12 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
     Engine e{m, ovc_hip_stream(stream), 0};
     const int nseq = c.B * c.S, rows = nseq * c.T;
     TRY(bind_train_drop(e, t, c));
+    if (c.head == LossHead::SoftTargets) {
+        // the teacher goes into its slot here, outside the captured body: a replayed graph reads this call's distribution
+        if (!c.teacher) return OVC_EINVAL;
+        if (hipMemcpyAsync(t.teacher, c.teacher, (size_t)rows * m->vocab * sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+            return OVC_ELAUNCH;
+    }
     if (c.seq() && c.plan) {
         // the row table is refreshed here as well, outside the captured body
         hipLaunchKernelGGL(seq_maskrow_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, c.slots, c.B, c.S, c.T, c.k, t.maskrow);
@@ -2958,6 +2995,32 @@ extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model
     if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
     if (!loss || !call_ok(m, c)) return OVC_EINVAL;
     TRY(make_smoothed_loss(m, loss, (long)B * T, &c.smoothed, &c.loss_hash));
+    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+                          stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training: ovc_forward_backward_distill (soft targets: the NLL mixed with the KL divergence from a teacher)
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ovc_train_distill_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::SoftTargets}, dropout != 0);
+}
+
+extern "C" int ovc_forward_backward_distill(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                            int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                            size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                            const ovc_distill* distill, const ovc_dropout* dropout) {
+    (void)boxes;
+    // before any launch: the table, the teacher's pointer and alignment, 0 <= weight <= 1 (NaN fails the comparison)
+    if (!distill || !distill->teacher_logp || !ovc_aligned16(distill->teacher_logp)) return OVC_EINVAL;
+    if (!(distill->weight >= 0.f && distill->weight <= 1.f)) return OVC_EINVAL;
+    TrainCall c{B, N, 1, T, LossHead::SoftTargets};
+    DropPlan plan{};
+    if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
+    if (!call_ok(m, c)) return OVC_EINVAL;
+    c.soft.hard = (float)(1.0 - (double)distill->weight); c.soft.soft = distill->weight;
+    c.teacher = distill->teacher_logp;
+    c.loss_hash = (hash_bytes(&distill->weight, sizeof(float)) | 1) * 0xA24BAED4963EE407ull;
     return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
                           stream);
 }

@@ -21,6 +21,7 @@ import threading
 import torch
 
 from . import constraints as _constraints
+from . import distill as _distill
 from . import dropout as _dropout
 from . import native
 from .native import check
@@ -850,7 +851,8 @@ class CaptionEngine:
         """The parameters ``forward_backward`` returns gradients for, in the order of its list."""
         return [p for p, _ in _grad_slots(self.model)]
 
-    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None):
+    def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None,
+                         distill=None):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -868,7 +870,25 @@ class CaptionEngine:
         ``loss=(smoothing, reduction)``: the label-smoothed cross-entropy in place of the NLL
         (``ovc_forward_backward_smoothed``; ``checked_label_smoothing`` states the arguments, ``BaseTransformer.xe_loss`` the
         loss).  The loss parameters are part of the graph key.  ``(0.0, "tokens")`` is the plain loss and takes the plain
-        path: the same launches, the same bits."""
+        path: the same launches, the same bits.
+
+        ``distill=(P, w)``: the soft-target loss in place of the NLL (``ovc_forward_backward_distill``; ``openviic_amd.distill``
+        states the rule and the arguments): ``P`` the teacher's ``(B, T, V)`` fp32 log-probabilities on this device, ``w`` the
+        weight of the KL term.  ``P`` is copied into the workspace on the stream before the body, so a replayed graph reads this
+        call's teacher; ``w`` is part of the graph key, ``P``'s contents never are.  No gradient flows into ``P``.  ``w = 0`` is
+        the plain loss and takes the plain path.  Refused together with ``loss``."""
+        if distill is not None:
+            if not isinstance(distill, (tuple, list)) or len(distill) != 2:
+                raise native.OvcError("forward_backward: distill must be a (teacher_log_probs, distill_weight) pair (got {!r})".format(
+                    type(distill).__name__))
+            if loss is not None:
+                raise native.OvcError("forward_backward: soft targets together with label smoothing are out of scope -- pass "
+                                      "distill or loss, not both")
+            B_T = tuple(caption_tokens.shape) if isinstance(caption_tokens, torch.Tensor) and caption_tokens.dim() == 2 else None
+            distill = _distill.check(distill[0], distill[1], "forward_backward",
+                                     shape=None if B_T is None else (*B_T, self.desc.vocab), device=self.device)
+            if distill is not None and distill.weight == 0.0:
+                distill = None
         if loss is not None:
             if not isinstance(loss, (tuple, list)) or len(loss) != 2:
                 raise native.OvcError("forward_backward: loss must be a (label_smoothing, reduction) pair (got {!r})".format(loss))
@@ -880,7 +900,7 @@ class CaptionEngine:
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T))
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill)
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -896,16 +916,24 @@ class CaptionEngine:
         (True, False, True): ("ovc_train_beams_dropout_workspace_bytes", "ovc_sequence_backward_dropout"),
     }
 
-    def _train_form(self, sequence, loss, table_drop, shape, search=()):
+    _DISTILL_FORM = ("ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill")
+
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None):
         """One training call's form: ``(entry point, shape, workspace bytes, trailing arguments)`` for ``shape`` ``(B, N, T)``
         or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes on.
-        A shape or model the sizer refuses raises here, before any launch."""
+        A shape or model the sizer refuses raises here, before any launch.  ``distill``: a checked ``distill.SoftTargets`` -- the
+        soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments."""
         sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
+        if distill is not None:
+            sizer, entry = self._DISTILL_FORM
         drop = () if table_drop is None else (ctypes.byref(table_drop),)
         size_tail, tail = (), (*search, *drop)
         if loss is not None:
             size_tail = (1 if drop else 0,)
             tail = (ctypes.byref(native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])), drop[0] if drop else None)
+        if distill is not None:
+            size_tail = (1 if drop else 0,)
+            tail = (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), drop[0] if drop else None)
         need = getattr(self.lib, sizer)(ctypes.byref(self.desc), *shape, *size_tail)
         if need == 0:
             raise native.OvcError("unsupported training configuration ({}, V={}; see {})".format(

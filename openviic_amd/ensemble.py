@@ -14,6 +14,10 @@ the same beams and, for beam row ``r`` and word ``w``::
 
 and everything else is the plain search.  The mean of log-probabilities is NOT renormalised: ``exp(mean)`` does not sum to one
 over the words -- the convention of the ensembles in the captioning literature (the meshed-memory ``TransformerEnsemble``).
+
+``Ensemble.teacher_log_probs(items)`` gives the same mean teacher-forced, ``(B, T, V)``, for word-level distillation
+(``xe_loss(items, teacher_log_probs=...)``, ``openviic_amd.distill``): the members' fused forwards, then one
+``ovc_ensemble_combine`` launch, by default renormalised so that every row is a distribution.
 """
 import ctypes
 
@@ -27,10 +31,12 @@ FUSED_TAIL_WORDS = 16384          # the fused vocabulary tail: 512 blocks of 32 
 
 # ---- the rule in numpy ---------------------------------------------------------------------------------------------------------
 
-def combine(logps):
+def combine(logps, renormalise=False):
     """The fp32 mean of ``M`` members' log-probabilities ``[M][...]`` in the rule's order: pairwise sums, then a division by
     ``float32(M)``.  The identity for one member, and for two or four identical members (``x + x``, ``2x + 2x`` and the divisions
-    by 2 and 4 are exact); three identical members are not (``3x`` rounds)."""
+    by 2 and 4 are exact); three identical members are not (``3x`` rounds).  ``renormalise``: the log-sum-exp of the mean over the
+    last axis is subtracted, ``(mean - max) - log(sum(exp(mean - max)))`` in fp32 (``ovc_ensemble_combine``; the device sums in
+    its own fixed order, so the two agree to rounding, not bit for bit); a row that is ``-inf`` everywhere stays as it is."""
     a = [np.asarray(x, dtype=np.float32) for x in logps]
     M = len(a)
     if not 1 <= M <= OVC_MAX_ENSEMBLE:
@@ -44,7 +50,14 @@ def combine(logps):
             s = (a[0] + a[1]) + a[2]
         else:
             s = (a[0] + a[1]) + (a[2] + a[3])
-        return (s / np.float32(M)).astype(np.float32)
+        mean = (s / np.float32(M)).astype(np.float32)
+        if not renormalise:
+            return mean
+        mx = mean.max(axis=-1, keepdims=True)
+        safe = np.where(np.isneginf(mx), np.float32(0), mx)
+        with np.errstate(divide="ignore"):                               # log 0 on a row without mass, which keeps its -inf
+            ls = np.log(np.exp(mean - safe, dtype=np.float32).sum(axis=-1, keepdims=True, dtype=np.float32), dtype=np.float32)
+        return np.where(np.isneginf(mx), mean, (mean - safe) - ls).astype(np.float32)
 
 
 def word_scores(x, row_max, row_lsum, running):
@@ -176,18 +189,44 @@ class Ensemble:
             m.eval()
         return self
 
-    def _engines(self):
+    def _engines(self, what="Ensemble.beam_search"):
         import torch
         engines = [m._fused_engine() for m in self.models]
         for i, (m, eng) in enumerate(zip(self.models, engines)):
             if eng.precision != "f32":
-                raise OvcError("Ensemble.beam_search: models[{}] runs in precision={!r} -- an ensemble runs in 'f32' only".format(
-                    i, eng.precision))
+                raise OvcError("{}: models[{}] runs in precision={!r} -- an ensemble runs in 'f32' only".format(
+                    what, i, eng.precision))
             if m.training and torch.is_grad_enabled():
-                raise OvcError("Ensemble.beam_search: models[{}] is in train() mode with gradients enabled -- the ensemble's "
+                raise OvcError("{}: models[{}] is in train() mode with gradients enabled -- the ensemble's "
                                "log_probs carry no gradient (SCST on an ensemble is out of scope): call eval() or use "
-                               "torch.no_grad()".format(i))
+                               "torch.no_grad()".format(what, i))
         return engines
+
+    def teacher_log_probs(self, items, renormalise=True):
+        """Teacher-forced ``(B, T, V)`` fp32 log-probabilities of the ensemble for ``items["caption_tokens"]``: what
+        ``xe_loss(items, teacher_log_probs=...)`` distils from.  Every member runs its fused forward -- ``model(items,
+        fused=True)`` -- under ``torch.no_grad()``, then ONE ``ovc_ensemble_combine`` launch forms the rule's mean of the members'
+        log-probabilities and, with ``renormalise`` (the default), subtracts each row's log-sum-exp, so that every row is a
+        distribution.  ``renormalise=False`` is the search's own un-renormalised mean (``combine`` bit for bit; every row's mass is
+        below 1 where the members disagree), which the soft-target loss accepts as it is; one member then returns that member's
+        forward bit for bit.  The result carries no gradient.  The members' agreement checks, the 'f32' requirement and the
+        16 384-word limit are the constructor's and ``beam_search``'s."""
+        import torch
+        what = "Ensemble.teacher_log_probs"
+        self._engines(what)
+        with torch.no_grad():
+            logps = [m(items, fused=True) for m in self.models]
+        for i, lp in enumerate(logps):
+            if lp.dtype != torch.float32 or lp.shape != logps[0].shape or not lp.is_contiguous():
+                raise OvcError("{}: models[{}] returned {} {}, models[0] {} {}".format(
+                    what, i, tuple(lp.shape), lp.dtype, tuple(logps[0].shape), logps[0].dtype))
+        B, T, V = logps[0].shape
+        out = torch.empty_like(logps[0])
+        M = len(logps)
+        pointers = (ctypes.c_void_p * M)(*[lp.data_ptr() for lp in logps])
+        check(native.load().ovc_ensemble_combine(pointers, M, B * T, V, 1 if renormalise else 0, out.data_ptr(),
+                                                 native.stream_handle()), "ovc_ensemble_combine")
+        return out
 
     def sample(self, *args, **kwargs):
         raise OvcError("Ensemble.sample: sampling from an ensemble is out of scope -- beam_search only")

@@ -63,6 +63,11 @@ class Loss(ctypes.Structure):
     _fields_ = [("smoothing", c_float), ("reduction", c_int32)]
 
 
+class Distill(ctypes.Structure):
+    """``ovc_distill``: the teacher's log-probabilities ``[B][T][V]`` (device pointer) and the weight of the soft-target term."""
+    _fields_ = [("teacher_logp", c_void_p), ("weight", c_float)]
+
+
 LOSS_MEAN, LOSS_TOKENS = 0, 1
 LOSS_REDUCTIONS = {"mean": LOSS_MEAN, "tokens": LOSS_TOKENS}
 
@@ -177,6 +182,10 @@ SIGNATURES = {
     "ovc_train_smoothed_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_forward_backward_smoothed": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                               c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Loss), POINTER(Dropout)]),
+    "ovc_train_distill_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_forward_backward_distill": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                             c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Distill), POINTER(Dropout)]),
+    "ovc_ensemble_combine": (c_int, [POINTER(c_void_p), c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
     "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
@@ -257,7 +266,8 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_search_constraints_ok", "ovc_beam_search_constrained", "ovc_beam_search_constrained_graph",
                  "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update",
                  "ovc_ensemble_ok", "ovc_ensemble_workspace_bytes", "ovc_ensemble_beam_search", "ovc_ensemble_beam_search_graph",
-                 "ovc_debug_ensemble_update_bytes", "ovc_debug_ensemble_update")
+                 "ovc_debug_ensemble_update_bytes", "ovc_debug_ensemble_update",
+                 "ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill", "ovc_ensemble_combine")
 
 _lib = None
 

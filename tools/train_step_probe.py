@@ -31,6 +31,14 @@ smoothed step's time stands next to the plain step's from the same build and run
 reads and writes beyond the plain one from the shapes: one more pass over the stored logits (R * V * 4 bytes) and the slice
 partials.
 
+--distill W (with --optimizer none and one --variant): the plain step and the distillation step under
+``model.xe_loss(items, teacher_log_probs=P, distill_weight=W)`` (``ovc_forward_backward_distill``) alternate in ONE process on one
+model, as the label-smoothing leg does.  The teacher ``P`` is a second model of the same variant with other weights, run once per
+batch size through its fused forward under ``no_grad`` -- outside the timed steps: running the teacher is not part of the student's
+call.  ``extra_mb`` is what the soft-target head moves beyond the plain one from the shapes: the copy of the teacher into its
+workspace slot (read + write), two passes over the teacher and one more pass over the stored logits (R * V * 4 bytes each), and the
+slice partials.
+
 Time: device events around ``--steps`` steps after ``--warmup`` (the second call captures the graph), one synchronise at the
 end.  FLOPs: the matrix products of the forward from the shapes (projections, attention scores and values, FFN, vocabulary)
 times 3 -- the backward has two products per forward product -- over the step time, against the nominal 157.3 TF fp32 matrix
@@ -159,6 +167,46 @@ def smoothing_probe(args, model, items, B, T, N, V):
     return rows
 
 
+def distill_probe(args, model, teacher, items, B, T, N, V):
+    """The plain step and the distillation step in turn on one model: rows ``loss = "plain"`` / ``"distill"`` per round."""
+    with torch.no_grad():
+        P = teacher(items, fused=True).contiguous()
+    torch.cuda.synchronize()
+
+    def step(**kw):
+        model.zero_grad(set_to_none=True)
+        model.xe_loss(items, dropout=args.dropout, **kw).backward()
+    forms = {"plain": {}, "distill": dict(teacher_log_probs=P, distill_weight=args.distill)}
+    for kw in forms.values():
+        for _ in range(args.warmup):
+            step(**kw)
+    torch.cuda.synchronize()
+    eng = model._fused_engine()
+    rows = []
+    for rnd in range(args.rounds):
+        for name, kw in forms.items():
+            ms = events_ms(lambda: step(**kw), args.steps)
+            if name == "plain":
+                sizer = eng.lib.ovc_train_dropout_workspace_bytes if args.dropout else eng.lib.ovc_train_workspace_bytes
+                ws = sizer(eng.desc, B, N, T)
+            else:
+                ws = eng.lib.ovc_train_distill_workspace_bytes(eng.desc, B, N, T, 1 if args.dropout else 0)
+            row = dict(variant=args.variant, B=B, T=T, N=N, dropout=args.dropout, loss=name, round=rnd, ms_per_step=round(ms, 3),
+                       workspace_mb=round(ws / 2 ** 20, 1))
+            if name == "distill":
+                R = B * T
+                row.update(distill_weight=args.distill, teacher_mb=round(4.0 * R * V / 1e6, 1),
+                           extra_mb=round(4.0 * (5 * R * V + 4 * R * ((V + 63) // 64)) / 1e6, 1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    plain = [r["ms_per_step"] for r in rows if r["loss"] == "plain"]
+    soft = [r["ms_per_step"] for r in rows if r["loss"] == "distill"]
+    rows.append(dict(variant=args.variant, B=B, dropout=args.dropout, distill_weight=args.distill, loss="ratio",
+                     distill_over_plain=round((sum(soft) / len(soft)) / (sum(plain) / len(plain)), 4)))
+    print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def variant_dims(variant):
     return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40)}.get(variant, {})
 
@@ -223,6 +271,8 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=None,
                     help="with --optimizer none and one --variant: alternate the plain step and the label-smoothed step")
     ap.add_argument("--reduction", default=None, choices=["mean", "tokens"], help="the smoothed loss's reduction (default mean)")
+    ap.add_argument("--distill", type=float, default=None,
+                    help="with --optimizer none and one --variant: alternate the plain step and the distillation step of this weight")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if "none" in args.optimizer and len(args.optimizer) > 1:
@@ -233,6 +283,8 @@ def main():
         ap.error("--label-smoothing goes with --optimizer none and one --variant")
     if args.reduction is not None and args.label_smoothing is None:
         ap.error("--reduction goes with --label-smoothing")
+    if args.distill is not None and (args.optimizer != ["none"] or len(args.variant) > 1 or args.label_smoothing is not None):
+        ap.error("--distill goes with --optimizer none and one --variant, without --label-smoothing")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
@@ -247,6 +299,10 @@ def main():
         model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
         return model.train() if args.dropout else model
     model = build() if args.optimizer == ["none"] else None
+    teacher = None
+    if args.distill is not None:
+        teacher = build_model(cfg, vocab).eval()
+        teacher.load_state_dict(synthetic_state_dict(teacher.state_dict(), seed=4321, mode="reference_init"), strict=False)
     dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3)
     dims.update(variant_dims(args.variant))
     results = []
@@ -263,6 +319,9 @@ def main():
             continue
         if args.label_smoothing is not None:
             results += smoothing_probe(args, model, items, B, T, N, V)
+            continue
+        if args.distill is not None:
+            results += distill_probe(args, model, teacher, items, B, T, N, V)
             continue
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)

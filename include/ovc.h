@@ -956,6 +956,64 @@ int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, c
 int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
 int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
 
+/* Test hooks: ONE product through ONE named GEMM tiling with every argument the internal launcher takes (appended to ABI 8; no
+ * struct of the engine changes), so that every kernel instance can be compared with an fp64 restatement over its whole argument
+ * surface (tests/test_gemm_instances_gpu.py).  The K-order class follows from the tiling, as in ovc_debug_linear_tiling.
+ *
+ *   y_s = act([x | x2_s] W_s^T + bias_s) . mask . scale + R        for each of the nseg segments s, seg_n columns each
+ *
+ * ovc_debug_gemm_call, natural C layout (pointers 8 bytes, every other field 4 unless noted):
+ *   x [M][ldx], K1 columns used; x2 [M][ldx2], K2 columns (NULL with K2 == 0, or when every segment brings seg[s].x2);
+ *   seg[s] = { W [seg_n][K1 + K2] dense, bias [seg_n] or NULL, y [M][ldy] (segments may share one buffer at column offsets or
+ *              own separate ones), x2 = this segment's own second block or NULL, planes = ovc_split_weight(W) or NULL };
+ *   residual [M][ldr], or [res_mod][ldr] read at row m % res_mod when res_mod > 0; act: 0 none, 1 ReLU;
+ *   ksplit > 1: slice s of K writes its raw partial product to seg[0].y + s * part_stride (int64, floats);
+ *   zero_rows_out [M] bytes: 1 where sum_k x[m, k] == 0;
+ *   stats [M][stats_ld] float2 / stats_t [seg_n][stats_ld] float2: per 32-column (stats) or 32-row (stats_t) block the maximum
+ *              and sum exp(y - maximum) of the finished outputs;
+ *   tgt [seg_n] int32 + tgt_logit [seg_n]: the scoring instance, tgt_logit[n] = y[tgt[n], n], y itself not stored (may be NULL);
+ *   gate: device int32 read by the gated instance (0: nothing is written);
+ *   drop_seed (device int64) + drop_site + drop_p: the dropout instance over all seg_n columns, threshold and scale from p as
+ *              everywhere (OVC_EINVAL for p outside [0, 1) or a site outside 0 .. OVC_DROPOUT_SITES - 1).
+ * Every other refusal is ovc_gemm_launch's own: ovc_debug_gemm adds no rule.
+ *
+ * ovc_debug_gemm_plan launches nothing, touches no device and dereferences none of the call's pointers (a box without a GPU can
+ * run it): from the launcher's own checks and tile-order functions it reports
+ *   out[0] OVC_OK or the code ovc_debug_gemm returns (also the return value; the rest is 0 when refused)
+ *   out[1] instance kind: 0 plain, 1 gated, 2 dropout, 3 scoring, 4 planes-direct (split classes reading seg[s].planes)
+ *   out[2] tiles_m   out[3] tiles_n per segment   out[4] group_m (M tiles per super-row)   out[5] xcd_pm (0 = super-rows)
+ *   out[6] tile order: 0 super-rows, 1 the 2-D XCD split with A inside an L2, 2 the 2-D split with A beyond an L2 and W inside
+ *          one, -1 the 16-row instances (a plain grid)
+ *   out[7] M tiles in the last super-row (< group_m: a partial one) */
+typedef struct {
+    const float* W;
+    const float* bias;
+    float* y;
+    const float* x2;
+    const void* planes;
+} ovc_debug_gemm_seg;
+typedef struct {
+    const float* x;
+    const float* x2;
+    int32_t ldx, ldx2, K1, K2, M, seg_n, nseg, ldy;
+    ovc_debug_gemm_seg seg[OVC_MAX_SEGMENTS];
+    const float* residual;
+    int32_t ldr, res_mod, act, ksplit;
+    int64_t part_stride;
+    uint8_t* zero_rows_out;
+    float* stats;
+    float* stats_t;
+    int32_t stats_ld, drop_site;
+    const int32_t* tgt;
+    float* tgt_logit;
+    const int32_t* gate;
+    const int64_t* drop_seed;
+    float drop_p;
+    int32_t reserved;
+} ovc_debug_gemm_call;
+int ovc_debug_gemm(const ovc_debug_gemm_call* call, int tiling, ovc_stream stream);
+int ovc_debug_gemm_plan(const ovc_debug_gemm_call* call, int tiling, int32_t out[8]);
+
 /* Distillation: a soft-target loss (torch's KLDivLoss(log_target = True) beside the NLL; the reference has no distillation).
  * Appended to ABI 8.  For row r = b T + t and word v, with
  *   lq[r, v]  the student's teacher-forced log-probability, (logit - M_r) - log S_r,      q = exp(lq),

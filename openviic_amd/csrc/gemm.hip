@@ -380,8 +380,9 @@ __global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void g
 }
 
 // tile order shared by both kernels: super-rows of M tiles when the A panel exceeds an L2, else the 2-D XCD split with
-// the least Infinity-Cache traffic  pn * |A| + pm * |W|
-void tile_order(const GemmArgs& a, int tiles_m, int tiles_n, int* group_m, int* xcd_pm) {
+// the least Infinity-Cache traffic  pn * |A| + pm * |W|.  Returns which of the three orders applies (ovc_debug_gemm_plan reports it).
+enum TileOrderRegime { kOrderSuperRows = 0, kOrderSplitSmallA = 1, kOrderSplitLargeA = 2 };
+int tile_order(const GemmArgs& a, int tiles_m, int tiles_n, int* group_m, int* xcd_pm) {
     const size_t a_bytes = sizeof(float) * (size_t)a.M * (a.K1 + a.K2);
     *group_m = a_bytes <= (size_t)3 << 20 ? tiles_m : (tiles_m < 8 ? tiles_m : 8);
     *xcd_pm = 0;
@@ -395,6 +396,7 @@ void tile_order(const GemmArgs& a, int tiles_m, int tiles_n, int* group_m, int* 
             const size_t cost = (size_t)(8 / pm) * a_bytes + (size_t)pm * w_bytes;
             if (cost < best) { best = cost; *xcd_pm = pm; }
         }
+        if (*xcd_pm > 0) return kOrderSplitSmallA;
     } else if (slices == 1 && w_bytes <= (size_t)3 << 20) {
         // A exceeds an L2 but W fits one and an XCD's share of A does (the transposed vocabulary product: A = fc, 21 MB,
         // W = the 2.6 MB of decoder outputs): split M over the XCDs -- inside a sub-rectangle M runs fastest, so the XCD's A
@@ -405,7 +407,28 @@ void tile_order(const GemmArgs& a, int tiles_m, int tiles_n, int* group_m, int* 
             const size_t cost = (size_t)(8 / pm) * a_bytes + (size_t)pm * w_bytes;
             if (cost < best) { best = cost; *xcd_pm = pm; }
         }
+        if (*xcd_pm > 0) return kOrderSplitLargeA;
     }
+    return kOrderSuperRows;
+}
+
+// Output tiles of a bm x bn tiling: rows, and columns per segment.
+inline void tile_counts(const GemmArgs& a, int bm, int bn, int* tiles_m, int* tiles_n) {
+    *tiles_m = (a.M + bm - 1) / bm;
+    *tiles_n = (a.seg_n + bn - 1) / bn;
+}
+
+// Which instance of a tiling a launch takes (ovc_debug_gemm_plan reports it).  fp32 tilings: by the launch options; the
+// split-precision ones: the planes-direct (WD) instance when every segment brings pre-cut planes and K has whole K tiles only
+// (the planes have no zero tail to read).
+enum GemmInstance { kInstPlain = 0, kInstGated = 1, kInstDropout = 2, kInstScoring = 3, kInstPlanesDirect = 4 };
+inline int f32_instance(const GemmLaunchOpts& opts) {
+    return opts.tgt_logit ? kInstScoring : (opts.drop_seed ? kInstDropout : (opts.gate ? kInstGated : kInstPlain));
+}
+inline bool split_reads_planes(const GemmArgs& a, int bk) {
+    bool planes = (a.K1 + a.K2) % bk == 0 && a.K1 % bk == 0;
+    for (int s = 0; s < a.nseg; ++s) planes = planes && a.seg[s].Wp != nullptr;
+    return planes;
 }
 
 // Host side of tile_coords_fast: the divisors of the tile map with their multiply-high magics.
@@ -479,11 +502,12 @@ int launch_dropout_config(const GemmArgs& a, hipStream_t stream, const GemmLaunc
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
 int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
     using Cfg = TileConfig<BM, BN, WM, WN, WK, BK, NC>;
-    const int tiles_m = (a.M + BM - 1) / BM;
-    const int tiles_n = (a.seg_n + BN - 1) / BN;
+    int tiles_m, tiles_n;
+    tile_counts(a, BM, BN, &tiles_m, &tiles_n);
     const int grid = tiles_m * tiles_n * a.nseg;
     const size_t lds_bytes = sizeof(float) * Cfg::kLdsFloats;
-    if (opts.tgt_logit) {
+    const int instance = f32_instance(opts);
+    if (instance == kInstScoring) {
         int group_m, xcd_pm;
         tile_order(a, tiles_m, tiles_n, &group_m, &xcd_pm);
         const TileMap map = make_tile_map(grid, tiles_m, tiles_n, group_m, xcd_pm, a.K1 + a.K2);
@@ -497,8 +521,8 @@ int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& o
     // opts.copies (tuner only): gridDim.z identical copies of the product in one launch (the kernel ignores
     // blockIdx.z), a proxy for "this many batches in flight" that needs no extra streams.
     const dim3 grid3(grid, slices, opts.copies > 1 ? opts.copies : 1);
-    if (opts.drop_seed) return launch_dropout_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, grid3, lds_bytes);
-    if (opts.gate) {
+    if (instance == kInstDropout) return launch_dropout_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, grid3, lds_bytes);
+    if (instance == kInstGated) {
         static std::once_flag gated_attr_once;
         std::call_once(gated_attr_once, [&] {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_gated<BM, BN, WM, WN, WK, BK, NC>),
@@ -530,12 +554,10 @@ template <int BM, int BN, int WM, int WN, int BK, int MODE, bool WD = false>
 int launch_split_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
     using Cfg = SplitConfig<BM, BN, WM, WN, BK, MODE, WD>;
     if constexpr (!WD) {             // pre-cut weights on every segment: the instance that reads them straight from memory
-        bool planes = (a.K1 + a.K2) % BK == 0 && a.K1 % BK == 0;   // whole K tiles only: the planes have no zero tail to read
-        for (int s = 0; s < a.nseg; ++s) planes = planes && a.seg[s].Wp != nullptr;
-        if (planes) return launch_split_config<BM, BN, WM, WN, BK, MODE, true>(a, stream, opts);
+        if (split_reads_planes(a, BK)) return launch_split_config<BM, BN, WM, WN, BK, MODE, true>(a, stream, opts);
     }
-    const int tiles_m = (a.M + BM - 1) / BM;
-    const int tiles_n = (a.seg_n + BN - 1) / BN;
+    int tiles_m, tiles_n;
+    tile_counts(a, BM, BN, &tiles_m, &tiles_n);
     const int grid = tiles_m * tiles_n * a.nseg;
     const size_t lds_bytes = Cfg::kLdsBytes;
     static std::once_flag attr_once;
@@ -557,8 +579,8 @@ int launch_split_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchO
 
 template <int NB>
 int launch_rows16_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
-    const int tiles_m = (a.M + 15) / 16;
-    const int tiles_n = (a.seg_n + 16 * NB - 1) / (16 * NB);
+    int tiles_m, tiles_n;
+    tile_counts(a, 16, 16 * NB, &tiles_m, &tiles_n);
     const size_t lds_bytes = sizeof(float) * 4 * (16 + 16 * NB) * kRows16Ldt;
     static std::once_flag attr_once;
     std::call_once(attr_once, [&] {
@@ -566,7 +588,7 @@ int launch_rows16_config(const GemmArgs& a, hipStream_t stream, const GemmLaunch
     });
     const int kslice = a.K1 / (a.ksplit > 1 ? a.ksplit : 1);
     const dim3 grid3(tiles_n * a.nseg, tiles_m * (opts.copies > 1 ? opts.copies : 1), a.ksplit > 1 ? a.ksplit : 1);
-    if (opts.gate) {
+    if (f32_instance(opts) == kInstGated) {
         static std::once_flag gated_attr_once;
         std::call_once(gated_attr_once, [&] {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows16_f32_gated<NB>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -769,8 +791,10 @@ int ovc_gemm_pick_tiling(const GemmArgs& a, const GemmLaunchOpts& opts) {
     return pick;
 }
 
-int ovc_gemm_launch(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
-    if (const int rc = ovc_device_guard()) return rc;
+namespace {
+// Every argument check of ovc_gemm_launch, host only (no device access): OVC_OK or the code the launch returns.  The one
+// validation path: ovc_debug_gemm_plan answers from it as well.
+int gemm_check_args(const GemmArgs& a, const GemmLaunchOpts& opts) {
     const int K = a.K1 + a.K2;
     if (a.M <= 0 || a.seg_n <= 0 || a.nseg <= 0 || a.nseg > OVC_MAX_SEGMENTS || K <= 0) return OVC_EINVAL;
     if (a.kchains != 0 && !class_ok(a.kchains)) return OVC_EINVAL;
@@ -805,7 +829,13 @@ int ovc_gemm_launch(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts&
     if ((long)(a.M + 256) * a.lda1 * 4 > kMaxBytes || (a.K2 && (long)(a.M + 256) * a.lda2 * 4 > kMaxBytes) ||
         (long)(a.seg_n + 256) * K * 4 > kMaxBytes || (long)(a.M + 256) * a.ldc * 4 > kMaxBytes ||
         (a.R && (long)(a.M + 256) * a.ldr * 4 > kMaxBytes)) return OVC_EINVAL;
+    return OVC_OK;
+}
+}  // namespace
 
+int ovc_gemm_launch(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
+    if (const int rc = ovc_device_guard()) return rc;
+    if (const int rc = gemm_check_args(a, opts)) return rc;
     const int pick = ovc_gemm_pick_tiling(a, opts);
     switch (pick) {
 #define OVC_TILING_CASE(id, bm, bn, wm, wn, wk, bk, nc) case id: return launch_config<bm, bn, wm, wn, wk, bk, nc>(a, stream, opts);
@@ -1004,6 +1034,65 @@ extern "C" int ovc_debug_linear_tiling(const float* x, int K, const float* W, co
         const int rc = ovc_gemm_launch(a, ovc_hip_stream(stream), opts);
         if (rc != OVC_OK) return rc;
     }
+    return OVC_OK;
+}
+
+namespace {
+// ovc_debug_gemm_call -> GemmArgs / GemmLaunchOpts (the class follows from the tiling).  false: no call, no such tiling, or a
+// dropout p / site outside what ovc_dropout_threshold and the site numbering are defined for.
+bool debug_gemm_fill(const ovc_debug_gemm_call* c, int tiling, GemmArgs* a, GemmLaunchOpts* opts) {
+    if (!c || tiling < 0 || tiling >= kNumTilings) return false;
+    if (c->drop_seed && (!(c->drop_p >= 0.f && c->drop_p < 1.f) || c->drop_site < 0 || c->drop_site >= OVC_DROPOUT_SITES)) return false;
+    *a = GemmArgs{};
+    a->A1 = c->x; a->lda1 = c->ldx; a->K1 = c->K1;
+    a->A2 = c->x2; a->lda2 = c->ldx2; a->K2 = c->K2;
+    a->M = c->M; a->seg_n = c->seg_n; a->nseg = c->nseg; a->ldc = c->ldy;
+    a->R = c->residual; a->ldr = c->ldr; a->res_mod = c->res_mod; a->act = c->act;
+    a->ksplit = c->ksplit; a->part_stride = (long)c->part_stride;
+    a->kchains = tiling_chains(tiling);
+    a->zero_rows_out = c->zero_rows_out; a->stats = c->stats; a->stats_t = c->stats_t; a->stats_ld = c->stats_ld;
+    for (int s = 0; s < OVC_MAX_SEGMENTS; ++s)
+        a->seg[s] = GemmSegment{c->seg[s].W, c->seg[s].bias, c->seg[s].y, c->seg[s].x2, c->seg[s].planes};
+    *opts = GemmLaunchOpts{};
+    opts->forced_tiling = tiling;
+    opts->tgt = c->tgt; opts->tgt_logit = c->tgt_logit; opts->gate = c->gate;
+    if (c->drop_seed) {
+        opts->drop_seed = c->drop_seed; opts->drop_site = (uint32_t)c->drop_site;
+        opts->drop_thr = ovc_dropout_threshold(c->drop_p); opts->drop_scale = ovc_dropout_scale(c->drop_p);
+        opts->drop_cols = c->seg_n;
+    }
+    return true;
+}
+}  // namespace
+
+// One product through ONE named tiling with every argument GemmArgs / GemmLaunchOpts carry (include/ovc.h).
+extern "C" int ovc_debug_gemm(const ovc_debug_gemm_call* call, int tiling, ovc_stream stream) {
+    GemmArgs a;
+    GemmLaunchOpts opts;
+    if (!debug_gemm_fill(call, tiling, &a, &opts)) return OVC_EINVAL;
+    return ovc_gemm_launch(a, ovc_hip_stream(stream), opts);
+}
+
+// What ovc_debug_gemm would do, from the launcher's own functions; host only.
+extern "C" int ovc_debug_gemm_plan(const ovc_debug_gemm_call* call, int tiling, int32_t out[8]) {
+    if (!out) return OVC_EINVAL;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    GemmArgs a;
+    GemmLaunchOpts opts;
+    if (!debug_gemm_fill(call, tiling, &a, &opts)) return out[0] = OVC_EINVAL;
+    if (const int rc = gemm_check_args(a, opts)) return out[0] = rc;
+    if (ovc_gemm_pick_tiling(a, opts) != tiling) return out[0] = OVC_EINVAL;
+    const TilingInfo& t = kTilings[tiling];
+    out[1] = t.planes ? (split_reads_planes(a, t.bk) ? kInstPlanesDirect : kInstPlain) : f32_instance(opts);
+    int tiles_m, tiles_n;
+    tile_counts(a, t.bm, t.bn, &tiles_m, &tiles_n);
+    out[2] = tiles_m; out[3] = tiles_n;
+    if (t.bm == 16) { out[4] = tiles_m; out[6] = -1; out[7] = tiles_m; return OVC_OK; }   // gemm_rows16_f32: a plain 3-D grid
+    int group_m, xcd_pm;
+    out[6] = tile_order(a, tiles_m, tiles_n, &group_m, &xcd_pm);
+    const int slices = a.ksplit > 1 ? a.ksplit : 1;
+    const TileMap map = make_tile_map(tiles_m * tiles_n * a.nseg, tiles_m, tiles_n, group_m, xcd_pm, (a.K1 + a.K2) / slices);
+    out[4] = map.group_m; out[5] = map.xcd_pm; out[7] = map.gm_last;
     return OVC_OK;
 }
 

@@ -105,7 +105,28 @@ class EvalCorpus(ctypes.Structure):
                 ("pad_idx", c_int32), ("bos_idx", c_int32), ("eos_idx", c_int32), ("unk_idx", c_int32)]
 
 
-OVC_METRIC_STATS = 12        # int32 per caption in front of the per-reference LCS lengths (include/ovc.h)
+OVC_MAX_SEGMENTS = 8
+OVC_DROPOUT_SITES = 1 + 3 * OVC_MAX_LAYERS + 4 * OVC_MAX_LAYERS
+
+
+class GemmSeg(ctypes.Structure):
+    """``ovc_debug_gemm_seg``: one weight segment of ``ovc_debug_gemm_call``."""
+    _fields_ = [("W", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("x2", c_void_p), ("planes", c_void_p)]
+
+
+class GemmCall(ctypes.Structure):
+    """``ovc_debug_gemm_call``: everything the internal GEMM launcher takes for one product (``include/ovc.h``)."""
+    _fields_ = [("x", c_void_p), ("x2", c_void_p), ("ldx", c_int32), ("ldx2", c_int32), ("K1", c_int32), ("K2", c_int32),
+                ("M", c_int32), ("seg_n", c_int32), ("nseg", c_int32), ("ldy", c_int32), ("seg", GemmSeg * OVC_MAX_SEGMENTS),
+                ("residual", c_void_p), ("ldr", c_int32), ("res_mod", c_int32), ("act", c_int32), ("ksplit", c_int32),
+                ("part_stride", c_int64), ("zero_rows_out", c_void_p), ("stats", c_void_p), ("stats_t", c_void_p),
+                ("stats_ld", c_int32), ("drop_site", c_int32), ("tgt", c_void_p), ("tgt_logit", c_void_p), ("gate", c_void_p),
+                ("drop_seed", c_void_p), ("drop_p", c_float), ("reserved", c_int32)]
+
+
+GEMM_PLAIN, GEMM_GATED, GEMM_DROPOUT, GEMM_SCORING, GEMM_PLANES_DIRECT = 0, 1, 2, 3, 4
+
+OVC_METRIC_STATS = 12       # int32 per caption in front of the per-reference LCS lengths (include/ovc.h)
 OVC_METRIC_MAX_REFS = 4096
 
 ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC, ENC_CROSS_LEVEL = 0, 1, 2, 3
@@ -245,6 +266,8 @@ SIGNATURES = {
                                                  c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "ovc_debug_decode_self_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ovc_debug_decode_cross_form": (c_int, [c_int, c_int, c_int, c_int]),
+    "ovc_debug_gemm": (c_int, [POINTER(GemmCall), c_int, c_void_p]),
+    "ovc_debug_gemm_plan": (c_int, [POINTER(GemmCall), c_int, POINTER(c_int32)]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -262,7 +285,7 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_sample_shaped_workspace_bytes", "ovc_sample_shaped", "ovc_sample_shaped_graph",
                  "ovc_sample_choice_workspace_bytes", "ovc_sample_choice",
                  "ovc_debug_decode_self_partial_bytes", "ovc_debug_decode_self_attention", "ovc_debug_decode_cross_attention",
-                 "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form",
+                 "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form", "ovc_debug_gemm", "ovc_debug_gemm_plan",
                  "ovc_search_constraints_ok", "ovc_beam_search_constrained", "ovc_beam_search_constrained_graph",
                  "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update",
                  "ovc_ensemble_ok", "ovc_ensemble_workspace_bytes", "ovc_ensemble_beam_search", "ovc_ensemble_beam_search_graph",

@@ -91,6 +91,20 @@ int ovc_attention(const float* q, const float* k, const float* v, int b, int nq,
                   const float* geometry, const float* mem_k, const float* mem_v, int m,
                   float mem_scale_k, float mem_scale_v, float* out, ovc_stream stream);
 
+/* The probabilities of that operator, written out: the arguments of ovc_attention without the values, the output and the geometry
+ * bias (no cross-attention has one), plus the map and its strides.
+ *   maps[b*map_sb + a*map_sh + iq*map_sq + j] = softmax_j( (q . k_j) / sqrtf(dk), masked keys -> -inf ),  j < nk + m
+ *   for head a and query iq; key j >= nk is memory slot j - nk, mem_scale_k * mem_k, never masked.  The arithmetic is the forward
+ *   kernels': an fp32 dot product, ONE division by sqrtf(dk), expf(s - max), ONE division by the sum; only the order of the dot
+ *   and of the sum differs from them (as it does among them).  A masked key is exactly 0; a query whose keys are all masked gets
+ *   NaN in every key.  Each row is written as float4s up to nk + m rounded up to 4 (the tail holds 0 or NaN), so map_sq >= that,
+ *   map_sh >= nq*map_sq, map_sb >= h*map_sh, all multiples of 4, and q, k, mem_k, maps 16-byte aligned: OVC_EINVAL otherwise, and
+ *   on a device without 102 400 bytes of LDS per workgroup.  Every (nq, nk, dk, m) ovc_attention serves; keys beyond 128 pass in
+ *   tiles of 128 in three sweeps (maximum, sum, probabilities), each forming the same scores again: the same rule, no rescaling. */
+int ovc_cross_attention_maps(const float* q, const float* k, int b, int nq, int nk, int h, int dk, const uint8_t* mask,
+                             long mask_sb, long mask_sq, const float* mem_k, int m, float mem_scale_k, float* maps,
+                             long map_sb, long map_sh, long map_sq, ovc_stream stream);
+
 /* The two element-wise tails of the cross-level (CaMo) encoder, encoders.py:238-247.
  * ovc_linear_leaky: y[M,N] = residual + scale * leaky_relu(x W^T + bias, slope)  (residual [M,N] row stride ldr, or NULL = 0);
  *   x [M,K] row stride ldx, y row stride ldy.  The product is ovc_linear's (same K order, same bits); the activation,
@@ -325,6 +339,41 @@ size_t ovc_forward_workspace_bytes(const ovc_model* m, int B, int N, int T, int 
 int ovc_forward(const ovc_model* m, const float* features, const float* boxes, int B, int N, const int64_t* tokens,
                 const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* logp_out, float* token_logp_out,
                 int use_graph, ovc_stream stream);
+
+/* Cross-attention maps of given captions (appended to ABI 8; no struct changes): which regions each word was read from.  The
+ * teacher-forced forward of ovc_forward / ovc_sequence_backward, with the decoder's cross-attention probabilities kept.
+ * The rule, for decoder layer l, encoder level v (n_levels: 1 unless the decoder is meshed), head a, decoder row (b, s, t) and key
+ * j < K = N + m, m the cross-attention's memory slots (ovc_model::memory where the layers' cross_att.m_k is set, else 0):
+ *   P[b,s,l,v,a,t,j] = softmax_j( (q . k_j) / sqrtf(d_k), masked keys -> -inf )
+ * q = row (b,s,t) of that layer's cross_att.q applied to the layer's self-attention output x1; k_j = the level's projected key j of
+ * image b, or slot key j - N, sqrtf(d_k) * m_k, exactly as the forward forms it.  Masked keys are the image's padding regions (a
+ * feature row that sums to 0); slot keys are never masked.  fp32 dot product, one division by sqrtf(d_k), expf(s - max), one
+ * division by the sum: the forward kernels' arithmetic (ovc_cross_attention_maps above; only the order of the dot and of the
+ * softmax sum may differ from them).  A masked key is exactly 0; an image without a valid region gives NaN rows, as the
+ * reference's softmax does; dropout is the identity, as in ovc_forward.
+ * Exactly one of tokens / ids is given (OVC_EINVAL otherwise):
+ *   tokens [B, T]     decoder inputs as ovc_forward takes them; S must be 1.
+ *   ids    [B, S, T]  a search's output, S sequences per image: the inputs are <bos>, ids[.., :-1] (ovc_sequence_backward's), and
+ *                     rows behind a sequence's first <eos> are exactly 0 in maps_out, like the search's log_probs.
+ * maps_out, reduce:
+ *   OVC_MAPS_NONE   [B, S, L, levels, h, T, K]
+ *   OVC_MAPS_HEADS  [B, S, L, levels, T, K]: the mean over heads, (((P_0 + P_1) + ...) + P_{h-1}) / h in fp32.
+ * token_logp_out [B, S, T], optional: the scoring tail of ovc_forward on the same pass -- ids form: the log-probability of
+ * ids[b, s, t] (0 where it is <pad>); tokens form: that of the NEXT token of the caption, tokens[b, t + 1] (<pad> behind the last:
+ * 0), which is ovc_forward's token_logp_out for the reference's shifted-right targets, bit for bit.
+ * The kernels that read the caller's inputs and those that write its outputs stay outside the hipGraph; use_graph != 0 captures the
+ * body on the second call of a (model contents, workspace, B, N, T, S) and replays it (the cache and rules of ovc_forward; the same
+ * bits either way).  No other call changes a launch.
+ * ovc_attention_maps_workspace_bytes: ovc_forward's scoring workspace for B*S*T rows plus the map of every layer, level and head
+ * and the staged inputs; 0 for anything ovc_forward_workspace_bytes refuses, for S outside 1..OVC_MAX_BEAM, for B*S*T above 2^24,
+ * for layers that disagree on their cross-attention slots, and where the map -- L * levels * B * h * S*T rows of K rounded up to 4
+ * floats -- has 2^31 elements or more (the finish kernel indexes it with one 32-bit index per output element). */
+#define OVC_MAPS_NONE   0
+#define OVC_MAPS_HEADS  1
+size_t ovc_attention_maps_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_attention_maps(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* tokens,
+                       const int64_t* ids, int T, void* workspace, size_t workspace_bytes, float* maps_out, int reduce,
+                       float* token_logp_out, int use_graph, ovc_stream stream);
 
 /* Training step of the reference's cross-entropy loss (vi_trainer.py:100-119): the forward of ovc_forward, then the gradient of
  *   loss = -sum_{r: targets[r] != pad} logp[r, targets[r]] / #{r: targets[r] != pad}      (NLLLoss(ignore_index=pad), mean)
@@ -955,6 +1004,12 @@ int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, c
                                      size_t out_level_stride, int ldo, const int32_t* gate, ovc_stream stream);
 int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
 int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
+
+/* Test hook (tests/test_attention_maps_gpu.py): ovc_cross_attention_maps on raw operands, as ovc_attention_maps launches it for one
+ * layer and level -- q [b, nq, h*d_k], k [b, nk, h*d_k], mask [b, nk] (the image's padding regions; NULL: none), m slot keys
+ * m_k [m, h*d_k] taken times sqrtf(d_k) -> P [b, h, nq, ld], ld = nk + m rounded up to 4. */
+int ovc_debug_cross_attention_maps(const float* q, const float* k, const uint8_t* mask, const float* m_k, int b, int nq, int nk,
+                                   int h, int d_k, int m, float* P, ovc_stream stream);
 
 /* Test hooks: ONE product through ONE named GEMM tiling with every argument the internal launcher takes (appended to ABI 8; no
  * struct of the engine changes), so that every kernel instance can be compared with an fp64 restatement over its whole argument

@@ -206,6 +206,23 @@ class BaseTransformer(Module):
         return self._fused_engine().score(*self._engine_inputs(input_features), input_features["caption_tokens"],
                                           input_features["shifted_right_caption_tokens"])
 
+    def attention_maps(self, input_features, ids=None, reduce="none", return_log_probs=False):
+        """Which regions each word was read from: the decoder's cross-attention probabilities of given captions on the HIP engine
+        (``CaptionEngine.attention_maps``, ``ovc_attention_maps``), ``softmax(q K^T / sqrt(d_k))`` of every decoder layer, encoder
+        level and head with the image's padding regions masked -- dropout taken as the identity, as in ``self(items, fused=True)``.
+        ``ids=None``: of ``input_features["caption_tokens"]`` ``(B, T)`` as decoder inputs; else of ``ids`` ``(B, T)`` or ``(B, S,
+        T)``, a search's output (inputs ``<bos>, ids[..., :-1]``; rows behind a sequence's first ``<eos>`` are 0, like the search's
+        ``log_probs``).  Returns ``(B, S, L, levels, h, T, K)`` (``reduce="none"``) or ``(B, S, L, levels, T, K)`` (``"heads"``: the
+        mean over heads) on the model's device, without gradient and without the S axis unless ``ids`` is 3-D; with
+        ``return_log_probs`` also the ``(B, S, T)`` log-probabilities of the same pass."""
+        eng = self._fused_engine()
+        features, boxes = self._engine_inputs(input_features)
+        with torch.no_grad():
+            if ids is None:
+                return eng.attention_maps(features, boxes, caption_tokens=input_features["caption_tokens"], reduce=reduce,
+                                          return_log_probs=return_log_probs)
+            return eng.attention_maps(features, boxes, ids=ids, reduce=reduce, return_log_probs=return_log_probs)
+
     def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None, teacher_log_probs=None,
                 distill_weight=None):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against

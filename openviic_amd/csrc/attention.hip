@@ -928,3 +928,263 @@ extern "C" int ovc_debug_decode_cross_attention(const float* q, int ldq, const f
     p.out = out; p.out_level_stride = out_level_stride; p.ldo = ldo;
     return ovc_decode_cross_attention(p, B, heads, levels, ovc_hip_stream(stream), gate);
 }
+
+// =================================================================================================
+// Cross-attention maps (ovc_cross_attention_maps): the probabilities themselves, to memory
+// =================================================================================================
+//
+// cross_attention_maps_kernel -- P = softmax(q K^T / sqrt(d_k), masked keys -> -inf) of ovc_attention's operands without the
+// values: the rule of include/ovc.h, the arithmetic of the forward kernels above (fp32 dot product on the matrix cores, ONE
+// division by sqrtf(d_k), expf(s - max), ONE division by the sum).
+//
+// One workgroup per (image, head, 128 queries), a wave per 32 queries, the register layout of attention_regs_kernel:
+//   S^T[key][q] = K Q^T on v_mfma_f32_32x32x2_f32 with the QUERY on the lane (q = lane & 31) and 16 keys of each 32-key tile on
+//   its accumulator registers (key = 32 tk + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)): scale, mask and the softmax over keys are
+//   register arithmetic plus one __shfl_xor(32) per reduction.
+// Keys pass through LDS in tiles of kMapKeys = 128 (four accumulators per wave).
+//   One tile (nk + m <= 128, every shipped configuration): the scores are formed once and stay in registers.
+//   More tiles: three sweeps over the tiles in ascending order -- the row maximum, then the sum of expf(s - max), then the
+//   probabilities -- each forming a tile's scores again from the same operands, so the three see the same bits and the result
+//   is the rule's: no running maximum, no rescaling.  Nothing is read back from the map.
+// A query's sum adds its lane's keys tile by tile in register order, then the other half's: only that order differs from the
+// forward kernels (include/ovc.h).
+// Output: a wave turns its [key][query] registers into a [32 queries][128 keys] image in LDS (its own region: no workgroup
+// barrier) and rows leave as contiguous keys, one float4 per lane, 512 bytes per row and tile.  p.kp = nk + m rounded up to 4
+// floats are written per row (the tail past nk + m holds 0, or NaN in a row without a valid key); nothing beyond it.
+// A row whose keys are all masked is NaN in every valid key, as the reference's softmax over a row of -inf.
+// KG = 8-deep d groups of Q.K (dk <= 8 KG).
+constexpr int kMapKeys = 128;
+constexpr int kMapLd = kMapKeys + 4;      // row stride (floats) of a wave's output image
+
+struct MapArgs {
+    const float* q; const float* k; float* maps;
+    int nq, nk, h, dk;
+    const uint8_t* mask; long mask_sb, mask_sq;
+    const float* mem_k; int m; float mem_scale_k;
+    long map_sb, map_sh, map_sq;          // strides (floats) of image, head and query row of the map; keys are contiguous
+    int kp;                               // nk + m rounded up to a multiple of 4
+    int qtiles;
+};
+
+template <int KG>
+__global__ __launch_bounds__(256) void cross_attention_maps_kernel(MapArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int NKT = kMapKeys / 32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int qt = blockIdx.x % p.qtiles;
+    const int hd = (blockIdx.x / p.qtiles) % p.h;
+    const int b = blockIdx.x / (p.qtiles * p.h);
+    const int nkt = p.nk + p.m;
+    const int tiles = (nkt + kMapKeys - 1) / kMapKeys;
+    float* Ks = lds;                                               // [128][68]
+    float* Ps = Ks + kMapKeys * kLdQK + wave * 32 * kMapLd;        // this wave's [32][132]
+
+    const int qi = lane & 31, half = lane >> 5;
+    const int gq = qt * kMapKeys + wave * 32 + qi;                 // this lane's query
+    const bool q_ok = gq < p.nq;
+    const bool wave_live = qt * kMapKeys + wave * 32 < p.nq;       // wave-uniform: waves past the last query only stage
+    f32x4 qf[KG];
+    {
+        const float* qrow = p.q + ((size_t)b * p.nq + min(gq, p.nq - 1)) * (p.h * p.dk) + hd * p.dk;
+#pragma unroll
+        for (int kk = 0; kk < KG; ++kk) {
+            const int d = 8 * kk + 4 * half;
+            qf[kk] = *reinterpret_cast<const f32x4*>(qrow + min(d, p.dk - 4));
+            if (!q_ok || d >= p.dk) qf[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    const float inv_scale = sqrtf((float)p.dk);
+    const uint8_t* mrow = p.mask ? p.mask + (size_t)b * p.mask_sb + (size_t)min(gq, p.nq - 1) * p.mask_sq : nullptr;
+    float* orow = p.maps + (size_t)b * p.map_sb + (size_t)hd * p.map_sh;
+
+    f32x16 st[NKT];
+    // The masked, scaled scores of key tile k0 .. k0 + 127 into st: the tile's K rows -> LDS (zero-filled past the last key,
+    // every load issued before the first LDS store, none of them conditional), S^T = K Q^T, then scale and mask.  All four
+    // waves stage and meet at both barriers; a wave without queries skips the arithmetic.
+    auto scores = [&](int k0) {
+        {
+            const int c4 = tid & 15, col = c4 * 4, r0 = tid >> 4;
+            constexpr int kPasses = kMapKeys / 16;
+            // Every load is unconditional and from ONE base with a clamped (always valid) row: the image's keys here, the slot
+            // keys -- only where the call has slots, a workgroup-uniform branch -- below.  Which VALUE a row takes is chosen
+            // afterwards; no address is ever chosen between the two bases (p.mem_k is NULL without slots).
+            f32x4 kv[kPasses], mv[kPasses];
+#pragma unroll
+            for (int i = 0; i < kPasses; ++i) {
+                const int kr = min(k0 + r0 + 16 * i, p.nk - 1);
+                kv[i] = *reinterpret_cast<const f32x4*>(p.k + ((size_t)b * p.nk + kr) * (p.h * p.dk) + hd * p.dk + min(col, p.dk - 4));
+                mv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            if (p.m > 0) {
+#pragma unroll
+                for (int i = 0; i < kPasses; ++i) {
+                    const int mr = min(max(k0 + r0 + 16 * i - p.nk, 0), p.m - 1);
+                    mv[i] = *reinterpret_cast<const f32x4*>(p.mem_k + (size_t)mr * (p.h * p.dk) + hd * p.dk + min(col, p.dk - 4)) * p.mem_scale_k;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < kPasses; ++i) {
+                const int r = r0 + 16 * i, kr = k0 + r;
+                f32x4 kx = kr < p.nk ? kv[i] : mv[i];               // a real key, else a slot key
+                if (kr >= nkt || col >= p.dk) kx = f32x4{0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(Ks + r * kLdQK + col) = kx;
+            }
+        }
+        __syncthreads();
+        if (wave_live) {
+#pragma unroll
+            for (int tk = 0; tk < NKT; ++tk)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) st[tk][r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < KG; ++kk) {
+                f32x4 kf[NKT];
+#pragma unroll
+                for (int tk = 0; tk < NKT; ++tk) kf[tk] = *reinterpret_cast<const f32x4*>(Ks + (tk * 32 + qi) * kLdQK + 8 * kk + 4 * half);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int tk = 0; tk < NKT; ++tk) st[tk] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[tk][s], qf[kk][s], st[tk], 0, 0, 0);
+            }
+            // per 32-key tile the mask bytes of this lane's 16 keys: unconditional loads at clamped (always valid) positions,
+            // in flight together; a call without a mask (workgroup-uniform) loads nothing
+#pragma unroll
+            for (int tk = 0; tk < NKT; ++tk) {
+                uint8_t mb[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mb[r] = 0;
+                if (p.mask) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mb[r] = mrow[min(k0 + tk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, p.nk - 1)];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kj = k0 + tk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const float s = st[tk][r] / inv_scale;
+                    st[tk][r] = (kj >= nkt || (kj < p.nk && mb[r])) ? -INFINITY : s;
+                }
+            }
+        }
+        __syncthreads();                                           // every wave is done with the K image
+    };
+    auto tile_max = [&](float mx) {
+#pragma unroll
+        for (int tk = 0; tk < NKT; ++tk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[tk][r]);
+        return mx;
+    };
+    // st <- expf(st - mx); returns sum + the tile's exponentials, added in register order
+    auto tile_exp = [&](float mx, float sum) {
+#pragma unroll
+        for (int tk = 0; tk < NKT; ++tk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = expf(st[tk][r] - mx);
+                st[tk][r] = e;
+                sum += e;
+            }
+        return sum;
+    };
+    // st / sum -> the wave's LDS image [query][key] -> the map's rows, contiguous keys
+    auto tile_store = [&](int k0, float sum) {
+#pragma unroll
+        for (int tk = 0; tk < NKT; ++tk)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                *reinterpret_cast<f32x4*>(Ps + qi * kMapLd + tk * 32 + 8 * j + 4 * half) =
+                    f32x4{st[tk][4 * j] / sum, st[tk][4 * j + 1] / sum, st[tk][4 * j + 2] / sum, st[tk][4 * j + 3] / sum};
+        // (the wave reads back only what it wrote itself: no workgroup barrier, the compiler's lgkmcnt wait orders it)
+        const int col = (lane & 31) * 4;
+#pragma unroll
+        for (int pass = 0; pass < 16; ++pass) {
+            const int row = pass * 2 + half;
+            const int oq = qt * kMapKeys + wave * 32 + row;
+            if (oq < p.nq && k0 + col < p.kp)
+                *reinterpret_cast<f32x4*>(orow + (size_t)oq * p.map_sq + k0 + col) = *reinterpret_cast<const f32x4*>(Ps + row * kMapLd + col);
+        }
+    };
+
+    if (tiles == 1) {
+        scores(0);
+        if (!wave_live) return;
+        float mx = tile_max(-INFINITY);
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = tile_exp(mx, 0.f);
+        sum += __shfl_xor(sum, 32, 64);
+        tile_store(0, sum);
+        return;
+    }
+    float mx = -INFINITY, sum = 0.f;
+    for (int t = 0; t < tiles; ++t) {
+        scores(t * kMapKeys);
+        if (wave_live) mx = tile_max(mx);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    for (int t = 0; t < tiles; ++t) {
+        scores(t * kMapKeys);
+        if (wave_live) sum = tile_exp(mx, sum);
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    for (int t = 0; t < tiles; ++t) {
+        scores(t * kMapKeys);
+        if (wave_live) {
+            (void)tile_exp(mx, 0.f);
+            tile_store(t * kMapKeys, sum);
+        }
+    }
+}
+
+// maps [b][h][nq][row stride map_sq]: image stride map_sb, head stride map_sh (floats; include/ovc.h)
+extern "C" int ovc_cross_attention_maps(const float* q, const float* k, int b, int nq, int nk, int h, int dk, const uint8_t* mask,
+                                        long mask_sb, long mask_sq, const float* mem_k, int m, float mem_scale_k, float* maps,
+                                        long map_sb, long map_sh, long map_sq, ovc_stream stream) {
+    if (!q || !k || !maps || b <= 0 || nq <= 0 || nk <= 0 || h <= 0) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;      // the kernel attribute below is raised once per process
+    if (dk <= 0 || (dk & 3) || dk > 64) return OVC_EINVAL;
+    if (m < 0 || (m > 0 && !mem_k)) return OVC_EINVAL;
+    if (!ovc_aligned16(q) || !ovc_aligned16(k) || !ovc_aligned16(maps) || (m > 0 && !ovc_aligned16(mem_k))) return OVC_EINVAL;
+    const long kp = ((long)nk + m + 3) & ~3L;
+    // float4 row stores: every stride a multiple of 4 floats, a row at least kp wide, rows / heads / images that do not overlap
+    if ((map_sq & 3) || (map_sh & 3) || (map_sb & 3) || map_sq < kp || map_sh < (long)nq * map_sq || map_sb < (long)h * map_sh)
+        return OVC_EINVAL;
+    const long qtiles = ((long)nq + kMapKeys - 1) / kMapKeys;
+    if (kp > 0x7fffffffL || (long)b * h * qtiles > 0x7fffffffL) return OVC_EINVAL;
+    MapArgs p{};
+    p.q = q; p.k = k; p.maps = maps;
+    p.nq = nq; p.nk = nk; p.h = h; p.dk = dk;
+    p.mask = mask; p.mask_sb = mask_sb; p.mask_sq = mask_sq;
+    p.mem_k = mem_k; p.m = m; p.mem_scale_k = mem_scale_k;
+    p.map_sb = map_sb; p.map_sh = map_sh; p.map_sq = map_sq;
+    p.kp = (int)kp; p.qtiles = (int)qtiles;
+    // LDS: the K tile [128][68] and four output images [32][132]: 102 400 bytes, above the 64 KiB a launch gets by default
+    constexpr size_t bytes = sizeof(float) * ((size_t)kMapKeys * kLdQK + 4 * 32 * (size_t)kMapLd);
+    const dim3 grid((unsigned)(b * h * qtiles)), block(256);
+#define OVC_MAPS(KG)                                                                                                  \
+    do {                                                                                                              \
+        static bool fits = false;                                                                                     \
+        static std::once_flag once;                                                                                   \
+        std::call_once(once, [] {                                                                                     \
+            fits = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attention_maps_kernel<KG>),               \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;         \
+            if (!fits) (void)hipGetLastError();                                                                       \
+        });                                                                                                           \
+        if (!fits) return OVC_EINVAL;                      /* a device without that much LDS per workgroup */         \
+        hipLaunchKernelGGL((cross_attention_maps_kernel<KG>), grid, block, bytes, ovc_hip_stream(stream), p);         \
+    } while (0)
+    if (dk <= 16) OVC_MAPS(2); else if (dk <= 32) OVC_MAPS(4); else OVC_MAPS(8);
+#undef OVC_MAPS
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+// Test hook (tests/test_attention_maps_gpu.py): the kernel on raw operands, as run_decoder_layer launches it for one level --
+// q [b, nq, h*d_k], k [b, nk, h*d_k], mask [b, nk] (NULL: none), m slot keys m_k [m, h*d_k] scaled by sqrtf(d_k) -> P [b, h, nq,
+// ld] with ld = nk + m rounded up to 4.
+extern "C" int ovc_debug_cross_attention_maps(const float* q, const float* k, const uint8_t* mask, const float* m_k, int b, int nq,
+                                              int nk, int h, int d_k, int m, float* P, ovc_stream stream) {
+    if (d_k <= 0 || nq <= 0 || nk <= 0 || h <= 0 || m < 0) return OVC_EINVAL;
+    const long ld = ((long)nk + m + 3) & ~3L;
+    return ovc_cross_attention_maps(q, k, b, nq, nk, h, d_k, mask, nk, 0, m_k, m, sqrtf((float)d_k), P, (long)h * nq * ld,
+                                    (long)nq * ld, ld, stream);
+}

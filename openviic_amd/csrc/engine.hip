@@ -138,6 +138,9 @@ struct Workspace {
     // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
     // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
+    // ovc_attention_maps: the cross-attention probabilities [L][levels][B][h][S*T][K rounded up to 4] (nullptr in every other call:
+    // run_decoder_layer then issues what it always did)
+    float* maps;
     // ensemble search: the M members' workspaces, [0] this one (nullptr otherwise).  The beam state -- running, alive, hist, lp, anc,
     // tok, padflag, order, the out buffers -- lives once, here; the other members' structs alias those pointers and own the rest
     Workspace* peers;
@@ -1048,6 +1051,15 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
                               dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
                               b.attc + (size_t)lvl * rows * hv, s));
         }
+        if (w.maps) {                                   // ovc_attention_maps: the same operands once more, the probabilities kept
+            const size_t nq = (size_t)p.S * p.T, kp = ((size_t)N + cmem + 3) & ~(size_t)3;
+            for (int lvl = 0; lvl < lv; ++lvl) {
+                const size_t slot = (size_t)l * lv + lvl;
+                RUN(ovc_cross_attention_maps(b.qc, w.kx + slot * B * N * hk, B, p.S * p.T, N, m->heads, m->d_k, w.enc_mask, N, 0,
+                                             dl.cross_att.m_k, cmem, scale, w.maps + slot * B * m->heads * nq * kp,
+                                             (long)(m->heads * nq * kp), (long)(nq * kp), (long)kp, s));
+            }
+        }
     }
     const float* ffn_in;
     if (m->dec_kind == OVC_DEC_MESHED) {
@@ -1489,6 +1501,7 @@ enum class GraphKind {
     ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
     EnsembleSearch,     // ovc_ensemble_beam_search_graph with more than one member (as Search; every member's contents in the hash)
     TrainDistill,       // ovc_forward_backward_distill, with or without dropout (k = T, out_size = 1; the weight in the hash)
+    ForwardMaps,        // ovc_attention_maps (k = T, out_size = S): ovc_forward's scoring body over B*S*T rows plus the map launches
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -2152,6 +2165,147 @@ extern "C" int ovc_forward(const ovc_model* m, const float* features, const floa
         TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_forward_body(ce, w, B, N, T, want_logp); }));
     }
     return finish_forward(e, w, B, T, logp_out, token_logp_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cross-attention maps of given captions (ovc_attention_maps; the rule is in include/ovc.h).  The scoring forward over B*S*T rows
+// with Workspace::maps set: run_decoder_layer then launches ovc_cross_attention_maps behind every layer's cross-attention.  Launch
+// order: the input kernels (feature projection, seq_inputs_kernel or maps_targets_kernel, tf_inputs_kernel), the body (captured
+// under GraphKind::ForwardMaps), then maps_finish_kernel and, on request, the scoring tail (finish_forward).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// The forward's workspace (scoring form, S sequences per image) and behind it the map and the staged inputs: the decoder inputs /
+// targets / keep flags seq_inputs_kernel derives from ids (its row weights and the zeros it reads as their gradient are not used).
+struct MapsWs {
+    Workspace w;
+    int64_t* tok; int64_t* tgt; uint8_t* keep; float* w_row; float* zeros;
+    int slots, K, Kp;                 // the cross-attention's memory slots, keys per row (N + slots), and K rounded up to 4
+    size_t map_elems, bytes;
+};
+
+// The layers' cross-attention memory slots (one value for all of them), -1 where they disagree.
+int maps_slots(const ovc_model* m) {
+    const bool first = m->dec[0].cross_att.m_k != nullptr;
+    for (int l = 1; l < m->n_dec; ++l)
+        if ((m->dec[l].cross_att.m_k != nullptr) != first) return -1;
+    return first ? m->memory : 0;
+}
+
+bool maps_ok(const ovc_model* m, int B, int N, int S, int T) {
+    if (B < 1 || S < 1 || S > OVC_MAX_BEAM || (long)B * S > (1L << 24) || !forward_ok(m, B * S, N, T)) return false;
+    const int slots = maps_slots(m);
+    if (slots < 0) return false;
+    const size_t kp = ((size_t)N + slots + 3) & ~(size_t)3;
+    const size_t rows = (size_t)m->n_dec * m->n_levels * B * m->heads * S * T;       // <= 8 * 4 * 2^24 * 32
+    return rows * kp < ((size_t)1 << 31);
+}
+
+MapsWs carve_maps(const ovc_model* m, void* base, int B, int N, int S, int T) {
+    MapsWs t{};
+    t.w = carve_forward(m, base, B, N, T, 0, S);
+    Bump a{reinterpret_cast<char*>(base), t.w.bytes};
+    const size_t rows = (size_t)B * S * T;
+    t.slots = maps_slots(m);
+    t.K = N + t.slots;
+    t.Kp = (t.K + 3) & ~3;
+    t.map_elems = (size_t)m->n_dec * m->n_levels * B * m->heads * S * T * t.Kp;
+    t.w.maps = a.take<float>(t.map_elems);
+    t.tok = a.take<int64_t>(rows); t.tgt = a.take<int64_t>(rows);
+    t.keep = a.take<uint8_t>(rows);
+    t.w_row = a.take<float>(rows); t.zeros = a.take<float>(rows);
+    t.bytes = (a.off + 255) & ~(size_t)255;
+    return t;
+}
+
+// tokens form with token_logp_out: the target of row (b, t) is the caption's next token, <pad> behind the last -- the
+// reference's shifted_right_caption_tokens (data_utils/dataset.py:55-68).
+__global__ void maps_targets_kernel(const int64_t* __restrict__ tokens, int rows, int T, int pad, int64_t* __restrict__ tgt) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) tgt[r] = r % T + 1 < T ? tokens[r + 1] : (int64_t)pad;
+}
+
+// The workspace map [L][levels][B][h][S*T][Kp] -> the caller's [B][S][L][levels][h][T][K] (HEADS = false) or [B][S][L][levels][T][K],
+// the mean over heads in ascending order, (((P_0 + P_1) + ...) + P_{h-1}) / h.  keep (the ids form): rows behind a sequence's first
+// <eos> are written as 0 whatever the map holds there.  One thread per output element; total < 2^31 (maps_ok).
+template <bool HEADS>
+__global__ __launch_bounds__(256) void maps_finish_kernel(const float* __restrict__ maps, const uint8_t* __restrict__ keep, int B, int S,
+                                                          int L, int lv, int h, int T, int K, int Kp, unsigned total,
+                                                          float* __restrict__ out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    unsigned r = i;
+    const int j = r % K; r /= K;
+    const int t = r % T; r /= T;
+    int a = 0;
+    if (!HEADS) { a = r % h; r /= h; }
+    const int v = r % lv; r /= lv;
+    const int l = r % L; r /= L;
+    const int s = r % S;
+    const int b = r / S;
+    if (keep && !keep[((size_t)b * S + s) * T + t]) { out[i] = 0.f; return; }
+    const size_t head = (size_t)S * T * Kp;
+    const float* src = maps + ((((size_t)l * lv + v) * B + b) * h + a) * head + ((size_t)s * T + t) * Kp + j;
+    if (!HEADS) { out[i] = src[0]; return; }
+    float acc = src[0];
+    for (int x = 1; x < h; ++x) acc += src[x * head];
+    out[i] = acc / (float)h;
+}
+
+}  // namespace
+
+extern "C" size_t ovc_attention_maps_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    return maps_ok(m, B, N, S, T) ? carve_maps(m, nullptr, B, N, S, T).bytes : 0;
+}
+
+extern "C" int ovc_attention_maps(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S,
+                                  const int64_t* tokens, const int64_t* ids, int T, void* workspace, size_t workspace_bytes,
+                                  float* maps_out, int reduce, float* token_logp_out, int use_graph, ovc_stream stream) {
+    if (!maps_ok(m, B, N, S, T) || !features || !workspace || !maps_out || (tokens != nullptr) == (ids != nullptr) ||
+        (tokens && S != 1) || (reduce != OVC_MAPS_NONE && reduce != OVC_MAPS_HEADS)) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    MapsWs t = carve_maps(m, workspace, B, N, S, T);
+    if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    const int nseq = B * S, rows = nseq * T;
+
+    // the kernels that read the caller's inputs, outside the captured body
+    TRY(run_encoder_inputs(e, t.w, features, boxes, B, N));
+    const int64_t* targets = nullptr;
+    if (ids) {
+        if (hipMemsetAsync(t.zeros, 0, sizeof(float) * rows, e.stream) != hipSuccess) return OVC_ELAUNCH;
+        hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, ids, t.zeros, nseq, T, m->bos_idx, m->eos_idx,
+                           t.tok, t.tgt, t.keep, t.w_row);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        tokens = t.tok; targets = t.tgt;
+    } else if (token_logp_out) {
+        hipLaunchKernelGGL(maps_targets_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, tokens, rows, T, m->pad_idx, t.tgt);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        targets = t.tgt;
+    }
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
+                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    if (!use_graph) {
+        TRY(issue_forward_body(e, t.w, B, N, T, 0, S));
+    } else {
+        const GraphKey key{GraphKind::ForwardMaps, hash_bytes(m, sizeof(*m)), workspace, B, N, T, S};
+        TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_forward_body(ce, t.w, B, N, T, 0, S); }));
+    }
+
+    // the kernels that write the caller's outputs
+    const int L = m->n_dec, lv = m->n_levels, h = m->heads;
+    const uint8_t* keep = ids ? t.keep : nullptr;
+    const unsigned total = (unsigned)((size_t)nseq * L * lv * (reduce == OVC_MAPS_HEADS ? 1 : h) * T * t.K);
+    if (reduce == OVC_MAPS_HEADS)
+        hipLaunchKernelGGL(maps_finish_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, e.stream, t.w.maps, keep, B, S, L, lv, h, T,
+                           t.K, t.Kp, total, maps_out);
+    else
+        hipLaunchKernelGGL(maps_finish_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, e.stream, t.w.maps, keep, B, S, L, lv, h, T,
+                           t.K, t.Kp, total, maps_out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return token_logp_out ? finish_forward(e, t.w, nseq, T, nullptr, token_logp_out) : OVC_OK;
 }
 
 // Test hook: ONE selection step of the fused path on caller-supplied decoder outputs -- the vocabulary product with its

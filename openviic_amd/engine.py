@@ -20,6 +20,7 @@ import threading
 
 import torch
 
+from . import attention_maps as _maps
 from . import constraints as _constraints
 from . import distill as _distill
 from . import dropout as _dropout
@@ -269,7 +270,7 @@ class CaptionEngine:
         # buffers: "search" (every generation and the encoder; its address keys the captured graphs), "forward" (the
         # teacher-forced forward's and the scoring's own, extra = logp wanted: a dev-loss pass between two searches leaves the
         # search's buffer where it is), "train" (ovc_forward_backward's own) and "sequence" (ovc_sequence_backward's own, extra =
-        # sequences per image).  Besides them "arena" (xe_step's gradient arena) and "steps" (early_exit="device": the step count).
+        # sequences per image) and "maps" (ovc_attention_maps' own).  Besides them "arena" (xe_step's gradient arena) and "steps" (early_exit="device": the step count).
         self._buffers = {}
         self.last_steps_device = None
         self._tuned = set()
@@ -1075,3 +1076,42 @@ class CaptionEngine:
                                    None if token_logp is None else token_logp.data_ptr(), 1 if self.use_graph else 0,
                                    native.stream_handle()), "ovc_forward")
         return logp, token_logp
+
+    # -- cross-attention maps ----------------------------------------------------------------------------------------
+    def attention_maps(self, features, boxes, caption_tokens=None, ids=None, reduce="none", return_log_probs=False):
+        """The decoder's cross-attention probabilities of given captions (``ovc_attention_maps``; ``include/ovc.h`` states the
+        rule).  Exactly one of ``caption_tokens`` ``(B, T)`` (decoder inputs, as ``forward`` takes them) and ``ids`` ``(B, T)`` or
+        ``(B, S, T)`` (a search's output: the inputs are ``<bos>, ids[..., :-1]`` and rows behind the first ``<eos>`` are 0).
+        Returns ``(B, S, L, levels, h, T, K)`` for ``reduce="none"`` and ``(B, S, L, levels, T, K)``, the mean over heads, for
+        ``"heads"`` -- without the S axis for 2-D ids and for ``caption_tokens``; ``K`` = regions + the cross-attention's memory
+        slots.  ``return_log_probs``: also the ``(B, S, T)`` log-probabilities of the same pass (of ``ids``, or of each caption
+        token's successor: ``score`` against the shifted-right caption)."""
+        d = self.desc
+        if (caption_tokens is None) == (ids is None):
+            raise native.OvcError("attention_maps takes exactly one of caption_tokens and ids")
+        features, boxes = self._checked_inputs(features, boxes)
+        B, N = features.shape[:2]
+        given, name = (caption_tokens, "caption_tokens") if ids is None else (ids, "ids")
+        S, T, squeeze = _maps.check(self.precision, reduce, given, B, d.max_len, d.vocab, device=self.device, name=name)
+        if ids is None and not squeeze:
+            raise native.OvcError("attention_maps: caption_tokens must be (B={}, T); got {}".format(B, tuple(given.shape)))
+        need = self.lib.ovc_attention_maps_workspace_bytes(ctypes.byref(d), B, N, S, T)
+        if need == 0:
+            raise native.OvcError("unsupported attention-maps configuration (B={}, N={}, S={}, T={}; see "
+                                  "ovc_attention_maps_workspace_bytes)".format(B, N, S, T))
+        given = given.contiguous()
+        self._refresh_derived()
+        ws = self._workspace("maps", need)
+        slots = d.memory if d.dec[0].cross_att.m_k else 0
+        heads = () if reduce == "heads" else (d.heads,)
+        maps = torch.empty((B, S, d.n_dec, d.n_levels) + heads + (T, N + slots), dtype=torch.float32, device=self.device)
+        logp = torch.empty(B, S, T, dtype=torch.float32, device=self.device) if return_log_probs else None
+        check(self.lib.ovc_attention_maps(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N, S,
+                                          given.data_ptr() if ids is None else None, None if ids is None else given.data_ptr(), T,
+                                          ws.data_ptr(), need, maps.data_ptr(), _maps.REDUCE[reduce],
+                                          None if logp is None else logp.data_ptr(), 1 if self.use_graph else 0,
+                                          native.stream_handle()), "ovc_attention_maps")
+        if squeeze:
+            maps = maps.squeeze(1)
+            logp = None if logp is None else logp.squeeze(1)
+        return (maps, logp) if return_log_probs else maps

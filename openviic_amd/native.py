@@ -192,6 +192,13 @@ SIGNATURES = {
     "ovc_forward_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_forward": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                             c_void_p, c_void_p, c_int, c_void_p]),
+    "ovc_cross_attention_maps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_void_p,
+                                         c_int, c_float, c_void_p, c_long, c_long, c_long, c_void_p]),
+    "ovc_debug_cross_attention_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_void_p, c_void_p]),
+    "ovc_attention_maps_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_attention_maps": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "ovc_train_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
     "ovc_forward_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
@@ -290,7 +297,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update",
                  "ovc_ensemble_ok", "ovc_ensemble_workspace_bytes", "ovc_ensemble_beam_search", "ovc_ensemble_beam_search_graph",
                  "ovc_debug_ensemble_update_bytes", "ovc_debug_ensemble_update",
-                 "ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill", "ovc_ensemble_combine")
+                 "ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill", "ovc_ensemble_combine",
+                 "ovc_cross_attention_maps", "ovc_debug_cross_attention_maps", "ovc_attention_maps_workspace_bytes",
+                 "ovc_attention_maps")
 
 _lib = None
 

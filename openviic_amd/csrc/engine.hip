@@ -135,12 +135,13 @@ struct Workspace {
                                                   // and the gated search's step count for the slot table
     float* choice_rows; int32_t* choice_word; int32_t* choice_kept;   // ovc_sample_shaped: the chooser's row-major logits [R][V],
                                                   // the drawn words and the kept counts [R]
-    // teacher-forced forward (ovc_forward; rows = B*T): the self-attention mask [B][T][T], the target words, the logit of each
-    // row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
+    // teacher-forced forward (a ForwardCall; rows = B*S*T): the self-attention mask [B*S][T][T], the target words, the logit of
+    // each row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
-    // ovc_attention_maps: the cross-attention probabilities [L][levels][B][h][S*T][K rounded up to 4] (nullptr in every other call:
-    // run_decoder_layer then issues what it always did)
+    // ForwardCall::keep_maps: the cross-attention probabilities [L][levels][B][h][S*T][K rounded up to 4]
     float* maps;
+    // ForwardCall::staged(): what stage_forward_inputs derives from the caller's sequences -- inputs, targets, keep flags, row weights
+    int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep; float* w_row;
     // ensemble search: the M members' workspaces, [0] this one (nullptr otherwise).  The beam state -- running, alive, hist, lp, anc,
     // tok, padflag, order, the out buffers -- lives once, here; the other members' structs alias those pointers and own the rest
     Workspace* peers;
@@ -272,15 +273,62 @@ Workspace carve(const ovc_model* m, void* base, int B, int N, int k, int return_
 // Vocabularies up to kFusedVocabBlocks 32-word blocks (common.h) take the fused vocabulary tail (the block pieces of the GEMM
 // epilogue), larger ones a row log-softmax -- the search's edge as well (run_decode_step).
 
-// ovc_forward: rows = B*T decoder rows.  With want_logp the transposed logits [V][rows padded to 4] are kept; scoring alone keeps
+// Where a teacher-forced pass takes its decoder inputs from.
+enum class ForwardInput {
+    Tokens,         // the caller's tokens, with the caller's targets or none
+    Ids,            // the caller's ids: inputs <bos>, ids[:-1], targets ids, rows kept up to the first <eos> (seq_inputs_kernel)
+    ShiftedTokens,  // the caller's tokens, their targets the tokens shifted left (maps_targets_kernel)
+};
+
+// One teacher-forced pass, described once.  ovc_forward, ovc_attention_maps and every training call (TrainCall::forward) fill one
+// of these, and the scope (forward_ok), the workspace (carve_forward), the kernels that read the caller's inputs
+// (stage_forward_inputs), the captured body (issue_forward_body), the graph key (forward_graph_key) and everything around them
+// (run_forward_call) are functions of it.
+struct ForwardCall {
+    // the members every call states, first: ForwardCall{B, N, S, T}; the rest is zero unless a form fills it in
+    int B, N, S, T;                                 // S sequences per image, decoder rows (b, s, t)
+    bool keep_logits;                               // the transposed logits stay (log-probabilities, the backward); else scoring only
+    bool keep_maps;                                 // every layer's cross-attention probabilities stay (Workspace::maps)
+    ForwardInput input;
+    bool row_weights;                               // Ids: a row gradient comes with the ids (a sizer states the form, not the pointer)
+    // the caller's sequences: tokens [B*S][T] (Ids: the ids), targets (Tokens: optional), the ids' row gradient (row_weights)
+    const int64_t* tokens; const int64_t* targets; const float* row_grad;
+    int nseq() const { return B * S; } int rows() const { return B * S * T; }
+    // the staged-sequence buffers are carved; a maps call has them whatever its input: its sizer does not know the form
+    bool staged() const { return input != ForwardInput::Tokens || keep_maps; }
+};
+
+bool forward_ok(const ovc_model* m, const ForwardCall& c) {
+    return model_ok(m) && m->precision == 0 && c.B > 0 && c.S > 0 && (long)c.B * c.S <= (1L << 24) && c.N > 0 &&
+           c.N <= OVC_MAX_REGIONS && c.T >= 1 && c.T <= m->max_len && (long)c.B * c.S * c.T <= (1L << 24);
+}
+
+// The decoder layers' cross-attention memory slots (one value for all of them), -1 where they disagree.
+int maps_slots(const ovc_model* m) {
+    const bool first = m->dec[0].cross_att.m_k != nullptr;
+    for (int l = 1; l < m->n_dec; ++l)
+        if ((m->dec[l].cross_att.m_k != nullptr) != first) return -1;
+    return first ? m->memory : 0;
+}
+// a row of Workspace::maps: the N + slots keys rounded up to 4 floats
+size_t maps_ld(const ovc_model* m, int N) { return ((size_t)N + maps_slots(m) + 3) & ~(size_t)3; }
+
+// On top of the pass's scope: a search's S, every layer with or without memory slots, and a map one thread per element can index.
+bool maps_ok(const ovc_model* m, const ForwardCall& c) {
+    if (!forward_ok(m, c) || c.S > OVC_MAX_BEAM || maps_slots(m) < 0) return false;
+    const size_t rows = (size_t)m->n_dec * m->n_levels * c.B * m->heads * c.S * c.T;       // <= 8 * 4 * 2^24 * 32
+    return rows * maps_ld(m, c.N) < ((size_t)1 << 31);
+}
+
+// A ForwardCall's buffers, rows = B*S*T.  With keep_logits the transposed logits [V][rows padded to 4] are kept; scoring alone keeps
 // only the block pieces and one logit per row.  Above kFusedVocabBlocks the row-major logits [rows][V] and, for scoring, the
-// log-probabilities they turn into.  S > 1 (ovc_sequence_backward): S sequences per image, rows = B*S*T laid out (b, s, t).
-Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int want_logp, int S = 1) {
+// log-probabilities they turn into.  Behind them what a form adds: the maps, the staged sequences.
+Workspace carve_forward(const ovc_model* m, void* base, const ForwardCall& c) {
     Workspace w{};
     Bump a{reinterpret_cast<char*>(base), 0};
-    const size_t rows = (size_t)B * S * T, V = m->vocab;
+    const size_t rows = (size_t)c.rows(), T = c.T, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, hv = (size_t)m->heads * m->d_v;
-    carve_encoder(w, a, m, B, N);
+    carve_encoder(w, a, m, c.B, c.N);
     carve_decoder_rows(w, a, m, rows);
     w.kc = a.take<float>(rows * hk); w.vc = a.take<float>(rows * hv);        // one layer's keys / values, not a cache
     w.padflag = a.take<uint8_t>(rows);
@@ -288,13 +336,18 @@ Workspace carve_forward(const ovc_model* m, void* base, int B, int N, int T, int
     w.tgt = a.take<int32_t>(rows);
     const size_t nblk = (V + 31) / 32;
     if (nblk <= (size_t)kFusedVocabBlocks) {
-        w.logits = a.take<float>(want_logp ? V * ((rows + 3) & ~(size_t)3) : 0);
+        w.logits = a.take<float>(c.keep_logits ? V * ((rows + 3) & ~(size_t)3) : 0);
         w.stats = a.take<float>(2 * ((nblk + 1) & ~(size_t)1) * rows);
         w.tgt_logit = a.take<float>(rows);
         w.lse = a.take<float>(2 * rows);
     } else {
         w.logits = a.take<float>(rows * V);
-        w.all_buf = a.take<float>(want_logp ? 0 : rows * V);
+        w.all_buf = a.take<float>(c.keep_logits ? 0 : rows * V);
+    }
+    if (c.keep_maps) w.maps = a.take<float>((size_t)m->n_dec * m->n_levels * c.B * m->heads * c.S * T * maps_ld(m, c.N));
+    if (c.staged()) {
+        w.seq_tok = a.take<int64_t>(rows); w.seq_tgt = a.take<int64_t>(rows); w.seq_keep = a.take<uint8_t>(rows);
+        if (c.row_weights) w.w_row = a.take<float>(rows);
     }
     w.bytes = (a.off + 255) & ~(size_t)255;
     return w;
@@ -452,8 +505,8 @@ __global__ __launch_bounds__(256) void tf_logp_kernel(const float* __restrict__ 
 // ---- sequence backward (ovc_sequence_backward) ---------------------------------------------------
 // One wave per sequence q (rows q*T .. q*T + T-1): e = the first t with ids[q, t] == eos (T-1 if none); the teacher-forced
 // inputs tok = <bos>, ids[q, 0..T-2] and targets tgt = ids[q, :] for tf_inputs_kernel; keep[r] = t <= e, and the dlogit's row weight
-// w_row[r] = -grad[r] where kept, exactly 0 elsewhere whatever grad holds there (beam_search.py:47-52 masks those log-probabilities).
-// Row r of the recompute is the step-t decode of the search's beam q: the mapping a search-side mask key would follow.
+// w_row[r] = -grad[r] where kept, exactly 0 elsewhere whatever grad holds there (beam_search.py:47-52 masks those log-probabilities);
+// without a gradient (grad == nullptr) no w_row is written.  Row r of the recompute is the step-t decode of the search's beam q: the mapping a search-side mask key would follow.
 __global__ __launch_bounds__(256) void seq_inputs_kernel(const int64_t* __restrict__ ids, const float* __restrict__ grad, int nseq,
                                                          int T, int bos, int eos, int64_t* __restrict__ tok, int64_t* __restrict__ tgt,
                                                          uint8_t* __restrict__ keep, float* __restrict__ w_row) {
@@ -470,8 +523,42 @@ __global__ __launch_bounds__(256) void seq_inputs_kernel(const int64_t* __restri
         tok[o + t] = t == 0 ? (int64_t)bos : ids[o + t - 1];
         tgt[o + t] = ids[o + t];
         keep[o + t] = t <= e ? 1 : 0;
-        w_row[o + t] = t <= e ? -grad[o + t] : 0.f;
+        if (grad) w_row[o + t] = t <= e ? -grad[o + t] : 0.f;
     }
+}
+
+// ForwardInput::ShiftedTokens: the target of row (b, t) is the caption's next token, <pad> behind the last -- the reference's
+// shifted_right_caption_tokens (data_utils/dataset.py:55-68).
+__global__ void maps_targets_kernel(const int64_t* __restrict__ tokens, int rows, int T, int pad, int64_t* __restrict__ tgt) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) tgt[r] = r % T + 1 < T ? tokens[r + 1] : (int64_t)pad;
+}
+
+// The workspace map [L][levels][B][h][S*T][Kp] -> the caller's [B][S][L][levels][h][T][K] (HEADS = false) or [B][S][L][levels][T][K],
+// the mean over heads in ascending order, (((P_0 + P_1) + ...) + P_{h-1}) / h.  keep (the ids form): rows behind a sequence's first
+// <eos> are written as 0 whatever the map holds there.  One thread per output element; total < 2^31 (maps_ok).
+template <bool HEADS>
+__global__ __launch_bounds__(256) void maps_finish_kernel(const float* __restrict__ maps, const uint8_t* __restrict__ keep, int B, int S,
+                                                          int L, int lv, int h, int T, int K, int Kp, unsigned total,
+                                                          float* __restrict__ out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    unsigned r = i;
+    const int j = r % K; r /= K;
+    const int t = r % T; r /= T;
+    int a = 0;
+    if (!HEADS) { a = r % h; r /= h; }
+    const int v = r % lv; r /= lv;
+    const int l = r % L; r /= L;
+    const int s = r % S;
+    const int b = r / S;
+    if (keep && !keep[((size_t)b * S + s) * T + t]) { out[i] = 0.f; return; }
+    const size_t head = (size_t)S * T * Kp;
+    const float* src = maps + ((((size_t)l * lv + v) * B + b) * h + a) * head + ((size_t)s * T + t) * Kp + j;
+    if (!HEADS) { out[i] = src[0]; return; }
+    float acc = src[0];
+    for (int x = 1; x < h; ++x) acc += src[x * head];
+    out[i] = acc / (float)h;
 }
 
 // ovc_beam_search_dropout: slots[b, o, t] = the beam slot that held final beam o of image b (the o-th of the sorted output) at step
@@ -747,6 +834,29 @@ int run_encoder_inputs(Engine& e, Workspace& w, const float* features, const flo
     return OVC_OK;
 }
 
+// Everything of a teacher-forced pass that reads the caller's inputs, outside the captured body: the feature projection, the
+// form's own staging of its sequences, then the decoder's inputs.  The only place that launches these.
+int stage_forward_inputs(Engine& e, Workspace& w, const ForwardCall& c, const float* features, const float* boxes) {
+    const ovc_model* m = e.m;
+    const int nseq = c.nseq(), rows = c.rows();
+    TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
+    const int64_t *tokens = c.tokens, *targets = c.targets;
+    if (c.input == ForwardInput::Ids) {
+        hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, c.tokens, c.row_grad, nseq, c.T, m->bos_idx,
+                           m->eos_idx, w.seq_tok, w.seq_tgt, w.seq_keep, w.w_row);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        tokens = w.seq_tok; targets = w.seq_tgt;
+    } else if (c.input == ForwardInput::ShiftedTokens) {
+        hipLaunchKernelGGL(maps_targets_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, c.tokens, rows, c.T, m->pad_idx, w.seq_tgt);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        targets = w.seq_tgt;
+    }
+    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, c.T,
+                       m->word_emb, m->pos_emb, w.x, w.padflag, w.self_mask, w.tgt, rows, m->d_model);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 // The cross-level (CaMo) encoder's tail, encoders.py:234-247, on the three layer outputs o1..o3 in w.cl_out (their padding rows
 // are 0, as every encoder layer leaves them):
 //   o2' = 0.1 MHA(o2; o1, o1) + o2,   o3' = 0.1 MHA(o3; o2', o2') + o3      one shared MHA, MHA(q; k, v) = LN(q + fc_o(att))
@@ -911,7 +1021,7 @@ struct SearchCall {
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
 
-bool dropout_train_ok(const ovc_model* m, int B, int N, int T);     // the dropout scope, defined with the training calls
+bool dropout_train_ok(const ovc_model* m, const ForwardCall& c);    // the dropout scope, defined with the training calls
 
 // The models a form runs: the part of the scope that is checked before the device is touched.
 bool search_model_ok(const ovc_model* m, const SearchCall& c) {
@@ -952,7 +1062,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                             !ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)))
         return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
-    return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, c.B, c.N, m->max_len));
+    return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
 }
 
 // With a plan, or sampling: the seed / step-count slots behind the plain layout.
@@ -999,7 +1109,7 @@ struct DecoderPass {
     float* part;                                    // the AddNorms' K-split partial products (Workspace::part); nullptr: whole products
     bool name_sites;                                // the dropout sites dec_site(l, j) are named (else -1: every launch the plain one)
     int t, width, R; const int32_t* anc;            // Step: step t of B*width rows in caches of R slots per position, its ancestor table
-    int S, T;                                       // Sequence: S sequences of T positions per image
+    int S, T; bool keep_maps;                       // Sequence: S sequences of T positions per image; ForwardCall::keep_maps
     int site(int l, int j) const { return name_sites ? dec_site(l, j) : -1; }
 };
 
@@ -1051,7 +1161,7 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
                               dl.cross_att.m_k, dl.cross_att.m_v, cmem, scale, sqrtf((float)(cmem > 0 ? cmem : 1)),
                               b.attc + (size_t)lvl * rows * hv, s));
         }
-        if (w.maps) {                                   // ovc_attention_maps: the same operands once more, the probabilities kept
+        if (p.keep_maps) {                              // ovc_attention_maps: the same operands once more, the probabilities kept
             const size_t nq = (size_t)p.S * p.T, kp = ((size_t)N + cmem + 3) & ~(size_t)3;
             for (int lvl = 0; lvl < lv; ++lvl) {
                 const size_t slot = (size_t)l * lv + lvl;
@@ -1302,18 +1412,18 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
 // projected encoder keys / values of every level (nq = T, the encoder mask), the meshed level gates or the AddNorm, AoA gates where
 // the model has them, the FFN with <pad> query rows cleared -- then the vocabulary product.  Every product is of the one-chain
 // class (M = B*T rows, like the encoder's), so the decoder outputs are those of the operator path (ovc_linear) bit for bit.
-// Vocabulary: up to kFusedVocabBlocks blocks the transposed product of the search with its block pieces (want_logp: the logits are
-// stored; scoring: gemm_f32_mfma_score keeps only each row's target logit); beyond, the row-major logits.
-// S > 1 (ovc_sequence_backward): S sequences per image, rows (b, s, t).  The self-attention runs over the B*S sequences, the
-// cross-attention of image b over its S*T rows at once (nq = S*T against the image's N keys, the per-image mask): the encoder and
-// the cross keys / values are computed once per image.  S = 1 is the call above, launch for launch.
-int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_logp, int S = 1) {
+// Vocabulary: up to kFusedVocabBlocks blocks the transposed product of the search with its block pieces (keep_logits: the logits
+// are stored; scoring: gemm_f32_mfma_score keeps only each row's target logit); beyond, the row-major logits.
+// S > 1: S sequences per image, rows (b, s, t).  The self-attention runs over the B*S sequences, the cross-attention of image b
+// over its S*T rows at once (nq = S*T against the image's N keys, the per-image mask): the encoder and the cross keys / values are
+// computed once per image.  S = 1 is the call above, launch for launch.
+int run_forward_decoder(Engine& e, Workspace& w, const ForwardCall& c) {
     const ovc_model* m = e.m;
-    const int d = m->d_model, rows = B * S * T;
+    const int d = m->d_model, rows = c.rows();
     e.gemm_class = 2;
     e.kchains = 1;
-    DecoderPass pass{DecoderPass::Sequence, rows, B, N, w.padflag, nullptr, true};
-    pass.S = S; pass.T = T;
+    DecoderPass pass{DecoderPass::Sequence, rows, c.B, c.N, w.padflag, nullptr, true};
+    pass.S = c.S; pass.T = c.T; pass.keep_maps = c.keep_maps;
     // training: the layer's own tape slots (see run_encoder_layers); the meshed branch never runs with a tape
     const DecTape scratch = scratch_dec(w, w.kc, w.vc);
     const float* x = w.x;
@@ -1326,9 +1436,9 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
     // ---- vocabulary product ----------------------------------------------------------------------
     e.gemm_class = 3;
     if ((m->vocab + 31) / 32 <= kFusedVocabBlocks) {
-        GemmArgs g = transposed_vocab_product(m, x, rows, want_logp ? w.logits : nullptr, w.stats);
+        GemmArgs g = transposed_vocab_product(m, x, rows, c.keep_logits ? w.logits : nullptr, w.stats);
         GemmLaunchOpts scoring{};
-        if (!want_logp) { scoring.tgt = w.tgt; scoring.tgt_logit = w.tgt_logit; }
+        if (!c.keep_logits) { scoring.tgt = w.tgt; scoring.tgt_logit = w.tgt_logit; }
         return e.gemm(g, scoring);
     }
     GemmArgs g{};
@@ -1338,10 +1448,10 @@ int run_forward_decoder(Engine& e, Workspace& w, int B, int N, int T, int want_l
 }
 
 // After the decoder: the kernels that write the caller's outputs (kept out of the captured graph, like the input kernels).
-int finish_forward(Engine& e, Workspace& w, int B, int T, float* logp_out, float* token_logp_out) {
+int finish_forward(Engine& e, Workspace& w, const ForwardCall& c, float* logp_out, float* token_logp_out) {
     const ovc_model* m = e.m;
     hipStream_t s = e.stream;
-    const int rows = B * T, V = m->vocab, nblk = (V + 31) / 32;
+    const int rows = c.rows(), V = m->vocab, nblk = (V + 31) / 32;
     if (nblk <= kFusedVocabBlocks) {
         const long ldt = (rows + 3) & ~3;
         hipLaunchKernelGGL(tf_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.stats, nblk, (nblk + 1) & ~1, rows, w.tgt,
@@ -1363,15 +1473,10 @@ int finish_forward(Engine& e, Workspace& w, int B, int T, float* logp_out, float
     return OVC_OK;
 }
 
-int issue_forward_body(Engine& e, Workspace& w, int B, int N, int T, int want_logp, int S = 1) {
-    TRY(run_encoder_layers(e, w, B, N));
-    TRY(project_cross_kv(e, w, B, N));
-    return run_forward_decoder(e, w, B, N, T, want_logp, S);
-}
-
-bool forward_ok(const ovc_model* m, int B, int N, int T) {
-    return model_ok(m) && m->precision == 0 && B > 0 && N > 0 && N <= OVC_MAX_REGIONS && T >= 1 && T <= m->max_len &&
-           (long)B * T <= (1L << 24);
+int issue_forward_body(Engine& e, Workspace& w, const ForwardCall& c) {
+    TRY(run_encoder_layers(e, w, c.B, c.N));
+    TRY(project_cross_kv(e, w, c.B, c.N));
+    return run_forward_decoder(e, w, c);
 }
 
 // What every search issues behind its input kernels and before step 0.  The early-exit forms clear this search's live-beam counts
@@ -1491,7 +1596,7 @@ namespace {
 // call with every p == 0 is the plain call and shares the plain entry.
 enum class GraphKind {
     Search,             // ovc_beam_search_graph and the per-step graphs of ovc_beam_search_early (k = beam, out_size)
-    Forward,            // ovc_forward (k = T, out_size = want_logp)
+    Forward,            // a ForwardCall without maps, ovc_forward (forward_graph_key: k = T, out_size = keep_logits)
     GatedSearch,        // ovc_beam_search_gated (k = beam, out_size)
     Train,              // ovc_forward_backward, with or without dropout (k = T, out_size = 1)
     SequenceBackward,   // ovc_sequence_backward, with or without dropout (k = T, out_size = S)
@@ -1501,7 +1606,8 @@ enum class GraphKind {
     ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
     EnsembleSearch,     // ovc_ensemble_beam_search_graph with more than one member (as Search; every member's contents in the hash)
     TrainDistill,       // ovc_forward_backward_distill, with or without dropout (k = T, out_size = 1; the weight in the hash)
-    ForwardMaps,        // ovc_attention_maps (k = T, out_size = S): ovc_forward's scoring body over B*S*T rows plus the map launches
+    ForwardMaps,        // a ForwardCall with maps, ovc_attention_maps (forward_graph_key: k = T, out_size = S): the scoring body
+                        // over B*S*T rows plus the map launches
 };
 struct GraphKey {
     GraphKind kind; uint64_t model_hash; const void* ws; int B, N, k, out_size;
@@ -1670,6 +1776,13 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
                         c.k, c.out_size};
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
+}
+
+// The graph key of run_forward_call, built here and nowhere else (the rule: GraphKind).  The input form is not in it: the kernels
+// that differ by form run outside the captured body.  Without maps S is 1 (ovc_forward).
+GraphKey forward_graph_key(const ovc_model* m, const void* workspace, const ForwardCall& c) {
+    if (c.keep_maps) return GraphKey{GraphKind::ForwardMaps, hash_bytes(m, sizeof(*m)), workspace, c.B, c.N, c.T, c.S};
+    return GraphKey{GraphKind::Forward, hash_bytes(m, sizeof(*m)), workspace, c.B, c.N, c.T, c.keep_logits};
 }
 }  // namespace
 
@@ -2130,182 +2243,74 @@ extern "C" int ovc_sample_shaped_graph(const ovc_model* m, const float* features
 }
 
 // ---------------------------------------------------------------------------------------------
-// Teacher-forced forward / caption scoring (decoders.py:95-123; the dev-loss loop of vi_trainer.py:56-76).  Launch order: the
-// input kernels (feature projection, box relations, tf_inputs_kernel: they read the caller's features / boxes / tokens / targets),
-// then the body -- encoder layers, cross keys / values, the decoder over B*T rows, the vocabulary product -- captured as a hipGraph
-// on the second call of a (model, workspace, B, N, T, want_logp) when use_graph is set, then the output kernels (tf_lse_kernel,
-// tf_logp_kernel or the row log-softmax + gather), which write the caller's buffers.
+// The teacher-forced pass (decoders.py:95-123): one host path for every ForwardCall that is not a training call.  Launch order:
+// the input kernels (stage_forward_inputs: they read the caller's features / boxes / tokens / targets / ids), then the body
+// (issue_forward_body: encoder layers, cross keys / values, the decoder over B*S*T rows with the map launches where they are kept,
+// the vocabulary product) -- captured as a hipGraph on the second call of its key (forward_graph_key) when use_graph is set -- then
+// `finish`, the entry point's own output kernels, which write the caller's buffers.
 // ---------------------------------------------------------------------------------------------
+namespace {
+template <typename Finish>
+int run_forward_call(const ovc_model* m, const ForwardCall& c, const float* features, const float* boxes, void* workspace,
+                     size_t workspace_bytes, int use_graph, ovc_stream stream, Finish finish) {
+    if (!forward_ok(m, c) || !features || !c.tokens || !workspace) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
+    Workspace w = carve_forward(m, workspace, c);
+    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
+    Engine e{m, ovc_hip_stream(stream), 0};
+    TRY(stage_forward_inputs(e, w, c, features, boxes));
+    auto body = [&](Engine& ce) { return issue_forward_body(ce, w, c); };
+    if (!use_graph) TRY(body(e));
+    else TRY(replay_or_issue(forward_graph_key(m, workspace, c), e.stream, m, body));
+    return finish(e, w);
+}
+}  // namespace
+
+// Teacher-forced forward / caption scoring (the dev-loss loop of vi_trainer.py:56-76): run_forward_call on the caller's tokens and
+// targets, the logits kept where the log-probabilities are wanted, then finish_forward.
 extern "C" size_t ovc_forward_workspace_bytes(const ovc_model* m, int B, int N, int T, int want_logp) {
-    if (!forward_ok(m, B, N, T)) return 0;
-    return carve_forward(m, nullptr, B, N, T, want_logp ? 1 : 0).bytes;
+    ForwardCall c{B, N, 1, T}; c.keep_logits = want_logp != 0;
+    return forward_ok(m, c) ? carve_forward(m, nullptr, c).bytes : 0;
 }
 
 extern "C" int ovc_forward(const ovc_model* m, const float* features, const float* boxes, int B, int N, const int64_t* tokens,
                            const int64_t* targets, int T, void* workspace, size_t workspace_bytes, float* logp_out,
                            float* token_logp_out, int use_graph, ovc_stream stream) {
-    if (!forward_ok(m, B, N, T) || !features || !tokens || !workspace || (!logp_out && !token_logp_out) ||
-        (token_logp_out && !targets)) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    const int want_logp = logp_out != nullptr;
-    Workspace w = carve_forward(m, workspace, B, N, T, want_logp);
-    if (w.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
-    const int rows = B * T;
-
-    TRY(run_encoder_inputs(e, w, features, boxes, B, N));
-    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
-                       m->word_emb, m->pos_emb, w.x, w.padflag, w.self_mask, w.tgt, rows, m->d_model);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    if (!use_graph) {
-        TRY(issue_forward_body(e, w, B, N, T, want_logp));
-    } else {
-        const GraphKey key{GraphKind::Forward, hash_bytes(m, sizeof(*m)), workspace, B, N, T, want_logp};
-        TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_forward_body(ce, w, B, N, T, want_logp); }));
-    }
-    return finish_forward(e, w, B, T, logp_out, token_logp_out);
+    if ((!logp_out && !token_logp_out) || (token_logp_out && !targets)) return OVC_EINVAL;
+    ForwardCall c{B, N, 1, T}; c.keep_logits = logp_out != nullptr; c.tokens = tokens; c.targets = targets;
+    return run_forward_call(m, c, features, boxes, workspace, workspace_bytes, use_graph, stream,
+                            [&](Engine& e, Workspace& w) { return finish_forward(e, w, c, logp_out, token_logp_out); });
 }
 
 // ---------------------------------------------------------------------------------------------
-// Cross-attention maps of given captions (ovc_attention_maps; the rule is in include/ovc.h).  The scoring forward over B*S*T rows
-// with Workspace::maps set: run_decoder_layer then launches ovc_cross_attention_maps behind every layer's cross-attention.  Launch
-// order: the input kernels (feature projection, seq_inputs_kernel or maps_targets_kernel, tf_inputs_kernel), the body (captured
-// under GraphKind::ForwardMaps), then maps_finish_kernel and, on request, the scoring tail (finish_forward).
+// Cross-attention maps of given captions (ovc_attention_maps; the rule is in include/ovc.h): run_forward_call on the scoring pass
+// over B*S*T rows with keep_maps (run_decoder_layer then launches ovc_cross_attention_maps behind every layer's cross-attention), on
+// the caller's ids or tokens; then maps_finish_kernel and, on request, the scoring tail (finish_forward) against the shifted tokens.
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-// The forward's workspace (scoring form, S sequences per image) and behind it the map and the staged inputs: the decoder inputs /
-// targets / keep flags seq_inputs_kernel derives from ids (its row weights and the zeros it reads as their gradient are not used).
-struct MapsWs {
-    Workspace w;
-    int64_t* tok; int64_t* tgt; uint8_t* keep; float* w_row; float* zeros;
-    int slots, K, Kp;                 // the cross-attention's memory slots, keys per row (N + slots), and K rounded up to 4
-    size_t map_elems, bytes;
-};
-
-// The layers' cross-attention memory slots (one value for all of them), -1 where they disagree.
-int maps_slots(const ovc_model* m) {
-    const bool first = m->dec[0].cross_att.m_k != nullptr;
-    for (int l = 1; l < m->n_dec; ++l)
-        if ((m->dec[l].cross_att.m_k != nullptr) != first) return -1;
-    return first ? m->memory : 0;
-}
-
-bool maps_ok(const ovc_model* m, int B, int N, int S, int T) {
-    if (B < 1 || S < 1 || S > OVC_MAX_BEAM || (long)B * S > (1L << 24) || !forward_ok(m, B * S, N, T)) return false;
-    const int slots = maps_slots(m);
-    if (slots < 0) return false;
-    const size_t kp = ((size_t)N + slots + 3) & ~(size_t)3;
-    const size_t rows = (size_t)m->n_dec * m->n_levels * B * m->heads * S * T;       // <= 8 * 4 * 2^24 * 32
-    return rows * kp < ((size_t)1 << 31);
-}
-
-MapsWs carve_maps(const ovc_model* m, void* base, int B, int N, int S, int T) {
-    MapsWs t{};
-    t.w = carve_forward(m, base, B, N, T, 0, S);
-    Bump a{reinterpret_cast<char*>(base), t.w.bytes};
-    const size_t rows = (size_t)B * S * T;
-    t.slots = maps_slots(m);
-    t.K = N + t.slots;
-    t.Kp = (t.K + 3) & ~3;
-    t.map_elems = (size_t)m->n_dec * m->n_levels * B * m->heads * S * T * t.Kp;
-    t.w.maps = a.take<float>(t.map_elems);
-    t.tok = a.take<int64_t>(rows); t.tgt = a.take<int64_t>(rows);
-    t.keep = a.take<uint8_t>(rows);
-    t.w_row = a.take<float>(rows); t.zeros = a.take<float>(rows);
-    t.bytes = (a.off + 255) & ~(size_t)255;
-    return t;
-}
-
-// tokens form with token_logp_out: the target of row (b, t) is the caption's next token, <pad> behind the last -- the
-// reference's shifted_right_caption_tokens (data_utils/dataset.py:55-68).
-__global__ void maps_targets_kernel(const int64_t* __restrict__ tokens, int rows, int T, int pad, int64_t* __restrict__ tgt) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < rows) tgt[r] = r % T + 1 < T ? tokens[r + 1] : (int64_t)pad;
-}
-
-// The workspace map [L][levels][B][h][S*T][Kp] -> the caller's [B][S][L][levels][h][T][K] (HEADS = false) or [B][S][L][levels][T][K],
-// the mean over heads in ascending order, (((P_0 + P_1) + ...) + P_{h-1}) / h.  keep (the ids form): rows behind a sequence's first
-// <eos> are written as 0 whatever the map holds there.  One thread per output element; total < 2^31 (maps_ok).
-template <bool HEADS>
-__global__ __launch_bounds__(256) void maps_finish_kernel(const float* __restrict__ maps, const uint8_t* __restrict__ keep, int B, int S,
-                                                          int L, int lv, int h, int T, int K, int Kp, unsigned total,
-                                                          float* __restrict__ out) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= total) return;
-    unsigned r = i;
-    const int j = r % K; r /= K;
-    const int t = r % T; r /= T;
-    int a = 0;
-    if (!HEADS) { a = r % h; r /= h; }
-    const int v = r % lv; r /= lv;
-    const int l = r % L; r /= L;
-    const int s = r % S;
-    const int b = r / S;
-    if (keep && !keep[((size_t)b * S + s) * T + t]) { out[i] = 0.f; return; }
-    const size_t head = (size_t)S * T * Kp;
-    const float* src = maps + ((((size_t)l * lv + v) * B + b) * h + a) * head + ((size_t)s * T + t) * Kp + j;
-    if (!HEADS) { out[i] = src[0]; return; }
-    float acc = src[0];
-    for (int x = 1; x < h; ++x) acc += src[x * head];
-    out[i] = acc / (float)h;
-}
-
-}  // namespace
-
 extern "C" size_t ovc_attention_maps_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    return maps_ok(m, B, N, S, T) ? carve_maps(m, nullptr, B, N, S, T).bytes : 0;
+    ForwardCall c{B, N, S, T}; c.keep_maps = true;          // the layout is the same for every input form (ForwardCall::staged)
+    return maps_ok(m, c) ? carve_forward(m, nullptr, c).bytes : 0;
 }
 
 extern "C" int ovc_attention_maps(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S,
                                   const int64_t* tokens, const int64_t* ids, int T, void* workspace, size_t workspace_bytes,
                                   float* maps_out, int reduce, float* token_logp_out, int use_graph, ovc_stream stream) {
-    if (!maps_ok(m, B, N, S, T) || !features || !workspace || !maps_out || (tokens != nullptr) == (ids != nullptr) ||
-        (tokens && S != 1) || (reduce != OVC_MAPS_NONE && reduce != OVC_MAPS_HEADS)) return OVC_EINVAL;
-    TRY(ovc_device_guard());
-    if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
-    MapsWs t = carve_maps(m, workspace, B, N, S, T);
-    if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
-    Engine e{m, ovc_hip_stream(stream), 0};
-    const int nseq = B * S, rows = nseq * T;
-
-    // the kernels that read the caller's inputs, outside the captured body
-    TRY(run_encoder_inputs(e, t.w, features, boxes, B, N));
-    const int64_t* targets = nullptr;
-    if (ids) {
-        if (hipMemsetAsync(t.zeros, 0, sizeof(float) * rows, e.stream) != hipSuccess) return OVC_ELAUNCH;
-        hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, ids, t.zeros, nseq, T, m->bos_idx, m->eos_idx,
-                           t.tok, t.tgt, t.keep, t.w_row);
+    ForwardCall c{B, N, S, T}; c.keep_maps = true;
+    if (!maps_ok(m, c) || !maps_out || (tokens != nullptr) == (ids != nullptr) || (tokens && S != 1) ||
+        (reduce != OVC_MAPS_NONE && reduce != OVC_MAPS_HEADS)) return OVC_EINVAL;
+    c.input = ids ? ForwardInput::Ids : token_logp_out ? ForwardInput::ShiftedTokens : ForwardInput::Tokens;
+    c.tokens = ids ? ids : tokens;
+    return run_forward_call(m, c, features, boxes, workspace, workspace_bytes, use_graph, stream, [&](Engine& e, Workspace& w) {
+        const int L = m->n_dec, lv = m->n_levels, h = m->heads, K = N + maps_slots(m), Kp = (int)maps_ld(m, N);
+        const uint8_t* keep = ids ? w.seq_keep : nullptr;
+        const unsigned total = (unsigned)((size_t)c.nseq() * L * lv * (reduce == OVC_MAPS_HEADS ? 1 : h) * T * K);
+        auto* finish = reduce == OVC_MAPS_HEADS ? maps_finish_kernel<true> : maps_finish_kernel<false>;
+        hipLaunchKernelGGL(finish, dim3((total + 255) / 256), dim3(256), 0, e.stream, w.maps, keep, B, S, L, lv, h, T, K, Kp, total,
+                           maps_out);
         OVC_RETURN_IF_LAUNCH_FAILED();
-        tokens = t.tok; targets = t.tgt;
-    } else if (token_logp_out) {
-        hipLaunchKernelGGL(maps_targets_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, tokens, rows, T, m->pad_idx, t.tgt);
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        targets = t.tgt;
-    }
-    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
-                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    if (!use_graph) {
-        TRY(issue_forward_body(e, t.w, B, N, T, 0, S));
-    } else {
-        const GraphKey key{GraphKind::ForwardMaps, hash_bytes(m, sizeof(*m)), workspace, B, N, T, S};
-        TRY(replay_or_issue(key, e.stream, m, [&](Engine& ce) { return issue_forward_body(ce, t.w, B, N, T, 0, S); }));
-    }
-
-    // the kernels that write the caller's outputs
-    const int L = m->n_dec, lv = m->n_levels, h = m->heads;
-    const uint8_t* keep = ids ? t.keep : nullptr;
-    const unsigned total = (unsigned)((size_t)nseq * L * lv * (reduce == OVC_MAPS_HEADS ? 1 : h) * T * t.K);
-    if (reduce == OVC_MAPS_HEADS)
-        hipLaunchKernelGGL(maps_finish_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, e.stream, t.w.maps, keep, B, S, L, lv, h, T,
-                           t.K, t.Kp, total, maps_out);
-    else
-        hipLaunchKernelGGL(maps_finish_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, e.stream, t.w.maps, keep, B, S, L, lv, h, T,
-                           t.K, t.Kp, total, maps_out);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    return token_logp_out ? finish_forward(e, t.w, nseq, T, nullptr, token_logp_out) : OVC_OK;
+        return token_logp_out ? finish_forward(e, w, c, nullptr, token_logp_out) : OVC_OK;
+    });
 }
 
 // Test hook: ONE selection step of the fused path on caller-supplied decoder outputs -- the vocabulary product with its
@@ -2414,7 +2419,7 @@ extern "C" const char* ovc_profile_kernel_name(int tiling) { return ovc_gemm_til
 // ---------------------------------------------------------------------------------------------
 // training: ovc_forward_backward
 // ---------------------------------------------------------------------------------------------
-// The forward of ovc_forward (want_logp: the transposed logits are kept) with every layer's intermediates on the tape, then one
+// The forward of ovc_forward (keep_logits: the transposed logits are kept) with every layer's intermediates on the tape, then one
 // reverse sweep -- vocabulary, decoder layers L-1 .. 0, encoder layers, the two embeddings.  Weight gradients dW = dY^T X are
 // the engine's NT GEMM on transposed operands (dY^T and X^T staged with K = rows padded to 4, zeros in the padding), input
 // gradients dX = dY W the NT GEMM on the transposed weight; both in the one-chain K-order class, so one fmaf chain over the
@@ -2424,11 +2429,11 @@ extern "C" const char* ovc_profile_kernel_name(int tiling) { return ovc_gemm_til
 namespace {
 
 struct TrainWs {
-    Workspace w;                  // the forward's buffers (carve_forward, want_logp), tape pointer set by the caller
+    Workspace w;                  // the forward's buffers (carve_forward of TrainCall::forward), tape pointer set by the caller
     Tape tape;
     float* feat_t;                // [d_feat][BN padded to 4] the caller's features, transposed (staged outside the captured body)
     int32_t* tok;                 // [rows] caption tokens, clamped
-    float* w_row; float* loss;    // [rows] loss weight of every row, the loss
+    float* w_row; float* loss;    // [rows] loss weight of every row (RowWeights: the forward's staged Workspace::w_row), the loss
     float* dl_t; float* dl;       // dlogit [V][ldt] and [rows][ldv]
     float* fc_t;                  // fc^T [d][ldv]
     float* wt;                    // a transposed weight (or stacked q|k|v, k|v), [max(d_ff, 3 h d_k)][d]
@@ -2448,9 +2453,6 @@ struct TrainWs {
     // dropout (TrainCall::plan only; ovc_train_dropout_workspace_bytes)
     float* dproj;                 // [Rmax][d] gradient of a masked projection: keep * s * dy
     int64_t* seed;                // the step's seed, copied in outside the captured body
-    // sequences (LossHead::RowWeights only; ovc_train_beams_workspace_bytes): the teacher-forced inputs and targets built
-    // from the caller's ids, and which rows lie up to their sequence's first <eos> -- written outside the captured body
-    int64_t* seq_tok; int64_t* seq_tgt; uint8_t* seq_keep;
     int32_t* maskrow;             // [rows] sequences with dropout: the mask row of every decoder row (seq_maskrow_kernel)
     // label smoothing (LossHead::SmoothedXent only; ovc_train_smoothed_workspace_bytes): the rows' sums of
     // log-probabilities [rows] and their slice partials [ceil(V / 64)][rows padded to 4]
@@ -2496,12 +2498,18 @@ struct TrainCall {
     DropPlan* plan; const int64_t* seed; uint64_t drop_hash;
     int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
     bool seq() const { return head == LossHead::RowWeights; }
+    // The call's teacher-forced pass: the logits kept for the backward; RowWeights: on the caller's ids and their row gradient.
+    ForwardCall forward() const {
+        ForwardCall f{B, N, S, T}; f.keep_logits = true;
+        if (seq()) { f.input = ForwardInput::Ids; f.row_weights = true; }
+        return f;
+    }
 };
 
 TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     const int B = c.B, N = c.N, S = c.S, T = c.T;
     TrainWs t{};
-    t.w = carve_forward(m, base, B, N, T, 1, S);
+    t.w = carve_forward(m, base, c.forward());
     Bump a{reinterpret_cast<char*>(base), t.w.bytes};
     const size_t rows = (size_t)B * S * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
@@ -2533,7 +2541,7 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d});
     t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
     t.tok = a.take<int32_t>(rows);
-    t.w_row = a.take<float>(rows); t.loss = a.take<float>(4);
+    t.w_row = c.seq() ? t.w.w_row : a.take<float>(rows); t.loss = a.take<float>(4);
     t.dl_t = a.take<float>(V * pad4(rows)); t.dl = a.take<float>(rows * pad4(V));
     t.fc_t = a.take<float>(d * pad4(V));
     t.wt = a.take<float>(wide * d);
@@ -2557,10 +2565,7 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         t.dproj = a.take<float>(R * d);
         t.seed = a.take<int64_t>(2);
     }
-    if (c.seq()) {
-        t.seq_tok = a.take<int64_t>(rows); t.seq_tgt = a.take<int64_t>(rows); t.seq_keep = a.take<uint8_t>(rows);
-        if (c.plan) t.maskrow = a.take<int32_t>(rows);
-    }
+    if (c.seq() && c.plan) t.maskrow = a.take<int32_t>(rows);
     if (c.head == LossHead::SmoothedXent) {
         t.lp_sum = a.take<float>(rows);
         t.lp_part = a.take<float>(ovc_bw_smoothed_part_floats((int)rows, m->vocab));
@@ -2588,8 +2593,8 @@ bool ffn_grad_ok(const ovc_ffn& f, const ovc_ffn& g) { return lin_grad_ok(f.fc1,
 // -- in the PLAIN encoder's layers also with memory slots (memory > 0 and m_k / m_v in every layer: the augmented-memory
 // transformer) -- fp32, and vocabularies that take the fused vocabulary tail (its transposed logits and block pieces are what the
 // cross-entropy backward reads).
-bool train_ok(const ovc_model* m, int B, int N, int T) {
-    if (!forward_ok(m, B, N, T)) return false;
+bool train_ok(const ovc_model* m, const ForwardCall& c) {
+    if (!forward_ok(m, c)) return false;
     if (m->enc_kind != OVC_ENC_PLAIN && m->enc_kind != OVC_ENC_CROSS_LEVEL) return false;
     if (m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1) return false;
     if (m->memory != 0 && m->enc_kind != OVC_ENC_PLAIN) return false;
@@ -2598,7 +2603,7 @@ bool train_ok(const ovc_model* m, int B, int N, int T) {
     for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
     if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
     // the dlogit products address their operands with 32-bit buffer descriptors (ovc_gemm_launch)
-    const long kMax = 0x7fffffffL - (1L << 20), rows = (long)B * T;
+    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
     return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
 }
 
@@ -2618,14 +2623,10 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
 
 // Dropout training (ovc_forward_backward_dropout) covers the plain encoder only: the cross-level tail applies its one nn.Dropout
 // twice and has no site of its own.
-bool dropout_train_ok(const ovc_model* m, int B, int N, int T) { return train_ok(m, B, N, T) && m->enc_kind == OVC_ENC_PLAIN; }
+bool dropout_train_ok(const ovc_model* m, const ForwardCall& c) { return train_ok(m, c) && m->enc_kind == OVC_ENC_PLAIN; }
 
-// The scope of a training call, for its sizer and its entry point alike: train_ok over the B*S sequences, under dropout the
-// dropout scope.
-bool call_ok(const ovc_model* m, const TrainCall& c) {
-    if (c.S < 1 || c.B < 1 || (long)c.B * c.S > (1L << 24)) return false;
-    return c.plan ? dropout_train_ok(m, c.B * c.S, c.N, c.T) : train_ok(m, c.B * c.S, c.N, c.T);
-}
+// The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope.
+bool call_ok(const ovc_model* m, const TrainCall& c) { return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward()); }
 
 // A sequence call with dropout recomputes under the masks of the search that made its sequences: that search's limits
 // (ovc_beam_search_dropout), full-length sequences and its slot table.  After call_ok: m has been checked.
@@ -2872,7 +2873,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
     hipStream_t s = e.stream;
     const int d = m->d_model, V = m->vocab, rows = B * S * T, BN = B * N, L = m->n_dec;
     const int nblk = (V + 31) / 32, ldt = (int)pad4(rows), ldv = (int)pad4(V);
-    TRY(issue_forward_body(e, w, B, N, T, 1, S));
+    TRY(issue_forward_body(e, w, c.forward()));
     if (!e.dry) {
         hipLaunchKernelGGL(tf_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.stats, nblk, (nblk + 1) & ~1, rows, w.tgt,
                            m->pad_idx, nullptr, nullptr, 0L, w.lse, nullptr);
@@ -2994,15 +2995,13 @@ int bind_train_drop(Engine& e, TrainWs& t, const TrainCall& c) {
     return OVC_OK;
 }
 
-// The staging that reads the caller's (or seq_inputs_kernel's) tokens / targets and features, outside the captured body: the
-// decoder's inputs, the token rows and the transposed features of the embedding gradients.
-int stage_train_inputs(Engine& e, TrainWs& t, const float* features, const int64_t* tokens, const int64_t* targets, int rows, int T,
-                       int BN) {
+// The staging that reads the caller's inputs, outside the captured body: the pass's own (the plain encoder reads no boxes), then
+// the token rows -- the caller's, or the ones staged from its ids -- and the transposed features of the embedding gradients.
+int stage_train_inputs(Engine& e, TrainWs& t, const ForwardCall& f, const float* features) {
     const ovc_model* m = e.m;
-    hipLaunchKernelGGL(tf_inputs_kernel, dim3((rows + 3) / 4), dim3(256), 0, e.stream, tokens, targets, m->vocab, m->pad_idx, T,
-                       m->word_emb, m->pos_emb, t.w.x, t.w.padflag, t.w.self_mask, t.w.tgt, rows, m->d_model);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    TRY(ovc_bw_tokens(tokens, rows, m->vocab, t.tok, e.stream));
+    const int BN = f.B * f.N;
+    TRY(stage_forward_inputs(e, t.w, f, features, nullptr));
+    TRY(ovc_bw_tokens(f.input == ForwardInput::Ids ? t.w.seq_tok : f.tokens, f.rows(), m->vocab, t.tok, e.stream));
     return ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream);
 }
 
@@ -3021,7 +3020,7 @@ GraphKey train_graph_key(const ovc_model* m, const ovc_model* grads, const void*
 // Every training entry point.  tokens / targets: the caller's caption and its targets, loss_out the loss; for RowWeights tokens are
 // the caller's ids [B][S][T], grad_logp their row weights, targets is unused and logp_out (optional) takes the recomputed
 // log-probabilities.  Launch order: the seed slot and, for sequences under dropout, the mask-row table; the kernels that read the
-// caller's inputs (feature projection, seq_inputs_kernel, tf_inputs_kernel, token and feature staging); the body -- captured on
+// caller's inputs (stage_forward_inputs of the call's pass, then token and feature staging); the body -- captured on
 // the second call of its key when use_graph is set; the loss copy or seq_logp_kernel.  Only the body is ever captured.
 int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& c, const float* features, const int64_t* tokens,
                    const int64_t* targets, const float* grad_logp, void* workspace, size_t workspace_bytes, float* loss_out,
@@ -3034,7 +3033,7 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
     t.w.tape = &t.tape;
     if (t.bytes > workspace_bytes) return OVC_EWORKSPACE;
     Engine e{m, ovc_hip_stream(stream), 0};
-    const int nseq = c.B * c.S, rows = nseq * c.T;
+    const int rows = c.B * c.S * c.T;
     TRY(bind_train_drop(e, t, c));
     if (c.head == LossHead::SoftTargets) {
         // the teacher goes into its slot here, outside the captured body: a replayed graph reads this call's distribution
@@ -3049,14 +3048,9 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
     }
 
     // the kernels that read the caller's inputs, outside the captured body
-    TRY(run_encoder_inputs(e, t.w, features, nullptr, c.B, c.N));
-    if (c.seq()) {
-        hipLaunchKernelGGL(seq_inputs_kernel, dim3((nseq + 3) / 4), dim3(256), 0, e.stream, tokens, grad_logp, nseq, c.T, m->bos_idx,
-                           m->eos_idx, t.seq_tok, t.seq_tgt, t.seq_keep, t.w_row);
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        tokens = t.seq_tok; targets = t.seq_tgt;
-    }
-    TRY(stage_train_inputs(e, t, features, tokens, targets, rows, c.T, c.B * c.N));
+    ForwardCall f = c.forward();
+    f.tokens = tokens; f.targets = targets; f.row_grad = grad_logp;
+    TRY(stage_train_inputs(e, t, f, features));
     auto body = [&](Engine& ce) {
         ce.maskrow = t.maskrow;         // nullptr but for sequences under dropout (carve_train)
         return issue_train_body(ce, t, grads, c);
@@ -3067,7 +3061,7 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
         if (hipMemcpyAsync(loss_out, t.loss, sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess) return OVC_ELAUNCH;
     } else if (logp_out) {
         hipLaunchKernelGGL(seq_logp_kernel, dim3((rows + 255) / 256), dim3(256), 0, e.stream, t.w.logits, (long)pad4(rows), t.w.lse,
-                           t.w.tgt, t.seq_keep, rows, logp_out);
+                           t.w.tgt, t.w.seq_keep, rows, logp_out);
         OVC_RETURN_IF_LAUNCH_FAILED();
     }
     return OVC_OK;
@@ -3230,7 +3224,7 @@ extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features
                                        int* steps_run_out) {
     constexpr SearchForm kModes[3] = {SearchForm::Graph, SearchForm::HostEarly, SearchForm::Gated};
     if (!dropout || !dropout->seed || !slots_out || !m || mode < 0 || mode > 2) return OVC_EINVAL;
-    if (!model_ok(m) || !dropout_train_ok(m, B, N, m->max_len) || (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
+    if (!model_ok(m) || !dropout_train_ok(m, ForwardCall{B, N, 1, m->max_len}) || (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
     DropPlan plan{};
     bool any = false;
     SearchCall c{B, N, k, out_size, kModes[mode], ids_out, logp_out};

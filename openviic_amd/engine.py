@@ -482,6 +482,15 @@ class CaptionEngine:
             raise native.OvcError("unsupported {} (B={}, N={}, {}={}; see {})".format(what, B, N, width_name, width, sizer))
         return self._workspace("search", need), need
 
+    def _sized_workspace(self, kind, sizer, shape, refusal, extra=None):
+        """The stream's buffer of a teacher-forced call -- forward, maps or training -- and the bytes the call needs of it: the
+        sizer's answer for ``shape``, ``refusal`` raised where that is 0, before any launch, then the derived weights refreshed."""
+        need = getattr(self.lib, sizer)(ctypes.byref(self.desc), *shape)
+        if need == 0:
+            raise native.OvcError(refusal)
+        self._refresh_derived()
+        return self._workspace(kind, need, extra), need
+
     def release(self):
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
@@ -920,9 +929,10 @@ class CaptionEngine:
     _DISTILL_FORM = ("ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill")
 
     def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None):
-        """One training call's form: ``(entry point, shape, workspace bytes, trailing arguments)`` for ``shape`` ``(B, N, T)``
-        or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes on.
-        A shape or model the sizer refuses raises here, before any launch.  ``distill``: a checked ``distill.SoftTargets`` -- the
+        """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
+        T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
+        on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
+        workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
         soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments."""
         sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
         if distill is not None:
@@ -935,24 +945,21 @@ class CaptionEngine:
         if distill is not None:
             size_tail = (1 if drop else 0,)
             tail = (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), drop[0] if drop else None)
-        need = getattr(self.lib, sizer)(ctypes.byref(self.desc), *shape, *size_tail)
-        if need == 0:
-            raise native.OvcError("unsupported training configuration ({}, V={}; see {})".format(
+        self._check_pointers()
+        ws, need = self._sized_workspace(
+            "sequence" if sequence else "train", sizer, (*shape, *size_tail),
+            "unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                self._TRAIN_FORMS[sequence, False, False][0]))
-        return entry, shape, need, tail
+                self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
+        return entry, shape, ws, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
-        """The call of a ``_train_form``: the pointer table and derived weights refreshed, the gradient arena (a fresh one unless
-        ``arena`` is given), the stream's workspace -- per S for sequences -- and the entry point.  ``inputs``: the two device
-        tensors between the shape's leading sizes and T; ``out_shape``: the result the entry point writes (None: not asked for).
-        Returns ``(arena, grads, out)``."""
-        entry, shape, need, tail = form
-        self._check_pointers()
-        self._refresh_derived()
+        """The call of a ``_train_form``: the gradient arena (a fresh one unless ``arena`` is given) and the entry point.
+        ``inputs``: the two device tensors between the shape's leading sizes and T; ``out_shape``: the result the entry point
+        writes (None: not asked for).  Returns ``(arena, grads, out)``."""
+        entry, shape, ws, need, tail = form
         d = self.desc
         arena, table, grads = self._gradient_arena() if arena is None else arena
-        ws = self._workspace("sequence", need, shape[2]) if len(shape) == 4 else self._workspace("train", need)
         out = None if out_shape is None else torch.empty(out_shape, dtype=torch.float32, device=self.device)
         graph = self.use_graph if use_graph is None else bool(use_graph)
         check(getattr(self.lib, entry)(
@@ -1062,12 +1069,9 @@ class CaptionEngine:
             targets = targets.to(self.device).contiguous()
         tokens = caption_tokens.to(self.device).contiguous()
         want_logp = targets is None
-        need = self.lib.ovc_forward_workspace_bytes(ctypes.byref(d), B, N, T, 1 if want_logp else 0)
-        if need == 0:
-            raise native.OvcError("unsupported teacher-forced configuration (B={}, N={}, T={}; see ovc_forward_workspace_bytes)"
-                                  .format(B, N, T))
-        self._refresh_derived()
-        ws = self._workspace("forward", need, want_logp)
+        ws, need = self._sized_workspace(
+            "forward", "ovc_forward_workspace_bytes", (B, N, T, 1 if want_logp else 0),
+            "unsupported teacher-forced configuration (B={}, N={}, T={}; see ovc_forward_workspace_bytes)".format(B, N, T), want_logp)
         logp = torch.empty(B, T, d.vocab, dtype=torch.float32, device=self.device) if want_logp else None
         token_logp = None if want_logp else torch.empty(B, T, dtype=torch.float32, device=self.device)
         check(self.lib.ovc_forward(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
@@ -1095,13 +1099,10 @@ class CaptionEngine:
         S, T, squeeze = _maps.check(self.precision, reduce, given, B, d.max_len, d.vocab, device=self.device, name=name)
         if ids is None and not squeeze:
             raise native.OvcError("attention_maps: caption_tokens must be (B={}, T); got {}".format(B, tuple(given.shape)))
-        need = self.lib.ovc_attention_maps_workspace_bytes(ctypes.byref(d), B, N, S, T)
-        if need == 0:
-            raise native.OvcError("unsupported attention-maps configuration (B={}, N={}, S={}, T={}; see "
-                                  "ovc_attention_maps_workspace_bytes)".format(B, N, S, T))
+        ws, need = self._sized_workspace("maps", "ovc_attention_maps_workspace_bytes", (B, N, S, T),
+                                         "unsupported attention-maps configuration (B={}, N={}, S={}, T={}; see "
+                                         "ovc_attention_maps_workspace_bytes)".format(B, N, S, T))
         given = given.contiguous()
-        self._refresh_derived()
-        ws = self._workspace("maps", need)
         slots = d.memory if d.dec[0].cross_att.m_k else 0
         heads = () if reduce == "heads" else (d.heads,)
         maps = torch.empty((B, S, d.n_dec, d.n_levels) + heads + (T, N + slots), dtype=torch.float32, device=self.device)

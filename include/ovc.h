@@ -630,7 +630,8 @@ int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, 
  * [0, V), a duplicate, <pad> or <eos> (min_length keeps <eos> out); V - n_banned - 1 - max_len < k (so that every live row keeps k
  * finite candidates at every step); precision != 0; a vocabulary of more than 16 384 words; and everything ovc_beam_search
  * refuses.  ovc_search_constraints_ok: 1 when (m, k, options) is in this scope, else 0; launches nothing.
- * Not covered: length penalty or normalisation, repetition penalty, forced or prefix-constrained decoding, diverse beam search,
+ * Not covered: length penalty or normalisation, repetition penalty, forced words (lexical constraints), a per-step callback of
+ * allowed words, diverse beam search (a given prefix is ovc_beam_search_prefix, below, and does not combine with a ban set),
  * more than OVC_MAX_BANNED ids, constraints under dropout, in the early-exit forms, in the split-precision modes or when sampling.
  * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel (the search's own routing: the constrained
  * instance with active options, the plain selection with neutral ones) on caller-given device inputs -- row-major
@@ -650,6 +651,49 @@ int ovc_debug_beam_constrained_update(const float* logits, const int32_t* hist, 
                                       int V, int k, int T, int t, int eos, int no_repeat_ngram, int min_length, const int32_t* banned,
                                       int n_banned, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
                                       float* running_out, float* row_max_out, float* row_lsum_out, ovc_stream stream);
+
+/* Prefix search: the search of ovc_beam_search continuing a given caption prefix per image (appended to ABI 8; no struct changes).
+ * The rule (openviic_amd/prefix.py mirrors it in numpy):
+ * Table.  prefix [B][P] int32 word ids and prefix_len [B] int32 in HOST memory, 0 <= P <= max_len - 1, 0 <= P_b = prefix_len[b] <= P;
+ * row b's first P_b ids are read.  The call copies the table into its workspace in stream order, outside any captured graph.
+ * For image b at decode step t (0-based), in terms of ovc_beam_search's step (width W = 1 at t = 0, else k; rows b*W .. b*W+W-1):
+ *   - t < P_b (forced): every one of the k output slots takes parent = row 0 of the image and word w = prefix[b][t]; its running
+ *     score is run_0 + ((x_w - M_0) - ls_0) with run_0, M_0, ls_0 row 0's running score, row maximum and log-sum and x_w row 0's
+ *     logit of w -- the arithmetic and the order of every candidate of ovc_beam_search; alive = 1 and the recorded log-probability
+ *     is (x_w - M_0) - ls_0.  Histories, the next input rows and the ancestor table are written as the plain step writes them.
+ *   - t == P_b and t >= 1 (first free step): rows 1..k-1 repeat row 0 and offer nothing; the k winners are the k best words of row
+ *     0 alone -- what step 0 does at width 1.
+ *   - t > P_b, or P_b == 0: the plain step.  An image with P_b = 0 gets ovc_beam_search's bits whatever the other images' prefixes.
+ * logp_out / all_logp_out are the model's own log-probabilities at every step, forced steps included (all_logp_out holds every
+ * row's, the repeated rows' too); the final ordering by total score and out_size are ovc_beam_search's.
+ * P = 0, or every length 0, are ovc_beam_search / ovc_beam_search_graph: the same launches, graph entry and bits.
+ * ovc_beam_search_prefix: plain launches, all_logp_out as ovc_beam_search.  ovc_beam_search_prefix_graph: one captured graph from
+ * the second call; "has a prefix" and P are part of its key, the words and lengths are not: one graph serves every table of a
+ * shape.  Workspace: ovc_prefix_workspace_bytes(m, B, N, k, return_probs, P) (ovc_workspace_bytes' layout, the table behind it;
+ * 0: out of scope).  The table must stay valid until the stream has passed the call's copies.
+ * OVC_EINVAL, nothing launched: P < 0 or P > max_len - 1; a length outside 0..P; a null table with P > 0; a forced id outside
+ * [0, V); with a length that is not 0: precision != 0, a vocabulary of more than 16 384 words; and everything ovc_beam_search
+ * refuses.  <bos>, <eos> or <pad> among the forced words are the caller's to refuse (openviic_amd/prefix.py does): the kernel forces
+ * what it is given.  ovc_search_prefix_ok: 1 when (m, k, P) is in this scope, else 0; launches nothing.
+ * Not covered: forced steps at width 1 or as one teacher-forced pass; a prefix together with a ban set, dropout, the early-exit
+ * forms, an ensemble, sampling or the split-precision modes.
+ * ovc_debug_beam_prefix_update: test entry, ONE step of the production kernel (the search's own routing: the prefix instance when a
+ * length is not 0, else the plain selection) on the inputs of ovc_debug_beam_constrained_update plus the table (width = 1 at t = 0,
+ * else k: a beam of 1 may be at any step).  scratch:
+ * ovc_debug_beam_prefix_update_bytes. */
+int ovc_search_prefix_ok(const ovc_model* m, int k, int P);
+size_t ovc_prefix_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int P);
+int ovc_beam_search_prefix(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                           const int32_t* prefix, const int32_t* prefix_len, int P, void* workspace, size_t workspace_bytes,
+                           int64_t* ids_out, float* logp_out, float* all_logp_out, ovc_stream stream);
+int ovc_beam_search_prefix_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                 const int32_t* prefix, const int32_t* prefix_len, int P, void* workspace, size_t workspace_bytes,
+                                 int64_t* ids_out, float* logp_out, ovc_stream stream);
+size_t ovc_debug_beam_prefix_update_bytes(int B, int width, int V, int k, int T);
+int ovc_debug_beam_prefix_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B, int width,
+                                 int V, int k, int T, int t, int eos, const int32_t* prefix, const int32_t* prefix_len, int P,
+                                 void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
+                                 float* row_max_out, float* row_lsum_out, ovc_stream stream);
 
 /* Ensemble beam search: ONE search over the mean of the log-probabilities of M models (the meshed-memory authors'
  * TransformerEnsemble).  Members m = 0..M-1, 1 <= M <= OVC_MAX_ENSEMBLE, read the same features (and the call's boxes, where a

@@ -17,6 +17,7 @@ import collections
 import torch
 
 from . import constraints as _constraints
+from . import prefix as _prefix
 from . import distill as _distill
 from . import dropout as _dropout
 from . import engine
@@ -471,7 +472,8 @@ class BaseTransformer(Module):
         return probs
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
-                    fused=True, dropout=False, generator=None, no_repeat_ngram_size=0, min_length=0, banned_words=None, **kwargs):
+                    fused=True, dropout=False, generator=None, no_repeat_ngram_size=0, min_length=0, banned_words=None, prefix=None,
+                    **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
 
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
@@ -496,11 +498,39 @@ class BaseTransformer(Module):
         applies after the log-softmax: ``log_probs`` / ``all_log_probs`` stay the model's own, so the gradient of ``log_probs``
         is the plain search's.  The defaults are the plain call, bit for bit.  Refused by name before any launch or draw: a bad
         option; active constraints with ``fused=False``, ``dropout=True``, an early-exit form, a precision other than 'f32' or a
-        vocabulary of more than 16 384 words; and length penalty, repetition penalty, forced or prefix-constrained decoding and
-        diverse beam search, which the engine does not have.
+        vocabulary of more than 16 384 words; and length penalty, repetition penalty, forced words (lexical constraints),
+        ``prefix_allowed_tokens_fn`` and diverse beam search, which the engine does not have.
+
+        ``prefix`` (fused only; ``ovc_beam_search_prefix``; the rule is stated in ``include/ovc.h`` and
+        mirrored by ``openviic_amd.prefix``): an int64 tensor ``(B, P)``, ``0 <= P <= max_len - 1``.  Image ``b`` emits
+        ``prefix[b, :P_b]`` at steps ``0 .. P_b - 1`` -- ``P_b`` the position of the row's first ``<pad>``, or ``P``; ``<pad>`` may
+        only trail, so prefixes may be ragged -- and from step ``P_b`` on the search is the reference's, started from that state:
+        its ``k`` beams are the ``k`` best continuations.  Shapes and the final ordering are unchanged; ``log_probs`` /
+        ``all_log_probs`` are the model's own at every step, forced steps included.  ``None``, ``P == 0`` or an all-``<pad>``
+        table are the plain call, bit for bit, and an image with ``P_b == 0`` gets its plain search whatever the others' prefixes.
+        Refused by name before any launch or draw: a wrong dtype, rank or batch size, ``P > max_len - 1``, an id outside
+        ``[0, V)``, ``<bos>`` or ``<eos>``, a word behind a ``<pad>``; a prefix with ``fused=False``, ``dropout=True``, an
+        early-exit form, active constraints, a precision other than 'f32' or more than 16 384 words; and a model in ``train()``
+        mode with gradients enabled (no SCST through a forced prefix: call ``eval()`` or use ``no_grad``).
         """
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
         constraints = _requested_constraints(no_repeat_ngram_size, min_length, banned_words)
+        if prefix is not None:       # every refusal of the table and of what it does not combine with, before any launch and draw
+            dec = self.decoder
+            prefix = _prefix.check(prefix, int(batch_size), dec.fc.out_features, dec.max_len, dec.padding_idx, self.vocab.bos_idx,
+                                   self.eos_idx)
+        if prefix is not None:       # not neutral
+            if not fused:
+                raise engine.native.OvcError("beam_search(prefix=...) needs fused=True: the host loop forces no word")
+            if dropout:
+                raise engine.native.OvcError("beam_search(prefix=...): dropout=True is not covered -- a prefix under dropout is out "
+                                             "of scope")
+            eng = self._fused_engine()
+            checked = eng.check_constraints(beam_size, constraints, kwargs.get("early_exit")) if constraints else None
+            prefix = eng.check_prefix(batch_size, beam_size, prefix, kwargs.get("early_exit"), None, checked)
+            if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                raise engine.native.OvcError("beam_search(prefix=...): the model is in train() mode with gradients enabled -- there "
+                                             "is no SCST through a forced prefix; call model.eval() or use torch.no_grad()")
         if constraints and not fused:
             raise engine.native.OvcError("beam_search(no_repeat_ngram_size / min_length / banned_words) needs fused=True: the host "
                                          "loop has no ban set")
@@ -516,7 +546,8 @@ class BaseTransformer(Module):
             if probs and return_probs:
                 raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
             ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
-                                                              return_probs, kwargs.get("early_exit"), constraints=constraints)
+                                                              return_probs, kwargs.get("early_exit"), constraints=constraints,
+                                                              prefix=prefix)
             logp = self._scst_log_probs(input_features, ids, logp, recompute)
             if out_size == 1:
                 ids, logp = ids.squeeze(1), logp.squeeze(1)
@@ -561,14 +592,15 @@ class BaseTransformer(Module):
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     def _generate(self, input_features, batch_size, width, out_size=None, probs=None, generator=None, return_probs=False,
-                  early_exit=None, checked=None, constraints=None):
+                  early_exit=None, checked=None, constraints=None, prefix=None):
         """One fused generation, for ``beam_search``, ``sample`` and ``scst_step``: ``width`` beams of which the best ``out_size``
         are returned -- with ``probs`` (what ``_search_dropout_probs`` returned, not empty) under this call's dropout masks -- or,
         with ``out_size=None``, ``width`` samples under the sampler's options (``checked``: what ``check_sample`` returned).  The masks' or the samples' seed is drawn here, one per call; plain beams draw
         nothing.  Returns ``(ids, log_probs, all_log_probs, recompute)``: the first two unsqueezed ``(B, out_size, T)``, the third
         None without ``return_probs``, the last the keyword arguments under which ``sequence_backward`` recomputes these
         log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``).  ``constraints``: the beam
-        search's ``(n, L, banned)`` as ``check_constraints`` returned them, or None."""
+        search's ``(n, L, banned)`` as ``check_constraints`` returned them, or None.  ``prefix``: the beam search's table as
+        ``check_prefix`` returned it, or None."""
         eng = self._fused_engine()
         feats, boxes = self._engine_inputs(input_features)
         recompute = {}
@@ -582,7 +614,7 @@ class BaseTransformer(Module):
             recompute = dict(dropout=drop, slots=slots, beam_size=width)
         else:
             out = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, return_probs=return_probs, early_exit=early_exit,
-                                  constraints=constraints)
+                                  constraints=constraints, prefix=prefix)
         ids, logp = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in out[:2])       # out_size = 1: the engine squeezed them
         return ids, logp, out[2] if return_probs else None, recompute
 

@@ -18,7 +18,6 @@ OUT_OF_SCOPE = {
     "length_normalization": "length penalty / length normalisation",
     "repetition_penalty": "repetition penalty",
     "forced_words": "forced decoding",
-    "prefix": "prefix-constrained decoding",
     "prefix_allowed_tokens_fn": "prefix-constrained decoding",
     "num_beam_groups": "diverse beam search",
     "diversity_penalty": "diverse beam search",

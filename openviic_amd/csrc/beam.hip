@@ -220,13 +220,16 @@ static_assert(kBanWords == 512 && OVC_MAX_BANNED <= 64, "one bitmap word per blo
 static_assert(kFusedVocabBlocks == 2 * 64 * kFusedPairs && kFusedVocabBlocks == kBanWords, "fused_tail_ok admits what one wave loads");
 
 // 512 threads per image: wave w < width owns beam row w through phases A and B (no workgroup-level reduction), then all
-// eight waves gather the hot blocks and wave 0 ranks the survivors in registers.  One body for the three instances: the plain and
-// the gated kernel compile it without a ban set (kBan = false: no constraints among their arguments, nothing of them in their code).
+// eight waves gather the hot blocks and wave 0 ranks the survivors in registers.  One body for the four instances: the plain and
+// the gated kernel compile it without a ban set (kBan = false: no constraints among their arguments, nothing of them in their code)
+// and without a prefix table (kPrefix = false, likewise).
 __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
                                                                           int stats_ld, const float* __restrict__ running_in,
                                                                           long ld_row, long ld_word) {
     constexpr bool kBan = false;                        // no ban set ...
     constexpr BeamConstraints cons{};                   // ... and no constraints among the arguments: the instance below has both
+    constexpr bool kPrefix = false;                     // no prefix table either: beam_prefix_update_kernel's
+    constexpr BeamPrefix pre{};
 #include "bodies/beam_fused_update.inc"
 }
 __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel_gated(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
@@ -235,6 +238,8 @@ __global__ __launch_bounds__(kFusedThreads) void beam_fused_update_kernel_gated(
     if (ovc_gate_closed(gate)) return;
     constexpr bool kBan = false;
     constexpr BeamConstraints cons{};
+    constexpr bool kPrefix = false;
+    constexpr BeamPrefix pre{};
 #include "bodies/beam_fused_update.inc"
 }
 
@@ -249,6 +254,22 @@ __global__ __launch_bounds__(kFusedThreads) void beam_constrained_update_kernel(
                                                                                 int stats_ld, const float* __restrict__ running_in,
                                                                                 long ld_row, long ld_word, BeamConstraints cons) {
     constexpr bool kBan = true;
+    constexpr bool kPrefix = false;
+    constexpr BeamPrefix pre{};
+#include "bodies/beam_fused_update.inc"
+}
+
+// Prefix selection (ovc_beam_search_prefix, include/ovc.h: the rule): the fused selection and bookkeeping of one image that may
+// have to continue a given prefix.  The workgroup reads the image's length P_b and, while t < P_b, its word of step t from device
+// memory.  Forced (t < P_b): row 0's pieces and one logit give the k slots' score, phase C is skipped.  First free step
+// (t == P_b >= 1): rows 1.. repeat row 0, so only row 0 offers candidates -- step 0's width 1 inside a call of width k.  Otherwise,
+// and for every image with P_b = 0, the plain kernel's text.  No LDS and no atomics of its own.
+__global__ __launch_bounds__(kFusedThreads) void beam_prefix_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                           int stats_ld, const float* __restrict__ running_in,
+                                                                           long ld_row, long ld_word, BeamPrefix pre) {
+    constexpr bool kBan = false;
+    constexpr BeamConstraints cons{};
+    constexpr bool kPrefix = true;
 #include "bodies/beam_fused_update.inc"
 }
 
@@ -546,6 +567,18 @@ int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail&
     for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
                        f.ld_row, f.ld_word, cons);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+// The prefix step: ovc_beam_fused_update_launch's arguments plus the table's device addresses (the contents are read by the kernel).
+// No gated instance: the early-exit forms are out of the prefix search's scope.
+int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const BeamPrefix& pre, int B,
+                                  hipStream_t stream) {
+    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || p.alive_count) return OVC_EINVAL;
+    if (p.T < 1 || p.t < 0 || p.t >= p.T || !pre.ids || !pre.len || pre.P < 1 || pre.P > p.T - 1) return OVC_EINVAL;
+    hipLaunchKernelGGL(beam_prefix_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
+                       f.ld_row, f.ld_word, pre);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

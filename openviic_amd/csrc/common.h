@@ -294,6 +294,17 @@ bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k
 // ovc_beam_fused_update_launch with a per-row ban set (p.hist_in holds the rows' histories); p.alive_count must be nullptr.
 int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamConstraints& cons,
                                        int B, hipStream_t stream);
+// The prefix search's table (include/ovc.h, ovc_beam_search_prefix), in DEVICE memory: read by the kernel, so one captured graph
+// serves every content of a shape.
+struct BeamPrefix {
+    const int32_t* ids;      // [B][P] the forced words; row b's first len[b] are read
+    const int32_t* len;      // [B] P_b in 0..P
+    int P;                   // the row stride of ids, >= 1
+};
+// ovc_beam_fused_update_launch with a prefix table: an image is forced (p.t < P_b), restricted to its row 0 (p.t == P_b >= 1) or
+// takes the plain step; p.alive_count must be nullptr.
+int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamPrefix& pre, int B,
+                                  hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
 // log-probabilities and the bookkeeping, one launch.  One argument block, by value: p is member 0's -- the shared beam state, and
 // member 0's embedding tables / next_x / d_model for the next step's input rows -- and every member's tail, logits, embedding

@@ -135,6 +135,8 @@ struct Workspace {
                                                   // and the gated search's step count for the slot table
     float* choice_rows; int32_t* choice_word; int32_t* choice_kept;   // ovc_sample_shaped: the chooser's row-major logits [R][V],
                                                   // the drawn words and the kept counts [R]
+    int32_t* prefix_ids; int32_t* prefix_len;     // ovc_beam_search_prefix: the call's table [B][P] / [B] (refreshed outside the
+                                                  // captured body)
     // teacher-forced forward (a ForwardCall; rows = B*S*T): the self-attention mask [B*S][T][T], the target words, the logit of
     // each row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -1015,6 +1017,11 @@ struct SearchCall {
     // Ensemble (ovc_ensemble_beam_search): ens_M > 1 members, ens[0] the call's model; every step runs each member's decoder rows
     // on the shared beams and selects on the mean of their log-probabilities.  One member is the plain call: ens_M stays 0.
     int ens_M; const ovc_model* ens[OVC_MAX_ENSEMBLE];
+    // Prefix search (ovc_beam_search_prefix): the caller's table in HOST memory -- ids [B][prefix_P], lengths [B] -- copied to the
+    // workspace outside any captured body.  prefix_P = 0 (no table, or every length 0): the plain search.  A sizer or predicate
+    // states prefix_P alone.
+    int prefix_P; const int32_t* prefix_ids; const int32_t* prefix_len;
+    bool prefixed() const { return prefix_P != 0; }
     bool ensemble() const { return ens_M > 1; }
     bool constrained() const { return cons.active(); }
     bool shaped() const { return sample && has_options && !(temperature == 1.0f && top_k == 0 && top_p == 1.0f); }
@@ -1035,7 +1042,8 @@ bool search_ok(const ovc_model* m, const SearchCall& c);
 // nothing else in the call.
 bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
     if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
-    if (c.plan || c.sample || c.has_options || c.constrained() || (c.form != SearchForm::Plain && c.form != SearchForm::Graph)) return false;
+    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
+        return false;
     SearchCall alone = c;
     alone.ens_M = 0;
     for (int i = 0; i < c.ens_M; ++i) {
@@ -1061,6 +1069,11 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                             (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
                             !ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)))
         return false;
+    // a prefix: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, no ban set, plain launches or the whole-search
+    // graph, and room for one free step behind the longest prefix
+    if (c.prefixed() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan || c.constrained() ||
+                         (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.prefix_P < 0 || c.prefix_P > m->max_len - 1))
+        return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
 }
@@ -1073,6 +1086,12 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
         const size_t R = (size_t)c.B * c.k;
         w.choice_rows = a.take<float>(R * (size_t)m->vocab);
         w.choice_word = a.take<int32_t>(R); w.choice_kept = a.take<int32_t>(R);
+        w.bytes = (a.off + 255) & ~(size_t)255;
+    }
+    if (c.prefixed()) {                           // behind everything else: ovc_beam_search's layout is a prefix of this one
+        Bump a{reinterpret_cast<char*>(base), w.bytes};
+        w.prefix_ids = a.take<int32_t>((size_t)c.B * c.prefix_P);
+        w.prefix_len = a.take<int32_t>((size_t)c.B);
         w.bytes = (a.off + 255) & ~(size_t)255;
     }
     return w;
@@ -1389,6 +1408,8 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
         else if (c.constrained())  // the one branch of a constrained step: the selection with a per-row ban set
             RUN(ovc_beam_constrained_update_launch(bu, tail, w.running[cur], c.cons, B, s));
+        else if (c.prefixed())     // the one branch of a prefix step: the selection reads the staged table
+            RUN(ovc_beam_prefix_update_launch(bu, tail, w.running[cur], BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P}, B, s));
         else if (!(debug_skip() & 8))
             RUN(ovc_beam_fused_update_launch(bu, tail, w.running[cur], B, s, e.gate));
         if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
@@ -1402,6 +1423,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
+    if (c.prefixed()) return OVC_EINVAL;       // search_ok: the fused tail; the two-pass pair knows no prefix
     RUN(ovc_beam_select_launch(bs, B, s, e.gate));
     RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
@@ -1606,6 +1628,8 @@ enum class GraphKind {
     ConstrainedSearch,  // ovc_beam_search_constrained_graph with options that are not neutral (as Search; the options in the hash)
     EnsembleSearch,     // ovc_ensemble_beam_search_graph with more than one member (as Search; every member's contents in the hash)
     TrainDistill,       // ovc_forward_backward_distill, with or without dropout (k = T, out_size = 1; the weight in the hash)
+    PrefixSearch,       // ovc_beam_search_prefix_graph with a table that forces a word (as Search; P in the hash, the table's contents
+                        // in the workspace)
     ForwardMaps,        // a ForwardCall with maps, ovc_attention_maps (forward_graph_key: k = T, out_size = S): the scoring body
                         // over B*S*T rows plus the map launches
 };
@@ -1774,6 +1798,10 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
     if (c.constrained())      // the options (banned ids sorted) are part of the key: no call replays another option set's graph
         return GraphKey{GraphKind::ConstrainedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&c.cons, sizeof(c.cons)), workspace, c.B, c.N,
                         c.k, c.out_size};
+    if (c.prefixed()) {       // "has a prefix" and P, never the words: the table is read from the workspace, refreshed per call
+        const int P = c.prefix_P;
+        return GraphKey{GraphKind::PrefixSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&P, sizeof(P)), workspace, c.B, c.N, c.k, c.out_size};
+    }
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1879,6 +1907,7 @@ namespace {
 int run_search(const ovc_model* m, const SearchCall& c, const float* features, const float* boxes, void* workspace,
                size_t workspace_bytes, ovc_stream stream) {
     if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out || (c.sample && !c.sample_seed)) return OVC_EINVAL;
+    if (c.prefixed() && (!c.prefix_ids || !c.prefix_len)) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
@@ -1898,6 +1927,10 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     }
     if (c.sample && hipMemcpyAsync(w.drop_seed, c.sample_seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
         return OVC_ELAUNCH;                        // the same slot, refreshed the same way: a replayed graph reads this call's seed
+    if (c.prefixed() &&                            // the table, refreshed the same way: a replayed graph reads this call's prefixes
+        (hipMemcpyAsync(w.prefix_ids, c.prefix_ids, sizeof(int32_t) * c.B * c.prefix_P, hipMemcpyHostToDevice, e.stream) != hipSuccess ||
+         hipMemcpyAsync(w.prefix_len, c.prefix_len, sizeof(int32_t) * c.B, hipMemcpyHostToDevice, e.stream) != hipSuccess))
+        return OVC_ELAUNCH;
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
     for (int i = 1; i < c.ens_M; ++i) {            // every member reads the call's features, and its boxes where its encoder takes them
         Engine me = e;
@@ -2063,6 +2096,115 @@ extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int3
     bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
     bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
     if (cons.active()) TRY(ovc_beam_constrained_update_launch(bu, tail, running, cons, B, s));      // run_decode_step's routing
+    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
+    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Prefix search (include/ovc.h: the rule).  The plain search started behind a given prefix per image; no table, P = 0 or every length
+// 0 are the plain calls, launch for launch (the same SearchCall, hence the same graph key; the plain workspace layout is a prefix
+// of this one).
+// ---------------------------------------------------------------------------------------------
+// The caller's table as the SearchCall takes it; false: P outside 0..max_len - 1, a null table with P > 0, a length outside 0..P.
+static bool prefix_from(const ovc_model* m, const int32_t* ids, const int32_t* len, int B, int P, SearchCall* c) {
+    if (!m || P < 0 || P > m->max_len - 1 || B <= 0) return false;
+    if (P == 0) return true;
+    if (!ids || !len) return false;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (len[b] < 0 || len[b] > P) return false;
+        for (int i = 0; i < len[b]; ++i)          // the kernel indexes the logits with these
+            if (ids[(size_t)b * P + i] < 0 || ids[(size_t)b * P + i] >= m->vocab) return false;
+        any = any || len[b] > 0;
+    }
+    if (any) { c->prefix_P = P; c->prefix_ids = ids; c->prefix_len = len; }
+    return true;
+}
+
+extern "C" int ovc_search_prefix_ok(const ovc_model* m, int k, int P) {
+    SearchCall c{1, 1, k, k};
+    if (!model_ok(m) || P < 0 || P > m->max_len - 1) return 0;
+    c.prefix_P = P;
+    return search_ok(m, c) ? 1 : 0;       // P = 0: the plain search's scope
+}
+
+extern "C" size_t ovc_prefix_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int P) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (!model_ok(m) || P < 0 || P > m->max_len - 1) return 0;
+    c.prefix_P = P;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+extern "C" int ovc_beam_search_prefix(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                      const int32_t* prefix, const int32_t* prefix_len, int P, void* workspace, size_t workspace_bytes,
+                                      int64_t* ids_out, float* logp_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    if (!prefix_from(m, prefix, prefix_len, B, P, &c)) return OVC_EINVAL;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_prefix_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                            int out_size, const int32_t* prefix, const int32_t* prefix_len, int P, void* workspace,
+                                            size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out};
+    if (!prefix_from(m, prefix, prefix_len, B, P, &c)) return OVC_EINVAL;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the prefix one when a
+// length is not 0, else the plain one -- on caller-given inputs as ovc_debug_beam_constrained_update takes them, plus the table in
+// HOST memory (prefix [B][P], prefix_len [B]).  scratch: ovc_debug_beam_prefix_update_bytes.
+extern "C" size_t ovc_debug_beam_prefix_update_bytes(int B, int width, int V, int k, int T) {
+    const size_t base = ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
+    return base ? base + 4 * ((size_t)B * T + (size_t)B) + 512 : 0;
+}
+
+extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B,
+                                            int width, int V, int k, int T, int t, int eos, const int32_t* prefix, const int32_t* prefix_len,
+                                            int P, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
+                                            float* running_out, float* row_max_out, float* row_lsum_out, ovc_stream stream) {
+    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
+        return OVC_EINVAL;
+    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || (width != 1 && width != k) || V <= 0 ||
+        (V + 31) / 32 > kFusedVocabBlocks || T < 1 || T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (P < 0 || P > T - 1 || (P > 0 && (!prefix || !prefix_len))) return OVC_EINVAL;
+    bool any = false;
+    for (int b = 0; b < B && P > 0; ++b) {
+        if (prefix_len[b] < 0 || prefix_len[b] > P) return OVC_EINVAL;
+        for (int i = 0; i < prefix_len[b]; ++i)
+            if (prefix[(size_t)b * P + i] < 0 || prefix[(size_t)b * P + i] >= V) return OVC_EINVAL;
+        any = any || prefix_len[b] > 0;
+    }
+    if (scratch_bytes < ovc_debug_beam_prefix_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const int rows = B * width, ldt = (rows + 3) & ~3;
+    const size_t Rk = (size_t)B * k;
+    Bump a{reinterpret_cast<char*>(scratch), 0};
+    float* logits_t = a.take<float>((size_t)V * ldt);
+    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
+    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
+    tail.stats = stats;
+    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
+    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
+    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
+    int32_t* ids_dev = a.take<int32_t>((size_t)B * T); int32_t* len_dev = a.take<int32_t>((size_t)B);
+    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
+        return OVC_ELAUNCH;
+    if (any && (hipMemcpyAsync(ids_dev, prefix, sizeof(int32_t) * B * P, hipMemcpyHostToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(len_dev, prefix_len, sizeof(int32_t) * B, hipMemcpyHostToDevice, s) != hipSuccess))
+        return OVC_ELAUNCH;
+    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
+    BeamUpdateArgs bu{};
+    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
+    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
+    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
+    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
+    if (any) TRY(ovc_beam_prefix_update_launch(bu, tail, running, BeamPrefix{ids_dev, len_dev, P}, B, s));      // run_decode_step's routing
     else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
     return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
 }

@@ -25,6 +25,7 @@ from . import constraints as _constraints
 from . import distill as _distill
 from . import dropout as _dropout
 from . import native
+from . import prefix as _prefix
 from .native import check
 
 
@@ -474,7 +475,7 @@ class CaptionEngine:
 
     def _search_workspace(self, kind, B, N, width, return_probs, options=()):
         """The stream's search buffer and the bytes a generation of a ``_SEARCH_FORMS`` kind needs of it, or the kind's refusal.
-        ``options``: the shaped sampler's ``(temperature, top_k, top_p)``."""
+        ``options``: the shaped sampler's ``(temperature, top_k, top_p)``, or the prefix search's ``(P,)``."""
         sizer, what, width_name, _ = self._SEARCH_FORMS[kind]
         need = getattr(self.lib, sizer)(ctypes.byref(self.desc), B, N, width,
                                         *(() if kind == "masked" else (1 if return_probs else 0,)), *options)
@@ -495,7 +496,7 @@ class CaptionEngine:
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
         for (kind, _, _), ws in getattr(self, "_buffers", {}).items():
-            if lib is not None and kind not in ("arena", "steps"):
+            if lib is not None and kind not in ("arena", "steps", "prefix_table"):
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._buffers = {}
 
@@ -627,6 +628,9 @@ class CaptionEngine:
                                                       "stream")),
             "graph": ("ovc_beam_search_constrained_graph", ("out_size", "ngram", "min_length", "banned", "n_banned", *_RESULTS,
                                                             "stream"))}),
+        "prefix": ("ovc_prefix_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search_prefix", ("out_size", "prefix", "prefix_len", "P", *_RESULTS, "everything", "stream")),
+            "graph": ("ovc_beam_search_prefix_graph", ("out_size", "prefix", "prefix_len", "P", *_RESULTS, "stream"))}),
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
@@ -639,7 +643,7 @@ class CaptionEngine:
     }
 
     def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None, constraints=None):
+                    options=None, constraints=None, prefix=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
@@ -648,10 +652,13 @@ class CaptionEngine:
         dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
         (``sequence_backward(dropout=..., slots=...)`` recomputes under them).  ``options``: what ``sample_options`` returned --
         the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw.  ``constraints``: what
-        ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search."""
+        ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search.  ``prefix``: what
+        ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None."""
         kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
         if constraints:
             kind = "constrained"
+        if prefix:
+            kind = "prefix"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -667,7 +674,7 @@ class CaptionEngine:
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
         if form == "graph" and not self.use_graph and kind != "masked":
             form = "plain"
-        ws, need = self._search_workspace(kind, B, N, width, return_probs, options or ())
+        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else options or ())
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
@@ -687,6 +694,14 @@ class CaptionEngine:
         if constraints:
             n, L, banned = constraints
             args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
+        if prefix:
+            table, lengths = prefix
+            if table.shape[0] != B:
+                raise native.OvcError("prefix holds {} rows but the batch {} images".format(table.shape[0], B))
+            # host memory the library copies in stream order: kept until the stream's next prefix call replaces it
+            self._buffers[self._stream_key("prefix_table")] = prefix
+            int_p = ctypes.POINTER(ctypes.c_int32)
+            args.update(prefix=table.ctypes.data_as(int_p), prefix_len=lengths.ctypes.data_as(int_p), P=table.shape[1])
         entry, names = self._SEARCH_FORMS[kind][3][form]
         self.last_steps_run = T
         check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
@@ -724,9 +739,44 @@ class CaptionEngine:
             raise native.OvcError(what + ": the engine refuses these options for this model (ovc_search_constraints_ok)")
         return options
 
+    def check_prefix(self, batch_size, beam_size, prefix=None, early_exit=None, dropout=None, constraints=None):
+        """The refusals of a prefix search that need no features, each naming its argument: callers run them before any launch
+        and any random draw.  ``prefix``: None or an int64 tensor ``(B, P)``; ``constraints``: what ``check_constraints``
+        returned.  Returns the table ``(ids, lengths)`` of ``openviic_amd.prefix.check``, or None when the prefix is neutral (the
+        plain search)."""
+        if prefix is None:
+            return None
+        d = self.desc
+        # a tuple: the table ``prefix.check`` has already returned (the model's beam_search runs it before anything else)
+        table = prefix if isinstance(prefix, tuple) else _prefix.check(prefix, int(batch_size), d.vocab, d.max_len, d.pad_idx, d.bos_idx,
+                                                                       d.eos_idx)
+        if table is None:
+            return None
+        what = "beam_search(prefix=...)"
+        if constraints:
+            raise native.OvcError(what + ": no_repeat_ngram_size / min_length / banned_words are not covered together with a "
+                                         "prefix -- a prefix under a ban set is out of scope")
+        if dropout is not None:
+            raise native.OvcError(what + ": dropout=... is not covered -- a prefix under dropout is out of scope")
+        early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
+        if early:
+            raise native.OvcError(what + ": early_exit={!r} is not covered -- the prefix search has no early-exit form; pass "
+                                         "early_exit=False".format("device" if early == "device" else True))
+        if self.precision != "f32":
+            raise native.OvcError(what + ": precision={!r} is not covered -- a prefix runs in 'f32' only".format(self.precision))
+        if d.vocab > 16384:
+            raise native.OvcError(what + ": a vocabulary of {} words is not covered -- at most 16384".format(d.vocab))
+        if not self.lib.ovc_search_prefix_ok(ctypes.byref(d), int(beam_size), table[0].shape[1]):
+            raise native.OvcError(what + ": the engine refuses this prefix for this model (ovc_search_prefix_ok)")
+        return table
+
     def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None,
-                    constraints=None):
-        """``constraints=(no_repeat_ngram_size, min_length, banned_words)`` (``ovc_beam_search_constrained``; DESIGN.md section 2s,
+                    constraints=None, prefix=None):
+        """``prefix`` (``ovc_beam_search_prefix``; DESIGN.md section 2w, ``openviic_amd.prefix`` mirrors the rule): an int64
+        tensor ``(B, P)``, ``<pad>`` trailing -- image ``b`` emits its row's words first and the search continues behind them;
+        None, ``P == 0`` or all ``<pad>`` are the plain call.  Refused by name before any launch: a bad table, or a prefix together
+        with active constraints, ``dropout``, an early-exit form, a split precision or a vocabulary of more than 16 384 words.
+        ``constraints=(no_repeat_ngram_size, min_length, banned_words)`` (``ovc_beam_search_constrained``; DESIGN.md section 2s,
         ``openviic_amd.constraints`` mirrors the rule): words are banned per beam row and step, everything else is the plain
         search; neutral values are the plain call.  Refused by name before any launch: a bad option, or constraints together with
         ``dropout``, an early-exit form, a split precision or a vocabulary of more than 16 384 words.
@@ -738,6 +788,7 @@ class CaptionEngine:
         stream order, the number of decode steps that did work; ``last_steps_run`` stays ``max_len``.  With ``return_probs``
         every mode runs the full search."""
         constraints = self.check_constraints(beam_size, constraints, early_exit, dropout)
+        prefix = self.check_prefix(batch_size, beam_size, prefix, early_exit, dropout, constraints)
         early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
         table_drop = None
         if dropout is not None:
@@ -745,7 +796,7 @@ class CaptionEngine:
                 raise native.OvcError("beam_search(dropout=...) has no return_probs form")
             table_drop = self._dropout_table(dropout)
         ids, logp, everything, slots = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early,
-                                                        table_drop, constraints=constraints)
+                                                        table_drop, constraints=constraints, prefix=prefix)
         if dropout is not None:
             return ids, logp, slots
         if out_size == 1:

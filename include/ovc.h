@@ -631,7 +631,8 @@ int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, 
  * finite candidates at every step); precision != 0; a vocabulary of more than 16 384 words; and everything ovc_beam_search
  * refuses.  ovc_search_constraints_ok: 1 when (m, k, options) is in this scope, else 0; launches nothing.
  * Not covered: length penalty or normalisation, repetition penalty, forced words (lexical constraints), a per-step callback of
- * allowed words, diverse beam search (a given prefix is ovc_beam_search_prefix, below, and does not combine with a ban set),
+ * allowed words, groups under a ban set (a given prefix is ovc_beam_search_prefix and diverse beam search ovc_beam_search_diverse,
+ * below; neither combines with a ban set),
  * more than OVC_MAX_BANNED ids, constraints under dropout, in the early-exit forms, in the split-precision modes or when sampling.
  * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel (the search's own routing: the constrained
  * instance with active options, the plain selection with neutral ones) on caller-given device inputs -- row-major
@@ -694,6 +695,53 @@ int ovc_debug_beam_prefix_update(const float* logits, const int32_t* hist, const
                                  int V, int k, int T, int t, int eos, const int32_t* prefix, const int32_t* prefix_len, int P,
                                  void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
                                  float* row_max_out, float* row_lsum_out, ovc_stream stream);
+
+/* Diverse beam search (Vijayakumar et al., 2016): the search of ovc_beam_search with its k beams in G groups and a Hamming penalty
+ * between the groups of one step (appended to ABI 8; no struct changes).  The rule (openviic_amd/diverse.py mirrors it in numpy):
+ * Groups and slots.  k beams, G groups, k' = k / G beams per group; k % G == 0, 1 <= G <= k <= OVC_MAX_BEAM.  Group g owns the beam
+ * slots g k' .. (g + 1) k' - 1 at every step.  lambda: the fp32 strength, finite, 0 <= lambda <= 1e30.
+ * Rows.  At step t = 0 the image has one row, row 0, and every group reads it.  At t >= 1 group g's candidates come from the k' rows
+ * of its own slots only.
+ * Order.  Within a step the groups are processed in order g = 0 .. G - 1.  count_g(w) is the number of winners of groups 0 .. g - 1 at
+ * THIS step whose parent row was live and whose word is w; <eos> counts like any word, the <pad> continuation of a frozen beam does
+ * not (nor does a slot without a winner: NaN rows).
+ * Score.  A live row r of group g offers word w at
+ *     score = fp32( c - fp32( lambda * fp32(count_g(w)) ) ),      c = run_r + ((x - M_r) - ls_r)
+ * c exactly ovc_beam_search's candidate; the product is rounded, then the difference, never a fused multiply-add; with count 0 the
+ * score is c itself.  A frozen row offers word 0 at its running score and -999 for every other word, unpenalised.
+ * Winners.  Group g's k' winners are its best candidates by (score descending, flat index slot * V + word ascending), placed in the
+ * group's slots in rank order.  running takes the penalised score (the penalty accumulates, as in the group beam search of the
+ * transformers library); logp_out / all_logp_out stay the model's own log-probabilities.  Parent, history, alive flags, the
+ * ancestor table and the next input rows are written as by the plain step.
+ * Final order.  ovc_beam_search's: all k slots by running descending, the lower slot first, the first out_size returned.  slot_out
+ * [B][out_size] int32 receives the beam slot of each returned caption; its group is slot / k'.
+ * Consequences: G = 1 is ovc_beam_search for any lambda -- the same launches, graph entry and bits (plus the copy of the slots);
+ * lambda = 0 is G independent k'-beam searches; at step 0 with a large lambda the k words are the k best words of row 0.
+ * The decoder rows of a group are those of a search of k' beams, bit for bit: the search runs step 0 on a copy of row 0 per group (where
+ * max_len >= 2; the same bits; each group's first cache row and first ancestor are its own) and the decode self-attention on one group's rows at a time,
+ * so with lambda = 0 caption o of the result is caption o / G of ovc_beam_search at k' beams, ids and log-probabilities alike.
+ * ovc_beam_search_diverse: plain launches, all_logp_out as ovc_beam_search.  ovc_beam_search_diverse_graph: one captured graph from
+ * the second call; G and the bits of lambda are part of its key.  Workspace: ovc_beam_search_diverse_workspace_bytes (ovc_workspace_bytes'
+ * layout; 0: out of scope).
+ * OVC_EINVAL, nothing launched: G outside 1..k or not dividing k; lambda negative, NaN, infinite or above 1e30; precision != 0; a
+ * vocabulary of more than 16 384 words; a null slot_out; and everything ovc_beam_search refuses.
+ * Not covered: other diversity functions, a per-group lambda, groups under dropout, with a ban set, a prefix, in the early-exit forms,
+ * in an ensemble or when sampling.
+ * ovc_debug_beam_diverse_update: test entry, ONE step of the production kernel (the search's own routing: the diverse instance with
+ * G > 1, else the plain selection) on the inputs of ovc_debug_beam_constrained_update (width = 1 at t = 0, else k) plus G and lambda.
+ * scratch: ovc_debug_beam_diverse_update_bytes. */
+size_t ovc_beam_search_diverse_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int G, float lambda);
+int ovc_beam_search_diverse(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, int G,
+                            float lambda, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, int32_t* slot_out,
+                            float* all_logp_out, ovc_stream stream);
+int ovc_beam_search_diverse_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size, int G,
+                                  float lambda, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                  int32_t* slot_out, ovc_stream stream);
+size_t ovc_debug_beam_diverse_update_bytes(int B, int width, int V, int k, int T);
+int ovc_debug_beam_diverse_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B, int width,
+                                  int V, int k, int T, int t, int eos, int G, float lambda, void* scratch, size_t scratch_bytes,
+                                  int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out, float* row_lsum_out,
+                                  ovc_stream stream);
 
 /* Ensemble beam search: ONE search over the mean of the log-probabilities of M models (the meshed-memory authors'
  * TransformerEnsemble).  Members m = 0..M-1, 1 <= M <= OVC_MAX_ENSEMBLE, read the same features (and the call's boxes, where a

@@ -17,6 +17,7 @@ import collections
 import torch
 
 from . import constraints as _constraints
+from . import diverse as _diverse
 from . import prefix as _prefix
 from . import distill as _distill
 from . import dropout as _dropout
@@ -499,7 +500,8 @@ class BaseTransformer(Module):
         is the plain search's.  The defaults are the plain call, bit for bit.  Refused by name before any launch or draw: a bad
         option; active constraints with ``fused=False``, ``dropout=True``, an early-exit form, a precision other than 'f32' or a
         vocabulary of more than 16 384 words; and length penalty, repetition penalty, forced words (lexical constraints),
-        ``prefix_allowed_tokens_fn`` and diverse beam search, which the engine does not have.
+        ``prefix_allowed_tokens_fn``, which the engine does not have, and ``num_beam_groups`` / ``diversity_penalty``: diverse beam
+        search is a method of its own, ``diverse_beam_search``, and the keyword form stays refused.
 
         ``prefix`` (fused only; ``ovc_beam_search_prefix``; the rule is stated in ``include/ovc.h`` and
         mirrored by ``openviic_amd.prefix``): an int64 tensor ``(B, P)``, ``0 <= P <= max_len - 1``.  Image ``b`` emits
@@ -557,6 +559,43 @@ class BaseTransformer(Module):
         with self.statefulness(batch_size):
             self.encoder_features, self.encoder_padding_mask = self.encoder_forward(input_features)
             return searcher.apply(out_size, return_probs, **kwargs)
+
+    def diverse_beam_search(self, input_features, batch_size: int, beam_size: int, groups: int, diversity_penalty=0.5, out_size=None,
+                            return_probs=False, return_groups=False, **kwargs):
+        """Diverse beam search (Vijayakumar et al., 2016) on the HIP engine (``ovc_beam_search_diverse``; the
+        rule is stated in ``include/ovc.h`` and mirrored by ``openviic_amd.diverse``): ``beam_size`` beams in ``groups`` groups of
+        ``beam_size // groups`` slots.  At every step the groups are decoded in order, and a live row of a later group offers word
+        ``w`` at its plain score minus ``diversity_penalty`` times the number of earlier groups' winners of this step that took
+        ``w`` (Hamming diversity); the penalised score is the beam's running score from then on.  Returns ``(ids [B, out_size, T],
+        log_probs [B, out_size, T])`` in the plain search's final order -- ``out_size`` defaults to ``beam_size`` -- plus
+        ``all_log_probs [B, beam_size, T, V]`` with ``return_probs`` and ``groups [B, out_size]`` (int64, on the device: the group
+        each caption's beam slot belongs to) with ``return_groups``, in this order.  ``log_probs`` / ``all_log_probs`` are the
+        model's own; the result is plain tensors without gradient.  ``groups=1`` is ``beam_search`` for any penalty, bit for bit;
+        ``diversity_penalty=0`` is ``groups`` independent searches of ``beam_size // groups`` beams.
+
+        Refused by name before any launch and any random draw: a bad option (``groups`` outside ``1..beam_size`` or not dividing
+        it, ``beam_size`` above 8, a negative, NaN or infinite penalty or one above 1e30, ``out_size`` outside ``1..beam_size``);
+        ``fused=False`` or any other keyword (the host loop has no groups; dropout, constraints, a prefix and the early-exit
+        forms do not combine with groups); a precision other than 'f32'; more than 16 384 words; and a model in ``train()`` mode
+        with gradients enabled (no SCST through a penalised search: call ``eval()`` or use ``no_grad``)."""
+        for name in kwargs:
+            if name == "fused":
+                raise engine.native.OvcError("diverse_beam_search(fused=...): there is no such keyword -- the search runs on the engine "
+                                             "only, the host loop has no groups")
+            raise engine.native.OvcError("diverse_beam_search({}=...) is not covered -- groups combine with nothing but out_size, "
+                                         "return_probs and return_groups".format(name))
+        k, G, _ = _diverse.check(beam_size, groups, diversity_penalty)
+        eng = self._fused_engine()
+        eng.check_diverse(k, G, diversity_penalty)
+        if out_size is not None and not 1 <= int(out_size) <= k:
+            raise engine.native.OvcError("diverse_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise engine.native.OvcError("diverse_beam_search: the model is in train() mode with gradients enabled -- there is no "
+                                         "SCST through a penalised search; call model.eval() or use torch.no_grad()")
+        feats, boxes = self._engine_inputs(input_features)
+        out = eng.diverse_beam_search(feats, boxes, batch_size, k, G, diversity_penalty, out_size=out_size, return_probs=return_probs)
+        result = (out[0], out[1]) + ((out[3],) if return_probs else ())
+        return result + ((out[2].long() // (k // G),) if return_groups else ())
 
     def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False, temperature=1.0,
                top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0, banned_words=None):

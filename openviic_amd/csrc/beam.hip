@@ -273,6 +273,18 @@ __global__ __launch_bounds__(kFusedThreads) void beam_prefix_update_kernel(BeamU
 #include "bodies/beam_fused_update.inc"
 }
 
+// Diverse selection (ovc_beam_search_diverse, include/ovc.h: the rule): the fused selection and bookkeeping of one image whose k
+// beams are G groups of k / G slots.  Phase A once for all rows; then the groups one after another inside the workgroup, each with
+// its own bound, hot blocks, survivors and ranks over its own rows, a later group paying lambda per earlier winner of the same word
+// (the table of at most 7 (word, count) pairs in LDS; a block holding one keeps its upper bound and feeds no lower bound).  Its own
+// body: the plain instances' text does not change.  LDS: the plain instance's 14 152 bytes + 68 (14 220).  Integer LDS atomics only where the
+// lists are appended to (ranks come from a strict total order), no float atomics.
+__global__ __launch_bounds__(kFusedThreads) void beam_diverse_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                            int stats_ld, const float* __restrict__ running_in,
+                                                                            long ld_row, long ld_word, int G, float lambda) {
+#include "bodies/beam_diverse_update.inc"
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Ensemble selection (ovc_ensemble_beam_search, include/ovc.h: the rule): one search over the mean of kM members' log-probabilities.
 // The mean of a word, in the rule's order: lp_0 | lp_0 + lp_1 | (lp_0 + lp_1) + lp_2 | (lp_0 + lp_1) + (lp_2 + lp_3), then a true
@@ -579,6 +591,24 @@ int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& f, c
     if (p.T < 1 || p.t < 0 || p.t >= p.T || !pre.ids || !pre.len || pre.P < 1 || pre.P > p.T - 1) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_prefix_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
                        f.ld_row, f.ld_word, pre);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+bool ovc_beam_diversity_ok(int k, int G, float lambda) {
+    return k >= 1 && k <= kMaxK && G >= 1 && G <= k && k % G == 0 && lambda >= 0.0f && lambda <= 1e30f;      // NaN fails both bounds
+}
+
+// The diverse step: ovc_beam_fused_update_launch's arguments plus the groups and the strength, by value (baked into a captured graph).
+// No gated instance: the early-exit forms are out of the diverse search's scope.
+int ovc_beam_diverse_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, int G, float lambda, int B,
+                                   hipStream_t stream) {
+    if (!fused_tail_ok(p, f, B) || !running_in || p.V < p.k || p.alive_count || !ovc_beam_diversity_ok(p.k, G, lambda)) return OVC_EINVAL;
+    // the groups' rows are the image's one row at step 0 (or its G copies, one per group) and each group's own slots later: the
+    // kernel indexes rows with this
+    if (p.T < 1 || p.t < 0 || p.t >= p.T || (p.t == 0 ? p.width != 1 && p.width != G : p.width != p.k)) return OVC_EINVAL;
+    hipLaunchKernelGGL(beam_diverse_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
+                       f.ld_row, f.ld_word, G, lambda);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -305,6 +305,12 @@ struct BeamPrefix {
 // takes the plain step; p.alive_count must be nullptr.
 int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamPrefix& pre, int B,
                                   hipStream_t stream);
+// The diverse search's options (include/ovc.h, ovc_beam_search_diverse): G groups dividing k, a finite strength in [0, 1e30].
+bool ovc_beam_diversity_ok(int k, int G, float lambda);
+// ovc_beam_fused_update_launch for G groups of k / G slots with the Hamming penalty lambda; p.width is 1 at p.t == 0, else p.k;
+// p.alive_count must be nullptr.
+int ovc_beam_diverse_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, int G, float lambda, int B,
+                                   hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
 // log-probabilities and the bookkeeping, one launch.  One argument block, by value: p is member 0's -- the shared beam state, and
 // member 0's embedding tables / next_x / d_model for the next step's input rows -- and every member's tail, logits, embedding

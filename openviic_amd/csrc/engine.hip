@@ -1021,6 +1021,14 @@ struct SearchCall {
     // workspace outside any captured body.  prefix_P = 0 (no table, or every length 0): the plain search.  A sizer or predicate
     // states prefix_P alone.
     int prefix_P; const int32_t* prefix_ids; const int32_t* prefix_len;
+    // Diverse search (ovc_beam_search_diverse): groups > 1 groups of k / groups slots and the Hamming penalty's strength; one group is
+    // the plain call: groups stays 0.  slot_out: the caller's [B][out_size], the beam slot of each returned caption, or nullptr.
+    int groups; float diversity; int32_t* slot_out;
+    bool diverse() const { return groups != 0; }
+    // The rows of an image at step t.  Step 0 has one row per image; a diverse search runs it once per group (the same <bos> row, the
+    // same bits), so that every group has a first cache row and a first ancestor of its own and is a search of k / groups beams
+    // from its first step on (a search of one step, T = 1, has no later step to prepare: one row).
+    int step_width(int t, int T) const { return t > 0 ? k : diverse() && T > 1 ? groups : 1; }
     bool prefixed() const { return prefix_P != 0; }
     bool ensemble() const { return ens_M > 1; }
     bool constrained() const { return cons.active(); }
@@ -1042,7 +1050,8 @@ bool search_ok(const ovc_model* m, const SearchCall& c);
 // nothing else in the call.
 bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
     if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
-    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
+    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() ||
+        (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
         return false;
     SearchCall alone = c;
     alone.ens_M = 0;
@@ -1073,6 +1082,12 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
     // graph, and room for one free step behind the longest prefix
     if (c.prefixed() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan || c.constrained() ||
                          (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.prefix_P < 0 || c.prefix_P > m->max_len - 1))
+        return false;
+    // groups: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, no ban set, no prefix, plain launches or the
+    // whole-search graph, and the options' own scope
+    if (c.diverse() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan || c.constrained() || c.prefixed() ||
+                        (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.groups < 2 ||
+                        !ovc_beam_diversity_ok(c.k, c.groups, c.diversity)))
         return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
@@ -1128,6 +1143,7 @@ struct DecoderPass {
     float* part;                                    // the AddNorms' K-split partial products (Workspace::part); nullptr: whole products
     bool name_sites;                                // the dropout sites dec_site(l, j) are named (else -1: every launch the plain one)
     int t, width, R; const int32_t* anc;            // Step: step t of B*width rows in caches of R slots per position, its ancestor table
+    int self_width;                                 // Step: the rows that share a self-attention key list (width; a diverse search: one group's)
     int S, T; bool keep_maps;                       // Sequence: S sequences of T positions per image; ForwardCall::keep_maps
     int site(int l, int j) const { return name_sites ? dec_site(l, j) : -1; }
 };
@@ -1151,7 +1167,7 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
         DecodeSelfArgs sa{};
         sa.q = b.q; sa.ldq = hk; sa.pos_stride = (size_t)p.R * hk; sa.ldkv = hk;
         sa.kcache = b.k - p.t * sa.pos_stride; sa.vcache = b.v - p.t * sa.pos_stride;     // b.k, b.v: the cache rows of step t
-        sa.anc = p.anc; sa.anc_ld = m->max_len; sa.padflag = w.padflag; sa.pad_ld = p.R; sa.t = p.t; sa.width = p.width;
+        sa.anc = p.anc; sa.anc_ld = m->max_len; sa.padflag = w.padflag; sa.pad_ld = p.R; sa.t = p.t; sa.width = p.self_width;
         sa.h = m->heads; sa.dk = m->d_k; sa.dv = m->d_v; sa.out = b.att; sa.ldo = hv;
         sa.part_o = w.sa_part_o; sa.part_ml = w.sa_part_ml;
         if (!(debug_skip() & 2)) RUN(ovc_decode_self_attention(sa, rows, s, e.gate));
@@ -1260,7 +1276,7 @@ int run_step_rows(Engine& e, Workspace& w, const SearchCall& c, int t, StepRows*
     const int B = c.B, N = c.N, k = c.k;
     hipStream_t s = e.stream;
     const int d = m->d_model, hk = m->heads * m->d_k, hv = m->heads * m->d_v, T = m->max_len;
-    const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
+    const int R = B * k, width = c.step_width(t, T), rows = B * width;
     const int cur = t & 1;
     uint8_t* padflag_t = w.padflag + (size_t)t * R;
     // ovc_beam_search_dropout: this step's rows key the decoder sites' masks; without a plan no site is on and the launches are
@@ -1282,6 +1298,9 @@ int run_step_rows(Engine& e, Workspace& w, const SearchCall& c, int t, StepRows*
     }
     DecoderPass pass{DecoderPass::Step, rows, B, N, padflag_t, w.part, keyed};
     pass.t = t; pass.width = width; pass.R = R; pass.anc = w.anc[cur];
+    // a diverse search: a group's beams descend from that group's alone, and the decode self-attention lists the keys of the rows
+    // it is given together -- per group, so that a group's decoder rows are those of a search of its own width, bit for bit
+    pass.self_width = c.diverse() ? (t == 0 ? 1 : k / c.groups) : width;
     const float* x = w.x;         // every layer reads and writes the one buffer
     for (int l = 0; l < m->n_dec; ++l) {
         // the layer's keys / values go to its cache [L][T][R][h*dk|h*dv], the rows of step t
@@ -1341,7 +1360,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     e.gate = c.form == SearchForm::Gated && t > 0 ? w.alive_count + (t - 1) : nullptr;
     hipStream_t s = e.stream;
     const int d = m->d_model, T = m->max_len;
-    const int R = B * k, width = t == 0 ? 1 : k, rows = B * width;
+    const int R = B * k, width = c.step_width(t, T), rows = B * width;
     const int cur = t & 1, nxt = cur ^ 1;
     StepRows sr{};
     TRY(run_step_rows(e, w, c, t, &sr));
@@ -1410,11 +1429,20 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_beam_constrained_update_launch(bu, tail, w.running[cur], c.cons, B, s));
         else if (c.prefixed())     // the one branch of a prefix step: the selection reads the staged table
             RUN(ovc_beam_prefix_update_launch(bu, tail, w.running[cur], BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P}, B, s));
+        else if (c.diverse())      // the one branch of a diverse step: the groups selected in order, under the Hamming penalty
+            RUN(ovc_beam_diverse_update_launch(bu, tail, w.running[cur], c.groups, c.diversity, B, s));
         else if (!(debug_skip() & 8))
             RUN(ovc_beam_fused_update_launch(bu, tail, w.running[cur], B, s, e.gate));
-        if (return_probs)     // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
-            RUN(ovc_masked_logp_launch(w.logits, tail.ld_row, tail.ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab,
-                                       w.all_buf + (size_t)t * R * m->vocab, s));
+        if (return_probs) {   // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
+            // step 0 is stored as one row per image: a diverse search's rows of step 0 (a copy per group) are staged in the block of
+            // step 1, which that step overwrites, and every image's first copy is kept (width > 1 at step 0 only where max_len >= 2)
+            const bool staged = t == 0 && width > 1;
+            float* all_t = w.all_buf + (size_t)(staged ? 1 : t) * R * m->vocab;
+            RUN(ovc_masked_logp_launch(w.logits, tail.ld_row, tail.ld_word, w.row_max, w.row_lsum, w.alive[cur], rows, m->vocab, all_t, s));
+            if (staged && hipMemcpy2DAsync(w.all_buf, sizeof(float) * m->vocab, all_t, sizeof(float) * m->vocab * width,
+                                           sizeof(float) * m->vocab, B, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return OVC_ELAUNCH;
+        }
         return OVC_OK;
     }
     BeamSelectArgs bs{};
@@ -1423,7 +1451,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
-    if (c.prefixed()) return OVC_EINVAL;       // search_ok: the fused tail; the two-pass pair knows no prefix
+    if (c.prefixed() || c.diverse()) return OVC_EINVAL;       // search_ok: the fused tail; the two-pass pair knows no prefix and no groups
     RUN(ovc_beam_select_launch(bs, B, s, e.gate));
     RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
@@ -1630,6 +1658,7 @@ enum class GraphKind {
     TrainDistill,       // ovc_forward_backward_distill, with or without dropout (k = T, out_size = 1; the weight in the hash)
     PrefixSearch,       // ovc_beam_search_prefix_graph with a table that forces a word (as Search; P in the hash, the table's contents
                         // in the workspace)
+    DiverseSearch,      // ovc_beam_search_diverse_graph with more than one group (as Search; G and the bits of lambda in the hash)
     ForwardMaps,        // a ForwardCall with maps, ovc_attention_maps (forward_graph_key: k = T, out_size = S): the scoring body
                         // over B*S*T rows plus the map launches
 };
@@ -1802,6 +1831,11 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
         const int P = c.prefix_P;
         return GraphKey{GraphKind::PrefixSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&P, sizeof(P)), workspace, c.B, c.N, c.k, c.out_size};
     }
+    if (c.diverse()) {        // G and the strength's bits are baked into every step's launch
+        const struct { int G; float lambda; } options{c.groups, c.diversity};
+        return GraphKey{GraphKind::DiverseSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N, c.k,
+                        c.out_size};
+    }
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1972,6 +2006,14 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     }
     if (c.all_logp_out) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, c.B, c.k, T, m->vocab, c.all_logp_out, e.stream));
     if (c.steps_run_out) *c.steps_run_out = steps_run;
+    // the beam slot of each returned caption: the first out_size entries of every image's final order, a copy of this call alone
+    if (c.slot_out) {
+        const hipError_t rc = c.out_size == c.k
+            ? hipMemcpyAsync(c.slot_out, w.order, sizeof(int32_t) * c.B * c.k, hipMemcpyDeviceToDevice, e.stream)
+            : hipMemcpy2DAsync(c.slot_out, sizeof(int32_t) * c.out_size, w.order, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size, c.B,
+                               hipMemcpyDeviceToDevice, e.stream);
+        if (rc != hipSuccess) return OVC_ELAUNCH;
+    }
     return write_search_slots(e, w, c, steps_run);
 }
 }  // namespace
@@ -2205,6 +2247,92 @@ extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* 
     bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
     bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
     if (any) TRY(ovc_beam_prefix_update_launch(bu, tail, running, BeamPrefix{ids_dev, len_dev, P}, B, s));      // run_decode_step's routing
+    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
+    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Diverse search (include/ovc.h: the rule).  The k beams in G groups under a Hamming penalty; one group is the plain call, launch for
+// launch (the same SearchCall, hence the same graph key and workspace), plus the copy of the slots.
+// ---------------------------------------------------------------------------------------------
+// The call's options as the SearchCall takes them; false: G outside 1..k or not dividing k, lambda negative, not finite or above 1e30.
+static bool diversity_from(int k, int G, float lambda, SearchCall* c) {
+    if (!ovc_beam_diversity_ok(k, G, lambda)) return false;
+    if (G > 1) { c->groups = G; c->diversity = lambda; }
+    return true;
+}
+
+extern "C" size_t ovc_beam_search_diverse_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int G, float lambda) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (!model_ok(m) || !diversity_from(k, G, lambda, &c)) return 0;
+    // one group runs the plain launches, but the call is the diverse search's: its scope holds for every G
+    if (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks) return 0;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+static int run_diverse(const ovc_model* m, SearchCall c, int G, float lambda, int32_t* slot_out, const float* features, const float* boxes,
+                       void* workspace, size_t workspace_bytes, ovc_stream stream) {
+    if (!model_ok(m) || !slot_out || !diversity_from(c.k, G, lambda, &c)) return OVC_EINVAL;
+    if (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks) return OVC_EINVAL;
+    c.slot_out = slot_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_diverse(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                       int G, float lambda, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                       int32_t* slot_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    return run_diverse(m, c, G, lambda, slot_out, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_diverse_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                             int out_size, int G, float lambda, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                             float* logp_out, int32_t* slot_out, ovc_stream stream) {
+    return run_diverse(m, SearchCall{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out}, G, lambda, slot_out, features, boxes, workspace,
+                       workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the diverse one with more
+// than one group, else the plain one -- on caller-given inputs as ovc_debug_beam_constrained_update takes them, plus G and lambda.
+extern "C" size_t ovc_debug_beam_diverse_update_bytes(int B, int width, int V, int k, int T) {
+    return ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
+}
+
+extern "C" int ovc_debug_beam_diverse_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B,
+                                             int width, int V, int k, int T, int t, int eos, int G, float lambda, void* scratch,
+                                             size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
+                                             float* row_max_out, float* row_lsum_out, ovc_stream stream) {
+    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
+        return OVC_EINVAL;
+    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
+        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (!ovc_beam_diversity_ok(k, G, lambda)) return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_beam_diverse_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const int rows = B * width, ldt = (rows + 3) & ~3;
+    const size_t Rk = (size_t)B * k;
+    Bump a{reinterpret_cast<char*>(scratch), 0};
+    float* logits_t = a.take<float>((size_t)V * ldt);
+    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
+    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
+    tail.stats = stats;
+    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
+    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
+    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
+    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
+        return OVC_ELAUNCH;
+    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
+    BeamUpdateArgs bu{};
+    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
+    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
+    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
+    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
+    if (G > 1) TRY(ovc_beam_diverse_update_launch(bu, tail, running, G, lambda, B, s));      // run_decode_step's routing
     else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
     return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
 }

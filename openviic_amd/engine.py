@@ -22,6 +22,7 @@ import torch
 
 from . import attention_maps as _maps
 from . import constraints as _constraints
+from . import diverse as _diverse
 from . import distill as _distill
 from . import dropout as _dropout
 from . import native
@@ -631,6 +632,9 @@ class CaptionEngine:
         "prefix": ("ovc_prefix_workspace_bytes", "engine configuration", "beam", {
             "plain": ("ovc_beam_search_prefix", ("out_size", "prefix", "prefix_len", "P", *_RESULTS, "everything", "stream")),
             "graph": ("ovc_beam_search_prefix_graph", ("out_size", "prefix", "prefix_len", "P", *_RESULTS, "stream"))}),
+        "diverse": ("ovc_beam_search_diverse_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search_diverse", ("out_size", "groups", "penalty", *_RESULTS, "slot", "everything", "stream")),
+            "graph": ("ovc_beam_search_diverse_graph", ("out_size", "groups", "penalty", *_RESULTS, "slot", "stream"))}),
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
@@ -643,7 +647,7 @@ class CaptionEngine:
     }
 
     def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None, constraints=None, prefix=None):
+                    options=None, constraints=None, prefix=None, diverse=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
@@ -653,12 +657,16 @@ class CaptionEngine:
         (``sequence_backward(dropout=..., slots=...)`` recomputes under them).  ``options``: what ``sample_options`` returned --
         the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw.  ``constraints``: what
         ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search.  ``prefix``: what
-        ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None."""
+        ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None.  ``diverse``: the diverse search's
+        ``(G, penalty)`` as ``diverse.check`` returned them, or None; ``slots`` is then int32 ``(B, out_size)``, the beam slot of each
+        returned caption."""
         kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
         if constraints:
             kind = "constrained"
         if prefix:
             kind = "prefix"
+        if diverse:
+            kind = "diverse"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -674,10 +682,12 @@ class CaptionEngine:
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
         if form == "graph" and not self.use_graph and kind != "masked":
             form = "plain"
-        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else options or ())
+        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else diverse or options or ())
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
+        if diverse:
+            slots = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
         everything = torch.empty(B, width, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
         steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
@@ -685,12 +695,15 @@ class CaptionEngine:
         if not self.use_graph and (form == "device" or table_drop is not None):
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         args = {name: None if t is None else t.data_ptr() for name, t in (
-            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", slots), ("steps", steps), ("seed", seed))}
+            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", slots), ("steps", steps), ("seed", seed),
+            ("slot", slots if diverse else None))}
         args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
         if table_drop is not None:
             args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
         if options:
             args.update(zip(("temperature", "top_k", "top_p"), options))
+        if diverse:
+            args.update(groups=diverse[0], penalty=diverse[1])
         if constraints:
             n, L, banned = constraints
             args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
@@ -802,6 +815,34 @@ class CaptionEngine:
         if out_size == 1:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
+
+    def check_diverse(self, beam_size, groups, diversity_penalty):
+        """The refusals of a diverse search that need no input, each naming its argument: callers run them before any launch.
+        Returns ``(k, G, penalty)`` as ``openviic_amd.diverse.check`` normalises them."""
+        checked = _diverse.check(beam_size, groups, diversity_penalty)
+        what = "diverse_beam_search"
+        if self.precision != "f32":
+            raise native.OvcError(what + ": precision={!r} is not covered -- groups run in 'f32' only".format(self.precision))
+        if self.desc.vocab > 16384:
+            raise native.OvcError(what + ": a vocabulary of {} words is not covered -- at most 16384".format(self.desc.vocab))
+        return checked
+
+    def diverse_beam_search(self, features, boxes, batch_size, beam_size, groups, diversity_penalty=0.5, out_size=None,
+                            return_probs=False):
+        """Diverse beam search (``ovc_beam_search_diverse``; DESIGN.md section 2x, ``openviic_amd.diverse`` mirrors the rule): the
+        ``beam_size`` beams in ``groups`` groups, decoded in order at every step, a later group paying ``diversity_penalty`` for
+        every earlier winner of the step that took the same word.  Returns ``(ids, logp, slots)`` -- ``(B, out_size, T)`` twice and
+        int32 ``(B, out_size)``, the beam slot of each returned caption (its group: ``slot // (beam_size // groups)``) -- plus
+        ``everything (B, beam_size, T, V)`` with ``return_probs``.  ``out_size`` defaults to ``beam_size``.  One group is the plain
+        search, bit for bit and graph entry for graph entry.  The whole-search graph, or plain launches with ``return_probs`` or
+        without ``use_graph``; no early-exit form.  Refused by name before any launch: a bad option, a split precision, more than
+        16 384 words."""
+        k, G, lam = self.check_diverse(beam_size, groups, diversity_penalty)
+        out_size = k if out_size is None else int(out_size)
+        if not 1 <= out_size <= k:
+            raise native.OvcError("diverse_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
+        ids, logp, everything, slots = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, diverse=(G, lam))
+        return (ids, logp, slots, everything) if return_probs else (ids, logp, slots)
 
     @staticmethod
     def sample_options(temperature=1.0, top_k=None, top_p=None):

@@ -257,6 +257,15 @@ SIGNATURES = {
     "ovc_debug_beam_prefix_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                              POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_beam_search_diverse_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int, c_int, c_float]),
+    "ovc_beam_search_diverse": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_beam_search_diverse_graph": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                              c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_beam_diverse_update_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ovc_debug_beam_diverse_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "ovc_ensemble_ok": (c_int, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int]),
     "ovc_ensemble_workspace_bytes": (c_size_t, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int, c_int]),
     "ovc_ensemble_beam_search": (c_int, [POINTER(POINTER(Model)), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
@@ -311,7 +320,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_cross_attention_maps", "ovc_debug_cross_attention_maps", "ovc_attention_maps_workspace_bytes",
                  "ovc_attention_maps",
                  "ovc_search_prefix_ok", "ovc_prefix_workspace_bytes", "ovc_beam_search_prefix", "ovc_beam_search_prefix_graph",
-                 "ovc_debug_beam_prefix_update_bytes", "ovc_debug_beam_prefix_update")
+                 "ovc_debug_beam_prefix_update_bytes", "ovc_debug_beam_prefix_update",
+                 "ovc_beam_search_diverse_workspace_bytes", "ovc_beam_search_diverse", "ovc_beam_search_diverse_graph",
+                 "ovc_debug_beam_diverse_update_bytes", "ovc_debug_beam_diverse_update")
 
 _lib = None
 

@@ -946,6 +946,40 @@ size_t ovc_caption_metrics_bytes(int B, int T, int max_refs);
 int ovc_caption_metrics(const ovc_eval_corpus* c, const int64_t* ids, const int32_t* rows, int B, int T, int64_t* clean_out,
                         int32_t* stats_out, size_t stats_bytes, ovc_stream stream);
 
+/* A caption set judged from its own members: consensus (minimum-Bayes-risk) reranking under CIDEr-D and the integer counts of the
+ * diversity metrics Div-n and mBLEU (openviic_amd/consensus.py).  Appended to ABI 8; no struct changes.  ids [B][S][T] (int64) are
+ * S candidate captions per image, decoded as ovc_cider_reward decodes (clamped into [0, vocab), cut at the first eos_idx, the four
+ * specials dropped).  c supplies only the idf side: hash_key / hash_idf / hash_size, ref_len, sigma, vocab and the special ids; its
+ * reference tables are not read.  With i, j candidates of image b:
+ *   pair_out[b][i][j]   (fp32) 10 * CIDEr-D of hypothesis i against the single reference j, what ovc_cider_reward gives when
+ *                       caption j is the image's only reference: min(w, r) r summed per order over i's distinct n-grams, divided
+ *                       by the norms, times the Gaussian of the difference of BIGRAM counts (the reference's length quirk),
+ *                       the mean over the orders, times 10, rounded once.  pair_out[b][i][i] = 0.
+ *   score_out[b][i]     (fp32) 10 * CIDEr-D of i against all its siblings j != i as references: per order the un-rounded terms
+ *                       are added over ascending j, then ((s0 + s1) + s2) + s3, / 4, / (S - 1), * 10, rounded once -- the
+ *                       operation order of the reference's CiderScorer with S - 1 references.  0 when S = 1.
+ *   best_out[b]         the argmax of score_out[b][:] as fp32; a tie goes to the lower index
+ *   stats_out[b][i][0..3]  correct[n] = sum over i's distinct n-grams of min(tf_i, max over j != i of tf_j): BLEU's clipped counts
+ *   stats_out[b][i][4..7]  guess[n] = max(0, L - n), n 0-based;  [8] testlen = L;  [9] reflen, the sibling length closest to L (a
+ *                          tie goes to the shorter; 0 when S = 1)
+ *   image_out[b][0..3]  distinct[n]: distinct n-grams over the whole set (a key of i counts when no j < i holds it)
+ *   image_out[b][4..7]  total[n]: the sum of guess[n];  [8] the words of the set;  [9] its empty captions
+ * Two launches.  Vectors: one wave per caption sorts its packed n-gram keys in LDS and writes the distinct keys ascending, their
+ * term frequencies, tf-idf weights, four norms, L and the bigram count to the workspace.  Pairs: one workgroup per image, one wave
+ * per caption; each distinct key of i binary-searches every sibling's entries; the waves meet once through LDS for the pick and
+ * the image's totals (integers added in ascending caption order).  float64 sums in a fixed order (lane partials over ascending
+ * index, one butterfly); every output element is written by one lane with a plain vector store, no atomics, no allocation, no
+ * synchronisation: capturable, the same bits on every call, stream and replay.  The workspace needs no initialisation and must be
+ * 8-byte aligned.  ovc_caption_set_workspace_bytes: its bytes, 0 when the shape is refused.  OVC_EINVAL (nothing launched): a
+ * null pointer, B < 1, S outside 1..OVC_MAX_BEAM, T outside 1..OVC_MAX_LEN, vocab outside 1..65535, B*S*T >= 2^31, a hash_size
+ * that is no power of two, a misaligned workspace; OVC_EWORKSPACE: workspace_bytes below the sizer's answer. */
+#define OVC_SET_STATS 10
+#define OVC_SET_IMAGE 10
+size_t ovc_caption_set_workspace_bytes(int B, int S, int T);
+int ovc_caption_set(const ovc_cider* c, const int64_t* ids, int B, int S, int T, float* pair_out, float* score_out,
+                    int32_t* best_out, int32_t* stats_out, int32_t* image_out, void* workspace, size_t workspace_bytes,
+                    ovc_stream stream);
+
 /* Optional device timing of the engine's GEMM launches (bench.py's roofline leg).  While enabled,
  * every GEMM launch carries a pair of hipEvents on its launch stream (hipExtLaunchKernelGGL start /
  * stop events, i.e. the dispatch's own begin / end timestamps, the quantity rocprofv3 reports as

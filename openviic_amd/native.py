@@ -128,6 +128,8 @@ GEMM_PLAIN, GEMM_GATED, GEMM_DROPOUT, GEMM_SCORING, GEMM_PLANES_DIRECT = 0, 1, 2
 
 OVC_METRIC_STATS = 12       # int32 per caption in front of the per-reference LCS lengths (include/ovc.h)
 OVC_METRIC_MAX_REFS = 4096
+OVC_SET_STATS = 10          # int32 per caption of ovc_caption_set: correct[4], guess[4], testlen, reflen
+OVC_SET_IMAGE = 10          # int32 per image: distinct[4], total[4], words, empty captions
 
 ENC_PLAIN, ENC_MULTILEVEL, ENC_GEOMETRIC, ENC_CROSS_LEVEL = 0, 1, 2, 3
 DEC_PLAIN, DEC_MESHED = 0, 1
@@ -284,6 +286,9 @@ SIGNATURES = {
     "ovc_scst_advantage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ovc_caption_metrics_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ovc_caption_metrics": (c_int, [POINTER(EvalCorpus), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ovc_caption_set_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ovc_caption_set": (c_int, [POINTER(Cider), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
     "ovc_debug_decode_self_partial_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ovc_debug_decode_self_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_int,
                                                 c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
@@ -322,7 +327,8 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_search_prefix_ok", "ovc_prefix_workspace_bytes", "ovc_beam_search_prefix", "ovc_beam_search_prefix_graph",
                  "ovc_debug_beam_prefix_update_bytes", "ovc_debug_beam_prefix_update",
                  "ovc_beam_search_diverse_workspace_bytes", "ovc_beam_search_diverse", "ovc_beam_search_diverse_graph",
-                 "ovc_debug_beam_diverse_update_bytes", "ovc_debug_beam_diverse_update")
+                 "ovc_debug_beam_diverse_update_bytes", "ovc_debug_beam_diverse_update",
+                 "ovc_caption_set_workspace_bytes", "ovc_caption_set")
 
 _lib = None
 

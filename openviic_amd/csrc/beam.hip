@@ -219,6 +219,15 @@ constexpr int kBanWords = 512;                           // the constrained inst
 static_assert(kBanWords == 512 && OVC_MAX_BANNED <= 64, "one bitmap word per block of the fused tail, one lane per banned id");
 static_assert(kFusedVocabBlocks == 2 * 64 * kFusedPairs && kFusedVocabBlocks == kBanWords, "fused_tail_ok admits what one wave loads");
 
+// What the bodies whose candidate is one model's logit (beam_fused_update.inc, beam_diverse_update.inc) give the shared pieces
+// (bodies/fused_select_*.inc) in the same words: what the words of row i share in the exhaustive rounds, and phase D's
+// log-probability of word wd of row par from the winner's carried logit, or from the logit read as the two-pass path reads it.
+#define FUSED_SELECT_ROW(i)                                       \
+    const float* x = p.logits + (size_t)(b * W + i) * ld_row;     \
+    const float mi = rowM[i], li = rowLs[i]
+#define FUSED_SELECT_LOGP(own, par, wd) \
+    ((((own) ? win_x[tid] : p.logits[(size_t)(b * W + par) * ld_row + (size_t)wd * ld_word]) - rowM[par]) - rowLs[par])
+
 // 512 threads per image: wave w < width owns beam row w through phases A and B (no workgroup-level reduction), then all
 // eight waves gather the hot blocks and wave 0 ranks the survivors in registers.  One body for the four instances: the plain and
 // the gated kernel compile it without a ban set (kBan = false: no constraints among their arguments, nothing of them in their code)
@@ -284,6 +293,8 @@ __global__ __launch_bounds__(kFusedThreads) void beam_diverse_update_kernel(Beam
                                                                             long ld_row, long ld_word, int G, float lambda) {
 #include "bodies/beam_diverse_update.inc"
 }
+#undef FUSED_SELECT_ROW
+#undef FUSED_SELECT_LOGP
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Ensemble selection (ovc_ensemble_beam_search, include/ovc.h: the rule): one search over the mean of kM members' log-probabilities.
@@ -544,19 +555,6 @@ static bool fused_tail_ok(const BeamUpdateArgs& p, const FusedTail& f, int B) {
     return f.ld_row > 0 && f.ld_word > 0;
 }
 
-int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, int B, hipStream_t stream,
-                                 const int32_t* gate) {
-    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k) return OVC_EINVAL;
-    if (gate)
-        hipLaunchKernelGGL(beam_fused_update_kernel_gated, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
-                           f.ld_row, f.ld_word, gate);
-    else
-        hipLaunchKernelGGL(beam_fused_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
-                           f.ld_row, f.ld_word);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    return OVC_OK;
-}
-
 bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k, int eos, int pad) {
     if (c.ngram < 0 || c.ngram > OVC_MAX_LEN || c.min_length < 0 || c.min_length > max_len - 1) return false;
     if (c.n_banned < 0 || c.n_banned > OVC_MAX_BANNED) return false;
@@ -568,50 +566,57 @@ bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k
     return (long)V - c.n_banned - 1 - max_len >= k;
 }
 
-// The constrained step: ovc_beam_fused_update_launch's arguments plus the constraints, by value (baked into a captured graph).
-// No gated instance: the early-exit forms are out of the constrained search's scope.
-int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const BeamConstraints& cons,
-                                       int B, hipStream_t stream) {
-    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || p.alive_count) return OVC_EINVAL;
-    // the staged histories and the bitmap are sized for these: anything beyond would not fit the workgroup's LDS
-    if (p.T < 1 || p.T > OVC_MAX_LEN || p.t < 0 || p.t >= p.T || !p.hist_in) return OVC_EINVAL;
-    if (cons.ngram < 0 || cons.min_length < 0 || cons.n_banned < 0 || cons.n_banned > OVC_MAX_BANNED) return OVC_EINVAL;
-    for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
-    hipLaunchKernelGGL(beam_constrained_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
-                       f.ld_row, f.ld_word, cons);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    return OVC_OK;
-}
-
-// The prefix step: ovc_beam_fused_update_launch's arguments plus the table's device addresses (the contents are read by the kernel).
-// No gated instance: the early-exit forms are out of the prefix search's scope.
-int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const BeamPrefix& pre, int B,
-                                  hipStream_t stream) {
-    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || p.alive_count) return OVC_EINVAL;
-    if (p.T < 1 || p.t < 0 || p.t >= p.T || !pre.ids || !pre.len || pre.P < 1 || pre.P > p.T - 1) return OVC_EINVAL;
-    hipLaunchKernelGGL(beam_prefix_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
-                       f.ld_row, f.ld_word, pre);
-    OVC_RETURN_IF_LAUNCH_FAILED();
-    return OVC_OK;
-}
-
 bool ovc_beam_diversity_ok(int k, int G, float lambda) {
     return k >= 1 && k <= kMaxK && G >= 1 && G <= k && k % G == 0 && lambda >= 0.0f && lambda <= 1e30f;      // NaN fails both bounds
 }
 
-// The diverse step: ovc_beam_fused_update_launch's arguments plus the groups and the strength, by value (baked into a captured graph).
-// No gated instance: the early-exit forms are out of the diverse search's scope.
-int ovc_beam_diverse_update_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, int G, float lambda, int B,
-                                   hipStream_t stream) {
-    if (!fused_tail_ok(p, f, B) || !running_in || p.V < p.k || p.alive_count || !ovc_beam_diversity_ok(p.k, G, lambda)) return OVC_EINVAL;
-    // the groups' rows are the image's one row at step 0 (or its G copies, one per group) and each group's own slots later: the
-    // kernel indexes rows with this
-    if (p.T < 1 || p.t < 0 || p.t >= p.T || (p.t == 0 ? p.width != 1 && p.width != G : p.width != p.k)) return OVC_EINVAL;
-    hipLaunchKernelGGL(beam_diverse_update_kernel, dim3(B), dim3(kFusedThreads), 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in,
-                       f.ld_row, f.ld_word, G, lambda);
+// The fused selection of a step, one launch: the instance the options name -- constrained, else prefix, else diverse, else the plain
+// one or its gated form.  The options reach the kernel by value (baked into a captured graph); of a prefix table only the device
+// addresses do, the contents are read by the kernel.  The early-exit forms (p.alive_count, the gate) are the plain instance's alone.
+int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const FusedSelectOptions& o, int B,
+                                 hipStream_t stream) {
+    const BeamConstraints& cons = o.cons;
+    const BeamPrefix& pre = o.prefix;
+    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0;
+    if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || (!plain && (p.alive_count || o.gate))) return OVC_EINVAL;
+    if (!plain && (p.T < 1 || p.t < 0 || p.t >= p.T)) return OVC_EINVAL;
+    const dim3 grid(B), block(kFusedThreads);
+    if (cons.active()) {
+        // the staged histories and the bitmap are sized for these: anything beyond would not fit the workgroup's LDS
+        if (p.T > OVC_MAX_LEN || !p.hist_in) return OVC_EINVAL;
+        if (cons.ngram < 0 || cons.min_length < 0 || cons.n_banned < 0 || cons.n_banned > OVC_MAX_BANNED) return OVC_EINVAL;
+        for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
+        hipLaunchKernelGGL(beam_constrained_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, cons);
+    } else if (pre.P != 0) {
+        if (!pre.ids || !pre.len || pre.P < 1 || pre.P > p.T - 1) return OVC_EINVAL;
+        hipLaunchKernelGGL(beam_prefix_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, pre);
+    } else if (o.groups != 0) {
+        if (p.V < p.k || !ovc_beam_diversity_ok(p.k, o.groups, o.diversity)) return OVC_EINVAL;
+        // the groups' rows are the image's one row at step 0 (or its G copies, one per group) and each group's own slots later: the
+        // kernel indexes rows with this
+        if (p.t == 0 ? p.width != 1 && p.width != o.groups : p.width != p.k) return OVC_EINVAL;
+        hipLaunchKernelGGL(beam_diverse_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, o.groups, o.diversity);
+    } else if (o.gate)
+        hipLaunchKernelGGL(beam_fused_update_kernel_gated, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, o.gate);
+    else
+        hipLaunchKernelGGL(beam_fused_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
+
+// The instance of an ensemble kernel template for a.M members (1..OVC_MAX_ENSEMBLE: every caller has checked it).
+#define OVC_ENSEMBLE_LAUNCH(kernel, grid, block, a)                                              \
+    switch ((a).M) {                                                                             \
+    case 1: hipLaunchKernelGGL(kernel<1>, grid, block, 0, stream, a); break;                     \
+    case 2: hipLaunchKernelGGL(kernel<2>, grid, block, 0, stream, a); break;                     \
+    case 3: hipLaunchKernelGGL(kernel<3>, grid, block, 0, stream, a); break;                     \
+    default: hipLaunchKernelGGL(kernel<4>, grid, block, 0, stream, a); break;                    \
+    }
 
 // The ensemble step: every member's tail passes the fused tail's validator with the shared shape, and what the kernel indexes with
 // a member's own strides and widths is checked here.  No gated instance: the early-exit forms are out of the ensemble's scope.
@@ -625,12 +630,7 @@ int ovc_beam_ensemble_update_launch(const EnsembleUpdateArgs& a, int B, hipStrea
     }
     if (p.next_x && (a.word_emb[0] != p.word_emb || a.pos_emb[0] != p.pos_emb || a.next_x[0] != p.next_x || a.d_model[0] != p.d_model))
         return OVC_EINVAL;
-    switch (a.M) {
-    case 1: hipLaunchKernelGGL(beam_ensemble_update_kernel<1>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL(beam_ensemble_update_kernel<2>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL(beam_ensemble_update_kernel<3>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
-    default: hipLaunchKernelGGL(beam_ensemble_update_kernel<4>, dim3(B), dim3(kFusedThreads), 0, stream, a); break;
-    }
+    OVC_ENSEMBLE_LAUNCH(beam_ensemble_update_kernel, dim3(B), dim3(kFusedThreads), a);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -639,12 +639,7 @@ int ovc_ensemble_masked_logp_launch(const EnsembleLogpArgs& a, int rows, hipStre
     if (a.M < 1 || a.M > OVC_MAX_ENSEMBLE || rows <= 0 || a.V <= 0 || !a.out) return OVC_EINVAL;
     for (int e = 0; e < a.M; ++e)
         if (!a.logits[e] || !a.row_max[e] || !a.row_lsum[e] || a.ld_row[e] <= 0 || a.ld_word[e] <= 0) return OVC_EINVAL;
-    switch (a.M) {
-    case 1: hipLaunchKernelGGL(ensemble_masked_logp_kernel<1>, dim3(rows), dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL(ensemble_masked_logp_kernel<2>, dim3(rows), dim3(256), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL(ensemble_masked_logp_kernel<3>, dim3(rows), dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL(ensemble_masked_logp_kernel<4>, dim3(rows), dim3(256), 0, stream, a); break;
-    }
+    OVC_ENSEMBLE_LAUNCH(ensemble_masked_logp_kernel, dim3(rows), dim3(256), a);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -654,15 +649,12 @@ int ovc_ensemble_combine_launch(const EnsembleCombineArgs& a, hipStream_t stream
     for (int e = 0; e < a.M; ++e)
         if (!a.logp[e]) return OVC_EINVAL;
     const dim3 grid((unsigned)((a.rows + 3) / 4));
-    switch (a.M) {
-    case 1: hipLaunchKernelGGL(ensemble_combine_rows_kernel<1>, grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL(ensemble_combine_rows_kernel<2>, grid, dim3(256), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL(ensemble_combine_rows_kernel<3>, grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL(ensemble_combine_rows_kernel<4>, grid, dim3(256), 0, stream, a); break;
-    }
+    OVC_ENSEMBLE_LAUNCH(ensemble_combine_rows_kernel, grid, dim3(256), a);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
+
+#undef OVC_ENSEMBLE_LAUNCH
 
 int ovc_block_pieces_launch(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t, hipStream_t stream) {
     const int nblk = (V + 31) / 32;

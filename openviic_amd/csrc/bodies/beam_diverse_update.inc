@@ -1,25 +1,21 @@
 // The body of beam_diverse_update_kernel (beam.hip): the fused selection and bookkeeping of one image for the diverse search
 // (include/ovc.h, ovc_beam_search_diverse: the rule).  The k beams are G groups of kg = k / G slots; the groups are selected one after
 // another inside the workgroup, and a later group pays lambda for every earlier winner of this step that took the same word.  Phase A
-// (fused_row_pieces.inc: the pieces M, ls and every block's upper bound) runs once for all W rows; each group then runs the plain
-// body's phases B and C over its own rows -- row 0 at t = 0 (its own copy of it where W = G), its own kg slots' rows later.  The earlier groups' (word, count) pairs
-// live in LDS (at most k - kg <= 7).  The penalty only lowers a score, so a block's maximum stays an upper bound; a block that holds
-// a listed word ("dirty") is not sure to hold a candidate of that score and feeds no lower bound.  Phase D is the plain body's.
-// Not a header: no include guard; p, stats, nblk, stats_ld, running_in, ld_row, ld_word, G, lambda are in scope.
+// (fused_row_pieces.inc: the pieces M, ls and every block's upper bound) runs once for all W rows; each group then runs phases B and C
+// over its own rows -- row 0 at t = 0 (its own copy of it where W = G), its own kg slots' rows later -- through the pieces every body
+// of the fused selection shares (fused_select_*.inc), which it gives the penalised score, its kg slots and its rows.  The earlier
+// groups' (word, count) pairs live in LDS (at most k - kg <= 7).  The penalty only lowers a score, so a block's maximum stays an upper
+// bound; a block that holds a listed word ("dirty") is not sure to hold a candidate of that score and feeds no lower bound.
+// Not a header: no include guard; p, stats, nblk, stats_ld, running_in, ld_row, ld_word, G, lambda are in scope, FUSED_SELECT_ROW
+// and FUSED_SELECT_LOGP (beam.hip: the one-model forms) are defined.
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
     const int kg = k / G;
-    __shared__ float rowM[kMaxK], rowLs[kMaxK], rowRun[kMaxK], thr[kMaxK];
-    __shared__ int rowLive[kMaxK];
-    __shared__ int nhot, nsurv, ntab;
+    constexpr int kListCap = kHotCap;
+    __shared__ float rowM[kMaxK], rowLs[kMaxK];
+#include "fused_select_lds.inc"
+    __shared__ int ntab;
     __shared__ int tab_w[kMaxK], tab_c[kMaxK];           // the words the earlier groups' live winners took at this step, and how often
-    __shared__ unsigned short hot_blk[kHotCap];
-    __shared__ uint8_t hot_row[kHotCap];
-    __shared__ float surv_v[kFusedSurvCap], surv_x[kFusedSurvCap];
-    __shared__ int surv_i[kFusedSurvCap];
-    __shared__ float win_v[kMaxK], win_x[kMaxK];
-    __shared__ int win_i[kMaxK];
-    __shared__ int parent[kMaxK], word[kMaxK];
 
     if (tid == 0) ntab = 0;
     if (tid < kMaxK) { win_v[tid] = -INFINITY; win_i[tid] = 0x7fffffff; win_x[tid] = 0.f; }
@@ -78,23 +74,11 @@
         float Tthr = -INFINITY;
         for (int i = r0; i < r0 + nr; ++i) Tthr = fmaxf(Tthr, thr[i]);
 
-        // ---- C: hot blocks -> survivors -> ranks, of this group's rows ------------------------------------------------------
-        if (mine) {
-#pragma unroll
-            for (int j = 0; j < kFusedPairs; ++j)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-                    if (ub[j][u] > -INFINITY && ub[j][u] >= Tthr) {
-                        const int pos = atomicAdd(&nhot, 1);
-                        if (pos < kHotCap) { hot_blk[pos] = (unsigned short)(2 * (lane + 64 * j) + u); hot_row[pos] = (uint8_t)wave; }
-                    }
-            // a frozen beam offers word 0 at its running score and -999 for every other word, unpenalised: its kg best are
-            // words 0..kg-1
-            if (!live && lane < kg && lane < V) {
-                const int pos = atomicAdd(&nsurv, 1);                                          // pos < kg * kg <= the cap
-                surv_v[pos] = lane == 0 ? run : -999.0f; surv_i[pos] = wave * V + lane; surv_x[pos] = 0.f;
-            }
-        }
+        // ---- C: hot blocks -> survivors -> ranks, of this group's rows, into the group's kg slots ----------------------------
+        const int nslot = kg, slot0 = g * kg, row0 = r0, row1 = r0 + nr;
+        const bool part = mine;
+        constexpr bool mute = false;
+#include "fused_select_publish.inc"
         __syncthreads();
         const int H = nhot;
         bool exhaustive = H > kHotCap;
@@ -130,67 +114,22 @@
             exhaustive = nsurv > kFusedSurvCap;
         }
         if (!exhaustive) {
-            const int ns = nsurv;
-            if (ns <= 64) {
-                // wave 0 ranks in registers (score descending, lower flat index first: a strict total order, so ranks are unique)
-                if (wave == 0) {
-                    const float v = lane < ns ? surv_v[lane] : -INFINITY;
-                    const int idx = lane < ns ? surv_i[lane] : 0x7fffffff;
-                    int rank = 0;
-                    for (int o = 0; o < ns; ++o) {
-                        const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), o));
-                        const int oi = __builtin_amdgcn_readlane(idx, o);
-                        rank += better(ov, oi, v, idx) ? 1 : 0;
-                    }
-                    if (lane < ns && rank < kg) { win_v[g * kg + rank] = v; win_i[g * kg + rank] = idx; win_x[g * kg + rank] = surv_x[lane]; }
-                }
-            } else {
-                for (int e = tid; e < ns; e += kFusedThreads) {
-                    const float v = surv_v[e];
-                    const int idx = surv_i[e];
-                    int rank = 0;
-                    for (int o = 0; o < ns; ++o) rank += better(surv_v[o], surv_i[o], v, idx) ? 1 : 0;
-                    if (rank < kg) { win_v[g * kg + rank] = v; win_i[g * kg + rank] = idx; win_x[g * kg + rank] = surv_x[e]; }
-                }
-            }
+#include "fused_select_rank.inc"
         } else {
-            // massive ties: kg rounds of a block-wide arg-max over the group's candidates that come after the previous pick in the
-            // (score descending, flat index ascending) order, under the same penalty; rare, written for simplicity
-            float pv = INFINITY;
-            int pi = -1;
-            for (int round = 0; round < kg; ++round) {
-                Cand c; c.v = -INFINITY; c.idx = 0x7fffffff;
-                float cx = 0.f;
-                for (int i = r0; i < r0 + nr; ++i) {
-                    const float* x = p.logits + (size_t)(b * W + i) * ld_row;
-                    const float ri = rowRun[i], mi = rowM[i], li = rowLs[i];
-                    const bool alive_i = rowLive[i] != 0;
-                    for (int col = tid; col < V; col += kFusedThreads) {
-                        const float xc = x[(size_t)col * ld_word];
-                        float cand = col == 0 ? ri : -999.0f;
-                        if (alive_i) {
-                            cand = ri + ((xc - mi) - li);
-                            int cnt = 0;
-                            for (int j = 0; j < nt; ++j) cnt = tab_w[j] == col ? tab_c[j] : cnt;
-                            if (cnt) cand = __fsub_rn(cand, __fmul_rn(lambda, (float)cnt));
-                        }
-                        const int idx = i * V + col;
-                        const bool after = cand < pv || (cand == pv && idx > pi);
-                        if (after && better(cand, idx, c.v, c.idx)) { c.v = cand; c.idx = idx; cx = xc; }
-                    }
-                }
-                const Cand wbest = wave_best(c);
-                __syncthreads();
-                if (c.idx == wbest.idx && wbest.idx != 0x7fffffff) { surv_v[wave] = c.v; surv_i[wave] = c.idx; surv_x[wave] = cx; }   // unique owner
-                if (lane == 0 && wbest.idx == 0x7fffffff) { surv_v[wave] = -INFINITY; surv_i[wave] = 0x7fffffff; surv_x[wave] = 0.f; }
-                __syncthreads();
-                int best_w = 0;
-#pragma unroll
-                for (int w = 1; w < kFusedThreads / 64; ++w)
-                    if (better(surv_v[w], surv_i[w], surv_v[best_w], surv_i[best_w])) best_w = w;
-                pv = surv_v[best_w]; pi = surv_i[best_w];
-                if (tid == 0) { win_v[g * kg + round] = pv; win_i[g * kg + round] = pi; win_x[g * kg + round] = surv_x[best_w]; }
+            // the group's candidates under the same penalty
+#define FUSED_SELECT_WORD(i, col)                                                                  \
+            const float xc = x[(size_t)col * ld_word], carried = xc;                               \
+            float cand = fixed;                                                                    \
+            if (alive_i) {                                                                         \
+                cand = ri + ((xc - mi) - li);                                                      \
+                int cnt = 0;                                                                       \
+                for (int j = 0; j < nt; ++j) cnt = tab_w[j] == col ? tab_c[j] : cnt;               \
+                if (cnt) cand = __fsub_rn(cand, __fmul_rn(lambda, (float)cnt));                    \
             }
+#define FUSED_SELECT_BANNED(i, col) false
+#include "fused_select_exhaustive.inc"
+#undef FUSED_SELECT_WORD
+#undef FUSED_SELECT_BANNED
         }
         __syncthreads();
         // ---- the group's live winners join the table the later groups pay for (one thread: at most kg words into at most 7) -------
@@ -210,21 +149,8 @@
         __syncthreads();
     }
 
-    // ---- D: bookkeeping, the plain body's: running takes the penalised score, the recorded log-probability is the model's own -------
-    if (tid < k) {
-        const int f = (unsigned)win_i[tid] < (unsigned)(W * V) ? win_i[tid] : tid;      // no winner (NaN scores): as beam_record_winner
-        const int par = f / V, wd = f - par * V;
-        parent[tid] = par; word[tid] = wd;
-        const float alive = rowLive[par] ? p.alive_in[b * W + par] : 0.0f;
-        const float x = ((unsigned)win_i[tid] < (unsigned)(W * V) && rowLive[par]) ? win_x[tid]
-                                                                                   : p.logits[(size_t)(b * W + par) * ld_row + (size_t)wd * ld_word];
-        const float lp = ((x - rowM[par]) - rowLs[par]) * alive;
-        p.running_out[b * k + tid] = win_v[tid];
-        p.alive_out[b * k + tid] = alive * (wd != p.eos ? 1.0f : 0.0f);
-        p.hist_out[((size_t)b * k + tid) * T + t] = wd;
-        p.lp_out[((size_t)b * k + tid) * T + t] = lp;
-        p.next_tok[b * k + tid] = wd;
-        p.anc_out[((size_t)b * k + tid) * T + t] = b * W + par;
-    }
+    // ---- D: bookkeeping: running takes the penalised score, the recorded log-probability is the model's own -----------------------
+    constexpr bool forced_alive = false;
+#include "fused_select_store.inc"
     __syncthreads();
     beam_follow_winners<kFusedThreads>(p, b, tid, parent, word);

@@ -1,23 +1,25 @@
 // The body of beam_ensemble_update_kernel<kM> (beam.hip): the fused selection and bookkeeping of one image from the block pieces of
 // kM members.  `a` (EnsembleUpdateArgs) and kM are in scope.  The layout of beam_fused_update.inc -- 512 threads, wave w < width owns
-// beam row w, the same lists, the same ranking and the same phase D -- with a candidate's score run + mean_m(lp_m) (ens_mean: the
-// rule's order and its division) and with the lower bound found from exact scores: a block's upper bound is attained by no word
-// once the members' maxima sit at different words.  Not a header: no include guard.
+// beam row w -- and the pieces every body of the fused selection shares (fused_select_*.inc), which this body gives a candidate's
+// score run + mean_m(lp_m) (ens_mean: the rule's order and its division), the mean as the carried value, all k slots and all W rows;
+// the lower bound is found from exact scores: a block's upper bound is attained by no word once the members' maxima sit at different
+// words.  Not a header: no include guard.
     const BeamUpdateArgs& p = a.p;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
     const int nblk = a.tail[0].nblk;
-    __shared__ float rowM[kM][kMaxK], rowLs[kM][kMaxK], rowRun[kMaxK], thr[kMaxK];
-    __shared__ int rowLive[kMaxK];
-    __shared__ int nhot, nsurv;
+    constexpr int kListCap = kEnsHotCap;                // the list holds every block of every row: it cannot overflow
+    __shared__ float rowM[kM][kMaxK], rowLs[kM][kMaxK];
+#include "fused_select_lds.inc"                         // surv_x / win_x: the candidate's mean (score - run)
     __shared__ float tighter;
-    __shared__ unsigned short hot_blk[kEnsHotCap];
-    __shared__ uint8_t hot_row[kEnsHotCap];
-    __shared__ float surv_v[kFusedSurvCap], surv_x[kFusedSurvCap];      // surv_x: the candidate's mean (score - run)
-    __shared__ int surv_i[kFusedSurvCap];
-    __shared__ float win_v[kMaxK], win_x[kMaxK];
-    __shared__ int win_i[kMaxK];
-    __shared__ int parent[kMaxK], word[kMaxK];
+    // the mean of word col of the image's row i, read from the members' logits (the rows' pieces are in LDS)
+    const auto word_mean = [&](int i, int col) {
+        float lp[kM];
+#pragma unroll
+        for (int e = 0; e < kM; ++e)
+            lp[e] = (a.logits[e][(size_t)(b * W + i) * a.tail[e].ld_row + (size_t)col * a.tail[e].ld_word] - rowM[e][i]) - rowLs[e][i];
+        return ens_mean<kM>(lp);
+    };
 
     if (tid == 0) { nhot = 0; nsurv = 0; }
     if (tid < kMaxK) { win_v[tid] = -INFINITY; win_i[tid] = 0x7fffffff; win_x[tid] = 0.f; }
@@ -109,21 +111,10 @@
     for (int i = 0; i < W; ++i) Tthr = fmaxf(Tthr, thr[i]);
 
     // ---- C: hot blocks (U_b >= the bound) -> survivors -> ranks ------------------------------------------------------------------
-    if (wave < W) {
-#pragma unroll
-        for (int j = 0; j < kFusedPairs; ++j)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-                if (ub[j][u] > -INFINITY && ub[j][u] >= Tthr) {
-                    const int pos = atomicAdd(&nhot, 1);
-                    if (pos < kEnsHotCap) { hot_blk[pos] = (unsigned short)(2 * (lane + 64 * j) + u); hot_row[pos] = (uint8_t)wave; }
-                }
-        // a frozen beam offers word 0 at its running score and -999 for every other word: its k best are words 0..k-1
-        if (!live && lane < k && lane < V) {
-            const int pos = atomicAdd(&nsurv, 1);                                          // pos < k * k <= the cap
-            surv_v[pos] = lane == 0 ? run : -999.0f; surv_i[pos] = wave * V + lane; surv_x[pos] = 0.f;
-        }
-    }
+    const int nslot = k, slot0 = 0, row0 = 0, row1 = W;
+    const bool part = wave < W;
+    constexpr bool mute = false;
+#include "fused_select_publish.inc"
     __syncthreads();
     const int H = nhot, nfixed = nsurv;                 // nfixed: the frozen beams' offers, at the front of the survivor list
     bool exhaustive = H > kEnsHotCap;                   // (the list holds every block of every row: never, by construction)
@@ -181,91 +172,29 @@
         __syncthreads();
     }
     if (!exhaustive) {
-        const int ns = nsurv;
-        if (ns <= 64) {
-            // wave 0 ranks in registers: lane e holds survivor e and counts the survivors that beat it (a strict total order)
-            if (wave == 0) {
-                const float v = lane < ns ? surv_v[lane] : -INFINITY;
-                const int idx = lane < ns ? surv_i[lane] : 0x7fffffff;
-                int rank = 0;
-                for (int o = 0; o < ns; ++o) {
-                    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), o));
-                    const int oi = __builtin_amdgcn_readlane(idx, o);
-                    rank += better(ov, oi, v, idx) ? 1 : 0;
-                }
-                if (lane < ns && rank < k) { win_v[rank] = v; win_i[rank] = idx; win_x[rank] = surv_x[lane]; }
-            }
-        } else {
-            for (int e = tid; e < ns; e += kFusedThreads) {
-                const float v = surv_v[e];
-                const int idx = surv_i[e];
-                int rank = 0;
-                for (int o = 0; o < ns; ++o) rank += better(surv_v[o], surv_i[o], v, idx) ? 1 : 0;
-                if (rank < k) { win_v[rank] = v; win_i[rank] = idx; win_x[rank] = surv_x[e]; }
-            }
-        }
+#include "fused_select_rank.inc"
     } else {
         // the lists overflowed (massive ties, or members whose maxima disagree in every block): k rounds of a block-wide arg-max
         // over the image's width * V exact candidates that come after the previous pick in the (score descending, flat index
         // ascending) order
-        float pv = INFINITY;
-        int pi = -1;
-        for (int round = 0; round < k; ++round) {
-            Cand c; c.v = -INFINITY; c.idx = 0x7fffffff;
-            float cx = 0.f;
-            for (int i = 0; i < W; ++i) {
-                const float ri = rowRun[i];
-                const bool alive_i = rowLive[i] != 0;
-                for (int col = tid; col < V; col += kFusedThreads) {
-                    float lp[kM];
-#pragma unroll
-                    for (int e = 0; e < kM; ++e)
-                        lp[e] = (a.logits[e][(size_t)(b * W + i) * a.tail[e].ld_row + (size_t)col * a.tail[e].ld_word] - rowM[e][i]) - rowLs[e][i];
-                    const float mean = ens_mean<kM>(lp);
-                    const float cand = alive_i ? ri + mean : (col == 0 ? ri : -999.0f);
-                    const int idx = i * V + col;
-                    const bool after = cand < pv || (cand == pv && idx > pi);
-                    if (after && better(cand, idx, c.v, c.idx)) { c.v = cand; c.idx = idx; cx = mean; }
-                }
-            }
-            const Cand wbest = wave_best(c);
-            __syncthreads();
-            if (c.idx == wbest.idx && wbest.idx != 0x7fffffff) { surv_v[wave] = c.v; surv_i[wave] = c.idx; surv_x[wave] = cx; }   // unique owner
-            if (lane == 0 && wbest.idx == 0x7fffffff) { surv_v[wave] = -INFINITY; surv_i[wave] = 0x7fffffff; surv_x[wave] = 0.f; }
-            __syncthreads();
-            int best_w = 0;
-#pragma unroll
-            for (int w = 1; w < kFusedThreads / 64; ++w)
-                if (better(surv_v[w], surv_i[w], surv_v[best_w], surv_i[best_w])) best_w = w;
-            pv = surv_v[best_w]; pi = surv_i[best_w];
-            if (tid == 0) { win_v[round] = pv; win_i[round] = pi; win_x[round] = surv_x[best_w]; }
-        }
+#define FUSED_SELECT_ROW(i)
+#define FUSED_SELECT_WORD(i, col)                                                                          \
+        const float mean = word_mean(i, col), carried = mean;                                              \
+        const float cand = alive_i ? ri + mean : fixed
+#define FUSED_SELECT_BANNED(i, col) false
+#include "fused_select_exhaustive.inc"
+#undef FUSED_SELECT_ROW
+#undef FUSED_SELECT_WORD
+#undef FUSED_SELECT_BANNED
     }
     if (tid == 0 && a.hot_out) a.hot_out[b] = exhaustive ? -1 : H;
     __syncthreads();
 
     // ---- D: the bookkeeping of the plain selection, once, into the shared beam state; the recorded log-prob is mean * alive --------
-    if (tid < k) {
-        const bool won = (unsigned)win_i[tid] < (unsigned)(W * V);
-        const int f = won ? win_i[tid] : tid;               // no winner (NaN scores): slot j takes word j of beam 0
-        const int par = f / V, wd = f - par * V;
-        parent[tid] = par; word[tid] = wd;
-        const float alive = rowLive[par] ? p.alive_in[b * W + par] : 0.0f;
-        float mean = win_x[tid];
-        if (!(won && rowLive[par])) {                       // no winner, or a frozen beam's fixed candidate: the word's own mean
-            float lp[kM];
-#pragma unroll
-            for (int e = 0; e < kM; ++e)
-                lp[e] = (a.logits[e][(size_t)(b * W + par) * a.tail[e].ld_row + (size_t)wd * a.tail[e].ld_word] - rowM[e][par]) - rowLs[e][par];
-            mean = ens_mean<kM>(lp);
-        }
-        p.running_out[b * k + tid] = win_v[tid];
-        p.alive_out[b * k + tid] = alive * (wd != p.eos ? 1.0f : 0.0f);
-        p.hist_out[((size_t)b * k + tid) * T + t] = wd;
-        p.lp_out[((size_t)b * k + tid) * T + t] = mean * alive;
-        p.next_tok[b * k + tid] = wd;
-        p.anc_out[((size_t)b * k + tid) * T + t] = b * W + par;
-    }
+    constexpr bool forced_alive = false;
+#define FUSED_SELECT_LOGP(own, par, wd) ((own) ? win_x[tid] : word_mean(par, wd))
+#include "fused_select_store.inc"
+#undef FUSED_SELECT_LOGP
     __syncthreads();
     // histories, member 0's next input rows and the shared pad flags; then the other members' rows: the same words, each member's
     // own embedding table and width

@@ -5,20 +5,15 @@
 // without it -- the bitmap and the staged histories are then not even allocated.  It also defines `constexpr bool kPrefix` and `pre`
 // (BeamPrefix: a kernel argument with kPrefix, a constexpr empty value without).  With kPrefix an image may be forced to a given word
 // or restricted to its row 0 (include/ovc.h, ovc_beam_search_prefix: the rule); the pieces that know of it are marked "prefix:" and
-// compile to nothing without it.  The log-softmax pieces, the candidate arithmetic, the order, the frozen beams' offers and phase D
-// are the same text for all four.  Not a header: no include guard.
+// compile to nothing without it.  The lists, the hot blocks' publication, the frozen beams' offers, the ranking, the exhaustive rounds
+// and phase D are the pieces every body of the fused selection shares (fused_select_*.inc); this body gives them the logit's score,
+// with the ban test, all k slots and the rows that offer.  Not a header: no include guard; FUSED_SELECT_ROW and FUSED_SELECT_LOGP
+// (beam.hip: the one-model forms) are defined.
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.width, k = p.k, V = p.V, T = p.T, t = p.t;
-    __shared__ float rowM[kMaxK], rowLs[kMaxK], rowRun[kMaxK], thr[kMaxK];
-    __shared__ int rowLive[kMaxK];
-    __shared__ int nhot, nsurv;
-    __shared__ unsigned short hot_blk[kHotCap];
-    __shared__ uint8_t hot_row[kHotCap];
-    __shared__ float surv_v[kFusedSurvCap], surv_x[kFusedSurvCap];
-    __shared__ int surv_i[kFusedSurvCap];
-    __shared__ float win_v[kMaxK], win_x[kMaxK];
-    __shared__ int win_i[kMaxK];
-    __shared__ int parent[kMaxK], word[kMaxK];
+    constexpr int kListCap = kHotCap;
+    __shared__ float rowM[kMaxK], rowLs[kMaxK];
+#include "fused_select_lds.inc"
     // ban: one bit per (row, word); 32-bit word j of a row IS the row's 32-word block j, so "block j holds a banned word"
     // is one LDS read.  The row's history is staged once for the n-gram scan.
     __shared__ unsigned ban[kMaxK][kBanWords];
@@ -110,22 +105,10 @@
         for (int i = 0; i < W; ++i) Tthr = fmaxf(Tthr, thr[i]);
 
         // ---- C: hot blocks -> survivors -> ranks --------------------------------------------------------------------------
-        if (wave < W) {
-#pragma unroll
-            for (int j = 0; j < kFusedPairs; ++j)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-                    if (ub[j][u] > -INFINITY && ub[j][u] >= Tthr) {
-                        const int pos = atomicAdd(&nhot, 1);
-                        if (pos < kHotCap) { hot_blk[pos] = (unsigned short)(2 * (lane + 64 * j) + u); hot_row[pos] = (uint8_t)wave; }
-                    }
-            // a frozen beam (it has emitted <eos>) offers word 0 at its running score and -999 for every other word
-            // (beam_search.py:52-55): its k best are words 0..k-1, whatever the logits are
-            if (!live && !mute && lane < k && lane < V) {
-                const int pos = atomicAdd(&nsurv, 1);                                          // pos < k * k <= the cap
-                surv_v[pos] = lane == 0 ? run : -999.0f; surv_i[pos] = wave * V + lane; surv_x[pos] = 0.f;
-            }
-        }
+        // all k slots are filled from the rows that offer
+        const int nslot = k, slot0 = 0, row0 = 0, row1 = Ws;
+        const bool part = wave < W;
+#include "fused_select_publish.inc"
         __syncthreads();
         const int H = nhot;
         bool exhaustive = H > kHotCap;
@@ -159,88 +142,23 @@
             exhaustive = nsurv > kFusedSurvCap;
         }
         if (!exhaustive) {
-            const int ns = nsurv;
-            if (ns <= 64) {
-                // the usual case: wave 0 ranks in registers -- lane e holds survivor e and counts the survivors that beat it
-                // (score descending, lower flat index first: a strict total order, so ranks are unique)
-                if (wave == 0) {
-                    const float v = lane < ns ? surv_v[lane] : -INFINITY;
-                    const int idx = lane < ns ? surv_i[lane] : 0x7fffffff;
-                    int rank = 0;
-                    for (int o = 0; o < ns; ++o) {
-                        const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), o));
-                        const int oi = __builtin_amdgcn_readlane(idx, o);
-                        rank += better(ov, oi, v, idx) ? 1 : 0;
-                    }
-                    if (lane < ns && rank < k) { win_v[rank] = v; win_i[rank] = idx; win_x[rank] = surv_x[lane]; }
-                }
-            } else {
-                for (int e = tid; e < ns; e += kFusedThreads) {
-                    const float v = surv_v[e];
-                    const int idx = surv_i[e];
-                    int rank = 0;
-                    for (int o = 0; o < ns; ++o) rank += better(surv_v[o], surv_i[o], v, idx) ? 1 : 0;
-                    if (rank < k) { win_v[rank] = v; win_i[rank] = idx; win_x[rank] = surv_x[e]; }
-                }
-            }
+#include "fused_select_rank.inc"
         } else {
-            // massive ties: k rounds of a block-wide arg-max over the candidates that come after the previous pick in the
-            // (score descending, flat index ascending) order; rare, written for simplicity
-            float pv = INFINITY;
-            int pi = -1;
-            for (int round = 0; round < k; ++round) {
-                Cand c; c.v = -INFINITY; c.idx = 0x7fffffff;
-                float cx = 0.f;
-                for (int i = 0; i < Ws; ++i) {                     // prefix: Ws rows offer; otherwise Ws is W itself
-                    const float* x = p.logits + (size_t)(b * W + i) * ld_row;
-                    const float ri = rowRun[i], mi = rowM[i], li = rowLs[i];
-                    const bool alive_i = rowLive[i] != 0;
-                    for (int col = tid; col < V; col += kFusedThreads) {
-                        const float xc = x[(size_t)col * ld_word];
-                        const float cand = alive_i ? ri + ((xc - mi) - li) : (col == 0 ? ri : -999.0f);
-                        const int idx = i * V + col;
-                        const bool after = cand < pv || (cand == pv && idx > pi);
-                        if (kBan && ((ban[i][col >> 5] >> (col & 31)) & 1u)) continue;        // ban: set for live rows only
-                        if (after && better(cand, idx, c.v, c.idx)) { c.v = cand; c.idx = idx; cx = xc; }
-                    }
-                }
-                const Cand wbest = wave_best(c);
-                __syncthreads();
-                if (c.idx == wbest.idx && wbest.idx != 0x7fffffff) { surv_v[wave] = c.v; surv_i[wave] = c.idx; surv_x[wave] = cx; }   // unique owner
-                if (lane == 0 && wbest.idx == 0x7fffffff) { surv_v[wave] = -INFINITY; surv_i[wave] = 0x7fffffff; surv_x[wave] = 0.f; }
-                __syncthreads();
-                int best_w = 0;
-#pragma unroll
-                for (int w = 1; w < kFusedThreads / 64; ++w)
-                    if (better(surv_v[w], surv_i[w], surv_v[best_w], surv_i[best_w])) best_w = w;
-                pv = surv_v[best_w]; pi = surv_i[best_w];
-                if (tid == 0) { win_v[round] = pv; win_i[round] = pi; win_x[round] = surv_x[best_w]; }
-            }
+            // prefix: Ws rows offer; otherwise Ws is W itself.  ban: set for live rows only
+#define FUSED_SELECT_WORD(i, col)                                                                  \
+            const float xc = x[(size_t)col * ld_word], carried = xc;                               \
+            const float cand = alive_i ? ri + ((xc - mi) - li) : fixed
+#define FUSED_SELECT_BANNED(i, col) (kBan && ((ban[i][col >> 5] >> (col & 31)) & 1u))
+#include "fused_select_exhaustive.inc"
+#undef FUSED_SELECT_WORD
+#undef FUSED_SELECT_BANNED
         }
     }
     __syncthreads();
 
-    // ---- D: bookkeeping (beam_update_kernel's, with the winner's logit carried along instead of re-read) -------------------
-    if (tid < k) {
-        const int f = (unsigned)win_i[tid] < (unsigned)(W * V) ? win_i[tid] : tid;      // no winner (NaN scores): as beam_record_winner
-        const int par = f / V, wd = f - par * V;
-        parent[tid] = par; word[tid] = wd;
-        // prefix: a forced slot is alive (the rule: the prefix holds no <eos>, so the row it continues is)
-        const float alive = kPrefix && forced ? 1.0f : rowLive[par] ? p.alive_in[b * W + par] : 0.0f;
-        // the carried logit is the winner's own; without a winner, or for a frozen beam's fixed candidates (whose product with
-        // alive = 0 only needs a finite operand), the logit is read as the two-pass path reads it
-        const float x = ((unsigned)win_i[tid] < (unsigned)(W * V) && rowLive[par]) ? win_x[tid]
-                                                                                   : p.logits[(size_t)(b * W + par) * ld_row + (size_t)wd * ld_word];
-        // (beam_write_winner's stores, in this body's own order: through the writer, which stores parent / word after the loads
-        // above, the three instances come out with another instruction stream)
-        const float lp = ((x - rowM[par]) - rowLs[par]) * alive;
-        p.running_out[b * k + tid] = win_v[tid];
-        p.alive_out[b * k + tid] = alive * (wd != p.eos ? 1.0f : 0.0f);
-        p.hist_out[((size_t)b * k + tid) * T + t] = wd;
-        p.lp_out[((size_t)b * k + tid) * T + t] = lp;
-        p.next_tok[b * k + tid] = wd;
-        p.anc_out[((size_t)b * k + tid) * T + t] = b * W + par;
-    }
+    // ---- D: bookkeeping.  prefix: a forced slot is alive (the rule: the prefix holds no <eos>, so the row it continues is) ----------
+    const bool forced_alive = kPrefix && forced;
+#include "fused_select_store.inc"
     if (p.alive_count && wave == 0) {      // early exit: beams of this image that go on (no valid winner = ended: NaN logits)
         const bool on = tid < k && (unsigned)win_i[tid] < (unsigned)(W * V) && rowLive[parent[tid]] &&
                         p.alive_in[b * W + parent[tid]] != 0.0f && word[tid] != p.eos;

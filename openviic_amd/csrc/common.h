@@ -267,7 +267,7 @@ struct BeamUpdateArgs {
 int ovc_beam_update_launch(const BeamUpdateArgs& p, int B, hipStream_t stream, const int32_t* gate = nullptr);
 // What the fused vocabulary tail -- selection or draw + update in one launch, no pass over the logits -- reads of the vocabulary
 // product: the block pieces of its epilogue (GemmArgs::stats / stats_t) and where a logit lives.  One block of arguments for the
-// four launchers below, checked by one validator (beam.hip, fused_tail_ok).
+// launchers below, checked by one validator (beam.hip, fused_tail_ok).
 constexpr int kFusedVocabBlocks = 512;              // 32 words each: vocabularies up to 16 384 words take the fused tail
 struct FusedTail {
     const float* stats;      // [rows][stats_ld] float2, 16-byte aligned: per 32-word block the maximum and sum exp(x - maximum)
@@ -280,9 +280,6 @@ static inline FusedTail ovc_fused_tail(const float* stats, int V, long ld_row, l
     const int nblk = (V + 31) / 32;
     return FusedTail{stats, nblk, (nblk + 1) & ~1, ld_row, ld_word};
 }
-// Selection + update.  p.cand_* / p.row_max / p.row_lsum are not used.
-int ovc_beam_fused_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, int B, hipStream_t stream,
-                                 const int32_t* gate = nullptr);
 // The constrained search's options (include/ovc.h, ovc_beam_search_constrained): passed to the kernel by value.
 struct BeamConstraints {
     int ngram, min_length, n_banned;                // 0, 0, 0: neutral
@@ -291,9 +288,6 @@ struct BeamConstraints {
 };
 // The options' scope for a model of V words, max_len steps, beam k: include/ovc.h lists the refusals.
 bool ovc_beam_constraints_ok(const BeamConstraints& c, int V, int max_len, int k, int eos, int pad);
-// ovc_beam_fused_update_launch with a per-row ban set (p.hist_in holds the rows' histories); p.alive_count must be nullptr.
-int ovc_beam_constrained_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamConstraints& cons,
-                                       int B, hipStream_t stream);
 // The prefix search's table (include/ovc.h, ovc_beam_search_prefix), in DEVICE memory: read by the kernel, so one captured graph
 // serves every content of a shape.
 struct BeamPrefix {
@@ -301,16 +295,20 @@ struct BeamPrefix {
     const int32_t* len;      // [B] P_b in 0..P
     int P;                   // the row stride of ids, >= 1
 };
-// ovc_beam_fused_update_launch with a prefix table: an image is forced (p.t < P_b), restricted to its row 0 (p.t == P_b >= 1) or
-// takes the plain step; p.alive_count must be nullptr.
-int ovc_beam_prefix_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const BeamPrefix& pre, int B,
-                                  hipStream_t stream);
 // The diverse search's options (include/ovc.h, ovc_beam_search_diverse): G groups dividing k, a finite strength in [0, 1e30].
 bool ovc_beam_diversity_ok(int k, int G, float lambda);
-// ovc_beam_fused_update_launch for G groups of k / G slots with the Hamming penalty lambda; p.width is 1 at p.t == 0, else p.k;
-// p.alive_count must be nullptr.
-int ovc_beam_diverse_update_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, int G, float lambda, int B,
-                                   hipStream_t stream);
+// The options of a step's fused selection, as the search call holds them; all zero: the plain selection.
+struct FusedSelectOptions {
+    BeamConstraints cons;           // active(): a per-row ban set (p.hist_in holds the rows' histories)
+    BeamPrefix prefix;              // P != 0: an image is forced (p.t < P_b), restricted to its row 0 (p.t == P_b >= 1) or free
+    int groups; float diversity;    // groups != 0: that many groups of k / groups slots under the Hamming penalty; p.width is 1
+                                    // (or groups) at p.t == 0, else p.k
+    const int32_t* gate;            // the plain selection's gated form (ovc_gate_closed)
+};
+// Selection + update of a step, one launch: the constrained instance, else the prefix one, else the diverse one, else the plain
+// one.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count and the gate go with the plain instance only.
+int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const FusedSelectOptions& o, int B,
+                                 hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
 // log-probabilities and the bookkeeping, one launch.  One argument block, by value: p is member 0's -- the shared beam state, and
 // member 0's embedding tables / next_x / d_model for the next step's input rows -- and every member's tail, logits, embedding

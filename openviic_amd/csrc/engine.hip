@@ -1425,14 +1425,12 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_shaped_update_launch(bu, tail, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
-        else if (c.constrained())  // the one branch of a constrained step: the selection with a per-row ban set
-            RUN(ovc_beam_constrained_update_launch(bu, tail, w.running[cur], c.cons, B, s));
-        else if (c.prefixed())     // the one branch of a prefix step: the selection reads the staged table
-            RUN(ovc_beam_prefix_update_launch(bu, tail, w.running[cur], BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P}, B, s));
-        else if (c.diverse())      // the one branch of a diverse step: the groups selected in order, under the Hamming penalty
-            RUN(ovc_beam_diverse_update_launch(bu, tail, w.running[cur], c.groups, c.diversity, B, s));
-        else if (!(debug_skip() & 8))
-            RUN(ovc_beam_fused_update_launch(bu, tail, w.running[cur], B, s, e.gate));
+        else if (c.constrained() || c.prefixed() || c.diverse() || !(debug_skip() & 8)) {
+            // the one branch of a beam step: the call's options pick the instance -- a per-row ban set, the staged prefix table, the
+            // groups under the Hamming penalty, else the plain selection or its gated form
+            const BeamPrefix pre = c.prefixed() ? BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P} : BeamPrefix{};
+            RUN(ovc_beam_fused_select_launch(bu, tail, w.running[cur], FusedSelectOptions{c.cons, pre, c.groups, c.diversity, e.gate}, B, s));
+        }
         if (return_probs) {   // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
             // step 0 is stored as one row per image: a diverse search's rows of step 0 (a copy per group) are staged in the block of
             // step 1, which that step overwrites, and every image's first copy is kept (width > 1 at step 0 only where max_len >= 2)
@@ -2091,11 +2089,71 @@ extern "C" int ovc_beam_search_constrained_graph(const ovc_model* m, const float
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
-// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the constrained one
-// with active options, the plain one with neutral options -- on caller-given inputs (device memory):
-// row-major logits [B*width][V], histories hist [B*width][T] (words of steps 0..t-1), running / alive [B*width].  The block pieces
-// are computed here and the logits laid out transposed, as the engine's vocabulary product leaves them.  parent_out / word_out
-// [B][k] (int32), running_out [B][k], row_max_out / row_lsum_out [B*width].  scratch: ovc_debug_beam_constrained_update_bytes.
+// The harness behind the step test entries: ONE step of the fused selection on caller-given inputs (device memory) -- row-major
+// logits [M][B*width][V], histories hist [B*width][T] (words of steps 0..t-1; nullptr: empty ones), running / alive [B*width].
+// Every member's block pieces are computed here and its logits laid out transposed, as the engine's vocabulary product leaves
+// them; then the launch a search step makes: with members == 0 the engine's routing of the one model's selection under `opt`
+// (ovc_beam_fused_select_launch, run_decode_step's own call; a prefix table comes in HOST memory and is staged here), else the
+// ensemble kernel's instance for that many members.  parent_out / word_out [B][k] (int32), running_out [B][k], row_max_out /
+// row_lsum_out [M][B*width]; lp_out: where the scratch holds the step's log-probs [B*k][T].  The entries have checked their
+// arguments and the scratch: nothing is refused here before the device is touched.
+struct StepTest {
+    const float* logits; const int32_t* hist; const float* running; const float* alive;
+    int B, width, V, k, T, t, eos;
+    int32_t* parent_out; int32_t* word_out; float* running_out; float* row_max_out; float* row_lsum_out;
+    FusedSelectOptions opt; const int32_t* prefix; const int32_t* prefix_len;      // one model: opt.prefix names no addresses yet
+    int members; int32_t* hot_out;                                                 // the ensemble kernel, and its hot-block count
+    float* lp_out;
+};
+
+static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const int B = c.B, V = c.V, T = c.T, M = c.members ? c.members : 1, rows = B * c.width, ldt = (rows + 3) & ~3;
+    const size_t Rk = (size_t)B * c.k;
+    Bump a{reinterpret_cast<char*>(scratch), 0};
+    EnsembleUpdateArgs en{};
+    en.M = M;
+    for (int i = 0; i < M; ++i) {
+        float* logits_t = a.take<float>((size_t)V * ldt);
+        en.tail[i] = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
+        float* stats = a.take<float>(2 * (size_t)rows * en.tail[i].stats_ld);
+        en.tail[i].stats = stats;
+        en.logits[i] = logits_t;
+        en.row_max_out[i] = c.row_max_out + (size_t)i * rows; en.row_lsum_out[i] = c.row_lsum_out + (size_t)i * rows;
+        TRY(ovc_block_pieces_launch(c.logits + (size_t)i * rows * V, rows, V, en.tail[i].stats_ld, ldt, stats, logits_t, s));
+    }
+    float* alive_out = a.take<float>(Rk); c.lp_out = a.take<float>(Rk * T);
+    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
+    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
+    int32_t* hist_in = c.hist ? nullptr : a.take<int32_t>(Rk * T);
+    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess ||
+        (hist_in && hipMemsetAsync(hist_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess))
+        return OVC_ELAUNCH;
+    if (c.opt.prefix.P != 0) {
+        int32_t* ids_dev = a.take<int32_t>((size_t)B * T); int32_t* len_dev = a.take<int32_t>((size_t)B);
+        if (hipMemcpyAsync(ids_dev, c.prefix, sizeof(int32_t) * B * c.opt.prefix.P, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(len_dev, c.prefix_len, sizeof(int32_t) * B, hipMemcpyHostToDevice, s) != hipSuccess)
+            return OVC_ELAUNCH;
+        c.opt.prefix.ids = ids_dev; c.opt.prefix.len = len_dev;
+    }
+    BeamUpdateArgs& bu = en.p;
+    bu.alive_in = c.alive; bu.alive_out = alive_out; bu.running_out = c.running_out;
+    bu.hist_in = c.hist ? c.hist : hist_in; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = c.lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
+    bu.next_tok = next_tok;
+    bu.width = c.width; bu.k = c.k; bu.V = V; bu.T = T; bu.t = c.t; bu.eos = c.eos;
+    if (c.members) {
+        en.running_in = c.running; en.hot_out = c.hot_out;
+        TRY(ovc_beam_ensemble_update_launch(en, B, s));
+    } else {
+        bu.logits = en.logits[0]; bu.ld = (V + 3) & ~3; bu.row_max_out = c.row_max_out; bu.row_lsum_out = c.row_lsum_out;
+        TRY(ovc_beam_fused_select_launch(bu, en.tail[0], c.running, c.opt, B, s));
+    }
+    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, c.width, c.k, T, c.t, c.parent_out, c.word_out, s);
+}
+
+// Test entry: ONE step of the fused selection (run_step_test) under the constrained search's options: the constrained instance with
+// active options, the plain one with neutral options.  scratch: ovc_debug_beam_constrained_update_bytes.
 extern "C" size_t ovc_debug_beam_constrained_update_bytes(int B, int width, int V, int k, int T) {
     if (B <= 0 || width <= 0 || V <= 0 || k <= 0 || T <= 0) return 0;
     const size_t R = (size_t)B * width, nblk = ((size_t)V + 31) / 32, ld = (nblk + 1) & ~(size_t)1, Rk = (size_t)B * k;
@@ -2117,29 +2175,9 @@ extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int3
         (cons.active() && !ovc_beam_constraints_ok(cons, V, T, k, eos, -1)))      // neutral options: the plain step's scope
         return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_constrained_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    TRY(ovc_device_guard());
-    hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, ldt = (rows + 3) & ~3;
-    const size_t Rk = (size_t)B * k;
-    Bump a{reinterpret_cast<char*>(scratch), 0};
-    float* logits_t = a.take<float>((size_t)V * ldt);
-    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
-    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
-    tail.stats = stats;
-    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
-    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
-    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
-    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
-        return OVC_ELAUNCH;
-    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
-    BeamUpdateArgs bu{};
-    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
-    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
-    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
-    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
-    if (cons.active()) TRY(ovc_beam_constrained_update_launch(bu, tail, running, cons, B, s));      // run_decode_step's routing
-    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
-    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    c.opt.cons = cons;
+    return run_step_test(c, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2196,9 +2234,8 @@ extern "C" int ovc_beam_search_prefix_graph(const ovc_model* m, const float* fea
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
-// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the prefix one when a
-// length is not 0, else the plain one -- on caller-given inputs as ovc_debug_beam_constrained_update takes them, plus the table in
-// HOST memory (prefix [B][P], prefix_len [B]).  scratch: ovc_debug_beam_prefix_update_bytes.
+// Test entry: ONE step of the fused selection (run_step_test) under a prefix table in HOST memory (prefix [B][P], prefix_len [B]):
+// the prefix instance when a length is not 0, else the plain one.  scratch: ovc_debug_beam_prefix_update_bytes.
 extern "C" size_t ovc_debug_beam_prefix_update_bytes(int B, int width, int V, int k, int T) {
     const size_t base = ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
     return base ? base + 4 * ((size_t)B * T + (size_t)B) + 512 : 0;
@@ -2222,33 +2259,9 @@ extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* 
         any = any || prefix_len[b] > 0;
     }
     if (scratch_bytes < ovc_debug_beam_prefix_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    TRY(ovc_device_guard());
-    hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, ldt = (rows + 3) & ~3;
-    const size_t Rk = (size_t)B * k;
-    Bump a{reinterpret_cast<char*>(scratch), 0};
-    float* logits_t = a.take<float>((size_t)V * ldt);
-    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
-    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
-    tail.stats = stats;
-    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
-    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
-    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
-    int32_t* ids_dev = a.take<int32_t>((size_t)B * T); int32_t* len_dev = a.take<int32_t>((size_t)B);
-    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
-        return OVC_ELAUNCH;
-    if (any && (hipMemcpyAsync(ids_dev, prefix, sizeof(int32_t) * B * P, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(len_dev, prefix_len, sizeof(int32_t) * B, hipMemcpyHostToDevice, s) != hipSuccess))
-        return OVC_ELAUNCH;
-    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
-    BeamUpdateArgs bu{};
-    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
-    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
-    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
-    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
-    if (any) TRY(ovc_beam_prefix_update_launch(bu, tail, running, BeamPrefix{ids_dev, len_dev, P}, B, s));      // run_decode_step's routing
-    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
-    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (any) { c.opt.prefix.P = P; c.prefix = prefix; c.prefix_len = prefix_len; }      // as prefix_from: no length, no table
+    return run_step_test(c, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2295,8 +2308,8 @@ extern "C" int ovc_beam_search_diverse_graph(const ovc_model* m, const float* fe
                        workspace_bytes, stream);
 }
 
-// Test entry: ONE step of the fused selection -- the production kernel instance run_decode_step would take: the diverse one with more
-// than one group, else the plain one -- on caller-given inputs as ovc_debug_beam_constrained_update takes them, plus G and lambda.
+// Test entry: ONE step of the fused selection (run_step_test) under G groups and the strength lambda: the diverse instance with more
+// than one group, else the plain one.
 extern "C" size_t ovc_debug_beam_diverse_update_bytes(int B, int width, int V, int k, int T) {
     return ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
 }
@@ -2312,29 +2325,9 @@ extern "C" int ovc_debug_beam_diverse_update(const float* logits, const int32_t*
         return OVC_EINVAL;
     if (!ovc_beam_diversity_ok(k, G, lambda)) return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_diverse_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    TRY(ovc_device_guard());
-    hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, ldt = (rows + 3) & ~3;
-    const size_t Rk = (size_t)B * k;
-    Bump a{reinterpret_cast<char*>(scratch), 0};
-    float* logits_t = a.take<float>((size_t)V * ldt);
-    FusedTail tail = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
-    float* stats = a.take<float>(2 * (size_t)rows * tail.stats_ld);
-    tail.stats = stats;
-    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
-    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
-    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T);
-    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
-        return OVC_ELAUNCH;
-    TRY(ovc_block_pieces_launch(logits, rows, V, tail.stats_ld, ldt, stats, logits_t, s));
-    BeamUpdateArgs bu{};
-    bu.logits = logits_t; bu.ld = (V + 3) & ~3; bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
-    bu.hist_in = hist; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
-    bu.next_tok = next_tok; bu.row_max_out = row_max_out; bu.row_lsum_out = row_lsum_out;
-    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
-    if (G > 1) TRY(ovc_beam_diverse_update_launch(bu, tail, running, G, lambda, B, s));      // run_decode_step's routing
-    else TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
-    return ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s);
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (G > 1) { c.opt.groups = G; c.opt.diversity = lambda; }                           // as diversity_from: one group is the plain call
+    return run_step_test(c, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2381,10 +2374,9 @@ extern "C" int ovc_ensemble_beam_search_graph(const ovc_model* const* models, in
     return run_search(models[0], c, features, boxes, workspace, workspace_bytes, stream);
 }
 
-// Test entry: ONE step of the ensemble selection kernel (M = 1 included: the kernel's one-member instance, not the plain kernel the
-// search itself takes for one member) on caller-given device inputs: row-major logits [M][B*width][V], running / alive [B*width].
-// Every member's block pieces are computed here and its logits laid out transposed, as the engine's vocabulary product leaves
-// them.  The step is t of T = t + 1 positions with empty histories: no next input rows are written.
+// Test entry: ONE step of the ensemble selection kernel (run_step_test; M = 1 included: the kernel's one-member instance, not the
+// plain kernel the search itself takes for one member) on row-major logits [M][B*width][V].  The step is t of T = t + 1 positions
+// with empty histories: no next input rows are written.
 extern "C" size_t ovc_debug_ensemble_update_bytes(int M, int B, int width, int V, int k) {
     if (M < 1 || M > OVC_MAX_ENSEMBLE || B <= 0 || width <= 0 || V <= 0 || k <= 0 || k > OVC_MAX_BEAM) return 0;
     const size_t R = (size_t)B * width, nblk = ((size_t)V + 31) / 32, ld = (nblk + 1) & ~(size_t)1, Rk = (size_t)B * k, T = OVC_MAX_LEN;
@@ -2403,38 +2395,13 @@ extern "C" int ovc_debug_ensemble_update(const float* logits, const float* runni
         (long)B * k * OVC_MAX_LEN > 0x7fffffffL / 8)
         return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_ensemble_update_bytes(M, B, width, V, k) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    TRY(ovc_device_guard());
-    hipStream_t s = ovc_hip_stream(stream);
-    const int rows = B * width, ldt = (rows + 3) & ~3, T = t + 1;
-    const size_t Rk = (size_t)B * k;
-    Bump a{reinterpret_cast<char*>(scratch), 0};
-    EnsembleUpdateArgs en{};
-    en.M = M;
-    for (int i = 0; i < M; ++i) {
-        float* logits_t = a.take<float>((size_t)V * ldt);
-        en.tail[i] = ovc_fused_tail(nullptr, V, 1, ldt);                     // the engine's layout: logits^T and its pieces
-        float* stats = a.take<float>(2 * (size_t)rows * en.tail[i].stats_ld);
-        en.tail[i].stats = stats;
-        en.logits[i] = logits_t;
-        en.row_max_out[i] = row_max_out + (size_t)i * rows; en.row_lsum_out[i] = row_lsum_out + (size_t)i * rows;
-        TRY(ovc_block_pieces_launch(logits + (size_t)i * rows * V, rows, V, en.tail[i].stats_ld, ldt, stats, logits_t, s));
-    }
-    float* alive_out = a.take<float>(Rk); float* lp_out = a.take<float>(Rk * T);
-    int32_t* hist_out = a.take<int32_t>(Rk * T); int32_t* anc_out = a.take<int32_t>(Rk * T); int32_t* next_tok = a.take<int32_t>(Rk);
-    float* lp_in = a.take<float>(Rk * T); int32_t* anc_in = a.take<int32_t>(Rk * T); int32_t* hist_in = a.take<int32_t>(Rk * T);
-    if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess ||
-        hipMemsetAsync(hist_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess)
-        return OVC_ELAUNCH;
-    BeamUpdateArgs& bu = en.p;
-    bu.alive_in = alive; bu.alive_out = alive_out; bu.running_out = running_out;
-    bu.hist_in = hist_in; bu.hist_out = hist_out; bu.lp_in = lp_in; bu.lp_out = lp_out; bu.anc_in = anc_in; bu.anc_out = anc_out;
-    bu.next_tok = next_tok;
-    bu.width = width; bu.k = k; bu.V = V; bu.T = T; bu.t = t; bu.eos = eos;
-    en.running_in = running; en.hot_out = hot_out;
-    TRY(ovc_beam_ensemble_update_launch(en, B, s));
-    TRY(ovc_debug_collect_parents_launch(anc_out, hist_out, B, width, k, T, t, parent_out, word_out, s));
+    const int T = t + 1;
+    StepTest c{logits, nullptr, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    c.members = M; c.hot_out = hot_out;
+    TRY(run_step_test(c, scratch, stream));
     // the step's recorded log-probs: column t of lp_out [B*k][T], as the caller's [B][k]
-    if (hipMemcpy2DAsync(logp_out, sizeof(float), lp_out + t, sizeof(float) * T, sizeof(float), Rk, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    if (hipMemcpy2DAsync(logp_out, sizeof(float), c.lp_out + t, sizeof(float) * T, sizeof(float), (size_t)B * k, hipMemcpyDeviceToDevice,
+                         ovc_hip_stream(stream)) != hipSuccess)
         return OVC_ELAUNCH;
     return OVC_OK;
 }
@@ -2626,7 +2593,7 @@ extern "C" int ovc_debug_vocab_select(const float* x, const float* fc, const flo
     bu.hist_out = hist_out; bu.lp_out = lp_out; bu.anc_out = anc_out; bu.next_tok = next_tok;
     bu.hist_in = hist_out; bu.lp_in = lp_out; bu.anc_in = anc_out;                 // t = 0: nothing is copied from them
     bu.width = width; bu.k = k; bu.V = V; bu.T = 1; bu.t = 0; bu.eos = -1;
-    TRY(ovc_beam_fused_update_launch(bu, tail, running, B, s));
+    TRY(ovc_beam_fused_select_launch(bu, tail, running, FusedSelectOptions{}, B, s));
     return ovc_debug_collect_winners_launch(anc_out, hist_out, running_out, B, width, V, k, chosen, score, s);
 }
 

@@ -102,6 +102,27 @@ def batch(feats, boxes=None, tokens=None, device="cuda", field="region_features"
     return items
 
 
+PLATEAU_V, PLATEAU_WORDS = 4099, 41 * np.arange(100)
+
+
+def plateau_case(k, t, seed, Bb=2):
+    """One step's inputs that send the fused selection through its all-threads ranking (65 .. 1024 survivors): V = 4099, and in
+    every row the 100 words 41 j (one per 32-word block) share the row's maximum 6.0 while every other logit is at most 3.0.  The
+    rows of an image have running scores 1.0 apart -- far more than the rows' log sums differ -- so only the best row's plateau
+    reaches the bound: 100 hot blocks, 100 survivors, ties resolved by the lower flat index.  (With equal rows at k = 8 the 800 hot
+    blocks would overflow the list into the exhaustive rounds.)  Returns (logits [R][V], hist [R][6], running [R], alive [R]),
+    R = Bb rows at t = 0 and Bb * k later; every row is alive."""
+    g = np.random.default_rng(seed)
+    width = 1 if t == 0 else k
+    R = Bb * width
+    logits = g.uniform(-3.0, 3.0, size=(R, PLATEAU_V)).astype(np.float32)
+    logits[:, PLATEAU_WORDS] = 6.0
+    hist = np.zeros((R, 6), np.int32)
+    hist[:, :t] = g.integers(4, PLATEAU_V, size=(R, t))
+    running = np.concatenate([-1.0 * g.permutation(width) - g.random() for _ in range(Bb)]).astype(np.float32)
+    return logits, hist, running, np.ones(R, np.float32)
+
+
 def decided_images(gaps, inner_gaps, tol):
     """Images whose every beam-boundary decision (k-th vs (k+1)-th candidate, each step) and whose
     final best-vs-second ordering had a margin above ``tol`` in the reference run.

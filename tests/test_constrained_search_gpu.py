@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, TINY, TINY_SHAPE, batch, device_model, tiny_case
+from helpers import GOLDEN, PLATEAU_WORDS, TINY, TINY_SHAPE, batch, device_model, plateau_case, tiny_case
 from openviic_amd import constraints, native
 from openviic_amd.builders import build_model
 from openviic_amd.config import model_config
@@ -220,6 +220,20 @@ def test_plain_instance_all_logits_equal():
     running[:] = -1.0
     parents, words = _check_step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL)
     assert (parents.numpy() == 0).all() and words.numpy().tolist() == [[0, 1, 2, 3, 4]] * 3
+
+
+@pytest.mark.parametrize("k", [1, 8])
+def test_both_instances_rank_a_plateau(k):
+    """``helpers.plateau_case``: 100 survivors, the ranking by all threads -- through the plain instance, and through the ban instance
+    with the plateau's second word banned (99 survivors).  The winners are the best row's lowest plateau words."""
+    for t in (0, 3) if k > 1 else (0,):                              # this entry takes width 1 at t = 0 only, as the other tests here
+        logits, hist, running, alive = plateau_case(k, t, seed=10 * k + t)
+        width = 1 if t == 0 else k
+        best = running.reshape(-1, width).argmax(axis=1)
+        parents, words = _check_step(logits, hist, running, alive, k, t, EOS, constraints.NEUTRAL)
+        assert (parents.numpy() == best[:, None]).all() and (words.numpy() == PLATEAU_WORDS[:k]).all()
+        parents, words = _check_step(logits, hist, running, alive, k, t, EOS, (0, 0, (UNK, int(PLATEAU_WORDS[1]))), binding=k > 1)
+        assert (parents.numpy() == best[:, None]).all() and (words.numpy() == np.delete(PLATEAU_WORDS, 1)[:k]).all()
 
 
 @pytest.mark.parametrize("Vv", [53, 4099])

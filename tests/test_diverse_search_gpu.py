@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TINY, TINY_SHAPE, VARIANTS, batch, device_model, tiny_case
+from helpers import PLATEAU_WORDS, TINY, TINY_SHAPE, VARIANTS, batch, device_model, plateau_case, tiny_case
 from openviic_amd import diverse, native
 from openviic_amd.builders import build_model
 from openviic_amd.config import model_config
@@ -149,6 +149,20 @@ def test_kernel_equals_the_rule(Vv, k, G):
             _check_step(*_equal_case(Vv, k, t, seed + 1), k, G, lam, t, what + " (all logits equal)")
             seed += 2
     assert bound == (4 if G > 1 else 0)
+
+
+@pytest.mark.parametrize("k,G", [(1, 1), (8, 4)])
+def test_kernel_ranks_a_plateau(k, G):
+    """``helpers.plateau_case``: every group finds about 100 survivors and ranks them with all threads (a later group's penalised
+    words drop out of its list).  One group is the plain instance."""
+    for t in (0, 3):
+        logits, hist, running, alive = plateau_case(k, t, seed=20 * k + t)
+        for lam in (0.0, 0.5):
+            what = "plateau k {} G {} t {} lambda {}".format(k, G, t, lam)
+            parents, words, _, _, _ = _check_step(logits, hist, running, alive, k, G, lam, t, what)
+            assert np.isin(words, PLATEAU_WORDS).all(), what
+            if t == 0 and lam > 0:                               # every group reads row 0 and pays for the words before it
+                assert (words == PLATEAU_WORDS[:k]).all(), what
 
 
 def test_step_entry_refuses_bad_options():

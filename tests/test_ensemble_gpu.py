@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from ensemble_oracle import EnsembleOracle, members_from
-from helpers import TINY, TINY_SHAPE, batch, decided_images, device_model, tiny_case
+from helpers import PLATEAU_WORDS, TINY, TINY_SHAPE, batch, decided_images, device_model, plateau_case, tiny_case
 from openviic_amd import ensemble, native
 from openviic_amd.ensemble import Ensemble
 from openviic_amd.utils.synthetic import synthetic_boxes, synthetic_features
@@ -253,6 +253,19 @@ def test_step_frozen_images_ties_and_nan():
     x[0, 2, :] = np.nan
     parents, _, _ = _check_step(x, *_state(2 * k, k, 4, frozen=False), k=k, t=2)
     assert not (parents[0] == 2).any()
+
+
+@pytest.mark.parametrize("M", [1, 3])
+@pytest.mark.parametrize("k", [1, 8])
+def test_step_ranks_a_plateau(M, k):
+    """``helpers.plateau_case`` with the same plateau in every member (the other words are each member's own): exactly the best row's
+    100 plateau blocks are hot -- the one place where the branch taken shows -- and their 100 survivors are ranked by all threads."""
+    for t in (0, 3):
+        cases = [plateau_case(k, t, seed=40 * k + t + 100 * m) for m in range(M)]
+        x = np.stack([c[0] for c in cases])
+        parents, words, hot = _check_step(x, cases[0][2], cases[0][3], k, t)
+        assert (hot == 100).all(), hot
+        assert (words == PLATEAU_WORDS[:k]).all()
 
 
 @pytest.mark.parametrize("M", [2, 4])

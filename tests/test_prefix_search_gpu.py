@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TINY, TINY_SHAPE, assert_ids_match_where_decided, batch, device_model, tiny_case
+from helpers import (PLATEAU_WORDS, TINY, TINY_SHAPE, assert_ids_match_where_decided, batch, device_model, plateau_case,
+                     tiny_case)
 from openviic_amd import native, prefix
 from openviic_amd.builders import build_model
 from openviic_amd.config import model_config
@@ -147,6 +148,18 @@ def test_kernel_equals_the_rule(Vv, k):
                 if k > 1:                                                                 # the frozen beam's offer: word 0 at its score
                     assert parents[b, 0] == 1 and words[b, 0] == 0 and run_out[b, 0] == running[b * k + 1]
         seed += 1
+
+
+@pytest.mark.parametrize("k", [1, 8])
+def test_kernel_ranks_a_plateau_at_a_free_step(k):
+    """``helpers.plateau_case`` through the prefix instance at free steps: 100 survivors, ranked by all threads.  t = 0: image 0 has no
+    prefix (image 1 is forced, which keeps the call on the prefix instance); t = 3: both images are past their prefixes."""
+    for t, lengths in ((0, [0, 1]), (3, [1, 2])):
+        logits, hist, running, alive = plateau_case(k, t, seed=30 * k + t)
+        ids = np.full((2, 5), 7, np.int32)
+        parents, words, _ = _check_step(logits, hist, running, alive, k, t, ids, np.asarray(lengths, np.int32))
+        free = [b for b in range(2) if t >= lengths[b]]
+        assert free and (words[free] == PLATEAU_WORDS[:k]).all()
 
 
 def test_step_entry_refuses_a_bad_table():

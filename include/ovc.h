@@ -1131,6 +1131,44 @@ int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, c
 int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
 int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
 
+/* Test hooks: the row operators of the decode path on caller buffers (appended to ABI 8; no struct changes), so that every kernel
+ * instance can be compared with an fp64 restatement at the operator level (tests/test_rowops_gpu.py).  Each calls the launcher the
+ * engine calls; every refusal (OVC_EINVAL, nothing launched) is that launcher's, plus the routing's below and a dropout p outside
+ * [0, 1) or a site outside 0 .. OVC_DROPOUT_SITES - 1.  gate: NULL = the ungated kernel, otherwise a device int32 (0: nothing is
+ * written).
+ *
+ * ovc_debug_add_norm:  y [rows][d] = LN(drop(sum_s parts[s] + bias) + residual) * gamma + beta (+ add[row % add_rows]), then
+ * 0.1 * (...) + residual with post_tenths = 1, then zeros in the rows whose zero_rows byte is set.  parts [nparts][rows][d] with
+ * part_stride floats between slices; d a multiple of 4, at most 2048.  Routing:
+ *   post_tenths = 1            ovc_layer_norm_post's launcher (nparts = 1, residual; no bias, add, zero_rows, dropout or gate)
+ *   seed != NULL               the dropout AddNorm: nparts in {1, 2, 4}, bias exactly when nparts > 1, residual, no add; the site is
+ *                              (seed, site, threshold and scale of p, drop_cols -- which must equal d); row r is masked as mask
+ *                              row ((r / width) * k + r % width) * T + t
+ *   nparts in {2, 4}           the K-split AddNorm: bias and residual, no add
+ *   nparts = 1, no bias        the plain AddNorm: residual, add and zero_rows optional
+ * ovc_debug_add_norm_form launches nothing and touches no device: from the same routing and the launchers' selection function it
+ * returns the instance such a call takes (each argument but nparts, post_tenths and d is "given or not"), coded
+ *   family * 1000 + kVecs * 100 + kParts * 10 + 2 * kBias + kRes,   kVecs in {1, 2, 4, 8} by d (<= 256, 512, 1024, 2048)
+ *   family 1 layer_norm_rows   2 layer_norm_rows_gated   3 layer_norm_rows_dropout (gated or not)   4 the post form
+ * e.g. 2843 = the gated 4-slice AddNorm of a row wider than 1024; or OVC_EINVAL.
+ *
+ * ovc_debug_dropout_rows: x [rows][cols] = (keep ? x * s : 0) + residual in place (residual may be NULL); the mask row of row r is
+ * rowmap[r] (taken as unsigned) when rowmap != NULL, else as above.  ovc_debug_meshed_mix: out [n] = (sum_l sigmoid(alpha[l][n]) *
+ * enc[l][n]) / divisor.  ovc_debug_leaky_residual: y [rows][ldy] = residual + scale * leaky_relu(x, slope) over cols columns
+ * (residual may be NULL; y may be x).  ovc_debug_sigmoid_gate: y [n] = a * sigmoid(g). */
+int ovc_debug_add_norm(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
+                       const float* gamma, const float* beta, const float* add, int add_rows, const uint8_t* zero_rows, float eps,
+                       int post_tenths, float* y, int rows, int d, const int64_t* seed, int site, float p, int drop_cols, int width,
+                       int k, int T, int t, const int32_t* gate, ovc_stream stream);
+int ovc_debug_add_norm_form(int nparts, int bias, int residual, int add, int post_tenths, int dropout, int gated, int d);
+int ovc_debug_dropout_rows(float* x, const float* residual, int rows, int cols, const int64_t* seed, int site, float p, int drop_cols,
+                           int width, int k, int T, int t, const int32_t* rowmap, const int32_t* gate, ovc_stream stream);
+int ovc_debug_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, const int32_t* gate,
+                         ovc_stream stream);
+int ovc_debug_leaky_residual(const float* x, int ldx, const float* residual, int ldr, float slope, float scale, float* y, int ldy,
+                             int rows, int cols, ovc_stream stream);
+int ovc_debug_sigmoid_gate(const float* a, const float* g, float* y, long n, const int32_t* gate, ovc_stream stream);
+
 /* Test hook (tests/test_attention_maps_gpu.py): ovc_cross_attention_maps on raw operands, as ovc_attention_maps launches it for one
  * layer and level -- q [b, nq, h*d_k], k [b, nk, h*d_k], mask [b, nk] (the image's padding regions; NULL: none), m slot keys
  * m_k [m, h*d_k] taken times sqrtf(d_k) -> P [b, h, nq, ld], ld = nk + m rounded up to 4. */

@@ -88,17 +88,46 @@ __global__ __launch_bounds__(256) void dropout_rows_kernel(float* __restrict__ x
 #undef OVC_LN_PARAMS
 #undef OVC_LN_ARGS
 
+// ---- which instance an AddNorm launch takes ---------------------------------------------------------------------------------
+// ONE selection function for the launchers below and for the form query of the test hook (ovc_debug_add_norm_form): the choice is
+// a function of (d, the operand set, post / dropout / gated) alone and is coded (include/ovc.h)
+//   family * 1000 + kVecs * 100 + kParts * 10 + 2 * kBias + kRes
+//   family 1 layer_norm_rows<kVecs, kParts, kBias, kRes>           2 layer_norm_rows_gated<...>         (a gate pointer)
+//          3 layer_norm_rows_dropout<kVecs, kParts, kBias> (kRes)  4 layer_norm_rows<kVecs, 1, false, true, kPostTenths>
+// kVecs: the float4 per lane that hold a row of d floats, rounded up to an instance built (1, 2, 4, 8).  The dropout kernels
+// take their gate as an argument, so a gated dropout launch is family 3 too.
+enum { kLnPlain = 1, kLnGated = 2, kLnDropout = 3, kLnPost = 4 };
+int layer_norm_form(int d, int parts, bool bias, bool res, int post_tenths, bool dropout, bool gated) {
+    if (d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
+    const int vecs = ((d >> 2) + 63) / 64;
+    const int kvecs = vecs <= 1 ? 1 : (vecs <= 2 ? 2 : (vecs <= 4 ? 4 : 8));
+    const int family = post_tenths > 0 ? kLnPost : (dropout ? kLnDropout : (gated ? kLnGated : kLnPlain));
+    return family * 1000 + kvecs * 100 + parts * 10 + (bias ? 2 : 0) + (res ? 1 : 0);
+}
+inline int ln_form_family(int form) { return form / 1000; }
+// OVC_LN(V) by the kVecs of a form
+#define OVC_LN_BY_VECS(form)                                                                                                    \
+    do {                                                                                                                        \
+        switch ((form) / 100 % 10) {                                                                                            \
+            case 1: OVC_LN(1); break;                                                                                           \
+            case 2: OVC_LN(2); break;                                                                                           \
+            case 4: OVC_LN(4); break;                                                                                           \
+            default: OVC_LN(8); break;                                                                                          \
+        }                                                                                                                       \
+    } while (0)
+
 template <int kParts, bool kBias, bool kRes, int kPostTenths = 0>
 int launch_layer_norm(const float* x, long part_stride, const float* bias, const float* residual, const float* gamma,
                       const float* beta, const float* add, int add_rows, const uint8_t* zero_rows, float eps, float* y,
                       int rows, int d, hipStream_t stream, const int32_t* gate = nullptr) {
-    const int vecs = ((d >> 2) + 63) / 64;
+    const int form = layer_norm_form(d, kParts, kBias, kRes, kPostTenths, false, gate != nullptr);
+    if (form < 0) return form;
     const dim3 grid((rows + 3) / 4), block(256);
     if constexpr (kPostTenths == 0) {
-        if (gate) {
+        if (ln_form_family(form) == kLnGated) {
 #define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows_gated<V, kParts, kBias, kRes>), grid, block, 0, stream, x, part_stride, bias, \
                                      residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, gate)
-            if (vecs <= 1) OVC_LN(1); else if (vecs <= 2) OVC_LN(2); else if (vecs <= 4) OVC_LN(4); else OVC_LN(8);
+            OVC_LN_BY_VECS(form);
 #undef OVC_LN
             OVC_RETURN_IF_LAUNCH_FAILED();
             return OVC_OK;
@@ -106,7 +135,7 @@ int launch_layer_norm(const float* x, long part_stride, const float* bias, const
     }
 #define OVC_LN(V) hipLaunchKernelGGL((layer_norm_rows<V, kParts, kBias, kRes, kPostTenths>), grid, block, 0, stream, x, part_stride, bias, \
                                      residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d)
-    if (vecs <= 1) OVC_LN(1); else if (vecs <= 2) OVC_LN(2); else if (vecs <= 4) OVC_LN(4); else OVC_LN(8);
+    OVC_LN_BY_VECS(form);
 #undef OVC_LN
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
@@ -328,7 +357,8 @@ int ovc_layer_norm_parts(const float* parts, int nparts, long part_stride, const
                          const float* gamma, const float* beta, const uint8_t* zero_rows, float eps, float* y,
                          int rows, int d, hipStream_t stream, const int32_t* gate) {
     if (!parts || !bias || !residual || !gamma || !beta || !y || rows <= 0 || d <= 0 || (d & 3) || d > 64 * 4 * kMaxVec) return OVC_EINVAL;
-    if ((part_stride & 3) || !ovc_aligned16(parts) || !ovc_aligned16(y) || !ovc_aligned16(bias) || !ovc_aligned16(residual)) return OVC_EINVAL;
+    if ((part_stride & 3) || !ovc_aligned16(parts) || !ovc_aligned16(y) || !ovc_aligned16(bias) || !ovc_aligned16(residual) ||
+        !ovc_aligned16(gamma) || !ovc_aligned16(beta)) return OVC_EINVAL;
     if (nparts == 2) return launch_layer_norm<2, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
     if (nparts == 4) return launch_layer_norm<4, true, true>(parts, part_stride, bias, residual, gamma, beta, nullptr, 0, zero_rows, eps, y, rows, d, stream, gate);
     return OVC_EINVAL;
@@ -342,17 +372,16 @@ int ovc_layer_norm_parts_dropout(const float* parts, int nparts, long part_strid
     if ((nparts == 1) != (bias == nullptr)) return OVC_EINVAL;
     if ((part_stride & 3) || !ovc_aligned16(parts) || !ovc_aligned16(y) || (bias && !ovc_aligned16(bias)) || !ovc_aligned16(residual) ||
         !ovc_aligned16(gamma) || !ovc_aligned16(beta)) return OVC_EINVAL;
-    const int vecs = ((d >> 2) + 63) / 64;
+    if (nparts != 1 && nparts != 2 && nparts != 4) return OVC_EINVAL;
+    const int form = layer_norm_form(d, nparts, bias != nullptr, true, 0, true, gate != nullptr);
+    if (form < 0) return form;
     const dim3 grid((rows + 3) / 4), block(256);
-#define OVC_LN(V, P, Bs) hipLaunchKernelGGL((layer_norm_rows_dropout<V, P, Bs>), grid, block, 0, stream, parts, part_stride, bias, residual, \
-                                            gamma, beta, (const float*)nullptr, 0, zero_rows, eps, y, rows, d, drop, key, gate)
-#define OVC_LN_V(P, Bs) do { if (vecs <= 1) OVC_LN(1, P, Bs); else if (vecs <= 2) OVC_LN(2, P, Bs); else if (vecs <= 4) OVC_LN(4, P, Bs); else OVC_LN(8, P, Bs); } while (0)
-    if (nparts == 1) OVC_LN_V(1, false);
-    else if (nparts == 2) OVC_LN_V(2, true);
-    else if (nparts == 4) OVC_LN_V(4, true);
-    else return OVC_EINVAL;
-#undef OVC_LN_V
+#define OVC_LN_DROP(V, P, Bs) hipLaunchKernelGGL((layer_norm_rows_dropout<V, P, Bs>), grid, block, 0, stream, parts, part_stride, bias, residual, \
+                                                 gamma, beta, (const float*)nullptr, 0, zero_rows, eps, y, rows, d, drop, key, gate)
+#define OVC_LN(V) do { if (nparts == 1) OVC_LN_DROP(V, 1, false); else if (nparts == 2) OVC_LN_DROP(V, 2, true); else OVC_LN_DROP(V, 4, true); } while (0)
+    OVC_LN_BY_VECS(form);
 #undef OVC_LN
+#undef OVC_LN_DROP
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
@@ -430,6 +459,7 @@ extern "C" int ovc_gated_accumulate(const float* acc_in, const float* alpha, con
 int ovc_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out, hipStream_t stream,
                    const int32_t* gate) {
     if (!alpha || !enc || !out || levels <= 0 || n <= 0 || (n & 3)) return OVC_EINVAL;
+    if (!ovc_aligned16(alpha) || !ovc_aligned16(enc) || !ovc_aligned16(out)) return OVC_EINVAL;       // float4 accesses
     if (gate) hipLaunchKernelGGL(meshed_mix_kernel_gated, dim3(elementwise_grid(n / 4)), dim3(256), 0, stream, alpha, enc, levels, n / 4, divisor,
                                  out, gate);
     else hipLaunchKernelGGL(meshed_mix_kernel, dim3(elementwise_grid(n / 4)), dim3(256), 0, stream, alpha, enc, levels, n / 4, divisor, out);
@@ -454,4 +484,73 @@ extern "C" int ovc_box_relation_weights(const float* boxes, int b, int n, const 
                        trig, w);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+// =================================================================================================
+// Test hooks (include/ovc.h): the row-operator launchers of the engine on caller buffers.  Thin: every refusal but the routing's
+// own is the launcher's, and the instance is chosen by layer_norm_form, as in the launchers.
+// =================================================================================================
+// Which launcher an AddNorm call of the hook goes to: 4 ovc_layer_norm_post_launch, 3 ovc_layer_norm_parts_dropout,
+// 2 ovc_layer_norm_parts, 1 ovc_layer_norm_gated; OVC_EINVAL for an operand set none of them takes.
+static int debug_add_norm_route(int nparts, bool bias, bool residual, bool add, int post_tenths, bool dropout, bool gated) {
+    if (post_tenths != 0)
+        return post_tenths == 1 && nparts == 1 && !bias && residual && !add && !dropout && !gated ? 4 : OVC_EINVAL;
+    if (dropout) return (nparts == 1 || nparts == 2 || nparts == 4) && (nparts == 1) == !bias && residual && !add ? 3 : OVC_EINVAL;
+    if (nparts == 2 || nparts == 4) return bias && residual && !add ? 2 : OVC_EINVAL;
+    return nparts == 1 && !bias ? 1 : OVC_EINVAL;
+}
+
+extern "C" int ovc_debug_add_norm_form(int nparts, int bias, int residual, int add, int post_tenths, int dropout, int gated, int d) {
+    const int route = debug_add_norm_route(nparts, bias != 0, residual != 0, add != 0, post_tenths, dropout != 0, gated != 0);
+    if (route < 0) return route;
+    return layer_norm_form(d, nparts, bias != 0, residual != 0, post_tenths, dropout != 0, gated != 0);
+}
+
+static bool debug_dropout_site(const int64_t* seed, int site, float p, int drop_cols, DropoutSite* drop) {
+    if (!(p >= 0.f && p < 1.f) || site < 0 || site >= OVC_DROPOUT_SITES) return false;
+    *drop = DropoutSite{seed, (uint32_t)site, ovc_dropout_threshold(p), ovc_dropout_scale(p), drop_cols};
+    return true;
+}
+
+extern "C" int ovc_debug_add_norm(const float* parts, int nparts, long part_stride, const float* bias, const float* residual,
+                                  const float* gamma, const float* beta, const float* add, int add_rows, const uint8_t* zero_rows,
+                                  float eps, int post_tenths, float* y, int rows, int d, const int64_t* seed, int site, float p,
+                                  int drop_cols, int width, int k, int T, int t, const int32_t* gate, ovc_stream stream) {
+    const int route = debug_add_norm_route(nparts, bias != nullptr, residual != nullptr, add != nullptr, post_tenths, seed != nullptr,
+                                           gate != nullptr);
+    if (route < 0) return route;
+    hipStream_t s = ovc_hip_stream(stream);
+    if (route == 1) return ovc_layer_norm_gated(parts, residual, gamma, beta, add, add_rows, zero_rows, eps, y, rows, d, s, gate);
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    if (route == 4) return zero_rows ? OVC_EINVAL : ovc_layer_norm_post_launch(parts, residual, gamma, beta, eps, 0.1f, y, rows, d, s);
+    if (route == 2) return ovc_layer_norm_parts(parts, nparts, part_stride, bias, residual, gamma, beta, zero_rows, eps, y, rows, d, s, gate);
+    DropoutSite drop;
+    if (!debug_dropout_site(seed, site, p, drop_cols, &drop)) return OVC_EINVAL;
+    return ovc_layer_norm_parts_dropout(parts, nparts, part_stride, bias, residual, gamma, beta, zero_rows, eps, y, rows, d, drop,
+                                        DecodeRowKey{width, k, T, t}, s, gate);
+}
+
+extern "C" int ovc_debug_dropout_rows(float* x, const float* residual, int rows, int cols, const int64_t* seed, int site, float p,
+                                      int drop_cols, int width, int k, int T, int t, const int32_t* rowmap, const int32_t* gate,
+                                      ovc_stream stream) {
+    DropoutSite drop;
+    if (!debug_dropout_site(seed, site, p, drop_cols, &drop)) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    return ovc_dropout_rows(x, residual, rows, cols, drop, DecodeRowKey{width, k, T, t}, rowmap, ovc_hip_stream(stream), gate);
+}
+
+extern "C" int ovc_debug_meshed_mix(const float* alpha, const float* enc, int levels, long n, float divisor, float* out,
+                                    const int32_t* gate, ovc_stream stream) {
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    return ovc_meshed_mix(alpha, enc, levels, n, divisor, out, ovc_hip_stream(stream), gate);
+}
+
+extern "C" int ovc_debug_leaky_residual(const float* x, int ldx, const float* residual, int ldr, float slope, float scale, float* y,
+                                        int ldy, int rows, int cols, ovc_stream stream) {
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    return ovc_leaky_residual(x, ldx, residual, ldr, slope, scale, y, ldy, rows, cols, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_sigmoid_gate(const float* a, const float* g, float* y, long n, const int32_t* gate, ovc_stream stream) {
+    return ovc_sigmoid_gate_gated(a, g, y, n, ovc_hip_stream(stream), gate);
 }

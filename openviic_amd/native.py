@@ -299,6 +299,15 @@ SIGNATURES = {
     "ovc_debug_decode_cross_form": (c_int, [c_int, c_int, c_int, c_int]),
     "ovc_debug_gemm": (c_int, [POINTER(GemmCall), c_int, c_void_p]),
     "ovc_debug_gemm_plan": (c_int, [POINTER(GemmCall), c_int, POINTER(c_int32)]),
+    "ovc_debug_add_norm": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float,
+                                   c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p]),
+    "ovc_debug_add_norm_form": (c_int, [c_int] * 8),
+    "ovc_debug_dropout_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_meshed_mix": (c_int, [c_void_p, c_void_p, c_int, c_long, c_float, c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_leaky_residual": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ovc_debug_sigmoid_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -328,7 +337,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_debug_beam_prefix_update_bytes", "ovc_debug_beam_prefix_update",
                  "ovc_beam_search_diverse_workspace_bytes", "ovc_beam_search_diverse", "ovc_beam_search_diverse_graph",
                  "ovc_debug_beam_diverse_update_bytes", "ovc_debug_beam_diverse_update",
-                 "ovc_caption_set_workspace_bytes", "ovc_caption_set")
+                 "ovc_caption_set_workspace_bytes", "ovc_caption_set",
+                 "ovc_debug_add_norm", "ovc_debug_add_norm_form", "ovc_debug_dropout_rows", "ovc_debug_meshed_mix",
+                 "ovc_debug_leaky_residual", "ovc_debug_sigmoid_gate")
 
 _lib = None
 

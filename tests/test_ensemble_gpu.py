@@ -67,6 +67,7 @@ def _equal(a, b, what=""):
 @pytest.mark.parametrize("variant", ["standard_transformer", "meshed_memory_transformer"])
 def test_one_member_is_the_plain_search(variant):
     lib = native.load()
+    lib.ovc_graph_cache_clear()                                       # entries are counted below: none is evicted from an empty cache
     model = _member(variant, 11)
     items = _items(variant)
     eng = model._fused_engine()

@@ -630,9 +630,9 @@ int ovc_sample_choice(const float* logits, long ld_row, long ld_word, int rows, 
  * [0, V), a duplicate, <pad> or <eos> (min_length keeps <eos> out); V - n_banned - 1 - max_len < k (so that every live row keeps k
  * finite candidates at every step); precision != 0; a vocabulary of more than 16 384 words; and everything ovc_beam_search
  * refuses.  ovc_search_constraints_ok: 1 when (m, k, options) is in this scope, else 0; launches nothing.
- * Not covered: length penalty or normalisation, repetition penalty, forced words (lexical constraints), a per-step callback of
- * allowed words, groups under a ban set (a given prefix is ovc_beam_search_prefix and diverse beam search ovc_beam_search_diverse,
- * below; neither combines with a ban set),
+ * Not covered: length penalty or normalisation, repetition penalty, a per-step callback of allowed words, groups under a ban set (a
+ * given prefix is ovc_beam_search_prefix, diverse beam search ovc_beam_search_diverse and forced words -- lexical constraints --
+ * ovc_beam_search_forced, below; none of them combines with a ban set),
  * more than OVC_MAX_BANNED ids, constraints under dropout, in the early-exit forms, in the split-precision modes or when sampling.
  * ovc_debug_beam_constrained_update: test entry, ONE step of the production kernel (the search's own routing: the constrained
  * instance with active options, the plain selection with neutral ones) on caller-given device inputs -- row-major
@@ -742,6 +742,62 @@ int ovc_debug_beam_diverse_update(const float* logits, const int32_t* hist, cons
                                   int V, int k, int T, int t, int eos, int G, float lambda, void* scratch, size_t scratch_bytes,
                                   int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out, float* row_lsum_out,
                                   ovc_stream stream);
+
+/* Beam search with forced words (lexically constrained beam search: Anderson et al., EMNLP 2017): the search of ovc_beam_search
+ * whose captions must contain given words (appended to ABI 8; no struct changes).  The rule (openviic_amd/forced.py mirrors it in
+ * numpy):
+ * Table.  forced [B][C] int32 word ids in HOST memory, 1 <= C <= OVC_MAX_FORCED: image b's C words c_0 .. c_{C-1}, each in [0, V),
+ * distinct within the row, none <pad>, <bos> or <eos>.  The call copies the table into its workspace in stream order, outside any
+ * captured graph; it must stay valid until the stream has passed that copy.
+ * Banks.  G = 2^C banks, one per subset s of met words (bit i of s: c_i has been emitted); k' = k / G slots per bank, k % G == 0,
+ * k <= OVC_MAX_BEAM -- C = 1: k in {2, 4, 6, 8}; C = 2: k in {4, 8}; C = 3: k = 8.  Bank s owns the slots s k' .. (s + 1) k' - 1 at
+ * every step, and a row's met set is its slot's bank: no further state.
+ * Rows.  Width W = 1 at t = 0, else k.  A row is live (alive != 0), frozen (alive 0 and a running score above -inf: it has ended)
+ * or empty (alive 0, running score -inf).  At t = 0 the image's one row counts as a row of bank 0.
+ * Candidates.  Every (row r, word w) of a live row has one target bank: the row's bank s_r, or s_r + {i} where w = c_i and i is not
+ * in s_r.  So bank s ranks (a) from each live row of bank s every word but the unmet forced words {c_i : i not in s} -- a met c_i is
+ * an ordinary word -- and (b) for every i in s, from each live row of bank s \ {i}, exactly the word c_i.  The score is
+ * run_r + ((x - M_r) - ls_r) with M and ls of the unmodified row: ovc_beam_search's arithmetic and order.  A frozen row offers ONLY
+ * word 0, at its running score, into its own bank; an empty row offers nothing.  This departs from ovc_beam_search's -999 fillers on
+ * purpose: a filler must never cross banks or fill an empty slot.  A candidate that is NaN or -inf beats nothing.
+ * Winners.  Bank s's k' best candidates, (a) and (b) ranked together by (score descending, flat index r * V + w ascending, r the
+ * row inside the image), go into its slots in rank order.  A slot without a candidate becomes empty: running -inf, alive 0, word
+ * <pad>, parent = its own row (row 0 at t = 0), recorded log-probability 0.  Otherwise alive = alive[parent] && word != <eos>, and
+ * history, ancestor table and next input rows are written as by the plain step.  logp_out / all_logp_out stay the model's own
+ * log-probabilities.
+ * Decoder.  The plain step at width k: parents cross banks, so there is no per-bank attention; empty rows are decoded like any row
+ * and never offered.
+ * Final order.  Non-empty slots before empty ones, then more met words first (the bank's population count), then running
+ * descending, then the lower slot; the first out_size are returned.  met_out [B][out_size] int32 (device) takes each returned
+ * caption's bank -- bit i set iff c_i is in the caption -- and -1 for an empty slot.  With out_size = 1 the result is the best
+ * caption among those that satisfy as many forced words as any beam does.
+ * ovc_beam_search_forced: plain launches, all_logp_out as ovc_beam_search.  ovc_beam_search_forced_graph: one captured graph from
+ * the second call; C is part of its key, the words are not: one graph serves every table of a shape.  Workspace:
+ * ovc_forced_workspace_bytes(m, B, N, k, return_probs, C) (ovc_workspace_bytes' layout, the table and the banks behind it; 0: out
+ * of scope).  ovc_search_forced_ok: 1 when (m, k, C) is in this scope, else 0; launches nothing.
+ * OVC_EINVAL, nothing launched: C outside 1..OVC_MAX_FORCED; 2^C not dividing k; a null table or met_out; a word outside [0, V),
+ * repeated within its row, <pad>, <bos> or <eos>; precision != 0; a vocabulary of more than 16 384 words; and everything
+ * ovc_beam_search refuses.
+ * Not covered: multi-word phrases, disjunctive sets (one of several words), more than OVC_MAX_FORCED words, ragged counts (every
+ * image has exactly C words), and forced words together with a ban set, a prefix, groups, dropout, the early-exit forms, an
+ * ensemble, sampling or the split-precision modes.
+ * ovc_debug_beam_forced_update: test entry, ONE step of the production kernel on the inputs of ovc_debug_beam_constrained_update
+ * (width = 1 at t = 0, else k) plus <pad> and the table (HOST memory); the outputs of ovc_debug_beam_diverse_update, an empty slot
+ * showing parent = its own row, word = pad, running = -inf.  scratch: ovc_debug_beam_forced_update_bytes. */
+#define OVC_MAX_FORCED 3
+int ovc_search_forced_ok(const ovc_model* m, int k, int C);
+size_t ovc_forced_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int C);
+int ovc_beam_search_forced(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                           const int32_t* forced, int C, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                           int32_t* met_out, float* all_logp_out, ovc_stream stream);
+int ovc_beam_search_forced_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                 const int32_t* forced, int C, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                 float* logp_out, int32_t* met_out, ovc_stream stream);
+size_t ovc_debug_beam_forced_update_bytes(int B, int width, int V, int k, int T);
+int ovc_debug_beam_forced_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B, int width,
+                                 int V, int k, int T, int t, int eos, int pad, const int32_t* forced, int C, void* scratch,
+                                 size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out,
+                                 float* row_lsum_out, ovc_stream stream);
 
 /* Ensemble beam search: ONE search over the mean of the log-probabilities of M models (the meshed-memory authors'
  * TransformerEnsemble).  Members m = 0..M-1, 1 <= M <= OVC_MAX_ENSEMBLE, read the same features (and the call's boxes, where a

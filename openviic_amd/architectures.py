@@ -18,6 +18,7 @@ import torch
 
 from . import constraints as _constraints
 from . import diverse as _diverse
+from . import forced as _forced
 from . import prefix as _prefix
 from . import distill as _distill
 from . import dropout as _dropout
@@ -499,9 +500,10 @@ class BaseTransformer(Module):
         applies after the log-softmax: ``log_probs`` / ``all_log_probs`` stay the model's own, so the gradient of ``log_probs``
         is the plain search's.  The defaults are the plain call, bit for bit.  Refused by name before any launch or draw: a bad
         option; active constraints with ``fused=False``, ``dropout=True``, an early-exit form, a precision other than 'f32' or a
-        vocabulary of more than 16 384 words; and length penalty, repetition penalty, forced words (lexical constraints),
-        ``prefix_allowed_tokens_fn``, which the engine does not have, and ``num_beam_groups`` / ``diversity_penalty``: diverse beam
-        search is a method of its own, ``diverse_beam_search``, and the keyword form stays refused.
+        vocabulary of more than 16 384 words; and length penalty, repetition penalty and ``prefix_allowed_tokens_fn``, which the
+        engine does not have, and ``forced_words``, ``num_beam_groups`` / ``diversity_penalty``: forced words (lexical constraints)
+        and diverse beam search are methods of their own, ``forced_beam_search`` and ``diverse_beam_search``, and the keyword
+        forms stay refused.
 
         ``prefix`` (fused only; ``ovc_beam_search_prefix``; the rule is stated in ``include/ovc.h`` and
         mirrored by ``openviic_amd.prefix``): an int64 tensor ``(B, P)``, ``0 <= P <= max_len - 1``.  Image ``b`` emits
@@ -596,6 +598,47 @@ class BaseTransformer(Module):
         out = eng.diverse_beam_search(feats, boxes, batch_size, k, G, diversity_penalty, out_size=out_size, return_probs=return_probs)
         result = (out[0], out[1]) + ((out[3],) if return_probs else ())
         return result + ((out[2].long() // (k // G),) if return_groups else ())
+
+    def forced_beam_search(self, input_features, batch_size: int, beam_size: int, forced_words, out_size=1, return_probs=False,
+                           return_met=False, **kwargs):
+        """Beam search with forced words -- lexically constrained beam search (Anderson et al., EMNLP 2017) -- on the HIP engine
+        (``ovc_beam_search_forced``; the rule is stated in ``include/ovc.h`` and mirrored by
+        ``openviic_amd.forced``).  ``forced_words``: an int64 tensor ``(B, C)`` or a nested list, ``1 <= C <= 3`` single word ids per
+        image that its caption must contain.  The ``beam_size`` beams are ``2 ** C`` banks of ``beam_size // 2 ** C`` slots, one
+        bank per subset of the image's words a beam has emitted; a beam moves to the next bank by emitting an unmet word, and the
+        best beam of the bank with the most met words is returned first.  Returns ``(ids [B, out_size, T], log_probs [B, out_size,
+        T])`` -- non-empty slots first, then more met words, then the total score -- plus ``all_log_probs [B, beam_size, T, V]``
+        with ``return_probs`` and ``met [B, out_size]`` (int64, on the device: bit ``i`` set iff ``forced_words[b, i]`` is in the
+        caption, ``-1`` for a slot that no candidate ever reached) with ``return_met``, in this order.  ``log_probs`` /
+        ``all_log_probs`` are the model's own; the result is plain tensors without gradient.
+
+        Refused by name before any launch and any random draw: a bad table (a wrong dtype, rank or batch size, ``C`` outside
+        ``1..3``, an id outside ``[0, V)``, ``<pad>``, ``<bos>`` or ``<eos>``, a repeated word, ragged rows), a ``beam_size`` above
+        8 or no multiple of ``2 ** C``, ``out_size`` outside ``1..beam_size``; ``fused=False`` or any other keyword (the host loop
+        has no banks; bans, a prefix, groups, dropout and the early-exit forms do not combine with forced words); a precision
+        other than 'f32'; more than 16 384 words; and a model in ``train()`` mode with gradients enabled (no SCST through a
+        constrained search: call ``eval()`` or use ``no_grad``).  Multi-word phrases, disjunctive sets, more than 3 words and
+        ragged counts are out of scope."""
+        for name in kwargs:
+            if name == "fused":
+                raise engine.native.OvcError("forced_beam_search(fused=...): there is no such keyword -- the search runs on the engine "
+                                             "only, the host loop has no banks")
+            raise engine.native.OvcError("forced_beam_search({}=...) is not covered -- forced words combine with nothing but out_size, "
+                                         "return_probs and return_met".format(name))
+        dec = self.decoder
+        k, _, table = _forced.check(forced_words, batch_size, beam_size, dec.fc.out_features, dec.padding_idx, self.vocab.bos_idx,
+                                    self.eos_idx)
+        if isinstance(out_size, bool) or not isinstance(out_size, int) or not 1 <= out_size <= k:
+            raise engine.native.OvcError("forced_beam_search: out_size must lie in 1..beam_size = {}, got {!r}".format(k, out_size))
+        eng = self._fused_engine()
+        eng.check_forced(batch_size, k, table.tolist())
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise engine.native.OvcError("forced_beam_search: the model is in train() mode with gradients enabled -- there is no "
+                                         "SCST through a constrained search; call model.eval() or use torch.no_grad()")
+        feats, boxes = self._engine_inputs(input_features)
+        out = eng.forced_beam_search(feats, boxes, batch_size, k, table.tolist(), out_size=out_size, return_probs=return_probs)
+        result = (out[0], out[1]) + ((out[3],) if return_probs else ())
+        return result + ((out[2].long(),) if return_met else ())
 
     def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False, temperature=1.0,
                top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0, banned_words=None):

@@ -293,6 +293,20 @@ __global__ __launch_bounds__(kFusedThreads) void beam_diverse_update_kernel(Beam
                                                                             long ld_row, long ld_word, int G, float lambda) {
 #include "bodies/beam_diverse_update.inc"
 }
+
+// Forced-word selection (ovc_beam_search_forced, include/ovc.h: the rule): the fused selection and bookkeeping of one image whose k
+// beams are 2^C banks of k / 2^C slots, one bank per subset of the image's C forced words that a beam has emitted.  Phase A once for
+// all rows; then the banks one after another inside the workgroup, each with its own bound, hot blocks, survivors and ranks over its
+// own rows' words (an unmet forced word belongs to another bank: its block feeds no lower bound and the survivor pass skips it) plus
+// the single-logit candidates that enter the bank from the banks one word short.  No -999 fillers: a slot without a candidate is
+// empty.  The word table [B][C] is read from device memory, so one captured graph serves every table of a shape.  Its own body: the
+// other instances' text does not change.  LDS: the diverse instance's lists + 12 bytes of words.
+__global__ __launch_bounds__(kFusedThreads) void beam_forced_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                           int stats_ld, const float* __restrict__ running_in,
+                                                                           long ld_row, long ld_word, const int32_t* __restrict__ forced,
+                                                                           int C, int pad) {
+#include "bodies/beam_forced_update.inc"
+}
 #undef FUSED_SELECT_ROW
 #undef FUSED_SELECT_LOGP
 
@@ -487,6 +501,13 @@ __global__ __launch_bounds__(64) void beam_finalize_gated_kernel(BeamFinalArgs e
 #include "bodies/beam_finalize.inc"
 }
 
+// The forced-word search's final ordering (include/ovc.h, ovc_beam_search_forced): non-empty slots first, then the banks with more met
+// words, then the total score, then the lower slot; met_out [B][k] takes every slot's bank in that order, -1 for an empty slot.  An
+// instance of its own: beam_finalize_kernel's text does not change.
+__global__ __launch_bounds__(64) void beam_finalize_forced_kernel(BeamFinalArgs p, int kb, int32_t* __restrict__ met_out) {
+#include "bodies/beam_finalize_forced.inc"
+}
+
 // all_out[b, o, t, :] = all_buf[t][b][order[b][o]][:] (t = 0: the single live beam)   (beam_search.py:68-72,103-107)
 __global__ __launch_bounds__(256) void beam_gather_all_kernel(const float* __restrict__ all_buf, const int* __restrict__ order,
                                                               int B, int k, int T, int V, float* __restrict__ all_out) {
@@ -570,14 +591,18 @@ bool ovc_beam_diversity_ok(int k, int G, float lambda) {
     return k >= 1 && k <= kMaxK && G >= 1 && G <= k && k % G == 0 && lambda >= 0.0f && lambda <= 1e30f;      // NaN fails both bounds
 }
 
-// The fused selection of a step, one launch: the instance the options name -- constrained, else prefix, else diverse, else the plain
-// one or its gated form.  The options reach the kernel by value (baked into a captured graph); of a prefix table only the device
+bool ovc_beam_forced_ok(int k, int C) {
+    return C >= 1 && C <= OVC_MAX_FORCED && k >= 1 && k <= kMaxK && k % (1 << C) == 0;
+}
+
+// The fused selection of a step, one launch: the instance the options name -- constrained, else prefix, else diverse, else forced
+// words, else the plain one or its gated form.  The options reach the kernel by value (baked into a captured graph); of a prefix table only the device
 // addresses do, the contents are read by the kernel.  The early-exit forms (p.alive_count, the gate) are the plain instance's alone.
 int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const FusedSelectOptions& o, int B,
                                  hipStream_t stream) {
     const BeamConstraints& cons = o.cons;
     const BeamPrefix& pre = o.prefix;
-    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0;
+    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0 && o.forced_C == 0;
     if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || (!plain && (p.alive_count || o.gate))) return OVC_EINVAL;
     if (!plain && (p.T < 1 || p.t < 0 || p.t >= p.T)) return OVC_EINVAL;
     const dim3 grid(B), block(kFusedThreads);
@@ -599,6 +624,12 @@ int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, co
         if (p.t == 0 ? p.width != 1 && p.width != o.groups : p.width != p.k) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_diverse_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.groups, o.diversity);
+    } else if (o.forced_C != 0) {
+        // the banks' rows are the image's one row at step 0 and every bank's own slots later: the kernel indexes rows with this
+        if (!o.forced || !ovc_beam_forced_ok(p.k, o.forced_C) || p.V < p.k || o.pad < 0 || o.pad >= p.V) return OVC_EINVAL;
+        if (p.width != (p.t == 0 ? 1 : p.k)) return OVC_EINVAL;
+        hipLaunchKernelGGL(beam_forced_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, o.forced, o.forced_C, o.pad);
     } else if (o.gate)
         hipLaunchKernelGGL(beam_fused_update_kernel_gated, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.gate);
@@ -772,6 +803,13 @@ int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const
 
 int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream) {
     hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(64), 0, stream, p);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_out, int B, hipStream_t stream) {
+    if (B <= 0 || !met_out || !p.order_out || !ovc_beam_forced_ok(p.k, C) || p.out_size < 1 || p.out_size > p.k) return OVC_EINVAL;
+    hipLaunchKernelGGL(beam_finalize_forced_kernel, dim3(B), dim3(64), 0, stream, p, p.k >> C, met_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

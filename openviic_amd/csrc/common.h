@@ -297,6 +297,8 @@ struct BeamPrefix {
 };
 // The diverse search's options (include/ovc.h, ovc_beam_search_diverse): G groups dividing k, a finite strength in [0, 1e30].
 bool ovc_beam_diversity_ok(int k, int G, float lambda);
+// The forced-word search's sizes (include/ovc.h, ovc_beam_search_forced): 1 <= C <= OVC_MAX_FORCED, 2^C dividing k <= OVC_MAX_BEAM.
+bool ovc_beam_forced_ok(int k, int C);
 // The options of a step's fused selection, as the search call holds them; all zero: the plain selection.
 struct FusedSelectOptions {
     BeamConstraints cons;           // active(): a per-row ban set (p.hist_in holds the rows' histories)
@@ -304,9 +306,13 @@ struct FusedSelectOptions {
     int groups; float diversity;    // groups != 0: that many groups of k / groups slots under the Hamming penalty; p.width is 1
                                     // (or groups) at p.t == 0, else p.k
     const int32_t* gate;            // the plain selection's gated form (ovc_gate_closed)
+    const int32_t* forced; int forced_C, pad;   // forced_C != 0: the forced-word instance -- the table [B][forced_C] in DEVICE memory
+                                    // (ids in [0, V), the caller's to check), 2^forced_C banks of k >> forced_C slots, and the
+                                    // <pad> id an empty slot takes; p.width is 1 at p.t == 0, else p.k
 };
 // Selection + update of a step, one launch: the constrained instance, else the prefix one, else the diverse one, else the plain
-// one.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count and the gate go with the plain instance only.
+// one.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count and the gate go with the plain instance only.  (Forced words:
+// behind the diverse instance.)
 int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const FusedSelectOptions& o, int B,
                                  hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
@@ -371,6 +377,9 @@ struct BeamFinalArgs {
                              // written and are emitted as word 0 / log-prob 0 -- what the remaining steps would have appended
 };
 int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream);
+// The final ordering of a search with forced words: (non-empty, met words descending, score descending, slot ascending); met_out
+// [B][k] int32 takes the bank of every slot in that order, -1 for an empty slot.  p.order_out is required, p.steps_run is not read.
+int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_out, int B, hipStream_t stream);
 // The final ordering of a gated search: the number of steps that ran, S, is read from the device -- S = 1 + the first i < T - 1
 // with alive_count[i] == 0, else T (step t >= 1 ran iff alive_count[t - 1] != 0) -- and the state is read from buf[S & 1] (dead
 // steps swap no buffers).  Positions S..T-1 are emitted as word 0 / log-prob 0, as BeamFinalArgs::steps_run does; block 0 writes

@@ -137,6 +137,8 @@ struct Workspace {
                                                   // the drawn words and the kept counts [R]
     int32_t* prefix_ids; int32_t* prefix_len;     // ovc_beam_search_prefix: the call's table [B][P] / [B] (refreshed outside the
                                                   // captured body)
+    int32_t* forced_words; int32_t* forced_met;   // ovc_beam_search_forced: the call's table [B][C] (refreshed the same way) and the
+                                                  // final ordering's banks [B][k]
     // teacher-forced forward (a ForwardCall; rows = B*S*T): the self-attention mask [B*S][T][T], the target words, the logit of
     // each row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -1025,6 +1027,11 @@ struct SearchCall {
     // the plain call: groups stays 0.  slot_out: the caller's [B][out_size], the beam slot of each returned caption, or nullptr.
     int groups; float diversity; int32_t* slot_out;
     bool diverse() const { return groups != 0; }
+    // Forced words (ovc_beam_search_forced): forced_C words per image in 2^forced_C banks of k >> forced_C slots; the caller's table
+    // [B][forced_C] in HOST memory, copied to the workspace outside any captured body, and the caller's met_out [B][out_size].  A
+    // sizer or predicate states forced_C alone.
+    int forced_C; const int32_t* forced_words; int32_t* met_out;
+    bool forced() const { return forced_C != 0; }
     // The rows of an image at step t.  Step 0 has one row per image; a diverse search runs it once per group (the same <bos> row, the
     // same bits), so that every group has a first cache row and a first ancestor of its own and is a search of k / groups beams
     // from its first step on (a search of one step, T = 1, has no later step to prepare: one row).
@@ -1050,7 +1057,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c);
 // nothing else in the call.
 bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
     if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
-    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() ||
+    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() || c.forced() ||
         (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
         return false;
     SearchCall alone = c;
@@ -1089,6 +1096,12 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                         (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.groups < 2 ||
                         !ovc_beam_diversity_ok(c.k, c.groups, c.diversity)))
         return false;
+    // forced words: fp32, the fused vocabulary tail, beams (no draw), nothing else in the call, plain launches or the whole-search
+    // graph, and the sizes' own scope
+    if (c.forced() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.has_options || c.plan || c.constrained() ||
+                       c.prefixed() || c.diverse() || c.ens_M != 0 || (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
+                       !ovc_beam_forced_ok(c.k, c.forced_C)))
+        return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
 }
@@ -1107,6 +1120,12 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
         Bump a{reinterpret_cast<char*>(base), w.bytes};
         w.prefix_ids = a.take<int32_t>((size_t)c.B * c.prefix_P);
         w.prefix_len = a.take<int32_t>((size_t)c.B);
+        w.bytes = (a.off + 255) & ~(size_t)255;
+    }
+    if (c.forced()) {                             // likewise behind ovc_beam_search's layout
+        Bump a{reinterpret_cast<char*>(base), w.bytes};
+        w.forced_words = a.take<int32_t>((size_t)c.B * c.forced_C);
+        w.forced_met = a.take<int32_t>((size_t)c.B * c.k);
         w.bytes = (a.off + 255) & ~(size_t)255;
     }
     return w;
@@ -1425,11 +1444,13 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_shaped_update_launch(bu, tail, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
-        else if (c.constrained() || c.prefixed() || c.diverse() || !(debug_skip() & 8)) {
+        else if (c.constrained() || c.prefixed() || c.diverse() || c.forced() || !(debug_skip() & 8)) {
             // the one branch of a beam step: the call's options pick the instance -- a per-row ban set, the staged prefix table, the
-            // groups under the Hamming penalty, else the plain selection or its gated form
+            // groups under the Hamming penalty, the banks of the staged forced words, else the plain selection or its gated form
             const BeamPrefix pre = c.prefixed() ? BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P} : BeamPrefix{};
-            RUN(ovc_beam_fused_select_launch(bu, tail, w.running[cur], FusedSelectOptions{c.cons, pre, c.groups, c.diversity, e.gate}, B, s));
+            FusedSelectOptions opt{c.cons, pre, c.groups, c.diversity, e.gate};
+            if (c.forced()) { opt.forced = w.forced_words; opt.forced_C = c.forced_C; opt.pad = m->pad_idx; }
+            RUN(ovc_beam_fused_select_launch(bu, tail, w.running[cur], opt, B, s));
         }
         if (return_probs) {   // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
             // step 0 is stored as one row per image: a diverse search's rows of step 0 (a copy per group) are staged in the block of
@@ -1449,7 +1470,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
-    if (c.prefixed() || c.diverse()) return OVC_EINVAL;       // search_ok: the fused tail; the two-pass pair knows no prefix and no groups
+    if (c.prefixed() || c.diverse() || c.forced()) return OVC_EINVAL;   // search_ok: the fused tail; the two-pass pair knows none of these
     RUN(ovc_beam_select_launch(bs, B, s, e.gate));
     RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
@@ -1553,6 +1574,11 @@ BeamFinalArgs final_args(const Workspace& w, int parity, const SearchCall& c, in
     return bf;
 }
 
+// The final ordering of a search: by total score, or a search with forced words by its own key (it also leaves the banks in w.forced_met).
+int finalize_search(const BeamFinalArgs& bf, const Workspace& w, const SearchCall& c, hipStream_t s) {
+    return c.forced() ? ovc_beam_finalize_forced_launch(bf, c.forced_C, w.forced_met, c.B, s) : ovc_beam_finalize_launch(bf, c.B, s);
+}
+
 // The launches of a search behind its input kernels: the prologue and max_len steps.  This is what the whole-search graphs
 // capture; the Graph form's holds the final ordering too, into the workspace (a graph cannot name the caller's buffers).
 // HostEarly issues the same prologue and steps one by one (run_host_early).
@@ -1561,7 +1587,7 @@ int issue_search_body(Engine& e, Workspace& w, const SearchCall& c) {
     TRY(issue_search_prologue(e, w, c));
     for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, c, t));
     if (c.form != SearchForm::Graph) return OVC_OK;
-    return ovc_beam_finalize_launch(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), c.B, e.stream);
+    return finalize_search(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), w, c, e.stream);
 }
 
 // A sizer builds the SearchCall its entry point will build (out_size plays no part in the layout).
@@ -1657,6 +1683,7 @@ enum class GraphKind {
     PrefixSearch,       // ovc_beam_search_prefix_graph with a table that forces a word (as Search; P in the hash, the table's contents
                         // in the workspace)
     DiverseSearch,      // ovc_beam_search_diverse_graph with more than one group (as Search; G and the bits of lambda in the hash)
+    ForcedSearch,       // ovc_beam_search_forced_graph (as Search; C in the hash, the word table's contents in the workspace)
     ForwardMaps,        // a ForwardCall with maps, ovc_attention_maps (forward_graph_key: k = T, out_size = S): the scoring body
                         // over B*S*T rows plus the map launches
 };
@@ -1834,6 +1861,10 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
         return GraphKey{GraphKind::DiverseSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N, c.k,
                         c.out_size};
     }
+    if (c.forced()) {         // C, never the words: the table is read from the workspace, refreshed per call
+        const int C = c.forced_C;
+        return GraphKey{GraphKind::ForcedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&C, sizeof(C)), workspace, c.B, c.N, c.k, c.out_size};
+    }
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1940,6 +1971,7 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
                size_t workspace_bytes, ovc_stream stream) {
     if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out || (c.sample && !c.sample_seed)) return OVC_EINVAL;
     if (c.prefixed() && (!c.prefix_ids || !c.prefix_len)) return OVC_EINVAL;
+    if (c.forced() && (!c.forced_words || !c.met_out)) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
@@ -1962,6 +1994,9 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     if (c.prefixed() &&                            // the table, refreshed the same way: a replayed graph reads this call's prefixes
         (hipMemcpyAsync(w.prefix_ids, c.prefix_ids, sizeof(int32_t) * c.B * c.prefix_P, hipMemcpyHostToDevice, e.stream) != hipSuccess ||
          hipMemcpyAsync(w.prefix_len, c.prefix_len, sizeof(int32_t) * c.B, hipMemcpyHostToDevice, e.stream) != hipSuccess))
+        return OVC_ELAUNCH;
+    if (c.forced() &&                              // the word table, refreshed the same way: a replayed graph reads this call's words
+        hipMemcpyAsync(w.forced_words, c.forced_words, sizeof(int32_t) * c.B * c.forced_C, hipMemcpyHostToDevice, e.stream) != hipSuccess)
         return OVC_ELAUNCH;
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
     for (int i = 1; i < c.ens_M; ++i) {            // every member reads the call's features, and its boxes where its encoder takes them
@@ -2000,8 +2035,12 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     } else {                                       // the state the last issued step left: its parity, and the positions never written
         BeamFinalArgs bf = final_args(w, steps_run & 1, c, T, c.ids_out, c.logp_out);
         bf.steps_run = steps_run < T ? steps_run : 0;
-        TRY(ovc_beam_finalize_launch(bf, c.B, e.stream));
+        TRY(finalize_search(bf, w, c, e.stream));
     }
+    // the banks of the returned captions: the first out_size entries of every image's final order (out_size == k: one block)
+    if (c.forced() && hipMemcpy2DAsync(c.met_out, sizeof(int32_t) * c.out_size, w.forced_met, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size,
+                                       c.B, hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+        return OVC_ELAUNCH;
     if (c.all_logp_out) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, c.B, c.k, T, m->vocab, c.all_logp_out, e.stream));
     if (c.steps_run_out) *c.steps_run_out = steps_run;
     // the beam slot of each returned caption: the first out_size entries of every image's final order, a copy of this call alone
@@ -2104,6 +2143,7 @@ struct StepTest {
     FusedSelectOptions opt; const int32_t* prefix; const int32_t* prefix_len;      // one model: opt.prefix names no addresses yet
     int members; int32_t* hot_out;                                                 // the ensemble kernel, and its hot-block count
     float* lp_out;
+    const int32_t* forced;                                                         // opt.forced_C != 0: the table [B][forced_C], HOST memory
 };
 
 static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
@@ -2136,6 +2176,11 @@ static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
             hipMemcpyAsync(len_dev, c.prefix_len, sizeof(int32_t) * B, hipMemcpyHostToDevice, s) != hipSuccess)
             return OVC_ELAUNCH;
         c.opt.prefix.ids = ids_dev; c.opt.prefix.len = len_dev;
+    }
+    if (c.opt.forced_C != 0) {                     // the forced words come in HOST memory and are staged likewise
+        int32_t* words_dev = a.take<int32_t>((size_t)B * c.opt.forced_C);
+        if (hipMemcpyAsync(words_dev, c.forced, sizeof(int32_t) * B * c.opt.forced_C, hipMemcpyHostToDevice, s) != hipSuccess) return OVC_ELAUNCH;
+        c.opt.forced = words_dev;
     }
     BeamUpdateArgs& bu = en.p;
     bu.alive_in = c.alive; bu.alive_out = alive_out; bu.running_out = c.running_out;
@@ -2327,6 +2372,83 @@ extern "C" int ovc_debug_beam_diverse_update(const float* logits, const int32_t*
     if (scratch_bytes < ovc_debug_beam_diverse_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
     StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
     if (G > 1) { c.opt.groups = G; c.opt.diversity = lambda; }                           // as diversity_from: one group is the plain call
+    return run_step_test(c, scratch, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Forced words (include/ovc.h: the rule).  Lexically constrained beam search: the k beams in 2^C banks, one per subset of the
+// image's C forced words that a beam has emitted.  A call of its own: no size of the table is the plain call.
+// ---------------------------------------------------------------------------------------------
+// The words of a table [B][C] in HOST memory as the kernel may index with them; false: an id outside [0, V), a repeat within a row,
+// or one of the ids in `special` (a negative entry names nothing).
+static bool forced_words_ok(const int32_t* words, int B, int C, int V, const int (&special)[3]) {
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < C; ++i) {
+            const int32_t w = words[(size_t)b * C + i];
+            if (w < 0 || w >= V || w == special[0] || w == special[1] || w == special[2]) return false;
+            for (int j = 0; j < i; ++j) if (words[(size_t)b * C + j] == w) return false;
+        }
+    return true;
+}
+
+extern "C" int ovc_search_forced_ok(const ovc_model* m, int k, int C) {
+    SearchCall c{1, 1, k, k};
+    if (!model_ok(m) || !ovc_beam_forced_ok(k, C)) return 0;
+    c.forced_C = C;
+    return search_ok(m, c) && m->vocab >= k ? 1 : 0;
+}
+
+extern "C" size_t ovc_forced_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int C) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (!model_ok(m) || !ovc_beam_forced_ok(k, C)) return 0;
+    c.forced_C = C;
+    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+static int run_forced(const ovc_model* m, SearchCall c, const int32_t* forced, int C, int32_t* met_out, const float* features,
+                      const float* boxes, void* workspace, size_t workspace_bytes, ovc_stream stream) {
+    if (!model_ok(m) || !forced || !met_out || c.B <= 0 || !ovc_beam_forced_ok(c.k, C)) return OVC_EINVAL;
+    if (!forced_words_ok(forced, c.B, C, m->vocab, {m->pad_idx, m->bos_idx, m->eos_idx})) return OVC_EINVAL;
+    c.forced_C = C; c.forced_words = forced; c.met_out = met_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_forced(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                      const int32_t* forced, int C, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                      float* logp_out, int32_t* met_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    return run_forced(m, c, forced, C, met_out, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_forced_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                            int out_size, const int32_t* forced, int C, void* workspace, size_t workspace_bytes,
+                                            int64_t* ids_out, float* logp_out, int32_t* met_out, ovc_stream stream) {
+    return run_forced(m, SearchCall{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out}, forced, C, met_out, features, boxes, workspace,
+                      workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the fused selection (run_step_test) under a table of forced words in HOST memory: the forced-word instance.
+extern "C" size_t ovc_debug_beam_forced_update_bytes(int B, int width, int V, int k, int T) {
+    const size_t base = ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
+    return base ? base + 4 * (size_t)B * OVC_MAX_FORCED + 512 : 0;
+}
+
+extern "C" int ovc_debug_beam_forced_update(const float* logits, const int32_t* hist, const float* running, const float* alive, int B,
+                                            int width, int V, int k, int T, int t, int eos, int pad, const int32_t* forced, int C,
+                                            void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
+                                            float* row_max_out, float* row_lsum_out, ovc_stream stream) {
+    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out || !forced)
+        return OVC_EINVAL;
+    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
+        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (!ovc_beam_forced_ok(k, C) || pad < 0 || pad >= V || !forced_words_ok(forced, B, C, V, {pad, -1, eos})) return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_beam_forced_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    c.opt.forced_C = C; c.opt.pad = pad; c.forced = forced;
     return run_step_test(c, scratch, stream);
 }
 

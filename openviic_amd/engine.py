@@ -23,6 +23,7 @@ import torch
 from . import attention_maps as _maps
 from . import constraints as _constraints
 from . import diverse as _diverse
+from . import forced as _forced
 from . import distill as _distill
 from . import dropout as _dropout
 from . import native
@@ -497,7 +498,7 @@ class CaptionEngine:
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
         for (kind, _, _), ws in getattr(self, "_buffers", {}).items():
-            if lib is not None and kind not in ("arena", "steps", "prefix_table"):
+            if lib is not None and kind not in ("arena", "steps", "prefix_table", "forced_table"):
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._buffers = {}
 
@@ -635,6 +636,9 @@ class CaptionEngine:
         "diverse": ("ovc_beam_search_diverse_workspace_bytes", "engine configuration", "beam", {
             "plain": ("ovc_beam_search_diverse", ("out_size", "groups", "penalty", *_RESULTS, "slot", "everything", "stream")),
             "graph": ("ovc_beam_search_diverse_graph", ("out_size", "groups", "penalty", *_RESULTS, "slot", "stream"))}),
+        "forced": ("ovc_forced_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search_forced", ("out_size", "forced", "C", *_RESULTS, "met", "everything", "stream")),
+            "graph": ("ovc_beam_search_forced_graph", ("out_size", "forced", "C", *_RESULTS, "met", "stream"))}),
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
@@ -647,7 +651,7 @@ class CaptionEngine:
     }
 
     def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None, constraints=None, prefix=None, diverse=None):
+                    options=None, constraints=None, prefix=None, diverse=None, forced=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
@@ -659,7 +663,8 @@ class CaptionEngine:
         ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search.  ``prefix``: what
         ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None.  ``diverse``: the diverse search's
         ``(G, penalty)`` as ``diverse.check`` returned them, or None; ``slots`` is then int32 ``(B, out_size)``, the beam slot of each
-        returned caption."""
+        returned caption.  ``forced``: the forced words' int32 numpy table ``(B, C)`` as ``forced.check`` returned it, or None;
+        ``slots`` is then int32 ``(B, out_size)``, the bank (met set) of each returned caption, -1 for an empty slot."""
         kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
         if constraints:
             kind = "constrained"
@@ -667,6 +672,8 @@ class CaptionEngine:
             kind = "prefix"
         if diverse:
             kind = "diverse"
+        if forced is not None:
+            kind = "forced"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -682,11 +689,11 @@ class CaptionEngine:
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
         if form == "graph" and not self.use_graph and kind != "masked":
             form = "plain"
-        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else diverse or options or ())
+        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else (forced.shape[1],) if forced is not None else diverse or options or ())
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
-        if diverse:
+        if diverse or forced is not None:
             slots = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
         everything = torch.empty(B, width, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
         steps = self._steps_tensor() if form == "device" else None
@@ -696,7 +703,7 @@ class CaptionEngine:
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         args = {name: None if t is None else t.data_ptr() for name, t in (
             ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", slots), ("steps", steps), ("seed", seed),
-            ("slot", slots if diverse else None))}
+            ("slot", slots if diverse else None), ("met", slots if forced is not None else None))}
         args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
         if table_drop is not None:
             args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
@@ -704,6 +711,12 @@ class CaptionEngine:
             args.update(zip(("temperature", "top_k", "top_p"), options))
         if diverse:
             args.update(groups=diverse[0], penalty=diverse[1])
+        if forced is not None:
+            if forced.shape[0] != B:
+                raise native.OvcError("forced_words holds {} rows but the batch {} images".format(forced.shape[0], B))
+            # host memory the library copies in stream order: kept until the stream's next call with forced words replaces it
+            self._buffers[self._stream_key("forced_table")] = forced
+            args.update(forced=forced.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), C=forced.shape[1])
         if constraints:
             n, L, banned = constraints
             args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
@@ -843,6 +856,35 @@ class CaptionEngine:
             raise native.OvcError("diverse_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
         ids, logp, everything, slots = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, diverse=(G, lam))
         return (ids, logp, slots, everything) if return_probs else (ids, logp, slots)
+
+    def check_forced(self, batch_size, beam_size, forced_words):
+        """The refusals of a search with forced words that need no features, each naming its argument: callers run them before any
+        launch.  Returns ``(k, C, table)`` as ``openviic_amd.forced.check`` normalises them."""
+        d = self.desc
+        k, C, table = _forced.check(forced_words, batch_size, beam_size, d.vocab, d.pad_idx, d.bos_idx, d.eos_idx)
+        what = "forced_beam_search"
+        if self.precision != "f32":
+            raise native.OvcError(what + ": precision={!r} is not covered -- forced words run in 'f32' only".format(self.precision))
+        if d.vocab > 16384:
+            raise native.OvcError(what + ": a vocabulary of {} words is not covered -- at most 16384".format(d.vocab))
+        if not self.lib.ovc_search_forced_ok(ctypes.byref(d), k, C):
+            raise native.OvcError(what + ": the engine refuses beam_size = {} with {} forced_words for this model "
+                                         "(ovc_search_forced_ok)".format(k, C))
+        return k, C, table
+
+    def forced_beam_search(self, features, boxes, batch_size, beam_size, forced_words, out_size=1, return_probs=False):
+        """Beam search with forced words (``ovc_beam_search_forced``; DESIGN.md section 2z, ``openviic_amd.forced`` mirrors the
+        rule): ``forced_words`` ``(B, C)``, ``1 <= C <= 3`` -- the ``beam_size`` beams in ``2 ** C`` banks, one per subset of the
+        image's words a beam has emitted.  Returns ``(ids, logp, met)`` -- ``(B, out_size, T)`` twice and int32 ``(B, out_size)``,
+        the met set of each returned caption as a bit mask, -1 for an empty slot -- plus ``everything (B, beam_size, T, V)`` with
+        ``return_probs``.  The whole-search graph, or plain launches with ``return_probs`` or without ``use_graph``; no early-exit
+        form.  Refused by name before any launch: a bad table or size, a split precision, more than 16 384 words."""
+        k, C, table = self.check_forced(batch_size, beam_size, forced_words)
+        out_size = _forced._index(out_size, "out_size")
+        if not 1 <= out_size <= k:
+            raise native.OvcError("forced_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
+        ids, logp, everything, met = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, forced=table)
+        return (ids, logp, met, everything) if return_probs else (ids, logp, met)
 
     @staticmethod
     def sample_options(temperature=1.0, top_k=None, top_p=None):

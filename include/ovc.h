@@ -486,6 +486,34 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
                           const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes, float* logp_out,
                           int use_graph, ovc_stream stream);
 
+/* Training the meshed-memory transformer: ovc_forward_backward and ovc_sequence_backward for the multilevel encoder in front of
+ * the meshed decoder (decoders.py:51-73: one shared enc_attn per encoder level, mixed through sigmoid gates).  Opt-in: the entry
+ * points above and their sizers keep refusing this model (OVC_EINVAL / 0), these two take it and nothing else.  The arguments,
+ * the results, what is read outside the captured body, the graph rule and the determinism are those of ovc_forward_backward and
+ * ovc_sequence_backward; grads additionally receives dec[l].alpha[lvl].w / .b, the gates' gradients.  Scope -- anything else is
+ * OVC_EINVAL before any launch, and the sizers answer 0:
+ *   precision 0 (fp32); enc_kind == OVC_ENC_MULTILEVEL, dec_kind == OVC_DEC_MESHED, n_levels == n_enc <= OVC_MAX_LEVELS;
+ *   every encoder layer's self-attention with memory slots (memory > 0, m_k and m_v given) or, memory == 0, every one plain;
+ *   every decoder self_att and cross_att plain: no AoA gates, no memory slots;  alpha[lvl].w given for every level, in the
+ *   model and (with .b where the model has one) in grads;
+ *   the fused vocabulary tail and the 32-bit descriptor limits of ovc_forward_backward, the latter also over levels * rows rows.
+ * Dropout is taken as the identity: there is no dropout form (ovc_dropout has no site per level).
+ * ovc_train_meshed_workspace_bytes / ovc_train_meshed_beams_workspace_bytes: bytes of workspace, 0 when unsupported. */
+size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, int N, int T);
+int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                float* loss_out, int use_graph, ovc_stream stream);
+size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                 int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                                 float* logp_out, int use_graph, ovc_stream stream);
+/* Test hook (tests/test_meshed_train_gpu.py): the backward of ovc_debug_meshed_mix as the meshed training calls launch it.  dmixed
+ * [n], alpha / enc / denc / dalpha [levels][n]:  denc[l] = (dmixed * sigmoid(alpha[l])) / divisor,  dalpha[l] = ((dmixed * enc[l]) *
+ * sigmoid'(alpha[l])) / divisor, finite for every finite alpha.  OVC_EINVAL, nothing written: n <= 0 or n % 4 != 0, levels outside
+ * 1..OVC_MAX_LEVELS, a NULL pointer or one not aligned to 16 bytes. */
+int ovc_debug_meshed_mix_backward(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor,
+                                  float* denc, float* dalpha, ovc_stream stream);
+
 /* SCST under dropout (the reference's train_scst searches in train() mode, vi_trainer.py:121-158): the beam search with the
  * dropout sites above applied, and the backward of its log-probabilities under the SAME masks.  The plain standard transformer,
  * with or without encoder memory slots, precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.

@@ -68,9 +68,25 @@ def _apply_step_gradients(eng, optimizer, grads, max_norm):
     optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
 
 
+_MESHED = ("meshed",)       # what ``_xe_call`` returns as the loss of a ``meshed=True`` call: the NLL on the meshed entry point
+
+
 def _loss_head(head):
-    """``forward_backward``'s keyword for what ``_xe_call`` returned as the call's loss: the NLL, the smoothed loss or soft targets."""
+    """``forward_backward``'s keyword for what ``_xe_call`` returned as the call's loss: the NLL, the smoothed loss or soft targets
+    -- or the NLL of the meshed-memory transformer (``meshed=True``)."""
+    if head is _MESHED:
+        return {"meshed": True}
     return {"distill": tuple(head)} if isinstance(head, _distill.SoftTargets) else {"loss": head}
+
+
+def _refuse_with_meshed(what, **given):
+    """``meshed=True`` together with what the meshed-memory transformer's training does not cover: refused by name."""
+    for name, value in given.items():
+        if value:
+            raise engine.native.OvcError(
+                "{}(meshed=True, {}=...): {} is out of scope for the meshed-memory transformer's training{}".format(
+                    what, name, name, " -- the meshed layer applies enc_attn.dropout once per level and the engine has no site "
+                    "for it; set DROPOUT: 0 or call model.eval()" if name == "dropout" else ""))
 
 
 class _XeLoss(torch.autograd.Function):
@@ -227,7 +243,7 @@ class BaseTransformer(Module):
             return eng.attention_maps(features, boxes, ids=ids, reduce=reduce, return_log_probs=return_log_probs)
 
     def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None, teacher_log_probs=None,
-                distill_weight=None):
+                distill_weight=None, meshed=False):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
         every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer, the
@@ -261,16 +277,26 @@ class BaseTransformer(Module):
         dropout setting above.  Refused before the engine is built, any launch and any draw: one of the two keywords without the
         other, either with ``label_smoothing`` / ``reduction``, a ``w`` that is not a Python number in ``[0, 1]``, and a ``P``
         that is not a contiguous fp32 ``(B, T, V)`` tensor on the model's device or that requires grad.  A temperature other
-        than 1, sparse teachers and 16-bit teachers are out of scope."""
+        than 1, sparse teachers and 16-bit teachers are out of scope.
+
+        ``meshed=True``: the meshed-memory transformer -- the ``MultilevelEncoder`` whose layers all have memory slots (or all
+        have none) in front of the ``MeshedDecoder`` with plain attentions -- on ``ovc_forward_backward_meshed``; the gates
+        ``fc_alphas`` get their gradients like every other parameter.  Opt-in: without the keyword such a model is refused as
+        before.  Refused by name before any launch and any draw: ``meshed=True`` on any other model, together with
+        ``dropout=True``, ``label_smoothing`` / ``reduction`` or ``teacher_log_probs`` / ``distill_weight``, and (the refusal
+        above) a ``train()``-mode model with a live dropout."""
         eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
-                                                    teacher_log_probs=teacher_log_probs, distill_weight=distill_weight)
+                                                    teacher_log_probs=teacher_log_probs, distill_weight=distill_weight, meshed=meshed)
         return _XeLoss.apply(eng, drop, smoothed, *inputs, *eng.gradient_parameters())
 
     def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None, teacher_log_probs=None,
-                 distill_weight=None):
+                 distill_weight=None, meshed=False):
         """The preamble of ``xe_loss`` / ``xe_step``: their refusals in their order -- the loss, the dropout rules, a model outside
         the backward's scope, ``xe_step``'s optimizer set -- and only then the draw of the step's seed.  Returns ``(engine,
         dropout (probs, seed) or None, smoothed loss / soft targets or None, (features, boxes, caption tokens, targets))``."""
+        if meshed:
+            _refuse_with_meshed(what, dropout=dropout, label_smoothing=label_smoothing is not None, reduction=reduction is not None,
+                                teacher_log_probs=teacher_log_probs is not None, distill_weight=distill_weight is not None)
         soft = None
         if teacher_log_probs is not None or distill_weight is not None:
             try:            # a batch without caption tokens is refused where the inputs are checked, after the arguments
@@ -282,7 +308,9 @@ class BaseTransformer(Module):
         smoothed = soft or engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
         probs = self._xe_dropout_probs(dropout, what)
         eng = self._fused_engine()
-        eng._check_trainable()
+        eng._check_trainable(meshed)
+        if meshed:
+            smoothed = _MESHED
         if optimizer is not None:
             _checked_step_optimizer(optimizer, what, eng)
         inputs = (*self._engine_inputs(input_features), input_features["caption_tokens"],
@@ -308,7 +336,7 @@ class BaseTransformer(Module):
         return {}
 
     def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None, label_smoothing=None,
-                reduction=None, teacher_log_probs=None, distill_weight=None):
+                reduction=None, teacher_log_probs=None, distill_weight=None, meshed=False):
         """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
         ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
         stands for ::
@@ -330,7 +358,8 @@ class BaseTransformer(Module):
 
         ``label_smoothing`` / ``reduction``: as ``xe_loss`` takes them -- the label-smoothed loss in the four lines and here, with
         the same refusals before any launch and any draw.  ``teacher_log_probs`` / ``distill_weight``: as ``xe_loss`` takes them
-        -- the soft-target loss in the four lines and here.
+        -- the soft-target loss in the four lines and here.  ``meshed``: as ``xe_loss`` takes it -- the meshed-memory transformer,
+        ``xe_loss(items, meshed=True)`` in the four lines.
 
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
@@ -339,14 +368,15 @@ class BaseTransformer(Module):
         _checked_step_optimizer(optimizer, "xe_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
         eng, drop, smoothed, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
-                                                    optimizer, teacher_log_probs=teacher_log_probs, distill_weight=distill_weight)
+                                                    optimizer, teacher_log_probs=teacher_log_probs, distill_weight=distill_weight,
+                                                    meshed=meshed)
         loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed))
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
                   max_norm=None, sample=False, temperature=1.0, top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0,
-                  banned_words=None):
+                  banned_words=None, meshed=False):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -388,7 +418,13 @@ class BaseTransformer(Module):
         DistributedDataParallel's gradient all-reduce.  A data-parallel run keeps the lines above.
 
         ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``beam_search``'s; anything but their defaults is refused by
-        name before any launch or draw (a constrained search inside ``scst_step`` is out of scope: run the lines above)."""
+        name before any launch or draw (a constrained search inside ``scst_step`` is out of scope: run the lines above).
+
+        ``meshed=True``: the meshed-memory transformer, as ``xe_loss`` takes it (``ovc_sequence_backward_meshed``); the first of
+        the lines above is then ``model.beam_search(items, B, k, out_size=k, meshed=True)``.  Refused by name before any launch or
+        draw: any other model, and ``meshed=True`` together with ``dropout=True`` or ``sample=True``."""
+        if meshed:
+            _refuse_with_meshed("scst_step", dropout=dropout, sample=sample)
         if _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
             raise engine.native.OvcError("scst_step(no_repeat_ngram_size / min_length / banned_words): a constrained search inside "
                                          "scst_step is out of scope -- call beam_search with them and backpropagate its log_probs")
@@ -416,7 +452,7 @@ class BaseTransformer(Module):
             raise engine.native.OvcError("scst_step: 1 <= beam_size <= {} expected, got {}".format(engine.native.OVC_MAX_BEAM, k))
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
-        eng._check_trainable()
+        eng._check_trainable(meshed)
         checked = eng.check_sample(k, temperature, top_k, top_p) if sample else None
         _checked_step_optimizer(optimizer, "scst_step", eng)
         feats, boxes = eng._checked_inputs(*self._engine_inputs(input_features))
@@ -445,6 +481,8 @@ class BaseTransformer(Module):
                                                      if isinstance(r, torch.Tensor) else type(r).__name__))
             r = r.detach().contiguous()
         g, stats = _scst.advantage(r, log_probs)
+        if meshed:
+            recompute = dict(recompute, meshed=True)
         _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena(), **recompute)
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
@@ -475,7 +513,7 @@ class BaseTransformer(Module):
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
                     fused=True, dropout=False, generator=None, no_repeat_ngram_size=0, min_length=0, banned_words=None, prefix=None,
-                    **kwargs):
+                    meshed=False, **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
 
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
@@ -516,8 +554,20 @@ class BaseTransformer(Module):
         ``[0, V)``, ``<bos>`` or ``<eos>``, a word behind a ``<pad>``; a prefix with ``fused=False``, ``dropout=True``, an
         early-exit form, active constraints, a precision other than 'f32' or more than 16 384 words; and a model in ``train()``
         mode with gradients enabled (no SCST through a forced prefix: call ``eval()`` or use ``no_grad``).
+
+        ``meshed=True`` (fused only): the meshed-memory transformer, as ``xe_loss`` takes it -- in ``train()`` mode with gradients
+        enabled ``log_probs`` carry a gradient (``ovc_sequence_backward_meshed``); the search itself is the plain one.  Refused by
+        name before any launch or draw: any other model, ``fused=False``, ``dropout=True``, and a ``train()``-mode model with a
+        live dropout and gradients enabled.  Without the keyword a meshed model's ``log_probs`` raise from ``backward()`` as before.
         """
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
+        if meshed:
+            _refuse_with_meshed("beam_search", dropout=dropout)
+            if not fused:
+                raise engine.native.OvcError("beam_search(meshed=True) needs fused=True: the host loop has no backward")
+            if self.training and torch.is_grad_enabled():
+                self._xe_dropout_probs(False, "beam_search(meshed=True)")
+            self._fused_engine()._check_trainable(True)
         constraints = _requested_constraints(no_repeat_ngram_size, min_length, banned_words)
         if prefix is not None:       # every refusal of the table and of what it does not combine with, before any launch and draw
             dec = self.decoder
@@ -552,7 +602,7 @@ class BaseTransformer(Module):
             ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
                                                               return_probs, kwargs.get("early_exit"), constraints=constraints,
                                                               prefix=prefix)
-            logp = self._scst_log_probs(input_features, ids, logp, recompute)
+            logp = self._scst_log_probs(input_features, ids, logp, dict(recompute, meshed=True) if meshed else recompute)
             if out_size == 1:
                 ids, logp = ids.squeeze(1), logp.squeeze(1)
             return (ids, logp, everything) if return_probs else (ids, logp)
@@ -707,7 +757,7 @@ class BaseTransformer(Module):
         params = [p for p in self.parameters() if p.requires_grad]
         if not (self.training and torch.is_grad_enabled() and params):
             return log_probs
-        live = [] if recompute else self._live_dropouts()          # a live dropout counts where the search ran without its masks
+        live = [] if "dropout" in recompute else self._live_dropouts()   # a live dropout counts where the search ran without its masks
         refusal = None if not live else (
             "beam_search: the model is in train() mode with dropout > 0 ({}); the engine's search and its backward take "
             "dropout as the identity -- set DROPOUT: 0 in the config or call model.eval()".format(live[0]))

@@ -118,3 +118,14 @@ int ovc_bw_leaky(const float* g, const float* act, float scale, float slope, flo
 // y[r, k] = (a[r, k] + b[r, k]) + c[r, k] (c may be nullptr), each operand with its own row stride; y may alias a, b or c
 int ovc_bw_sum(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols, float* y, long ldy,
                hipStream_t s);
+
+// The meshed decoder's gate block (engine.hip bw_meshed_decoder_layer).
+// Backward of mixed = (sum_l sigmoid(alpha[l]) enc[l]) / divisor (ovc_meshed_mix), alpha / enc / denc / dalpha [levels][n]:
+// denc[l] = (dmixed sigmoid(alpha[l])) / divisor, dalpha[l] = ((dmixed enc[l]) sigmoid'(alpha[l])) / divisor; finite for every finite
+// alpha.  One launch for levels 1..OVC_MAX_LEVELS, dmixed read once.  OVC_EINVAL for n % 4 != 0, levels outside 1..OVC_MAX_LEVELS,
+// a null or misaligned pointer.
+int ovc_bw_meshed_mix(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor, float* denc,
+                      float* dalpha, hipStream_t s);
+// out[i] = ((acc[i] + src[i]) + src[stride + i]) + ... over `levels` blocks of n floats in ascending order; acc may be nullptr (the sum
+// starts from block 0), out may alias acc
+int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out, hipStream_t s);

@@ -925,3 +925,76 @@ int ovc_bw_sum(const float* a, long lda, const float* b, long ldb, const float* 
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
+
+// ---- the meshed decoder's gate block (engine.hip, bw_meshed_decoder_layer) -------------------------------------------------------
+namespace {
+
+// mixed = (sum_l sigmoid(a_l) e_l) / divisor (rowops.hip, meshed_mix): per element and level
+//   d(e_l) = (d(mixed) sigmoid(a_l)) / divisor,   d(a_l) = ((d(mixed) e_l) sigmoid'(a_l)) / divisor.
+// With t = exp(-|a|) in (0, 1]: sigmoid(a) = 1 / (1 + t) or t / (1 + t) by the sign of a, and sigmoid'(a) = t / (1 + t)^2 <= 1 / 4 -- no
+// overflow for any finite a, and no cancellation in 1 - sigmoid for large a.  One lane per four elements: d(mixed) is read once,
+// every level's two outputs are written with 16-byte stores by that lane alone.
+template <int LEVELS>
+__global__ __launch_bounds__(256) void bw_meshed_mix_kernel(const float* __restrict__ dmixed, const float* __restrict__ alpha,
+                                                            const float* __restrict__ enc, long n4, float divisor,
+                                                            float* __restrict__ denc, float* __restrict__ dalpha) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 dm = reinterpret_cast<const f32x4*>(dmixed)[i];
+#pragma unroll
+        for (int l = 0; l < LEVELS; ++l) {
+            const f32x4 al = reinterpret_cast<const f32x4*>(alpha)[(size_t)l * n4 + i];
+            const f32x4 ev = reinterpret_cast<const f32x4*>(enc)[(size_t)l * n4 + i];
+            f32x4 de, da;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float t = expf(-fabsf(al[j])), r = 1.f / (1.f + t);
+                const float sig = al[j] >= 0.f ? r : t * r;
+                de[j] = (dm[j] * sig) / divisor;
+                da[j] = ((dm[j] * ev[j]) * ((t * r) * r)) / divisor;
+            }
+            reinterpret_cast<f32x4*>(denc)[(size_t)l * n4 + i] = de;
+            reinterpret_cast<f32x4*>(dalpha)[(size_t)l * n4 + i] = da;
+        }
+    }
+}
+
+// out[i] = ((acc[i] + src[i]) + src[stride + i]) + ... over `levels` blocks in ascending order (acc may be nullptr: the sum starts
+// from block 0); out may be acc
+__global__ void bw_sum_levels_kernel(const float* acc, const float* src, int levels, long stride, long n, float* out) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float s = acc ? acc[i] + src[i] : src[i];
+        for (int l = 1; l < levels; ++l) s += src[l * stride + i];
+        out[i] = s;
+    }
+}
+
+}  // namespace
+
+int ovc_bw_meshed_mix(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor, float* denc,
+                      float* dalpha, hipStream_t s) {
+    if (!dmixed || !alpha || !enc || !denc || !dalpha || levels < 1 || levels > OVC_MAX_LEVELS || n <= 0 || (n & 3)) return OVC_EINVAL;
+    if (!ovc_aligned16(dmixed) || !ovc_aligned16(alpha) || !ovc_aligned16(enc) || !ovc_aligned16(denc) || !ovc_aligned16(dalpha))
+        return OVC_EINVAL;                                                                             // float4 accesses
+    const dim3 grid(blocks_for(n / 4)), block(256);
+    switch (levels) {
+    case 1: hipLaunchKernelGGL(bw_meshed_mix_kernel<1>, grid, block, 0, s, dmixed, alpha, enc, n / 4, divisor, denc, dalpha); break;
+    case 2: hipLaunchKernelGGL(bw_meshed_mix_kernel<2>, grid, block, 0, s, dmixed, alpha, enc, n / 4, divisor, denc, dalpha); break;
+    case 3: hipLaunchKernelGGL(bw_meshed_mix_kernel<3>, grid, block, 0, s, dmixed, alpha, enc, n / 4, divisor, denc, dalpha); break;
+    default: hipLaunchKernelGGL(bw_meshed_mix_kernel<4>, grid, block, 0, s, dmixed, alpha, enc, n / 4, divisor, denc, dalpha); break;
+    }
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out, hipStream_t s) {
+    if (!src || !out || levels < 1 || levels > OVC_MAX_LEVELS || n <= 0 || stride < n) return OVC_EINVAL;
+    hipLaunchKernelGGL(bw_sum_levels_kernel, dim3(blocks_for(n)), dim3(256), 0, s, acc, src, levels, stride, n, out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+extern "C" int ovc_debug_meshed_mix_backward(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor,
+                                             float* denc, float* dalpha, ovc_stream stream) {
+    if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
+    return ovc_bw_meshed_mix(dmixed, alpha, enc, levels, n, divisor, denc, dalpha, ovc_hip_stream(stream));
+}

@@ -101,7 +101,12 @@ struct Bump {
 // outputs, the pre-norm sums (the LayerNorm statistics are recomputed from them), the norm outputs, the ReLU outputs and the
 // layer outputs.  The inference forward reuses one set of buffers across layers instead (Workspace::tape == nullptr).
 struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out; };
-struct DecTape { float *q, *k, *v, *att, *ys, *x1, *qc, *attc, *yc, *x2, *ff, *yf, *out; };
+struct DecTape {
+    float *q, *k, *v, *att, *ys, *x1, *qc, *attc, *yc, *x2, *ff, *yf, *out;
+    // the meshed decoder's gate block (run_decoder_layer): the stacked pre-norm sums, their norms e_l and the gate pre-activations
+    // a_l, [levels][rows][d] each, and the gated sum [rows][d]; attc is then [levels][rows][h d_v]
+    float *ymesh, *enc_att, *alpha, *mixed;
+};
 // The cross-level (CaMo) tail (run_cross_level_tail): per cross call c (0: q = o2, k = v = o1; 1: q = o3, k = v = o2') its k, v, the
 // attention output att [2][B*N][h_enc*dv_enc] and fc_o's output ya [2][B*N][d] (the pre-norm sum is ya + q, formed again by the
 // backward as the norm formed it); o2'; mlp1's leaky-ReLU output a1 and mlp2's output h2 (its activation's sign).  The layer
@@ -363,7 +368,7 @@ Workspace carve_forward(const ovc_model* m, void* base, const ForwardCall& c) {
 EncTape scratch_enc(const Workspace& w) { return EncTape{w.eq, w.ek, w.ev, w.eatt, w.ey, w.xe[1], w.eff, w.ey, nullptr}; }
 ClTape scratch_cl(const Workspace& w) { return ClTape{{w.ek, w.ek}, {w.ev, w.ev}, w.eatt, w.ey, w.xe[0], w.einfo, w.ey}; }
 DecTape scratch_dec(const Workspace& w, float* k, float* v) {
-    return DecTape{w.q, k, v, w.att, w.y, w.x1, w.q, w.att, w.y, w.x2, w.ff, w.y, w.x};
+    return DecTape{w.q, k, v, w.att, w.y, w.x1, w.q, w.att, w.y, w.x2, w.ff, w.y, w.x, w.ymesh, w.enc_att, w.alpha, w.mixed};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -946,7 +951,8 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
                                                         : (l == m->n_enc - 1 ? w.enc_levels : x);
-        if (w.tape && l < m->n_enc - 1 && m->enc_kind != OVC_ENC_CROSS_LEVEL) out = b.out;   // cl_out keeps every level
+        // cl_out / enc_levels keep every level
+        if (w.tape && l < m->n_enc - 1 && m->enc_kind != OVC_ENC_CROSS_LEVEL && m->enc_kind != OVC_ENC_MULTILEVEL) out = b.out;
         TRY(e.ffn(m->enc[l].ffn, b.x1, b.ff, b.yf, nullptr, out, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         x = out;
     }
@@ -1235,16 +1241,16 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
             GemmArgs o{};
             o.A1 = b.attc; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
             o.R = b.x1; o.ldr = d; o.res_mod = rows;
-            o.seg[0] = e.seg(dl.cross_att.o, w.ymesh);
+            o.seg[0] = e.seg(dl.cross_att.o, b.ymesh);
             TRY(e.gemm(o));
-            RUN(ovc_layer_norm_gated(w.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                     w.enc_att, lv * rows, d, s, e.gate));
+            RUN(ovc_layer_norm_gated(b.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                     b.enc_att, lv * rows, d, s, e.gate));
         } else {
             for (int lvl = 0; lvl < lv; ++lvl) {      // AoA gates need the per-level pair (x1, enc_att_l)
                 TRY(e.linear(b.attc + (size_t)lvl * rows * hv, hv, dl.cross_att.o, b.x1, b.yc, rows, d, 0));
                 RUN(ovc_layer_norm_gated(b.yc, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                         w.enc_att + lvl * nrd, rows, d, s, e.gate));
-                TRY(e.aoa(dl.cross_att, b.x1, w.enc_att + lvl * nrd, w.info, w.gate, rows));
+                                         b.enc_att + lvl * nrd, rows, d, s, e.gate));
+                TRY(e.aoa(dl.cross_att, b.x1, b.enc_att + lvl * nrd, w.info, w.gate, rows));
             }
         }
         // level gates alpha_l = W_l [x1 ; enc_att_l] + b_l (decoders.py:59-66): one launch, a segment per level,
@@ -1255,15 +1261,15 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
             g.M = rows; g.seg_n = d; g.ldc = d;
             const bool fused = d % 64 == 0 && lv <= OVC_MAX_SEGMENTS;
             for (int lvl = 0; lvl < lv; ++lvl) {
-                const GemmSegment seg = e.seg(dl.alpha[lvl], w.alpha + lvl * nrd, w.enc_att + lvl * nrd);
+                const GemmSegment seg = e.seg(dl.alpha[lvl], b.alpha + lvl * nrd, b.enc_att + lvl * nrd);
                 if (fused) { g.seg[lvl] = seg; continue; }
                 g.seg[0] = seg; g.nseg = 1;
                 TRY(e.gemm(g));
             }
             if (fused) { g.nseg = lv; TRY(e.gemm(g)); }
         }
-        RUN(ovc_meshed_mix(w.alpha, w.enc_att, lv, (long)nrd, sqrtf((float)lv), w.mixed, s, e.gate));
-        ffn_in = w.mixed;
+        RUN(ovc_meshed_mix(b.alpha, b.enc_att, lv, (long)nrd, sqrtf((float)lv), b.mixed, s, e.gate));
+        ffn_in = b.mixed;
     } else {
         TRY(e.linear_ln(b.attc, hv, dl.cross_att.o, b.x1, dl.cross_att.ln, nullptr, b.yc, p.part, b.x2, rows, p.site(l, 1)));
         TRY(e.aoa(dl.cross_att, b.x1, b.x2, w.info, w.gate, rows));
@@ -1493,7 +1499,7 @@ int run_forward_decoder(Engine& e, Workspace& w, const ForwardCall& c) {
     e.kchains = 1;
     DecoderPass pass{DecoderPass::Sequence, rows, c.B, c.N, w.padflag, nullptr, true};
     pass.S = c.S; pass.T = c.T; pass.keep_maps = c.keep_maps;
-    // training: the layer's own tape slots (see run_encoder_layers); the meshed branch never runs with a tape
+    // training: the layer's own tape slots (see run_encoder_layers), the meshed branch's gate block included
     const DecTape scratch = scratch_dec(w, w.kc, w.vc);
     const float* x = w.x;
     for (int l = 0; l < m->n_dec; ++l) {
@@ -2826,6 +2832,10 @@ struct TrainWs {
     // gradients dlev [3][B*N][d]
     float* cl_dh; float* cl_da; float* cl_dcat; float* cl_dss; float* cl_dq; float* cl_dkv; float* cl_do2p; float* cl_dq23;
     float* cl_dlev;
+    // the meshed decoder (bw_meshed_decoder_layer; TrainCall::meshed only), rows = B*S*T: the gate block's d(e_l) before and after
+    // the gates' share and d(a_l), [levels][rows][d] each; the running d(x1) [2][rows][d]; the levels' dq [levels][rows][h d_k] and
+    // dk|dv [levels][B*N][2 h d_k]; the encoder levels' gradients, summed over the decoder layers, [2][levels][B*N][d]
+    float* ms_de; float* ms_de2; float* ms_da; float* ms_dx1[2]; float* ms_dq; float* ms_dkv; float* ms_dlev[2];
     size_t bytes;
 };
 
@@ -2842,7 +2852,7 @@ enum class LossHead {
     SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The twelve exported functions fill one of these, and the scope (call_ok), the workspace
+// One training call, described once.  The fourteen exported functions fill one of these, and the scope (call_ok), the workspace
 // layout and size (carve_train), the captured body (issue_train_body), the graph key (train_graph_key) and the launches around
 // the body (run_train_call) are functions of it: a sizer and the entry point that carves its buffer cannot disagree.
 struct TrainCall {
@@ -2856,6 +2866,7 @@ struct TrainCall {
     // and narrows the scope.
     DropPlan* plan; const int64_t* seed; uint64_t drop_hash;
     int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
+    bool meshed;                                    // the multilevel encoder + meshed decoder (meshed_train_ok), the opt-in entry points
     bool seq() const { return head == LossHead::RowWeights; }
     // The call's teacher-forced pass: the logits kept for the backward; RowWeights: on the caller's ids and their row gradient.
     ForwardCall forward() const {
@@ -2873,13 +2884,14 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     const size_t rows = (size_t)B * S * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
     const bool cl = m->enc_kind == OVC_ENC_CROSS_LEVEL;
+    const size_t lv = c.meshed ? m->n_levels : 1;   // the meshed block's products run over the stacked levels * rows (levels * B*N) rows
     // the tail's weight gradients run over both cross calls' rows at once (2 B*N), mlp1's over K = 3d
-    const size_t R = std::max(rows, cl ? 2 * BN : BN), Rp = pad4(R);
+    const size_t R = lv * std::max(rows, cl ? 2 * BN : BN), Rp = pad4(R);
     for (int l = 0; l < m->n_enc; ++l) {
         EncTape& p = t.tape.enc[l];
         p.q = a.take<float>(BN * ehk); p.k = a.take<float>(BN * ehk); p.v = a.take<float>(BN * ehk); p.att = a.take<float>(BN * ehk);
         p.ya = a.take<float>(BN * d); p.x1 = a.take<float>(BN * d); p.ff = a.take<float>(BN * dff); p.yf = a.take<float>(BN * d);
-        p.out = a.take<float>(l < m->n_enc - 1 && !cl ? BN * d : 0);
+        p.out = a.take<float>(l < m->n_enc - 1 && !cl && !c.meshed ? BN * d : 0);
     }
     if (cl) {
         ClTape& p = t.tape.cl;
@@ -2894,10 +2906,14 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         DecTape& p = t.tape.dec[l];
         p.q = a.take<float>(rows * hk); p.k = a.take<float>(rows * hk); p.v = a.take<float>(rows * hk); p.att = a.take<float>(rows * hk);
         p.ys = a.take<float>(rows * d); p.x1 = a.take<float>(rows * d); p.qc = a.take<float>(rows * hk);
-        p.attc = a.take<float>(rows * hk); p.yc = a.take<float>(rows * d); p.x2 = a.take<float>(rows * d);
+        p.attc = a.take<float>(lv * rows * hk); p.yc = a.take<float>(rows * d); p.x2 = a.take<float>(rows * d);
         p.ff = a.take<float>(rows * dff); p.yf = a.take<float>(rows * d); p.out = a.take<float>(rows * d);
+        if (c.meshed) {
+            p.ymesh = a.take<float>(lv * rows * d); p.enc_att = a.take<float>(lv * rows * d); p.alpha = a.take<float>(lv * rows * d);
+            p.mixed = a.take<float>(rows * d);
+        }
     }
-    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d});
+    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d, c.meshed ? 2 * d : d});   // the gates' operand [x1 ; e_l]
     t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
     t.tok = a.take<int32_t>(rows);
     t.w_row = c.seq() ? t.w.w_row : a.take<float>(rows); t.loss = a.take<float>(4);
@@ -2919,6 +2935,12 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     if (mem) {
         t.mem_part_k = a.take<float>((size_t)B * mem * ehk); t.mem_part_v = a.take<float>((size_t)B * mem * ehk);
         t.mem_colpart = a.take<float>((((size_t)B + 63) / 64) * mem * ehk);
+    }
+    if (c.meshed) {
+        t.ms_de = a.take<float>(lv * rows * d); t.ms_de2 = a.take<float>(lv * rows * d); t.ms_da = a.take<float>(lv * rows * d);
+        for (int i = 0; i < 2; ++i) t.ms_dx1[i] = a.take<float>(rows * d);
+        t.ms_dq = a.take<float>(lv * rows * hk); t.ms_dkv = a.take<float>(lv * BN * 2 * hk);
+        for (int i = 0; i < 2; ++i) t.ms_dlev[i] = a.take<float>(lv * BN * d);
     }
     if (c.plan) {
         t.dproj = a.take<float>(R * d);
@@ -2966,8 +2988,30 @@ bool train_ok(const ovc_model* m, const ForwardCall& c) {
     return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
 }
 
+// The opt-in scope (ovc_forward_backward_meshed, ovc_sequence_backward_meshed): the multilevel encoder, every layer's self-attention
+// with memory slots (or every layer plain), in front of the meshed decoder with plain attentions and a gate per level; fp32 and the
+// fused vocabulary tail as in train_ok.  The 32-bit descriptor limits also hold for the products over the stacked levels * rows rows.
+bool meshed_train_ok(const ovc_model* m, const ForwardCall& c) {
+    if (!forward_ok(m, c)) return false;
+    if (m->enc_kind != OVC_ENC_MULTILEVEL || m->dec_kind != OVC_DEC_MESHED) return false;
+    if (m->n_levels != m->n_enc || m->n_levels > OVC_MAX_LEVELS) return false;
+    for (int l = 0; l < m->n_enc; ++l) if (!(m->memory != 0 ? mha_memory(m->enc[l].att) : mha_plain(m->enc[l].att))) return false;
+    for (int l = 0; l < m->n_dec; ++l) {
+        if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
+        for (int lvl = 0; lvl < m->n_levels; ++lvl) if (!m->dec[l].alpha[lvl].w) return false;
+    }
+    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
+    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows(), lv = m->n_levels;
+    const long stacked = lv * std::max(rows, (long)c.B * c.N), widest = std::max({(long)m->d_ff, 3L * m->heads * m->d_k, 2L * m->d_model});
+    if ((stacked + 256) * widest * 4 > kMax) return false;
+    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
+}
+
 bool grads_ok(const ovc_model* m, const ovc_model* g) {
     if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
+    if (m->dec_kind == OVC_DEC_MESHED)
+        for (int l = 0; l < m->n_dec; ++l)
+            for (int lvl = 0; lvl < m->n_levels; ++lvl) if (!lin_grad_ok(m->dec[l].alpha[lvl], g->dec[l].alpha[lvl])) return false;
     for (int l = 0; l < m->n_enc; ++l)
         if (!mha_grad_ok(m->enc[l].att, g->enc[l].att) || !ffn_grad_ok(m->enc[l].ffn, g->enc[l].ffn) ||
             (m->enc[l].att.m_k && (!g->enc[l].att.m_k || !g->enc[l].att.m_v))) return false;
@@ -2984,8 +3028,12 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
 // twice and has no site of its own.
 bool dropout_train_ok(const ovc_model* m, const ForwardCall& c) { return train_ok(m, c) && m->enc_kind == OVC_ENC_PLAIN; }
 
-// The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope.
-bool call_ok(const ovc_model* m, const TrainCall& c) { return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward()); }
+// The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope;
+// the opt-in meshed scope for the meshed entry points, and nothing else reaches it.
+bool call_ok(const ovc_model* m, const TrainCall& c) {
+    if (c.meshed) return !c.plan && meshed_train_ok(m, c.forward());      // no dropout form: ovc_dropout has no per-level site
+    return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward());
+}
 
 // A sequence call with dropout recomputes under the masks of the search that made its sequences: that search's limits
 // (ovc_beam_search_dropout), full-length sequences and its slot table.  After call_ok: m has been checked.
@@ -3132,6 +3180,79 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const Tr
                              B * S, T, h, dk, dxin, dec_site(l, 0));
 }
 
+int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk);
+
+// A meshed decoder layer (run_decoder_layer's OVC_DEC_MESHED branch; decoders.py:51-73), DESIGN.md section 2aa.  With x1 the
+// self-attention block's output, e_l = LN(attc_l Wo + bo + x1), a_l = W_l [x1 ; e_l] + b_l and mixed = (sum_l sigmoid(a_l) e_l) /
+// sqrt(levels): the FFN from `mixed`, the mix, the gates, ONE LayerNorm / Wo backward over the stacked levels * rows rows, the
+// cross-attention per level on the shared queries, then the self-attention with the total d(x1).  Every sum across levels runs
+// in ascending level order.  dlev_prev / dlev_next [levels][B*N][d]: the encoder levels' gradients from the layers above (nullptr
+// for the top layer) and with this layer's share added.
+int bw_meshed_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const TrainCall& c, const float* xin, const float* dout,
+                            float* dxin, const float* dlev_prev, float* dlev_next) {
+    const ovc_model* m = e.m;
+    const int B = c.B, N = c.N, S = c.S, T = c.T;
+    const Workspace& w = t.w;
+    const DecTape& p = t.tape.dec[l];
+    const ovc_dec_layer& dl = m->dec[l];
+    const ovc_dec_layer& gl = gr->dec[l];
+    hipStream_t s = e.stream;
+    const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * S * T, BN = B * N, lv = m->n_levels;
+    const size_t nrd = (size_t)rows * d, nd = (size_t)BN * d;
+    const int rp = (int)pad4(rows);
+    // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(mixed)
+    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.mixed, p.ff, p.yf, dout, w.padflag, rows));
+    // the mix: d(e_l) and d(a_l) of every level from one read of d(mixed)
+    RUN(ovc_bw_meshed_mix(t.dx1, p.alpha, p.enc_att, lv, (long)nrd, sqrtf((float)lv), t.ms_de, t.ms_da, s));
+    // the gates: dW_l = d(a_l)^T [x1 ; e_l] with the concatenated operand staged transposed (K = rows ascending), db_l its row sums,
+    // d(e_l) += d(a_l) W_l[:, d:], and d(x1) = sum_l d(a_l) W_l[:, :d] through the GEMM's residual input
+    int cur = 0;
+    for (int lvl = 0; lvl < lv; ++lvl) {
+        const float* da = t.ms_da + lvl * nrd;
+        const float* el = p.enc_att + lvl * nrd;
+        RUN(ovc_bw_transpose(da, d, rows, d, t.ta, rp, rp, s));
+        RUN(ovc_bw_transpose(p.x1, d, rows, d, t.tb, rp, rp, s));
+        RUN(ovc_bw_transpose(el, d, rows, d, t.tb + (size_t)d * rp, rp, rp, s));
+        TRY(bw_mm(e, t.ta, rp, d, rp, t.tb, 2 * d, out_ptr(gl.alpha[lvl].w)));
+        if (dl.alpha[lvl].b) RUN(ovc_bw_rowsum(t.ta, rp, d, rows, out_ptr(gl.alpha[lvl].b), s));
+        RUN(ovc_bw_transpose(dl.alpha[lvl].w + d, 2 * d, d, d, t.wt, d, d, s));
+        TRY(bw_mm(e, da, d, rows, d, t.wt, d, t.ms_de2 + lvl * nrd, t.ms_de + lvl * nrd));
+        RUN(ovc_bw_transpose(dl.alpha[lvl].w, 2 * d, d, d, t.wt, d, d, s));
+        TRY(bw_mm(e, da, d, rows, d, t.wt, d, t.ms_dx1[lvl == 0 ? cur : cur ^ 1], lvl == 0 ? nullptr : t.ms_dx1[cur]));
+        if (lvl) cur ^= 1;
+    }
+    // the shared AddNorm over the stacked rows: t.dy = d(ymesh) [levels][rows][d]; the residual x1 was broadcast to every level
+    TRY(bw_norm(e, t, p.ymesh, dl.cross_att.ln, gl.cross_att.ln, t.ms_de2, nullptr, lv * rows));
+    RUN(ovc_bw_sum_levels(t.ms_dx1[cur], t.dy, lv, (long)nrd, (long)nrd, t.ms_dx1[cur ^ 1], s));
+    cur ^= 1;
+    TRY(bw_weight(e, t, t.dy, d, d, p.attc, hk, hk, lv * rows, dl.cross_att.o, gl.cross_att.o));
+    TRY(bw_input(e, t, t.dy, d, dl.cross_att.o, hk, t.datt, nullptr, lv * rows));
+    // cross-attention: once per level on the shared queries and the level's keys / values
+    for (int lvl = 0; lvl < lv; ++lvl) {
+        const size_t kvoff = ((size_t)l * lv + lvl) * BN * hk;
+        AttnBwdArgs a{};
+        a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt + (size_t)lvl * rows * hk; a.ldo = hk;
+        a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
+        a.B = B; a.nq = S * T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+        a.P = t.P; a.dS = t.dS; a.dq = t.ms_dq + (size_t)lvl * rows * hk; a.lddq = hk;
+        a.dk_out = t.ms_dkv + (size_t)lvl * BN * 2 * hk; a.dv_out = a.dk_out + hk; a.lddkv = 2 * hk;
+        RUN(ovc_bw_attention(a, s));
+    }
+    RUN(ovc_bw_sum_levels(nullptr, t.ms_dq, lv, (long)rows * hk, (long)rows * hk, t.dqkv, s));       // d(qc)
+    TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
+    TRY(bw_input(e, t, t.dqkv, hk, dl.cross_att.q, d, t.dx1, t.ms_dx1[cur], rows));                   // t.dx1 = d(x1)
+    // the encoder levels: W_k / W_v over the stacked levels * B*N rows of enc_levels, then each level's share
+    TRY(bw_weight(e, t, t.ms_dkv, 2 * hk, hk, w.enc_levels, d, d, lv * BN, dl.cross_att.k, gl.cross_att.k));
+    TRY(bw_weight(e, t, t.ms_dkv + hk, 2 * hk, hk, w.enc_levels, d, d, lv * BN, dl.cross_att.v, gl.cross_att.v));
+    TRY(stage_kv_weights(e, t, dl.cross_att, hk));
+    for (int lvl = 0; lvl < lv; ++lvl)
+        TRY(bw_mm(e, t.ms_dkv + (size_t)lvl * BN * 2 * hk, 2 * hk, BN, 2 * hk, t.wt, d, dlev_next + lvl * nd,
+                  dlev_prev ? dlev_prev + lvl * nd : nullptr));
+    // masked self-attention over the caption
+    return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
+                             B * S, T, h, dk, dxin);
+}
+
 // bw_weight over 2 * rows rows whose inputs lie in two blocks: X0 for the first `rows`, X1 for the next (dY [2 rows][ldy] in one
 // block).  Both are staged into one transposed operand, so the sum still runs over the 2 * rows rows in ascending order.
 int bw_weight_pair(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const float* X0, const float* X1, int ldx, int k, int rows,
@@ -3266,8 +3387,13 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
     int cur = 0, enc_cur = 0;
     for (int l = L - 1; l >= 0; --l) {
         const float* xin = l == 0 ? w.x : t.tape.dec[l - 1].out;
-        TRY(bw_decoder_layer(e, t, gr, l, c, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
-                             t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1]));
+        if (c.meshed) {
+            TRY(bw_meshed_decoder_layer(e, t, gr, l, c, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.ms_dlev[enc_cur],
+                                        t.ms_dlev[l == L - 1 ? enc_cur : enc_cur ^ 1]));
+        } else {
+            TRY(bw_decoder_layer(e, t, gr, l, c, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.denc[enc_cur],
+                                 t.denc[l == L - 1 ? enc_cur : enc_cur ^ 1]));
+        }
         if (l != L - 1) enc_cur ^= 1;
         cur ^= 1;
     }
@@ -3283,17 +3409,21 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         TRY(bw_cross_level_tail(e, t, gr, B, N, dout));
         dout = t.cl_dlev + 2 * nd;
     }
+    // the multilevel encoder: layer l's output is level l -- its gradient is the decoder's for that level plus layer l+1's input gradient
+    float* mlev = c.meshed ? t.ms_dlev[enc_cur] : nullptr;
+    if (mlev) dout = mlev + (size_t)(m->n_enc - 1) * nd;
     for (int l = m->n_enc - 1; l >= 0; --l) {
         const EncTape& p = t.tape.enc[l];
         const ovc_enc_layer& el = m->enc[l];
         const ovc_enc_layer& gl = gr->enc[l];
-        const float* xin = l == 0 ? w.xe[0] : cl ? w.cl_out + (size_t)(l - 1) * nd : t.tape.enc[l - 1].out;
+        const float* xin = l == 0 ? w.xe[0] : cl ? w.cl_out + (size_t)(l - 1) * nd
+                           : mlev ? w.enc_levels + (size_t)(l - 1) * nd : t.tape.enc[l - 1].out;
         TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
                               enc_site(l, 0), train_memory(m)));
         dout = t.g[cur];
-        if (cl && l > 0) {
-            float* lev = t.cl_dlev + (size_t)(l - 1) * nd;
+        if ((cl || mlev) && l > 0) {
+            float* lev = (cl ? t.cl_dlev : mlev) + (size_t)(l - 1) * nd;
             RUN(ovc_bw_sum(lev, d, t.g[cur], d, nullptr, 0, BN, d, lev, d, s));
             dout = lev;
         }
@@ -3550,6 +3680,44 @@ extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads,
                                      float* logp_out, int use_graph, ovc_stream stream) {
     (void)boxes;       // the plain encoder reads no boxes
     return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights}, features, ids, nullptr, grad_logp, workspace,
+                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training the meshed-memory transformer: the opt-in entry points
+// ---------------------------------------------------------------------------------------------
+// ovc_forward_backward / ovc_sequence_backward for the multilevel encoder + meshed decoder (meshed_train_ok): the same TrainCall
+// with `meshed` set, so the same carve_train, issue_train_body and run_train_call.  The graph key needs nothing new: it hashes the
+// whole ovc_model (its kinds and gate pointers included), and a meshed model reaches the body through these two alone.
+namespace {
+TrainCall meshed_call(int B, int N, int S, int T, LossHead head) {
+    TrainCall c{B, N, S, T, head};
+    c.meshed = true;
+    return c;
+}
+}  // namespace
+
+extern "C" size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, int N, int T) {
+    return train_workspace_bytes(m, meshed_call(B, N, 1, T, LossHead::Xent), false);
+}
+
+extern "C" int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                           int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                           size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream) {
+    (void)boxes;       // the multilevel encoder reads no boxes
+    return run_train_call(m, grads, meshed_call(B, N, 1, T, LossHead::Xent), features, tokens, targets, nullptr, workspace,
+                          workspace_bytes, loss_out, nullptr, use_graph, stream);
+}
+
+extern "C" size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    return train_workspace_bytes(m, meshed_call(B, N, S, T, LossHead::RowWeights), false);
+}
+
+extern "C" int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                            int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                            size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
+    (void)boxes;
+    return run_train_call(m, grads, meshed_call(B, N, S, T, LossHead::RowWeights), features, ids, nullptr, grad_logp, workspace,
                           workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 

@@ -168,8 +168,8 @@ def _ffn(dst, pwff, planes=None, mode=0):
 def _grad_slots(model):
     """(parameter, field path in the ``ovc_model`` table) of every parameter ``ovc_forward_backward`` writes a gradient for:
     the plain encoder / decoder's projections, norms and FFNs, the encoder layers' memory slots (``attention.m_k`` / ``m_v``,
-    the augmented-memory transformer), the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``, ``mlp2``), the word
-    embedding and the vocabulary projection."""
+    the augmented-memory transformer), the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``, ``mlp2``), the meshed
+    decoder's level gates (``fc_alphas``; ``ovc_forward_backward_meshed``), the word embedding and the vocabulary projection."""
     from .modules import encoders
     enc, dec = model.encoder, model.decoder
     slots = []
@@ -209,6 +209,8 @@ def _grad_slots(model):
         mha(("dec", i, "self_att"), layer.self_attn)
         mha(("dec", i, "cross_att"), layer.enc_attn)
         ffn(("dec", i, "ffn"), layer.pwff)
+        for j, fc in enumerate(getattr(layer, "fc_alphas", ())):
+            lin(("dec", i, "alpha", j), fc)
     slots.append((dec.word_emb.components.weight, ("word_emb",)))
     slots.append((dec.fc.weight, ("fc",)))
     return slots
@@ -955,13 +957,15 @@ class CaptionEngine:
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------
-    def _check_trainable(self):
+    def _check_trainable(self, meshed=False):
         """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'
         self-attention has memory slots, plain decoder) and the CaMo transformer (cross-level encoder, plain decoder) in fp32:
-        anything else is refused before a launch."""
+        anything else is refused before a launch.  ``meshed=True``: the opt-in scope instead (``_check_trainable_meshed``)."""
         d = self.desc
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
+        if meshed:
+            return self._check_trainable_meshed()
         if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
             raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
                                   "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
@@ -983,6 +987,36 @@ class CaptionEngine:
         if extra:
             raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
 
+    def _check_trainable_meshed(self):
+        """``meshed=True``: the meshed-memory transformer -- the multilevel encoder, every layer's self-attention with memory
+        slots (or every one plain), in front of the meshed decoder with plain attentions and one gate per level
+        (``ovc_forward_backward_meshed``).  Anything else is refused by name before a launch."""
+        d = self.desc
+        if d.enc_kind != native.ENC_MULTILEVEL or d.dec_kind != native.DEC_MESHED:
+            raise native.OvcError("meshed=True covers the MultilevelEncoder in front of the MeshedDecoder only (this model has {} / "
+                                  "{}); call without meshed=True".format(type(self.model.encoder).__name__,
+                                                                        type(self.model.decoder).__name__))
+        model = self.model
+        layers = [layer.mhatt for layer in model.encoder.layers]
+        others = [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
+        if any(m.use_aoa for m in layers + others):
+            raise native.OvcError("meshed=True: the training backward does not cover attention-on-attention gates")
+        with_memory = [hasattr(m.attention, "m_k") for m in layers]
+        if any(hasattr(m.attention, "m_k") for m in others):
+            raise native.OvcError("meshed=True: the training backward does not cover memory slots in the decoder's attentions")
+        if any(with_memory) != all(with_memory) or all(with_memory) != (d.memory > 0):
+            raise native.OvcError("meshed=True: every encoder layer's self-attention needs memory slots, or none of them")
+        if d.n_levels != d.n_enc or d.n_levels > native.OVC_MAX_LEVELS or any(
+                len(layer.fc_alphas) != d.n_levels for layer in model.decoder.layers):
+            raise native.OvcError("meshed=True: the decoder needs one gate per encoder layer, at most {} (has {} levels, {} encoder "
+                                  "layers)".format(native.OVC_MAX_LEVELS, d.n_levels, d.n_enc))
+        if not hasattr(model.decoder.word_emb, "components"):
+            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
+        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
+        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
+        if extra:
+            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
+
     def _check_pointers(self):
         """Re-read the pointer table when a parameter's storage moved (``p.data = ...``): in-place updates (an optimizer step)
         keep the storage and are seen by every call as they are."""
@@ -996,7 +1030,7 @@ class CaptionEngine:
         return [p for p, _ in _grad_slots(self.model)]
 
     def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None,
-                         distill=None):
+                         distill=None, meshed=False):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -1020,7 +1054,13 @@ class CaptionEngine:
         states the rule and the arguments): ``P`` the teacher's ``(B, T, V)`` fp32 log-probabilities on this device, ``w`` the
         weight of the KL term.  ``P`` is copied into the workspace on the stream before the body, so a replayed graph reads this
         call's teacher; ``w`` is part of the graph key, ``P``'s contents never are.  No gradient flows into ``P``.  ``w = 0`` is
-        the plain loss and takes the plain path.  Refused together with ``loss``."""
+        the plain loss and takes the plain path.  Refused together with ``loss``.
+
+        ``meshed=True``: the meshed-memory transformer (``ovc_forward_backward_meshed``; ``_check_trainable_meshed`` states the
+        scope).  Refused together with ``dropout``, ``loss`` and ``distill``."""
+        if meshed and (dropout is not None or loss is not None or distill is not None):
+            raise native.OvcError("forward_backward(meshed=True): dropout, the label-smoothed loss and soft targets are out of "
+                                  "scope for the meshed-memory transformer")
         if distill is not None:
             if not isinstance(distill, (tuple, list)) or len(distill) != 2:
                 raise native.OvcError("forward_backward: distill must be a (teacher_log_probs, distill_weight) pair (got {!r})".format(
@@ -1039,12 +1079,12 @@ class CaptionEngine:
             loss = checked_label_smoothing(loss[0], loss[1], "forward_backward", self.desc.vocab)
             if loss == (0.0, "tokens"):
                 loss = None
-        self._check_trainable()
+        self._check_trainable(meshed)
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill)
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed)
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -1061,14 +1101,20 @@ class CaptionEngine:
     }
 
     _DISTILL_FORM = ("ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill")
+    # sequence -> the opt-in forms of the meshed-memory transformer
+    _MESHED_FORMS = {False: ("ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed"),
+                     True: ("ovc_train_meshed_beams_workspace_bytes", "ovc_sequence_backward_meshed")}
 
-    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None):
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False):
         """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
         T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
         on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
-        soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments."""
+        soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``meshed``: the
+        meshed-memory transformer's form (no loss, dropout or distill with it: the callers refuse them)."""
         sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
+        if meshed:
+            sizer, entry = self._MESHED_FORMS[bool(sequence)]
         if distill is not None:
             sizer, entry = self._DISTILL_FORM
         drop = () if table_drop is None else (ctypes.byref(table_drop),)
@@ -1084,7 +1130,7 @@ class CaptionEngine:
             "sequence" if sequence else "train", sizer, (*shape, *size_tail),
             "unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
+                sizer if meshed else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
         return entry, shape, ws, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
@@ -1127,7 +1173,7 @@ class CaptionEngine:
         return self._buffers[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
-                          beam_size=None, arena=None):
+                          beam_size=None, arena=None, meshed=False):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -1141,8 +1187,12 @@ class CaptionEngine:
         masks ``beam_search(dropout=...)`` used (``ovc_sequence_backward_dropout``).
 
         ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer, as ``forward_backward`` takes it
-        (``BaseTransformer.scst_step``); the returned ``arena`` and ``grads`` are then that arena's."""
-        self._check_trainable()
+        (``BaseTransformer.scst_step``); the returned ``arena`` and ``grads`` are then that arena's.
+
+        ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``."""
+        if meshed and dropout is not None:
+            raise native.OvcError("sequence_backward(meshed=True): dropout is out of scope for the meshed-memory transformer")
+        self._check_trainable(meshed)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         if table_drop is not None:
             if (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or
@@ -1164,7 +1214,7 @@ class CaptionEngine:
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
         form = self._train_form(True, None, table_drop, (B, N, S, T),
-                                () if table_drop is None else (int(beam_size), slots.data_ptr()))
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed)
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
         arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,

@@ -219,6 +219,13 @@ SIGNATURES = {
     "ovc_train_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sequence_backward": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_train_meshed_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
+    "ovc_forward_backward_meshed": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                            c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_train_meshed_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward_meshed": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_debug_meshed_mix_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_float, c_void_p, c_void_p, c_void_p]),
     "ovc_dropout_mask_rows": (c_int, [c_void_p, c_int, c_void_p, c_long, c_long, c_float, c_void_p, c_void_p]),
     "ovc_beam_search_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
     "ovc_beam_search_dropout": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
@@ -351,7 +358,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_search_forced_ok", "ovc_forced_workspace_bytes", "ovc_beam_search_forced", "ovc_beam_search_forced_graph",
                  "ovc_debug_beam_forced_update_bytes", "ovc_debug_beam_forced_update",
                  "ovc_debug_add_norm", "ovc_debug_add_norm_form", "ovc_debug_dropout_rows", "ovc_debug_meshed_mix",
-                 "ovc_debug_leaky_residual", "ovc_debug_sigmoid_gate")
+                 "ovc_debug_leaky_residual", "ovc_debug_sigmoid_gate",
+                 "ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed", "ovc_train_meshed_beams_workspace_bytes",
+                 "ovc_sequence_backward_meshed", "ovc_debug_meshed_mix_backward")
 
 _lib = None
 

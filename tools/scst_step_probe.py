@@ -66,9 +66,12 @@ def recompute_flops(dims, images, S, N, T):
     if dims.get("tail"):            # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
         f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * images * he * N * N * dk + 2 * BN * he * dk * d)
         f += 2 * BN * 3 * d * d + 2 * BN * d * d
-    f += Ld * 2 * BN * d * 2 * hk
-    f += Ld * (2 * R * d * 3 * hk + 4 * images * S * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * R * N * h * dk
-               + 2 * R * hk * d + 4 * R * d * dff)
+    lv = dims.get("levels", 1)      # the meshed decoder: keys / values, cross-attention and its output projection per level
+    f += Ld * lv * 2 * BN * d * 2 * hk
+    f += Ld * (2 * R * d * 3 * hk + 4 * images * S * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + lv * 4 * R * N * h * dk
+               + lv * 2 * R * hk * d + 4 * R * d * dff)
+    if "levels" in dims:            # the level gates: Linear(2d -> d) per level
+        f += Ld * lv * 2 * R * 2 * d * d
     f += 2 * R * d * V
     return 3 * f
 
@@ -300,9 +303,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--variant", default="standard_transformer",
-                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer"],
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", "meshed_memory_transformer"],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
-                         "augmented_memory_transformer: the plain encoder with 40 memory slots per layer")
+                         "augmented_memory_transformer: the plain encoder with 40 memory slots per layer; "
+                         "meshed_memory_transformer: the multilevel encoder and the meshed decoder (meshed=True; search and "
+                         "backward only: --reward none, --optimizer none, no --dropout)")
     ap.add_argument("--reward", default="none", choices=["none", "host", "device"],
                     help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
     ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
@@ -318,6 +323,9 @@ def main():
         ap.error("--fused needs --reward device --optimizer engine")
     if "none" in args.optimizer and len(args.optimizer) > 1:
         ap.error("--optimizer none stands alone")
+    meshed = dict(meshed=True) if args.variant == "meshed_memory_transformer" else {}
+    if meshed and (args.reward != "none" or args.optimizer != ["none"] or args.dropout or args.fused):
+        ap.error("meshed_memory_transformer goes with --reward none --optimizer none, without --dropout or --fused")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D, k = 10201, 20, 50, 2048, args.beam
     vocab = SyntheticVocab(V, T)
@@ -340,6 +348,8 @@ def main():
         dims.update(he=1, tail=True)
     if args.variant == "augmented_memory_transformer":
         dims.update(memory=40)
+    if meshed:
+        dims.update(memory=40, levels=3)
     results = reward_probe(args, model, V, T, N, D, k) if args.reward != "none" and not args.fused else []
     if args.fused:
         results = fused_probe(args, build, V, T, N, D, k)
@@ -355,7 +365,7 @@ def main():
         search_ms, backward_ms, lengths = [], [], []
         try:
             for i in range(args.warmup + args.steps):
-                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k))
+                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k, **meshed))
                 loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
                 model.zero_grad(set_to_none=True)
                 ms_b, _ = timed(loss.backward)
@@ -370,8 +380,8 @@ def main():
             fe, ie, ge = feats.repeat_interleave(k, 0), ids.reshape(B * k, 1, T), g.reshape(B * k, 1, T)
             shared, expanded = [], []
             for i in range(args.warmup + args.steps):
-                ms_a, _ = timed(lambda: eng.sequence_backward(feats, None, ids, g))
-                ms_e, _ = timed(lambda: eng.sequence_backward(fe, None, ie, ge))
+                ms_a, _ = timed(lambda: eng.sequence_backward(feats, None, ids, g, **meshed))
+                ms_e, _ = timed(lambda: eng.sequence_backward(fe, None, ie, ge, **meshed))
                 if i >= args.warmup:
                     shared.append(ms_a)
                     expanded.append(ms_e)

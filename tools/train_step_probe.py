@@ -5,6 +5,8 @@ configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, 
     python tools/train_step_probe.py --optimizer torch engine xe_step [--rounds 2] ...     # the whole iteration, optimizer included
 
 --variant augmented_memory_transformer: the plain encoder with 40 memory slots per layer (the memory-slot attention backward).
+--variant meshed_memory_transformer: the multilevel encoder with 40 memory slots per layer and the meshed decoder, through
+``model.xe_loss(items, meshed=True)`` (``ovc_forward_backward_meshed``; no dropout form, --optimizer none only).
 Several --variant values alternate in ONE process -- per batch size, ``--rounds`` rounds of ``--steps`` steps of each variant in
 turn, each on its own model -- so a variant's step time stands next to the standard transformer's from the same run.
 
@@ -70,9 +72,12 @@ def step_flops(cfg_dims, B, N, T):
     if cfg_dims.get("tail"):        # the cross-level tail: q of both calls, k|v, attention, fc_o per call, mlp1 (K = 3d), mlp2
         f += 2 * (2 * BN) * d * he * dk + 2 * (2 * BN * d * 2 * he * dk + 4 * B * he * N * N * dk + 2 * BN * he * dk * d)
         f += 2 * BN * 3 * d * d + 2 * BN * d * d
-    f += Ld * 2 * BN * d * 2 * hk
-    f += Ld * (2 * R * d * 3 * hk + 4 * B * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + 4 * B * h * T * N * dk
-               + 2 * R * hk * d + 4 * R * d * dff)
+    lv = cfg_dims.get("levels", 1)  # the meshed decoder: keys / values, cross-attention and its output projection per level
+    f += Ld * lv * 2 * BN * d * 2 * hk
+    f += Ld * (2 * R * d * 3 * hk + 4 * B * h * T * T * dk + 2 * R * hk * d + 2 * R * d * hk + lv * 4 * B * h * T * N * dk
+               + lv * 2 * R * hk * d + 4 * R * d * dff)
+    if "levels" in cfg_dims:        # the level gates: Linear(2d -> d) per level
+        f += Ld * lv * 2 * R * 2 * d * d
     f += 2 * R * d * V
     return 3 * f
 
@@ -207,8 +212,23 @@ def distill_probe(args, model, teacher, items, B, T, N, V):
     return rows
 
 
+MESHED = "meshed_memory_transformer"
+
+
 def variant_dims(variant):
-    return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40)}.get(variant, {})
+    return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40),
+            MESHED: dict(memory=40, levels=3)}.get(variant, {})
+
+
+def loss_kw(variant, dropout):
+    """The keywords of ``xe_loss`` for a variant: the meshed-memory transformer is opt-in and has no dropout form."""
+    return dict(meshed=True) if variant == MESHED else dict(dropout=dropout)
+
+
+def train_sizer(lib, variant, dropout):
+    if variant == MESHED:
+        return lib.ovc_train_meshed_workspace_bytes
+    return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
 
 
 def alternate_variants(args, vocab, V, T, N, D):
@@ -228,21 +248,20 @@ def alternate_variants(args, vocab, V, T, N, D):
         items.caption_tokens = tokens.cuda()
         items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
 
-        def step(model):
+        def step(variant, model):
             model.zero_grad(set_to_none=True)
-            model.xe_loss(items, dropout=args.dropout).backward()
-        for model in models.values():
+            model.xe_loss(items, **loss_kw(variant, args.dropout)).backward()
+        for variant, model in models.items():
             for _ in range(args.warmup):
-                step(model)
+                step(variant, model)
         torch.cuda.synchronize()
         for rnd in range(args.rounds):
             for variant, model in models.items():
-                ms = events_ms(lambda: step(model), args.steps)
+                ms = events_ms(lambda: step(variant, model), args.steps)
                 dims = dict(d=512, h=8, dk=64, dff=2048, dfeat=D, V=V, Le=3, Ld=3, **variant_dims(variant))
                 flops = step_flops(dims, B, N, T)
                 lib = model._fused_engine().lib
-                sizer = lib.ovc_train_dropout_workspace_bytes if args.dropout else lib.ovc_train_workspace_bytes
-                ws = sizer(model._fused_engine().desc, B, N, T)
+                ws = train_sizer(lib, variant, args.dropout)(model._fused_engine().desc, B, N, T)
                 row = dict(variant=variant, B=B, T=T, N=N, dropout=args.dropout, round=rnd, ms_per_step=round(ms, 3),
                            gflop_per_step=round(flops / 1e9, 1), tflops=round(flops / ms / 1e9, 2), workspace_mb=round(ws / 2 ** 20, 1))
                 results.append(row)
@@ -260,9 +279,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
     ap.add_argument("--variant", nargs="+", default=["standard_transformer"],
-                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer"],
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
-                         "augmented_memory_transformer: 40 memory slots in the encoder; several values alternate in one process")
+                         "augmented_memory_transformer: 40 memory slots in the encoder; meshed_memory_transformer: the multilevel "
+                         "encoder and the meshed decoder (meshed=True); several values alternate in one process")
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
                     help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
@@ -285,6 +305,9 @@ def main():
         ap.error("--reduction goes with --label-smoothing")
     if args.distill is not None and (args.optimizer != ["none"] or len(args.variant) > 1 or args.label_smoothing is not None):
         ap.error("--distill goes with --optimizer none and one --variant, without --label-smoothing")
+    if MESHED in args.variant and (args.dropout or args.optimizer != ["none"] or args.label_smoothing is not None or
+                                   args.distill is not None):
+        ap.error("meshed_memory_transformer goes with --optimizer none, without --dropout, --label-smoothing or --distill")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)
@@ -325,20 +348,19 @@ def main():
             continue
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)
-            model.xe_loss(items, dropout=args.dropout).backward()
+            model.xe_loss(items, **loss_kw(args.variant, args.dropout)).backward()
         torch.cuda.synchronize()
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         for _ in range(args.steps):
             model.zero_grad(set_to_none=True)
-            model.xe_loss(items, dropout=args.dropout).backward()
+            model.xe_loss(items, **loss_kw(args.variant, args.dropout)).backward()
         stop.record()
         torch.cuda.synchronize()
         ms = start.elapsed_time(stop) / args.steps
         flops = step_flops(dims, B, N, T)
         lib = model._fused_engine().lib
-        sizer = lib.ovc_train_dropout_workspace_bytes if args.dropout else lib.ovc_train_workspace_bytes
-        ws = sizer(model._fused_engine().desc, B, N, T)
+        ws = train_sizer(lib, args.variant, args.dropout)(model._fused_engine().desc, B, N, T)
         row = dict(variant=args.variant, B=B, T=T, N=N, dropout=args.dropout, ms_per_step=round(ms, 3), gflop_per_step=round(flops / 1e9, 1),
                    tflops=round(flops / ms / 1e9, 2), fp32_matrix_fraction=round(flops / (ms * 1e-3) / PEAK_F32_MATRIX, 4),
                    workspace_mb=round(ws / 2 ** 20, 1))

@@ -514,6 +514,47 @@ int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, con
 int ovc_debug_meshed_mix_backward(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor,
                                   float* denc, float* dalpha, ovc_stream stream);
 
+/* Training the object-relation transformer: ovc_forward_backward and ovc_sequence_backward for the geometric encoder
+ * (encoders.py:93-112: plain layers whose attention adds log(clamp(relu(fc_g(emb(boxes))), 1e-6)) to the scaled, masked scores,
+ * attentions.py:97-114) in front of the plain decoder.  Opt-in: the entry points above and their sizers keep refusing this model
+ * (OVC_EINVAL / 0), these two take it and nothing else.  The arguments, the results, what is read outside the captured body, the
+ * graph rule and the determinism are those of ovc_forward_backward(_dropout) and ovc_sequence_backward; boxes [B][N][4] are
+ * required (NULL or not aligned to 16 bytes: OVC_EINVAL) and are copied into the workspace before the body, so a replayed graph
+ * reads this call's boxes; they get no gradient.  grads additionally receives fc_g_w [h][d_g] and fc_g_b as [h][4], element 0 of
+ * each group the gradient and the other three 0 (a gradient arena pads every slot to 4 floats).  With a = fc_g_w[h] . emb(i, j) + fc_g_b[h] and w = relu(a)
+ * the forward's stored value: d(bias) = the encoder layers' dS summed from the top layer down, d(a) = w >= 1e-6 ? d(bias) / w : 0.
+ * dropout: NULL, or the table of ovc_forward_backward_dropout (the encoder's sites are the plain encoder's).  Scope -- anything
+ * else is OVC_EINVAL before any launch, and the sizers answer 0:
+ *   precision 0 (fp32); enc_kind == OVC_ENC_GEOMETRIC, dec_kind == OVC_DEC_PLAIN, n_levels == 1, memory == 0; fc_g_w / fc_g_b
+ *   given in the model and in grads; every attention plain: no AoA gates, no memory slots;
+ *   encoder heads <= 16; d_g == 4 without the trigonometric embedding, a multiple of 8 in 8..64 with it; N <= 1024;
+ *   the fused vocabulary tail and the 32-bit descriptor limits of ovc_forward_backward.
+ * There is no sequence form under dropout.
+ * ovc_train_geometric_workspace_bytes (dropout != 0: for a call with a table) / ovc_train_geometric_beams_workspace_bytes: bytes
+ * of workspace, 0 when unsupported. */
+size_t ovc_train_geometric_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout);
+int ovc_forward_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                   const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                                   float* loss_out, int use_graph, ovc_stream stream, const ovc_dropout* dropout);
+size_t ovc_train_geometric_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                                    int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                                    float* logp_out, int use_graph, ovc_stream stream);
+/* Test hooks (tests/test_geometric_train_gpu.py).  ovc_debug_box_relation_backward: the bias's parameter gradients as the
+ * geometric training calls launch them -- boxes [B][N][4], w (the forward's stored relu output) and dG [B][h][N][N], dfc_w
+ * [h][d_g], dfc_b [h][4] (element 0 of each group the gradient, the other three 0); scratch: at least ovc_debug_box_relation_backward_floats floats.
+ * Every sum runs in an order fixed by the shape.  OVC_EINVAL, nothing written: h outside 1..16, d_g != 4 for trig == 0, d_g not a
+ * multiple of 8 in 8..64 for trig != 0, N outside 1..1024, B < 1, too little scratch, a NULL pointer or one not aligned to 16 bytes.
+ * ovc_debug_attention_backward: the attention backward of the training calls on caller tensors -- q / dout / dq [B*nq][h dk],
+ * k / v / dk_out / dv_out [B*nk][h dk], mask [B][nk] (nonzero: key masked; NULL: none), geometry [B][h][nq][nk] (NULL: none), P and
+ * dS [B][h][nq][nk] written.  dk <= 64, nk <= 8000. */
+size_t ovc_debug_box_relation_backward_floats(int B, int N, int h, int d_g);
+int ovc_debug_box_relation_backward(const float* boxes, const float* w, const float* dG, int B, int N, int h, int d_g, int trig,
+                                    float* scratch, size_t scratch_floats, float* dfc_w, float* dfc_b, ovc_stream stream);
+int ovc_debug_attention_backward(const float* q, const float* k, const float* v, const float* dout, const uint8_t* mask,
+                                 const float* geometry, int B, int nq, int nk, int h, int dk, float* P, float* dS, float* dq,
+                                 float* dk_out, float* dv_out, ovc_stream stream);
+
 /* SCST under dropout (the reference's train_scst searches in train() mode, vi_trainer.py:121-158): the beam search with the
  * dropout sites above applied, and the backward of its log-probabilities under the SAME masks.  The plain standard transformer,
  * with or without encoder memory slots, precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.

@@ -45,6 +45,10 @@ struct AttnBwdArgs {
     float* P; float* dS;               // scratch [B][h][nq][nk]
     float* dq; long lddq;
     float* dk_out; float* dv_out; long lddkv;
+    // the geometric encoder's bias [B][h][nq][nk] (the forward's stored relu(fc_g(emb)), Workspace::geometry), nullptr: none.  The
+    // rows pass adds log(max(g, 1e-6)) to the scaled, masked score as the forward does; a compile-time instance, so without it the
+    // kernel is the one without the member.  dS is then also d(bias).
+    const float* geometry;
 };
 int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s);
 
@@ -129,3 +133,21 @@ int ovc_bw_meshed_mix(const float* dmixed, const float* alpha, const float* enc,
 // out[i] = ((acc[i] + src[i]) + src[stride + i]) + ... over `levels` blocks of n floats in ascending order; acc may be nullptr (the sum
 // starts from block 0), out may alias acc
 int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out, hipStream_t s);
+
+// The geometric (object-relation) encoder's bias (engine.hip issue_train_body).
+// acc[i] = acc[i] + src[i] over n floats: the layers' dS summed into d(bias) in the caller's order.  16-byte accesses when n % 4 == 0
+// and both pointers are aligned to 16 bytes, scalar ones otherwise -- the same bits either way (element-wise).
+int ovc_bw_accumulate(float* acc, const float* src, long n, hipStream_t s);
+// Backward of w = relu(fc_w[h] . emb(i, j) + fc_b[h]) feeding log(max(w, 1e-6)) (ovc_box_relation_weights + the attention's bias):
+// with d(a) = w >= 1e-6 ? dG / w : 0 (torch's clamp(min) and relu backward together, decided by the forward's STORED w),
+//   dfc_w[hd][c] = sum_{b,i,j} d(a)[b,hd,i,j] emb_c(i,j),   dfc_b[hd * kBoxBiasStride] = sum_{b,i,j} d(a)[b,hd,i,j].
+// boxes [B][N][4]; w, dG [B][h][N][N]; dfc_w [h][d_g]; dfc_b [h][kBoxBiasStride] (element 0 of each group is the gradient, the other
+// three are written 0: the gradient arena pads every slot to 4 floats).  emb is recomputed with box_relation.h's expressions.  One workgroup per (b, i) runs one fmaf chain per
+// output over ascending j (64-key tiles staged in LDS, every sin / cos once), the rows' partials [B*N][h (d_g + 1)] are summed by
+// ovc_bw_colsum, and a last launch writes the slots: fixed order, no atomics.  scratch: ovc_bw_box_relation_scratch_floats floats.
+// OVC_EINVAL: h outside 1..16, d_g != 4 for trig == 0, d_g not a multiple of 8 in 8..64 for trig == 1, N outside 1..1024, B < 1, a
+// null pointer or one not aligned to 16 bytes.
+constexpr int kBoxBiasStride = 4;
+size_t ovc_bw_box_relation_scratch_floats(int B, int N, int h, int d_g);
+int ovc_bw_box_relation(const float* boxes, const float* w, const float* dG, int B, int N, int h, int d_g, int trig, float* scratch,
+                        float* dfc_w, float* dfc_b, hipStream_t s);

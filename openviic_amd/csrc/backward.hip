@@ -2,6 +2,7 @@
 // Everything here is deterministic by construction: each output element is written by one lane, and every sum over rows,
 // queries, keys or columns runs in an order fixed by the shape alone.
 #include "backward.h"
+#include "box_relation.h"
 
 namespace {
 
@@ -141,7 +142,10 @@ __global__ void bw_relu_kernel(float* __restrict__ g, const float* __restrict__ 
         if (!(act[i] > 0.f)) g[i] = 0.f;
 }
 
-// one wave per (b, head, query row); LDS: q and dout of the row (dk <= 64), scores / dP of the nk keys
+// one wave per (b, head, query row); LDS: q and dout of the row (dk <= 64), scores / dP of the nk keys.  GEO: the encoder's geometry
+// bias log(max(g, 1e-6)) + s added to the scaled, masked score in the forward's operation order (attention.hip); the <false>
+// instance is the kernel without it, instruction for instruction.
+template <bool GEO>
 __global__ __launch_bounds__(64) void bw_attention_rows_kernel(AttnBwdArgs a) {
     extern __shared__ float sm[];
     float* qs = sm; float* os = sm + 64; float* s = sm + 128; float* dp = s + a.nk;
@@ -152,6 +156,7 @@ __global__ __launch_bounds__(64) void bw_attention_rows_kernel(AttnBwdArgs a) {
     if (lane < dk) { qs[lane] = a.q[qrow * a.ldq + hh * dk + lane]; os[lane] = a.dout[qrow * a.ldo + hh * dk + lane]; }
     __syncthreads();
     const uint8_t* mrow = a.mask ? a.mask + (size_t)b * a.mask_b + (size_t)i * a.mask_r : nullptr;
+    const size_t po = (((size_t)b * a.h + hh) * a.nq + i) * a.nk;
     float mx = -INFINITY;
     for (int j = lane; j < a.nk; j += 64) {
         const float* kr = a.k + ((size_t)b * a.nk + j) * a.ldkv + hh * dk;
@@ -159,6 +164,7 @@ __global__ __launch_bounds__(64) void bw_attention_rows_kernel(AttnBwdArgs a) {
         float sc = 0.f, g = 0.f;
         for (int t = 0; t < dk; ++t) { sc = fmaf(qs[t], kr[t], sc); g = fmaf(os[t], vr[t], g); }
         sc = (mrow && mrow[j]) ? -INFINITY : sc / a.scale;
+        if (GEO) sc = logf(fmaxf(a.geometry[po + j], 1e-6f)) + sc;
         s[j] = sc; dp[j] = g;
         mx = fmaxf(mx, sc);
     }
@@ -173,7 +179,6 @@ __global__ __launch_bounds__(64) void bw_attention_rows_kernel(AttnBwdArgs a) {
         delta = fmaf(p, dp[j], delta);
     }
     delta = wave_sum(delta);
-    const size_t po = (((size_t)b * a.h + hh) * a.nq + i) * a.nk;
     for (int j = lane; j < a.nk; j += 64) {
         const float p = s[j], g = p * (dp[j] - delta);
         dp[j] = g;
@@ -696,7 +701,8 @@ int ovc_bw_relu_dropout(float* g, const float* act, float scale, long n, hipStre
 int ovc_bw_attention(const AttnBwdArgs& a, hipStream_t s) {
     if (a.dk > 64 || a.dk <= 0 || a.nk <= 0 || a.nq <= 0) return OVC_EINVAL;
     const size_t lds = (128 + 2 * (size_t)a.nk) * sizeof(float);
-    hipLaunchKernelGGL(bw_attention_rows_kernel, dim3(a.B * a.h * a.nq), dim3(64), lds, s, a);
+    if (a.geometry) hipLaunchKernelGGL(bw_attention_rows_kernel<true>, dim3(a.B * a.h * a.nq), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL(bw_attention_rows_kernel<false>, dim3(a.B * a.h * a.nq), dim3(64), lds, s, a);
     OVC_RETURN_IF_LAUNCH_FAILED();
     hipLaunchKernelGGL(bw_attention_keys_kernel, dim3(a.B * a.h * a.nk), dim3(64), 0, s, a);
     OVC_RETURN_IF_LAUNCH_FAILED();
@@ -991,6 +997,177 @@ int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long strid
     hipLaunchKernelGGL(bw_sum_levels_kernel, dim3(blocks_for(n)), dim3(256), 0, s, acc, src, levels, stride, n, out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
+}
+
+// ---- the geometric (object-relation) encoder's bias (engine.hip, issue_train_body) ------------------------
+namespace {
+
+constexpr int kBoxTile = 64;           // keys staged per round
+constexpr int kBoxThreads = 256;
+constexpr int kBoxOuts = 5;            // outputs per thread: ceil(16 (64 + 1) / 256)
+
+// no __restrict__: element-wise, acc is read and written by the same lane
+__global__ void bw_accumulate4_kernel(float* acc, const float* src, long n4) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 a = reinterpret_cast<const f32x4*>(acc)[i], b = reinterpret_cast<const f32x4*>(src)[i];
+        reinterpret_cast<f32x4*>(acc)[i] = a + b;
+    }
+}
+__global__ void bw_accumulate_kernel(float* acc, const float* src, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) acc[i] = acc[i] + src[i];
+}
+
+// One workgroup per (image b, query region i).  Per round of 64 keys: the keys' four log-ratios, then the embedding emb [64][d_g]
+// (every sin / cos once) and d(a) [h][64] = w >= 1e-6 ? dG / w : 0 go to LDS; output o = (head, c) -- c == d_g: the bias -- is owned
+// by thread o % 256 and continues ONE fmaf chain over the keys in ascending order across the rounds.  part [B*N][h (d_g + 1)].
+// LDS: (64 d_g + 64 h + 256) floats <= 21 KB.
+__global__ __launch_bounds__(kBoxThreads) void bw_box_relation_kernel(const float* __restrict__ boxes, const float* __restrict__ w,
+                                                                      const float* __restrict__ dG, int n, int h, int d_g, int trig,
+                                                                      float* __restrict__ part) {
+    extern __shared__ float sm[];
+    float* emb = sm;                              // [64][d_g]
+    float* da = emb + kBoxTile * d_g;             // [h][64]
+    float* logs = da + h * kBoxTile;              // [64][4]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / n, i = blockIdx.x - b * n;
+    const BoxGeom gi = box_geom(boxes + ((size_t)b * n + i) * 4);
+    const int per = d_g + 1, nout = h * per;
+    int ohd[kBoxOuts], oc[kBoxOuts];
+    float acc[kBoxOuts];
+#pragma unroll
+    for (int r = 0; r < kBoxOuts; ++r) {
+        const int o = tid + kBoxThreads * r;
+        ohd[r] = o / per; oc[r] = o - ohd[r] * per; acc[r] = 0.f;
+    }
+    for (int j0 = 0; j0 < n; j0 += kBoxTile) {
+        const int nt = min(kBoxTile, n - j0);
+        if (tid < nt) {
+            float g[4];
+            box_relation_logs(gi, box_geom(boxes + ((size_t)b * n + j0 + tid) * 4), g);
+            float* dst = trig ? logs + tid * 4 : emb + tid * 4;       // without the trigonometric embedding emb is the log-ratios
+            dst[0] = g[0]; dst[1] = g[1]; dst[2] = g[2]; dst[3] = g[3];
+        }
+        for (int e = tid; e < h * kBoxTile; e += kBoxThreads) {
+            const int hd = e / kBoxTile, jj = e - hd * kBoxTile;
+            float v = 0.f;
+            if (jj < nt) {
+                const size_t o = (((size_t)b * h + hd) * n + i) * n + j0 + jj;
+                const float wv = w[o];
+                v = wv >= 1e-6f ? dG[o] / wv : 0.f;
+            }
+            da[e] = v;
+        }
+        if (trig) {
+            __syncthreads();
+            const int nf = d_g / 8, half = d_g / 2;
+            for (int e = tid; e < nt * half; e += kBoxThreads) {
+                const int jj = e / half, cq = e - jj * half, c = cq / nf, q = cq - c * nf;
+                const float ang = box_relation_angle(logs[jj * 4 + c], q, nf);
+                emb[jj * d_g + cq] = sinf(ang);
+                emb[jj * d_g + half + cq] = cosf(ang);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kBoxOuts; ++r) {
+            if (tid + kBoxThreads * r >= nout) continue;
+            const float* dr = da + ohd[r] * kBoxTile;
+            float s = acc[r];
+            if (oc[r] < d_g) {
+                const float* er = emb + oc[r];
+                for (int jj = 0; jj < nt; ++jj) s = fmaf(dr[jj], er[jj * d_g], s);
+            } else {
+                for (int jj = 0; jj < nt; ++jj) s += dr[jj];
+            }
+            acc[r] = s;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < kBoxOuts; ++r) {
+        const int o = tid + kBoxThreads * r;
+        if (o < nout) part[(size_t)blockIdx.x * nout + o] = acc[r];
+    }
+}
+
+// sum [h][d_g + 1] -> dfc_w [h][d_g] and dfc_b [h][kBoxBiasStride]: element 0 of a group is the gradient, the padding behind it 0 (a
+// gradient arena is compared and summed as a whole: its padding must not depend on what the allocator left there)
+__global__ void bw_box_relation_write_kernel(const float* __restrict__ sum, int h, int d_g, float* __restrict__ dfc_w,
+                                             float* __restrict__ dfc_b) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x, per = d_g + 1;
+    if (o >= h * per) return;
+    const int hd = o / per, c = o - hd * per;
+    if (c < d_g) dfc_w[hd * d_g + c] = sum[o];
+    else
+        for (int p = 0; p < kBoxBiasStride; ++p) dfc_b[hd * kBoxBiasStride + p] = p == 0 ? sum[o] : 0.f;
+}
+
+inline size_t box_pad4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+}  // namespace
+
+int ovc_bw_accumulate(float* acc, const float* src, long n, hipStream_t s) {
+    if (!acc || !src || n <= 0) return OVC_EINVAL;
+    if (n % 4 == 0 && ovc_aligned16(acc) && ovc_aligned16(src))
+        hipLaunchKernelGGL(bw_accumulate4_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, s, acc, src, n / 4);
+    else
+        hipLaunchKernelGGL(bw_accumulate_kernel, dim3(blocks_for(n)), dim3(256), 0, s, acc, src, n);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+size_t ovc_bw_box_relation_scratch_floats(int B, int N, int h, int d_g) {
+    if (B < 1 || N < 1 || h < 1 || d_g < 1) return 0;
+    const size_t rows = (size_t)B * N, nout = (size_t)h * (d_g + 1);
+    return box_pad4(rows * nout) + box_pad4(((rows + kChunk - 1) / kChunk) * nout) + box_pad4(nout);
+}
+
+int ovc_bw_box_relation(const float* boxes, const float* w, const float* dG, int B, int N, int h, int d_g, int trig, float* scratch,
+                        float* dfc_w, float* dfc_b, hipStream_t s) {
+    if (!boxes || !w || !dG || !scratch || !dfc_w || !dfc_b) return OVC_EINVAL;
+    if (!ovc_aligned16(boxes) || !ovc_aligned16(w) || !ovc_aligned16(dG) || !ovc_aligned16(scratch) || !ovc_aligned16(dfc_w) ||
+        !ovc_aligned16(dfc_b)) return OVC_EINVAL;
+    if (B < 1 || N < 1 || N > 1024 || h < 1 || h > 16 || (long)B * N > 0x7fffffffL / 2) return OVC_EINVAL;
+    if (trig ? (d_g < 8 || d_g > 64 || d_g % 8 != 0) : d_g != 4) return OVC_EINVAL;
+    const int rows = B * N, nout = h * (d_g + 1);
+    float* part = scratch;
+    float* colpart = part + box_pad4((size_t)rows * nout);
+    float* sum = colpart + box_pad4((size_t)((rows + kChunk - 1) / kChunk) * nout);
+    const size_t lds = ((size_t)kBoxTile * d_g + (size_t)kBoxTile * h + kBoxTile * 4) * sizeof(float);
+    hipLaunchKernelGGL(bw_box_relation_kernel, dim3(rows), dim3(kBoxThreads), lds, s, boxes, w, dG, N, h, d_g, trig ? 1 : 0, part);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    if (const int rc = ovc_bw_colsum(part, nout, rows, nout, colpart, sum, s)) return rc;
+    hipLaunchKernelGGL(bw_box_relation_write_kernel, dim3((nout + 255) / 256), dim3(256), 0, s, sum, h, d_g, dfc_w, dfc_b);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+// Test hooks (include/ovc.h; tests/test_geometric_train_gpu.py): ovc_bw_box_relation and ovc_bw_attention on caller-supplied buffers.
+extern "C" size_t ovc_debug_box_relation_backward_floats(int B, int N, int h, int d_g) {
+    return ovc_bw_box_relation_scratch_floats(B, N, h, d_g);
+}
+
+extern "C" int ovc_debug_box_relation_backward(const float* boxes, const float* w, const float* dG, int B, int N, int h, int d_g, int trig,
+                                               float* scratch, size_t scratch_floats, float* dfc_w, float* dfc_b, ovc_stream stream) {
+    if (B < 1 || N < 1 || h < 1 || d_g < 1 || scratch_floats < ovc_bw_box_relation_scratch_floats(B, N, h, d_g)) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_box_relation(boxes, w, dG, B, N, h, d_g, trig, scratch, dfc_w, dfc_b, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_attention_backward(const float* q, const float* k, const float* v, const float* dout, const uint8_t* mask,
+                                            const float* geometry, int B, int nq, int nk, int h, int dk, float* P, float* dS, float* dq,
+                                            float* dk_out, float* dv_out, ovc_stream stream) {
+    if (!q || !k || !v || !dout || !P || !dS || !dq || !dk_out || !dv_out || B <= 0 || nq <= 0 || nk <= 0 || h <= 0) return OVC_EINVAL;
+    if (dk <= 0 || dk > 64 || nk > 8000 || (long)B * h * std::max(nq, nk) > 0x7fffffffL / 2) return OVC_EINVAL;   // LDS: 128 + 2 nk floats
+    if (const int rc = ovc_device_guard()) return rc;
+    const int hk = h * dk;
+    AttnBwdArgs a{};
+    a.q = q; a.ldq = hk; a.k = k; a.v = v; a.ldkv = hk; a.dout = dout; a.ldo = hk;
+    a.mask = mask; a.mask_b = nk; a.mask_r = 0;
+    a.B = B; a.nq = nq; a.nk = nk; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+    a.P = P; a.dS = dS; a.dq = dq; a.lddq = hk; a.dk_out = dk_out; a.dv_out = dv_out; a.lddkv = hk;
+    a.geometry = geometry;
+    return ovc_bw_attention(a, ovc_hip_stream(stream));
 }
 
 extern "C" int ovc_debug_meshed_mix_backward(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor,

@@ -2836,6 +2836,9 @@ struct TrainWs {
     // the gates' share and d(a_l), [levels][rows][d] each; the running d(x1) [2][rows][d]; the levels' dq [levels][rows][h d_k] and
     // dk|dv [levels][B*N][2 h d_k]; the encoder levels' gradients, summed over the decoder layers, [2][levels][B*N][d]
     float* ms_de; float* ms_de2; float* ms_da; float* ms_dx1[2]; float* ms_dq; float* ms_dkv; float* ms_dlev[2];
+    // the geometric encoder's bias (TrainCall::geometric only): the caller's boxes [B*N][4], copied in outside the captured body;
+    // d(bias) [B][h_enc][N][N], the encoder layers' dS summed top down; ovc_bw_box_relation's scratch
+    float* geo_boxes; float* geo_dG; float* geo_scratch;
     size_t bytes;
 };
 
@@ -2852,9 +2855,10 @@ enum class LossHead {
     SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The fourteen exported functions fill one of these, and the scope (call_ok), the workspace
-// layout and size (carve_train), the captured body (issue_train_body), the graph key (train_graph_key) and the launches around
-// the body (run_train_call) are functions of it: a sizer and the entry point that carves its buffer cannot disagree.
+// One training call, described once.  The twenty exported functions (ten entry points, ten sizers) fill one of these, and the
+// scope (call_ok), the workspace layout and size (carve_train), the captured body (issue_train_body), the graph key
+// (train_graph_key) and the launches around the body (run_train_call) are functions of it: a sizer and the entry point that carves
+// its buffer cannot disagree.
 struct TrainCall {
     // the members every call states, first: TrainCall{B, N, S, T, head}; the rest is zero unless a form fills it in
     int B, N, S, T;                                 // S sequences per image, rows = B*S*T (run_forward_decoder); 1 but for RowWeights
@@ -2867,6 +2871,7 @@ struct TrainCall {
     DropPlan* plan; const int64_t* seed; uint64_t drop_hash;
     int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
     bool meshed;                                    // the multilevel encoder + meshed decoder (meshed_train_ok), the opt-in entry points
+    bool geometric;                                 // the geometric encoder + plain decoder (geometric_train_ok), the opt-in entry points
     bool seq() const { return head == LossHead::RowWeights; }
     // The call's teacher-forced pass: the logits kept for the backward; RowWeights: on the caller's ids and their row gradient.
     ForwardCall forward() const {
@@ -2942,6 +2947,11 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         t.ms_dq = a.take<float>(lv * rows * hk); t.ms_dkv = a.take<float>(lv * BN * 2 * hk);
         for (int i = 0; i < 2; ++i) t.ms_dlev[i] = a.take<float>(lv * BN * d);
     }
+    if (c.geometric) {
+        const size_t eh = enc_heads(m);
+        t.geo_boxes = a.take<float>(BN * 4); t.geo_dG = a.take<float>((size_t)B * eh * N * N);
+        t.geo_scratch = a.take<float>(ovc_bw_box_relation_scratch_floats(B, N, (int)eh, m->d_g));
+    }
     if (c.plan) {
         t.dproj = a.take<float>(R * d);
         t.seed = a.take<int64_t>(2);
@@ -3007,8 +3017,25 @@ bool meshed_train_ok(const ovc_model* m, const ForwardCall& c) {
     return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
 }
 
+// The opt-in scope (ovc_forward_backward_geometric, ovc_sequence_backward_geometric): the geometric (object-relation) encoder --
+// plain layers whose attention scores take the box-relation bias log(max(relu(fc_g(emb(boxes))), 1e-6)) -- in front of the plain
+// decoder; fp32, the fused vocabulary tail and the descriptor limits as in train_ok.  The bias's backward (ovc_bw_box_relation)
+// covers h <= 16, d_g == 4 without and a multiple of 8 up to 64 with the trigonometric embedding, and N <= 1024.
+bool geometric_train_ok(const ovc_model* m, const ForwardCall& c) {
+    if (!forward_ok(m, c) || m->precision != 0) return false;
+    if (m->enc_kind != OVC_ENC_GEOMETRIC || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    if (!m->fc_g_w || !m->fc_g_b) return false;
+    if (enc_heads(m) > 16 || c.N > 1024 || (m->trig ? (m->d_g < 8 || m->d_g > 64 || m->d_g % 8 != 0) : m->d_g != 4)) return false;
+    for (int l = 0; l < m->n_enc; ++l) if (!mha_plain(m->enc[l].att)) return false;
+    for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
+    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
+    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
+    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
+}
+
 bool grads_ok(const ovc_model* m, const ovc_model* g) {
     if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
+    if (m->enc_kind == OVC_ENC_GEOMETRIC && (!g->fc_g_w || !g->fc_g_b)) return false;
     if (m->dec_kind == OVC_DEC_MESHED)
         for (int l = 0; l < m->n_dec; ++l)
             for (int lvl = 0; lvl < m->n_levels; ++lvl) if (!lin_grad_ok(m->dec[l].alpha[lvl], g->dec[l].alpha[lvl])) return false;
@@ -3029,9 +3056,11 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
 bool dropout_train_ok(const ovc_model* m, const ForwardCall& c) { return train_ok(m, c) && m->enc_kind == OVC_ENC_PLAIN; }
 
 // The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope;
-// the opt-in meshed scope for the meshed entry points, and nothing else reaches it.
+// the opt-in meshed scope for the meshed entry points and the opt-in geometric scope for the geometric ones, and nothing else
+// reaches either.  A geometric call takes a dropout plan: the encoder's sites are the plain encoder's.
 bool call_ok(const ovc_model* m, const TrainCall& c) {
-    if (c.meshed) return !c.plan && meshed_train_ok(m, c.forward());      // no dropout form: ovc_dropout has no per-level site
+    if (c.meshed) return !c.plan && !c.geometric && meshed_train_ok(m, c.forward());   // no dropout form: ovc_dropout has no per-level site
+    if (c.geometric) return geometric_train_ok(m, c.forward());
     return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward());
 }
 
@@ -3112,7 +3141,8 @@ int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const flo
 // to dx (gradient of the layer input x, which fed q, k, v and the residual)
 int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const float* x, const float* q, const float* k,
                       const float* v, const float* att, const float* y, const float* dnorm, const uint8_t* mask, long mask_b,
-                      long mask_r, int B, int n, int h, int dk, float* dx, int site = -1, int mem = 0) {
+                      long mask_r, int B, int n, int h, int dk, float* dx, int site = -1, int mem = 0, const float* geometry = nullptr,
+                      float* dS_out = nullptr) {
     const int d = e.m->d_model, hk = h * dk, rows = B * n;
     TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows, site));
     const float* dp = proj_grad(e, t, site);
@@ -3123,6 +3153,9 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
     p.mask = mask; p.mask_b = mask_b; p.mask_r = mask_r;
     p.B = B; p.nq = n; p.nk = n; p.h = h; p.dk = dk; p.scale = sqrtf((float)dk);
     p.P = t.P; p.dS = t.dS; p.dq = t.dqkv; p.lddq = 3 * hk; p.dk_out = t.dqkv + hk; p.dv_out = t.dqkv + 2 * hk; p.lddkv = 3 * hk;
+    // the geometric encoder: the forward's bias in the recomputed scores; dS, which is also d(bias), where the caller wants it
+    p.geometry = geometry;
+    if (dS_out) p.dS = dS_out;
     if (mem > 0) {
         // the encoder's memory slots: the forward's scales (run_encoder_layers), d(m_k) / d(m_v) summed over the whole batch
         AttnBwdMemArgs pm{};
@@ -3419,8 +3452,13 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         const float* xin = l == 0 ? w.xe[0] : cl ? w.cl_out + (size_t)(l - 1) * nd
                            : mlev ? w.enc_levels + (size_t)(l - 1) * nd : t.tape.enc[l - 1].out;
         TRY(bw_ffn(e, t, el.ffn, gl.ffn, p.x1, p.ff, p.yf, dout, w.enc_mask, BN, enc_site(l, 1), enc_site(l, 2)));
+        // the geometric encoder: every layer adds the same bias, so d(bias) is the layers' dS summed top down -- the top layer's
+        // rows pass writes it in place, the layers below add theirs
+        const bool top = l == m->n_enc - 1;
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
-                              enc_site(l, 0), train_memory(m)));
+                              enc_site(l, 0), train_memory(m), c.geometric ? w.geometry : nullptr,
+                              c.geometric && top ? t.geo_dG : nullptr));
+        if (c.geometric && !top) RUN(ovc_bw_accumulate(t.geo_dG, t.dS, (long)B * eh * N * N, s));
         dout = t.g[cur];
         if ((cl || mlev) && l > 0) {
             float* lev = (cl ? t.cl_dlev : mlev) + (size_t)(l - 1) * nd;
@@ -3429,6 +3467,10 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         }
         cur ^= 1;
     }
+    // the bias's parameters, from the stored w (Workspace::geometry: written before the body, read-only since) and the staged boxes
+    if (c.geometric)
+        RUN(ovc_bw_box_relation(t.geo_boxes, w.geometry, t.geo_dG, B, N, eh, m->d_g, m->trig, t.geo_scratch, out_ptr(gr->fc_g_w),
+                                out_ptr(gr->fc_g_b), s));
     // feature embedding: encoder.layer_norm over the projection (the sinusoid added after it has no parameters)
     e.gemm_class = 0;
     TRY(bw_norm(e, t, w.ey, m->enc_ln, gr->enc_ln, dout, nullptr, BN, kSiteEmb));
@@ -3484,12 +3526,16 @@ int bind_train_drop(Engine& e, TrainWs& t, const TrainCall& c) {
     return OVC_OK;
 }
 
-// The staging that reads the caller's inputs, outside the captured body: the pass's own (the plain encoder reads no boxes), then
-// the token rows -- the caller's, or the ones staged from its ids -- and the transposed features of the embedding gradients.
-int stage_train_inputs(Engine& e, TrainWs& t, const ForwardCall& f, const float* features) {
+// The staging that reads the caller's inputs, outside the captured body: the pass's own (the geometric encoder's bias from the
+// boxes; every other encoder reads none), then the token rows -- the caller's, or the ones staged from its ids -- and the
+// transposed features of the embedding gradients.  A geometric call also copies the boxes into their slot: the body's
+// ovc_bw_box_relation reads them there, so a replayed graph reads this call's.
+int stage_train_inputs(Engine& e, TrainWs& t, const ForwardCall& f, const float* features, const float* boxes) {
     const ovc_model* m = e.m;
     const int BN = f.B * f.N;
-    TRY(stage_forward_inputs(e, t.w, f, features, nullptr));
+    TRY(stage_forward_inputs(e, t.w, f, features, boxes));
+    if (t.geo_boxes && hipMemcpyAsync(t.geo_boxes, boxes, (size_t)BN * 4 * sizeof(float), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+        return OVC_ELAUNCH;
     TRY(ovc_bw_tokens(f.input == ForwardInput::Ids ? t.w.seq_tok : f.tokens, f.rows(), m->vocab, t.tok, e.stream));
     return ovc_bw_transpose(features, m->d_feat, BN, m->d_feat, t.feat_t, (long)pad4(BN), (int)pad4(BN), e.stream);
 }
@@ -3511,11 +3557,13 @@ GraphKey train_graph_key(const ovc_model* m, const ovc_model* grads, const void*
 // log-probabilities.  Launch order: the seed slot and, for sequences under dropout, the mask-row table; the kernels that read the
 // caller's inputs (stage_forward_inputs of the call's pass, then token and feature staging); the body -- captured on
 // the second call of its key when use_graph is set; the loss copy or seq_logp_kernel.  Only the body is ever captured.
-int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& c, const float* features, const int64_t* tokens,
+int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& c, const float* features, const float* boxes,
+                   const int64_t* tokens,
                    const int64_t* targets, const float* grad_logp, void* workspace, size_t workspace_bytes, float* loss_out,
                    float* logp_out, int use_graph, ovc_stream stream) {
     if (!call_ok(m, c) || !grads || !grads_ok(m, grads) || !features || !tokens || !workspace) return OVC_EINVAL;
     if (c.seq() ? !grad_logp : (!targets || !loss_out)) return OVC_EINVAL;
+    if (c.geometric ? !boxes || !ovc_aligned16(boxes) : false) return OVC_EINVAL;      // every other encoder reads no boxes
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
     TrainWs t = carve_train(m, workspace, c);
@@ -3539,7 +3587,7 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
     // the kernels that read the caller's inputs, outside the captured body
     ForwardCall f = c.forward();
     f.tokens = tokens; f.targets = targets; f.row_grad = grad_logp;
-    TRY(stage_train_inputs(e, t, f, features));
+    TRY(stage_train_inputs(e, t, f, features, c.geometric ? boxes : nullptr));
     auto body = [&](Engine& ce) {
         ce.maskrow = t.maskrow;         // nullptr but for sequences under dropout (carve_train)
         return issue_train_body(ce, t, grads, c);
@@ -3572,8 +3620,7 @@ extern "C" size_t ovc_train_workspace_bytes(const ovc_model* m, int B, int N, in
 extern "C" int ovc_forward_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                     const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
                                     float* loss_out, int use_graph, ovc_stream stream) {
-    (void)boxes;       // the plain encoder reads no boxes
-    return run_train_call(m, grads, TrainCall{B, N, 1, T, LossHead::Xent}, features, tokens, targets, nullptr, workspace,
+    return run_train_call(m, grads, TrainCall{B, N, 1, T, LossHead::Xent}, features, boxes, tokens, targets, nullptr, workspace,
                           workspace_bytes, loss_out, nullptr, use_graph, stream);
 }
 
@@ -3585,11 +3632,10 @@ extern "C" int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model*
                                             int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                             size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                             const ovc_dropout* dropout) {
-    (void)boxes;
     TrainCall c{B, N, 1, T, LossHead::Xent};
     DropPlan plan{};
     TRY(bind_dropout(m, dropout, &plan, c));
-    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
                           stream);
 }
 
@@ -3626,13 +3672,12 @@ extern "C" int ovc_forward_backward_smoothed(const ovc_model* m, const ovc_model
                                              int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                              size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                              const ovc_loss* loss, const ovc_dropout* dropout) {
-    (void)boxes;
     TrainCall c{B, N, 1, T, LossHead::SmoothedXent};
     DropPlan plan{};
     if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
     if (!loss || !call_ok(m, c)) return OVC_EINVAL;
     TRY(make_smoothed_loss(m, loss, (long)B * T, &c.smoothed, &c.loss_hash));
-    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
                           stream);
 }
 
@@ -3647,7 +3692,6 @@ extern "C" int ovc_forward_backward_distill(const ovc_model* m, const ovc_model*
                                             int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                             size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                             const ovc_distill* distill, const ovc_dropout* dropout) {
-    (void)boxes;
     // before any launch: the table, the teacher's pointer and alignment, 0 <= weight <= 1 (NaN fails the comparison)
     if (!distill || !distill->teacher_logp || !ovc_aligned16(distill->teacher_logp)) return OVC_EINVAL;
     if (!(distill->weight >= 0.f && distill->weight <= 1.f)) return OVC_EINVAL;
@@ -3658,7 +3702,7 @@ extern "C" int ovc_forward_backward_distill(const ovc_model* m, const ovc_model*
     c.soft.hard = (float)(1.0 - (double)distill->weight); c.soft.soft = distill->weight;
     c.teacher = distill->teacher_logp;
     c.loss_hash = (hash_bytes(&distill->weight, sizeof(float)) | 1) * 0xA24BAED4963EE407ull;
-    return run_train_call(m, grads, c, features, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
                           stream);
 }
 
@@ -3678,8 +3722,7 @@ extern "C" size_t ovc_train_beams_workspace_bytes(const ovc_model* m, int B, int
 extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                      int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
                                      float* logp_out, int use_graph, ovc_stream stream) {
-    (void)boxes;       // the plain encoder reads no boxes
-    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights}, features, ids, nullptr, grad_logp, workspace,
+    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights}, features, boxes, ids, nullptr, grad_logp, workspace,
                           workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
@@ -3704,8 +3747,7 @@ extern "C" size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, in
 extern "C" int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                            int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                            size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream) {
-    (void)boxes;       // the multilevel encoder reads no boxes
-    return run_train_call(m, grads, meshed_call(B, N, 1, T, LossHead::Xent), features, tokens, targets, nullptr, workspace,
+    return run_train_call(m, grads, meshed_call(B, N, 1, T, LossHead::Xent), features, boxes, tokens, targets, nullptr, workspace,
                           workspace_bytes, loss_out, nullptr, use_graph, stream);
 }
 
@@ -3716,8 +3758,48 @@ extern "C" size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int
 extern "C" int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                             int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                             size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
-    (void)boxes;
-    return run_train_call(m, grads, meshed_call(B, N, S, T, LossHead::RowWeights), features, ids, nullptr, grad_logp, workspace,
+    return run_train_call(m, grads, meshed_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
+                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training the object-relation transformer: the opt-in entry points
+// ---------------------------------------------------------------------------------------------
+// ovc_forward_backward / ovc_sequence_backward for the geometric encoder + plain decoder (geometric_train_ok): the same TrainCall
+// with `geometric` set, so the same carve_train, issue_train_body and run_train_call -- which stages the boxes.  The graph key needs
+// nothing new: it hashes the whole ovc_model (enc_kind, d_g, trig and the fc_g pointers included); the boxes' contents are never
+// part of it, they are copied into the workspace before the body.
+namespace {
+TrainCall geometric_call(int B, int N, int S, int T, LossHead head) {
+    TrainCall c{B, N, S, T, head};
+    c.geometric = true;
+    return c;
+}
+}  // namespace
+
+extern "C" size_t ovc_train_geometric_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
+    return train_workspace_bytes(m, geometric_call(B, N, 1, T, LossHead::Xent), dropout != 0);
+}
+
+extern "C" int ovc_forward_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
+                                              int B, int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                              size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                              const ovc_dropout* dropout) {
+    TrainCall c = geometric_call(B, N, 1, T, LossHead::Xent);
+    DropPlan plan{};
+    if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr,
+                          use_graph, stream);
+}
+
+extern "C" size_t ovc_train_geometric_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    return train_workspace_bytes(m, geometric_call(B, N, S, T, LossHead::RowWeights), false);
+}
+
+extern "C" int ovc_sequence_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
+                                               int B, int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                               size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
+    return run_train_call(m, grads, geometric_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
                           workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
@@ -3732,12 +3814,11 @@ extern "C" int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model
                                              int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                              size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream, int k,
                                              const int32_t* slots, const ovc_dropout* dropout) {
-    (void)boxes;
     TrainCall c{B, N, S, T, LossHead::RowWeights};
     c.k = k; c.slots = slots;
     DropPlan plan{};
     TRY(bind_dropout(m, dropout, &plan, c));
-    return run_train_call(m, grads, c, features, ids, nullptr, grad_logp, workspace, workspace_bytes, nullptr, logp_out, use_graph,
+    return run_train_call(m, grads, c, features, boxes, ids, nullptr, grad_logp, workspace, workspace_bytes, nullptr, logp_out, use_graph,
                           stream);
 }
 

@@ -2,6 +2,7 @@
 // row, 16-byte accesses, wave-shuffle reductions).  Reference call sites: include/ovc.h.
 #include <algorithm>
 
+#include "box_relation.h"
 #include "common.h"
 #include "dropout.h"
 
@@ -264,18 +265,11 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const float* __restric
 __global__ void box_relation_kernel(const float* __restrict__ boxes, int n, const float* __restrict__ fc_w,
                                     const float* __restrict__ fc_b, int h, int d_g, int trig, float* __restrict__ w) {
     const int b = blockIdx.x / n, i = blockIdx.x - b * n;
-    const float* bi = boxes + ((size_t)b * n + i) * 4;
-    const float cxi = (bi[0] + bi[2]) * 0.5f, cyi = (bi[1] + bi[3]) * 0.5f;
-    const float wi = (bi[2] - bi[0]) + 1.0f, hi = (bi[3] - bi[1]) + 1.0f;
+    const BoxGeom gi = box_geom(boxes + ((size_t)b * n + i) * 4);
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const float* bj = boxes + ((size_t)b * n + j) * 4;
-        const float cxj = (bj[0] + bj[2]) * 0.5f, cyj = (bj[1] + bj[3]) * 0.5f;
-        const float wj = (bj[2] - bj[0]) + 1.0f, hj = (bj[3] - bj[1]) + 1.0f;
+        const BoxGeom gj = box_geom(boxes + ((size_t)b * n + j) * 4);
         float g[4];
-        g[0] = logf(fmaxf(fabsf((cxi - cxj) / wi), 1e-3f));
-        g[1] = logf(fmaxf(fabsf((cyi - cyj) / hi), 1e-3f));
-        g[2] = logf(wi / wj);
-        g[3] = logf(hi / hj);
+        box_relation_logs(gi, gj, g);     // box_relation.h: the backward recomputes the embedding with the same expressions
         for (int hd = 0; hd < h; ++hd) {
             const float* fw = fc_w + (size_t)hd * d_g;
             float acc = fc_b[hd];
@@ -286,9 +280,8 @@ __global__ void box_relation_kernel(const float* __restrict__ boxes, int n, cons
                 const int nf = d_g / 8;
                 for (int c = 0; c < 4; ++c)
                     for (int q = 0; q < nf; ++q) {
-                        const float freq = 1.0f / powf(1000.0f, (float)q / (float)nf);
-                        const float ang = (100.0f * g[c]) * freq;
-                        acc += fw[c * nf + q] * sinf(ang) + fw[d_g / 2 + c * nf + q] * cosf(ang);
+                        const float ang = box_relation_angle(g[c], q, nf);
+                        acc +=fw[c * nf + q] * sinf(ang) + fw[d_g / 2 + c * nf + q] * cosf(ang);
                     }
             }
             w[(((size_t)b * h + hd) * n + i) * n + j] = fmaxf(acc, 0.f);

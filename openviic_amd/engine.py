@@ -169,7 +169,12 @@ def _grad_slots(model):
     """(parameter, field path in the ``ovc_model`` table) of every parameter ``ovc_forward_backward`` writes a gradient for:
     the plain encoder / decoder's projections, norms and FFNs, the encoder layers' memory slots (``attention.m_k`` / ``m_v``,
     the augmented-memory transformer), the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``, ``mlp2``), the meshed
-    decoder's level gates (``fc_alphas``; ``ovc_forward_backward_meshed``), the word embedding and the vocabulary projection."""
+    decoder's level gates (``fc_alphas``; ``ovc_forward_backward_meshed``), the geometric encoder's ``fc_gs``
+    (``ovc_forward_backward_geometric``), the word embedding and the vocabulary projection.
+
+    The ``h`` ``fc_gs[i].weight`` come consecutively, then the ``h`` ``fc_gs[i].bias``: the arena pads every slot to 4 floats, so it
+    holds the weight gradients as one ``[h][d_g]`` block (``d_g % 4 == 0``) and the bias gradients as ``[h][4]``, which is what
+    ``ovc_bw_box_relation`` writes.  The table's ``fc_g_w`` / ``fc_g_b`` point at the first of each; the others carry no path."""
     from .modules import encoders
     enc, dec = model.encoder, model.decoder
     slots = []
@@ -201,6 +206,9 @@ def _grad_slots(model):
             slots.append((layer.mhatt.attention.m_k, ("enc", i, "att", "m_k")))
             slots.append((layer.mhatt.attention.m_v, ("enc", i, "att", "m_v")))
         ffn(("enc", i, "ffn"), layer.pwff)
+    if isinstance(enc, encoders.GeometricEncoder):
+        slots.extend((fc.weight, ("fc_g_w",) if i == 0 else None) for i, fc in enumerate(enc.fc_gs))
+        slots.extend((fc.bias, ("fc_g_b",) if i == 0 else None) for i, fc in enumerate(enc.fc_gs))
     if isinstance(enc, encoders.CrossAttentionMultiLevelEncoder):
         mha(("cl_att",), enc.self_attn)
         lin(("cl_mlp1",), enc.mlp1)
@@ -957,15 +965,20 @@ class CaptionEngine:
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------
-    def _check_trainable(self, meshed=False):
+    def _check_trainable(self, meshed=False, geometric=False):
         """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'
         self-attention has memory slots, plain decoder) and the CaMo transformer (cross-level encoder, plain decoder) in fp32:
-        anything else is refused before a launch.  ``meshed=True``: the opt-in scope instead (``_check_trainable_meshed``)."""
+        anything else is refused before a launch.  ``meshed=True`` / ``geometric=True``: the opt-in scope instead
+        (``_check_trainable_meshed`` / ``_check_trainable_geometric``); both together are refused."""
         d = self.desc
+        if meshed and geometric:
+            raise native.OvcError("meshed=True and geometric=True name two different models: pass the one this model is")
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
         if meshed:
             return self._check_trainable_meshed()
+        if geometric:
+            return self._check_trainable_geometric()
         if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
             raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
                                   "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
@@ -1017,6 +1030,34 @@ class CaptionEngine:
         if extra:
             raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
 
+    def _check_trainable_geometric(self):
+        """``geometric=True``: the object-relation transformer -- the geometric encoder (plain layers whose attention adds the
+        box-relation bias from ``fc_gs``) in front of the plain decoder (``ovc_forward_backward_geometric``).  Anything else is
+        refused by name before a launch."""
+        d = self.desc
+        if d.enc_kind != native.ENC_GEOMETRIC or d.dec_kind != native.DEC_PLAIN:
+            raise native.OvcError("geometric=True covers the GeometricEncoder in front of the plain Decoder only (this model has {} "
+                                  "/ {}); call without geometric=True".format(type(self.model.encoder).__name__,
+                                                                             type(self.model.decoder).__name__))
+        model = self.model
+        layers = [layer.mhatt for layer in model.encoder.layers]
+        others = [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
+        if any(m.use_aoa for m in layers + others):
+            raise native.OvcError("geometric=True: the training backward does not cover attention-on-attention gates")
+        if any(hasattr(m.attention, "m_k") for m in layers + others) or d.memory:
+            raise native.OvcError("geometric=True: the training backward does not cover attention memory slots")
+        heads = len(model.encoder.fc_gs)
+        if heads > 16 or (d.d_g % 8 != 0 or not 8 <= d.d_g <= 64 if d.trig else d.d_g != 4):
+            raise native.OvcError("geometric=True: the box-relation backward covers at most 16 encoder heads and an embedding of 4 "
+                                  "(plain) or a multiple of 8 up to 64 (trigonometric) values (has {} heads, d_g={}, trig={})".format(
+                                      heads, d.d_g, bool(d.trig)))
+        if not hasattr(model.decoder.word_emb, "components"):
+            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
+        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
+        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
+        if extra:
+            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
+
     def _check_pointers(self):
         """Re-read the pointer table when a parameter's storage moved (``p.data = ...``): in-place updates (an optimizer step)
         keep the storage and are seen by every call as they are."""
@@ -1030,7 +1071,7 @@ class CaptionEngine:
         return [p for p, _ in _grad_slots(self.model)]
 
     def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None,
-                         distill=None, meshed=False):
+                         distill=None, meshed=False, geometric=False):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -1057,7 +1098,14 @@ class CaptionEngine:
         the plain loss and takes the plain path.  Refused together with ``loss``.
 
         ``meshed=True``: the meshed-memory transformer (``ovc_forward_backward_meshed``; ``_check_trainable_meshed`` states the
-        scope).  Refused together with ``dropout``, ``loss`` and ``distill``."""
+        scope).  Refused together with ``dropout``, ``loss`` and ``distill``.
+
+        ``geometric=True``: the object-relation transformer (``ovc_forward_backward_geometric``; ``_check_trainable_geometric``
+        states the scope).  ``boxes`` are required; they are staged before the body, so a replayed graph reads this call's.
+        ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``."""
+        if geometric and (loss is not None or distill is not None):
+            raise native.OvcError("forward_backward(geometric=True): the label-smoothed loss and soft targets are out of scope for "
+                                  "the object-relation transformer")
         if meshed and (dropout is not None or loss is not None or distill is not None):
             raise native.OvcError("forward_backward(meshed=True): dropout, the label-smoothed loss and soft targets are out of "
                                   "scope for the meshed-memory transformer")
@@ -1079,12 +1127,12 @@ class CaptionEngine:
             loss = checked_label_smoothing(loss[0], loss[1], "forward_backward", self.desc.vocab)
             if loss == (0.0, "tokens"):
                 loss = None
-        self._check_trainable(meshed)
+        self._check_trainable(meshed, geometric)
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed)
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed, geometric=geometric)
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -1105,13 +1153,18 @@ class CaptionEngine:
     _MESHED_FORMS = {False: ("ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed"),
                      True: ("ovc_train_meshed_beams_workspace_bytes", "ovc_sequence_backward_meshed")}
 
-    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False):
+    # sequence -> the opt-in forms of the object-relation transformer; the loss form takes the dropout table or NULL
+    _GEOMETRIC_FORMS = {False: ("ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric"),
+                        True: ("ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric")}
+
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False, geometric=False):
         """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
         T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
         on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
         soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``meshed``: the
-        meshed-memory transformer's form (no loss, dropout or distill with it: the callers refuse them)."""
+        meshed-memory transformer's form (no loss, dropout or distill with it: the callers refuse them).  ``geometric``: the
+        object-relation transformer's form (no loss or distill, and no dropout with ``sequence``: the callers refuse them)."""
         sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
         if meshed:
             sizer, entry = self._MESHED_FORMS[bool(sequence)]
@@ -1125,12 +1178,16 @@ class CaptionEngine:
         if distill is not None:
             size_tail = (1 if drop else 0,)
             tail = (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), drop[0] if drop else None)
+        if geometric:
+            sizer, entry = self._GEOMETRIC_FORMS[bool(sequence)]
+            if not sequence:
+                size_tail, tail = (1 if drop else 0,), (drop[0] if drop else None,)
         self._check_pointers()
         ws, need = self._sized_workspace(
             "sequence" if sequence else "train", sizer, (*shape, *size_tail),
             "unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                sizer if meshed else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
+                sizer if meshed or geometric else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
         return entry, shape, ws, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
@@ -1158,7 +1215,8 @@ class CaptionEngine:
         grads, off = [], 0
         for (p, path), size in zip(slots, sizes):
             view = arena[off:off + p.numel()].view(p.shape)
-            _set_field(table, path, view.data_ptr())
+            if path is not None:        # the geometric encoder's fc_gs: one table entry for the block (_grad_slots)
+                _set_field(table, path, view.data_ptr())
             grads.append(view)
             off += size
         return arena, table, grads
@@ -1173,7 +1231,7 @@ class CaptionEngine:
         return self._buffers[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
-                          beam_size=None, arena=None, meshed=False):
+                          beam_size=None, arena=None, meshed=False, geometric=False):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -1189,10 +1247,15 @@ class CaptionEngine:
         ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer, as ``forward_backward`` takes it
         (``BaseTransformer.scst_step``); the returned ``arena`` and ``grads`` are then that arena's.
 
-        ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``."""
+        ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``.
+        ``geometric=True``: the object-relation transformer (``ovc_sequence_backward_geometric``), ``boxes`` required; refused
+        together with ``dropout``."""
         if meshed and dropout is not None:
             raise native.OvcError("sequence_backward(meshed=True): dropout is out of scope for the meshed-memory transformer")
-        self._check_trainable(meshed)
+        if geometric and dropout is not None:
+            raise native.OvcError("sequence_backward(geometric=True): the sequence form under dropout is out of scope for the "
+                                  "object-relation transformer")
+        self._check_trainable(meshed, geometric)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         if table_drop is not None:
             if (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or
@@ -1214,7 +1277,7 @@ class CaptionEngine:
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
         form = self._train_form(True, None, table_drop, (B, N, S, T),
-                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed)
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed, geometric=geometric)
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
         arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,

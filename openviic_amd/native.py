@@ -226,6 +226,17 @@ SIGNATURES = {
     "ovc_sequence_backward_meshed": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                              c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "ovc_debug_meshed_mix_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_float, c_void_p, c_void_p, c_void_p]),
+    "ovc_train_geometric_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_forward_backward_geometric": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                               c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Dropout)]),
+    "ovc_train_geometric_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward_geometric": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_debug_box_relation_backward_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ovc_debug_box_relation_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                                c_void_p, c_void_p, c_void_p]),
+    "ovc_debug_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ovc_dropout_mask_rows": (c_int, [c_void_p, c_int, c_void_p, c_long, c_long, c_float, c_void_p, c_void_p]),
     "ovc_beam_search_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
     "ovc_beam_search_dropout": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
@@ -360,7 +371,10 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_debug_add_norm", "ovc_debug_add_norm_form", "ovc_debug_dropout_rows", "ovc_debug_meshed_mix",
                  "ovc_debug_leaky_residual", "ovc_debug_sigmoid_gate",
                  "ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed", "ovc_train_meshed_beams_workspace_bytes",
-                 "ovc_sequence_backward_meshed", "ovc_debug_meshed_mix_backward")
+                 "ovc_sequence_backward_meshed", "ovc_debug_meshed_mix_backward",
+                 "ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric",
+                 "ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric",
+                 "ovc_debug_box_relation_backward_floats", "ovc_debug_box_relation_backward", "ovc_debug_attention_backward")
 
 _lib = None
 

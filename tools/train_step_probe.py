@@ -5,6 +5,8 @@ configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, 
     python tools/train_step_probe.py --optimizer torch engine xe_step [--rounds 2] ...     # the whole iteration, optimizer included
 
 --variant augmented_memory_transformer: the plain encoder with 40 memory slots per layer (the memory-slot attention backward).
+--variant object_relation_transformer (next to another variant): the geometric encoder -- the box-relation bias in the encoder's
+attention backward and ovc_bw_box_relation -- through xe_loss(geometric=True).
 --variant meshed_memory_transformer: the multilevel encoder with 40 memory slots per layer and the meshed decoder, through
 ``model.xe_loss(items, meshed=True)`` (``ovc_forward_backward_meshed``; no dropout form, --optimizer none only).
 Several --variant values alternate in ONE process -- per batch size, ``--rounds`` rounds of ``--steps`` steps of each variant in
@@ -57,7 +59,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from openviic_amd.builders import build_model                                        # noqa: E402
 from openviic_amd.config import model_config                                         # noqa: E402
 from openviic_amd.instance import InstanceList                                       # noqa: E402
-from openviic_amd.utils.synthetic import SyntheticVocab, synthetic_features, synthetic_state_dict   # noqa: E402
+from openviic_amd.utils.synthetic import SyntheticVocab, synthetic_boxes, synthetic_features, synthetic_state_dict   # noqa: E402
 
 PEAK_F32_MATRIX = 157.3e12
 COPY_RATE = 6.29e12           # bytes/s of a float4 copy on one MI355X (measured; HBM3E nominal 8.0e12)
@@ -213,6 +215,7 @@ def distill_probe(args, model, teacher, items, B, T, N, V):
 
 
 MESHED = "meshed_memory_transformer"
+GEOMETRIC = "object_relation_transformer"
 
 
 def variant_dims(variant):
@@ -221,13 +224,18 @@ def variant_dims(variant):
 
 
 def loss_kw(variant, dropout):
-    """The keywords of ``xe_loss`` for a variant: the meshed-memory transformer is opt-in and has no dropout form."""
+    """The keywords of ``xe_loss`` for a variant: the meshed-memory transformer is opt-in and has no dropout form, the
+    object-relation transformer is opt-in too."""
+    if variant == GEOMETRIC:
+        return dict(geometric=True, dropout=dropout)
     return dict(meshed=True) if variant == MESHED else dict(dropout=dropout)
 
 
 def train_sizer(lib, variant, dropout):
     if variant == MESHED:
         return lib.ovc_train_meshed_workspace_bytes
+    if variant == GEOMETRIC:
+        return lambda d, B, N, T: lib.ovc_train_geometric_workspace_bytes(d, B, N, T, 1 if dropout else 0)
     return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
 
 
@@ -245,6 +253,7 @@ def alternate_variants(args, vocab, V, T, N, D):
         tokens[:, 0] = 1
         items = InstanceList()
         items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
+        items.region_boxes = synthetic_boxes(B, N, seed=0).cuda()         # read by the object-relation transformer alone
         items.caption_tokens = tokens.cuda()
         items.shifted_right_caption_tokens = torch.cat([tokens[:, 1:], torch.zeros_like(tokens[:, :1])], 1).cuda()
 
@@ -279,10 +288,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
     ap.add_argument("--variant", nargs="+", default=["standard_transformer"],
-                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED],
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED, GEOMETRIC],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
                          "augmented_memory_transformer: 40 memory slots in the encoder; meshed_memory_transformer: the multilevel "
-                         "encoder and the meshed decoder (meshed=True); several values alternate in one process")
+                         "encoder and the meshed decoder (meshed=True); object_relation_transformer: the geometric encoder "
+                         "(geometric=True; next to another --variant only); several values alternate in one process")
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
                     help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
@@ -308,6 +318,8 @@ def main():
     if MESHED in args.variant and (args.dropout or args.optimizer != ["none"] or args.label_smoothing is not None or
                                    args.distill is not None):
         ap.error("meshed_memory_transformer goes with --optimizer none, without --dropout, --label-smoothing or --distill")
+    if GEOMETRIC in args.variant and len(args.variant) < 2:
+        ap.error("object_relation_transformer runs next to another --variant (its step is reported against that one)")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D = 10201, 20, 50, 2048
     vocab = SyntheticVocab(V, T)

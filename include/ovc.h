@@ -555,6 +555,35 @@ int ovc_debug_attention_backward(const float* q, const float* k, const float* v,
                                  const float* geometry, int B, int nq, int nk, int h, int dk, float* P, float* dS, float* dq,
                                  float* dk_out, float* dv_out, ovc_stream stream);
 
+/* Training the attention-on-attention transformer: ovc_forward_backward and ovc_sequence_backward for the plain encoder and plain
+ * decoder whose MultiHeadAttention blocks carry AoA gates (attentions.py:296-318): behind the AddNorm u = LN(q + att(q, k, v)),
+ * i = aoa_i [q ; u], a = aoa_g [q ; u], out = i * sigmoid(a), and the next block reads out.  Opt-in: the entry points above and their
+ * sizers keep refusing a model with gates (OVC_EINVAL / 0), these take it and nothing else.  The arguments, the results, what is
+ * read outside the captured body, the graph rule and the determinism are those of ovc_forward_backward(_dropout) and
+ * ovc_sequence_backward; boxes are not read.  grads additionally receives aoa_i / aoa_g (w [d][2d] and b) of every gated attention.
+ * dropout: NULL, or the table of ovc_forward_backward_dropout (the sites are the plain transformer's: the gate sits behind the
+ * AddNorm and has none).  The rule -- anything else is OVC_EINVAL before any launch, and the sizers answer 0:
+ *   precision 0 (fp32); enc_kind == OVC_ENC_PLAIN, dec_kind == OVC_DEC_PLAIN, n_levels == 1, memory == 0, no m_k / m_v anywhere;
+ *   every attention has BOTH gates or NEITHER (any subset of sites may be gated), and at least one is gated;
+ *   grads has w (and b where the model has one) for every gate the model has;
+ *   the fused vocabulary tail and the 32-bit descriptor limits of ovc_forward_backward, also over the gates' [rows][2d] operands.
+ * There is no sequence form under dropout.
+ * ovc_train_aoa_workspace_bytes (dropout != 0: for a call with a table) / ovc_train_aoa_beams_workspace_bytes: bytes of workspace,
+ * 0 when unsupported.  A gated site adds 3 * rows * d floats of tape (u, i, a; rows = B*N in the encoder, B*S*T in the decoder). */
+size_t ovc_train_aoa_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout);
+int ovc_forward_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                             const int64_t* tokens, const int64_t* targets, int T, void* workspace, size_t workspace_bytes,
+                             float* loss_out, int use_graph, ovc_stream stream, const ovc_dropout* dropout);
+size_t ovc_train_aoa_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
+                              int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
+                              float* logp_out, int use_graph, ovc_stream stream);
+/* Test hook (tests/test_aoa_train_gpu.py).  ovc_debug_aoa_gate_backward: the gate's backward as the AoA training calls launch it --
+ * dout, i, a: n = rows * d floats each; dcat [rows][2d] receives d(i) = dout sigmoid(a) at columns [0, d) and d(a) = (dout i)
+ * sigmoid'(a) at columns [d, 2d) of each row.  Finite for every finite a.  OVC_EINVAL, nothing written: n <= 0, n % 4 != 0,
+ * d % 4 != 0, n % d != 0, a NULL pointer or one not aligned to 16 bytes. */
+int ovc_debug_aoa_gate_backward(const float* dout, const float* i, const float* a, long n, int d, float* dcat, ovc_stream stream);
+
 /* SCST under dropout (the reference's train_scst searches in train() mode, vi_trainer.py:121-158): the beam search with the
  * dropout sites above applied, and the backward of its log-probabilities under the SAME masks.  The plain standard transformer,
  * with or without encoder memory slots, precision 0 (what ovc_forward_backward_dropout covers); site ids and the counter mapping are unchanged.

@@ -74,13 +74,19 @@ _MESHED = ("meshed",)       # what ``_xe_call`` returns as the loss of a ``meshe
 _GEOMETRIC = ("geometric",)  # ... of a ``geometric=True`` call: the NLL on the object-relation transformer's entry point
 
 
+_AOA = ("aoa",)              # ... of an ``aoa=True`` call: the NLL on the attention-on-attention transformer's entry point
+
+
 def _loss_head(head):
     """``forward_backward``'s keyword for what ``_xe_call`` returned as the call's loss: the NLL, the smoothed loss or soft targets
-    -- or the NLL of the meshed-memory transformer (``meshed=True``) or of the object-relation transformer (``geometric=True``)."""
+    -- or the NLL of the meshed-memory transformer (``meshed=True``), of the object-relation transformer (``geometric=True``) or
+    of the attention-on-attention transformer (``aoa=True``)."""
     if head is _MESHED:
         return {"meshed": True}
     if head is _GEOMETRIC:
         return {"geometric": True}
+    if head is _AOA:
+        return {"aoa": True}
     return {"distill": tuple(head)} if isinstance(head, _distill.SoftTargets) else {"loss": head}
 
 
@@ -102,6 +108,16 @@ def _refuse_with_geometric(what, **given):
                 "{}(geometric=True, {}=...): {} is out of scope for the object-relation transformer's training{}".format(
                     what, name, name, " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
                     if name == "dropout" else " -- a model is one or the other" if name == "meshed" else ""))
+
+
+def _refuse_with_aoa(what, **given):
+    """``aoa=True`` together with what the attention-on-attention transformer's training does not cover: refused by name."""
+    for name, value in given.items():
+        if value:
+            raise engine.native.OvcError(
+                "{}(aoa=True, {}=...): {} is out of scope for the attention-on-attention transformer's training{}".format(
+                    what, name, name, " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
+                    if name == "dropout" else " -- a model is one or the other" if name in ("meshed", "geometric") else ""))
 
 
 def _require_boxes(what, input_features):
@@ -269,7 +285,7 @@ class BaseTransformer(Module):
             return eng.attention_maps(features, boxes, ids=ids, reduce=reduce, return_log_probs=return_log_probs)
 
     def xe_loss(self, input_features, dropout=False, generator=None, label_smoothing=None, reduction=None, teacher_log_probs=None,
-                distill_weight=None, meshed=False, geometric=False):
+                distill_weight=None, meshed=False, geometric=False, aoa=False):
         """The reference's training loss on the HIP engine: ``NLLLoss(ignore_index=pad)`` of ``self(items)`` against
         ``shifted_right_caption_tokens`` (``vi_trainer.py:100-119``), a 0-dim device tensor whose ``backward()`` accumulates
         every parameter's gradient into ``p.grad`` as usual (``ovc_forward_backward``).  The plain standard transformer, the
@@ -317,17 +333,29 @@ class BaseTransformer(Module):
         boxes get none.  ``dropout=True`` works as for the standard transformer (the encoder's sites are the plain encoder's).
         Opt-in: without the keyword such a model is refused as before.  Refused by name before any launch and any draw:
         ``geometric=True`` on any other model, together with ``meshed=True``, ``label_smoothing`` / ``reduction`` or
-        ``teacher_log_probs`` / ``distill_weight``, a batch without ``region_boxes``, and AoA gates or memory slots anywhere."""
+        ``teacher_log_probs`` / ``distill_weight``, a batch without ``region_boxes``, and AoA gates or memory slots anywhere.
+
+        ``aoa=True``: the attention-on-attention transformer -- the plain encoder and decoder whose ``MultiHeadAttention`` blocks
+        have ``USE_AOA`` set, all of them or any subset -- on ``ovc_forward_backward_aoa``; every ``informative_attention`` and
+        ``gated_attention`` gets its gradient like every other parameter.  ``dropout=True`` works as for the standard transformer
+        (the gate sits behind the AddNorm and has no dropout of its own).  Opt-in: without the keyword such a model is refused as
+        before.  Refused by name before any launch and any draw: ``aoa=True`` on a model without gates, with another encoder or
+        decoder or with memory slots, together with ``meshed=True``, ``geometric=True``, ``label_smoothing`` / ``reduction`` or
+        ``teacher_log_probs`` / ``distill_weight``, and (the refusal above) a ``train()``-mode model with a live dropout."""
         eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
                                                     teacher_log_probs=teacher_log_probs, distill_weight=distill_weight, meshed=meshed,
-                                                    geometric=geometric)
+                                                    geometric=geometric, aoa=aoa)
         return _XeLoss.apply(eng, drop, smoothed, *inputs, *eng.gradient_parameters())
 
     def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None, teacher_log_probs=None,
-                 distill_weight=None, meshed=False, geometric=False):
+                 distill_weight=None, meshed=False, geometric=False, aoa=False):
         """The preamble of ``xe_loss`` / ``xe_step``: their refusals in their order -- the loss, the dropout rules, a model outside
         the backward's scope, ``xe_step``'s optimizer set -- and only then the draw of the step's seed.  Returns ``(engine,
         dropout (probs, seed) or None, smoothed loss / soft targets or None, (features, boxes, caption tokens, targets))``."""
+        if aoa:
+            _refuse_with_aoa(what, meshed=meshed, geometric=geometric, label_smoothing=label_smoothing is not None,
+                             reduction=reduction is not None, teacher_log_probs=teacher_log_probs is not None,
+                             distill_weight=distill_weight is not None)
         if geometric:
             _refuse_with_geometric(what, meshed=meshed, label_smoothing=label_smoothing is not None, reduction=reduction is not None,
                                    teacher_log_probs=teacher_log_probs is not None, distill_weight=distill_weight is not None)
@@ -345,7 +373,9 @@ class BaseTransformer(Module):
         smoothed = soft or engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
         probs = self._xe_dropout_probs(dropout, what)
         eng = self._fused_engine()
-        eng._check_trainable(meshed, geometric)
+        eng._check_trainable(meshed, geometric, aoa)
+        if aoa:
+            smoothed = _AOA
         if meshed:
             smoothed = _MESHED
         if geometric:
@@ -376,7 +406,7 @@ class BaseTransformer(Module):
         return {}
 
     def xe_step(self, input_features, optimizer, dropout=False, generator=None, max_norm=None, label_smoothing=None,
-                reduction=None, teacher_log_probs=None, distill_weight=None, meshed=False, geometric=False):
+                reduction=None, teacher_log_probs=None, distill_weight=None, meshed=False, geometric=False, aoa=False):
         """One cross-entropy training iteration in one call, with no autograd in between: ``ovc_forward_backward`` followed by
         ``ovc_adam_step`` reading the engine's gradient arena in place.  Returns the loss as a detached 0-dim device tensor.  It
         stands for ::
@@ -400,7 +430,8 @@ class BaseTransformer(Module):
         the same refusals before any launch and any draw.  ``teacher_log_probs`` / ``distill_weight``: as ``xe_loss`` takes them
         -- the soft-target loss in the four lines and here.  ``meshed``: as ``xe_loss`` takes it -- the meshed-memory transformer,
         ``xe_loss(items, meshed=True)`` in the four lines.  ``geometric``: likewise the object-relation transformer,
-        ``xe_loss(items, dropout=..., geometric=True)`` in the four lines.
+        ``xe_loss(items, dropout=..., geometric=True)`` in the four lines.  ``aoa``: likewise the attention-on-attention
+        transformer, ``xe_loss(items, dropout=..., aoa=True)`` in the four lines.
 
         ``p.grad`` is neither read nor written, and autograd is not involved: gradient hooks do NOT fire --
         ``register_hook`` / ``register_post_accumulate_grad_hook`` callbacks, and with them DistributedDataParallel's gradient
@@ -410,14 +441,14 @@ class BaseTransformer(Module):
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
         eng, drop, smoothed, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
                                                     optimizer, teacher_log_probs=teacher_log_probs, distill_weight=distill_weight,
-                                                    meshed=meshed, geometric=geometric)
+                                                    meshed=meshed, geometric=geometric, aoa=aoa)
         loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed))
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
     def scst_step(self, input_features, optimizer, reward, beam_size, rows=None, dropout=False, generator=None, early_exit=None,
                   max_norm=None, sample=False, temperature=1.0, top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0,
-                  banned_words=None, meshed=False, geometric=False):
+                  banned_words=None, meshed=False, geometric=False, aoa=False):
         """One self-critical training iteration (the reference's ``train_scst``, ``vi_trainer.py:121-158``) in one call, with no
         autograd in between: the fused search with ``out_size = beam_size``, the reward, ``ovc_scst_advantage`` (baseline,
         advantage, loss and its gradient), ``ovc_sequence_backward`` into the engine's step arena and ``ovc_adam_step`` reading
@@ -468,7 +499,14 @@ class BaseTransformer(Module):
         ``geometric=True``: the object-relation transformer, as ``xe_loss`` takes it (``ovc_sequence_backward_geometric``); the
         first of the lines above is then ``model.beam_search(items, B, k, out_size=k, geometric=True)``.  Refused by name before
         any launch or draw: any other model, and ``geometric=True`` together with ``meshed=True``, ``dropout=True`` or
+        ``sample=True``.
+
+        ``aoa=True``: the attention-on-attention transformer, as ``xe_loss`` takes it (``ovc_sequence_backward_aoa``); the first
+        of the lines above is then ``model.beam_search(items, B, k, out_size=k, aoa=True)``.  Refused by name before any launch
+        or draw: any other model, and ``aoa=True`` together with ``meshed=True``, ``geometric=True``, ``dropout=True`` or
         ``sample=True``."""
+        if aoa:
+            _refuse_with_aoa("scst_step", meshed=meshed, geometric=geometric, dropout=dropout, sample=sample)
         if geometric:
             _refuse_with_geometric("scst_step", meshed=meshed, dropout=dropout, sample=sample)
         if meshed:
@@ -500,7 +538,7 @@ class BaseTransformer(Module):
             raise engine.native.OvcError("scst_step: 1 <= beam_size <= {} expected, got {}".format(engine.native.OVC_MAX_BEAM, k))
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
-        eng._check_trainable(meshed, geometric)
+        eng._check_trainable(meshed, geometric, aoa)
         if geometric:
             _require_boxes("scst_step", input_features)
         checked = eng.check_sample(k, temperature, top_k, top_p) if sample else None
@@ -535,6 +573,8 @@ class BaseTransformer(Module):
             recompute = dict(recompute, meshed=True)
         if geometric:
             recompute = dict(recompute, geometric=True)
+        if aoa:
+            recompute = dict(recompute, aoa=True)
         _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena(), **recompute)
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
@@ -565,7 +605,7 @@ class BaseTransformer(Module):
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
                     fused=True, dropout=False, generator=None, no_repeat_ngram_size=0, min_length=0, banned_words=None, prefix=None,
-                    meshed=False, geometric=False, **kwargs):
+                    meshed=False, geometric=False, aoa=False, **kwargs):
         """Beam-search decode (``base_transformer.py:45-53`` + ``beam_search.py:85-118``).
 
         ``fused=True`` (default) runs the whole search in the HIP engine.  ``fused=False`` runs the
@@ -614,8 +654,18 @@ class BaseTransformer(Module):
 
         ``geometric=True`` (fused only): the object-relation transformer, likewise (``ovc_sequence_backward_geometric``), with the
         same refusals and ``meshed=True`` among them.
+
+        ``aoa=True`` (fused only): the attention-on-attention transformer, likewise (``ovc_sequence_backward_aoa``), with the same
+        refusals and ``meshed=True`` / ``geometric=True`` among them.
         """
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
+        if aoa:
+            _refuse_with_aoa("beam_search", meshed=meshed, geometric=geometric, dropout=dropout)
+            if not fused:
+                raise engine.native.OvcError("beam_search(aoa=True) needs fused=True: the host loop has no backward")
+            if self.training and torch.is_grad_enabled():
+                self._xe_dropout_probs(False, "beam_search(aoa=True)")
+            self._fused_engine()._check_trainable(False, False, True)
         if geometric:
             _refuse_with_geometric("beam_search", meshed=meshed, dropout=dropout)
             if not fused:
@@ -669,6 +719,8 @@ class BaseTransformer(Module):
                 recompute = dict(recompute, meshed=True)
             if geometric:
                 recompute = dict(recompute, geometric=True)
+            if aoa:
+                recompute = dict(recompute, aoa=True)
             logp = self._scst_log_probs(input_features, ids, logp, recompute)
             if out_size == 1:
                 ids, logp = ids.squeeze(1), logp.squeeze(1)

@@ -134,6 +134,13 @@ int ovc_bw_meshed_mix(const float* dmixed, const float* alpha, const float* enc,
 // starts from block 0), out may alias acc
 int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out, hipStream_t s);
 
+// The attention-on-attention gate (engine.hip bw_aoa_gate).
+// Backward of out = i * sigmoid(a) (ovc_sigmoid_gate) over n = rows * d floats: dcat [rows][2d] receives d(i) = dout sigmoid(a) at
+// columns [0, d) and d(a) = (dout i) sigmoid'(a) at columns [d, 2d) of each row, so that d([q ; u]) is one K = 2d product against the
+// staged [W_i ; W_g].  Finite for every finite a.  OVC_EINVAL, nothing written: n % 4 != 0, d % 4 != 0, n % d != 0, a null pointer or
+// one not aligned to 16 bytes.
+int ovc_bw_aoa_gate(const float* dout, const float* info, const float* gate, long n, int d, float* dcat, hipStream_t s);
+
 // The geometric (object-relation) encoder's bias (engine.hip issue_train_body).
 // acc[i] = acc[i] + src[i] over n floats: the layers' dS summed into d(bias) in the caller's order.  16-byte accesses when n % 4 == 0
 // and both pointers are aligned to 16 bytes, scalar ones otherwise -- the same bits either way (element-wise).

@@ -999,6 +999,45 @@ int ovc_bw_sum_levels(const float* acc, const float* src, int levels, long strid
     return OVC_OK;
 }
 
+// ---- the attention-on-attention gate (engine.hip, bw_aoa_gate) --------------------------------------------
+namespace {
+
+// out = i * sigmoid(a) (rowops.hip, sigmoid_gate): per element d(i) = d(out) sigmoid(a) and d(a) = (d(out) i) sigmoid'(a), with
+// t = exp(-|a|) as in bw_meshed_mix_kernel -- finite for every finite a, and sigmoid'(a) = t / (1 + t)^2 underflows to 0 for large
+// |a| without passing through 1 - sigmoid.  One lane per four elements of a row (d % 4 == 0, so four elements never straddle two
+// rows): three 16-byte loads, and the two 16-byte stores land d(i) at columns [0, d) and d(a) at columns [d, 2d) of the row of the
+// [rows][2d] block, the left operand of the one K = 2d product against the staged [W_i ; W_g].
+__global__ __launch_bounds__(256) void bw_aoa_gate_kernel(const float* __restrict__ dout, const float* __restrict__ info,
+                                                          const float* __restrict__ gate, long n4, int d4,
+                                                          float* __restrict__ dcat) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 g = reinterpret_cast<const f32x4*>(dout)[i];
+        const f32x4 iv = reinterpret_cast<const f32x4*>(info)[i];
+        const f32x4 av = reinterpret_cast<const f32x4*>(gate)[i];
+        f32x4 di, da;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float t = expf(-fabsf(av[j])), r = 1.f / (1.f + t);
+            const float sig = av[j] >= 0.f ? r : t * r;
+            di[j] = g[j] * sig;
+            da[j] = (g[j] * iv[j]) * ((t * r) * r);
+        }
+        const long row = i / d4, at = row * 2 * d4 + (i - row * d4);
+        reinterpret_cast<f32x4*>(dcat)[at] = di;
+        reinterpret_cast<f32x4*>(dcat)[at + d4] = da;
+    }
+}
+
+}  // namespace
+
+int ovc_bw_aoa_gate(const float* dout, const float* info, const float* gate, long n, int d, float* dcat, hipStream_t s) {
+    if (!dout || !info || !gate || !dcat || n <= 0 || (n & 3) || d <= 0 || (d & 3) || n % d != 0) return OVC_EINVAL;
+    if (!ovc_aligned16(dout) || !ovc_aligned16(info) || !ovc_aligned16(gate) || !ovc_aligned16(dcat)) return OVC_EINVAL;   // float4 accesses
+    hipLaunchKernelGGL(bw_aoa_gate_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, s, dout, info, gate, n / 4, d / 4, dcat);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
 // ---- the geometric (object-relation) encoder's bias (engine.hip, issue_train_body) ------------------------
 namespace {
 
@@ -1168,6 +1207,12 @@ extern "C" int ovc_debug_attention_backward(const float* q, const float* k, cons
     a.P = P; a.dS = dS; a.dq = dq; a.lddq = hk; a.dk_out = dk_out; a.dv_out = dv_out; a.lddkv = hk;
     a.geometry = geometry;
     return ovc_bw_attention(a, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_aoa_gate_backward(const float* dout, const float* info, const float* gate, long n, int d, float* dcat,
+                                           ovc_stream stream) {
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_aoa_gate(dout, info, gate, n, d, dcat, ovc_hip_stream(stream));
 }
 
 extern "C" int ovc_debug_meshed_mix_backward(const float* dmixed, const float* alpha, const float* enc, int levels, long n, float divisor,

@@ -100,12 +100,17 @@ struct Bump {
 // Training (ovc_forward_backward): per layer, what the backward reads from the forward -- the projected q / k / v, the attention
 // outputs, the pre-norm sums (the LayerNorm statistics are recomputed from them), the norm outputs, the ReLU outputs and the
 // layer outputs.  The inference forward reuses one set of buffers across layers instead (Workspace::tape == nullptr).
-struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out; };
+// A gated attention (AoA, Engine::aoa) reads the AddNorm output u and writes the block's output (x1, x2) from the gate's two
+// products info / gate.  Only a training call that differentiates the gates (TrainCall::aoa) keeps the four apart per site; every
+// other tape and the scratch set alias u to the block's output and share the workspace's info / gate, as the gate always ran.
+struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out, *u, *info, *gate; };
 struct DecTape {
     float *q, *k, *v, *att, *ys, *x1, *qc, *attc, *yc, *x2, *ff, *yf, *out;
     // the meshed decoder's gate block (run_decoder_layer): the stacked pre-norm sums, their norms e_l and the gate pre-activations
     // a_l, [levels][rows][d] each, and the gated sum [rows][d]; attc is then [levels][rows][h d_v]
     float *ymesh, *enc_att, *alpha, *mixed;
+    // the gates' operands (see EncTape): the self block's u / info / gate (its output is x1), the cross block's (its output is x2)
+    float *us, *infos, *gates, *uc, *infoc, *gatec;
 };
 // The cross-level (CaMo) tail (run_cross_level_tail): per cross call c (0: q = o2, k = v = o1; 1: q = o3, k = v = o2') its k, v, the
 // attention output att [2][B*N][h_enc*dv_enc] and fc_o's output ya [2][B*N][d] (the pre-norm sum is ya + q, formed again by the
@@ -365,10 +370,11 @@ Workspace carve_forward(const ovc_model* m, void* base, const ForwardCall& c) {
 // Without a tape (Workspace::tape == nullptr) every layer writes the ONE shared set of buffers: that set in the tape's shape, so
 // that a layer is issued against a tape slot either way.  The encoder's `out` is chosen per layer (run_encoder_layers); the
 // decoder's keys / values are the forward's w.kc / w.vc or the step's cache rows.
-EncTape scratch_enc(const Workspace& w) { return EncTape{w.eq, w.ek, w.ev, w.eatt, w.ey, w.xe[1], w.eff, w.ey, nullptr}; }
+EncTape scratch_enc(const Workspace& w) { return EncTape{w.eq, w.ek, w.ev, w.eatt, w.ey, w.xe[1], w.eff, w.ey, nullptr, w.xe[1], w.einfo, w.egate}; }
 ClTape scratch_cl(const Workspace& w) { return ClTape{{w.ek, w.ek}, {w.ev, w.ev}, w.eatt, w.ey, w.xe[0], w.einfo, w.ey}; }
 DecTape scratch_dec(const Workspace& w, float* k, float* v) {
-    return DecTape{w.q, k, v, w.att, w.y, w.x1, w.q, w.att, w.y, w.x2, w.ff, w.y, w.x, w.ymesh, w.enc_att, w.alpha, w.mixed};
+    return DecTape{w.q, k, v, w.att, w.y, w.x1, w.q, w.att, w.y, w.x2, w.ff, w.y, w.x, w.ymesh, w.enc_att, w.alpha, w.mixed,
+                   w.x1, w.info, w.gate, w.x2, w.info, w.gate};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -784,12 +790,13 @@ struct Engine {
         return OVC_OK;
     }
 
-    // AoA gate (attentions.py:311-315): out = W_i [q; x] * sigmoid(W_g [q; x]), one two-segment GEMM.
-    int aoa(const ovc_mha& w, const float* queries, float* x, float* info, float* gate, int M) {
+    // AoA gate (attentions.py:311-315): out = W_i [q; u] * sigmoid(W_g [q; u]), one two-segment GEMM.  out may be u (every call
+    // but a training call that keeps u for the gate's backward): the gate kernel is elementwise.
+    int aoa(const ovc_mha& w, const float* queries, const float* u, float* out, float* info, float* gate, int M) {
         if (!w.aoa_i.w) return OVC_OK;
         const int d = m->d_model;
         GemmArgs a{};
-        a.A1 = queries; a.lda1 = d; a.K1 = d; a.A2 = x; a.lda2 = d; a.K2 = d;
+        a.A1 = queries; a.lda1 = d; a.K1 = d; a.A2 = u; a.lda2 = d; a.K2 = d;
         a.M = M; a.seg_n = d; a.nseg = 2; a.ldc = d;
         a.seg[0] = seg(w.aoa_i, info);
         a.seg[1] = seg(w.aoa_g, gate);
@@ -802,7 +809,7 @@ struct Engine {
             TRY(gemm(a));
         }
         if (dry) return OVC_OK;
-        return ovc_sigmoid_gate_gated(info, gate, x, (long)M * d, stream, this->gate);
+        return ovc_sigmoid_gate_gated(info, gate, out, (long)M * d, stream, this->gate);
     }
 
     // site_inner / site_out: the dropout sites on relu(fc1) and on fc2 (-1: none)
@@ -945,8 +952,8 @@ int run_encoder_layers(Engine& e, Workspace& w, int B, int N) {
                           m->enc_kind == OVC_ENC_GEOMETRIC ? w.geometry : nullptr, at.m_k, at.m_v, mem,
                           sqrtf((float)edk), sqrtf((float)(mem > 0 ? mem : 1)), b.att, s));
         TRY(e.linear(b.att, hv, at.o, x, b.ya, BN, d, 0, enc_site(l, 0)));
-        RUN(ovc_layer_norm(b.ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, b.x1, BN, d, s));
-        TRY(e.aoa(at, x, b.x1, w.einfo, w.egate, BN));
+        RUN(ovc_layer_norm(b.ya, nullptr, at.ln.g, at.ln.b, nullptr, 0, nullptr, m->ln_eps, b.u, BN, d, s));
+        TRY(e.aoa(at, x, b.u, b.x1, b.info, b.gate, BN));
         // layer output: straight into the level slot (multilevel, cross-level) or the ping-pong buffer
         float* out = m->enc_kind == OVC_ENC_MULTILEVEL ? w.enc_levels + (size_t)l * BN * d
                    : m->enc_kind == OVC_ENC_CROSS_LEVEL ? w.cl_out + (size_t)l * BN * d
@@ -1201,8 +1208,8 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
         RUN(ovc_attention(b.q, b.k, b.v, B * p.S, p.T, p.T, m->heads, m->d_k, m->d_v, w.self_mask, (long)p.T * p.T, p.T, nullptr,
                           dl.self_att.m_k, dl.self_att.m_v, smem, scale, sqrtf((float)(smem > 0 ? smem : 1)), b.att, s));
     }
-    TRY(e.linear_ln(b.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, b.ys, p.part, b.x1, rows, p.site(l, 0)));
-    TRY(e.aoa(dl.self_att, x, b.x1, w.info, w.gate, rows));
+    TRY(e.linear_ln(b.att, hv, dl.self_att.o, x, dl.self_att.ln, nullptr, b.ys, p.part, b.us, rows, p.site(l, 0)));
+    TRY(e.aoa(dl.self_att, x, b.us, b.x1, b.infos, b.gates, rows));
 
     // ---- cross-attention over every encoder level: the image's rows share its projected keys / values ----
     TRY(e.linear(b.x1, d, dl.cross_att.q, nullptr, b.qc, rows, hk, 0));
@@ -1250,7 +1257,7 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
                 TRY(e.linear(b.attc + (size_t)lvl * rows * hv, hv, dl.cross_att.o, b.x1, b.yc, rows, d, 0));
                 RUN(ovc_layer_norm_gated(b.yc, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
                                          b.enc_att + lvl * nrd, rows, d, s, e.gate));
-                TRY(e.aoa(dl.cross_att, b.x1, b.enc_att + lvl * nrd, w.info, w.gate, rows));
+                TRY(e.aoa(dl.cross_att, b.x1, b.enc_att + lvl * nrd, b.enc_att + lvl * nrd, w.info, w.gate, rows));
             }
         }
         // level gates alpha_l = W_l [x1 ; enc_att_l] + b_l (decoders.py:59-66): one launch, a segment per level,
@@ -1271,8 +1278,8 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
         RUN(ovc_meshed_mix(b.alpha, b.enc_att, lv, (long)nrd, sqrtf((float)lv), b.mixed, s, e.gate));
         ffn_in = b.mixed;
     } else {
-        TRY(e.linear_ln(b.attc, hv, dl.cross_att.o, b.x1, dl.cross_att.ln, nullptr, b.yc, p.part, b.x2, rows, p.site(l, 1)));
-        TRY(e.aoa(dl.cross_att, b.x1, b.x2, w.info, w.gate, rows));
+        TRY(e.linear_ln(b.attc, hv, dl.cross_att.o, b.x1, dl.cross_att.ln, nullptr, b.yc, p.part, b.uc, rows, p.site(l, 1)));
+        TRY(e.aoa(dl.cross_att, b.x1, b.uc, b.x2, b.infoc, b.gatec, rows));
         ffn_in = b.x2;
     }
     return e.ffn(dl.ffn, ffn_in, b.ff, b.yf, p.part, b.out, p.zero_rows, rows, p.site(l, 2), p.site(l, 3));
@@ -2839,6 +2846,9 @@ struct TrainWs {
     // the geometric encoder's bias (TrainCall::geometric only): the caller's boxes [B*N][4], copied in outside the captured body;
     // d(bias) [B][h_enc][N][N], the encoder layers' dS summed top down; ovc_bw_box_relation's scratch
     float* geo_boxes; float* geo_dG; float* geo_scratch;
+    // the AoA gates (bw_aoa_gate; TrainCall::aoa only): [d(i) | d(a)] [Rmax][2d], the staged [W_i ; W_g]^T [2d][2d], d(u) and the
+    // site's d(q) -- the AddNorm residual's share plus the gate's -- [Rmax][d] each
+    float* aoa_dcat; float* aoa_wt; float* aoa_du; float* aoa_dq;
     size_t bytes;
 };
 
@@ -2855,7 +2865,7 @@ enum class LossHead {
     SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The twenty exported functions (ten entry points, ten sizers) fill one of these, and the
+// One training call, described once.  The twenty-four exported functions (twelve entry points, twelve sizers) fill one of these, and the
 // scope (call_ok), the workspace layout and size (carve_train), the captured body (issue_train_body), the graph key
 // (train_graph_key) and the launches around the body (run_train_call) are functions of it: a sizer and the entry point that carves
 // its buffer cannot disagree.
@@ -2872,6 +2882,7 @@ struct TrainCall {
     int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
     bool meshed;                                    // the multilevel encoder + meshed decoder (meshed_train_ok), the opt-in entry points
     bool geometric;                                 // the geometric encoder + plain decoder (geometric_train_ok), the opt-in entry points
+    bool aoa;                                       // plain encoder + plain decoder with AoA gates (aoa_train_ok), the opt-in entry points
     bool seq() const { return head == LossHead::RowWeights; }
     // The call's teacher-forced pass: the logits kept for the backward; RowWeights: on the caller's ids and their row gradient.
     ForwardCall forward() const {
@@ -2897,6 +2908,7 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         p.q = a.take<float>(BN * ehk); p.k = a.take<float>(BN * ehk); p.v = a.take<float>(BN * ehk); p.att = a.take<float>(BN * ehk);
         p.ya = a.take<float>(BN * d); p.x1 = a.take<float>(BN * d); p.ff = a.take<float>(BN * dff); p.yf = a.take<float>(BN * d);
         p.out = a.take<float>(l < m->n_enc - 1 && !cl && !c.meshed ? BN * d : 0);
+        p.u = p.x1; p.info = t.w.einfo; p.gate = t.w.egate;            // no gate's backward: aliased, as without a tape
     }
     if (cl) {
         ClTape& p = t.tape.cl;
@@ -2917,8 +2929,25 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
             p.ymesh = a.take<float>(lv * rows * d); p.enc_att = a.take<float>(lv * rows * d); p.alpha = a.take<float>(lv * rows * d);
             p.mixed = a.take<float>(rows * d);
         }
+        p.us = p.x1; p.infos = t.w.info; p.gates = t.w.gate; p.uc = p.x2; p.infoc = t.w.info; p.gatec = t.w.gate;
     }
-    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d, c.meshed ? 2 * d : d});   // the gates' operand [x1 ; e_l]
+    if (c.aoa) {
+        // every gated site keeps its own u, info and gate pre-activation beside the block's output (3 x [rows][d] per site)
+        for (int l = 0; l < m->n_enc; ++l) {
+            EncTape& p = t.tape.enc[l];
+            if (!m->enc[l].att.aoa_i.w) continue;
+            p.u = a.take<float>(BN * d); p.info = a.take<float>(BN * d); p.gate = a.take<float>(BN * d);
+        }
+        for (int l = 0; l < m->n_dec; ++l) {
+            DecTape& p = t.tape.dec[l];
+            if (m->dec[l].self_att.aoa_i.w) { p.us = a.take<float>(rows * d); p.infos = a.take<float>(rows * d); p.gates = a.take<float>(rows * d); }
+            if (m->dec[l].cross_att.aoa_i.w) { p.uc = a.take<float>(rows * d); p.infoc = a.take<float>(rows * d); p.gatec = a.take<float>(rows * d); }
+        }
+        t.aoa_dcat = a.take<float>(R * 2 * d); t.aoa_wt = a.take<float>(4 * d * d);
+        t.aoa_du = a.take<float>(R * d); t.aoa_dq = a.take<float>(R * d);
+    }
+    // the meshed gates' operand [x1 ; e_l] and the AoA gates' [q ; u] are 2d wide
+    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d, c.meshed || c.aoa ? 2 * d : d});
     t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
     t.tok = a.take<int32_t>(rows);
     t.w_row = c.seq() ? t.w.w_row : a.take<float>(rows); t.loss = a.take<float>(4);
@@ -3033,8 +3062,40 @@ bool geometric_train_ok(const ovc_model* m, const ForwardCall& c) {
     return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
 }
 
+// a gated attention (AoA): both gate products and no memory slots; a pair with one gate missing is neither this nor plain
+bool mha_gated(const ovc_mha& a) { return a.aoa_i.w && a.aoa_g.w && !a.m_k && !a.m_v; }
+
+// The opt-in scope (ovc_forward_backward_aoa, ovc_sequence_backward_aoa): the plain encoder and the plain decoder whose attentions
+// are each plain or gated (out = W_i [q ; u] * sigmoid(W_g [q ; u]) behind the AddNorm), at least one of them gated; no memory
+// slots; fp32, the fused vocabulary tail and the descriptor limits as in train_ok -- also for the gate block's K = 2d products
+// over [rows][2d] operands.
+bool aoa_train_ok(const ovc_model* m, const ForwardCall& c) {
+    if (!forward_ok(m, c) || m->precision != 0) return false;
+    if (m->enc_kind != OVC_ENC_PLAIN || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
+    int gated = 0;
+    const auto site_ok = [&](const ovc_mha& a) {
+        if (mha_gated(a)) { ++gated; return true; }
+        return mha_plain(a);
+    };
+    for (int l = 0; l < m->n_enc; ++l) if (!site_ok(m->enc[l].att)) return false;
+    for (int l = 0; l < m->n_dec; ++l) if (!site_ok(m->dec[l].self_att) || !site_ok(m->dec[l].cross_att)) return false;
+    if (gated == 0) return false;
+    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
+    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
+    const long most = std::max(rows, (long)c.B * c.N), widest = std::max({(long)m->d_ff, 3L * m->heads * m->d_k, 2L * m->d_model});
+    if ((most + 256) * widest * 4 > kMax || 4L * m->d_model * m->d_model * 4 > kMax) return false;
+    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
+}
+
 bool grads_ok(const ovc_model* m, const ovc_model* g) {
     if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
+    // the AoA gates, where a site has them (only an aoa call reaches this with gates: every other scope refuses them)
+    const auto gates_ok = [](const ovc_mha& a, const ovc_mha& ga) {
+        return (!a.aoa_i.w || lin_grad_ok(a.aoa_i, ga.aoa_i)) && (!a.aoa_g.w || lin_grad_ok(a.aoa_g, ga.aoa_g));
+    };
+    for (int l = 0; l < m->n_enc; ++l) if (!gates_ok(m->enc[l].att, g->enc[l].att)) return false;
+    for (int l = 0; l < m->n_dec; ++l)
+        if (!gates_ok(m->dec[l].self_att, g->dec[l].self_att) || !gates_ok(m->dec[l].cross_att, g->dec[l].cross_att)) return false;
     if (m->enc_kind == OVC_ENC_GEOMETRIC && (!g->fc_g_w || !g->fc_g_b)) return false;
     if (m->dec_kind == OVC_DEC_MESHED)
         for (int l = 0; l < m->n_dec; ++l)
@@ -3057,10 +3118,13 @@ bool dropout_train_ok(const ovc_model* m, const ForwardCall& c) { return train_o
 
 // The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope;
 // the opt-in meshed scope for the meshed entry points and the opt-in geometric scope for the geometric ones, and nothing else
-// reaches either.  A geometric call takes a dropout plan: the encoder's sites are the plain encoder's.
+// reaches either.  A geometric call takes a dropout plan: the encoder's sites are the plain encoder's.  Likewise the opt-in AoA
+// scope for the AoA entry points: the only one that takes a model with gates.
 bool call_ok(const ovc_model* m, const TrainCall& c) {
-    if (c.meshed) return !c.plan && !c.geometric && meshed_train_ok(m, c.forward());   // no dropout form: ovc_dropout has no per-level site
-    if (c.geometric) return geometric_train_ok(m, c.forward());
+    if (c.meshed) return !c.plan && !c.geometric && !c.aoa && meshed_train_ok(m, c.forward());   // no dropout form: ovc_dropout has no per-level site
+    if (c.geometric) return !c.aoa && geometric_train_ok(m, c.forward());
+    if (c.aoa) return aoa_train_ok(m, c.forward());       // takes a dropout plan: the gate sits behind the AddNorm and has no site
+
     return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward());
 }
 
@@ -3137,14 +3201,59 @@ int bw_ffn(Engine& e, TrainWs& t, const ovc_ffn& f, const ovc_ffn& gf, const flo
     return bw_input(e, t, t.dff, dff, f.fc1, d, t.dx1, t.dy, rows);
 }
 
-// Self-attention + AddNorm of one layer (rows = B*n): from dnorm (gradient of the norm output, read before anything is written)
-// to dx (gradient of the layer input x, which fed q, k, v and the residual)
+// What a gated site (AoA) left on the tape: the gate's query input q, the AddNorm output u and the two products i and a
+// (out = i * sigmoid(a), i = W_i [q ; u] + b_i, a = W_g [q ; u] + b_g).
+struct AoaSite { const float* q; const float* u; const float* info; const float* gate; };
+
+// The gate of one site, first half: from dout = d(out) to t.aoa_du = d(u), which enters the site's bw_norm,
+// and the gates' weight and bias gradients.  ovc_bw_aoa_gate writes [d(i) | d(a)] as one [rows][2d] block; dW_i = d(i)^T [q ; u]
+// and dW_g = d(a)^T [q ; u] read the concatenated operand staged transposed once (rows ascending, as bw_meshed_decoder_layer stages
+// [x1 ; e_l]); d([q ; u]) = [d(i) | d(a)] . [W_i ; W_g] is one K = 2d sum per output, issued as two products over the staged
+// [W_i ; W_g]^T: the u half here, the q half in bw_aoa_query once the AddNorm's residual share exists.
+int bw_aoa_gate(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const AoaSite& g, const float* dout, int rows) {
+    hipStream_t s = e.stream;
+    const int d = e.m->d_model, rp = (int)pad4(rows);
+    RUN(ovc_bw_aoa_gate(dout, g.info, g.gate, (long)rows * d, d, t.aoa_dcat, s));
+    RUN(ovc_bw_transpose(g.q, d, rows, d, t.tb, rp, rp, s));
+    RUN(ovc_bw_transpose(g.u, d, rows, d, t.tb + (size_t)d * rp, rp, rp, s));
+    const ovc_lin* lins[2] = {&at.aoa_i, &at.aoa_g};
+    const ovc_lin* glins[2] = {&ga.aoa_i, &ga.aoa_g};
+    for (int j = 0; j < 2; ++j) {
+        RUN(ovc_bw_transpose(t.aoa_dcat + j * d, 2 * d, rows, d, t.ta, rp, rp, s));
+        TRY(bw_mm(e, t.ta, rp, d, rp, t.tb, 2 * d, out_ptr(glins[j]->w)));
+        if (lins[j]->b) RUN(ovc_bw_rowsum(t.ta, rp, d, rows, out_ptr(glins[j]->b), s));
+        // aoa_wt [2d inputs][2d outputs i | a] = [W_i ; W_g]^T
+        RUN(ovc_bw_transpose(lins[j]->w, 2 * d, d, 2 * d, t.aoa_wt + j * d, 2 * d, d, s));
+    }
+    return bw_mm(e, t.aoa_dcat, 2 * d, rows, 2 * d, t.aoa_wt + (size_t)d * 2 * d, d, t.aoa_du);
+}
+
+// The gate of one site, second half, after the site's bw_norm: t.aoa_dq = t.dy + [d(i) | d(a)] . [W_i ; W_g][:, :d] -- the AddNorm
+// residual's share of d(q) with the gate's share added through the GEMM's residual input, the ONE place where the two meet.  The
+// caller passes t.aoa_dq on where the ungated path passes t.dy as the residual share.
+int bw_aoa_query(Engine& e, TrainWs& t, int rows) {
+    const int d = e.m->d_model;
+    return bw_mm(e, t.aoa_dcat, 2 * d, rows, 2 * d, t.aoa_wt, d, t.aoa_dq, t.dy);
+}
+
+// Self-attention + AddNorm of one layer (rows = B*n): from dnorm (gradient of the block's output, read before anything is written)
+// to dx (gradient of the layer input x, which fed q, k, v and the residual -- and, at a gated site, the gate).  gated: what an AoA
+// site kept (its q is x); nullptr: the plain block, launch for launch.
 int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& ga, const float* x, const float* q, const float* k,
                       const float* v, const float* att, const float* y, const float* dnorm, const uint8_t* mask, long mask_b,
                       long mask_r, int B, int n, int h, int dk, float* dx, int site = -1, int mem = 0, const float* geometry = nullptr,
-                      float* dS_out = nullptr) {
+                      float* dS_out = nullptr, const AoaSite* gated = nullptr) {
     const int d = e.m->d_model, hk = h * dk, rows = B * n;
+    const float* resid = t.dy;          // d(x)'s share through the AddNorm's residual
+    if (gated) {
+        TRY(bw_aoa_gate(e, t, at, ga, *gated, dnorm, rows));
+        dnorm = t.aoa_du;
+    }
     TRY(bw_norm(e, t, y, at.ln, ga.ln, dnorm, nullptr, rows, site));
+    if (gated) {
+        TRY(bw_aoa_query(e, t, rows));
+        resid = t.aoa_dq;
+    }
     const float* dp = proj_grad(e, t, site);
     TRY(bw_weight(e, t, dp, d, d, att, hk, hk, rows, at.o, ga.o));
     TRY(bw_input(e, t, dp, d, at.o, hk, t.datt, nullptr, rows));
@@ -3173,7 +3282,7 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
         TRY(bw_weight(e, t, t.dqkv + i * hk, 3 * hk, hk, x, d, d, rows, *lins[i], *glins[i]));
         RUN(ovc_bw_transpose(lins[i]->w, d, hk, d, t.wt + i * hk, 3 * hk, hk, e.stream));
     }
-    return bw_mm(e, t.dqkv, 3 * hk, rows, 3 * hk, t.wt, d, dx, t.dy);
+    return bw_mm(e, t.dqkv, 3 * hk, rows, 3 * hk, t.wt, d, dx, resid);
 }
 
 // S sequences per image (run_forward_decoder): the cross-attention of image b over its S*T query rows, the self-attention per sequence
@@ -3188,8 +3297,21 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const Tr
     const int d = m->d_model, h = m->heads, dk = m->d_k, hk = h * dk, rows = B * S * T, BN = B * N;
     // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(x2)
     TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.x2, p.ff, p.yf, dout, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
+    // a gated cross block (AoA): x2 is the gate's output, so its backward comes first and d(u) enters the norm; the gate's query is
+    // x1, so its share joins the residual's share of d(x1)
+    const bool cross_gated = dl.cross_att.aoa_i.w != nullptr, self_gated = dl.self_att.aoa_i.w != nullptr;
+    const float* dnorm = t.dx1;
+    if (cross_gated) {
+        TRY(bw_aoa_gate(e, t, dl.cross_att, gl.cross_att, AoaSite{p.x1, p.uc, p.infoc, p.gatec}, t.dx1, rows));
+        dnorm = t.aoa_du;
+    }
     // cross-attention AddNorm -> t.dy = d(yc), the residual's share of d(x1)
-    TRY(bw_norm(e, t, p.yc, dl.cross_att.ln, gl.cross_att.ln, t.dx1, nullptr, rows, dec_site(l, 1)));
+    TRY(bw_norm(e, t, p.yc, dl.cross_att.ln, gl.cross_att.ln, dnorm, nullptr, rows, dec_site(l, 1)));
+    const float* resid = t.dy;
+    if (cross_gated) {
+        TRY(bw_aoa_query(e, t, rows));
+        resid = t.aoa_dq;
+    }
     const float* dp = proj_grad(e, t, dec_site(l, 1));
     TRY(bw_weight(e, t, dp, d, d, p.attc, hk, hk, rows, dl.cross_att.o, gl.cross_att.o));
     TRY(bw_input(e, t, dp, d, dl.cross_att.o, hk, t.datt, nullptr, rows));
@@ -3201,16 +3323,17 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const Tr
     a.P = t.P; a.dS = t.dS; a.dq = t.dqkv; a.lddq = hk; a.dk_out = t.dkv; a.dv_out = t.dkv + hk; a.lddkv = 2 * hk;
     RUN(ovc_bw_attention(a, e.stream));
     TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
-    TRY(bw_input(e, t, t.dqkv, hk, dl.cross_att.q, d, t.dx1, t.dy, rows));      // t.dx1 = d(x1)
+    TRY(bw_input(e, t, t.dqkv, hk, dl.cross_att.q, d, t.dx1, resid, rows));     // t.dx1 = d(x1)
     // the encoder output's share: this layer's cross keys / values, added to what layers above contributed
     TRY(bw_weight(e, t, t.dkv, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.k, gl.cross_att.k));
     TRY(bw_weight(e, t, t.dkv + hk, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.v, gl.cross_att.v));
     RUN(ovc_bw_transpose(dl.cross_att.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
     RUN(ovc_bw_transpose(dl.cross_att.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
     TRY(bw_mm(e, t.dkv, 2 * hk, BN, 2 * hk, t.wt, d, denc_next, denc_prev));
-    // masked self-attention over the caption
+    // masked self-attention over the caption; x1 is the self block's output -- the gate's, where that block is gated
+    const AoaSite self_site{xin, p.us, p.infos, p.gates};
     return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
-                             B * S, T, h, dk, dxin, dec_site(l, 0));
+                             B * S, T, h, dk, dxin, dec_site(l, 0), 0, nullptr, nullptr, self_gated ? &self_site : nullptr);
 }
 
 int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk);
@@ -3455,9 +3578,11 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         // the geometric encoder: every layer adds the same bias, so d(bias) is the layers' dS summed top down -- the top layer's
         // rows pass writes it in place, the layers below add theirs
         const bool top = l == m->n_enc - 1;
+        // a gated layer (AoA): x1 is the gate's output and the gate's query is the layer input
+        const AoaSite site{xin, p.u, p.info, p.gate};
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
                               enc_site(l, 0), train_memory(m), c.geometric ? w.geometry : nullptr,
-                              c.geometric && top ? t.geo_dG : nullptr));
+                              c.geometric && top ? t.geo_dG : nullptr, el.att.aoa_i.w ? &site : nullptr));
         if (c.geometric && !top) RUN(ovc_bw_accumulate(t.geo_dG, t.dS, (long)B * eh * N * N, s));
         dout = t.g[cur];
         if ((cl || mlev) && l > 0) {
@@ -3800,6 +3925,46 @@ extern "C" int ovc_sequence_backward_geometric(const ovc_model* m, const ovc_mod
                                                int B, int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                                size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
     return run_train_call(m, grads, geometric_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
+                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training the attention-on-attention transformer: the opt-in entry points
+// ---------------------------------------------------------------------------------------------
+// ovc_forward_backward / ovc_sequence_backward for the plain encoder + plain decoder with AoA gates (aoa_train_ok): the same
+// TrainCall with `aoa` set, so the same carve_train (which gives every gated site its own u / info / gate), issue_train_body and
+// run_train_call.  The graph key hashes the whole ovc_model, the gates' pointers included.
+namespace {
+TrainCall aoa_call(int B, int N, int S, int T, LossHead head) {
+    TrainCall c{B, N, S, T, head};
+    c.aoa = true;
+    return c;
+}
+}  // namespace
+
+extern "C" size_t ovc_train_aoa_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
+    return train_workspace_bytes(m, aoa_call(B, N, 1, T, LossHead::Xent), dropout != 0);
+}
+
+extern "C" int ovc_forward_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                        int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                        size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                        const ovc_dropout* dropout) {
+    TrainCall c = aoa_call(B, N, 1, T, LossHead::Xent);
+    DropPlan plan{};
+    if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr,
+                          use_graph, stream);
+}
+
+extern "C" size_t ovc_train_aoa_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    return train_workspace_bytes(m, aoa_call(B, N, S, T, LossHead::RowWeights), false);
+}
+
+extern "C" int ovc_sequence_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                         int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                         size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
+    return run_train_call(m, grads, aoa_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
                           workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 

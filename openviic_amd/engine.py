@@ -170,7 +170,8 @@ def _grad_slots(model):
     the plain encoder / decoder's projections, norms and FFNs, the encoder layers' memory slots (``attention.m_k`` / ``m_v``,
     the augmented-memory transformer), the cross-level (CaMo) encoder's tail (``self_attn``, ``mlp1``, ``mlp2``), the meshed
     decoder's level gates (``fc_alphas``; ``ovc_forward_backward_meshed``), the geometric encoder's ``fc_gs``
-    (``ovc_forward_backward_geometric``), the word embedding and the vocabulary projection.
+    (``ovc_forward_backward_geometric``), the AoA gates ``informative_attention`` / ``gated_attention`` of every gated attention
+    (``ovc_forward_backward_aoa``), the word embedding and the vocabulary projection.
 
     The ``h`` ``fc_gs[i].weight`` come consecutively, then the ``h`` ``fc_gs[i].bias``: the arena pads every slot to 4 floats, so it
     holds the weight gradients as one ``[h][d_g]`` block (``d_g % 4 == 0``) and the bias gradients as ``[h][4]``, which is what
@@ -192,6 +193,9 @@ def _grad_slots(model):
         for name, fc in (("q", att.fc_q), ("k", att.fc_k), ("v", att.fc_v), ("o", att.fc_o)):
             lin(path + (name,), fc)
         norm(path + ("ln",), m.layer_norm)
+        if m.use_aoa:       # the AoA gates behind the norm (``ovc_forward_backward_aoa``)
+            lin(path + ("aoa_i",), m.informative_attention)
+            lin(path + ("aoa_g",), m.gated_attention)
 
     def ffn(path, pwff):
         lin(path + ("fc1",), pwff.fc1)
@@ -965,20 +969,26 @@ class CaptionEngine:
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------
-    def _check_trainable(self, meshed=False, geometric=False):
+    def _check_trainable(self, meshed=False, geometric=False, aoa=False):
         """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'
         self-attention has memory slots, plain decoder) and the CaMo transformer (cross-level encoder, plain decoder) in fp32:
-        anything else is refused before a launch.  ``meshed=True`` / ``geometric=True``: the opt-in scope instead
-        (``_check_trainable_meshed`` / ``_check_trainable_geometric``); both together are refused."""
+        anything else is refused before a launch.  ``meshed=True`` / ``geometric=True`` / ``aoa=True``: the opt-in scope instead
+        (``_check_trainable_meshed`` / ``_check_trainable_geometric`` / ``_check_trainable_aoa``); two of them together are
+        refused."""
         d = self.desc
         if meshed and geometric:
             raise native.OvcError("meshed=True and geometric=True name two different models: pass the one this model is")
+        if aoa and (meshed or geometric):
+            raise native.OvcError("aoa=True and {}=True name two different models: pass the one this model is".format(
+                "meshed" if meshed else "geometric"))
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
         if meshed:
             return self._check_trainable_meshed()
         if geometric:
             return self._check_trainable_geometric()
+        if aoa:
+            return self._check_trainable_aoa()
         if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
             raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
                                   "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
@@ -1058,6 +1068,29 @@ class CaptionEngine:
         if extra:
             raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
 
+    def _check_trainable_aoa(self):
+        """``aoa=True``: the attention-on-attention transformer -- the plain encoder and the plain decoder whose attentions carry
+        AoA gates, all of them or any subset (``ovc_forward_backward_aoa``).  Anything else is refused by name before a launch."""
+        d = self.desc
+        if d.enc_kind != native.ENC_PLAIN or d.dec_kind != native.DEC_PLAIN:
+            raise native.OvcError("aoa=True covers the plain Encoder in front of the plain Decoder only (this model has {} / {}); "
+                                  "call without aoa=True".format(type(self.model.encoder).__name__,
+                                                                 type(self.model.decoder).__name__))
+        model = self.model
+        sites = [layer.mhatt for layer in model.encoder.layers]
+        sites += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
+        if not any(m.use_aoa for m in sites):
+            raise native.OvcError("aoa=True: this model has no attention-on-attention gates (USE_AOA is off in every attention); "
+                                  "call without aoa=True")
+        if any(hasattr(m.attention, "m_k") for m in sites) or d.memory:
+            raise native.OvcError("aoa=True: the training backward does not cover attention memory slots beside the gates")
+        if not hasattr(model.decoder.word_emb, "components"):
+            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
+        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
+        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
+        if extra:
+            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
+
     def _check_pointers(self):
         """Re-read the pointer table when a parameter's storage moved (``p.data = ...``): in-place updates (an optimizer step)
         keep the storage and are seen by every call as they are."""
@@ -1071,7 +1104,7 @@ class CaptionEngine:
         return [p for p, _ in _grad_slots(self.model)]
 
     def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None,
-                         distill=None, meshed=False, geometric=False):
+                         distill=None, meshed=False, geometric=False, aoa=False):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -1102,7 +1135,13 @@ class CaptionEngine:
 
         ``geometric=True``: the object-relation transformer (``ovc_forward_backward_geometric``; ``_check_trainable_geometric``
         states the scope).  ``boxes`` are required; they are staged before the body, so a replayed graph reads this call's.
-        ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``."""
+        ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``.
+
+        ``aoa=True``: the attention-on-attention transformer (``ovc_forward_backward_aoa``; ``_check_trainable_aoa`` states the
+        scope).  ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``."""
+        if aoa and (loss is not None or distill is not None):
+            raise native.OvcError("forward_backward(aoa=True): the label-smoothed loss and soft targets are out of scope for the "
+                                  "attention-on-attention transformer")
         if geometric and (loss is not None or distill is not None):
             raise native.OvcError("forward_backward(geometric=True): the label-smoothed loss and soft targets are out of scope for "
                                   "the object-relation transformer")
@@ -1127,12 +1166,12 @@ class CaptionEngine:
             loss = checked_label_smoothing(loss[0], loss[1], "forward_backward", self.desc.vocab)
             if loss == (0.0, "tokens"):
                 loss = None
-        self._check_trainable(meshed, geometric)
+        self._check_trainable(meshed, geometric, aoa)
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed, geometric=geometric)
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed, geometric=geometric, aoa=aoa)
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -1157,14 +1196,19 @@ class CaptionEngine:
     _GEOMETRIC_FORMS = {False: ("ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric"),
                         True: ("ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric")}
 
-    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False, geometric=False):
+    # ... and of the attention-on-attention transformer, likewise
+    _AOA_FORMS = {False: ("ovc_train_aoa_workspace_bytes", "ovc_forward_backward_aoa"),
+                  True: ("ovc_train_aoa_beams_workspace_bytes", "ovc_sequence_backward_aoa")}
+
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False, geometric=False, aoa=False):
         """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
         T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
         on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
         soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``meshed``: the
         meshed-memory transformer's form (no loss, dropout or distill with it: the callers refuse them).  ``geometric``: the
-        object-relation transformer's form (no loss or distill, and no dropout with ``sequence``: the callers refuse them)."""
+        object-relation transformer's form (no loss or distill, and no dropout with ``sequence``: the callers refuse them).
+        ``aoa``: the attention-on-attention transformer's form, under the same rules."""
         sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
         if meshed:
             sizer, entry = self._MESHED_FORMS[bool(sequence)]
@@ -1178,8 +1222,8 @@ class CaptionEngine:
         if distill is not None:
             size_tail = (1 if drop else 0,)
             tail = (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), drop[0] if drop else None)
-        if geometric:
-            sizer, entry = self._GEOMETRIC_FORMS[bool(sequence)]
+        if geometric or aoa:
+            sizer, entry = (self._GEOMETRIC_FORMS if geometric else self._AOA_FORMS)[bool(sequence)]
             if not sequence:
                 size_tail, tail = (1 if drop else 0,), (drop[0] if drop else None,)
         self._check_pointers()
@@ -1187,7 +1231,7 @@ class CaptionEngine:
             "sequence" if sequence else "train", sizer, (*shape, *size_tail),
             "unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                sizer if meshed or geometric else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
+                sizer if meshed or geometric or aoa else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
         return entry, shape, ws, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
@@ -1231,7 +1275,7 @@ class CaptionEngine:
         return self._buffers[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
-                          beam_size=None, arena=None, meshed=False, geometric=False):
+                          beam_size=None, arena=None, meshed=False, geometric=False, aoa=False):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -1249,13 +1293,17 @@ class CaptionEngine:
 
         ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``.
         ``geometric=True``: the object-relation transformer (``ovc_sequence_backward_geometric``), ``boxes`` required; refused
+        together with ``dropout``.  ``aoa=True``: the attention-on-attention transformer (``ovc_sequence_backward_aoa``); refused
         together with ``dropout``."""
+        if aoa and dropout is not None:
+            raise native.OvcError("sequence_backward(aoa=True): the sequence form under dropout is out of scope for the "
+                                  "attention-on-attention transformer")
         if meshed and dropout is not None:
             raise native.OvcError("sequence_backward(meshed=True): dropout is out of scope for the meshed-memory transformer")
         if geometric and dropout is not None:
             raise native.OvcError("sequence_backward(geometric=True): the sequence form under dropout is out of scope for the "
                                   "object-relation transformer")
-        self._check_trainable(meshed, geometric)
+        self._check_trainable(meshed, geometric, aoa)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         if table_drop is not None:
             if (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or
@@ -1277,7 +1325,8 @@ class CaptionEngine:
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
         form = self._train_form(True, None, table_drop, (B, N, S, T),
-                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed, geometric=geometric)
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed, geometric=geometric,
+                                aoa=aoa)
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
         arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,

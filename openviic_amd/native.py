@@ -237,6 +237,13 @@ SIGNATURES = {
                                                 c_void_p, c_void_p, c_void_p]),
     "ovc_debug_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ovc_train_aoa_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_forward_backward_aoa": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, POINTER(Dropout)]),
+    "ovc_train_aoa_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward_aoa": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ovc_debug_aoa_gate_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
     "ovc_dropout_mask_rows": (c_int, [c_void_p, c_int, c_void_p, c_long, c_long, c_float, c_void_p, c_void_p]),
     "ovc_beam_search_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
     "ovc_beam_search_dropout": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
@@ -374,7 +381,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_sequence_backward_meshed", "ovc_debug_meshed_mix_backward",
                  "ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric",
                  "ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric",
-                 "ovc_debug_box_relation_backward_floats", "ovc_debug_box_relation_backward", "ovc_debug_attention_backward")
+                 "ovc_debug_box_relation_backward_floats", "ovc_debug_box_relation_backward", "ovc_debug_attention_backward",
+                 "ovc_train_aoa_workspace_bytes", "ovc_forward_backward_aoa", "ovc_train_aoa_beams_workspace_bytes",
+                 "ovc_sequence_backward_aoa", "ovc_debug_aoa_gate_backward")
 
 _lib = None
 

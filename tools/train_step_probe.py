@@ -7,6 +7,8 @@ configuration (d_model 512, 8 x 64 heads, d_ff 2048, 3 + 3 layers, d_feat 2048, 
 --variant augmented_memory_transformer: the plain encoder with 40 memory slots per layer (the memory-slot attention backward).
 --variant object_relation_transformer (next to another variant): the geometric encoder -- the box-relation bias in the encoder's
 attention backward and ovc_bw_box_relation -- through xe_loss(geometric=True).
+--variant attention_on_attention: the plain encoder / decoder with AoA gates in all nine attentions -- the gate backward and its
+K = 2d products -- through xe_loss(aoa=True) (ovc_forward_backward_aoa; --optimizer none only).
 --variant meshed_memory_transformer: the multilevel encoder with 40 memory slots per layer and the meshed decoder, through
 ``model.xe_loss(items, meshed=True)`` (``ovc_forward_backward_meshed``; no dropout form, --optimizer none only).
 Several --variant values alternate in ONE process -- per batch size, ``--rounds`` rounds of ``--steps`` steps of each variant in
@@ -80,6 +82,8 @@ def step_flops(cfg_dims, B, N, T):
                + lv * 2 * R * hk * d + 4 * R * d * dff)
     if "levels" in cfg_dims:        # the level gates: Linear(2d -> d) per level
         f += Ld * lv * 2 * R * 2 * d * d
+    if cfg_dims.get("aoa"):         # the AoA gates: two Linear(2d -> d) per attention -- one per encoder layer, two per decoder layer
+        f += (Le * BN + 2 * Ld * R) * 2 * (2 * 2 * d * d)
     f += 2 * R * d * V
     return 3 * f
 
@@ -216,18 +220,21 @@ def distill_probe(args, model, teacher, items, B, T, N, V):
 
 MESHED = "meshed_memory_transformer"
 GEOMETRIC = "object_relation_transformer"
+AOA = "attention_on_attention"
 
 
 def variant_dims(variant):
     return {"camo_transformer": dict(he=1, tail=True), "augmented_memory_transformer": dict(memory=40),
-            MESHED: dict(memory=40, levels=3)}.get(variant, {})
+            MESHED: dict(memory=40, levels=3), AOA: dict(aoa=True)}.get(variant, {})
 
 
 def loss_kw(variant, dropout):
     """The keywords of ``xe_loss`` for a variant: the meshed-memory transformer is opt-in and has no dropout form, the
-    object-relation transformer is opt-in too."""
+    object-relation and the attention-on-attention transformers are opt-in too."""
     if variant == GEOMETRIC:
         return dict(geometric=True, dropout=dropout)
+    if variant == AOA:
+        return dict(aoa=True, dropout=dropout)
     return dict(meshed=True) if variant == MESHED else dict(dropout=dropout)
 
 
@@ -236,6 +243,8 @@ def train_sizer(lib, variant, dropout):
         return lib.ovc_train_meshed_workspace_bytes
     if variant == GEOMETRIC:
         return lambda d, B, N, T: lib.ovc_train_geometric_workspace_bytes(d, B, N, T, 1 if dropout else 0)
+    if variant == AOA:
+        return lambda d, B, N, T: lib.ovc_train_aoa_workspace_bytes(d, B, N, T, 1 if dropout else 0)
     return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
 
 
@@ -288,11 +297,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
     ap.add_argument("--variant", nargs="+", default=["standard_transformer"],
-                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED, GEOMETRIC],
+                    choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED, GEOMETRIC, AOA],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
                          "augmented_memory_transformer: 40 memory slots in the encoder; meshed_memory_transformer: the multilevel "
                          "encoder and the meshed decoder (meshed=True); object_relation_transformer: the geometric encoder "
-                         "(geometric=True; next to another --variant only); several values alternate in one process")
+                         "(geometric=True; next to another --variant only); attention_on_attention: the AoA gates in every "
+                         "attention (aoa=True; --optimizer none); several values alternate in one process")
     ap.add_argument("--optimizer", nargs="+", default=["none"], choices=["none", "torch", "engine", "xe_step"],
                     help="none: forward + backward only; torch / engine / xe_step: the whole iteration (several values alternate)")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --steps iterations per --optimizer form")
@@ -318,6 +328,8 @@ def main():
     if MESHED in args.variant and (args.dropout or args.optimizer != ["none"] or args.label_smoothing is not None or
                                    args.distill is not None):
         ap.error("meshed_memory_transformer goes with --optimizer none, without --dropout, --label-smoothing or --distill")
+    if AOA in args.variant and (args.optimizer != ["none"] or args.label_smoothing is not None or args.distill is not None):
+        ap.error("attention_on_attention goes with --optimizer none, without --label-smoothing or --distill")
     if GEOMETRIC in args.variant and len(args.variant) < 2:
         ap.error("object_relation_transformer runs next to another --variant (its step is reported against that one)")
     assert torch.cuda.is_available(), "needs a HIP device"

@@ -1323,6 +1323,61 @@ int ovc_debug_leaky_residual(const float* x, int ldx, const float* residual, int
                              int rows, int cols, ovc_stream stream);
 int ovc_debug_sigmoid_gate(const float* a, const float* g, float* y, long n, const int32_t* gate, ovc_stream stream);
 
+/* Test hooks: the kernels of the training backward (csrc/backward.hip) on caller buffers (appended to ABI 8; no struct changes), so
+ * that every kernel can be compared with an fp64 restatement at the kernel level, over every stride its launcher takes
+ * (tests/test_backward_gpu.py; csrc/backward.h states each operation and its summation order).  Each hook validates its arguments on
+ * the host BEFORE it looks at a device -- so every refusal below is OVC_EINVAL on a machine without a GPU too, with nothing launched
+ * and nothing written -- and then calls the launcher the training calls use.  Refused by all of them: a required pointer that is
+ * NULL, a float / int32 pointer not aligned to 4 bytes or an int64 pointer not aligned to 8, a count (rows, cols, n, d, V, B, nq, nk,
+ * h) <= 0, a row stride smaller than the row.
+ *
+ * ovc_debug_bw_transpose: dst[c * ldd + r] = src[r * lds + c], +0 for rows <= r < rows_pad; rows <= rows_pad <= ldd.
+ * ovc_debug_bw_rowsum: dst[i] = sum_j src[i * ld + j].  ovc_debug_bw_colsum: dst[c] = sum_r src[r * ld + c] through part, which
+ * holds part_floats >= ceil(rows / 64) * cols floats.
+ * ovc_debug_bw_layer_norm: the LayerNorm backward, form 0 plain, 1 with a dropout site on the projection (dproj = keep ? dx * s : 0;
+ * the site is built from (seed, site, p, drop_cols) as the training calls build it), 2 the same with the mask row of row r read from
+ * rowmap[r], 3 the backward of y = alpha LN(x + r) + r.  d <= 2048, eps >= 0; forms 1 and 2 need dproj, seed, 0 <= site <
+ * OVC_DROPOUT_SITES, 0 <= p < 1 and drop_cols == d, the others take neither dproj nor seed; rowmap exactly with form 2; r exactly
+ * with form 3, which takes no zero_rows.
+ * ovc_debug_bw_relu: g = act > 0 ? g : 0, with dropout = 1: act > 0 ? g * s : 0, s the scale of 0 <= p < 1.  ovc_debug_bw_leaky:
+ * out = (g * scale) * (act > 0 ? 1 : slope), out may be g.  ovc_debug_bw_sum: y = (a + b) + c (c may be NULL) on strided rows, y may
+ * be an operand.  ovc_debug_bw_sum_levels: out = ((acc + src[0]) + src[1]) + ... over `levels` in 1..OVC_MAX_LEVELS blocks `stride`
+ * >= n apart (acc may be NULL, out may be acc).  ovc_debug_bw_accumulate: acc += src.
+ * ovc_debug_bw_loss: the loss heads on the stored transposed logits logits_t [V][ldt] and the forward's pieces lse [rows][2] (row
+ * maximum, log of the sum); head 0 the cross-entropy (w_row, loss, dl_t [V][ldt], dl [rows][ldv] written), 1 the dlogit alone under
+ * the caller's w_row (loss must be NULL), 2 the label-smoothed loss (param = smoothing in [0, 1), V > 2 when it is > 0; reduction
+ * OVC_LOSS_MEAN / OVC_LOSS_TOKENS; part: the partial row sums, row_a: the row sums [rows]), 3 the soft-target loss (param = the
+ * teacher's weight in [0, 1]; teacher [rows][V]; part: both partials, row_a: kl [rows], row_b: mass [rows]).  0 <= pad < V,
+ * rows <= ldt <= rows rounded up to 4, ldv >= V; part_floats >= ovc_debug_bw_loss_part_floats(rows, V) for head 2 and twice that for
+ * head 3; a head is given the buffers it uses and no others.
+ * ovc_debug_bw_embedding: out[w] = sum over the rows with tok[r] == w of dx[r], the pad row 0; d <= 2048, 0 <= pad < V.
+ * ovc_debug_bw_tokens: tok32[r] = clamp(tokens[r], 0, V - 1).
+ * ovc_debug_bw_attention: ovc_debug_attention_backward with every stride of the internal launcher: q [B*nq][ldq], k / v [B*nk][ldkv],
+ * dout [B*nq][ldo], dq [B*nq][lddq], dk_out / dv_out [B*nk][lddkv] (separate pointers: the training calls interleave them in one
+ * buffer), mask[b * mask_b + i * mask_r + j] (NULL: none; mask_r = 0: one row of keys per image), geometry [B][h][nq][nk] or NULL.
+ * dk in 1..64, nk <= 8000, every stride >= h dk, mask_b >= 0, mask_r = 0 or >= nk. */
+int ovc_debug_bw_transpose(const float* src, long lds, int rows, int cols, float* dst, long ldd, int rows_pad, ovc_stream stream);
+int ovc_debug_bw_rowsum(const float* src, long ld, int rows, int n, float* dst, ovc_stream stream);
+int ovc_debug_bw_colsum(const float* src, long ld, int rows, int cols, float* part, size_t part_floats, float* dst, ovc_stream stream);
+int ovc_debug_bw_layer_norm(int form, const float* x, const float* r, const float* gamma, const float* dy, const uint8_t* zero_rows,
+                            float alpha, float eps, int rows, int d, float* dx, float* prod, float* dyc, float* dproj,
+                            const int64_t* seed, int site, float p, int drop_cols, const int32_t* rowmap, ovc_stream stream);
+int ovc_debug_bw_relu(float* g, const float* act, int dropout, float p, long n, ovc_stream stream);
+int ovc_debug_bw_leaky(const float* g, const float* act, float scale, float slope, float* out, long n, ovc_stream stream);
+int ovc_debug_bw_sum(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols, float* y,
+                     long ldy, ovc_stream stream);
+int ovc_debug_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out, ovc_stream stream);
+int ovc_debug_bw_accumulate(float* acc, const float* src, long n, ovc_stream stream);
+size_t ovc_debug_bw_loss_part_floats(int rows, int V);
+int ovc_debug_bw_loss(int head, const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V,
+                      float param, int reduction, const float* teacher, float* part, size_t part_floats, float* row_a, float* row_b,
+                      float* w_row, float* loss, float* dl_t, float* dl, long ldv, ovc_stream stream);
+int ovc_debug_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, ovc_stream stream);
+int ovc_debug_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, ovc_stream stream);
+int ovc_debug_bw_attention(const float* q, long ldq, const float* k, const float* v, long ldkv, const float* dout, long ldo,
+                           const uint8_t* mask, long mask_b, long mask_r, const float* geometry, int B, int nq, int nk, int h, int dk,
+                           float* P, float* dS, float* dq, long lddq, float* dk_out, float* dv_out, long lddkv, ovc_stream stream);
+
 /* Test hook (tests/test_attention_maps_gpu.py): ovc_cross_attention_maps on raw operands, as ovc_attention_maps launches it for one
  * layer and level -- q [b, nq, h*d_k], k [b, nk, h*d_k], mask [b, nk] (the image's padding regions; NULL: none), m slot keys
  * m_k [m, h*d_k] taken times sqrtf(d_k) -> P [b, h, nq, ld], ld = nk + m rounded up to 4. */

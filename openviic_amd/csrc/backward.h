@@ -20,8 +20,9 @@ int ovc_bw_layer_norm(const float* x, const float* gamma, const float* dy, const
 int ovc_bw_relu(float* g, const float* act, long n, hipStream_t s);
 
 // Dropout (ovc_forward_backward_dropout).  ovc_bw_layer_norm of a norm whose input x = residual + drop(proj) has a dropout site on
-// the projection: the same dx / prod / dyc, and dproj = keep * s * dx, the projection's gradient (mask regenerated from the
-// counter, columns = d).
+// the projection: the same dx / prod / dyc -- the bits of ovc_bw_layer_norm at every width: the kernels share its loops, and dproj
+// is formed from the stored dx in a loop of its own -- and dproj = keep * s * dx, the projection's gradient (mask regenerated from
+// the counter, columns = d).
 int ovc_bw_layer_norm_dropout(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows, int d,
                               float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop, hipStream_t s);
 // the same with the mask row of row r read from rowmap[r] (ovc_sequence_backward_dropout, decoder sites)
@@ -85,6 +86,8 @@ int ovc_bw_dlogit(const float* logits_t, long ldt, const float* lse, const int32
 // slices of 64 words into lp_part [ceil(V / 64)][ldt], then the slices in ascending order into lp_sum [rows]; read by the loss
 // only), the loss and the row weights (one workgroup, ovc_bw_xent's order; reduction 0: w = w_mean on kept rows, 1: 1 / count),
 // and dlogit = (softmax - t) w_row in ovc_bw_xent's two layouts.  C, conf, u and w_mean are the host's float64 values rounded once.
+// OVC_EINVAL for ldt outside rows..rows padded to 4, as ovc_bw_xent_soft: lp_part's rows are ldt apart and ovc_bw_smoothed_part_floats
+// sizes them for the padded row count.
 struct SmoothedLoss {
     float conf, u, C, w_mean;
     int reduction;

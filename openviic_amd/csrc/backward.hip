@@ -1,6 +1,7 @@
 // Device kernels of the training backward (ovc_forward_backward, engine.hip).  Declarations and contracts: backward.h.
 // Everything here is deterministic by construction: each output element is written by one lane, and every sum over rows,
 // queries, keys or columns runs in an order fixed by the shape alone.
+#include <cmath>
 #include "backward.h"
 #include "box_relation.h"
 
@@ -88,7 +89,9 @@ __global__ __launch_bounds__(256) void bw_layer_norm_kernel(const float* __restr
     }
 }
 
-// bw_layer_norm_kernel plus the masked copy of dx (the gradient of the pre-norm sum x) for a dropout site on the projection inside x
+// bw_layer_norm_kernel plus the masked copy of dx (the gradient of the pre-norm sum x) for a dropout site on the projection inside x.
+// The body's loops are bw_layer_norm_kernel's, statement for statement, and dproj is formed from the stored dx in a loop of its own:
+// dx, prod and dyc then have the plain kernel's bits at every width (tests/test_backward_gpu.py holds all three instances to that)
 __global__ __launch_bounds__(256) void bw_layer_norm_dropout_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                     const float* __restrict__ dy, const uint8_t* __restrict__ zero_rows,
                                                                     float eps, int rows, int d, float* __restrict__ dx,
@@ -751,8 +754,9 @@ size_t ovc_bw_smoothed_part_floats(int rows, int V) {
 int ovc_bw_xent_smoothed(const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows, int V,
                          const SmoothedLoss& l, float* lp_part, float* lp_sum, float* w_row, float* loss, float* dl_t, float* dl,
                          long ldv, hipStream_t s) {
-    if (rows <= 0 || V <= 0 || pad < 0 || pad >= V || ldt < rows || !lp_part || !lp_sum || (l.reduction != 0 && l.reduction != 1))
-        return OVC_EINVAL;
+    if (rows <= 0 || V <= 0 || pad < 0 || pad >= V || ldt < rows || ldt > (((long)rows + 3) & ~3L) || !lp_part || !lp_sum ||
+        (l.reduction != 0 && l.reduction != 1))
+        return OVC_EINVAL;           // lp_part's rows are ldt apart: ovc_bw_smoothed_part_floats sizes them for rows padded to 4
     const int slices = (V + kLpSlice - 1) / kLpSlice;
     hipLaunchKernelGGL(bw_logp_rowsum_part_kernel, dim3((rows + 63) / 64, (slices + 3) / 4), dim3(256), 0, s, logits_t, ldt, lse, rows,
                        V, lp_part);
@@ -1219,4 +1223,167 @@ extern "C" int ovc_debug_meshed_mix_backward(const float* dmixed, const float* a
                                              float* denc, float* dalpha, ovc_stream stream) {
     if (const int rc = ovc_device_guard()) return rc;          // one device per process (include/ovc.h)
     return ovc_bw_meshed_mix(dmixed, alpha, enc, levels, n, divisor, denc, dalpha, ovc_hip_stream(stream));
+}
+
+// ---- Test hooks (include/ovc.h, "the kernels of the training backward on caller buffers"; tests/test_backward_gpu.py) ------------
+// Each validates everything it can on the host, BEFORE the device guard (so the refusals hold on a machine with no GPU and write
+// nothing), then calls the launcher the engine calls.
+namespace {
+
+inline bool dbg_f32(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }        // a float / int32 array
+inline bool dbg_f32_or_null(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool dbg_i64(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }        // an int64 array
+inline long dbg_pad4(long n) { return (n + 3) & ~3L; }
+constexpr long kDbgGridY = 65535;                                                                     // tiles along a grid's y
+inline bool dbg_prob(float p) { return p >= 0.f && p < 1.f; }                                         // NaN: false
+
+}  // namespace
+
+extern "C" int ovc_debug_bw_transpose(const float* src, long lds, int rows, int cols, float* dst, long ldd, int rows_pad,
+                                      ovc_stream stream) {
+    if (!dbg_f32(src) || !dbg_f32(dst) || rows <= 0 || cols <= 0 || lds < cols || rows_pad < rows || ldd < rows_pad) return OVC_EINVAL;
+    if (((long)cols + 63) / 64 > kDbgGridY) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_transpose(src, lds, rows, cols, dst, ldd, rows_pad, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_rowsum(const float* src, long ld, int rows, int n, float* dst, ovc_stream stream) {
+    if (!dbg_f32(src) || !dbg_f32(dst) || rows <= 0 || n <= 0 || ld < n) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_rowsum(src, ld, rows, n, dst, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_colsum(const float* src, long ld, int rows, int cols, float* part, size_t part_floats, float* dst,
+                                   ovc_stream stream) {
+    if (!dbg_f32(src) || !dbg_f32(part) || !dbg_f32(dst) || rows <= 0 || cols <= 0 || ld < cols) return OVC_EINVAL;
+    const long chunks = ((long)rows + kChunk - 1) / kChunk;
+    if (chunks > kDbgGridY || part_floats < (size_t)chunks * (size_t)cols) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_colsum(src, ld, rows, cols, part, dst, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_layer_norm(int form, const float* x, const float* r, const float* gamma, const float* dy,
+                                       const uint8_t* zero_rows, float alpha, float eps, int rows, int d, float* dx, float* prod,
+                                       float* dyc, float* dproj, const int64_t* seed, int site, float p, int drop_cols,
+                                       const int32_t* rowmap, ovc_stream stream) {
+    if (form < 0 || form > 3 || !dbg_f32(x) || !dbg_f32(gamma) || !dbg_f32(dy) || !dbg_f32(dx) || !dbg_f32(prod) || !dbg_f32(dyc))
+        return OVC_EINVAL;
+    if (rows <= 0 || d <= 0 || d > 2048 || !(eps >= 0.f)) return OVC_EINVAL;
+    const bool drop = form == 1 || form == 2;
+    if (drop ? (!dbg_f32(dproj) || !dbg_i64(seed) || site < 0 || site >= OVC_DROPOUT_SITES || !dbg_prob(p) || drop_cols != d)
+             : (dproj || seed)) return OVC_EINVAL;
+    if (form == 2 ? !dbg_f32(rowmap) : rowmap != nullptr) return OVC_EINVAL;
+    if (form == 3 ? (!dbg_f32(r) || zero_rows) : r != nullptr) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    hipStream_t s = ovc_hip_stream(stream);
+    if (form == 0) return ovc_bw_layer_norm(x, gamma, dy, zero_rows, eps, rows, d, dx, prod, dyc, s);
+    if (form == 3) return ovc_bw_layer_norm_post(x, r, gamma, dy, alpha, eps, rows, d, dx, prod, dyc, s);
+    const DropoutSite drop_site{seed, (uint32_t)site, ovc_dropout_threshold(p), ovc_dropout_scale(p), drop_cols};
+    if (form == 1) return ovc_bw_layer_norm_dropout(x, gamma, dy, zero_rows, eps, rows, d, dx, prod, dyc, dproj, drop_site, s);
+    return ovc_bw_layer_norm_dropout_mapped(x, gamma, dy, zero_rows, eps, rows, d, dx, prod, dyc, dproj, drop_site, rowmap, s);
+}
+
+extern "C" int ovc_debug_bw_relu(float* g, const float* act, int dropout, float p, long n, ovc_stream stream) {
+    if (!dbg_f32(g) || !dbg_f32(act) || n <= 0 || (dropout != 0 && dropout != 1) || (dropout && !dbg_prob(p))) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    if (dropout) return ovc_bw_relu_dropout(g, act, ovc_dropout_scale(p), n, ovc_hip_stream(stream));
+    return ovc_bw_relu(g, act, n, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_leaky(const float* g, const float* act, float scale, float slope, float* out, long n, ovc_stream stream) {
+    if (!dbg_f32(g) || !dbg_f32(act) || !dbg_f32(out) || n <= 0) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_leaky(g, act, scale, slope, out, n, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_sum(const float* a, long lda, const float* b, long ldb, const float* c, long ldc, int rows, int cols,
+                                float* y, long ldy, ovc_stream stream) {
+    if (!dbg_f32(a) || !dbg_f32(b) || !dbg_f32_or_null(c) || !dbg_f32(y) || rows <= 0 || cols <= 0) return OVC_EINVAL;
+    if (lda < cols || ldb < cols || (c && ldc < cols) || ldy < cols) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_sum(a, lda, b, ldb, c, ldc, rows, cols, y, ldy, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_sum_levels(const float* acc, const float* src, int levels, long stride, long n, float* out,
+                                       ovc_stream stream) {
+    if (!dbg_f32_or_null(acc) || !dbg_f32(src) || !dbg_f32(out) || levels < 1 || levels > OVC_MAX_LEVELS || n <= 0 || stride < n)
+        return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_sum_levels(acc, src, levels, stride, n, out, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_accumulate(float* acc, const float* src, long n, ovc_stream stream) {
+    if (!dbg_f32(acc) || !dbg_f32(src) || n <= 0) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_accumulate(acc, src, n, ovc_hip_stream(stream));
+}
+
+extern "C" size_t ovc_debug_bw_loss_part_floats(int rows, int V) {
+    return rows > 0 && V > 0 ? ovc_bw_smoothed_part_floats(rows, V) : 0;
+}
+
+extern "C" int ovc_debug_bw_loss(int head, const float* logits_t, long ldt, const float* lse, const int32_t* tgt, int pad, int rows,
+                                 int V, float param, int reduction, const float* teacher, float* part, size_t part_floats, float* row_a,
+                                 float* row_b, float* w_row, float* loss, float* dl_t, float* dl, long ldv, ovc_stream stream) {
+    if (head < 0 || head > 3 || !dbg_f32(logits_t) || !dbg_f32(lse) || !dbg_f32(tgt) || !dbg_f32(w_row) || !dbg_f32(dl_t) || !dbg_f32(dl))
+        return OVC_EINVAL;
+    if (rows <= 0 || V <= 0 || pad < 0 || pad >= V || ldt < rows || ldt > dbg_pad4(rows) || ldv < V || (ldv + 63) / 64 > kDbgGridY)
+        return OVC_EINVAL;
+    if (head == 1 ? loss != nullptr : !dbg_f32(loss)) return OVC_EINVAL;
+    const size_t need = ovc_bw_smoothed_part_floats(rows, V);
+    if (head == 2) {
+        if (!dbg_f32(part) || part_floats < need || !dbg_f32(row_a) || row_b || teacher) return OVC_EINVAL;
+        if (!dbg_prob(param) || (reduction != 0 && reduction != 1) || (param > 0.f && V <= 2)) return OVC_EINVAL;
+    } else if (head == 3) {
+        if (!dbg_f32(part) || part_floats < 2 * need || !dbg_f32(row_a) || !dbg_f32(row_b) || !dbg_f32(teacher)) return OVC_EINVAL;
+        if (!(param >= 0.f && param <= 1.f)) return OVC_EINVAL;
+    } else if (part || row_a || row_b || teacher) {
+        return OVC_EINVAL;
+    }
+    if (const int rc = ovc_device_guard()) return rc;
+    hipStream_t s = ovc_hip_stream(stream);
+    if (head == 0) return ovc_bw_xent(logits_t, ldt, lse, tgt, pad, rows, V, w_row, loss, dl_t, dl, ldv, s);
+    if (head == 1) return ovc_bw_dlogit(logits_t, ldt, lse, tgt, w_row, rows, V, dl_t, dl, ldv, s);
+    if (head == 2) {
+        // the constants of engine.hip's make_smoothed_loss: float64, rounded once
+        const double sm = param, conf = 1.0 - sm, u = sm > 0.0 ? sm / (V - 2) : 0.0;
+        const auto xlogx = [](double v) { return v > 0 ? v * std::log(v) : 0.0; };
+        const SmoothedLoss l{(float)conf, (float)u, (float)(xlogx(conf) + (V - 2) * xlogx(u)), (float)(1.0 / ((double)rows * V)), reduction};
+        return ovc_bw_xent_smoothed(logits_t, ldt, lse, tgt, pad, rows, V, l, part, row_a, w_row, loss, dl_t, dl, ldv, s);
+    }
+    const SoftLoss l{(float)(1.0 - (double)param), param};                     // ovc_forward_backward_distill's two weights
+    return ovc_bw_xent_soft(logits_t, ldt, lse, tgt, pad, rows, V, l, teacher, part, row_a, row_b, w_row, loss, dl_t, dl, ldv, s);
+}
+
+extern "C" int ovc_debug_bw_embedding(const int32_t* tok, int rows, int pad, const float* dx, int d, int V, float* out, ovc_stream stream) {
+    if (!dbg_f32(tok) || !dbg_f32(dx) || !dbg_f32(out) || rows <= 0 || d <= 0 || d > 2048 || V <= 0 || pad < 0 || pad >= V) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_embedding(tok, rows, pad, dx, d, V, out, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_tokens(const int64_t* tokens, int rows, int V, int32_t* tok32, ovc_stream stream) {
+    if (!dbg_i64(tokens) || !dbg_f32(tok32) || rows <= 0 || V <= 0) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    return ovc_bw_tokens(tokens, rows, V, tok32, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_bw_attention(const float* q, long ldq, const float* k, const float* v, long ldkv, const float* dout, long ldo,
+                                      const uint8_t* mask, long mask_b, long mask_r, const float* geometry, int B, int nq, int nk, int h,
+                                      int dk, float* P, float* dS, float* dq, long lddq, float* dk_out, float* dv_out, long lddkv,
+                                      ovc_stream stream) {
+    if (!dbg_f32(q) || !dbg_f32(k) || !dbg_f32(v) || !dbg_f32(dout) || !dbg_f32_or_null(geometry) || !dbg_f32(P) || !dbg_f32(dS) ||
+        !dbg_f32(dq) || !dbg_f32(dk_out) || !dbg_f32(dv_out)) return OVC_EINVAL;
+    if (B <= 0 || nq <= 0 || nk <= 0 || h <= 0 || dk <= 0 || dk > 64 || nk > 8000) return OVC_EINVAL;               // LDS: 128 + 2 nk floats
+    if ((long)B * h * std::max(nq, nk) > 0x7fffffffL / 2) return OVC_EINVAL;
+    const long hk = (long)h * dk;
+    if (ldq < hk || ldkv < hk || ldo < hk || lddq < hk || lddkv < hk) return OVC_EINVAL;
+    if (mask && (mask_b < 0 || mask_r < 0 || (mask_r != 0 && mask_r < nk))) return OVC_EINVAL;
+    if (const int rc = ovc_device_guard()) return rc;
+    AttnBwdArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldkv = ldkv; a.dout = dout; a.ldo = ldo;
+    a.mask = mask; a.mask_b = mask_b; a.mask_r = mask_r;
+    a.B = B; a.nq = nq; a.nk = nk; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+    a.P = P; a.dS = dS; a.dq = dq; a.lddq = lddq; a.dk_out = dk_out; a.dv_out = dv_out; a.lddkv = lddkv;
+    a.geometry = geometry;
+    return ovc_bw_attention(a, ovc_hip_stream(stream));
 }

@@ -23,9 +23,12 @@
     a = wave_sum(a) / d; b = wave_sum(b) / d;
     for (int c = lane; c < d; c += 64) {
         const float xh = (x[o + c] - mean) * rstd, g = dy[o + c];
-        const float gx = rstd * (gamma[c] * g - a - xh * b);
-        dx[o + c] = gx;
+        dx[o + c] = rstd * (gamma[c] * g - a - xh * b);
         prod[o + c] = g * xh;
         dyc[o + c] = g;
-        dproj[o + c] = ovc_dropout_keep(seed, drop.site, (uint64_t)(OVC_BW_MASK_ROW) * (uint64_t)drop.cols + (uint64_t)c, drop.thr) ? gx * drop.scale : 0.f;
     }
+    // The masked copy in a loop of its own, from the dx this lane stored.  With dproj formed inside the loop above, the compiler
+    // contracted gamma g - a - xh b otherwise than in bw_layer_norm_kernel (whose unrolled rounds fuse gamma g - a and whose odd last
+    // round rounds the product first), and dx missed the plain kernel's bits at every width with an odd number of 64-column rounds.
+    for (int c = lane; c < d; c += 64)
+        dproj[o + c] = ovc_dropout_keep(seed, drop.site, (uint64_t)(OVC_BW_MASK_ROW) * (uint64_t)drop.cols + (uint64_t)c, drop.thr) ? dx[o + c] * drop.scale : 0.f;

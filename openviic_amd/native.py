@@ -343,6 +343,24 @@ SIGNATURES = {
     "ovc_debug_meshed_mix": (c_int, [c_void_p, c_void_p, c_int, c_long, c_float, c_void_p, c_void_p, c_void_p]),
     "ovc_debug_leaky_residual": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ovc_debug_sigmoid_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "ovc_debug_bw_transpose": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_int, c_void_p]),
+    "ovc_debug_bw_rowsum": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "ovc_debug_bw_colsum": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ovc_debug_bw_layer_norm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "ovc_debug_bw_relu": (c_int, [c_void_p, c_void_p, c_int, c_float, c_long, c_void_p]),
+    "ovc_debug_bw_leaky": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_long, c_void_p]),
+    "ovc_debug_bw_sum": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p]),
+    "ovc_debug_bw_sum_levels": (c_int, [c_void_p, c_void_p, c_int, c_long, c_long, c_void_p, c_void_p]),
+    "ovc_debug_bw_accumulate": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    "ovc_debug_bw_loss_part_floats": (c_size_t, [c_int, c_int]),
+    "ovc_debug_bw_loss": (c_int, [c_int, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
+                                  c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "ovc_debug_bw_embedding": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ovc_debug_bw_tokens": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ovc_debug_bw_attention": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_long,
+                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                       c_void_p, c_long, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -383,7 +401,11 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric",
                  "ovc_debug_box_relation_backward_floats", "ovc_debug_box_relation_backward", "ovc_debug_attention_backward",
                  "ovc_train_aoa_workspace_bytes", "ovc_forward_backward_aoa", "ovc_train_aoa_beams_workspace_bytes",
-                 "ovc_sequence_backward_aoa", "ovc_debug_aoa_gate_backward")
+                 "ovc_sequence_backward_aoa", "ovc_debug_aoa_gate_backward",
+                 "ovc_debug_bw_transpose", "ovc_debug_bw_rowsum", "ovc_debug_bw_colsum", "ovc_debug_bw_layer_norm", "ovc_debug_bw_relu",
+                 "ovc_debug_bw_leaky", "ovc_debug_bw_sum", "ovc_debug_bw_sum_levels", "ovc_debug_bw_accumulate",
+                 "ovc_debug_bw_loss_part_floats", "ovc_debug_bw_loss", "ovc_debug_bw_embedding", "ovc_debug_bw_tokens",
+                 "ovc_debug_bw_attention")
 
 _lib = None
 

@@ -897,6 +897,56 @@ int ovc_debug_beam_forced_update(const float* logits, const int32_t* hist, const
                                  size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out,
                                  float* row_lsum_out, ovc_stream stream);
 
+/* Length-normalised beam search: the search of ovc_beam_search with a length penalty and a word reward inside the selection
+ * (appended to ABI 8; no struct changes).  The plain search ranks by the sum of log-probabilities, so a beam that ends early keeps
+ * its score while its live rivals lose a little at every step, and short captions win.  The rule (openviic_amd/length.py mirrors
+ * it in numpy):
+ * State and length.  A beam carries its raw running score `raw`, exactly ovc_beam_search's, and a length L.  A live candidate
+ * offered at step t has L = t + 1 (an <eos> counts).  A frozen beam keeps the L it had when it emitted <eos>; it offers word 0 at
+ * its raw score and the usual -999 fillers for the other words, all at its own L.  A beam still alive after the last step has
+ * L = max_len.
+ * Tables.  inv, bonus: max_len floats each in HOST memory, entry L - 1 for L = 1 .. max_len, built by the caller in float64 and
+ * rounded once: inv[L] = 1 / lp(L) with lp(L) = L^alpha ("avg") or ((5 + L) / 6)^alpha ("wu"), alpha finite, |alpha| <= 8;
+ * bonus[L] = gamma L, gamma finite, |gamma| <= 100.  The call copies both into its workspace in stream order, outside any
+ * captured graph; they must stay valid until the stream has passed that copy.
+ * Key.  key = fp32(fp32(raw + bonus[L]) * inv[L]): the sum is rounded, then the product; never a fused multiply-add.
+ * Order.  Candidates are ranked by (key descending, raw descending, flat index row * V + word ascending); a NaN candidate beats
+ * nothing.  A total order.  All live candidates of an image share L at a given step, and raw -> key is monotone non-decreasing
+ * for one L, so among them this is the plain search's order -- rounding the key can never reorder two live candidates; what changes
+ * is where frozen beams and their fillers stand against live ones.
+ * Carried state.  running carries raw, never the key.  Parent, history, alive flags, the ancestor table and the next input rows
+ * are written as by the plain step; the length follows the parent.  logp_out / all_logp_out stay the model's own.
+ * Final order.  All k slots by (key, raw, lower slot), each slot's key at its own L (a NaN key behind every number); the first
+ * out_size are returned.  score_out [B][out_size] float and len_out [B][out_size] int32 (device) take each returned caption's key
+ * and length.
+ * Consequences.  alpha = 0, gamma = 0 (inv all 1, bonus all 0) gives key = raw: ovc_beam_search's results.  With alpha > 0 a
+ * frozen beam of length L0 < t + 1 loses to a live candidate of equal (negative) raw score; with alpha < 0 the reverse holds.
+ * ovc_beam_search_normalized: plain launches, all_logp_out as ovc_beam_search.  ovc_beam_search_normalized_graph: one captured
+ * graph from the second call; the tables are no part of its key: one graph serves every (alpha, gamma, form) of a shape.
+ * Workspace: ovc_beam_search_normalized_workspace_bytes(m, B, N, k, return_probs) (ovc_workspace_bytes' layout, the tables, the
+ * per-slot lengths of both state buffers and the ordered keys / lengths behind it; 0: out of scope).
+ * OVC_EINVAL, nothing launched: a null table, score_out or len_out; an inv entry that is not finite and positive; a bonus entry
+ * that is not finite; precision != 0; a vocabulary of more than 16 384 words; and everything ovc_beam_search refuses.
+ * Not covered: normalisation together with a ban set, a prefix, groups, forced words, dropout, the early-exit forms, an ensemble,
+ * sampling or the split-precision modes.
+ * ovc_debug_beam_normalized_update: test entry, ONE step of the production kernel on the inputs of
+ * ovc_debug_beam_constrained_update (width = 1 at t = 0, else k) plus len_in [B*width] int32 (device; read for frozen rows) and
+ * the two tables of T floats (HOST memory); additionally returns len_out [B][k] int32 and key_out [B][k] float (device), the
+ * winners' lengths and keys.  scratch: ovc_debug_beam_normalized_update_bytes. */
+size_t ovc_beam_search_normalized_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs);
+int ovc_beam_search_normalized(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                               const float* inv, const float* bonus, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                               float* logp_out, float* score_out, int32_t* len_out, float* all_logp_out, ovc_stream stream);
+int ovc_beam_search_normalized_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                     const float* inv, const float* bonus, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                     float* logp_out, float* score_out, int32_t* len_out, ovc_stream stream);
+size_t ovc_debug_beam_normalized_update_bytes(int B, int width, int V, int k, int T);
+int ovc_debug_beam_normalized_update(const float* logits, const int32_t* hist, const float* running, const float* alive,
+                                     const int32_t* len_in, int B, int width, int V, int k, int T, int t, int eos, const float* inv,
+                                     const float* bonus, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
+                                     float* running_out, float* row_max_out, float* row_lsum_out, int32_t* len_out, float* key_out,
+                                     ovc_stream stream);
+
 /* Ensemble beam search: ONE search over the mean of the log-probabilities of M models (the meshed-memory authors'
  * TransformerEnsemble).  Members m = 0..M-1, 1 <= M <= OVC_MAX_ENSEMBLE, read the same features (and the call's boxes, where a
  * member's encoder takes boxes); at every step each member runs its own decoder step on the SAME beams -- the same words, the same

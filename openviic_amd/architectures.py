@@ -19,6 +19,7 @@ import torch
 from . import constraints as _constraints
 from . import diverse as _diverse
 from . import forced as _forced
+from . import length as _length
 from . import prefix as _prefix
 from . import distill as _distill
 from . import dropout as _dropout
@@ -630,10 +631,10 @@ class BaseTransformer(Module):
         applies after the log-softmax: ``log_probs`` / ``all_log_probs`` stay the model's own, so the gradient of ``log_probs``
         is the plain search's.  The defaults are the plain call, bit for bit.  Refused by name before any launch or draw: a bad
         option; active constraints with ``fused=False``, ``dropout=True``, an early-exit form, a precision other than 'f32' or a
-        vocabulary of more than 16 384 words; and length penalty, repetition penalty and ``prefix_allowed_tokens_fn``, which the
-        engine does not have, and ``forced_words``, ``num_beam_groups`` / ``diversity_penalty``: forced words (lexical constraints)
-        and diverse beam search are methods of their own, ``forced_beam_search`` and ``diverse_beam_search``, and the keyword
-        forms stay refused.
+        vocabulary of more than 16 384 words; and a repetition penalty and ``prefix_allowed_tokens_fn``, which the engine does not
+        have, and ``length_penalty``, ``forced_words``, ``num_beam_groups`` / ``diversity_penalty``: the length penalty, forced
+        words (lexical constraints) and diverse beam search are methods of their own, ``normalized_beam_search``,
+        ``forced_beam_search`` and ``diverse_beam_search``, and the keyword forms stay refused.
 
         ``prefix`` (fused only; ``ovc_beam_search_prefix``; the rule is stated in ``include/ovc.h`` and
         mirrored by ``openviic_amd.prefix``): an int64 tensor ``(B, P)``, ``0 <= P <= max_len - 1``.  Image ``b`` emits
@@ -808,6 +809,46 @@ class BaseTransformer(Module):
         out = eng.forced_beam_search(feats, boxes, batch_size, k, table.tolist(), out_size=out_size, return_probs=return_probs)
         result = (out[0], out[1]) + ((out[3],) if return_probs else ())
         return result + ((out[2].long(),) if return_met else ())
+
+    def normalized_beam_search(self, input_features, batch_size: int, beam_size: int, length_penalty=1.0, length_form="avg",
+                               word_reward=0.0, out_size=1, return_probs=False, return_scores=False, **kwargs):
+        """Length-normalised beam search on the HIP engine (``ovc_beam_search_normalized``; the rule is stated
+        in ``include/ovc.h`` and mirrored by ``openviic_amd.length``).  The plain search ranks by the sum of log-probabilities, so a
+        beam that ends early keeps its score while its live rivals lose a little at every step; here every candidate is ranked,
+        inside the selection step, by ``key = (raw + word_reward * L) / lp(L)`` with ``L`` its length in words (``<eos>`` counts) and
+        ``lp(L) = L ** length_penalty`` (``length_form="avg"``) or ``((5 + L) / 6) ** length_penalty`` (``"wu"``, Wu et al. 2016),
+        ties by the raw score, then by the lower index.  The beams carry the raw score; a finished beam keeps the length it ended
+        with.  Returns ``(ids [B, out_size, T], log_probs [B, out_size, T])`` shaped as ``beam_search`` returns them, ordered by the
+        key, plus ``all_log_probs [B, beam_size, T, V]`` with ``return_probs`` and ``(scores [B, out_size] fp32, lengths [B, out_size]
+        int64)`` with ``return_scores`` -- the key each returned caption was ranked by, and its length -- in this order.
+        ``log_probs`` / ``all_log_probs`` are the model's own; the result is plain tensors without gradient.
+        ``length_penalty=0, word_reward=0`` is ``beam_search``: the same launches, graph and bits.
+
+        Refused by name before any launch and any random draw: a bad ``length_form``, ``length_penalty`` (not a Python number, NaN,
+        infinite or outside [-8, 8]) or ``word_reward`` (likewise, [-100, 100]); ``beam_size`` outside 1..8; ``out_size`` outside
+        ``1..beam_size``; ``fused=False`` or any other keyword (the host loop has no lengths; constraints, a prefix, dropout, the
+        early-exit forms and sampling do not combine with the normalisation); a precision other than 'f32'; more than 16 384 words;
+        and a model in ``train()`` mode with gradients enabled (no SCST through a normalised search: call ``eval()`` or use
+        ``no_grad``)."""
+        for name in kwargs:
+            if name == "fused":
+                raise engine.native.OvcError("normalized_beam_search(fused=...): there is no such keyword -- the search runs on the "
+                                             "engine only, the host loop has no lengths")
+            raise engine.native.OvcError("normalized_beam_search({}=...) is not covered -- the normalisation combines with nothing but "
+                                         "out_size, return_probs and return_scores".format(name))
+        k, alpha, form, gamma, out_size = _length.check(length_penalty, length_form, word_reward, beam_size, out_size,
+                                                        self.decoder.fc.out_features)
+        eng = self._fused_engine()
+        eng.check_normalized(k, alpha, form, gamma, out_size)
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise engine.native.OvcError("normalized_beam_search: the model is in train() mode with gradients enabled -- there is no "
+                                         "SCST through a normalised search; call model.eval() or use torch.no_grad()")
+        feats, boxes = self._engine_inputs(input_features)
+        out = eng.normalized_beam_search(feats, boxes, batch_size, k, alpha, form, gamma, out_size=out_size, return_probs=return_probs,
+                                         return_scores=return_scores)
+        ids, logp = (out[0].squeeze(1), out[1].squeeze(1)) if out_size == 1 else out[:2]       # as beam_search shapes them
+        result = (ids, logp) + ((out[4],) if return_probs else ())
+        return result + ((out[2], out[3].long()) if return_scores else ())
 
     def sample(self, input_features, batch_size: int, n_samples: int, generator=None, return_probs=False, temperature=1.0,
                top_k=None, top_p=None, no_repeat_ngram_size=0, min_length=0, banned_words=None):

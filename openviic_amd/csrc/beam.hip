@@ -307,6 +307,40 @@ __global__ __launch_bounds__(kFusedThreads) void beam_forced_update_kernel(BeamU
                                                                            int C, int pad) {
 #include "bodies/beam_forced_update.inc"
 }
+// Length-normalised selection (ovc_beam_search_normalized, include/ovc.h: the rule).  A candidate of raw score `raw` and length L is
+// ranked by key = fp32(fp32(raw + bonus[L]) * inv[L]): the sum is rounded, then the product (the intrinsics keep the two roundings
+// whatever the contraction mode), then by the raw score, then by the lower flat index.  A NaN key beats nothing.
+__device__ __forceinline__ float length_key(float raw, float bonus, float inv) { return __fmul_rn(__fadd_rn(raw, bonus), inv); }
+
+__device__ __forceinline__ bool better3(float key, float v, int idx, float bkey, float bv, int bidx) {
+    return key > bkey || (key == bkey && (v > bv || (v == bv && idx < bidx)));
+}
+
+struct Cand3 { float k, v; int idx; };
+
+__device__ __forceinline__ Cand3 wave_best3(Cand3 c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ok = __shfl_xor(c.k, off, 64);
+        const float ov = __shfl_xor(c.v, off, 64);
+        const int oi = __shfl_xor(c.idx, off, 64);
+        if (better3(ok, ov, oi, c.k, c.v, c.idx)) { c.k = ok; c.v = ov; c.idx = oi; }
+    }
+    return c;
+}
+
+// One more instance of the fused selection: the pieces, the lists and the bookkeeping are the plain kernel's; every row has one length
+// (t + 1 where it is live, its own where it is frozen), so raw -> key is monotone per row and the block bounds, the row's k-th-best
+// bound, the hot-block threshold, the frozen rows' offers, the ranking and the exhaustive rounds all work on keys.  The running score
+// it carries is the raw one; the winners' lengths follow their parents into nl.len_out.  The tables are read from device memory, so
+// one captured graph serves every (alpha, gamma, form) of a shape.  Its own body: the other instances' text does not change.  LDS: the
+// plain instance's 14 152 bytes + 4 KB of survivor keys + 128 bytes of row lengths, table entries and winner keys.  Integer LDS
+// atomics only where the lists are appended to, no float atomics.
+__global__ __launch_bounds__(kFusedThreads) void beam_normalized_update_kernel(BeamUpdateArgs p, const float* __restrict__ stats, int nblk,
+                                                                               int stats_ld, const float* __restrict__ running_in,
+                                                                               long ld_row, long ld_word, BeamLength nl) {
+#include "bodies/beam_normalized_update.inc"
+}
 #undef FUSED_SELECT_ROW
 #undef FUSED_SELECT_LOGP
 
@@ -508,6 +542,14 @@ __global__ __launch_bounds__(64) void beam_finalize_forced_kernel(BeamFinalArgs 
 #include "bodies/beam_finalize_forced.inc"
 }
 
+// The length-normalised search's final ordering (include/ovc.h, ovc_beam_search_normalized): every slot's key at its own length, then
+// (key, raw score, lower slot); score_out / len_out [B][k] take every slot's key and length in that order.  An instance of its own:
+// beam_finalize_kernel's text does not change.
+__global__ __launch_bounds__(64) void beam_finalize_normalized_kernel(BeamFinalArgs p, BeamLength nl, float* __restrict__ score_out,
+                                                                      int32_t* __restrict__ len_out) {
+#include "bodies/beam_finalize_normalized.inc"
+}
+
 // all_out[b, o, t, :] = all_buf[t][b][order[b][o]][:] (t = 0: the single live beam)   (beam_search.py:68-72,103-107)
 __global__ __launch_bounds__(256) void beam_gather_all_kernel(const float* __restrict__ all_buf, const int* __restrict__ order,
                                                               int B, int k, int T, int V, float* __restrict__ all_out) {
@@ -602,7 +644,7 @@ int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, co
                                  hipStream_t stream) {
     const BeamConstraints& cons = o.cons;
     const BeamPrefix& pre = o.prefix;
-    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0 && o.forced_C == 0;
+    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0 && o.forced_C == 0 && !o.length.active();
     if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || (!plain && (p.alive_count || o.gate))) return OVC_EINVAL;
     if (!plain && (p.T < 1 || p.t < 0 || p.t >= p.T)) return OVC_EINVAL;
     const dim3 grid(B), block(kFusedThreads);
@@ -630,6 +672,12 @@ int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, co
         if (p.width != (p.t == 0 ? 1 : p.k)) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_forced_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.forced, o.forced_C, o.pad);
+    } else if (o.length.active()) {
+        // the rows are the image's one row at step 0 and its k slots later; the tables hold p.T entries, indexed with a length the
+        // kernel clamps to 1..p.T
+        if (!o.length.len_in || !o.length.len_out || !o.length.bonus || p.V < p.k || p.width != (p.t == 0 ? 1 : p.k)) return OVC_EINVAL;
+        hipLaunchKernelGGL(beam_normalized_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                           f.ld_word, o.length);
     } else if (o.gate)
         hipLaunchKernelGGL(beam_fused_update_kernel_gated, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.gate);
@@ -810,6 +858,16 @@ int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream) 
 int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_out, int B, hipStream_t stream) {
     if (B <= 0 || !met_out || !p.order_out || !ovc_beam_forced_ok(p.k, C) || p.out_size < 1 || p.out_size > p.k) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_finalize_forced_kernel, dim3(B), dim3(64), 0, stream, p, p.k >> C, met_out);
+    OVC_RETURN_IF_LAUNCH_FAILED();
+    return OVC_OK;
+}
+
+int ovc_beam_finalize_normalized_launch(const BeamFinalArgs& p, const BeamLength& n, float* score_out, int32_t* len_out, int B,
+                                        hipStream_t stream) {
+    if (B <= 0 || !n.len_in || !n.inv || !n.bonus || !score_out || !len_out || !p.order_out || p.k < 1 || p.k > kMaxK || p.T < 1 ||
+        p.out_size < 1 || p.out_size > p.k)
+        return OVC_EINVAL;
+    hipLaunchKernelGGL(beam_finalize_normalized_kernel, dim3(B), dim3(64), 0, stream, p, n, score_out, len_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -299,6 +299,14 @@ struct BeamPrefix {
 bool ovc_beam_diversity_ok(int k, int G, float lambda);
 // The forced-word search's sizes (include/ovc.h, ovc_beam_search_forced): 1 <= C <= OVC_MAX_FORCED, 2^C dividing k <= OVC_MAX_BEAM.
 bool ovc_beam_forced_ok(int k, int C);
+// The length-normalised search's state and tables (include/ovc.h, ovc_beam_search_normalized), in DEVICE memory: read by the kernel,
+// so one captured graph serves every (alpha, gamma, form) of a shape.
+struct BeamLength {
+    const int32_t* len_in; int32_t* len_out;        // [B*width] / [B*k]: the length a frozen row carries, the winners' lengths
+    const float* inv; const float* bonus;           // [T]: entry L - 1 is 1 / lp(L) and gamma * L for L = 1..T
+    float* key_out;                                 // [B*k] or nullptr: the key every winner was ranked by
+    bool active() const { return inv != nullptr; }
+};
 // The options of a step's fused selection, as the search call holds them; all zero: the plain selection.
 struct FusedSelectOptions {
     BeamConstraints cons;           // active(): a per-row ban set (p.hist_in holds the rows' histories)
@@ -309,10 +317,11 @@ struct FusedSelectOptions {
     const int32_t* forced; int forced_C, pad;   // forced_C != 0: the forced-word instance -- the table [B][forced_C] in DEVICE memory
                                     // (ids in [0, V), the caller's to check), 2^forced_C banks of k >> forced_C slots, and the
                                     // <pad> id an empty slot takes; p.width is 1 at p.t == 0, else p.k
+    BeamLength length;              // active(): the length-normalised instance -- candidates ranked by (key, raw score, flat index)
 };
 // Selection + update of a step, one launch: the constrained instance, else the prefix one, else the diverse one, else the plain
 // one.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count and the gate go with the plain instance only.  (Forced words:
-// behind the diverse instance.)
+// behind the diverse instance; the length-normalised instance: behind that.)
 int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const FusedSelectOptions& o, int B,
                                  hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'
@@ -380,6 +389,11 @@ int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream);
 // The final ordering of a search with forced words: (non-empty, met words descending, score descending, slot ascending); met_out
 // [B][k] int32 takes the bank of every slot in that order, -1 for an empty slot.  p.order_out is required, p.steps_run is not read.
 int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_out, int B, hipStream_t stream);
+// The final ordering of a length-normalised search: every slot's key at its own length, then (key descending, raw score descending,
+// slot ascending), a NaN key last; score_out / len_out [B][k] take every slot's key and length in that order.  n.len_in: the state's
+// lengths [B*k]; n.len_out / n.key_out are not read.  p.order_out is required, p.steps_run is not read.
+int ovc_beam_finalize_normalized_launch(const BeamFinalArgs& p, const BeamLength& n, float* score_out, int32_t* len_out, int B,
+                                        hipStream_t stream);
 // The final ordering of a gated search: the number of steps that ran, S, is read from the device -- S = 1 + the first i < T - 1
 // with alive_count[i] == 0, else T (step t >= 1 ran iff alive_count[t - 1] != 0) -- and the state is read from buf[S & 1] (dead
 // steps swap no buffers).  Positions S..T-1 are emitted as word 0 / log-prob 0, as BeamFinalArgs::steps_run does; block 0 writes

@@ -149,6 +149,9 @@ struct Workspace {
                                                   // captured body)
     int32_t* forced_words; int32_t* forced_met;   // ovc_beam_search_forced: the call's table [B][C] (refreshed the same way) and the
                                                   // final ordering's banks [B][k]
+    // ovc_beam_search_normalized: the call's tables [max_len] each (refreshed the same way), the per-slot lengths of the two state
+    // buffers [B*k] and the final ordering's keys / lengths [B][k]
+    float* norm_inv; float* norm_bonus; int32_t* norm_len[2]; float* norm_score; int32_t* norm_len_out;
     // teacher-forced forward (a ForwardCall; rows = B*S*T): the self-attention mask [B*S][T][T], the target words, the logit of
     // each row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -1045,6 +1048,10 @@ struct SearchCall {
     // sizer or predicate states forced_C alone.
     int forced_C; const int32_t* forced_words; int32_t* met_out;
     bool forced() const { return forced_C != 0; }
+    // Length-normalised search (ovc_beam_search_normalized): the caller's two tables of max_len floats in HOST memory (entry L - 1:
+    // 1 / lp(L) and gamma * L), copied to the workspace outside any captured body, and the caller's score_out / len_out
+    // [B][out_size].  A sizer or predicate sets `normalized` alone.
+    bool normalized; const float* norm_inv; const float* norm_bonus; float* score_out; int32_t* len_out;
     // The rows of an image at step t.  Step 0 has one row per image; a diverse search runs it once per group (the same <bos> row, the
     // same bits), so that every group has a first cache row and a first ancestor of its own and is a search of k / groups beams
     // from its first step on (a search of one step, T = 1, has no later step to prepare: one row).
@@ -1070,7 +1077,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c);
 // nothing else in the call.
 bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
     if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
-    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() || c.forced() ||
+    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() || c.forced() || c.normalized ||
         (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
         return false;
     SearchCall alone = c;
@@ -1115,6 +1122,12 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                        c.prefixed() || c.diverse() || c.ens_M != 0 || (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
                        !ovc_beam_forced_ok(c.k, c.forced_C)))
         return false;
+    // length normalisation: fp32, the fused vocabulary tail, beams (no draw), nothing else in the call, plain launches or the
+    // whole-search graph
+    if (c.normalized && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.has_options || c.plan || c.constrained() ||
+                         c.prefixed() || c.diverse() || c.forced() || c.ens_M != 0 ||
+                         (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
+        return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
 }
@@ -1139,6 +1152,14 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
         Bump a{reinterpret_cast<char*>(base), w.bytes};
         w.forced_words = a.take<int32_t>((size_t)c.B * c.forced_C);
         w.forced_met = a.take<int32_t>((size_t)c.B * c.k);
+        w.bytes = (a.off + 255) & ~(size_t)255;
+    }
+    if (c.normalized) {                           // likewise behind ovc_beam_search's layout
+        Bump a{reinterpret_cast<char*>(base), w.bytes};
+        const size_t R = (size_t)c.B * c.k;
+        w.norm_inv = a.take<float>((size_t)m->max_len); w.norm_bonus = a.take<float>((size_t)m->max_len);
+        w.norm_len[0] = a.take<int32_t>(R); w.norm_len[1] = a.take<int32_t>(R);
+        w.norm_score = a.take<float>(R); w.norm_len_out = a.take<int32_t>(R);
         w.bytes = (a.off + 255) & ~(size_t)255;
     }
     return w;
@@ -1457,12 +1478,14 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_shaped_update_launch(bu, tail, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
-        else if (c.constrained() || c.prefixed() || c.diverse() || c.forced() || !(debug_skip() & 8)) {
+        else if (c.constrained() || c.prefixed() || c.diverse() || c.forced() || c.normalized || !(debug_skip() & 8)) {
             // the one branch of a beam step: the call's options pick the instance -- a per-row ban set, the staged prefix table, the
-            // groups under the Hamming penalty, the banks of the staged forced words, else the plain selection or its gated form
+            // groups under the Hamming penalty, the banks of the staged forced words, the staged length tables, else the plain selection
+            // or its gated form
             const BeamPrefix pre = c.prefixed() ? BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P} : BeamPrefix{};
             FusedSelectOptions opt{c.cons, pre, c.groups, c.diversity, e.gate};
             if (c.forced()) { opt.forced = w.forced_words; opt.forced_C = c.forced_C; opt.pad = m->pad_idx; }
+            if (c.normalized) opt.length = BeamLength{w.norm_len[cur], w.norm_len[nxt], w.norm_inv, w.norm_bonus, nullptr};
             RUN(ovc_beam_fused_select_launch(bu, tail, w.running[cur], opt, B, s));
         }
         if (return_probs) {   // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
@@ -1483,7 +1506,7 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
-    if (c.prefixed() || c.diverse() || c.forced()) return OVC_EINVAL;   // search_ok: the fused tail; the two-pass pair knows none of these
+    if (c.prefixed() || c.diverse() || c.forced() || c.normalized) return OVC_EINVAL;   // search_ok: the fused tail; the two-pass pair knows none of these
     RUN(ovc_beam_select_launch(bs, B, s, e.gate));
     RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
@@ -1587,8 +1610,13 @@ BeamFinalArgs final_args(const Workspace& w, int parity, const SearchCall& c, in
     return bf;
 }
 
-// The final ordering of a search: by total score, or a search with forced words by its own key (it also leaves the banks in w.forced_met).
-int finalize_search(const BeamFinalArgs& bf, const Workspace& w, const SearchCall& c, hipStream_t s) {
+// The final ordering of a search: by total score, or a search with forced words by its own key (it also leaves the banks in w.forced_met),
+// or a length-normalised search by its keys (it also leaves them and the lengths in w.norm_score / w.norm_len_out).  parity: the state
+// buffer bf reads.
+int finalize_search(const BeamFinalArgs& bf, const Workspace& w, const SearchCall& c, int parity, hipStream_t s) {
+    if (c.normalized)
+        return ovc_beam_finalize_normalized_launch(bf, BeamLength{w.norm_len[parity], nullptr, w.norm_inv, w.norm_bonus, nullptr}, w.norm_score,
+                                                   w.norm_len_out, c.B, s);
     return c.forced() ? ovc_beam_finalize_forced_launch(bf, c.forced_C, w.forced_met, c.B, s) : ovc_beam_finalize_launch(bf, c.B, s);
 }
 
@@ -1600,7 +1628,7 @@ int issue_search_body(Engine& e, Workspace& w, const SearchCall& c) {
     TRY(issue_search_prologue(e, w, c));
     for (int t = 0; t < T; ++t) TRY(run_decode_step(e, w, c, t));
     if (c.form != SearchForm::Graph) return OVC_OK;
-    return finalize_search(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), w, c, e.stream);
+    return finalize_search(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), w, c, T & 1, e.stream);
 }
 
 // A sizer builds the SearchCall its entry point will build (out_size plays no part in the layout).
@@ -1697,6 +1725,7 @@ enum class GraphKind {
                         // in the workspace)
     DiverseSearch,      // ovc_beam_search_diverse_graph with more than one group (as Search; G and the bits of lambda in the hash)
     ForcedSearch,       // ovc_beam_search_forced_graph (as Search; C in the hash, the word table's contents in the workspace)
+    NormalizedSearch,   // ovc_beam_search_normalized_graph (as Search; the tables' contents in the workspace: the tag is all the key adds)
     ForwardMaps,        // a ForwardCall with maps, ovc_attention_maps (forward_graph_key: k = T, out_size = S): the scoring body
                         // over B*S*T rows plus the map launches
 };
@@ -1878,6 +1907,8 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
         const int C = c.forced_C;
         return GraphKey{GraphKind::ForcedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&C, sizeof(C)), workspace, c.B, c.N, c.k, c.out_size};
     }
+    if (c.normalized)         // never the tables: they are read from the workspace, refreshed per call
+        return GraphKey{GraphKind::NormalizedSearch, hash_bytes(m, sizeof(*m)), workspace, c.B, c.N, c.k, c.out_size};
     const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
     return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
 }
@@ -1985,6 +2016,7 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out || (c.sample && !c.sample_seed)) return OVC_EINVAL;
     if (c.prefixed() && (!c.prefix_ids || !c.prefix_len)) return OVC_EINVAL;
     if (c.forced() && (!c.forced_words || !c.met_out)) return OVC_EINVAL;
+    if (c.normalized && (!c.norm_inv || !c.norm_bonus || !c.score_out || !c.len_out)) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
@@ -2010,6 +2042,10 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
         return OVC_ELAUNCH;
     if (c.forced() &&                              // the word table, refreshed the same way: a replayed graph reads this call's words
         hipMemcpyAsync(w.forced_words, c.forced_words, sizeof(int32_t) * c.B * c.forced_C, hipMemcpyHostToDevice, e.stream) != hipSuccess)
+        return OVC_ELAUNCH;
+    if (c.normalized &&                            // the length tables, refreshed the same way: a replayed graph reads this call's
+        (hipMemcpyAsync(w.norm_inv, c.norm_inv, sizeof(float) * T, hipMemcpyHostToDevice, e.stream) != hipSuccess ||
+         hipMemcpyAsync(w.norm_bonus, c.norm_bonus, sizeof(float) * T, hipMemcpyHostToDevice, e.stream) != hipSuccess))
         return OVC_ELAUNCH;
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
     for (int i = 1; i < c.ens_M; ++i) {            // every member reads the call's features, and its boxes where its encoder takes them
@@ -2048,11 +2084,18 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     } else {                                       // the state the last issued step left: its parity, and the positions never written
         BeamFinalArgs bf = final_args(w, steps_run & 1, c, T, c.ids_out, c.logp_out);
         bf.steps_run = steps_run < T ? steps_run : 0;
-        TRY(finalize_search(bf, w, c, e.stream));
+        TRY(finalize_search(bf, w, c, steps_run & 1, e.stream));
     }
     // the banks of the returned captions: the first out_size entries of every image's final order (out_size == k: one block)
     if (c.forced() && hipMemcpy2DAsync(c.met_out, sizeof(int32_t) * c.out_size, w.forced_met, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size,
                                        c.B, hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
+        return OVC_ELAUNCH;
+    // the keys and lengths of the returned captions, likewise
+    if (c.normalized &&
+        (hipMemcpy2DAsync(c.score_out, sizeof(float) * c.out_size, w.norm_score, sizeof(float) * c.k, sizeof(float) * c.out_size, c.B,
+                          hipMemcpyDeviceToDevice, e.stream) != hipSuccess ||
+         hipMemcpy2DAsync(c.len_out, sizeof(int32_t) * c.out_size, w.norm_len_out, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size, c.B,
+                          hipMemcpyDeviceToDevice, e.stream) != hipSuccess))
         return OVC_ELAUNCH;
     if (c.all_logp_out) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, c.B, c.k, T, m->vocab, c.all_logp_out, e.stream));
     if (c.steps_run_out) *c.steps_run_out = steps_run;
@@ -2157,6 +2200,9 @@ struct StepTest {
     int members; int32_t* hot_out;                                                 // the ensemble kernel, and its hot-block count
     float* lp_out;
     const int32_t* forced;                                                         // opt.forced_C != 0: the table [B][forced_C], HOST memory
+    // the length-normalised instance (norm_inv != nullptr): the tables [T] in HOST memory, the rows' lengths [B*width] and the
+    // winners' lengths and keys [B][k] in device memory
+    const float* norm_inv; const float* norm_bonus; const int32_t* len_in; int32_t* len_out; float* key_out;
 };
 
 static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
@@ -2194,6 +2240,13 @@ static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
         int32_t* words_dev = a.take<int32_t>((size_t)B * c.opt.forced_C);
         if (hipMemcpyAsync(words_dev, c.forced, sizeof(int32_t) * B * c.opt.forced_C, hipMemcpyHostToDevice, s) != hipSuccess) return OVC_ELAUNCH;
         c.opt.forced = words_dev;
+    }
+    if (c.norm_inv) {                              // the length tables come in HOST memory and are staged likewise
+        float* inv_dev = a.take<float>((size_t)T); float* bonus_dev = a.take<float>((size_t)T);
+        if (hipMemcpyAsync(inv_dev, c.norm_inv, sizeof(float) * T, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(bonus_dev, c.norm_bonus, sizeof(float) * T, hipMemcpyHostToDevice, s) != hipSuccess)
+            return OVC_ELAUNCH;
+        c.opt.length = BeamLength{c.len_in, c.len_out, inv_dev, bonus_dev, c.key_out};
     }
     BeamUpdateArgs& bu = en.p;
     bu.alive_in = c.alive; bu.alive_out = alive_out; bu.running_out = c.running_out;
@@ -2462,6 +2515,74 @@ extern "C" int ovc_debug_beam_forced_update(const float* logits, const int32_t* 
     if (scratch_bytes < ovc_debug_beam_forced_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
     StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
     c.opt.forced_C = C; c.opt.pad = pad; c.forced = forced;
+    return run_step_test(c, scratch, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Length-normalised search (include/ovc.h: the rule).  Candidates ranked by key = (raw + bonus[L]) * inv[L], then the raw score, then
+// the flat index; the running score stays raw.  A call of its own: whatever the tables hold, the normalised instance runs (neutral
+// tables give the plain search's results by the rule; the Python layer routes them to the plain call).
+// ---------------------------------------------------------------------------------------------
+// The two tables of n floats in HOST memory as the rule takes them: every inv finite and positive, every bonus finite.
+static bool length_tables_ok(const float* inv, const float* bonus, int n) {
+    if (!inv || !bonus || n < 1) return false;
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(inv[i]) || !(inv[i] > 0.0f) || !std::isfinite(bonus[i])) return false;
+    return true;
+}
+
+extern "C" size_t ovc_beam_search_normalized_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs) {
+    SearchCall c{B, N, k, k};
+    float sized_probs = 0.f;
+    if (return_probs) c.all_logp_out = &sized_probs;
+    if (!model_ok(m)) return 0;
+    c.normalized = true;
+    return search_ok(m, c) && m->vocab >= k ? carve_search(m, nullptr, c).bytes : 0;
+}
+
+static int run_normalized(const ovc_model* m, SearchCall c, const float* inv, const float* bonus, float* score_out, int32_t* len_out,
+                          const float* features, const float* boxes, void* workspace, size_t workspace_bytes, ovc_stream stream) {
+    if (!model_ok(m) || !score_out || !len_out || c.B <= 0 || !length_tables_ok(inv, bonus, m->max_len)) return OVC_EINVAL;
+    c.normalized = true; c.norm_inv = inv; c.norm_bonus = bonus; c.score_out = score_out; c.len_out = len_out;
+    return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_normalized(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                          const float* inv, const float* bonus, void* workspace, size_t workspace_bytes, int64_t* ids_out,
+                                          float* logp_out, float* score_out, int32_t* len_out, float* all_logp_out, ovc_stream stream) {
+    SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
+    c.all_logp_out = all_logp_out;
+    return run_normalized(m, c, inv, bonus, score_out, len_out, features, boxes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ovc_beam_search_normalized_graph(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                                int out_size, const float* inv, const float* bonus, void* workspace, size_t workspace_bytes,
+                                                int64_t* ids_out, float* logp_out, float* score_out, int32_t* len_out, ovc_stream stream) {
+    return run_normalized(m, SearchCall{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out}, inv, bonus, score_out, len_out, features,
+                          boxes, workspace, workspace_bytes, stream);
+}
+
+// Test entry: ONE step of the fused selection (run_step_test) under the two tables in HOST memory: the length-normalised instance.
+extern "C" size_t ovc_debug_beam_normalized_update_bytes(int B, int width, int V, int k, int T) {
+    const size_t base = ovc_debug_beam_constrained_update_bytes(B, width, V, k, T);
+    return base ? base + 8 * (size_t)T + 512 : 0;
+}
+
+extern "C" int ovc_debug_beam_normalized_update(const float* logits, const int32_t* hist, const float* running, const float* alive,
+                                                const int32_t* len_in, int B, int width, int V, int k, int T, int t, int eos, const float* inv,
+                                                const float* bonus, void* scratch, size_t scratch_bytes, int32_t* parent_out,
+                                                int32_t* word_out, float* running_out, float* row_max_out, float* row_lsum_out,
+                                                int32_t* len_out, float* key_out, ovc_stream stream) {
+    if (!logits || !hist || !running || !alive || !len_in || !scratch || !parent_out || !word_out || !running_out || !row_max_out ||
+        !row_lsum_out || !len_out || !key_out)
+        return OVC_EINVAL;
+    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
+        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
+        return OVC_EINVAL;
+    if (!length_tables_ok(inv, bonus, T)) return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_beam_normalized_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    c.norm_inv = inv; c.norm_bonus = bonus; c.len_in = len_in; c.len_out = len_out; c.key_out = key_out;
     return run_step_test(c, scratch, stream);
 }
 

@@ -220,7 +220,7 @@ def feature_file_loader(paths: Sequence[str], batch_size: int, workers: int, key
 def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, beam_size: int = 5, slots: Optional[int] = None,
                           keys: Optional[Iterable[str]] = None, trusted: bool = False, workers: int = 0,
                           loader_context="forkserver", early_exit=False, direct: bool = True, no_repeat_ngram_size=0, min_length=0,
-                          banned_words=None):
+                          banned_words=None, length_penalty=None, length_form="avg", word_reward=0.0):
     """The reference's prediction loop (``trainers/vi_trainer.py:241-252``: per batch ``items.to(device)`` ->
     ``model.beam_search(items, batch_size, beam_size, out_size=1)`` -> ``decode_caption`` -> duplicate collapse) as a
     software pipeline on ONE host thread:
@@ -272,6 +272,9 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
 
     ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``model.beam_search``'s constraints, passed through (default off:
     the plain search).  They exclude the early-exit forms.
+
+    ``length_penalty``: None is the plain search; a number routes every batch through ``model.normalized_beam_search`` with
+    ``length_form`` and ``word_reward``.  That search takes no constraints and no early-exit form: it refuses them by name.
     """
     import sys
     import time
@@ -298,8 +301,15 @@ def predict_feature_files(model, vocab, paths: Sequence[str], batch_size: int, b
     def search(slot, items, ready, names):
         with torch.no_grad(), torch.cuda.stream(decode_streams[slot]):
             decode_streams[slot].wait_event(ready)
-            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1, early_exit=early_exit,
-                                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
+            if length_penalty is not None:
+                other = {name: value for name, value, off in (("early_exit", early_exit, False), ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
+                                                              ("min_length", min_length, 0), ("banned_words", banned_words, None))
+                         if value != off}
+                outs, _ = model.normalized_beam_search(items, batch_size=items.batch_size, beam_size=beam_size, length_penalty=length_penalty,
+                                                       length_form=length_form, word_reward=word_reward, out_size=1, **other)
+            else:
+                outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1, early_exit=early_exit,
+                                            no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
             ids_host = pinned_like(slot, "__ids__", outs.shape, outs.dtype)
             ids_host.copy_(outs, non_blocking=True)
             done = torch.cuda.Event()

@@ -145,9 +145,12 @@ def draw_seed(device, generator=None):
 
 
 def native_table(probs, seed):
-    """The ``ovc_dropout`` of ``{site: p}`` and a device int64 ``seed`` tensor (which must stay alive for the call)."""
+    """The ``ovc_dropout`` of ``{site: p}`` and a device int64 ``seed`` tensor.  The table holds the seed's ADDRESS, so it also keeps
+    the tensor itself: a caller that passes a temporary would otherwise hand the library memory that torch's allocator may give to
+    the next small tensor, and the masks would follow whatever that tensor holds."""
     d = native.Dropout()
     d.seed = seed.data_ptr()
+    d._seed_tensor = seed                                # alive as long as the table is
     for site, p in probs.items():
         if site == SITE_EMB:
             d.emb = p

@@ -24,6 +24,7 @@ from . import attention_maps as _maps
 from . import constraints as _constraints
 from . import diverse as _diverse
 from . import forced as _forced
+from . import length as _length
 from . import distill as _distill
 from . import dropout as _dropout
 from . import native
@@ -512,7 +513,7 @@ class CaptionEngine:
         """Drop this engine's workspaces and the hipGraphs captured on them."""
         lib = getattr(self, "lib", None)
         for (kind, _, _), ws in getattr(self, "_buffers", {}).items():
-            if lib is not None and kind not in ("arena", "steps", "prefix_table", "forced_table"):
+            if lib is not None and kind not in ("arena", "steps", "prefix_table", "forced_table", "length_tables"):
                 lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         self._buffers = {}
 
@@ -653,6 +654,9 @@ class CaptionEngine:
         "forced": ("ovc_forced_workspace_bytes", "engine configuration", "beam", {
             "plain": ("ovc_beam_search_forced", ("out_size", "forced", "C", *_RESULTS, "met", "everything", "stream")),
             "graph": ("ovc_beam_search_forced_graph", ("out_size", "forced", "C", *_RESULTS, "met", "stream"))}),
+        "normalized": ("ovc_beam_search_normalized_workspace_bytes", "engine configuration", "beam", {
+            "plain": ("ovc_beam_search_normalized", ("out_size", "inv", "bonus", *_RESULTS, "score", "lengths", "everything", "stream")),
+            "graph": ("ovc_beam_search_normalized_graph", ("out_size", "inv", "bonus", *_RESULTS, "score", "lengths", "stream"))}),
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
@@ -665,7 +669,7 @@ class CaptionEngine:
     }
 
     def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None, constraints=None, prefix=None, diverse=None, forced=None):
+                    options=None, constraints=None, prefix=None, diverse=None, forced=None, length=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
         ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
@@ -678,7 +682,9 @@ class CaptionEngine:
         ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None.  ``diverse``: the diverse search's
         ``(G, penalty)`` as ``diverse.check`` returned them, or None; ``slots`` is then int32 ``(B, out_size)``, the beam slot of each
         returned caption.  ``forced``: the forced words' int32 numpy table ``(B, C)`` as ``forced.check`` returned it, or None;
-        ``slots`` is then int32 ``(B, out_size)``, the bank (met set) of each returned caption, -1 for an empty slot."""
+        ``slots`` is then int32 ``(B, out_size)``, the bank (met set) of each returned caption, -1 for an empty slot.  ``length``:
+        the normalised search's fp32 numpy tables ``(inv, bonus)`` as ``length.tables`` built them, or None; ``slots`` is then the
+        pair ``(scores fp32, lengths int32)``, each ``(B, out_size)``: every returned caption's key and length."""
         kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
         if constraints:
             kind = "constrained"
@@ -688,6 +694,8 @@ class CaptionEngine:
             kind = "diverse"
         if forced is not None:
             kind = "forced"
+        if length is not None:
+            kind = "normalized"
         if table_drop is not None:
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -709,6 +717,11 @@ class CaptionEngine:
         slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
         if diverse or forced is not None:
             slots = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
+        score = lengths = None
+        if length is not None:
+            score = torch.empty(B, out_size, dtype=torch.float32, device=self.device)
+            lengths = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
+            slots = (score, lengths)
         everything = torch.empty(B, width, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
         steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
@@ -716,7 +729,8 @@ class CaptionEngine:
         if not self.use_graph and (form == "device" or table_drop is not None):
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         args = {name: None if t is None else t.data_ptr() for name, t in (
-            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", slots), ("steps", steps), ("seed", seed),
+            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", None if length is not None else slots),
+            ("steps", steps), ("seed", seed), ("score", score), ("lengths", lengths),
             ("slot", slots if diverse else None), ("met", slots if forced is not None else None))}
         args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
         if table_drop is not None:
@@ -731,6 +745,14 @@ class CaptionEngine:
             # host memory the library copies in stream order: kept until the stream's next call with forced words replaces it
             self._buffers[self._stream_key("forced_table")] = forced
             args.update(forced=forced.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), C=forced.shape[1])
+        if length is not None:
+            inv, bonus = length
+            if len(inv) != T or len(bonus) != T or inv.dtype != "float32" or bonus.dtype != "float32":
+                raise native.OvcError("the length tables must hold max_len = {} float32 entries each".format(T))
+            # host memory the library copies in stream order: kept until the stream's next normalised call replaces it
+            self._buffers[self._stream_key("length_tables")] = length
+            float_p = ctypes.POINTER(ctypes.c_float)
+            args.update(inv=inv.ctypes.data_as(float_p), bonus=bonus.ctypes.data_as(float_p))
         if constraints:
             n, L, banned = constraints
             args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
@@ -899,6 +921,45 @@ class CaptionEngine:
             raise native.OvcError("forced_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
         ids, logp, everything, met = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, forced=table)
         return (ids, logp, met, everything) if return_probs else (ids, logp, met)
+
+    def check_normalized(self, beam_size, length_penalty=1.0, length_form="avg", word_reward=0.0, out_size=1):
+        """The refusals of a length-normalised search that need no features, each naming its argument: callers run them before any
+        launch.  Returns ``(k, alpha, form, gamma, out_size)`` as ``openviic_amd.length.check`` normalises them."""
+        d = self.desc
+        out = _length.check(length_penalty, length_form, word_reward, beam_size, out_size, d.vocab, self.precision)
+        if not _length.neutral(out[1], out[3]) and not self.lib.ovc_beam_search_normalized_workspace_bytes(ctypes.byref(d), 1, 1, out[0], 0):
+            raise native.OvcError("normalized_beam_search: the engine refuses beam_size = {} for this model "
+                                  "(ovc_beam_search_normalized_workspace_bytes)".format(out[0]))
+        return out
+
+    def normalized_beam_search(self, features, boxes, batch_size, beam_size, length_penalty=1.0, length_form="avg", word_reward=0.0,
+                               out_size=1, return_probs=False, return_scores=True):
+        """Length-normalised beam search (``ovc_beam_search_normalized``; DESIGN.md section 2ad, ``openviic_amd.length`` mirrors the
+        rule): candidates are ranked inside the selection by ``key = (raw + word_reward * L) / lp(L)``, ``lp(L) = L ** alpha``
+        (``"avg"``) or ``((5 + L) / 6) ** alpha`` (``"wu"``), ``alpha = length_penalty``.  Returns ``(ids, logp, scores, lengths)``
+        -- ``(B, out_size, T)`` twice, then fp32 and int32 ``(B, out_size)``: the key each returned caption was ranked by and its
+        length -- plus ``everything (B, beam_size, T, V)`` with ``return_probs``.  The whole-search graph, or plain launches with
+        ``return_probs`` or without ``use_graph``; no early-exit form.  ``alpha = 0, word_reward = 0`` is the plain search, launch
+        for launch (the same entry point, graph and bits); its scores and lengths are derived from the result where ``return_scores``
+        asks for them, and are None otherwise.  Refused by name before any launch: a bad option or size, a split precision, more
+        than 16 384 words."""
+        k, alpha, form, gamma, out_size = self.check_normalized(beam_size, length_penalty, length_form, word_reward, out_size)
+        if _length.neutral(alpha, gamma):
+            ids, logp, everything, _ = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False)
+            score = first = None
+            if return_scores:
+                score = torch.zeros(logp.shape[:2], dtype=torch.float32, device=logp.device)
+                for t in range(logp.shape[2]):           # the search's own running sum: fp32, in step order
+                    score = score + logp[:, :, t]
+                ended = ids == self.desc.eos_idx
+                first = torch.where(ended.any(2), ended.int().argmax(2) + 1, torch.full_like(ids[:, :, 0], ids.shape[2])).int()
+            out = (ids, logp, score, first)
+        else:
+            tables = _length.tables(alpha, form, gamma, self.desc.max_len)
+            ids, logp, everything, (score, lengths) = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False,
+                                                                       length=tables)
+            out = (ids, logp, score, lengths)
+        return out + ((everything,) if return_probs else ())
 
     @staticmethod
     def sample_options(temperature=1.0, top_k=None, top_p=None):

@@ -319,16 +319,28 @@ class EvalCorpus:
         return self.scores_from_stats(*self.statistics())
 
 
-def evaluate_metrics(model, dataloader, corpus, beam_size, no_repeat_ngram_size=0, min_length=0, banned_words=None):
+def evaluate_metrics(model, dataloader, corpus, beam_size, no_repeat_ngram_size=0, min_length=0, banned_words=None,
+                     length_penalty=None, length_form="avg", word_reward=0.0):
     """The reference's ``evaluate_metrics`` (``vi_trainer.py:78-98``) with the scoring on the device: returns its ``scores``
     (without METEOR).  Every batch needs ``items.captions``, per image the references the corpus was built from.
-    ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``model.beam_search``'s constraints (default off)."""
+    ``no_repeat_ngram_size`` / ``min_length`` / ``banned_words``: ``model.beam_search``'s constraints (default off).
+    ``length_penalty``: None is the plain search; a number routes every batch through ``model.normalized_beam_search`` with
+    ``length_form`` and ``word_reward`` (which takes no constraints: it refuses them by name) -- sweep it to find the ``alpha`` that
+    maximises the dev CIDEr."""
     model.eval()
     corpus.reset()
     for items in dataloader:
         items = items.to(corpus.device)
         with torch.no_grad():
-            outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1,
-                                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
+            if length_penalty is not None:
+                constraints = {name: value for name, value, off in (("no_repeat_ngram_size", no_repeat_ngram_size, 0),
+                                                                    ("min_length", min_length, 0), ("banned_words", banned_words, None))
+                               if value != off}
+                outs, _ = model.normalized_beam_search(items, batch_size=items.batch_size, beam_size=beam_size,
+                                                       length_penalty=length_penalty, length_form=length_form, word_reward=word_reward,
+                                                       out_size=1, **constraints)
+            else:
+                outs, _ = model.beam_search(items, batch_size=items.batch_size, beam_size=beam_size, out_size=1,
+                                            no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, banned_words=banned_words)
         corpus.update(outs, corpus.rows(items.captions))
     return corpus.compute()[0]

@@ -303,6 +303,17 @@ SIGNATURES = {
     "ovc_debug_beam_forced_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                              c_int, POINTER(c_int32), c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "ovc_beam_search_normalized_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_beam_search_normalized": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                           POINTER(c_float), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "ovc_beam_search_normalized_graph": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                                 POINTER(c_float), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "ovc_debug_beam_normalized_update_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ovc_debug_beam_normalized_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p, c_size_t, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ovc_ensemble_ok": (c_int, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int]),
     "ovc_ensemble_workspace_bytes": (c_size_t, [POINTER(POINTER(Model)), c_int, c_int, c_int, c_int, c_int]),
     "ovc_ensemble_beam_search": (c_int, [POINTER(POINTER(Model)), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
@@ -393,6 +404,8 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_caption_set_workspace_bytes", "ovc_caption_set",
                  "ovc_search_forced_ok", "ovc_forced_workspace_bytes", "ovc_beam_search_forced", "ovc_beam_search_forced_graph",
                  "ovc_debug_beam_forced_update_bytes", "ovc_debug_beam_forced_update",
+                 "ovc_beam_search_normalized_workspace_bytes", "ovc_beam_search_normalized", "ovc_beam_search_normalized_graph",
+                 "ovc_debug_beam_normalized_update_bytes", "ovc_debug_beam_normalized_update",
                  "ovc_debug_add_norm", "ovc_debug_add_norm_form", "ovc_debug_dropout_rows", "ovc_debug_meshed_mix",
                  "ovc_debug_leaky_residual", "ovc_debug_sigmoid_gate",
                  "ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed", "ovc_train_meshed_beams_workspace_bytes",

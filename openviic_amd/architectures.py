@@ -21,6 +21,7 @@ from . import diverse as _diverse
 from . import forced as _forced
 from . import length as _length
 from . import prefix as _prefix
+from . import train_arch
 from . import distill as _distill
 from . import dropout as _dropout
 from . import engine
@@ -69,56 +70,21 @@ def _apply_step_gradients(eng, optimizer, grads, max_norm):
     optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
 
 
-_MESHED = ("meshed",)       # what ``_xe_call`` returns as the loss of a ``meshed=True`` call: the NLL on the meshed entry point
-
-
-_GEOMETRIC = ("geometric",)  # ... of a ``geometric=True`` call: the NLL on the object-relation transformer's entry point
-
-
-_AOA = ("aoa",)              # ... of an ``aoa=True`` call: the NLL on the attention-on-attention transformer's entry point
-
-
-def _loss_head(head):
-    """``forward_backward``'s keyword for what ``_xe_call`` returned as the call's loss: the NLL, the smoothed loss or soft targets
-    -- or the NLL of the meshed-memory transformer (``meshed=True``), of the object-relation transformer (``geometric=True``) or
-    of the attention-on-attention transformer (``aoa=True``)."""
-    if head is _MESHED:
-        return {"meshed": True}
-    if head is _GEOMETRIC:
-        return {"geometric": True}
-    if head is _AOA:
-        return {"aoa": True}
+def _loss_head(head, arch=None):
+    """``forward_backward``'s keyword for a call's loss -- the NLL, the smoothed loss or soft targets, as ``_xe_call`` returned it
+    -- or, for an architecture with a keyword of its own (``train_arch.TrainArch``), that keyword: its NLL."""
+    if arch is not None:
+        return arch.keywords()
     return {"distill": tuple(head)} if isinstance(head, _distill.SoftTargets) else {"loss": head}
 
 
-def _refuse_with_meshed(what, **given):
-    """``meshed=True`` together with what the meshed-memory transformer's training does not cover: refused by name."""
-    for name, value in given.items():
-        if value:
-            raise engine.native.OvcError(
-                "{}(meshed=True, {}=...): {} is out of scope for the meshed-memory transformer's training{}".format(
-                    what, name, name, " -- the meshed layer applies enc_attn.dropout once per level and the engine has no site "
-                    "for it; set DROPOUT: 0 or call model.eval()" if name == "dropout" else ""))
-
-
-def _refuse_with_geometric(what, **given):
-    """``geometric=True`` together with what the object-relation transformer's training does not cover: refused by name."""
-    for name, value in given.items():
-        if value:
-            raise engine.native.OvcError(
-                "{}(geometric=True, {}=...): {} is out of scope for the object-relation transformer's training{}".format(
-                    what, name, name, " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
-                    if name == "dropout" else " -- a model is one or the other" if name == "meshed" else ""))
-
-
-def _refuse_with_aoa(what, **given):
-    """``aoa=True`` together with what the attention-on-attention transformer's training does not cover: refused by name."""
-    for name, value in given.items():
-        if value:
-            raise engine.native.OvcError(
-                "{}(aoa=True, {}=...): {} is out of scope for the attention-on-attention transformer's training{}".format(
-                    what, name, name, " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
-                    if name == "dropout" else " -- a model is one or the other" if name in ("meshed", "geometric") else ""))
+def _named_arch(what, meshed, geometric, aoa):
+    """The architecture ``what`` was called for, from its three keywords (``None``: none of them); two of them together are
+    refused by name.  The caller goes on with ``arch.refuse_with`` for what else that architecture does not combine with."""
+    arch = next(iter(train_arch.named(aoa=aoa, geometric=geometric, meshed=meshed)), None)
+    if arch is not None:
+        arch.refuse_with(what, meshed=meshed, geometric=geometric)
+    return arch
 
 
 def _require_boxes(what, input_features):
@@ -139,10 +105,10 @@ class _XeLoss(torch.autograd.Function):
     until it is freed; no ``.grad`` is touched."""
 
     @staticmethod
-    def forward(ctx, engine_, dropout, smoothed, features, boxes, tokens, targets, *params):
-        # smoothed: None (the NLL), (label_smoothing, reduction) or a distill.SoftTargets (teacher, weight) -- inside a tuple,
-        # so autograd never sees the teacher: no gradient flows into it
-        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout, **_loss_head(smoothed))
+    def forward(ctx, engine_, dropout, head, features, boxes, tokens, targets, *params):
+        # head: the call's _loss_head -- a teacher (distill.SoftTargets) sits inside its tuple, so autograd never sees it: no
+        # gradient flows into it
+        loss, arena, grads = engine_.forward_backward(features, boxes, tokens, targets, dropout=dropout, **head)
         ctx.engine, ctx.arena = engine_, arena
         ctx.layout = [(g.storage_offset(), g.shape) for g in grads]
         ctx.wanted = [p.requires_grad for p in params]
@@ -343,26 +309,22 @@ class BaseTransformer(Module):
         before.  Refused by name before any launch and any draw: ``aoa=True`` on a model without gates, with another encoder or
         decoder or with memory slots, together with ``meshed=True``, ``geometric=True``, ``label_smoothing`` / ``reduction`` or
         ``teacher_log_probs`` / ``distill_weight``, and (the refusal above) a ``train()``-mode model with a live dropout."""
-        eng, drop, smoothed, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
-                                                    teacher_log_probs=teacher_log_probs, distill_weight=distill_weight, meshed=meshed,
-                                                    geometric=geometric, aoa=aoa)
-        return _XeLoss.apply(eng, drop, smoothed, *inputs, *eng.gradient_parameters())
+        eng, drop, smoothed, arch, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
+                                                          teacher_log_probs=teacher_log_probs, distill_weight=distill_weight,
+                                                          meshed=meshed, geometric=geometric, aoa=aoa)
+        return _XeLoss.apply(eng, drop, _loss_head(smoothed, arch), *inputs, *eng.gradient_parameters())
 
     def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None, teacher_log_probs=None,
                  distill_weight=None, meshed=False, geometric=False, aoa=False):
         """The preamble of ``xe_loss`` / ``xe_step``: their refusals in their order -- the loss, the dropout rules, a model outside
         the backward's scope, ``xe_step``'s optimizer set -- and only then the draw of the step's seed.  Returns ``(engine,
-        dropout (probs, seed) or None, smoothed loss / soft targets or None, (features, boxes, caption tokens, targets))``."""
-        if aoa:
-            _refuse_with_aoa(what, meshed=meshed, geometric=geometric, label_smoothing=label_smoothing is not None,
+        dropout (probs, seed) or None, smoothed loss / soft targets or None, the call's ``train_arch.TrainArch`` or None,
+        (features, boxes, caption tokens, targets))``."""
+        arch = _named_arch(what, meshed, geometric, aoa)
+        if arch is not None:
+            arch.refuse_with(what, dropout=dropout and not arch.loss_dropout, label_smoothing=label_smoothing is not None,
                              reduction=reduction is not None, teacher_log_probs=teacher_log_probs is not None,
                              distill_weight=distill_weight is not None)
-        if geometric:
-            _refuse_with_geometric(what, meshed=meshed, label_smoothing=label_smoothing is not None, reduction=reduction is not None,
-                                   teacher_log_probs=teacher_log_probs is not None, distill_weight=distill_weight is not None)
-        if meshed:
-            _refuse_with_meshed(what, dropout=dropout, label_smoothing=label_smoothing is not None, reduction=reduction is not None,
-                                teacher_log_probs=teacher_log_probs is not None, distill_weight=distill_weight is not None)
         soft = None
         if teacher_log_probs is not None or distill_weight is not None:
             try:            # a batch without caption tokens is refused where the inputs are checked, after the arguments
@@ -374,20 +336,15 @@ class BaseTransformer(Module):
         smoothed = soft or engine.checked_label_smoothing(label_smoothing, reduction, what, len(self.vocab))
         probs = self._xe_dropout_probs(dropout, what)
         eng = self._fused_engine()
-        eng._check_trainable(meshed, geometric, aoa)
-        if aoa:
-            smoothed = _AOA
-        if meshed:
-            smoothed = _MESHED
-        if geometric:
-            smoothed = _GEOMETRIC
+        eng._check_trainable(arch)
+        if arch is not None and arch.needs_boxes:
             _require_boxes(what, input_features)
         if optimizer is not None:
             _checked_step_optimizer(optimizer, what, eng)
         inputs = (*self._engine_inputs(input_features), input_features["caption_tokens"],
                   input_features["shifted_right_caption_tokens"])
         drop = (probs, _dropout.draw_seed(eng.device, generator)) if probs else None
-        return eng, drop, smoothed, inputs
+        return eng, drop, smoothed, arch, inputs
 
     def _xe_dropout_probs(self, dropout, what):
         """``{site: p}`` of the live dropouts for ``xe_loss`` / ``xe_step`` (empty: the plain call), or the refusals of their
@@ -440,10 +397,10 @@ class BaseTransformer(Module):
         from . import optim as _optim
         _checked_step_optimizer(optimizer, "xe_step")
         max_norm = _optim.checked_max_norm(max_norm, None, "xe_step")
-        eng, drop, smoothed, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
-                                                    optimizer, teacher_log_probs=teacher_log_probs, distill_weight=distill_weight,
-                                                    meshed=meshed, geometric=geometric, aoa=aoa)
-        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed))
+        eng, drop, smoothed, arch, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
+                                                          optimizer, teacher_log_probs=teacher_log_probs,
+                                                          distill_weight=distill_weight, meshed=meshed, geometric=geometric, aoa=aoa)
+        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed, arch))
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
@@ -506,12 +463,9 @@ class BaseTransformer(Module):
         of the lines above is then ``model.beam_search(items, B, k, out_size=k, aoa=True)``.  Refused by name before any launch
         or draw: any other model, and ``aoa=True`` together with ``meshed=True``, ``geometric=True``, ``dropout=True`` or
         ``sample=True``."""
-        if aoa:
-            _refuse_with_aoa("scst_step", meshed=meshed, geometric=geometric, dropout=dropout, sample=sample)
-        if geometric:
-            _refuse_with_geometric("scst_step", meshed=meshed, dropout=dropout, sample=sample)
-        if meshed:
-            _refuse_with_meshed("scst_step", dropout=dropout, sample=sample)
+        arch = _named_arch("scst_step", meshed, geometric, aoa)
+        if arch is not None:
+            arch.refuse_with("scst_step", dropout=dropout, sample=sample)
         if _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
             raise engine.native.OvcError("scst_step(no_repeat_ngram_size / min_length / banned_words): a constrained search inside "
                                          "scst_step is out of scope -- call beam_search with them and backpropagate its log_probs")
@@ -539,8 +493,8 @@ class BaseTransformer(Module):
             raise engine.native.OvcError("scst_step: 1 <= beam_size <= {} expected, got {}".format(engine.native.OVC_MAX_BEAM, k))
         probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
         eng = self._fused_engine()
-        eng._check_trainable(meshed, geometric, aoa)
-        if geometric:
+        eng._check_trainable(arch)
+        if arch is not None and arch.needs_boxes:
             _require_boxes("scst_step", input_features)
         checked = eng.check_sample(k, temperature, top_k, top_p) if sample else None
         _checked_step_optimizer(optimizer, "scst_step", eng)
@@ -570,12 +524,8 @@ class BaseTransformer(Module):
                                                      if isinstance(r, torch.Tensor) else type(r).__name__))
             r = r.detach().contiguous()
         g, stats = _scst.advantage(r, log_probs)
-        if meshed:
-            recompute = dict(recompute, meshed=True)
-        if geometric:
-            recompute = dict(recompute, geometric=True)
-        if aoa:
-            recompute = dict(recompute, aoa=True)
+        if arch is not None:
+            recompute = dict(recompute, **arch.keywords())
         _, grads = eng.sequence_backward(feats, boxes, outs, g, arena=eng.step_arena(), **recompute)
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return ScstStep(stats[0], stats[1], stats[2], outs, r)
@@ -660,28 +610,16 @@ class BaseTransformer(Module):
         refusals and ``meshed=True`` / ``geometric=True`` among them.
         """
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
-        if aoa:
-            _refuse_with_aoa("beam_search", meshed=meshed, geometric=geometric, dropout=dropout)
+        arch = _named_arch("beam_search", meshed, geometric, aoa)
+        if arch is not None:
+            arch.refuse_with("beam_search", dropout=dropout)
             if not fused:
-                raise engine.native.OvcError("beam_search(aoa=True) needs fused=True: the host loop has no backward")
+                raise engine.native.OvcError("beam_search({}=True) needs fused=True: the host loop has no backward".format(arch.key))
             if self.training and torch.is_grad_enabled():
-                self._xe_dropout_probs(False, "beam_search(aoa=True)")
-            self._fused_engine()._check_trainable(False, False, True)
-        if geometric:
-            _refuse_with_geometric("beam_search", meshed=meshed, dropout=dropout)
-            if not fused:
-                raise engine.native.OvcError("beam_search(geometric=True) needs fused=True: the host loop has no backward")
-            if self.training and torch.is_grad_enabled():
-                self._xe_dropout_probs(False, "beam_search(geometric=True)")
-            self._fused_engine()._check_trainable(False, True)
-            _require_boxes("beam_search", input_features)
-        if meshed:
-            _refuse_with_meshed("beam_search", dropout=dropout)
-            if not fused:
-                raise engine.native.OvcError("beam_search(meshed=True) needs fused=True: the host loop has no backward")
-            if self.training and torch.is_grad_enabled():
-                self._xe_dropout_probs(False, "beam_search(meshed=True)")
-            self._fused_engine()._check_trainable(True)
+                self._xe_dropout_probs(False, "beam_search({}=True)".format(arch.key))
+            self._fused_engine()._check_trainable(arch)
+            if arch.needs_boxes:
+                _require_boxes("beam_search", input_features)
         constraints = _requested_constraints(no_repeat_ngram_size, min_length, banned_words)
         if prefix is not None:       # every refusal of the table and of what it does not combine with, before any launch and draw
             dec = self.decoder
@@ -716,12 +654,8 @@ class BaseTransformer(Module):
             ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
                                                               return_probs, kwargs.get("early_exit"), constraints=constraints,
                                                               prefix=prefix)
-            if meshed:
-                recompute = dict(recompute, meshed=True)
-            if geometric:
-                recompute = dict(recompute, geometric=True)
-            if aoa:
-                recompute = dict(recompute, aoa=True)
+            if arch is not None:
+                recompute = dict(recompute, **arch.keywords())
             logp = self._scst_log_probs(input_features, ids, logp, recompute)
             if out_size == 1:
                 ids, logp = ids.squeeze(1), logp.squeeze(1)

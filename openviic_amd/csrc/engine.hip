@@ -101,7 +101,7 @@ struct Bump {
 // outputs, the pre-norm sums (the LayerNorm statistics are recomputed from them), the norm outputs, the ReLU outputs and the
 // layer outputs.  The inference forward reuses one set of buffers across layers instead (Workspace::tape == nullptr).
 // A gated attention (AoA, Engine::aoa) reads the AddNorm output u and writes the block's output (x1, x2) from the gate's two
-// products info / gate.  Only a training call that differentiates the gates (TrainCall::aoa) keeps the four apart per site; every
+// products info / gate.  Only a training call that differentiates the gates (TrainArch::Aoa) keeps the four apart per site; every
 // other tape and the scratch set alias u to the block's output and share the workspace's info / gate, as the gate always ran.
 struct EncTape { float *q, *k, *v, *att, *ya, *x1, *ff, *yf, *out, *u, *info, *gate; };
 struct DecTape {
@@ -1063,7 +1063,11 @@ struct SearchCall {
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
 
-bool dropout_train_ok(const ovc_model* m, const ForwardCall& c);    // the dropout scope, defined with the training calls
+// The architecture a training call names (TrainCall::arch).  Standard is what the plain entry points train: the plain,
+// augmented-memory and cross-level (CaMo) models; the other three are reached through their own entry points alone.
+enum class TrainArch { Standard, Meshed, Geometric, Aoa };
+// the scope of a training call (with `plan`: under dropout), defined with the training calls
+bool train_scope_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch, bool plan);
 
 // The models a form runs: the part of the scope that is checked before the device is touched.
 bool search_model_ok(const ovc_model* m, const SearchCall& c) {
@@ -1129,7 +1133,8 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                          (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
         return false;
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
-    return c.out_size > 0 && c.out_size <= c.k && (!c.plan || dropout_train_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}));
+    return c.out_size > 0 && c.out_size <= c.k &&
+           (!c.plan || train_scope_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}, TrainArch::Standard, true));
 }
 
 // With a plan, or sampling: the seed / step-count slots behind the plain layout.
@@ -2960,14 +2965,14 @@ struct TrainWs {
     // gradients dlev [3][B*N][d]
     float* cl_dh; float* cl_da; float* cl_dcat; float* cl_dss; float* cl_dq; float* cl_dkv; float* cl_do2p; float* cl_dq23;
     float* cl_dlev;
-    // the meshed decoder (bw_meshed_decoder_layer; TrainCall::meshed only), rows = B*S*T: the gate block's d(e_l) before and after
+    // the meshed decoder (bw_meshed_decoder_layer; TrainArch::Meshed only), rows = B*S*T: the gate block's d(e_l) before and after
     // the gates' share and d(a_l), [levels][rows][d] each; the running d(x1) [2][rows][d]; the levels' dq [levels][rows][h d_k] and
     // dk|dv [levels][B*N][2 h d_k]; the encoder levels' gradients, summed over the decoder layers, [2][levels][B*N][d]
     float* ms_de; float* ms_de2; float* ms_da; float* ms_dx1[2]; float* ms_dq; float* ms_dkv; float* ms_dlev[2];
-    // the geometric encoder's bias (TrainCall::geometric only): the caller's boxes [B*N][4], copied in outside the captured body;
+    // the geometric encoder's bias (TrainArch::Geometric only): the caller's boxes [B*N][4], copied in outside the captured body;
     // d(bias) [B][h_enc][N][N], the encoder layers' dS summed top down; ovc_bw_box_relation's scratch
     float* geo_boxes; float* geo_dG; float* geo_scratch;
-    // the AoA gates (bw_aoa_gate; TrainCall::aoa only): [d(i) | d(a)] [Rmax][2d], the staged [W_i ; W_g]^T [2d][2d], d(u) and the
+    // the AoA gates (bw_aoa_gate; TrainArch::Aoa only): [d(i) | d(a)] [Rmax][2d], the staged [W_i ; W_g]^T [2d][2d], d(u) and the
     // site's d(q) -- the AddNorm residual's share plus the gate's -- [Rmax][d] each
     float* aoa_dcat; float* aoa_wt; float* aoa_du; float* aoa_dq;
     size_t bytes;
@@ -2975,7 +2980,7 @@ struct TrainWs {
 
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 
-// the memory slots of the encoder layers' self-attention in a training call (train_ok: every layer has them, or none)
+// the memory slots of the encoder layers' self-attention in a training call (train_scope_ok: every layer has them, or none)
 inline int train_memory(const ovc_model* m) { return m->enc[0].att.m_k ? m->memory : 0; }
 
 // The loss head of a training call's body: issue_train_body switches on it, and nothing else does.
@@ -2991,9 +2996,11 @@ enum class LossHead {
 // (train_graph_key) and the launches around the body (run_train_call) are functions of it: a sizer and the entry point that carves
 // its buffer cannot disagree.
 struct TrainCall {
-    // the members every call states, first: TrainCall{B, N, S, T, head}; the rest is zero unless a form fills it in
+    // the members every call states, first: TrainCall{B, N, S, T, head}, and the architecture where the entry point names one:
+    // TrainCall{B, N, S, T, head, arch}; the rest is zero unless a form fills it in
     int B, N, S, T;                                 // S sequences per image, rows = B*S*T (run_forward_decoder); 1 but for RowWeights
     LossHead head;
+    TrainArch arch;                                 // Standard unless stated; scope, layout and body switch on it
     SmoothedLoss smoothed; uint64_t loss_hash;      // SmoothedXent: the loss's constants and their hash (make_smoothed_loss)
     SoftLoss soft; const float* teacher;            // SoftTargets: the two weights (their hash in loss_hash) and the caller's teacher
     // Dropout: the plan, or nullptr when no site is active (the plain call, launch for launch), with the caller's seed and the
@@ -3001,9 +3008,6 @@ struct TrainCall {
     // and narrows the scope.
     DropPlan* plan; const int64_t* seed; uint64_t drop_hash;
     int k; const int32_t* slots;                    // RowWeights with dropout: the search's beam width and its slot table
-    bool meshed;                                    // the multilevel encoder + meshed decoder (meshed_train_ok), the opt-in entry points
-    bool geometric;                                 // the geometric encoder + plain decoder (geometric_train_ok), the opt-in entry points
-    bool aoa;                                       // plain encoder + plain decoder with AoA gates (aoa_train_ok), the opt-in entry points
     bool seq() const { return head == LossHead::RowWeights; }
     // The call's teacher-forced pass: the logits kept for the backward; RowWeights: on the caller's ids and their row gradient.
     ForwardCall forward() const {
@@ -3021,14 +3025,15 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
     const size_t rows = (size_t)B * S * T, BN = (size_t)B * N, d = m->d_model, dff = m->d_ff, V = m->vocab;
     const size_t hk = (size_t)m->heads * m->d_k, ehk = (size_t)enc_heads(m) * enc_dk(m);
     const bool cl = m->enc_kind == OVC_ENC_CROSS_LEVEL;
-    const size_t lv = c.meshed ? m->n_levels : 1;   // the meshed block's products run over the stacked levels * rows (levels * B*N) rows
+    const bool meshed = c.arch == TrainArch::Meshed, geometric = c.arch == TrainArch::Geometric, aoa = c.arch == TrainArch::Aoa;
+    const size_t lv = meshed ? m->n_levels : 1;   // the meshed block's products run over the stacked levels * rows (levels * B*N) rows
     // the tail's weight gradients run over both cross calls' rows at once (2 B*N), mlp1's over K = 3d
     const size_t R = lv * std::max(rows, cl ? 2 * BN : BN), Rp = pad4(R);
     for (int l = 0; l < m->n_enc; ++l) {
         EncTape& p = t.tape.enc[l];
         p.q = a.take<float>(BN * ehk); p.k = a.take<float>(BN * ehk); p.v = a.take<float>(BN * ehk); p.att = a.take<float>(BN * ehk);
         p.ya = a.take<float>(BN * d); p.x1 = a.take<float>(BN * d); p.ff = a.take<float>(BN * dff); p.yf = a.take<float>(BN * d);
-        p.out = a.take<float>(l < m->n_enc - 1 && !cl && !c.meshed ? BN * d : 0);
+        p.out = a.take<float>(l < m->n_enc - 1 && !cl && !meshed ? BN * d : 0);
         p.u = p.x1; p.info = t.w.einfo; p.gate = t.w.egate;            // no gate's backward: aliased, as without a tape
     }
     if (cl) {
@@ -3046,13 +3051,13 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         p.ys = a.take<float>(rows * d); p.x1 = a.take<float>(rows * d); p.qc = a.take<float>(rows * hk);
         p.attc = a.take<float>(lv * rows * hk); p.yc = a.take<float>(rows * d); p.x2 = a.take<float>(rows * d);
         p.ff = a.take<float>(rows * dff); p.yf = a.take<float>(rows * d); p.out = a.take<float>(rows * d);
-        if (c.meshed) {
+        if (meshed) {
             p.ymesh = a.take<float>(lv * rows * d); p.enc_att = a.take<float>(lv * rows * d); p.alpha = a.take<float>(lv * rows * d);
             p.mixed = a.take<float>(rows * d);
         }
         p.us = p.x1; p.infos = t.w.info; p.gates = t.w.gate; p.uc = p.x2; p.infoc = t.w.info; p.gatec = t.w.gate;
     }
-    if (c.aoa) {
+    if (aoa) {
         // every gated site keeps its own u, info and gate pre-activation beside the block's output (3 x [rows][d] per site)
         for (int l = 0; l < m->n_enc; ++l) {
             EncTape& p = t.tape.enc[l];
@@ -3068,7 +3073,7 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         t.aoa_du = a.take<float>(R * d); t.aoa_dq = a.take<float>(R * d);
     }
     // the meshed gates' operand [x1 ; e_l] and the AoA gates' [q ; u] are 2d wide
-    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d, c.meshed || c.aoa ? 2 * d : d});
+    const size_t wide = std::max({d, dff, 3 * hk, 3 * ehk, cl ? 3 * d : d, meshed || aoa ? 2 * d : d});
     t.feat_t = a.take<float>((size_t)m->d_feat * pad4(BN));
     t.tok = a.take<int32_t>(rows);
     t.w_row = c.seq() ? t.w.w_row : a.take<float>(rows); t.loss = a.take<float>(4);
@@ -3091,13 +3096,13 @@ TrainWs carve_train(const ovc_model* m, void* base, const TrainCall& c) {
         t.mem_part_k = a.take<float>((size_t)B * mem * ehk); t.mem_part_v = a.take<float>((size_t)B * mem * ehk);
         t.mem_colpart = a.take<float>((((size_t)B + 63) / 64) * mem * ehk);
     }
-    if (c.meshed) {
+    if (meshed) {
         t.ms_de = a.take<float>(lv * rows * d); t.ms_de2 = a.take<float>(lv * rows * d); t.ms_da = a.take<float>(lv * rows * d);
         for (int i = 0; i < 2; ++i) t.ms_dx1[i] = a.take<float>(rows * d);
         t.ms_dq = a.take<float>(lv * rows * hk); t.ms_dkv = a.take<float>(lv * BN * 2 * hk);
         for (int i = 0; i < 2; ++i) t.ms_dlev[i] = a.take<float>(lv * BN * d);
     }
-    if (c.geometric) {
+    if (geometric) {
         const size_t eh = enc_heads(m);
         t.geo_boxes = a.take<float>(BN * 4); t.geo_dG = a.take<float>((size_t)B * eh * N * N);
         t.geo_scratch = a.take<float>(ovc_bw_box_relation_scratch_floats(B, N, (int)eh, m->d_g));
@@ -3130,87 +3135,112 @@ bool mha_grad_ok(const ovc_mha& a, const ovc_mha& g) {
 }
 bool ffn_grad_ok(const ovc_ffn& f, const ovc_ffn& g) { return lin_grad_ok(f.fc1, g.fc1) && lin_grad_ok(f.fc2, g.fc2) && norm_grad_ok(g.ln); }
 
-// What the backward covers: the plain or cross-level (CaMo) encoder with the plain decoder, plain scaled dot-product attention
-// -- in the PLAIN encoder's layers also with memory slots (memory > 0 and m_k / m_v in every layer: the augmented-memory
-// transformer) -- fp32, and vocabularies that take the fused vocabulary tail (its transposed logits and block pieces are what the
-// cross-entropy backward reads).
-bool train_ok(const ovc_model* m, const ForwardCall& c) {
-    if (!forward_ok(m, c)) return false;
-    if (m->enc_kind != OVC_ENC_PLAIN && m->enc_kind != OVC_ENC_CROSS_LEVEL) return false;
-    if (m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1) return false;
-    if (m->memory != 0 && m->enc_kind != OVC_ENC_PLAIN) return false;
-    if (m->enc_kind == OVC_ENC_CROSS_LEVEL && (m->precision != 0 || !mha_plain(m->cl_att))) return false;
-    for (int l = 0; l < m->n_enc; ++l) if (!(m->memory != 0 ? mha_memory(m->enc[l].att) : mha_plain(m->enc[l].att))) return false;
-    for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
-    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
-    // the dlogit products address their operands with 32-bit buffer descriptors (ovc_gemm_launch)
-    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
-    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
-}
-
-// The opt-in scope (ovc_forward_backward_meshed, ovc_sequence_backward_meshed): the multilevel encoder, every layer's self-attention
-// with memory slots (or every layer plain), in front of the meshed decoder with plain attentions and a gate per level; fp32 and the
-// fused vocabulary tail as in train_ok.  The 32-bit descriptor limits also hold for the products over the stacked levels * rows rows.
-bool meshed_train_ok(const ovc_model* m, const ForwardCall& c) {
-    if (!forward_ok(m, c)) return false;
-    if (m->enc_kind != OVC_ENC_MULTILEVEL || m->dec_kind != OVC_DEC_MESHED) return false;
-    if (m->n_levels != m->n_enc || m->n_levels > OVC_MAX_LEVELS) return false;
-    for (int l = 0; l < m->n_enc; ++l) if (!(m->memory != 0 ? mha_memory(m->enc[l].att) : mha_plain(m->enc[l].att))) return false;
-    for (int l = 0; l < m->n_dec; ++l) {
-        if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
-        for (int lvl = 0; lvl < m->n_levels; ++lvl) if (!m->dec[l].alpha[lvl].w) return false;
-    }
-    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
-    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows(), lv = m->n_levels;
-    const long stacked = lv * std::max(rows, (long)c.B * c.N), widest = std::max({(long)m->d_ff, 3L * m->heads * m->d_k, 2L * m->d_model});
-    if ((stacked + 256) * widest * 4 > kMax) return false;
-    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
-}
-
-// The opt-in scope (ovc_forward_backward_geometric, ovc_sequence_backward_geometric): the geometric (object-relation) encoder --
-// plain layers whose attention scores take the box-relation bias log(max(relu(fc_g(emb(boxes))), 1e-6)) -- in front of the plain
-// decoder; fp32, the fused vocabulary tail and the descriptor limits as in train_ok.  The bias's backward (ovc_bw_box_relation)
-// covers h <= 16, d_g == 4 without and a multiple of 8 up to 64 with the trigonometric embedding, and N <= 1024.
-bool geometric_train_ok(const ovc_model* m, const ForwardCall& c) {
-    if (!forward_ok(m, c) || m->precision != 0) return false;
-    if (m->enc_kind != OVC_ENC_GEOMETRIC || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
-    if (!m->fc_g_w || !m->fc_g_b) return false;
-    if (enc_heads(m) > 16 || c.N > 1024 || (m->trig ? (m->d_g < 8 || m->d_g > 64 || m->d_g % 8 != 0) : m->d_g != 4)) return false;
-    for (int l = 0; l < m->n_enc; ++l) if (!mha_plain(m->enc[l].att)) return false;
-    for (int l = 0; l < m->n_dec; ++l) if (!mha_plain(m->dec[l].self_att) || !mha_plain(m->dec[l].cross_att)) return false;
-    if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
-    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
-    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
-}
-
 // a gated attention (AoA): both gate products and no memory slots; a pair with one gate missing is neither this nor plain
 bool mha_gated(const ovc_mha& a) { return a.aoa_i.w && a.aoa_g.w && !a.m_k && !a.m_v; }
+bool mha_plain_or_gated(const ovc_mha& a) { return mha_plain(a) || mha_gated(a); }
 
-// The opt-in scope (ovc_forward_backward_aoa, ovc_sequence_backward_aoa): the plain encoder and the plain decoder whose attentions
-// are each plain or gated (out = W_i [q ; u] * sigmoid(W_g [q ; u]) behind the AddNorm), at least one of them gated; no memory
-// slots; fp32, the fused vocabulary tail and the descriptor limits as in train_ok -- also for the gate block's K = 2d products
-// over [rows][2d] operands.
-bool aoa_train_ok(const ovc_model* m, const ForwardCall& c) {
-    if (!forward_ok(m, c) || m->precision != 0) return false;
-    if (m->enc_kind != OVC_ENC_PLAIN || m->dec_kind != OVC_DEC_PLAIN || m->n_levels != 1 || m->memory != 0) return false;
-    int gated = 0;
-    const auto site_ok = [&](const ovc_mha& a) {
-        if (mha_gated(a)) { ++gated; return true; }
-        return mha_plain(a);
-    };
-    for (int l = 0; l < m->n_enc; ++l) if (!site_ok(m->enc[l].att)) return false;
-    for (int l = 0; l < m->n_dec; ++l) if (!site_ok(m->dec[l].self_att) || !site_ok(m->dec[l].cross_att)) return false;
-    if (gated == 0) return false;
+// The scope of a training call (train_scope_ok), piece by piece: each rule is stated once, and an architecture names the ones
+// it takes.
+//
+//   Standard   the plain or cross-level (CaMo) encoder with the plain decoder, plain attentions -- in the PLAIN encoder's layers
+//              also with memory slots in every layer (the augmented-memory transformer).  Under dropout the plain encoder only:
+//              the cross-level tail applies its one nn.Dropout twice and has no site of its own.
+//   Meshed     the multilevel encoder, every layer's self-attention with memory slots (or every layer plain), in front of the
+//              meshed decoder with plain attentions and a gate per level.  No dropout form: ovc_dropout has no per-level site.
+//   Geometric  the geometric (object-relation) encoder -- plain layers whose scores take the box-relation bias
+//              log(max(relu(fc_g(emb(boxes))), 1e-6)) -- in front of the plain decoder.  The bias's backward
+//              (ovc_bw_box_relation) covers h <= 16, d_g == 4 without and a multiple of 8 up to 64 with the trigonometric
+//              embedding, and N <= 1024.  Takes a dropout plan: the encoder's sites are the plain encoder's.
+//   Aoa        the plain encoder and decoder whose attentions are each plain or gated (out = W_i [q ; u] * sigmoid(W_g [q ; u])
+//              behind the AddNorm), at least one of them gated; no memory slots.  Takes a dropout plan: the gate sits behind
+//              the AddNorm and has no site.
+//
+// All of them: fp32 (forward_ok) and a vocabulary that takes the fused vocabulary tail, whose transposed logits and block pieces
+// the cross-entropy backward reads.
+
+// the encoder and decoder kinds an architecture takes, with the level count and the memory slots that go with them
+bool train_kinds_ok(const ovc_model* m, TrainArch arch) {
+    switch (arch) {
+    case TrainArch::Standard:
+        return (m->enc_kind == OVC_ENC_PLAIN || m->enc_kind == OVC_ENC_CROSS_LEVEL) && m->dec_kind == OVC_DEC_PLAIN &&
+               m->n_levels == 1 && (m->memory == 0 || m->enc_kind == OVC_ENC_PLAIN);
+    case TrainArch::Meshed:
+        return m->enc_kind == OVC_ENC_MULTILEVEL && m->dec_kind == OVC_DEC_MESHED && m->n_levels == m->n_enc &&
+               m->n_levels <= OVC_MAX_LEVELS;
+    case TrainArch::Geometric:
+        return m->enc_kind == OVC_ENC_GEOMETRIC && m->dec_kind == OVC_DEC_PLAIN && m->n_levels == 1 && m->memory == 0;
+    case TrainArch::Aoa:
+        return m->enc_kind == OVC_ENC_PLAIN && m->dec_kind == OVC_DEC_PLAIN && m->n_levels == 1 && m->memory == 0;
+    }
+    return false;
+}
+
+// a dropout plan: where the architecture has a dropout form at all
+bool train_plan_ok(const ovc_model* m, TrainArch arch) {
+    return arch == TrainArch::Standard ? m->enc_kind == OVC_ENC_PLAIN : arch != TrainArch::Meshed;
+}
+
+// every encoder layer's self-attention passes `enc`, every decoder attention (self and cross) `dec`
+using SiteOk = bool (*)(const ovc_mha&);
+bool train_sites_ok(const ovc_model* m, SiteOk enc, SiteOk dec) {
+    for (int l = 0; l < m->n_enc; ++l) if (!enc(m->enc[l].att)) return false;
+    for (int l = 0; l < m->n_dec; ++l) if (!dec(m->dec[l].self_att) || !dec(m->dec[l].cross_att)) return false;
+    return true;
+}
+
+// The 32-bit buffer descriptors of the backward's products (ovc_gemm_launch).
+constexpr long kDescriptorMax = 0x7fffffffL - (1L << 20);
+
+// the fused vocabulary tail, and the two dlogit products' operands
+bool train_vocab_ok(const ovc_model* m, long rows) {
     if ((m->vocab + 31) / 32 > kFusedVocabBlocks) return false;
-    const long kMax = 0x7fffffffL - (1L << 20), rows = c.rows();
-    const long most = std::max(rows, (long)c.B * c.N), widest = std::max({(long)m->d_ff, 3L * m->heads * m->d_k, 2L * m->d_model});
-    if ((most + 256) * widest * 4 > kMax || 4L * m->d_model * m->d_model * 4 > kMax) return false;
-    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kMax;
+    return (rows + 256) * (long)pad4(m->vocab) * 4 <= kDescriptorMax && ((long)m->vocab + 256) * (long)pad4(rows) * 4 <= kDescriptorMax;
+}
+
+// The rows an architecture's gate block stacks into one operand, as a factor of the call's most rows: the meshed decoder's
+// levels * rows (levels * B*N) rows, the AoA gates' rows; 0: no stacked operand, no limit.  Its widest operand is [.][2d].
+long train_row_factor(const ovc_model* m, TrainArch arch) {
+    return arch == TrainArch::Meshed ? m->n_levels : arch == TrainArch::Aoa ? 1 : 0;
+}
+bool train_stacked_ok(const ovc_model* m, const ForwardCall& c, long factor) {
+    const long stacked = factor * std::max((long)c.rows(), (long)c.B * c.N);
+    const long widest = std::max({(long)m->d_ff, 3L * m->heads * m->d_k, 2L * m->d_model});
+    return (stacked + 256) * widest * 4 <= kDescriptorMax;
+}
+
+// what an architecture asks on top: after train_kinds_ok and train_sites_ok
+bool train_extras_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch) {
+    switch (arch) {
+    case TrainArch::Standard:
+        return m->enc_kind != OVC_ENC_CROSS_LEVEL || mha_plain(m->cl_att);
+    case TrainArch::Meshed:
+        for (int l = 0; l < m->n_dec; ++l)
+            for (int lvl = 0; lvl < m->n_levels; ++lvl) if (!m->dec[l].alpha[lvl].w) return false;
+        return true;
+    case TrainArch::Geometric:
+        return m->fc_g_w && m->fc_g_b && enc_heads(m) <= 16 && c.N <= 1024 &&
+               (m->trig ? m->d_g >= 8 && m->d_g <= 64 && m->d_g % 8 == 0 : m->d_g == 4);
+    case TrainArch::Aoa:
+        // at least one gated site, and the staged [W_i ; W_g]^T [2d][2d] of a gate
+        return !train_sites_ok(m, mha_plain, mha_plain) && 4L * m->d_model * m->d_model * 4 <= kDescriptorMax;
+    }
+    return false;
+}
+
+// The scope of a training call, for its sizer and its entry point alike -- and, as (Standard, plan), of the search under dropout.
+// An architecture is reached through its own entry points alone: nothing here derives it from the model.
+bool train_scope_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch, bool plan) {
+    if (!forward_ok(m, c) || !train_kinds_ok(m, arch) || (plan && !train_plan_ok(m, arch))) return false;
+    const SiteOk enc = arch == TrainArch::Aoa ? mha_plain_or_gated : m->memory != 0 ? mha_memory : mha_plain;
+    if (!train_sites_ok(m, enc, arch == TrainArch::Aoa ? mha_plain_or_gated : mha_plain)) return false;
+    if (!train_extras_ok(m, c, arch)) return false;
+    const long factor = train_row_factor(m, arch);
+    return (factor == 0 || train_stacked_ok(m, c, factor)) && train_vocab_ok(m, c.rows());
 }
 
 bool grads_ok(const ovc_model* m, const ovc_model* g) {
     if (!lin_grad_ok(m->proj, g->proj) || !norm_grad_ok(g->enc_ln) || !g->word_emb || !g->fc) return false;
-    // the AoA gates, where a site has them (only an aoa call reaches this with gates: every other scope refuses them)
+    // the AoA gates, where a site has them (only a TrainArch::Aoa call reaches this with gates: every other scope refuses them)
     const auto gates_ok = [](const ovc_mha& a, const ovc_mha& ga) {
         return (!a.aoa_i.w || lin_grad_ok(a.aoa_i, ga.aoa_i)) && (!a.aoa_g.w || lin_grad_ok(a.aoa_g, ga.aoa_g));
     };
@@ -3233,21 +3263,7 @@ bool grads_ok(const ovc_model* m, const ovc_model* g) {
     return true;
 }
 
-// Dropout training (ovc_forward_backward_dropout) covers the plain encoder only: the cross-level tail applies its one nn.Dropout
-// twice and has no site of its own.
-bool dropout_train_ok(const ovc_model* m, const ForwardCall& c) { return train_ok(m, c) && m->enc_kind == OVC_ENC_PLAIN; }
-
-// The scope of a training call, for its sizer and its entry point alike: train_ok of its pass, under dropout the dropout scope;
-// the opt-in meshed scope for the meshed entry points and the opt-in geometric scope for the geometric ones, and nothing else
-// reaches either.  A geometric call takes a dropout plan: the encoder's sites are the plain encoder's.  Likewise the opt-in AoA
-// scope for the AoA entry points: the only one that takes a model with gates.
-bool call_ok(const ovc_model* m, const TrainCall& c) {
-    if (c.meshed) return !c.plan && !c.geometric && !c.aoa && meshed_train_ok(m, c.forward());   // no dropout form: ovc_dropout has no per-level site
-    if (c.geometric) return !c.aoa && geometric_train_ok(m, c.forward());
-    if (c.aoa) return aoa_train_ok(m, c.forward());       // takes a dropout plan: the gate sits behind the AddNorm and has no site
-
-    return c.plan ? dropout_train_ok(m, c.forward()) : train_ok(m, c.forward());
-}
+bool call_ok(const ovc_model* m, const TrainCall& c) { return train_scope_ok(m, c.forward(), c.arch, c.plan != nullptr); }
 
 // A sequence call with dropout recomputes under the masks of the search that made its sequences: that search's limits
 // (ovc_beam_search_dropout), full-length sequences and its slot table.  After call_ok: m has been checked.
@@ -3406,6 +3422,28 @@ int bw_self_attention(Engine& e, TrainWs& t, const ovc_mha& at, const ovc_mha& g
     return bw_mm(e, t.dqkv, 3 * hk, rows, 3 * hk, t.wt, d, dx, resid);
 }
 
+// t.wt = [W_k ; W_v]^T [d][2 hk] of one attention (the k|v input gradient dX = [dk | dv] . [W_k ; W_v])
+int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk) {
+    const int d = e.m->d_model;
+    RUN(ovc_bw_transpose(at.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
+    RUN(ovc_bw_transpose(at.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
+    return OVC_OK;
+}
+
+// The attention backward of image b's nq queries over its nk regions under the encoder mask: dq [B*nq][h dk] and the pair
+// dkv = [dk | dv] [B*nk][2 h dk], from the output gradient dout [B*nq][h dk].
+int bw_region_attention(Engine& e, TrainWs& t, const float* q, const float* k, const float* v, const float* dout, float* dq, float* dkv,
+                        int B, int nq, int nk, int h, int dk) {
+    const int hk = h * dk;
+    AttnBwdArgs a{};
+    a.q = q; a.ldq = hk; a.k = k; a.v = v; a.ldkv = hk; a.dout = dout; a.ldo = hk;
+    a.mask = t.w.enc_mask; a.mask_b = nk; a.mask_r = 0;
+    a.B = B; a.nq = nq; a.nk = nk; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
+    a.P = t.P; a.dS = t.dS; a.dq = dq; a.lddq = hk; a.dk_out = dkv; a.dv_out = dkv + hk; a.lddkv = 2 * hk;
+    RUN(ovc_bw_attention(a, e.stream));
+    return OVC_OK;
+}
+
 // S sequences per image (run_forward_decoder): the cross-attention of image b over its S*T query rows, the self-attention per sequence
 int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const TrainCall& c, const float* xin, const float* dout,
                      float* dxin, float* denc_prev, float* denc_next) {
@@ -3437,27 +3475,19 @@ int bw_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, const Tr
     TRY(bw_weight(e, t, dp, d, d, p.attc, hk, hk, rows, dl.cross_att.o, gl.cross_att.o));
     TRY(bw_input(e, t, dp, d, dl.cross_att.o, hk, t.datt, nullptr, rows));
     const size_t kvoff = (size_t)l * BN * hk;
-    AttnBwdArgs a{};
-    a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
-    a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
-    a.B = B; a.nq = S * T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
-    a.P = t.P; a.dS = t.dS; a.dq = t.dqkv; a.lddq = hk; a.dk_out = t.dkv; a.dv_out = t.dkv + hk; a.lddkv = 2 * hk;
-    RUN(ovc_bw_attention(a, e.stream));
+    TRY(bw_region_attention(e, t, p.qc, w.kx + kvoff, w.vx + kvoff, t.datt, t.dqkv, t.dkv, B, S * T, N, h, dk));
     TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
     TRY(bw_input(e, t, t.dqkv, hk, dl.cross_att.q, d, t.dx1, resid, rows));     // t.dx1 = d(x1)
     // the encoder output's share: this layer's cross keys / values, added to what layers above contributed
     TRY(bw_weight(e, t, t.dkv, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.k, gl.cross_att.k));
     TRY(bw_weight(e, t, t.dkv + hk, 2 * hk, hk, w.enc_levels, d, d, BN, dl.cross_att.v, gl.cross_att.v));
-    RUN(ovc_bw_transpose(dl.cross_att.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
-    RUN(ovc_bw_transpose(dl.cross_att.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
+    TRY(stage_kv_weights(e, t, dl.cross_att, hk));
     TRY(bw_mm(e, t.dkv, 2 * hk, BN, 2 * hk, t.wt, d, denc_next, denc_prev));
     // masked self-attention over the caption; x1 is the self block's output -- the gate's, where that block is gated
     const AoaSite self_site{xin, p.us, p.infos, p.gates};
     return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
                              B * S, T, h, dk, dxin, dec_site(l, 0), 0, nullptr, nullptr, self_gated ? &self_site : nullptr);
 }
-
-int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk);
 
 // A meshed decoder layer (run_decoder_layer's OVC_DEC_MESHED branch; decoders.py:51-73), DESIGN.md section 2aa.  With x1 the
 // self-attention block's output, e_l = LN(attc_l Wo + bo + x1), a_l = W_l [x1 ; e_l] + b_l and mixed = (sum_l sigmoid(a_l) e_l) /
@@ -3507,13 +3537,8 @@ int bw_meshed_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, c
     // cross-attention: once per level on the shared queries and the level's keys / values
     for (int lvl = 0; lvl < lv; ++lvl) {
         const size_t kvoff = ((size_t)l * lv + lvl) * BN * hk;
-        AttnBwdArgs a{};
-        a.q = p.qc; a.ldq = hk; a.k = w.kx + kvoff; a.v = w.vx + kvoff; a.ldkv = hk; a.dout = t.datt + (size_t)lvl * rows * hk; a.ldo = hk;
-        a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
-        a.B = B; a.nq = S * T; a.nk = N; a.h = h; a.dk = dk; a.scale = sqrtf((float)dk);
-        a.P = t.P; a.dS = t.dS; a.dq = t.ms_dq + (size_t)lvl * rows * hk; a.lddq = hk;
-        a.dk_out = t.ms_dkv + (size_t)lvl * BN * 2 * hk; a.dv_out = a.dk_out + hk; a.lddkv = 2 * hk;
-        RUN(ovc_bw_attention(a, s));
+        TRY(bw_region_attention(e, t, p.qc, w.kx + kvoff, w.vx + kvoff, t.datt + (size_t)lvl * rows * hk, t.ms_dq + (size_t)lvl * rows * hk,
+                                t.ms_dkv + (size_t)lvl * BN * 2 * hk, B, S * T, N, h, dk));
     }
     RUN(ovc_bw_sum_levels(nullptr, t.ms_dq, lv, (long)rows * hk, (long)rows * hk, t.dqkv, s));       // d(qc)
     TRY(bw_weight(e, t, t.dqkv, hk, hk, p.x1, d, d, rows, dl.cross_att.q, gl.cross_att.q));
@@ -3541,14 +3566,6 @@ int bw_weight_pair(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const
     RUN(ovc_bw_transpose(X1, ldx, rows, k, t.tb + rows, rp, rp - rows, s));
     TRY(bw_mm(e, t.ta, rp, n, rp, t.tb, k, out_ptr(g.w)));
     if (l.b) RUN(ovc_bw_rowsum(t.ta, rp, n, 2 * rows, out_ptr(g.b), s));
-    return OVC_OK;
-}
-
-// t.wt = [W_k ; W_v]^T [d][2 hk] of one attention (the k|v input gradient dX = [dk | dv] . [W_k ; W_v])
-int stage_kv_weights(Engine& e, TrainWs& t, const ovc_mha& at, int hk) {
-    const int d = e.m->d_model;
-    RUN(ovc_bw_transpose(at.k.w, d, hk, d, t.wt, 2 * hk, hk, e.stream));
-    RUN(ovc_bw_transpose(at.v.w, d, hk, d, t.wt + hk, 2 * hk, hk, e.stream));
     return OVC_OK;
 }
 
@@ -3592,17 +3609,12 @@ int bw_cross_level_tail(Engine& e, TrainWs& t, const ovc_model* gr, int B, int N
         RUN(ovc_bw_layer_norm_post(p.ya + (size_t)c * nd, queries[c], at.ln.g, dout[c], kCrossScale, m->ln_eps, BN, d, dss,
                                    t.prod + (size_t)c * nd, t.dyc + (size_t)c * nd, s));
         TRY(bw_input(e, t, dss, d, at.o, hk, t.datt, nullptr, BN));
-        AttnBwdArgs a{};
-        a.q = w.cl_q + (size_t)c * BN * hk; a.ldq = hk; a.k = p.k[c]; a.v = p.v[c]; a.ldkv = hk; a.dout = t.datt; a.ldo = hk;
-        a.mask = w.enc_mask; a.mask_b = N; a.mask_r = 0;
-        a.B = B; a.nq = N; a.nk = N; a.h = eh; a.dk = edk; a.scale = sqrtf((float)edk);
-        a.P = t.P; a.dS = t.dS;
-        a.dq = t.cl_dq + (size_t)c * BN * hk; a.lddq = hk;
-        a.dk_out = t.cl_dkv + (size_t)c * BN * 2 * hk; a.dv_out = a.dk_out + hk; a.lddkv = 2 * hk;
-        RUN(ovc_bw_attention(a, s));
+        float* dkv = t.cl_dkv + (size_t)c * BN * 2 * hk;
+        TRY(bw_region_attention(e, t, w.cl_q + (size_t)c * BN * hk, p.k[c], p.v[c], t.datt, t.cl_dq + (size_t)c * BN * hk, dkv, B, N, N,
+                                eh, edk));
         TRY(stage_kv_weights(e, t, at, hk));
         // call 2's keys / values are o2' (its whole gradient); call 1's are o1 (its tail share before dcat1)
-        TRY(bw_mm(e, a.dk_out, 2 * hk, BN, 2 * hk, t.wt, d, c == 1 ? t.cl_do2p : t.cl_dlev));
+        TRY(bw_mm(e, dkv, 2 * hk, BN, 2 * hk, t.wt, d, c == 1 ? t.cl_do2p : t.cl_dlev));
     }
     // self_attn's weights over both calls' rows
     TRY(bw_weight(e, t, t.cl_dss, d, d, p.att, hk, hk, 2 * BN, at.o, ga.o));
@@ -3629,6 +3641,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
     Workspace& w = t.w;
     hipStream_t s = e.stream;
     const int d = m->d_model, V = m->vocab, rows = B * S * T, BN = B * N, L = m->n_dec;
+    const bool meshed = c.arch == TrainArch::Meshed, geometric = c.arch == TrainArch::Geometric;
     const int nblk = (V + 31) / 32, ldt = (int)pad4(rows), ldv = (int)pad4(V);
     TRY(issue_forward_body(e, w, c.forward()));
     if (!e.dry) {
@@ -3664,7 +3677,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
     int cur = 0, enc_cur = 0;
     for (int l = L - 1; l >= 0; --l) {
         const float* xin = l == 0 ? w.x : t.tape.dec[l - 1].out;
-        if (c.meshed) {
+        if (meshed) {
             TRY(bw_meshed_decoder_layer(e, t, gr, l, c, xin, t.g[cur], t.g[cur ^ 1], l == L - 1 ? nullptr : t.ms_dlev[enc_cur],
                                         t.ms_dlev[l == L - 1 ? enc_cur : enc_cur ^ 1]));
         } else {
@@ -3687,7 +3700,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         dout = t.cl_dlev + 2 * nd;
     }
     // the multilevel encoder: layer l's output is level l -- its gradient is the decoder's for that level plus layer l+1's input gradient
-    float* mlev = c.meshed ? t.ms_dlev[enc_cur] : nullptr;
+    float* mlev = meshed ? t.ms_dlev[enc_cur] : nullptr;
     if (mlev) dout = mlev + (size_t)(m->n_enc - 1) * nd;
     for (int l = m->n_enc - 1; l >= 0; --l) {
         const EncTape& p = t.tape.enc[l];
@@ -3702,9 +3715,9 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         // a gated layer (AoA): x1 is the gate's output and the gate's query is the layer input
         const AoaSite site{xin, p.u, p.info, p.gate};
         TRY(bw_self_attention(e, t, el.att, gl.att, xin, p.q, p.k, p.v, p.att, p.ya, t.dx1, w.enc_mask, N, 0, B, N, eh, edk, t.g[cur],
-                              enc_site(l, 0), train_memory(m), c.geometric ? w.geometry : nullptr,
-                              c.geometric && top ? t.geo_dG : nullptr, el.att.aoa_i.w ? &site : nullptr));
-        if (c.geometric && !top) RUN(ovc_bw_accumulate(t.geo_dG, t.dS, (long)B * eh * N * N, s));
+                              enc_site(l, 0), train_memory(m), geometric ? w.geometry : nullptr,
+                              geometric && top ? t.geo_dG : nullptr, el.att.aoa_i.w ? &site : nullptr));
+        if (geometric && !top) RUN(ovc_bw_accumulate(t.geo_dG, t.dS, (long)B * eh * N * N, s));
         dout = t.g[cur];
         if ((cl || mlev) && l > 0) {
             float* lev = (cl ? t.cl_dlev : mlev) + (size_t)(l - 1) * nd;
@@ -3714,7 +3727,7 @@ int issue_train_body(Engine& e, TrainWs& t, const ovc_model* gr, const TrainCall
         cur ^= 1;
     }
     // the bias's parameters, from the stored w (Workspace::geometry: written before the body, read-only since) and the staged boxes
-    if (c.geometric)
+    if (geometric)
         RUN(ovc_bw_box_relation(t.geo_boxes, w.geometry, t.geo_dG, B, N, eh, m->d_g, m->trig, t.geo_scratch, out_ptr(gr->fc_g_w),
                                 out_ptr(gr->fc_g_b), s));
     // feature embedding: encoder.layer_norm over the projection (the sinusoid added after it has no parameters)
@@ -3809,7 +3822,8 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
                    float* logp_out, int use_graph, ovc_stream stream) {
     if (!call_ok(m, c) || !grads || !grads_ok(m, grads) || !features || !tokens || !workspace) return OVC_EINVAL;
     if (c.seq() ? !grad_logp : (!targets || !loss_out)) return OVC_EINVAL;
-    if (c.geometric ? !boxes || !ovc_aligned16(boxes) : false) return OVC_EINVAL;      // every other encoder reads no boxes
+    const bool geometric = c.arch == TrainArch::Geometric;                             // every other encoder reads no boxes
+    if (geometric && (!boxes || !ovc_aligned16(boxes))) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
     TrainWs t = carve_train(m, workspace, c);
@@ -3833,7 +3847,7 @@ int run_train_call(const ovc_model* m, const ovc_model* grads, const TrainCall& 
     // the kernels that read the caller's inputs, outside the captured body
     ForwardCall f = c.forward();
     f.tokens = tokens; f.targets = targets; f.row_grad = grad_logp;
-    TRY(stage_train_inputs(e, t, f, features, c.geometric ? boxes : nullptr));
+    TRY(stage_train_inputs(e, t, f, features, geometric ? boxes : nullptr));
     auto body = [&](Engine& ce) {
         ce.maskrow = t.maskrow;         // nullptr but for sequences under dropout (carve_train)
         return issue_train_body(ce, t, grads, c);
@@ -3975,63 +3989,47 @@ extern "C" int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads,
 // ---------------------------------------------------------------------------------------------
 // training the meshed-memory transformer: the opt-in entry points
 // ---------------------------------------------------------------------------------------------
-// ovc_forward_backward / ovc_sequence_backward for the multilevel encoder + meshed decoder (meshed_train_ok): the same TrainCall
-// with `meshed` set, so the same carve_train, issue_train_body and run_train_call.  The graph key needs nothing new: it hashes the
+// ovc_forward_backward / ovc_sequence_backward for the multilevel encoder + meshed decoder (TrainArch::Meshed): the same TrainCall
+// with that arch, so the same carve_train, issue_train_body and run_train_call.  The graph key needs nothing new: it hashes the
 // whole ovc_model (its kinds and gate pointers included), and a meshed model reaches the body through these two alone.
-namespace {
-TrainCall meshed_call(int B, int N, int S, int T, LossHead head) {
-    TrainCall c{B, N, S, T, head};
-    c.meshed = true;
-    return c;
-}
-}  // namespace
-
 extern "C" size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, int N, int T) {
-    return train_workspace_bytes(m, meshed_call(B, N, 1, T, LossHead::Xent), false);
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Meshed}, false);
 }
 
 extern "C" int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                            int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                            size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream) {
-    return run_train_call(m, grads, meshed_call(B, N, 1, T, LossHead::Xent), features, boxes, tokens, targets, nullptr, workspace,
-                          workspace_bytes, loss_out, nullptr, use_graph, stream);
+    return run_train_call(m, grads, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Meshed}, features, boxes, tokens, targets, nullptr,
+                          workspace, workspace_bytes, loss_out, nullptr, use_graph, stream);
 }
 
 extern "C" size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    return train_workspace_bytes(m, meshed_call(B, N, S, T, LossHead::RowWeights), false);
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Meshed}, false);
 }
 
 extern "C" int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                             int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                             size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
-    return run_train_call(m, grads, meshed_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
-                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Meshed}, features, boxes, ids, nullptr, grad_logp,
+                          workspace, workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // training the object-relation transformer: the opt-in entry points
 // ---------------------------------------------------------------------------------------------
-// ovc_forward_backward / ovc_sequence_backward for the geometric encoder + plain decoder (geometric_train_ok): the same TrainCall
-// with `geometric` set, so the same carve_train, issue_train_body and run_train_call -- which stages the boxes.  The graph key needs
+// ovc_forward_backward / ovc_sequence_backward for the geometric encoder + plain decoder (TrainArch::Geometric): the same TrainCall
+// with that arch, so the same carve_train, issue_train_body and run_train_call -- which stages the boxes.  The graph key needs
 // nothing new: it hashes the whole ovc_model (enc_kind, d_g, trig and the fc_g pointers included); the boxes' contents are never
 // part of it, they are copied into the workspace before the body.
-namespace {
-TrainCall geometric_call(int B, int N, int S, int T, LossHead head) {
-    TrainCall c{B, N, S, T, head};
-    c.geometric = true;
-    return c;
-}
-}  // namespace
-
 extern "C" size_t ovc_train_geometric_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
-    return train_workspace_bytes(m, geometric_call(B, N, 1, T, LossHead::Xent), dropout != 0);
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Geometric}, dropout != 0);
 }
 
 extern "C" int ovc_forward_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
                                               int B, int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                               size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                               const ovc_dropout* dropout) {
-    TrainCall c = geometric_call(B, N, 1, T, LossHead::Xent);
+    TrainCall c{B, N, 1, T, LossHead::Xent, TrainArch::Geometric};
     DropPlan plan{};
     if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
     return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr,
@@ -4039,39 +4037,31 @@ extern "C" int ovc_forward_backward_geometric(const ovc_model* m, const ovc_mode
 }
 
 extern "C" size_t ovc_train_geometric_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    return train_workspace_bytes(m, geometric_call(B, N, S, T, LossHead::RowWeights), false);
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Geometric}, false);
 }
 
 extern "C" int ovc_sequence_backward_geometric(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
                                                int B, int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                                size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
-    return run_train_call(m, grads, geometric_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
-                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Geometric}, features, boxes, ids, nullptr, grad_logp,
+                          workspace, workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // training the attention-on-attention transformer: the opt-in entry points
 // ---------------------------------------------------------------------------------------------
-// ovc_forward_backward / ovc_sequence_backward for the plain encoder + plain decoder with AoA gates (aoa_train_ok): the same
-// TrainCall with `aoa` set, so the same carve_train (which gives every gated site its own u / info / gate), issue_train_body and
+// ovc_forward_backward / ovc_sequence_backward for the plain encoder + plain decoder with AoA gates (TrainArch::Aoa): the same
+// TrainCall with that arch, so the same carve_train (which gives every gated site its own u / info / gate), issue_train_body and
 // run_train_call.  The graph key hashes the whole ovc_model, the gates' pointers included.
-namespace {
-TrainCall aoa_call(int B, int N, int S, int T, LossHead head) {
-    TrainCall c{B, N, S, T, head};
-    c.aoa = true;
-    return c;
-}
-}  // namespace
-
 extern "C" size_t ovc_train_aoa_workspace_bytes(const ovc_model* m, int B, int N, int T, int dropout) {
-    return train_workspace_bytes(m, aoa_call(B, N, 1, T, LossHead::Xent), dropout != 0);
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Aoa}, dropout != 0);
 }
 
 extern "C" int ovc_forward_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                         int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
                                         size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
                                         const ovc_dropout* dropout) {
-    TrainCall c = aoa_call(B, N, 1, T, LossHead::Xent);
+    TrainCall c{B, N, 1, T, LossHead::Xent, TrainArch::Aoa};
     DropPlan plan{};
     if (dropout) TRY(bind_dropout(m, dropout, &plan, c));
     return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr,
@@ -4079,14 +4069,14 @@ extern "C" int ovc_forward_backward_aoa(const ovc_model* m, const ovc_model* gra
 }
 
 extern "C" size_t ovc_train_aoa_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
-    return train_workspace_bytes(m, aoa_call(B, N, S, T, LossHead::RowWeights), false);
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Aoa}, false);
 }
 
 extern "C" int ovc_sequence_backward_aoa(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
                                          int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
                                          size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream) {
-    return run_train_call(m, grads, aoa_call(B, N, S, T, LossHead::RowWeights), features, boxes, ids, nullptr, grad_logp, workspace,
-                          workspace_bytes, nullptr, logp_out, use_graph, stream);
+    return run_train_call(m, grads, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Aoa}, features, boxes, ids, nullptr, grad_logp,
+                          workspace, workspace_bytes, nullptr, logp_out, use_graph, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4118,7 +4108,9 @@ extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features
                                        int* steps_run_out) {
     constexpr SearchForm kModes[3] = {SearchForm::Graph, SearchForm::HostEarly, SearchForm::Gated};
     if (!dropout || !dropout->seed || !slots_out || !m || mode < 0 || mode > 2) return OVC_EINVAL;
-    if (!model_ok(m) || !dropout_train_ok(m, ForwardCall{B, N, 1, m->max_len}) || (long)B * k * m->max_len > (1L << 30)) return OVC_EINVAL;
+    if (!model_ok(m) || !train_scope_ok(m, ForwardCall{B, N, 1, m->max_len}, TrainArch::Standard, true) ||
+        (long)B * k * m->max_len > (1L << 30))
+        return OVC_EINVAL;
     DropPlan plan{};
     bool any = false;
     SearchCall c{B, N, k, out_size, kModes[mode], ids_out, logp_out};

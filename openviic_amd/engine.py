@@ -29,6 +29,7 @@ from . import distill as _distill
 from . import dropout as _dropout
 from . import native
 from . import prefix as _prefix
+from . import train_arch
 from .native import check
 
 
@@ -1030,121 +1031,72 @@ class CaptionEngine:
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------
-    def _check_trainable(self, meshed=False, geometric=False, aoa=False):
+    def _check_trainable(self, arch=None):
         """The backward covers the plain standard transformer, the augmented-memory transformer (plain encoder whose layers'
         self-attention has memory slots, plain decoder) and the CaMo transformer (cross-level encoder, plain decoder) in fp32:
-        anything else is refused before a launch.  ``meshed=True`` / ``geometric=True`` / ``aoa=True``: the opt-in scope instead
-        (``_check_trainable_meshed`` / ``_check_trainable_geometric`` / ``_check_trainable_aoa``); two of them together are
-        refused."""
-        d = self.desc
-        if meshed and geometric:
-            raise native.OvcError("meshed=True and geometric=True name two different models: pass the one this model is")
-        if aoa and (meshed or geometric):
-            raise native.OvcError("aoa=True and {}=True name two different models: pass the one this model is".format(
-                "meshed" if meshed else "geometric"))
+        anything else is refused before a launch.  ``arch``: a ``train_arch.TrainArch`` -- the opt-in scope of that
+        architecture instead, which each block below states; anything else is refused by name."""
+        d, model = self.desc, self.model
         if self.precision != "f32":
             raise native.OvcError("the training backward runs in 'f32' only (precision={!r})".format(self.precision))
-        if meshed:
-            return self._check_trainable_meshed()
-        if geometric:
-            return self._check_trainable_geometric()
-        if aoa:
-            return self._check_trainable_aoa()
-        if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
-            raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
-                                  "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
-        model = self.model
+        key = arch.key if arch is not None else None
+        encoder, decoder = type(model.encoder).__name__, type(model.decoder).__name__
+        # the attention sites: the encoder layers' self-attentions, and the rest -- the cross-level tail's, the decoder's
         layers = [layer.mhatt for layer in model.encoder.layers]
         others = [model.encoder.self_attn] if d.enc_kind == native.ENC_CROSS_LEVEL else []
         others += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
-        if any(m.use_aoa for m in layers + others):
-            raise native.OvcError("the training backward does not cover attention-on-attention gates")
-        # memory slots: in every layer of the plain encoder (the augmented-memory transformer) or nowhere
-        with_memory = [hasattr(m.attention, "m_k") for m in layers]
-        memory_ok = all(with_memory) and d.enc_kind == native.ENC_PLAIN and d.memory > 0
-        if any(hasattr(m.attention, "m_k") for m in others) or (any(with_memory) or d.memory) and not memory_ok:
-            raise native.OvcError("the training backward does not cover attention memory slots")
-        if not hasattr(model.decoder.word_emb, "components"):
-            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
-        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
-        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
-        if extra:
-            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
-
-    def _check_trainable_meshed(self):
-        """``meshed=True``: the meshed-memory transformer -- the multilevel encoder, every layer's self-attention with memory
-        slots (or every one plain), in front of the meshed decoder with plain attentions and one gate per level
-        (``ovc_forward_backward_meshed``).  Anything else is refused by name before a launch."""
-        d = self.desc
-        if d.enc_kind != native.ENC_MULTILEVEL or d.dec_kind != native.DEC_MESHED:
-            raise native.OvcError("meshed=True covers the MultilevelEncoder in front of the MeshedDecoder only (this model has {} / "
-                                  "{}); call without meshed=True".format(type(self.model.encoder).__name__,
-                                                                        type(self.model.decoder).__name__))
-        model = self.model
-        layers = [layer.mhatt for layer in model.encoder.layers]
-        others = [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
-        if any(m.use_aoa for m in layers + others):
-            raise native.OvcError("meshed=True: the training backward does not cover attention-on-attention gates")
-        with_memory = [hasattr(m.attention, "m_k") for m in layers]
-        if any(hasattr(m.attention, "m_k") for m in others):
-            raise native.OvcError("meshed=True: the training backward does not cover memory slots in the decoder's attentions")
-        if any(with_memory) != all(with_memory) or all(with_memory) != (d.memory > 0):
-            raise native.OvcError("meshed=True: every encoder layer's self-attention needs memory slots, or none of them")
-        if d.n_levels != d.n_enc or d.n_levels > native.OVC_MAX_LEVELS or any(
-                len(layer.fc_alphas) != d.n_levels for layer in model.decoder.layers):
-            raise native.OvcError("meshed=True: the decoder needs one gate per encoder layer, at most {} (has {} levels, {} encoder "
-                                  "layers)".format(native.OVC_MAX_LEVELS, d.n_levels, d.n_enc))
-        if not hasattr(model.decoder.word_emb, "components"):
-            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
-        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
-        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
-        if extra:
-            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
-
-    def _check_trainable_geometric(self):
-        """``geometric=True``: the object-relation transformer -- the geometric encoder (plain layers whose attention adds the
-        box-relation bias from ``fc_gs``) in front of the plain decoder (``ovc_forward_backward_geometric``).  Anything else is
-        refused by name before a launch."""
-        d = self.desc
-        if d.enc_kind != native.ENC_GEOMETRIC or d.dec_kind != native.DEC_PLAIN:
-            raise native.OvcError("geometric=True covers the GeometricEncoder in front of the plain Decoder only (this model has {} "
-                                  "/ {}); call without geometric=True".format(type(self.model.encoder).__name__,
-                                                                             type(self.model.decoder).__name__))
-        model = self.model
-        layers = [layer.mhatt for layer in model.encoder.layers]
-        others = [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
-        if any(m.use_aoa for m in layers + others):
-            raise native.OvcError("geometric=True: the training backward does not cover attention-on-attention gates")
-        if any(hasattr(m.attention, "m_k") for m in layers + others) or d.memory:
-            raise native.OvcError("geometric=True: the training backward does not cover attention memory slots")
-        heads = len(model.encoder.fc_gs)
-        if heads > 16 or (d.d_g % 8 != 0 or not 8 <= d.d_g <= 64 if d.trig else d.d_g != 4):
-            raise native.OvcError("geometric=True: the box-relation backward covers at most 16 encoder heads and an embedding of 4 "
-                                  "(plain) or a multiple of 8 up to 64 (trigonometric) values (has {} heads, d_g={}, trig={})".format(
-                                      heads, d.d_g, bool(d.trig)))
-        if not hasattr(model.decoder.word_emb, "components"):
-            raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
-        covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
-        extra = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in covered]
-        if extra:
-            raise native.OvcError("the training backward has no gradient for {}".format(", ".join(extra[:4])))
-
-    def _check_trainable_aoa(self):
-        """``aoa=True``: the attention-on-attention transformer -- the plain encoder and the plain decoder whose attentions carry
-        AoA gates, all of them or any subset (``ovc_forward_backward_aoa``).  Anything else is refused by name before a launch."""
-        d = self.desc
-        if d.enc_kind != native.ENC_PLAIN or d.dec_kind != native.DEC_PLAIN:
-            raise native.OvcError("aoa=True covers the plain Encoder in front of the plain Decoder only (this model has {} / {}); "
-                                  "call without aoa=True".format(type(self.model.encoder).__name__,
-                                                                 type(self.model.decoder).__name__))
-        model = self.model
-        sites = [layer.mhatt for layer in model.encoder.layers]
-        sites += [a for layer in model.decoder.layers for a in (layer.self_attn, layer.enc_attn)]
-        if not any(m.use_aoa for m in sites):
-            raise native.OvcError("aoa=True: this model has no attention-on-attention gates (USE_AOA is off in every attention); "
-                                  "call without aoa=True")
-        if any(hasattr(m.attention, "m_k") for m in sites) or d.memory:
-            raise native.OvcError("aoa=True: the training backward does not cover attention memory slots beside the gates")
+        gated = any(m.use_aoa for m in layers + others)
+        with_memory, others_memory = [hasattr(m.attention, "m_k") for m in layers], any(hasattr(m.attention, "m_k") for m in others)
+        if key is None:
+            if d.enc_kind not in (native.ENC_PLAIN, native.ENC_CROSS_LEVEL) or d.dec_kind != native.DEC_PLAIN:
+                raise native.OvcError("the training backward covers the plain Encoder / Decoder and the cross-level (CaMo) encoder "
+                                      "only (the meshed decoder and the multilevel and geometric encoders are not supported)")
+            if gated:
+                raise native.OvcError("the training backward does not cover attention-on-attention gates")
+            # memory slots: in every layer of the plain encoder (the augmented-memory transformer) or nowhere
+            memory_ok = all(with_memory) and d.enc_kind == native.ENC_PLAIN and d.memory > 0
+            if others_memory or (any(with_memory) or d.memory) and not memory_ok:
+                raise native.OvcError("the training backward does not cover attention memory slots")
+        elif key == "meshed":
+            # the multilevel encoder, every layer's self-attention with memory slots (or every one plain), in front of the meshed
+            # decoder with plain attentions and one gate per level
+            if d.enc_kind != native.ENC_MULTILEVEL or d.dec_kind != native.DEC_MESHED:
+                raise native.OvcError("meshed=True covers the MultilevelEncoder in front of the MeshedDecoder only (this model has "
+                                      "{} / {}); call without meshed=True".format(encoder, decoder))
+            if gated:
+                raise native.OvcError("meshed=True: the training backward does not cover attention-on-attention gates")
+            if others_memory:
+                raise native.OvcError("meshed=True: the training backward does not cover memory slots in the decoder's attentions")
+            if any(with_memory) != all(with_memory) or all(with_memory) != (d.memory > 0):
+                raise native.OvcError("meshed=True: every encoder layer's self-attention needs memory slots, or none of them")
+            if d.n_levels != d.n_enc or d.n_levels > native.OVC_MAX_LEVELS or any(
+                    len(layer.fc_alphas) != d.n_levels for layer in model.decoder.layers):
+                raise native.OvcError("meshed=True: the decoder needs one gate per encoder layer, at most {} (has {} levels, {} "
+                                      "encoder layers)".format(native.OVC_MAX_LEVELS, d.n_levels, d.n_enc))
+        elif key == "geometric":
+            # the geometric encoder (plain layers whose attention adds the box-relation bias from fc_gs), the plain decoder
+            if d.enc_kind != native.ENC_GEOMETRIC or d.dec_kind != native.DEC_PLAIN:
+                raise native.OvcError("geometric=True covers the GeometricEncoder in front of the plain Decoder only (this model "
+                                      "has {} / {}); call without geometric=True".format(encoder, decoder))
+            if gated:
+                raise native.OvcError("geometric=True: the training backward does not cover attention-on-attention gates")
+            if any(with_memory) or others_memory or d.memory:
+                raise native.OvcError("geometric=True: the training backward does not cover attention memory slots")
+            heads = len(model.encoder.fc_gs)
+            if heads > 16 or (d.d_g % 8 != 0 or not 8 <= d.d_g <= 64 if d.trig else d.d_g != 4):
+                raise native.OvcError("geometric=True: the box-relation backward covers at most 16 encoder heads and an embedding "
+                                      "of 4 (plain) or a multiple of 8 up to 64 (trigonometric) values (has {} heads, d_g={}, "
+                                      "trig={})".format(heads, d.d_g, bool(d.trig)))
+        else:
+            # aoa: the plain encoder and decoder whose attentions carry AoA gates, all of them or any subset
+            if d.enc_kind != native.ENC_PLAIN or d.dec_kind != native.DEC_PLAIN:
+                raise native.OvcError("aoa=True covers the plain Encoder in front of the plain Decoder only (this model has {} / "
+                                      "{}); call without aoa=True".format(encoder, decoder))
+            if not gated:
+                raise native.OvcError("aoa=True: this model has no attention-on-attention gates (USE_AOA is off in every "
+                                      "attention); call without aoa=True")
+            if any(with_memory) or others_memory or d.memory:
+                raise native.OvcError("aoa=True: the training backward does not cover attention memory slots beside the gates")
         if not hasattr(model.decoder.word_emb, "components"):
             raise native.OvcError("the training backward covers UsualEmbedding without pretrained vectors only")
         covered = {id(p) for p, _ in _grad_slots(model)} | {id(model.decoder.pos_emb.weight)}
@@ -1191,24 +1143,17 @@ class CaptionEngine:
         call's teacher; ``w`` is part of the graph key, ``P``'s contents never are.  No gradient flows into ``P``.  ``w = 0`` is
         the plain loss and takes the plain path.  Refused together with ``loss``.
 
-        ``meshed=True``: the meshed-memory transformer (``ovc_forward_backward_meshed``; ``_check_trainable_meshed`` states the
+        ``meshed=True``: the meshed-memory transformer (``ovc_forward_backward_meshed``; ``_check_trainable`` states the
         scope).  Refused together with ``dropout``, ``loss`` and ``distill``.
 
-        ``geometric=True``: the object-relation transformer (``ovc_forward_backward_geometric``; ``_check_trainable_geometric``
+        ``geometric=True``: the object-relation transformer (``ovc_forward_backward_geometric``; ``_check_trainable``
         states the scope).  ``boxes`` are required; they are staged before the body, so a replayed graph reads this call's.
         ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``.
 
-        ``aoa=True``: the attention-on-attention transformer (``ovc_forward_backward_aoa``; ``_check_trainable_aoa`` states the
+        ``aoa=True``: the attention-on-attention transformer (``ovc_forward_backward_aoa``; ``_check_trainable`` states the
         scope).  ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``."""
-        if aoa and (loss is not None or distill is not None):
-            raise native.OvcError("forward_backward(aoa=True): the label-smoothed loss and soft targets are out of scope for the "
-                                  "attention-on-attention transformer")
-        if geometric and (loss is not None or distill is not None):
-            raise native.OvcError("forward_backward(geometric=True): the label-smoothed loss and soft targets are out of scope for "
-                                  "the object-relation transformer")
-        if meshed and (dropout is not None or loss is not None or distill is not None):
-            raise native.OvcError("forward_backward(meshed=True): dropout, the label-smoothed loss and soft targets are out of "
-                                  "scope for the meshed-memory transformer")
+        for named in train_arch.named(aoa=aoa, geometric=geometric, meshed=meshed):
+            named.refuse_in_engine("forward_backward", dropout is not None, loss is not None, distill is not None)
         if distill is not None:
             if not isinstance(distill, (tuple, list)) or len(distill) != 2:
                 raise native.OvcError("forward_backward: distill must be a (teacher_log_probs, distill_weight) pair (got {!r})".format(
@@ -1227,12 +1172,13 @@ class CaptionEngine:
             loss = checked_label_smoothing(loss[0], loss[1], "forward_backward", self.desc.vocab)
             if loss == (0.0, "tokens"):
                 loss = None
-        self._check_trainable(meshed, geometric, aoa)
+        arch = train_arch.resolve(meshed, geometric, aoa)
+        self._check_trainable(arch)
         features, boxes = self._checked_inputs(features, boxes)
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, meshed=meshed, geometric=geometric, aoa=aoa)
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, arch=arch)
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -1249,50 +1195,34 @@ class CaptionEngine:
     }
 
     _DISTILL_FORM = ("ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill")
-    # sequence -> the opt-in forms of the meshed-memory transformer
-    _MESHED_FORMS = {False: ("ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed"),
-                     True: ("ovc_train_meshed_beams_workspace_bytes", "ovc_sequence_backward_meshed")}
 
-    # sequence -> the opt-in forms of the object-relation transformer; the loss form takes the dropout table or NULL
-    _GEOMETRIC_FORMS = {False: ("ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric"),
-                        True: ("ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric")}
-
-    # ... and of the attention-on-attention transformer, likewise
-    _AOA_FORMS = {False: ("ovc_train_aoa_workspace_bytes", "ovc_forward_backward_aoa"),
-                  True: ("ovc_train_aoa_beams_workspace_bytes", "ovc_sequence_backward_aoa")}
-
-    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, meshed=False, geometric=False, aoa=False):
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, arch=None):
         """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
         T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
         on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
-        soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``meshed``: the
-        meshed-memory transformer's form (no loss, dropout or distill with it: the callers refuse them).  ``geometric``: the
-        object-relation transformer's form (no loss or distill, and no dropout with ``sequence``: the callers refuse them).
-        ``aoa``: the attention-on-attention transformer's form, under the same rules."""
-        sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
-        if meshed:
-            sizer, entry = self._MESHED_FORMS[bool(sequence)]
-        if distill is not None:
-            sizer, entry = self._DISTILL_FORM
+        soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``arch``: a
+        ``train_arch.TrainArch`` -- that architecture's form (what it does not combine with, the callers have refused)."""
         drop = () if table_drop is None else (ctypes.byref(table_drop),)
+        flagged = (1 if drop else 0,), (drop[0] if drop else None,)      # a sizer's dropout flag, the table or NULL behind the arguments
         size_tail, tail = (), (*search, *drop)
-        if loss is not None:
-            size_tail = (1 if drop else 0,)
-            tail = (ctypes.byref(native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])), drop[0] if drop else None)
-        if distill is not None:
-            size_tail = (1 if drop else 0,)
-            tail = (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), drop[0] if drop else None)
-        if geometric or aoa:
-            sizer, entry = (self._GEOMETRIC_FORMS if geometric else self._AOA_FORMS)[bool(sequence)]
-            if not sequence:
-                size_tail, tail = (1 if drop else 0,), (drop[0] if drop else None,)
+        if arch is not None:
+            sizer, entry = arch.sequence_form if sequence else arch.loss_form
+            if arch.loss_dropout and not sequence:
+                size_tail, tail = flagged
+        elif distill is not None:
+            sizer, entry = self._DISTILL_FORM
+            size_tail, tail = flagged[0], (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), *flagged[1])
+        else:
+            sizer, entry = self._TRAIN_FORMS[sequence, loss is not None, table_drop is not None]
+            if loss is not None:
+                size_tail, tail = flagged[0], (ctypes.byref(native.Loss(loss[0], native.LOSS_REDUCTIONS[loss[1]])), *flagged[1])
         self._check_pointers()
         ws, need = self._sized_workspace(
             "sequence" if sequence else "train", sizer, (*shape, *size_tail),
             "unsupported training configuration ({}, V={}; see {})".format(
                 ", ".join("{}={}".format(n, v) for n, v in zip("BNST" if sequence else "BNT", shape)), self.desc.vocab,
-                sizer if meshed or geometric or aoa else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
+                sizer if arch is not None else self._TRAIN_FORMS[sequence, False, False][0]), shape[2] if sequence else None)
         return entry, shape, ws, need, tail
 
     def _run_train_form(self, form, features, boxes, inputs, out_shape, arena, use_graph):
@@ -1356,15 +1286,10 @@ class CaptionEngine:
         ``geometric=True``: the object-relation transformer (``ovc_sequence_backward_geometric``), ``boxes`` required; refused
         together with ``dropout``.  ``aoa=True``: the attention-on-attention transformer (``ovc_sequence_backward_aoa``); refused
         together with ``dropout``."""
-        if aoa and dropout is not None:
-            raise native.OvcError("sequence_backward(aoa=True): the sequence form under dropout is out of scope for the "
-                                  "attention-on-attention transformer")
-        if meshed and dropout is not None:
-            raise native.OvcError("sequence_backward(meshed=True): dropout is out of scope for the meshed-memory transformer")
-        if geometric and dropout is not None:
-            raise native.OvcError("sequence_backward(geometric=True): the sequence form under dropout is out of scope for the "
-                                  "object-relation transformer")
-        self._check_trainable(meshed, geometric, aoa)
+        for named in train_arch.named(aoa=aoa, meshed=meshed, geometric=geometric):
+            named.refuse_in_engine("sequence_backward", dropout is not None)
+        arch = train_arch.resolve(meshed, geometric, aoa)
+        self._check_trainable(arch)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
         if table_drop is not None:
             if (not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or
@@ -1386,8 +1311,7 @@ class CaptionEngine:
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
         form = self._train_form(True, None, table_drop, (B, N, S, T),
-                                () if table_drop is None else (int(beam_size), slots.data_ptr()), meshed=meshed, geometric=geometric,
-                                aoa=aoa)
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()), arch=arch)
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
         arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,

@@ -286,7 +286,7 @@ def test_python_refusals_that_need_no_device():
     with pytest.raises(native.OvcError, match="train\\(\\) mode with dropout"):
         model.xe_loss(items, aoa=True)
     assert model._engine is None                                           # no engine was built for any of them
-    assert architectures._loss_head(architectures._AOA) == {"aoa": True}
-    assert architectures._loss_head(architectures._GEOMETRIC) == {"geometric": True}
-    assert architectures._loss_head(architectures._MESHED) == {"meshed": True}
+    assert architectures._loss_head(None, architectures.train_arch.TRAIN_ARCHS["aoa"]) == {"aoa": True}
+    assert architectures._loss_head(None, architectures.train_arch.TRAIN_ARCHS["geometric"]) == {"geometric": True}
+    assert architectures._loss_head(None, architectures.train_arch.TRAIN_ARCHS["meshed"]) == {"meshed": True}
     assert architectures._loss_head(None) == {"loss": None}

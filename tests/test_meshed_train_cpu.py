@@ -178,5 +178,5 @@ def test_python_refusals_that_need_no_device():
         with pytest.raises(native.OvcError, match=match):
             call()
     assert model._engine is None                                           # no engine was built for any of them
-    assert architectures._loss_head(architectures._MESHED) == {"meshed": True}
+    assert architectures._loss_head(None, architectures.train_arch.TRAIN_ARCHS["meshed"]) == {"meshed": True}
     assert architectures._loss_head(None) == {"loss": None}

@@ -48,6 +48,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 
+from openviic_amd import train_arch                                                  # noqa: E402
 from openviic_amd.builders import build_model                                        # noqa: E402
 from openviic_amd.config import model_config                                         # noqa: E402
 from openviic_amd.instance import InstanceList                                       # noqa: E402
@@ -323,7 +324,8 @@ def main():
         ap.error("--fused needs --reward device --optimizer engine")
     if "none" in args.optimizer and len(args.optimizer) > 1:
         ap.error("--optimizer none stands alone")
-    meshed = dict(meshed=True) if args.variant == "meshed_memory_transformer" else {}
+    arch = train_arch.of_variant(args.variant)
+    meshed = arch.keywords() if arch is not None else {}       # of --variant's choices only the meshed-memory transformer has one
     if meshed and (args.reward != "none" or args.optimizer != ["none"] or args.dropout or args.fused):
         ap.error("meshed_memory_transformer goes with --reward none --optimizer none, without --dropout or --fused")
     assert torch.cuda.is_available(), "needs a HIP device"

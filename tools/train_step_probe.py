@@ -58,6 +58,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from openviic_amd import train_arch                                                  # noqa: E402
 from openviic_amd.builders import build_model                                        # noqa: E402
 from openviic_amd.config import model_config                                         # noqa: E402
 from openviic_amd.instance import InstanceList                                       # noqa: E402
@@ -229,23 +230,20 @@ def variant_dims(variant):
 
 
 def loss_kw(variant, dropout):
-    """The keywords of ``xe_loss`` for a variant: the meshed-memory transformer is opt-in and has no dropout form, the
-    object-relation and the attention-on-attention transformers are opt-in too."""
-    if variant == GEOMETRIC:
-        return dict(geometric=True, dropout=dropout)
-    if variant == AOA:
-        return dict(aoa=True, dropout=dropout)
-    return dict(meshed=True) if variant == MESHED else dict(dropout=dropout)
+    """The keywords of ``xe_loss`` for a variant: an architecture with a keyword of its own (``train_arch.TRAIN_ARCHS``) is
+    opt-in, and takes ``dropout`` where its loss form has it."""
+    arch = train_arch.of_variant(variant)
+    if arch is None:
+        return dict(dropout=dropout)
+    return dict(arch.keywords(), dropout=dropout) if arch.loss_dropout else arch.keywords()
 
 
 def train_sizer(lib, variant, dropout):
-    if variant == MESHED:
-        return lib.ovc_train_meshed_workspace_bytes
-    if variant == GEOMETRIC:
-        return lambda d, B, N, T: lib.ovc_train_geometric_workspace_bytes(d, B, N, T, 1 if dropout else 0)
-    if variant == AOA:
-        return lambda d, B, N, T: lib.ovc_train_aoa_workspace_bytes(d, B, N, T, 1 if dropout else 0)
-    return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
+    arch = train_arch.of_variant(variant)
+    if arch is None:
+        return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
+    sizer = getattr(lib, arch.loss_form[0])
+    return (lambda d, B, N, T: sizer(d, B, N, T, 1 if dropout else 0)) if arch.loss_dropout else sizer
 
 
 def alternate_variants(args, vocab, V, T, N, D):

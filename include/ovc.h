@@ -412,10 +412,16 @@ int ovc_scale(const float* x, const float* scale, float* y, long n, ovc_stream s
  *   1 + 3 OVC_MAX_LAYERS + 4 l + {0, 1, 2, 3}   decoder.layers.l.{self_attn.dropout, enc_attn.dropout, pwff.dropout_2, pwff.dropout}
  * Rows are the product's rows: b * N + n on the encoder side, b * T + t on the decoder side.
  * Mask (counter-based, Philox4x32-10 -- the generator torch uses): idx = row * cols + col (64-bit),
- *   r = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), site, 0), key = (lo32(seed), hi32(seed)))[idx & 3],
+ *   r = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), site, level), key = (lo32(seed), hi32(seed)))[idx & 3],
  *   keep = r >= thr with thr = uint32(floor(p * 2^32 + 0.5)) (clamped to 2^32 - 1), out = keep ? x * s : 0, s = fp32(1 / (1 - p)).
- * A pure function of (seed, site, row, col): the same masks, and so the same gradient bits, whatever the tiling, stream or graph
- * replay.  The backward regenerates the masks instead of storing them. */
+ * level is 0 at every site of every model but one: the meshed decoder applies its single enc_attn.dropout module once per encoder
+ * level (decoders.py:51-73), each application with a mask of its own, and there -- site 1 + 3 OVC_MAX_LAYERS + 4 l + 1 in
+ * ovc_forward_backward_level_dropout -- level is the encoder level lvl in 0 .. n_levels - 1, with the decoder row b * T + t the same
+ * at every level and p that module's one p (dec[l][1]):
+ *   e_lvl = LN(x1 + (keep(lvl, row, col) ? (attc_lvl Wo + bo) * s : 0)).
+ * Level 0's mask is the plain rule's, bit for bit.
+ * A pure function of (seed, site, level, row, col): the same masks, and so the same gradient bits, whatever the tiling, stream or
+ * graph replay.  The backward regenerates the masks instead of storing them. */
 #define OVC_DROPOUT_SITES (1 + 3 * OVC_MAX_LAYERS + 4 * OVC_MAX_LAYERS)
 typedef struct {
     const int64_t* seed;                 /* device: the 64-bit seed of this step (read on the stream; never baked into a graph) */
@@ -439,6 +445,9 @@ int ovc_forward_backward_dropout(const ovc_model* m, const ovc_model* grads, con
 /* keep[r * cols + c] = 1 if element (r, c) of site `site` is kept under *seed and p, else 0 -- the mask the kernels apply
  * (tests compare it with openviic_amd/dropout.py).  p in [0, 1), 0 <= site < OVC_DROPOUT_SITES. */
 int ovc_dropout_mask(const int64_t* seed, int site, long rows, long cols, float p, uint8_t* keep, ovc_stream stream);
+/* The same at encoder level `level` (counter word 3; 0 <= level < OVC_MAX_LEVELS): the mask ovc_forward_backward_level_dropout
+ * applies to level `level` of a meshed decoder layer's enc_attn.dropout.  level == 0 is ovc_dropout_mask.  Appended to ABI 8. */
+int ovc_dropout_mask_level(const int64_t* seed, int site, int level, long rows, long cols, float p, uint8_t* keep, ovc_stream stream);
 
 /* Label-smoothed cross-entropy (the reference's loss_utils/label_smoothing.py, LabelSmoothing(size = V, padding_idx = pad,
  * smoothing = s) on the log-probabilities [R, V], R = B*T, and the targets).  Appended to ABI 8.  With conf = 1 - s, u = s / (V - 2),
@@ -497,7 +506,8 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
  *   every decoder self_att and cross_att plain: no AoA gates, no memory slots;  alpha[lvl].w given for every level, in the
  *   model and (with .b where the model has one) in grads;
  *   the fused vocabulary tail and the 32-bit descriptor limits of ovc_forward_backward, the latter also over levels * rows rows.
- * Dropout is taken as the identity: there is no dropout form (ovc_dropout has no site per level).
+ * Dropout is taken as the identity by these two; the loss form under dropout is ovc_forward_backward_level_dropout below, the
+ * sequence form has none.
  * ovc_train_meshed_workspace_bytes / ovc_train_meshed_beams_workspace_bytes: bytes of workspace, 0 when unsupported. */
 size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, int N, int T);
 int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
@@ -507,6 +517,23 @@ size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int B, int N, 
 int ovc_sequence_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
                                  int S, const int64_t* ids, const float* grad_logp, int T, void* workspace, size_t workspace_bytes,
                                  float* logp_out, int use_graph, ovc_stream stream);
+/* ovc_forward_backward_meshed under dropout (the reference's train() mode for this model; appended to ABI 8): the arguments of
+ * ovc_forward_backward_meshed and an ovc_dropout table behind them.  Every site is ovc_forward_backward_dropout's -- the feature
+ * embedding, the multilevel encoder's three per layer (with or without memory slots), the decoder's self_attn.dropout and the two of
+ * its FFN -- and keeps that rule; enc_attn.dropout (dec[l][1]) is masked per encoder level, see the counter rule above: the shared
+ * output projection's epilogue keys product row m of its levels * rows rows as (level m / rows, row m % rows), and the backward
+ * regenerates the same masks for the projection's gradient while the residual's share d(x1) += sum_lvl d(ymesh_lvl) stays
+ * unmasked, levels ascending.  Scope: that of ovc_forward_backward_meshed; a null dropout or seed, any p outside [0, 1) (NaN
+ * included) or any other model: OVC_EINVAL, nothing launched.  The seed is copied into the workspace outside the captured body and
+ * the p values are part of the graph's key, as in ovc_forward_backward_dropout.  With every p == 0 this is
+ * ovc_forward_backward_meshed launch for launch (same bits, ovc_train_meshed_workspace_bytes suffices).
+ * ovc_level_dropout_workspace_bytes: bytes of workspace for calls with a site active -- ovc_train_meshed_workspace_bytes' carve plus
+ * the projection gradients' [levels * rows][d] buffer and the seed slot; 0 when unsupported. */
+size_t ovc_level_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T);
+int ovc_forward_backward_level_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                       int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                       size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                       const ovc_dropout* dropout);
 /* Test hook (tests/test_meshed_train_gpu.py): the backward of ovc_debug_meshed_mix as the meshed training calls launch it.  dmixed
  * [n], alpha / enc / denc / dalpha [levels][n]:  denc[l] = (dmixed * sigmoid(alpha[l])) / divisor,  dalpha[l] = ((dmixed * enc[l]) *
  * sigmoid'(alpha[l])) / divisor, finite for every finite alpha.  OVC_EINVAL, nothing written: n <= 0 or n % 4 != 0, levels outside

@@ -70,11 +70,12 @@ def _apply_step_gradients(eng, optimizer, grads, max_norm):
     optimizer.apply_gradients({p: g for p, g in zip(eng.gradient_parameters(), grads) if p.requires_grad}, max_norm=max_norm)
 
 
-def _loss_head(head, arch=None):
+def _loss_head(head, arch=None, level=False):
     """``forward_backward``'s keyword for a call's loss -- the NLL, the smoothed loss or soft targets, as ``_xe_call`` returned it
-    -- or, for an architecture with a keyword of its own (``train_arch.TrainArch``), that keyword: its NLL."""
+    -- or, for an architecture with a keyword of its own (``train_arch.TrainArch``), that keyword: its NLL (``level``: under
+    ``dropout="levels"``, its ``level_dropout_form``)."""
     if arch is not None:
-        return arch.keywords()
+        return dict(arch.keywords(), level_dropout=True) if level else arch.keywords()
     return {"distill": tuple(head)} if isinstance(head, _distill.SoftTargets) else {"loss": head}
 
 
@@ -85,6 +86,37 @@ def _named_arch(what, meshed, geometric, aoa):
     if arch is not None:
         arch.refuse_with(what, meshed=meshed, geometric=geometric)
     return arch
+
+
+def _level_dropout(what, dropout, arch, **others):
+    """``dropout`` given as a string, for ``xe_loss`` / ``xe_step``: True for ``dropout="levels"`` on the architecture that has that
+    form (``train_arch.TrainArch.level_dropout_form``), with none of ``others`` (what that form does not combine with) set;
+    every other string, the spelling without that architecture's keyword and the combinations are refused by name.  False for
+    anything that is no string: the plain dropout rules apply."""
+    if not isinstance(dropout, str):
+        return False
+    spelled = "{}(dropout={!r})".format(what, dropout)
+    if dropout != train_arch.LEVEL_DROPOUT:
+        raise engine.native.OvcError("{}: dropout is False, True or \"{}\" (the meshed-memory transformer's: a mask per encoder "
+                                     "level)".format(spelled, train_arch.LEVEL_DROPOUT))
+    if arch is None or not arch.takes_level_dropout(dropout):
+        raise engine.native.OvcError("{}: a mask per encoder level is the meshed-memory transformer's dropout -- it needs meshed=True "
+                                     "and no other architecture's keyword{}".format(
+                                         spelled, "" if arch is None else " ({}=True takes dropout=True)".format(arch.key)
+                                         if arch.loss_dropout else " ({}=True was given)".format(arch.key)))
+    for name, value in others.items():
+        if value:
+            raise engine.native.OvcError("{}({}=True, dropout={!r}, {}=...): {} is out of scope for {}'s training under "
+                                         "dropout".format(what, arch.key, dropout, name, name, arch.noun))
+    return True
+
+
+def _refuse_level_dropout(what, dropout):
+    """``dropout`` given as a string where only ``xe_loss`` / ``xe_step`` take one: refused by name."""
+    if isinstance(dropout, str):
+        raise engine.native.OvcError("{}(dropout={!r}): dropout is False or True here -- dropout=\"{}\" is xe_loss's and xe_step's, "
+                                     "the sequence form and the search of the meshed-memory transformer have no dropout "
+                                     "form".format(what, dropout, train_arch.LEVEL_DROPOUT))
 
 
 def _require_boxes(what, input_features):
@@ -295,6 +327,15 @@ class BaseTransformer(Module):
         ``dropout=True``, ``label_smoothing`` / ``reduction`` or ``teacher_log_probs`` / ``distill_weight``, and (the refusal
         above) a ``train()``-mode model with a live dropout.
 
+        ``meshed=True, dropout="levels"``: that model under dropout, as the reference trains it
+        (``ovc_forward_backward_level_dropout``).  The meshed layer applies its ONE ``enc_attn.dropout`` once per encoder level
+        with an independent mask each time: level ``lvl`` of layer ``l`` is masked at ``dec_site(l, 1)`` with ``level = lvl`` over
+        the rows ``b * T + t`` (``openviic_amd.dropout``), every other ``nn.Dropout`` at its plain site with its own ``p``.  Seed,
+        ``generator``, ``eval()`` mode and ``p == 0`` as for ``dropout=True``.  Refused by name before any launch and any draw:
+        ``dropout="levels"`` without ``meshed=True``, with another architecture's keyword or on a model the meshed scope
+        refuses, any other string, ``label_smoothing`` / ``reduction`` / ``teacher_log_probs`` / ``distill_weight`` beside it,
+        and a ``p >= 1`` (naming the module).
+
         ``geometric=True``: the object-relation transformer -- the ``GeometricEncoder`` in front of the plain ``Decoder`` -- on
         ``ovc_forward_backward_geometric``; the per-head ``encoder.fc_gs`` get their gradients like every other parameter, the
         boxes get none.  ``dropout=True`` works as for the standard transformer (the encoder's sites are the plain encoder's).
@@ -312,7 +353,7 @@ class BaseTransformer(Module):
         eng, drop, smoothed, arch, inputs = self._xe_call("xe_loss", input_features, dropout, generator, label_smoothing, reduction,
                                                           teacher_log_probs=teacher_log_probs, distill_weight=distill_weight,
                                                           meshed=meshed, geometric=geometric, aoa=aoa)
-        return _XeLoss.apply(eng, drop, _loss_head(smoothed, arch), *inputs, *eng.gradient_parameters())
+        return _XeLoss.apply(eng, drop, _loss_head(smoothed, arch, isinstance(dropout, str)), *inputs, *eng.gradient_parameters())
 
     def _xe_call(self, what, input_features, dropout, generator, label_smoothing, reduction, optimizer=None, teacher_log_probs=None,
                  distill_weight=None, meshed=False, geometric=False, aoa=False):
@@ -321,8 +362,10 @@ class BaseTransformer(Module):
         dropout (probs, seed) or None, smoothed loss / soft targets or None, the call's ``train_arch.TrainArch`` or None,
         (features, boxes, caption tokens, targets))``."""
         arch = _named_arch(what, meshed, geometric, aoa)
+        level = _level_dropout(what, dropout, arch, label_smoothing=label_smoothing is not None, reduction=reduction is not None,
+                               teacher_log_probs=teacher_log_probs is not None, distill_weight=distill_weight is not None)
         if arch is not None:
-            arch.refuse_with(what, dropout=dropout and not arch.loss_dropout, label_smoothing=label_smoothing is not None,
+            arch.refuse_with(what, dropout=dropout and not arch.loss_dropout and not level, label_smoothing=label_smoothing is not None,
                              reduction=reduction is not None, teacher_log_probs=teacher_log_probs is not None,
                              distill_weight=distill_weight is not None)
         soft = None
@@ -387,7 +430,8 @@ class BaseTransformer(Module):
         ``label_smoothing`` / ``reduction``: as ``xe_loss`` takes them -- the label-smoothed loss in the four lines and here, with
         the same refusals before any launch and any draw.  ``teacher_log_probs`` / ``distill_weight``: as ``xe_loss`` takes them
         -- the soft-target loss in the four lines and here.  ``meshed``: as ``xe_loss`` takes it -- the meshed-memory transformer,
-        ``xe_loss(items, meshed=True)`` in the four lines.  ``geometric``: likewise the object-relation transformer,
+        ``xe_loss(items, meshed=True)`` in the four lines, and with ``dropout="levels"`` ``xe_loss(items, meshed=True,
+        dropout="levels")``.  ``geometric``: likewise the object-relation transformer,
         ``xe_loss(items, dropout=..., geometric=True)`` in the four lines.  ``aoa``: likewise the attention-on-attention
         transformer, ``xe_loss(items, dropout=..., aoa=True)`` in the four lines.
 
@@ -400,7 +444,8 @@ class BaseTransformer(Module):
         eng, drop, smoothed, arch, inputs = self._xe_call("xe_step", input_features, dropout, generator, label_smoothing, reduction,
                                                           optimizer, teacher_log_probs=teacher_log_probs,
                                                           distill_weight=distill_weight, meshed=meshed, geometric=geometric, aoa=aoa)
-        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(), **_loss_head(smoothed, arch))
+        loss, _, grads = eng.forward_backward(*inputs, dropout=drop, arena=eng.step_arena(),
+                                              **_loss_head(smoothed, arch, isinstance(dropout, str)))
         _apply_step_gradients(eng, optimizer, grads, max_norm)
         return loss
 
@@ -463,6 +508,7 @@ class BaseTransformer(Module):
         of the lines above is then ``model.beam_search(items, B, k, out_size=k, aoa=True)``.  Refused by name before any launch
         or draw: any other model, and ``aoa=True`` together with ``meshed=True``, ``geometric=True``, ``dropout=True`` or
         ``sample=True``."""
+        _refuse_level_dropout("scst_step", dropout)
         arch = _named_arch("scst_step", meshed, geometric, aoa)
         if arch is not None:
             arch.refuse_with("scst_step", dropout=dropout, sample=sample)
@@ -610,6 +656,7 @@ class BaseTransformer(Module):
         refusals and ``meshed=True`` / ``geometric=True`` among them.
         """
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
+        _refuse_level_dropout("beam_search", dropout)
         arch = _named_arch("beam_search", meshed, geometric, aoa)
         if arch is not None:
             arch.refuse_with("beam_search", dropout=dropout)

@@ -12,7 +12,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "beam.hip", "backward.hip", "engine.hip", "cider.hip", "optim.hip", "scst.hip", "metrics.hip", "consensus.hip"]
+SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "beam.hip", "backward.hip", "engine.hip", "cider.hip", "optim.hip", "scst.hip", "metrics.hip", "consensus.hip", "level_dropout.hip"]
 HEADERS = ["common.h", "backward.h", "box_relation.h","dropout.h", "gemm_split.h", "gemm_rows16.h", "gemm_f32_body.inc", os.path.join("..", "..", "include", "ovc.h")] + sorted(
     os.path.join("bodies", f) for f in os.listdir(os.path.join(HERE, "bodies")) if f.endswith(".inc"))   # kernel bodies shared by gated instances
 LIBRARY = os.path.join(HERE, "libovc.so")

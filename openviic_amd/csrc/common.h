@@ -168,6 +168,10 @@ struct GemmLaunchOpts {
     uint32_t drop_site = 0, drop_thr = 0;
     float drop_scale = 1.f;
     int drop_cols = 0;
+    // > 0 (with drop_seed): the LEVEL-KEYED dropout instance -- the product's rows are stacked blocks of drop_level_rows rows, one
+    // block per encoder level (the meshed decoder's shared output projection, GemmArgs::res_mod == drop_level_rows), and row m is
+    // masked as (level m / drop_level_rows, row m % drop_level_rows): ovc_dropout_keep_level
+    int drop_level_rows = 0;
 };
 
 // Launches C = act([A1|A2] W^T + bias) + R on `stream`; returns an OVC_* code.

@@ -3,11 +3,14 @@
 // openviic_amd/dropout.py.
 //
 //   idx  = row * cols + col                          (64-bit; cols = the product's logical column count)
-//   r    = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), site, 0), key = (lo32(seed), hi32(seed)))[idx & 3]
+//   r    = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), site, level), key = (lo32(seed), hi32(seed)))[idx & 3]
 //   keep = r >= thr,  thr = uint32(floor(p * 2^32 + 0.5)) clamped to 2^32 - 1;  out = keep ? x * s : 0,  s = fp32(1 / (1 - p))
 //
-// The decision is a pure function of (seed, site, row, col): never of the tiling, grid, stream or batch position of a launch, so
-// the forward's masks and the backward's regenerated ones agree, and every tiling / graph replay gives the same bits.
+// level is 0 everywhere but at the meshed decoder's enc_attn.dropout, which one module applies once per encoder level: there it is
+// the level, with the decoder row b * T + t the same at every level (ovc_dropout_keep_level).
+//
+// The decision is a pure function of (seed, site, level, row, col): never of the tiling, grid, stream or batch position of a
+// launch, so the forward's masks and the backward's regenerated ones agree, and every tiling / graph replay gives the same bits.
 #pragma once
 #include "common.h"
 
@@ -44,6 +47,14 @@ __device__ __forceinline__ uint32_t ovc_philox_word(uint64_t key, uint32_t c0, u
 __device__ __forceinline__ bool ovc_dropout_keep(uint64_t seed, uint32_t site, uint64_t idx, uint32_t thr) {
     const uint64_t g = idx >> 2;
     return ovc_philox_word(seed, (uint32_t)g, (uint32_t)(g >> 32), site, 0u, (int)(idx & 3)) >= thr;
+}
+
+// The level-keyed decision (ovc_forward_backward_level_dropout): ONE nn.Dropout module applied once per encoder level, as the meshed
+// decoder applies enc_attn.dropout -- the level is counter word 3, so the levels' masks are independent, level 0 is
+// ovc_dropout_keep bit for bit, and the mask is a pure function of (seed, site, level, row, col).
+__device__ __forceinline__ bool ovc_dropout_keep_level(uint64_t seed, uint32_t site, uint32_t level, uint64_t idx, uint32_t thr) {
+    const uint64_t g = idx >> 2;
+    return ovc_philox_word(seed, (uint32_t)g, (uint32_t)(g >> 32), site, level, (int)(idx & 3)) >= thr;
 }
 
 // The four keep decisions of element group g (elements 4 g .. 4 g + 3 of the site's index space) as bits 0..3: one Philox block.

@@ -1275,7 +1275,11 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
             o.A1 = b.attc; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
             o.R = b.x1; o.ldr = d; o.res_mod = rows;
             o.seg[0] = e.seg(dl.cross_att.o, b.ymesh);
-            TRY(e.gemm(o));
+            // enc_attn.dropout, ONE module applied once per level: the level-keyed instance masks product row m as (level m / rows,
+            // decoder row m % rows), so ymesh holds the dropped sums (site not active: the plain launch)
+            GemmLaunchOpts level_drop = e.drop_opts(p.site(l, 1), d);
+            if (level_drop.drop_seed) level_drop.drop_level_rows = rows;
+            TRY(e.gemm(o, level_drop));
             RUN(ovc_layer_norm_gated(b.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
                                      b.enc_att, lv * rows, d, s, e.gate));
         } else {
@@ -2991,7 +2995,7 @@ enum class LossHead {
     SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The twenty-four exported functions (twelve entry points, twelve sizers) fill one of these, and the
+// One training call, described once.  The twenty-six exported functions (thirteen entry points, thirteen sizers) fill one of these, and the
 // scope (call_ok), the workspace layout and size (carve_train), the captured body (issue_train_body), the graph key
 // (train_graph_key) and the launches around the body (run_train_call) are functions of it: a sizer and the entry point that carves
 // its buffer cannot disagree.
@@ -3146,7 +3150,9 @@ bool mha_plain_or_gated(const ovc_mha& a) { return mha_plain(a) || mha_gated(a);
 //              also with memory slots in every layer (the augmented-memory transformer).  Under dropout the plain encoder only:
 //              the cross-level tail applies its one nn.Dropout twice and has no site of its own.
 //   Meshed     the multilevel encoder, every layer's self-attention with memory slots (or every layer plain), in front of the
-//              meshed decoder with plain attentions and a gate per level.  No dropout form: ovc_dropout has no per-level site.
+//              meshed decoder with plain attentions and a gate per level.  The loss form takes a dropout plan
+//              (ovc_forward_backward_level_dropout): enc_attn.dropout, one module applied once per level, is masked per (level, row)
+//              at dec_site(l, 1); every other site is the plain one.  The sequence form takes none.
 //   Geometric  the geometric (object-relation) encoder -- plain layers whose scores take the box-relation bias
 //              log(max(relu(fc_g(emb(boxes))), 1e-6)) -- in front of the plain decoder.  The bias's backward
 //              (ovc_bw_box_relation) covers h <= 16, d_g == 4 without and a multiple of 8 up to 64 with the trigonometric
@@ -3175,9 +3181,11 @@ bool train_kinds_ok(const ovc_model* m, TrainArch arch) {
     return false;
 }
 
-// a dropout plan: where the architecture has a dropout form at all
-bool train_plan_ok(const ovc_model* m, TrainArch arch) {
-    return arch == TrainArch::Standard ? m->enc_kind == OVC_ENC_PLAIN : arch != TrainArch::Meshed;
+// a dropout plan: where the architecture has a dropout form at all.  Meshed: the loss form alone, whose one entry point
+// (ovc_forward_backward_level_dropout) binds the plan; the sequence form has none
+bool train_plan_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch) {
+    if (arch == TrainArch::Meshed) return !c.row_weights;
+    return arch != TrainArch::Standard || m->enc_kind == OVC_ENC_PLAIN;
 }
 
 // every encoder layer's self-attention passes `enc`, every decoder attention (self and cross) `dec`
@@ -3230,7 +3238,7 @@ bool train_extras_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch) {
 // The scope of a training call, for its sizer and its entry point alike -- and, as (Standard, plan), of the search under dropout.
 // An architecture is reached through its own entry points alone: nothing here derives it from the model.
 bool train_scope_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch, bool plan) {
-    if (!forward_ok(m, c) || !train_kinds_ok(m, arch) || (plan && !train_plan_ok(m, arch))) return false;
+    if (!forward_ok(m, c) || !train_kinds_ok(m, arch) || (plan && !train_plan_ok(m, c, arch))) return false;
     const SiteOk enc = arch == TrainArch::Aoa ? mha_plain_or_gated : m->memory != 0 ? mha_memory : mha_plain;
     if (!train_sites_ok(m, enc, arch == TrainArch::Aoa ? mha_plain_or_gated : mha_plain)) return false;
     if (!train_extras_ok(m, c, arch)) return false;
@@ -3295,12 +3303,17 @@ int bw_weight(Engine& e, TrainWs& t, const float* dY, int ldy, int n, const floa
 }
 
 // LayerNorm of the pre-norm sum y: t.dy = d(y) from dout; gamma / beta gradients.  With the dropout site `site` active on the
-// projection inside y, also t.dproj = keep * s * t.dy, that projection's gradient (proj_grad)
+// projection inside y, also t.dproj = keep * s * t.dy, that projection's gradient (proj_grad).  level_rows > 0: the rows are stacked
+// blocks of level_rows rows, one per encoder level, and the site's mask is keyed by (level, row within the block) -- the meshed
+// decoder's shared AddNorm
 int bw_norm(Engine& e, TrainWs& t, const float* y, const ovc_norm& n, const ovc_norm& gn, const float* dout, const uint8_t* zero_rows,
-            int rows, int site = -1) {
+            int rows, int site = -1, int level_rows = 0) {
     hipStream_t s = e.stream;
     const int d = e.m->d_model;
-    if (e.row_keyed(site))
+    if (level_rows > 0 && e.site_on(site))
+        RUN(ovc_bw_layer_norm_dropout_level(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d),
+                                            level_rows, s));
+    else if (e.row_keyed(site))
         RUN(ovc_bw_layer_norm_dropout_mapped(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d),
                                              e.maskrow, s));
     else if (e.site_on(site))
@@ -3508,7 +3521,7 @@ int bw_meshed_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, c
     const size_t nrd = (size_t)rows * d, nd = (size_t)BN * d;
     const int rp = (int)pad4(rows);
     // FFN (pad-token rows were cleared after its norm: they pass nothing) -> t.dx1 = d(mixed)
-    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.mixed, p.ff, p.yf, dout, w.padflag, rows));
+    TRY(bw_ffn(e, t, dl.ffn, gl.ffn, p.mixed, p.ff, p.yf, dout, w.padflag, rows, dec_site(l, 2), dec_site(l, 3)));
     // the mix: d(e_l) and d(a_l) of every level from one read of d(mixed)
     RUN(ovc_bw_meshed_mix(t.dx1, p.alpha, p.enc_att, lv, (long)nrd, sqrtf((float)lv), t.ms_de, t.ms_da, s));
     // the gates: dW_l = d(a_l)^T [x1 ; e_l] with the concatenated operand staged transposed (K = rows ascending), db_l its row sums,
@@ -3528,12 +3541,15 @@ int bw_meshed_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, c
         TRY(bw_mm(e, da, d, rows, d, t.wt, d, t.ms_dx1[lvl == 0 ? cur : cur ^ 1], lvl == 0 ? nullptr : t.ms_dx1[cur]));
         if (lvl) cur ^= 1;
     }
-    // the shared AddNorm over the stacked rows: t.dy = d(ymesh) [levels][rows][d]; the residual x1 was broadcast to every level
-    TRY(bw_norm(e, t, p.ymesh, dl.cross_att.ln, gl.cross_att.ln, t.ms_de2, nullptr, lv * rows));
+    // the shared AddNorm over the stacked rows: t.dy = d(ymesh) [levels][rows][d]; the residual x1 was broadcast to every level.
+    // Under enc_attn.dropout (one module, a mask per level) the residual's share stays t.dy, and the projection's gradient is
+    // t.dproj = keep * s * t.dy with the masks regenerated per (level, row)
+    TRY(bw_norm(e, t, p.ymesh, dl.cross_att.ln, gl.cross_att.ln, t.ms_de2, nullptr, lv * rows, dec_site(l, 1), rows));
     RUN(ovc_bw_sum_levels(t.ms_dx1[cur], t.dy, lv, (long)nrd, (long)nrd, t.ms_dx1[cur ^ 1], s));
     cur ^= 1;
-    TRY(bw_weight(e, t, t.dy, d, d, p.attc, hk, hk, lv * rows, dl.cross_att.o, gl.cross_att.o));
-    TRY(bw_input(e, t, t.dy, d, dl.cross_att.o, hk, t.datt, nullptr, lv * rows));
+    const float* dp = proj_grad(e, t, dec_site(l, 1));
+    TRY(bw_weight(e, t, dp, d, d, p.attc, hk, hk, lv * rows, dl.cross_att.o, gl.cross_att.o));
+    TRY(bw_input(e, t, dp, d, dl.cross_att.o, hk, t.datt, nullptr, lv * rows));
     // cross-attention: once per level on the shared queries and the level's keys / values
     for (int lvl = 0; lvl < lv; ++lvl) {
         const size_t kvoff = ((size_t)l * lv + lvl) * BN * hk;
@@ -3552,7 +3568,7 @@ int bw_meshed_decoder_layer(Engine& e, TrainWs& t, const ovc_model* gr, int l, c
                   dlev_prev ? dlev_prev + lvl * nd : nullptr));
     // masked self-attention over the caption
     return bw_self_attention(e, t, dl.self_att, gl.self_att, xin, p.q, p.k, p.v, p.att, p.ys, t.dx1, w.self_mask, (long)T * T, T,
-                             B * S, T, h, dk, dxin);
+                             B * S, T, h, dk, dxin, dec_site(l, 0));
 }
 
 // bw_weight over 2 * rows rows whose inputs lie in two blocks: X0 for the first `rows`, X1 for the next (dY [2 rows][ldy] in one
@@ -4001,6 +4017,24 @@ extern "C" int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* 
                                            size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream) {
     return run_train_call(m, grads, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Meshed}, features, boxes, tokens, targets, nullptr,
                           workspace, workspace_bytes, loss_out, nullptr, use_graph, stream);
+}
+
+// The loss form under dropout: the same call with a plan bound (bind_dropout), so the meshed carve plus dproj [levels * rows][d] and
+// the seed slot.  With no site active it is ovc_forward_backward_meshed launch for launch (plan == nullptr: the plain layout, graph
+// entry and bits), and ovc_train_meshed_workspace_bytes suffices.
+extern "C" size_t ovc_level_dropout_workspace_bytes(const ovc_model* m, int B, int N, int T) {
+    return train_workspace_bytes(m, TrainCall{B, N, 1, T, LossHead::Xent, TrainArch::Meshed}, true);
+}
+
+extern "C" int ovc_forward_backward_level_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
+                                                  int B, int N, const int64_t* tokens, const int64_t* targets, int T, void* workspace,
+                                                  size_t workspace_bytes, float* loss_out, int use_graph, ovc_stream stream,
+                                                  const ovc_dropout* dropout) {
+    TrainCall c{B, N, 1, T, LossHead::Xent, TrainArch::Meshed};
+    DropPlan plan{};
+    TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, boxes, tokens, targets, nullptr, workspace, workspace_bytes, loss_out, nullptr, use_graph,
+                          stream);
 }
 
 extern "C" size_t ovc_train_meshed_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {

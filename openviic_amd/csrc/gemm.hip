@@ -282,6 +282,68 @@ __device__ __forceinline__ void store_wave_tiles(const GemmArgs& p, const float*
     }
 }
 
+// The level-keyed dropout form of store_wave_tiles (gemm_f32_mfma_level_dropout; no K split, no log-softmax pieces): the product's
+// rows are stacked blocks of level_rows rows, one block per encoder level, with the residual broadcast over the blocks
+// (GemmArgs::res_mod == level_rows, checked on the host).  Product row m is decoder row m % level_rows at level m / level_rows, for
+// the residual and the mask alike: act(acc + bias) is masked by ovc_dropout_keep_level and scaled before the residual is added,
+// statement for statement what store_wave_tiles<TM, TN, true> does at level 0.  level_magic: fast_div's constant of level_rows.
+template <int TM, int TN>
+__device__ __forceinline__ void store_wave_tiles_level_dropout(const GemmArgs& p, const float* __restrict__ bias, float* __restrict__ C,
+                                                               const f32x16 (&acc)[TM][TN], int m0, int n0, int lane,
+                                                               const DropoutSite& drop, int level_rows, unsigned level_magic) {
+    // The seed is uniform, so the compiler keeps the ten rounds' keys of both halves in 20 scalar registers across the rolled loop --
+    // and the 128 x 128 tilings then move five scalars to vector lanes and back.  The high half held in a vector register keeps its
+    // ten keys out of the scalar file (one v_add per round instead): no instance moves a register, at the same occupancy.
+    uint32_t seed_lo = (uint32_t)*drop.seed, seed_hi = (uint32_t)((uint64_t)*drop.seed >> 32);
+    asm volatile("" : "+v"(seed_hi));
+    const uint64_t drop_seed = ((uint64_t)seed_hi << 32) | seed_lo;
+    const int half = lane >> 5;
+    const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(C, 0, p.M * p.ldc * 4, 0x00020000);
+    constexpr int kOutOfRange = 0x7ffffff0;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = n0 + j * 32 + (lane & 31);
+        const bool n_ok = n < p.seg_n;
+        const int nc = min(n, p.seg_n - 1);
+        const float bv = bias ? bias[nc] : 0.f;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int mbase = m0 + i * 32 + 4 * half;
+            float out[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = acc[i][j][r] + bv;
+                out[r] = p.act == 1 ? fmaxf(v, 0.f) : v;
+            }
+            // the 16 keep decisions into a bit mask first (a rolled loop, as in store_wave_tiles), then the registers with
+            // compile-time indices; rows past M are clamped (their stores fall outside the descriptor)
+            uint32_t keep = 0;
+#pragma unroll 1
+            for (int r = 0; r < 16; ++r) {
+                const int m = min(mbase + (r & 3) + 8 * (r >> 2), p.M - 1);
+                const int level = fast_div(m, level_magic, level_rows);
+                const uint64_t row = (uint64_t)(m - level * level_rows);
+                keep |= (ovc_dropout_keep_level(drop_seed, drop.site, (uint32_t)level, row * (uint64_t)drop.cols + (uint64_t)n, drop.thr) ? 1u : 0u) << r;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) out[r] = (keep >> r) & 1u ? out[r] * drop.scale : 0.f;
+            float res[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = min(mbase + (r & 3) + 8 * (r >> 2), p.M - 1);
+                const int mc = m - fast_div(m, level_magic, level_rows) * level_rows;
+                res[r] = p.R[(size_t)mc * p.ldr + nc];
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) out[r] += res[r];
+            const int voff_c = n_ok ? (mbase * p.ldc + n) * 4 : kOutOfRange;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, out[r]), rsrc_c, voff_c, ((r & 3) + 8 * (r >> 2)) * p.ldc * 4, 0);
+        }
+    }
+}
+
 // The scoring form of store_wave_tiles (transposed product with stats_t, no bias / activation / residual / K split): the same block
 // pieces, computed by the same statements, and for every column n the logit of its target word tgt[n] -- stored by the one lane
 // register in the whole grid that holds it.  That is the value the plain form writes to C, so a scored logit equals the stored one
@@ -368,6 +430,19 @@ __global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void g
 #undef OVC_GEMM_F32_EPILOGUE
 }
 
+// The level-keyed dropout instance (GemmLaunchOpts::drop_level_rows, the meshed decoder's shared output projection in training):
+// gemm_f32_mfma with store_wave_tiles_level_dropout; one-chain tilings only.
+template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
+__global__ __launch_bounds__(256, (min_waves_per_simd<BM, BN, BK, NC>())) void gemm_f32_mfma_level_dropout(TileMap tmap, GemmArgs p,
+                                                                                                         DropoutSite drop, int level_rows,
+                                                                                                         unsigned level_magic) {
+#define OVC_GEMM_F32_EPILOGUE \
+    store_wave_tiles_level_dropout<Cfg::TM, Cfg::TN>(p, seg_bias, seg_C, acc[0], m0 + wm * Cfg::kWaveM, n0 + wn * Cfg::kWaveN, lane, drop, \
+                                                     level_rows, level_magic)
+#include "gemm_f32_body.inc"
+#undef OVC_GEMM_F32_EPILOGUE
+}
+
 // The scoring epilogue (GemmLaunchOpts::tgt_logit) of the transposed vocabulary product: one-chain instances only, the class that
 // product runs in.  Stores the block pieces and the target logits (store_wave_tiles_score), no C tile.
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
@@ -421,8 +496,9 @@ inline void tile_counts(const GemmArgs& a, int bm, int bn, int* tiles_m, int* ti
 // Which instance of a tiling a launch takes (ovc_debug_gemm_plan reports it).  fp32 tilings: by the launch options; the
 // split-precision ones: the planes-direct (WD) instance when every segment brings pre-cut planes and K has whole K tiles only
 // (the planes have no zero tail to read).
-enum GemmInstance { kInstPlain = 0, kInstGated = 1, kInstDropout = 2, kInstScoring = 3, kInstPlanesDirect = 4 };
+enum GemmInstance { kInstPlain = 0, kInstGated = 1, kInstDropout = 2, kInstScoring = 3, kInstPlanesDirect = 4, kInstLevelDropout = 5 };
 inline int f32_instance(const GemmLaunchOpts& opts) {
+    if (opts.drop_seed && opts.drop_level_rows > 0) return kInstLevelDropout;
     return opts.tgt_logit ? kInstScoring : (opts.drop_seed ? kInstDropout : (opts.gate ? kInstGated : kInstPlain));
 }
 inline bool split_reads_planes(const GemmArgs& a, int bk) {
@@ -499,6 +575,32 @@ int launch_dropout_config(const GemmArgs& a, hipStream_t stream, const GemmLaunc
     }
 }
 
+// The level-keyed dropout instance of a one-chain tiling (GemmLaunchOpts::drop_level_rows).
+template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
+int launch_level_dropout_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts, const TileMap& map, dim3 grid3,
+                                size_t lds_bytes) {
+    if constexpr (WK * NC == 1) {
+        static std::once_flag attr_once;
+        std::call_once(attr_once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_level_dropout<BM, BN, WM, WN, WK, BK, NC>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        });
+        const DropoutSite drop{opts.drop_seed, opts.drop_site, opts.drop_thr, opts.drop_scale, opts.drop_cols};
+        const int level_rows = opts.drop_level_rows;
+        const unsigned level_magic = level_rows > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)level_rows + 1) : 0u;     // fast_div
+        if (opts.start && opts.stop)
+            hipExtLaunchKernelGGL((gemm_f32_mfma_level_dropout<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), (uint32_t)lds_bytes, stream,
+                                  opts.start, opts.stop, 0, map, a, drop, level_rows, level_magic);
+        else
+            hipLaunchKernelGGL((gemm_f32_mfma_level_dropout<BM, BN, WM, WN, WK, BK, NC>), grid3, dim3(256), lds_bytes, stream, map, a, drop,
+                               level_rows, level_magic);
+        OVC_RETURN_IF_LAUNCH_FAILED();
+        return OVC_OK;
+    } else {
+        return OVC_EINVAL;           // ovc_gemm_launch refuses the dropout epilogue outside the one-chain class
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int WK, int BK, int NC>
 int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& opts) {
     using Cfg = TileConfig<BM, BN, WM, WN, WK, BK, NC>;
@@ -522,6 +624,7 @@ int launch_config(const GemmArgs& a, hipStream_t stream, const GemmLaunchOpts& o
     // blockIdx.z), a proxy for "this many batches in flight" that needs no extra streams.
     const dim3 grid3(grid, slices, opts.copies > 1 ? opts.copies : 1);
     if (instance == kInstDropout) return launch_dropout_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, grid3, lds_bytes);
+    if (instance == kInstLevelDropout) return launch_level_dropout_config<BM, BN, WM, WN, WK, BK, NC>(a, stream, opts, map, grid3, lds_bytes);
     if (instance == kInstGated) {
         static std::once_flag gated_attr_once;
         std::call_once(gated_attr_once, [&] {
@@ -816,6 +919,10 @@ int gemm_check_args(const GemmArgs& a, const GemmLaunchOpts& opts) {
     // dropout instances (training): one chain, one segment, no K split, no other epilogue, the whole column range masked
     if (opts.drop_seed && (args_chains(a) != 1 || opts.gate || opts.tgt_logit || a.nseg != 1 || a.ksplit > 1 || a.stats || a.stats_t ||
                            opts.drop_cols != a.seg_n)) return OVC_EINVAL;
+    // the level-keyed dropout instance: a dropout instance whose rows are whole blocks of drop_level_rows rows under a residual
+    // broadcast over the same blocks
+    if (opts.drop_level_rows != 0 && (!opts.drop_seed || opts.drop_level_rows < 0 || !a.R || a.res_mod != opts.drop_level_rows ||
+                                      a.M % opts.drop_level_rows)) return OVC_EINVAL;
     if (a.K2 > 0 && (a.K1 % 32)) return OVC_EINVAL;      // the A1|A2 seam must fall on a K-tile boundary
     if (a.ksplit > 1) {                                  // raw partial products: see GemmArgs::ksplit
         if (a.ksplit > kMaxKSplit || a.nseg != 1 || a.K2 || a.R || a.act || a.seg[0].bias) return OVC_EINVAL;

@@ -5,11 +5,15 @@ Every ``nn.Dropout`` of the standard transformer is one *site* with its own ``p`
 ``(seed, site, row, col)`` (Philox4x32-10, the generator torch uses, in counter mode)::
 
     idx  = row * cols + col
-    r    = philox4x32_10(counter=(lo32(idx >> 2), hi32(idx >> 2), site, 0), key=(lo32(seed), hi32(seed)))[idx & 3]
+    r    = philox4x32_10(counter=(lo32(idx >> 2), hi32(idx >> 2), site, level), key=(lo32(seed), hi32(seed)))[idx & 3]
     keep = r >= threshold(p),   out = keep ? x * scale(p) : 0
 
 so it does not depend on GEMM tiling, stream, graph replay or batch position, and the backward regenerates it instead of storing
 it.  ``keep_mask`` computes the same bits in numpy (``ovc_dropout_mask`` writes the device's, for the tests).
+
+``level`` is 0 everywhere but at the meshed decoder's ``enc_attn.dropout``: that layer applies its one module once per encoder
+level, each time with an independent mask, and ``xe_loss(meshed=True, dropout="levels")`` keys application ``lvl`` of
+``dec_site(l, 1)`` with ``level = lvl`` over the same rows ``b * T + t`` (``ovc_dropout_mask_level``).  Level 0 is the plain mask.
 """
 import re
 
@@ -94,8 +98,9 @@ def philox4x32_10(c0, c1, c2, c3, k0, k1):
     return [x.astype(np.uint32) for x in c]
 
 
-def keep_mask(seed, site, rows, cols, p, chunk=1 << 22):
-    """The kernels' keep mask of ``site`` over a ``rows x cols`` tensor, a bool array (``ovc_dropout_mask`` bit for bit)."""
+def keep_mask(seed, site, rows, cols, p, chunk=1 << 22, level=0):
+    """The kernels' keep mask of ``site`` over a ``rows x cols`` tensor, a bool array (``ovc_dropout_mask`` bit for bit; with
+    ``level``, ``ovc_dropout_mask_level``: the mask of that encoder level at a meshed decoder layer's ``enc_attn.dropout``)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     thr = np.uint32(threshold(p))
     n = int(rows) * int(cols)
@@ -103,7 +108,7 @@ def keep_mask(seed, site, rows, cols, p, chunk=1 << 22):
     for start in range(0, n, chunk):
         idx = np.arange(start, min(n, start + chunk), dtype=np.uint64)
         g = idx >> np.uint64(2)
-        words = philox4x32_10(g & _LO, g >> np.uint64(32), np.full_like(g, site), np.zeros_like(g), seed, seed >> 32)
+        words = philox4x32_10(g & _LO, g >> np.uint64(32), np.full_like(g, site), np.full_like(g, level), seed, seed >> 32)
         w = (idx & np.uint64(3)).astype(np.int64)
         r = np.choose(w, words)
         out[start:start + len(idx)] = r >= thr
@@ -125,15 +130,15 @@ def mask_rows_of_slots(slots, k):
     return mask_row(np.arange(B)[:, None, None], slots, np.arange(T)[None, None, :], k, T)
 
 
-def keep_rows(seed, site, mask_rows, cols, p):
+def keep_rows(seed, site, mask_rows, cols, p, level=0):
     """The keep bits of an arbitrary list of mask rows (``keep_mask`` does rows ``0..rows-1``): a bool array
-    ``(len(mask_rows), cols)``, ``ovc_dropout_mask_rows`` bit for bit."""
+    ``(len(mask_rows), cols)``, ``ovc_dropout_mask_rows`` bit for bit; ``level`` as in ``keep_mask``."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     thr = np.uint32(threshold(p))
     rows = np.asarray(mask_rows, dtype=np.uint64).reshape(-1)
     idx = (rows[:, None] * np.uint64(cols) + np.arange(int(cols), dtype=np.uint64)[None, :]).reshape(-1)
     g = idx >> np.uint64(2)
-    words = philox4x32_10(g & _LO, g >> np.uint64(32), np.full_like(g, site), np.zeros_like(g), seed, seed >> 32)
+    words = philox4x32_10(g & _LO, g >> np.uint64(32), np.full_like(g, site), np.full_like(g, level), seed, seed >> 32)
     r = np.choose((idx & np.uint64(3)).astype(np.int64), words)
     return (r >= thr).reshape(len(rows), int(cols))
 

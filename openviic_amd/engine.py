@@ -1117,7 +1117,7 @@ class CaptionEngine:
         return [p for p, _ in _grad_slots(self.model)]
 
     def forward_backward(self, features, boxes, caption_tokens, targets, use_graph=None, dropout=None, arena=None, loss=None,
-                         distill=None, meshed=False, geometric=False, aoa=False):
+                         distill=None, meshed=False, geometric=False, aoa=False, level_dropout=False):
         """Loss and gradients of one training step (``ovc_forward_backward``): ``NLLLoss(ignore_index=pad)`` of the teacher-forced
         log-probabilities of ``caption_tokens`` against ``targets`` (both ``(B, T)`` int64), and its gradient for every tensor of
         ``gradient_parameters()``.  Returns ``(loss, arena, grads)``: a 0-dim device tensor, the flat fp32 buffer holding every
@@ -1144,7 +1144,11 @@ class CaptionEngine:
         the plain loss and takes the plain path.  Refused together with ``loss``.
 
         ``meshed=True``: the meshed-memory transformer (``ovc_forward_backward_meshed``; ``_check_trainable`` states the
-        scope).  Refused together with ``dropout``, ``loss`` and ``distill``.
+        scope).  Refused together with ``loss`` and ``distill``, and with ``dropout`` unless ``level_dropout=True``: then
+        ``dropout=(probs, seed)`` is taken as for the plain transformer with ``dec_site(l, 1)``, the layer's one
+        ``enc_attn.dropout`` applied once per encoder level, masked per level (``ovc_forward_backward_level_dropout``,
+        ``openviic_amd.dropout``); with no ``p > 0`` that is the plain meshed call.  ``level_dropout=True`` with any other
+        architecture, or with none, is refused by name.
 
         ``geometric=True``: the object-relation transformer (``ovc_forward_backward_geometric``; ``_check_trainable``
         states the scope).  ``boxes`` are required; they are staged before the body, so a replayed graph reads this call's.
@@ -1152,8 +1156,12 @@ class CaptionEngine:
 
         ``aoa=True``: the attention-on-attention transformer (``ovc_forward_backward_aoa``; ``_check_trainable`` states the
         scope).  ``dropout`` is taken as for the plain transformer; refused together with ``loss`` and ``distill``."""
-        for named in train_arch.named(aoa=aoa, geometric=geometric, meshed=meshed):
-            named.refuse_in_engine("forward_backward", dropout is not None, loss is not None, distill is not None)
+        archs = train_arch.named(aoa=aoa, geometric=geometric, meshed=meshed)
+        if level_dropout and (len(archs) != 1 or archs[0].level_dropout_form is None):
+            raise native.OvcError("forward_backward(level_dropout=True): a mask per encoder level is the meshed-memory transformer's "
+                                  "dropout form -- it needs meshed=True and no other architecture's keyword")
+        for named in archs:
+            named.refuse_in_engine("forward_backward", dropout is not None and not level_dropout, loss is not None, distill is not None)
         if distill is not None:
             if not isinstance(distill, (tuple, list)) or len(distill) != 2:
                 raise native.OvcError("forward_backward: distill must be a (teacher_log_probs, distill_weight) pair (got {!r})".format(
@@ -1178,7 +1186,7 @@ class CaptionEngine:
         B, N = features.shape[:2]
         T = self._check_caption_pair(B, caption_tokens, targets)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
-        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, arch=arch)
+        form = self._train_form(False, loss, table_drop, (B, N, T), distill=distill, arch=arch, level=bool(level_dropout))
         tokens = caption_tokens.to(self.device).contiguous()
         targets = targets.to(self.device).contiguous()
         arena, grads, out = self._run_train_form(form, features, boxes, (tokens, targets), (), arena, use_graph)
@@ -1196,13 +1204,14 @@ class CaptionEngine:
 
     _DISTILL_FORM = ("ovc_train_distill_workspace_bytes", "ovc_forward_backward_distill")
 
-    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, arch=None):
+    def _train_form(self, sequence, loss, table_drop, shape, search=(), distill=None, arch=None, level=False):
         """One training call's form: ``(entry point, shape, workspace, its bytes, trailing arguments)`` for ``shape`` ``(B, N,
         T)`` or, with ``sequence``, ``(B, N, S, T)``; ``search``: the ``(k, slots pointer)`` a sequence call with dropout passes
         on.  The pointer table is re-read first; a shape or model the sizer refuses raises here, before any launch; the
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
         soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``arch``: a
-        ``train_arch.TrainArch`` -- that architecture's form (what it does not combine with, the callers have refused)."""
+        ``train_arch.TrainArch`` -- that architecture's form (what it does not combine with, the callers have refused); with
+        ``level`` and a dropout table its ``level_dropout_form``, the table behind the plain arguments."""
         drop = () if table_drop is None else (ctypes.byref(table_drop),)
         flagged = (1 if drop else 0,), (drop[0] if drop else None,)      # a sizer's dropout flag, the table or NULL behind the arguments
         size_tail, tail = (), (*search, *drop)
@@ -1210,6 +1219,8 @@ class CaptionEngine:
             sizer, entry = arch.sequence_form if sequence else arch.loss_form
             if arch.loss_dropout and not sequence:
                 size_tail, tail = flagged
+            elif level and drop and not sequence:
+                sizer, entry = arch.level_dropout_form
         elif distill is not None:
             sizer, entry = self._DISTILL_FORM
             size_tail, tail = flagged[0], (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), *flagged[1])

@@ -18,9 +18,16 @@ class TrainArch:
     loss_dropout: bool      # the loss form takes the dropout table (or NULL) behind the plain arguments, its sizer the flag
     dropout_note: str       # what a refusal of ``dropout`` adds (``refuse_with``)
     needs_boxes: bool = False
+    # (sizer, entry point) of the loss form under dropout where the plain loss form takes none: reached through
+    # ``dropout=LEVEL_DROPOUT`` -- one module applied once per encoder level, a mask per level (``openviic_amd.dropout``)
+    level_dropout_form: tuple = None
 
     def keywords(self):
         return {self.key: True}
+
+    def takes_level_dropout(self, dropout):
+        """``dropout`` is the level-keyed spelling and this architecture has that form."""
+        return self.level_dropout_form is not None and isinstance(dropout, str) and dropout == LEVEL_DROPOUT
 
     def refuse_in_engine(self, where, dropout, loss=False, distill=False):
         """What ``forward_backward`` / ``sequence_backward`` (``where``) refuse together with this architecture: the smoothed
@@ -43,14 +50,18 @@ class TrainArch:
                     self.dropout_note if name == "dropout" else " -- a model is one or the other" if name in TRAIN_ARCHS else ""))
 
 
+LEVEL_DROPOUT = "levels"    # ``xe_loss`` / ``xe_step``'s ``dropout`` value that selects an architecture's ``level_dropout_form``
+
 _SEARCH_HAS_ITS_OWN_SCOPE = " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
 
 TRAIN_ARCHS = {a.key: a for a in (
     TrainArch("meshed", "the meshed-memory transformer", "meshed_memory_transformer",
               ("ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed"),
               ("ovc_train_meshed_beams_workspace_bytes", "ovc_sequence_backward_meshed"), loss_dropout=False,
-              dropout_note=" -- the meshed layer applies enc_attn.dropout once per level and the engine has no site for it; set "
-                           "DROPOUT: 0 or call model.eval()"),
+              dropout_note=" -- the meshed layer applies enc_attn.dropout once per level, with a mask per level: xe_loss / xe_step take "
+                           "dropout=\"levels\" for it, the sequence form and the search have no dropout form; or set DROPOUT: 0 or "
+                           "call model.eval()",
+              level_dropout_form=("ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout")),
     TrainArch("geometric", "the object-relation transformer", "object_relation_transformer",
               ("ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric"),
               ("ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric"), loss_dropout=True,

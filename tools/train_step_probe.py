@@ -10,7 +10,8 @@ attention backward and ovc_bw_box_relation -- through xe_loss(geometric=True).
 --variant attention_on_attention: the plain encoder / decoder with AoA gates in all nine attentions -- the gate backward and its
 K = 2d products -- through xe_loss(aoa=True) (ovc_forward_backward_aoa; --optimizer none only).
 --variant meshed_memory_transformer: the multilevel encoder with 40 memory slots per layer and the meshed decoder, through
-``model.xe_loss(items, meshed=True)`` (``ovc_forward_backward_meshed``; no dropout form, --optimizer none only).
+``model.xe_loss(items, meshed=True)`` (``ovc_forward_backward_meshed``; --optimizer none only).  With --dropout:
+``model.xe_loss(items, meshed=True, dropout="levels")`` (``ovc_forward_backward_level_dropout``: a mask per encoder level).
 Several --variant values alternate in ONE process -- per batch size, ``--rounds`` rounds of ``--steps`` steps of each variant in
 turn, each on its own model -- so a variant's step time stands next to the standard transformer's from the same run.
 
@@ -29,6 +30,10 @@ read, p, m, v written) over its time as achieved bytes/s, against the 6.29 TB/s 
 (``ovc_grad_norm`` between the backward and the Adam launch), alternating with the others; its rows also carry ``grad_norm_ms``,
 ``optimizer.grad_norm(gradients)`` alone, back to back, with the 4 bytes per element it reads as achieved bytes/s.  ``xe_step``
 without ``max_norm`` launches what it launched before the keyword existed, so it is the baseline of the same run.
+
+--dropout-leg (with --optimizer none and one --variant): the plain step (the model in eval() mode) and the step under dropout (a
+twin in train() mode, DROPOUT 0.1 at every site, a fresh seed per step) alternate in this one process, --rounds rounds of --steps
+steps each per batch size, and the ratio of the rounds' means closes each batch size.
 
 --label-smoothing S [--reduction mean|tokens] (with --optimizer none and one --variant): the plain step and the step under
 ``model.xe_loss(items, label_smoothing=S, reduction=...)`` (``ovc_forward_backward_smoothed``) alternate in ONE process on one
@@ -235,6 +240,8 @@ def loss_kw(variant, dropout):
     arch = train_arch.of_variant(variant)
     if arch is None:
         return dict(dropout=dropout)
+    if dropout and arch.level_dropout_form is not None:
+        return dict(arch.keywords(), dropout=train_arch.LEVEL_DROPOUT)
     return dict(arch.keywords(), dropout=dropout) if arch.loss_dropout else arch.keywords()
 
 
@@ -242,8 +249,35 @@ def train_sizer(lib, variant, dropout):
     arch = train_arch.of_variant(variant)
     if arch is None:
         return lib.ovc_train_dropout_workspace_bytes if dropout else lib.ovc_train_workspace_bytes
+    if dropout and arch.level_dropout_form is not None:
+        return getattr(lib, arch.level_dropout_form[0])
     sizer = getattr(lib, arch.loss_form[0])
     return (lambda d, B, N, T: sizer(d, B, N, T, 1 if dropout else 0)) if arch.loss_dropout else sizer
+
+
+def dropout_probe(args, models, items, B, T, N):
+    """--dropout-leg: ``models`` = {False: the eval()-mode model, True: its train()-mode twin}."""
+    def step(dropout):
+        models[dropout].zero_grad(set_to_none=True)
+        models[dropout].xe_loss(items, **loss_kw(args.variant, dropout)).backward()
+    for dropout in (False, True):
+        for _ in range(args.warmup):
+            step(dropout)
+    torch.cuda.synchronize()
+    rows, times = [], {False: [], True: []}
+    for rnd in range(args.rounds):
+        for dropout in (False, True):
+            ms = events_ms(lambda: step(dropout), args.steps)
+            times[dropout].append(ms)
+            eng = models[dropout]._fused_engine()
+            ws = train_sizer(eng.lib, args.variant, dropout)(eng.desc, B, N, T)
+            rows.append(dict(variant=args.variant, B=B, T=T, N=N, dropout=dropout, round=rnd, ms_per_step=round(ms, 3), workspace_bytes=ws))
+            print(json.dumps(rows[-1]), flush=True)
+    plain, masked = (sum(times[k]) / len(times[k]) for k in (False, True))
+    rows.append(dict(variant=args.variant, B=B, dropout="ratio", plain_ms=round(plain, 3), dropout_ms=round(masked, 3),
+                     dropout_over_plain=round(masked / plain, 4)))
+    print(json.dumps(rows[-1]), flush=True)
+    return rows
 
 
 def alternate_variants(args, vocab, V, T, N, D):
@@ -294,6 +328,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dropout", action="store_true")
+    ap.add_argument("--dropout-leg", action="store_true",
+                    help="with --optimizer none and one --variant: alternate the plain step and the step under dropout")
     ap.add_argument("--variant", nargs="+", default=["standard_transformer"],
                     choices=["standard_transformer", "camo_transformer", "augmented_memory_transformer", MESHED, GEOMETRIC, AOA],
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
@@ -323,9 +359,11 @@ def main():
         ap.error("--reduction goes with --label-smoothing")
     if args.distill is not None and (args.optimizer != ["none"] or len(args.variant) > 1 or args.label_smoothing is not None):
         ap.error("--distill goes with --optimizer none and one --variant, without --label-smoothing")
-    if MESHED in args.variant and (args.dropout or args.optimizer != ["none"] or args.label_smoothing is not None or
-                                   args.distill is not None):
-        ap.error("meshed_memory_transformer goes with --optimizer none, without --dropout, --label-smoothing or --distill")
+    if args.dropout_leg and (args.optimizer != ["none"] or len(args.variant) > 1 or args.dropout or args.label_smoothing is not None or
+                             args.distill is not None):
+        ap.error("--dropout-leg goes with --optimizer none and one --variant, without --dropout, --label-smoothing or --distill")
+    if MESHED in args.variant and (args.optimizer != ["none"] or args.label_smoothing is not None or args.distill is not None):
+        ap.error("meshed_memory_transformer goes with --optimizer none, without --label-smoothing or --distill")
     if AOA in args.variant and (args.optimizer != ["none"] or args.label_smoothing is not None or args.distill is not None):
         ap.error("attention_on_attention goes with --optimizer none, without --label-smoothing or --distill")
     if GEOMETRIC in args.variant and len(args.variant) < 2:
@@ -344,6 +382,7 @@ def main():
         model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=1234, mode="reference_init"), strict=False)
         return model.train() if args.dropout else model
     model = build() if args.optimizer == ["none"] else None
+    twins = {False: model, True: build().train()} if args.dropout_leg else None
     teacher = None
     if args.distill is not None:
         teacher = build_model(cfg, vocab).eval()
@@ -367,6 +406,9 @@ def main():
             continue
         if args.distill is not None:
             results += distill_probe(args, model, teacher, items, B, T, N, V)
+            continue
+        if args.dropout_leg:
+            results += dropout_probe(args, twins, items, B, T, N)
             continue
         for _ in range(args.warmup):
             model.zero_grad(set_to_none=True)

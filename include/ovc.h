@@ -85,6 +85,8 @@ int ovc_layer_norm(const float* x, const float* residual, const float* gamma, co
  *   attentions.py:44-58): up to 192 keys (nk + m) and 128 queries the scores of a query stay in registers; beyond that the
  *   keys pass in tiles of 128, ascending, under an online softmax (a fixed order: results depend on the operands only).
  *   A query whose keys are all masked gets NaN, as torch.softmax over a row of -inf does.
+ *   q, k, v, out and (with m > 0) mem_k, mem_v 16-byte aligned: rows are read and written as float4.  OVC_EINVAL, nothing
+ *   launched, otherwise, for dk or dv that is no multiple of 4 in 4..64, and for m > 0 without both slot pointers.
  * Replaces attentions.py:51-55 (plain), :102-111 (geometry), :171-183 (memory). */
 int ovc_attention(const float* q, const float* k, const float* v, int b, int nq, int nk, int h,
                   int dk, int dv, const uint8_t* mask, long mask_sb, long mask_sq,
@@ -1361,6 +1363,17 @@ int ovc_debug_decode_cross_attention(const float* q, int ldq, const float* kx, c
                                      size_t out_level_stride, int ldo, const int32_t* gate, ovc_stream stream);
 int ovc_debug_decode_self_form(int t, int width, int rows, int h, int d_k, int per_row);
 int ovc_debug_decode_cross_form(int N, int width, int h, int d_k);
+
+/* Test hook: the instance an ovc_attention launch takes (appended to ABI 8; no struct changes), so that every instance of the
+ * general operator can be named by a test case (tests/test_attention_instances_gpu.py).  It launches nothing and touches no
+ * device.  The same selection function as the launcher's, a function of these five numbers alone; OVC_EINVAL for what ovc_attention
+ * refuses from them (nq, nk <= 0, m < 0, dk or dv no multiple of 4 in 4..64).  Coded family * 100 + NKT * 10 + C, where C = 1, 2, 3
+ * for max(dk, dv) <= 16, 32, 64:
+ *   1 NKT C  attention_regs_kernel<NKT, KG, DVT>   NKT = 1..6 key tiles of 32 (nk + m <= 192) and nq <= 128
+ *   2 0 C    attention_tiled_kernel<KG, DVT>       nk + m > 192, or nk + m > 128 with nq > 128
+ *   3 0 0    attention_mfma_kernel                 nq > 128 with nk + m <= 128 (the LDS-score kernel)
+ * e.g. 163 = six key tiles in registers at a head size above 32. */
+int ovc_debug_attention_form(int nq, int nk, int m, int dk, int dv);
 
 /* Test hooks: the row operators of the decode path on caller buffers (appended to ABI 8; no struct changes), so that every kernel
  * instance can be compared with an fp64 restatement at the operator level (tests/test_rowops_gpu.py).  Each calls the launcher the

@@ -511,15 +511,43 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(AttnArgs p) {
 
 }  // namespace
 
+// ---- which instance an ovc_attention launch takes ------------------------------------------------------------------------------
+// ONE selection function for the launcher below and for the form query of the test hook (ovc_debug_attention_form): the choice
+// is a function of (nq, nk, m, dk, dv) alone and is coded family * 100 + NKT * 10 + C (include/ovc.h), C = 1, 2, 3 for
+// max(dk, dv) <= 16, 32, 64 -- (KG, DVT) = (2, 1), (4, 1), (8, 2):
+//   1 NKT C   attention_regs_kernel<NKT, KG, DVT>   up to 192 keys (nk + m: NKT = 1..6 tiles of 32; 128 regions + 40 memory slots
+//                                                   and a bit, so that the shipped meshed-memory configuration stays here for
+//                                                   every N <= 128) for up to 128 queries: one workgroup per (image, head), a wave
+//                                                   per 32 queries, scores never leave the accumulators
+//   2 0 C     attention_tiled_kernel<KG, DVT>       more than 192 keys, or more than 128 keys for more than 128 queries: key tiles
+//                                                   of 128 under an online softmax, any nq and nk
+//   3 0 0     attention_mfma_kernel                 more than 128 queries with at most 128 keys: the LDS-score kernel, 64-query tiles
+// OVC_EINVAL for what the operator refuses from these five numbers.  OVC_ATTENTION_GENERAL (hooks build only) keeps every shape
+// off the register instances.
+constexpr int kFormAttRegs = 100, kFormAttTiled = 200, kFormAttLds = 300;
+
+static int attention_form(int nq, int nk, int m, int dk, int dv) {
+    if (nq <= 0 || nk <= 0 || m < 0) return OVC_EINVAL;
+    if (dk <= 0 || dv <= 0 || (dk & 3) || (dv & 3) || dk > 64 || dv > 64) return OVC_EINVAL;
+    const int nkt = (nk + m + 31) / 32, waves = (nq + 31) / 32, hmax = dk > dv ? dk : dv;
+    const int cls = hmax <= 16 ? 1 : hmax <= 32 ? 2 : 3;
+    if (nkt <= 6 && waves <= 4 && !OVC_HOOK_ENV("OVC_ATTENTION_GENERAL")) return kFormAttRegs + nkt * 10 + cls;
+    if (nk + m > 128) return kFormAttTiled + cls;
+    return kFormAttLds;
+}
+
+extern "C" int ovc_debug_attention_form(int nq, int nk, int m, int dk, int dv) { return attention_form(nq, nk, m, dk, dv); }
+
 extern "C" int ovc_attention(const float* q, const float* k, const float* v, int b, int nq, int nk, int h,
                              int dk, int dv, const uint8_t* mask, long mask_sb, long mask_sq,
                              const float* geometry, const float* mem_k, const float* mem_v, int m,
                              float mem_scale_k, float mem_scale_v, float* out, ovc_stream stream) {
     if (!q || !k || !v || !out || b <= 0 || nq <= 0 || nk <= 0 || h <= 0) return OVC_EINVAL;
     if (const int rc = ovc_device_guard()) return rc;      // kernel attributes below are raised once per process
-    if (dk <= 0 || dv <= 0 || (dk & 3) || (dv & 3) || dk > 64 || dv > 64) return OVC_EINVAL;
-    if (m < 0 || (m > 0 && (!mem_k || !mem_v))) return OVC_EINVAL;
-    if (!ovc_aligned16(q) || !ovc_aligned16(k) || !ovc_aligned16(v)) return OVC_EINVAL;
+    const int form = attention_form(nq, nk, m, dk, dv);
+    if (form < 0) return form;
+    if (m > 0 && (!mem_k || !mem_v)) return OVC_EINVAL;
+    if (!ovc_aligned16(q) || !ovc_aligned16(k) || !ovc_aligned16(v) || !ovc_aligned16(out)) return OVC_EINVAL;
     if (m > 0 && (!ovc_aligned16(mem_k) || !ovc_aligned16(mem_v))) return OVC_EINVAL;
     AttnArgs p{};
     p.q = q; p.k = k; p.v = v; p.out = out;
@@ -529,66 +557,47 @@ extern "C" int ovc_attention(const float* q, const float* k, const float* v, int
     p.mem_k = mem_k; p.mem_v = mem_v; p.m = m; p.mem_scale_k = mem_scale_k; p.mem_scale_v = mem_scale_v;
     p.nkp = ((nk + m + 31) / 32) * 32;
     p.qtiles = (nq + kQTile - 1) / kQTile;
-    // Register-resident kernel: one workgroup per (image, head), a wave per 32 queries (nq <= 128), scores never leave
-    // the accumulators.  Head sizes up to 64, key tiles up to 4 x 32: everything the path uses.
-    {
-        const int nkt = (nk + m + 31) / 32, waves = (nq + 31) / 32, hmax = dk > dv ? dk : dv;
-        // up to 192 keys (six 32-key tiles: 128 regions + 40 memory slots and a bit) for up to 128 queries; instances 5 and 6 exist
-        // since round 4 so that the shipped meshed-memory configuration (MEMORY: 40) stays on this kernel for every N <= 128
-        if (nkt <= 6 && waves <= 4 && !OVC_HOOK_ENV("OVC_ATTENTION_GENERAL")) {
-            const int k_rows = nkt * 32 > waves * 32 ? nkt * 32 : waves * 32;
-            const size_t bytes = sizeof(float) * (size_t)(k_rows + nkt * 32) * kLdQK;
-            const dim3 grid(b * h), block(256);
-#define OVC_ATT(NKT, KG, DVT)                                                                                         \
-    do {                                                                                                              \
+    const int nkt = (nk + m + 31) / 32, waves = (nq + 31) / 32;
+    switch (form) {
+#define OVC_ATT(NKT, C, KG, DVT)                                                                                      \
+    case kFormAttRegs + NKT * 10 + C: {                                                                               \
+        const int k_rows = nkt * 32 > waves * 32 ? nkt * 32 : waves * 32;    /* the K image doubles as the output staging area */ \
+        const size_t bytes = sizeof(float) * (size_t)(k_rows + nkt * 32) * kLdQK;                                     \
         static std::once_flag once;                                                                                   \
         std::call_once(once, [] {                                                                                     \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_regs_kernel<NKT, KG, DVT>),            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);                        \
         });                                                                                                           \
-        hipLaunchKernelGGL((attention_regs_kernel<NKT, KG, DVT>), grid, block, bytes, ovc_hip_stream(stream), p);     \
-    } while (0)
-#define OVC_ATT_H(NKT)                                                                                                \
-    do {                                                                                                              \
-        if (hmax <= 16) OVC_ATT(NKT, 2, 1); else if (hmax <= 32) OVC_ATT(NKT, 4, 1); else OVC_ATT(NKT, 8, 2);          \
-    } while (0)
-            if (nkt == 1) OVC_ATT_H(1); else if (nkt == 2) OVC_ATT_H(2); else if (nkt == 3) OVC_ATT_H(3); else if (nkt == 4) OVC_ATT_H(4);
-            else if (nkt == 5) OVC_ATT_H(5); else OVC_ATT_H(6);
+        hipLaunchKernelGGL((attention_regs_kernel<NKT, KG, DVT>), dim3(b * h), dim3(256), bytes, ovc_hip_stream(stream), p); \
+    } break
+#define OVC_ATT_H(NKT) OVC_ATT(NKT, 1, 2, 1); OVC_ATT(NKT, 2, 4, 1); OVC_ATT(NKT, 3, 8, 2)
+        OVC_ATT_H(1); OVC_ATT_H(2); OVC_ATT_H(3); OVC_ATT_H(4); OVC_ATT_H(5); OVC_ATT_H(6);
 #undef OVC_ATT_H
 #undef OVC_ATT
-            OVC_RETURN_IF_LAUNCH_FAILED();
-            return OVC_OK;
-        }
-    }
-    // More than 192 keys (real + memory slots), or more than 128 keys for more than 128 queries: the key-tiled kernel with an
-    // online softmax, any nq and nk.
-    if (nk + m > 128) {
-        const int hmax = dk > dv ? dk : dv;
-        p.qtiles = (nq + 127) / 128;
-        const size_t bytes = sizeof(float) * (size_t)(2 * 128) * kLdQK;
-        const dim3 grid(b * h * p.qtiles), block(256);
-#define OVC_ATT_TILED(KG, DVT)                                                                                        \
-    do {                                                                                                              \
+#define OVC_ATT_TILED(C, KG, DVT)                                                                                     \
+    case kFormAttTiled + C: {                                                                                         \
+        p.qtiles = (nq + 127) / 128;                                                                                  \
+        const size_t bytes = sizeof(float) * (size_t)(2 * 128) * kLdQK;                                               \
         static std::once_flag once;                                                                                   \
         std::call_once(once, [] {                                                                                     \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_tiled_kernel<KG, DVT>),                \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                         \
         });                                                                                                           \
-        hipLaunchKernelGGL((attention_tiled_kernel<KG, DVT>), grid, block, bytes, ovc_hip_stream(stream), p);         \
-    } while (0)
-        if (hmax <= 16) OVC_ATT_TILED(2, 1); else if (hmax <= 32) OVC_ATT_TILED(4, 1); else OVC_ATT_TILED(8, 2);
+        hipLaunchKernelGGL((attention_tiled_kernel<KG, DVT>), dim3(b * h * p.qtiles), dim3(256), bytes, ovc_hip_stream(stream), p); \
+    } break
+        OVC_ATT_TILED(1, 2, 1); OVC_ATT_TILED(2, 4, 1); OVC_ATT_TILED(3, 8, 2);
 #undef OVC_ATT_TILED
-        OVC_RETURN_IF_LAUNCH_FAILED();
-        return OVC_OK;
+        case kFormAttLds: {
+            const size_t lds_bytes = sizeof(float) * ((size_t)kQTile * kLdQK + 2 * (size_t)p.nkp * kLdQK + (size_t)kQTile * (p.nkp + 4));
+            static std::once_flag attr_once;
+            std::call_once(attr_once, [] {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+            });
+            hipLaunchKernelGGL(attention_mfma_kernel, dim3(b * h * p.qtiles), dim3(256), lds_bytes, ovc_hip_stream(stream), p);
+        } break;
+        default: return OVC_EINVAL;
     }
-    // nq > 128 with at most 128 keys: the LDS-score kernel over 64-query tiles
-    const size_t lds_bytes = sizeof(float) * ((size_t)kQTile * kLdQK + 2 * (size_t)p.nkp * kLdQK + (size_t)kQTile * (p.nkp + 4));
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    });
-    hipLaunchKernelGGL(attention_mfma_kernel, dim3(b * h * p.qtiles), dim3(256), lds_bytes, ovc_hip_stream(stream), p);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -347,6 +347,7 @@ SIGNATURES = {
                                                  c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "ovc_debug_decode_self_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ovc_debug_decode_cross_form": (c_int, [c_int, c_int, c_int, c_int]),
+    "ovc_debug_attention_form": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "ovc_debug_gemm": (c_int, [POINTER(GemmCall), c_int, c_void_p]),
     "ovc_debug_gemm_plan": (c_int, [POINTER(GemmCall), c_int, POINTER(c_int32)]),
     "ovc_debug_add_norm": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float,
@@ -394,6 +395,7 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_sample_choice_workspace_bytes", "ovc_sample_choice",
                  "ovc_debug_decode_self_partial_bytes", "ovc_debug_decode_self_attention", "ovc_debug_decode_cross_attention",
                  "ovc_debug_decode_self_form", "ovc_debug_decode_cross_form", "ovc_debug_gemm", "ovc_debug_gemm_plan",
+                 "ovc_debug_attention_form",
                  "ovc_search_constraints_ok", "ovc_beam_search_constrained", "ovc_beam_search_constrained_graph",
                  "ovc_debug_beam_constrained_update_bytes", "ovc_debug_beam_constrained_update",
                  "ovc_ensemble_ok", "ovc_ensemble_workspace_bytes", "ovc_ensemble_beam_search", "ovc_ensemble_beam_search_graph",

@@ -637,53 +637,63 @@ bool ovc_beam_forced_ok(int k, int C) {
     return C >= 1 && C <= OVC_MAX_FORCED && k >= 1 && k <= kMaxK && k % (1 << C) == 0;
 }
 
-// The fused selection of a step, one launch: the instance the options name -- constrained, else prefix, else diverse, else forced
-// words, else the plain one or its gated form.  The options reach the kernel by value (baked into a captured graph); of a prefix table only the device
-// addresses do, the contents are read by the kernel.  The early-exit forms (p.alive_count, the gate) are the plain instance's alone.
+// The fused selection of a step, one launch: the instance of o.rule -- for Best the plain one or its gated form.  The options reach
+// the kernel by value (baked into a captured graph); of a prefix table only the device addresses do, the contents are read by the
+// kernel.  The early-exit forms (p.alive_count, the gate) are the plain instance's alone.
 int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& f, const float* running_in, const FusedSelectOptions& o, int B,
                                  hipStream_t stream) {
     const BeamConstraints& cons = o.cons;
     const BeamPrefix& pre = o.prefix;
-    const bool plain = !cons.active() && pre.P == 0 && o.groups == 0 && o.forced_C == 0 && !o.length.active();
+    const bool plain = o.rule == SelectRule::Best;
     if (!fused_tail_ok(p, f, B) || !running_in || (long)p.width * p.V < p.k || (!plain && (p.alive_count || o.gate))) return OVC_EINVAL;
     if (!plain && (p.T < 1 || p.t < 0 || p.t >= p.T)) return OVC_EINVAL;
     const dim3 grid(B), block(kFusedThreads);
-    if (cons.active()) {
+    switch (o.rule) {
+    case SelectRule::Constrained:
         // the staged histories and the bitmap are sized for these: anything beyond would not fit the workgroup's LDS
         if (p.T > OVC_MAX_LEN || !p.hist_in) return OVC_EINVAL;
         if (cons.ngram < 0 || cons.min_length < 0 || cons.n_banned < 0 || cons.n_banned > OVC_MAX_BANNED) return OVC_EINVAL;
         for (int i = 0; i < cons.n_banned; ++i) if (cons.banned[i] < 0 || cons.banned[i] >= p.V) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_constrained_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, cons);
-    } else if (pre.P != 0) {
+        break;
+    case SelectRule::Prefix:
         if (!pre.ids || !pre.len || pre.P < 1 || pre.P > p.T - 1) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_prefix_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, pre);
-    } else if (o.groups != 0) {
+        break;
+    case SelectRule::Diverse:
         if (p.V < p.k || !ovc_beam_diversity_ok(p.k, o.groups, o.diversity)) return OVC_EINVAL;
         // the groups' rows are the image's one row at step 0 (or its G copies, one per group) and each group's own slots later: the
         // kernel indexes rows with this
         if (p.t == 0 ? p.width != 1 && p.width != o.groups : p.width != p.k) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_diverse_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.groups, o.diversity);
-    } else if (o.forced_C != 0) {
+        break;
+    case SelectRule::Forced:
         // the banks' rows are the image's one row at step 0 and every bank's own slots later: the kernel indexes rows with this
         if (!o.forced || !ovc_beam_forced_ok(p.k, o.forced_C) || p.V < p.k || o.pad < 0 || o.pad >= p.V) return OVC_EINVAL;
         if (p.width != (p.t == 0 ? 1 : p.k)) return OVC_EINVAL;
         hipLaunchKernelGGL(beam_forced_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.forced, o.forced_C, o.pad);
-    } else if (o.length.active()) {
+        break;
+    case SelectRule::Normalized:
         // the rows are the image's one row at step 0 and its k slots later; the tables hold p.T entries, indexed with a length the
         // kernel clamps to 1..p.T
-        if (!o.length.len_in || !o.length.len_out || !o.length.bonus || p.V < p.k || p.width != (p.t == 0 ? 1 : p.k)) return OVC_EINVAL;
+        if (!o.length.len_in || !o.length.len_out || !o.length.inv || !o.length.bonus || p.V < p.k || p.width != (p.t == 0 ? 1 : p.k))
+            return OVC_EINVAL;
         hipLaunchKernelGGL(beam_normalized_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
                            f.ld_word, o.length);
-    } else if (o.gate)
-        hipLaunchKernelGGL(beam_fused_update_kernel_gated, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
-                           f.ld_word, o.gate);
-    else
-        hipLaunchKernelGGL(beam_fused_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
-                           f.ld_word);
+        break;
+    case SelectRule::Best:
+        if (o.gate)
+            hipLaunchKernelGGL(beam_fused_update_kernel_gated, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                               f.ld_word, o.gate);
+        else
+            hipLaunchKernelGGL(beam_fused_update_kernel, grid, block, 0, stream, p, f.stats, f.nblk, f.stats_ld, running_in, f.ld_row,
+                               f.ld_word);
+        break;
+    }
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }

@@ -309,23 +309,25 @@ struct BeamLength {
     const int32_t* len_in; int32_t* len_out;        // [B*width] / [B*k]: the length a frozen row carries, the winners' lengths
     const float* inv; const float* bonus;           // [T]: entry L - 1 is 1 / lp(L) and gamma * L for L = 1..T
     float* key_out;                                 // [B*k] or nullptr: the key every winner was ranked by
-    bool active() const { return inv != nullptr; }
 };
-// The options of a step's fused selection, as the search call holds them; all zero: the plain selection.
+// The rule a search selects its beams by.  A search has exactly one: Best is the plain selection, every other rule is reached
+// through its own entry points with options that are not neutral, and brings the payload named beside it below.
+enum class SelectRule { Best, Constrained, Prefix, Diverse, Forced, Normalized };
+// The options of a step's fused selection, as the search call holds them: the rule and that rule's payload (the rest is not read).
 struct FusedSelectOptions {
-    BeamConstraints cons;           // active(): a per-row ban set (p.hist_in holds the rows' histories)
-    BeamPrefix prefix;              // P != 0: an image is forced (p.t < P_b), restricted to its row 0 (p.t == P_b >= 1) or free
-    int groups; float diversity;    // groups != 0: that many groups of k / groups slots under the Hamming penalty; p.width is 1
+    SelectRule rule;
+    BeamConstraints cons;           // Constrained: a per-row ban set (p.hist_in holds the rows' histories)
+    BeamPrefix prefix;              // Prefix: an image is forced (p.t < P_b), restricted to its row 0 (p.t == P_b >= 1) or free
+    int groups; float diversity;    // Diverse: that many groups of k / groups slots under the Hamming penalty; p.width is 1
                                     // (or groups) at p.t == 0, else p.k
-    const int32_t* gate;            // the plain selection's gated form (ovc_gate_closed)
-    const int32_t* forced; int forced_C, pad;   // forced_C != 0: the forced-word instance -- the table [B][forced_C] in DEVICE memory
-                                    // (ids in [0, V), the caller's to check), 2^forced_C banks of k >> forced_C slots, and the
-                                    // <pad> id an empty slot takes; p.width is 1 at p.t == 0, else p.k
-    BeamLength length;              // active(): the length-normalised instance -- candidates ranked by (key, raw score, flat index)
+    const int32_t* gate;            // Best: the plain selection's gated form (ovc_gate_closed)
+    const int32_t* forced; int forced_C, pad;   // Forced: the table [B][forced_C] in DEVICE memory (ids in [0, V), the caller's to
+                                    // check), 2^forced_C banks of k >> forced_C slots, and the <pad> id an empty slot takes;
+                                    // p.width is 1 at p.t == 0, else p.k
+    BeamLength length;              // Normalized: candidates ranked by (key, raw score, flat index)
 };
-// Selection + update of a step, one launch: the constrained instance, else the prefix one, else the diverse one, else the plain
-// one.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count and the gate go with the plain instance only.  (Forced words:
-// behind the diverse instance; the length-normalised instance: behind that.)
+// Selection + update of a step, one launch: the instance of o.rule.  p.cand_* / p.row_max / p.row_lsum are not used; p.alive_count
+// and the gate go with the plain instance only.
 int ovc_beam_fused_select_launch(const BeamUpdateArgs& p, const FusedTail& tail, const float* running_in, const FusedSelectOptions& o, int B,
                                  hipStream_t stream);
 // The ensemble search's step (include/ovc.h, ovc_ensemble_beam_search: the rule): the fused selection over the mean of M members'

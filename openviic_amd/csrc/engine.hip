@@ -119,6 +119,22 @@ struct DecTape {
 struct ClTape { float *k[2], *v[2], *att, *ya, *o2p, *a1, *h2; };
 struct Tape { EncTape enc[OVC_MAX_LAYERS]; DecTape dec[OVC_MAX_LAYERS]; ClTape cl; };
 
+// What a search's selection rule moves between the caller and the workspace (rule_io fills it, carve_search keeps it in the
+// workspace): the caller's HOST tables, copied to the workspace outside any captured body so that a replayed graph reads this call's
+// -- in this order -- and the [B][k] columns the final ordering leaves, whose first out_size entries per image go to the caller's
+// [B][out_size].  order_out: the caller's buffer that takes the final order itself, or nullptr (not wanted).
+struct RuleIO {
+    struct Table { void* dst; const void* src; size_t bytes; } table[2];
+    struct Column { void* out; const void* col; size_t elem; } column[2];
+    int ntable, ncolumn;
+    int32_t* order_out;
+    bool pointers_ok() const {      // the caller's side of every entry: checked before the device is touched
+        for (int i = 0; i < ntable; ++i) if (!table[i].src) return false;
+        for (int i = 0; i < ncolumn; ++i) if (!column[i].out) return false;
+        return true;
+    }
+};
+
 struct Workspace {
     const Tape* tape;                             // training only: the forward keeps every layer's intermediates here
     // encoder
@@ -152,6 +168,7 @@ struct Workspace {
     // ovc_beam_search_normalized: the call's tables [max_len] each (refreshed the same way), the per-slot lengths of the two state
     // buffers [B*k] and the final ordering's keys / lengths [B][k]
     float* norm_inv; float* norm_bonus; int32_t* norm_len[2]; float* norm_score; int32_t* norm_len_out;
+    RuleIO rule;                                  // the copies that go with the three rules' buffers above (carve_search)
     // teacher-forced forward (a ForwardCall; rows = B*S*T): the self-attention mask [B*S][T][T], the target words, the logit of
     // each row's target (scoring) and the row's log-softmax pieces (maximum, log sum exp)
     uint8_t* self_mask; int32_t* tgt; float* tgt_logit; float* lse;
@@ -1030,35 +1047,33 @@ struct SearchCall {
     // Shaped sampling (ovc_sample_shaped): has_options marks a call through the shaped entry points, whose workspace holds the
     // chooser's buffers; with neutral options the launches are ovc_sample's.
     bool has_options; float temperature; int top_k; float top_p;
-    // Constrained search (ovc_beam_search_constrained): the ban options, banned ids sorted; all zero: the plain search.
+    // The selection rule -- one per search -- and below the payload of each.  The *_from helpers and the rules' entry points set
+    // it together with the payload, and only for options that are not neutral: neutral options leave the plain call.  A new rule
+    // is declared here, in search_ok's switch and in rule_io, and routed in run_decode_step, finalize_search and search_graph_key.
+    SelectRule rule;
+    // Constrained (ovc_beam_search_constrained): the ban options, banned ids sorted.
     BeamConstraints cons;
     // Ensemble (ovc_ensemble_beam_search): ens_M > 1 members, ens[0] the call's model; every step runs each member's decoder rows
     // on the shared beams and selects on the mean of their log-probabilities.  One member is the plain call: ens_M stays 0.
     int ens_M; const ovc_model* ens[OVC_MAX_ENSEMBLE];
-    // Prefix search (ovc_beam_search_prefix): the caller's table in HOST memory -- ids [B][prefix_P], lengths [B] -- copied to the
-    // workspace outside any captured body.  prefix_P = 0 (no table, or every length 0): the plain search.  A sizer or predicate
-    // states prefix_P alone.
+    // Prefix (ovc_beam_search_prefix): the caller's table in HOST memory -- ids [B][prefix_P], lengths [B].  No table, or every
+    // length 0: the plain search.  A sizer or predicate states prefix_P alone.
     int prefix_P; const int32_t* prefix_ids; const int32_t* prefix_len;
-    // Diverse search (ovc_beam_search_diverse): groups > 1 groups of k / groups slots and the Hamming penalty's strength; one group is
-    // the plain call: groups stays 0.  slot_out: the caller's [B][out_size], the beam slot of each returned caption, or nullptr.
+    // Diverse (ovc_beam_search_diverse): groups > 1 groups of k / groups slots and the Hamming penalty's strength; one group is
+    // the plain search.  slot_out: the caller's [B][out_size], the beam slot of each returned caption, or nullptr -- the entry
+    // point's, one group included.
     int groups; float diversity; int32_t* slot_out;
-    bool diverse() const { return groups != 0; }
-    // Forced words (ovc_beam_search_forced): forced_C words per image in 2^forced_C banks of k >> forced_C slots; the caller's table
-    // [B][forced_C] in HOST memory, copied to the workspace outside any captured body, and the caller's met_out [B][out_size].  A
-    // sizer or predicate states forced_C alone.
+    // Forced (ovc_beam_search_forced): forced_C words per image in 2^forced_C banks of k >> forced_C slots; the caller's table
+    // [B][forced_C] in HOST memory and the caller's met_out [B][out_size].  A sizer or predicate states forced_C alone.
     int forced_C; const int32_t* forced_words; int32_t* met_out;
-    bool forced() const { return forced_C != 0; }
-    // Length-normalised search (ovc_beam_search_normalized): the caller's two tables of max_len floats in HOST memory (entry L - 1:
-    // 1 / lp(L) and gamma * L), copied to the workspace outside any captured body, and the caller's score_out / len_out
-    // [B][out_size].  A sizer or predicate sets `normalized` alone.
-    bool normalized; const float* norm_inv; const float* norm_bonus; float* score_out; int32_t* len_out;
+    // Normalized (ovc_beam_search_normalized): the caller's two tables of max_len floats in HOST memory (entry L - 1: 1 / lp(L) and
+    // gamma * L) and the caller's score_out / len_out [B][out_size].  A sizer or predicate sets the rule alone.
+    const float* norm_inv; const float* norm_bonus; float* score_out; int32_t* len_out;
     // The rows of an image at step t.  Step 0 has one row per image; a diverse search runs it once per group (the same <bos> row, the
     // same bits), so that every group has a first cache row and a first ancestor of its own and is a search of k / groups beams
     // from its first step on (a search of one step, T = 1, has no later step to prepare: one row).
-    int step_width(int t, int T) const { return t > 0 ? k : diverse() && T > 1 ? groups : 1; }
-    bool prefixed() const { return prefix_P != 0; }
+    int step_width(int t, int T) const { return t > 0 ? k : rule == SelectRule::Diverse && T > 1 ? groups : 1; }
     bool ensemble() const { return ens_M > 1; }
-    bool constrained() const { return cons.active(); }
     bool shaped() const { return sample && has_options && !(temperature == 1.0f && top_k == 0 && top_p == 1.0f); }
     bool counts_alive() const { return form == SearchForm::HostEarly || form == SearchForm::Gated; }
 };
@@ -1081,8 +1096,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c);
 // nothing else in the call.
 bool ensemble_ok(const ovc_model* m, const SearchCall& c) {
     if (c.ens_M < 2 || c.ens_M > OVC_MAX_ENSEMBLE || c.ens[0] != m) return false;
-    if (c.plan || c.sample || c.has_options || c.constrained() || c.prefixed() || c.diverse() || c.forced() || c.normalized ||
-        (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
+    if (c.plan || c.sample || c.has_options || c.rule != SelectRule::Best || (c.form != SearchForm::Plain && c.form != SearchForm::Graph))
         return false;
     SearchCall alone = c;
     alone.ens_M = 0;
@@ -1104,37 +1118,76 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
                      (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
         return false;
     if (c.has_options && (!c.sample || !ovc_sample_options_ok(c.temperature, c.top_k, c.top_p))) return false;
-    // constraints: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, plain launches or the whole-search graph
-    if (c.constrained() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan ||
-                            (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
-                            !ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)))
+    // every rule but the plain one: fp32, the fused vocabulary tail, beams (no draw), nothing else in the call, plain launches or the
+    // whole-search graph -- then the rule's own scope
+    if (c.rule != SelectRule::Best && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.has_options || c.plan ||
+                                       c.ens_M != 0 || (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
         return false;
-    // a prefix: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, no ban set, plain launches or the whole-search
-    // graph, and room for one free step behind the longest prefix
-    if (c.prefixed() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan || c.constrained() ||
-                         (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.prefix_P < 0 || c.prefix_P > m->max_len - 1))
-        return false;
-    // groups: fp32, the fused vocabulary tail, beams (no draw), no dropout plan, no ban set, no prefix, plain launches or the
-    // whole-search graph, and the options' own scope
-    if (c.diverse() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.plan || c.constrained() || c.prefixed() ||
-                        (c.form != SearchForm::Plain && c.form != SearchForm::Graph) || c.groups < 2 ||
-                        !ovc_beam_diversity_ok(c.k, c.groups, c.diversity)))
-        return false;
-    // forced words: fp32, the fused vocabulary tail, beams (no draw), nothing else in the call, plain launches or the whole-search
-    // graph, and the sizes' own scope
-    if (c.forced() && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.has_options || c.plan || c.constrained() ||
-                       c.prefixed() || c.diverse() || c.ens_M != 0 || (c.form != SearchForm::Plain && c.form != SearchForm::Graph) ||
-                       !ovc_beam_forced_ok(c.k, c.forced_C)))
-        return false;
-    // length normalisation: fp32, the fused vocabulary tail, beams (no draw), nothing else in the call, plain launches or the
-    // whole-search graph
-    if (c.normalized && (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks || c.sample || c.has_options || c.plan || c.constrained() ||
-                         c.prefixed() || c.diverse() || c.forced() || c.ens_M != 0 ||
-                         (c.form != SearchForm::Plain && c.form != SearchForm::Graph)))
-        return false;
+    switch (c.rule) {
+    case SelectRule::Best: case SelectRule::Normalized: break;
+    case SelectRule::Constrained:
+        if (!ovc_beam_constraints_ok(c.cons, m->vocab, m->max_len, c.k, m->eos_idx, m->pad_idx)) return false;
+        break;
+    case SelectRule::Prefix:        // room for one free step behind the longest prefix
+        if (c.prefix_P < 1 || c.prefix_P > m->max_len - 1) return false;
+        break;
+    case SelectRule::Diverse:
+        if (c.groups < 2 || !ovc_beam_diversity_ok(c.k, c.groups, c.diversity)) return false;
+        break;
+    case SelectRule::Forced:
+        if (!ovc_beam_forced_ok(c.k, c.forced_C)) return false;
+        break;
+    }
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k &&
            (!c.plan || train_scope_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}, TrainArch::Standard, true));
+}
+
+// A rule's buffers and copies, described here and nowhere else: its tail of w behind everything else (ovc_beam_search's layout is
+// a prefix of every rule's), carved at base + w.bytes, and the RuleIO between that tail and the call's pointers.
+RuleIO rule_io(const ovc_model* m, const SearchCall& c, Workspace& w, void* base) {
+    RuleIO io{};
+    Bump a{reinterpret_cast<char*>(base), w.bytes};
+    const size_t B = (size_t)c.B, R = B * c.k, T = (size_t)m->max_len;
+    switch (c.rule) {
+    case SelectRule::Best: case SelectRule::Constrained: case SelectRule::Diverse: break;
+    case SelectRule::Prefix:
+        w.prefix_ids = a.take<int32_t>(B * c.prefix_P); w.prefix_len = a.take<int32_t>(B);
+        io.table[0] = {w.prefix_ids, c.prefix_ids, sizeof(int32_t) * B * c.prefix_P};
+        io.table[1] = {w.prefix_len, c.prefix_len, sizeof(int32_t) * B};
+        io.ntable = 2;
+        break;
+    case SelectRule::Forced:
+        w.forced_words = a.take<int32_t>(B * c.forced_C); w.forced_met = a.take<int32_t>(R);
+        io.table[0] = {w.forced_words, c.forced_words, sizeof(int32_t) * B * c.forced_C};
+        io.column[0] = {c.met_out, w.forced_met, sizeof(int32_t)};
+        io.ntable = io.ncolumn = 1;
+        break;
+    case SelectRule::Normalized:
+        w.norm_inv = a.take<float>(T); w.norm_bonus = a.take<float>(T);
+        w.norm_len[0] = a.take<int32_t>(R); w.norm_len[1] = a.take<int32_t>(R);
+        w.norm_score = a.take<float>(R); w.norm_len_out = a.take<int32_t>(R);
+        io.table[0] = {w.norm_inv, c.norm_inv, sizeof(float) * T}; io.table[1] = {w.norm_bonus, c.norm_bonus, sizeof(float) * T};
+        io.column[0] = {c.score_out, w.norm_score, sizeof(float)}; io.column[1] = {c.len_out, w.norm_len_out, sizeof(int32_t)};
+        io.ntable = io.ncolumn = 2;
+        break;
+    }
+    if (a.off != w.bytes) w.bytes = (a.off + 255) & ~(size_t)255;
+    io.order_out = c.slot_out;
+    return io;
+}
+
+// The host tables to the workspace, in stream order and outside any captured body.
+bool stage_tables(const RuleIO& io, hipStream_t s) {
+    for (int i = 0; i < io.ntable; ++i)
+        if (hipMemcpyAsync(io.table[i].dst, io.table[i].src, io.table[i].bytes, hipMemcpyHostToDevice, s) != hipSuccess) return false;
+    return true;
+}
+
+// The first out_size entries of every image's [k] of a column to the caller's [B][out_size]; whole: one block (out_size == k).
+bool copy_column(const SearchCall& c, void* out, const void* col, size_t elem, bool whole, hipStream_t s) {
+    return (whole ? hipMemcpyAsync(out, col, elem * c.B * c.k, hipMemcpyDeviceToDevice, s)
+                  : hipMemcpy2DAsync(out, elem * c.out_size, col, elem * c.k, elem * c.out_size, c.B, hipMemcpyDeviceToDevice, s)) == hipSuccess;
 }
 
 // With a plan, or sampling: the seed / step-count slots behind the plain layout.
@@ -1147,26 +1200,7 @@ Workspace carve_search(const ovc_model* m, void* base, const SearchCall& c) {
         w.choice_word = a.take<int32_t>(R); w.choice_kept = a.take<int32_t>(R);
         w.bytes = (a.off + 255) & ~(size_t)255;
     }
-    if (c.prefixed()) {                           // behind everything else: ovc_beam_search's layout is a prefix of this one
-        Bump a{reinterpret_cast<char*>(base), w.bytes};
-        w.prefix_ids = a.take<int32_t>((size_t)c.B * c.prefix_P);
-        w.prefix_len = a.take<int32_t>((size_t)c.B);
-        w.bytes = (a.off + 255) & ~(size_t)255;
-    }
-    if (c.forced()) {                             // likewise behind ovc_beam_search's layout
-        Bump a{reinterpret_cast<char*>(base), w.bytes};
-        w.forced_words = a.take<int32_t>((size_t)c.B * c.forced_C);
-        w.forced_met = a.take<int32_t>((size_t)c.B * c.k);
-        w.bytes = (a.off + 255) & ~(size_t)255;
-    }
-    if (c.normalized) {                           // likewise behind ovc_beam_search's layout
-        Bump a{reinterpret_cast<char*>(base), w.bytes};
-        const size_t R = (size_t)c.B * c.k;
-        w.norm_inv = a.take<float>((size_t)m->max_len); w.norm_bonus = a.take<float>((size_t)m->max_len);
-        w.norm_len[0] = a.take<int32_t>(R); w.norm_len[1] = a.take<int32_t>(R);
-        w.norm_score = a.take<float>(R); w.norm_len_out = a.take<int32_t>(R);
-        w.bytes = (a.off + 255) & ~(size_t)255;
-    }
+    w.rule = rule_io(m, c, w, base);
     return w;
 }
 
@@ -1362,7 +1396,7 @@ int run_step_rows(Engine& e, Workspace& w, const SearchCall& c, int t, StepRows*
     pass.t = t; pass.width = width; pass.R = R; pass.anc = w.anc[cur];
     // a diverse search: a group's beams descend from that group's alone, and the decode self-attention lists the keys of the rows
     // it is given together -- per group, so that a group's decoder rows are those of a search of its own width, bit for bit
-    pass.self_width = c.diverse() ? (t == 0 ? 1 : k / c.groups) : width;
+    pass.self_width = c.rule == SelectRule::Diverse ?(t == 0 ? 1 : k / c.groups) : width;
     const float* x = w.x;         // every layer reads and writes the one buffer
     for (int l = 0; l < m->n_dec; ++l) {
         // the layer's keys / values go to its cache [L][T][R][h*dk|h*dv], the rows of step t
@@ -1487,14 +1521,12 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
             RUN(ovc_sample_shaped_update_launch(bu, tail, w.choice_word, B, s));
         } else if (c.sample)  // the one branch of a sampling step: a draw from the row's distribution in place of the k best
             RUN(ovc_sample_fused_update_launch(bu, tail, w.drop_seed, B, s));
-        else if (c.constrained() || c.prefixed() || c.diverse() || c.forced() || c.normalized || !(debug_skip() & 8)) {
-            // the one branch of a beam step: the call's options pick the instance -- a per-row ban set, the staged prefix table, the
-            // groups under the Hamming penalty, the banks of the staged forced words, the staged length tables, else the plain selection
-            // or its gated form
-            const BeamPrefix pre = c.prefixed() ? BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P} : BeamPrefix{};
-            FusedSelectOptions opt{c.cons, pre, c.groups, c.diversity, e.gate};
-            if (c.forced()) { opt.forced = w.forced_words; opt.forced_C = c.forced_C; opt.pad = m->pad_idx; }
-            if (c.normalized) opt.length = BeamLength{w.norm_len[cur], w.norm_len[nxt], w.norm_inv, w.norm_bonus, nullptr};
+        else if (c.rule != SelectRule::Best || !(debug_skip() & 8)) {
+            // the one branch of a beam step: the call's rule names the instance, its payload from the call (by value) and the
+            // workspace (the staged tables); the plain selection takes the gate
+            FusedSelectOptions opt{c.rule, c.cons, BeamPrefix{w.prefix_ids, w.prefix_len, c.prefix_P}, c.groups, c.diversity, e.gate,
+                                   w.forced_words, c.forced_C, m->pad_idx,
+                                   BeamLength{w.norm_len[cur], w.norm_len[nxt], w.norm_inv, w.norm_bonus, nullptr}};
             RUN(ovc_beam_fused_select_launch(bu, tail, w.running[cur], opt, B, s));
         }
         if (return_probs) {   // beam_search.py:68-72: every word's masked log-probability, from the pieces the decisions used
@@ -1515,7 +1547,9 @@ int run_decode_step(Engine& e, Workspace& w, const SearchCall& c, int t) {
     bs.cand_v = w.cand_v; bs.cand_i = w.cand_i; bs.chosen = nullptr; bs.score = nullptr;   // merged by the update kernel
     bs.masked_logp = return_probs ? w.all_buf + (size_t)t * R * m->vocab : nullptr;
     bs.row_max_out = w.row_max; bs.row_lsum_out = w.row_lsum;
-    if (c.prefixed() || c.diverse() || c.forced() || c.normalized) return OVC_EINVAL;   // search_ok: the fused tail; the two-pass pair knows none of these
+    // search_ok: the fused tail; the two-pass pair (the measurement switch) knows none of the rules' instances and, as ever, runs a
+    // ban set's search as the plain one
+    if (c.rule != SelectRule::Best && c.rule != SelectRule::Constrained) return OVC_EINVAL;
     RUN(ovc_beam_select_launch(bs, B, s, e.gate));
     RUN(ovc_beam_update_launch(bu, B, s, e.gate));
     return OVC_OK;
@@ -1623,10 +1657,13 @@ BeamFinalArgs final_args(const Workspace& w, int parity, const SearchCall& c, in
 // or a length-normalised search by its keys (it also leaves them and the lengths in w.norm_score / w.norm_len_out).  parity: the state
 // buffer bf reads.
 int finalize_search(const BeamFinalArgs& bf, const Workspace& w, const SearchCall& c, int parity, hipStream_t s) {
-    if (c.normalized)
+    switch (c.rule) {
+    case SelectRule::Normalized:
         return ovc_beam_finalize_normalized_launch(bf, BeamLength{w.norm_len[parity], nullptr, w.norm_inv, w.norm_bonus, nullptr}, w.norm_score,
                                                    w.norm_len_out, c.B, s);
-    return c.forced() ? ovc_beam_finalize_forced_launch(bf, c.forced_C, w.forced_met, c.B, s) : ovc_beam_finalize_launch(bf, c.B, s);
+    case SelectRule::Forced: return ovc_beam_finalize_forced_launch(bf, c.forced_C, w.forced_met, c.B, s);
+    default: return ovc_beam_finalize_launch(bf, c.B, s);
+    }
 }
 
 // The launches of a search behind its input kernels: the prologue and max_len steps.  This is what the whole-search graphs
@@ -1640,14 +1677,21 @@ int issue_search_body(Engine& e, Workspace& w, const SearchCall& c) {
     return finalize_search(final_args(w, T & 1, c, T, w.out_ids, w.out_logp), w, c, T & 1, e.stream);
 }
 
-// A sizer builds the SearchCall its entry point will build (out_size plays no part in the layout).
-size_t search_workspace_bytes(const ovc_model* m, int B, int N, int k, bool return_probs, bool dropout) {
+// A sizer builds the SearchCall its entry point will build (out_size plays no part in the layout; any non-null all_logp_out marks
+// return_probs: its presence alone adds the buffer), fills in its kind's members and asks sized_bytes.
+SearchCall sized_call(int B, int N, int k, bool return_probs) {
+    static float sized_probs;
     SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    DropPlan sized{};
     if (return_probs) c.all_logp_out = &sized_probs;
+    return c;
+}
+size_t sized_bytes(const ovc_model* m, const SearchCall& c) { return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0; }
+
+size_t search_workspace_bytes(const ovc_model* m, int B, int N, int k, bool return_probs, bool dropout) {
+    SearchCall c = sized_call(B, N, k, return_probs);
+    DropPlan sized{};
     if (dropout) c.plan = &sized;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+    return sized_bytes(m, c);
 }
 
 }  // namespace
@@ -1900,26 +1944,20 @@ GraphKey search_graph_key(const ovc_model* m, const SearchCall& c, const void* w
         return GraphKey{GraphKind::ShapedSampleSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N,
                         c.k, c.out_size};
     }
-    if (c.constrained())      // the options (banned ids sorted) are part of the key: no call replays another option set's graph
-        return GraphKey{GraphKind::ConstrainedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&c.cons, sizeof(c.cons)), workspace, c.B, c.N,
-                        c.k, c.out_size};
-    if (c.prefixed()) {       // "has a prefix" and P, never the words: the table is read from the workspace, refreshed per call
-        const int P = c.prefix_P;
-        return GraphKey{GraphKind::PrefixSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&P, sizeof(P)), workspace, c.B, c.N, c.k, c.out_size};
+    // a rule: its kind, and in the hash what its launches bake in -- never a staged table's contents, which are read from the
+    // workspace and refreshed per call.  The plain rule: the dropout plan's constants
+    GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
+    uint64_t h = c.drop_hash;
+    const struct { int G; float lambda; } groups{c.groups, c.diversity};
+    switch (c.rule) {
+    case SelectRule::Best: break;
+    case SelectRule::Constrained: kind = GraphKind::ConstrainedSearch; h = hash_bytes(&c.cons, sizeof(c.cons)); break;   // banned ids sorted
+    case SelectRule::Prefix: kind = GraphKind::PrefixSearch; h = hash_bytes(&c.prefix_P, sizeof(int)); break;
+    case SelectRule::Diverse: kind = GraphKind::DiverseSearch; h = hash_bytes(&groups, sizeof(groups)); break;
+    case SelectRule::Forced: kind = GraphKind::ForcedSearch; h = hash_bytes(&c.forced_C, sizeof(int)); break;
+    case SelectRule::Normalized: kind = GraphKind::NormalizedSearch; h = 0; break;
     }
-    if (c.diverse()) {        // G and the strength's bits are baked into every step's launch
-        const struct { int G; float lambda; } options{c.groups, c.diversity};
-        return GraphKey{GraphKind::DiverseSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&options, sizeof(options)), workspace, c.B, c.N, c.k,
-                        c.out_size};
-    }
-    if (c.forced()) {         // C, never the words: the table is read from the workspace, refreshed per call
-        const int C = c.forced_C;
-        return GraphKey{GraphKind::ForcedSearch, hash_bytes(m, sizeof(*m)) ^ hash_bytes(&C, sizeof(C)), workspace, c.B, c.N, c.k, c.out_size};
-    }
-    if (c.normalized)         // never the tables: they are read from the workspace, refreshed per call
-        return GraphKey{GraphKind::NormalizedSearch, hash_bytes(m, sizeof(*m)), workspace, c.B, c.N, c.k, c.out_size};
-    const GraphKind kind = c.sample ? GraphKind::SampleSearch : c.form == SearchForm::Gated ? GraphKind::GatedSearch : GraphKind::Search;
-    return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ c.drop_hash, workspace, c.B, c.N, c.k, c.out_size};
+    return GraphKey{kind, hash_bytes(m, sizeof(*m)) ^ h, workspace, c.B, c.N, c.k, c.out_size};
 }
 
 // The graph key of run_forward_call, built here and nowhere else (the rule: GraphKind).  The input form is not in it: the kernels
@@ -2023,9 +2061,8 @@ namespace {
 int run_search(const ovc_model* m, const SearchCall& c, const float* features, const float* boxes, void* workspace,
                size_t workspace_bytes, ovc_stream stream) {
     if (!search_model_ok(m, c) || !features || !workspace || !c.ids_out || !c.logp_out || (c.sample && !c.sample_seed)) return OVC_EINVAL;
-    if (c.prefixed() && (!c.prefix_ids || !c.prefix_len)) return OVC_EINVAL;
-    if (c.forced() && (!c.forced_words || !c.met_out)) return OVC_EINVAL;
-    if (c.normalized && (!c.norm_inv || !c.norm_bonus || !c.score_out || !c.len_out)) return OVC_EINVAL;
+    Workspace none{};                              // the rule's pointers of the caller's, before any layout exists
+    if (!rule_io(m, c, none, nullptr).pointers_ok()) return OVC_EINVAL;
     TRY(ovc_device_guard());
     if (!search_ok(m, c) || (!c.sample && (long)m->vocab < c.k)) return OVC_EINVAL;      // samples may repeat a word, beams may not
     if (!ovc_aligned16(features) || !ovc_aligned16(workspace)) return OVC_EINVAL;
@@ -2045,17 +2082,7 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
     }
     if (c.sample && hipMemcpyAsync(w.drop_seed, c.sample_seed, sizeof(int64_t), hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
         return OVC_ELAUNCH;                        // the same slot, refreshed the same way: a replayed graph reads this call's seed
-    if (c.prefixed() &&                            // the table, refreshed the same way: a replayed graph reads this call's prefixes
-        (hipMemcpyAsync(w.prefix_ids, c.prefix_ids, sizeof(int32_t) * c.B * c.prefix_P, hipMemcpyHostToDevice, e.stream) != hipSuccess ||
-         hipMemcpyAsync(w.prefix_len, c.prefix_len, sizeof(int32_t) * c.B, hipMemcpyHostToDevice, e.stream) != hipSuccess))
-        return OVC_ELAUNCH;
-    if (c.forced() &&                              // the word table, refreshed the same way: a replayed graph reads this call's words
-        hipMemcpyAsync(w.forced_words, c.forced_words, sizeof(int32_t) * c.B * c.forced_C, hipMemcpyHostToDevice, e.stream) != hipSuccess)
-        return OVC_ELAUNCH;
-    if (c.normalized &&                            // the length tables, refreshed the same way: a replayed graph reads this call's
-        (hipMemcpyAsync(w.norm_inv, c.norm_inv, sizeof(float) * T, hipMemcpyHostToDevice, e.stream) != hipSuccess ||
-         hipMemcpyAsync(w.norm_bonus, c.norm_bonus, sizeof(float) * T, hipMemcpyHostToDevice, e.stream) != hipSuccess))
-        return OVC_ELAUNCH;
+    if (!stage_tables(w.rule, e.stream)) return OVC_ELAUNCH;   // the rule's tables, refreshed the same way
     TRY(run_encoder_inputs(e, w, features, boxes, c.B, c.N));
     for (int i = 1; i < c.ens_M; ++i) {            // every member reads the call's features, and its boxes where its encoder takes them
         Engine me = e;
@@ -2095,27 +2122,13 @@ int run_search(const ovc_model* m, const SearchCall& c, const float* features, c
         bf.steps_run = steps_run < T ? steps_run : 0;
         TRY(finalize_search(bf, w, c, steps_run & 1, e.stream));
     }
-    // the banks of the returned captions: the first out_size entries of every image's final order (out_size == k: one block)
-    if (c.forced() && hipMemcpy2DAsync(c.met_out, sizeof(int32_t) * c.out_size, w.forced_met, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size,
-                                       c.B, hipMemcpyDeviceToDevice, e.stream) != hipSuccess)
-        return OVC_ELAUNCH;
-    // the keys and lengths of the returned captions, likewise
-    if (c.normalized &&
-        (hipMemcpy2DAsync(c.score_out, sizeof(float) * c.out_size, w.norm_score, sizeof(float) * c.k, sizeof(float) * c.out_size, c.B,
-                          hipMemcpyDeviceToDevice, e.stream) != hipSuccess ||
-         hipMemcpy2DAsync(c.len_out, sizeof(int32_t) * c.out_size, w.norm_len_out, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size, c.B,
-                          hipMemcpyDeviceToDevice, e.stream) != hipSuccess))
-        return OVC_ELAUNCH;
+    // what the rule's final ordering left of the returned captions: the banks, or the keys and lengths
+    for (int i = 0; i < w.rule.ncolumn; ++i)
+        if (!copy_column(c, w.rule.column[i].out, w.rule.column[i].col, w.rule.column[i].elem, false, e.stream)) return OVC_ELAUNCH;
     if (c.all_logp_out) TRY(ovc_beam_gather_all_launch(w.all_buf, w.order, c.B, c.k, T, m->vocab, c.all_logp_out, e.stream));
     if (c.steps_run_out) *c.steps_run_out = steps_run;
-    // the beam slot of each returned caption: the first out_size entries of every image's final order, a copy of this call alone
-    if (c.slot_out) {
-        const hipError_t rc = c.out_size == c.k
-            ? hipMemcpyAsync(c.slot_out, w.order, sizeof(int32_t) * c.B * c.k, hipMemcpyDeviceToDevice, e.stream)
-            : hipMemcpy2DAsync(c.slot_out, sizeof(int32_t) * c.out_size, w.order, sizeof(int32_t) * c.k, sizeof(int32_t) * c.out_size, c.B,
-                               hipMemcpyDeviceToDevice, e.stream);
-        if (rc != hipSuccess) return OVC_ELAUNCH;
-    }
+    // the beam slot of each returned caption: the final order itself, a copy of this call alone
+    if (w.rule.order_out && !copy_column(c, w.rule.order_out, w.order, sizeof(int32_t), c.out_size == c.k, e.stream)) return OVC_ELAUNCH;
     return write_search_slots(e, w, c, steps_run);
 }
 }  // namespace
@@ -2155,22 +2168,23 @@ extern "C" int ovc_beam_search_gated(const ovc_model* m, const float* features, 
 // Constrained search (include/ovc.h: the rule).  The plain search with a ban set in the selection of every step; neutral options
 // are the plain calls, launch for launch (the same SearchCall, hence the same graph key and workspace).
 // ---------------------------------------------------------------------------------------------
-// The options as the kernel takes them (ids sorted ascending); false: n_banned out of range or a null list.  The rest of the
-// scope is ovc_beam_constraints_ok's, inside search_ok.
-static bool constraints_from(int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, BeamConstraints* out) {
+// The options as the kernel takes them (ids sorted ascending) and, where they are not neutral, the rule; false: n_banned out of
+// range or a null list.  The rest of the scope is ovc_beam_constraints_ok's, inside search_ok.
+static bool constraints_from(int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, SelectRule* rule, BeamConstraints* out) {
     BeamConstraints c{};
     if (n_banned < 0 || n_banned > OVC_MAX_BANNED || (n_banned > 0 && !banned)) return false;
     c.ngram = no_repeat_ngram; c.min_length = min_length; c.n_banned = n_banned;
     for (int i = 0; i < n_banned; ++i) c.banned[i] = banned[i];
     std::sort(c.banned, c.banned + n_banned);
     *out = c;
+    if (c.active()) *rule = SelectRule::Constrained;
     return true;
 }
 
 extern "C" int ovc_search_constraints_ok(const ovc_model* m, int k, int no_repeat_ngram, int min_length, const int32_t* banned,
                                          int n_banned) {
     SearchCall c{1, 1, k, k};
-    if (!model_ok(m) || !constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return 0;
+    if (!model_ok(m) || !constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.rule, &c.cons)) return 0;
     return search_ok(m, c) ? 1 : 0;       // neutral options: the plain search's scope
 }
 
@@ -2180,7 +2194,7 @@ extern "C" int ovc_beam_search_constrained(const ovc_model* m, const float* feat
                                            float* all_logp_out, ovc_stream stream) {
     SearchCall c{B, N, k, out_size, SearchForm::Plain, ids_out, logp_out};
     c.all_logp_out = all_logp_out;
-    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return OVC_EINVAL;
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.rule, &c.cons)) return OVC_EINVAL;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
@@ -2189,7 +2203,7 @@ extern "C" int ovc_beam_search_constrained_graph(const ovc_model* m, const float
                                                  int n_banned, void* workspace, size_t workspace_bytes, int64_t* ids_out,
                                                  float* logp_out, ovc_stream stream) {
     SearchCall c{B, N, k, out_size, SearchForm::Graph, ids_out, logp_out};
-    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.cons)) return OVC_EINVAL;
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.rule, &c.cons)) return OVC_EINVAL;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
@@ -2205,13 +2219,11 @@ struct StepTest {
     const float* logits; const int32_t* hist; const float* running; const float* alive;
     int B, width, V, k, T, t, eos;
     int32_t* parent_out; int32_t* word_out; float* running_out; float* row_max_out; float* row_lsum_out;
-    FusedSelectOptions opt; const int32_t* prefix; const int32_t* prefix_len;      // one model: opt.prefix names no addresses yet
+    // one model: the rule and its payload, which names no staged table's address yet, and the rule's tables in HOST memory (src and
+    // bytes; in rule_io's order: the prefix ids [B][P] and lengths [B], the forced words [B][C], the length tables [T] twice)
+    FusedSelectOptions opt; RuleIO io;
     int members; int32_t* hot_out;                                                 // the ensemble kernel, and its hot-block count
     float* lp_out;
-    const int32_t* forced;                                                         // opt.forced_C != 0: the table [B][forced_C], HOST memory
-    // the length-normalised instance (norm_inv != nullptr): the tables [T] in HOST memory, the rows' lengths [B*width] and the
-    // winners' lengths and keys [B][k] in device memory
-    const float* norm_inv; const float* norm_bonus; const int32_t* len_in; int32_t* len_out; float* key_out;
 };
 
 static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
@@ -2238,24 +2250,15 @@ static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
     if (hipMemsetAsync(lp_in, 0, sizeof(float) * Rk * T, s) != hipSuccess || hipMemsetAsync(anc_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess ||
         (hist_in && hipMemsetAsync(hist_in, 0, sizeof(int32_t) * Rk * T, s) != hipSuccess))
         return OVC_ELAUNCH;
-    if (c.opt.prefix.P != 0) {
-        int32_t* ids_dev = a.take<int32_t>((size_t)B * T); int32_t* len_dev = a.take<int32_t>((size_t)B);
-        if (hipMemcpyAsync(ids_dev, c.prefix, sizeof(int32_t) * B * c.opt.prefix.P, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(len_dev, c.prefix_len, sizeof(int32_t) * B, hipMemcpyHostToDevice, s) != hipSuccess)
-            return OVC_ELAUNCH;
-        c.opt.prefix.ids = ids_dev; c.opt.prefix.len = len_dev;
-    }
-    if (c.opt.forced_C != 0) {                     // the forced words come in HOST memory and are staged likewise
-        int32_t* words_dev = a.take<int32_t>((size_t)B * c.opt.forced_C);
-        if (hipMemcpyAsync(words_dev, c.forced, sizeof(int32_t) * B * c.opt.forced_C, hipMemcpyHostToDevice, s) != hipSuccess) return OVC_ELAUNCH;
-        c.opt.forced = words_dev;
-    }
-    if (c.norm_inv) {                              // the length tables come in HOST memory and are staged likewise
-        float* inv_dev = a.take<float>((size_t)T); float* bonus_dev = a.take<float>((size_t)T);
-        if (hipMemcpyAsync(inv_dev, c.norm_inv, sizeof(float) * T, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(bonus_dev, c.norm_bonus, sizeof(float) * T, hipMemcpyHostToDevice, s) != hipSuccess)
-            return OVC_ELAUNCH;
-        c.opt.length = BeamLength{c.len_in, c.len_out, inv_dev, bonus_dev, c.key_out};
+    // the rule's tables come in HOST memory and are staged as run_search stages them, into the scratch
+    for (int i = 0; i < c.io.ntable; ++i) c.io.table[i].dst = a.take<char>(c.io.table[i].bytes);
+    if (!stage_tables(c.io, s)) return OVC_ELAUNCH;
+    void* const tab0 = c.io.table[0].dst; void* const tab1 = c.io.table[1].dst;
+    switch (c.opt.rule) {
+    case SelectRule::Prefix: c.opt.prefix.ids = static_cast<int32_t*>(tab0); c.opt.prefix.len = static_cast<int32_t*>(tab1); break;
+    case SelectRule::Forced: c.opt.forced = static_cast<int32_t*>(tab0); break;
+    case SelectRule::Normalized: c.opt.length.inv = static_cast<float*>(tab0); c.opt.length.bonus = static_cast<float*>(tab1); break;
+    default: break;
     }
     BeamUpdateArgs& bu = en.p;
     bu.alive_in = c.alive; bu.alive_out = alive_out; bu.running_out = c.running_out;
@@ -2272,6 +2275,19 @@ static int run_step_test(StepTest& c, void* scratch, ovc_stream stream) {
     return ovc_debug_collect_parents_launch(anc_out, hist_out, B, c.width, c.k, T, c.t, c.parent_out, c.word_out, s);
 }
 
+// What the five rule entries below refuse alike: a null pointer among those every one takes, and a bad shape.  Where the entries
+// differ the caller says which: min_V, the smallest vocabulary (1, or k where a row must offer k words), and one_is_first -- the
+// constrained entry reads width == 1 as step 0, so a beam of 1 has no later step there.
+static bool step_pointers_ok(const StepTest& c, const void* scratch) {
+    return c.logits && c.hist && c.running && c.alive && scratch && c.parent_out && c.word_out && c.running_out && c.row_max_out && c.row_lsum_out;
+}
+static bool step_shape_ok(const StepTest& c, int min_V, bool one_is_first) {
+    if (c.B <= 0 || c.width <= 0 || c.width > OVC_MAX_BEAM || c.k <= 0 || c.k > OVC_MAX_BEAM || c.V < min_V || (c.V + 31) / 32 > kFusedVocabBlocks ||
+        c.T < 1 || c.T > OVC_MAX_LEN || c.t < 0 || c.t >= c.T || (long)c.B * c.k * c.T > 0x7fffffffL / 8)
+        return false;
+    return c.width == (c.t == 0 ? 1 : c.k) && !(one_is_first && c.k == 1 && c.t > 0);
+}
+
 // Test entry: ONE step of the fused selection (run_step_test) under the constrained search's options: the constrained instance with
 // active options, the plain one with neutral options.  scratch: ovc_debug_beam_constrained_update_bytes.
 extern "C" size_t ovc_debug_beam_constrained_update_bytes(int B, int width, int V, int k, int T) {
@@ -2285,18 +2301,12 @@ extern "C" int ovc_debug_beam_constrained_update(const float* logits, const int3
                                                  const int32_t* banned, int n_banned, void* scratch, size_t scratch_bytes,
                                                  int32_t* parent_out, int32_t* word_out, float* running_out, float* row_max_out,
                                                  float* row_lsum_out, ovc_stream stream) {
-    BeamConstraints cons{};
-    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
-        return OVC_EINVAL;
-    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || (width != 1 && width != k) || V <= 0 ||
-        (V + 31) / 32 > kFusedVocabBlocks || T < 1 || T > OVC_MAX_LEN || t < 0 || t >= T || (width == 1) != (t == 0) || (long)B * k * T > 0x7fffffffL / 8)
-        return OVC_EINVAL;
-    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &cons) ||
-        (cons.active() && !ovc_beam_constraints_ok(cons, V, T, k, eos, -1)))      // neutral options: the plain step's scope
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (!step_pointers_ok(c, scratch) || !step_shape_ok(c, 1, true)) return OVC_EINVAL;
+    if (!constraints_from(no_repeat_ngram, min_length, banned, n_banned, &c.opt.rule, &c.opt.cons) ||
+        (c.opt.cons.active() && !ovc_beam_constraints_ok(c.opt.cons, V, T, k, eos, -1)))      // neutral options: the plain step's scope
         return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_constrained_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
-    c.opt.cons = cons;
     return run_step_test(c, scratch, stream);
 }
 
@@ -2317,25 +2327,18 @@ static bool prefix_from(const ovc_model* m, const int32_t* ids, const int32_t* l
             if (ids[(size_t)b * P + i] < 0 || ids[(size_t)b * P + i] >= m->vocab) return false;
         any = any || len[b] > 0;
     }
-    if (any) { c->prefix_P = P; c->prefix_ids = ids; c->prefix_len = len; }
+    if (any) { c->rule = SelectRule::Prefix; c->prefix_P = P; c->prefix_ids = ids; c->prefix_len = len; }
     return true;
 }
 
-extern "C" int ovc_search_prefix_ok(const ovc_model* m, int k, int P) {
-    SearchCall c{1, 1, k, k};
+extern "C" size_t ovc_prefix_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int P) {
+    SearchCall c = sized_call(B, N, k, return_probs);
     if (!model_ok(m) || P < 0 || P > m->max_len - 1) return 0;
-    c.prefix_P = P;
-    return search_ok(m, c) ? 1 : 0;       // P = 0: the plain search's scope
+    if (P > 0) { c.rule = SelectRule::Prefix; c.prefix_P = P; }      // P = 0: the plain search's scope
+    return sized_bytes(m, c);
 }
 
-extern "C" size_t ovc_prefix_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int P) {
-    SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
-    if (!model_ok(m) || P < 0 || P > m->max_len - 1) return 0;
-    c.prefix_P = P;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
-}
+extern "C" int ovc_search_prefix_ok(const ovc_model* m, int k, int P) { return ovc_prefix_workspace_bytes(m, 1, 1, k, 0, P) != 0; }
 
 extern "C" int ovc_beam_search_prefix(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
                                       const int32_t* prefix, const int32_t* prefix_len, int P, void* workspace, size_t workspace_bytes,
@@ -2365,11 +2368,8 @@ extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* 
                                             int width, int V, int k, int T, int t, int eos, const int32_t* prefix, const int32_t* prefix_len,
                                             int P, void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out,
                                             float* running_out, float* row_max_out, float* row_lsum_out, ovc_stream stream) {
-    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
-        return OVC_EINVAL;
-    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || (width != 1 && width != k) || V <= 0 ||
-        (V + 31) / 32 > kFusedVocabBlocks || T < 1 || T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
-        return OVC_EINVAL;
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (!step_pointers_ok(c, scratch) || !step_shape_ok(c, 1, false)) return OVC_EINVAL;
     if (P < 0 || P > T - 1 || (P > 0 && (!prefix || !prefix_len))) return OVC_EINVAL;
     bool any = false;
     for (int b = 0; b < B && P > 0; ++b) {
@@ -2379,8 +2379,11 @@ extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* 
         any = any || prefix_len[b] > 0;
     }
     if (scratch_bytes < ovc_debug_beam_prefix_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
-    if (any) { c.opt.prefix.P = P; c.prefix = prefix; c.prefix_len = prefix_len; }      // as prefix_from: no length, no table
+    if (any) {                                      // as prefix_from: no length, no table
+        c.opt.rule = SelectRule::Prefix; c.opt.prefix.P = P;
+        c.io.table[0] = {nullptr, prefix, sizeof(int32_t) * B * P}; c.io.table[1] = {nullptr, prefix_len, sizeof(int32_t) * B};
+        c.io.ntable = 2;
+    }
     return run_step_test(c, scratch, stream);
 }
 
@@ -2391,18 +2394,16 @@ extern "C" int ovc_debug_beam_prefix_update(const float* logits, const int32_t* 
 // The call's options as the SearchCall takes them; false: G outside 1..k or not dividing k, lambda negative, not finite or above 1e30.
 static bool diversity_from(int k, int G, float lambda, SearchCall* c) {
     if (!ovc_beam_diversity_ok(k, G, lambda)) return false;
-    if (G > 1) { c->groups = G; c->diversity = lambda; }
+    if (G > 1) { c->rule = SelectRule::Diverse; c->groups = G; c->diversity = lambda; }
     return true;
 }
 
 extern "C" size_t ovc_beam_search_diverse_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int G, float lambda) {
-    SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
+    SearchCall c = sized_call(B, N, k, return_probs);
     if (!model_ok(m) || !diversity_from(k, G, lambda, &c)) return 0;
     // one group runs the plain launches, but the call is the diverse search's: its scope holds for every G
     if (m->precision != 0 || (m->vocab + 31) / 32 > kFusedVocabBlocks) return 0;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+    return sized_bytes(m, c);
 }
 
 static int run_diverse(const ovc_model* m, SearchCall c, int G, float lambda, int32_t* slot_out, const float* features, const float* boxes,
@@ -2438,15 +2439,10 @@ extern "C" int ovc_debug_beam_diverse_update(const float* logits, const int32_t*
                                              int width, int V, int k, int T, int t, int eos, int G, float lambda, void* scratch,
                                              size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
                                              float* row_max_out, float* row_lsum_out, ovc_stream stream) {
-    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out)
-        return OVC_EINVAL;
-    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
-        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
-        return OVC_EINVAL;
-    if (!ovc_beam_diversity_ok(k, G, lambda)) return OVC_EINVAL;
-    if (scratch_bytes < ovc_debug_beam_diverse_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
     StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
-    if (G > 1) { c.opt.groups = G; c.opt.diversity = lambda; }                           // as diversity_from: one group is the plain call
+    if (!step_pointers_ok(c, scratch) || !step_shape_ok(c, k, false) || !ovc_beam_diversity_ok(k, G, lambda)) return OVC_EINVAL;
+    if (scratch_bytes < ovc_debug_beam_diverse_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
+    if (G > 1) { c.opt.rule = SelectRule::Diverse; c.opt.groups = G; c.opt.diversity = lambda; }   // as diversity_from: one group is the plain call
     return run_step_test(c, scratch, stream);
 }
 
@@ -2466,27 +2462,22 @@ static bool forced_words_ok(const int32_t* words, int B, int C, int V, const int
     return true;
 }
 
-extern "C" int ovc_search_forced_ok(const ovc_model* m, int k, int C) {
-    SearchCall c{1, 1, k, k};
+extern "C" size_t ovc_forced_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int C) {
+    SearchCall c = sized_call(B, N, k, return_probs);
     if (!model_ok(m) || !ovc_beam_forced_ok(k, C)) return 0;
-    c.forced_C = C;
-    return search_ok(m, c) && m->vocab >= k ? 1 : 0;
+    c.rule = SelectRule::Forced; c.forced_C = C;
+    return sized_bytes(m, c);
 }
 
-extern "C" size_t ovc_forced_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs, int C) {
-    SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
-    if (!model_ok(m) || !ovc_beam_forced_ok(k, C)) return 0;
-    c.forced_C = C;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+extern "C" int ovc_search_forced_ok(const ovc_model* m, int k, int C) {
+    return ovc_forced_workspace_bytes(m, 1, 1, k, 0, C) != 0 && m->vocab >= k;
 }
 
 static int run_forced(const ovc_model* m, SearchCall c, const int32_t* forced, int C, int32_t* met_out, const float* features,
                       const float* boxes, void* workspace, size_t workspace_bytes, ovc_stream stream) {
     if (!model_ok(m) || !forced || !met_out || c.B <= 0 || !ovc_beam_forced_ok(c.k, C)) return OVC_EINVAL;
     if (!forced_words_ok(forced, c.B, C, m->vocab, {m->pad_idx, m->bos_idx, m->eos_idx})) return OVC_EINVAL;
-    c.forced_C = C; c.forced_words = forced; c.met_out = met_out;
+    c.rule = SelectRule::Forced; c.forced_C = C; c.forced_words = forced; c.met_out = met_out;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
@@ -2515,15 +2506,12 @@ extern "C" int ovc_debug_beam_forced_update(const float* logits, const int32_t* 
                                             int width, int V, int k, int T, int t, int eos, int pad, const int32_t* forced, int C,
                                             void* scratch, size_t scratch_bytes, int32_t* parent_out, int32_t* word_out, float* running_out,
                                             float* row_max_out, float* row_lsum_out, ovc_stream stream) {
-    if (!logits || !hist || !running || !alive || !scratch || !parent_out || !word_out || !running_out || !row_max_out || !row_lsum_out || !forced)
-        return OVC_EINVAL;
-    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
-        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
-        return OVC_EINVAL;
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (!step_pointers_ok(c, scratch) || !forced || !step_shape_ok(c, k, false)) return OVC_EINVAL;
     if (!ovc_beam_forced_ok(k, C) || pad < 0 || pad >= V || !forced_words_ok(forced, B, C, V, {pad, -1, eos})) return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_forced_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
-    c.opt.forced_C = C; c.opt.pad = pad; c.forced = forced;
+    c.opt.rule = SelectRule::Forced; c.opt.forced_C = C; c.opt.pad = pad;
+    c.io.table[0] = {nullptr, forced, sizeof(int32_t) * B * C}; c.io.ntable = 1;
     return run_step_test(c, scratch, stream);
 }
 
@@ -2541,18 +2529,16 @@ static bool length_tables_ok(const float* inv, const float* bonus, int n) {
 }
 
 extern "C" size_t ovc_beam_search_normalized_workspace_bytes(const ovc_model* m, int B, int N, int k, int return_probs) {
-    SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
-    if (!model_ok(m)) return 0;
-    c.normalized = true;
-    return search_ok(m, c) && m->vocab >= k ? carve_search(m, nullptr, c).bytes : 0;
+    SearchCall c = sized_call(B, N, k, return_probs);
+    if (!model_ok(m) || m->vocab < k) return 0;
+    c.rule = SelectRule::Normalized;
+    return sized_bytes(m, c);
 }
 
 static int run_normalized(const ovc_model* m, SearchCall c, const float* inv, const float* bonus, float* score_out, int32_t* len_out,
                           const float* features, const float* boxes, void* workspace, size_t workspace_bytes, ovc_stream stream) {
     if (!model_ok(m) || !score_out || !len_out || c.B <= 0 || !length_tables_ok(inv, bonus, m->max_len)) return OVC_EINVAL;
-    c.normalized = true; c.norm_inv = inv; c.norm_bonus = bonus; c.score_out = score_out; c.len_out = len_out;
+    c.rule = SelectRule::Normalized; c.norm_inv = inv; c.norm_bonus = bonus; c.score_out = score_out; c.len_out = len_out;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
 }
 
@@ -2582,16 +2568,12 @@ extern "C" int ovc_debug_beam_normalized_update(const float* logits, const int32
                                                 const float* bonus, void* scratch, size_t scratch_bytes, int32_t* parent_out,
                                                 int32_t* word_out, float* running_out, float* row_max_out, float* row_lsum_out,
                                                 int32_t* len_out, float* key_out, ovc_stream stream) {
-    if (!logits || !hist || !running || !alive || !len_in || !scratch || !parent_out || !word_out || !running_out || !row_max_out ||
-        !row_lsum_out || !len_out || !key_out)
-        return OVC_EINVAL;
-    if (B <= 0 || width <= 0 || width > OVC_MAX_BEAM || k <= 0 || k > OVC_MAX_BEAM || V < k || (V + 31) / 32 > kFusedVocabBlocks || T < 1 ||
-        T > OVC_MAX_LEN || t < 0 || t >= T || width != (t == 0 ? 1 : k) || (long)B * k * T > 0x7fffffffL / 8)
-        return OVC_EINVAL;
+    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
+    if (!step_pointers_ok(c, scratch) || !len_in || !len_out || !key_out || !step_shape_ok(c, k, false)) return OVC_EINVAL;
     if (!length_tables_ok(inv, bonus, T)) return OVC_EINVAL;
     if (scratch_bytes < ovc_debug_beam_normalized_update_bytes(B, width, V, k, T) || !ovc_aligned16(scratch)) return OVC_EWORKSPACE;
-    StepTest c{logits, hist, running, alive, B, width, V, k, T, t, eos, parent_out, word_out, running_out, row_max_out, row_lsum_out};
-    c.norm_inv = inv; c.norm_bonus = bonus; c.len_in = len_in; c.len_out = len_out; c.key_out = key_out;
+    c.opt.rule = SelectRule::Normalized; c.opt.length = BeamLength{len_in, len_out, nullptr, nullptr, key_out};
+    c.io.table[0] = {nullptr, inv, sizeof(float) * T}; c.io.table[1] = {nullptr, bonus, sizeof(float) * T}; c.io.ntable = 2;
     return run_step_test(c, scratch, stream);
 }
 
@@ -2610,9 +2592,7 @@ static bool members_from(const ovc_model* const* models, int M, SearchCall* c) {
 }
 
 extern "C" size_t ovc_ensemble_workspace_bytes(const ovc_model* const* models, int M, int B, int N, int k, int return_probs) {
-    SearchCall c{B, N, k, k};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
+    SearchCall c = sized_call(B, N, k, return_probs);
     if (!members_from(models, M, &c) || !search_ok(models[0], c)) return 0;
     Workspace members[OVC_MAX_ENSEMBLE];
     return c.ensemble() ? carve_ensemble(c, nullptr, members) : carve_search(models[0], nullptr, c).bytes;
@@ -2690,11 +2670,9 @@ extern "C" int ovc_ensemble_combine(const float* const* logps, int M, long rows,
 // ancestor, every total score 0 -- so the final kernel, whose order is stable, returns the samples in sample order.
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t ovc_sample_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs) {
-    SearchCall c{B, N, S, S};
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
+    SearchCall c = sized_call(B, N, S, return_probs);
     c.sample = true;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+    return sized_bytes(m, c);
 }
 
 extern "C" int ovc_sample(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,
@@ -2723,10 +2701,7 @@ static SearchCall shaped_sample_call(SearchCall c, const int64_t* seed, float te
 
 extern "C" size_t ovc_sample_shaped_workspace_bytes(const ovc_model* m, int B, int N, int S, int return_probs, float temperature,
                                                     int top_k, float top_p) {
-    SearchCall c = shaped_sample_call(SearchCall{B, N, S, S}, nullptr, temperature, top_k, top_p);
-    float sized_probs = 0.f;
-    if (return_probs) c.all_logp_out = &sized_probs;
-    return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0;
+    return sized_bytes(m, shaped_sample_call(sized_call(B, N, S, return_probs), nullptr, temperature, top_k, top_p));
 }
 
 extern "C" int ovc_sample_shaped(const ovc_model* m, const float* features, const float* boxes, int B, int N, int S, const int64_t* seed,

@@ -11,6 +11,7 @@ engine (``BaseTransformer._apply``).
 Numerics never depend on a timing: the order in which every GEMM sums over K is fixed per call site
 (``csrc/gemm.hip``, K-order classes), the tiling measurement below only ranks bit-identical tilings.
 """
+import collections
 import ctypes
 import json
 import math
@@ -36,6 +37,45 @@ from .native import check
 # one tiling measurement at a time per process (it synchronises the stream and shares one scratch buffer); the tuning
 # objective travels as an explicit argument of every tune / get / set call (ABI 6), not as process-wide state
 _TUNE_LOCK = threading.Lock()
+
+
+# What ``CaptionEngine._run_search`` needs to know of a generation's kind besides the plain search and the plain draw: a
+# selection rule, the shaped draw or the masked search.  A new rule is one more ``_SEARCH_FORMS`` entry and one more ``_RULES`` entry.
+#   kind    the ``_SEARCH_FORMS`` key
+#   sizer   the sizer's arguments behind ``return_probs``
+#   args    the entry point's named arguments that are no tensor of the call
+#   keep    ``_stream_key`` name -> host memory the library copies in stream order, kept per stream
+#   extras  ``(argument name, dtype, per_step)`` of each further result, ``(B, out_size)`` or per step ``(B, out_size, T)``
+#   check   ``check(B, T)``: the refusal that needs the batch -- its message, or a false value -- or None
+_Rule = collections.namedtuple("_Rule", "kind sizer args keep extras check", defaults=((), {}, {}, (), None))
+_INT_P, _FLOAT_P = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+
+
+def _rows(what, rows):
+    return lambda B, T: rows != B and "{} holds {} rows but the batch {} images".format(what, rows, B)
+
+
+# kind -> its record from what the kind's check returned (and is not neutral): the ``ovc_dropout`` table; ``sample_options``'
+# ``(temperature, top_k, top_p)``; ``check_constraints``' ``(n, L, banned)``; ``check_prefix``' int32 numpy ``(ids, lengths)``;
+# ``diverse.check``'s ``G, penalty``; ``forced.check``'s int32 numpy ``(B, C)``; ``length.tables``' fp32 numpy ``(inv, bonus)``.
+# The extras: the slot each returned beam's ancestor held at every step; each returned caption's slot; its bank (met set, -1 for
+# an empty slot); its key and length.
+_RULES = {
+    "masked": lambda table: _Rule("masked", args={"table": ctypes.byref(table)}, extras=(("slots", torch.int32, True),)),
+    "shaped": lambda options: _Rule("shaped", options, dict(zip(("temperature", "top_k", "top_p"), options))),
+    "constrained": lambda o: _Rule("constrained", args=dict(ngram=o[0], min_length=o[1], n_banned=len(o[2]),
+                                                            banned=(ctypes.c_int32 * max(1, len(o[2])))(*o[2]))),
+    "prefix": lambda t: _Rule("prefix", (t[0].shape[1],), dict(prefix=t[0].ctypes.data_as(_INT_P), prefix_len=t[1].ctypes.data_as(_INT_P),
+                                                               P=t[0].shape[1]), {"prefix_table": t}, check=_rows("prefix", t[0].shape[0])),
+    "diverse": lambda G, penalty: _Rule("diverse", (G, penalty), dict(groups=G, penalty=penalty), extras=(("slot", torch.int32, False),)),
+    "forced": lambda t: _Rule("forced", (t.shape[1],), dict(forced=t.ctypes.data_as(_INT_P), C=t.shape[1]), {"forced_table": t},
+                              (("met", torch.int32, False),), _rows("forced_words", t.shape[0])),
+    "normalized": lambda t: _Rule(
+        "normalized", (), dict(inv=t[0].ctypes.data_as(_FLOAT_P), bonus=t[1].ctypes.data_as(_FLOAT_P)), {"length_tables": t},
+        (("score", torch.float32, False), ("lengths", torch.int32, False)),
+        lambda B, T: (len(t[0]) != T or len(t[1]) != T or t[0].dtype != "float32" or t[1].dtype != "float32")
+        and "the length tables must hold max_len = {} float32 entries each".format(T)),
+}
 
 
 def _p(t):
@@ -669,35 +709,15 @@ class CaptionEngine:
             "graph": ("ovc_sample_shaped_graph", ("seed", "temperature", "top_k", "top_p", *_RESULTS, "stream"))}),
     }
 
-    def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, table_drop=None, seed=None,
-                    options=None, constraints=None, prefix=None, diverse=None, forced=None, length=None):
+    def _run_search(self, features, boxes, batch_size, width, out_size, return_probs, early=False, seed=None, rule=None):
         """Every generation: the refusals, the kind and form, the stream's workspace, the results, and the call.  ``width``: the
         beam size or, with ``seed`` (a checked one-element int64 device tensor), the number of samples, which is then
-        ``out_size`` as well.  ``table_drop``: the ``ovc_dropout`` table of a search with dropout (``ovc_beam_search_dropout`` in
-        the form ``early`` selects), or None.  Returns ``(ids, logp, everything, slots)``, ``ids`` / ``logp`` / ``slots``
-        ``(B, out_size, T)``; ``everything`` ``(B, width, T, V)`` with ``return_probs``, else None; ``slots`` (int32, None without
-        dropout): the beam slot each returned beam's ancestor held at every step, the key of its masks
-        (``sequence_backward(dropout=..., slots=...)`` recomputes under them).  ``options``: what ``sample_options`` returned --
-        the shaped sampler's ``(temperature, top_k, top_p)``, or None for the plain draw.  ``constraints``: what
-        ``check_constraints`` returned and is not neutral -- ``(n, L, banned)`` -- or None for the plain search.  ``prefix``: what
-        ``check_prefix`` returned and is not neutral -- the table ``(ids, lengths)`` -- or None.  ``diverse``: the diverse search's
-        ``(G, penalty)`` as ``diverse.check`` returned them, or None; ``slots`` is then int32 ``(B, out_size)``, the beam slot of each
-        returned caption.  ``forced``: the forced words' int32 numpy table ``(B, C)`` as ``forced.check`` returned it, or None;
-        ``slots`` is then int32 ``(B, out_size)``, the bank (met set) of each returned caption, -1 for an empty slot.  ``length``:
-        the normalised search's fp32 numpy tables ``(inv, bonus)`` as ``length.tables`` built them, or None; ``slots`` is then the
-        pair ``(scores fp32, lengths int32)``, each ``(B, out_size)``: every returned caption's key and length."""
-        kind = ("shaped" if options else "sample") if seed is not None else "beam" if table_drop is None else "masked"
-        if constraints:
-            kind = "constrained"
-        if prefix:
-            kind = "prefix"
-        if diverse:
-            kind = "diverse"
-        if forced is not None:
-            kind = "forced"
-        if length is not None:
-            kind = "normalized"
-        if table_drop is not None:
+        ``out_size`` as well.  ``rule``: the ``_Rule`` of the call's kind, or None for the plain search and the plain draw.  Returns
+        ``(ids, logp, everything, extras)``, ``ids`` / ``logp`` ``(B, out_size, T)``; ``everything`` ``(B, width, T, V)`` with
+        ``return_probs``, else None; ``extras``: the tensors ``rule.extras`` declares, in that order."""
+        rule = rule or _Rule("beam" if seed is None else "sample")
+        kind = rule.kind
+        if kind == "masked":
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
                 raise native.OvcError("beam_search(dropout=...): dropout covers the plain standard transformer (with or without "
@@ -712,59 +732,27 @@ class CaptionEngine:
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
         if form == "graph" and not self.use_graph and kind != "masked":
             form = "plain"
-        ws, need = self._search_workspace(kind, B, N, width, return_probs, (prefix[0].shape[1],) if prefix else (forced.shape[1],) if forced is not None else diverse or options or ())
+        ws, need = self._search_workspace(kind, B, N, width, return_probs, rule.sizer)
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
         logp = torch.empty(B, out_size, T, dtype=torch.float32, device=self.device)
-        slots = None if table_drop is None else torch.empty(B, out_size, T, dtype=torch.int32, device=self.device)
-        if diverse or forced is not None:
-            slots = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
-        score = lengths = None
-        if length is not None:
-            score = torch.empty(B, out_size, dtype=torch.float32, device=self.device)
-            lengths = torch.empty(B, out_size, dtype=torch.int32, device=self.device)
-            slots = (score, lengths)
+        extras = tuple(torch.empty((B, out_size, T) if per_step else (B, out_size), dtype=dtype, device=self.device)
+                       for _, dtype, per_step in rule.extras)
         everything = torch.empty(B, width, T, d.vocab, dtype=torch.float32, device=self.device) if return_probs else None
         steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
         # OVC_GRAPH=0: every call is the first of its shape (plain launches; the host-early search without dropout keeps its graphs)
-        if not self.use_graph and (form == "device" or table_drop is not None):
+        if not self.use_graph and (form == "device" or kind == "masked"):
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         args = {name: None if t is None else t.data_ptr() for name, t in (
-            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("slots", None if length is not None else slots),
-            ("steps", steps), ("seed", seed), ("score", score), ("lengths", lengths),
-            ("slot", slots if diverse else None), ("met", slots if forced is not None else None))}
-        args.update(out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
-        if table_drop is not None:
-            args.update(table=ctypes.byref(table_drop), mode=("graph", "early", "device").index(form))
-        if options:
-            args.update(zip(("temperature", "top_k", "top_p"), options))
-        if diverse:
-            args.update(groups=diverse[0], penalty=diverse[1])
-        if forced is not None:
-            if forced.shape[0] != B:
-                raise native.OvcError("forced_words holds {} rows but the batch {} images".format(forced.shape[0], B))
-            # host memory the library copies in stream order: kept until the stream's next call with forced words replaces it
-            self._buffers[self._stream_key("forced_table")] = forced
-            args.update(forced=forced.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), C=forced.shape[1])
-        if length is not None:
-            inv, bonus = length
-            if len(inv) != T or len(bonus) != T or inv.dtype != "float32" or bonus.dtype != "float32":
-                raise native.OvcError("the length tables must hold max_len = {} float32 entries each".format(T))
-            # host memory the library copies in stream order: kept until the stream's next normalised call replaces it
-            self._buffers[self._stream_key("length_tables")] = length
-            float_p = ctypes.POINTER(ctypes.c_float)
-            args.update(inv=inv.ctypes.data_as(float_p), bonus=bonus.ctypes.data_as(float_p))
-        if constraints:
-            n, L, banned = constraints
-            args.update(ngram=n, min_length=L, banned=(ctypes.c_int32 * max(1, len(banned)))(*banned), n_banned=len(banned))
-        if prefix:
-            table, lengths = prefix
-            if table.shape[0] != B:
-                raise native.OvcError("prefix holds {} rows but the batch {} images".format(table.shape[0], B))
-            # host memory the library copies in stream order: kept until the stream's next prefix call replaces it
-            self._buffers[self._stream_key("prefix_table")] = prefix
-            int_p = ctypes.POINTER(ctypes.c_int32)
-            args.update(prefix=table.ctypes.data_as(int_p), prefix_len=lengths.ctypes.data_as(int_p), P=table.shape[1])
+            ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("steps", steps), ("seed", seed),
+            *zip((name for name, _, _ in rule.extras), extras))}
+        args.update(rule.args, out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
+        if kind == "masked":
+            args["mode"] = ("graph", "early", "device").index(form)
+        if rule.check and rule.check(B, T):
+            raise native.OvcError(rule.check(B, T))
+        for name, table in rule.keep.items():     # kept until the stream's next call of the kind replaces them
+            self._buffers[self._stream_key(name)] = table
         entry, names = self._SEARCH_FORMS[kind][3][form]
         self.last_steps_run = T
         check(getattr(self.lib, entry)(ctypes.byref(d), features.data_ptr(), None if boxes is None else boxes.data_ptr(), B, N,
@@ -773,7 +761,7 @@ class CaptionEngine:
             self.last_steps_run = issued.value
         if form == "device":
             self.last_steps_device = steps
-        return ids, logp, everything, slots
+        return ids, logp, everything, extras
 
     def check_constraints(self, beam_size, constraints=None, early_exit=None, dropout=None):
         """The refusals of a constrained search that need no input, each naming its argument: callers run them before any
@@ -858,10 +846,12 @@ class CaptionEngine:
             if return_probs:
                 raise native.OvcError("beam_search(dropout=...) has no return_probs form")
             table_drop = self._dropout_table(dropout)
-        ids, logp, everything, slots = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early,
-                                                        table_drop, constraints=constraints, prefix=prefix)
+        # one rule per search: check_constraints / check_prefix have refused the combinations
+        rule = (_RULES["masked"](table_drop) if table_drop is not None else _RULES["constrained"](constraints) if constraints
+                else _RULES["prefix"](prefix) if prefix else None)
+        ids, logp, everything, extras = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early, rule=rule)
         if dropout is not None:
-            return ids, logp, slots
+            return ids, logp, extras[0] if extras else None
         if out_size == 1:
             ids, logp = ids.squeeze(1), logp.squeeze(1)
         return (ids, logp, everything) if return_probs else (ids, logp)
@@ -891,7 +881,8 @@ class CaptionEngine:
         out_size = k if out_size is None else int(out_size)
         if not 1 <= out_size <= k:
             raise native.OvcError("diverse_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
-        ids, logp, everything, slots = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, diverse=(G, lam))
+        ids, logp, everything, (slots,) = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False,
+                                                           rule=_RULES["diverse"](G, lam))
         return (ids, logp, slots, everything) if return_probs else (ids, logp, slots)
 
     def check_forced(self, batch_size, beam_size, forced_words):
@@ -920,7 +911,8 @@ class CaptionEngine:
         out_size = _forced._index(out_size, "out_size")
         if not 1 <= out_size <= k:
             raise native.OvcError("forced_beam_search: out_size must lie in 1..beam_size = {}, got {}".format(k, out_size))
-        ids, logp, everything, met = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False, forced=table)
+        ids, logp, everything, (met,) = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False,
+                                                         rule=_RULES["forced"](table))
         return (ids, logp, met, everything) if return_probs else (ids, logp, met)
 
     def check_normalized(self, beam_size, length_penalty=1.0, length_form="avg", word_reward=0.0, out_size=1):
@@ -958,7 +950,7 @@ class CaptionEngine:
         else:
             tables = _length.tables(alpha, form, gamma, self.desc.max_len)
             ids, logp, everything, (score, lengths) = self._run_search(features, boxes, batch_size, k, out_size, return_probs, False,
-                                                                       length=tables)
+                                                                       rule=_RULES["normalized"](tables))
             out = (ids, logp, score, lengths)
         return out + ((everything,) if return_probs else ())
 
@@ -1027,7 +1019,8 @@ class CaptionEngine:
         S, options = checked or self.check_sample(n_samples, temperature, top_k, top_p)
         if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != self.device:
             raise native.OvcError("sample: the seed must be a one-element int64 tensor on {}".format(self.device))
-        ids, logp, everything, _ = self._run_search(features, boxes, batch_size, S, S, return_probs, seed=seed, options=options)
+        ids, logp, everything, _ = self._run_search(features, boxes, batch_size, S, S, return_probs, seed=seed,
+                                                    rule=_RULES["shaped"](options) if options else None)
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     # -- training ---------------------------------------------------------------------------------------------------

@@ -509,7 +509,7 @@ int ovc_sequence_backward(const ovc_model* m, const ovc_model* grads, const floa
  *   model and (with .b where the model has one) in grads;
  *   the fused vocabulary tail and the 32-bit descriptor limits of ovc_forward_backward, the latter also over levels * rows rows.
  * Dropout is taken as the identity by these two; the loss form under dropout is ovc_forward_backward_level_dropout below, the
- * sequence form has none.
+ * sequence form's ovc_sequence_backward_level_dropout (behind ovc_beam_search_dropout).
  * ovc_train_meshed_workspace_bytes / ovc_train_meshed_beams_workspace_bytes: bytes of workspace, 0 when unsupported. */
 size_t ovc_train_meshed_workspace_bytes(const ovc_model* m, int B, int N, int T);
 int ovc_forward_backward_meshed(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B, int N,
@@ -651,6 +651,50 @@ int ovc_sequence_backward_dropout(const ovc_model* m, const ovc_model* grads, co
                                   const ovc_dropout* dropout);
 int ovc_dropout_mask_rows(const int64_t* seed, int site, const int32_t* mask_rows, long rows, long cols, float p, uint8_t* keep,
                           ovc_stream stream);
+
+/* SCST of the meshed-memory transformer under dropout (appended to ABI 8; no struct changes): the two calls above for the model of
+ * ovc_forward_backward_level_dropout.  The rule.  Every dropout site keeps the rule above -- encoder sites (the multilevel encoder's
+ * three per layer, the feature embedding) key on b * N + n, decoder sites on the mask row mrow(b, slot, t) -- but one: enc_attn.dropout
+ * of a meshed decoder layer, ONE module applied once per encoder level.  For decoder layer l, encoder level lvl and the decoder row
+ * that beam slot `slot` of image b holds at step t:
+ *     mrow = (b * k + slot) * T + t                  (T = max_len; step 0: slot 0, one row per image)
+ *     idx  = mrow * d + col
+ *     keep = Philox4x32-10(counter = (lo32(idx >> 2), hi32(idx >> 2), dec_site(l, 1), lvl), key = seed)[idx & 3] >= thr(p)
+ *     e_lvl = LN(x1 + (keep ? (attc_lvl Wo + bo) * s(p) : 0))
+ * -- ovc_forward_backward_level_dropout's counter, level as word 3, evaluated at the search's mask row: k = 1 gives b * T + t, that
+ * call's mask, and level 0 is the mask of ovc_beam_search_dropout bit for bit.  The shared output projection runs as without
+ * dropout (same class and K order, its bias, no residual) over the stacked levels * rows rows; the AddNorm behind it masks stacked row
+ * m as (level m / rows, mask row of decoder row m % rows) and adds the residual row m % rows.
+ * ovc_beam_search_level_dropout: the arguments, modes, slot table and graph behaviour of ovc_beam_search_dropout.
+ * ovc_sequence_backward_level_dropout: the arguments of ovc_sequence_backward_dropout; the recompute masks through the table built
+ * from `slots`, the backward regenerates the same masks for the projection's gradient and the residual's share stays unmasked
+ * (d(x1) += sum_lvl d(ymesh_lvl), levels ascending).  With every p == 0 the search is the plain search's launches (the slot table is
+ * still written) and the backward is ovc_sequence_backward_meshed launch for launch.
+ * Scope: ovc_forward_backward_meshed's, precision 0, T == max_len.  OVC_EINVAL, nothing launched: a null dropout table, seed or slot
+ * table, any p outside [0, 1) (NaN included), k outside 1..OVC_MAX_BEAM, S > k, T != max_len, any other model.
+ * The sizers answer 0 for what their calls refuse.
+ * ovc_dropout_mask_rows_level: ovc_dropout_mask_rows at encoder level `level` (0 <= level < OVC_MAX_LEVELS; level 0 is
+ * ovc_dropout_mask_rows, mask rows 0 .. rows - 1 give ovc_dropout_mask_level) -- openviic_amd/dropout.py keep_rows(level=). */
+size_t ovc_beam_search_level_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k);
+int ovc_beam_search_level_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                  void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
+                                  const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out, int* steps_run_out);
+size_t ovc_level_dropout_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T);
+int ovc_sequence_backward_level_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes, int B,
+                                        int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                        size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream, int k,
+                                        const int32_t* slots, const ovc_dropout* dropout);
+int ovc_dropout_mask_rows_level(const int64_t* seed, int site, int level, const int32_t* mask_rows, long rows, long cols, float p,
+                                uint8_t* keep, ovc_stream stream);
+/* Test hook (tests/test_meshed_scst_dropout_gpu.py): the level-keyed AddNorm of a meshed decode step alone, as the search launches it.
+ * v [levels * level_rows][d] the finished projections (bias applied), residual [level_rows][d], y [levels * level_rows][d]; site, p and
+ * (width, k, T, t) as in ovc_debug_add_norm.  y[m] = LN((keep ? v[m] * s : 0) + residual[m % level_rows]) * gamma + beta with keep the
+ * level m / level_rows decision at the mask row of decoder row m % level_rows.  gate: NULL = ungated.  OVC_EINVAL, nothing launched: a
+ * NULL or unaligned pointer, d % 4 != 0 or d > 2048, levels outside 1..OVC_MAX_LEVELS, p outside [0, 1), a site or row key out of
+ * range. */
+int ovc_debug_add_norm_level_dropout(const float* v, const float* residual, const float* gamma, const float* beta, float eps, float* y,
+                                     int levels, int level_rows, int d, const int64_t* seed, int site, float p, int width, int k, int T,
+                                     int t, const int32_t* gate, ovc_stream stream);
 
 /* Sampling: S captions per image drawn from the model's distribution, 1 <= S <= OVC_MAX_BEAM (appended to ABI 8; no struct
  * changes).  The search machinery with a draw in place of the selection of the k best; every model the search runs, precision 0,

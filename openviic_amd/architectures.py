@@ -112,11 +112,31 @@ def _level_dropout(what, dropout, arch, **others):
 
 
 def _refuse_level_dropout(what, dropout):
-    """``dropout`` given as a string where only ``xe_loss`` / ``xe_step`` take one: refused by name."""
-    if isinstance(dropout, str):
-        raise engine.native.OvcError("{}(dropout={!r}): dropout is False or True here -- dropout=\"{}\" is xe_loss's and xe_step's, "
-                                     "the sequence form and the search of the meshed-memory transformer have no dropout "
-                                     "form".format(what, dropout, train_arch.LEVEL_DROPOUT))
+    """``dropout`` given as a string to ``beam_search`` / ``scst_step``: every string but the search's own spelling
+    (``train_arch.BEAM_LEVEL_DROPOUT``) is refused by name -- ``xe_loss``'s ``"levels"`` among them."""
+    if isinstance(dropout, str) and dropout != train_arch.BEAM_LEVEL_DROPOUT:
+        raise engine.native.OvcError("{}(dropout={!r}): dropout is False, True or \"{}\" here -- dropout=\"{}\" is xe_loss's and "
+                                     "xe_step's; the search and the sequence form of the meshed-memory transformer take "
+                                     "meshed=True, dropout=\"{}\"".format(what, dropout, train_arch.BEAM_LEVEL_DROPOUT,
+                                                                         train_arch.LEVEL_DROPOUT, train_arch.BEAM_LEVEL_DROPOUT))
+
+
+def _beam_level_dropout(what, dropout, arch, **others):
+    """``dropout`` given as a string, for ``beam_search`` / ``scst_step`` (after ``_refuse_level_dropout``): True for
+    ``dropout="beam_levels"`` on the architecture that has that form (``train_arch.TrainArch.beam_level_search_form``), with none of
+    ``others`` (what that form does not combine with) set; the spelling without that architecture's keyword and the combinations
+    are refused by name.  False for anything that is no string: the plain dropout rules apply."""
+    if not isinstance(dropout, str):
+        return False
+    if arch is None or not arch.takes_beam_level_dropout(dropout):
+        raise engine.native.OvcError("{}(dropout={!r}): a mask per encoder level is the meshed-memory transformer's dropout -- it needs "
+                                     "meshed=True and no other architecture's keyword{}".format(
+                                         what, dropout, "" if arch is None else " ({}=True was given)".format(arch.key)))
+    for name, value in others.items():
+        if value:
+            raise engine.native.OvcError("{}({}=True, dropout={!r}, {}=...): {} is out of scope for {}'s search under "
+                                         "dropout".format(what, arch.key, dropout, name, name, arch.noun))
+    return True
 
 
 def _require_boxes(what, input_features):
@@ -497,7 +517,10 @@ class BaseTransformer(Module):
 
         ``meshed=True``: the meshed-memory transformer, as ``xe_loss`` takes it (``ovc_sequence_backward_meshed``); the first of
         the lines above is then ``model.beam_search(items, B, k, out_size=k, meshed=True)``.  Refused by name before any launch or
-        draw: any other model, and ``meshed=True`` together with ``dropout=True`` or ``sample=True``.
+        draw: any other model, and ``meshed=True`` together with ``dropout=True`` or ``sample=True``.  ``meshed=True,
+        dropout="beam_levels"``: that model's whole iteration under dropout, as ``beam_search`` takes the pair
+        (``ovc_beam_search_level_dropout``, ``ovc_sequence_backward_level_dropout``); ``"beam_levels"`` without ``meshed=True``,
+        with another architecture's keyword or with ``sample=True`` is refused by name.
 
         ``geometric=True``: the object-relation transformer, as ``xe_loss`` takes it (``ovc_sequence_backward_geometric``); the
         first of the lines above is then ``model.beam_search(items, B, k, out_size=k, geometric=True)``.  Refused by name before
@@ -510,8 +533,9 @@ class BaseTransformer(Module):
         ``sample=True``."""
         _refuse_level_dropout("scst_step", dropout)
         arch = _named_arch("scst_step", meshed, geometric, aoa)
+        level = _beam_level_dropout("scst_step", dropout, arch, sample=sample)
         if arch is not None:
-            arch.refuse_with("scst_step", dropout=dropout, sample=sample)
+            arch.refuse_with("scst_step", dropout=dropout and not level, sample=sample)
         if _requested_constraints(no_repeat_ngram_size, min_length, banned_words):
             raise engine.native.OvcError("scst_step(no_repeat_ngram_size / min_length / banned_words): a constrained search inside "
                                          "scst_step is out of scope -- call beam_search with them and backpropagate its log_probs")
@@ -537,7 +561,8 @@ class BaseTransformer(Module):
         k = int(beam_size)
         if not 1 <= k <= engine.native.OVC_MAX_BEAM:
             raise engine.native.OvcError("scst_step: 1 <= beam_size <= {} expected, got {}".format(engine.native.OVC_MAX_BEAM, k))
-        probs = self._search_dropout_probs() if dropout else self._xe_dropout_probs(False, "scst_step")
+        probs = (self._level_search_probs("scst_step", arch) if level else self._search_dropout_probs() if dropout
+                 else self._xe_dropout_probs(False, "scst_step"))
         eng = self._fused_engine()
         eng._check_trainable(arch)
         if arch is not None and arch.needs_boxes:
@@ -558,7 +583,7 @@ class BaseTransformer(Module):
                     B, eng.device, "{} {} on {}".format(rows.dtype, tuple(rows.shape), rows.device)
                     if isinstance(rows, torch.Tensor) else type(rows).__name__))
         outs, log_probs, _, recompute = self._generate(input_features, B, k, None if sample else k, probs, generator,
-                                                       early_exit=early_exit, checked=checked)
+                                                       early_exit=early_exit, checked=checked, level=level)
         if corpus is not None:
             r = corpus.reward(outs, rows)
         else:
@@ -598,6 +623,19 @@ class BaseTransformer(Module):
             raise engine.native.OvcError("beam_search(dropout=True) runs in 'f32' only (precision={!r}; live: {})".format(
                 eng.precision, live[0]))
         eng._check_trainable()
+        return probs
+
+    def _level_search_probs(self, what, arch):
+        """``{site: p}`` for ``beam_search`` / ``scst_step`` under ``meshed=True, dropout="beam_levels"`` (empty: the plain meshed
+        call), or the refusals of that form's scope: before any launch and any draw."""
+        if not self._live_dropouts():
+            return {}
+        probs = _dropout.model_probs(self)          # names a p >= 1 and a live dropout without a site
+        eng = self._fused_engine()
+        if eng.precision != "f32":
+            raise engine.native.OvcError("{}({}=True, dropout={!r}) runs in 'f32' only (precision={!r})".format(
+                what, arch.key, train_arch.BEAM_LEVEL_DROPOUT, eng.precision))
+        eng._check_trainable(arch)
         return probs
 
     def beam_search(self, input_features, batch_size: int, beam_size: int, out_size=1, return_probs=False,
@@ -649,6 +687,15 @@ class BaseTransformer(Module):
         name before any launch or draw: any other model, ``fused=False``, ``dropout=True``, and a ``train()``-mode model with a
         live dropout and gradients enabled.  Without the keyword a meshed model's ``log_probs`` raise from ``backward()`` as before.
 
+        ``meshed=True, dropout="beam_levels"`` (fused only, 'f32'): that model's search under dropout, as the reference's
+        ``train_scst`` runs it (``ovc_beam_search_level_dropout``).  Every ``nn.Dropout`` applies its own ``p`` at its site as for
+        ``dropout=True``; the meshed layer's ONE ``enc_attn.dropout``, applied once per encoder level, gets an independent mask
+        per level at the search's mask row (``openviic_amd.dropout``), and the backward of ``log_probs`` recomputes the beams under
+        the same masks through the slot table (``ovc_sequence_backward_level_dropout``).  Seed, ``generator``, ``eval()`` mode and
+        ``p == 0`` as for ``dropout=True``.  Refused by name before any launch and any draw: ``"beam_levels"`` without
+        ``meshed=True`` or with another architecture's keyword, together with ``return_probs``, constraints, a prefix or
+        ``fused=False``, a precision other than 'f32', a ``p >= 1`` or a live dropout without a site (naming the module).
+
         ``geometric=True`` (fused only): the object-relation transformer, likewise (``ovc_sequence_backward_geometric``), with the
         same refusals and ``meshed=True`` among them.
 
@@ -658,11 +705,16 @@ class BaseTransformer(Module):
         _constraints.refuse_out_of_scope(kwargs, "beam_search")
         _refuse_level_dropout("beam_search", dropout)
         arch = _named_arch("beam_search", meshed, geometric, aoa)
+        level = _beam_level_dropout("beam_search", dropout, arch, return_probs=return_probs, prefix=prefix is not None,
+                                    constraints=_requested_constraints(no_repeat_ngram_size, min_length, banned_words))
+        level_probs = None
         if arch is not None:
-            arch.refuse_with("beam_search", dropout=dropout)
+            arch.refuse_with("beam_search", dropout=dropout and not level)
             if not fused:
                 raise engine.native.OvcError("beam_search({}=True) needs fused=True: the host loop has no backward".format(arch.key))
-            if self.training and torch.is_grad_enabled():
+            if level:
+                level_probs = self._level_search_probs("beam_search", arch)
+            elif self.training and torch.is_grad_enabled():
                 self._xe_dropout_probs(False, "beam_search({}=True)".format(arch.key))
             self._fused_engine()._check_trainable(arch)
             if arch.needs_boxes:
@@ -695,12 +747,12 @@ class BaseTransformer(Module):
         if fused:
             if constraints:      # every refusal of the options, before any launch and any draw
                 constraints = self._fused_engine().check_constraints(beam_size, constraints, kwargs.get("early_exit"))
-            probs = self._search_dropout_probs() if dropout else None
+            probs = level_probs if level else self._search_dropout_probs() if dropout else None
             if probs and return_probs:
                 raise engine.native.OvcError("beam_search(dropout=True) has no return_probs form")
             ids, logp, everything, recompute = self._generate(input_features, batch_size, beam_size, out_size, probs, generator,
                                                               return_probs, kwargs.get("early_exit"), constraints=constraints,
-                                                              prefix=prefix)
+                                                              prefix=prefix, level=level)
             if arch is not None:
                 recompute = dict(recompute, **arch.keywords())
             logp = self._scst_log_probs(input_features, ids, logp, recompute)
@@ -865,7 +917,7 @@ class BaseTransformer(Module):
         return (ids, logp, everything) if return_probs else (ids, logp)
 
     def _generate(self, input_features, batch_size, width, out_size=None, probs=None, generator=None, return_probs=False,
-                  early_exit=None, checked=None, constraints=None, prefix=None):
+                  early_exit=None, checked=None, constraints=None, prefix=None, level=False):
         """One fused generation, for ``beam_search``, ``sample`` and ``scst_step``: ``width`` beams of which the best ``out_size``
         are returned -- with ``probs`` (what ``_search_dropout_probs`` returned, not empty) under this call's dropout masks -- or,
         with ``out_size=None``, ``width`` samples under the sampler's options (``checked``: what ``check_sample`` returned).  The masks' or the samples' seed is drawn here, one per call; plain beams draw
@@ -873,7 +925,8 @@ class BaseTransformer(Module):
         None without ``return_probs``, the last the keyword arguments under which ``sequence_backward`` recomputes these
         log-probabilities (empty, or the masked search's ``dropout``, ``slots`` and ``beam_size``).  ``constraints``: the beam
         search's ``(n, L, banned)`` as ``check_constraints`` returned them, or None.  ``prefix``: the beam search's table as
-        ``check_prefix`` returned it, or None."""
+        ``check_prefix`` returned it, or None.  ``level``: ``probs`` are ``_level_search_probs``' -- the search and the recompute
+        take the level-keyed form (``level_dropout=True``)."""
         eng = self._fused_engine()
         feats, boxes = self._engine_inputs(input_features)
         recompute = {}
@@ -883,8 +936,9 @@ class BaseTransformer(Module):
                              checked=checked)
         elif probs:
             drop = (probs, _dropout.draw_seed(eng.device, generator))
-            *out, slots = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, early_exit=early_exit, dropout=drop)
-            recompute = dict(dropout=drop, slots=slots, beam_size=width)
+            form = {"level_dropout": True} if level else {}
+            *out, slots = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, early_exit=early_exit, dropout=drop, **form)
+            recompute = dict(dropout=drop, slots=slots, beam_size=width, **form)
         else:
             out = eng.beam_search(feats, boxes, batch_size, width, out_size=out_size, return_probs=return_probs, early_exit=early_exit,
                                   constraints=constraints, prefix=prefix)

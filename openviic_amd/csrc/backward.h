@@ -34,6 +34,11 @@ int ovc_bw_layer_norm_dropout_mapped(const float* x, const float* gamma, const f
 int ovc_bw_layer_norm_dropout_level(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps, int rows,
                                     int d, float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop, int level_rows,
                                     hipStream_t s);
+// the level-keyed form under a row table (ovc_sequence_backward_level_dropout): row r is masked as mask row rowmap[r % level_rows] at
+// level r / level_rows
+int ovc_bw_layer_norm_dropout_level_mapped(const float* x, const float* gamma, const float* dy, const uint8_t* zero_rows, float eps,
+                                           int rows, int d, float* dx, float* prod, float* dyc, float* dproj, const DropoutSite& drop,
+                                           int level_rows, const int32_t* rowmap, hipStream_t s);
 // The FFN's inner site: act is the stored DROPPED ReLU output, nonzero iff kept and positive, so g[i] = act[i] > 0 ? g[i] * s : 0
 // needs no mask.
 int ovc_bw_relu_dropout(float* g, const float* act, float scale, long n, hipStream_t s);

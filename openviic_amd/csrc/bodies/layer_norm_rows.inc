@@ -29,10 +29,17 @@
 #pragma unroll
         for (int i = 0; i < kVecs; ++i) bv[i] = reinterpret_cast<const f32x4*>(bias)[col[i]];
     }
+#ifdef OVC_LN_RES_ROW                   // the level-keyed instance (level_dropout.hip): one residual row under every level's block
+    if (kRes) {
+#pragma unroll
+        for (int i = 0; i < kVecs; ++i) rv[i] = reinterpret_cast<const f32x4*>(residual + (size_t)(OVC_LN_RES_ROW) * d)[col[i]];
+    }
+#else
     if (kRes) {
 #pragma unroll
         for (int i = 0; i < kVecs; ++i) rv[i] = reinterpret_cast<const f32x4*>(residual + (size_t)row * d)[col[i]];
     }
+#endif
     // gamma / beta do not depend on the row's moments: fetched now, not after them (one memory round trip less
     // on a kernel that is nothing but a chain of them)
     f32x4 gv[kVecs], bev[kVecs];

@@ -65,6 +65,14 @@ __device__ __forceinline__ uint32_t ovc_dropout_keep4(uint64_t key, uint32_t sit
     return (c0 >= thr ? 1u : 0u) | (c1 >= thr ? 2u : 0u) | (c2 >= thr ? 4u : 0u) | (c3 >= thr ? 8u : 0u);
 }
 
+// The same block at encoder level `level` (counter word 3): bit j is ovc_dropout_keep_level(seed, site, level, 4 g + j, thr), and level
+// 0 is ovc_dropout_keep4.  A function of its own, so that ovc_dropout_keep4's callers keep their code.
+__device__ __forceinline__ uint32_t ovc_dropout_keep4_level(uint64_t key, uint32_t site, uint32_t level, uint64_t g, uint32_t thr) {
+    uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = site, c3 = level;
+    ovc_philox_block(key, c0, c1, c2, c3);
+    return (c0 >= thr ? 1u : 0u) | (c1 >= thr ? 2u : 0u) | (c2 >= thr ? 4u : 0u) | (c3 >= thr ? 8u : 0u);
+}
+
 // Dropout inside the beam search (ovc_beam_search_dropout): row r of decode step t is beam slot r % width of image r / width
 // (width = 1 at step 0, the beam size k later), and its decoder-side masks are keyed by the MASK ROW
 //   mrow(b, slot, t) = (b * k + slot) * T + t                                        (T = max_len; k = 1: xe_loss's b * T + t)
@@ -94,3 +102,15 @@ int ovc_layer_norm_parts_dropout(const float* parts, int nparts, long part_strid
 // row r is rowmap[r] when rowmap != nullptr (the teacher-forced recompute), else ovc_decode_mask_row(key, r) (the search).
 int ovc_dropout_rows(float* x, const float* residual, int rows, int cols, const DropoutSite& drop, const DecodeRowKey& key,
                      const int32_t* rowmap, hipStream_t stream, const int32_t* gate);
+
+// ---- level-keyed row launches (level_dropout.hip): the meshed decoder's enc_attn.dropout in the search and the sequence form -------
+// The rows are stacked blocks of level_rows rows, one block per encoder level: stacked row m is decoder row r = m % level_rows at level
+// m / level_rows, its residual row is r, and its mask is the level-keyed one (counter word 3) at the MASK ROW of r.
+// LayerNorm((keep ? v * s : 0) + residual[r]) with v the finished projection (bias applied): the AddNorm of a decode step, mask row
+// ovc_decode_mask_row(key, r).  gate: nullptr = ungated.
+int ovc_layer_norm_level_dropout(const float* v, const float* residual, const float* gamma, const float* beta, float eps, float* y, int rows,
+                                 int level_rows, int d, const DropoutSite& drop, const DecodeRowKey& key, hipStream_t stream,
+                                 const int32_t* gate);
+// x[m, :] = (keep ? x[m, :] * s : 0) + residual[r, :] in place, mask row rowmap[r]: the teacher-forced recompute.
+int ovc_dropout_rows_level(float* x, const float* residual, int rows, int level_rows, int cols, const DropoutSite& drop,
+                           const int32_t* rowmap, hipStream_t stream);

@@ -1040,7 +1040,8 @@ struct SearchCall {
     // Dropout (ovc_beam_search_dropout): the plan -- bound even when no site is active, the slot table is still written -- with
     // the caller's seed, the hash of the plan's constants and the caller's slot table [B][out_size][T].  A sizer binds an empty
     // plan (and any non-null all_logp_out): their presence alone adds the buffers.
-    DropPlan* plan; const int64_t* seed; uint64_t drop_hash; int32_t* slots_out;
+    // level_plan (ovc_beam_search_level_dropout): the plan is bound under TrainArch::Meshed -- enc_attn.dropout masked per level.
+    DropPlan* plan; const int64_t* seed; uint64_t drop_hash; int32_t* slots_out; bool level_plan;
     // Sampling (ovc_sample, ovc_sample_graph): the selection of every step is a draw from the row's distribution (k = out_size =
     // the samples per image) and the caller's seed, copied to the workspace's seed slot outside any captured body.
     bool sample; const int64_t* sample_seed;
@@ -1140,7 +1141,7 @@ bool search_ok(const ovc_model* m, const SearchCall& c) {
     }
     if (c.ens_M != 0 && !ensemble_ok(m, c)) return false;
     return c.out_size > 0 && c.out_size <= c.k &&
-           (!c.plan || train_scope_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}, TrainArch::Standard, true));
+           (!c.plan || train_scope_ok(m, ForwardCall{c.B, c.N, 1, m->max_len}, c.level_plan ? TrainArch::Meshed : TrainArch::Standard, true));
 }
 
 // A rule's buffers and copies, described here and nowhere else: its tail of w behind everything else (ovc_beam_search's layout is
@@ -1309,13 +1310,32 @@ int run_decoder_layer(Engine& e, Workspace& w, int l, const DecoderPass& p, cons
             o.A1 = b.attc; o.lda1 = hv; o.K1 = hv; o.M = lv * rows; o.seg_n = d; o.nseg = 1; o.ldc = d;
             o.R = b.x1; o.ldr = d; o.res_mod = rows;
             o.seg[0] = e.seg(dl.cross_att.o, b.ymesh);
-            // enc_attn.dropout, ONE module applied once per level: the level-keyed instance masks product row m as (level m / rows,
-            // decoder row m % rows), so ymesh holds the dropped sums (site not active: the plain launch)
-            GemmLaunchOpts level_drop = e.drop_opts(p.site(l, 1), d);
-            if (level_drop.drop_seed) level_drop.drop_level_rows = rows;
-            TRY(e.gemm(o, level_drop));
-            RUN(ovc_layer_norm_gated(b.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
-                                     b.enc_att, lv * rows, d, s, e.gate));
+            if (e.row_keyed(p.site(l, 1))) {
+                // the search and the sequence form under dropout (ovc_beam_search_level_dropout, ovc_sequence_backward_level_dropout):
+                // the mask row of decoder row r is the search's, not r.  The product keeps its class and K order, with its bias and
+                // without the residual; the mask at (level m / rows, mask row of m % rows) and the residual x1[m % rows] follow it
+                const DropoutSite site = e.drop_site(p.site(l, 1), d);
+                o.R = nullptr; o.res_mod = 0;
+                TRY(e.gemm(o));
+                if (e.maskrow) {
+                    // the recompute: the mask through the row table and the residual, then the plain norm
+                    TRY(ovc_dropout_rows_level(b.ymesh, b.x1, lv * rows, rows, d, site, e.maskrow, s));
+                    RUN(ovc_layer_norm_gated(b.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                             b.enc_att, lv * rows, d, s, e.gate));
+                } else {
+                    // a decode step: the level-keyed AddNorm instance masks the finished projection before it adds the residual
+                    TRY(ovc_layer_norm_level_dropout(b.ymesh, b.x1, dl.cross_att.ln.g, dl.cross_att.ln.b, m->ln_eps, b.enc_att, lv * rows,
+                                                     rows, d, site, e.decode_key, s, e.gate));
+                }
+            } else {
+                // enc_attn.dropout, ONE module applied once per level: the level-keyed instance masks product row m as (level m /
+                // rows, decoder row m % rows), so ymesh holds the dropped sums (site not active: the plain launch)
+                GemmLaunchOpts level_drop = e.drop_opts(p.site(l, 1), d);
+                if (level_drop.drop_seed) level_drop.drop_level_rows = rows;
+                TRY(e.gemm(o, level_drop));
+                RUN(ovc_layer_norm_gated(b.ymesh, nullptr, dl.cross_att.ln.g, dl.cross_att.ln.b, nullptr, 0, nullptr, m->ln_eps,
+                                         b.enc_att, lv * rows, d, s, e.gate));
+            }
         } else {
             for (int lvl = 0; lvl < lv; ++lvl) {      // AoA gates need the per-level pair (x1, enc_att_l)
                 TRY(e.linear(b.attc + (size_t)lvl * rows * hv, hv, dl.cross_att.o, b.x1, b.yc, rows, d, 0));
@@ -1687,10 +1707,11 @@ SearchCall sized_call(int B, int N, int k, bool return_probs) {
 }
 size_t sized_bytes(const ovc_model* m, const SearchCall& c) { return search_ok(m, c) ? carve_search(m, nullptr, c).bytes : 0; }
 
-size_t search_workspace_bytes(const ovc_model* m, int B, int N, int k, bool return_probs, bool dropout) {
+size_t search_workspace_bytes(const ovc_model* m, int B, int N, int k, bool return_probs, bool dropout, bool level_plan = false) {
     SearchCall c = sized_call(B, N, k, return_probs);
     DropPlan sized{};
     if (dropout) c.plan = &sized;
+    c.level_plan = level_plan;
     return sized_bytes(m, c);
 }
 
@@ -2970,7 +2991,7 @@ enum class LossHead {
     SoftTargets,    // ovc_bw_xent_soft: the NLL mixed with the KL divergence from a teacher's distribution, TrainCall::soft / teacher
 };
 
-// One training call, described once.  The twenty-six exported functions (thirteen entry points, thirteen sizers) fill one of these, and the
+// One training call, described once.  The twenty-eight exported functions (fourteen entry points, fourteen sizers) fill one of these, and the
 // scope (call_ok), the workspace layout and size (carve_train), the captured body (issue_train_body), the graph key
 // (train_graph_key) and the launches around the body (run_train_call) are functions of it: a sizer and the entry point that carves
 // its buffer cannot disagree.
@@ -3127,7 +3148,8 @@ bool mha_plain_or_gated(const ovc_mha& a) { return mha_plain(a) || mha_gated(a);
 //   Meshed     the multilevel encoder, every layer's self-attention with memory slots (or every layer plain), in front of the
 //              meshed decoder with plain attentions and a gate per level.  The loss form takes a dropout plan
 //              (ovc_forward_backward_level_dropout): enc_attn.dropout, one module applied once per level, is masked per (level, row)
-//              at dec_site(l, 1); every other site is the plain one.  The sequence form takes none.
+//              at dec_site(l, 1); every other site is the plain one.  The sequence form and the search take it as well
+//              (ovc_sequence_backward_level_dropout, ovc_beam_search_level_dropout): the level's mask at the search's mask row.
 //   Geometric  the geometric (object-relation) encoder -- plain layers whose scores take the box-relation bias
 //              log(max(relu(fc_g(emb(boxes))), 1e-6)) -- in front of the plain decoder.  The bias's backward
 //              (ovc_bw_box_relation) covers h <= 16, d_g == 4 without and a multiple of 8 up to 64 with the trigonometric
@@ -3156,10 +3178,10 @@ bool train_kinds_ok(const ovc_model* m, TrainArch arch) {
     return false;
 }
 
-// a dropout plan: where the architecture has a dropout form at all.  Meshed: the loss form alone, whose one entry point
-// (ovc_forward_backward_level_dropout) binds the plan; the sequence form has none
-bool train_plan_ok(const ovc_model* m, const ForwardCall& c, TrainArch arch) {
-    if (arch == TrainArch::Meshed) return !c.row_weights;
+// a dropout plan: where the architecture has a dropout form at all.  Meshed: the plan is bound by its level-keyed entry points alone
+// (ovc_forward_backward_level_dropout, ovc_sequence_backward_level_dropout, ovc_beam_search_level_dropout); every other sizer and
+// entry point that binds a plan names another architecture, and train_kinds_ok refuses the model there
+bool train_plan_ok(const ovc_model* m, const ForwardCall&, TrainArch arch) {
     return arch != TrainArch::Standard || m->enc_kind == OVC_ENC_PLAIN;
 }
 
@@ -3285,7 +3307,10 @@ int bw_norm(Engine& e, TrainWs& t, const float* y, const ovc_norm& n, const ovc_
             int rows, int site = -1, int level_rows = 0) {
     hipStream_t s = e.stream;
     const int d = e.m->d_model;
-    if (level_rows > 0 && e.site_on(site))
+    if (level_rows > 0 && e.row_keyed(site))        // the sequence form: the level's mask at the search's row (the table)
+        RUN(ovc_bw_layer_norm_dropout_level_mapped(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj,
+                                                   e.drop_site(site, d), level_rows, e.maskrow, s));
+    else if (level_rows > 0 && e.site_on(site))
         RUN(ovc_bw_layer_norm_dropout_level(y, n.g, dout, zero_rows, e.m->ln_eps, rows, d, t.dy, t.prod, t.dyc, t.dproj, e.drop_site(site, d),
                                             level_rows, s));
     else if (e.row_keyed(site))
@@ -4111,14 +4136,15 @@ extern "C" size_t ovc_beam_search_dropout_workspace_bytes(const ovc_model* m, in
     return search_workspace_bytes(m, B, N, k, false, true);
 }
 
-extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
-                                       void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
-                                       const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out,
-                                       int* steps_run_out) {
+namespace {
+// The search under a dropout plan, for the architecture whose scope the plan is bound under: Standard (ovc_beam_search_dropout) or
+// Meshed (ovc_beam_search_level_dropout, SearchCall::level_plan).  Everything else is one path.
+int run_search_dropout(const ovc_model* m, TrainArch arch, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                       void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
+                       const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out, int* steps_run_out) {
     constexpr SearchForm kModes[3] = {SearchForm::Graph, SearchForm::HostEarly, SearchForm::Gated};
     if (!dropout || !dropout->seed || !slots_out || !m || mode < 0 || mode > 2) return OVC_EINVAL;
-    if (!model_ok(m) || !train_scope_ok(m, ForwardCall{B, N, 1, m->max_len}, TrainArch::Standard, true) ||
-        (long)B * k * m->max_len > (1L << 30))
+    if (!model_ok(m) || !train_scope_ok(m, ForwardCall{B, N, 1, m->max_len}, arch, true) || (long)B * k * m->max_len > (1L << 30))
         return OVC_EINVAL;
     DropPlan plan{};
     bool any = false;
@@ -4127,8 +4153,53 @@ extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features
     // with every p == 0 the plan stays bound (the slot table is still written) but no site is on: the plain launches, the plain
     // bits, and a graph entry of its own
     if (!any) c.drop_hash = 0x5D0Full;
-    c.plan = &plan; c.seed = dropout->seed; c.slots_out = slots_out;
+    c.plan = &plan; c.seed = dropout->seed; c.slots_out = slots_out; c.level_plan = arch == TrainArch::Meshed;
     if (c.form == SearchForm::Gated) c.steps_out = steps_out;
     if (c.form == SearchForm::HostEarly) c.steps_run_out = steps_run_out;
     return run_search(m, c, features, boxes, workspace, workspace_bytes, stream);
+}
+}  // namespace
+
+extern "C" int ovc_beam_search_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k, int out_size,
+                                       void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out, ovc_stream stream,
+                                       const ovc_dropout* dropout, int32_t* slots_out, int mode, int32_t* steps_out,
+                                       int* steps_run_out) {
+    return run_search_dropout(m, TrainArch::Standard, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out,
+                              stream, dropout, slots_out, mode, steps_out, steps_run_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// SCST of the meshed-memory transformer under dropout: the two calls above with the plan bound under
+// TrainArch::Meshed.  enc_attn.dropout of a meshed layer is masked per encoder level at the search's mask row (csrc/level_dropout.hip);
+// every other site keeps section 2i's rule.  With every p == 0 the search is the plain search's launches (the slot table is still
+// written) and the backward is ovc_sequence_backward_meshed launch for launch.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ovc_beam_search_level_dropout_workspace_bytes(const ovc_model* m, int B, int N, int k) {
+    return search_workspace_bytes(m, B, N, k, false, true, true);
+}
+
+extern "C" int ovc_beam_search_level_dropout(const ovc_model* m, const float* features, const float* boxes, int B, int N, int k,
+                                             int out_size, void* workspace, size_t workspace_bytes, int64_t* ids_out, float* logp_out,
+                                             ovc_stream stream, const ovc_dropout* dropout, int32_t* slots_out, int mode,
+                                             int32_t* steps_out, int* steps_run_out) {
+    return run_search_dropout(m, TrainArch::Meshed, features, boxes, B, N, k, out_size, workspace, workspace_bytes, ids_out, logp_out,
+                              stream, dropout, slots_out, mode, steps_out, steps_run_out);
+}
+
+extern "C" size_t ovc_level_dropout_beams_workspace_bytes(const ovc_model* m, int B, int N, int S, int T) {
+    // the recompute runs under a search's masks: full-length sequences only (search_ok of the call)
+    if (!m || T != m->max_len) return 0;
+    return train_workspace_bytes(m, TrainCall{B, N, S, T, LossHead::RowWeights, TrainArch::Meshed}, true);
+}
+
+extern "C" int ovc_sequence_backward_level_dropout(const ovc_model* m, const ovc_model* grads, const float* features, const float* boxes,
+                                                   int B, int N, int S, const int64_t* ids, const float* grad_logp, int T, void* workspace,
+                                                   size_t workspace_bytes, float* logp_out, int use_graph, ovc_stream stream, int k,
+                                                   const int32_t* slots, const ovc_dropout* dropout) {
+    TrainCall c{B, N, S, T, LossHead::RowWeights, TrainArch::Meshed};
+    c.k = k; c.slots = slots;
+    DropPlan plan{};
+    TRY(bind_dropout(m, dropout, &plan, c));
+    return run_train_call(m, grads, c, features, boxes, ids, nullptr, grad_logp, workspace, workspace_bytes, nullptr, logp_out, use_graph,
+                          stream);
 }

@@ -14,6 +14,19 @@ it.  ``keep_mask`` computes the same bits in numpy (``ovc_dropout_mask`` writes 
 ``level`` is 0 everywhere but at the meshed decoder's ``enc_attn.dropout``: that layer applies its one module once per encoder
 level, each time with an independent mask, and ``xe_loss(meshed=True, dropout="levels")`` keys application ``lvl`` of
 ``dec_site(l, 1)`` with ``level = lvl`` over the same rows ``b * T + t`` (``ovc_dropout_mask_level``).  Level 0 is the plain mask.
+
+The search and the sequence form of that model (``beam_search`` / ``scst_step`` with ``meshed=True, dropout="beam_levels"``;
+``include/ovc.h``, ``ovc_beam_search_level_dropout``) evaluate the same counter at the search's mask row: for decoder layer ``l``,
+encoder level ``lvl`` and the decoder row that beam slot ``slot`` of image ``b`` holds at step ``t``::
+
+    mrow = (b * k + slot) * T + t                    (mask_row; T = max_len; step 0: slot 0, one row per image)
+    idx  = mrow * d + col
+    keep = philox4x32_10(counter=(lo32(idx >> 2), hi32(idx >> 2), dec_site(l, 1), lvl), key=seed)[idx & 3] >= threshold(p)
+    e_lvl = LN(x1 + (keep ? (attc_lvl Wo + bo) * scale(p) : 0))
+
+-- ``keep_rows(seed, dec_site(l, 1), mrows, d, p, level=lvl)`` (``ovc_dropout_mask_rows_level``).  ``k = 1`` gives ``b * T + t``,
+the loss form's mask, and level 0 is ``beam_search(dropout=True)``'s mask bit for bit.  Every other site keeps the row-keyed rule;
+encoder sites key on ``b * N + n`` in every form.
 """
 import re
 

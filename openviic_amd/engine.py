@@ -62,6 +62,7 @@ def _rows(what, rows):
 # an empty slot); its key and length.
 _RULES = {
     "masked": lambda table: _Rule("masked", args={"table": ctypes.byref(table)}, extras=(("slots", torch.int32, True),)),
+    "masked_levels": lambda table: _Rule("masked_levels", args={"table": ctypes.byref(table)}, extras=(("slots", torch.int32, True),)),
     "shaped": lambda options: _Rule("shaped", options, dict(zip(("temperature", "top_k", "top_p"), options))),
     "constrained": lambda o: _Rule("constrained", args=dict(ngram=o[0], min_length=o[1], n_banned=len(o[2]),
                                                             banned=(ctypes.c_int32 * max(1, len(o[2])))(*o[2]))),
@@ -76,6 +77,18 @@ _RULES = {
         lambda B, T: (len(t[0]) != T or len(t[1]) != T or t[0].dtype != "float32" or t[1].dtype != "float32")
         and "the length tables must hold max_len = {} float32 entries each".format(T)),
 }
+
+
+# the masked searches: ``ovc_beam_search_dropout`` and, for the architecture with a level-keyed form
+# (``train_arch.TrainArch.beam_level_search_form``), that form's -- same arguments, modes and results
+_MASKED = ("masked", "masked_levels")
+_MASKED_ARGS = ("out_size", "ws", "need", "ids", "logp", "stream", "table", "slots", "mode", "steps", "steps_run")
+
+
+def _level_search_form():
+    sizer, entry = next(a.beam_level_search_form for a in train_arch.TRAIN_ARCHS.values() if a.beam_level_search_form)
+    return (sizer, "configuration for a search with dropout per encoder level", "beam",
+            dict.fromkeys(("graph", "early", "device"), (entry, _MASKED_ARGS)))
 
 
 def _p(t):
@@ -536,7 +549,7 @@ class CaptionEngine:
         ``options``: the shaped sampler's ``(temperature, top_k, top_p)``, or the prefix search's ``(P,)``."""
         sizer, what, width_name, _ = self._SEARCH_FORMS[kind]
         need = getattr(self.lib, sizer)(ctypes.byref(self.desc), B, N, width,
-                                        *(() if kind == "masked" else (1 if return_probs else 0,)), *options)
+                                        *(() if kind in _MASKED else (1 if return_probs else 0,)), *options)
         if need == 0:
             raise native.OvcError("unsupported {} (B={}, N={}, {}={}; see {})".format(what, B, N, width_name, width, sizer))
         return self._workspace("search", need), need
@@ -701,6 +714,7 @@ class CaptionEngine:
         "masked": ("ovc_beam_search_dropout_workspace_bytes", "configuration for a search with dropout", "beam", dict.fromkeys(
             ("graph", "early", "device"),
             ("ovc_beam_search_dropout", ("out_size", *_RESULTS, "stream", "table", "slots", "mode", "steps", "steps_run")))),
+        "masked_levels": _level_search_form(),
         "sample": ("ovc_sample_workspace_bytes", "configuration for sampling", "n_samples", {
             "plain": ("ovc_sample", ("seed", *_RESULTS, "everything", "stream")),
             "graph": ("ovc_sample_graph", ("seed", *_RESULTS, "stream"))}),
@@ -717,6 +731,8 @@ class CaptionEngine:
         ``return_probs``, else None; ``extras``: the tensors ``rule.extras`` declares, in that order."""
         rule = rule or _Rule("beam" if seed is None else "sample")
         kind = rule.kind
+        if kind == "masked_levels":
+            self._check_trainable(next(a for a in train_arch.TRAIN_ARCHS.values() if a.beam_level_search_form))
         if kind == "masked":
             self._check_trainable()
             if self.desc.enc_kind != native.ENC_PLAIN:
@@ -730,7 +746,7 @@ class CaptionEngine:
         # with return_probs every early_exit value runs the full plain form; without use_graph (OVC_GRAPH=0) the whole-search
         # graph's form is the plain one as well, for beams and samples (the masked search has no plain form)
         form = "plain" if return_probs else ("device" if early == "device" else ("early" if early else "graph"))
-        if form == "graph" and not self.use_graph and kind != "masked":
+        if form == "graph" and not self.use_graph and kind not in _MASKED:
             form = "plain"
         ws, need = self._search_workspace(kind, B, N, width, return_probs, rule.sizer)
         ids = torch.empty(B, out_size, T, dtype=torch.int64, device=self.device)
@@ -741,13 +757,13 @@ class CaptionEngine:
         steps = self._steps_tensor() if form == "device" else None
         issued = ctypes.c_int(T)
         # OVC_GRAPH=0: every call is the first of its shape (plain launches; the host-early search without dropout keeps its graphs)
-        if not self.use_graph and (form == "device" or kind == "masked"):
+        if not self.use_graph and (form == "device" or kind in _MASKED):
             self.lib.ovc_graph_cache_drop_workspace(ws.data_ptr())
         args = {name: None if t is None else t.data_ptr() for name, t in (
             ("ws", ws), ("ids", ids), ("logp", logp), ("everything", everything), ("steps", steps), ("seed", seed),
             *zip((name for name, _, _ in rule.extras), extras))}
         args.update(rule.args, out_size=out_size, need=need, stream=native.stream_handle(), steps_run=ctypes.byref(issued))
-        if kind == "masked":
+        if kind in _MASKED:
             args["mode"] = ("graph", "early", "device").index(form)
         if rule.check and rule.check(B, T):
             raise native.OvcError(rule.check(B, T))
@@ -822,7 +838,7 @@ class CaptionEngine:
         return table
 
     def beam_search(self, features, boxes, batch_size, beam_size, out_size=1, return_probs=False, early_exit=None, dropout=None,
-                    constraints=None, prefix=None):
+                    constraints=None, prefix=None, level_dropout=False):
         """``prefix`` (``ovc_beam_search_prefix``; DESIGN.md section 2w, ``openviic_amd.prefix`` mirrors the rule): an int64
         tensor ``(B, P)``, ``<pad>`` trailing -- image ``b`` emits its row's words first and the search continues behind them;
         None, ``P == 0`` or all ``<pad>`` are the plain call.  Refused by name before any launch: a bad table, or a prefix together
@@ -833,6 +849,10 @@ class CaptionEngine:
         ``dropout``, an early-exit form, a split precision or a vocabulary of more than 16 384 words.
         ``dropout=(probs, seed)`` (as ``forward_backward``): the search runs with every site's mask applied and returns
         ``(ids, logp, slots)``, unsqueezed ``(B, out_size, T)``; with no ``p > 0`` it is the plain call and ``slots`` is None.
+        ``level_dropout=True`` next to ``dropout=(probs, seed)``: the meshed-memory transformer's search under dropout
+        (``ovc_beam_search_level_dropout``) -- ``dec_site(l, 1)``, the layer's one ``enc_attn.dropout`` applied once per encoder
+        level, is masked per level at the search's mask row (``openviic_amd.dropout``); same results.  Without ``dropout`` it is
+        refused by name.
         ``early_exit`` (default: the class attribute / OVC_EARLY_EXIT): see above and ``early_exit_mode``.  ``True``:
         ``self.last_steps_run`` then holds the number of decode steps that were issued for the call.  ``"device"``:
         ``self.last_steps_device`` is a one-element int32 device tensor (one per workspace, i.e. per stream) that receives, in
@@ -842,12 +862,14 @@ class CaptionEngine:
         prefix = self.check_prefix(batch_size, beam_size, prefix, early_exit, dropout, constraints)
         early = early_exit_mode(self.early_exit if early_exit is None else early_exit)
         table_drop = None
+        if level_dropout and dropout is None:
+            raise native.OvcError("beam_search(level_dropout=True): a mask per encoder level needs dropout=(probs, seed)")
         if dropout is not None:
             if return_probs:
                 raise native.OvcError("beam_search(dropout=...) has no return_probs form")
             table_drop = self._dropout_table(dropout)
         # one rule per search: check_constraints / check_prefix have refused the combinations
-        rule = (_RULES["masked"](table_drop) if table_drop is not None else _RULES["constrained"](constraints) if constraints
+        rule = (_RULES["masked_levels" if level_dropout else "masked"](table_drop) if table_drop is not None else _RULES["constrained"](constraints) if constraints
                 else _RULES["prefix"](prefix) if prefix else None)
         ids, logp, everything, extras = self._run_search(features, boxes, batch_size, beam_size, out_size, return_probs, early, rule=rule)
         if dropout is not None:
@@ -1204,7 +1226,8 @@ class CaptionEngine:
         workspace is the stream's, per S for sequences (``_sized_workspace``).  ``distill``: a checked ``distill.SoftTargets`` -- the
         soft-target form, its ``ovc_distill`` and the dropout table (or NULL) behind the plain arguments.  ``arch``: a
         ``train_arch.TrainArch`` -- that architecture's form (what it does not combine with, the callers have refused); with
-        ``level`` and a dropout table its ``level_dropout_form``, the table behind the plain arguments."""
+        ``level`` and a dropout table its ``level_dropout_form`` (with ``sequence`` its ``beam_level_sequence_form``), the table
+        behind the plain arguments."""
         drop = () if table_drop is None else (ctypes.byref(table_drop),)
         flagged = (1 if drop else 0,), (drop[0] if drop else None,)      # a sizer's dropout flag, the table or NULL behind the arguments
         size_tail, tail = (), (*search, *drop)
@@ -1212,8 +1235,8 @@ class CaptionEngine:
             sizer, entry = arch.sequence_form if sequence else arch.loss_form
             if arch.loss_dropout and not sequence:
                 size_tail, tail = flagged
-            elif level and drop and not sequence:
-                sizer, entry = arch.level_dropout_form
+            elif level and drop:
+                sizer, entry = arch.beam_level_sequence_form if sequence else arch.level_dropout_form
         elif distill is not None:
             sizer, entry = self._DISTILL_FORM
             size_tail, tail = flagged[0], (ctypes.byref(native.Distill(distill.teacher.data_ptr(), distill.weight)), *flagged[1])
@@ -1270,7 +1293,7 @@ class CaptionEngine:
         return self._buffers[key]
 
     def sequence_backward(self, features, boxes, ids, grad_logp, use_graph=None, want_logp=False, dropout=None, slots=None,
-                          beam_size=None, arena=None, meshed=False, geometric=False, aoa=False):
+                          beam_size=None, arena=None, meshed=False, geometric=False, aoa=False, level_dropout=False):
         """Gradients of ``sum g[b,s,t] * logp[b,s,t]`` over the positions up to each sequence's first ``<eos>``
         (``ovc_sequence_backward``): ``ids`` ``(B, S, T)`` int64 are S generated sequences per image (a beam search's outputs),
         ``grad_logp`` ``(B, S, T)`` the gradient ``g`` of a loss with respect to the search's log-probabilities, which are the
@@ -1286,12 +1309,20 @@ class CaptionEngine:
         ``arena``: a ``step_arena()`` to write the gradients into instead of a fresh buffer, as ``forward_backward`` takes it
         (``BaseTransformer.scst_step``); the returned ``arena`` and ``grads`` are then that arena's.
 
-        ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``.
+        ``meshed=True``: the meshed-memory transformer (``ovc_sequence_backward_meshed``); refused together with ``dropout``
+        unless ``level_dropout=True``: then ``dropout``, ``slots`` and ``beam_size`` are those of
+        ``beam_search(dropout=..., level_dropout=True)`` and the recompute runs under that search's masks, ``enc_attn.dropout``
+        per encoder level (``ovc_sequence_backward_level_dropout``); with no ``p > 0`` that is the plain meshed call.
+        ``level_dropout=True`` with any other architecture, or with none, is refused by name.
         ``geometric=True``: the object-relation transformer (``ovc_sequence_backward_geometric``), ``boxes`` required; refused
         together with ``dropout``.  ``aoa=True``: the attention-on-attention transformer (``ovc_sequence_backward_aoa``); refused
         together with ``dropout``."""
-        for named in train_arch.named(aoa=aoa, meshed=meshed, geometric=geometric):
-            named.refuse_in_engine("sequence_backward", dropout is not None)
+        archs = train_arch.named(aoa=aoa, meshed=meshed, geometric=geometric)
+        if level_dropout and (len(archs) != 1 or archs[0].beam_level_sequence_form is None):
+            raise native.OvcError("sequence_backward(level_dropout=True): a mask per encoder level is the meshed-memory transformer's "
+                                  "dropout form -- it needs meshed=True and no other architecture's keyword")
+        for named in archs:
+            named.refuse_in_engine("sequence_backward", dropout is not None and not level_dropout)
         arch = train_arch.resolve(meshed, geometric, aoa)
         self._check_trainable(arch)
         table_drop = self._dropout_table(dropout) if dropout is not None else None
@@ -1315,7 +1346,7 @@ class CaptionEngine:
         if not isinstance(grad_logp, torch.Tensor) or tuple(grad_logp.shape) != tuple(ids.shape):
             raise native.OvcError("grad_logp must have the shape of ids {}".format(tuple(ids.shape)))
         form = self._train_form(True, None, table_drop, (B, N, S, T),
-                                () if table_drop is None else (int(beam_size), slots.data_ptr()), arch=arch)
+                                () if table_drop is None else (int(beam_size), slots.data_ptr()), arch=arch, level=bool(level_dropout))
         ids = ids.to(self.device).contiguous()
         grad_logp = grad_logp.to(device=self.device, dtype=torch.float32).contiguous()
         arena, grads, logp = self._run_train_form(form, features, boxes, (ids, grad_logp), (B, S, T) if want_logp else None,

@@ -256,6 +256,17 @@ SIGNATURES = {
     "ovc_sequence_backward_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                               c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                               POINTER(Dropout)]),
+    "ovc_beam_search_level_dropout_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int]),
+    "ovc_beam_search_level_dropout": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, POINTER(Dropout), c_void_p, c_int, c_void_p,
+                                              POINTER(c_int)]),
+    "ovc_level_dropout_beams_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
+    "ovc_sequence_backward_level_dropout": (c_int, [POINTER(Model), POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                    c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                    POINTER(Dropout)]),
+    "ovc_dropout_mask_rows_level": (c_int, [c_void_p, c_int, c_int, c_void_p, c_long, c_long, c_float, c_void_p, c_void_p]),
+    "ovc_debug_add_norm_level_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
+                                                 c_void_p, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ovc_sample_workspace_bytes": (c_size_t, [POINTER(Model), c_int, c_int, c_int, c_int]),
     "ovc_sample": (c_int, [POINTER(Model), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                            c_void_p, c_void_p]),
@@ -425,7 +436,10 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_debug_bw_leaky", "ovc_debug_bw_sum", "ovc_debug_bw_sum_levels", "ovc_debug_bw_accumulate",
                  "ovc_debug_bw_loss_part_floats", "ovc_debug_bw_loss", "ovc_debug_bw_embedding", "ovc_debug_bw_tokens",
                  "ovc_debug_bw_attention",
-                 "ovc_dropout_mask_level", "ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout")
+                 "ovc_dropout_mask_level", "ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout",
+                 "ovc_beam_search_level_dropout_workspace_bytes", "ovc_beam_search_level_dropout",
+                 "ovc_level_dropout_beams_workspace_bytes", "ovc_sequence_backward_level_dropout", "ovc_dropout_mask_rows_level",
+                 "ovc_debug_add_norm_level_dropout")
 
 _lib = None
 

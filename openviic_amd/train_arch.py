@@ -21,6 +21,10 @@ class TrainArch:
     # (sizer, entry point) of the loss form under dropout where the plain loss form takes none: reached through
     # ``dropout=LEVEL_DROPOUT`` -- one module applied once per encoder level, a mask per level (``openviic_amd.dropout``)
     level_dropout_form: tuple = None
+    # the SCST pair under dropout, reached through ``dropout=BEAM_LEVEL_DROPOUT``: (sizer, entry point) of the search and of the
+    # sequence form's recompute -- the level-keyed mask at the search's mask row (``openviic_amd.dropout``)
+    beam_level_search_form: tuple = None
+    beam_level_sequence_form: tuple = None
 
     def keywords(self):
         return {self.key: True}
@@ -28,6 +32,10 @@ class TrainArch:
     def takes_level_dropout(self, dropout):
         """``dropout`` is the level-keyed spelling and this architecture has that form."""
         return self.level_dropout_form is not None and isinstance(dropout, str) and dropout == LEVEL_DROPOUT
+
+    def takes_beam_level_dropout(self, dropout):
+        """``dropout`` is the SCST spelling of the level-keyed form and this architecture has it."""
+        return self.beam_level_search_form is not None and isinstance(dropout, str) and dropout == BEAM_LEVEL_DROPOUT
 
     def refuse_in_engine(self, where, dropout, loss=False, distill=False):
         """What ``forward_backward`` / ``sequence_backward`` (``where``) refuse together with this architecture: the smoothed
@@ -51,6 +59,8 @@ class TrainArch:
 
 
 LEVEL_DROPOUT = "levels"    # ``xe_loss`` / ``xe_step``'s ``dropout`` value that selects an architecture's ``level_dropout_form``
+# ``beam_search`` / ``scst_step``'s ``dropout`` value that selects an architecture's ``beam_level_search_form`` / ``..._sequence_form``
+BEAM_LEVEL_DROPOUT = "beam_levels"
 
 _SEARCH_HAS_ITS_OWN_SCOPE = " -- the search under dropout has its own scope; set DROPOUT: 0 or call model.eval()"
 
@@ -59,9 +69,11 @@ TRAIN_ARCHS = {a.key: a for a in (
               ("ovc_train_meshed_workspace_bytes", "ovc_forward_backward_meshed"),
               ("ovc_train_meshed_beams_workspace_bytes", "ovc_sequence_backward_meshed"), loss_dropout=False,
               dropout_note=" -- the meshed layer applies enc_attn.dropout once per level, with a mask per level: xe_loss / xe_step take "
-                           "dropout=\"levels\" for it, the sequence form and the search have no dropout form; or set DROPOUT: 0 or "
-                           "call model.eval()",
-              level_dropout_form=("ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout")),
+                           "dropout=\"levels\" for it, beam_search / scst_step dropout=\"beam_levels\"; or set DROPOUT: 0 or call "
+                           "model.eval()",
+              level_dropout_form=("ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout"),
+              beam_level_search_form=("ovc_beam_search_level_dropout_workspace_bytes", "ovc_beam_search_level_dropout"),
+              beam_level_sequence_form=("ovc_level_dropout_beams_workspace_bytes", "ovc_sequence_backward_level_dropout")),
     TrainArch("geometric", "the object-relation transformer", "object_relation_transformer",
               ("ovc_train_geometric_workspace_bytes", "ovc_forward_backward_geometric"),
               ("ovc_train_geometric_beams_workspace_bytes", "ovc_sequence_backward_geometric"), loss_dropout=True,

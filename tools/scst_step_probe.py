@@ -168,26 +168,34 @@ def reward_probe(args, model, V, T, N, D, k):
     return results
 
 
-def dropout_probe(args, model, N, D, k):
-    """SCST steps under dropout (p = 0.1 at every site) against the same build at p = 0, alternating."""
+def dropout_probe(args, model, N, D, k, search_kw):
+    """SCST steps under dropout (p = 0.1 at every site) against the same build at p = 0, alternating; ``search_kw``: the search's
+    dropout keywords (``dropout=True``, or the meshed-memory transformer's ``meshed=True, dropout="beam_levels"``).  ``--rounds``
+    runs per batch size, each a result of its own; the mean caption length of each leg's last step is reported with the times (with
+    EOS-biased weights the two legs may run different numbers of decode steps: ``--eos-free`` takes that out of the ratio)."""
     drops = [m for m in model.modules() if isinstance(m, torch.nn.Dropout)]
     results = []
-    for B in args.batches:
+    for B in [b for b in args.batches for _ in range(args.rounds)]:
         items = InstanceList()
         items.region_features = synthetic_features(B, N, D, seed=0, ragged=True).cuda()
         reward = torch.rand(B, k, generator=torch.Generator().manual_seed(1)).cuda()
         runs = {0.0: [], 0.1: []}
+        lengths = {}
         for i in range(args.warmup + args.steps):
             for p in (0.0, 0.1):
                 for m in drops:
                     m.p = p
-                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k, dropout=True))
+                ms_s, (ids, log_probs) = timed(lambda: model.beam_search(items, batch_size=B, beam_size=k, out_size=k, **search_kw))
+                ended = (ids == 2).any(-1)
+                first = torch.where(ended, (ids == 2).int().argmax(-1), torch.full_like(ended, ids.shape[-1] - 1, dtype=torch.long))
+                lengths[p] = (first + 1).float().mean().item()
                 loss = (-torch.mean(log_probs, -1) * (reward - reward.mean(-1, keepdim=True))).mean()
                 model.zero_grad(set_to_none=True)
                 ms_b, _ = timed(loss.backward)
                 if i >= args.warmup:
                     runs[p].append((ms_s, ms_b))
-        r = {"variant": args.variant, "B": B, "k": k, "N": N, "p": 0.1}
+        r = {"variant": args.variant, "B": B, "k": k, "N": N, "p": 0.1, "eos_free_weights": bool(args.eos_free),
+             "mean_caption_length_p0": lengths[0.0], "mean_caption_length_dropout": lengths[0.1]}
         for p, name in ((0.0, "p0"), (0.1, "dropout")):
             r["search_ms_" + name] = spread([a for a, _ in runs[p]])
             r["backward_ms_" + name] = spread([b for _, b in runs[p]])
@@ -308,7 +316,7 @@ def main():
                     help="camo_transformer: the cross-level encoder (1 x 64 encoder heads) and its tail; "
                          "augmented_memory_transformer: the plain encoder with 40 memory slots per layer; "
                          "meshed_memory_transformer: the multilevel encoder and the meshed decoder (meshed=True; search and "
-                         "backward only: --reward none, --optimizer none, no --dropout)")
+                         "backward only: --reward none, --optimizer none; --dropout runs meshed=True, dropout=\"beam_levels\")")
     ap.add_argument("--reward", default="none", choices=["none", "host", "device"],
                     help="none: a fixed random reward (search and backward only); device / host: the CIDEr reward inside the step")
     ap.add_argument("--corpus-images", type=int, default=5000, help="images of the synthetic reward corpus (5 references each)")
@@ -317,7 +325,10 @@ def main():
                     help="none: search and backward only; torch / engine: the whole step with optimizer.step() (they alternate)")
     ap.add_argument("--fused", action="store_true",
                     help="model.scst_step against the lines it stands for, alternating (needs --reward device --optimizer engine)")
-    ap.add_argument("--rounds", type=int, default=2, help="--fused: alternating rounds of --warmup + --steps steps per form")
+    ap.add_argument("--rounds", type=int, default=2,
+                    help="--fused / --dropout: alternating rounds of --warmup + --steps steps per form (--dropout: a result per round)")
+    ap.add_argument("--eos-free", action="store_true",
+                    help="weights without the <eos> bias: every caption runs all T steps, so two legs of a ratio run the same steps")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.fused and (args.reward != "device" or args.optimizer != ["engine"]):
@@ -326,8 +337,8 @@ def main():
         ap.error("--optimizer none stands alone")
     arch = train_arch.of_variant(args.variant)
     meshed = arch.keywords() if arch is not None else {}       # of --variant's choices only the meshed-memory transformer has one
-    if meshed and (args.reward != "none" or args.optimizer != ["none"] or args.dropout or args.fused):
-        ap.error("meshed_memory_transformer goes with --reward none --optimizer none, without --dropout or --fused")
+    if meshed and (args.reward != "none" or args.optimizer != ["none"] or args.fused):
+        ap.error("meshed_memory_transformer goes with --reward none --optimizer none, without --fused")
     assert torch.cuda.is_available(), "needs a HIP device"
     V, T, N, D, k = 10201, 20, 50, 2048, args.beam
     vocab = SyntheticVocab(V, T)
@@ -336,7 +347,9 @@ def main():
     def build():
         model = build_model(cfg, vocab)
         template = model.state_dict()
-        sd = eos_biased_state_dict({**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}, template)
+        sd = {**template, **synthetic_state_dict(template, seed=1234, mode="reference_init")}
+        if not args.eos_free:
+            sd = eos_biased_state_dict(sd, template)
         model.load_state_dict(sd, strict=False)
         model.train()
         for m in model.modules():
@@ -356,7 +369,7 @@ def main():
     if args.fused:
         results = fused_probe(args, build, V, T, N, D, k)
     if args.dropout:
-        results = dropout_probe(args, model, N, D, k)
+        results = dropout_probe(args, model, N, D, k, dict(meshed, dropout=train_arch.BEAM_LEVEL_DROPOUT) if meshed else {"dropout": True})
     if args.optimizer != ["none"] and not args.fused:
         results = optimizer_probe(args, build, N, D, k)
     for B in args.batches if args.reward == "none" and not args.dropout and args.optimizer == ["none"] else []:

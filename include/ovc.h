@@ -1617,6 +1617,126 @@ int ovc_forward_backward_distill(const ovc_model* m, const ovc_model* grads, con
                                  const ovc_dropout* dropout);
 int ovc_ensemble_combine(const float* const* logps, int M, long rows, int V, int renormalise, float* out, ovc_stream stream);
 
+/* Test hooks: the search's bookkeeping kernels on caller-given state (appended to ABI 8; no struct, entry or kernel of the engine
+ * changes), so that everything a step does after it has chosen its k winners, the final orderings and the return_probs outputs can
+ * be compared bit for bit with a host restatement (tests/test_beam_state_gpu.py, tests/beam_state_oracle.py).
+ *
+ * ovc_debug_beam_step: ONE step t of T on the whole state, all of it in caller buffers on the device.  Inputs: row-major logits
+ * [members][B*width][V] (members counts only with OVC_STEP_ENSEMBLE, else one block), running / alive [B*width], hist_in / lp_in /
+ * anc_in [B*width][T] (columns 0..t-1 are read), len_in [B*width] (OVC_STEP_NORMALIZED).  The entry computes every member's block
+ * pieces and lays its logits out transposed, as the vocabulary product leaves them (the two-pass form reads the row-major logits),
+ * and makes the one launch of `form`:
+ *   OVC_STEP_BEST          the plain fused selection, with `gate` (a device int32) its gated kernel
+ *   OVC_STEP_CONSTRAINED   ngram / min_length / banned [n_banned] (HOST)           OVC_STEP_PREFIX   prefix [B][P], prefix_len [B] (HOST)
+ *   OVC_STEP_DIVERSE       groups, diversity                                       OVC_STEP_FORCED   forced [B][C] (HOST), pad
+ *   OVC_STEP_NORMALIZED    inv / bonus [T] (HOST), len_in -> len_out, key_out [B*k]
+ *   OVC_STEP_TWO_PASS      the row pass and the update kernel whatever V is, with `gate` their gated kernels
+ *   OVC_STEP_SAMPLE        seed (a device int64)                                   OVC_STEP_SAMPLE_SHAPED   chosen [B*k] (device int32)
+ *   OVC_STEP_ENSEMBLE      members in 1..OVC_MAX_ENSEMBLE, each with its own word_emb / pos_emb / d_model / next_x
+ * Outputs: hist_out / lp_out / anc_out [B*k][T] (columns 0..t), alive_out / running_out / next_tok [B*k], row_max_out / row_lsum_out
+ * [members][B*width]; with next_x[0] != NULL also next_x[m] [B*k][d_model[m]] = word_emb[m][word] + pos_emb[m][t + 2] and
+ * next_padflag [B*k] = (word == pad); with alive_count != NULL (BEST and TWO_PASS only) alive_count[t] += the beams that go on.
+ * *kernel_out: which kernel was launched, OVC_STEP_KERNEL_* below.  word_rows[m] / pos_rows[m]: the rows of member m's tables.
+ * Refused with OVC_EINVAL and nothing launched: a NULL among the buffers named above, hist_in == hist_out (lp, anc, alive
+ * likewise), T outside 1..OVC_MAX_LEN, t outside 0..T-1, k or width outside 1..OVC_MAX_BEAM, width * V < k, more than 512 blocks of
+ * 32 words, and with next_x: pos_rows[m] < t + 3, word_rows[m] < V, pad outside [0, V), d_model[m] < 4 or not a multiple of 4, a table
+ * or next_x[m] that is not 16-byte aligned; a rule table outside what its search entry accepts; whatever the step's launcher
+ * refuses.  OVC_EWORKSPACE: scratch smaller than ovc_debug_beam_step_bytes or not 16-byte aligned. */
+#define OVC_STEP_BEST          0
+#define OVC_STEP_CONSTRAINED   1
+#define OVC_STEP_PREFIX        2
+#define OVC_STEP_DIVERSE       3
+#define OVC_STEP_FORCED        4
+#define OVC_STEP_NORMALIZED    5
+#define OVC_STEP_TWO_PASS      6
+#define OVC_STEP_SAMPLE        7
+#define OVC_STEP_SAMPLE_SHAPED 8
+#define OVC_STEP_ENSEMBLE      9
+/* beam.hip's kernels that end in beam_follow_winners, in this order from 1: beam_update_kernel, beam_update_kernel_gated,
+ * beam_fused_update_kernel, beam_fused_update_kernel_gated, beam_constrained_update_kernel, beam_prefix_update_kernel,
+ * beam_diverse_update_kernel, beam_forced_update_kernel, beam_normalized_update_kernel, sample_fused_update_kernel,
+ * sample_shaped_update_kernel, then beam_ensemble_update_kernel<1..4> as 12..15. */
+#define OVC_STEP_KERNEL_UPDATE       1
+#define OVC_STEP_KERNEL_ENSEMBLE_1  12
+typedef struct {
+    int32_t form, B, width, V, k, T, t, eos, pad, members;
+    int32_t d_model[OVC_MAX_ENSEMBLE], word_rows[OVC_MAX_ENSEMBLE], pos_rows[OVC_MAX_ENSEMBLE];
+    int32_t ngram, min_length, n_banned, P, groups, C;
+    float diversity;
+    int32_t reserved;
+    const float* logits;
+    const float* running;
+    const float* alive;
+    const int32_t* hist_in;
+    const float* lp_in;
+    const int32_t* anc_in;
+    const int32_t* len_in;
+    const float* word_emb[OVC_MAX_ENSEMBLE];
+    const float* pos_emb[OVC_MAX_ENSEMBLE];
+    const int32_t* gate;
+    const int32_t* banned;
+    const int32_t* prefix;
+    const int32_t* prefix_len;
+    const int32_t* forced;
+    const float* inv;
+    const float* bonus;
+    const int64_t* seed;
+    const int32_t* chosen;
+    int32_t* hist_out;
+    float* lp_out;
+    int32_t* anc_out;
+    float* alive_out;
+    float* running_out;
+    int32_t* next_tok;
+    uint8_t* next_padflag;
+    float* next_x[OVC_MAX_ENSEMBLE];
+    int32_t* alive_count;
+    int32_t* len_out;
+    float* key_out;
+    float* row_max_out;
+    float* row_lsum_out;
+    void* scratch;
+    size_t scratch_bytes;
+} ovc_debug_beam_step_call;
+size_t ovc_debug_beam_step_bytes(const ovc_debug_beam_step_call* call);
+int ovc_debug_beam_step(const ovc_debug_beam_step_call* call, int32_t* kernel_out, ovc_stream stream);
+
+/* ovc_debug_beam_finalize: the final ordering of a search's state in caller buffers (device): running [B*k], hist / lp [B*k][T] ->
+ * ids_out (int64) / logp_out [B][out_size][T], order_out [B][k].  form:
+ *   OVC_FINAL_PLAIN       score descending, the lower slot first among equals; steps_run in 0..T-1 (0: all T ran; else the positions
+ *                         from steps_run on are word 0 / log-prob 0)
+ *   OVC_FINAL_GATED       two states (running / hist / lp and running2 / hist2 / lp2) and alive_count [T]: S = 1 + the first
+ *                         i < T - 1 with alive_count[i] == 0, else T; the state of buffer S & 1 (the first is buffer 0) is ordered
+ *                         as PLAIN with steps_run = S; *steps_out (device) = S
+ *   OVC_FINAL_FORCED      (non-empty, met words descending, score descending, slot ascending); met_out [B][k]
+ *   OVC_FINAL_NORMALIZED  len_in [B*k], inv / bonus [T] (device): (key descending, raw score descending, slot ascending), a NaN key
+ *                         last; score_out / len_out [B][k]
+ * Refused with OVC_EINVAL and nothing launched: B < 1, k outside 1..OVC_MAX_BEAM, out_size outside 1..k, T < 1, steps_run outside
+ * 0..T-1, a NULL among the buffers the form names, an unknown form, what the form's launcher refuses.
+ *
+ * ovc_debug_beam_gather_all: all_out [B][k][T][V] from the steps' rows all_buf (step 0 compact as [B][V], step t >= 1 at
+ * [t][B][k][V]) and order [B][k] (every entry in 0..k-1: the caller's to keep).
+ * ovc_debug_masked_logp: out [rows][V] = mean over the M members of ((x_m - row_max_m) - row_lsum_m), times alive (NULL: 1), a
+ * logit at logits[m][row * ld_row[m] + word * ld_word[m]]; logits / row_max / row_lsum: M device pointers in HOST memory.  ensemble
+ * == 0 (M must be 1): the one-model kernel; else the ensemble kernel's instance for M members.
+ * ovc_debug_block_pieces: row-major x [rows][V] -> stats [rows][stats_ld] float2 (the maximum and sum exp(x - maximum) of every
+ * 32-word block; stats_ld >= ceil(V / 32)) and the transposed logits_t [V][ldt] (ldt >= rows). */
+#define OVC_FINAL_PLAIN      0
+#define OVC_FINAL_GATED      1
+#define OVC_FINAL_FORCED     2
+#define OVC_FINAL_NORMALIZED 3
+int ovc_debug_beam_finalize(int form, const float* running, const int32_t* hist, const float* lp, const float* running2,
+                            const int32_t* hist2, const float* lp2, const int32_t* alive_count, const int32_t* len_in, const float* inv,
+                            const float* bonus, int B, int k, int T, int out_size, int steps_run, int C, int64_t* ids_out,
+                            float* logp_out, int32_t* order_out, int32_t* steps_out, int32_t* met_out, float* score_out,
+                            int32_t* len_out, ovc_stream stream);
+int ovc_debug_beam_gather_all(const float* all_buf, const int32_t* order, int B, int k, int T, int V, float* all_out,
+                              ovc_stream stream);
+int ovc_debug_masked_logp(const float* const* logits, const long* ld_row, const long* ld_word, const float* const* row_max,
+                          const float* const* row_lsum, const float* alive, int M, int ensemble, int rows, int V, float* out,
+                          ovc_stream stream);
+int ovc_debug_block_pieces(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t, ovc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -859,14 +859,21 @@ int ovc_masked_logp_launch(const float* logits, long ld_row, long ld_word, const
     return OVC_OK;
 }
 
+// What every final ordering indexes with: order[kMaxK] lives in LDS and is written at a rank < k and read at o < out_size.
+static bool final_args_ok(const BeamFinalArgs& p, int B) {
+    return B > 0 && p.k >= 1 && p.k <= kMaxK && p.out_size >= 1 && p.out_size <= p.k && p.T >= 1 && p.running && p.hist && p.lp && p.ids_out &&
+           p.logp_out;
+}
+
 int ovc_beam_finalize_launch(const BeamFinalArgs& p, int B, hipStream_t stream) {
+    if (!final_args_ok(p, B) || p.steps_run < 0 || p.steps_run >= p.T) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(64), 0, stream, p);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
 }
 
 int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_out, int B, hipStream_t stream) {
-    if (B <= 0 || !met_out || !p.order_out || !ovc_beam_forced_ok(p.k, C) || p.out_size < 1 || p.out_size > p.k) return OVC_EINVAL;
+    if (!final_args_ok(p, B) || !met_out || !p.order_out || !ovc_beam_forced_ok(p.k, C)) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_finalize_forced_kernel, dim3(B), dim3(64), 0, stream, p, p.k >> C, met_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
@@ -874,9 +881,7 @@ int ovc_beam_finalize_forced_launch(const BeamFinalArgs& p, int C, int32_t* met_
 
 int ovc_beam_finalize_normalized_launch(const BeamFinalArgs& p, const BeamLength& n, float* score_out, int32_t* len_out, int B,
                                         hipStream_t stream) {
-    if (B <= 0 || !n.len_in || !n.inv || !n.bonus || !score_out || !len_out || !p.order_out || p.k < 1 || p.k > kMaxK || p.T < 1 ||
-        p.out_size < 1 || p.out_size > p.k)
-        return OVC_EINVAL;
+    if (!final_args_ok(p, B) || !n.len_in || !n.inv || !n.bonus || !score_out || !len_out || !p.order_out) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_finalize_normalized_kernel, dim3(B), dim3(64), 0, stream, p, n, score_out, len_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
@@ -885,6 +890,7 @@ int ovc_beam_finalize_normalized_launch(const BeamFinalArgs& p, const BeamLength
 int ovc_beam_finalize_gated_launch(const BeamFinalArgs (&buf)[2], const int32_t* alive_count, int32_t* steps_out, int B,
                                    hipStream_t stream) {
     if (B <= 0 || !alive_count || buf[0].T != buf[1].T || buf[0].T < 1) return OVC_EINVAL;
+    if (!final_args_ok(buf[0], B) || !final_args_ok(buf[1], B) || buf[0].k != buf[1].k || buf[0].out_size != buf[1].out_size) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_finalize_gated_kernel, dim3(B), dim3(64), 0, stream, buf[0], buf[1], alive_count, steps_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;
@@ -892,6 +898,7 @@ int ovc_beam_finalize_gated_launch(const BeamFinalArgs (&buf)[2], const int32_t*
 
 int ovc_beam_gather_all_launch(const float* all_buf, const int* order, int B, int k, int T, int V, float* all_out,
                                hipStream_t stream) {
+    if (!all_buf || !order || !all_out || B <= 0 || k < 1 || k > kMaxK || T < 1 || V < 1 || (long)B * k * T > 0x7fffffffL) return OVC_EINVAL;
     hipLaunchKernelGGL(beam_gather_all_kernel, dim3(B * k * T), dim3(256), 0, stream, all_buf, order, B, k, T, V, all_out);
     OVC_RETURN_IF_LAUNCH_FAILED();
     return OVC_OK;

@@ -4203,3 +4203,211 @@ extern "C" int ovc_sequence_backward_level_dropout(const ovc_model* m, const ovc
     return run_train_call(m, grads, c, features, boxes, ids, nullptr, grad_logp, workspace, workspace_bytes, nullptr, logp_out, use_graph,
                           stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Test entries of the search's bookkeeping (include/ovc.h: ovc_debug_beam_step and the entries behind it).  The state is the
+// caller's, whole: nothing of a step or of a final ordering stays inside a scratch.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// The carve of a step call's scratch: per member the transposed logits and the block pieces, the two-pass path's row candidates,
+// the rule's staged tables.  base == nullptr: the size alone.
+struct StepCarve { float* logits_t[OVC_MAX_ENSEMBLE]; float* stats[OVC_MAX_ENSEMBLE]; float* cand_v; int* cand_i; void* tab[2]; size_t bytes; };
+StepCarve carve_step(const ovc_debug_beam_step_call& c, int M, void* base) {
+    const size_t rows = (size_t)c.B * c.width, ldt = (rows + 3) & ~(size_t)3, nblk = ((size_t)c.V + 31) / 32, ld = (nblk + 1) & ~(size_t)1;
+    Bump a{reinterpret_cast<char*>(base), 0};
+    StepCarve s{};
+    for (int i = 0; i < M; ++i) { s.logits_t[i] = a.take<float>((size_t)c.V * ldt); s.stats[i] = a.take<float>(2 * rows * ld); }
+    s.cand_v = a.take<float>(rows * c.k); s.cand_i = a.take<int>(rows * c.k);
+    s.tab[0] = a.take<char>(4 * std::max((size_t)c.B * c.T, (size_t)c.B * OVC_MAX_FORCED) + 4 * (size_t)c.T);
+    s.tab[1] = a.take<char>(4 * ((size_t)c.B + c.T));
+    s.bytes = a.off + 256;
+    return s;
+}
+bool step_call_shape_ok(const ovc_debug_beam_step_call& c) {
+    if (c.form < OVC_STEP_BEST || c.form > OVC_STEP_ENSEMBLE) return false;
+    if (c.B <= 0 || c.width <= 0 || c.width > OVC_MAX_BEAM || c.k <= 0 || c.k > OVC_MAX_BEAM || c.V <= 0 || (c.V + 31) / 32 > kFusedVocabBlocks ||
+        c.T < 1 || c.T > OVC_MAX_LEN || c.t < 0 || c.t >= c.T || (long)c.B * c.width > 65535 || (long)c.width * c.V < c.k)
+        return false;
+    return c.form != OVC_STEP_ENSEMBLE || (c.members >= 1 && c.members <= OVC_MAX_ENSEMBLE);
+}
+}  // namespace
+
+extern "C" size_t ovc_debug_beam_step_bytes(const ovc_debug_beam_step_call* call) {
+    if (!call || !step_call_shape_ok(*call)) return 0;
+    return carve_step(*call, call->form == OVC_STEP_ENSEMBLE ? call->members : 1, nullptr).bytes;
+}
+
+extern "C" int ovc_debug_beam_step(const ovc_debug_beam_step_call* call, int32_t* kernel_out, ovc_stream stream) {
+    if (!call || !kernel_out || !step_call_shape_ok(*call)) return OVC_EINVAL;
+    const ovc_debug_beam_step_call& c = *call;
+    const int B = c.B, V = c.V, T = c.T, M = c.form == OVC_STEP_ENSEMBLE ? c.members : 1, rows = B * c.width, ldt = (rows + 3) & ~3;
+    if (!c.logits || !c.running || !c.alive || !c.hist_in || !c.lp_in || !c.anc_in || !c.hist_out || !c.lp_out || !c.anc_out || !c.alive_out ||
+        !c.running_out || !c.next_tok || !c.row_max_out || !c.row_lsum_out || !c.scratch)
+        return OVC_EINVAL;
+    if (c.hist_in == c.hist_out || c.lp_in == c.lp_out || c.anc_in == c.anc_out || c.alive == c.alive_out || c.running == c.running_out ||
+        (c.len_in && c.len_in == c.len_out))
+        return OVC_EINVAL;
+    const bool next = c.next_x[0] != nullptr;
+    for (int i = 0; i < M && next; ++i) {
+        // the kernel reads row word < V of word_emb and row t + 2 of pos_emb, 16 bytes at a time
+        if (!c.word_emb[i] || !c.pos_emb[i] || !c.next_x[i] || !c.next_padflag || c.d_model[i] < 4 || (c.d_model[i] & 3)) return OVC_EINVAL;
+        if (!ovc_aligned16(c.word_emb[i]) || !ovc_aligned16(c.pos_emb[i]) || !ovc_aligned16(c.next_x[i])) return OVC_EINVAL;
+        if (c.word_rows[i] < V || c.pos_rows[i] < c.t + 3 || c.pad < 0 || c.pad >= V) return OVC_EINVAL;
+    }
+    // the rule's payload, as its search entry takes it
+    FusedSelectOptions opt{};
+    RuleIO io{};
+    int kernel = 0;
+    switch (c.form) {
+    case OVC_STEP_BEST: opt.rule = SelectRule::Best; opt.gate = c.gate; kernel = c.gate ? 4 : 3; break;
+    case OVC_STEP_TWO_PASS: kernel = c.gate ? 2 : 1; break;
+    case OVC_STEP_CONSTRAINED: {
+        SelectRule ignored = SelectRule::Best;
+        if (!constraints_from(c.ngram, c.min_length, c.banned, c.n_banned, &ignored, &opt.cons)) return OVC_EINVAL;
+        if (opt.cons.active() && !ovc_beam_constraints_ok(opt.cons, V, T, c.k, c.eos, -1)) return OVC_EINVAL;
+        opt.rule = SelectRule::Constrained; kernel = 5;
+        break;
+    }
+    case OVC_STEP_PREFIX:
+        if (c.P < 1 || c.P > T - 1 || !c.prefix || !c.prefix_len) return OVC_EINVAL;
+        for (int b = 0; b < B; ++b) {
+            if (c.prefix_len[b] < 0 || c.prefix_len[b] > c.P) return OVC_EINVAL;
+            for (int i = 0; i < c.prefix_len[b]; ++i)
+                if (c.prefix[(size_t)b * c.P + i] < 0 || c.prefix[(size_t)b * c.P + i] >= V) return OVC_EINVAL;
+        }
+        opt.rule = SelectRule::Prefix; opt.prefix.P = c.P; kernel = 6;
+        io.table[0] = {nullptr, c.prefix, sizeof(int32_t) * B * c.P}; io.table[1] = {nullptr, c.prefix_len, sizeof(int32_t) * B}; io.ntable = 2;
+        break;
+    case OVC_STEP_DIVERSE:
+        if (!ovc_beam_diversity_ok(c.k, c.groups, c.diversity)) return OVC_EINVAL;
+        opt.rule = SelectRule::Diverse; opt.groups = c.groups; opt.diversity = c.diversity; kernel = 7;
+        break;
+    case OVC_STEP_FORCED:
+        if (!c.forced || !ovc_beam_forced_ok(c.k, c.C) || c.pad < 0 || c.pad >= V || !forced_words_ok(c.forced, B, c.C, V, {c.pad, -1, c.eos}))
+            return OVC_EINVAL;
+        opt.rule = SelectRule::Forced; opt.forced_C = c.C; opt.pad = c.pad; kernel = 8;
+        io.table[0] = {nullptr, c.forced, sizeof(int32_t) * B * c.C}; io.ntable = 1;
+        break;
+    case OVC_STEP_NORMALIZED:
+        if (!c.len_in || !c.len_out || !c.key_out || !length_tables_ok(c.inv, c.bonus, T)) return OVC_EINVAL;
+        opt.rule = SelectRule::Normalized; kernel = 9;
+        io.table[0] = {nullptr, c.inv, sizeof(float) * T}; io.table[1] = {nullptr, c.bonus, sizeof(float) * T}; io.ntable = 2;
+        break;
+    case OVC_STEP_SAMPLE: if (!c.seed) return OVC_EINVAL; kernel = 10; break;
+    case OVC_STEP_SAMPLE_SHAPED: if (!c.chosen) return OVC_EINVAL; kernel = 11; break;
+    default: kernel = OVC_STEP_KERNEL_ENSEMBLE_1 + M - 1; break;
+    }
+    if (c.gate && c.form != OVC_STEP_BEST && c.form != OVC_STEP_TWO_PASS) return OVC_EINVAL;
+    if (c.alive_count && c.form != OVC_STEP_BEST && c.form != OVC_STEP_TWO_PASS) return OVC_EINVAL;
+    if (c.scratch_bytes < carve_step(c, M, nullptr).bytes || !ovc_aligned16(c.scratch)) return OVC_EWORKSPACE;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    const StepCarve w = carve_step(c, M, c.scratch);
+
+    EnsembleUpdateArgs en{};
+    en.M = M;
+    for (int i = 0; i < M; ++i) {
+        en.tail[i] = ovc_fused_tail(w.stats[i], V, 1, ldt);                  // the engine's layout: logits^T and its pieces
+        en.logits[i] = w.logits_t[i];
+        en.row_max_out[i] = c.row_max_out + (size_t)i * rows; en.row_lsum_out[i] = c.row_lsum_out + (size_t)i * rows;
+        if (next) { en.word_emb[i] = c.word_emb[i]; en.pos_emb[i] = c.pos_emb[i]; en.next_x[i] = c.next_x[i]; en.d_model[i] = c.d_model[i]; }
+        if (c.form != OVC_STEP_TWO_PASS)
+            TRY(ovc_block_pieces_launch(c.logits + (size_t)i * rows * V, rows, V, en.tail[i].stats_ld, ldt, w.stats[i], w.logits_t[i], s));
+    }
+    for (int i = 0; i < io.ntable; ++i) io.table[i].dst = w.tab[i];
+    if (!stage_tables(io, s)) return OVC_ELAUNCH;
+    switch (opt.rule) {
+    case SelectRule::Prefix: opt.prefix.ids = static_cast<int32_t*>(w.tab[0]); opt.prefix.len = static_cast<int32_t*>(w.tab[1]); break;
+    case SelectRule::Forced: opt.forced = static_cast<int32_t*>(w.tab[0]); break;
+    case SelectRule::Normalized:
+        opt.length = BeamLength{c.len_in, c.len_out, static_cast<float*>(w.tab[0]), static_cast<float*>(w.tab[1]), c.key_out};
+        break;
+    default: break;
+    }
+    BeamUpdateArgs& bu = en.p;
+    bu.alive_in = c.alive; bu.alive_out = c.alive_out; bu.running_out = c.running_out;
+    bu.hist_in = c.hist_in; bu.hist_out = c.hist_out; bu.lp_in = c.lp_in; bu.lp_out = c.lp_out; bu.anc_in = c.anc_in; bu.anc_out = c.anc_out;
+    bu.next_tok = c.next_tok;
+    bu.width = c.width; bu.k = c.k; bu.V = V; bu.T = T; bu.t = c.t; bu.eos = c.eos;
+    bu.alive_count = c.alive_count;
+    if (next) {
+        bu.word_emb = c.word_emb[0]; bu.pos_emb = c.pos_emb[0]; bu.next_x = c.next_x[0]; bu.next_padflag = c.next_padflag;
+        bu.d_model = c.d_model[0]; bu.pad = c.pad;
+    }
+    *kernel_out = kernel;
+    if (c.form == OVC_STEP_ENSEMBLE) {
+        en.running_in = c.running;
+        return ovc_beam_ensemble_update_launch(en, B, s);
+    }
+    if (c.form == OVC_STEP_TWO_PASS) {
+        // the row pass over the row-major logits and the update kernel, as the engine's two-pass step issues them
+        BeamSelectArgs bs{};
+        bs.logits = c.logits; bs.ld = V; bs.is_logp = 0;
+        bs.running = c.running; bs.alive = c.alive; bs.width = c.width; bs.V = V; bs.k = c.k;
+        bs.cand_v = w.cand_v; bs.cand_i = w.cand_i;
+        bs.row_max_out = c.row_max_out; bs.row_lsum_out = c.row_lsum_out;
+        bu.cand_v = w.cand_v; bu.cand_i = w.cand_i; bu.logits = c.logits; bu.ld = V;
+        bu.row_max = c.row_max_out; bu.row_lsum = c.row_lsum_out;
+        TRY(ovc_beam_select_launch(bs, B, s, c.gate));
+        return ovc_beam_update_launch(bu, B, s, c.gate);
+    }
+    bu.logits = w.logits_t[0]; bu.ld = (V + 3) & ~3; bu.row_max_out = c.row_max_out; bu.row_lsum_out = c.row_lsum_out;
+    if (c.form == OVC_STEP_SAMPLE) return ovc_sample_fused_update_launch(bu, en.tail[0], c.seed, B, s);
+    if (c.form == OVC_STEP_SAMPLE_SHAPED) return ovc_sample_shaped_update_launch(bu, en.tail[0], c.chosen, B, s);
+    return ovc_beam_fused_select_launch(bu, en.tail[0], c.running, opt, B, s);
+}
+
+extern "C" int ovc_debug_beam_finalize(int form, const float* running, const int32_t* hist, const float* lp, const float* running2,
+                                       const int32_t* hist2, const float* lp2, const int32_t* alive_count, const int32_t* len_in,
+                                       const float* inv, const float* bonus, int B, int k, int T, int out_size, int steps_run, int C,
+                                       int64_t* ids_out, float* logp_out, int32_t* order_out, int32_t* steps_out, int32_t* met_out,
+                                       float* score_out, int32_t* len_out, ovc_stream stream) {
+    if (form < OVC_FINAL_PLAIN || form > OVC_FINAL_NORMALIZED || !order_out || steps_run < 0 || (T >= 1 && steps_run >= T)) return OVC_EINVAL;
+    if ((long)B * k * T > 0x7fffffffL / 8) return OVC_EINVAL;
+    BeamFinalArgs bf{running, hist, lp, k, T, out_size, ids_out, logp_out, order_out, form == OVC_FINAL_PLAIN ? steps_run : 0};
+    if (form == OVC_FINAL_GATED && !steps_out) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    hipStream_t s = ovc_hip_stream(stream);
+    // every other refusal is the launcher's own, taken before anything is launched
+    switch (form) {
+    case OVC_FINAL_PLAIN: return ovc_beam_finalize_launch(bf, B, s);
+    case OVC_FINAL_GATED: {
+        BeamFinalArgs odd = bf;
+        odd.running = running2; odd.hist = hist2; odd.lp = lp2;
+        const BeamFinalArgs buf[2] = {bf, odd};
+        return ovc_beam_finalize_gated_launch(buf, alive_count, steps_out, B, s);
+    }
+    case OVC_FINAL_FORCED: return ovc_beam_finalize_forced_launch(bf, C, met_out, B, s);
+    default: return ovc_beam_finalize_normalized_launch(bf, BeamLength{len_in, nullptr, inv, bonus, nullptr}, score_out, len_out, B, s);
+    }
+}
+
+extern "C" int ovc_debug_beam_gather_all(const float* all_buf, const int32_t* order, int B, int k, int T, int V, float* all_out,
+                                         ovc_stream stream) {
+    TRY(ovc_device_guard());
+    return ovc_beam_gather_all_launch(all_buf, order, B, k, T, V, all_out, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_masked_logp(const float* const* logits, const long* ld_row, const long* ld_word, const float* const* row_max,
+                                     const float* const* row_lsum, const float* alive, int M, int ensemble, int rows, int V, float* out,
+                                     ovc_stream stream) {
+    if (!logits || !ld_row || !ld_word || !row_max || !row_lsum || !out || M < 1 || M > OVC_MAX_ENSEMBLE || (!ensemble && M != 1) || rows <= 0 ||
+        V <= 0)
+        return OVC_EINVAL;
+    EnsembleLogpArgs lg{};
+    lg.M = M; lg.V = V; lg.alive = alive; lg.out = out;
+    for (int i = 0; i < M; ++i) {
+        if (!logits[i] || !row_max[i] || !row_lsum[i] || ld_row[i] <= 0 || ld_word[i] <= 0) return OVC_EINVAL;
+        lg.logits[i] = logits[i]; lg.ld_row[i] = ld_row[i]; lg.ld_word[i] = ld_word[i]; lg.row_max[i] = row_max[i]; lg.row_lsum[i] = row_lsum[i];
+    }
+    TRY(ovc_device_guard());
+    if (ensemble) return ovc_ensemble_masked_logp_launch(lg, rows, ovc_hip_stream(stream));
+    return ovc_masked_logp_launch(logits[0], ld_row[0], ld_word[0], row_max[0], row_lsum[0], alive, rows, V, out, ovc_hip_stream(stream));
+}
+
+extern "C" int ovc_debug_block_pieces(const float* x, int rows, int V, int stats_ld, int ldt, float* stats, float* logits_t,
+                                      ovc_stream stream) {
+    if (!x || !stats || !logits_t || rows <= 0 || rows > 65535 || V <= 0 || stats_ld < (V + 31) / 32 || ldt < rows) return OVC_EINVAL;
+    TRY(ovc_device_guard());
+    return ovc_block_pieces_launch(x, rows, V, stats_ld, ldt, stats, logits_t, ovc_hip_stream(stream));
+}

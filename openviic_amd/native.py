@@ -126,6 +126,27 @@ class GemmCall(ctypes.Structure):
 
 GEMM_PLAIN, GEMM_GATED, GEMM_DROPOUT, GEMM_SCORING, GEMM_PLANES_DIRECT = 0, 1, 2, 3, 4
 
+OVC_MAX_ENSEMBLE = 4
+
+
+class BeamStepCall(ctypes.Structure):
+    """``ovc_debug_beam_step_call``: one step of a search on caller-given state (``include/ovc.h``)."""
+    _fields_ = [(n, c_int32) for n in ("form", "B", "width", "V", "k", "T", "t", "eos", "pad", "members")] + [
+                ("d_model", c_int32 * OVC_MAX_ENSEMBLE), ("word_rows", c_int32 * OVC_MAX_ENSEMBLE), ("pos_rows", c_int32 * OVC_MAX_ENSEMBLE)] + [
+                (n, c_int32) for n in ("ngram", "min_length", "n_banned", "P", "groups", "C")] + [("diversity", c_float), ("reserved", c_int32)] + [
+                (n, c_void_p) for n in ("logits", "running", "alive", "hist_in", "lp_in", "anc_in", "len_in")] + [
+                ("word_emb", c_void_p * OVC_MAX_ENSEMBLE), ("pos_emb", c_void_p * OVC_MAX_ENSEMBLE)] + [
+                (n, c_void_p) for n in ("gate", "banned", "prefix", "prefix_len", "forced", "inv", "bonus", "seed", "chosen", "hist_out",
+                                        "lp_out", "anc_out", "alive_out", "running_out", "next_tok", "next_padflag")] + [
+                ("next_x", c_void_p * OVC_MAX_ENSEMBLE)] + [
+                (n, c_void_p) for n in ("alive_count", "len_out", "key_out", "row_max_out", "row_lsum_out", "scratch")] + [
+                ("scratch_bytes", c_size_t)]
+
+
+(STEP_BEST, STEP_CONSTRAINED, STEP_PREFIX, STEP_DIVERSE, STEP_FORCED, STEP_NORMALIZED, STEP_TWO_PASS, STEP_SAMPLE, STEP_SAMPLE_SHAPED,
+ STEP_ENSEMBLE) = range(10)
+FINAL_PLAIN, FINAL_GATED, FINAL_FORCED, FINAL_NORMALIZED = range(4)
+
 OVC_METRIC_STATS = 12       # int32 per caption in front of the per-reference LCS lengths (include/ovc.h)
 OVC_METRIC_MAX_REFS = 4096
 OVC_SET_STATS = 10          # int32 per caption of ovc_caption_set: correct[4], guess[4], testlen, reflen
@@ -388,6 +409,13 @@ SIGNATURES = {
     "ovc_debug_bw_attention": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_long,
                                        c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
                                        c_void_p, c_long, c_void_p]),
+    "ovc_debug_beam_step_bytes": (c_size_t, [POINTER(BeamStepCall)]),
+    "ovc_debug_beam_step": (c_int, [POINTER(BeamStepCall), POINTER(c_int32), c_void_p]),
+    "ovc_debug_beam_finalize": (c_int, [c_int] + [c_void_p] * 10 + [c_int] * 6 + [c_void_p] * 8),
+    "ovc_debug_beam_gather_all": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ovc_debug_masked_logp": (c_int, [POINTER(c_void_p), POINTER(c_long), POINTER(c_long), POINTER(c_void_p), POINTER(c_void_p), c_void_p,
+                                      c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ovc_debug_block_pieces": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ovc_graph_cache_clear": (c_int, []),
     "ovc_profile_enable": (c_int, [c_int]),
     "ovc_profile_read": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
@@ -439,7 +467,9 @@ APPENDED_ABI8 = ("ovc_dropout_mask_rows", "ovc_beam_search_dropout_workspace_byt
                  "ovc_dropout_mask_level", "ovc_level_dropout_workspace_bytes", "ovc_forward_backward_level_dropout",
                  "ovc_beam_search_level_dropout_workspace_bytes", "ovc_beam_search_level_dropout",
                  "ovc_level_dropout_beams_workspace_bytes", "ovc_sequence_backward_level_dropout", "ovc_dropout_mask_rows_level",
-                 "ovc_debug_add_norm_level_dropout")
+                 "ovc_debug_add_norm_level_dropout",
+                 "ovc_debug_beam_step_bytes", "ovc_debug_beam_step", "ovc_debug_beam_finalize", "ovc_debug_beam_gather_all",
+                 "ovc_debug_masked_logp", "ovc_debug_block_pieces")
 
 _lib = None
 
